@@ -33,6 +33,11 @@ per-env results are all-gathered with RCCL bound directly through ctypes (gym_cl
 Cloths never interact, so there is no other collective.
 
 Prints ONE JSON line on rank 0.
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) measures the headline only: set-up, warm-up, the N timed steps, the line.
+--full adds everything else: the CPU baseline (unless --no-cpu-baseline), the companion records (f64, the other mode, relaxed
+order, tier 2, 1536 / 2048 cloths, 50x50, renderer, demonstration writer; unless --no-extra) and the full records in bench_extra.json.
+--dump-outputs DIR writes the headline path's outputs as DIR/<name>.npy (see dump_arrays).
 """
 import argparse
 import json
@@ -121,6 +126,73 @@ def cpu_baseline(cfg, acts0, states, budget_s=15.0):
             "single_core_samples": singles}
 
 
+class ActionStreams(object):
+    """The bench's per-env action streams: env g draws its actions from RandomState(2000 + g).uniform(-1, 1, size=(n, 4)). Drawn
+    only as far as the launches consume them (numpy draws the same doubles whether a stream is drawn at once or in pieces), so
+    a long run does not hold every action it might have needed."""
+
+    def __init__(self, first, n_envs, n0=64):
+        self.rs = [np.random.RandomState(2000 + first + e) for e in range(n_envs)]
+        self.buf = np.empty((n_envs, 0, 4))
+        self._grow(n0)
+
+    def _grow(self, n):
+        self.buf = np.concatenate([self.buf, np.stack([r.uniform(-1, 1, size=(n, 4)) for r in self.rs])], axis=1)
+
+    def reserve(self, n):
+        """Draw every stream up to n actions now."""
+        if n > self.buf.shape[1]:
+            self._grow(n - self.buf.shape[1])
+
+    def table(self, cnt, n_slots):
+        """[n_slots, n_envs, 4]: every env's next n_slots actions, from its counter cnt[e] on."""
+        need = int(np.max(cnt)) + n_slots
+        if need > self.buf.shape[1]:
+            self._grow(max(need - self.buf.shape[1], self.buf.shape[1]))
+        idx = np.asarray(cnt, dtype=np.int64)[None, :] + np.arange(n_slots)[:, None]
+        return self.buf[np.arange(len(self.rs))[None, :], idx]
+
+
+DUMP_MAX_BYTES = 64 * 10 ** 6
+
+
+def dump_arrays(dirname, arrays, n_envs):
+    """--dump-outputs: arrays = {name: (array, env axis)} -> dirname/<name>.npy, float32 where the path computed float32, float64
+    otherwise (counts and flags included), plus env_index.npy: the envs the files hold -- all of them, or, when that would exceed
+    DUMP_MAX_BYTES, a fixed seeded sample of them."""
+    arrs = {}
+    for name, (a, ax) in arrays.items():
+        a = np.asarray(a)
+        arrs[name] = (a.astype(np.float32 if a.dtype == np.float32 else np.float64), ax)
+    data = sum(a.nbytes for a, _ in arrs.values()) + 8 * n_envs
+    room = DUMP_MAX_BYTES - 1024 * (len(arrs) + 1)                # (.npy headers)
+    keep = np.arange(n_envs)
+    if data > room:
+        keep = np.sort(np.random.RandomState(0).choice(n_envs, max(1, n_envs * room // data), replace=False))
+    os.makedirs(dirname, exist_ok=True)
+    for name, (a, ax) in arrs.items():
+        np.save(os.path.join(dirname, name + ".npy"), a if len(keep) == n_envs else np.take(a, keep, axis=ax))
+    np.save(os.path.join(dirname, "env_index.npy"), keep.astype(np.float64))
+
+
+def fused_dump(cfg, E, g0, device, precision, relaxed, n_actions, max_resets):
+    """The outputs of one timed launch of the fused path, reproducibly. The timed launches are time slices bounded by the device
+    clock, so how many actions an env completes in one of them varies from run to run; this runs the same call (ClothVecEnv.step_many,
+    same kernel) once more on a handle of its own, from the seeded start of the timed run (reset draws RandomState(1000+g)), over every
+    env's first `n_actions` actions of its stream, without the time bound. Returns {name: (array, env axis)} for dump_arrays."""
+    from gym_cloth_amd.envs import ClothVecEnv
+    env = ClothVecEnv(cfg, n_envs=E, device=device, precision=precision, consume_domrand_draws=False)
+    if relaxed:
+        env.batch.set_relaxed_order(True)
+    for e in range(E):
+        env.np_randoms[e] = np.random.RandomState(1000 + g0 + e)
+    env.reset()
+    acts = np.ascontiguousarray(ActionStreams(g0, E).table(np.zeros(E, dtype=np.int64), n_actions))
+    out = env.step_many(acts, auto_reset=True, max_resets=max_resets if max_resets > 0 else min(n_actions, 250))
+    env.close()
+    return {k: (v, 0 if (k in ("obs", "op_substeps") or k.startswith("tail_")) else 1) for k, v in out.items() if k != "op_ticks"}
+
+
 TRAFFIC_FILES = ("r06_traffic.json", "r05_traffic.json", "r04_traffic.json", "r03_traffic.json")       # the newest committed PMC record wins
 
 
@@ -149,16 +221,18 @@ def load_traffic(mode, E, n_side, precision, init, substeps_per_launch, b_alg=No
 
 
 def run_workload(n_side, E, precision, init, mode, steps, warmup, fuse_max, rank, world, local_rank, thickness=None,
-                 want_cpu=False, step_ms=170.0, slots=0, max_resets=0, allow_tcp_fallback=False, relaxed=False):
+                 want_cpu=False, step_ms=170.0, slots=0, max_resets=0, allow_tcp_fallback=False, relaxed=False, dump_dir=None):
     """One bench configuration on this rank's GPU; returns the result record (rank 0) or None.
     relaxed=True: the relaxed-order companion kernel (self-collision in Jacobi order, strain limit in coloured order: NOT the
-    reference's trajectories, no parity claim) -- what the exact order costs, as a measured figure. Never `value`."""
+    reference's trajectories, no parity claim) -- what the exact order costs, as a measured figure. Never `value`.
+    dump_dir: rank 0 writes its envs' outputs of the last timed step there (step mode), or of one launch of the timed path run
+    reproducibly (fused mode, fused_dump), after the timed region."""
     return _run_workload(n_side, E, precision, init, mode, steps, warmup, fuse_max, rank, world, local_rank, thickness, want_cpu,
-                         step_ms, slots, max_resets, allow_tcp_fallback, relaxed)
+                         step_ms, slots, max_resets, allow_tcp_fallback, relaxed, dump_dir)
 
 
 def _run_workload(n_side, E, precision, init, mode, steps, warmup, fuse_max, rank, world, local_rank, thickness, want_cpu,
-                  step_ms, slots, max_resets, allow_tcp_fallback, relaxed):
+                  step_ms, slots, max_resets, allow_tcp_fallback, relaxed, dump_dir):
     from gym_cloth_amd.dist import LocalTransport, RcclTransport, SocketTransport, StepExchange
     from gym_cloth_amd.envs import ClothVecEnv
     thickness = thickness if thickness is not None else (0.02 if n_side <= 25 else 0.0095)
@@ -197,7 +271,7 @@ def _run_workload(n_side, E, precision, init, mode, steps, warmup, fuse_max, ran
     P = env.P
     fuse = 1
     if mode == "fused":
-        fuse = max(1, min(fuse_max, steps))              # nominal steps per launch: the timed region is steps // fuse launches
+        fuse = max(1, min(fuse_max, steps))              # nominal steps per launch: the timed region is ceil(steps / fuse) launches
         if not env.batch.fused_supported:                    # grid too large for the in-kernel metrics: report the step mode
             if rank == 0:
                 print("bench: fused mode unavailable for %dx%d; using step mode" % (n_side, n_side), file=sys.stderr)
@@ -221,6 +295,7 @@ def _run_workload(n_side, E, precision, init, mode, steps, warmup, fuse_max, ran
     t_timed = 0.0
     slice_ms = fuse * step_ms
     calib = None
+    dumped = None
     if mode == "step":
         auto_reset_host = init in ("tier1", "tier2", "tier3")
         for t in range(total):
@@ -238,6 +313,8 @@ def _run_workload(n_side, E, precision, init, mode, steps, warmup, fuse_max, ran
                 s = int(env.last_executed.sum())
                 stat["sub"] += s; stat["act_sub"] += s; stat["kms"] += env.batch.last_kernel_ms; stat["launches"] += 1
                 stat["ran"] += E; stat["grabbed"] += int((info["n_grabbed"] > 0).sum()); stat["slots"] += E
+            if dump_dir and rank == 0 and t == total - 1:    # what the last timed step returned (before the host resets)
+                dumped = {k: (np.array(v), 0) for k, v in dict(info, obs=obs, rew=rew, done=done).items()}
             if auto_reset_host and done.any():               # the reference's episode loop; clock stopped
                 stat["resets"] += int(done.sum()) if t >= warmup else 0
                 env.reset(mask=done)
@@ -245,16 +322,16 @@ def _run_workload(n_side, E, precision, init, mode, steps, warmup, fuse_max, ran
         # every env consumes ITS OWN action stream (RandomState(2000+e)) at its own pace: per launch rank 0 builds the table
         # of each env's next `slots` actions from the per-env counters, broadcasts it, and gets the consumed counts back.
         # The launches are time slices of fuse x (duration of one env step). That duration is MEASURED here, outside the timed
-        # region: a short calibration launch, then the warm-up launches (each refines it); the timed launches all get the same slice,
-        # so that the timed region covers `--steps` env steps per env whatever kernel is being measured.
-        n_warm, n_timed = (warmup + fuse - 1) // fuse, max(1, steps // fuse)
+        # region: a short calibration launch, then the warm-up launches (each refines it); the timed launches all get the same slice
+        # (the last one the remainder when fuse does not divide --steps), so that the timed region covers `--steps` env steps per env
+        # whatever kernel is being measured.
+        n_warm, n_timed = (warmup + fuse - 1) // fuse, max(1, (steps + fuse - 1) // fuse)
         est_ms = float(step_ms)                              # the caller's hint, replaced by measurements below
         cal_steps = 2.0
         mk_slots = lambda ms: slots0 if slots0 > 0 else max(4 * fuse, int(ms / 40.0), 8)   # a missed grab costs no time: be generous
         max_slots = mk_slots(16.0 * fuse * est_ms)
-        n_stream = total + max_slots * (n_warm + n_timed + 2) * 4
         if rank == 0:
-            streams = np.stack([np.random.RandomState(2000 + e).uniform(-1, 1, size=(n_stream, 4)) for e in range(world * E)])
+            streams = ActionStreams(0, world * E)
             cnt = np.zeros(world * E, dtype=np.int64)
         device_xch = world > 1 and hasattr(transport, "broadcast_device")
         op_ticks = np.zeros(4)
@@ -263,8 +340,7 @@ def _run_workload(n_side, E, precision, init, mode, steps, warmup, fuse_max, ran
         def launch(ms, n_slots):
             tbl = None
             if rank == 0:
-                idx = (cnt[None, :] + np.arange(n_slots)[:, None]) % n_stream
-                tbl = streams[np.arange(world * E)[None, :], idx]                     # [slots, world*E, 4]
+                tbl = streams.table(cnt, n_slots)                                      # [slots, world*E, 4]
                 tbl = np.ascontiguousarray(tbl.reshape(n_slots, world, E, 4).transpose(1, 0, 2, 3))   # rank-major blocks
             # RCCL: the table is broadcast in place in device memory and the launch reads this rank's block there
             return xch.broadcast_action_blocks(tbl, n_slots, env.batch if device_xch else None)
@@ -296,14 +372,17 @@ def _run_workload(n_side, E, precision, init, mode, steps, warmup, fuse_max, ran
             if w <= n_warm:
                 slice_ms = fuse * est_ms                     # (fixed from the first timed launch on)
                 slots = min(mk_slots(slice_ms), max_slots)
-            blk, d_blk = launch(slice_ms, slots)
+            ms = slice_ms * (steps % fuse) / fuse if (w == n_warm + n_timed - 1 and steps % fuse) else slice_ms
+            if w == n_warm and rank == 0:                    # draw what the timed launches can consume before the clock starts
+                streams.reserve(int(cnt.max()) + (n_timed + 1) * slots)
+            blk, d_blk = launch(ms, slots)
             if w == n_warm:
                 if want_cpu and rank == 0:
                     cpu_states = env.batch.get_state(0, min(E, 512))
                     cpu_acts = blk[0][:min(E, 512)].copy() if blk is not None else None
                 fence()
                 t0 = time.perf_counter()
-            out, res, n_ran = run(blk, d_blk, slice_ms, slots)
+            out, res, n_ran = run(blk, d_blk, ms, slots)
             if w < n_warm:
                 e2 = refine(slice_ms, res)
                 if e2 is not None:
@@ -430,6 +509,10 @@ def _run_workload(n_side, E, precision, init, mode, steps, warmup, fuse_max, ran
     xch.barrier()
     xch.t.close()
     env.close()
+    if dump_dir and rank == 0:
+        if dumped is None:
+            dumped = fused_dump(cfg, E, g0, local_rank, precision, relaxed, fuse, max_resets)
+        dump_arrays(dump_dir, dumped, E)
     return rec
 
 
@@ -625,7 +708,16 @@ def main():
                     help="multi-GPU: run the exchange over TCP sockets if RCCL cannot be initialised (default: fail)")
     ap.add_argument("--dry-run", action="store_true", help="no GPU: exercise launcher, rendezvous and exchange plumbing only")
     ap.add_argument("--no-extra", action="store_true", help="skip the companion records (f64, step mode, tier-2, 50x50, 2048 cloths)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the CPU baseline, the companion records and bench_extra.json (a plain run measures the "
+                         "headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the headline path's outputs (rank 0's envs) as DIR/<name>.npy, float32 / float64, "
+                         "at most 64 MB in all: step mode, the last timed step's; fused mode, one launch of the same call run reproducibly "
+                         "(bench.fused_dump)")
     args = ap.parse_args()
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
 
     if args.step_ms is None:
         args.step_ms = STEP_MS_HINT * (args.n_side / 25.0) ** 2 * (1.8 if args.precision == "f64" else 1.0) * max(1.0, args.envs / 1024.0)
@@ -640,10 +732,10 @@ def main():
 
     head = run_workload(args.n_side, args.envs, args.precision, args.init, args.mode, args.steps, args.warmup, args.fuse,
                         rank, world, local_rank, thickness=args.thickness,
-                        want_cpu=(world == 1 and not args.no_cpu_baseline), step_ms=args.step_ms, slots=args.slots,
-                        allow_tcp_fallback=args.allow_tcp_fallback)
+                        want_cpu=(world == 1 and args.full and not args.no_cpu_baseline), step_ms=args.step_ms, slots=args.slots,
+                        allow_tcp_fallback=args.allow_tcp_fallback, dump_dir=args.dump_outputs)
     extra = []
-    if world == 1 and not args.no_extra:
+    if world == 1 and args.full and not args.no_extra:
         def companion(key, label, **kw):
             t0 = time.perf_counter()
             try:
@@ -699,7 +791,8 @@ def main():
         out = compact_line(args, world, head, extra)
         line = json.dumps(out, separators=(",", ":"))
         assert len(line) <= MAX_LINE_BYTES, len(line)      # the driver parses ONE short line; everything else is in the side file
-        write_extra(head, extra, out)
+        if args.full:
+            write_extra(head, extra, out)
         print(line)
 
 
@@ -758,6 +851,8 @@ def compact_line(args, world, head, extra):
         out["cpu_baseline"] = {k: b[k] for k in ("value", "unit", "cores", "kind", "sample", "single_core_value") if k in b}
     elif world > 1:
         out["cpu_baseline"] = "skipped (world > 1: the CPU port is timed by the 1-GPU run only)"
+    elif not args.full:
+        out["cpu_baseline"] = "skipped (plain run: bench.py --full times the CPU port)"
     by_key = {r_.get("key"): r_ for r_ in extra}
     for key in ("f64", "f32", "relaxed_order", "step_mode", "fused_mode", "tier2_512", "e1536", "e2048", "configs4_50x50"):
         if key in by_key:

@@ -1,11 +1,13 @@
 """The driver's contract with bench.py, checked on a small batch: ONE JSON line with the keys the task names, `value` on SURVEY 8d's
 definition (the actions' update() calls over the actions' share of the timed wall time), the roofline and CPU-baseline objects, and the
-relaxed-order companion labelled as what it is."""
+relaxed-order companion labelled as what it is. A plain run measures the headline only; --full adds the CPU baseline and the companions;
+--dump-outputs writes the same outputs on every run."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -27,13 +29,13 @@ CONTRACT_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per
 
 
 def test_default_command_prints_one_short_parsable_line():
-    """The command the driver runs -- `python bench.py --gpus 1 --steps 20 --warmup 5`, companions ON -- prints exactly one stdout line of at
-    most 4 KB that json.loads accepts, with `roofline` and `cpu_baseline` on it and one-line summaries of the companions; the full records go
-    to bench_extra.json."""
+    """The driver's command with everything on -- `python bench.py --gpus 1 --steps 20 --warmup 5 --full`, companions ON -- prints exactly one
+    stdout line of at most 4 KB that json.loads accepts, with `roofline` and `cpu_baseline` on it and one-line summaries of the companions; the
+    full records go to bench_extra.json."""
     side = os.path.join(ROOT, "bench_extra.json")
     if os.path.exists(side):
         os.remove(side)
-    d = _bench("--gpus", "1", "--steps", "20", "--warmup", "5")
+    d = _bench("--gpus", "1", "--steps", "20", "--warmup", "5", "--full")
     for k in CONTRACT_KEYS:
         assert k in d, k
     assert d["steps"] == 20 and d["warmup"] == 5 and d["n_gpus"] == 1
@@ -57,7 +59,7 @@ def test_default_command_prints_one_short_parsable_line():
 
 
 def test_bench_line_contract_small_batch():
-    d = _bench("--envs", "64", "--steps", "4", "--warmup", "2", "--fuse", "2", "--no-extra")
+    d = _bench("--envs", "64", "--steps", "4", "--warmup", "2", "--fuse", "2", "--no-extra", "--full")
     for k in CONTRACT_KEYS:
         assert k in d, k
     assert d["n_gpus"] == 1 and d["steps"] == 4 and d["warmup"] == 2 and d["higher_is_better"] is True and d["scaling"] == "weak"
@@ -89,3 +91,36 @@ def test_relaxed_companion_is_labelled(monkeypatch):
     # per handle (ABI 7): a handle created next to it in the same process steps in the reference's order
     rec2 = bench.run_workload(25, 64, "f32", "tier1", "fused", 4, 2, 2, 0, 1, 0, step_ms=40.0)
     assert rec2["config"]["exact_order"] is True and "true,1,N25>" in rec2["config"]["variant"]
+
+
+def test_plain_run_is_the_headline_only_and_dumps_the_same_outputs_every_run(tmp_path):
+    """`bench.py --gpus 1 --steps N --warmup W` without --full: the contract keys, no CPU port timed, no companion, no side file; --steps
+    launches that do not divide by --fuse still cover N steps (the last slice is the remainder); --dump-outputs writes float32 / float64
+    .npy files, at most 64 MB, identical from run to run."""
+    side = os.path.join(ROOT, "bench_extra.json")
+    before = os.path.getmtime(side) if os.path.exists(side) else None
+    runs = []
+    for k in range(2):
+        out = tmp_path / ("run%d" % k)
+        d = _bench("--gpus", "1", "--envs", "64", "--steps", "5", "--warmup", "2", "--fuse", "2", "--dump-outputs", str(out))
+        runs.append((d, out))
+    d = runs[0][0]
+    for k in CONTRACT_KEYS:
+        assert k in d, k
+    assert d["steps"] == 5 and d["warmup"] == 2 and d["ms_per_step"] > 0 and d["value"] > 0 and d["dtype"] == "f32"
+    assert d["cpu_baseline"].startswith("skipped") and "extra_file" not in d
+    assert not any(k in d for k in ("f64", "relaxed_order", "step_mode", "tier2_512", "e1536", "e2048", "configs4_50x50", "render", "demos"))
+    assert (os.path.getmtime(side) if os.path.exists(side) else None) == before
+    assert d["config"]["launches"] == 3 and d["roofline"]["launches"] == 3            # 2 + 2 + 1 steps
+    assert abs(d["ms_per_step"] * d["config"]["steps_equivalent"] - 1e3 * d["config"]["timed_region_s"] * d["config"]["action_time_frac"]) <= 1e-1
+    files = sorted(os.listdir(str(runs[0][1])))
+    assert files == sorted(os.listdir(str(runs[1][1]))) and {"obs.npy", "rew.npy", "done.npy", "env_index.npy"} <= set(files)
+    total = 0
+    for f in files:
+        a, b = np.load(str(runs[0][1] / f)), np.load(str(runs[1][1] / f))
+        assert a.dtype in (np.float32, np.float64) and a.dtype == b.dtype and np.array_equal(a, b), f
+        total += os.path.getsize(str(runs[0][1] / f))
+    assert total <= 64 * 10 ** 6
+    obs, rew, executed = (np.load(str(runs[0][1] / f)) for f in ("obs.npy", "rew.npy", "executed.npy"))
+    assert obs.shape == (64, 3 * 625) and np.isfinite(obs).all()
+    assert rew.shape == (2, 64) and executed.sum() > 0                                  # one launch of --fuse actions per env

@@ -11,8 +11,8 @@ HEAD="--no-extra --no-cpu-baseline"        # the headline configuration only (51
 # STAGES="bench trace traffic writerep l2 sq sq2 phases census action large n50 ablation" selects stages (default: all)
 want() { [[ -z "${STAGES:-}" || " $STAGES " == *" $1 "* ]]; }
 if want bench; then
-# 0. the full default bench line (what the driver runs), untraced
-$T python3 bench.py > "$OUT/bench.json" 2> "$OUT/bench.log"
+# 0. the full bench line (--full: headline, CPU baseline, companions), untraced
+$T python3 bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.log"
 fi
 if want trace; then
 # 1. kernel trace + stats of the headline bench command

@@ -3,7 +3,7 @@
 out=gpurun_out/${1:-bench}; shift
 mkdir -p $out
 t0=$(date +%s)
-python3 bench.py "$@" > $out/bench.json 2> $out/bench.err
+python3 bench.py --full "$@" > $out/bench.json 2> $out/bench.err
 echo "bench rc=$? wall=$(( $(date +%s) - t0 )) s"; tail -3 $out/bench.err
 python3 - $out/bench.json <<'PY'
 import json, sys
