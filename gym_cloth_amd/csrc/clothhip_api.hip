@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -46,6 +47,36 @@ static inline int metrics_scratch_bytes(int NS, int NH, int tsz, bool hull_idx =
     return hull_idx ? 2 * NS * tsz + 64 * 8 + ((2 * NH + 15) / 16) * 16 : 2 * NS * tsz + (2 * NH + 64) * 8;
 }
 
+// Every CLOTHHIP_DEBUG_* switch, read here and nowhere else. The planning switches are read when a handle is created
+// (clothhip_create, clothhip_selftest_layout) and kept on it; NOSPEC and ONE_LAUNCH are read again at every launch.
+struct DebugKnobs {
+    bool w8_off = false;         // W8=0: the four-wave standard builds of the 25x25 class (only the value 0 switches)
+    bool nt1024 = false;         // NT1024 (set at all): 1024 x 3 instead of 512 x 5 for the grids of 769 .. 2 560 points
+    int tab_lds = INT_MAX;       // TAB_LDS: caps the window-table mode
+    bool rest_reg = true;        // REST_REG=0: no rest lengths in registers
+    bool cell_copy = true;       // CELL_COPY=0: no cell-ordered record copy (the switch can only turn it off)
+    bool lean_set = false;       // LEAN: 0 never the LEAN arithmetic, 8 (or 2) its eight-wave build, 3 (or 1) / 4 / 5 / 6 its build for that
+    int lean = 0;                //   many cloths per CU; any value also keeps clothhip_create from lowering the residency after its occupancy query
+    bool large2_set = false, large2 = false;   // LARGE2: 0 / 1 one / two large-grid cloths per CU
+    int phase_mask = 15;         // PHASES: phase ablation mask
+    bool nospec = false;         // NOSPEC (nonzero): the generic build instead of the grid-specialised one
+    bool one_launch = false;     // ONE_LAUNCH (set at all): a time-sliced episode launch as one dispatch, not one per generation
+};
+static DebugKnobs read_debug_knobs() {
+    DebugKnobs k;
+    if (const char *t = getenv("CLOTHHIP_DEBUG_W8")) k.w8_off = atoi(t) == 0;
+    k.nt1024 = getenv("CLOTHHIP_DEBUG_NT1024") != nullptr;
+    if (const char *t = getenv("CLOTHHIP_DEBUG_TAB_LDS")) k.tab_lds = atoi(t);
+    if (const char *t = getenv("CLOTHHIP_DEBUG_REST_REG")) k.rest_reg = atoi(t) != 0;
+    if (const char *t = getenv("CLOTHHIP_DEBUG_CELL_COPY")) k.cell_copy = atoi(t) != 0;
+    if (const char *t = getenv("CLOTHHIP_DEBUG_LEAN")) { k.lean_set = true; k.lean = atoi(t); }
+    if (const char *t = getenv("CLOTHHIP_DEBUG_LARGE2")) { k.large2_set = true; k.large2 = atoi(t) != 0; }
+    if (const char *t = getenv("CLOTHHIP_DEBUG_PHASES")) k.phase_mask = atoi(t);
+    if (const char *t = getenv("CLOTHHIP_DEBUG_NOSPEC")) k.nospec = atoi(t) != 0;
+    k.one_launch = getenv("CLOTHHIP_DEBUG_ONE_LAUNCH") != nullptr;
+    return k;
+}
+
 struct clothhip_handle {
     ClothParams prm{};
     int E = 0, N = 0, P = 0, Ppad = 0, S = 0, Spad = 0, precision = 0, device = 0;
@@ -61,10 +92,7 @@ struct clothhip_handle {
     ClothSchedule *d_sched = nullptr, *h_sched = nullptr;   // h_sched: pinned staging
     uint32_t *d_gather = nullptr, *d_wt_ent = nullptr;
     unsigned long long *d_wt_dep = nullptr;
-    int cell_copy = 0;
-    int HT = 0, ht_bits = 0, lds_bytes = 0, phase_mask = 15, nt = 256, ppt = 3;
-    int tab = 0;            // the strain sweep's window table (+ rest lengths) resident in LDS: 0 no (streamed from L2), 1 yes
-    bool rest_reg = false;
+    DebugKnobs dbg;
     // LEAN stepper (fp32, n_side <= 27, batches of >= 1024 cloths): 168 VGPRs and 33 KB of LDS per cloth -> three cloths per CU.
     // It needs ONE shared rest table whose fp32 values are one per spring type (checked on the device's table whenever that table
     // may have changed) and the regular gather stencil (checked once); otherwise the (0, false) variant runs on the same layout.
@@ -80,8 +108,10 @@ struct clothhip_handle {
     int32_t last_variant[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // what the last launch ran (clothhip_last_variant)
     bool have_variant = false;
     int n_cus = 0;
-    // (scratch_have / scratch_need: the LDS behind the hash table that the in-kernel metrics of the episode launches borrow, and what they need)
-    struct Layout { int nt, ppt, tab; bool rest_reg; int cell_copy; int lds_bytes; int HT, ht_bits; int scratch_have, scratch_need; } lay_std = {256, 3, 0, false, 0, 0, 0, 0, 0, 0}, lay_lean = {256, 3, 0, true, 0, 0, 0, 0, 0, 0};
+    // the two layouts a handle may run (plan_layouts) and which one runs now (lean_refresh)
+    Layout lay_std = {256, 3, 0, false, 0, 0, 0, 0, 0, 0}, lay_lean = {256, 3, 0, true, 0, 0, 0, 0, 0, 0};
+    bool on_lean = false;
+    const Layout &lay() const { return on_lean ? lay_lean : lay_std; }
     struct OccKey { const void *fn; int lds; int occ; } occ_cache[8] = {};   // hipOccupancyMaxActiveBlocksPerMultiprocessor per (kernel, LDS bytes)
     double *d_levels = nullptr, *d_xy = nullptr, *d_radius = nullptr, *d_cov = nullptr, *d_vinv = nullptr;
     uint8_t *d_oob = nullptr;
@@ -215,13 +245,12 @@ static void free_handle(clothhip_handle *h) {
     delete h;
 }
 
-static const void *stepper_fn(const clothhip_handle *h, int fused);
-static int spec_ns(const clothhip_handle *h, bool with_palette = true);
+static int spec_ns(const clothhip_handle *h, const Layout &L, bool with_palette = true);
 
 // The LDS a layout leaves the in-kernel metrics (from the hash table to the end of the allocation) against what they need; the
 // allocation is padded behind the layout's end when that fits the budget (the kernel addresses LDS by the layout's offsets: bytes
 // behind `total` are free). False: the episode launches cannot run on this layout.
-static bool fit_scratch(clothhip_handle::Layout &L, int tsz, int Ppad, int Spad, int P, int budget) {
+static bool fit_scratch(Layout &L, int tsz, int Ppad, int Spad, int P, int budget) {
     int NS = 1; while (NS < P) NS <<= 1;
     const int lst = (tsz == 8 && v_lean(L.tab, L.rest_reg, tsz)) ? 1 : 0;
     const LdsLayout lay(tsz, Ppad, Spad, L.HT, L.tab == 2 ? 2 : (v_ldstab(L.tab) ? 1 : 0), L.cell_copy, lst);
@@ -238,146 +267,132 @@ static constexpr int LDS_GRANULE = 1280;
 static constexpr int lds_budget(int r) { return (128 / (r < 1 ? 1 : r)) * LDS_GRANULE; }
 static_assert(lds_budget(1) == 160 * 1024 && lds_budget(2) == 80 * 1024 && lds_budget(4) == 40 * 1024, "granule arithmetic");
 
-// Which stepper variant and which LDS layout a handle runs: pure host logic (no HIP call), so that the CPU test suite can sweep it
-// over grid sizes and precisions (clothhip_selftest_layout). Fills nt / ppt / HT / tab / rest_reg / cell_copy / lds_bytes, the
-// standard layout lay_std and, where the LEAN arithmetic applies, lay_lean + lean_r.
+// A layout of variant (nt, ppt, tab, rest_reg) with a hash table of HT (a power of two) slots: the cell-ordered record copy for the collision
+// pre-check is taken only if the layout with it fits `budget` (and CLOTHHIP_DEBUG_CELL_COPY allows it). The scratch of the in-kernel
+// metrics is the caller's (fit_scratch).
+static Layout make_layout(const clothhip_handle *h, int nt, int ppt, int tab, bool rest_reg, int HT, int budget) {
+    const int tsz = (int)h->tsz, ltab = tab == 2 ? 2 : (v_ldstab(tab) ? 1 : 0), lst = (tsz == 8 && v_lean(tab, rest_reg, tsz)) ? 1 : 0;
+    const int cc = h->dbg.cell_copy && LdsLayout(tsz, h->Ppad, h->Spad, HT, ltab, 1, lst).total <= budget ? 1 : 0;
+    int ht_bits = 0;
+    while ((1 << ht_bits) < HT) ht_bits++;
+    return {nt, ppt, tab, rest_reg, cc, LdsLayout(tsz, h->Ppad, h->Spad, HT, ltab, cc, lst).total, HT, ht_bits, 0, 0};
+}
+
+// Which stepper variants and which LDS layouts a handle runs: pure host logic (no HIP call), so that the CPU test suite can sweep it
+// over grid sizes and precisions (clothhip_selftest_layout). Fills the standard layout lay_std and, where the LEAN arithmetic applies,
+// lay_lean, lean and lean_r.
 // max_r: the highest residency the pick may choose (clothhip_create lowers it when the device's occupancy query grants the chosen LEAN
 // build fewer workgroups per CU than it was planned for).
 static void plan_layouts(clothhip_handle *h, int cus, const std::vector<uint32_t> &gather, int max_r = 6) {
+    const DebugKnobs &dbg = h->dbg;
+    const int tsz = (int)h->tsz, precision = h->precision;
     // threads per cloth x particles per thread (compile-time variants of the stepper)
     // P <= 768 (the 25x25 class, two cloths per CU): EIGHT waves per cloth -- 512 threads x 2 particles, compiled for 128 VGPRs: the cell
     // sweeps have eight ticket takers and the parallel phases two waves per SIMD to hide their LDS latency (+4 % fp32 standard
     // arithmetic, +9 % fp64, +13 % tier 2 over the four-wave 256 x 3 variants, bit-identical; CLOTHHIP_DEBUG_W8=0 selects those)
     const bool small_grid = h->P <= 768;
-    const bool w8 = !(getenv("CLOTHHIP_DEBUG_W8") && atoi(getenv("CLOTHHIP_DEBUG_W8")) == 0);
-    if (small_grid) { h->nt = w8 ? 512 : 256; h->ppt = w8 ? 2 : 3; }
-    else if (h->P <= 2560 && !getenv("CLOTHHIP_DEBUG_NT1024")) { h->nt = 512; h->ppt = 5; }
-    else if (h->P <= 3072) { h->nt = 1024; h->ppt = 3; } else { h->nt = 1024; h->ppt = 4; }
-    h->HT = 64; h->ht_bits = 0;
-    while (h->HT <= h->P + h->P / 2) h->HT <<= 1;
-    while ((1 << h->ht_bits) < h->HT) h->ht_bits++;
+    int nt, ppt;
+    if (small_grid) { nt = dbg.w8_off ? 256 : 512; ppt = dbg.w8_off ? 3 : 2; }
+    else if (h->P <= 2560 && !dbg.nt1024) { nt = 512; ppt = 5; }
+    else if (h->P <= 3072) { nt = 1024; ppt = 3; } else { nt = 1024; ppt = 4; }
+    int HT = 64;
+    while (HT <= h->P + h->P / 2) HT <<= 1;
     // large dynamic LDS (up to the CU's 160 KiB) for the stepper kernels. The static tables ride in LDS too
     // as long as TWO cloths still fit per CU (512 cloths = 2 per CU on the 256 CUs of an MI355X).
+    // 256-thread variants: two cloths per CU (<= 80 KiB each); the larger ones own the CU (<= 160 KiB)
+    const int budget = small_grid ? lds_budget(2) : lds_budget(1);
+    const int tab = std::min((nt <= 512 && LdsLayout(tsz, h->Ppad, h->Spad, HT, 1, 0).total <= budget) ? 1 : 0, dbg.tab_lds);
+    const bool rest_reg = nt == 256 && precision == CLOTHHIP_F32 && tab == 1 && dbg.rest_reg;
+    // LEAN variants: three to six cloths per CU instead of two, each stepping at a lower rate (lean_rates.hpp, measured by
+    // tools/measure_pick_table.py). A launch runs its cloths in generations of what is resident, so the batch size decides:
+    // the largest rate_r / ceil(E / (r * CUs)) wins.
     {
-        const int tsz = (int)h->tsz;
-        const int precision = h->precision;
-        // 256-thread variants: two cloths per CU (<= 80 KiB each); the larger ones own the CU (<= 160 KiB)
-        const int budget = small_grid ? lds_budget(2) : lds_budget(1);
-        const int tmax = h->nt <= 512 ? 1 : 0;
-        h->tab = (tmax >= 1 && LdsLayout(tsz, h->Ppad, h->Spad, h->HT, 1, 0).total <= budget) ? 1 : 0;
-        if (const char *t = getenv("CLOTHHIP_DEBUG_TAB_LDS")) h->tab = std::min(h->tab, atoi(t));
-        h->rest_reg = (h->nt == 256 && precision == CLOTHHIP_F32 && h->tab == 1);
-        if (const char *t = getenv("CLOTHHIP_DEBUG_REST_REG")) h->rest_reg = h->rest_reg && atoi(t);
-        // LEAN variants: three to six cloths per CU instead of two, each stepping at a lower rate (lean_rates.hpp, measured by
-        // tools/measure_pick_table.py). A launch runs its cloths in generations of what is resident, so the batch size decides:
-        // the largest rate_r / ceil(E / (r * CUs)) wins.
-        {
-            h->n_cus = cus;
-            // substeps/s of ONE resident cloth at 2 (standard), 3 and 4 cloths per CU, relative to the standard variant's: measured
-            // by tools/measure_pick_table.py on the bench workload and written to lean_rates.hpp (its output: profiles/)
-            // r = 2: the EIGHT-WAVE LEAN build (512 threads x 2 particles, window table in LDS) when the flat palette holds, else the
-            // standard variant; r = 3 .. 6: the four-wave LEAN builds with the table streamed from L2 (168 / 128 / 96 / 80 VGPRs; from
-            // five per CU on without the cell-ordered record copy: 22.6 KB of LDS per cloth)
-            const bool lean_able = small_grid && precision == CLOTHHIP_F32;
-            const double rate[5] = {lean_able ? LEAN_RATE_2_PER_CU_8W : 1.0, LEAN_RATE_3_PER_CU, LEAN_RATE_4_PER_CU, LEAN_RATE_5_PER_CU, LEAN_RATE_6_PER_CU};
-            double best = 0.0; int best_r = 2;
-            for (int r = 2; r <= std::max(2, std::min(6, max_r)); r++) {
-                // (r >= 3: the four-wave LEAN layout, table streamed, must fit r times in the CU's LDS -- 27x27 does not at five per CU)
-                if (r >= 3 && (!lean_able || LdsLayout(tsz, h->Ppad, h->Spad, h->HT, 0, 0).total > lds_budget(r))) continue;
-                const double v = rate[r - 2] / (double)((h->E + r * cus - 1) / (r * cus));
-                if (v > best * 1.02) { best = v; best_r = r; }
-            }
-            h->lean = lean_able;
-            h->lean_r = best_r;
-            // the large grids (one cloth per CU): the LEAN arithmetic frees the registers of the gather entries and takes the rest lengths
-            // off the L2 path, which lets SIXTEEN waves step a cloth at 128 VGPRs (1024 threads x 3 or 4 particles; 50x50: 2.90 M/s
-            // standard 512 x 5 -> 3.05 LEAN 512 x 5 -> 3.26 LEAN 1024 x 3); the standard variant stays as the fallback (per-env rest tables)
-            if (!small_grid && precision == CLOTHHIP_F32) { h->lean = true; h->lean_r = 1; }
-            // fp64, 25x25 class, eight waves per cloth (round 6): the LEAN arithmetic with per-spring ulp offsets (StepArgs::lstc) -- no gather-table and no
-            // rest-length loads from L2 in the Hooke gather and the strain pre-pass; same layout class as the standard fp64 variant (two cloths per CU)
-            if (small_grid && precision == CLOTHHIP_F64 && h->nt == 512) { h->lean = true; h->lean_r = 2; }
+        h->n_cus = cus;
+        // substeps/s of ONE resident cloth at 2 (standard), 3 and 4 cloths per CU, relative to the standard variant's: measured
+        // by tools/measure_pick_table.py on the bench workload and written to lean_rates.hpp (its output: profiles/)
+        // r = 2: the EIGHT-WAVE LEAN build (512 threads x 2 particles, window table in LDS) when the flat palette holds, else the
+        // standard variant; r = 3 .. 6: the four-wave LEAN builds with the table streamed from L2 (168 / 128 / 96 / 80 VGPRs; from
+        // five per CU on without the cell-ordered record copy: 22.6 KB of LDS per cloth)
+        const bool lean_able = small_grid && precision == CLOTHHIP_F32;
+        const double rate[5] = {lean_able ? LEAN_RATE_2_PER_CU_8W : 1.0, LEAN_RATE_3_PER_CU, LEAN_RATE_4_PER_CU, LEAN_RATE_5_PER_CU, LEAN_RATE_6_PER_CU};
+        double best = 0.0; int best_r = 2;
+        for (int r = 2; r <= std::max(2, std::min(6, max_r)); r++) {
+            // (r >= 3: the four-wave LEAN layout, table streamed, must fit r times in the CU's LDS -- 27x27 does not at five per CU)
+            if (r >= 3 && (!lean_able || LdsLayout(tsz, h->Ppad, h->Spad, HT, 0, 0).total > lds_budget(r))) continue;
+            const double v = rate[r - 2] / (double)((h->E + r * cus - 1) / (r * cus));
+            if (v > best * 1.02) { best = v; best_r = r; }
         }
-        if (const char *t = getenv("CLOTHHIP_DEBUG_LEAN")) {      // 0: never; 8 (or 2): the eight-wave build; 3 (or 1) / 4 / 5 / 6: the LEAN build for that many cloths per CU, whatever the batch size
-            const int v = atoi(t);
-            if (v == 0) h->lean = false;
-            else if (small_grid && precision == CLOTHHIP_F32) { h->lean = true; h->lean_r = (v == 8 || v == 2) ? 2 : ((v >= 4 && v <= 6) ? v : 3); }
-        }
-        if (h->lean) {
-            // the arithmetic stencil of the LEAN kernel against the gather table built from the reference's spring list
-            h->lean_stencil_ok = true;
-            for (int i = 0; i < h->P && h->lean_stencil_ok; i++) {
-                const uint32_t vm = lean_valid_mask(i / h->N, i % h->N, h->N);
-                int slot = 0;
-                for (int k = 0; k < HK_SLOTS; k++) {
-                    if (!((vm >> k) & 1u)) continue;
-                    const int off[12] = {-h->N, -1, -h->N - 1, -h->N + 1, -2 * h->N, -2, 1, 2, h->N - 1, h->N, h->N + 1, 2 * h->N};
-                    const uint32_t want = (uint32_t)(i + off[k]) | HK_VALID | (k < HK_SLOTS / 2 ? HK_ASB : 0u) | (lean_bend(k) ? HK_BEND : 0u);
-                    const uint32_t g = gather[(size_t)slot * h->Ppad + i];
-                    const uint32_t have = g & (HK_NBR_MASK | HK_VALID | HK_ASB | HK_BEND);
-                    const int sp = h->wt.spring_at[(g >> HK_POS_SHIFT) & HK_POS_MASK];
-                    const int ty = sp >= 0 ? h->topo.type[sp] : -1;
-                    const int want_ty = lean_bend(k) ? SPRING_BENDING : (lean_shear(k) ? SPRING_SHEARING : SPRING_STRUCTURAL);
-                    if (have != want || ty != want_ty) h->lean_stencil_ok = false;
-                    slot++;
-                }
-                if (slot < HK_SLOTS && h->lean_stencil_ok && (gather[(size_t)slot * h->Ppad + i] & HK_VALID)) h->lean_stencil_ok = false;
-            }
-            if (!h->lean_stencil_ok) h->lean = false;
-        }
-        // the cell-ordered record copy for the collision pre-check is taken only if it does not cost the table its place
-        h->cell_copy = LdsLayout(tsz, h->Ppad, h->Spad, h->HT, h->tab, 1).total <= budget ? 1 : 0;
-        if (const char *t = getenv("CLOTHHIP_DEBUG_CELL_COPY")) h->cell_copy = h->cell_copy && atoi(t);
-        h->lds_bytes = LdsLayout(tsz, h->Ppad, h->Spad, h->HT, h->tab, h->cell_copy).total;
-        h->lay_std = {h->nt, h->ppt, h->tab, h->rest_reg, h->cell_copy, h->lds_bytes, h->HT, h->ht_bits, 0, 0};
-        // the in-kernel metrics of the episode launches borrow the LDS from the hash table on (the window table in front of it stays
-        // resident). With the table in LDS but no room for the cell-ordered copy that region can be too small (fp64 21, 22, 30-32;
-        // fp32 41-43): the allocation is then padded behind the layout's end, or, if the budget forbids that, the table leaves LDS
-        if (!fit_scratch(h->lay_std, tsz, h->Ppad, h->Spad, h->P, budget) && h->tab == 1) {
-            h->tab = 0; h->rest_reg = false;
-            h->cell_copy = LdsLayout(tsz, h->Ppad, h->Spad, h->HT, 0, 1).total <= budget ? 1 : 0;
-            if (const char *t = getenv("CLOTHHIP_DEBUG_CELL_COPY")) h->cell_copy = h->cell_copy && atoi(t);
-            h->lay_std = {h->nt, h->ppt, 0, false, h->cell_copy, LdsLayout(tsz, h->Ppad, h->Spad, h->HT, 0, h->cell_copy).total, h->HT, h->ht_bits, 0, 0};
-            fit_scratch(h->lay_std, tsz, h->Ppad, h->Spad, h->P, budget);
-        }
-        h->lds_bytes = h->lay_std.lds_bytes;
-        if (h->lean) {                                   // the lean layout: window table streamed from L2, 33 KB of LDS
-            int cc = LdsLayout(tsz, h->Ppad, h->Spad, h->HT, 0, 1).total <= lds_budget(std::max(h->lean_r, 3)) ? 1 : 0;
-            if (const char *t = getenv("CLOTHHIP_DEBUG_CELL_COPY")) cc = cc && atoi(t);
-            h->lay_lean = {256, 3, h->lean_r >= 4 ? 3 - h->lean_r : 0, true, cc, LdsLayout(tsz, h->Ppad, h->Spad, h->HT, 0, cc).total, h->HT, h->ht_bits};   // (r = 3, 4: four waves per cloth)
-            if (precision == CLOTHHIP_F64) {             // fp64 LEAN: table streamed (TAB 0), the stencil constants in LDS
-                cc = LdsLayout(tsz, h->Ppad, h->Spad, h->HT, 0, 1, 1).total <= lds_budget(2) ? 1 : 0;
-                if (const char *t = getenv("CLOTHHIP_DEBUG_CELL_COPY")) cc = cc && atoi(t);
-                h->lay_lean = {512, 2, 0, true, cc, LdsLayout(tsz, h->Ppad, h->Spad, h->HT, 0, cc, 1).total, h->HT, h->ht_bits};
-                if (h->lay_lean.lds_bytes > lds_budget(2)) h->lean = false;
-            } else
-            if (h->lean_r == 2 && small_grid) {          // eight waves per cloth, two cloths per CU: the standard variant's LDS budget
-                cc = LdsLayout(tsz, h->Ppad, h->Spad, h->HT, 2, 1).total <= 80 * 1024 ? 1 : 0;
-                if (const char *t = getenv("CLOTHHIP_DEBUG_CELL_COPY")) cc = cc && atoi(t);
-                h->lay_lean = {512, 2, 2, true, cc, LdsLayout(tsz, h->Ppad, h->Spad, h->HT, 2, cc).total, h->HT, h->ht_bits};
-                if (h->lay_lean.lds_bytes > 80 * 1024 || h->P > 1024) h->lean = false;      // (the table must fit beside a second cloth)
-            }
-            if (h->lean_r == 1) {                        // the whole CU: same LDS budget as the standard variant of these grids
-                cc = LdsLayout(tsz, h->Ppad, h->Spad, h->HT, 0, 1).total <= 160 * 1024 ? 1 : 0;
-                if (const char *t = getenv("CLOTHHIP_DEBUG_CELL_COPY")) cc = cc && atoi(t);
-                h->lay_lean = {1024, h->P <= 3072 ? 3 : 4, 3, true, cc, LdsLayout(tsz, h->Ppad, h->Spad, h->HT, 0, cc).total, h->HT, h->ht_bits};
-                // TWO large-grid cloths per CU (eight waves each, 128 VGPRs) when the batch has more cloths than the device has CUs and it
-                // pays by the measured rates: <= 80 KB of LDS per cloth -- no cell-ordered copy, and a hash table of just enough slots
-                // (not a power of two: > P, so that a free slot always exists, and large enough that the in-kernel metrics' scratch fits)
-                int NSb = 1; while (NSb < h->P) NSb <<= 1;
-                int ht2 = (h->P / 64 + 2) * 64;
-                while (LdsLayout(tsz, h->Ppad, h->Spad, ht2, 0, 0).total - LdsLayout(tsz, h->Ppad, h->Spad, ht2, 0, 0).hkey < metrics_scratch_bytes(NSb, h->Ppad + 8, tsz, true)) ht2 += 64;
-                const int lds2 = LdsLayout(tsz, h->Ppad, h->Spad, ht2, 0, 0).total;
-                const int gens1 = (h->E + h->n_cus - 1) / h->n_cus, gens2 = (h->E + 2 * h->n_cus - 1) / (2 * h->n_cus);
-                const bool two = h->P <= 2560 && lds2 <= 80 * 1024 && LEAN_RATE_LARGE_2_PER_CU / gens2 > 1.02 / gens1;
-                int want2 = two ? 1 : 0;
-                if (const char *t = getenv("CLOTHHIP_DEBUG_LARGE2")) want2 = atoi(t) && h->P <= 2560 && lds2 <= 80 * 1024;
-                if (want2) { h->lay_lean = {512, 5, 4, true, 0, lds2, ht2, 0}; h->lean_r = 2; }
-            }
-            // the in-kernel metrics borrow the region behind the hash table (clothhip_fused_supported): it must hold them here too
-            const int lean_budget = lds_budget(h->lean_r);
-            if (!fit_scratch(h->lay_lean, tsz, h->Ppad, h->Spad, h->P, lean_budget)) h->lean = false;
-        }
+        h->lean = lean_able;
+        h->lean_r = best_r;
+        // the large grids (one cloth per CU): the LEAN arithmetic frees the registers of the gather entries and takes the rest lengths
+        // off the L2 path, which lets SIXTEEN waves step a cloth at 128 VGPRs (1024 threads x 3 or 4 particles; 50x50: 2.90 M/s
+        // standard 512 x 5 -> 3.05 LEAN 512 x 5 -> 3.26 LEAN 1024 x 3); the standard variant stays as the fallback (per-env rest tables)
+        if (!small_grid && precision == CLOTHHIP_F32) { h->lean = true; h->lean_r = 1; }
+        // fp64, 25x25 class, eight waves per cloth (round 6): the LEAN arithmetic with per-spring ulp offsets (StepArgs::lstc) -- no gather-table and no
+        // rest-length loads from L2 in the Hooke gather and the strain pre-pass; same layout class as the standard fp64 variant (two cloths per CU)
+        if (small_grid && precision == CLOTHHIP_F64 && nt == 512) { h->lean = true; h->lean_r = 2; }
     }
+    if (dbg.lean_set) {      // 0: never; 8 (or 2): the eight-wave build; 3 (or 1) / 4 / 5 / 6: the LEAN build for that many cloths per CU, whatever the batch size
+        if (dbg.lean == 0) h->lean = false;
+        else if (small_grid && precision == CLOTHHIP_F32) { h->lean = true; h->lean_r = (dbg.lean == 8 || dbg.lean == 2) ? 2 : ((dbg.lean >= 4 && dbg.lean <= 6) ? dbg.lean : 3); }
+    }
+    if (h->lean) {
+        // the arithmetic stencil of the LEAN kernel against the gather table built from the reference's spring list
+        h->lean_stencil_ok = true;
+        for (int i = 0; i < h->P && h->lean_stencil_ok; i++) {
+            const uint32_t vm = lean_valid_mask(i / h->N, i % h->N, h->N);
+            int slot = 0;
+            for (int k = 0; k < HK_SLOTS; k++) {
+                if (!((vm >> k) & 1u)) continue;
+                const int off[12] = {-h->N, -1, -h->N - 1, -h->N + 1, -2 * h->N, -2, 1, 2, h->N - 1, h->N, h->N + 1, 2 * h->N};
+                const uint32_t want = (uint32_t)(i + off[k]) | HK_VALID | (k < HK_SLOTS / 2 ? HK_ASB : 0u) | (lean_bend(k) ? HK_BEND : 0u);
+                const uint32_t g = gather[(size_t)slot * h->Ppad + i];
+                const uint32_t have = g & (HK_NBR_MASK | HK_VALID | HK_ASB | HK_BEND);
+                const int sp = h->wt.spring_at[(g >> HK_POS_SHIFT) & HK_POS_MASK];
+                const int ty = sp >= 0 ? h->topo.type[sp] : -1;
+                const int want_ty = lean_bend(k) ? SPRING_BENDING : (lean_shear(k) ? SPRING_SHEARING : SPRING_STRUCTURAL);
+                if (have != want || ty != want_ty) h->lean_stencil_ok = false;
+                slot++;
+            }
+            if (slot < HK_SLOTS && h->lean_stencil_ok && (gather[(size_t)slot * h->Ppad + i] & HK_VALID)) h->lean_stencil_ok = false;
+        }
+        if (!h->lean_stencil_ok) h->lean = false;
+    }
+    // the cell-ordered record copy for the collision pre-check is taken only if it does not cost the table its place
+    h->lay_std = make_layout(h, nt, ppt, tab, rest_reg, HT, budget);
+    // the in-kernel metrics of the episode launches borrow the LDS from the hash table on (the window table in front of it stays
+    // resident). With the table in LDS but no room for the cell-ordered copy that region can be too small (fp64 21, 22, 30-32;
+    // fp32 41-43): the allocation is then padded behind the layout's end, or, if the budget forbids that, the table leaves LDS
+    if (!fit_scratch(h->lay_std, tsz, h->Ppad, h->Spad, h->P, budget) && tab == 1) {
+        h->lay_std = make_layout(h, nt, ppt, 0, false, HT, budget);
+        fit_scratch(h->lay_std, tsz, h->Ppad, h->Spad, h->P, budget);
+    }
+    if (!h->lean) return;
+    if (precision == CLOTHHIP_F64) {                     // fp64 LEAN: table streamed (TAB 0), the stencil constants in LDS
+        h->lay_lean = make_layout(h, 512, 2, 0, true, HT, lds_budget(2));
+        if (h->lay_lean.lds_bytes > lds_budget(2)) h->lean = false;
+    } else if (h->lean_r == 2 && small_grid) {           // eight waves per cloth, two cloths per CU: the standard variant's LDS budget
+        h->lay_lean = make_layout(h, 512, 2, 2, true, HT, 80 * 1024);
+        if (h->lay_lean.lds_bytes > 80 * 1024 || h->P > 1024) h->lean = false;      // (the table must fit beside a second cloth)
+    } else if (h->lean_r == 1) {                         // the whole CU: same LDS budget as the standard variant of these grids
+        h->lay_lean = make_layout(h, 1024, h->P <= 3072 ? 3 : 4, 3, true, HT, 160 * 1024);
+        // TWO large-grid cloths per CU (eight waves each, 128 VGPRs) when the batch has more cloths than the device has CUs and it
+        // pays by the measured rates: <= 80 KB of LDS per cloth -- no cell-ordered copy, and a hash table of just enough slots
+        // (not a power of two: > P, so that a free slot always exists, and large enough that the in-kernel metrics' scratch fits)
+        int NSb = 1; while (NSb < h->P) NSb <<= 1;
+        int ht2 = (h->P / 64 + 2) * 64;
+        while (LdsLayout(tsz, h->Ppad, h->Spad, ht2, 0, 0).total - LdsLayout(tsz, h->Ppad, h->Spad, ht2, 0, 0).hkey < metrics_scratch_bytes(NSb, h->Ppad + 8, tsz, true)) ht2 += 64;
+        const int lds2 = LdsLayout(tsz, h->Ppad, h->Spad, ht2, 0, 0).total;
+        const int gens1 = (h->E + h->n_cus - 1) / h->n_cus, gens2 = (h->E + 2 * h->n_cus - 1) / (2 * h->n_cus);
+        const bool fits2 = h->P <= 2560 && lds2 <= 80 * 1024;
+        if (dbg.large2_set ? dbg.large2 && fits2 : fits2 && LEAN_RATE_LARGE_2_PER_CU / gens2 > 1.02 / gens1) {
+            h->lay_lean = {512, 5, 4, true, 0, lds2, ht2, 0, 0, 0}; h->lean_r = 2;
+        }
+    } else {                                             // the four-wave LEAN builds, window table streamed from L2, 33 KB of LDS
+        h->lay_lean = make_layout(h, 256, 3, h->lean_r >= 4 ? 3 - h->lean_r : 0, true, HT, lds_budget(h->lean_r));
+    }
+    // the in-kernel metrics borrow the region behind the hash table (clothhip_fused_supported): it must hold them here too
+    if (!fit_scratch(h->lay_lean, tsz, h->Ppad, h->Spad, h->P, lds_budget(h->lean_r))) h->lean = false;
 }
 
 extern "C" int clothhip_create(const ClothParams *params, int32_t n_envs, int32_t device, int32_t precision,
@@ -399,7 +414,7 @@ extern "C" int clothhip_create(const ClothParams *params, int32_t n_envs, int32_
     h->topo = build_topology(h->N);
     h->wt = build_windows(h->topo, build_levels(h->topo));
     h->S = h->topo.S; h->Spad = h->wt.n_slots;               // rest-length arrays are kept in window-table slot order
-    if (const char *pmk = getenv("CLOTHHIP_DEBUG_PHASES")) h->phase_mask = atoi(pmk);
+    h->dbg = read_debug_knobs();
     std::vector<uint32_t> gather = build_gather(h->topo, h->wt, h->Ppad);
     std::vector<double> levels = build_grab_levels(params->height, params->thickness);
     h->n_grab_levels = (int)levels.size();
@@ -460,50 +475,29 @@ extern "C" int clothhip_create(const ClothParams *params, int32_t n_envs, int32_
         plan_layouts(h, cus, gather);
         // the pick assumed lean_r resident cloths per CU: ask the device (registers, LDS granules, what else it counts) and fall back to the
         // best residency it does grant -- a build planned for r that runs at r - 1 would be slower than the build meant for r - 1
-        for (int guard = 0; guard < 5 && h->lean && h->lean_r >= 3 && !getenv("CLOTHHIP_DEBUG_LEAN"); guard++) {
-            const clothhip_handle::Layout keep = {h->nt, h->ppt, h->tab, h->rest_reg, h->cell_copy, h->lds_bytes};
-            h->nt = h->lay_lean.nt; h->ppt = h->lay_lean.ppt; h->tab = h->lay_lean.tab; h->rest_reg = h->lay_lean.rest_reg;
-            const void *fl = stepper_fn(h, 1);
-            h->nt = keep.nt; h->ppt = keep.ppt; h->tab = keep.tab; h->rest_reg = keep.rest_reg;
+        for (int guard = 0; guard < 5 && h->lean && h->lean_r >= 3 && !h->dbg.lean_set; guard++) {
+            const void *fl = find_stepper((int)h->tsz, h->lay_lean, 0, 1);
             int occ = 0;
             if (!fl || hipFuncSetAttribute(fl, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
                 hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fl, h->lay_lean.nt, (size_t)h->lay_lean.lds_bytes) != hipSuccess) { (void)hipGetLastError(); break; }
             if (occ >= h->lean_r) break;
             plan_layouts(h, cus, gather, std::max(2, occ));
         }
-        if (h->lds_bytes > 160 * 1024) { free_handle(h); return fail(CLOTHHIP_EINVAL, "n_side %d needs %d B of LDS (> 160 KiB)", h->N, h->lds_bytes); }
-        if (h->lean) {                                   // the lean kernels too (which layout runs is decided per launch)
-            const clothhip_handle::Layout keep = {h->nt, h->ppt, h->tab, h->rest_reg, h->cell_copy, h->lds_bytes};
-            const int keep_ht = h->HT, keep_hb = h->ht_bits;
-            h->nt = h->lay_lean.nt; h->ppt = h->lay_lean.ppt; h->tab = h->lay_lean.tab; h->rest_reg = h->lay_lean.rest_reg;
-            h->cell_copy = h->lay_lean.cell_copy; h->HT = h->lay_lean.HT; h->ht_bits = h->lay_lean.ht_bits;
-            for (int sp = 0; sp < 2; sp++) {             // the generic build of the layout and, where it exists for it, the grid-specialised one
-                h->spec_now = sp == 1 ? spec_ns(h, false) : 0;
-                if (sp == 1 && !h->spec_now) break;
-                for (int f = 0; f < 3; f++) {
-                    const void *fl = stepper_fn(h, f);
-                    if (!fl) { free_handle(h); return fail(CLOTHHIP_EINVAL, "no lean stepper variant for n_side %d", h->N); }
-                    HC(hipFuncSetAttribute(fl, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                }
-            }
-            h->spec_now = 0; h->cell_copy = keep.cell_copy; h->HT = keep_ht; h->ht_bits = keep_hb;
-            h->nt = keep.nt; h->ppt = keep.ppt; h->tab = keep.tab; h->rest_reg = keep.rest_reg;
-        }
-        const void *fn = stepper_fn(h, 0), *fnf = stepper_fn(h, 1), *fnf2 = stepper_fn(h, 2);
-        if (!fn || !fnf || !fnf2) { free_handle(h); return fail(CLOTHHIP_EINVAL, "no stepper variant for n_side %d", h->N); }
-        HC(hipFuncSetAttribute(fnf, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HC(hipFuncSetAttribute(fnf2, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        // the attribute is per kernel function and process-global: always the CU's full 160 KiB, so that a later handle
-        // with a smaller footprint can never lower it under an earlier one
-        HC(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        h->spec_now = spec_ns(h, false);                 // the grid-specialised build of the standard layout, where one exists (tier 2 at 25x25)
-        if (h->spec_now) {
+        if (h->lay_std.lds_bytes > 160 * 1024) { free_handle(h); return fail(CLOTHHIP_EINVAL, "n_side %d needs %d B of LDS (> 160 KiB)", h->N, h->lay_std.lds_bytes); }
+        // every kernel the handle may launch: the generic build of the standard layout, of the lean one (which of the two runs is decided
+        // per launch) and, where one exists for a layout, its grid-specialised build (tier 2 at 25x25, the LEAN builds). The attribute is
+        // per kernel function and process-global: always the CU's full 160 KiB, so that a later handle with a smaller footprint can never
+        // lower it under an earlier one
+        for (const Layout *L : {&h->lay_std, &h->lay_lean}) {
+            if (L == &h->lay_lean && !h->lean) continue;
+            const int ns = spec_ns(h, *L, false);
             for (int f = 0; f < 3; f++) {
-                const void *fs = stepper_fn(h, f);
-                if (fs) HC(hipFuncSetAttribute(fs, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                const void *fn = find_stepper((int)h->tsz, *L, 0, f);
+                if (!fn) { free_handle(h); return fail(CLOTHHIP_EINVAL, "no %sstepper variant for n_side %d", L == &h->lay_lean ? "lean " : "", h->N); }
+                HC(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                if (ns) HC(hipFuncSetAttribute(find_stepper((int)h->tsz, *L, ns, f), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             }
         }
-        h->spec_now = 0;
     }
 #undef HC
     // initial state: flat tier-1 grid for every env, shared rest table
@@ -767,10 +761,10 @@ template <typename T> static StepArgs<T> make_args(clothhip_handle *h, const Clo
     a.e0 = 0;
     a.pos = (T *)h->d_pos; a.prev = (T *)h->d_prev; a.cnt = h->d_cnt; a.rest = (const T *)h->d_rest;
     a.tear = h->d_tear; a.executed = h->d_exec; a.stats = h->d_stats; a.sched = d_sched;
-    a.gather = h->d_gather; a.wt_ent = h->d_wt_ent; a.wt_dep = h->d_wt_dep; a.nW = h->wt.nW; a.wt_rshift = h->wt.reach_shift; a.cell_copy = h->cell_copy;
+    a.gather = h->d_gather; a.wt_ent = h->d_wt_ent; a.wt_dep = h->d_wt_dep; a.nW = h->wt.nW; a.wt_rshift = h->wt.reach_shift; a.cell_copy = h->lay().cell_copy;
     a.N = h->N; a.P = h->P; a.Ppad = h->Ppad; a.S = h->S; a.Spad = h->Spad;
-    a.HT = h->HT; a.ht_bits = h->ht_bits;
-    a.rest_stride = h->rest_stride; a.phase_mask = h->phase_mask;
+    a.HT = h->lay().HT; a.ht_bits = h->lay().ht_bits;
+    a.rest_stride = h->rest_stride; a.phase_mask = h->dbg.phase_mask;
     a.k = make_consts<T>(h->prm);
     if (sizeof(T) == 8) { a.pal_struct = (T)h->pal64[SPRING_STRUCTURAL]; a.pal_shear = (T)h->pal64[SPRING_SHEARING]; a.pal_bend = (T)h->pal64[SPRING_BENDING]; }
     else { a.pal_struct = (T)h->pal[SPRING_STRUCTURAL]; a.pal_shear = (T)h->pal[SPRING_SHEARING]; a.pal_bend = (T)h->pal[SPRING_BENDING]; }
@@ -779,18 +773,14 @@ template <typename T> static StepArgs<T> make_args(clothhip_handle *h, const Clo
     return a;
 }
 
-// Which stepper runs the next launch: the LEAN variant (three cloths per CU) when this handle wants it and the device's shared
-// rest table is a three-value palette (re-checked whenever the table may have changed: per-env tables, i.e. tier 2, or odd
-// rest lengths uploaded by the caller switch back), else the standard variant. LDS is rebuilt by every launch, so the layout
-// may change from one launch to the next.
-// Which grid-specialised kernel (k_run_schedule<..., NS>, NS = 25 or 50) may run the layout the handle's fields describe NOW -- 0: none, the generic
-// build. Only if the variant is one of the specialised ones (stepper_variants.hpp: CLOTH_SPEC_*) AND every constant that build has compiled in
+// Which grid-specialised kernel (k_run_schedule<..., NS>, NS = 25 or 50) may run layout L -- 0: none, the generic build. Only if the
+// variant is one of the specialised ones (stepper_variants.hpp: CLOTH_SPEC_*) AND every constant that build has compiled in
 // (cloth_common.hpp: spec_*) is what this handle computed: grid, window table, hash-table size, whether the cell-ordered copy exists, all phases
-// on (debug masks take the generic build, as does CLOTHHIP_DEBUG_NOSPEC=1 -- the A/B and the bit-identity test of the two).
+// on (debug masks take the generic build, as does CLOTHHIP_DEBUG_NOSPEC=1 -- the A/B and the bit-identity test of the two; read at every call).
 // (with_palette false: clothhip_create, which prepares every kernel the handle may launch before any rest table has been read back)
-static int spec_ns(const clothhip_handle *h, bool with_palette) {
-    if (getenv("CLOTHHIP_DEBUG_NOSPEC") && atoi(getenv("CLOTHHIP_DEBUG_NOSPEC"))) return 0;
-    if (h->phase_mask != 15 || (h->N != 25 && h->N != 50)) return 0;
+static int spec_ns(const clothhip_handle *h, const Layout &L, bool with_palette) {
+    if (read_debug_knobs().nospec) return 0;
+    if (h->dbg.phase_mask != 15 || (h->N != 25 && h->N != 50)) return 0;
     const int ns = h->N;
     {   // the physics constants the build has compiled in (cloth_common.hpp: spec_phys) must be this handle's
         const SpecPhys q = spec_phys(ns);
@@ -802,24 +792,22 @@ static int spec_ns(const clothhip_handle *h, bool with_palette) {
         if (h->precision == CLOTHHIP_F32) { const DevConsts<float> a = make_consts<float>(p), b = spec_consts<float>(ns); if (memcmp(&a, &b, sizeof(a)) != 0) return 0; }
         else { const DevConsts<double> a = make_consts<double>(p), b = spec_consts<double>(ns); if (memcmp(&a, &b, sizeof(a)) != 0) return 0; }
     }
-    bool listed = false;
-#define XS(T_, NT, PPT, TAB, RR, NS_) \
-    if (NS_ == ns && (sizeof(T_) == 4) == (h->precision == CLOTHHIP_F32) && h->nt == NT && h->ppt == PPT && h->tab == TAB && h->rest_reg == RR) listed = true;
-    CLOTH_SPEC_F32(XS) CLOTH_SPEC_F64(XS)
-#undef XS
-    if (!listed) return 0;
-    const bool same = h->P == spec_p(ns) && h->Ppad == spec_ppad(ns) && h->HT == spec_ht(ns, h->tab) && h->ht_bits == spec_htbits(ns, h->tab) &&
-                      h->Spad == spec_spad(ns) && h->wt.nW == spec_nw(ns) && h->wt.reach_shift == spec_rshift(ns) && h->cell_copy == spec_cell_copy(ns, h->tab);
+    if (!find_stepper((int)h->tsz, L, ns, 0)) return 0;
+    const bool same = h->P == spec_p(ns) && h->Ppad == spec_ppad(ns) && L.HT == spec_ht(ns, L.tab) && L.ht_bits == spec_htbits(ns, L.tab) &&
+                      h->Spad == spec_spad(ns) && h->wt.nW == spec_nw(ns) && h->wt.reach_shift == spec_rshift(ns) && L.cell_copy == spec_cell_copy(ns, L.tab);
     if (!same) return 0;
     // the LEAN fp32 builds hold the rest-length palette as literals: it must be what lean_refresh read back from the device's table
-    if (with_palette && h->precision == CLOTHHIP_F32 && h->rest_reg) {
+    if (with_palette && h->precision == CLOTHHIP_F32 && L.rest_reg) {
         for (int t = 0; t < 3; t++) { const float v = spec_pal(ns, t); if (memcmp(&v, &h->pal[t], 4) != 0) return 0; }
     }
     return ns;
 }
 
+// Which of the handle's two layouts the next launch runs: the LEAN one when this handle has one and the device's shared rest table is
+// its palette (re-checked whenever the table may have changed: per-env tables, i.e. tier 2, or odd rest lengths uploaded by the
+// caller switch back), else the standard one. LDS is rebuilt by every launch, so the layout may change from one launch to the next.
 static int lean_refresh(clothhip_handle *h) {
-    if (!h->lean) { h->spec_now = spec_ns(h); return 0; }
+    if (!h->lean) { h->spec_now = spec_ns(h, h->lay()); return 0; }
     if (h->lean_dirty) {
         h->lean_dirty = false; h->lean_ok = false;
         if (h->rest_stride == 0 && h->precision == CLOTHHIP_F64) {
@@ -874,98 +862,64 @@ static int lean_refresh(clothhip_handle *h) {
             h->lean_ok = ok && have[0] && have[1] && have[2];
         }
     }
-    const clothhip_handle::Layout &L = (h->lean_ok && h->rest_stride == 0) ? h->lay_lean : h->lay_std;
-    h->nt = L.nt; h->ppt = L.ppt; h->tab = L.tab; h->rest_reg = L.rest_reg; h->cell_copy = L.cell_copy; h->lds_bytes = L.lds_bytes;
-    h->HT = L.HT; h->ht_bits = L.ht_bits;
-    h->spec_now = spec_ns(h);
+    h->on_lean = h->lean_ok && h->rest_stride == 0;
+    h->spec_now = spec_ns(h, h->lay());
     return 0;
 }
 
-// (the compile-time variants -- CLOTH_VARIANTS, CLOTH_VARIANTS_LEAN -- and the object file each is compiled in: stepper_variants.hpp)
-template <typename T, int FUSED> static const void *stepper_fn_t(const clothhip_handle *h) {
-#define X(T_, NT, PPT, TAB, RR) \
-    if (h->nt == NT && h->ppt == PPT && h->tab == TAB && h->rest_reg == RR) return (const void *)k_run_schedule<T_, NT, PPT, TAB, RR, FUSED>;
-    if (h->spec_now) {
-#define XS(T_, NT, PPT, TAB, RR, NS_) \
-        if constexpr (sizeof(T_) == sizeof(T)) { if (h->spec_now == NS_ && h->nt == NT && h->ppt == PPT && h->tab == TAB && h->rest_reg == RR) return (const void *)k_run_schedule<T, NT, PPT, TAB, RR, FUSED, NS_>; }
-        CLOTH_SPEC_F32(XS) CLOTH_SPEC_F64(XS)
-#undef XS
-    }
-    CLOTH_VARIANTS(X, T)
-    if constexpr (sizeof(T) == 4) { CLOTH_VARIANTS_LEAN(X, T) } else { CLOTH_VARIANTS_LEAN64(X, T) }
-#undef X
-    return nullptr;
-}
-static const void *stepper_fn(const clothhip_handle *h, int fused) {
-    if (fused == 2) return h->precision == CLOTHHIP_F64 ? stepper_fn_t<double, 2>(h) : stepper_fn_t<float, 2>(h);
-    if (fused == 1) return h->precision == CLOTHHIP_F64 ? stepper_fn_t<double, 1>(h) : stepper_fn_t<float, 1>(h);
-    return h->precision == CLOTHHIP_F64 ? stepper_fn_t<double, 0>(h) : stepper_fn_t<float, 0>(h);
-}
-
-// resident workgroups per CU of a stepper kernel at the handle's LDS footprint (for clothhip_last_variant): asked once per (kernel,
+// resident workgroups per CU of a stepper kernel at the active layout's LDS footprint (for clothhip_last_variant): asked once per (kernel,
 // LDS bytes), not on every launch -- the step mode launches once per env step
-static int cached_occupancy(clothhip_handle *h, const void *fn, int nt) {
-    for (auto &c : h->occ_cache) if (c.fn == fn && c.lds == h->lds_bytes) return c.occ;
+static int cached_occupancy(clothhip_handle *h, const void *fn) {
+    const Layout &L = h->lay();
+    for (auto &c : h->occ_cache) if (c.fn == fn && c.lds == L.lds_bytes) return c.occ;
     int occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, nt, (size_t)h->lds_bytes) != hipSuccess) { (void)hipGetLastError(); occ = 0; }
-    for (auto &c : h->occ_cache) if (c.fn == nullptr) { c = {fn, h->lds_bytes, occ}; return occ; }
-    h->occ_cache[0] = {fn, h->lds_bytes, occ};
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, L.nt, (size_t)L.lds_bytes) != hipSuccess) { (void)hipGetLastError(); occ = 0; }
+    for (auto &c : h->occ_cache) if (c.fn == nullptr) { c = {fn, L.lds_bytes, occ}; return occ; }
+    h->occ_cache[0] = {fn, L.lds_bytes, occ};
     return occ;
 }
 
-// (the caller has run lean_refresh(h) -- which of the handle's two layouts may run now -- BEFORE recording its start event)
+template <typename T> static int launch_generations(clothhip_handle *h, const void *fn, int cap, const ClothSchedule *d_sched, const void *d_fz) {
+    StepArgs<T> a = make_args<T>(h, d_sched);
+    a.fz = (const FusedArgs<T> *)d_fz;
+    void *args[] = {&a};
+    h->last_dispatches = 0;
+    for (int e0 = 0; e0 < h->E; e0 += cap) {
+        a.e0 = e0; h->last_dispatches++;
+        HIPCHECK(hipLaunchKernel(fn, dim3(std::min(cap, h->E - e0)), dim3(h->lay().nt), args, (size_t)h->lay().lds_bytes, h->stream));
+    }
+    return 0;
+}
+
+// One stepper launch of the active layout (the caller has run lean_refresh(h) -- which of the handle's two layouts may run now -- BEFORE
+// recording its start event). fused: 0 one external schedule, 1 episodes, 2 episodes incl. tier-2 resets and the cold policies, 3 the
+// relaxed-order companion (Jacobi self-collision, coloured strain limit; the headline variant's layout only): its results differ from the
+// reference's by construction -- a labelled measurement of what the exact order costs (bench.py's companion record "exact_order": false),
+// never a product path.
 // `by_generation` (the time-sliced episode launches): every workgroup runs for the same time slice, counted from its own start, so a batch of
 // more cloths than are resident runs in generations -- which go out as ONE LAUNCH EACH, in stream order. Left to the hardware's
 // dispatcher the generations of a single launch change hands on every CU within a few dozen microseconds, and now and then a CU
 // that has just lost both of its workgroups takes only one new one for the whole slice (measured on 1 024 cloths of 50x50, two per
 // CU at 79.9 KB of LDS and 4 x 128 VGPRs per SIMD: in 3 launches of 8 one workgroup of the 1 024 started only when the second
 // generation had ended, 2 400 instead of 1 600 ms -- tools/placement.py, profiles/r05_placement.txt). A fresh launch finds every CU empty.
-template <typename T, int FUSED> static void launch_run(clothhip_handle *h, const ClothSchedule *d_sched, const void *d_fz, bool by_generation = false) {
-    StepArgs<T> a = make_args<T>(h, d_sched);
-    a.fz = (const FusedArgs<T> *)d_fz;
-    a.e0 = 0;
-#define XN(T_, NT, PPT, TAB, RR, NS_)                                                                   \
-    if (h->nt == NT && h->ppt == PPT && h->tab == TAB && h->rest_reg == RR) {                           \
-        const int occ_ = cached_occupancy(h, (const void *)k_run_schedule<T_, NT, PPT, TAB, RR, FUSED, NS_>, NT);    \
-        const int cap_ = by_generation && occ_ > 0 && h->n_cus > 0 && !getenv("CLOTHHIP_DEBUG_ONE_LAUNCH") ? occ_ * h->n_cus : h->E;   \
-        h->last_dispatches = 0;                                                                         \
-        for (int e0_ = 0; e0_ < h->E; e0_ += cap_) {                                                    \
-            a.e0 = e0_; h->last_dispatches++;                                                           \
-            hipLaunchKernelGGL((k_run_schedule<T_, NT, PPT, TAB, RR, FUSED, NS_>), dim3(std::min(cap_, h->E - e0_)), dim3(NT), h->lds_bytes, h->stream, a); \
-        }                                                                                               \
-        const int32_t v_[10] = {NT, PPT, TAB, RR ? 1 : 0, v_lean(TAB, RR, (int)sizeof(T_)) ? 1 : 0, FUSED, h->lds_bytes, occ_, h->n_cus, sizeof(T_) == 4 ? 1 : 0}; \
-        memcpy(h->last_variant, v_, sizeof(v_)); h->have_variant = true; h->last_spec = NS_;            \
-        return;                                                                                         \
-    }
-#define X(T_, NT, PPT, TAB, RR) XN(T_, NT, PPT, TAB, RR, 0)
-#define XS(T_, NT, PPT, TAB, RR, NS_) if constexpr (sizeof(T_) == sizeof(T)) { if (h->spec_now == NS_) { XN(T, NT, PPT, TAB, RR, NS_) } }
-    if (h->spec_now) { CLOTH_SPEC_F32(XS) CLOTH_SPEC_F64(XS) }
-    CLOTH_VARIANTS(X, T)
-    if constexpr (sizeof(T) == 4) { CLOTH_VARIANTS_LEAN(X, T) } else { CLOTH_VARIANTS_LEAN64(X, T) }
-#undef X
-#undef XS
-#undef XN
-}
-
-// The relaxed-order companion (k_run_schedule<float, 512, 2, 2, true, 3>: Jacobi self-collision, coloured strain limit): ONE instantiation,
-// the headline variant's layout. Results differ from the reference's by construction -- a labelled measurement of what the exact order
-// costs (bench.py's companion record "exact_order": false), never a product path.
-static void launch_relaxed(clothhip_handle *h, const void *d_fz) {
-    StepArgs<float> a = make_args<float>(h, h->d_sched);
-    a.fz = (const FusedArgs<float> *)d_fz;
-    hipLaunchKernelGGL((k_run_schedule<float, 512, 2, 2, true, 3>), dim3(h->E), dim3(512), h->lds_bytes, h->stream, a);
-    h->last_dispatches = 1; h->last_spec = 0;
-    const int occ_ = cached_occupancy(h, (const void *)k_run_schedule<float, 512, 2, 2, true, 3>, 512);
-    const int32_t v_[10] = {512, 2, 2, 1, 1, 3, h->lds_bytes, occ_, h->n_cus, 1};
-    memcpy(h->last_variant, v_, sizeof(v_)); h->have_variant = true;
+static int launch_run(clothhip_handle *h, int fused, const ClothSchedule *d_sched, const void *d_fz, bool by_generation) {
+    const Layout &L = h->lay();
+    const int tsz = (int)h->tsz, ns = fused == 3 ? 0 : h->spec_now;
+    const void *fn = find_stepper(tsz, L, ns, fused);
+    if (!fn) return fail(CLOTHHIP_ESTATE, "no stepper variant for this layout (fused mode %d)", fused);
+    const int occ = cached_occupancy(h, fn);
+    const int cap = by_generation && occ > 0 && h->n_cus > 0 && !read_debug_knobs().one_launch ? occ * h->n_cus : h->E;
+    if (int rc = tsz == 8 ? launch_generations<double>(h, fn, cap, d_sched, d_fz) : launch_generations<float>(h, fn, cap, d_sched, d_fz)) return rc;
+    const int32_t v[10] = {L.nt, L.ppt, L.tab, L.rest_reg ? 1 : 0, v_lean(L.tab, L.rest_reg, tsz) ? 1 : 0, fused, L.lds_bytes, occ, h->n_cus, tsz == 4 ? 1 : 0};
+    memcpy(h->last_variant, v, sizeof(v)); h->have_variant = true; h->last_spec = ns;
+    return 0;
 }
 
 static int run_common(clothhip_handle *h, const ClothSchedule *d_sched) {
     if (int rc = drop_in_flight(h, nullptr, d_sched)) return rc;
     if (int rc = lean_refresh(h)) return rc;         // (may synchronise and read the rest table back: outside the timed events)
     HIPCHECK(hipEventRecord(h->ev0, h->stream));
-    if (h->precision == CLOTHHIP_F64) launch_run<double, 0>(h, d_sched, nullptr);
-    else launch_run<float, 0>(h, d_sched, nullptr);
+    if (int rc = launch_run(h, 0, d_sched, nullptr, false)) return rc;
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipEventRecord(h->ev1, h->stream));
     h->have_timing = true;
@@ -1046,14 +1000,14 @@ static int grow(void **p, size_t *cap, size_t need) {
     return 0;
 }
 
-// (of the layout the handle's fields describe NOW: call lean_refresh first -- the LEAN and the standard layout differ in hash-table
-//  size, cell copy and hull-stack format)
+// (of the active layout: call lean_refresh first -- the LEAN and the standard layout differ in hash-table size, cell copy and hull-stack format)
 static int fused_scratch(const clothhip_handle *h, int *need_out) {
+    const Layout &L = h->lay();
     int NS = 1; while (NS < h->P) NS <<= 1;
     const int NH = h->Ppad + 8;
-    *need_out = metrics_scratch_bytes(NS, NH, (int)h->tsz, v_hull_idx(h->tab, (int)h->tsz, h->nt, h->ppt));
-    const LdsLayout lay((int)h->tsz, h->Ppad, h->Spad, h->HT, h->tab == 2 ? 2 : (v_ldstab(h->tab) ? 1 : 0), h->cell_copy);
-    return h->lds_bytes - lay.hkey;
+    *need_out = metrics_scratch_bytes(NS, NH, (int)h->tsz, v_hull_idx(L.tab, (int)h->tsz, L.nt, L.ppt));
+    const LdsLayout lay((int)h->tsz, h->Ppad, h->Spad, L.HT, L.tab == 2 ? 2 : (v_ldstab(L.tab) ? 1 : 0), L.cell_copy);
+    return L.lds_bytes - lay.hkey;
 }
 
 // Every layout the handle may run (the standard one always; the LEAN one while its palette holds) was sized in clothhip_create
@@ -1076,8 +1030,9 @@ extern "C" int clothhip_selftest_layout(const ClothParams *p, int32_t precision,
     h.topo = build_topology(h.N);
     h.wt = build_windows(h.topo, build_levels(h.topo));
     h.S = h.topo.S; h.Spad = h.wt.n_slots;
+    h.dbg = read_debug_knobs();
     plan_layouts(&h, n_cus, build_gather(h.topo, h.wt, h.Ppad));
-    auto put = [&](int o, const clothhip_handle::Layout &L) {
+    auto put = [&](int o, const Layout &L) {
         out[o] = L.nt; out[o + 1] = L.ppt; out[o + 2] = L.tab; out[o + 3] = L.rest_reg ? 1 : 0; out[o + 4] = L.cell_copy;
         out[o + 5] = L.lds_bytes; out[o + 6] = L.HT; out[o + 7] = L.scratch_have; out[o + 8] = L.scratch_need;
         out[o + 9] = L.scratch_have >= L.scratch_need ? 1 : 0;
@@ -1085,7 +1040,7 @@ extern "C" int clothhip_selftest_layout(const ClothParams *p, int32_t precision,
     put(0, h.lay_std);
     out[10] = h.lean ? 1 : 0; out[11] = h.lean_r;
     put(12, h.lay_lean);
-    out[22] = clothhip_fused_supported(&h); out[23] = h.lds_bytes <= 160 * 1024 ? 1 : 0;
+    out[22] = clothhip_fused_supported(&h); out[23] = h.lay_std.lds_bytes <= 160 * 1024 ? 1 : 0;
     return 0;
 }
 
@@ -1181,17 +1136,12 @@ extern "C" int clothhip_run_actions_begin(clothhip_handle *h, const ClothEpisode
                            rng_states != nullptr, rng_tier, domrand_words, NS, NH);
     HIPCHECK(hipMemcpyAsync(h->d_fz, fzbuf, 1024, hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipStreamSynchronize(h->stream));          // fzbuf is on this stack frame
-    if (h->relaxed && !(h->precision == CLOTHHIP_F32 && h->nt == 512 && h->ppt == 2 && h->tab == 2 && h->rest_reg && h->cell_copy && !tier2 &&
-                        policy != CLOTHHIP_POLICY_HIGHEST_POINT))
+    if (h->relaxed && !(find_stepper((int)h->tsz, h->lay(), 0, 3) && h->lay().cell_copy && !tier2 && policy != CLOTHHIP_POLICY_HIGHEST_POINT))
         return fail(CLOTHHIP_ESTATE, "clothhip_set_relaxed_order: the relaxed-order companion exists for the eight-wave LEAN layout only (fp32, flat tiers, 25x25 class, <= 512 cloths)");
     HIPCHECK(hipEventRecord(h->ev0, h->stream));
-    if (h->relaxed) launch_relaxed(h, h->d_fz);
-    else
-    if (tier2 || policy == CLOTHHIP_POLICY_HIGHEST_POINT) {   // the variant that also carries the tier-2 reset code and the cold policies
-        if (h->precision == CLOTHHIP_F64) launch_run<double, 2>(h, h->d_sched, h->d_fz, budget_ticks != 0);
-        else launch_run<float, 2>(h, h->d_sched, h->d_fz, budget_ticks != 0);
-    } else if (h->precision == CLOTHHIP_F64) launch_run<double, 1>(h, h->d_sched, h->d_fz, budget_ticks != 0);
-    else launch_run<float, 1>(h, h->d_sched, h->d_fz, budget_ticks != 0);
+    // (FUSED 2: the variant that also carries the tier-2 reset code and the cold policies; the relaxed-order companion is one launch)
+    const int fused = h->relaxed ? 3 : (tier2 || policy == CLOTHHIP_POLICY_HIGHEST_POINT) ? 2 : 1;
+    if (int rc = launch_run(h, fused, h->d_sched, h->d_fz, !h->relaxed && budget_ticks != 0)) return rc;
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipEventRecord(h->ev1, h->stream));
     h->have_timing = true;
@@ -1429,7 +1379,7 @@ extern "C" int clothhip_set_relaxed_order(clothhip_handle *h, int32_t on) {
     if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
     if (on) {
         HIPCHECK(hipSetDevice(h->device));
-        HIPCHECK(hipFuncSetAttribute((const void *)k_run_schedule<float, 512, 2, 2, true, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        HIPCHECK(hipFuncSetAttribute(find_stepper(4, Layout{512, 2, 2, true}, 0, 3), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     }
     h->relaxed = on != 0;
     return 0;

@@ -1,22 +1,27 @@
-// stepper_variants.hpp -- the compile-time variants of k_run_schedule (episode_loop.hpp) and the translation unit each one is compiled in.
+// stepper_variants.hpp -- the compile-time variants of k_run_schedule (episode_loop.hpp), the translation unit each one is compiled in, and
+// the table the host picks them from.
 //
-// The library has ~80 instantiations of one kernel template; compiled in one translation unit they took three minutes. They are split into
+// The library has 100 instantiations of one kernel template; compiled in one translation unit they took three minutes. They are split into
 // GROUPS, one object file each (stepper_inst.hip compiled with -DCLOTHHIP_INST_GROUP=g, in parallel by make); clothhip_api.hip sees them as
-// `extern template` declarations and only takes their addresses (a kernel launch across translation units needs no relocatable device code:
-// the host stub is an ordinary symbol, the device code is registered by the object that defines it).
+// `extern template` declarations and only takes their addresses, through STEPPER_ROWS / find_stepper below (a kernel launch across
+// translation units needs no relocatable device code: the host stub is an ordinary symbol, the device code is registered by the object that
+// defines it).
 //   X(T, NT, PPT, TAB, REST_REG): threads per cloth, particles per thread, table mode, rest lengths in registers / LEAN palette (episode_loop.hpp)
 #pragma once
 
 #include "episode_loop.hpp"
 
-// standard arithmetic (fp32 and fp64): the 25x25 class, then the large grids
-#define CLOTH_VARIANTS_SMALL(X, T) X(T, 512, 2, 1, false) X(T, 512, 2, 0, false) X(T, 256, 3, 1, true) X(T, 256, 3, 1, false) X(T, 256, 3, 0, false)
+// standard arithmetic: the 25x25 class, then the large grids. Rest lengths in registers and the 1024 x 4 variant are fp32 only: the plan
+// (clothhip_api.hip: plan_layouts) keeps REST_REG to fp32, and fp64 grids of more than 3 072 points exceed the CU's LDS.
+#define CLOTH_VARIANTS_SMALL_F32(X) X(float, 512, 2, 1, false) X(float, 512, 2, 0, false) X(float, 256, 3, 1, true) X(float, 256, 3, 1, false) X(float, 256, 3, 0, false)
+#define CLOTH_VARIANTS_SMALL_F64(X) X(double, 512, 2, 1, false) X(double, 512, 2, 0, false) X(double, 256, 3, 1, false) X(double, 256, 3, 0, false)
 #ifdef CLOTHHIP_FAST_BUILD           // development builds: the 25x25-class variants only (make fast)
-#define CLOTH_VARIANTS_LARGE(X, T)
+#define CLOTH_VARIANTS_LARGE_F32(X)
+#define CLOTH_VARIANTS_LARGE_F64(X)
 #else
-#define CLOTH_VARIANTS_LARGE(X, T) X(T, 512, 5, 0, false) X(T, 512, 5, 1, false) X(T, 1024, 3, 0, false) X(T, 1024, 4, 0, false)
+#define CLOTH_VARIANTS_LARGE_F32(X) X(float, 512, 5, 0, false) X(float, 512, 5, 1, false) X(float, 1024, 3, 0, false) X(float, 1024, 4, 0, false)
+#define CLOTH_VARIANTS_LARGE_F64(X) X(double, 512, 5, 0, false) X(double, 512, 5, 1, false) X(double, 1024, 3, 0, false)
 #endif
-#define CLOTH_VARIANTS(X, T) CLOTH_VARIANTS_SMALL(X, T) CLOTH_VARIANTS_LARGE(X, T)
 // the LEAN builds (fp32 only; 25x25 class: three to six cloths per CU, and eight waves per cloth at two per CU; the large grids: the whole CU
 // for a cloth, or two 512 x 5 cloths per CU)
 #define CLOTH_VARIANTS_LEAN_SMALL(X, T) X(T, 256, 3, 0, true) X(T, 256, 3, -1, true) X(T, 256, 3, -2, true) X(T, 256, 3, -3, true) X(T, 512, 2, 2, true)
@@ -25,7 +30,6 @@
 #else
 #define CLOTH_VARIANTS_LEAN_LARGE(X, T) X(T, 1024, 3, 3, true) X(T, 1024, 4, 3, true) X(T, 512, 5, 4, true)
 #endif
-#define CLOTH_VARIANTS_LEAN(X, T) CLOTH_VARIANTS_LEAN_SMALL(X, T) CLOTH_VARIANTS_LEAN_LARGE(X, T)
 // the fp64 LEAN build (25x25 class, eight waves per cloth; rest lengths = palette value + per-spring ulp offset)
 #define CLOTH_VARIANTS_LEAN64(X, T) X(T, 512, 2, 0, true)
 
@@ -61,10 +65,10 @@
 // The groups (object files). CLOTHHIP_INST_GROUPS of them; stepper_inst.hip defines group CLOTHHIP_INST_GROUP, everybody else declares.
 //   0 fp32 standard small   1 fp64 standard small   2 fp32 standard large   3 fp64 standard large   4 LEAN small (+ the relaxed-order companion)   5 LEAN large + fp64 LEAN   6, 7, 8 the grid-specialised builds (CLOTH_SPEC_A / _B / _C)
 #define CLOTHHIP_INST_GROUPS 9
-#define CLOTH_GROUP_0(M) CLOTH_VARIANTS_SMALL(M, float)
-#define CLOTH_GROUP_1(M) CLOTH_VARIANTS_SMALL(M, double)
-#define CLOTH_GROUP_2(M) CLOTH_VARIANTS_LARGE(M, float)
-#define CLOTH_GROUP_3(M) CLOTH_VARIANTS_LARGE(M, double)
+#define CLOTH_GROUP_0(M) CLOTH_VARIANTS_SMALL_F32(M)
+#define CLOTH_GROUP_1(M) CLOTH_VARIANTS_SMALL_F64(M)
+#define CLOTH_GROUP_2(M) CLOTH_VARIANTS_LARGE_F32(M)
+#define CLOTH_GROUP_3(M) CLOTH_VARIANTS_LARGE_F64(M)
 #define CLOTH_GROUP_4(M) CLOTH_VARIANTS_LEAN_SMALL(M, float)
 #define CLOTH_GROUP_5(M) CLOTH_VARIANTS_LEAN_LARGE(M, float) CLOTH_VARIANTS_LEAN64(M, double)
 #define CLOTH_RELAXED(KW) KW template __global__ void clothhip::k_run_schedule<float, 512, 2, 2, true, 3>(clothhip::StepArgs<float>);
@@ -73,4 +77,33 @@
 CLOTH_GROUP_0(CLOTH_DECL) CLOTH_GROUP_1(CLOTH_DECL) CLOTH_GROUP_2(CLOTH_DECL) CLOTH_GROUP_3(CLOTH_DECL) CLOTH_GROUP_4(CLOTH_DECL) CLOTH_GROUP_5(CLOTH_DECL)
 CLOTH_SPEC_F32(CLOTH_DECL_S) CLOTH_SPEC_F64(CLOTH_DECL_S)
 CLOTH_RELAXED(extern)
+
+namespace clothhip {
+// What a stepper launch runs: the variant (threads per cloth, particles per thread, table mode, rest lengths in registers) and its LDS
+// carve-up (clothhip_api.hip: plan_layouts). scratch_have / scratch_need: the LDS behind the hash table that the in-kernel metrics of
+// the episode launches borrow, and what they need.
+struct Layout { int nt, ppt, tab; bool rest_reg; int cell_copy, lds_bytes, HT, ht_bits, scratch_have, scratch_need; };
+
+// Every instantiation above as one row {sizeof(T), NT, PPT, TAB, REST_REG, NS, FUSED, kernel}: the only place the host names a kernel.
+struct StepperRow { int tsz, nt, ppt, tab; bool rest_reg; int ns, fused; const void *fn; };
+#define CLOTH_ROW(T, NT, PPT, TAB, RR, NS_, F) {(int)sizeof(T), NT, PPT, TAB, RR, NS_, F, (const void *)k_run_schedule<T, NT, PPT, TAB, RR, F, NS_>},
+#define CLOTH_ROWS_S(T, NT, PPT, TAB, RR, NS_) CLOTH_ROW(T, NT, PPT, TAB, RR, NS_, 0) CLOTH_ROW(T, NT, PPT, TAB, RR, NS_, 1) CLOTH_ROW(T, NT, PPT, TAB, RR, NS_, 2)
+#define CLOTH_ROWS(T, NT, PPT, TAB, RR) CLOTH_ROWS_S(T, NT, PPT, TAB, RR, 0)
+static const StepperRow STEPPER_ROWS[] = {
+    CLOTH_GROUP_0(CLOTH_ROWS) CLOTH_GROUP_1(CLOTH_ROWS) CLOTH_GROUP_2(CLOTH_ROWS) CLOTH_GROUP_3(CLOTH_ROWS) CLOTH_GROUP_4(CLOTH_ROWS) CLOTH_GROUP_5(CLOTH_ROWS)
+    CLOTH_SPEC_F32(CLOTH_ROWS_S) CLOTH_SPEC_F64(CLOTH_ROWS_S)
+    CLOTH_ROW(float, 512, 2, 2, true, 0, 3)    // the relaxed-order companion (CLOTH_RELAXED)
+};
+#undef CLOTH_ROWS
+#undef CLOTH_ROWS_S
+#undef CLOTH_ROW
+
+// The kernel that runs layout L in precision tsz (4 / 8) as the grid-specialised build NS = ns (0: the generic one) for FUSED = fused;
+// nullptr: not compiled.
+inline const void *find_stepper(int tsz, const Layout &L, int ns, int fused) {
+    for (const StepperRow &r : STEPPER_ROWS)
+        if (r.tsz == tsz && r.nt == L.nt && r.ppt == L.ppt && r.tab == L.tab && r.rest_reg == L.rest_reg && r.ns == ns && r.fused == fused) return r.fn;
+    return nullptr;
+}
+}  // namespace clothhip
 #endif
