@@ -140,7 +140,6 @@ inline WindowTable build_windows(const Topology &t, const LevelSchedule &L) {
         }
     }
     W.nW = w + 1;
-#ifndef CLOTHHIP_WINDOW_LEVEL_ORDER
     // Lane order inside a window (round 5): any linear extension of "an earlier spring that shares a particle comes first" serves the sweep
     // (its pass rule reads the dependency masks, not the lane numbers). Level order is one; this one is chosen for the LDS banks: the sweep
     // reads the two particle records of every lane (16-byte records: two particles whose indices agree mod 16 share their banks), sixteen lanes
@@ -183,7 +182,6 @@ inline WindowTable build_windows(const Topology &t, const LevelSchedule &L) {
             for (size_t q = 0; q < placed.size(); q++) W.slot_of[placed[q]] = ws * 64 + (int)q;
         }
     }
-#endif
 
     std::vector<int> last_win(t.P, 0);                            // window of the last spring incident to a point
     for (int s = 0; s < t.S; s++) {

@@ -107,11 +107,7 @@ __global__ __launch_bounds__(NT, v_waves_per_eu(NT, TAB, v_lean(TAB, REST_REG, (
     const WEnt<T> *wtab = reinterpret_cast<const WEnt<T> *>(smem + lay.wtab);    // TAB >= 1 only
     // rest length of the spring in window-table slot i (Hooke, pre-pass; the sweep streams its own)
     auto rest_at = [&](uint32_t i) -> T { return v_ldstab(TAB) ? wtab[i].rest : g_rest[i]; };
-#ifdef CLOTHHIP_FORCE_PM            // register-pressure bisection (dev): the phase mask as a compile-time constant
-    const int pm = CLOTHHIP_FORCE_PM;
-#else
     const int pm = NS > 0 ? (PH_HOOKE | PH_COLLIDE | PH_PLANE | PH_STRAIN) : A.phase_mask;     // (the specialised builds run every phase: debug masks take the generic build)
-#endif
 
     T pvx[PPT], pvy[PPT], pvz[PPT];         // previous positions of the owned particles
     // their incident-spring gather entries (static): in registers for fp32; the fp64 instantiation has no room
@@ -213,29 +209,15 @@ __global__ __launch_bounds__(NT, v_waves_per_eu(NT, TAB, v_lean(TAB, REST_REG, (
 #else
     constexpr bool SWEEP_TIMED = false;
 #endif
-#ifndef CLOTHHIP_SWEEP_LEAN
-#define CLOTHHIP_SWEEP_LEAN 1           // A/B: 0 = strain_sweep everywhere, 2 = the lean walk for fp32 only
-#endif
-#if !defined(CLOTHHIP_SWEEP_STAMPS) && !defined(CLOTHHIP_SWEEP_OUTER) && !defined(CLOTHHIP_CELL_COUNTERS)
-    constexpr bool SWEEP_LEAN = CLOTHHIP_SWEEP_LEAN != 0 && (CLOTHHIP_SWEEP_LEAN != 2 || sizeof(T) == 4);
+#if !defined(CLOTHHIP_SWEEP_STAMPS) && !defined(CLOTHHIP_CELL_COUNTERS)
+    constexpr bool SWEEP_LEAN = true;   // the production walk (strain_sweep_lean)
 #else
     constexpr bool SWEEP_LEAN = false;  // (the sweep-stamps and census builds instrument strain_sweep)
 #endif
-#ifndef CLOTHHIP_SWEEP_AHEAD_MIN_TAB
-#define CLOTHHIP_SWEEP_AHEAD_MIN_TAB 1      // TAB below this (the four-wave builds for three to six cloths per CU: 768 cloths 24.9 -> 25.2 M/s, 1 024: 31.4 -> 31.7, 1 280: +-0,
-                                            // 1 536: 33.8 -> 34.2): the lean walk without its read-ahead; the eight-wave headline build loses 2.8 % without it
-#endif
-    constexpr bool SWEEP_AHEAD = TAB >= CLOTHHIP_SWEEP_AHEAD_MIN_TAB;
-#ifndef CLOTHHIP_PRECHECK2_MAX_TAB
-#define CLOTHHIP_PRECHECK2_MAX_TAB -3       // TAB at or below this: the collision pre-check takes two members per trip instead of four (substep_collision.inc.hpp)
-#endif
+    // TAB below 1 (the four-wave builds for three to six cloths per CU: 768 cloths 24.9 -> 25.2 M/s, 1 024: 31.4 -> 31.7, 1 280: +-0,
+    // 1 536: 33.8 -> 34.2): the lean walk without its read-ahead; the eight-wave headline build loses 2.8 % without it
+    constexpr bool SWEEP_AHEAD = TAB >= 1;
     (void)SWEEP_AHEAD;
-#if defined(CLOTHHIP_SWEEP_MW) && !defined(CLOTHHIP_SWEEP_STAMPS) && !defined(CLOTHHIP_SWEEP_OUTER)
-    constexpr bool SWEEP_MW = true;     // A/B build (round 5): every wave of the cloth looks ahead one window each (strain_sweep_mw);
-                                        // bit-identical, measured -8 % on the headline workload: not the production path
-#else
-    constexpr bool SWEEP_MW = false;    // the one-wave walk (strain_sweep)
-#endif
 #if defined(CLOTHHIP_PHASE_STAMPS) || defined(CLOTHHIP_CELL_COUNTERS)   // the sweep's window / pass / correction counters cost its loop three instructions per pass:
     constexpr bool SWEEP_STATS = true;  // profiling builds only (the production build counts sweeps)
 #else
@@ -334,19 +316,16 @@ __global__ __launch_bounds__(NT, v_waves_per_eu(NT, TAB, v_lean(TAB, REST_REG, (
         };
         const T dz_up = uni((T)sc.dz_up), dxp = uni((T)sc.dx_pull), dyp = uni((T)sc.dy_pull), dzp = uni((T)sc.dz_pull);
         const bool sliced = FUSED && Fp->budget_ticks != 0 && Fp->resume != nullptr;
-#ifndef CLOTHHIP_UNIFORM_SCHED
-#define CLOTHHIP_UNIFORM_SCHED 1
-#endif
         // (round 6, from the ISA: the schedule's phase bounds and the loop counter are the same in every lane, but the compiler does not know --
         //  held in VGPRs they turned the "which phase is substep `it` in" ladder at the head of every substep and the loop's exit test into
         //  vector compares + exec-mask branches, ~40 cycles each, and occupied seven VGPRs across the whole loop: scalar from here on)
-        const int n_up_end_ = CLOTHHIP_UNIFORM_SCHED ? __builtin_amdgcn_readfirstlane(sc.n_up_end) : sc.n_up_end;
-        const int n_uprest_end_ = CLOTHHIP_UNIFORM_SCHED ? __builtin_amdgcn_readfirstlane(sc.n_uprest_end) : sc.n_uprest_end;
-        const int n_pull_end_ = CLOTHHIP_UNIFORM_SCHED ? __builtin_amdgcn_readfirstlane(sc.n_pull_end) : sc.n_pull_end;
-        const int n_griprest_end_ = CLOTHHIP_UNIFORM_SCHED ? __builtin_amdgcn_readfirstlane(sc.n_griprest_end) : sc.n_griprest_end;
-        const int n_total_ = CLOTHHIP_UNIFORM_SCHED ? __builtin_amdgcn_readfirstlane(sc.n_total) : sc.n_total;
-        const int break_on_tear_ = CLOTHHIP_UNIFORM_SCHED ? __builtin_amdgcn_readfirstlane(sc.break_on_tear) : sc.break_on_tear;
-        const int it0_ = CLOTHHIP_UNIFORM_SCHED ? __builtin_amdgcn_readfirstlane(resumed_run ? resume_it : 0) : (resumed_run ? resume_it : 0);
+        const int n_up_end_ = __builtin_amdgcn_readfirstlane(sc.n_up_end);
+        const int n_uprest_end_ = __builtin_amdgcn_readfirstlane(sc.n_uprest_end);
+        const int n_pull_end_ = __builtin_amdgcn_readfirstlane(sc.n_pull_end);
+        const int n_griprest_end_ = __builtin_amdgcn_readfirstlane(sc.n_griprest_end);
+        const int n_total_ = __builtin_amdgcn_readfirstlane(sc.n_total);
+        const int break_on_tear_ = __builtin_amdgcn_readfirstlane(sc.break_on_tear);
+        const int it0_ = __builtin_amdgcn_readfirstlane(resumed_run ? resume_it : 0);
     const int tid_outer_ = tid;
 #ifdef CLOTHHIP_CELL_COUNTERS
     bool frozen_prev_ = false; (void)frozen_prev_;

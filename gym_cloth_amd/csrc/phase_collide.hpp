@@ -38,11 +38,12 @@ __device__ __forceinline__ int collide_cell_wave(Pt<T> *cur, uint16_t *m, const 
     const T cfac = (T)1 + (T)2 / k.sim_steps;
     const T thr2c = thr2 * cfac * cfac;
     bool moved = false;
-#ifndef CLOTHHIP_SERIAL_HITSUM
     if constexpr (sizeof(T) == 4) {
         // fp32: the lane predicates of a visit as wave masks in scalar registers (one compare each; the conjunctions, "not the visited
         // member", "later than it" are scalar bit operations), the exact test without a branch around it (a big cell nearly always
-        // has a candidate), the selects straight from the masks. Same arithmetic per lane, same visiting order.
+        // has a candidate), the selects straight from the masks. Same arithmetic per lane, same visiting order. (Parity is a tolerance:
+        // the hits' contributions, zero in the other lanes, are summed by a DPP tree instead of one by one in ascending order -- the
+        // Gauss-Seidel visiting order is untouched, only the association of this one sum differs.)
         const unsigned long long inm = n >= 64 ? ~0ull : ((1ull << n) - 1ull);
         const unsigned long long freem = ballot64(free_);
         unsigned long long movedm = 0ull;
@@ -85,9 +86,7 @@ __device__ __forceinline__ int collide_cell_wave(Pt<T> *cur, uint16_t *m, const 
             todo |= ballot64(!(d2 > thr2c)) & freem & ~((2ull << a) - 1ull);            // a moved: later neighbours must look
         }
         moved = __builtin_amdgcn_inverse_ballot_w64(movedm);
-    } else
-#endif
-    {
+    } else {
     while (todo) {
 #if defined(CLOTHHIP_MUTATE) && CLOTHHIP_MUTATE == 2
         const bool mut2_ = visits_ == 0 && (todo & (todo - 1ull)) != 0ull;      // MUTANT 2 (see the fp32 loop above)
@@ -114,15 +113,6 @@ __device__ __forceinline__ int collide_cell_wave(Pt<T> *cur, uint16_t *m, const 
         if (!hm) continue;
         T tx = (T)0, ty = (T)0, tz = (T)0;
         int nh = 0;
-#ifndef CLOTHHIP_SERIAL_HITSUM
-        if constexpr (sizeof(T) == 4) {
-            // fp32 (parity is a tolerance): the hits' contributions (zero in the other lanes) summed by a DPP tree instead of one by
-            // one in ascending order -- the Gauss-Seidel visiting order is untouched, only the association of this one sum differs
-            tx = wave_sum_f32(fx); ty = wave_sum_f32(fy); tz = wave_sum_f32(fz);
-            nh = __builtin_popcount((uint32_t)hm) + __builtin_popcount((uint32_t)(hm >> 32));    // (two 32-bit counts: the 64-bit one reached
-                                                                                                   //  the float conversion as a 64-bit integer, seven instructions)
-        } else
-#endif
         while (hm) {                                                                    // ascending candidate order
             const int b = __builtin_amdgcn_readfirstlane(__ffsll((long long)hm) - 1);
             tx += bcast(fx, b); ty += bcast(fy, b); tz += bcast(fz, b);
@@ -201,12 +191,10 @@ __device__ __forceinline__ void collide_cells_group(Pt<T> *cur, uint16_t *memb, 
         if (!__any(hm != 0u)) continue;
         T tx = (T)0, ty = (T)0, tz = (T)0;
         int nh = 0;
-#ifndef CLOTHHIP_SERIAL_HITSUM
         if constexpr (sizeof(T) == 4 && GSZ == 16) {
             tx = row_allsum_f32(fx); ty = row_allsum_f32(fy); tz = row_allsum_f32(fz);      // (see collide_cell_wave)
             nh = __popc(hm);
         } else
-#endif
         while (__any(hm != 0u)) {               // ascending candidate order; four hits are fetched per LDS round trip
             bool has[4]; T vx[4], vy[4], vz[4];
 #pragma unroll

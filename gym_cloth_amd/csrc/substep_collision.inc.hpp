@@ -136,7 +136,6 @@
                 for (int q = 0; q < PPT; q++) hit[q] = false;
                 // (left to itself the compiler unrolls the member loops several times: fine at 256 VGPRs, 500 spilled registers at
                 //  the LEAN variant's 168 -- that variant gets its own copy of the loops, not unrolled)
-#ifndef CLOTHHIP_BISECT_NOPRECHECK
                 if constexpr (LEAN || (NT == 512 && PPT == 2)) {
                     // register-lean form (the builds with a VGPR cap: LEAN, eight waves per cloth): one owned particle after the other (a real branch each: a scheduling region of its own),
                     // the member loop not unrolled; the trip count is the wave's largest member count for THAT particle
@@ -153,8 +152,8 @@
                                 // a read past the cell's range (another cell's record or the padding behind the array) is masked out
                                 // by the member count; the trip base is clamped so that no read leaves the padded array
                                 // (round 5: four members per trip -- half the loop branches and LDS waits per member: +0.25 % at two cloths per
-                                //  CU; two per trip where the register cap is 80 (six per CU): 23 fewer spill reloads, +1.6 % at 1536 cloths)
-                                if constexpr (TAB > CLOTHHIP_PRECHECK2_MAX_TAB) {
+                                //  CU; two per trip where the register cap is 80 (six per CU: TAB -3): 23 fewer spill reloads, +1.6 % at 1536 cloths)
+                                if constexpr (TAB > -3) {
 #pragma unroll 1
                                 for (int b = 0; b < nq; b += 4) {
                                     const int base = cs_ + b < Ppad + 28 ? cs_ + b : Ppad + 28;
@@ -237,7 +236,6 @@
                         }
                     }
                 }
-#endif
 #pragma unroll
                 for (int q = 0; q < PPT; q++) {
                     if (hit[q]) {
@@ -281,11 +279,7 @@
                         const int n = (int)(co & 0xFFFFu);
                         uint16_t *m = memb + (int)(co >> 16);
                         if (n <= 64) {
-#ifndef CLOTHHIP_BISECT_NOWAVE
                             const int nv_ = collide_cell_wave<T>(cur, m, slot, n, k, lane);
-#else
-                            const int nv_ = 0;
-#endif
 #ifdef CLOTHHIP_CELL_COUNTERS
                             tph[4] += 64; tph[5] += 64 * n; tph[6] += 64 * (nv_ & 0xffff); tph[11] += 64 * (nv_ >> 16);
 #else
@@ -316,9 +310,7 @@
 #ifdef CLOTHHIP_CELL_COUNTERS
                         tph[8] += 64;
 #endif
-#ifndef CLOTHHIP_BISECT_NOGROUP
                         collide_cells_group<T, 16>(cur, memb, slot, hco, hs, k, lane);
-#endif
                     }
                     sbase += nsb;
 #ifdef CLOTHHIP_CELL_STAMPS

@@ -8,7 +8,7 @@
         //     (in window-table order) are kept: a spring untouched by earlier corrections of the sweep behaves exactly as
         //     evaluated here, so nothing before the first needs a look, and nothing behind the last unless a correction
         //     reaches it. No spring flagged: the sweep is skipped (a cloth at rest).
-        // (2) wave 0 walks the windows in between (strain_sweep above).
+        // (2) wave 0 walks the windows in between (phase_strain.hpp).
         if constexpr (RELAXED) {
             // Coloured order (NOT the reference's list order, cloth.pyx:258-296): the six springs a particle owns (to r-1, c-1, the two
             // diagonals, r-2, c-2) in two parity classes each -- twelve classes whose springs share no particle --, one class after the
@@ -149,41 +149,6 @@
 #ifdef CLOTHHIP_CELL_COUNTERS
             int swept_ = 0;
 #endif
-            if (SWEEP_MW) {
-                // every wave of the cloth takes part (strain_sweep_mw): the decision and the walk's bounds are read by all of them
-                // before the sweep's first barrier and reset by wave 0 behind its last
-                if (misc[1] || (pm & PH_NOSKIP)) {
-                    const bool all_ = (pm & PH_NOSKIP) != 0;
-                    const int w0 = __builtin_amdgcn_readfirstlane(all_ ? 0 : (misc[10] >> 6));
-                    const int w1 = __builtin_amdgcn_readfirstlane(all_ ? KA_NW(Ak_) - 1 : (misc[11] >> 6));
-                    const bool tic = __builtin_amdgcn_readfirstlane(!(k.tear_thresh < k.c11) ? 1 : 0) != 0;
-                    const int wave_ = __builtin_amdgcn_readfirstlane(tid >> 6);
-                    const int wl_ = (Ak_->Spad >> 6) - 1;                   // the table's last (padding, empty) window
-                    int *const sw_ = misc + 24, *const st_ = misc + 20;
-#ifdef CLOTHHIP_MW_PRIO
-                    __builtin_amdgcn_s_setprio(CLOTHHIP_MW_PRIO);
-#endif
-                    const int tear = tic ? strain_sweep_mw<T, v_ldstab(TAB), NT / 64, SWEEP_STATS, true>(cur, wtab, Ak_->wt_ent, g_rest, Ak_->wt_dep, w0, w1, wl_, KA_RSHIFT(Ak_), k, lane, wave_, sw_, st_)
-                                         : strain_sweep_mw<T, v_ldstab(TAB), NT / 64, SWEEP_STATS, false>(cur, wtab, Ak_->wt_ent, g_rest, Ak_->wt_dep, w0, w1, wl_, KA_RSHIFT(Ak_), k, lane, wave_, sw_, st_);
-#ifdef CLOTHHIP_MW_PRIO
-                    __builtin_amdgcn_s_setprio(0);
-#endif
-                    if (__any(tear) && lane == 0) misc[0] = 1;
-#ifdef CLOTHHIP_CELL_COUNTERS
-                    swept_ = 1;
-#endif
-                    if (tid == 0) {
-                        misc[15]++; misc[1] = 0; misc[10] = 0x7fffffff; misc[11] = -1;
-                        if (SWEEP_STATS) {
-                            st_passes += st_[0]; st_commits += st_[1]; st_windows += st_[2];
-#ifdef CLOTHHIP_MW_ROUNDS
-                            st_commits += st_[3] - st_[1]; st_[3] = 0;
-#endif
-                            st_[0] = 0; st_[1] = 0; st_[2] = 0;
-                        }
-                    }
-                }
-            } else
             if (tid < 64 && (misc[1] || (pm & PH_NOSKIP))) {
                 __builtin_amdgcn_s_setprio(3);            // the serial sweep is the critical path of the whole cloth
                 const bool all_ = (pm & PH_NOSKIP) != 0;
