@@ -7,6 +7,7 @@
 #include "../../include/clothhip.h"
 #include "cloth_rng.hpp"
 #include "cloth_tables.hpp"
+#include "stepper_traits.hpp"
 
 namespace clothhip {
 
@@ -264,9 +265,14 @@ template <typename T> using KArgsC = const __attribute__((address_space(4))) Ste
 // thickness of cfg/_json_files/default184.json:19). The host selects such a build only for a handle whose ClothParams equal these (spec_ns).
 struct SpecPhys { double width, height, density, ks, damping, thickness, plane_friction, tear_thresh, gravity, minimum_z; int frames_per_sec, simulation_steps; };
 constexpr SpecPhys spec_phys(int ns) { return SpecPhys{1.0, 1.0, 200.0, 10000.0, 2.0, ns == 50 ? 0.0095 : 0.02, 1.0, 2.0, -9.8, 0.0, 30, 30}; }
-// ... and the stepper's constants derived from them, by the very expressions (same doubles, same roundings) make_consts evaluates on the host
-template <typename T> constexpr DevConsts<T> spec_consts(int ns) {
-    const SpecPhys p = spec_phys(ns);
+// ... and the stepper's constants derived from physics parameters and grid side (cloth.pyx:178-180, :308-310): the ONE derivation -- the host
+// evaluates it at run time for the handle's ClothParams, a specialised build at compile time for spec_phys(NS); same doubles, same roundings
+constexpr bool operator==(const SpecPhys &a, const SpecPhys &b) {
+    return a.width == b.width && a.height == b.height && a.density == b.density && a.ks == b.ks && a.damping == b.damping && a.thickness == b.thickness &&
+           a.plane_friction == b.plane_friction && a.tear_thresh == b.tear_thresh && a.gravity == b.gravity && a.minimum_z == b.minimum_z &&
+           a.frames_per_sec == b.frames_per_sec && a.simulation_steps == b.simulation_steps;
+}
+template <typename T> constexpr DevConsts<T> make_consts(const SpecPhys &p, int ns) {
     const double dx = p.width * 1.0 / (ns - 1), dy = p.height * 1.0 / (ns - 1);
     const double mass = p.density / ns / ns;
     const double delta_t = 1.0 / p.frames_per_sec / p.simulation_steps;
@@ -286,6 +292,7 @@ template <typename T> constexpr DevConsts<T> spec_consts(int ns) {
     k.c11 = (T)1.1;
     return k;
 }
+template <typename T> constexpr DevConsts<T> spec_consts(int ns) { return make_consts<T>(spec_phys(ns), ns); }
 // the fp32 palette of the flat tiers' rest lengths at grid ns (cloth.pyx:117-146, :417: structural dx, shearing sqrt(dx^2 + dy^2), bending 2 dx,
 // rounded to float): what the LEAN arithmetic of a specialised fp32 build uses as literals; the host compares them with the palette it read
 // back from the device's rest table (spec_ns) -- a mismatch selects the generic build
@@ -314,24 +321,24 @@ template <typename T, int NS = 0> __device__ __forceinline__ DevConsts<T> load_c
 // count, hash-table size, window-table size, the whole LDS carve-up, "all phases on", whether the cell-ordered copy exists -- so none of it occupies
 // registers across the substep loop (the generic build holds ~30 loop-invariant VGPRs of LDS base addresses and constants: headline +1.9 %, the
 // six-per-CU build +3.3 %). NS = 0 is the generic build (any grid, debug phase masks). The host picks the specialised kernel only when every constant
-// below equals what it computed for the handle (clothhip_api.hip::spec_ok); the names are used inside the kernel body, where NS and TAB are in scope.
+// below equals what it computed for the handle (clothhip_api.hip::spec_ns); the names are used inside the kernel body, where NS and the Variant V are in scope.
 constexpr int spec_p(int ns) { return ns * ns; }
 constexpr int spec_ppad(int ns) { return (ns * ns + 63) / 64 * 64; }
-// hash-table slots: the smallest power of two above 1.5 P -- except the two-cloths-per-CU layout of 50x50 (TAB 4), whose table is sized to the LDS left
-constexpr int spec_ht(int ns, int tab) { if (ns == 50 && tab == 4) return 2880; int h = 64; while (h <= ns * ns + ns * ns / 2) h <<= 1; return h; }
-constexpr int spec_htbits(int ns, int tab) { if (ns == 50 && tab == 4) return 0; int b = 0; while ((1 << b) < spec_ht(ns, tab)) b++; return b; }
+// hash-table slots: the smallest power of two above 1.5 P -- except the two-cloths-per-CU layout of 50x50, whose table is sized to the LDS left
+constexpr int spec_ht(int ns, Variant v) { if (ns == 50 && v.spec_ht_fitted()) return 2880; int h = 64; while (h <= ns * ns + ns * ns / 2) h <<= 1; return h; }
+constexpr int spec_htbits(int ns, Variant v) { if (ns == 50 && v.spec_ht_fitted()) return 0; int b = 0; while ((1 << b) < spec_ht(ns, v)) b++; return b; }
 constexpr int spec_nw(int ns) { return ns == 25 ? 55 : (ns == 50 ? 227 : 0); }             // windows of the strain sweep's table (cloth_tables.hpp)
 constexpr int spec_spad(int ns) { return ns == 25 ? 3776 : (ns == 50 ? 14976 : 0); }       // its slots incl. padding
 constexpr int spec_rshift(int ns) { return ns == 50 ? 2 : 0; }                             // unit of the entries' reach field
 // the cell-ordered record copy: every specialised 25x25 layout but the LEAN builds for five / six cloths per CU has it; 50x50 at two per CU has not
-constexpr int spec_cell_copy(int ns, int tab) { return ns == 25 ? (tab > -2 ? 1 : 0) : 0; }
+constexpr int spec_cell_copy(int ns, Variant v) { return ns == 25 ? (v.spec_has_cell_copy() ? 1 : 0) : 0; }
 #define KA_N(p_) (NS > 0 ? NS : (p_)->N)
-#define KA_HTBITS(p_) (NS > 0 ? spec_htbits(NS, TAB) : (p_)->ht_bits)
+#define KA_HTBITS(p_) (NS > 0 ? spec_htbits(NS, V) : (p_)->ht_bits)
 #define KA_NW(p_) (NS > 0 ? spec_nw(NS) : (p_)->nW)
 #define KA_SPAD(p_) (NS > 0 ? spec_spad(NS) : (p_)->Spad)
 #define KA_RSHIFT(p_) (NS > 0 ? spec_rshift(NS) : (p_)->wt_rshift)
-#define KA_CELLCOPY(p_) (NS > 0 ? spec_cell_copy(NS, TAB) : (p_)->cell_copy)
-#define CLOTH_PHASE_DIMS() const int P = NS > 0 ? spec_p(NS) : Ak_->P, Ppad = NS > 0 ? spec_ppad(NS) : Ak_->Ppad, HT = NS > 0 ? spec_ht(NS, TAB) : Ak_->HT;
+#define KA_CELLCOPY(p_) (NS > 0 ? spec_cell_copy(NS, V) : (p_)->cell_copy)
+#define CLOTH_PHASE_DIMS() const int P = NS > 0 ? spec_p(NS) : Ak_->P, Ppad = NS > 0 ? spec_ppad(NS) : Ak_->Ppad, HT = NS > 0 ? spec_ht(NS, V) : Ak_->HT;
 #define CLOTH_PHASE_ARGS()                                                        \
     asm volatile("" : "+s"(Ak_));                                                 \
     const DevConsts<T> k = load_consts<T, NS>(Ak_);                               \
@@ -342,7 +349,7 @@ constexpr int EPSTATE_LDS_BYTES = 240;
 static_assert(sizeof(EpState) <= EPSTATE_LDS_BYTES, "EpState outgrew its LDS slot (LdsLayout::eps): the window table / hash region follows it");
 static_assert(WT_IDX_BITS == 12 && HK_NBR_MASK == WT_IDX_MASK, "point indices are 12 bits in the gather entries and in the window table alike");
 // LDS carve-up (dynamic shared memory), all offsets in bytes, 16-byte aligned.
-// tab: 0 = the window table stays in global memory (L2), 1 = table + rest lengths resident in LDS
+// table: LDS_TABLE_NONE = the window table stays in global memory (L2), LDS_TABLE = table + rest lengths resident in LDS
 #if defined(CLOTHHIP_PHASE_STAMPS) || defined(CLOTHHIP_CELL_COUNTERS) || defined(CLOTHHIP_SWEEP_STAMPS)
 #define CLOTHHIP_TPH_LDS 1
 #endif
@@ -350,16 +357,16 @@ struct LdsLayout {
     int lkey;        // census build: every particle's cell key of the previous substep
     int tphs;        // profiling / census builds: their twelve 64-bit accumulators (in front of the region the in-kernel metrics borrow)
     int cur, eps, wtab, pslot, lstc, hkey, hco, memb, slot, misc, alist, olist, cpos, total;
-    // tab 2 (the eight-wave LEAN build): like 1, plus the table slots of every particle's six own springs (u16 [6][Ppad]): the strain
+    // LDS_TABLE_SLOTS (the eight-wave LEAN build): like LDS_TABLE, plus the table slots of every particle's six own springs (u16 [6][Ppad]): the strain
     // pre-pass of the LEAN arithmetic needs the slot of a flagged spring, and read it from the L2-resident gather table otherwise
     // lst 1 (the fp64 LEAN build): the per-particle stencil constants (StepArgs::lstc, 16 bytes each) resident in LDS
-    __host__ __device__ LdsLayout(int tsz, int Ppad, int Spad, int HT, int tab, int cp, int lst = 0) {
+    __host__ __device__ LdsLayout(int tsz, int Ppad, int Spad, int HT, int table, int cp, int lst) {
         int o = 0;
         auto take = [&](int bytes) { int r = o; o += (bytes + 15) / 16 * 16; return r; };
         cur = take(4 * Ppad * tsz);
         eps = take(EPSTATE_LDS_BYTES);   // EpState (fused episodes)
-        wtab = take(tab >= 1 ? Spad * (tsz == 8 ? 16 : 8) : 0);   // WEnt<T>[Spad]
-        pslot = take(tab == 2 ? (HK_SLOTS / 2) * Ppad * 2 : 0);
+        wtab = take(table != LDS_TABLE_NONE ? Spad * (tsz == 8 ? 16 : 8) : 0);   // WEnt<T>[Spad]
+        pslot = take(table == LDS_TABLE_SLOTS ? (HK_SLOTS / 2) * Ppad * 2 : 0);
         lstc = take(lst ? Ppad * 16 : 0);
 #ifdef CLOTHHIP_TPH_LDS
         tphs = take(96);
@@ -383,6 +390,10 @@ struct LdsLayout {
         total = o;
     }
 };
+// the carve-up of variant v: the one place a Variant becomes an LdsLayout (kernel, and the host's plan: clothhip_api.hip)
+__host__ __device__ __forceinline__ LdsLayout lds_layout(Variant v, int Ppad, int Spad, int HT, int cell_copy) {
+    return LdsLayout(v.tsz, Ppad, Spad, HT, v.lds_table_mode(), cell_copy, v.lean64() ? 1 : 0);
+}
 
 // Accumulators of the profiling / census builds (per-phase cycles, counters): in LDS, written by thread 0 alone -- as twelve 64-bit
 // registers per wave they cost the VGPR-capped variants two dozen SGPRs and turned the profile into one of the spills they caused.

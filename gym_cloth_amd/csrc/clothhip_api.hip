@@ -42,9 +42,13 @@ static int fail(int code, const char *fmt, ...) {
     } while (0)
 
 
-// LDS scratch of metrics_block (cloth_kernels.hpp): two sort buffers of NS values in the handle's precision, 64 doubles, NH u16 hull indices
-static inline int metrics_scratch_bytes(int NS, int NH, int tsz, bool hull_idx = false) {
-    return hull_idx ? 2 * NS * tsz + 64 * 8 + ((2 * NH + 15) / 16) * 16 : 2 * NS * tsz + (2 * NH + 64) * 8;
+// metrics_block (cloth_metrics.hpp) for a grid of P points: it sorts NS values (the next power of two >= P) and its hull's monotone chain holds
+// at most m + 1 <= P + 1 points (NH)
+struct MetricsDims { int NS, NH; };
+static inline MetricsDims metrics_dims(int P, int Ppad) { int n = 1; while (n < P) n <<= 1; return {n, Ppad + 8}; }
+// ... and its LDS scratch: two sort buffers of NS values in the handle's precision, 64 doubles, the hull stack (NH points, or NH u16 indices)
+static inline int metrics_scratch_bytes(MetricsDims d, int tsz, bool hull_idx) {
+    return hull_idx ? 2 * d.NS * tsz + 64 * 8 + ((2 * d.NH + 15) / 16) * 16 : 2 * d.NS * tsz + (2 * d.NH + 64) * 8;
 }
 
 // Every CLOTHHIP_DEBUG_* switch, read here and nowhere else. The planning switches are read when a handle is created
@@ -52,7 +56,7 @@ static inline int metrics_scratch_bytes(int NS, int NH, int tsz, bool hull_idx =
 struct DebugKnobs {
     bool w8_off = false;         // W8=0: the four-wave standard builds of the 25x25 class (only the value 0 switches)
     bool nt1024 = false;         // NT1024 (set at all): 1024 x 3 instead of 512 x 5 for the grids of 769 .. 2 560 points
-    int tab_lds = INT_MAX;       // TAB_LDS: caps the window-table mode
+    int tab_lds = INT_MAX;       // TAB_LDS: caps the standard layout's TAB code (TAB_STREAM < TAB_LDS)
     bool rest_reg = true;        // REST_REG=0: no rest lengths in registers
     bool cell_copy = true;       // CELL_COPY=0: no cell-ordered record copy (the switch can only turn it off)
     bool lean_set = false;       // LEAN: 0 never the LEAN arithmetic, 8 (or 2) its eight-wave build, 3 (or 1) / 4 / 5 / 6 its build for that
@@ -109,7 +113,7 @@ struct clothhip_handle {
     bool have_variant = false;
     int n_cus = 0;
     // the two layouts a handle may run (plan_layouts) and which one runs now (lean_refresh)
-    Layout lay_std = {256, 3, 0, false, 0, 0, 0, 0, 0, 0}, lay_lean = {256, 3, 0, true, 0, 0, 0, 0, 0, 0};
+    Layout lay_std = {Variant{8, 256, 3, TAB_STREAM, false}, 0, 0, 0, 0, 0, 0}, lay_lean = {Variant{8, 256, 3, TAB_STREAM, true}, 0, 0, 0, 0, 0, 0};
     bool on_lean = false;
     const Layout &lay() const { return on_lean ? lay_lean : lay_std; }
     struct OccKey { const void *fn; int lds; int occ; } occ_cache[8] = {};   // hipOccupancyMaxActiveBlocksPerMultiprocessor per (kernel, LDS bytes)
@@ -129,9 +133,13 @@ struct clothhip_handle {
     size_t cap_fact = 0, cap_frec = 0, cap_fobs = 0, cap_fscr = 0, cap_frst = 0, cap_frobs = 0, cap_fparg = 0;
     Topology topo;
     WindowTable wt;
+    std::vector<uint32_t> gather;       // the gather table (host copy of d_gather): the LEAN stencil checks read it
     std::vector<unsigned char> stage;   // host staging for layout conversion
     std::vector<double> flat_rest;
 };
+
+// f(float{}) or f(double{}) by the handle's precision: a launch that exists in both precisions is written once, as a generic lambda
+template <typename F> static auto by_precision(const clothhip_handle *h, F &&f) { return h->precision == CLOTHHIP_F64 ? f(double{}) : f(float{}); }
 
 extern "C" const char *clothhip_last_error(void) { return g_err.c_str(); }
 extern "C" int clothhip_abi_version(void) { return CLOTHHIP_ABI_VERSION; }
@@ -210,26 +218,9 @@ extern "C" int clothhip_selftest_windows(const ClothParams *p, int32_t *n_window
     return 0;
 }
 
-template <typename T> static DevConsts<T> make_consts(const ClothParams &p) {
-    const int N = p.n_side;
-    const double dx = p.width * 1.0 / (N - 1), dy = p.height * 1.0 / (N - 1);
-    const double mass = p.density / N / N;                              // cloth.pyx:178
-    const double delta_t = 1.0 / p.frames_per_sec / p.simulation_steps; // :180
-    const double w = 3 * dx, h = 3 * dy, t = (w > h) ? w : h;           // :308-310
-    DevConsts<T> k;
-    k.mg = (T)(mass * p.gravity);
-    k.ks_str = (T)(p.ks * 1.0); k.ks_bend = (T)(p.ks * 0.2);
-    k.dsm = (T)((delta_t * delta_t) / mass);
-    k.damp = (T)(1.0 - p.damping / 100.0);
-    k.cw = (T)w; k.ch = (T)h; k.ct = (T)t;
-    k.thresh = (T)(2.0 * p.thickness);
-    k.sim_steps = (T)p.simulation_steps;
-    k.min_z = (T)p.minimum_z;
-    k.surf_off = (T)0.0001;
-    k.one_m_fric = (T)(1. - p.plane_friction);
-    k.tear_thresh = (T)p.tear_thresh;
-    k.c11 = (T)1.1;
-    return k;
+// the physics parameters of a handle in the form the one derivation of the stepper's constants takes (cloth_common.hpp: make_consts)
+static SpecPhys phys_of(const ClothParams &p) {
+    return SpecPhys{p.width, p.height, p.density, p.ks, p.damping, p.thickness, p.plane_friction, p.tear_thresh, p.gravity, p.minimum_z, p.frames_per_sec, p.simulation_steps};
 }
 
 static void free_handle(clothhip_handle *h) {
@@ -250,11 +241,9 @@ static int spec_ns(const clothhip_handle *h, const Layout &L, bool with_palette 
 // The LDS a layout leaves the in-kernel metrics (from the hash table to the end of the allocation) against what they need; the
 // allocation is padded behind the layout's end when that fits the budget (the kernel addresses LDS by the layout's offsets: bytes
 // behind `total` are free). False: the episode launches cannot run on this layout.
-static bool fit_scratch(Layout &L, int tsz, int Ppad, int Spad, int P, int budget) {
-    int NS = 1; while (NS < P) NS <<= 1;
-    const int lst = (tsz == 8 && v_lean(L.tab, L.rest_reg, tsz)) ? 1 : 0;
-    const LdsLayout lay(tsz, Ppad, Spad, L.HT, L.tab == 2 ? 2 : (v_ldstab(L.tab) ? 1 : 0), L.cell_copy, lst);
-    L.scratch_need = metrics_scratch_bytes(NS, Ppad + 8, tsz, v_hull_idx(L.tab, tsz, L.nt, L.ppt));
+static bool fit_scratch(const clothhip_handle *h, Layout &L, int budget) {
+    const LdsLayout lay = lds_layout(L.v, h->Ppad, h->Spad, L.HT, L.cell_copy);
+    L.scratch_need = metrics_scratch_bytes(metrics_dims(h->P, h->Ppad), L.v.tsz, L.v.hull_as_indices());
     if (L.lds_bytes < lay.total) L.lds_bytes = lay.total;
     if (L.lds_bytes - lay.hkey < L.scratch_need && lay.hkey + L.scratch_need <= budget) L.lds_bytes = (lay.hkey + L.scratch_need + 15) / 16 * 16;
     L.scratch_have = L.lds_bytes - lay.hkey;
@@ -267,15 +256,27 @@ static constexpr int LDS_GRANULE = 1280;
 static constexpr int lds_budget(int r) { return (128 / (r < 1 ? 1 : r)) * LDS_GRANULE; }
 static_assert(lds_budget(1) == 160 * 1024 && lds_budget(2) == 80 * 1024 && lds_budget(4) == 40 * 1024, "granule arithmetic");
 
-// A layout of variant (nt, ppt, tab, rest_reg) with a hash table of HT (a power of two) slots: the cell-ordered record copy for the collision
+// A layout of variant v with a hash table of HT (a power of two) slots: the cell-ordered record copy for the collision
 // pre-check is taken only if the layout with it fits `budget` (and CLOTHHIP_DEBUG_CELL_COPY allows it). The scratch of the in-kernel
 // metrics is the caller's (fit_scratch).
-static Layout make_layout(const clothhip_handle *h, int nt, int ppt, int tab, bool rest_reg, int HT, int budget) {
-    const int tsz = (int)h->tsz, ltab = tab == 2 ? 2 : (v_ldstab(tab) ? 1 : 0), lst = (tsz == 8 && v_lean(tab, rest_reg, tsz)) ? 1 : 0;
-    const int cc = h->dbg.cell_copy && LdsLayout(tsz, h->Ppad, h->Spad, HT, ltab, 1, lst).total <= budget ? 1 : 0;
+static Layout make_layout(const clothhip_handle *h, Variant v, int HT, int budget) {
+    const int cc = h->dbg.cell_copy && lds_layout(v, h->Ppad, h->Spad, HT, 1).total <= budget ? 1 : 0;
     int ht_bits = 0;
     while ((1 << ht_bits) < HT) ht_bits++;
-    return {nt, ppt, tab, rest_reg, cc, LdsLayout(tsz, h->Ppad, h->Spad, HT, ltab, cc, lst).total, HT, ht_bits, 0, 0};
+    return {v, cc, lds_layout(v, h->Ppad, h->Spad, HT, cc).total, HT, ht_bits, 0, 0};
+}
+
+// For particle i: body(k, g) for each stencil position k that exists (lean_valid_mask), g = the particle's slot-th gather entry, slot = how
+// many positions below k exist (the gather table is compacted). Stops when body returns false (-1); else the number of entries visited.
+template <typename F> static int walk_stencil(const clothhip_handle *h, int i, F &&body) {
+    const uint32_t vm = lean_valid_mask(i / h->N, i % h->N, h->N);
+    int slot = 0;
+    for (int k = 0; k < HK_SLOTS; k++) {
+        if (!((vm >> k) & 1u)) continue;
+        if (!body(k, h->gather[(size_t)slot * h->Ppad + i])) return -1;
+        slot++;
+    }
+    return slot;
 }
 
 // Which stepper variants and which LDS layouts a handle runs: pure host logic (no HIP call), so that the CPU test suite can sweep it
@@ -283,7 +284,7 @@ static Layout make_layout(const clothhip_handle *h, int nt, int ppt, int tab, bo
 // lay_lean, lean and lean_r.
 // max_r: the highest residency the pick may choose (clothhip_create lowers it when the device's occupancy query grants the chosen LEAN
 // build fewer workgroups per CU than it was planned for).
-static void plan_layouts(clothhip_handle *h, int cus, const std::vector<uint32_t> &gather, int max_r = 6) {
+static void plan_layouts(clothhip_handle *h, int cus, int max_r = 6) {
     const DebugKnobs &dbg = h->dbg;
     const int tsz = (int)h->tsz, precision = h->precision;
     // threads per cloth x particles per thread (compile-time variants of the stepper)
@@ -301,8 +302,9 @@ static void plan_layouts(clothhip_handle *h, int cus, const std::vector<uint32_t
     // as long as TWO cloths still fit per CU (512 cloths = 2 per CU on the 256 CUs of an MI355X).
     // 256-thread variants: two cloths per CU (<= 80 KiB each); the larger ones own the CU (<= 160 KiB)
     const int budget = small_grid ? lds_budget(2) : lds_budget(1);
-    const int tab = std::min((nt <= 512 && LdsLayout(tsz, h->Ppad, h->Spad, HT, 1, 0).total <= budget) ? 1 : 0, dbg.tab_lds);
-    const bool rest_reg = nt == 256 && precision == CLOTHHIP_F32 && tab == 1 && dbg.rest_reg;
+    Variant vstd{tsz, nt, ppt, TAB_LDS, false};
+    vstd.tab = std::min((nt <= 512 && lds_layout(vstd, h->Ppad, h->Spad, HT, 0).total <= budget) ? TAB_LDS : TAB_STREAM, dbg.tab_lds);
+    vstd.rest_reg = nt == 256 && precision == CLOTHHIP_F32 && vstd.table_in_lds() && dbg.rest_reg;
     // LEAN variants: three to six cloths per CU instead of two, each stepping at a lower rate (lean_rates.hpp, measured by
     // tools/measure_pick_table.py). A launch runs its cloths in generations of what is resident, so the batch size decides:
     // the largest rate_r / ceil(E / (r * CUs)) wins.
@@ -318,7 +320,7 @@ static void plan_layouts(clothhip_handle *h, int cus, const std::vector<uint32_t
         double best = 0.0; int best_r = 2;
         for (int r = 2; r <= std::max(2, std::min(6, max_r)); r++) {
             // (r >= 3: the four-wave LEAN layout, table streamed, must fit r times in the CU's LDS -- 27x27 does not at five per CU)
-            if (r >= 3 && (!lean_able || LdsLayout(tsz, h->Ppad, h->Spad, HT, 0, 0).total > lds_budget(r))) continue;
+            if (r >= 3 && (!lean_able || lds_layout(lean_four_wave(r), h->Ppad, h->Spad, HT, 0).total > lds_budget(r))) continue;
             const double v = rate[r - 2] / (double)((h->E + r * cus - 1) / (r * cus));
             if (v > best * 1.02) { best = v; best_r = r; }
         }
@@ -340,59 +342,69 @@ static void plan_layouts(clothhip_handle *h, int cus, const std::vector<uint32_t
         // the arithmetic stencil of the LEAN kernel against the gather table built from the reference's spring list
         h->lean_stencil_ok = true;
         for (int i = 0; i < h->P && h->lean_stencil_ok; i++) {
-            const uint32_t vm = lean_valid_mask(i / h->N, i % h->N, h->N);
-            int slot = 0;
-            for (int k = 0; k < HK_SLOTS; k++) {
-                if (!((vm >> k) & 1u)) continue;
-                const int off[12] = {-h->N, -1, -h->N - 1, -h->N + 1, -2 * h->N, -2, 1, 2, h->N - 1, h->N, h->N + 1, 2 * h->N};
-                const uint32_t want = (uint32_t)(i + off[k]) | HK_VALID | (k < HK_SLOTS / 2 ? HK_ASB : 0u) | (lean_bend(k) ? HK_BEND : 0u);
-                const uint32_t g = gather[(size_t)slot * h->Ppad + i];
+            const int n = walk_stencil(h, i, [&](int k, uint32_t g) {
+                const uint32_t want = (uint32_t)(i + lean_off(k, h->N)) | HK_VALID | (k < HK_SLOTS / 2 ? HK_ASB : 0u) | (lean_bend(k) ? HK_BEND : 0u);
                 const uint32_t have = g & (HK_NBR_MASK | HK_VALID | HK_ASB | HK_BEND);
                 const int sp = h->wt.spring_at[(g >> HK_POS_SHIFT) & HK_POS_MASK];
                 const int ty = sp >= 0 ? h->topo.type[sp] : -1;
                 const int want_ty = lean_bend(k) ? SPRING_BENDING : (lean_shear(k) ? SPRING_SHEARING : SPRING_STRUCTURAL);
-                if (have != want || ty != want_ty) h->lean_stencil_ok = false;
-                slot++;
-            }
-            if (slot < HK_SLOTS && h->lean_stencil_ok && (gather[(size_t)slot * h->Ppad + i] & HK_VALID)) h->lean_stencil_ok = false;
+                return have == want && ty == want_ty;
+            });
+            // (and the entry behind the last one the stencil has must be empty)
+            if (n < 0 || (n < HK_SLOTS && (h->gather[(size_t)n * h->Ppad + i] & HK_VALID))) h->lean_stencil_ok = false;
         }
         if (!h->lean_stencil_ok) h->lean = false;
     }
     // the cell-ordered record copy for the collision pre-check is taken only if it does not cost the table its place
-    h->lay_std = make_layout(h, nt, ppt, tab, rest_reg, HT, budget);
+    h->lay_std = make_layout(h, vstd, HT, budget);
     // the in-kernel metrics of the episode launches borrow the LDS from the hash table on (the window table in front of it stays
     // resident). With the table in LDS but no room for the cell-ordered copy that region can be too small (fp64 21, 22, 30-32;
     // fp32 41-43): the allocation is then padded behind the layout's end, or, if the budget forbids that, the table leaves LDS
-    if (!fit_scratch(h->lay_std, tsz, h->Ppad, h->Spad, h->P, budget) && tab == 1) {
-        h->lay_std = make_layout(h, nt, ppt, 0, false, HT, budget);
-        fit_scratch(h->lay_std, tsz, h->Ppad, h->Spad, h->P, budget);
+    if (!fit_scratch(h, h->lay_std, budget) && vstd.table_in_lds()) {
+        h->lay_std = make_layout(h, Variant{tsz, nt, ppt, TAB_STREAM, false}, HT, budget);
+        fit_scratch(h, h->lay_std, budget);
     }
     if (!h->lean) return;
-    if (precision == CLOTHHIP_F64) {                     // fp64 LEAN: table streamed (TAB 0), the stencil constants in LDS
-        h->lay_lean = make_layout(h, 512, 2, 0, true, HT, lds_budget(2));
+    if (precision == CLOTHHIP_F64) {                     // fp64 LEAN: table streamed, the stencil constants in LDS
+        h->lay_lean = make_layout(h, Variant{tsz, 512, 2, TAB_STREAM, true}, HT, lds_budget(2));
         if (h->lay_lean.lds_bytes > lds_budget(2)) h->lean = false;
     } else if (h->lean_r == 2 && small_grid) {           // eight waves per cloth, two cloths per CU: the standard variant's LDS budget
-        h->lay_lean = make_layout(h, 512, 2, 2, true, HT, 80 * 1024);
+        h->lay_lean = make_layout(h, Variant{tsz, 512, 2, TAB_LDS_SLOTS, true}, HT, 80 * 1024);
         if (h->lay_lean.lds_bytes > 80 * 1024 || h->P > 1024) h->lean = false;      // (the table must fit beside a second cloth)
     } else if (h->lean_r == 1) {                         // the whole CU: same LDS budget as the standard variant of these grids
-        h->lay_lean = make_layout(h, 1024, h->P <= 3072 ? 3 : 4, 3, true, HT, 160 * 1024);
+        h->lay_lean = make_layout(h, Variant{tsz, 1024, h->P <= 3072 ? 3 : 4, TAB_LARGE_1, true}, HT, 160 * 1024);
         // TWO large-grid cloths per CU (eight waves each, 128 VGPRs) when the batch has more cloths than the device has CUs and it
         // pays by the measured rates: <= 80 KB of LDS per cloth -- no cell-ordered copy, and a hash table of just enough slots
         // (not a power of two: > P, so that a free slot always exists, and large enough that the in-kernel metrics' scratch fits)
-        int NSb = 1; while (NSb < h->P) NSb <<= 1;
+        const Variant v2{tsz, 512, 5, TAB_LARGE_2, true};
+        const int need2 = metrics_scratch_bytes(metrics_dims(h->P, h->Ppad), tsz, v2.hull_as_indices());
         int ht2 = (h->P / 64 + 2) * 64;
-        while (LdsLayout(tsz, h->Ppad, h->Spad, ht2, 0, 0).total - LdsLayout(tsz, h->Ppad, h->Spad, ht2, 0, 0).hkey < metrics_scratch_bytes(NSb, h->Ppad + 8, tsz, true)) ht2 += 64;
-        const int lds2 = LdsLayout(tsz, h->Ppad, h->Spad, ht2, 0, 0).total;
+        auto lay2 = [&]() { return lds_layout(v2, h->Ppad, h->Spad, ht2, 0); };
+        while (lay2().total - lay2().hkey < need2) ht2 += 64;
+        const int lds2 = lay2().total;
         const int gens1 = (h->E + h->n_cus - 1) / h->n_cus, gens2 = (h->E + 2 * h->n_cus - 1) / (2 * h->n_cus);
         const bool fits2 = h->P <= 2560 && lds2 <= 80 * 1024;
         if (dbg.large2_set ? dbg.large2 && fits2 : fits2 && LEAN_RATE_LARGE_2_PER_CU / gens2 > 1.02 / gens1) {
-            h->lay_lean = {512, 5, 4, true, 0, lds2, ht2, 0, 0, 0}; h->lean_r = 2;
+            h->lay_lean = {v2, 0, lds2, ht2, 0, 0, 0}; h->lean_r = 2;
         }
     } else {                                             // the four-wave LEAN builds, window table streamed from L2, 33 KB of LDS
-        h->lay_lean = make_layout(h, 256, 3, h->lean_r >= 4 ? 3 - h->lean_r : 0, true, HT, lds_budget(h->lean_r));
+        h->lay_lean = make_layout(h, lean_four_wave(h->lean_r), HT, lds_budget(h->lean_r));
     }
     // the in-kernel metrics borrow the region behind the hash table (clothhip_fused_supported): it must hold them here too
-    if (!fit_scratch(h->lay_lean, tsz, h->Ppad, h->Spad, h->P, lds_budget(h->lean_r))) h->lean = false;
+    if (!fit_scratch(h, h->lay_lean, lds_budget(h->lean_r))) h->lean = false;
+}
+
+// The host fields of a handle -- grid, topology, window and gather tables, debug switches: nothing here touches a device (clothhip_create,
+// and clothhip_selftest_layout, which plans on a handle that has nothing else)
+static void init_host_fields(clothhip_handle *h, const ClothParams &p, int n_envs, int precision) {
+    h->prm = p; h->E = n_envs; h->precision = precision;
+    h->N = p.n_side; h->P = h->N * h->N; h->Ppad = (h->P + 63) / 64 * 64;
+    h->tsz = precision == CLOTHHIP_F64 ? 8 : 4;
+    h->topo = build_topology(h->N);
+    h->wt = build_windows(h->topo, build_levels(h->topo));
+    h->S = h->topo.S; h->Spad = h->wt.n_slots;               // rest-length arrays are kept in window-table slot order
+    h->dbg = read_debug_knobs();
+    h->gather = build_gather(h->topo, h->wt, h->Ppad);
 }
 
 extern "C" int clothhip_create(const ClothParams *params, int32_t n_envs, int32_t device, int32_t precision,
@@ -408,14 +420,8 @@ extern "C" int clothhip_create(const ClothParams *params, int32_t n_envs, int32_
     HIPCHECK(hipSetDevice(device));
     clothhip_handle *h = new (std::nothrow) clothhip_handle();
     if (!h) return fail(CLOTHHIP_ENOMEM, "out of host memory");
-    h->prm = *params; h->E = n_envs; h->device = device; h->precision = precision;
-    h->N = params->n_side; h->P = h->N * h->N; h->Ppad = (h->P + 63) / 64 * 64;
-    h->tsz = precision == CLOTHHIP_F64 ? 8 : 4;
-    h->topo = build_topology(h->N);
-    h->wt = build_windows(h->topo, build_levels(h->topo));
-    h->S = h->topo.S; h->Spad = h->wt.n_slots;               // rest-length arrays are kept in window-table slot order
-    h->dbg = read_debug_knobs();
-    std::vector<uint32_t> gather = build_gather(h->topo, h->wt, h->Ppad);
+    h->device = device;
+    init_host_fields(h, *params, n_envs, precision);
     std::vector<double> levels = build_grab_levels(params->height, params->thickness);
     h->n_grab_levels = (int)levels.size();
 
@@ -445,7 +451,7 @@ extern "C" int clothhip_create(const ClothParams *params, int32_t n_envs, int32_
     HC(hipMemset(h->d_stats, 0, E * 64));
     HC(hipMalloc(&h->d_sched, E * sizeof(ClothSchedule)));
     HC(hipHostMalloc((void **)&h->h_sched, E * sizeof(ClothSchedule), hipHostMallocDefault));
-    HC(hipMalloc(&h->d_gather, gather.size() * 4));
+    HC(hipMalloc(&h->d_gather, h->gather.size() * 4));
     HC(hipMalloc(&h->d_wt_ent, (size_t)h->Spad * 4));
     HC(hipMalloc(&h->d_wt_dep, (size_t)h->Spad * 8));
     HC(hipMalloc(&h->d_lstc, (size_t)h->Ppad * 16));
@@ -461,7 +467,7 @@ extern "C" int clothhip_create(const ClothParams *params, int32_t n_envs, int32_
     HC(hipMemset(h->d_resume, 0, E * sizeof(EpResume)));
     HC(hipMalloc(&h->d_flat, (size_t)3 * h->Ppad * h->tsz));
     HC(hipMalloc(&h->d_flat_rest, (size_t)h->Spad * h->tsz));
-    HC(hipMemcpy(h->d_gather, gather.data(), gather.size() * 4, hipMemcpyHostToDevice));
+    HC(hipMemcpy(h->d_gather, h->gather.data(), h->gather.size() * 4, hipMemcpyHostToDevice));
     HC(hipMemcpy(h->d_wt_ent, h->wt.ent.data(), (size_t)h->Spad * 4, hipMemcpyHostToDevice));
     HC(hipMemcpy(h->d_wt_dep, h->wt.dep.data(), (size_t)h->Spad * 8, hipMemcpyHostToDevice));
     HC(hipMemset(h->d_rest, 0, E * h->Spad * h->tsz));
@@ -472,16 +478,16 @@ extern "C" int clothhip_create(const ClothParams *params, int32_t n_envs, int32_
         hipDeviceProp_t dp;
         int cus = 256;
         if (hipGetDeviceProperties(&dp, device) == hipSuccess && dp.multiProcessorCount > 0) cus = dp.multiProcessorCount;
-        plan_layouts(h, cus, gather);
+        plan_layouts(h, cus);
         // the pick assumed lean_r resident cloths per CU: ask the device (registers, LDS granules, what else it counts) and fall back to the
         // best residency it does grant -- a build planned for r that runs at r - 1 would be slower than the build meant for r - 1
         for (int guard = 0; guard < 5 && h->lean && h->lean_r >= 3 && !h->dbg.lean_set; guard++) {
-            const void *fl = find_stepper((int)h->tsz, h->lay_lean, 0, 1);
+            const void *fl = find_stepper(h->lay_lean.v, 0, 1);
             int occ = 0;
             if (!fl || hipFuncSetAttribute(fl, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-                hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fl, h->lay_lean.nt, (size_t)h->lay_lean.lds_bytes) != hipSuccess) { (void)hipGetLastError(); break; }
+                hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fl, h->lay_lean.v.nt, (size_t)h->lay_lean.lds_bytes) != hipSuccess) { (void)hipGetLastError(); break; }
             if (occ >= h->lean_r) break;
-            plan_layouts(h, cus, gather, std::max(2, occ));
+            plan_layouts(h, cus, std::max(2, occ));
         }
         if (h->lay_std.lds_bytes > 160 * 1024) { free_handle(h); return fail(CLOTHHIP_EINVAL, "n_side %d needs %d B of LDS (> 160 KiB)", h->N, h->lay_std.lds_bytes); }
         // every kernel the handle may launch: the generic build of the standard layout, of the lean one (which of the two runs is decided
@@ -492,10 +498,10 @@ extern "C" int clothhip_create(const ClothParams *params, int32_t n_envs, int32_
             if (L == &h->lay_lean && !h->lean) continue;
             const int ns = spec_ns(h, *L, false);
             for (int f = 0; f < 3; f++) {
-                const void *fn = find_stepper((int)h->tsz, *L, 0, f);
+                const void *fn = find_stepper(L->v, 0, f);
                 if (!fn) { free_handle(h); return fail(CLOTHHIP_EINVAL, "no %sstepper variant for n_side %d", L == &h->lay_lean ? "lean " : "", h->N); }
                 HC(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                if (ns) HC(hipFuncSetAttribute(find_stepper((int)h->tsz, *L, ns, f), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                if (ns) HC(hipFuncSetAttribute(find_stepper(L->v, ns, f), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             }
         }
     }
@@ -583,8 +589,7 @@ extern "C" int clothhip_set_state(clothhip_handle *h, int32_t env0, int32_t n, c
         const double *src = pass == 0 ? pos : prev;
         if (!src) continue;
         h->stage.resize(per * n);
-        if (h->precision == CLOTHHIP_F64) aos_to_soa<double>(src, (double *)h->stage.data(), n, h->P, h->Ppad);
-        else aos_to_soa<float>(src, (float *)h->stage.data(), n, h->P, h->Ppad);
+        by_precision(h, [&](auto t) { aos_to_soa(src, (decltype(t) *)h->stage.data(), n, h->P, h->Ppad); });
         char *dst = (char *)(pass == 0 ? h->d_pos : h->d_prev) + per * env0;
         HIPCHECK(hipMemcpy(dst, h->stage.data(), per * n, hipMemcpyHostToDevice));
     }
@@ -609,8 +614,7 @@ extern "C" int clothhip_set_state(clothhip_handle *h, int32_t env0, int32_t n, c
             for (int p = 0; p < h->S; p++) {
                 const int i = h->wt.slot_of[p];                               // list order -> table slot (empty slots stay 0)
                 const double v = rest[(size_t)e * h->S + p];
-                if (h->precision == CLOTHHIP_F64) ((double *)buf.data())[(size_t)e * h->Spad + i] = v;
-                else ((float *)buf.data())[(size_t)e * h->Spad + i] = (float)v;
+                by_precision(h, [&](auto t) { ((decltype(t) *)buf.data())[(size_t)e * h->Spad + i] = (decltype(t))v; });
             }
         char *dst = (char *)h->d_rest + (rest_shared ? 0 : (size_t)env0 * h->Spad * h->tsz);
         HIPCHECK(hipMemcpy(dst, buf.data(), buf.size(), hipMemcpyHostToDevice));
@@ -631,8 +635,7 @@ extern "C" int clothhip_get_state(clothhip_handle *h, int32_t env0, int32_t n, d
         h->stage.resize(per * n);
         const char *src = (const char *)(pass == 0 ? h->d_pos : h->d_prev) + per * env0;
         HIPCHECK(hipMemcpy(h->stage.data(), src, per * n, hipMemcpyDeviceToHost));
-        if (h->precision == CLOTHHIP_F64) soa_to_aos<double>((const double *)h->stage.data(), dst, n, h->P, h->Ppad);
-        else soa_to_aos<float>((const float *)h->stage.data(), dst, n, h->P, h->Ppad);
+        by_precision(h, [&](auto t) { soa_to_aos((const decltype(t) *)h->stage.data(), dst, n, h->P, h->Ppad); });
     }
     if (pinned) {
         std::vector<uint8_t> c((size_t)n * h->Ppad);
@@ -665,14 +668,12 @@ extern "C" int clothhip_reset_flat(clothhip_handle *h, const uint8_t *mask) {
     HIPCHECK(hipSetDevice(h->device));
     if (mask) HIPCHECK(hipMemcpyAsync(h->d_active, mask, (size_t)h->E, hipMemcpyHostToDevice, h->stream));
     if (int rc = drop_in_flight(h, mask ? h->d_active : nullptr, nullptr)) return rc;
-    if (h->precision == CLOTHHIP_F64)
-        hipLaunchKernelGGL(k_reset_flat<double>, dim3(h->E), dim3(256), 0, h->stream, (double *)h->d_pos, (double *)h->d_prev, h->d_cnt,
-                           h->d_tear, (const double *)h->d_flat, mask ? h->d_active : nullptr, h->Ppad, (double *)h->d_rest,
-                           (const double *)h->d_flat_rest, h->rest_stride, h->Spad);
-    else
-        hipLaunchKernelGGL(k_reset_flat<float>, dim3(h->E), dim3(256), 0, h->stream, (float *)h->d_pos, (float *)h->d_prev, h->d_cnt,
-                           h->d_tear, (const float *)h->d_flat, mask ? h->d_active : nullptr, h->Ppad, (float *)h->d_rest,
-                           (const float *)h->d_flat_rest, h->rest_stride, h->Spad);
+    by_precision(h, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(k_reset_flat<T>, dim3(h->E), dim3(256), 0, h->stream, (T *)h->d_pos, (T *)h->d_prev, h->d_cnt,
+                           h->d_tear, (const T *)h->d_flat, mask ? h->d_active : nullptr, h->Ppad, (T *)h->d_rest,
+                           (const T *)h->d_flat_rest, h->rest_stride, h->Spad);
+    });
     // (the LEAN palette verdict stands: a shared rest table is not touched here, and per-env tables rule the variant out anyway)
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(h->stream));
@@ -707,17 +708,13 @@ static int do_grab(clothhip_handle *h, const double *xy, const double *radius, c
     if (radius) HIPCHECK(hipMemcpyAsync(h->d_radius, radius, (size_t)h->E * 8, hipMemcpyHostToDevice, h->stream));
     if (active) HIPCHECK(hipMemcpyAsync(h->d_active, active, (size_t)h->E, hipMemcpyHostToDevice, h->stream));
     if (int rc = drop_in_flight(h, active ? h->d_active : nullptr, nullptr)) return rc;
-    if (h->precision == CLOTHHIP_F64) {
-        GrabArgs<double> a{(const double *)h->d_pos, h->d_cnt, h->d_xy, radius ? h->d_radius : nullptr,
-                           active ? h->d_active : nullptr, h->d_ngrab, h->d_levels, h->n_grab_levels, h->P, h->Ppad, top,
-                           h->prm.grip_radius, 2 * h->prm.thickness};
-        hipLaunchKernelGGL(k_grab<double>, dim3(h->E), dim3(64), 0, h->stream, a);
-    } else {
-        GrabArgs<float> a{(const float *)h->d_pos, h->d_cnt, h->d_xy, radius ? h->d_radius : nullptr,
-                          active ? h->d_active : nullptr, h->d_ngrab, h->d_levels, h->n_grab_levels, h->P, h->Ppad, top,
-                          h->prm.grip_radius, 2 * h->prm.thickness};
-        hipLaunchKernelGGL(k_grab<float>, dim3(h->E), dim3(64), 0, h->stream, a);
-    }
+    by_precision(h, [&](auto t) {
+        using T = decltype(t);
+        GrabArgs<T> a{(const T *)h->d_pos, h->d_cnt, h->d_xy, radius ? h->d_radius : nullptr,
+                      active ? h->d_active : nullptr, h->d_ngrab, h->d_levels, h->n_grab_levels, h->P, h->Ppad, top,
+                      h->prm.grip_radius, 2 * h->prm.thickness};
+        hipLaunchKernelGGL(k_grab<T>, dim3(h->E), dim3(64), 0, h->stream, a);
+    });
     HIPCHECK(hipGetLastError());
     if (n_grabbed) HIPCHECK(hipMemcpyAsync(n_grabbed, h->d_ngrab, (size_t)h->E * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(hipStreamSynchronize(h->stream));
@@ -765,7 +762,7 @@ template <typename T> static StepArgs<T> make_args(clothhip_handle *h, const Clo
     a.N = h->N; a.P = h->P; a.Ppad = h->Ppad; a.S = h->S; a.Spad = h->Spad;
     a.HT = h->lay().HT; a.ht_bits = h->lay().ht_bits;
     a.rest_stride = h->rest_stride; a.phase_mask = h->dbg.phase_mask;
-    a.k = make_consts<T>(h->prm);
+    a.k = make_consts<T>(phys_of(h->prm), h->N);
     if (sizeof(T) == 8) { a.pal_struct = (T)h->pal64[SPRING_STRUCTURAL]; a.pal_shear = (T)h->pal64[SPRING_SHEARING]; a.pal_bend = (T)h->pal64[SPRING_BENDING]; }
     else { a.pal_struct = (T)h->pal[SPRING_STRUCTURAL]; a.pal_shear = (T)h->pal[SPRING_SHEARING]; a.pal_bend = (T)h->pal[SPRING_BENDING]; }
     a.lstc = h->d_lstc;
@@ -782,87 +779,87 @@ static int spec_ns(const clothhip_handle *h, const Layout &L, bool with_palette)
     if (read_debug_knobs().nospec) return 0;
     if (h->dbg.phase_mask != 15 || (h->N != 25 && h->N != 50)) return 0;
     const int ns = h->N;
-    {   // the physics constants the build has compiled in (cloth_common.hpp: spec_phys) must be this handle's
-        const SpecPhys q = spec_phys(ns);
-        const ClothParams &p = h->prm;
-        if (p.width != q.width || p.height != q.height || p.density != q.density || p.ks != q.ks || p.damping != q.damping || p.thickness != q.thickness ||
-            p.plane_friction != q.plane_friction || p.tear_thresh != q.tear_thresh || p.gravity != q.gravity || p.minimum_z != q.minimum_z ||
-            p.frames_per_sec != q.frames_per_sec || p.simulation_steps != q.simulation_steps) return 0;
-        // (belt and braces: the literals the kernel holds are what make_consts gives the generic build, bit for bit)
-        if (h->precision == CLOTHHIP_F32) { const DevConsts<float> a = make_consts<float>(p), b = spec_consts<float>(ns); if (memcmp(&a, &b, sizeof(a)) != 0) return 0; }
-        else { const DevConsts<double> a = make_consts<double>(p), b = spec_consts<double>(ns); if (memcmp(&a, &b, sizeof(a)) != 0) return 0; }
-    }
-    if (!find_stepper((int)h->tsz, L, ns, 0)) return 0;
-    const bool same = h->P == spec_p(ns) && h->Ppad == spec_ppad(ns) && L.HT == spec_ht(ns, L.tab) && L.ht_bits == spec_htbits(ns, L.tab) &&
-                      h->Spad == spec_spad(ns) && h->wt.nW == spec_nw(ns) && h->wt.reach_shift == spec_rshift(ns) && L.cell_copy == spec_cell_copy(ns, L.tab);
+    // the physics constants the build has compiled in (cloth_common.hpp: spec_phys) must be this handle's
+    if (!(phys_of(h->prm) == spec_phys(ns))) return 0;
+    // (belt and braces: the literals the kernel holds, evaluated at compile time, are what the generic build is given at run time, bit for bit)
+    const bool same_consts = by_precision(h, [&](auto t) {
+        using T = decltype(t);
+        static constexpr DevConsts<T> c25 = spec_consts<T>(25), c50 = spec_consts<T>(50);
+        const DevConsts<T> a = make_consts<T>(phys_of(h->prm), h->N);
+        return memcmp(&a, ns == 25 ? &c25 : &c50, sizeof(a)) == 0;
+    });
+    if (!same_consts) return 0;
+    if (!find_stepper(L.v, ns, 0)) return 0;
+    const bool same = h->P == spec_p(ns) && h->Ppad == spec_ppad(ns) && L.HT == spec_ht(ns, L.v) && L.ht_bits == spec_htbits(ns, L.v) &&
+                      h->Spad == spec_spad(ns) && h->wt.nW == spec_nw(ns) && h->wt.reach_shift == spec_rshift(ns) && L.cell_copy == spec_cell_copy(ns, L.v);
     if (!same) return 0;
     // the LEAN fp32 builds hold the rest-length palette as literals: it must be what lean_refresh read back from the device's table
-    if (with_palette && h->precision == CLOTHHIP_F32 && L.rest_reg) {
+    if (with_palette && h->precision == CLOTHHIP_F32 && L.v.lean()) {
         for (int t = 0; t < 3; t++) { const float v = spec_pal(ns, t); if (memcmp(&v, &h->pal[t], 4) != 0) return 0; }
     }
     return ns;
+}
+
+// fp64 LEAN: every spring's rest length in the device's shared table must be its type's smallest value + at most 255 ulps (the flat tiers: <= 46
+// at 50x50). Fills pal64 and the per-particle stencil table d_lstc: slot k of particle i = the offset of its k-th stencil position (lean_off).
+static int check_palette_f64(clothhip_handle *h) {
+    std::vector<double> r((size_t)h->Spad);
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    HIPCHECK(hipMemcpy(r.data(), h->d_rest, r.size() * 8, hipMemcpyDeviceToHost));
+    long long base[3] = {0, 0, 0}; bool have[3] = {false, false, false}, ok = true;
+    auto bits = [](double v) { long long b; memcpy(&b, &v, 8); return b; };
+    for (int sp = 0; sp < h->S; sp++) {
+        const int ty = h->topo.type[sp];
+        const double v = r[h->wt.slot_of[sp]];
+        if (!(v > 0.0) || !std::isfinite(v)) { ok = false; break; }
+        if (!have[ty] || bits(v) < base[ty]) { base[ty] = bits(v); have[ty] = true; }
+    }
+    ok = ok && have[0] && have[1] && have[2];
+    std::vector<uint32_t> tab((size_t)h->Ppad * 4, 0u);
+    for (int i = 0; i < h->P && ok; i++) {
+        tab[(size_t)4 * i] = lean_valid_mask(i / h->N, i % h->N, h->N);
+        ok = walk_stencil(h, i, [&](int k, uint32_t g) {
+            const int pos = (int)((g >> HK_POS_SHIFT) & HK_POS_MASK);
+            const int sp = h->wt.spring_at[pos];
+            const long long off = sp >= 0 ? bits(r[pos]) - base[h->topo.type[sp]] : -1;
+            if (off < 0 || off > 255) return false;
+            tab[(size_t)4 * i + 1 + (k >> 2)] |= (uint32_t)off << (8 * (k & 3));
+            return true;
+        }) >= 0;
+    }
+    if (ok) {
+        for (int t = 0; t < 3; t++) memcpy(&h->pal64[t], &base[t], 8);
+        HIPCHECK(hipMemcpy(h->d_lstc, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+    }
+    h->lean_ok = ok;
+    return 0;
+}
+// fp32 LEAN: the device's shared rest table must hold ONE value per spring type, bit for bit (pal)
+static int check_palette_f32(clothhip_handle *h) {
+    std::vector<float> r((size_t)h->Spad);
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    HIPCHECK(hipMemcpy(r.data(), h->d_rest, r.size() * 4, hipMemcpyDeviceToHost));
+    bool have[3] = {false, false, false}, ok = true;
+    for (int sp = 0; sp < h->S && ok; sp++) {
+        const int ty = h->topo.type[sp];
+        const float v = r[h->wt.slot_of[sp]];
+        if (!have[ty]) { h->pal[ty] = v; have[ty] = true; }
+        else if (memcmp(&h->pal[ty], &v, 4) != 0) ok = false;
+    }
+    h->lean_ok = ok && have[0] && have[1] && have[2];
+    return 0;
 }
 
 // Which of the handle's two layouts the next launch runs: the LEAN one when this handle has one and the device's shared rest table is
 // its palette (re-checked whenever the table may have changed: per-env tables, i.e. tier 2, or odd rest lengths uploaded by the
 // caller switch back), else the standard one. LDS is rebuilt by every launch, so the layout may change from one launch to the next.
 static int lean_refresh(clothhip_handle *h) {
-    if (!h->lean) { h->spec_now = spec_ns(h, h->lay()); return 0; }
-    if (h->lean_dirty) {
+    if (h->lean && h->lean_dirty) {
         h->lean_dirty = false; h->lean_ok = false;
-        if (h->rest_stride == 0 && h->precision == CLOTHHIP_F64) {
-            // fp64: every spring's rest length must be its type's smallest value + at most 255 ulps (the flat tiers: <= 46 at 50x50); the offsets go to
-            // the per-particle stencil table, slot k of particle i = its k-th stencil position (lean_off), i.e. the popcount(valid below k)-th gather entry
-            std::vector<double> r((size_t)h->Spad);
-            HIPCHECK(hipStreamSynchronize(h->stream));
-            HIPCHECK(hipMemcpy(r.data(), h->d_rest, r.size() * 8, hipMemcpyDeviceToHost));
-            long long base[3] = {0, 0, 0}; bool have[3] = {false, false, false}, ok = true;
-            auto bits = [](double v) { long long b; memcpy(&b, &v, 8); return b; };
-            for (int sp = 0; sp < h->S; sp++) {
-                const int ty = h->topo.type[sp];
-                const double v = r[h->wt.slot_of[sp]];
-                if (!(v > 0.0) || !std::isfinite(v)) { ok = false; break; }
-                if (!have[ty] || bits(v) < base[ty]) { base[ty] = bits(v); have[ty] = true; }
-            }
-            ok = ok && have[0] && have[1] && have[2];
-            std::vector<uint32_t> tab((size_t)h->Ppad * 4, 0u);
-            std::vector<uint32_t> gather = build_gather(h->topo, h->wt, h->Ppad);
-            for (int i = 0; i < h->P && ok; i++) {
-                const uint32_t vm = lean_valid_mask(i / h->N, i % h->N, h->N);
-                tab[(size_t)4 * i] = vm;
-                int slot = 0;
-                for (int k = 0; k < HK_SLOTS; k++) {
-                    if (!((vm >> k) & 1u)) continue;
-                    const uint32_t g = gather[(size_t)slot * h->Ppad + i];
-                    const int pos = (int)((g >> HK_POS_SHIFT) & HK_POS_MASK);
-                    const int sp = h->wt.spring_at[pos];
-                    const long long off = sp >= 0 ? bits(r[pos]) - base[h->topo.type[sp]] : -1;
-                    if (off < 0 || off > 255) { ok = false; break; }
-                    tab[(size_t)4 * i + 1 + (k >> 2)] |= (uint32_t)off << (8 * (k & 3));
-                    slot++;
-                }
-            }
-            if (ok) {
-                for (int t = 0; t < 3; t++) memcpy(&h->pal64[t], &base[t], 8);
-                HIPCHECK(hipMemcpy(h->d_lstc, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
-            }
-            h->lean_ok = ok;
-        } else
-        if (h->rest_stride == 0) {
-            std::vector<float> r((size_t)h->Spad);
-            HIPCHECK(hipStreamSynchronize(h->stream));
-            HIPCHECK(hipMemcpy(r.data(), h->d_rest, r.size() * 4, hipMemcpyDeviceToHost));
-            bool have[3] = {false, false, false}, ok = true;
-            for (int sp = 0; sp < h->S && ok; sp++) {
-                const int ty = h->topo.type[sp];
-                const float v = r[h->wt.slot_of[sp]];
-                if (!have[ty]) { h->pal[ty] = v; have[ty] = true; }
-                else if (memcmp(&h->pal[ty], &v, 4) != 0) ok = false;
-            }
-            h->lean_ok = ok && have[0] && have[1] && have[2];
-        }
+        if (h->rest_stride == 0)
+            if (int rc = h->precision == CLOTHHIP_F64 ? check_palette_f64(h) : check_palette_f32(h)) return rc;
     }
-    h->on_lean = h->lean_ok && h->rest_stride == 0;
+    if (h->lean) h->on_lean = h->lean_ok && h->rest_stride == 0;
     h->spec_now = spec_ns(h, h->lay());
     return 0;
 }
@@ -873,7 +870,7 @@ static int cached_occupancy(clothhip_handle *h, const void *fn) {
     const Layout &L = h->lay();
     for (auto &c : h->occ_cache) if (c.fn == fn && c.lds == L.lds_bytes) return c.occ;
     int occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, L.nt, (size_t)L.lds_bytes) != hipSuccess) { (void)hipGetLastError(); occ = 0; }
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, L.v.nt, (size_t)L.lds_bytes) != hipSuccess) { (void)hipGetLastError(); occ = 0; }
     for (auto &c : h->occ_cache) if (c.fn == nullptr) { c = {fn, L.lds_bytes, occ}; return occ; }
     h->occ_cache[0] = {fn, L.lds_bytes, occ};
     return occ;
@@ -886,7 +883,7 @@ template <typename T> static int launch_generations(clothhip_handle *h, const vo
     h->last_dispatches = 0;
     for (int e0 = 0; e0 < h->E; e0 += cap) {
         a.e0 = e0; h->last_dispatches++;
-        HIPCHECK(hipLaunchKernel(fn, dim3(std::min(cap, h->E - e0)), dim3(h->lay().nt), args, (size_t)h->lay().lds_bytes, h->stream));
+        HIPCHECK(hipLaunchKernel(fn, dim3(std::min(cap, h->E - e0)), dim3(h->lay().v.nt), args, (size_t)h->lay().lds_bytes, h->stream));
     }
     return 0;
 }
@@ -904,13 +901,14 @@ template <typename T> static int launch_generations(clothhip_handle *h, const vo
 // generation had ended, 2 400 instead of 1 600 ms -- tools/placement.py, profiles/r05_placement.txt). A fresh launch finds every CU empty.
 static int launch_run(clothhip_handle *h, int fused, const ClothSchedule *d_sched, const void *d_fz, bool by_generation) {
     const Layout &L = h->lay();
-    const int tsz = (int)h->tsz, ns = fused == 3 ? 0 : h->spec_now;
-    const void *fn = find_stepper(tsz, L, ns, fused);
+    const Variant &V = L.v;
+    const int ns = fused == 3 ? 0 : h->spec_now;
+    const void *fn = find_stepper(V, ns, fused);
     if (!fn) return fail(CLOTHHIP_ESTATE, "no stepper variant for this layout (fused mode %d)", fused);
     const int occ = cached_occupancy(h, fn);
     const int cap = by_generation && occ > 0 && h->n_cus > 0 && !read_debug_knobs().one_launch ? occ * h->n_cus : h->E;
-    if (int rc = tsz == 8 ? launch_generations<double>(h, fn, cap, d_sched, d_fz) : launch_generations<float>(h, fn, cap, d_sched, d_fz)) return rc;
-    const int32_t v[10] = {L.nt, L.ppt, L.tab, L.rest_reg ? 1 : 0, v_lean(L.tab, L.rest_reg, tsz) ? 1 : 0, fused, L.lds_bytes, occ, h->n_cus, tsz == 4 ? 1 : 0};
+    if (int rc = by_precision(h, [&](auto t) { return launch_generations<decltype(t)>(h, fn, cap, d_sched, d_fz); })) return rc;
+    const int32_t v[10] = {V.nt, V.ppt, V.tab, V.rest_reg ? 1 : 0, V.lean() ? 1 : 0, fused, L.lds_bytes, occ, h->n_cus, V.tsz == 4 ? 1 : 0};
     memcpy(h->last_variant, v, sizeof(v)); h->have_variant = true; h->last_spec = ns;
     return 0;
 }
@@ -1000,16 +998,6 @@ static int grow(void **p, size_t *cap, size_t need) {
     return 0;
 }
 
-// (of the active layout: call lean_refresh first -- the LEAN and the standard layout differ in hash-table size, cell copy and hull-stack format)
-static int fused_scratch(const clothhip_handle *h, int *need_out) {
-    const Layout &L = h->lay();
-    int NS = 1; while (NS < h->P) NS <<= 1;
-    const int NH = h->Ppad + 8;
-    *need_out = metrics_scratch_bytes(NS, NH, (int)h->tsz, v_hull_idx(L.tab, (int)h->tsz, L.nt, L.ppt));
-    const LdsLayout lay((int)h->tsz, h->Ppad, h->Spad, L.HT, L.tab == 2 ? 2 : (v_ldstab(L.tab) ? 1 : 0), L.cell_copy);
-    return L.lds_bytes - lay.hkey;
-}
-
 // Every layout the handle may run (the standard one always; the LEAN one while its palette holds) was sized in clothhip_create
 extern "C" int clothhip_fused_supported(const clothhip_handle *h) {
     if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
@@ -1024,16 +1012,10 @@ extern "C" int clothhip_selftest_layout(const ClothParams *p, int32_t precision,
     if (precision != CLOTHHIP_F64 && precision != CLOTHHIP_F32) return fail(CLOTHHIP_EINVAL, "precision must be 0 (f64) or 1 (f32)");
     if (n_envs < 1 || n_cus < 1) return fail(CLOTHHIP_EINVAL, "n_envs and n_cus must be >= 1");
     clothhip_handle h;                                       // host fields only: nothing here touches a device
-    h.prm = *p; h.E = n_envs; h.precision = precision;
-    h.N = p->n_side; h.P = h.N * h.N; h.Ppad = (h.P + 63) / 64 * 64;
-    h.tsz = precision == CLOTHHIP_F64 ? 8 : 4;
-    h.topo = build_topology(h.N);
-    h.wt = build_windows(h.topo, build_levels(h.topo));
-    h.S = h.topo.S; h.Spad = h.wt.n_slots;
-    h.dbg = read_debug_knobs();
-    plan_layouts(&h, n_cus, build_gather(h.topo, h.wt, h.Ppad));
+    init_host_fields(&h, *p, n_envs, precision);
+    plan_layouts(&h, n_cus);
     auto put = [&](int o, const Layout &L) {
-        out[o] = L.nt; out[o + 1] = L.ppt; out[o + 2] = L.tab; out[o + 3] = L.rest_reg ? 1 : 0; out[o + 4] = L.cell_copy;
+        out[o] = L.v.nt; out[o + 1] = L.v.ppt; out[o + 2] = L.v.tab; out[o + 3] = L.v.rest_reg ? 1 : 0; out[o + 4] = L.cell_copy;
         out[o + 5] = L.lds_bytes; out[o + 6] = L.HT; out[o + 7] = L.scratch_have; out[o + 8] = L.scratch_need;
         out[o + 9] = L.scratch_have >= L.scratch_need ? 1 : 0;
     };
@@ -1072,16 +1054,12 @@ extern "C" int clothhip_run_actions_begin(clothhip_handle *h, const ClothEpisode
         return fail(CLOTHHIP_ESTATE, "in-kernel tier-2 resets rebuild per-env rest lengths; upload per-env rest tables first (clothhip_set_state without CLOTHHIP_REST_SHARED)");
     if (tier2 && (size_t)3 * h->P * 8 > (size_t)160 * 1024) return fail(CLOTHHIP_ESTATE, "grid too large for the tier-2 reset scratch");
     if (!(ep->reduce_factor > 0) || ep->max_actions < 1) return fail(CLOTHHIP_EINVAL, "bad episode parameters");
-    int NS = 1; while (NS < h->P) NS <<= 1;
-    const int NH = h->Ppad + 8;
     HIPCHECK(hipSetDevice(h->device));
     // which of the handle's two layouts runs now (may synchronise and read the rest table back: long before the timed events) -- the
     // scratch check below is against THAT layout, not the previous launch's
     if (int rc = lean_refresh(h)) return rc;
-    int need = 0;
-    const int have = fused_scratch(h, &need);
-    if (have < need)
-        return fail(CLOTHHIP_ESTATE, "n_side %d: the in-kernel metrics need %d B of LDS scratch, this variant has %d", h->N, need, have);
+    if (h->lay().scratch_have < h->lay().scratch_need)
+        return fail(CLOTHHIP_ESTATE, "n_side %d: the in-kernel metrics need %d B of LDS scratch, this variant has %d", h->N, h->lay().scratch_need, h->lay().scratch_have);
     HIPCHECK(hipStreamSynchronize(h->stream));
     const size_t E = h->E, nrec = (size_t)T_ * E;
     if (!h->d_fz) {
@@ -1128,15 +1106,14 @@ extern "C" int clothhip_run_actions_begin(clothhip_handle *h, const ClothEpisode
     const uint64_t budget_ticks = time_budget_ms > 0 ? (uint64_t)(time_budget_ms * 1e5) : 0;      // s_memrealtime: 100 MHz
     static_assert(sizeof(FusedArgs<double>) <= 1024 && sizeof(FusedArgs<float>) <= 1024, "fused argument block");
     unsigned char fzbuf[1024];
-    if (h->precision == CLOTHHIP_F64)
-        fill_fused<double>(h, *reinterpret_cast<FusedArgs<double> *>(fzbuf), ep, T_, policy, d_actions, policy_arg != nullptr, scripts != nullptr, resets, obs, reset_obs, n_scripts, budget_ticks,
-                           rng_states != nullptr, rng_tier, domrand_words, NS, NH);
-    else
-        fill_fused<float>(h, *reinterpret_cast<FusedArgs<float> *>(fzbuf), ep, T_, policy, d_actions, policy_arg != nullptr, scripts != nullptr, resets, obs, reset_obs, n_scripts, budget_ticks,
-                           rng_states != nullptr, rng_tier, domrand_words, NS, NH);
+    const MetricsDims md = metrics_dims(h->P, h->Ppad);
+    by_precision(h, [&](auto t) {
+        fill_fused(h, *reinterpret_cast<FusedArgs<decltype(t)> *>(fzbuf), ep, T_, policy, d_actions, policy_arg != nullptr, scripts != nullptr, resets, obs, reset_obs, n_scripts,
+                   budget_ticks, rng_states != nullptr, rng_tier, domrand_words, md.NS, md.NH);
+    });
     HIPCHECK(hipMemcpyAsync(h->d_fz, fzbuf, 1024, hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipStreamSynchronize(h->stream));          // fzbuf is on this stack frame
-    if (h->relaxed && !(find_stepper((int)h->tsz, h->lay(), 0, 3) && h->lay().cell_copy && !tier2 && policy != CLOTHHIP_POLICY_HIGHEST_POINT))
+    if (h->relaxed && !(find_stepper(h->lay().v, 0, 3) && h->lay().cell_copy && !tier2 && policy != CLOTHHIP_POLICY_HIGHEST_POINT))
         return fail(CLOTHHIP_ESTATE, "clothhip_set_relaxed_order: the relaxed-order companion exists for the eight-wave LEAN layout only (fp32, flat tiers, 25x25 class, <= 512 cloths)");
     HIPCHECK(hipEventRecord(h->ev0, h->stream));
     // (FUSED 2: the variant that also carries the tier-2 reset code and the cold policies; the relaxed-order companion is one launch)
@@ -1251,17 +1228,15 @@ extern "C" double clothhip_hull_area(const double *xy, int32_t n) {
 }
 
 static int launch_metrics(clothhip_handle *h) {
-    int NS = 1; while (NS < h->P) NS <<= 1;
-    const int NH = h->Ppad + 8;                 // the monotone chain holds at most m + 1 <= P + 1 points
-    const int lds = metrics_scratch_bytes(NS, NH, (int)h->tsz);
+    const MetricsDims md = metrics_dims(h->P, h->Ppad);
+    const int lds = metrics_scratch_bytes(md, (int)h->tsz, false);
     const double half_thick = h->prm.thickness / 2.0;                                   // cloth_env.py:604
-    if (h->precision == CLOTHHIP_F64) {
-        HIPCHECK(hipFuncSetAttribute((const void *)k_metrics<double>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        hipLaunchKernelGGL(k_metrics<double>, dim3(h->E), dim3(256), lds, h->stream, (const double *)h->d_pos, h->P, h->Ppad, NS, NH, h->d_cov, h->d_vinv, h->d_oob, h->d_hcnt, half_thick);
-    } else {
-        HIPCHECK(hipFuncSetAttribute((const void *)k_metrics<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        hipLaunchKernelGGL(k_metrics<float>, dim3(h->E), dim3(256), lds, h->stream, (const float *)h->d_pos, h->P, h->Ppad, NS, NH, h->d_cov, h->d_vinv, h->d_oob, h->d_hcnt, half_thick);
-    }
+    if (int rc = by_precision(h, [&](auto t) {
+            using T = decltype(t);
+            HIPCHECK(hipFuncSetAttribute((const void *)k_metrics<T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            hipLaunchKernelGGL(k_metrics<T>, dim3(h->E), dim3(256), lds, h->stream, (const T *)h->d_pos, h->P, h->Ppad, md.NS, md.NH, h->d_cov, h->d_vinv, h->d_oob, h->d_hcnt, half_thick);
+            return 0;
+        })) return rc;
     HIPCHECK(hipGetLastError());
     return 0;
 }
@@ -1288,10 +1263,9 @@ extern "C" int clothhip_metrics(clothhip_handle *h, double *coverage, double *va
 extern "C" int clothhip_write_obs_f32_device(clothhip_handle *h, void *d_out) {
     if (!h || !d_out) return fail(CLOTHHIP_EINVAL, "NULL argument");
     HIPCHECK(hipSetDevice(h->device));
-    if (h->precision == CLOTHHIP_F64)
-        hipLaunchKernelGGL(k_write_obs<double>, dim3(h->E), dim3(256), 0, h->stream, (const double *)h->d_pos, (float *)d_out, h->P, h->Ppad);
-    else
-        hipLaunchKernelGGL(k_write_obs<float>, dim3(h->E), dim3(256), 0, h->stream, (const float *)h->d_pos, (float *)d_out, h->P, h->Ppad);
+    by_precision(h, [&](auto t) {
+        hipLaunchKernelGGL(k_write_obs<decltype(t)>, dim3(h->E), dim3(256), 0, h->stream, (const decltype(t) *)h->d_pos, (float *)d_out, h->P, h->Ppad);
+    });
     HIPCHECK(hipGetLastError());
     return 0;
 }
@@ -1320,13 +1294,12 @@ extern "C" int clothhip_render(clothhip_handle *h, const ClothRenderParams *p, c
     a.ambient = p->ambient; a.energy = p->energy;
     a.swap = d_sw; a.zbuf = d_z; a.rgb = d_rgb; a.depth = d_dep;
     const int lds = 7 * h->Ppad * 4;
-    if (h->precision == CLOTHHIP_F64) {
-        RC(hipFuncSetAttribute((const void *)k_render<double>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        hipLaunchKernelGGL(k_render<double>, dim3(h->E), dim3(256), lds, h->stream, (const double *)h->d_pos, a);
-    } else {
-        RC(hipFuncSetAttribute((const void *)k_render<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        hipLaunchKernelGGL(k_render<float>, dim3(h->E), dim3(256), lds, h->stream, (const float *)h->d_pos, a);
-    }
+    if (int rc = by_precision(h, [&](auto t) {
+            using T = decltype(t);
+            RC(hipFuncSetAttribute((const void *)k_render<T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            hipLaunchKernelGGL(k_render<T>, dim3(h->E), dim3(256), lds, h->stream, (const T *)h->d_pos, a);
+            return 0;
+        })) return rc;
     RC(hipGetLastError());
     if (rgb) RC(hipMemcpyAsync(rgb, d_rgb, E * npx * 3, hipMemcpyDeviceToHost, h->stream));
     if (depth) RC(hipMemcpyAsync(depth, d_dep, E * npx * 4, hipMemcpyDeviceToHost, h->stream));
@@ -1379,7 +1352,7 @@ extern "C" int clothhip_set_relaxed_order(clothhip_handle *h, int32_t on) {
     if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
     if (on) {
         HIPCHECK(hipSetDevice(h->device));
-        HIPCHECK(hipFuncSetAttribute(find_stepper(4, Layout{512, 2, 2, true}, 0, 3), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        HIPCHECK(hipFuncSetAttribute(find_stepper(Variant{4, 512, 2, TAB_LDS_SLOTS, true}, 0, 3), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     }
     h->relaxed = on != 0;
     return 0;

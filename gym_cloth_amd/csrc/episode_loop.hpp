@@ -14,19 +14,19 @@ namespace clothhip {
 // of a particle is only ever touched by its owner (adjust, Verlet, plane), so it lives in the owner's
 // registers for the whole schedule, as do the particle's static gather entries (and, with REST_REG, the rest
 // lengths of its incident springs). Only the current positions are shared, through LDS.
-//   TAB: 0 static tables in global memory, 1 ent/rest/offsets in LDS, 2 also the per-point level table.
+//   TAB, REST_REG: the table mode and the arithmetic -- stepper_traits.hpp names the codes and answers every question about a variant (V below).
 //   FUSED: 0 = one externally decoded schedule per env (clothhip_run); 1 = whole episodes per launch (clothhip_run_actions)
 //          with the resets of the flat tiers 1 and 3; 2 = also tier-2 resets. (The tier-2 reset code is cold, but its presence
 //          costs the substep loop registers: -7 % on the headline workload, so it is compiled in only where it is asked for.)
-// LEAN variant (TAB <= 0 with REST_REG, fp32): the 12-slot gather stencil of a particle is recomputed from its grid position
+// LEAN variant (Variant::lean): the 12-slot gather stencil of a particle is recomputed from its grid position
 // instead of being held in 36 registers, and rest lengths come from a three-value palette instead of 36 more: the stepper is then
-// compiled for 168 VGPRs (TAB 0: three cloths share a CU) or 128 (TAB -1: four). Position k of the stencil = the k-th incident spring in ascending list index when
+// compiled for 168 VGPRs (three cloths share a CU) down to 80 (six). Position k of the stencil = the k-th incident spring in ascending list index when
 // all twelve exist (cloth.pyx:134-146: the six springs the point owns, then those its later neighbours own):
 //   k      0    1    2      3      4     5    6   7    8      9    10     11
 //   nbr   -N   -1   -N-1   -N+1   -2N   -2   +1  +2   +N-1   +N   +N+1   +2N      (index i = r*N + c)
 //   type   S    S    Sh     Sh     B     B    S   B    Sh     S    Sh     B
 // (the host checks this against the gather table it builds from the reference's spring list before choosing the variant).
-__device__ __forceinline__ int lean_off(int k, int N) {
+__host__ __device__ __forceinline__ int lean_off(int k, int N) {
     switch (k) {
         case 0: return -N; case 1: return -1; case 2: return -N - 1; case 3: return -N + 1; case 4: return -2 * N; case 5: return -2;
         case 6: return 1; case 7: return 2; case 8: return N - 1; case 9: return N; case 10: return N + 1; default: return 2 * N;
@@ -40,30 +40,12 @@ __host__ __device__ inline uint32_t lean_valid_mask(int r, int c, int N) {
            (r1 ? 64u : 0u) | (r2 ? 128u : 0u) | ((d1 && l1) ? 256u : 0u) | (d1 ? 512u : 0u) | ((d1 && r1) ? 1024u : 0u) | (d2 ? 2048u : 0u);
 }
 
-// How a (TAB, REST_REG, precision) triple is compiled:
-//   standard arithmetic   TAB 1: window table + rest lengths resident in LDS; TAB 0: streamed from L2
-//   LEAN arithmetic       (REST_REG, fp32) TAB 0: built for three cloths per CU (168 VGPRs), -1: for four (128), 3: the whole CU for one cloth
-//                         (the large grids), 4: two large-grid cloths per CU -- the table streamed from L2 in these --; 2: table in LDS, two per CU
-//                         (with 512 threads x 2 particles: eight waves per cloth at 128 VGPRs, the headline variant)
-//   LEAN arithmetic, fp64 (round 6) TAB 0 only: the stencil recomputed as above; a spring's rest length = the bit pattern of its type's palette value + a per-spring
-//                         offset in ulps (one byte, from an LDS-resident table): bit-identical to the table read it replaces, without the 24 L2 loads per particle
-constexpr bool v_lean(int TAB, bool RR, int tsz) { return RR && (tsz == 4 ? (TAB <= 0 || TAB == 2 || TAB == 3 || TAB == 4) : TAB == 0); }
-constexpr bool v_ldstab(int TAB) { return TAB == 1 || TAB == 2; }
-// the in-kernel metrics' hull stack as u16 indices (same arithmetic, an eighth of the LDS): the variants whose LDS is tight -- two large-grid
-// cloths per CU, five / six 25x25 cloths per CU, the fp64 instantiation of the large grids (50x50: 71 KB of scratch instead of 107 KB,
-// which is what lets its episode launches exist at all) and the 1024 x 4 variants (64x64)
-constexpr bool v_hull_idx(int TAB, int tsz = 4, int NT = 0, int PPT = 0) { return TAB == 4 || TAB <= -2 || (tsz == 8 && NT * PPT > 1024) || NT * PPT >= 4096; }
-constexpr int v_waves_per_eu(int NT, int TAB, bool lean, int PPT = 0) {      // __launch_bounds__' second argument: waves per SIMD
-    if (!lean && NT == 512 && PPT == 2) return 4;                // eight waves per cloth, two cloths per CU (standard arithmetic)
-    if (lean && NT == 512 && PPT == 2 && TAB == 0) return 4;    // the fp64 LEAN build: eight waves per cloth, two cloths per CU (fp32 TAB 0 is a 256-thread build)
-    if (!lean || TAB == 3) return NT <= 512 ? 2 : NT / 256;
-    if (TAB == 2 || TAB == 4) return NT / 128;                   // two cloths per CU (4: the large grids, table streamed)
-    return TAB < 0 ? 3 - TAB : 3;                                // TAB 0, -1, -2, -3: three, four, five, six cloths per CU
-}
 // NS: 0 = any grid (sizes from the kernel arguments); 25 / 50 = a BASELINE grid known at compile time (cloth_common.hpp: spec_*)
 template <typename T, int NT, int PPT, int TAB, bool REST_REG, int FUSED, int NS = 0>
-__global__ __launch_bounds__(NT, v_waves_per_eu(NT, TAB, v_lean(TAB, REST_REG, (int)sizeof(T)), PPT)) void k_run_schedule(StepArgs<T> A) {
+__global__ __launch_bounds__(NT, (Variant{(int)sizeof(T), NT, PPT, TAB, REST_REG}.waves_per_eu())) void k_run_schedule(StepArgs<T> A) {
     static_assert((NS == 0 || NS == 25 || NS == 50) && (NS == 0 || FUSED != 3), "grid-specialised builds exist for 25x25 and 50x50 (stepper_variants.hpp: CLOTH_SPEC_*)");
+    // every question about the variant goes through V (stepper_traits.hpp). static: an automatic V would be captured by the [&] lambdas below, which moves registers
+    static constexpr Variant V{(int)sizeof(T), NT, PPT, TAB, REST_REG};
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int e = blockIdx.x + A.e0;
     const int tid = threadIdx.x;
@@ -89,9 +71,9 @@ __global__ __launch_bounds__(NT, v_waves_per_eu(NT, TAB, v_lean(TAB, REST_REG, (
         sc.break_on_tear = 1; sc.active = 1; sc._pad = 0;
         sc.dz_up = sc.dx_pull = sc.dy_pull = sc.dz_pull = 0.0;
     }
-    const int P = NS > 0 ? spec_p(NS) : A.P, Ppad = NS > 0 ? spec_ppad(NS) : A.Ppad, HT = NS > 0 ? spec_ht(NS, TAB) : A.HT;
-    constexpr bool LEAN64 = v_lean(TAB, REST_REG, (int)sizeof(T)) && sizeof(T) == 8;
-    const LdsLayout lay((int)sizeof(T), Ppad, KA_SPAD(&A), HT, TAB == 2 ? 2 : (v_ldstab(TAB) ? 1 : 0), KA_CELLCOPY(&A), LEAN64 ? 1 : 0);
+    const int P = NS > 0 ? spec_p(NS) : A.P, Ppad = NS > 0 ? spec_ppad(NS) : A.Ppad, HT = NS > 0 ? spec_ht(NS, V) : A.HT;
+    constexpr bool LEAN64 = V.lean64();
+    const LdsLayout lay = lds_layout(V, Ppad, KA_SPAD(&A), HT, KA_CELLCOPY(&A));
     Pt<T> *cur = reinterpret_cast<Pt<T> *>(smem + lay.cur);
     uint32_t *hkey = reinterpret_cast<uint32_t *>(smem + lay.hkey);
     uint32_t *hco = reinterpret_cast<uint32_t *>(smem + lay.hco);
@@ -104,17 +86,17 @@ __global__ __launch_bounds__(NT, v_waves_per_eu(NT, TAB, v_lean(TAB, REST_REG, (
     const DevConsts<T> &k = A.k;                         // (every phase of the substep loop shadows this by its own freshly loaded copy: CLOTH_PHASE_ARGS)
     (void)k;
     const T *g_rest = A.rest + (size_t)e * A.rest_stride;
-    const WEnt<T> *wtab = reinterpret_cast<const WEnt<T> *>(smem + lay.wtab);    // TAB >= 1 only
+    const WEnt<T> *wtab = reinterpret_cast<const WEnt<T> *>(smem + lay.wtab);    // V.table_in_lds() only
     // rest length of the spring in window-table slot i (Hooke, pre-pass; the sweep streams its own)
-    auto rest_at = [&](uint32_t i) -> T { return v_ldstab(TAB) ? wtab[i].rest : g_rest[i]; };
+    auto rest_at = [&](uint32_t i) -> T { return V.table_in_lds() ? wtab[i].rest : g_rest[i]; };
     const int pm = NS > 0 ? (PH_HOOKE | PH_COLLIDE | PH_PLANE | PH_STRAIN) : A.phase_mask;     // (the specialised builds run every phase: debug masks take the generic build)
 
     T pvx[PPT], pvy[PPT], pvz[PPT];         // previous positions of the owned particles
     // their incident-spring gather entries (static): in registers for fp32; the fp64 instantiation has no room
     // (they ended up in scratch, reloaded one by one) and re-reads the L2-resident table, 12 loads in flight
-    constexpr bool LEAN = v_lean(TAB, REST_REG, (int)sizeof(T));      // (the variants: see v_lean above)
+    constexpr bool LEAN = V.lean();
     constexpr bool GT_REG = sizeof(T) == 4 && !LEAN;
-    constexpr bool REST_R = REST_REG && !LEAN;
+    constexpr bool REST_R = V.rest_in_registers();
     uint32_t gt[GT_REG ? PPT : 1][HK_SLOTS];
     T rr[REST_R ? PPT : 1][HK_SLOTS];     // and those springs' rest lengths
     uint32_t vm[(LEAN && !LEAN64) ? PPT : 1];   // LEAN: which of the twelve stencil positions exist for the particle (fp64: in the LDS table below)
@@ -162,7 +144,7 @@ __global__ __launch_bounds__(NT, v_waves_per_eu(NT, TAB, v_lean(TAB, REST_REG, (
     // everything in LDS behind the particle records: static tables, hash table, sweep flags (also re-run after the in-kernel
     // metrics, which borrow that region as scratch)
     auto init_lds = [&](int tear_flag, const uint32_t *s_ent, const T *s_rest) {
-        if (v_ldstab(TAB) && s_ent != nullptr) {         // (nullptr: the table in LDS is intact, only the scratch behind it is rebuilt)
+        if (V.table_in_lds() && s_ent != nullptr) {         // (nullptr: the table in LDS is intact, only the scratch behind it is rebuilt)
             WEnt<T> *d0 = reinterpret_cast<WEnt<T> *>(smem + lay.wtab);
             for (int i = tid; i < KA_SPAD(&A); i += NT) { WEnt<T> w_; w_.ab = s_ent[i]; w_.rest = s_rest[i]; d0[i] = w_; }
         }
@@ -175,8 +157,8 @@ __global__ __launch_bounds__(NT, v_waves_per_eu(NT, TAB, v_lean(TAB, REST_REG, (
         uint4 *d_ = reinterpret_cast<uint4 *>(smem + lay.lstc);
         for (int i = tid; i < Ppad; i += NT) d_[i] = A.lstc[i];
     }
-    uint16_t *pslot = reinterpret_cast<uint16_t *>(smem + lay.pslot);       // TAB 2 only
-    if (TAB == 2) {
+    uint16_t *pslot = reinterpret_cast<uint16_t *>(smem + lay.pslot);       // V.has_point_slots() only
+    if (V.has_point_slots()) {
         for (int i = tid; i < Ppad; i += NT) {
             const int r_ = i / KA_N(&A);
             const uint32_t vmi = i < P ? lean_valid_mask(r_, i - r_ * KA_N(&A), KA_N(&A)) : 0u;
@@ -214,9 +196,7 @@ __global__ __launch_bounds__(NT, v_waves_per_eu(NT, TAB, v_lean(TAB, REST_REG, (
 #else
     constexpr bool SWEEP_LEAN = false;  // (the sweep-stamps and census builds instrument strain_sweep)
 #endif
-    // TAB below 1 (the four-wave builds for three to six cloths per CU: 768 cloths 24.9 -> 25.2 M/s, 1 024: 31.4 -> 31.7, 1 280: +-0,
-    // 1 536: 33.8 -> 34.2): the lean walk without its read-ahead; the eight-wave headline build loses 2.8 % without it
-    constexpr bool SWEEP_AHEAD = TAB >= 1;
+    constexpr bool SWEEP_AHEAD = V.sweep_read_ahead();
     (void)SWEEP_AHEAD;
 #if defined(CLOTHHIP_PHASE_STAMPS) || defined(CLOTHHIP_CELL_COUNTERS)   // the sweep's window / pass / correction counters cost its loop three instructions per pass:
     constexpr bool SWEEP_STATS = true;  // profiling builds only (the production build counts sweeps)

@@ -6,7 +6,8 @@
 // `extern template` declarations and only takes their addresses, through STEPPER_ROWS / find_stepper below (a kernel launch across
 // translation units needs no relocatable device code: the host stub is an ordinary symbol, the device code is registered by the object that
 // defines it).
-//   X(T, NT, PPT, TAB, REST_REG): threads per cloth, particles per thread, table mode, rest lengths in registers / LEAN palette (episode_loop.hpp)
+//   X(T, NT, PPT, TAB, REST_REG): threads per cloth, particles per thread, table mode, rest lengths in registers / LEAN palette. TAB stays a number here,
+//   as a table reads best: stepper_traits.hpp names the codes (-3 .. -1 TAB_LEAN_6 / _5 / _4, 0 TAB_STREAM, 1 TAB_LDS, 2 TAB_LDS_SLOTS, 3 / 4 TAB_LARGE_1 / _2)
 #pragma once
 
 #include "episode_loop.hpp"
@@ -79,14 +80,14 @@ CLOTH_SPEC_F32(CLOTH_DECL_S) CLOTH_SPEC_F64(CLOTH_DECL_S)
 CLOTH_RELAXED(extern)
 
 namespace clothhip {
-// What a stepper launch runs: the variant (threads per cloth, particles per thread, table mode, rest lengths in registers) and its LDS
+// What a stepper launch runs: the variant (stepper_traits.hpp) and its LDS
 // carve-up (clothhip_api.hip: plan_layouts). scratch_have / scratch_need: the LDS behind the hash table that the in-kernel metrics of
 // the episode launches borrow, and what they need.
-struct Layout { int nt, ppt, tab; bool rest_reg; int cell_copy, lds_bytes, HT, ht_bits, scratch_have, scratch_need; };
+struct Layout { Variant v; int cell_copy, lds_bytes, HT, ht_bits, scratch_have, scratch_need; };
 
-// Every instantiation above as one row {sizeof(T), NT, PPT, TAB, REST_REG, NS, FUSED, kernel}: the only place the host names a kernel.
-struct StepperRow { int tsz, nt, ppt, tab; bool rest_reg; int ns, fused; const void *fn; };
-#define CLOTH_ROW(T, NT, PPT, TAB, RR, NS_, F) {(int)sizeof(T), NT, PPT, TAB, RR, NS_, F, (const void *)k_run_schedule<T, NT, PPT, TAB, RR, F, NS_>},
+// Every instantiation above as one row {Variant{sizeof(T), NT, PPT, TAB, REST_REG}, NS, FUSED, kernel}: the only place the host names a kernel.
+struct StepperRow { Variant v; int ns, fused; const void *fn; };
+#define CLOTH_ROW(T, NT, PPT, TAB, RR, NS_, F) {{(int)sizeof(T), NT, PPT, TAB, RR}, NS_, F, (const void *)k_run_schedule<T, NT, PPT, TAB, RR, F, NS_>},
 #define CLOTH_ROWS_S(T, NT, PPT, TAB, RR, NS_) CLOTH_ROW(T, NT, PPT, TAB, RR, NS_, 0) CLOTH_ROW(T, NT, PPT, TAB, RR, NS_, 1) CLOTH_ROW(T, NT, PPT, TAB, RR, NS_, 2)
 #define CLOTH_ROWS(T, NT, PPT, TAB, RR) CLOTH_ROWS_S(T, NT, PPT, TAB, RR, 0)
 static const StepperRow STEPPER_ROWS[] = {
@@ -98,11 +99,11 @@ static const StepperRow STEPPER_ROWS[] = {
 #undef CLOTH_ROWS_S
 #undef CLOTH_ROW
 
-// The kernel that runs layout L in precision tsz (4 / 8) as the grid-specialised build NS = ns (0: the generic one) for FUSED = fused;
+// The kernel that runs variant v as the grid-specialised build NS = ns (0: the generic one) for FUSED = fused;
 // nullptr: not compiled.
-inline const void *find_stepper(int tsz, const Layout &L, int ns, int fused) {
+inline const void *find_stepper(const Variant &v, int ns, int fused) {
     for (const StepperRow &r : STEPPER_ROWS)
-        if (r.tsz == tsz && r.nt == L.nt && r.ppt == L.ppt && r.tab == L.tab && r.rest_reg == L.rest_reg && r.ns == ns && r.fused == fused) return r.fn;
+        if (r.v == v && r.ns == ns && r.fused == fused) return r.fn;
     return nullptr;
 }
 }  // namespace clothhip

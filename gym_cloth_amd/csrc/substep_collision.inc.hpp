@@ -152,8 +152,8 @@
                                 // a read past the cell's range (another cell's record or the padding behind the array) is masked out
                                 // by the member count; the trip base is clamped so that no read leaves the padded array
                                 // (round 5: four members per trip -- half the loop branches and LDS waits per member: +0.25 % at two cloths per
-                                //  CU; two per trip where the register cap is 80 (six per CU: TAB -3): 23 fewer spill reloads, +1.6 % at 1536 cloths)
-                                if constexpr (TAB > -3) {
+                                //  CU; two per trip where the register cap is 80 (six per CU: Variant::collide_two_visits_per_trip))
+                                if constexpr (!V.collide_two_visits_per_trip()) {
 #pragma unroll 1
                                 for (int b = 0; b < nq; b += 4) {
                                     const int base = cs_ + b < Ppad + 28 ? cs_ + b : Ppad + 28;

@@ -365,8 +365,10 @@ double clothhip_last_kernel_ms(clothhip_handle *h);
 
 /* (new, ABI 5) Which compiled stepper variant the handle's LAST launch ran (clothhip_run*, clothhip_update, clothhip_run_actions*),
  * so that tests and the benchmark can tell the variants apart instead of inferring them from the batch size:
- *   v[0] threads per cloth, v[1] particles per thread, v[2] table mode (1: strain-sweep window table resident in LDS, 0: streamed
- *   from L2; LEAN builds: 0 = compiled for three cloths per CU, -1 = for four, 2 = LEAN arithmetic with the table in LDS),
+ *   v[0] threads per cloth, v[1] particles per thread, v[2] table mode: 1 strain-sweep window table resident in LDS, 0 streamed
+ *   from L2 (standard arithmetic; with v[4] the fp32 LEAN build compiled for three cloths per CU, or the fp64 LEAN build), and LEAN only:
+ *   -1 / -2 / -3 compiled for four / five / six cloths per CU, 2 the table in LDS plus per-point slots (eight waves per cloth),
+ *   3 a large grid with the whole CU for one cloth, 4 two large-grid cloths per CU (names: csrc/stepper_traits.hpp),
  *   v[3] rest lengths in registers / LEAN flag as compiled (0/1), v[4] 1 when the LEAN arithmetic ran (gather stencil recomputed,
  *   rest lengths from the three-value palette), v[5] episode-loop flavour (0 plain schedule, 1 flat-tier episodes, 2 + tier-2 /
  *   highest-point code), v[6] dynamic LDS bytes per cloth, v[7] cloths resident per CU for that kernel and LDS size
