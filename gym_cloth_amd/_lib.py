@@ -31,6 +31,17 @@ class ClothParams(C.Structure):
                 ("gravity", C.c_double), ("minimum_z", C.c_double), ("grip_radius", C.c_double)]
 
 
+class ClothMaterial(C.Structure):
+    """The per-env material (clothhip_set_material): the cfg quantities Cloth.update() reads anew on every call (cloth.pyx:175-186)."""
+    _fields_ = [("density", C.c_double), ("ks", C.c_double), ("damping", C.c_double), ("plane_friction", C.c_double),
+                ("tear_thresh", C.c_double), ("gravity", C.c_double)]
+
+
+MATERIAL_FIELDS = ("density", "ks", "damping", "plane_friction", "tear_thresh", "gravity")
+MATERIAL_DTYPE = np.dtype([(k, "<f8") for k in MATERIAL_FIELDS])
+assert MATERIAL_DTYPE.itemsize == C.sizeof(ClothMaterial) == 48
+
+
 class ClothSchedule(C.Structure):
     _fields_ = [("n_up_end", C.c_int32), ("n_uprest_end", C.c_int32), ("n_pull_end", C.c_int32),
                 ("n_griprest_end", C.c_int32), ("n_total", C.c_int32), ("break_on_tear", C.c_int32),
@@ -133,6 +144,9 @@ SYMBOLS = [
     ("clothhip_last_dispatches", C.c_int, [_vp, _i32p]),
     ("clothhip_last_specialised", C.c_int, [_vp, _i32p]),
     ("clothhip_set_relaxed_order", C.c_int, [_vp, C.c_int32]),
+    ("clothhip_set_material", C.c_int, [_vp, C.c_int32, C.c_int32, _vp]),
+    ("clothhip_get_material", C.c_int, [_vp, C.c_int32, C.c_int32, _vp]),
+    ("clothhip_selftest_material", C.c_int, [_PP, C.POINTER(ClothMaterial), C.c_int32, _dp]),
     ("clothhip_selftest_windows", C.c_int, [_PP, _i32p, _i32p, _i32p, _i32p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_int32]),
     ("clothhip_selftest_layout", C.c_int, [_PP, C.c_int32, C.c_int32, C.c_int32, _i32p, C.c_int32]),
     ("clothhip_selftest_rng", C.c_int, [_vp, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, _dp]),

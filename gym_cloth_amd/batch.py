@@ -99,6 +99,45 @@ class ClothBatch(object):
         check(self._L.clothhip_set_state(self._h, env0, n, _lib.dp(pos), _lib.dp(prev), _lib.u8p(pin),
                                          _lib.dp(rest), flags))
 
+    # ---- per-env materials -----------------------------------------------------------------------------
+    def set_material(self, material=None, env0=0, n=None):
+        """Give envs [env0, env0+n) a material of their own (clothhip_set_material): density, ks, damping, plane_friction,
+        tear_thresh, gravity -- what Cloth.update() reads from the cfg on every call (cloth.pyx:175-186). `material`: a structured
+        array of _lib.MATERIAL_DTYPE, or a dict with all six fields (scalars or arrays, broadcast over the n envs); None: these envs go
+        back to the handle's parameters. n defaults to the array's length, else to every env from env0 on. The material stays with the
+        env slot through set_state, reset_flat and episode resets."""
+        if n is None and material is not None and not isinstance(material, dict) and np.ndim(material) == 1:
+            n = len(material)
+        n = self.E - env0 if n is None else int(n)
+        if material is None:
+            check(self._L.clothhip_set_material(self._h, int(env0), n, None))
+            return
+        if isinstance(material, dict):
+            missing = [k for k in _lib.MATERIAL_FIELDS if k not in material]
+            extra = [k for k in material if k not in _lib.MATERIAL_FIELDS]
+            if missing or extra:
+                raise ValueError("a material has exactly the fields %s (missing %s, unknown %s)" % (_lib.MATERIAL_FIELDS, missing, extra))
+            m = np.empty(n, dtype=_lib.MATERIAL_DTYPE)
+            for k in _lib.MATERIAL_FIELDS:
+                m[k] = np.broadcast_to(np.asarray(material[k], dtype=np.float64), (n,))
+        else:
+            m = np.asarray(material)
+            if m.dtype.names is None or set(m.dtype.names) != set(_lib.MATERIAL_FIELDS):
+                raise ValueError("material must be a structured array with the fields %s" % (_lib.MATERIAL_FIELDS,))
+            src = np.broadcast_to(m, (n,))
+            m = np.empty(n, dtype=_lib.MATERIAL_DTYPE)
+            for k in _lib.MATERIAL_FIELDS:                # by NAME: numpy converts structured dtypes by position
+                m[k] = src[k]
+        m = np.ascontiguousarray(m)
+        check(self._L.clothhip_set_material(self._h, int(env0), n, m.ctypes.data_as(C.c_void_p)))
+
+    def get_material(self, env0=0, n=None):
+        """The effective materials of envs [env0, env0+n), _lib.MATERIAL_DTYPE[n] (the handle's parameters where none was set)."""
+        n = self.E - env0 if n is None else int(n)
+        m = np.zeros(n, dtype=_lib.MATERIAL_DTYPE)
+        check(self._L.clothhip_get_material(self._h, int(env0), n, m.ctypes.data_as(C.c_void_p)))
+        return m
+
     def get_rest(self, env0=0, n=None):
         """Spring.rest_length per env in reference list order, [n, S]."""
         n = self.E - env0 if n is None else n

@@ -132,6 +132,10 @@ template <typename T> struct StepArgs {
     int32_t e0;              // env of workgroup 0: a time-sliced episode launch over more cloths than are resident goes out as one launch per generation (launch_run)
     const uint4 *lstc;       // fp64 LEAN build: [Ppad] per particle {stencil mask, 12 rest-length offsets in ulps (one byte each)}: the flat tiers' fp64 rest
                              // lengths (cloth.pyx:417 on the grid of :117-130) are one value per spring type up to a few dozen ulps -- rest = bits(pal_type) + offset
+    const DevConsts<T> *mat; // [E] or nullptr: every env's constants, when at least one env holds a material of its own (clothhip_set_material). The
+                             // reference reads density, ks, damping, friction, tear threshold and gravity from the cfg in every Cloth.update()
+                             // (cloth.pyx:175-186, :240-241, :368), so they are inputs per cloth. Whole records: the per-handle fields repeat `k`'s.
+                             // Only the generic build (NS = 0) reads it; nullptr = a uniform handle, every env runs on `k`
 };
 
 constexpr int KEY_SHIFT = 12;
@@ -303,7 +307,15 @@ constexpr float spec_pal(int ns, int type) {
 // NS > 0: the constants as LITERALS (no scalar loads at the head of every phase, no SGPRs held, constant subexpressions folded: +1 % on the
 // headline) -- all but sim_steps: the fp32 arithmetic divides by it through v_rcp_f32, which the compiler would fold to the correctly rounded
 // reciprocal, and the specialised build must stay bit-identical to the generic one (every other use of a constant is an exactly rounded operation).
-template <typename T, int NS = 0> __device__ __forceinline__ DevConsts<T> load_consts(KArgsC<T> *p) {
+// NS = 0 on a handle with per-env materials (StepArgs::mat): the seven material fields come from record `e` of the device's table instead of the
+// kernel-argument block. ONE base address is selected for them (s_cselect between the record and the argument block, both in the constant address
+// space: the host writes the table between launches only, `e` is the workgroup's), so they arrive by scalar loads into SGPRs that die with the
+// phase, like the kernel-argument ones. The select waits for the table pointer, so every handle -- with materials or not -- pays a second,
+// dependent scalar-load latency in the phases that use a material field; the eight per-handle fields do not go through the selected base, so
+// a phase that uses none (self-collision) pays nothing. Cost on a handle WITHOUT materials on the generic build: -0.4 % on the headline
+// workload, more than the parent's run-to-run spread. The other forms that were built (all fifteen fields through the base, a pinned branch on the
+// pointer, a flag bit in the env index) measured -0.8 % .. -1.6 %: profiles/material_ab.txt.
+template <typename T, int NS = 0> __device__ __forceinline__ DevConsts<T> load_consts(KArgsC<T> *p, int e) {
     DevConsts<T> k;
     if constexpr (NS > 0) {
         constexpr DevConsts<T> c = spec_consts<T>(NS);
@@ -311,9 +323,12 @@ template <typename T, int NS = 0> __device__ __forceinline__ DevConsts<T> load_c
         k.sim_steps = p->k.sim_steps;
         return k;
     }
-    k.mg = p->k.mg; k.ks_str = p->k.ks_str; k.ks_bend = p->k.ks_bend; k.dsm = p->k.dsm; k.damp = p->k.damp;
+    typedef const __attribute__((address_space(4))) DevConsts<T> ConstsC;
+    const DevConsts<T> *const tab = p->mat;
+    ConstsC *const c = tab != nullptr ? (ConstsC *)(uintptr_t)(tab + e) : &p->k;
+    k.mg = c->mg; k.ks_str = c->ks_str; k.ks_bend = c->ks_bend; k.dsm = c->dsm; k.damp = c->damp; k.one_m_fric = c->one_m_fric; k.tear_thresh = c->tear_thresh;
     k.cw = p->k.cw; k.ch = p->k.ch; k.ct = p->k.ct; k.thresh = p->k.thresh; k.sim_steps = p->k.sim_steps;
-    k.min_z = p->k.min_z; k.surf_off = p->k.surf_off; k.one_m_fric = p->k.one_m_fric; k.tear_thresh = p->k.tear_thresh; k.c11 = p->k.c11;
+    k.min_z = p->k.min_z; k.surf_off = p->k.surf_off; k.c11 = p->k.c11;
     return k;
 }
 // (in a phase's scope: shadows the kernel's `k`, `P`, `Ppad`, `HT` by freshly loaded copies)
@@ -341,7 +356,7 @@ constexpr int spec_cell_copy(int ns, Variant v) { return ns == 25 ? (v.spec_has_
 #define CLOTH_PHASE_DIMS() const int P = NS > 0 ? spec_p(NS) : Ak_->P, Ppad = NS > 0 ? spec_ppad(NS) : Ak_->Ppad, HT = NS > 0 ? spec_ht(NS, V) : Ak_->HT;
 #define CLOTH_PHASE_ARGS()                                                        \
     asm volatile("" : "+s"(Ak_));                                                 \
-    const DevConsts<T> k = load_consts<T, NS>(Ak_);                               \
+    const DevConsts<T> k = load_consts<T, NS>(Ak_, e);                             \
     CLOTH_PHASE_DIMS()                                                            \
     (void)k; (void)P; (void)Ppad; (void)HT;
 

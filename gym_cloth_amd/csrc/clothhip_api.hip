@@ -109,6 +109,11 @@ struct clothhip_handle {
     float pal[3] = {0, 0, 0};
     double pal64[3] = {0, 0, 0};     // fp64 LEAN build: the smallest rest length of each spring type (the others are it + a few ulps: StepArgs::lstc)
     uint4 *d_lstc = nullptr;         // [Ppad] fp64 LEAN build: per particle {stencil mask, 12 offset bytes}
+    // per-env materials (clothhip_set_material): every env's effective values; how many differ bitwise from the handle's parameters (0: a uniform
+    // handle -- no table goes to the kernel, the grid-specialised builds stay eligible); the device's [E] DevConsts<T> table, allocated by the first set
+    std::vector<ClothMaterial> mat;
+    int n_mixed = 0;
+    void *d_mat = nullptr;
     int32_t last_variant[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // what the last launch ran (clothhip_last_variant)
     bool have_variant = false;
     int n_cus = 0;
@@ -157,6 +162,13 @@ static int check_params(const ClothParams *p) {
     if (p->height != p->width) return fail(CLOTHHIP_EINVAL, "height must equal width (cloth.pyx:91)");
     if (p->frames_per_sec <= 0 || p->simulation_steps <= 0) return fail(CLOTHHIP_EINVAL, "frames_per_sec/simulation_steps must be > 0");
     if (!(p->density > 0) || !(p->thickness > 0)) return fail(CLOTHHIP_EINVAL, "density/thickness must be > 0");
+    return 0;
+}
+// the rules check_params applies to the fields a material overrides: the material put into the handle's parameters must pass them
+static int check_material(const ClothParams &prm, const ClothMaterial &m, int idx) {
+    ClothParams p = prm;
+    p.density = m.density; p.ks = m.ks; p.damping = m.damping; p.plane_friction = m.plane_friction; p.tear_thresh = m.tear_thresh; p.gravity = m.gravity;
+    if (check_params(&p)) return fail(CLOTHHIP_EINVAL, "material %d: %s", idx, std::string(g_err).c_str());
     return 0;
 }
 
@@ -222,12 +234,19 @@ extern "C" int clothhip_selftest_windows(const ClothParams *p, int32_t *n_window
 static SpecPhys phys_of(const ClothParams &p) {
     return SpecPhys{p.width, p.height, p.density, p.ks, p.damping, p.thickness, p.plane_friction, p.tear_thresh, p.gravity, p.minimum_z, p.frames_per_sec, p.simulation_steps};
 }
+// ... and of one env of it that holds material m: the material's six fields over the handle's (cloth.pyx:175-186)
+static SpecPhys phys_of(const ClothParams &p, const ClothMaterial &m) {
+    SpecPhys s = phys_of(p);
+    s.density = m.density; s.ks = m.ks; s.damping = m.damping; s.plane_friction = m.plane_friction; s.tear_thresh = m.tear_thresh; s.gravity = m.gravity;
+    return s;
+}
+static ClothMaterial material_of(const ClothParams &p) { return ClothMaterial{p.density, p.ks, p.damping, p.plane_friction, p.tear_thresh, p.gravity}; }
 
 static void free_handle(clothhip_handle *h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     void *ptrs[] = {h->d_pos, h->d_prev, h->d_rest, h->d_cnt, h->d_active, h->d_tear, h->d_exec, h->d_ngrab, h->d_stats,
-                    h->d_sched, h->d_flat, h->d_flat_rest, h->d_hcnt, h->d_fz, h->d_fact, h->d_fscr, h->d_frec, h->d_frst, h->d_fobs, h->d_frobs, h->d_fsteps, h->d_fparg, h->d_fdone, h->d_fticks, h->d_fsum, h->d_fmt, h->d_resume, h->d_gather, h->d_wt_ent, h->d_wt_dep, h->d_lstc, h->d_levels, h->d_xy, h->d_radius, h->d_cov, h->d_vinv, h->d_oob};
+                    h->d_sched, h->d_flat, h->d_flat_rest, h->d_hcnt, h->d_fz, h->d_fact, h->d_fscr, h->d_frec, h->d_frst, h->d_fobs, h->d_frobs, h->d_fsteps, h->d_fparg, h->d_fdone, h->d_fticks, h->d_fsum, h->d_fmt, h->d_resume, h->d_gather, h->d_wt_ent, h->d_wt_dep, h->d_lstc, h->d_mat, h->d_levels, h->d_xy, h->d_radius, h->d_cov, h->d_vinv, h->d_oob};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (h->h_sched) (void)hipHostFree(h->h_sched);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -405,6 +424,7 @@ static void init_host_fields(clothhip_handle *h, const ClothParams &p, int n_env
     h->S = h->topo.S; h->Spad = h->wt.n_slots;               // rest-length arrays are kept in window-table slot order
     h->dbg = read_debug_knobs();
     h->gather = build_gather(h->topo, h->wt, h->Ppad);
+    h->mat.assign((size_t)n_envs, material_of(p));
 }
 
 extern "C" int clothhip_create(const ClothParams *params, int32_t n_envs, int32_t device, int32_t precision,
@@ -766,8 +786,63 @@ template <typename T> static StepArgs<T> make_args(clothhip_handle *h, const Clo
     if (sizeof(T) == 8) { a.pal_struct = (T)h->pal64[SPRING_STRUCTURAL]; a.pal_shear = (T)h->pal64[SPRING_SHEARING]; a.pal_bend = (T)h->pal64[SPRING_BENDING]; }
     else { a.pal_struct = (T)h->pal[SPRING_STRUCTURAL]; a.pal_shear = (T)h->pal[SPRING_SHEARING]; a.pal_bend = (T)h->pal[SPRING_BENDING]; }
     a.lstc = h->d_lstc;
+    a.mat = h->n_mixed ? (const DevConsts<T> *)h->d_mat : nullptr;
     a.fz = nullptr;
     return a;
+}
+
+// ---- per-env materials -------------------------------------------------------------------------------------------------------------------
+extern "C" int clothhip_set_material(clothhip_handle *h, int32_t env0, int32_t n, const ClothMaterial *m) {
+    if (int rc = check_range(h, env0, n)) return rc;
+    if (h->f_pending) return fail(CLOTHHIP_ESTATE, "clothhip_run_actions_begin still in flight: call clothhip_run_actions_end first");
+    const ClothMaterial own = material_of(h->prm);
+    for (int e = 0; m && e < n; e++)
+        if (int rc = check_material(h->prm, m[e], e)) return rc;
+    std::vector<ClothMaterial> next = h->mat;
+    for (int e = 0; e < n; e++) next[(size_t)env0 + e] = m ? m[e] : own;
+    int mixed = 0;
+    for (const ClothMaterial &v : next) mixed += memcmp(&v, &own, sizeof(own)) != 0 ? 1 : 0;
+    HIPCHECK(hipSetDevice(h->device));
+    if (mixed) {
+        // the device's table, rebuilt whole: every env's record by the ONE derivation (make_consts), in the handle's precision
+        const size_t bytes = (size_t)h->E * (h->precision == CLOTHHIP_F64 ? sizeof(DevConsts<double>) : sizeof(DevConsts<float>));
+        if (!h->d_mat) {
+            const hipError_t err = hipMalloc(&h->d_mat, bytes);
+            if (err != hipSuccess) { h->d_mat = nullptr; return fail(err == hipErrorOutOfMemory ? CLOTHHIP_ENOMEM : CLOTHHIP_EHIP, "hipMalloc of the material table failed: %s", hipGetErrorString(err)); }
+        }
+        std::vector<unsigned char> buf(bytes);
+        by_precision(h, [&](auto t) {
+            using T = decltype(t);
+            DevConsts<T> *d = (DevConsts<T> *)buf.data();
+            for (int e = 0; e < h->E; e++) d[e] = make_consts<T>(phys_of(h->prm, next[e]), h->N);
+        });
+        HIPCHECK(hipStreamSynchronize(h->stream));     // (a launch of clothhip_run_async may still be reading the table)
+        HIPCHECK(hipMemcpy(h->d_mat, buf.data(), bytes, hipMemcpyHostToDevice));
+    }
+    h->mat.swap(next);
+    h->n_mixed = mixed;
+    return 0;
+}
+
+extern "C" int clothhip_get_material(clothhip_handle *h, int32_t env0, int32_t n, ClothMaterial *m) {
+    if (int rc = check_range(h, env0, n)) return rc;
+    if (!m) return fail(CLOTHHIP_EINVAL, "m is NULL");
+    for (int e = 0; e < n; e++) m[e] = h->mat[(size_t)env0 + e];
+    return 0;
+}
+
+extern "C" int clothhip_selftest_material(const ClothParams *p, const ClothMaterial *m, int32_t precision, double out[7]) {
+    if (int rc = check_params(p)) return rc;
+    if (!out) return fail(CLOTHHIP_EINVAL, "out is NULL");
+    if (precision != CLOTHHIP_F64 && precision != CLOTHHIP_F32) return fail(CLOTHHIP_EINVAL, "precision must be 0 (f64) or 1 (f32)");
+    if (m) if (int rc = check_material(*p, *m, 0)) return rc;
+    const SpecPhys s = m ? phys_of(*p, *m) : phys_of(*p);
+    auto fill = [&](auto k) {
+        const double v[7] = {(double)k.mg, (double)k.ks_str, (double)k.ks_bend, (double)k.dsm, (double)k.damp, (double)k.one_m_fric, (double)k.tear_thresh};
+        memcpy(out, v, sizeof(v));
+    };
+    if (precision == CLOTHHIP_F64) fill(make_consts<double>(s, p->n_side)); else fill(make_consts<float>(s, p->n_side));
+    return 0;
 }
 
 // Which grid-specialised kernel (k_run_schedule<..., NS>, NS = 25 or 50) may run layout L -- 0: none, the generic build. Only if the
@@ -778,6 +853,7 @@ template <typename T> static StepArgs<T> make_args(clothhip_handle *h, const Clo
 static int spec_ns(const clothhip_handle *h, const Layout &L, bool with_palette) {
     if (read_debug_knobs().nospec) return 0;
     if (h->dbg.phase_mask != 15 || (h->N != 25 && h->N != 50)) return 0;
+    if (h->n_mixed) return 0;       // per-env materials: the specialised builds hold ONE material as literals and never read the table
     const int ns = h->N;
     // the physics constants the build has compiled in (cloth_common.hpp: spec_phys) must be this handle's
     if (!(phys_of(h->prm) == spec_phys(ns))) return 0;
@@ -1054,6 +1130,8 @@ extern "C" int clothhip_run_actions_begin(clothhip_handle *h, const ClothEpisode
         return fail(CLOTHHIP_ESTATE, "in-kernel tier-2 resets rebuild per-env rest lengths; upload per-env rest tables first (clothhip_set_state without CLOTHHIP_REST_SHARED)");
     if (tier2 && (size_t)3 * h->P * 8 > (size_t)160 * 1024) return fail(CLOTHHIP_ESTATE, "grid too large for the tier-2 reset scratch");
     if (!(ep->reduce_factor > 0) || ep->max_actions < 1) return fail(CLOTHHIP_EINVAL, "bad episode parameters");
+    if (h->relaxed && h->n_mixed)
+        return fail(CLOTHHIP_ESTATE, "clothhip_set_relaxed_order: the relaxed-order companion is a bench-only kernel; this handle holds per-env materials (clothhip_set_material)");
     HIPCHECK(hipSetDevice(h->device));
     // which of the handle's two layouts runs now (may synchronise and read the rest table back: long before the timed events) -- the
     // scratch check below is against THAT layout, not the previous launch's

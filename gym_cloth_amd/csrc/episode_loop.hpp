@@ -83,8 +83,8 @@ __global__ __launch_bounds__(NT, (Variant{(int)sizeof(T), NT, PPT, TAB, REST_REG
     uint16_t *olist = reinterpret_cast<uint16_t *>(smem + lay.olist);
     uint16_t *alist_end = olist + (Ppad - 1);            // active list grows downwards: entry k = alist_end[-k]
     Pt<T> *cpos = reinterpret_cast<Pt<T> *>(smem + lay.cpos);
-    const DevConsts<T> &k = A.k;                         // (every phase of the substep loop shadows this by its own freshly loaded copy: CLOTH_PHASE_ARGS)
-    (void)k;
+    // (no `k` at this scope: every phase loads its own copy of the constants -- CLOTH_PHASE_ARGS -- from the kernel arguments or, on a handle with
+    //  per-env materials, from the env's record of StepArgs::mat; a use outside a phase would silently read the handle's and must not compile)
     const T *g_rest = A.rest + (size_t)e * A.rest_stride;
     const WEnt<T> *wtab = reinterpret_cast<const WEnt<T> *>(smem + lay.wtab);    // V.table_in_lds() only
     // rest length of the spring in window-table slot i (Hooke, pre-pass; the sweep streams its own)

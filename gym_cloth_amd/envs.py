@@ -18,7 +18,7 @@ import numpy as np
 import ctypes as _ctypes
 import yaml
 
-from . import seeding
+from . import _lib, seeding
 from .batch import ClothBatch, make_schedules
 
 _REWARD_THRESHOLDS = {           # cloth_env.py:42-50
@@ -211,6 +211,59 @@ class ClothVecEnv(object):
             out.append(s2)
         self._pending = [None] * self.E                                # reset scripts pre-drawn from the old generators
         return out
+
+    # ---- per-env materials (physics domain randomisation, material sweeps) ------------------------------------
+    @property
+    def material(self):
+        """Every env's material, a read-only structured array [E] with the fields density, ks, damping, plane_friction,
+        tear_thresh, gravity (the cfg's values for envs never given one)."""
+        m = self.batch.get_material()
+        m.flags.writeable = False
+        return m
+
+    def _env_indices(self, envs):
+        idx = np.arange(self.E) if envs is None else np.atleast_1d(np.asarray(envs))
+        if idx.dtype == bool:
+            if idx.shape != (self.E,):
+                raise ValueError("a boolean env mask must have shape (%d,)" % self.E)
+            idx = np.nonzero(idx)[0]
+        idx = idx.astype(np.int64)
+        if idx.size and (idx.min() < 0 or idx.max() >= self.E):
+            raise ValueError("env index outside [0, %d)" % self.E)
+        return idx
+
+    def set_material(self, envs=None, **fields):
+        """Change the material of the chosen envs (None: all; indices or a boolean mask): the named fields -- scalars or arrays,
+        broadcast over the chosen envs -- are set, the others keep their current value. It belongs to the env slot and survives
+        resets; the particle state is not touched. What Cloth.update() reads from the cfg on every call (cloth.pyx:175-186)."""
+        unknown = [k for k in fields if k not in _lib.MATERIAL_FIELDS]
+        if unknown:
+            raise ValueError("unknown material field(s) %s; a material has %s" % (unknown, _lib.MATERIAL_FIELDS))
+        idx = self._env_indices(envs)
+        if idx.size == 0:
+            return
+        lo, hi = int(idx.min()), int(idx.max()) + 1             # only the touched range of envs is read and rewritten
+        m = self.batch.get_material(lo, hi - lo)
+        for k, v in fields.items():
+            m[k][idx - lo] = np.broadcast_to(np.asarray(v, dtype=np.float64), idx.shape)
+        self.batch.set_material(m, env0=lo)
+
+    def randomize_material(self, ranges, seed=None, envs=None):
+        """Draw the fields named in `ranges` ({field: (low, high)}, uniform) for the chosen envs, from a RandomState of its own
+        seeded by `seed`: the envs' np_randoms do not advance (the reset streams stay the reference's), and the same seed gives the
+        same materials. Returns the new material table. Call it between launches to resample."""
+        unknown = [k for k in ranges if k not in _lib.MATERIAL_FIELDS]
+        if unknown:
+            raise ValueError("unknown material field(s) %s; a material has %s" % (unknown, _lib.MATERIAL_FIELDS))
+        rng = np.random.RandomState(seed)
+        idx = self._env_indices(envs)
+        draws = {}
+        for k in _lib.MATERIAL_FIELDS:                # drawn in the fixed field order, whatever order `ranges` names them in
+            if k in ranges:
+                lo, hi = ranges[k]
+                draws[k] = rng.uniform(float(lo), float(hi), size=idx.shape)
+        self.set_material(idx, **draws)
+        return self.material
 
     @property
     def state(self):
@@ -931,6 +984,14 @@ class ClothEnv(object):
         if atype == 'over_xy_plane':
             return self.action_space.sample()
         raise ValueError(atype)
+
+    def set_material(self, **fields):
+        """The env's material: density, ks, damping, plane_friction, tear_thresh, gravity (ClothVecEnv.set_material)."""
+        self._vec.set_material(None, **fields)
+
+    @property
+    def material(self):
+        return self._vec.material[0]
 
     def save_state(self, cloth_file):
         """cloth_env.py:343-350 (npz of SoA arrays instead of a pickle of Python objects)."""

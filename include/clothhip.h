@@ -134,6 +134,27 @@ int clothhip_reset_flat(clothhip_handle *h, const uint8_t *mask);
 int clothhip_get_tear(clothhip_handle *h, uint8_t *tear);
 int clothhip_set_tear(clothhip_handle *h, const uint8_t *tear);
 
+/* Per-env MATERIAL: the six quantities of ClothParams that describe the fabric and its world but not the grid. The reference reads them
+ * from the cfg in every Cloth.update() call (cloth.pyx:175-186: density -> mass and mass * gravity, ks, damping, plane_friction; used at
+ * :240-241 (Verlet: (dt*dt)/mass, 1 - damping/100), :368 (1. - plane_friction) and :272 (tear_thresh)), so they are ordinary inputs per
+ * cloth: one handle may step cloths of different fabrics. Everything else of ClothParams stays per handle (grid, thickness, rates, ...). */
+typedef struct ClothMaterial { double density, ks, damping, plane_friction, tear_thresh, gravity; } ClothMaterial;
+/* Give envs [env0, env0+n) the materials m[n]; m NULL: these envs go back to the handle's ClothParams. A material belongs to the env
+ * SLOT: set_state, reset_flat, the resets inside an episode launch and the parked operations of a time-sliced launch keep it; only this
+ * call changes it. Values follow the rules clothhip_create applies to these fields (density > 0): a bad value or range returns
+ * CLOTHHIP_EINVAL and changes nothing. CLOTHHIP_ESTATE between clothhip_run_actions_begin and _end. Touches neither the particle state nor
+ * the operations in flight. While any env's material differs bitwise from the handle's parameters the handle runs the generic stepper
+ * build (clothhip_last_specialised reports 0), which reads every env's constants from a device table; without one it runs exactly the
+ * kernels and the bits it runs without this call. With clothhip_set_relaxed_order on, such a handle gets CLOTHHIP_ESTATE from
+ * clothhip_run_actions* (the companion kernel is bench-only). */
+int clothhip_set_material(clothhip_handle *h, int32_t env0, int32_t n, const ClothMaterial *m);
+/* The effective materials of envs [env0, env0+n) into m[n] (the handle's parameters for envs never given one). */
+int clothhip_get_material(clothhip_handle *h, int32_t env0, int32_t n, ClothMaterial *m);
+/* Host only: the seven stepper constants a material turns into on a handle of `params` and `precision` (m NULL: the handle's own), by the
+ * one derivation the kernels' constants come from, widened to double: out = {mass * gravity, ks * 1.0, ks * 0.2, (dt*dt)/mass,
+ * 1 - damping/100, 1. - plane_friction, tear_thresh}. */
+int clothhip_selftest_material(const ClothParams *params, const ClothMaterial *m, int32_t precision, double out[7]);
+
 /* Gripper.grab_top(x, y) (gripper.pyx:23-42) for every active env: xy[E][2]; radius[E] or NULL
  * (= params.grip_radius; cloth_env.py:436-442 mutates it for force_grab); active[E] or NULL (= all).
  * n_grabbed[E] receives the number of points appended to grabbed_pts by THIS call (0 = nothing grabbed). */
