@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("CLOTHHIP_LIB") or os.path.join(_HERE, "libclothhip.so
 
 F64, F32 = 0, 1
 REST_SHARED, KEEP_TEAR = 1, 2           # clothhip_set_state flags
+FORK_STATE_ONLY = 1                     # clothhip_fork flags
 ABI_VERSION = 7
 
 OK, EINVAL, ENODEV, EHIP, ENOMEM, ESTATE = 0, -1, -2, -3, -4, -5
@@ -146,6 +147,9 @@ SYMBOLS = [
     ("clothhip_set_relaxed_order", C.c_int, [_vp, C.c_int32]),
     ("clothhip_set_material", C.c_int, [_vp, C.c_int32, C.c_int32, _vp]),
     ("clothhip_get_material", C.c_int, [_vp, C.c_int32, C.c_int32, _vp]),
+    ("clothhip_fork", C.c_int, [_vp, _i32p, _vp, _i32p, C.c_int32, C.c_int32]),
+    ("clothhip_in_flight", C.c_int, [_vp, _u8p]),
+    ("clothhip_get_pin_counts", C.c_int, [_vp, C.c_int32, C.c_int32, _u8p]),
     ("clothhip_selftest_material", C.c_int, [_PP, C.POINTER(ClothMaterial), C.c_int32, _dp]),
     ("clothhip_selftest_windows", C.c_int, [_PP, _i32p, _i32p, _i32p, _i32p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_int32]),
     ("clothhip_selftest_layout", C.c_int, [_PP, C.c_int32, C.c_int32, C.c_int32, _i32p, C.c_int32]),

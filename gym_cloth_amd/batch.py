@@ -138,6 +138,34 @@ class ClothBatch(object):
         check(self._L.clothhip_get_material(self._h, int(env0), n, m.ctypes.data_as(C.c_void_p)))
         return m
 
+    # ---- device-side copies of whole cloths ---------------------------------------------------------------
+    def fork_from(self, src_batch, src_env, dst_env=None, state_only=False):
+        """Make env dst_env[j] of THIS batch a copy of env src_env[j] of `src_batch`, on the device (clothhip_fork): positions,
+        previous positions, the pin bytes as they are (grab multiplicities, pinned-from-outside), the tear flag, the rest lengths
+        and -- unless state_only -- the material. One source may feed many destinations. dst_env None: envs 0 .. len(src_env)-1.
+        The batches must agree in device, precision and grid; src_batch may be this batch when the two lists are disjoint."""
+        src = np.ascontiguousarray(np.atleast_1d(src_env), dtype=np.int32)
+        dst = np.arange(len(src), dtype=np.int32) if dst_env is None else np.ascontiguousarray(np.atleast_1d(dst_env), dtype=np.int32)
+        if src.ndim != 1 or dst.shape != src.shape:
+            raise ValueError("src_env and dst_env must be index lists of one length")
+        check(self._L.clothhip_fork(self._h, _lib.i32p(dst), src_batch._h, _lib.i32p(src), len(src),
+                                    _lib.FORK_STATE_ONLY if state_only else 0))
+
+    def pin_counts(self, env0=0, n=None):
+        """The raw pin byte of every point, uint8[n, P] (clothhip_get_pin_counts): bits 0-6 how many times the gripper holds the
+        point, bit 7 pinned from outside (pin_points). get_state's `pinned` is this != 0."""
+        n = self.E - env0 if n is None else int(n)
+        c = np.empty((n, self.P), dtype=np.uint8)
+        check(self._L.clothhip_get_pin_counts(self._h, int(env0), n, _lib.u8p(c)))
+        return c
+
+    def in_flight(self):
+        """bool[E]: the env holds an operation that a time-sliced episode launch cut and the next launch continues
+        (clothhip_in_flight)."""
+        p = np.zeros(self.E, dtype=np.uint8)
+        check(self._L.clothhip_in_flight(self._h, _lib.u8p(p)))
+        return p.astype(bool)
+
     def get_rest(self, env0=0, n=None):
         """Spring.rest_length per env in reference list order, [n, S]."""
         n = self.E - env0 if n is None else n

@@ -119,6 +119,68 @@ __global__ void k_clear_resume(EpResume *r, const uint8_t *mask, const ClothSche
     r[e].valid = 0;
 }
 
+// ---- clothhip_fork: a whole cloth from env slot to env slot, device to device -------------------------------------------------------------
+// nbytes from src to dst by the whole workgroup, bits untouched: 16-byte vectors while both addresses allow them (the state rows always do:
+// Ppad and Spad are multiples of 64 elements and hipMalloc aligns to 256 bytes), else 4-byte words (a DevConsts<float> record is 52 bytes
+// into its table), and what is left by the plain path, byte by byte.
+__device__ __forceinline__ void fork_copy(void *__restrict__ dst, const void *__restrict__ src, size_t nbytes) {
+    const size_t tid = threadIdx.x, nt = blockDim.x;
+    const uintptr_t both = (uintptr_t)dst | (uintptr_t)src;
+    size_t done = 0;
+    if ((both & 15) == 0) {
+        const size_t nv = nbytes / 16;
+        const uint4 *__restrict__ s = (const uint4 *)src; uint4 *__restrict__ d = (uint4 *)dst;
+        size_t i = tid;
+        for (; i + nt < nv; i += 2 * nt) {             // two loads in flight per thread before the first store
+            const uint4 a = s[i], b = s[i + nt];
+            d[i] = a; d[i + nt] = b;
+        }
+        if (i < nv) d[i] = s[i];
+        done = nv * 16;
+    } else if ((both & 3) == 0) {
+        const size_t nw = nbytes / 4;
+        const uint32_t *__restrict__ s = (const uint32_t *)src; uint32_t *__restrict__ d = (uint32_t *)dst;
+        for (size_t i = tid; i < nw; i += nt) d[i] = s[i];
+        done = nw * 4;
+    }
+    const unsigned char *__restrict__ s = (const unsigned char *)src; unsigned char *__restrict__ d = (unsigned char *)dst;
+    for (size_t i = done + tid; i < nbytes; i += nt) d[i] = s[i];
+}
+
+// All sizes in bytes, all offsets 64-bit. rest_* / mat_* nullptr: that part is not copied (shared rest tables that are equal; STATE_ONLY or
+// no device material table in play). rest_src_stride 0: the source's one shared table feeds every destination row.
+struct ForkArgs {
+    unsigned char *pos_dst, *prev_dst, *cnt_dst, *rest_dst, *mat_dst;
+    const unsigned char *pos_src, *prev_src, *cnt_src, *rest_src, *mat_src;
+    int32_t *tear_dst; const int32_t *tear_src;
+    EpResume *resume_dst;                 // the destination's parked time-slice operations: dropped for the envs written here
+    const int32_t *dst_env, *src_env;     // [n]
+    size_t pos_bytes, cnt_bytes, rest_bytes, rest_src_stride, mat_bytes;
+};
+
+// One workgroup per DESTINATION env j: the cloth of the source's env src_env[j] -- positions and previous positions [3][Ppad], the pin
+// bytes (grab multiplicity and the pinned-from-outside bit as they are), the tear flag, and where asked the rest-length row and the
+// material record. Many destinations may name one source (branching); no destination is a source of the same call (checked on the host).
+// Nothing is computed: the kernel is a copy and runs at memory bandwidth.
+__global__ __launch_bounds__(256) void k_fork(ForkArgs A) {
+    const size_t j = blockIdx.x;
+    const size_t d = (size_t)A.dst_env[j], s = (size_t)A.src_env[j];
+    fork_copy(A.pos_dst + d * A.pos_bytes, A.pos_src + s * A.pos_bytes, A.pos_bytes);
+    fork_copy(A.prev_dst + d * A.pos_bytes, A.prev_src + s * A.pos_bytes, A.pos_bytes);
+    fork_copy(A.cnt_dst + d * A.cnt_bytes, A.cnt_src + s * A.cnt_bytes, A.cnt_bytes);
+    if (A.rest_dst) fork_copy(A.rest_dst + d * A.rest_bytes, A.rest_src + s * A.rest_src_stride, A.rest_bytes);
+    if (A.mat_dst) fork_copy(A.mat_dst + d * A.mat_bytes, A.mat_src + s * A.mat_bytes, A.mat_bytes);
+    if (threadIdx.x == 0) {
+        A.tear_dst[d] = A.tear_src[s];
+        if (A.resume_dst) A.resume_dst[d].valid = 0;
+    }
+}
+
+// A handle that leaves its one shared rest table for per-env tables: rows 1 .. E-1 <- row 0 (one workgroup per row)
+__global__ __launch_bounds__(256) void k_replicate_rest(unsigned char *rest, size_t row_bytes) {
+    fork_copy(rest + ((size_t)blockIdx.x + 1) * row_bytes, rest, row_bytes);
+}
+
 __global__ void k_selftest(int op, const double *a, const double *b, double *out, long long n) {
     long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;

@@ -6,6 +6,7 @@
 #include <climits>
 #include <cmath>
 #include <cstdarg>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -141,6 +142,12 @@ struct clothhip_handle {
     std::vector<uint32_t> gather;       // the gather table (host copy of d_gather): the LEAN stencil checks read it
     std::vector<unsigned char> stage;   // host staging for layout conversion
     std::vector<double> flat_rest;
+    // clothhip_fork: the bytes of the ONE shared rest table as clothhip_set_state last uploaded them (handle precision, slot order) -- the only
+    // writer of a shared table, so two shared tables are equal exactly when these mirrors are; the device index lists of a fork; the event
+    // that orders a fork after the source handle's stream
+    std::vector<unsigned char> shared_rest;
+    int32_t *d_fork_idx = nullptr, *h_fork_idx = nullptr; size_t cap_fork_idx = 0;   // (h_: pinned staging, so that the upload is a plain DMA)
+    hipEvent_t ev_fork = nullptr;
 };
 
 // f(float{}) or f(double{}) by the handle's precision: a launch that exists in both precisions is written once, as a generic lambda
@@ -246,16 +253,19 @@ static void free_handle(clothhip_handle *h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     void *ptrs[] = {h->d_pos, h->d_prev, h->d_rest, h->d_cnt, h->d_active, h->d_tear, h->d_exec, h->d_ngrab, h->d_stats,
-                    h->d_sched, h->d_flat, h->d_flat_rest, h->d_hcnt, h->d_fz, h->d_fact, h->d_fscr, h->d_frec, h->d_frst, h->d_fobs, h->d_frobs, h->d_fsteps, h->d_fparg, h->d_fdone, h->d_fticks, h->d_fsum, h->d_fmt, h->d_resume, h->d_gather, h->d_wt_ent, h->d_wt_dep, h->d_lstc, h->d_mat, h->d_levels, h->d_xy, h->d_radius, h->d_cov, h->d_vinv, h->d_oob};
+                    h->d_sched, h->d_flat, h->d_flat_rest, h->d_hcnt, h->d_fz, h->d_fact, h->d_fscr, h->d_frec, h->d_frst, h->d_fobs, h->d_frobs, h->d_fsteps, h->d_fparg, h->d_fdone, h->d_fticks, h->d_fsum, h->d_fmt, h->d_resume, h->d_gather, h->d_wt_ent, h->d_wt_dep, h->d_lstc, h->d_mat, h->d_fork_idx, h->d_levels, h->d_xy, h->d_radius, h->d_cov, h->d_vinv, h->d_oob};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (h->h_sched) (void)hipHostFree(h->h_sched);
+    if (h->h_fork_idx) (void)hipHostFree(h->h_fork_idx);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
+    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
 
 static int spec_ns(const clothhip_handle *h, const Layout &L, bool with_palette = true);
+static int grow(void **p, size_t *cap, size_t need);
 
 // The LDS a layout leaves the in-kernel metrics (from the hash table to the end of the allocation) against what they need; the
 // allocation is padded behind the layout's end when that fits the budget (the kernel addresses LDS by the layout's offsets: bytes
@@ -640,6 +650,7 @@ extern "C" int clothhip_set_state(clothhip_handle *h, int32_t env0, int32_t n, c
         HIPCHECK(hipMemcpy(dst, buf.data(), buf.size(), hipMemcpyHostToDevice));
         h->rest_stride = rest_shared ? 0 : h->Spad;
         h->lean_dirty = true;
+        if (rest_shared) h->shared_rest.swap(buf);       // (clothhip_fork compares shared tables by this mirror)
     }
     return 0;
 }
@@ -792,18 +803,15 @@ template <typename T> static StepArgs<T> make_args(clothhip_handle *h, const Clo
 }
 
 // ---- per-env materials -------------------------------------------------------------------------------------------------------------------
-extern "C" int clothhip_set_material(clothhip_handle *h, int32_t env0, int32_t n, const ClothMaterial *m) {
-    if (int rc = check_range(h, env0, n)) return rc;
-    if (h->f_pending) return fail(CLOTHHIP_ESTATE, "clothhip_run_actions_begin still in flight: call clothhip_run_actions_end first");
+// The one path by which a handle's materials change (clothhip_set_material, clothhip_fork): `next` becomes the host vector, n_mixed follows, and
+// while any env differs from the handle's parameters the device's table is (created and) rebuilt whole -- unless `upload` is false: the
+// caller has the device copy the records it changes (a fork between two handles whose tables are both live).
+static int apply_materials(clothhip_handle *h, std::vector<ClothMaterial> &next, bool upload) {
     const ClothMaterial own = material_of(h->prm);
-    for (int e = 0; m && e < n; e++)
-        if (int rc = check_material(h->prm, m[e], e)) return rc;
-    std::vector<ClothMaterial> next = h->mat;
-    for (int e = 0; e < n; e++) next[(size_t)env0 + e] = m ? m[e] : own;
     int mixed = 0;
     for (const ClothMaterial &v : next) mixed += memcmp(&v, &own, sizeof(own)) != 0 ? 1 : 0;
     HIPCHECK(hipSetDevice(h->device));
-    if (mixed) {
+    if (mixed && upload) {
         // the device's table, rebuilt whole: every env's record by the ONE derivation (make_consts), in the handle's precision
         const size_t bytes = (size_t)h->E * (h->precision == CLOTHHIP_F64 ? sizeof(DevConsts<double>) : sizeof(DevConsts<float>));
         if (!h->d_mat) {
@@ -824,10 +832,138 @@ extern "C" int clothhip_set_material(clothhip_handle *h, int32_t env0, int32_t n
     return 0;
 }
 
+extern "C" int clothhip_set_material(clothhip_handle *h, int32_t env0, int32_t n, const ClothMaterial *m) {
+    if (int rc = check_range(h, env0, n)) return rc;
+    if (h->f_pending) return fail(CLOTHHIP_ESTATE, "clothhip_run_actions_begin still in flight: call clothhip_run_actions_end first");
+    const ClothMaterial own = material_of(h->prm);
+    for (int e = 0; m && e < n; e++)
+        if (int rc = check_material(h->prm, m[e], e)) return rc;
+    std::vector<ClothMaterial> next = h->mat;
+    for (int e = 0; e < n; e++) next[(size_t)env0 + e] = m ? m[e] : own;
+    return apply_materials(h, next, true);
+}
+
 extern "C" int clothhip_get_material(clothhip_handle *h, int32_t env0, int32_t n, ClothMaterial *m) {
     if (int rc = check_range(h, env0, n)) return rc;
     if (!m) return fail(CLOTHHIP_EINVAL, "m is NULL");
     for (int e = 0; e < n; e++) m[e] = h->mat[(size_t)env0 + e];
+    return 0;
+}
+
+// ---- clothhip_fork: whole cloths between env slots and handles, on the device ---------------------------------------------------------------
+// the fields of ClothParams a material does not override, bit for bit: two handles that agree in them derive the same DevConsts record from
+// the same material, so a fork may copy the record on the device instead of deriving it again
+static bool same_non_material_params(const ClothParams &a, const ClothParams &b) {
+    ClothParams x = a, y = b;
+    for (ClothParams *p : {&x, &y}) { p->density = 1; p->ks = 0; p->damping = 0; p->plane_friction = 0; p->tear_thresh = 0; p->gravity = 0; p->_pad = 0; }
+    return memcmp(&x, &y, sizeof(x)) == 0;
+}
+
+extern "C" int clothhip_fork(clothhip_handle *dst, const int32_t *dst_env, clothhip_handle *src, const int32_t *src_env, int32_t n, int32_t flags) {
+    if (!dst || !src) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (n < 0 || (n > 0 && (!dst_env || !src_env))) return fail(CLOTHHIP_EINVAL, "bad index lists");
+    if (flags & ~CLOTHHIP_FORK_STATE_ONLY) return fail(CLOTHHIP_EINVAL, "unknown flags %d", flags);
+    if (dst->device != src->device) return fail(CLOTHHIP_EINVAL, "fork across devices (%d <- %d)", dst->device, src->device);
+    if (dst->precision != src->precision) return fail(CLOTHHIP_EINVAL, "fork between handles of different precision");
+    if (dst->N != src->N) return fail(CLOTHHIP_EINVAL, "fork between grids of %d and %d points a side", dst->N, src->N);
+    if (dst->f_pending || src->f_pending) return fail(CLOTHHIP_ESTATE, "clothhip_run_actions_begin still in flight: call clothhip_run_actions_end first");
+    {
+        std::vector<uint8_t> seen((size_t)dst->E, 0);
+        for (int j = 0; j < n; j++) {
+            if (dst_env[j] < 0 || dst_env[j] >= dst->E) return fail(CLOTHHIP_EINVAL, "dst_env[%d] = %d outside [0,%d)", j, dst_env[j], dst->E);
+            if (src_env[j] < 0 || src_env[j] >= src->E) return fail(CLOTHHIP_EINVAL, "src_env[%d] = %d outside [0,%d)", j, src_env[j], src->E);
+            if (seen[dst_env[j]]) return fail(CLOTHHIP_EINVAL, "env %d occurs twice in dst_env", dst_env[j]);
+            seen[dst_env[j]] = 1;
+        }
+        for (int j = 0; dst == src && j < n; j++)
+            if (seen[src_env[j]]) return fail(CLOTHHIP_EINVAL, "env %d is both a source and a destination of one fork", src_env[j]);
+    }
+    if (n == 0) return 0;
+    // (two uniform handles of one material: every destination env already holds what its source holds -- nothing to do for the materials)
+    const ClothMaterial own_dst = material_of(dst->prm), own_src = material_of(src->prm);
+    const bool with_mat = !(flags & CLOTHHIP_FORK_STATE_ONLY) &&
+                          !(dst->n_mixed == 0 && src->n_mixed == 0 && memcmp(&own_dst, &own_src, sizeof(own_dst)) == 0);
+    std::vector<ClothMaterial> next;
+    if (with_mat) {
+        next = dst->mat;
+        for (int j = 0; j < n; j++) {
+            if (int rc = check_material(dst->prm, src->mat[src_env[j]], j)) return rc;
+            next[dst_env[j]] = src->mat[src_env[j]];
+        }
+    }
+    HIPCHECK(hipSetDevice(dst->device));
+    if (dst->cap_fork_idx < (size_t)2 * n * 4 || !dst->h_fork_idx) {
+        if (dst->h_fork_idx) HIPCHECK(hipHostFree(dst->h_fork_idx));
+        dst->h_fork_idx = nullptr;
+        if (int rc = grow((void **)&dst->d_fork_idx, &dst->cap_fork_idx, (size_t)2 * n * 4)) return rc;
+        HIPCHECK(hipHostMalloc((void **)&dst->h_fork_idx, dst->cap_fork_idx, hipHostMallocDefault));
+    }
+    if (dst->stream != src->stream) {                  // the copy reads what the source's stream has enqueued so far
+        if (!dst->ev_fork) HIPCHECK(hipEventCreateWithFlags(&dst->ev_fork, hipEventDisableTiming));
+        HIPCHECK(hipEventRecord(dst->ev_fork, src->stream));
+        HIPCHECK(hipStreamWaitEvent(dst->stream, dst->ev_fork, 0));
+    }
+    // materials: the host vector, n_mixed and so spec_ns by clothhip_set_material's path; the records themselves on the device when both
+    // tables are live and derived under the same parameters, else the destination's table is rebuilt whole as set_material does
+    bool mat_on_device = false;
+    if (with_mat) {
+        mat_on_device = dst->n_mixed > 0 && src->n_mixed > 0 && dst->d_mat && src->d_mat && same_non_material_params(dst->prm, src->prm);
+        if (int rc = apply_materials(dst, next, !mat_on_device)) return rc;
+        if (dst->n_mixed == 0) mat_on_device = false;
+    }
+    // rest lengths: two handles that each share ONE table keep doing so when the tables are bitwise equal (the mirrors of what set_state
+    // uploaded); in every other case the destination takes per-env tables, as set_state does when it is given per-env rest
+    const size_t rest_bytes = (size_t)dst->Spad * dst->tsz;
+    const bool rest_equal_shared = dst == src ? dst->rest_stride == 0
+                                              : dst->rest_stride == 0 && src->rest_stride == 0 && !dst->shared_rest.empty() &&
+                                                    dst->shared_rest.size() == src->shared_rest.size() &&
+                                                    memcmp(dst->shared_rest.data(), src->shared_rest.data(), dst->shared_rest.size()) == 0;
+    const bool copy_rest = !rest_equal_shared;
+    if (copy_rest && dst->rest_stride == 0) {
+        if (dst->E > 1) hipLaunchKernelGGL(k_replicate_rest, dim3(dst->E - 1), dim3(256), 0, dst->stream, (unsigned char *)dst->d_rest, rest_bytes);
+        HIPCHECK(hipGetLastError());
+        dst->rest_stride = dst->Spad;
+        dst->lean_dirty = true;
+    }
+    memcpy(dst->h_fork_idx, dst_env, (size_t)n * 4); memcpy(dst->h_fork_idx + n, src_env, (size_t)n * 4);   // (free again: every fork ends synchronised)
+    HIPCHECK(hipMemcpyAsync(dst->d_fork_idx, dst->h_fork_idx, (size_t)2 * n * 4, hipMemcpyHostToDevice, dst->stream));
+    ForkArgs a;
+    a.pos_dst = (unsigned char *)dst->d_pos; a.prev_dst = (unsigned char *)dst->d_prev; a.cnt_dst = dst->d_cnt;
+    a.pos_src = (const unsigned char *)src->d_pos; a.prev_src = (const unsigned char *)src->d_prev; a.cnt_src = src->d_cnt;
+    a.rest_dst = copy_rest ? (unsigned char *)dst->d_rest : nullptr; a.rest_src = (const unsigned char *)src->d_rest;
+    a.mat_dst = mat_on_device ? (unsigned char *)dst->d_mat : nullptr; a.mat_src = (const unsigned char *)src->d_mat;
+    a.tear_dst = dst->d_tear; a.tear_src = src->d_tear;
+    a.resume_dst = dst->d_resume;
+    a.dst_env = dst->d_fork_idx; a.src_env = dst->d_fork_idx + n;
+    a.pos_bytes = (size_t)3 * dst->Ppad * dst->tsz; a.cnt_bytes = (size_t)dst->Ppad;
+    a.rest_bytes = rest_bytes; a.rest_src_stride = (size_t)src->rest_stride * src->tsz;
+    a.mat_bytes = dst->precision == CLOTHHIP_F64 ? sizeof(DevConsts<double>) : sizeof(DevConsts<float>);
+    hipLaunchKernelGGL(k_fork, dim3(n), dim3(256), 0, dst->stream, a);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(dst->stream));
+    return 0;
+}
+
+extern "C" int clothhip_in_flight(clothhip_handle *h, uint8_t *parked) {
+    if (!h || !parked) return fail(CLOTHHIP_EINVAL, "NULL argument");
+    if (h->f_pending) return fail(CLOTHHIP_ESTATE, "clothhip_run_actions_begin still in flight: call clothhip_run_actions_end first");
+    HIPCHECK(hipSetDevice(h->device));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    std::vector<int32_t> v((size_t)h->E);
+    static_assert(offsetof(EpResume, valid) == 0, "the valid flag leads the record");
+    HIPCHECK(hipMemcpy2D(v.data(), 4, h->d_resume, sizeof(EpResume), 4, (size_t)h->E, hipMemcpyDeviceToHost));
+    for (int e = 0; e < h->E; e++) parked[e] = v[e] ? 1 : 0;
+    return 0;
+}
+
+extern "C" int clothhip_get_pin_counts(clothhip_handle *h, int32_t env0, int32_t n, uint8_t *cnt) {
+    if (int rc = check_range(h, env0, n)) return rc;
+    if (!cnt) return fail(CLOTHHIP_EINVAL, "cnt is NULL");
+    HIPCHECK(hipSetDevice(h->device));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    std::vector<uint8_t> c((size_t)n * h->Ppad);
+    HIPCHECK(hipMemcpy(c.data(), h->d_cnt + (size_t)env0 * h->Ppad, c.size(), hipMemcpyDeviceToHost));
+    for (int e = 0; e < n; e++) memcpy(cnt + (size_t)e * h->P, c.data() + (size_t)e * h->Ppad, (size_t)h->P);
     return 0;
 }
 

@@ -3,7 +3,8 @@ reset, act until done, append obs / act / rew / done / info per step, pickle the
 
 With the oracle-corner policy the whole loop -- policy, steps, episode resets -- runs on the device
 (ClothVecEnv.step_many(policy='oracle_corner')): the host only cuts the per-slot records into episodes. Any other
-policy object (gym_cloth_amd/policies.py, or anything with get_action(obs, t)) is driven through ClothVecEnv.step.
+policy object (gym_cloth_amd/policies.py -- LookaheadPolicy included --, or anything with get_action(obs, t)) is driven through
+ClothVecEnv.step.
 
 An episode has the reference's layout (analytic.py:866-882):
     {'obs': [obs_0 (what reset() returned), obs_1, ...], 'act': [...], 'rew': [...], 'done': [...], 'info': [dict, ...]}

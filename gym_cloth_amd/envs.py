@@ -123,6 +123,69 @@ def decode_actions(actions, low, high, clip_act_space, delta_actions, reduce_fac
     return dict(x=x_coord, y=y_coord, x_dir_r=x_dir_r, y_dir_r=y_dir_r, iters_pull=iters_pull, bounds=bounds)
 
 
+_REWARD_CONSTS = dict(neg_living_rew=0.0, nogrip_penalty=-0.01, tear_penalty=0.0, oob_penalty=0.0, cover_success=5.,
+                      act_bound_factor=1.0, act_pen_limit=3.0)            # cloth_env.py:132-141
+
+
+def compute_reward(reward_type, actions, exit_early, cov, vinv, oob, mask, have_tear, prev_reward, height=None,
+                   clip_act_space=True, act_low=None, act_high=None, consts=_REWARD_CONSTS):
+    """ClothEnv._reward (cloth_env.py:536-683) as a pure function of its inputs, vectorised over n cloths: nothing is read from or
+    written to an env, so the branches of a lookahead can be rewarded without touching the env they started from.
+
+    have_tear is the flag AFTER the action, prev_reward what the '-delta' types subtract (the env's _prev_reward), height the
+    fraction of points below half the thickness (only the 'height' types read it). Returns (rew[n], tracked): rew is 0 where mask is
+    False; tracked is the value _prev_reward takes for the envs in mask ('-delta' types), or None."""
+    n = len(cov)
+    rew = np.zeros(n)
+    rew += np.where(have_tear, consts['tear_penalty'], np.where(oob, consts['oob_penalty'], 0.0))   # :557-562
+    rew += np.where(exit_early, consts['nogrip_penalty'], 0.0)                                      # :563-565
+    if not clip_act_space:                                                                          # :579-593
+        a = np.asarray(actions, dtype=np.float64).reshape(n, 4)
+        diff = np.where(a < act_low, act_low - a, np.where(a > act_high, a - act_high, 0.0))
+        pen = -np.minimum(diff ** 2, consts['act_pen_limit']) * consts['act_bound_factor']
+        rew += pen.sum(axis=1)
+    rew += np.where(cov > _REWARD_THRESHOLDS['coverage'], consts['cover_success'], 0.0)             # :648-650
+    rew += consts['neg_living_rew']
+    tracked = None
+    rt = reward_type                                                                                # :656-679
+    if rt == 'coverage':
+        rew += cov
+    elif rt == 'coverage-delta':
+        tracked = cov
+    elif rt == 'height':
+        rew += height
+    elif rt == 'height-delta':
+        tracked = height
+    elif rt == 'variance':
+        rew += vinv
+    elif rt == 'variance-delta':
+        tracked = vinv
+    elif rt == 'folding-number':
+        raise NotImplementedError()
+    else:
+        raise ValueError(rt)
+    if tracked is not None:
+        rew += tracked - prev_reward
+    return np.where(mask, rew, 0.0), tracked
+
+
+def compute_terminal(reward_type, max_actions, num_steps, have_tear, oob, current_coverage, mask):
+    """ClothEnv._terminal (cloth_env.py:684-715) as a pure function: num_steps, have_tear and current_coverage AFTER the action."""
+    done = (num_steps >= max_actions) | have_tear | oob                                             # :692-703
+    done = done | (current_coverage > _REWARD_THRESHOLDS[reward_type])                              # :706-710
+    return done & mask
+
+
+class ClothSnapshot(object):
+    """What ClothVecEnv.snapshot() returns: opaque. `batch` holds the E cloths on the device, `host` the per-env host state."""
+
+    def __init__(self, batch, host):
+        self.batch, self.host = batch, host
+
+    def close(self):
+        self.batch.close()
+
+
 class ClothVecEnv(object):
     metadata = {'render.modes': ['human']}
 
@@ -192,9 +255,15 @@ class ClothVecEnv(object):
         self._ep_done = np.zeros(E, dtype=bool)                      # episode over, reset pending (step_many's auto-reset)
         self._pending = [None] * E                                   # pre-drawn reset scripts of step_many, per env
         self.total_substeps = 0                                      # executed update() calls, all envs
+        self._version = 0                                            # counts the calls that change the env (commit checks it)
+        self._scratch = None                                         # lookahead's ClothBatch of E*K cloths
+        self._look = None                                            # the last lookahead, for commit
 
     def close(self):
         self.batch.close()
+        if self._scratch is not None:
+            self._scratch.close()
+            self._scratch = None
 
     # ------------------------------------------------------------------------------------------------
     def seed(self, seed=None):
@@ -209,6 +278,7 @@ class ClothVecEnv(object):
         for e, s in enumerate(seeds):
             self.np_randoms[e], s2 = seeding.np_random(s)
             out.append(s2)
+        self._version = getattr(self, '_version', 0) + 1
         self._pending = [None] * self.E                                # reset scripts pre-drawn from the old generators
         return out
 
@@ -242,6 +312,7 @@ class ClothVecEnv(object):
         idx = self._env_indices(envs)
         if idx.size == 0:
             return
+        self._version += 1
         lo, hi = int(idx.min()), int(idx.max()) + 1             # only the touched range of envs is read and rewritten
         m = self.batch.get_material(lo, hi - lo)
         for k, v in fields.items():
@@ -305,38 +376,55 @@ class ClothVecEnv(object):
         reference's episode loop does (`while not done: step` then `env.reset()`, examples/analytic.py:872-882);
         their row of `obs` is then the first observation of the new episode, info['terminal_observation'] holds
         the last one of the finished episode and info['reset_mask'] says which envs were reset."""
-        E = self.E
-        act_mask = np.ones(E, dtype=bool) if active is None else np.asarray(active, dtype=bool).copy()
-        d = self.decode_actions(actions)
+        self._version += 1
+        act_mask = np.ones(self.E, dtype=bool) if active is None else np.asarray(active, dtype=bool).copy()
+        r = self._run_action(self.batch, actions, self._iters_up_env, act_mask)
+        return self._finish_step(actions, r, act_mask, initialize, auto_reset)
+
+    def _run_action(self, batch, actions, iters_up, act_mask):
+        """The device half of step() on `batch` (the env's own, or the scratch batch of lookahead: n = batch.E cloths): decode with
+        the given per-cloth iters_up, grab_top with the force_grab radius loop, the schedule, the metrics. Touches no env state."""
+        n = batch.E
+        d = self.decode_actions(actions, iters_up=iters_up)
         xy = np.stack([d['x'], d['y']], axis=1)
-        n_grab = self.batch.grab_top(xy, active=act_mask).astype(np.int64)              # :431
+        n_grab = batch.grab_top(xy, active=act_mask).astype(np.int64)                   # :431
         if self._force_grab:                                                            # :434-444
-            radius = np.full(E, float(self.grip_radius))
+            radius = np.full(n, float(self.grip_radius))
             need = act_mask & (n_grab == 0)
             while need.any():
                 radius[need] += self._radius_inc
-                n2 = self.batch.grab_top(xy, radius=radius, active=need)
+                n2 = batch.grab_top(xy, radius=radius, active=need)
                 n_grab[need] = n2[need]
                 need = need & (n_grab == 0)
         exit_early = act_mask & (n_grab == 0)                                           # :490-493
         run_mask = act_mask & ~exit_early
-        s = make_schedules(E, break_on_tear=1, dz_up=0.0025)                            # :359
+        s = make_schedules(n, break_on_tear=1, dz_up=0.0025)                            # :359
         b = d['bounds']
         s['n_up_end'], s['n_uprest_end'], s['n_pull_end'] = b[:, 0], b[:, 1], b[:, 2]
         s['n_griprest_end'], s['n_total'] = b[:, 3], b[:, 4]
         s['dx_pull'], s['dy_pull'] = d['x_dir_r'], d['y_dir_r']
         s['active'] = run_mask
-        executed = self.batch.run(s).astype(np.int64)
+        executed = batch.run(s).astype(np.int64)
         executed[~run_mask] = 0
+        if self.reward_type.startswith('height'):
+            cov, vinv, oob, tear, height = batch.metrics(want_height=True)
+        else:
+            (cov, vinv, oob, tear), height = batch.metrics(), None
+        return dict(executed=executed, n_grabbed=n_grab, iters_pull=d['iters_pull'], exit_early=exit_early, run_mask=run_mask,
+                    cov=cov, vinv=vinv, oob=oob, tear=tear, height=height)
+
+    def _finish_step(self, actions, r, act_mask, initialize, auto_reset):
+        """The host half of step(): counters, reward, terminal test, info, auto-reset -- from the results `r` of _run_action (step),
+        or of the adopted branches of a lookahead (commit)."""
+        executed, n_grab, oob, vinv = r['executed'], r['n_grabbed'], r['oob'], r['vinv']
         self.total_substeps += int(executed.sum())
-        self.last_executed, self.last_grabbed, self.last_iters_pull = executed, n_grab, d['iters_pull']
-        cov, vinv, oob, tear = self.batch.metrics()
-        self.have_tear |= (run_mask & tear)                                             # :511-514
+        self.last_executed, self.last_grabbed, self.last_iters_pull = executed, n_grab, r['iters_pull']
+        self.have_tear |= (r['run_mask'] & r['tear'])                                   # :511-514
         if initialize:                                                                  # :517-518
             return None
         self.num_sim_steps[act_mask] += executed[act_mask]
         self.num_steps[act_mask] += 1
-        rew = self._reward(actions, exit_early, cov, vinv, oob, act_mask)
+        rew = self._reward(actions, r['exit_early'], r['cov'], vinv, oob, act_mask, height=r['height'])
         term = self._terminal(oob, act_mask)
         self._ep_done = np.where(act_mask, term, self._ep_done)
         info = {
@@ -352,6 +440,106 @@ class ClothVecEnv(object):
             info['reset_mask'] = term.copy()
             obs = self.reset(mask=term)
         return obs, rew, term, info
+
+    # ---- forks of the device state: snapshot / restore, action lookahead (clothhip_fork) ---------------------------------
+    _SNAP_ARRAYS = ('num_steps', 'num_sim_steps', 'have_tear', '_prev_reward', '_start_coverage', '_start_variance_inv',
+                    '_current_coverage', '_iters_up_env', 'init_side', '_ep_done', 'last_executed', 'last_grabbed', 'last_iters_pull')
+
+    def _require_whole_actions(self, what):
+        if self.batch.in_flight().any():
+            raise RuntimeError("%s: a time-sliced step_many left operations in flight on env(s) %s; take it between whole actions "
+                               "(finish them with another step_many launch first)" % (what, np.nonzero(self.batch.in_flight())[0].tolist()))
+
+    def snapshot(self):
+        """Keep the env as it is now, to come back to with restore(): an opaque ClothSnapshot holding a device-resident copy of all E
+        cloths (a private ClothBatch filled by ONE fork: particles, pin bytes, tear flags, rest lengths, materials -- no host staging)
+        and everything the host keeps per env (step counters, tear flags, reward bookkeeping, per-env iters_up, init_side, episode-over
+        flags, the last_* arrays, every env's RandomState and the reset scripts pre-drawn for step_many). Snapshots are taken between
+        whole actions: it raises if a time-sliced step_many left operations in flight."""
+        self._require_whole_actions("snapshot")
+        b = ClothBatch(self.cfg, n_envs=self.E, device=self.batch.device, precision=self.batch.precision)
+        b.fork_from(self.batch, np.arange(self.E))
+        host = {k: np.array(getattr(self, k), copy=True) for k in self._SNAP_ARRAYS}
+        host['rng'] = [r.get_state() for r in self.np_randoms]
+        host['pending'] = copy.deepcopy(self._pending)
+        host['built_pos0'] = copy.deepcopy(getattr(self, '_built_pos0', None))
+        return ClothSnapshot(b, host)
+
+    def restore(self, snap, envs=None):
+        """Put the chosen envs (None: all; indices or a boolean mask) back to where `snap` = snapshot() saw them: the device state
+        (materials included) by one fork, and the host state. Afterwards they behave bit for bit as they did after snapshot(),
+        including the reset draws of later step_many launches; the other envs stay where they are. A snapshot can be restored any
+        number of times."""
+        if snap.batch.E != self.E or snap.batch.P != self.P or snap.batch.precision != self.batch.precision:
+            raise ValueError("the snapshot was taken from another env")
+        idx = self._env_indices(envs)
+        self._version += 1
+        if idx.size == 0:
+            return
+        self.batch.fork_from(snap.batch, idx, idx)
+        for k in self._SNAP_ARRAYS:
+            a = np.array(getattr(self, k), copy=True)
+            a[idx] = snap.host[k][idx]
+            setattr(self, k, a)
+        for e in idx:
+            self.np_randoms[e].set_state(snap.host['rng'][e])
+            self._pending[e] = copy.deepcopy(snap.host['pending'][e])
+        if 0 in idx:
+            self._built_pos0 = copy.deepcopy(snap.host['built_pos0'])
+
+    def lookahead(self, actions):
+        """What would step(a) return? -- for K candidate actions per env at once, WITHOUT changing the env. actions: float [E, K, 4].
+        One fork copies env e into slots e*K .. e*K+K-1 of a scratch ClothBatch of E*K cloths (created on first use, kept for the next
+        call with the same K; materials included), which then runs exactly the device half of step() -- decode with the env's own
+        iters_up, grab_top with the force_grab radius loop, the schedule, the metrics. Returns a dict of [E, K] arrays: `rew` and
+        `done` as step() would return them for that action, and actual_coverage, variance_inv, out_of_bounds, have_tear, executed,
+        n_grabbed as in its info. commit() adopts one branch per env."""
+        a = np.ascontiguousarray(actions, dtype=np.float64)
+        if a.ndim != 3 or a.shape[0] != self.E or a.shape[2] != 4 or a.shape[1] < 1:
+            raise ValueError("actions must have shape (%d, K, 4)" % self.E)
+        self._require_whole_actions("lookahead")
+        E, K = self.E, a.shape[1]
+        if self._scratch is None or self._scratch.E != E * K:
+            if self._scratch is not None:
+                self._scratch.close()
+            self._scratch = ClothBatch(self.cfg, n_envs=E * K, device=self.batch.device, precision=self.batch.precision)
+        self._look = None
+        rep = np.repeat(np.arange(E), K)
+        self._scratch.fork_from(self.batch, rep)
+        flat = a.reshape(E * K, 4)
+        mask = np.ones(E * K, dtype=bool)
+        r = self._run_action(self._scratch, flat, self._iters_up_env[rep], mask)
+        have_tear = self.have_tear[rep] | (r['run_mask'] & r['tear'])
+        rew, _ = compute_reward(self.reward_type, flat, r['exit_early'], r['cov'], r['vinv'], r['oob'], mask, have_tear,
+                                self._prev_reward[rep], height=r['height'], clip_act_space=self._clip_act_space,
+                                act_low=self.action_space.low, act_high=self.action_space.high, consts=self._reward_consts())
+        done = compute_terminal(self.reward_type, self.max_actions, self.num_steps[rep] + 1, have_tear, r['oob'], r['cov'], mask)
+        self._look = dict(K=K, version=self._version, actions=a.copy(), r=r)
+        sh = lambda v: np.asarray(v).reshape(E, K).copy()
+        return dict(rew=sh(rew), done=sh(done), actual_coverage=sh(r['cov']), variance_inv=sh(r['vinv']), out_of_bounds=sh(r['oob']),
+                    have_tear=sh(have_tear), executed=sh(r['executed']), n_grabbed=sh(r['n_grabbed']))
+
+    def commit(self, choice, auto_reset=False):
+        """Adopt branch choice[e] of the LAST lookahead() for every env e: returns (obs, rew, done, info) exactly as
+        step(actions[e, choice[e]], auto_reset=auto_reset) would have. The state is forked back from the scratch batch; the action is
+        not simulated again. Raises if anything changed the env since that lookahead -- step, step_many, reset, restore, seed,
+        set_material, another commit. Changes accepted in between: none (a further lookahead replaces the one to commit)."""
+        L = self._look
+        if L is None:
+            raise RuntimeError("commit: no lookahead to adopt a branch of")
+        if L['version'] != self._version:
+            self._look = None
+            raise RuntimeError("commit: the env changed since the last lookahead; its branches no longer start from the env's state")
+        E, K = self.E, L['K']
+        c = np.asarray(choice)
+        if c.shape != (E,) or c.dtype.kind not in 'iu' or (c < 0).any() or (c >= K).any():
+            raise ValueError("choice must be int[%d] with values in [0, %d)" % (E, K))
+        sel = np.arange(E) * K + c.astype(np.int64)
+        self._look = None
+        self._version += 1
+        self.batch.fork_from(self._scratch, sel, np.arange(E))
+        r = {k: (None if v is None else np.array(v[sel], copy=True)) for k, v in L['r'].items()}
+        return self._finish_step(L['actions'][np.arange(E), c], r, np.ones(E, dtype=bool), False, auto_reset)
 
     # ---- whole episodes on the device (clothhip_run_actions) ------------------------------------------------------
     def _episode_params(self):
@@ -507,6 +695,7 @@ class ClothVecEnv(object):
         accounting 'op_ticks' / 'op_substeps' uint64[E, 4] (ClothBatch.op_ticks)."""
         from . import _lib
         import time as _time
+        self._version += 1
         _tp = [_time.perf_counter()]
         prof = self.__dict__.setdefault('host_prof', {})
 
@@ -667,48 +856,25 @@ class ClothVecEnv(object):
         return self.batch.metrics(want_height=True)[4]
 
     def _reward(self, actions, exit_early, cov, vinv, oob, mask, height=None):
-        E = self.E
-        hf = (lambda: height) if height is not None else self._height_fraction
-        rew = np.zeros(E)
-        rew += np.where(self.have_tear, self._tear_penalty, np.where(oob, self._oob_penalty, 0.0))   # :557-562
-        rew += np.where(exit_early, self._nogrip_penalty, 0.0)                                       # :563-565
-        if not self._clip_act_space:                                                                 # :579-593
-            a = np.asarray(actions, dtype=np.float64).reshape(E, 4)
-            low, high = self.action_space.low, self.action_space.high
-            diff = np.where(a < low, low - a, np.where(a > high, a - high, 0.0))
-            pen = -np.minimum(diff ** 2, self._act_pen_limit) * self._act_bound_factor
-            rew += pen.sum(axis=1)
+        """compute_reward on the env's own state, then the two updates ClothEnv._reward makes (_current_coverage, :647; _prev_reward
+        of the '-delta' types, :656-679)."""
+        if height is None and self.reward_type.startswith('height'):
+            height = self._height_fraction()
+        rew, tracked = compute_reward(self.reward_type, actions, exit_early, cov, vinv, oob, mask, self.have_tear, self._prev_reward,
+                                      height=height, clip_act_space=self._clip_act_space, act_low=self.action_space.low,
+                                      act_high=self.action_space.high, consts=self._reward_consts())
         self._current_coverage = np.where(mask, cov, self._current_coverage)                         # :647
-        rew += np.where(cov > _REWARD_THRESHOLDS['coverage'], self._cover_success, 0.0)              # :648-650
-        rew += self._neg_living_rew
+        if tracked is not None:
+            self._prev_reward = np.where(mask, tracked, self._prev_reward)
+        return rew
 
-        def delta(val):
-            diff = val - self._prev_reward
-            self._prev_reward = np.where(mask, val, self._prev_reward)
-            return diff
-        rt = self.reward_type                                                                        # :656-679
-        if rt == 'coverage':
-            rew += cov
-        elif rt == 'coverage-delta':
-            rew += delta(cov)
-        elif rt == 'height':
-            rew += hf()
-        elif rt == 'height-delta':
-            rew += delta(hf())
-        elif rt == 'variance':
-            rew += vinv
-        elif rt == 'variance-delta':
-            rew += delta(vinv)
-        elif rt == 'folding-number':
-            raise NotImplementedError()
-        else:
-            raise ValueError(rt)
-        return np.where(mask, rew, 0.0)
+    def _reward_consts(self):
+        return dict(neg_living_rew=self._neg_living_rew, nogrip_penalty=self._nogrip_penalty, tear_penalty=self._tear_penalty,
+                    oob_penalty=self._oob_penalty, cover_success=self._cover_success, act_bound_factor=self._act_bound_factor,
+                    act_pen_limit=self._act_pen_limit)
 
     def _terminal(self, oob, mask):
-        done = (self.num_steps >= self.max_actions) | self.have_tear | oob                           # :692-703
-        done |= self._current_coverage > _REWARD_THRESHOLDS[self.reward_type]                        # :706-710
-        return done & mask
+        return compute_terminal(self.reward_type, self.max_actions, self.num_steps, self.have_tear, oob, self._current_coverage, mask)
 
     def _compute_coverage(self):
         return self.batch.metrics()[0]
@@ -747,6 +913,7 @@ class ClothVecEnv(object):
     def reset(self, mask=None):
         """Reset the envs selected by `mask` (default all) and return the '1d' observation of ALL envs."""
         E, P = self.E, self.P
+        self._version += 1
         m = np.ones(E, dtype=bool) if mask is None else np.asarray(mask, dtype=bool)
         idx = np.nonzero(m)[0]
         tier = {'tier1': 1, 'tier2': 2, 'tier3': 3}.get(self._init_type)
@@ -984,6 +1151,16 @@ class ClothEnv(object):
         if atype == 'over_xy_plane':
             return self.action_space.sample()
         raise ValueError(atype)
+
+    def snapshot(self):
+        """ClothVecEnv.snapshot of the single env."""
+        return self._vec.snapshot()
+
+    def restore(self, snap):
+        """Back to where snapshot() saw the env (ClothVecEnv.restore)."""
+        self.cloth._invalidate()
+        self._vec.restore(snap)
+        self.cloth.init_side = bool(self._vec.init_side[0])
 
     def set_material(self, **fields):
         """The env's material: density, ks, damping, plane_friction, tear_thresh, gravity (ClothVecEnv.set_material)."""

@@ -6,6 +6,8 @@ OracleCornerPolicy   examples/analytic.py:70-155  (distance method, delta action
 HighestPointPolicy   examples/analytic.py:723-808
 RandomPolicy         examples/analytic.py:811-823 (the reference samples from an UNSEEDED space RNG,
                      cloth_env.py:1004; here each env gets its own RandomState so runs are reproducible)
+LookaheadPolicy      no reference counterpart: one-step greedy action selection over K candidates per env, evaluated on
+                     device-side forks of the env's state (ClothVecEnv.lookahead)
 """
 import numpy as np
 
@@ -104,3 +106,40 @@ class RandomPolicy(object):
     def get_action(self, obs=None, t=0):
         sp = self.env.action_space
         return np.stack([r.uniform(low=sp.low, high=sp.high) for r in self.rngs])
+
+
+class LookaheadPolicy(object):
+    """Greedy one-step lookahead: K candidate actions per env, each tried from the env's current state on a fork of it
+    (ClothVecEnv.lookahead -- the env itself does not move), the candidate with the highest reward wins; ties go to the lowest
+    candidate index. The candidates are uniform over the action space, drawn from ONE RandomState(seed) of the policy's own (the
+    envs' np_randoms, i.e. the reset streams, do not advance; the same seed gives the same candidate stream); with `include`, another
+    policy's proposal is candidate 0, so the lookahead never does worse in one-step reward than that policy. After get_action,
+    last_candidates [E, K, 4], last_lookahead (the dict lookahead returned) and last_choice [E] describe the decision, and
+    env.commit(last_choice) adopts the winning branches without simulating them again (step(action) does the same from scratch)."""
+
+    def __init__(self, env, n_candidates=16, seed=0, include=None):
+        if int(n_candidates) < 1:
+            raise ValueError("n_candidates must be >= 1")
+        self.env, self.K, self.include = env, int(n_candidates), include
+        self.rng = np.random.RandomState(seed)
+        self.last_candidates = self.last_lookahead = self.last_choice = None
+
+    def candidates(self, obs=None, t=0):
+        """The next [E, K, 4] candidate table (advances the policy's stream)."""
+        sp = self.env.action_space
+        cand = self.rng.uniform(low=sp.low, high=sp.high, size=(self.env.E, self.K, 4))
+        if self.include is not None:
+            cand[:, 0] = np.asarray(self.include.get_action(obs, t), dtype=np.float64)
+        return cand
+
+    @staticmethod
+    def choose(rew):
+        """arg-max over the candidates of every env, the lowest index among equals: rew [E, K] -> int64[E]."""
+        return np.argmax(np.asarray(rew), axis=1).astype(np.int64)
+
+    def get_action(self, obs=None, t=0):
+        cand = self.candidates(obs, t)
+        out = self.env.lookahead(cand)
+        best = self.choose(out['rew'])
+        self.last_candidates, self.last_lookahead, self.last_choice = cand, out, best
+        return cand[np.arange(self.env.E), best]

@@ -155,6 +155,41 @@ int clothhip_get_material(clothhip_handle *h, int32_t env0, int32_t n, ClothMate
  * 1 - damping/100, 1. - plane_friction, tear_thresh}. */
 int clothhip_selftest_material(const ClothParams *params, const ClothMaterial *m, int32_t precision, double out[7]);
 
+/* Whole cloths from env slot to env slot, ON THE DEVICE: destination env dst_env[j] of `dst` becomes a copy of env src_env[j] of `src`, j in
+ * [0, n). Replaces the host round trip clothhip_get_state -> clothhip_set_state (+ get_tear / get_rest / get_material and their setters) for
+ * branching one state into many (action lookahead), keeping a state and coming back to it (snapshot / restore) and starting every env from
+ * one state -- what the reference does with save_state / Cloth(state=...) through a pickle (cloth_env.py:343-350, :736-741). One kernel on
+ * dst's stream copies, bit for bit and without conversion: positions and previous positions, the per-point pin bytes VERBATIM (the grab
+ * multiplicity clothhip_get_state collapses to 0/1 and the pinned-from-outside bit of clothhip_pin_points, which it hides), the tear flag
+ * (copied, not cleared) and, unless CLOTHHIP_FORK_STATE_ONLY, the material. The launch waits for what src's stream has enqueued (an event)
+ * and the call returns when the copy is done.
+ *   - dst and src: same device, precision and n_side, else CLOTHHIP_EINVAL; dst == src is allowed when no env is in both lists.
+ *     CLOTHHIP_EINVAL also for an index out of range, a duplicate in dst_env, or an env that is source and destination on one handle; a
+ *     duplicate in src_env is the point (one state, many branches). n == 0 succeeds and does nothing. A failed call changes nothing.
+ *     CLOTHHIP_ESTATE between clothhip_run_actions_begin and _end on either handle.
+ *   - like clothhip_set_state, the fork drops the operation a time slice left in flight -- for the destination envs it writes, only;
+ *     the source's parked operations are neither copied nor disturbed.
+ *   - rest lengths: afterwards clothhip_get_rest of a destination env equals its source env's bit for bit. A destination that shares ONE
+ *     rest table keeps sharing it when the source shares a bitwise-equal one (the flat tiers keep their LEAN and grid-specialised builds).
+ *     Equality is decided on the host without a download: clothhip_set_state with CLOTHHIP_REST_SHARED is the only writer of a shared table
+ *     (the kernels write rest lengths into per-env tables only), every handle keeps the bytes it last uploaded that way, in its precision,
+ *     and two shared tables are equal exactly when those bytes are. In every other case the destination switches to per-env tables (its
+ *     other envs keep their values), as clothhip_set_state does when given per-env `rest`, and the source env's row is copied.
+ *   - materials: without CLOTHHIP_FORK_STATE_ONLY the destination envs take their source envs' ClothMaterial by clothhip_set_material's
+ *     rules (the handle's material table, the generic build while any env differs from the handle's parameters, clothhip_last_specialised
+ *     following); with the flag they keep their own. */
+enum { CLOTHHIP_FORK_STATE_ONLY = 1 };   /* leave the destination envs' materials as they are */
+int clothhip_fork(clothhip_handle *dst, const int32_t *dst_env, clothhip_handle *src, const int32_t *src_env,
+                  int32_t n, int32_t flags);
+/* The raw per-point pin byte of envs [env0, env0+n): cnt[n][P], bits 0-6 = how many times the gripper holds the point (grabbed_pts may
+ * list a point more than once, gripper.pyx:41,52), bit 7 = pinned from outside (clothhip_pin_points). clothhip_get_state's `pinned` is
+ * this byte != 0. */
+int clothhip_get_pin_counts(clothhip_handle *h, int32_t env0, int32_t n, uint8_t *cnt);
+/* parked[E]: 1 for every env that holds an operation a time-sliced clothhip_run_actions launch cut and the next launch would continue
+ * (see time_budget_ms there), else 0. A fork, a snapshot or a lookahead of such an env would copy a cloth in the middle of an action
+ * without the action's remainder: callers take them between whole actions and ask here. */
+int clothhip_in_flight(clothhip_handle *h, uint8_t *parked);
+
 /* Gripper.grab_top(x, y) (gripper.pyx:23-42) for every active env: xy[E][2]; radius[E] or NULL
  * (= params.grip_radius; cloth_env.py:436-442 mutates it for force_grab); active[E] or NULL (= all).
  * n_grabbed[E] receives the number of points appended to grabbed_pts by THIS call (0 = nothing grabbed). */
