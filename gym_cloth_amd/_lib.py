@@ -72,6 +72,11 @@ class ClothRenderParams(C.Structure):
                 ("background", C.c_float * 3), ("light_dir", C.c_float * 3), ("ambient", C.c_float), ("energy", C.c_float)]
 
 
+IMG_RGB, IMG_DEPTH, IMG_RGBD = 0, 1, 2                                  # clothhip_render_obs formats ...
+IMG_FORMATS = {'rgb': IMG_RGB, 'depth': IMG_DEPTH, 'rgbd': IMG_RGBD}
+OBS_STATE, OBS_SLOTS, OBS_RESETS, OBS_HOST = 0, 1, 2, 3                 # ... and sources
+OBS_SOURCES = {'state': OBS_STATE, 'slots': OBS_SLOTS, 'resets': OBS_RESETS, 'host': OBS_HOST}
+
 POLICY_TABLE, POLICY_ORACLE_CORNER, POLICY_HIGHEST_POINT = 0, 1, 2
 MT_WORDS = 626                      # per-env RandomState image: key[624], pos, pad (csrc/cloth_rng.hpp)
 
@@ -134,6 +139,8 @@ SYMBOLS = [
     ("clothhip_write_obs_f32_device", C.c_int, [_vp, _vp]),
     ("clothhip_run_device_sched_async", C.c_int, [_vp, _vp]),
     ("clothhip_render", C.c_int, [_vp, C.POINTER(ClothRenderParams), _u8p, _u8p, C.POINTER(C.c_float)]),
+    ("clothhip_render_obs", C.c_int, [_vp, C.POINTER(ClothRenderParams), C.c_int32, C.POINTER(C.c_float), C.c_int64, _u8p, _u8p,
+                                      C.c_int32, _u8p, _vp]),
     ("clothhip_device_alloc", C.c_int, [_vp, C.c_uint64, C.POINTER(_vp)]),
     ("clothhip_device_free", C.c_int, [_vp, _vp]),
     ("clothhip_device_upload", C.c_int, [_vp, _vp, _vp, C.c_uint64]),
@@ -154,6 +161,8 @@ SYMBOLS = [
     ("clothhip_selftest_windows", C.c_int, [_PP, _i32p, _i32p, _i32p, _i32p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_int32]),
     ("clothhip_selftest_layout", C.c_int, [_PP, C.c_int32, C.c_int32, C.c_int32, _i32p, C.c_int32]),
     ("clothhip_selftest_rng", C.c_int, [_vp, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, _dp]),
+    ("clothhip_selftest_depth8", C.c_int, [C.POINTER(C.c_float), C.c_int32, C.c_int64, _u8p]),
+    ("clothhip_selftest_render_plan", C.c_int, [_PP, C.c_int32, C.c_int32, _i32p]),
     ("clothhip_selftest_arith", C.c_int, [C.c_int32, C.c_int32, _dp, _dp, _dp, C.c_int64]),
 ]
 

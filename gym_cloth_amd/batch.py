@@ -263,6 +263,34 @@ class ClothBatch(object):
                                       None if dep is None else dep.ctypes.data_as(C.POINTER(C.c_float))))
         return rgb, dep
 
+    def render_obs(self, source, obs=None, valid=None, swap_sides=None, fmt='rgbd', params=None, out_device_ptr=None, **render_kw):
+        """Finished image observations of many cloths in one call (clothhip_render_obs): uint8 [n, H, W, C], C = 4 for
+        fmt 'rgbd', 3 for 'rgb' and 'depth' (the 8-bit depth replicated). source: 'state' (this batch's particles, n = E),
+        'slots' / 'resets' (the obs_t / reset_obs tables the last run_actions launch left on the device, n = T * E in [t][e]
+        order / E * R in [e][k] order) or 'host' (obs: float32 [n, 3P] '1d' observations). valid[n]: False = not rendered,
+        all bytes zero; swap_sides[n]: swap the two side colours of that image. out_device_ptr: also keep the images in
+        that device buffer (n * H * W * C bytes). The pixels are those of render() for the same float32 positions."""
+        p = params if params is not None else self.render_params(**render_kw)
+        src = _lib.OBS_SOURCES[source] if isinstance(source, str) else int(source)
+        f = _lib.IMG_FORMATS[fmt] if isinstance(fmt, str) else int(fmt)
+        if src == _lib.OBS_HOST:
+            obs = np.ascontiguousarray(obs, dtype=np.float32)
+            if obs.ndim != 2 or obs.shape[1] != 3 * self.P:
+                raise ValueError("obs must have shape (n, %d)" % (3 * self.P))
+            n = obs.shape[0]
+        elif src == _lib.OBS_STATE:
+            n = self.E
+        else:
+            last = getattr(self, '_last_launch', None)                # (T, R) of the last run_actions launch
+            n = 0 if last is None else (last[0] * self.E if src == _lib.OBS_SLOTS else self.E * last[1])
+        flag = lambda a: None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a).astype(bool).astype(np.uint8), (n,)))
+        v, sw = flag(valid), flag(swap_sides)
+        out = np.empty((n, p.height, p.width, 4 if f == _lib.IMG_RGBD else 3), dtype=np.uint8)
+        check(self._L.clothhip_render_obs(self._h, C.byref(p), src, None if obs is None else obs.ctypes.data_as(C.POINTER(C.c_float)),
+                                          n, _lib.u8p(v), _lib.u8p(sw), f, _lib.u8p(out),
+                                          None if out_device_ptr is None else C.c_void_p(int(out_device_ptr))))
+        return out
+
     # ---- gripper ---------------------------------------------------------------------------------------
     def _grab(self, fn, xy, radius, active):
         xy = np.ascontiguousarray(np.broadcast_to(np.asarray(xy, dtype=np.float64), (self.E, 2)))
@@ -356,6 +384,7 @@ class ClothBatch(object):
                                                  int(domrand_words), int(have_rst), int(bool(want_obs)), int(have_robs),
                                                  float(time_budget_ms)))
         self._fused = (T, R, num_steps, done, have_rst, bool(want_obs), have_robs, rng_states)
+        self._last_launch = (T, R)                       # the shapes of the tables render_obs('slots' / 'resets') reads
 
     def run_actions_end(self):
         """Second half: wait for the launch and fetch its outputs. num_steps / done given to _begin are updated in place.

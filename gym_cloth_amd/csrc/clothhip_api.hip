@@ -19,6 +19,7 @@
 #include "stepper_variants.hpp"
 #include "lean_rates.hpp"
 #include "cloth_render.hpp"
+#include "cloth_render_obs.hpp"
 
 using namespace clothhip;
 
@@ -66,6 +67,8 @@ struct DebugKnobs {
     int phase_mask = 15;         // PHASES: phase ablation mask
     bool nospec = false;         // NOSPEC (nonzero): the generic build instead of the grid-specialised one
     bool one_launch = false;     // ONE_LAUNCH (set at all): a time-sliced episode launch as one dispatch, not one per generation
+    int render_lds_kib = 160;    // RENDER_LDS: LDS budget in KiB of a clothhip_render_obs workgroup (smaller: shorter bands, more workgroups per CU)
+    bool render_walk = false;    // RENDER_WALK (nonzero): one workgroup walks all bands of an image instead of one workgroup per band
 };
 static DebugKnobs read_debug_knobs() {
     DebugKnobs k;
@@ -79,6 +82,8 @@ static DebugKnobs read_debug_knobs() {
     if (const char *t = getenv("CLOTHHIP_DEBUG_PHASES")) k.phase_mask = atoi(t);
     if (const char *t = getenv("CLOTHHIP_DEBUG_NOSPEC")) k.nospec = atoi(t) != 0;
     k.one_launch = getenv("CLOTHHIP_DEBUG_ONE_LAUNCH") != nullptr;
+    if (const char *t = getenv("CLOTHHIP_DEBUG_RENDER_LDS")) { const int v = atoi(t); if (v >= 1 && v <= 160) k.render_lds_kib = v; }
+    if (const char *t = getenv("CLOTHHIP_DEBUG_RENDER_WALK")) k.render_walk = atoi(t) != 0;
     return k;
 }
 
@@ -137,6 +142,10 @@ struct clothhip_handle {
     uint64_t *d_fticks = nullptr;   // [E][8] per-operation-class ticks and update() counts of the last episode launch
     int f_T = 0; size_t f_nscr = 0; bool f_pending = false, f_resets = false, f_obs = false, f_robs = false, f_mt = false;
     size_t cap_fact = 0, cap_frec = 0, cap_fobs = 0, cap_fscr = 0, cap_frst = 0, cap_frobs = 0, cap_fparg = 0;
+    // clothhip_render_obs scratch for ONE chunk of images, grown on demand: finished images (when the caller gives no device buffer),
+    // raw depth, uploaded '1d' rows, valid + swap flags
+    void *d_ro_img = nullptr, *d_ro_depth = nullptr, *d_ro_src = nullptr, *d_ro_flags = nullptr;
+    size_t cap_ro_img = 0, cap_ro_depth = 0, cap_ro_src = 0, cap_ro_flags = 0;
     Topology topo;
     WindowTable wt;
     std::vector<uint32_t> gather;       // the gather table (host copy of d_gather): the LEAN stencil checks read it
@@ -253,7 +262,8 @@ static void free_handle(clothhip_handle *h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     void *ptrs[] = {h->d_pos, h->d_prev, h->d_rest, h->d_cnt, h->d_active, h->d_tear, h->d_exec, h->d_ngrab, h->d_stats,
-                    h->d_sched, h->d_flat, h->d_flat_rest, h->d_hcnt, h->d_fz, h->d_fact, h->d_fscr, h->d_frec, h->d_frst, h->d_fobs, h->d_frobs, h->d_fsteps, h->d_fparg, h->d_fdone, h->d_fticks, h->d_fsum, h->d_fmt, h->d_resume, h->d_gather, h->d_wt_ent, h->d_wt_dep, h->d_lstc, h->d_mat, h->d_fork_idx, h->d_levels, h->d_xy, h->d_radius, h->d_cov, h->d_vinv, h->d_oob};
+                    h->d_sched, h->d_flat, h->d_flat_rest, h->d_hcnt, h->d_fz, h->d_fact, h->d_fscr, h->d_frec, h->d_frst, h->d_fobs, h->d_frobs, h->d_fsteps, h->d_fparg, h->d_fdone, h->d_fticks, h->d_fsum, h->d_fmt, h->d_resume, h->d_gather, h->d_wt_ent, h->d_wt_dep, h->d_lstc, h->d_mat, h->d_fork_idx, h->d_levels, h->d_xy, h->d_radius, h->d_cov, h->d_vinv, h->d_oob,
+                    h->d_ro_img, h->d_ro_depth, h->d_ro_src, h->d_ro_flags};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     if (h->h_sched) (void)hipHostFree(h->h_sched);
     if (h->h_fork_idx) (void)hipHostFree(h->h_fork_idx);
@@ -1520,6 +1530,113 @@ extern "C" int clothhip_render(clothhip_handle *h, const ClothRenderParams *p, c
     RC(hipStreamSynchronize(h->stream));
 #undef RC
     cleanup();
+    return 0;
+}
+
+// ---- image observations for many cloths (cloth_render_obs.hpp) -------------------------------------------------------------
+// images per chunk: the scratch (finished images, raw depth, uploaded rows) is sized for one chunk, whatever n is
+static int render_obs_chunk(size_t npx) {
+    const size_t per_image = npx * 4, budget = (size_t)64 << 20;      // the largest scratch: 4 B per pixel (RGBD bytes, float depth)
+    const size_t c = budget / per_image;
+    return c < 1 ? 1 : (c > 256 ? 256 : (int)c);
+}
+
+extern "C" int clothhip_render_obs(clothhip_handle *h, const ClothRenderParams *p, int32_t source, const float *obs_host, int64_t n,
+                                   const uint8_t *valid, const uint8_t *swap, int32_t format, uint8_t *out, void *d_out) {
+    if (!h || !p) return fail(CLOTHHIP_EINVAL, "NULL argument");
+    if (p->width < 1 || p->height < 1 || p->width > 4096 || p->height > 4096) return fail(CLOTHHIP_EINVAL, "image size outside [1, 4096]");
+    if (!(p->lens_mm > 0) || !(p->sensor_mm > 0)) return fail(CLOTHHIP_EINVAL, "lens / sensor must be > 0");
+    if (format != CLOTHHIP_IMG_RGB && format != CLOTHHIP_IMG_DEPTH && format != CLOTHHIP_IMG_RGBD) return fail(CLOTHHIP_EINVAL, "unknown image format %d", format);
+    if (source < CLOTHHIP_OBS_STATE || source > CLOTHHIP_OBS_HOST) return fail(CLOTHHIP_EINVAL, "unknown observation source %d", source);
+    if (n < 0) return fail(CLOTHHIP_EINVAL, "n < 0");
+    if (source == CLOTHHIP_OBS_HOST && !obs_host && n > 0) return fail(CLOTHHIP_EINVAL, "CLOTHHIP_OBS_HOST needs obs_host[n][3P]");
+    if (source == CLOTHHIP_OBS_SLOTS || source == CLOTHHIP_OBS_RESETS) {
+        if (h->f_pending) return fail(CLOTHHIP_ESTATE, "clothhip_run_actions_begin still in flight: call clothhip_run_actions_end first");
+        if (h->f_T < 1) return fail(CLOTHHIP_ESTATE, "no clothhip_run_actions launch yet");
+        if (source == CLOTHHIP_OBS_SLOTS && !h->f_obs) return fail(CLOTHHIP_ESTATE, "the last clothhip_run_actions launch was not given want_obs");
+        if (source == CLOTHHIP_OBS_RESETS && !h->f_robs) return fail(CLOTHHIP_ESTATE, "the last clothhip_run_actions launch was not given want_reset_obs");
+    }
+    const int64_t n_src = source == CLOTHHIP_OBS_STATE ? (int64_t)h->E : source == CLOTHHIP_OBS_SLOTS ? (int64_t)h->f_T * h->E
+                        : source == CLOTHHIP_OBS_RESETS ? (int64_t)h->f_nscr : n;
+    if (n != n_src) return fail(CLOTHHIP_EINVAL, "n = %lld, the source holds %lld cloths", (long long)n, (long long)n_src);
+    const RenderPlan plan = render_plan(h->Ppad, p->width, p->height, h->dbg.render_lds_kib * 1024);
+    if (!plan.fits) return fail(CLOTHHIP_EINVAL, "a one-row band of width %d needs %d B of LDS beside the %d-point grid", p->width, plan.lds, h->P);
+    if (n == 0 || (!out && !d_out)) return 0;
+    HIPCHECK(hipSetDevice(h->device));
+    const size_t npx = (size_t)p->width * p->height, C = format == CLOTHHIP_IMG_RGBD ? 4 : 3, img_bytes = npx * C;
+    const size_t chunk = (size_t)render_obs_chunk(npx), cmax = (size_t)n < chunk ? (size_t)n : chunk;
+    const bool need_depth = format != CLOTHHIP_IMG_RGB, have_flags = valid || swap;
+    if (!d_out) if (int rc = grow(&h->d_ro_img, &h->cap_ro_img, cmax * img_bytes)) return rc;
+    if (need_depth) if (int rc = grow(&h->d_ro_depth, &h->cap_ro_depth, cmax * npx * 4)) return rc;
+    if (source == CLOTHHIP_OBS_HOST) if (int rc = grow(&h->d_ro_src, &h->cap_ro_src, cmax * 3 * h->P * 4)) return rc;
+    if (have_flags) if (int rc = grow(&h->d_ro_flags, &h->cap_ro_flags, 2 * chunk)) return rc;
+    RenderObsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.s.N = h->N; a.s.P = h->P; a.s.Ppad = h->Ppad; a.s.W = p->width; a.s.H = p->height; a.s.E = h->E;
+    for (int k = 0; k < 9; k++) a.s.R[k] = p->world_to_cam[k];
+    for (int k = 0; k < 3; k++) { a.s.cam[k] = p->cam_pos[k]; a.s.front[k] = p->front[k]; a.s.back[k] = p->back[k]; a.s.bg[k] = p->background[k]; a.s.light[k] = p->light_dir[k]; }
+    a.s.fx = (p->lens_mm / p->sensor_mm) * (float)p->width; a.s.fy = a.s.fx;     // square pixels, horizontal sensor fit
+    a.s.cx = 0.5f * (float)p->width; a.s.cy = 0.5f * (float)p->height;
+    a.s.ambient = p->ambient; a.s.energy = p->energy;
+    a.rows = plan.rows; a.bands = plan.bands; a.format = format; a.C = (int)C;
+    const bool soa = source == CLOTHHIP_OBS_STATE;
+    a.src_stride = soa ? 3LL * h->Ppad : 3LL * h->P;
+    a.depth = need_depth ? (float *)h->d_ro_depth : nullptr;
+    const unsigned wg_per_image = h->dbg.render_walk ? 1 : plan.bands;      // one workgroup per band, or one that walks them all
+    const float *d_table = source == CLOTHHIP_OBS_SLOTS ? (const float *)h->d_fobs : source == CLOTHHIP_OBS_RESETS ? (const float *)h->d_frobs : nullptr;
+    HIPCHECK(hipFuncSetAttribute((const void *)k_render_obs<float, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    HIPCHECK(hipFuncSetAttribute((const void *)k_render_obs<float, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    HIPCHECK(hipFuncSetAttribute((const void *)k_render_obs<double, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    for (size_t i0 = 0; i0 < (size_t)n; i0 += chunk) {
+        const size_t m = (size_t)n - i0 < chunk ? (size_t)n - i0 : chunk;
+        if (have_flags) {
+            uint8_t *fl = (uint8_t *)h->d_ro_flags;
+            if (valid) HIPCHECK(hipMemcpyAsync(fl, valid + i0, m, hipMemcpyHostToDevice, h->stream));
+            if (swap) HIPCHECK(hipMemcpyAsync(fl + chunk, swap + i0, m, hipMemcpyHostToDevice, h->stream));
+            a.valid = valid ? fl : nullptr; a.swap = swap ? fl + chunk : nullptr;
+        }
+        a.out = d_out ? (uint8_t *)d_out + i0 * img_bytes : (uint8_t *)h->d_ro_img;
+        const dim3 grid((unsigned)m, wg_per_image);
+        if (soa) {
+            by_precision(h, [&](auto t) {
+                using T = decltype(t);
+                hipLaunchKernelGGL((k_render_obs<T, false>), grid, dim3(256), plan.lds, h->stream, (const T *)h->d_pos + i0 * 3 * h->Ppad, a);
+            });
+        } else {
+            const float *rows = d_table ? d_table + i0 * 3 * h->P : (const float *)h->d_ro_src;
+            if (!d_table) HIPCHECK(hipMemcpyAsync(h->d_ro_src, obs_host + i0 * 3 * h->P, m * 3 * h->P * 4, hipMemcpyHostToDevice, h->stream));
+            hipLaunchKernelGGL((k_render_obs<float, true>), grid, dim3(256), plan.lds, h->stream, rows, a);
+        }
+        HIPCHECK(hipGetLastError());
+        if (need_depth) {
+            hipLaunchKernelGGL(k_depth8, dim3((unsigned)m), dim3(256), 0, h->stream, a);
+            HIPCHECK(hipGetLastError());
+        }
+        if (out && !d_out) HIPCHECK(hipMemcpyAsync(out + i0 * img_bytes, h->d_ro_img, m * img_bytes, hipMemcpyDeviceToHost, h->stream));
+    }
+    if (out && d_out) HIPCHECK(hipMemcpyAsync(out, d_out, (size_t)n * img_bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+extern "C" int clothhip_selftest_depth8(const float *depth, int32_t n_images, int64_t npx, uint8_t *out) {
+    if (n_images < 0 || npx < 0 || ((!depth || !out) && n_images > 0 && npx > 0)) return fail(CLOTHHIP_EINVAL, "bad argument");
+    for (int64_t e = 0; e < n_images; e++) {
+        const float *d = depth + e * npx;
+        if (npx == 0) break;
+        float lo = d[0], hi = d[0];
+        for (int64_t i = 1; i < npx; i++) { lo = fminf(lo, d[i]); hi = fmaxf(hi, d[i]); }
+        for (int64_t i = 0; i < npx; i++) out[e * npx + i] = depth8(d[i], lo, hi);
+    }
+    return 0;
+}
+
+extern "C" int clothhip_selftest_render_plan(const ClothParams *p, int32_t width, int32_t height, int32_t out[4]) {
+    if (int rc = check_params(p)) return rc;
+    if (!out || width < 1 || height < 1) return fail(CLOTHHIP_EINVAL, "bad argument");
+    const int P = p->n_side * p->n_side, Ppad = (P + 63) / 64 * 64;           // as init_host_fields pads the grid
+    const RenderPlan plan = render_plan(Ppad, width, height, read_debug_knobs().render_lds_kib * 1024);
+    out[0] = plan.rows; out[1] = plan.bands; out[2] = plan.lds; out[3] = plan.fits ? 1 : 0;
     return 0;
 }
 

@@ -8,7 +8,9 @@ ClothVecEnv.step.
 
 An episode has the reference's layout (analytic.py:866-882):
     {'obs': [obs_0 (what reset() returned), obs_1, ...], 'act': [...], 'rew': [...], 'done': [...], 'info': [dict, ...]}
-with the '1d' observation (cloth_env.py:196-200) as float32[3P] on the device path (float64 on the host path).
+with the '1d' observation (cloth_env.py:196-200) as float32[3P] on the device path (float64 on the host path), or, with
+obs='rgb' / 'depth' / 'rgbd', the image observation the reference's shipped configurations record (uint8 [H, W, C], rendered on
+the device for every slot of a launch: ClothVecEnv.step_many(images=...)).
 """
 import pickle
 
@@ -30,12 +32,23 @@ def _info_at(src, t, e):
     return out
 
 
+def _state_images(env, fmt, image_kw):
+    """The image observation of every env's present state, finished on the device (what reset() / step() just returned as '1d')."""
+    swap = ~env.init_side if env._init_type == 'tier2' else None
+    return env.batch.render_obs('state', swap_sides=swap, fmt=fmt, **dict(image_kw or {}))
+
+
 def collect_demos(env, policy='oracle_corner', max_episodes=10, slots_per_launch=12, path=None, time_budget_ms=0.0,
-                  on_device=False):
+                  on_device=False, obs='1d', image_kw=None):
     """Run `policy` until `max_episodes` episodes have finished (over all envs of `env`, in order of completion) and return
     them as a list of episode dicts; with `path` the list is also pickled there (analytic.py:900-901).
     `env` must have been seeded; it is reset here. A policies.HighestPointPolicy with on_device=True is evaluated in the
-    kernel as well: its per-env pick streams are drawn here and handed to the launch slot by slot."""
+    kernel as well: its per-env pick streams are drawn here and handed to the launch slot by slot.
+    obs: '1d', or 'rgb' / 'depth' / 'rgbd' for image observations in the episodes' 'obs' lists (image_kw: render parameters);
+    everything else in an episode is the same either way."""
+    if obs not in ('1d', 'rgb', 'depth', 'rgbd'):
+        raise ValueError("obs must be '1d', 'rgb', 'depth' or 'rgbd' (got %r)" % (obs,))
+    fmt = None if obs == '1d' else obs
     episodes = []
     E = env.E
     obs = env.reset()
@@ -44,7 +57,8 @@ def collect_demos(env, policy='oracle_corner', max_episodes=10, slots_per_launch
     if isinstance(policy, str) or hp is not None:
         if hp is None and policy != 'oracle_corner':
             raise ValueError(policy)
-        cur = [_new_episode(obs[e].astype(np.float32), e) for e in range(E)]
+        first = obs.astype(np.float32) if fmt is None else _state_images(env, fmt, image_kw)
+        cur = [_new_episode(first[e], e) for e in range(E)]
         picks = [[] for _ in range(E)]                                # highest point: picks drawn but not consumed yet
         while len(episodes) < max_episodes:
             if hp is not None:
@@ -53,19 +67,20 @@ def collect_demos(env, policy='oracle_corner', max_episodes=10, slots_per_launch
                         picks[e].append(hp.draw(e))
                 tbl = np.array([[picks[e][t] for e in range(E)] for t in range(slots_per_launch)], dtype=np.int32)
                 out = env.step_many(policy='highest_point', n_actions=slots_per_launch, policy_choices=tbl, auto_reset=True,
-                                    want_obs=True, time_budget_ms=time_budget_ms)
+                                    want_obs=True, time_budget_ms=time_budget_ms, images=fmt, image_kw=image_kw)
                 for e in range(E):
                     del picks[e][:int(out['ran'][:, e].sum())]
             else:
                 out = env.step_many(policy='oracle_corner', n_actions=slots_per_launch, auto_reset=True, want_obs=True,
-                                    time_budget_ms=time_budget_ms)
+                                    time_budget_ms=time_budget_ms, images=fmt, image_kw=image_kw)
+            obs_t, reset_obs = (out['obs_t'], out['reset_obs']) if fmt is None else (out['img_t'], out['reset_img'])
             for t in range(slots_per_launch):
                 for e in np.nonzero(out['ran'][t])[0]:
                     k = int(out['reset_before'][t, e])
                     if k:                                             # a new episode started right before this action
-                        cur[e] = _new_episode(out['reset_obs'][e, k - 1].copy(), e)
+                        cur[e] = _new_episode(reset_obs[e, k - 1].copy(), e)
                     ep = cur[e]
-                    ep['obs'].append(out['obs_t'][t, e].copy())
+                    ep['obs'].append(obs_t[t, e].copy())
                     ep['act'].append(tuple(out['actions'][t, e]))
                     ep['rew'].append(float(out['rew'][t, e]))
                     ep['done'].append(bool(out['done'][t, e]))
@@ -75,14 +90,26 @@ def collect_demos(env, policy='oracle_corner', max_episodes=10, slots_per_launch
             # a time slice can end right after a completed reset: no action of this launch carries its reset_before mark, the
             # next launch's first action belongs to the NEW episode (analytic.py:866-882: every episode opens with reset()'s obs)
             for e in np.nonzero(out.get('tail_reset_index', np.zeros(E, dtype=np.int64)))[0]:
-                cur[e] = _new_episode(out['reset_obs'][e, int(out['tail_reset_index'][e]) - 1].copy(), e)
+                cur[e] = _new_episode(reset_obs[e, int(out['tail_reset_index'][e]) - 1].copy(), e)
     else:
-        cur = [_new_episode(obs[e].copy(), e) for e in range(E)]
+        seen = obs if fmt is None else _state_images(env, fmt, image_kw)      # what the episodes record; the policy reads '1d'
+        cur = [_new_episode(seen[e].copy(), e) for e in range(E)]
         steps = np.zeros(E, dtype=np.int64)
         while len(episodes) < max_episodes:
             act = np.asarray(policy.get_action(obs, t=int(steps.max())), dtype=np.float64)
+            side = env.init_side.copy()
             obs, rew, done, info = env.step(act, auto_reset=True)
             last = info.get('terminal_observation', obs)
+            if fmt is not None:                                       # the present states, and the finished episodes' last ones
+                seen = _state_images(env, fmt, image_kw)
+                last = seen
+                if 'terminal_observation' in info:
+                    m = np.nonzero(info['reset_mask'])[0]
+                    last = seen.copy()
+                    last[m] = env.render_observations(info['terminal_observation'][m], fmt=fmt,
+                                                      swap_sides=~side[m] if env._init_type == 'tier2' else None, **dict(image_kw or {}))
+            else:
+                seen = obs
             for e in range(E):
                 ep = cur[e]
                 ep['obs'].append(last[e].copy())
@@ -93,7 +120,7 @@ def collect_demos(env, policy='oracle_corner', max_episodes=10, slots_per_launch
                 steps[e] += 1
                 if done[e]:
                     episodes.append(ep)
-                    cur[e] = _new_episode(obs[e].copy(), e)
+                    cur[e] = _new_episode(seen[e].copy(), e)
                     steps[e] = 0
     episodes = episodes[:max_episodes]
     if path is not None:

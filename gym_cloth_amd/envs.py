@@ -360,6 +360,15 @@ class ClothVecEnv(object):
             return np.concatenate([rgb, d8[..., None]], axis=-1)
         return np.repeat(d8[..., None], 3, axis=-1) if use_depth else rgb
 
+    def render_observations(self, obs1d, fmt='rgbd', swap_sides=None, **render_kw):
+        """Stored '1d' observations [n, 3P] (or one, [3P]) as finished images, uint8 [n, H, W, C]: what image_obs returns for a
+        cloth at those float32 positions (fmt 'rgb' = image_obs(), 'depth' = use_depth, 'rgbd' = rgbd), rendered and finished
+        on the device in one call (ClothBatch.render_obs, source 'host'). Turns a '1d' demonstration file into an image set.
+        swap_sides[n]: the side swap of a tier-2 cloth dropped with init_side False (~init_side), which a '1d' row does not
+        record."""
+        obs1d = np.asarray(obs1d, dtype=np.float32).reshape(-1, 3 * self.P)
+        return self.batch.render_obs('host', obs=obs1d, swap_sides=swap_sides, fmt=fmt, **render_kw)
+
     # ---- action decoding (cloth_env.py:396-475) -------------------------------------------------------
     def decode_actions(self, actions, iters_up=None):
         """-> dict(x, y, x_dir_r, y_dir_r, iters_pull, bounds[E,5])."""
@@ -667,7 +676,8 @@ class ClothVecEnv(object):
         self._ep_done[ie] = False
 
     def step_many(self, actions=None, n_actions=None, policy=None, auto_reset=True, want_obs=False, reset_tail=False,
-                  actions_device_ptr=None, max_resets=None, time_budget_ms=0.0, device_rng=True, policy_choices=None):
+                  actions_device_ptr=None, max_resets=None, time_budget_ms=0.0, device_rng=True, policy_choices=None,
+                  images=None, image_kw=None):
         """T consecutive `step(a_t, auto_reset=auto_reset)` calls for every env in ONE device launch
         (clothhip_run_actions): decoding, grab, the substep loop, metrics, the terminal test and the episode resets all
         run in the kernel, envs never wait for each other, and the host only does the reward / info bookkeeping below.
@@ -692,7 +702,13 @@ class ClothVecEnv(object):
 
         Returns a dict of arrays [T, E] (rew, done, ran, executed, n_grabbed, reset_before, and the info keys of step())
         plus 'obs' [E, 3P] (state after the launch), 'actions' [T, E, 4], with want_obs 'obs_t' [T, E, 3P], and the launch's time
-        accounting 'op_ticks' / 'op_substeps' uint64[E, 4] (ClothBatch.op_ticks)."""
+        accounting 'op_ticks' / 'op_substeps' uint64[E, 4] (ClothBatch.op_ticks).
+
+        images='rgb' | 'depth' | 'rgbd' (implies want_obs) adds the image observation of every slot, rendered on the device from
+        the launch's resident observation tables after the bookkeeping (ClothBatch.render_obs; image_kw: render parameters, as
+        image_obs takes them): 'img_t' uint8 [T, E, H, W, C], what image_obs would have returned after that step, zeros where
+        `ran` is False, and 'reset_img' [E, R, H, W, C] beside 'reset_obs' (None without in-kernel resets), zeros for the resets
+        the launch did not consume. A tier-2 image swaps the side colours by the init_side its episode was dropped with."""
         from . import _lib
         import time as _time
         self._version += 1
@@ -723,6 +739,10 @@ class ClothVecEnv(object):
             raise ValueError(policy)
         if not self._delta_actions:
             raise NotImplementedError("non-delta actions are decoded on the host only (cos/sin, cloth_env.py:452-453)")
+        if images is not None:
+            if images not in _lib.IMG_FORMATS:
+                raise ValueError("images must be None, 'rgb', 'depth' or 'rgbd' (got %r)" % (images,))
+            want_obs = True
         dev_reset = auto_reset and (self._init_type in ('tier1', 'tier3') or (self._init_type == 'tier2' and device_rng))
         R = min(T, 255) if max_resets is None else int(max_resets)      # clothhip_run_actions: n_scripts in [1, 255]
         if dev_reset and not 1 <= R <= 255:
@@ -779,10 +799,12 @@ class ClothVecEnv(object):
         # per env: 100 MHz ticks of this launch spent in {actions, reset pulls, reset settling, the rest} and the update() calls of each
         out['op_ticks'], out['op_substeps'] = op_ticks, op_substeps
         n_consumed = np.zeros(E, dtype=np.int64)
+        side_t = np.zeros((T, E), dtype=bool)                         # init_side as it stands at each slot (images of tier 2)
         for t in range(T):
             r = rec[t]
             rb = r['reset_before'].astype(np.int64)
             self._apply_reset_records(np.nonzero(rb)[0], rb, rst, n_consumed, out['reset_substeps'][t], use_rng)
+            side_t[t] = self.init_side
             ran = r['ran'] == 1
             executed = np.where(ran, r['executed'], 0).astype(np.int64)
             self.total_substeps += int(executed.sum())
@@ -841,6 +863,19 @@ class ClothVecEnv(object):
                     rng.set_state(nodes[c]['before'])
                     self._pending[e] = {'nodes': nodes[c:], 'recs': chain['recs'][c:], 'sides': chain['sides'][c:]}
         _lap('rng_commit')
+        if images is not None:                                        # the launch's tables are still on the device
+            tier2 = self._init_type == 'tier2'
+            kw = dict(image_kw or {})
+            img = self.batch.render_obs('slots', valid=out['ran'].reshape(-1), swap_sides=(~side_t).reshape(-1) if tier2 else None,
+                                        fmt=images, **kw)
+            out['img_t'] = img.reshape((T, E) + img.shape[1:])
+            out['reset_img'] = None
+            if robs is not None:
+                sides = (rst['init_side'] != 0) if use_rng else self._script_sides
+                rimg = self.batch.render_obs('resets', valid=(np.arange(R)[None, :] < n_consumed[:, None]).reshape(-1),
+                                             swap_sides=(~sides).reshape(-1) if tier2 else None, fmt=images, **kw)
+                out['reset_img'] = rimg.reshape((E, R) + rimg.shape[1:])
+            _lap('images')
         obs = self.state
         _lap('obs_download')
         if reset_tail and auto_reset and self._ep_done.any():

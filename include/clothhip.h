@@ -405,6 +405,36 @@ typedef struct ClothRenderParams {
 int clothhip_render(clothhip_handle *h, const ClothRenderParams *params, const uint8_t *swap_sides, uint8_t *rgb,
                     float *depth);
 
+/* (additive, ABI 7) Finished uint8 image observations of n cloths in one call: the observation type the reference's shipped
+ * configurations train on (t{1,2,3}_rgbd.yaml; ClothEnv.state with obs_type 'blender', cloth_env.py:196-209), for every slot of
+ * an episode launch at once. Same scene and pixel rules as clothhip_render -- every image equals, byte for byte, what
+ * clothhip_render gives for the same float32 positions, finished as below -- but the z-buffer lives in LDS, band of rows by band
+ * (csrc/cloth_render_obs.hpp), the image is finished on the device, and the device scratch is that of a fixed chunk of images
+ * whatever n is.
+ *   format: CLOTHHIP_IMG_RGB [H][W][3]; CLOTHHIP_IMG_DEPTH [H][W][3], the 8-bit depth replicated (cloth_env.py:207-209);
+ *           CLOTHHIP_IMG_RGBD [H][W][4] (:202-205). The 8-bit depth of a pixel of camera-space depth d, in float32:
+ *           lo, hi = min, max of d over the image; nz = hi > lo ? (d - lo) / (hi - lo) : 0; d8 = max(0, rint(nz * 255) - 50)
+ *           (get_image_rep_279.py:390-406, cloth_env.py:301-302; rint rounds half to even).
+ *   source: where the n cloths come from, each converted to float32 as clothhip_render converts the state.
+ *   valid[n] or NULL (= all): an image with valid[i] == 0 is not rasterised, its bytes are zero.
+ *   swap[n] or NULL: != 0 swaps the two side colours of image i (a tier-2 cloth with init_side False).
+ *   out: host [n][H][W][C] or NULL; d_out: device buffer of the same layout on the handle's device, or NULL. With d_out the images
+ *   are rendered into it (and copied to out as well when both are given); byte offsets are 64-bit.
+ * Runs on the handle's stream and returns when out is filled / the work on d_out has completed.
+ * CLOTHHIP_EINVAL: n does not match the source, unknown format or source, the image-size or lens rules of clothhip_render, an
+ * image too wide for a one-row band in LDS beside the grid, CLOTHHIP_OBS_HOST without obs_host. CLOTHHIP_ESTATE:
+ * CLOTHHIP_OBS_SLOTS / CLOTHHIP_OBS_RESETS before any clothhip_run_actions launch, between its _begin and _end, or when the last
+ * launch was not given want_obs / want_reset_obs (the tables stay resident until the next launch). A failed call writes
+ * nothing; n == 0 succeeds. */
+enum { CLOTHHIP_IMG_RGB = 0, CLOTHHIP_IMG_DEPTH = 1, CLOTHHIP_IMG_RGBD = 2 };
+enum { CLOTHHIP_OBS_STATE = 0,   /* the handle's particles, n == E */
+       CLOTHHIP_OBS_SLOTS = 1,   /* obs table of the last run_actions launch, n == T*E, image i = slot [t][e] */
+       CLOTHHIP_OBS_RESETS = 2,  /* its reset_obs table, n == E*n_scripts, image i = [e][k] */
+       CLOTHHIP_OBS_HOST = 3 };  /* obs_host[n][3P] float32, uploaded */
+int clothhip_render_obs(clothhip_handle *h, const ClothRenderParams *p, int32_t source, const float *obs_host,
+                        int64_t n, const uint8_t *valid /*[n] or NULL = all*/, const uint8_t *swap /*[n] or NULL*/,
+                        int32_t format, uint8_t *out /*host [n][H][W][C] or NULL*/, void *d_out /*device, same layout, or NULL*/);
+
 /* Raw device buffers on the handle's device, for the multi-GPU driver's RCCL staging (action tables in, result /
  * observation tables out; gym_cloth_amd/dist.py). upload/download run on the handle's stream and synchronise it, so
  * they are ordered with the stepper launches. */
@@ -479,6 +509,15 @@ int clothhip_selftest_layout(const ClothParams *params, int32_t precision, int32
  * 2 uniform(a, b), 3 randint((uint32)a), 4 _randval_minabs(a, b, minabs = c) into out[n]; kind 5 skips (uint64)a words.
  * state[625] = key[624], pos: numpy RandomState.get_state()[1:3], advanced in place. No device needed. */
 int clothhip_selftest_rng(uint32_t *state, int32_t kind, int32_t n, double a, double b, double c, double *out);
+
+/* Host-side self-tests of clothhip_render_obs; no device needed.
+ * _depth8: the finishing rule of its DEPTH / RGBD formats, through the same inline function the kernel runs (csrc/cloth_render_obs.hpp
+ * depth8): depth[n_images][npx] float32 camera-space depth -> out[n_images][npx], lo / hi taken per image.
+ * _render_plan: the band plan for a params->n_side grid and a width x height image: out[4] = {rows per band, bands per image,
+ * dynamic LDS bytes per workgroup, 1 if it fits}; 0 in the last entry: not even a one-row band fits beside the grid's per-vertex arrays
+ * (out[2] is then what that band would need) and clothhip_render_obs returns CLOTHHIP_EINVAL for that size. */
+int clothhip_selftest_depth8(const float *depth, int32_t n_images, int64_t npx, uint8_t *out);
+int clothhip_selftest_render_plan(const ClothParams *params, int32_t width, int32_t height, int32_t out[4]);
 int clothhip_selftest_arith(int32_t device, int32_t op, const double *a, const double *b, double *out,
                             int64_t n);
 
