@@ -3,160 +3,80 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <climits>
 #include <cmath>
-#include <cstdarg>
 #include <cstddef>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
-#include <string>
 #include <utility>
 #include <vector>
 
 #include "cloth_kernels.hpp"
-#include "stepper_variants.hpp"
-#include "lean_rates.hpp"
+#include "device_buffer.hpp"
+#include "layout_plan.hpp"
 #include "cloth_render.hpp"
 #include "cloth_render_obs.hpp"
 
 using namespace clothhip;
 
-static thread_local std::string g_err;
-
-static int fail(int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-
-#define HIPCHECK(expr)                                                                          \
-    do {                                                                                        \
-        hipError_t err_ = (expr);                                                               \
-        if (err_ != hipSuccess)                                                                 \
-            return fail(CLOTHHIP_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(err_), \
-                        __FILE__, __LINE__);                                                    \
-    } while (0)
-
-
-// metrics_block (cloth_metrics.hpp) for a grid of P points: it sorts NS values (the next power of two >= P) and its hull's monotone chain holds
-// at most m + 1 <= P + 1 points (NH)
-struct MetricsDims { int NS, NH; };
-static inline MetricsDims metrics_dims(int P, int Ppad) { int n = 1; while (n < P) n <<= 1; return {n, Ppad + 8}; }
-// ... and its LDS scratch: two sort buffers of NS values in the handle's precision, 64 doubles, the hull stack (NH points, or NH u16 indices)
-static inline int metrics_scratch_bytes(MetricsDims d, int tsz, bool hull_idx) {
-    return hull_idx ? 2 * d.NS * tsz + 64 * 8 + ((2 * d.NH + 15) / 16) * 16 : 2 * d.NS * tsz + (2 * d.NH + 64) * 8;
-}
-
-// Every CLOTHHIP_DEBUG_* switch, read here and nowhere else. The planning switches are read when a handle is created
-// (clothhip_create, clothhip_selftest_layout) and kept on it; NOSPEC and ONE_LAUNCH are read again at every launch.
-struct DebugKnobs {
-    bool w8_off = false;         // W8=0: the four-wave standard builds of the 25x25 class (only the value 0 switches)
-    bool nt1024 = false;         // NT1024 (set at all): 1024 x 3 instead of 512 x 5 for the grids of 769 .. 2 560 points
-    int tab_lds = INT_MAX;       // TAB_LDS: caps the standard layout's TAB code (TAB_STREAM < TAB_LDS)
-    bool rest_reg = true;        // REST_REG=0: no rest lengths in registers
-    bool cell_copy = true;       // CELL_COPY=0: no cell-ordered record copy (the switch can only turn it off)
-    bool lean_set = false;       // LEAN: 0 never the LEAN arithmetic, 8 (or 2) its eight-wave build, 3 (or 1) / 4 / 5 / 6 its build for that
-    int lean = 0;                //   many cloths per CU; any value also keeps clothhip_create from lowering the residency after its occupancy query
-    bool large2_set = false, large2 = false;   // LARGE2: 0 / 1 one / two large-grid cloths per CU
-    int phase_mask = 15;         // PHASES: phase ablation mask
-    bool nospec = false;         // NOSPEC (nonzero): the generic build instead of the grid-specialised one
-    bool one_launch = false;     // ONE_LAUNCH (set at all): a time-sliced episode launch as one dispatch, not one per generation
-    int render_lds_kib = 160;    // RENDER_LDS: LDS budget in KiB of a clothhip_render_obs workgroup (smaller: shorter bands, more workgroups per CU)
-    bool render_walk = false;    // RENDER_WALK (nonzero): one workgroup walks all bands of an image instead of one workgroup per band
-};
-static DebugKnobs read_debug_knobs() {
-    DebugKnobs k;
-    if (const char *t = getenv("CLOTHHIP_DEBUG_W8")) k.w8_off = atoi(t) == 0;
-    k.nt1024 = getenv("CLOTHHIP_DEBUG_NT1024") != nullptr;
-    if (const char *t = getenv("CLOTHHIP_DEBUG_TAB_LDS")) k.tab_lds = atoi(t);
-    if (const char *t = getenv("CLOTHHIP_DEBUG_REST_REG")) k.rest_reg = atoi(t) != 0;
-    if (const char *t = getenv("CLOTHHIP_DEBUG_CELL_COPY")) k.cell_copy = atoi(t) != 0;
-    if (const char *t = getenv("CLOTHHIP_DEBUG_LEAN")) { k.lean_set = true; k.lean = atoi(t); }
-    if (const char *t = getenv("CLOTHHIP_DEBUG_LARGE2")) { k.large2_set = true; k.large2 = atoi(t) != 0; }
-    if (const char *t = getenv("CLOTHHIP_DEBUG_PHASES")) k.phase_mask = atoi(t);
-    if (const char *t = getenv("CLOTHHIP_DEBUG_NOSPEC")) k.nospec = atoi(t) != 0;
-    k.one_launch = getenv("CLOTHHIP_DEBUG_ONE_LAUNCH") != nullptr;
-    if (const char *t = getenv("CLOTHHIP_DEBUG_RENDER_LDS")) { const int v = atoi(t); if (v >= 1 && v <= 160) k.render_lds_kib = v; }
-    if (const char *t = getenv("CLOTHHIP_DEBUG_RENDER_WALK")) k.render_walk = atoi(t) != 0;
-    return k;
-}
-
-struct clothhip_handle {
-    ClothParams prm{};
-    int E = 0, N = 0, P = 0, Ppad = 0, S = 0, Spad = 0, precision = 0, device = 0;
-    size_t tsz = 8;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+// The host fields (HostPlan: layout_plan.hpp) and everything the handle holds on its device. Each buffer frees itself; the stream and the
+// events are declared in front of the buffers, so they go after them.
+struct clothhip_handle : HostPlan {
+    int device = 0;
+    Stream stream;
+    Event ev0, ev1, ev_fork;   // ev_fork (clothhip_fork): orders a fork after the source handle's stream
+    ~clothhip_handle() { (void)hipSetDevice(device); }
     bool have_timing = false, pending_exec = false;
-    void *d_pos = nullptr, *d_prev = nullptr, *d_rest = nullptr;
-    void *d_flat = nullptr, *d_flat_rest = nullptr;   // flat tier-1 grid [3][Ppad] and its rest table [Spad] (window-table slot order), handle precision
-    uint8_t *d_cnt = nullptr, *d_active = nullptr;
+    Buffer<void> d_pos, d_prev, d_rest;
+    Buffer<void> d_flat, d_flat_rest;   // flat tier-1 grid [3][Ppad] and its rest table [Spad] (window-table slot order), handle precision
+    Buffer<uint8_t> d_cnt, d_active;
     int rest_stride = 0;
-    int32_t *d_tear = nullptr, *d_exec = nullptr, *d_ngrab = nullptr, *d_stats = nullptr;
-    ClothSchedule *d_sched = nullptr, *h_sched = nullptr;   // h_sched: pinned staging
-    uint32_t *d_gather = nullptr, *d_wt_ent = nullptr;
-    unsigned long long *d_wt_dep = nullptr;
-    DebugKnobs dbg;
-    // LEAN stepper (fp32, n_side <= 27, batches of >= 1024 cloths): 168 VGPRs and 33 KB of LDS per cloth -> three cloths per CU.
-    // It needs ONE shared rest table whose fp32 values are one per spring type (checked on the device's table whenever that table
-    // may have changed) and the regular gather stencil (checked once); otherwise the (0, false) variant runs on the same layout.
-    bool lean = false, lean_dirty = true, lean_ok = false, lean_stencil_ok = false;
+    Buffer<int32_t> d_tear, d_exec, d_ngrab, d_stats;
+    Buffer<ClothSchedule> d_sched;
+    PinnedBuffer<ClothSchedule> h_sched;   // pinned staging
+    Buffer<uint32_t> d_gather, d_wt_ent;
+    Buffer<unsigned long long> d_wt_dep;
+    bool lean_dirty = true, lean_ok = false;   // (HostPlan::lean: the shared rest table is checked whenever it may have changed)
     bool relaxed = false;   // clothhip_set_relaxed_order(h, 1): THIS handle's episode launches run the relaxed-order companion kernel (bench only, no parity)
     int last_dispatches = 0; // kernel dispatches the last stepper launch was issued as (clothhip_last_dispatches)
     int spec_now = 0;        // 25 / 50: the layout in use runs that grid-specialised build (decided by lean_refresh per launch: spec_ns); 0: the generic build
     int last_spec = 0;       // what the last launch ran (clothhip_last_specialised)
-    int lean_r = 3;         // cloths per CU the chosen LEAN build is compiled for (3: 168 VGPRs, 4: 128 VGPRs; 2: eight waves per cloth, table in LDS; 1: the large grids)
     float pal[3] = {0, 0, 0};
     double pal64[3] = {0, 0, 0};     // fp64 LEAN build: the smallest rest length of each spring type (the others are it + a few ulps: StepArgs::lstc)
-    uint4 *d_lstc = nullptr;         // [Ppad] fp64 LEAN build: per particle {stencil mask, 12 offset bytes}
+    Buffer<uint4> d_lstc;            // [Ppad] fp64 LEAN build: per particle {stencil mask, 12 offset bytes}
     // per-env materials (clothhip_set_material): every env's effective values; how many differ bitwise from the handle's parameters (0: a uniform
     // handle -- no table goes to the kernel, the grid-specialised builds stay eligible); the device's [E] DevConsts<T> table, allocated by the first set
     std::vector<ClothMaterial> mat;
     int n_mixed = 0;
-    void *d_mat = nullptr;
+    Buffer<void> d_mat;
     int32_t last_variant[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // what the last launch ran (clothhip_last_variant)
     bool have_variant = false;
-    int n_cus = 0;
-    // the two layouts a handle may run (plan_layouts) and which one runs now (lean_refresh)
-    Layout lay_std = {Variant{8, 256, 3, TAB_STREAM, false}, 0, 0, 0, 0, 0, 0}, lay_lean = {Variant{8, 256, 3, TAB_STREAM, true}, 0, 0, 0, 0, 0, 0};
-    bool on_lean = false;
+    bool on_lean = false;            // which of the two layouts runs now (lean_refresh)
     const Layout &lay() const { return on_lean ? lay_lean : lay_std; }
     struct OccKey { const void *fn; int lds; int occ; } occ_cache[8] = {};   // hipOccupancyMaxActiveBlocksPerMultiprocessor per (kernel, LDS bytes)
-    double *d_levels = nullptr, *d_xy = nullptr, *d_radius = nullptr, *d_cov = nullptr, *d_vinv = nullptr;
-    uint8_t *d_oob = nullptr;
-    int32_t *d_hcnt = nullptr;      // per env: #points with z < thickness/2 (height reward, cloth_env.py:1047-1073)
+    Buffer<double> d_levels, d_xy, d_radius, d_cov, d_vinv;
+    Buffer<uint8_t> d_oob;
+    Buffer<int32_t> d_hcnt;         // per env: #points with z < thickness/2 (height reward, cloth_env.py:1047-1073)
     int n_grab_levels = 0;
-    // clothhip_run_actions staging (device), grown on demand
-    void *d_fz = nullptr, *d_fact = nullptr, *d_fscr = nullptr, *d_frec = nullptr, *d_frst = nullptr, *d_fobs = nullptr, *d_frobs = nullptr;
-    int32_t *d_fsteps = nullptr, *d_fparg = nullptr;
-    EpResume *d_resume = nullptr;   // [E] operations cut by a time slice (clothhip_run_actions), continued by the next launch
-    uint32_t *d_fmt = nullptr;      // [E][MT_WORDS] numpy RandomState of every env (device-drawn resets)
-    uint8_t *d_fdone = nullptr;
-    double *d_fsum = nullptr;       // [E][4] per-env summary of the last episode launch (what the multi-GPU driver all-gathers)
-    uint64_t *d_fticks = nullptr;   // [E][8] per-operation-class ticks and update() counts of the last episode launch
+    // clothhip_run_actions staging (device), sized on demand
+    Buffer<void> d_fz, d_fact, d_fscr, d_frec, d_frst, d_fobs, d_frobs;
+    Buffer<int32_t> d_fsteps, d_fparg;
+    Buffer<EpResume> d_resume;      // [E] operations cut by a time slice (clothhip_run_actions), continued by the next launch
+    Buffer<uint32_t> d_fmt;         // [E][MT_WORDS] numpy RandomState of every env (device-drawn resets)
+    Buffer<uint8_t> d_fdone;
+    Buffer<double> d_fsum;          // [E][4] per-env summary of the last episode launch (what the multi-GPU driver all-gathers)
+    Buffer<uint64_t> d_fticks;      // [E][8] per-operation-class ticks and update() counts of the last episode launch
     int f_T = 0; size_t f_nscr = 0; bool f_pending = false, f_resets = false, f_obs = false, f_robs = false, f_mt = false;
-    size_t cap_fact = 0, cap_frec = 0, cap_fobs = 0, cap_fscr = 0, cap_frst = 0, cap_frobs = 0, cap_fparg = 0;
-    // clothhip_render_obs scratch for ONE chunk of images, grown on demand: finished images (when the caller gives no device buffer),
+    // clothhip_render_obs scratch for ONE chunk of images, sized on demand: finished images (when the caller gives no device buffer),
     // raw depth, uploaded '1d' rows, valid + swap flags
-    void *d_ro_img = nullptr, *d_ro_depth = nullptr, *d_ro_src = nullptr, *d_ro_flags = nullptr;
-    size_t cap_ro_img = 0, cap_ro_depth = 0, cap_ro_src = 0, cap_ro_flags = 0;
-    Topology topo;
-    WindowTable wt;
-    std::vector<uint32_t> gather;       // the gather table (host copy of d_gather): the LEAN stencil checks read it
+    Buffer<void> d_ro_img, d_ro_depth, d_ro_src, d_ro_flags;
     std::vector<unsigned char> stage;   // host staging for layout conversion
     std::vector<double> flat_rest;
     // clothhip_fork: the bytes of the ONE shared rest table as clothhip_set_state last uploaded them (handle precision, slot order) -- the only
-    // writer of a shared table, so two shared tables are equal exactly when these mirrors are; the device index lists of a fork; the event
-    // that orders a fork after the source handle's stream
+    // writer of a shared table, so two shared tables are equal exactly when these mirrors are; the device index lists of a fork
     std::vector<unsigned char> shared_rest;
-    int32_t *d_fork_idx = nullptr, *h_fork_idx = nullptr; size_t cap_fork_idx = 0;   // (h_: pinned staging, so that the upload is a plain DMA)
-    hipEvent_t ev_fork = nullptr;
+    Buffer<int32_t> d_fork_idx;
+    PinnedBuffer<int32_t> h_fork_idx;   // (pinned staging, so that the upload is a plain DMA)
 };
 
 // f(float{}) or f(double{}) by the handle's precision: a launch that exists in both precisions is written once, as a generic lambda
@@ -258,194 +178,7 @@ static SpecPhys phys_of(const ClothParams &p, const ClothMaterial &m) {
 }
 static ClothMaterial material_of(const ClothParams &p) { return ClothMaterial{p.density, p.ks, p.damping, p.plane_friction, p.tear_thresh, p.gravity}; }
 
-static void free_handle(clothhip_handle *h) {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    void *ptrs[] = {h->d_pos, h->d_prev, h->d_rest, h->d_cnt, h->d_active, h->d_tear, h->d_exec, h->d_ngrab, h->d_stats,
-                    h->d_sched, h->d_flat, h->d_flat_rest, h->d_hcnt, h->d_fz, h->d_fact, h->d_fscr, h->d_frec, h->d_frst, h->d_fobs, h->d_frobs, h->d_fsteps, h->d_fparg, h->d_fdone, h->d_fticks, h->d_fsum, h->d_fmt, h->d_resume, h->d_gather, h->d_wt_ent, h->d_wt_dep, h->d_lstc, h->d_mat, h->d_fork_idx, h->d_levels, h->d_xy, h->d_radius, h->d_cov, h->d_vinv, h->d_oob,
-                    h->d_ro_img, h->d_ro_depth, h->d_ro_src, h->d_ro_flags};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    if (h->h_sched) (void)hipHostFree(h->h_sched);
-    if (h->h_fork_idx) (void)hipHostFree(h->h_fork_idx);
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-}
-
 static int spec_ns(const clothhip_handle *h, const Layout &L, bool with_palette = true);
-static int grow(void **p, size_t *cap, size_t need);
-
-// The LDS a layout leaves the in-kernel metrics (from the hash table to the end of the allocation) against what they need; the
-// allocation is padded behind the layout's end when that fits the budget (the kernel addresses LDS by the layout's offsets: bytes
-// behind `total` are free). False: the episode launches cannot run on this layout.
-static bool fit_scratch(const clothhip_handle *h, Layout &L, int budget) {
-    const LdsLayout lay = lds_layout(L.v, h->Ppad, h->Spad, L.HT, L.cell_copy);
-    L.scratch_need = metrics_scratch_bytes(metrics_dims(h->P, h->Ppad), L.v.tsz, L.v.hull_as_indices());
-    if (L.lds_bytes < lay.total) L.lds_bytes = lay.total;
-    if (L.lds_bytes - lay.hkey < L.scratch_need && lay.hkey + L.scratch_need <= budget) L.lds_bytes = (lay.hkey + L.scratch_need + 15) / 16 * 16;
-    L.scratch_have = L.lds_bytes - lay.hkey;
-    return L.scratch_have >= L.scratch_need;
-}
-
-// LDS a workgroup may use when r workgroups are to share a CU: LDS is allocated in granules of 1 280 bytes on gfx950 (128 granules = the CU's
-// 160 KiB), so r cloths fit when each takes at most floor(128 / r) granules -- 160 KiB / r overstates that for r = 3, 5, 6.
-static constexpr int LDS_GRANULE = 1280;
-static constexpr int lds_budget(int r) { return (128 / (r < 1 ? 1 : r)) * LDS_GRANULE; }
-static_assert(lds_budget(1) == 160 * 1024 && lds_budget(2) == 80 * 1024 && lds_budget(4) == 40 * 1024, "granule arithmetic");
-
-// A layout of variant v with a hash table of HT (a power of two) slots: the cell-ordered record copy for the collision
-// pre-check is taken only if the layout with it fits `budget` (and CLOTHHIP_DEBUG_CELL_COPY allows it). The scratch of the in-kernel
-// metrics is the caller's (fit_scratch).
-static Layout make_layout(const clothhip_handle *h, Variant v, int HT, int budget) {
-    const int cc = h->dbg.cell_copy && lds_layout(v, h->Ppad, h->Spad, HT, 1).total <= budget ? 1 : 0;
-    int ht_bits = 0;
-    while ((1 << ht_bits) < HT) ht_bits++;
-    return {v, cc, lds_layout(v, h->Ppad, h->Spad, HT, cc).total, HT, ht_bits, 0, 0};
-}
-
-// For particle i: body(k, g) for each stencil position k that exists (lean_valid_mask), g = the particle's slot-th gather entry, slot = how
-// many positions below k exist (the gather table is compacted). Stops when body returns false (-1); else the number of entries visited.
-template <typename F> static int walk_stencil(const clothhip_handle *h, int i, F &&body) {
-    const uint32_t vm = lean_valid_mask(i / h->N, i % h->N, h->N);
-    int slot = 0;
-    for (int k = 0; k < HK_SLOTS; k++) {
-        if (!((vm >> k) & 1u)) continue;
-        if (!body(k, h->gather[(size_t)slot * h->Ppad + i])) return -1;
-        slot++;
-    }
-    return slot;
-}
-
-// Which stepper variants and which LDS layouts a handle runs: pure host logic (no HIP call), so that the CPU test suite can sweep it
-// over grid sizes and precisions (clothhip_selftest_layout). Fills the standard layout lay_std and, where the LEAN arithmetic applies,
-// lay_lean, lean and lean_r.
-// max_r: the highest residency the pick may choose (clothhip_create lowers it when the device's occupancy query grants the chosen LEAN
-// build fewer workgroups per CU than it was planned for).
-static void plan_layouts(clothhip_handle *h, int cus, int max_r = 6) {
-    const DebugKnobs &dbg = h->dbg;
-    const int tsz = (int)h->tsz, precision = h->precision;
-    // threads per cloth x particles per thread (compile-time variants of the stepper)
-    // P <= 768 (the 25x25 class, two cloths per CU): EIGHT waves per cloth -- 512 threads x 2 particles, compiled for 128 VGPRs: the cell
-    // sweeps have eight ticket takers and the parallel phases two waves per SIMD to hide their LDS latency (+4 % fp32 standard
-    // arithmetic, +9 % fp64, +13 % tier 2 over the four-wave 256 x 3 variants, bit-identical; CLOTHHIP_DEBUG_W8=0 selects those)
-    const bool small_grid = h->P <= 768;
-    int nt, ppt;
-    if (small_grid) { nt = dbg.w8_off ? 256 : 512; ppt = dbg.w8_off ? 3 : 2; }
-    else if (h->P <= 2560 && !dbg.nt1024) { nt = 512; ppt = 5; }
-    else if (h->P <= 3072) { nt = 1024; ppt = 3; } else { nt = 1024; ppt = 4; }
-    int HT = 64;
-    while (HT <= h->P + h->P / 2) HT <<= 1;
-    // large dynamic LDS (up to the CU's 160 KiB) for the stepper kernels. The static tables ride in LDS too
-    // as long as TWO cloths still fit per CU (512 cloths = 2 per CU on the 256 CUs of an MI355X).
-    // 256-thread variants: two cloths per CU (<= 80 KiB each); the larger ones own the CU (<= 160 KiB)
-    const int budget = small_grid ? lds_budget(2) : lds_budget(1);
-    Variant vstd{tsz, nt, ppt, TAB_LDS, false};
-    vstd.tab = std::min((nt <= 512 && lds_layout(vstd, h->Ppad, h->Spad, HT, 0).total <= budget) ? TAB_LDS : TAB_STREAM, dbg.tab_lds);
-    vstd.rest_reg = nt == 256 && precision == CLOTHHIP_F32 && vstd.table_in_lds() && dbg.rest_reg;
-    // LEAN variants: three to six cloths per CU instead of two, each stepping at a lower rate (lean_rates.hpp, measured by
-    // tools/measure_pick_table.py). A launch runs its cloths in generations of what is resident, so the batch size decides:
-    // the largest rate_r / ceil(E / (r * CUs)) wins.
-    {
-        h->n_cus = cus;
-        // substeps/s of ONE resident cloth at 2 (standard), 3 and 4 cloths per CU, relative to the standard variant's: measured
-        // by tools/measure_pick_table.py on the bench workload and written to lean_rates.hpp (its output: profiles/)
-        // r = 2: the EIGHT-WAVE LEAN build (512 threads x 2 particles, window table in LDS) when the flat palette holds, else the
-        // standard variant; r = 3 .. 6: the four-wave LEAN builds with the table streamed from L2 (168 / 128 / 96 / 80 VGPRs; from
-        // five per CU on without the cell-ordered record copy: 22.6 KB of LDS per cloth)
-        const bool lean_able = small_grid && precision == CLOTHHIP_F32;
-        const double rate[5] = {lean_able ? LEAN_RATE_2_PER_CU_8W : 1.0, LEAN_RATE_3_PER_CU, LEAN_RATE_4_PER_CU, LEAN_RATE_5_PER_CU, LEAN_RATE_6_PER_CU};
-        double best = 0.0; int best_r = 2;
-        for (int r = 2; r <= std::max(2, std::min(6, max_r)); r++) {
-            // (r >= 3: the four-wave LEAN layout, table streamed, must fit r times in the CU's LDS -- 27x27 does not at five per CU)
-            if (r >= 3 && (!lean_able || lds_layout(lean_four_wave(r), h->Ppad, h->Spad, HT, 0).total > lds_budget(r))) continue;
-            const double v = rate[r - 2] / (double)((h->E + r * cus - 1) / (r * cus));
-            if (v > best * 1.02) { best = v; best_r = r; }
-        }
-        h->lean = lean_able;
-        h->lean_r = best_r;
-        // the large grids (one cloth per CU): the LEAN arithmetic frees the registers of the gather entries and takes the rest lengths
-        // off the L2 path, which lets SIXTEEN waves step a cloth at 128 VGPRs (1024 threads x 3 or 4 particles; 50x50: 2.90 M/s
-        // standard 512 x 5 -> 3.05 LEAN 512 x 5 -> 3.26 LEAN 1024 x 3); the standard variant stays as the fallback (per-env rest tables)
-        if (!small_grid && precision == CLOTHHIP_F32) { h->lean = true; h->lean_r = 1; }
-        // fp64, 25x25 class, eight waves per cloth (round 6): the LEAN arithmetic with per-spring ulp offsets (StepArgs::lstc) -- no gather-table and no
-        // rest-length loads from L2 in the Hooke gather and the strain pre-pass; same layout class as the standard fp64 variant (two cloths per CU)
-        if (small_grid && precision == CLOTHHIP_F64 && nt == 512) { h->lean = true; h->lean_r = 2; }
-    }
-    if (dbg.lean_set) {      // 0: never; 8 (or 2): the eight-wave build; 3 (or 1) / 4 / 5 / 6: the LEAN build for that many cloths per CU, whatever the batch size
-        if (dbg.lean == 0) h->lean = false;
-        else if (small_grid && precision == CLOTHHIP_F32) { h->lean = true; h->lean_r = (dbg.lean == 8 || dbg.lean == 2) ? 2 : ((dbg.lean >= 4 && dbg.lean <= 6) ? dbg.lean : 3); }
-    }
-    if (h->lean) {
-        // the arithmetic stencil of the LEAN kernel against the gather table built from the reference's spring list
-        h->lean_stencil_ok = true;
-        for (int i = 0; i < h->P && h->lean_stencil_ok; i++) {
-            const int n = walk_stencil(h, i, [&](int k, uint32_t g) {
-                const uint32_t want = (uint32_t)(i + lean_off(k, h->N)) | HK_VALID | (k < HK_SLOTS / 2 ? HK_ASB : 0u) | (lean_bend(k) ? HK_BEND : 0u);
-                const uint32_t have = g & (HK_NBR_MASK | HK_VALID | HK_ASB | HK_BEND);
-                const int sp = h->wt.spring_at[(g >> HK_POS_SHIFT) & HK_POS_MASK];
-                const int ty = sp >= 0 ? h->topo.type[sp] : -1;
-                const int want_ty = lean_bend(k) ? SPRING_BENDING : (lean_shear(k) ? SPRING_SHEARING : SPRING_STRUCTURAL);
-                return have == want && ty == want_ty;
-            });
-            // (and the entry behind the last one the stencil has must be empty)
-            if (n < 0 || (n < HK_SLOTS && (h->gather[(size_t)n * h->Ppad + i] & HK_VALID))) h->lean_stencil_ok = false;
-        }
-        if (!h->lean_stencil_ok) h->lean = false;
-    }
-    // the cell-ordered record copy for the collision pre-check is taken only if it does not cost the table its place
-    h->lay_std = make_layout(h, vstd, HT, budget);
-    // the in-kernel metrics of the episode launches borrow the LDS from the hash table on (the window table in front of it stays
-    // resident). With the table in LDS but no room for the cell-ordered copy that region can be too small (fp64 21, 22, 30-32;
-    // fp32 41-43): the allocation is then padded behind the layout's end, or, if the budget forbids that, the table leaves LDS
-    if (!fit_scratch(h, h->lay_std, budget) && vstd.table_in_lds()) {
-        h->lay_std = make_layout(h, Variant{tsz, nt, ppt, TAB_STREAM, false}, HT, budget);
-        fit_scratch(h, h->lay_std, budget);
-    }
-    if (!h->lean) return;
-    if (precision == CLOTHHIP_F64) {                     // fp64 LEAN: table streamed, the stencil constants in LDS
-        h->lay_lean = make_layout(h, Variant{tsz, 512, 2, TAB_STREAM, true}, HT, lds_budget(2));
-        if (h->lay_lean.lds_bytes > lds_budget(2)) h->lean = false;
-    } else if (h->lean_r == 2 && small_grid) {           // eight waves per cloth, two cloths per CU: the standard variant's LDS budget
-        h->lay_lean = make_layout(h, Variant{tsz, 512, 2, TAB_LDS_SLOTS, true}, HT, 80 * 1024);
-        if (h->lay_lean.lds_bytes > 80 * 1024 || h->P > 1024) h->lean = false;      // (the table must fit beside a second cloth)
-    } else if (h->lean_r == 1) {                         // the whole CU: same LDS budget as the standard variant of these grids
-        h->lay_lean = make_layout(h, Variant{tsz, 1024, h->P <= 3072 ? 3 : 4, TAB_LARGE_1, true}, HT, 160 * 1024);
-        // TWO large-grid cloths per CU (eight waves each, 128 VGPRs) when the batch has more cloths than the device has CUs and it
-        // pays by the measured rates: <= 80 KB of LDS per cloth -- no cell-ordered copy, and a hash table of just enough slots
-        // (not a power of two: > P, so that a free slot always exists, and large enough that the in-kernel metrics' scratch fits)
-        const Variant v2{tsz, 512, 5, TAB_LARGE_2, true};
-        const int need2 = metrics_scratch_bytes(metrics_dims(h->P, h->Ppad), tsz, v2.hull_as_indices());
-        int ht2 = (h->P / 64 + 2) * 64;
-        auto lay2 = [&]() { return lds_layout(v2, h->Ppad, h->Spad, ht2, 0); };
-        while (lay2().total - lay2().hkey < need2) ht2 += 64;
-        const int lds2 = lay2().total;
-        const int gens1 = (h->E + h->n_cus - 1) / h->n_cus, gens2 = (h->E + 2 * h->n_cus - 1) / (2 * h->n_cus);
-        const bool fits2 = h->P <= 2560 && lds2 <= 80 * 1024;
-        if (dbg.large2_set ? dbg.large2 && fits2 : fits2 && LEAN_RATE_LARGE_2_PER_CU / gens2 > 1.02 / gens1) {
-            h->lay_lean = {v2, 0, lds2, ht2, 0, 0, 0}; h->lean_r = 2;
-        }
-    } else {                                             // the four-wave LEAN builds, window table streamed from L2, 33 KB of LDS
-        h->lay_lean = make_layout(h, lean_four_wave(h->lean_r), HT, lds_budget(h->lean_r));
-    }
-    // the in-kernel metrics borrow the region behind the hash table (clothhip_fused_supported): it must hold them here too
-    if (!fit_scratch(h, h->lay_lean, lds_budget(h->lean_r))) h->lean = false;
-}
-
-// The host fields of a handle -- grid, topology, window and gather tables, debug switches: nothing here touches a device (clothhip_create,
-// and clothhip_selftest_layout, which plans on a handle that has nothing else)
-static void init_host_fields(clothhip_handle *h, const ClothParams &p, int n_envs, int precision) {
-    h->prm = p; h->E = n_envs; h->precision = precision;
-    h->N = p.n_side; h->P = h->N * h->N; h->Ppad = (h->P + 63) / 64 * 64;
-    h->tsz = precision == CLOTHHIP_F64 ? 8 : 4;
-    h->topo = build_topology(h->N);
-    h->wt = build_windows(h->topo, build_levels(h->topo));
-    h->S = h->topo.S; h->Spad = h->wt.n_slots;               // rest-length arrays are kept in window-table slot order
-    h->dbg = read_debug_knobs();
-    h->gather = build_gather(h->topo, h->wt, h->Ppad);
-    h->mat.assign((size_t)n_envs, material_of(p));
-}
 
 extern "C" int clothhip_create(const ClothParams *params, int32_t n_envs, int32_t device, int32_t precision,
                                clothhip_handle **out) {
@@ -458,61 +191,37 @@ extern "C" int clothhip_create(const ClothParams *params, int32_t n_envs, int32_
     if (ndev <= 0) return fail(CLOTHHIP_ENODEV, "no HIP device visible: libclothhip has no CPU fallback");
     if (device < 0 || device >= ndev) return fail(CLOTHHIP_EINVAL, "device %d outside [0,%d)", device, ndev);
     HIPCHECK(hipSetDevice(device));
-    clothhip_handle *h = new (std::nothrow) clothhip_handle();
+    std::unique_ptr<clothhip_handle> owner(new (std::nothrow) clothhip_handle());      // (destroyed, with all it holds, by every early return)
+    clothhip_handle *const h = owner.get();
     if (!h) return fail(CLOTHHIP_ENOMEM, "out of host memory");
     h->device = device;
     init_host_fields(h, *params, n_envs, precision);
+    h->mat.assign((size_t)n_envs, material_of(*params));
     std::vector<double> levels = build_grab_levels(params->height, params->thickness);
     h->n_grab_levels = (int)levels.size();
-
-#define HC(expr)                                                                                      \
-    do {                                                                                              \
-        hipError_t err_ = (expr);                                                                     \
-        if (err_ != hipSuccess) {                                                                     \
-            int rc_ = fail(err_ == hipErrorOutOfMemory ? CLOTHHIP_ENOMEM : CLOTHHIP_EHIP,             \
-                           "%s failed: %s", #expr, hipGetErrorString(err_));                          \
-            free_handle(h);                                                                           \
-            return rc_;                                                                               \
-        }                                                                                             \
-    } while (0)
-    HC(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    HC(hipEventCreate(&h->ev0));
-    HC(hipEventCreate(&h->ev1));
+    HIPCHECK(hipStreamCreateWithFlags(&h->stream.v, hipStreamNonBlocking));
+    HIPCHECK(hipEventCreate(&h->ev0.v));
+    HIPCHECK(hipEventCreate(&h->ev1.v));
     const size_t E = h->E;
-    HC(hipMalloc(&h->d_pos, E * 3 * h->Ppad * h->tsz));
-    HC(hipMalloc(&h->d_prev, E * 3 * h->Ppad * h->tsz));
-    HC(hipMalloc(&h->d_rest, E * h->Spad * h->tsz));
-    HC(hipMalloc(&h->d_cnt, E * h->Ppad));
-    HC(hipMalloc(&h->d_active, E));
-    HC(hipMalloc(&h->d_tear, E * 4));
-    HC(hipMalloc(&h->d_exec, E * 4));
-    HC(hipMalloc(&h->d_ngrab, E * 4));
-    HC(hipMalloc(&h->d_stats, E * 64));
-    HC(hipMemset(h->d_stats, 0, E * 64));
-    HC(hipMalloc(&h->d_sched, E * sizeof(ClothSchedule)));
-    HC(hipHostMalloc((void **)&h->h_sched, E * sizeof(ClothSchedule), hipHostMallocDefault));
-    HC(hipMalloc(&h->d_gather, h->gather.size() * 4));
-    HC(hipMalloc(&h->d_wt_ent, (size_t)h->Spad * 4));
-    HC(hipMalloc(&h->d_wt_dep, (size_t)h->Spad * 8));
-    HC(hipMalloc(&h->d_lstc, (size_t)h->Ppad * 16));
-    HC(hipMemset(h->d_lstc, 0, (size_t)h->Ppad * 16));
-    HC(hipMalloc(&h->d_levels, (levels.size() + 1) * 8));
-    HC(hipMalloc(&h->d_xy, E * 2 * 8));
-    HC(hipMalloc(&h->d_radius, E * 8));
-    HC(hipMalloc(&h->d_cov, E * 8));
-    HC(hipMalloc(&h->d_vinv, E * 8));
-    HC(hipMalloc(&h->d_oob, E));
-    HC(hipMalloc(&h->d_hcnt, E * 4));
-    HC(hipMalloc(&h->d_resume, E * sizeof(EpResume)));
-    HC(hipMemset(h->d_resume, 0, E * sizeof(EpResume)));
-    HC(hipMalloc(&h->d_flat, (size_t)3 * h->Ppad * h->tsz));
-    HC(hipMalloc(&h->d_flat_rest, (size_t)h->Spad * h->tsz));
-    HC(hipMemcpy(h->d_gather, h->gather.data(), h->gather.size() * 4, hipMemcpyHostToDevice));
-    HC(hipMemcpy(h->d_wt_ent, h->wt.ent.data(), (size_t)h->Spad * 4, hipMemcpyHostToDevice));
-    HC(hipMemcpy(h->d_wt_dep, h->wt.dep.data(), (size_t)h->Spad * 8, hipMemcpyHostToDevice));
-    HC(hipMemset(h->d_rest, 0, E * h->Spad * h->tsz));
-    if (!levels.empty()) HC(hipMemcpy(h->d_levels, levels.data(), levels.size() * 8, hipMemcpyHostToDevice));
-    HC(hipMemset(h->d_exec, 0, E * 4));
+    int rc = 0;      // (the first allocation that fails ends them)
+    auto take = [&rc](auto &buf, size_t bytes) { if (!rc) rc = buf.reserve(bytes); };
+    take(h->d_pos, E * 3 * h->Ppad * h->tsz); take(h->d_prev, E * 3 * h->Ppad * h->tsz); take(h->d_rest, E * h->Spad * h->tsz);
+    take(h->d_cnt, E * h->Ppad); take(h->d_active, E); take(h->d_tear, E * 4); take(h->d_exec, E * 4); take(h->d_ngrab, E * 4); take(h->d_stats, E * 64);
+    take(h->d_sched, E * sizeof(ClothSchedule)); take(h->h_sched, E * sizeof(ClothSchedule));
+    take(h->d_gather, h->gather.size() * 4); take(h->d_wt_ent, (size_t)h->Spad * 4); take(h->d_wt_dep, (size_t)h->Spad * 8); take(h->d_lstc, (size_t)h->Ppad * 16);
+    take(h->d_levels, (levels.size() + 1) * 8); take(h->d_xy, E * 2 * 8); take(h->d_radius, E * 8); take(h->d_cov, E * 8); take(h->d_vinv, E * 8);
+    take(h->d_oob, E); take(h->d_hcnt, E * 4); take(h->d_resume, E * sizeof(EpResume));
+    take(h->d_flat, (size_t)3 * h->Ppad * h->tsz); take(h->d_flat_rest, (size_t)h->Spad * h->tsz);
+    if (rc) return rc;
+    HIPCHECK(hipMemset(h->d_stats, 0, E * 64));
+    HIPCHECK(hipMemset(h->d_lstc, 0, (size_t)h->Ppad * 16));
+    HIPCHECK(hipMemset(h->d_resume, 0, E * sizeof(EpResume)));
+    HIPCHECK(hipMemcpy(h->d_gather, h->gather.data(), h->gather.size() * 4, hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(h->d_wt_ent, h->wt.ent.data(), (size_t)h->Spad * 4, hipMemcpyHostToDevice));
+    HIPCHECK(hipMemcpy(h->d_wt_dep, h->wt.dep.data(), (size_t)h->Spad * 8, hipMemcpyHostToDevice));
+    HIPCHECK(hipMemset(h->d_rest, 0, E * h->Spad * h->tsz));
+    if (!levels.empty()) HIPCHECK(hipMemcpy(h->d_levels, levels.data(), levels.size() * 8, hipMemcpyHostToDevice));
+    HIPCHECK(hipMemset(h->d_exec, 0, E * 4));
     // large dynamic LDS (up to the CU's 160 KiB) for the stepper kernels: which variant, which layout (plan_layouts)
     {
         hipDeviceProp_t dp;
@@ -529,7 +238,7 @@ extern "C" int clothhip_create(const ClothParams *params, int32_t n_envs, int32_
             if (occ >= h->lean_r) break;
             plan_layouts(h, cus, std::max(2, occ));
         }
-        if (h->lay_std.lds_bytes > 160 * 1024) { free_handle(h); return fail(CLOTHHIP_EINVAL, "n_side %d needs %d B of LDS (> 160 KiB)", h->N, h->lay_std.lds_bytes); }
+        if (h->lay_std.lds_bytes > 160 * 1024) return fail(CLOTHHIP_EINVAL, "n_side %d needs %d B of LDS (> 160 KiB)", h->N, h->lay_std.lds_bytes);
         // every kernel the handle may launch: the generic build of the standard layout, of the lean one (which of the two runs is decided
         // per launch) and, where one exists for a layout, its grid-specialised build (tier 2 at 25x25, the LEAN builds). The attribute is
         // per kernel function and process-global: always the CU's full 160 KiB, so that a later handle with a smaller footprint can never
@@ -539,30 +248,25 @@ extern "C" int clothhip_create(const ClothParams *params, int32_t n_envs, int32_
             const int ns = spec_ns(h, *L, false);
             for (int f = 0; f < 3; f++) {
                 const void *fn = find_stepper(L->v, 0, f);
-                if (!fn) { free_handle(h); return fail(CLOTHHIP_EINVAL, "no %sstepper variant for n_side %d", L == &h->lay_lean ? "lean " : "", h->N); }
-                HC(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                if (ns) HC(hipFuncSetAttribute(find_stepper(L->v, ns, f), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                if (!fn) return fail(CLOTHHIP_EINVAL, "no %sstepper variant for n_side %d", L == &h->lay_lean ? "lean " : "", h->N);
+                HIPCHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                if (ns) HIPCHECK(hipFuncSetAttribute(find_stepper(L->v, ns, f), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             }
         }
     }
-#undef HC
     // initial state: flat tier-1 grid for every env, shared rest table
     std::vector<double> pos((size_t)h->P * 3), rest(h->S);
-    int rc = clothhip_init_grid(params, 1, 0, nullptr, pos.data(), rest.data());
-    if (rc) { free_handle(h); return rc; }
+    if ((rc = clothhip_init_grid(params, 1, 0, nullptr, pos.data(), rest.data()))) return rc;
     h->flat_rest = rest;
     std::vector<double> all((size_t)h->E * h->P * 3);
     for (int e = 0; e < h->E; e++) memcpy(all.data() + (size_t)e * h->P * 3, pos.data(), sizeof(double) * h->P * 3);
     std::vector<uint8_t> pin((size_t)h->E * h->P, 0);
-    rc = clothhip_set_state(h, 0, h->E, all.data(), all.data(), pin.data(), rest.data(), CLOTHHIP_REST_SHARED);
-    if (rc) { free_handle(h); return rc; }
+    if ((rc = clothhip_set_state(h, 0, h->E, all.data(), all.data(), pin.data(), rest.data(), CLOTHHIP_REST_SHARED))) return rc;
     // the flat grid and its rest table stay on the device for clothhip_reset_flat / the in-kernel episode reset
     if (hipMemcpy(h->d_flat, h->d_pos, (size_t)3 * h->Ppad * h->tsz, hipMemcpyDeviceToDevice) != hipSuccess ||
-        hipMemcpy(h->d_flat_rest, h->d_rest, (size_t)h->Spad * h->tsz, hipMemcpyDeviceToDevice) != hipSuccess) {
-        free_handle(h);
+        hipMemcpy(h->d_flat_rest, h->d_rest, (size_t)h->Spad * h->tsz, hipMemcpyDeviceToDevice) != hipSuccess)
         return fail(CLOTHHIP_EHIP, "copying the flat-grid template failed");
-    }
-    *out = h;
+    *out = owner.release();
     return 0;
 }
 
@@ -570,7 +274,7 @@ extern "C" int clothhip_destroy(clothhip_handle *h) {
     if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    free_handle(h);
+    delete h;
     return 0;
 }
 
@@ -593,6 +297,9 @@ static int drop_in_flight_range(clothhip_handle *h, int env0, int n) {
     if (h->d_resume && n > 0) HIPCHECK(hipMemsetAsync(h->d_resume + env0, 0, (size_t)n * sizeof(EpResume), h->stream));
     return 0;
 }
+
+// no call that touches what an episode launch reads or writes between clothhip_run_actions_begin and _end
+static int check_idle(const clothhip_handle *h) { return h->f_pending ? fail(CLOTHHIP_ESTATE, "clothhip_run_actions_begin still in flight: call clothhip_run_actions_end first") : 0; }
 
 static int check_range(const clothhip_handle *h, int env0, int n) {
     if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
@@ -816,6 +523,7 @@ template <typename T> static StepArgs<T> make_args(clothhip_handle *h, const Clo
 // The one path by which a handle's materials change (clothhip_set_material, clothhip_fork): `next` becomes the host vector, n_mixed follows, and
 // while any env differs from the handle's parameters the device's table is (created and) rebuilt whole -- unless `upload` is false: the
 // caller has the device copy the records it changes (a fork between two handles whose tables are both live).
+static size_t mat_record_bytes(const clothhip_handle *h) { return h->precision == CLOTHHIP_F64 ? sizeof(DevConsts<double>) : sizeof(DevConsts<float>); }
 static int apply_materials(clothhip_handle *h, std::vector<ClothMaterial> &next, bool upload) {
     const ClothMaterial own = material_of(h->prm);
     int mixed = 0;
@@ -823,11 +531,8 @@ static int apply_materials(clothhip_handle *h, std::vector<ClothMaterial> &next,
     HIPCHECK(hipSetDevice(h->device));
     if (mixed && upload) {
         // the device's table, rebuilt whole: every env's record by the ONE derivation (make_consts), in the handle's precision
-        const size_t bytes = (size_t)h->E * (h->precision == CLOTHHIP_F64 ? sizeof(DevConsts<double>) : sizeof(DevConsts<float>));
-        if (!h->d_mat) {
-            const hipError_t err = hipMalloc(&h->d_mat, bytes);
-            if (err != hipSuccess) { h->d_mat = nullptr; return fail(err == hipErrorOutOfMemory ? CLOTHHIP_ENOMEM : CLOTHHIP_EHIP, "hipMalloc of the material table failed: %s", hipGetErrorString(err)); }
-        }
+        const size_t bytes = (size_t)h->E * mat_record_bytes(h);
+        if (int rc = h->d_mat.reserve(bytes)) return rc;
         std::vector<unsigned char> buf(bytes);
         by_precision(h, [&](auto t) {
             using T = decltype(t);
@@ -844,7 +549,7 @@ static int apply_materials(clothhip_handle *h, std::vector<ClothMaterial> &next,
 
 extern "C" int clothhip_set_material(clothhip_handle *h, int32_t env0, int32_t n, const ClothMaterial *m) {
     if (int rc = check_range(h, env0, n)) return rc;
-    if (h->f_pending) return fail(CLOTHHIP_ESTATE, "clothhip_run_actions_begin still in flight: call clothhip_run_actions_end first");
+    if (int rc = check_idle(h)) return rc;
     const ClothMaterial own = material_of(h->prm);
     for (int e = 0; m && e < n; e++)
         if (int rc = check_material(h->prm, m[e], e)) return rc;
@@ -876,7 +581,8 @@ extern "C" int clothhip_fork(clothhip_handle *dst, const int32_t *dst_env, cloth
     if (dst->device != src->device) return fail(CLOTHHIP_EINVAL, "fork across devices (%d <- %d)", dst->device, src->device);
     if (dst->precision != src->precision) return fail(CLOTHHIP_EINVAL, "fork between handles of different precision");
     if (dst->N != src->N) return fail(CLOTHHIP_EINVAL, "fork between grids of %d and %d points a side", dst->N, src->N);
-    if (dst->f_pending || src->f_pending) return fail(CLOTHHIP_ESTATE, "clothhip_run_actions_begin still in flight: call clothhip_run_actions_end first");
+    if (int rc = check_idle(dst)) return rc;
+    if (int rc = check_idle(src)) return rc;
     {
         std::vector<uint8_t> seen((size_t)dst->E, 0);
         for (int j = 0; j < n; j++) {
@@ -902,14 +608,10 @@ extern "C" int clothhip_fork(clothhip_handle *dst, const int32_t *dst_env, cloth
         }
     }
     HIPCHECK(hipSetDevice(dst->device));
-    if (dst->cap_fork_idx < (size_t)2 * n * 4 || !dst->h_fork_idx) {
-        if (dst->h_fork_idx) HIPCHECK(hipHostFree(dst->h_fork_idx));
-        dst->h_fork_idx = nullptr;
-        if (int rc = grow((void **)&dst->d_fork_idx, &dst->cap_fork_idx, (size_t)2 * n * 4)) return rc;
-        HIPCHECK(hipHostMalloc((void **)&dst->h_fork_idx, dst->cap_fork_idx, hipHostMallocDefault));
-    }
+    if (int rc = dst->d_fork_idx.reserve((size_t)2 * n * 4)) return rc;
+    if (int rc = dst->h_fork_idx.reserve((size_t)2 * n * 4)) return rc;
     if (dst->stream != src->stream) {                  // the copy reads what the source's stream has enqueued so far
-        if (!dst->ev_fork) HIPCHECK(hipEventCreateWithFlags(&dst->ev_fork, hipEventDisableTiming));
+        if (!dst->ev_fork) HIPCHECK(hipEventCreateWithFlags(&dst->ev_fork.v, hipEventDisableTiming));
         HIPCHECK(hipEventRecord(dst->ev_fork, src->stream));
         HIPCHECK(hipStreamWaitEvent(dst->stream, dst->ev_fork, 0));
     }
@@ -947,7 +649,7 @@ extern "C" int clothhip_fork(clothhip_handle *dst, const int32_t *dst_env, cloth
     a.dst_env = dst->d_fork_idx; a.src_env = dst->d_fork_idx + n;
     a.pos_bytes = (size_t)3 * dst->Ppad * dst->tsz; a.cnt_bytes = (size_t)dst->Ppad;
     a.rest_bytes = rest_bytes; a.rest_src_stride = (size_t)src->rest_stride * src->tsz;
-    a.mat_bytes = dst->precision == CLOTHHIP_F64 ? sizeof(DevConsts<double>) : sizeof(DevConsts<float>);
+    a.mat_bytes = mat_record_bytes(dst);
     hipLaunchKernelGGL(k_fork, dim3(n), dim3(256), 0, dst->stream, a);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(dst->stream));
@@ -956,7 +658,7 @@ extern "C" int clothhip_fork(clothhip_handle *dst, const int32_t *dst_env, cloth
 
 extern "C" int clothhip_in_flight(clothhip_handle *h, uint8_t *parked) {
     if (!h || !parked) return fail(CLOTHHIP_EINVAL, "NULL argument");
-    if (h->f_pending) return fail(CLOTHHIP_ESTATE, "clothhip_run_actions_begin still in flight: call clothhip_run_actions_end first");
+    if (int rc = check_idle(h)) return rc;
     HIPCHECK(hipSetDevice(h->device));
     HIPCHECK(hipStreamSynchronize(h->stream));
     std::vector<int32_t> v((size_t)h->E);
@@ -1182,7 +884,6 @@ extern "C" int clothhip_run(clothhip_handle *h, const ClothSchedule *sched, int3
     return clothhip_sync(h, executed);
 }
 
-
 // ---- whole episodes on the device ---------------------------------------------------------------------------------
 template <typename T> static void fill_fused(clothhip_handle *h, FusedArgs<T> &f, const ClothEpisodeParams *ep, int T_, int policy,
                                              const double *d_actions, bool have_parg, bool have_scripts, bool have_resets, bool have_obs,
@@ -1211,29 +912,14 @@ template <typename T> static void fill_fused(clothhip_handle *h, FusedArgs<T> &f
     f.ep = *ep;
 }
 
-static int grow(void **p, size_t *cap, size_t need) {
-    if (*cap >= need) return 0;
-    if (*p) HIPCHECK(hipFree(*p));
-    *p = nullptr; *cap = 0;
-    HIPCHECK(hipMalloc(p, need));
-    *cap = need;
-    return 0;
-}
-
-// Every layout the handle may run (the standard one always; the LEAN one while its palette holds) was sized in clothhip_create
-extern "C" int clothhip_fused_supported(const clothhip_handle *h) {
-    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
-    const bool std_ok = h->lay_std.scratch_have >= h->lay_std.scratch_need;
-    const bool lean_ok = !h->lean || h->lay_lean.scratch_have >= h->lay_lean.scratch_need;
-    return std_ok && lean_ok ? 1 : 0;
-}
+extern "C" int clothhip_fused_supported(const clothhip_handle *h) { return h ? (fused_supported(*h) ? 1 : 0) : fail(CLOTHHIP_EINVAL, "handle is NULL"); }
 
 extern "C" int clothhip_selftest_layout(const ClothParams *p, int32_t precision, int32_t n_envs, int32_t n_cus, int32_t *out, int32_t capacity) {
     if (int rc = check_params(p)) return rc;
     if (!out || capacity < 24) return fail(CLOTHHIP_EINVAL, "out needs 24 entries");
     if (precision != CLOTHHIP_F64 && precision != CLOTHHIP_F32) return fail(CLOTHHIP_EINVAL, "precision must be 0 (f64) or 1 (f32)");
     if (n_envs < 1 || n_cus < 1) return fail(CLOTHHIP_EINVAL, "n_envs and n_cus must be >= 1");
-    clothhip_handle h;                                       // host fields only: nothing here touches a device
+    HostPlan h;                                              // host fields only: nothing here touches a device
     init_host_fields(&h, *p, n_envs, precision);
     plan_layouts(&h, n_cus);
     auto put = [&](int o, const Layout &L) {
@@ -1244,7 +930,7 @@ extern "C" int clothhip_selftest_layout(const ClothParams *p, int32_t precision,
     put(0, h.lay_std);
     out[10] = h.lean ? 1 : 0; out[11] = h.lean_r;
     put(12, h.lay_lean);
-    out[22] = clothhip_fused_supported(&h); out[23] = h.lay_std.lds_bytes <= 160 * 1024 ? 1 : 0;
+    out[22] = fused_supported(h) ? 1 : 0; out[23] = h.lay_std.lds_bytes <= 160 * 1024 ? 1 : 0;
     return 0;
 }
 
@@ -1286,40 +972,38 @@ extern "C" int clothhip_run_actions_begin(clothhip_handle *h, const ClothEpisode
         return fail(CLOTHHIP_ESTATE, "n_side %d: the in-kernel metrics need %d B of LDS scratch, this variant has %d", h->N, h->lay().scratch_need, h->lay().scratch_have);
     HIPCHECK(hipStreamSynchronize(h->stream));
     const size_t E = h->E, nrec = (size_t)T_ * E;
-    if (!h->d_fz) {
-        HIPCHECK(hipMalloc(&h->d_fz, 1024));
-        HIPCHECK(hipMalloc(&h->d_fsteps, E * 4));
-        HIPCHECK(hipMalloc(&h->d_fdone, E));
-        HIPCHECK(hipMalloc(&h->d_fticks, E * 64));
-        HIPCHECK(hipMalloc(&h->d_fsum, E * 32));
-    }
+    if (int rc = h->d_fz.reserve(1024)) return rc;
+    if (int rc = h->d_fsteps.reserve(E * 4)) return rc;
+    if (int rc = h->d_fdone.reserve(E)) return rc;
+    if (int rc = h->d_fticks.reserve(E * 64)) return rc;
+    if (int rc = h->d_fsum.reserve(E * 32)) return rc;
     HIPCHECK(hipMemsetAsync(h->d_fticks, 0, E * 64, h->stream));
-    if (int rc = grow(&h->d_frec, &h->cap_frec, nrec * sizeof(ClothStepRecord))) return rc;
+    if (int rc = h->d_frec.reserve(nrec * sizeof(ClothStepRecord))) return rc;
     const size_t nscr = E * (size_t)(n_scripts > 0 ? n_scripts : 1);
-    if (int rc = grow(&h->d_fscr, &h->cap_fscr, nscr * sizeof(ClothResetScript))) return rc;
-    if (int rc = grow(&h->d_frst, &h->cap_frst, nscr * sizeof(ClothResetRecord))) return rc;
+    if (int rc = h->d_fscr.reserve(nscr * sizeof(ClothResetScript))) return rc;
+    if (int rc = h->d_frst.reserve(nscr * sizeof(ClothResetRecord))) return rc;
     const double *d_actions = nullptr;
     if (policy == CLOTHHIP_POLICY_TABLE) {
         if (actions_on_device) d_actions = actions;
         else {
-            if (int rc = grow(&h->d_fact, &h->cap_fact, nrec * 4 * 8)) return rc;
+            if (int rc = h->d_fact.reserve(nrec * 4 * 8)) return rc;
             HIPCHECK(hipMemcpyAsync(h->d_fact, actions, nrec * 4 * 8, hipMemcpyHostToDevice, h->stream));
             d_actions = (const double *)h->d_fact;
         }
     }
-    if (obs) if (int rc = grow(&h->d_fobs, &h->cap_fobs, nrec * 3 * h->P * 4)) return rc;
+    if (obs) if (int rc = h->d_fobs.reserve(nrec * 3 * h->P * 4)) return rc;
     if ((reset_obs || resets) && !scripts && !rng_states) return fail(CLOTHHIP_EINVAL, "reset outputs without a reset source");
     if (reset_obs) {
-        if (int rc = grow(&h->d_frobs, &h->cap_frobs, nscr * 3 * h->P * 4)) return rc;
+        if (int rc = h->d_frobs.reserve(nscr * 3 * h->P * 4)) return rc;
         HIPCHECK(hipMemsetAsync(h->d_frobs, 0, nscr * 3 * h->P * 4, h->stream));
     }
     if (rng_states) {
-        if (!h->d_fmt) HIPCHECK(hipMalloc(&h->d_fmt, E * MT_WORDS * 4));
+        if (int rc = h->d_fmt.reserve(E * MT_WORDS * 4)) return rc;
         HIPCHECK(hipMemcpyAsync(h->d_fmt, rng_states, E * MT_WORDS * 4, hipMemcpyHostToDevice, h->stream));
     }
     if (policy_arg) {
         const size_t nb = (policy == CLOTHHIP_POLICY_HIGHEST_POINT ? (size_t)(1 + T_) : (size_t)1) * E * 4;
-        if (int rc = grow((void **)&h->d_fparg, &h->cap_fparg, nb)) return rc;
+        if (int rc = h->d_fparg.reserve(nb)) return rc;
         HIPCHECK(hipMemcpyAsync(h->d_fparg, policy_arg, nb, hipMemcpyHostToDevice, h->stream));
     }
     if (scripts) HIPCHECK(hipMemcpyAsync(h->d_fscr, scripts, nscr * sizeof(ClothResetScript), hipMemcpyHostToDevice, h->stream));
@@ -1388,7 +1072,7 @@ extern "C" int clothhip_run_actions_summary(clothhip_handle *h, double *summary,
 extern "C" int clothhip_run_actions_op_ticks(clothhip_handle *h, uint64_t *ticks) {
     if (!h || !ticks) return fail(CLOTHHIP_EINVAL, "NULL argument");
     if (!h->d_fticks) return fail(CLOTHHIP_ESTATE, "no clothhip_run_actions launch yet");
-    if (h->f_pending) return fail(CLOTHHIP_ESTATE, "clothhip_run_actions_begin still in flight: call clothhip_run_actions_end first");
+    if (int rc = check_idle(h)) return rc;
     HIPCHECK(hipSetDevice(h->device));
     HIPCHECK(hipMemcpyAsync(ticks, h->d_fticks, (size_t)h->E * 64, hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(hipStreamSynchronize(h->stream));
@@ -1495,41 +1179,47 @@ extern "C" int clothhip_write_obs_f32_device(clothhip_handle *h, void *d_out) {
 }
 
 // ---- headless rendering ------------------------------------------------------------------------------------
-extern "C" int clothhip_render(clothhip_handle *h, const ClothRenderParams *p, const uint8_t *swap_sides, uint8_t *rgb, float *depth) {
+// the image-size and lens rules of both render entry points
+static int check_render_params(const clothhip_handle *h, const ClothRenderParams *p) {
     if (!h || !p) return fail(CLOTHHIP_EINVAL, "NULL argument");
     if (p->width < 1 || p->height < 1 || p->width > 4096 || p->height > 4096) return fail(CLOTHHIP_EINVAL, "image size outside [1, 4096]");
     if (!(p->lens_mm > 0) || !(p->sensor_mm > 0)) return fail(CLOTHHIP_EINVAL, "lens / sensor must be > 0");
-    if (!rgb && !depth) return 0;
-    HIPCHECK(hipSetDevice(h->device));
-    const size_t npx = (size_t)p->width * p->height, E = h->E;
-    unsigned long long *d_z = nullptr; uint8_t *d_rgb = nullptr, *d_sw = nullptr; float *d_dep = nullptr;
-    auto cleanup = [&]() { if (d_z) (void)hipFree(d_z); if (d_rgb) (void)hipFree(d_rgb); if (d_sw) (void)hipFree(d_sw); if (d_dep) (void)hipFree(d_dep); };
-#define RC(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { cleanup(); return fail(CLOTHHIP_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); } } while (0)
-    RC(hipMalloc(&d_z, E * npx * 8));
-    if (rgb) RC(hipMalloc(&d_rgb, E * npx * 3));
-    if (depth) RC(hipMalloc(&d_dep, E * npx * 4));
-    if (swap_sides) { RC(hipMalloc(&d_sw, E)); RC(hipMemcpyAsync(d_sw, swap_sides, E, hipMemcpyHostToDevice, h->stream)); }
-    RenderArgs a;
+    return 0;
+}
+// ... and their scene: grid, camera, colours, lamp
+static void fill_scene(RenderArgs &a, const clothhip_handle *h, const ClothRenderParams *p) {
     a.N = h->N; a.P = h->P; a.Ppad = h->Ppad; a.W = p->width; a.H = p->height; a.E = h->E;
     for (int k = 0; k < 9; k++) a.R[k] = p->world_to_cam[k];
     for (int k = 0; k < 3; k++) { a.cam[k] = p->cam_pos[k]; a.front[k] = p->front[k]; a.back[k] = p->back[k]; a.bg[k] = p->background[k]; a.light[k] = p->light_dir[k]; }
     a.fx = (p->lens_mm / p->sensor_mm) * (float)p->width; a.fy = a.fx;           // square pixels, horizontal sensor fit
     a.cx = 0.5f * (float)p->width; a.cy = 0.5f * (float)p->height;
     a.ambient = p->ambient; a.energy = p->energy;
+}
+
+extern "C" int clothhip_render(clothhip_handle *h, const ClothRenderParams *p, const uint8_t *swap_sides, uint8_t *rgb, float *depth) {
+    if (int rc = check_render_params(h, p)) return rc;
+    if (!rgb && !depth) return 0;
+    HIPCHECK(hipSetDevice(h->device));
+    const size_t npx = (size_t)p->width * p->height, E = h->E;
+    Buffer<unsigned long long> d_z; Buffer<uint8_t> d_rgb, d_sw; Buffer<float> d_dep;      // per call: a handle retains no image memory
+    if (int rc = d_z.reserve(E * npx * 8)) return rc;
+    if (rgb) if (int rc = d_rgb.reserve(E * npx * 3)) return rc;
+    if (depth) if (int rc = d_dep.reserve(E * npx * 4)) return rc;
+    if (swap_sides) { if (int rc = d_sw.reserve(E)) return rc; HIPCHECK(hipMemcpyAsync(d_sw, swap_sides, E, hipMemcpyHostToDevice, h->stream)); }
+    RenderArgs a;
+    fill_scene(a, h, p);
     a.swap = d_sw; a.zbuf = d_z; a.rgb = d_rgb; a.depth = d_dep;
     const int lds = 7 * h->Ppad * 4;
     if (int rc = by_precision(h, [&](auto t) {
             using T = decltype(t);
-            RC(hipFuncSetAttribute((const void *)k_render<T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            HIPCHECK(hipFuncSetAttribute((const void *)k_render<T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             hipLaunchKernelGGL(k_render<T>, dim3(h->E), dim3(256), lds, h->stream, (const T *)h->d_pos, a);
             return 0;
         })) return rc;
-    RC(hipGetLastError());
-    if (rgb) RC(hipMemcpyAsync(rgb, d_rgb, E * npx * 3, hipMemcpyDeviceToHost, h->stream));
-    if (depth) RC(hipMemcpyAsync(depth, d_dep, E * npx * 4, hipMemcpyDeviceToHost, h->stream));
-    RC(hipStreamSynchronize(h->stream));
-#undef RC
-    cleanup();
+    HIPCHECK(hipGetLastError());
+    if (rgb) HIPCHECK(hipMemcpyAsync(rgb, d_rgb, E * npx * 3, hipMemcpyDeviceToHost, h->stream));
+    if (depth) HIPCHECK(hipMemcpyAsync(depth, d_dep, E * npx * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
     return 0;
 }
 
@@ -1543,15 +1233,13 @@ static int render_obs_chunk(size_t npx) {
 
 extern "C" int clothhip_render_obs(clothhip_handle *h, const ClothRenderParams *p, int32_t source, const float *obs_host, int64_t n,
                                    const uint8_t *valid, const uint8_t *swap, int32_t format, uint8_t *out, void *d_out) {
-    if (!h || !p) return fail(CLOTHHIP_EINVAL, "NULL argument");
-    if (p->width < 1 || p->height < 1 || p->width > 4096 || p->height > 4096) return fail(CLOTHHIP_EINVAL, "image size outside [1, 4096]");
-    if (!(p->lens_mm > 0) || !(p->sensor_mm > 0)) return fail(CLOTHHIP_EINVAL, "lens / sensor must be > 0");
+    if (int rc = check_render_params(h, p)) return rc;
     if (format != CLOTHHIP_IMG_RGB && format != CLOTHHIP_IMG_DEPTH && format != CLOTHHIP_IMG_RGBD) return fail(CLOTHHIP_EINVAL, "unknown image format %d", format);
     if (source < CLOTHHIP_OBS_STATE || source > CLOTHHIP_OBS_HOST) return fail(CLOTHHIP_EINVAL, "unknown observation source %d", source);
     if (n < 0) return fail(CLOTHHIP_EINVAL, "n < 0");
     if (source == CLOTHHIP_OBS_HOST && !obs_host && n > 0) return fail(CLOTHHIP_EINVAL, "CLOTHHIP_OBS_HOST needs obs_host[n][3P]");
     if (source == CLOTHHIP_OBS_SLOTS || source == CLOTHHIP_OBS_RESETS) {
-        if (h->f_pending) return fail(CLOTHHIP_ESTATE, "clothhip_run_actions_begin still in flight: call clothhip_run_actions_end first");
+        if (int rc = check_idle(h)) return rc;
         if (h->f_T < 1) return fail(CLOTHHIP_ESTATE, "no clothhip_run_actions launch yet");
         if (source == CLOTHHIP_OBS_SLOTS && !h->f_obs) return fail(CLOTHHIP_ESTATE, "the last clothhip_run_actions launch was not given want_obs");
         if (source == CLOTHHIP_OBS_RESETS && !h->f_robs) return fail(CLOTHHIP_ESTATE, "the last clothhip_run_actions launch was not given want_reset_obs");
@@ -1566,18 +1254,13 @@ extern "C" int clothhip_render_obs(clothhip_handle *h, const ClothRenderParams *
     const size_t npx = (size_t)p->width * p->height, C = format == CLOTHHIP_IMG_RGBD ? 4 : 3, img_bytes = npx * C;
     const size_t chunk = (size_t)render_obs_chunk(npx), cmax = (size_t)n < chunk ? (size_t)n : chunk;
     const bool need_depth = format != CLOTHHIP_IMG_RGB, have_flags = valid || swap;
-    if (!d_out) if (int rc = grow(&h->d_ro_img, &h->cap_ro_img, cmax * img_bytes)) return rc;
-    if (need_depth) if (int rc = grow(&h->d_ro_depth, &h->cap_ro_depth, cmax * npx * 4)) return rc;
-    if (source == CLOTHHIP_OBS_HOST) if (int rc = grow(&h->d_ro_src, &h->cap_ro_src, cmax * 3 * h->P * 4)) return rc;
-    if (have_flags) if (int rc = grow(&h->d_ro_flags, &h->cap_ro_flags, 2 * chunk)) return rc;
+    if (!d_out) if (int rc = h->d_ro_img.reserve(cmax * img_bytes)) return rc;
+    if (need_depth) if (int rc = h->d_ro_depth.reserve(cmax * npx * 4)) return rc;
+    if (source == CLOTHHIP_OBS_HOST) if (int rc = h->d_ro_src.reserve(cmax * 3 * h->P * 4)) return rc;
+    if (have_flags) if (int rc = h->d_ro_flags.reserve(2 * chunk)) return rc;
     RenderObsArgs a;
     memset(&a, 0, sizeof(a));
-    a.s.N = h->N; a.s.P = h->P; a.s.Ppad = h->Ppad; a.s.W = p->width; a.s.H = p->height; a.s.E = h->E;
-    for (int k = 0; k < 9; k++) a.s.R[k] = p->world_to_cam[k];
-    for (int k = 0; k < 3; k++) { a.s.cam[k] = p->cam_pos[k]; a.s.front[k] = p->front[k]; a.s.back[k] = p->back[k]; a.s.bg[k] = p->background[k]; a.s.light[k] = p->light_dir[k]; }
-    a.s.fx = (p->lens_mm / p->sensor_mm) * (float)p->width; a.s.fy = a.s.fx;     // square pixels, horizontal sensor fit
-    a.s.cx = 0.5f * (float)p->width; a.s.cy = 0.5f * (float)p->height;
-    a.s.ambient = p->ambient; a.s.energy = p->energy;
+    fill_scene(a.s, h, p);
     a.rows = plan.rows; a.bands = plan.bands; a.format = format; a.C = (int)C;
     const bool soa = source == CLOTHHIP_OBS_STATE;
     a.src_stride = soa ? 3LL * h->Ppad : 3LL * h->P;
@@ -1645,7 +1328,7 @@ extern "C" int clothhip_device_alloc(clothhip_handle *h, uint64_t nbytes, void *
     if (!h || !d_out || nbytes == 0) return fail(CLOTHHIP_EINVAL, "bad argument");
     HIPCHECK(hipSetDevice(h->device));
     hipError_t err = hipMalloc(d_out, (size_t)nbytes);
-    if (err != hipSuccess) return fail(err == hipErrorOutOfMemory ? CLOTHHIP_ENOMEM : CLOTHHIP_EHIP, "hipMalloc(%llu) failed: %s",
+    if (err != hipSuccess) return fail(hip_status(err), "hipMalloc(%llu) failed: %s",
                                        (unsigned long long)nbytes, hipGetErrorString(err));
     return 0;
 }
@@ -1739,15 +1422,14 @@ extern "C" int clothhip_selftest_arith(int32_t device, int32_t op, const double 
     if (!a || !out || n <= 0) return fail(CLOTHHIP_EINVAL, "bad argument");
     if (clothhip_device_count() <= 0) return fail(CLOTHHIP_ENODEV, "no HIP device visible");
     HIPCHECK(hipSetDevice(device));
-    double *da = nullptr, *db = nullptr, *dout = nullptr;
-    HIPCHECK(hipMalloc(&da, n * 8));
-    HIPCHECK(hipMalloc(&dout, n * 8));
-    if (b) { HIPCHECK(hipMalloc(&db, n * 8)); HIPCHECK(hipMemcpy(db, b, n * 8, hipMemcpyHostToDevice)); }
+    Buffer<double> da, db, dout;
+    if (int rc = da.reserve(n * 8)) return rc;
+    if (int rc = dout.reserve(n * 8)) return rc;
+    if (b) { if (int rc = db.reserve(n * 8)) return rc; HIPCHECK(hipMemcpy(db, b, n * 8, hipMemcpyHostToDevice)); }
     HIPCHECK(hipMemcpy(da, a, n * 8, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_selftest, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, op, da, db, dout, (long long)n);
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipDeviceSynchronize());
     HIPCHECK(hipMemcpy(out, dout, n * 8, hipMemcpyDeviceToHost));
-    (void)hipFree(da); (void)hipFree(dout); if (db) (void)hipFree(db);
     return 0;
 }

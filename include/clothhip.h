@@ -35,7 +35,9 @@ enum {
     CLOTHHIP_EINVAL = -1,   /* bad argument (ValueError / AssertionError in the reference, cloth.pyx:85,91,132) */
     CLOTHHIP_ENODEV = -2,   /* no usable HIP device */
     CLOTHHIP_EHIP = -3,     /* a HIP runtime call failed; message has the hipError string */
-    CLOTHHIP_ENOMEM = -4,
+    CLOTHHIP_ENOMEM = -4,   /* out of host or device memory: any HIP call that reports hipErrorOutOfMemory, whichever buffer ran out -- the fixed
+                               ones of clothhip_create and clothhip_set_material as well as the ones a call sizes by its arguments (episode
+                               launches, render, fork) */
     CLOTHHIP_ESTATE = -5    /* call not valid in the handle's current state */
 };
 

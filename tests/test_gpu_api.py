@@ -124,3 +124,75 @@ def test_error_paths():
     b.close()
     with pytest.raises(ValueError):
         ClothBatch(base_cfg("tier1", 1), n_envs=0)
+
+
+SMALL_CALLS = dict(T=2, R=1, px=8, fork=([0, 1], [3, 2]))            # (src envs, dst envs)
+LARGE_CALLS = dict(T=6, R=2, px=16, fork=([0, 1, 2, 3], [0, 1, 2, 3]))
+
+
+def _short_env(E, prec, n_side):
+    """A vector env whose actions and resets are short (the buffers' sizes do not depend on how long an action runs)."""
+    import bench
+    from gym_cloth_amd.envs import ClothVecEnv
+    cfg = bench.bench_cfg(n_side, 0.02)
+    cfg["env"].update(iters_up_rest=10, iters_pull_max=60, iters_grip_rest=20, iters_rest=40)
+    v = ClothVecEnv(cfg, n_envs=E, precision=prec, consume_domrand_draws=False)
+    for e in range(E):
+        v.np_randoms[e] = np.random.RandomState(1000 + e)
+    return v
+
+
+def _calls(va, vb, c, E):
+    """Every call that sizes a buffer by its arguments, on handle va.batch (forks come from vb.batch): what the calls returned."""
+    a, T, R = va.batch, c["T"], c["R"]
+    a.fork_from(vb.batch, c["fork"][0], c["fork"][1])
+    acts = np.stack([np.random.RandomState(2000 + e).uniform(-1, 1, size=(T, 4)) for e in range(E)], axis=1)
+    done = np.array([1, 1, 0, 0], dtype=np.uint8)                    # two envs start with an in-kernel reset
+    rec, rst, obs, robs = a.run_actions(va._episode_params(), T, np.zeros(E, dtype=np.int32), done, actions=acts,
+                                        scripts=va._prepare_scripts(R), want_obs=True)
+    assert (rec["reset_before"][0, :2] == 1).all() and robs[:2, 0].any()
+    ran = rec["ran"] == 1
+    obs = np.where(ran[..., None], obs, np.float32(0))               # (a slot that did not run leaves its observation unwritten)
+    kw = dict(width=c["px"], height=c["px"])
+    flags = (np.arange(T * E) % 3 != 0) & ran.reshape(-1)
+    out = {"rec": rec, "rst": rst, "obs": obs, "robs": robs,
+           "img_slots": a.render_obs("slots", valid=ran.reshape(-1), fmt="rgbd", **kw), "img_resets": a.render_obs("resets", fmt="depth", **kw),
+           "img_host": a.render_obs("host", obs=obs.reshape(T * E, -1), valid=flags, swap_sides=np.arange(T * E) % 2, fmt="rgb", **kw)}
+    assert out["img_slots"].shape == (T * E, c["px"], c["px"], 4) and out["img_slots"].any() and out["img_host"].any()
+    out["pos"], out["prev"], out["pin"] = a.get_state()
+    out["mat"], out["tear"], out["rest"] = a.get_material(), a.tear, a.get_rest()
+    return out
+
+
+def _round(prec, n_side, small_first):
+    E = 4
+    va, vb = _short_env(E, prec, n_side), _short_env(E, prec, n_side)
+    pos = vb.batch.positions()
+    pos[..., 2] += np.random.RandomState(7).uniform(0.0, 0.01, size=pos.shape[:2])   # the source of the forks: four different cloths
+    vb.batch.set_state(pos, pos)
+    m = vb.batch.get_material(2, 1); m["ks"] *= 0.5; m["damping"] *= 1.5
+    vb.batch.set_material(m, env0=2)                                                  # ... one of another fabric
+    if small_first:
+        _calls(va, vb, SMALL_CALLS, E)
+        m = va.batch.get_material(1, 1); m["density"] *= 2.0
+        va.batch.set_material(m, env0=1)
+    out = _calls(va, vb, LARGE_CALLS, E)
+    va.close(); vb.close()
+    return out
+
+
+@pytest.mark.parametrize("prec,n_side", [("f32", 25), ("f64", 9)])
+def test_buffers_regrow_and_handles_recycle(prec, n_side):
+    """The staging of the episode launches, of render_obs and of the fork is sized by the call: small calls first (T = 2, one reset
+    script, 8x8 pixels, a fork of 2 envs, a material on one env), then larger ones on the same handle (T = 6, two scripts, 16x16
+    pixels, a fork of all 4 envs from a second handle) make every one of these buffers regrow. The records, observations,
+    images and states of the larger calls equal, byte for byte, those of a fresh handle that only ever ran the larger calls;
+    and closing both handles and running the whole sequence on new ones, five more times in one process, gives the same again."""
+    fresh = _round(prec, n_side, small_first=False)
+    first = _round(prec, n_side, small_first=True)
+    assert fresh["rec"]["executed"].sum() > 0 and (fresh["mat"]["ks"][2] != fresh["mat"]["ks"][0])
+    rounds = [first] + [_round(prec, n_side, small_first=True) for _ in range(5)]
+    for r in rounds:
+        assert set(r) == set(fresh)
+        for k in fresh:
+            assert fresh[k].dtype == r[k].dtype and fresh[k].tobytes() == r[k].tobytes(), k
