@@ -77,7 +77,8 @@ IMG_FORMATS = {'rgb': IMG_RGB, 'depth': IMG_DEPTH, 'rgbd': IMG_RGBD}
 OBS_STATE, OBS_SLOTS, OBS_RESETS, OBS_HOST = 0, 1, 2, 3                 # ... and sources
 OBS_SOURCES = {'state': OBS_STATE, 'slots': OBS_SLOTS, 'resets': OBS_RESETS, 'host': OBS_HOST}
 
-POLICY_TABLE, POLICY_ORACLE_CORNER, POLICY_HIGHEST_POINT = 0, 1, 2
+POLICY_TABLE, POLICY_ORACLE_CORNER, POLICY_HIGHEST_POINT, POLICY_MLP = 0, 1, 2, 3
+MLP_MAX_LAYERS, MLP_MAX_WIDTH = 4, 256   # clothhip_set_policy_mlp (csrc/cloth_policy_mlp.hpp)
 MT_WORDS = 626                      # per-env RandomState image: key[624], pos, pad (csrc/cloth_rng.hpp)
 
 RESET_PULL_DTYPE = np.dtype([("point", "<i4"), ("need_coverage", "<i4"), ("x", "<f8"), ("y", "<f8"), ("dx", "<f8"),
@@ -132,6 +133,8 @@ SYMBOLS = [
     ("clothhip_run_actions_summary", C.c_int, [_vp, _dp, C.POINTER(_vp)]),
     ("clothhip_run_actions", C.c_int, [_vp, C.POINTER(ClothEpisodeParams), C.c_int32, C.c_int32, _vp, C.c_int32, _i32p, _vp,
                                        C.c_int32, _i32p, _u8p, _vp, _vp, _vp, _vp, C.c_double]),
+    ("clothhip_set_policy_mlp", C.c_int, [_vp, C.c_int32, _i32p, C.POINTER(C.c_float), C.c_size_t]),
+    ("clothhip_policy_eval", C.c_int, [_vp, C.POINTER(C.c_float), C.c_int64, _dp]),
     ("clothhip_update", C.c_int, [_vp, C.c_int32, _dp]),
     ("clothhip_metrics", C.c_int, [_vp, _dp, _dp, _u8p, _u8p]),
     ("clothhip_metrics_ex", C.c_int, [_vp, _dp, _dp, _u8p, _u8p, _i32p]),

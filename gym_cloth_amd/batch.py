@@ -351,7 +351,7 @@ class ClothBatch(object):
         pol = _lib.POLICY_TABLE if policy is None else int(policy)
         on_dev = 0
         ap = None
-        if pol == _lib.POLICY_TABLE:
+        if pol == _lib.POLICY_TABLE or (pol == _lib.POLICY_MLP and (actions is not None or actions_device_ptr is not None)):
             if actions_device_ptr is not None:
                 ap, on_dev = C.c_void_p(int(actions_device_ptr)), 1
             else:
@@ -427,6 +427,32 @@ class ClothBatch(object):
         """clothhip_run_actions: `n_actions` whole ClothEnv.step calls per env in one launch (begin + end)."""
         self.run_actions_begin(*a, **k)
         return self.run_actions_end()
+
+    def set_policy_mlp(self, layers):
+        """The handle's policy network (clothhip_set_policy_mlp): `layers` is a list of (W, b) with W [out, in] (torch.nn.Linear.weight's
+        layout) and b [out], ReLU between them, the first `in` = 3 P, the last `out` = 4; None or [] clears it. The values are
+        uploaded as float32; every env of the batch evaluates the same network. ValueError for shapes the library refuses."""
+        if not layers:
+            check(self._L.clothhip_set_policy_mlp(self._h, 0, None, None, 0))
+            return
+        from .policies import pack_mlp
+        widths, blob = pack_mlp(layers)
+        check(self._L.clothhip_set_policy_mlp(self._h, len(widths) - 1, _lib.i32p(widths), blob.ctypes.data_as(C.POINTER(C.c_float)), blob.size))
+
+    def policy_eval(self, obs=None):
+        """The handle's network on float32 '1d' observations obs [n, 3P], or with obs=None on every env's present state: float64
+        [n, 4], the network's output before noise and clipping, computed by the device function the episode launch runs
+        (clothhip_policy_eval) -- the same bits."""
+        if obs is None:
+            n, ptr = self.E, None
+        else:
+            obs = np.ascontiguousarray(obs, dtype=np.float32)
+            if obs.ndim != 2 or obs.shape[1] != 3 * self.P:
+                raise ValueError("obs must have shape (n, %d)" % (3 * self.P))
+            n, ptr = obs.shape[0], obs.ctypes.data_as(C.POINTER(C.c_float))
+        out = np.zeros((n, 4), dtype=np.float64)
+        check(self._L.clothhip_policy_eval(self._h, ptr, n, _lib.dp(out)))
+        return out
 
     def update(self, n=1, delta=None):
         """n x Cloth.update() (cloth.pyx:169), each preceded by Gripper.adjust(*delta) if delta is given."""

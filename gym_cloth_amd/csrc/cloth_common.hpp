@@ -8,6 +8,7 @@
 #include "cloth_rng.hpp"
 #include "cloth_tables.hpp"
 #include "stepper_traits.hpp"
+#include "cloth_policy_mlp.hpp"
 
 namespace clothhip {
 
@@ -60,6 +61,7 @@ template <typename T> struct FusedArgs {
     uint64_t budget_ticks;            // 0 = none; else no new action / reset starts once the launch has run this many 100 MHz ticks
     double two_thickness, half_thickness;
     ClothEpisodeParams ep;
+    MlpDesc mlp;                      // CLOTHHIP_POLICY_MLP: the handle's network (cloth_policy_mlp.hpp); `actions` is then the optional noise table
 };
 
 // episode state of one cloth between the operations of the fused loop: kept in LDS, not in registers, so that nothing of it

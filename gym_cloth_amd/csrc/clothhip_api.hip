@@ -77,6 +77,10 @@ struct clothhip_handle : HostPlan {
     std::vector<unsigned char> shared_rest;
     Buffer<int32_t> d_fork_idx;
     PinnedBuffer<int32_t> h_fork_idx;   // (pinned staging, so that the upload is a plain DMA)
+    // clothhip_set_policy_mlp: the handle's network (n_layers 0: none; mlp.params = d_mlp) and clothhip_policy_eval's scratch for ONE chunk of rows
+    MlpDesc mlp = {};
+    Buffer<float> d_mlp, d_pe_rows;
+    Buffer<double> d_pe_out;
 };
 
 // f(float{}) or f(double{}) by the handle's precision: a launch that exists in both precisions is written once, as a generic lambda
@@ -910,6 +914,7 @@ template <typename T> static void fill_fused(clothhip_handle *h, FusedArgs<T> &f
     f.mt = have_mt ? h->d_fmt : nullptr; f.rng_tier = rng_tier; f.domrand_words = domrand_words;
     f.two_thickness = 2 * h->prm.thickness; f.half_thickness = h->prm.thickness / 2.0;
     f.ep = *ep;
+    f.mlp = h->mlp;
 }
 
 extern "C" int clothhip_fused_supported(const clothhip_handle *h) { return h ? (fused_supported(*h) ? 1 : 0) : fail(CLOTHHIP_EINVAL, "handle is NULL"); }
@@ -944,8 +949,11 @@ extern "C" int clothhip_run_actions_begin(clothhip_handle *h, const ClothEpisode
     if (h->f_pending) return fail(CLOTHHIP_ESTATE, "a clothhip_run_actions_begin is already in flight");
     const bool resets = want_resets != 0, obs = want_obs != 0, reset_obs = want_reset_obs != 0;
     if (T_ < 1 || T_ > 4096) return fail(CLOTHHIP_EINVAL, "T must be in [1, 4096]");
-    if (policy != CLOTHHIP_POLICY_TABLE && policy != CLOTHHIP_POLICY_ORACLE_CORNER && policy != CLOTHHIP_POLICY_HIGHEST_POINT)
+    if (policy != CLOTHHIP_POLICY_TABLE && policy != CLOTHHIP_POLICY_ORACLE_CORNER && policy != CLOTHHIP_POLICY_HIGHEST_POINT && policy != CLOTHHIP_POLICY_MLP)
         return fail(CLOTHHIP_EINVAL, "unknown policy %d", policy);
+    if (policy == CLOTHHIP_POLICY_MLP && h->mlp.n_layers < 1) return fail(CLOTHHIP_ESTATE, "the MLP policy needs a network: call clothhip_set_policy_mlp first");
+    if (policy == CLOTHHIP_POLICY_MLP && h->relaxed)
+        return fail(CLOTHHIP_ESTATE, "clothhip_set_relaxed_order: the relaxed-order companion is a bench-only kernel without the MLP policy");
     if (policy == CLOTHHIP_POLICY_HIGHEST_POINT && !policy_arg)
         return fail(CLOTHHIP_EINVAL, "the highest-point policy needs policy_arg[1 + T][E] (construction codes + which of the highest points per slot)");
     if (policy == CLOTHHIP_POLICY_TABLE && !actions) return fail(CLOTHHIP_EINVAL, "the table policy needs actions[T][E][4]");
@@ -970,6 +978,8 @@ extern "C" int clothhip_run_actions_begin(clothhip_handle *h, const ClothEpisode
     if (int rc = lean_refresh(h)) return rc;
     if (h->lay().scratch_have < h->lay().scratch_need)
         return fail(CLOTHHIP_ESTATE, "n_side %d: the in-kernel metrics need %d B of LDS scratch, this variant has %d", h->N, h->lay().scratch_need, h->lay().scratch_have);
+    if (policy == CLOTHHIP_POLICY_MLP && h->lay().scratch_have < MLP_SCRATCH_BYTES)
+        return fail(CLOTHHIP_ESTATE, "n_side %d: the MLP policy's hidden vectors need %d B of LDS scratch, this variant has %d", h->N, MLP_SCRATCH_BYTES, h->lay().scratch_have);
     HIPCHECK(hipStreamSynchronize(h->stream));
     const size_t E = h->E, nrec = (size_t)T_ * E;
     if (int rc = h->d_fz.reserve(1024)) return rc;
@@ -983,7 +993,7 @@ extern "C" int clothhip_run_actions_begin(clothhip_handle *h, const ClothEpisode
     if (int rc = h->d_fscr.reserve(nscr * sizeof(ClothResetScript))) return rc;
     if (int rc = h->d_frst.reserve(nscr * sizeof(ClothResetRecord))) return rc;
     const double *d_actions = nullptr;
-    if (policy == CLOTHHIP_POLICY_TABLE) {
+    if (policy == CLOTHHIP_POLICY_TABLE || (policy == CLOTHHIP_POLICY_MLP && actions)) {      // (MLP: the optional noise table)
         if (actions_on_device) d_actions = actions;
         else {
             if (int rc = h->d_fact.reserve(nrec * 4 * 8)) return rc;
@@ -1025,7 +1035,7 @@ extern "C" int clothhip_run_actions_begin(clothhip_handle *h, const ClothEpisode
         return fail(CLOTHHIP_ESTATE, "clothhip_set_relaxed_order: the relaxed-order companion exists for the eight-wave LEAN layout only (fp32, flat tiers, 25x25 class, <= 512 cloths)");
     HIPCHECK(hipEventRecord(h->ev0, h->stream));
     // (FUSED 2: the variant that also carries the tier-2 reset code and the cold policies; the relaxed-order companion is one launch)
-    const int fused = h->relaxed ? 3 : (tier2 || policy == CLOTHHIP_POLICY_HIGHEST_POINT) ? 2 : 1;
+    const int fused = h->relaxed ? 3 : (tier2 || policy == CLOTHHIP_POLICY_HIGHEST_POINT || policy == CLOTHHIP_POLICY_MLP || read_debug_knobs().cold_build) ? 2 : 1;
     if (int rc = launch_run(h, fused, h->d_sched, h->d_fz, !h->relaxed && budget_ticks != 0)) return rc;
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipEventRecord(h->ev1, h->stream));
@@ -1175,6 +1185,97 @@ extern "C" int clothhip_write_obs_f32_device(clothhip_handle *h, void *d_out) {
         hipLaunchKernelGGL(k_write_obs<decltype(t)>, dim3(h->E), dim3(256), 0, h->stream, (const decltype(t) *)h->d_pos, (float *)d_out, h->P, h->Ppad);
     });
     HIPCHECK(hipGetLastError());
+    return 0;
+}
+
+// ---- a learned policy: the handle's network (cloth_policy_mlp.hpp) ----------------------------------------------------------------------
+extern "C" int clothhip_set_policy_mlp(clothhip_handle *h, int32_t n_layers, const int32_t *widths, const float *params, size_t n_params) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (int rc = check_idle(h)) return rc;
+    if (n_layers == 0) { h->mlp = MlpDesc{}; return 0; }      // (the blob's memory stays with the handle for the next network)
+    if (n_layers < 0 || n_layers > MLP_MAX_LAYERS) return fail(CLOTHHIP_EINVAL, "n_layers %d outside [0, %d]", n_layers, MLP_MAX_LAYERS);
+    if (!widths || !params) return fail(CLOTHHIP_EINVAL, "NULL argument");
+    if (widths[0] != 3 * h->P) return fail(CLOTHHIP_EINVAL, "the network's input width is %d, the '1d' observation has %d values", widths[0], 3 * h->P);
+    if (widths[n_layers] != MLP_OUT) return fail(CLOTHHIP_EINVAL, "the network's output width is %d, an action has %d values", widths[n_layers], MLP_OUT);
+    for (int l = 1; l < n_layers; l++)
+        if (widths[l] < 1 || widths[l] > MLP_MAX_WIDTH) return fail(CLOTHHIP_EINVAL, "hidden width %d (layer %d) outside [1, %d]", widths[l], l, MLP_MAX_WIDTH);
+    const size_t need = mlp_param_count(n_layers, widths);
+    if (n_params != need) return fail(CLOTHHIP_EINVAL, "n_params = %zu, these widths hold %zu parameters", n_params, need);
+    HIPCHECK(hipSetDevice(h->device));
+    HIPCHECK(hipStreamSynchronize(h->stream));      // nothing in flight reads the blob reserve() may free
+    h->mlp = MlpDesc{};                             // from here on the old network is gone: a failure below leaves the handle without one
+    if (int rc = h->d_mlp.reserve(need * 4)) return rc;
+    HIPCHECK(hipMemcpyAsync(h->d_mlp, params, need * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));      // the host blob is never retained
+    MlpDesc d = {};
+    d.n_layers = n_layers;
+    for (int l = 0; l <= n_layers; l++) d.widths[l] = widths[l];
+    d.params = h->d_mlp;
+    h->mlp = d;
+    return 0;
+}
+
+// ---- clothhip_policy_eval: one workgroup per row --------------------------------------------------------------------------------
+struct PolicyEvalArgs {
+    MlpDesc mlp;
+    const float *rows;       // [n][3P] '1d' observations, or nullptr: the SoA state below
+    const void *pos;         // [n][3][Ppad], handle precision
+    int32_t P, Ppad;
+    double *out;             // [n][4]
+};
+template <typename T> __global__ __launch_bounds__(256) void k_policy_eval(PolicyEvalArgs A) {
+    __shared__ float buf[2 * MLP_MAX_WIDTH];
+    const size_t r = blockIdx.x;
+    const int tid = threadIdx.x;
+    if (A.rows != nullptr) {
+        const float *x = A.rows + r * 3 * (size_t)A.P;
+        mlp_eval(A.mlp, [x](int i) -> float { return x[i]; }, buf, tid, 256);
+    } else {
+        const T *p = (const T *)A.pos + r * 3 * (size_t)A.Ppad;
+        const int Ppad = A.Ppad;
+        mlp_eval(A.mlp, [p, Ppad](int i) -> float { const int q = i / 3, ax = i - 3 * q; return (float)p[ax * Ppad + q]; }, buf, tid, 256);
+    }
+    if (tid < MLP_OUT) A.out[r * MLP_OUT + tid] = (double)buf[mlp_out_offset(A.mlp.n_layers) + tid];
+}
+
+// rows per chunk: the uploaded rows of one chunk take at most 32 MB, whatever n is
+static size_t policy_eval_chunk(int P) {
+    const size_t c = ((size_t)32 << 20) / ((size_t)3 * P * 4);
+    return c < 1 ? 1 : (c > 65536 ? 65536 : c);
+}
+
+extern "C" int clothhip_policy_eval(clothhip_handle *h, const float *obs_rows, int64_t n, double *actions_out) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (n < 0) return fail(CLOTHHIP_EINVAL, "n < 0");
+    if (!obs_rows && n != h->E) return fail(CLOTHHIP_EINVAL, "n = %lld, the handle's state holds %d cloths", (long long)n, h->E);
+    if (!actions_out && n > 0) return fail(CLOTHHIP_EINVAL, "actions_out is NULL");
+    if (int rc = check_idle(h)) return rc;
+    if (h->mlp.n_layers < 1) return fail(CLOTHHIP_ESTATE, "no network on this handle: call clothhip_set_policy_mlp first");
+    if (n == 0) return 0;
+    HIPCHECK(hipSetDevice(h->device));
+    const size_t row = (size_t)3 * h->P, chunk = policy_eval_chunk(h->P), cmax = (size_t)n < chunk ? (size_t)n : chunk;
+    if (obs_rows) if (int rc = h->d_pe_rows.reserve(cmax * row * 4)) return rc;
+    if (int rc = h->d_pe_out.reserve(cmax * MLP_OUT * 8)) return rc;
+    PolicyEvalArgs a;
+    memset(&a, 0, sizeof(a));
+    a.mlp = h->mlp; a.P = h->P; a.Ppad = h->Ppad; a.out = h->d_pe_out;
+    for (size_t i0 = 0; i0 < (size_t)n; i0 += chunk) {
+        const size_t m = (size_t)n - i0 < chunk ? (size_t)n - i0 : chunk;
+        if (obs_rows) {
+            HIPCHECK(hipMemcpyAsync(h->d_pe_rows, obs_rows + i0 * row, m * row * 4, hipMemcpyHostToDevice, h->stream));
+            a.rows = h->d_pe_rows;
+            hipLaunchKernelGGL(k_policy_eval<float>, dim3((unsigned)m), dim3(256), 0, h->stream, a);
+        } else {
+            by_precision(h, [&](auto t) {
+                using T = decltype(t);
+                a.pos = (const T *)h->d_pos + i0 * 3 * h->Ppad;
+                hipLaunchKernelGGL(k_policy_eval<T>, dim3((unsigned)m), dim3(256), 0, h->stream, a);
+            });
+        }
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipMemcpyAsync(actions_out + i0 * MLP_OUT, h->d_pe_out, m * MLP_OUT * 8, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHECK(hipStreamSynchronize(h->stream));
     return 0;
 }
 

@@ -19,7 +19,7 @@ static inline int metrics_scratch_bytes(MetricsDims d, int tsz, bool hull_idx) {
 }
 
 // Every CLOTHHIP_DEBUG_* switch, read here and nowhere else. The planning switches are read when a handle is created
-// (clothhip_create, clothhip_selftest_layout) and kept on it; NOSPEC and ONE_LAUNCH are read again at every launch.
+// (clothhip_create, clothhip_selftest_layout) and kept on it; NOSPEC, ONE_LAUNCH and COLD are read again at every launch.
 struct DebugKnobs {
     bool w8_off = false;         // W8=0: the four-wave standard builds of the 25x25 class (only the value 0 switches)
     bool nt1024 = false;         // NT1024 (set at all): 1024 x 3 instead of 512 x 5 for the grids of 769 .. 2 560 points
@@ -34,6 +34,7 @@ struct DebugKnobs {
     bool one_launch = false;     // ONE_LAUNCH (set at all): a time-sliced episode launch as one dispatch, not one per generation
     int render_lds_kib = 160;    // RENDER_LDS: LDS budget in KiB of a clothhip_render_obs workgroup (smaller: shorter bands, more workgroups per CU)
     bool render_walk = false;    // RENDER_WALK (nonzero): one workgroup walks all bands of an image instead of one workgroup per band
+    bool cold_build = false;     // COLD (nonzero): every episode launch takes the build that carries the tier-2 resets and the cold policies (tools/policy_bench.py)
 };
 static DebugKnobs read_debug_knobs() {
     DebugKnobs k;
@@ -49,6 +50,7 @@ static DebugKnobs read_debug_knobs() {
     k.one_launch = getenv("CLOTHHIP_DEBUG_ONE_LAUNCH") != nullptr;
     if (const char *t = getenv("CLOTHHIP_DEBUG_RENDER_LDS")) { const int v = atoi(t); if (v >= 1 && v <= 160) k.render_lds_kib = v; }
     if (const char *t = getenv("CLOTHHIP_DEBUG_RENDER_WALK")) k.render_walk = atoi(t) != 0;
+    if (const char *t = getenv("CLOTHHIP_DEBUG_COLD")) k.cold_build = atoi(t) != 0;
     return k;
 }
 

@@ -43,7 +43,9 @@ def collect_demos(env, policy='oracle_corner', max_episodes=10, slots_per_launch
     """Run `policy` until `max_episodes` episodes have finished (over all envs of `env`, in order of completion) and return
     them as a list of episode dicts; with `path` the list is also pickled there (analytic.py:900-901).
     `env` must have been seeded; it is reset here. A policies.HighestPointPolicy with on_device=True is evaluated in the
-    kernel as well: its per-env pick streams are drawn here and handed to the launch slot by slot.
+    kernel as well: its per-env pick streams are drawn here and handed to the launch slot by slot. So is a policies.MLPPolicy
+    with on_device=True (the network runs inside the launch, ClothVecEnv.step_many(policy='mlp')): its per-env noise streams are
+    drawn here, one [4] per slot, and what a time-sliced launch leaves unused goes to the next one.
     obs: '1d', or 'rgb' / 'depth' / 'rgbd' for image observations in the episodes' 'obs' lists (image_kw: render parameters);
     everything else in an episode is the same either way."""
     if obs not in ('1d', 'rgb', 'depth', 'rgbd'):
@@ -52,14 +54,17 @@ def collect_demos(env, policy='oracle_corner', max_episodes=10, slots_per_launch
     episodes = []
     E = env.E
     obs = env.reset()
-    from .policies import HighestPointPolicy
+    from .policies import HighestPointPolicy, MLPPolicy
     hp = policy if (on_device and isinstance(policy, HighestPointPolicy)) else None
-    if isinstance(policy, str) or hp is not None:
-        if hp is None and policy != 'oracle_corner':
+    mlp = policy if (on_device and isinstance(policy, MLPPolicy)) else None
+    if mlp is not None:
+        env.set_policy(mlp)
+    if isinstance(policy, str) or hp is not None or mlp is not None:
+        if hp is None and mlp is None and policy != 'oracle_corner':
             raise ValueError(policy)
         first = obs.astype(np.float32) if fmt is None else _state_images(env, fmt, image_kw)
         cur = [_new_episode(first[e], e) for e in range(E)]
-        picks = [[] for _ in range(E)]                                # highest point: picks drawn but not consumed yet
+        picks = [[] for _ in range(E)]                                # highest point / MLP noise: drawn but not consumed yet
         while len(episodes) < max_episodes:
             if hp is not None:
                 for e in range(E):
@@ -67,6 +72,17 @@ def collect_demos(env, policy='oracle_corner', max_episodes=10, slots_per_launch
                         picks[e].append(hp.draw(e))
                 tbl = np.array([[picks[e][t] for e in range(E)] for t in range(slots_per_launch)], dtype=np.int32)
                 out = env.step_many(policy='highest_point', n_actions=slots_per_launch, policy_choices=tbl, auto_reset=True,
+                                    want_obs=True, time_budget_ms=time_budget_ms, images=fmt, image_kw=image_kw)
+                for e in range(E):
+                    del picks[e][:int(out['ran'][:, e].sum())]
+            elif mlp is not None:
+                tbl = None
+                if mlp.noise_std > 0.0:
+                    for e in range(E):
+                        while len(picks[e]) < slots_per_launch:
+                            picks[e].append(mlp.draw(e))
+                    tbl = np.array([[picks[e][t] for e in range(E)] for t in range(slots_per_launch)], dtype=np.float64)
+                out = env.step_many(policy='mlp', n_actions=slots_per_launch, policy_noise=tbl, auto_reset=True,
                                     want_obs=True, time_budget_ms=time_budget_ms, images=fmt, image_kw=image_kw)
                 for e in range(E):
                     del picks[e][:int(out['ran'][:, e].sum())]

@@ -5,6 +5,8 @@ Cloth instances never interact, so the only exchange steps are
   * all-gather of per-env result records and, optionally, of the '1d' observations (cloth_env.py:196-200)
     float32[world*E][3P].
 There is no all-reduce on the data path (the bench uses one for its max-over-ranks clock and as barrier).
+A policy network (ClothVecEnv.set_policy, step_many(policy='mlp')) belongs to a rank's own handle: nothing here broadcasts weights,
+every rank sets them itself (the same layers on every rank give the same bits on every rank).
 
 Two transports behind one interface:
   RcclTransport    RCCL over xGMI, bound directly through ctypes (rccl.py); buffers are device allocations of the

@@ -256,6 +256,7 @@ class ClothVecEnv(object):
         self._pending = [None] * E                                   # pre-drawn reset scripts of step_many, per env
         self.total_substeps = 0                                      # executed update() calls, all envs
         self._version = 0                                            # counts the calls that change the env (commit checks it)
+        self._policy_mlp = None                                      # the network on the batch (set_policy): an MLPPolicy or its layers
         self._scratch = None                                         # lookahead's ClothBatch of E*K cloths
         self._look = None                                            # the last lookahead, for commit
 
@@ -453,6 +454,25 @@ class ClothVecEnv(object):
     # ---- forks of the device state: snapshot / restore, action lookahead (clothhip_fork) ---------------------------------
     _SNAP_ARRAYS = ('num_steps', 'num_sim_steps', 'have_tear', '_prev_reward', '_start_coverage', '_start_variance_inv',
                     '_current_coverage', '_iters_up_env', 'init_side', '_ep_done', 'last_executed', 'last_grabbed', 'last_iters_pull')
+
+    def set_policy(self, mlp):
+        """Upload a policies.MLPPolicy's network (or a list of (W, b) layers) to this env's batch for step_many(policy='mlp') and
+        policy_actions; None clears it. The network belongs to the batch, not to an env slot: snapshot / restore, forks and resets
+        leave it alone. On several GPUs every rank sets it itself (dist.py broadcasts no weights)."""
+        layers = None if mlp is None else getattr(mlp, 'layers', mlp)
+        if layers:
+            from .policies import pack_mlp
+            pack_mlp(layers, n_in=3 * self.P)      # a malformed network is refused here and the earlier one stays ...
+        self._policy_mlp = None                    # ... a failed upload leaves the batch without one (clothhip_set_policy_mlp)
+        self.batch.set_policy_mlp(layers)
+        self._policy_mlp = mlp if layers else None
+
+    def policy_actions(self, obs=None):
+        """The network's actions float64[E, 4] (before noise and clipping) for '1d' observations obs [E, 3P], or with obs=None for
+        every env's present state, computed on the device (ClothBatch.policy_eval)."""
+        if self._policy_mlp is None:
+            raise ValueError("no policy network: call set_policy(MLPPolicy(...)) first")
+        return self.batch.policy_eval(None if obs is None else np.asarray(obs).reshape(self.E, -1).astype(np.float32))
 
     def _require_whole_actions(self, what):
         if self.batch.in_flight().any():
@@ -677,7 +697,7 @@ class ClothVecEnv(object):
 
     def step_many(self, actions=None, n_actions=None, policy=None, auto_reset=True, want_obs=False, reset_tail=False,
                   actions_device_ptr=None, max_resets=None, time_budget_ms=0.0, device_rng=True, policy_choices=None,
-                  images=None, image_kw=None):
+                  images=None, image_kw=None, policy_noise=None):
         """T consecutive `step(a_t, auto_reset=auto_reset)` calls for every env in ONE device launch
         (clothhip_run_actions): decoding, grab, the substep loop, metrics, the terminal test and the episode resets all
         run in the kernel, envs never wait for each other, and the host only does the reward / info bookkeeping below.
@@ -685,7 +705,10 @@ class ClothVecEnv(object):
         actions: float64[T, E, 4], or policy='oracle_corner' (examples/analytic.py's oracle, evaluated on the device)
         with n_actions=T, or policy='highest_point' (analytic.py:723-808 on the device) with n_actions=T and
         policy_choices int[T, E]: which of the highest points (0 = the highest; the reference draws randint(5)) the env
-        pulls in its t-th slot. With auto_reset=False an env whose episode ends idles for the rest of the launch (`ran` False). Up to `max_resets` (default min(T, 255), the
+        pulls in its t-th slot, or policy='mlp' (the network of set_policy, evaluated in the kernel on the cloth's '1d' observation when
+        the slot begins -- after an in-kernel reset on the new episode's first state) with n_actions=T and optionally policy_noise
+        float64[T, E, 4], added to the network's output of that slot before clipping (exploration noise comes from the caller's table, so
+        the launch stays deterministic; with a time budget the caller passes the unused rows again, as for actions). With auto_reset=False an env whose episode ends idles for the rest of the launch (`ran` False). Up to `max_resets` (default min(T, 255), the
         launch's limit) resets per env and launch; an env that has used them idles until the launch ends. The resets are drawn on the device from
         each env's numpy RandomState stream (device_rng=True: the states are uploaded before and read back after the
         launch; csrc/cloth_rng.hpp reproduces numpy's MT19937 draws bit for bit; all three tiers, tier 2 rebuilding the
@@ -735,8 +758,20 @@ class ClothVecEnv(object):
             policy_choices = np.asarray(policy_choices, dtype=np.int32)                  # [T, E]: 0 = the highest point, 1 = the next ...
             if policy_choices.shape != (T, E):
                 raise ValueError("policy_choices must have shape (%d, %d)" % (T, E))
+        elif policy == 'mlp':
+            pol, T = _lib.POLICY_MLP, int(n_actions)
+            if self._policy_mlp is None:
+                raise ValueError("policy='mlp' needs a network: call set_policy(MLPPolicy(...)) first")
+            if actions is not None or actions_device_ptr is not None:
+                raise ValueError("policy='mlp' takes no actions: the network gives them; exploration noise goes into policy_noise")
+            if policy_noise is not None:
+                actions = np.ascontiguousarray(policy_noise, dtype=np.float64)
+                if actions.shape != (T, E, 4):
+                    raise ValueError("policy_noise must have shape (%d, %d, 4)" % (T, E))
         else:
             raise ValueError(policy)
+        if policy_noise is not None and policy != 'mlp':
+            raise ValueError("policy_noise goes with policy='mlp'")
         if not self._delta_actions:
             raise NotImplementedError("non-delta actions are decoded on the host only (cos/sin, cloth_env.py:452-453)")
         if images is not None:

@@ -8,6 +8,8 @@ RandomPolicy         examples/analytic.py:811-823 (the reference samples from an
                      cloth_env.py:1004; here each env gets its own RandomState so runs are reproducible)
 LookaheadPolicy      no reference counterpart: one-step greedy action selection over K candidates per env, evaluated on
                      device-side forks of the env's state (ClothVecEnv.lookahead)
+MLPPolicy            no reference counterpart: a small fully-connected network over the '1d' observation, evaluated on the device -- by
+                     the host loop through ClothBatch.policy_eval, or inside the episode launch (ClothVecEnv.step_many(policy='mlp'))
 """
 import numpy as np
 
@@ -143,3 +145,91 @@ class LookaheadPolicy(object):
         best = self.choose(out['rew'])
         self.last_candidates, self.last_lookahead, self.last_choice = cand, out, best
         return cand[np.arange(self.env.E), best]
+
+
+MLP_MAX_LAYERS, MLP_MAX_WIDTH = 4, 256
+
+
+def pack_mlp(layers, n_in=None):
+    """[(W, b), ...] -> (widths int32[L + 1], blob float32): for every layer W [out, in] row-major (torch.nn.Linear.weight's layout),
+    then b [out] -- what clothhip_set_policy_mlp takes. ValueError for anything the library would refuse: no or more than four layers,
+    a W that is not 2-d or a b that is not [out], widths that do not chain, an input width other than n_in (when given), a last width
+    other than 4, a hidden width outside [1, 256], non-finite values."""
+    layers = list(layers)
+    if not 1 <= len(layers) <= MLP_MAX_LAYERS:
+        raise ValueError("an MLP policy has 1 to %d weight layers (got %d)" % (MLP_MAX_LAYERS, len(layers)))
+    widths, parts = [], []
+    for l, wb in enumerate(layers):
+        if len(wb) != 2:
+            raise ValueError("layer %d must be a (W, b) pair" % l)
+        W, b = np.asarray(wb[0], dtype=np.float32), np.asarray(wb[1], dtype=np.float32)
+        if W.ndim != 2 or W.shape[0] < 1 or W.shape[1] < 1:
+            raise ValueError("layer %d: W must be a non-empty [out, in] matrix (got shape %r)" % (l, W.shape))
+        if b.shape != (W.shape[0],):
+            raise ValueError("layer %d: b must have shape (%d,) (got %r)" % (l, W.shape[0], b.shape))
+        if l and W.shape[1] != widths[-1]:
+            raise ValueError("layer %d takes %d inputs, layer %d gives %d" % (l, W.shape[1], l - 1, widths[-1]))
+        if not (np.isfinite(W).all() and np.isfinite(b).all()):
+            raise ValueError("layer %d holds non-finite values" % l)
+        if not l:
+            widths.append(int(W.shape[1]))
+        widths.append(int(W.shape[0]))
+        parts += [np.ascontiguousarray(W).reshape(-1), b]
+    if n_in is not None and widths[0] != int(n_in):
+        raise ValueError("the network's input width is %d, the '1d' observation has %d values" % (widths[0], int(n_in)))
+    if widths[-1] != 4:
+        raise ValueError("the network's output width is %d, an action has 4 values" % widths[-1])
+    for l in range(1, len(widths) - 1):
+        if not 1 <= widths[l] <= MLP_MAX_WIDTH:
+            raise ValueError("hidden width %d (layer %d) outside [1, %d]" % (widths[l], l, MLP_MAX_WIDTH))
+    return np.asarray(widths, dtype=np.int32), np.ascontiguousarray(np.concatenate(parts), dtype=np.float32)
+
+
+class MLPPolicy(object):
+    """A fully-connected network over the '1d' observation: `layers` = [(W, b), ...] numpy arrays, W [out, in] as torch.nn.Linear
+    holds it -- from a torch.nn.Sequential of Linear and ReLU modules:
+        [(m.weight.detach().cpu().numpy(), m.bias.detach().cpu().numpy()) for m in net if hasattr(m, 'weight')]
+    ReLU follows every layer but the last; the env's decode clips the action to the action space. The weights are held as float32.
+
+    get_action evaluates the network ON THE DEVICE (ClothBatch.policy_eval on the float32 observation), with the device function
+    the episode launch runs, so that ClothVecEnv.step(policy.get_action(obs)) and step_many(policy='mlp') compute the same bits;
+    reference(obs) is a float64 numpy evaluation of the same float32 weights, for tests. noise_std > 0 adds N(0, noise_std^2)
+    exploration noise to every action component, drawn from one RandomState(seed + e) per env: draw(e) is the next [4] of env e, which
+    collect_demos(on_device=True) hands to the launch slot by slot (step_many(policy_noise=...)). The constructor uploads the network
+    to env's batch (ClothVecEnv.set_policy); on several GPUs every rank does so itself."""
+
+    def __init__(self, env, layers, noise_std=0.0, seed=0):
+        self.env = env
+        self.layers = [(np.ascontiguousarray(W, dtype=np.float32), np.ascontiguousarray(b, dtype=np.float32)) for W, b in layers]
+        self.widths, self._blob = pack_mlp(self.layers, n_in=3 * env.P)
+        self.noise_std = float(noise_std)
+        self.rngs = [np.random.RandomState(seed + e) for e in range(env.E)]
+        env.set_policy(self)
+
+    def pack(self):
+        """(widths int32[L + 1], blob float32): the network as clothhip_set_policy_mlp takes it."""
+        return self.widths.copy(), self._blob.copy()
+
+    def reference(self, obs):
+        """float64 evaluation of the float32 weights on obs [n, 3P] (rounded to float32 first, as the device reads it): [n, 4]."""
+        x = np.asarray(obs, dtype=np.float32).astype(np.float64).reshape(-1, int(self.widths[0]))
+        for l, (W, b) in enumerate(self.layers):
+            x = x @ W.astype(np.float64).T + b.astype(np.float64)
+            if l + 1 < len(self.layers):
+                x = np.maximum(x, 0.0)
+        return x
+
+    def draw(self, e):
+        """The next noise vector [4] of env e (zeros without noise; the stream then does not advance)."""
+        if self.noise_std <= 0.0:
+            return np.zeros(4)
+        return self.rngs[e].normal(size=4) * self.noise_std
+
+    def get_action(self, obs, t=0):
+        E = self.env.E
+        if self.env._policy_mlp is not self:       # another network was set on the env since: put this one back, never answer with the other's
+            self.env.set_policy(self)
+        act = self.env.batch.policy_eval(np.asarray(obs).reshape(E, -1).astype(np.float32))
+        if self.noise_std > 0.0:
+            act = act + np.stack([self.draw(e) for e in range(E)])
+        return act

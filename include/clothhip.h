@@ -22,6 +22,7 @@
 #ifndef CLOTHHIP_H
 #define CLOTHHIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -241,9 +242,11 @@ typedef struct ClothEpisodeParams {
 
 enum { CLOTHHIP_POLICY_TABLE = 0,          /* actions[t][e][4] given by the caller (any policy run on the host, or random) */
        CLOTHHIP_POLICY_ORACLE_CORNER = 1,  /* examples/analytic.py:105-155, 'distance' method, delta actions, 25x25 only */
-       CLOTHHIP_POLICY_HIGHEST_POINT = 2   /* examples/analytic.py:723-808: the k-th highest point (stable order), pulled to where it
+       CLOTHHIP_POLICY_HIGHEST_POINT = 2,  /* examples/analytic.py:723-808: the k-th highest point (stable order), pulled to where it
                                               sits on the flat cloth; k per slot and env from policy_arg (the reference draws it
-                                              with np.random.randint(top_k = 5)) */ };
+                                              with np.random.randint(top_k = 5)) */
+       CLOTHHIP_POLICY_MLP = 3             /* the handle's network (clothhip_set_policy_mlp) on the cloth's '1d' observation at the start of
+                                              the slot, + actions[t][e][4] where `actions` is given (no reference counterpart) */ };
 
 /* One scripted pull of a reset (cloth_env.py:851-877 tier 1, :959-978 tier 3): the raw RNG draws; everything that
  * depends on the particle state (the picked point's position, _prevent_oob) is evaluated on the device. */
@@ -351,6 +354,26 @@ int clothhip_run_actions_summary(clothhip_handle *h, double *summary, void **d_s
 int clothhip_run_actions_op_ticks(clothhip_handle *h, uint64_t *ticks);
 /* 1 if this handle's kernel variant has the LDS room for the in-kernel metrics of clothhip_run_actions, else 0 */
 int clothhip_fused_supported(const clothhip_handle *h);
+
+/* A learned policy inside the episode launch (no reference counterpart): a fully-connected network over the '1d' observation
+ * (cloth_env.py:196-200), n_layers weight layers (1..4), widths[0 .. n_layers] with widths[0] = 3 P, widths[n_layers] = 4, hidden widths in
+ * [1, 256], ReLU after every layer but the last (the launch's decode clips to act_low / act_high as for any action). params: ONE float32
+ * blob of n_params values, for l = 0 .. n_layers-1 W_l[out][in] row-major (torch.nn.Linear.weight's layout), then b_l[out]. The input
+ * is (float)position, element 3 i + ax, also on an fp64 handle, and the arithmetic is float32 in one fixed order
+ * (csrc/cloth_policy_mlp.hpp), so the network is one function of the observation the caller would have seen, whatever stepper variant
+ * runs. The call validates, uploads (the host blob is not retained) and replaces any earlier network; n_layers == 0 clears it.
+ * CLOTHHIP_EINVAL: more than 4 layers, widths[0] != 3 P, a last width other than 4, a hidden width outside [1, 256], n_params not what
+ * the widths give -- the earlier network then stays. The network belongs to the HANDLE, not to an env slot: every env evaluates it;
+ * clothhip_fork, resets and clothhip_set_state never touch it. CLOTHHIP_ESTATE between clothhip_run_actions_begin and _end.
+ * clothhip_run_actions* with CLOTHHIP_POLICY_MLP evaluates it once per action slot, when the slot begins (after an in-kernel reset: on the
+ * new episode's first state), act = (double)y + actions[t][e] (`actions` optional there: the caller's exploration noise, NULL = none;
+ * the record's `action` holds that sum before clipping); an action a time slice cuts is not evaluated again. CLOTHHIP_ESTATE from
+ * those calls without a network, on a relaxed-order handle, or when the variant's LDS scratch cannot hold the two hidden vectors. */
+int clothhip_set_policy_mlp(clothhip_handle *h, int32_t n_layers, const int32_t *widths, const float *params, size_t n_params);
+/* The handle's network on n float32 rows obs_rows[n][3P] (host), or with obs_rows == NULL on the handle's present state (n must then be
+ * E): actions_out[n][4], the network's output as doubles, no noise, not clipped -- the very device function the launch runs, one
+ * workgroup per row, the rows in bounded chunks. CLOTHHIP_ESTATE without a network or with a launch in flight. Synchronous. */
+int clothhip_policy_eval(clothhip_handle *h, const float *obs_rows, int64_t n, double *actions_out);
 int clothhip_run_actions(clothhip_handle *h, const ClothEpisodeParams *ep, int32_t T, int32_t policy,
                          const double *actions, int32_t actions_on_device, const int32_t *policy_arg,
                          const ClothResetScript *scripts, int32_t n_scripts, int32_t *num_steps, uint8_t *done,
