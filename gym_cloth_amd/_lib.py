@@ -79,6 +79,8 @@ OBS_SOURCES = {'state': OBS_STATE, 'slots': OBS_SLOTS, 'resets': OBS_RESETS, 'ho
 
 POLICY_TABLE, POLICY_ORACLE_CORNER, POLICY_HIGHEST_POINT, POLICY_MLP = 0, 1, 2, 3
 MLP_MAX_LAYERS, MLP_MAX_WIDTH = 4, 256   # clothhip_set_policy_mlp (csrc/cloth_policy_mlp.hpp)
+POP_ANTITHETIC = 1                       # clothhip_policy_population_perturb flags (csrc/cloth_policy_population.hpp)
+POP_ROW_ALIGN, POP_MAX_G = 64, 65534     # floats a population's row stride is rounded up to; the most perturbations of one call
 MT_WORDS = 626                      # per-env RandomState image: key[624], pos, pad (csrc/cloth_rng.hpp)
 
 RESET_PULL_DTYPE = np.dtype([("point", "<i4"), ("need_coverage", "<i4"), ("x", "<f8"), ("y", "<f8"), ("dx", "<f8"),
@@ -135,6 +137,13 @@ SYMBOLS = [
                                        C.c_int32, _i32p, _u8p, _vp, _vp, _vp, _vp, C.c_double]),
     ("clothhip_set_policy_mlp", C.c_int, [_vp, C.c_int32, _i32p, C.POINTER(C.c_float), C.c_size_t]),
     ("clothhip_policy_eval", C.c_int, [_vp, C.POINTER(C.c_float), C.c_int64, _dp]),
+    ("clothhip_set_policy_population", C.c_int, [_vp, C.c_int32, _i32p, C.POINTER(C.c_float), C.c_int32, _i32p]),
+    ("clothhip_set_policy_members", C.c_int, [_vp, _i32p]),
+    ("clothhip_get_policy_mlp", C.c_int, [_vp, C.c_int64, C.POINTER(C.c_float), C.c_size_t]),
+    ("clothhip_policy_eval_members", C.c_int, [_vp, C.POINTER(C.c_float), C.c_int64, _i32p, _dp]),
+    ("clothhip_policy_population_perturb", C.c_int, [_vp, C.c_int32, _i32p, C.POINTER(C.c_float), C.c_int32, C.c_float, C.c_uint64,
+                                                     C.c_int32, _i32p]),
+    ("clothhip_policy_population_combine", C.c_int, [_vp, C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_float)]),
     ("clothhip_update", C.c_int, [_vp, C.c_int32, _dp]),
     ("clothhip_metrics", C.c_int, [_vp, _dp, _dp, _u8p, _u8p]),
     ("clothhip_metrics_ex", C.c_int, [_vp, _dp, _dp, _u8p, _u8p, _i32p]),

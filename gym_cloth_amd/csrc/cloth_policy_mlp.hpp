@@ -1,6 +1,7 @@
 // cloth_policy_mlp.hpp -- a small fully-connected policy network over the '1d' observation (no reference counterpart: the policy kind a
 // learner brings), evaluated by ONE device function that the episode launch (episode_plan.inc.hpp, CLOTHHIP_POLICY_MLP) and the stand-alone
 // kernel (k_policy_eval in clothhip_api.hip, behind clothhip_policy_eval) share, so the host loop and the launch compute the same bits.
+// One network for all cloths, or one per env slot out of a population of blobs (MlpDesc::member; cloth_policy_population.hpp makes one).
 //
 //   L weight layers (1 <= L <= MLP_MAX_LAYERS), widths[0] = 3 P (the observation), widths[L] = 4 (the action), hidden widths in
 //   [1, MLP_MAX_WIDTH]; ReLU after every layer but the last. Parameters: one float32 blob, for l = 0 .. L-1 W_l[out][in] row-major
@@ -31,6 +32,9 @@ struct MlpDesc {
     int32_t widths[MLP_MAX_LAYERS + 1];     // widths[0 .. n_layers]
     int32_t _pad;
     const float *params;                    // device memory, owned by the handle
+    // a population (clothhip_set_policy_population): env e runs the blob at params + member[e] * stride. nullptr: every env runs `params`.
+    const int32_t *member;                  // device [E], values in [0, rows)
+    int64_t stride;                         // floats between two blobs: n_params rounded up to 64, so every blob is 256-byte aligned
 };
 
 // floats in the blob of a network with these widths
@@ -68,10 +72,12 @@ template <class In> __device__ __forceinline__ void mlp_eval(const MlpDesc &D, I
     }
 }
 
-// ... on particle records {x, y, z, w} in LDS (the episode launch's resident state). Not inlined: the plan's register allocation stays
-// out of the stepper kernel's body, and nothing of it is live across the substep loop.
-template <class Rec> __device__ __noinline__ void mlp_eval_records(const MlpDesc *D, const Rec *cur, float *buf, int tid, int nt) {
-    const MlpDesc d = *D;
+// ... on particle records {x, y, z, w} in LDS (the episode launch's resident state), for env slot e: with a population the slot's own blob --
+// only the base pointer moves, so a cloth under network g computes the bits a handle with g as its shared network computes. Not inlined:
+// the plan's register allocation stays out of the stepper kernel's body, and nothing of it is live across the substep loop.
+template <class Rec> __device__ __noinline__ void mlp_eval_records(const MlpDesc *D, int e, const Rec *cur, float *buf, int tid, int nt) {
+    MlpDesc d = *D;
+    if (d.member != nullptr) d.params += (size_t)d.member[e] * (size_t)d.stride;
     mlp_eval(d, [cur](int i) -> float { const int p = i / 3, ax = i - 3 * p; const Rec c = cur[p]; return (float)(ax == 0 ? c.x : (ax == 1 ? c.y : c.z)); },
              buf, tid, nt);
 }

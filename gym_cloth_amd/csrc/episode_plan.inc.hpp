@@ -182,14 +182,14 @@
                     act[0] = F.ep.clip_act_space ? cx : x; act[1] = F.ep.clip_act_space ? cy : y; // :803-806
                     act[2] = dx; act[3] = dy;
                 } else if (with_tier2 && F.policy == CLOTHHIP_POLICY_MLP) {
-                    // the handle's network on this cloth's '1d' observation (cloth_policy_mlp.hpp: the order of its arithmetic does not depend on
-                    // NT), + the caller's noise for this slot. The two hidden vectors borrow the head of the scratch the in-kernel metrics
+                    // the handle's network (with a population: this env slot's, MlpDesc::member) on this cloth's '1d' observation
+                    // (cloth_policy_mlp.hpp: the order of its arithmetic does not depend on NT), + the caller's noise for this slot. The two hidden vectors borrow the head of the scratch the in-kernel metrics
                     // borrow (on a small grid `misc` lies inside it: the tear flag is carried over), which is rebuilt as after the metrics.
                     if constexpr (with_tier2) {
                         const int tear_keep = misc[0];
                         __syncthreads();
                         float *mbuf = reinterpret_cast<float *>(smem + lay.hkey);
-                        mlp_eval_records<Pt<T>>(&F.mlp, cur, mbuf, tid, NT);
+                        mlp_eval_records<Pt<T>>(&F.mlp, e, cur, mbuf, tid, NT);
                         const float *y = mbuf + mlp_out_offset(F.mlp.n_layers);
                         const double *nz = F.actions != nullptr ? F.actions + ((size_t)t_slot * F.E + e) * 4 : nullptr;
 #pragma unroll

@@ -45,7 +45,8 @@ def collect_demos(env, policy='oracle_corner', max_episodes=10, slots_per_launch
     `env` must have been seeded; it is reset here. A policies.HighestPointPolicy with on_device=True is evaluated in the
     kernel as well: its per-env pick streams are drawn here and handed to the launch slot by slot. So is a policies.MLPPolicy
     with on_device=True (the network runs inside the launch, ClothVecEnv.step_many(policy='mlp')): its per-env noise streams are
-    drawn here, one [4] per slot, and what a time-sliced launch leaves unused goes to the next one.
+    drawn here, one [4] per slot, and what a time-sliced launch leaves unused goes to the next one. A policies.MLPPopulation goes the
+    same way, every env under its own network (it adds no noise).
     obs: '1d', or 'rgb' / 'depth' / 'rgbd' for image observations in the episodes' 'obs' lists (image_kw: render parameters);
     everything else in an episode is the same either way."""
     if obs not in ('1d', 'rgb', 'depth', 'rgbd'):
@@ -54,9 +55,9 @@ def collect_demos(env, policy='oracle_corner', max_episodes=10, slots_per_launch
     episodes = []
     E = env.E
     obs = env.reset()
-    from .policies import HighestPointPolicy, MLPPolicy
+    from .policies import HighestPointPolicy, MLPPolicy, MLPPopulation
     hp = policy if (on_device and isinstance(policy, HighestPointPolicy)) else None
-    mlp = policy if (on_device and isinstance(policy, MLPPolicy)) else None
+    mlp = policy if (on_device and isinstance(policy, (MLPPolicy, MLPPopulation))) else None
     if mlp is not None:
         env.set_policy(mlp)
     if isinstance(policy, str) or hp is not None or mlp is not None:

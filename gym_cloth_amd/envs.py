@@ -457,8 +457,16 @@ class ClothVecEnv(object):
 
     def set_policy(self, mlp):
         """Upload a policies.MLPPolicy's network (or a list of (W, b) layers) to this env's batch for step_many(policy='mlp') and
-        policy_actions; None clears it. The network belongs to the batch, not to an env slot: snapshot / restore, forks and resets
-        leave it alone. On several GPUs every rank sets it itself (dist.py broadcasts no weights)."""
+        policy_actions; None clears it. That network belongs to the batch, not to an env slot. A policies.MLPPopulation puts ONE NETWORK
+        PER ENV SLOT there instead (its present generation, made on the device). Either way snapshot / restore, forks, the lookahead's
+        scratch batch and resets neither carry nor touch networks. On several GPUs every rank sets it itself (dist.py broadcasts no
+        weights)."""
+        from .policies import MLPPopulation
+        if isinstance(mlp, MLPPopulation):
+            self._policy_mlp = None                # a failed upload leaves the batch without a network
+            mlp._upload(self.batch)
+            self._policy_mlp = mlp
+            return
         layers = None if mlp is None else getattr(mlp, 'layers', mlp)
         if layers:
             from .policies import pack_mlp
@@ -469,10 +477,15 @@ class ClothVecEnv(object):
 
     def policy_actions(self, obs=None):
         """The network's actions float64[E, 4] (before noise and clipping) for '1d' observations obs [E, 3P], or with obs=None for
-        every env's present state, computed on the device (ClothBatch.policy_eval)."""
+        every env's present state, computed on the device (ClothBatch.policy_eval; with an MLPPopulation every env under its own
+        network, ClothBatch.policy_eval_members)."""
         if self._policy_mlp is None:
             raise ValueError("no policy network: call set_policy(MLPPolicy(...)) first")
-        return self.batch.policy_eval(None if obs is None else np.asarray(obs).reshape(self.E, -1).astype(np.float32))
+        rows = None if obs is None else np.asarray(obs).reshape(self.E, -1).astype(np.float32)
+        member = getattr(self._policy_mlp, 'member', None)
+        if member is not None:
+            return self.batch.policy_eval_members(rows, member)
+        return self.batch.policy_eval(rows)
 
     def _require_whole_actions(self, what):
         if self.batch.in_flight().any():

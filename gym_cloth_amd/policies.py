@@ -10,6 +10,9 @@ LookaheadPolicy      no reference counterpart: one-step greedy action selection 
                      device-side forks of the env's state (ClothVecEnv.lookahead)
 MLPPolicy            no reference counterpart: a small fully-connected network over the '1d' observation, evaluated on the device -- by
                      the host loop through ClothBatch.policy_eval, or inside the episode launch (ClothVecEnv.step_many(policy='mlp'))
+MLPPopulation        no reference counterpart: one MLP per env slot -- G perturbed copies of a centre network made on the device
+                     (ClothBatch.population_perturb), rolled out in ONE episode launch, and the evolution-strategies update summed on
+                     the device (ClothBatch.population_combine)
 """
 import numpy as np
 
@@ -233,3 +236,177 @@ class MLPPolicy(object):
         if self.noise_std > 0.0:
             act = act + np.stack([self.draw(e) for e in range(E)])
         return act
+
+
+def unpack_mlp(widths, blob):
+    """The inverse of pack_mlp: [(W, b), ...] float32 copies out of one blob."""
+    layers, o = [], 0
+    for l in range(len(widths) - 1):
+        n_in, n_out = int(widths[l]), int(widths[l + 1])
+        W = np.array(blob[o:o + n_out * n_in], dtype=np.float32).reshape(n_out, n_in); o += n_out * n_in
+        b = np.array(blob[o:o + n_out], dtype=np.float32); o += n_out
+        layers.append((W, b))
+    if o != len(blob):
+        raise ValueError("the blob holds %d values, these widths %d" % (len(blob), o))
+    return layers
+
+
+def pack_population(members, n_in=None):
+    """[network, ...] (each a list of (W, b) layers, all of ONE shape) -> (widths int32[L + 1], float32 [G, n_params]): what
+    clothhip_set_policy_population takes. ValueError for what pack_mlp refuses, and for networks of different shapes."""
+    members = list(members)
+    if not members:
+        raise ValueError("a population has at least one network")
+    widths, rows = None, []
+    for g, layers in enumerate(members):
+        w, blob = pack_mlp(layers, n_in=n_in)
+        if widths is not None and not np.array_equal(w, widths):
+            raise ValueError("network %d has widths %r, network 0 has %r: a population has one shape" % (g, w.tolist(), widths.tolist()))
+        widths = w
+        rows.append(blob)
+    return widths, np.ascontiguousarray(np.stack(rows), dtype=np.float32)
+
+
+def population_stride(n_params):
+    """Floats between two rows of a population on the device: n_params rounded up to 64, so that every row is 256-byte aligned."""
+    return (int(n_params) + 63) // 64 * 64
+
+
+def es_coefficients(fitness, sigma, antithetic=True, shaping="centered_rank"):
+    """The coefficients w_k of the evolution-strategies estimate g = sum_k w_k eps_k from the G members' fitness (float64 arithmetic,
+    returned as float32 -- what ClothBatch.population_combine takes).
+      shaping 'centered_rank': u_g = rank_g / (G - 1) - 1/2, rank 0 for the lowest fitness (equal values rank in member order; G = 1: 0);
+              'raw':           u_g = fitness_g, unchanged.
+      plain:       g = 1 / (G sigma) sum_g u_g eps_g                          -> w_g = u_g / (G sigma), K = G
+      antithetic:  rows 2k, 2k + 1 carry +eps_k, -eps_k, so the same estimate -> w_k = (u_2k - u_2k+1) / (G sigma), K = G / 2."""
+    f = np.asarray(fitness, dtype=np.float64).reshape(-1)
+    G = f.size
+    if G < 1 or not np.isfinite(f).all():
+        raise ValueError("fitness must hold one finite value per member")
+    if antithetic and G % 2:
+        raise ValueError("antithetic perturbations come in pairs: %d fitness values" % G)
+    if not float(sigma) > 0.0:
+        raise ValueError("sigma must be > 0")
+    if shaping == "centered_rank":
+        rank = np.empty(G, dtype=np.float64)
+        rank[np.argsort(f, kind="stable")] = np.arange(G)
+        u = rank / (G - 1) - 0.5 if G > 1 else np.zeros(1)
+    elif shaping == "raw":
+        u = f
+    else:
+        raise ValueError(shaping)
+    w = (u[0::2] - u[1::2]) if antithetic else u
+    return (w / (G * float(sigma))).astype(np.float32)
+
+
+class MLPPopulation(object):
+    """G = n_members perturbed copies of ONE centre network, one per env slot, for gradient-free learners (evolution strategies, CEM over
+    parameters, checkpoints side by side): the copies are made on the device, all E cloths roll out under their own network in one
+    step_many(policy='mlp') launch, and the update sum_k w_k eps_k is summed on the device as well -- no normal variate is drawn on
+    the host and no blob crosses PCIe but the centre.
+
+    The device holds G + 1 rows: with antithetic=True (G even) rows 2k and 2k + 1 are theta + sigma eps_k and theta - sigma eps_k, else
+    row g is theta + sigma eps_g; row G is theta, the unperturbed centre. `member` int[E] says which row env e runs (default
+    e % (G + 1)). eps is defined in csrc/cloth_policy_population.hpp (Philox4x32-10; zero mean, unit variance, symmetric, |eps| <= 3.47:
+    a sum of four uniforms, NOT a Gaussian). THE SEED OF GENERATION n IS seed + n (mod 2^64): perturb(n) makes that generation's rows,
+    the same bits every time. sigma is held as float32.
+
+    The networks belong to the env slots of env's batch: resets and uploads leave them alone; snapshots, forks and the lookahead's
+    scratch batch do not carry them. The constructor makes generation 0 (ClothVecEnv.set_policy(self))."""
+
+    noise_std = 0.0        # (collect_demos: no exploration noise on top of the parameter noise)
+
+    def __init__(self, env, center_layers, n_members, sigma, seed, antithetic=True, member=None):
+        self.env = env
+        self.center = [(np.array(W, dtype=np.float32), np.array(b, dtype=np.float32)) for W, b in center_layers]
+        self.widths, self._blob = pack_mlp(self.center, n_in=3 * env.P)
+        self.G = int(n_members)
+        self.antithetic = bool(antithetic)
+        if self.G < 1:
+            raise ValueError("n_members = %d: a population has at least one member" % self.G)
+        if self.antithetic and self.G % 2:
+            raise ValueError("n_members = %d: antithetic perturbations come in pairs, n_members must be even" % self.G)
+        self.sigma = float(np.float32(sigma))
+        if not (np.isfinite(self.sigma) and self.sigma > 0.0):
+            raise ValueError("sigma must be a finite float32 > 0")
+        self.seed = int(seed)
+        if not 0 <= self.seed < 2 ** 64:
+            raise ValueError("seed must lie in [0, 2^64)")
+        m = np.arange(env.E) % (self.G + 1) if member is None else np.asarray(member)
+        if m.shape != (env.E,):
+            raise ValueError("member must have shape (%d,) (got %r)" % (env.E, m.shape))
+        if not np.issubdtype(m.dtype, np.integer) or m.min() < 0 or m.max() > self.G:
+            raise ValueError("member must hold integers in [0, %d]" % self.G)
+        self.member = m.astype(np.int32)
+        self.generation = 0
+        env.set_policy(self)
+
+    @property
+    def n_params(self):
+        return int(self._blob.size)
+
+    def generation_seed(self, generation):
+        return (self.seed + int(generation)) % 2 ** 64
+
+    def _upload(self, batch):
+        batch.population_perturb(self.center, self.G, self.sigma, self.generation_seed(self.generation), antithetic=self.antithetic,
+                                 member=self.member)
+
+    def perturb(self, generation):
+        """Make generation `generation`'s G + 1 rows around the present centre (seed + generation) and put them on the env."""
+        self.generation = int(generation)
+        self.env.set_policy(self)
+
+    def set_members(self, member):
+        """Another map env -> row, without touching the rows (ClothBatch.set_policy_members)."""
+        m = np.asarray(member)
+        if m.shape != (self.env.E,) or not np.issubdtype(m.dtype, np.integer) or m.min() < 0 or m.max() > self.G:
+            raise ValueError("member must be %d integers in [0, %d]" % (self.env.E, self.G))
+        self._on_env()
+        self.env.batch.set_policy_members(m)
+        self.member = m.astype(np.int32)
+
+    def _on_env(self):
+        if self.env._policy_mlp is not self:       # another network was set on the env since: put this generation back (the same bits)
+            self.env.set_policy(self)
+
+    def members(self):
+        """The G + 1 rows as the device holds them: a list of layer lists, by download."""
+        self._on_env()
+        return [unpack_mlp(self.widths, self.env.batch.get_policy_mlp(g, self.n_params)) for g in range(self.G + 1)]
+
+    def get_action(self, obs, t=0):
+        """float64[E, 4]: env e's row on obs[e], on the device (ClothBatch.policy_eval_members) -- the bits the launch computes."""
+        self._on_env()
+        return self.env.batch.policy_eval_members(np.asarray(obs).reshape(self.env.E, -1).astype(np.float32), self.member)
+
+    def fitness(self, out):
+        """float64[G + 1] from a step_many result: per row the mean, over the envs that ran it, of the rewards the env collected in
+        the launch (slots it did not run count nothing); NaN for a row no env ran."""
+        ret = np.where(out["ran"], out["rew"], 0.0).sum(axis=0)
+        return np.array([ret[self.member == g].mean() if (self.member == g).any() else np.nan for g in range(self.G + 1)])
+
+    def coefficients(self, fitness, shaping="centered_rank"):
+        """es_coefficients of the G members' fitness (a [G + 1] vector's last entry, the centre's, is left out)."""
+        f = np.asarray(fitness, dtype=np.float64).reshape(-1)
+        if f.size == self.G + 1:
+            f = f[:self.G]
+        if f.size != self.G:
+            raise ValueError("fitness must hold %d (or %d) values" % (self.G, self.G + 1))
+        return es_coefficients(f, self.sigma, self.antithetic, shaping)
+
+    def gradient(self, fitness, shaping="centered_rank"):
+        """The evolution-strategies estimate of d E[fitness] / d theta as a float32 blob [n_params]: the coefficients on the host
+        (es_coefficients), their sum over this generation's eps on the device (ClothBatch.population_combine)."""
+        w = self.coefficients(fitness, shaping)
+        self._on_env()
+        return self.env.batch.population_combine(w)
+
+    def apply(self, delta):
+        """centre += delta (float32 [n_params], one float32 addition per parameter, on the host), then the next generation's rows."""
+        d = np.asarray(delta, dtype=np.float32).reshape(-1)
+        if d.size != self.n_params or not np.isfinite(d).all():
+            raise ValueError("delta must hold %d finite values" % self.n_params)
+        self._blob = (self._blob + d).astype(np.float32)
+        self.center = unpack_mlp(self.widths, self._blob)
+        self.perturb(self.generation + 1)

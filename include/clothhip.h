@@ -363,7 +363,8 @@ int clothhip_fused_supported(const clothhip_handle *h);
  * (csrc/cloth_policy_mlp.hpp), so the network is one function of the observation the caller would have seen, whatever stepper variant
  * runs. The call validates, uploads (the host blob is not retained) and replaces any earlier network; n_layers == 0 clears it.
  * CLOTHHIP_EINVAL: more than 4 layers, widths[0] != 3 P, a last width other than 4, a hidden width outside [1, 256], n_params not what
- * the widths give -- the earlier network then stays. The network belongs to the HANDLE, not to an env slot: every env evaluates it;
+ * the widths give -- the earlier network then stays. This network belongs to the HANDLE: every env evaluates it (one network per env
+ * slot: clothhip_set_policy_population below, which this call drops);
  * clothhip_fork, resets and clothhip_set_state never touch it. CLOTHHIP_ESTATE between clothhip_run_actions_begin and _end.
  * clothhip_run_actions* with CLOTHHIP_POLICY_MLP evaluates it once per action slot, when the slot begins (after an in-kernel reset: on the
  * new episode's first state), act = (double)y + actions[t][e] (`actions` optional there: the caller's exploration noise, NULL = none;
@@ -374,6 +375,44 @@ int clothhip_set_policy_mlp(clothhip_handle *h, int32_t n_layers, const int32_t 
  * E): actions_out[n][4], the network's output as doubles, no noise, not clipped -- the very device function the launch runs, one
  * workgroup per row, the rows in bounded chunks. CLOTHHIP_ESTATE without a network or with a launch in flight. Synchronous. */
 int clothhip_policy_eval(clothhip_handle *h, const float *obs_rows, int64_t n, double *actions_out);
+
+/* A POPULATION of networks, one per env slot (no reference counterpart: what evolution strategies, CEM over parameters, population-based
+ * training or ten checkpoints side by side need -- E cloths under E different networks in ONE episode launch). G blobs of one shape (the
+ * shape rules of clothhip_set_policy_mlp), params[G][n_params] on the host; the handle stores them at a stride of n_params rounded up to 64
+ * floats (every blob 256-byte aligned, the pad zeros) with the device table member[E], 0 <= member[e] < G: env slot e runs blob member[e].
+ * A cloth under blob g computes the bits a handle with g as its shared network computes (only a base pointer moves). The network belongs
+ * to the ENV SLOT, as the material does: uploads, clothhip_reset_flat, in-kernel resets and parked time-slice operations never touch it;
+ * clothhip_fork carries no networks. The shared network and a population replace each other: setting one drops the
+ * other; n_layers == 0 drops both. CLOTHHIP_EINVAL: the shape rules, G < 1, a member outside [0, G) -- the earlier network then stays (an
+ * allocation or upload that fails leaves the handle without one). */
+int clothhip_set_policy_population(clothhip_handle *h, int32_t n_layers, const int32_t *widths, const float *params, int32_t G,
+                                   const int32_t *member);
+/* the map alone: member[E], each in [0, rows) (rows = G, or G + 1 after clothhip_policy_population_perturb). CLOTHHIP_ESTATE without a population. */
+int clothhip_set_policy_members(clothhip_handle *h, const int32_t *member);
+/* download blob g (g = 0 for a shared network): out[n_params], n_params what the handle's widths give -- or, for a population, the row stride
+ * (n_params rounded up to 64), which gives the row's pad as well */
+int clothhip_get_policy_mlp(clothhip_handle *h, int64_t g, float *out, size_t n_params);
+/* clothhip_policy_eval with a network per row: row r is evaluated under blob members[r] (host int32 [n]); obs_rows == NULL: the handle's
+ * present state, n == E. The same kernel in the same chunks. On a shared-network handle the only blob is 0. The plain clothhip_policy_eval
+ * on a population handle is refused with CLOTHHIP_ESTATE: it cannot say which network a row means. */
+int clothhip_policy_eval_members(clothhip_handle *h, const float *obs_rows, int64_t n, const int32_t *members, double *actions_out);
+
+/* Make the population ON THE DEVICE (no reference counterpart; csrc/cloth_policy_population.hpp has the definition): G + 1 rows around the
+ * blob center[n_params] = theta. With CLOTHHIP_POP_ANTITHETIC (G even) rows 2k and 2k + 1 are theta + sigma eps_k and theta - sigma eps_k,
+ * without it row g is theta + sigma eps_g; row G is theta itself. eps_k[i] is a function of (seed, k, i) alone: Philox4x32-10 keyed by the
+ * two halves of seed on the counter (i_lo, i_hi, k, 0), the four words' top 24 bits summed and centred, times (float)(sqrt(3) / 2^24) --
+ * zero mean, unit variance, exactly symmetric, |eps| <= 3.47: the sum of four uniforms, NOT a Gaussian. A weight is
+ * (float)((double)theta[i] + (double)(+-sigma) * (double)eps). member[E], each in [0, G]. The handle remembers (seed, sigma, flags, G, theta).
+ * CLOTHHIP_EINVAL: the shape rules, G outside [1, 65534], odd G with the flag, unknown flags, a non-finite sigma, a member outside [0, G]
+ * -- the earlier network then stays. clothhip_last_kernel_ms gives the kernel's time. */
+enum { CLOTHHIP_POP_ANTITHETIC = 1 };
+int clothhip_policy_population_perturb(clothhip_handle *h, int32_t n_layers, const int32_t *widths, const float *center, int32_t G,
+                                       float sigma, uint64_t seed, int32_t flags, const int32_t *member);
+/* out[i] = (float) sum_{k ascending} (double)coef[k] * (double)eps_k[i], i < n_params, eps made again from the remembered seed: the
+ * evolution-strategies update without a second copy of the noise. K = G / 2 with the antithetic flag, G without; anything else is
+ * CLOTHHIP_EINVAL. CLOTHHIP_ESTATE without a population, or with one that was uploaded rather than generated. clothhip_last_kernel_ms
+ * gives the kernel's time. */
+int clothhip_policy_population_combine(clothhip_handle *h, const float *coef, int32_t K, float *out);
 int clothhip_run_actions(clothhip_handle *h, const ClothEpisodeParams *ep, int32_t T, int32_t policy,
                          const double *actions, int32_t actions_on_device, const int32_t *policy_arg,
                          const ClothResetScript *scripts, int32_t n_scripts, int32_t *num_steps, uint8_t *done,
