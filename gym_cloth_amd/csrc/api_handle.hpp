@@ -1,0 +1,118 @@
+// api_handle.hpp -- private to the api_*.hip units that implement include/clothhip.h: the handle, and the few helpers more than one of them calls.
+// Each group of fields below names the one unit that writes it; a field another unit reads is read directly.
+#pragma once
+#include <cstring>
+#include <vector>
+
+#include "cloth_common.hpp"
+#include "device_buffer.hpp"
+#include "layout_plan.hpp"
+
+using namespace clothhip;
+#pragma GCC visibility push(hidden)      // the handle and the shared helpers are private to the library: nothing here reaches its dynamic symbol table
+
+// The host fields (HostPlan: layout_plan.hpp) and everything the handle holds on its device. Each buffer frees itself; the stream and the
+// events are declared in front of the buffers, so they go after them.
+struct clothhip_handle : HostPlan {
+    int device = 0;
+    Stream stream;
+    Event ev0, ev1;
+    // clothhip_fork (api_state.hip): ev_fork orders a fork after the source handle's stream; the bytes of the ONE shared rest table as
+    // clothhip_set_state last uploaded them (handle precision, slot order) -- the only writer of a shared table, so two shared tables are
+    // equal exactly when these mirrors are; the device index lists of a fork
+    struct ForkScratch {
+        Event ev_fork;
+        std::vector<unsigned char> shared_rest;
+        Buffer<int32_t> d_fork_idx;
+        PinnedBuffer<int32_t> h_fork_idx;   // (pinned staging, so that the upload is a plain DMA)
+    } fork;
+    ~clothhip_handle() { (void)hipSetDevice(device); }
+    bool have_timing = false, pending_exec = false;
+    Buffer<void> d_pos, d_prev, d_rest;
+    Buffer<void> d_flat, d_flat_rest;   // flat tier-1 grid [3][Ppad] and its rest table [Spad] (window-table slot order), handle precision
+    Buffer<uint8_t> d_cnt, d_active;
+    int rest_stride = 0;
+    Buffer<int32_t> d_tear, d_exec, d_ngrab, d_stats;
+    Buffer<ClothSchedule> d_sched;
+    PinnedBuffer<ClothSchedule> h_sched;   // pinned staging
+    Buffer<uint32_t> d_gather, d_wt_ent;
+    Buffer<unsigned long long> d_wt_dep;
+    bool relaxed = false;   // clothhip_set_relaxed_order(h, 1): THIS handle's episode launches run the relaxed-order companion kernel (bench only, no parity)
+    // what the next stepper launch selects and what the last one ran (api_run.hip; clothhip_set_state and clothhip_fork set lean_dirty)
+    struct Launch {
+        bool lean_dirty = true, lean_ok = false;   // (HostPlan::lean: the shared rest table is checked whenever it may have changed)
+        int last_dispatches = 0; // kernel dispatches the last stepper launch was issued as (clothhip_last_dispatches)
+        int spec_now = 0;        // 25 / 50: the layout in use runs that grid-specialised build (decided by lean_refresh per launch: spec_ns); 0: the generic build
+        int last_spec = 0;       // what the last launch ran (clothhip_last_specialised)
+        float pal[3] = {0, 0, 0};
+        double pal64[3] = {0, 0, 0};     // fp64 LEAN build: the smallest rest length of each spring type (the others are it + a few ulps: StepArgs::lstc)
+        Buffer<uint4> d_lstc;            // [Ppad] fp64 LEAN build: per particle {stencil mask, 12 offset bytes}
+        int32_t last_variant[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // what the last launch ran (clothhip_last_variant)
+        bool have_variant = false;
+        bool on_lean = false;            // which of the two layouts runs now (lean_refresh)
+        struct OccKey { const void *fn; int lds; int occ; } occ_cache[8] = {};   // hipOccupancyMaxActiveBlocksPerMultiprocessor per (kernel, LDS bytes)
+    } launch;
+    const Layout &lay() const { return launch.on_lean ? lay_lean : lay_std; }
+    // per-env materials (clothhip_set_material): every env's effective values; how many differ bitwise from the handle's parameters (0: a uniform
+    // handle -- no table goes to the kernel, the grid-specialised builds stay eligible); the device's [E] DevConsts<T> table, allocated by the first set
+    std::vector<ClothMaterial> mat;
+    int n_mixed = 0;
+    Buffer<void> d_mat;
+    Buffer<double> d_levels, d_xy, d_radius, d_cov, d_vinv;
+    Buffer<uint8_t> d_oob;
+    Buffer<int32_t> d_hcnt;         // per env: #points with z < thickness/2 (height reward, cloth_env.py:1047-1073)
+    int n_grab_levels = 0;
+    // clothhip_run_actions staging (device), sized on demand: written by clothhip_run_actions_begin / _end alone (api_run.hip). Read elsewhere:
+    // f_pending (check_idle), f_T, f_nscr, f_obs, f_robs, d_fobs, d_frobs (clothhip_render_obs); d_resume is cleared by drop_in_flight* and clothhip_fork
+    struct EpisodeStaging {
+        Buffer<void> d_fz, d_fact, d_fscr, d_frec, d_frst, d_fobs, d_frobs;
+        Buffer<int32_t> d_fsteps, d_fparg;
+        Buffer<EpResume> d_resume;      // [E] operations cut by a time slice (clothhip_run_actions), continued by the next launch
+        Buffer<uint32_t> d_fmt;         // [E][MT_WORDS] numpy RandomState of every env (device-drawn resets)
+        Buffer<uint8_t> d_fdone;
+        Buffer<double> d_fsum;          // [E][4] per-env summary of the last episode launch (what the multi-GPU driver all-gathers)
+        Buffer<uint64_t> d_fticks;      // [E][8] per-operation-class ticks and update() counts of the last episode launch
+        int f_T = 0; size_t f_nscr = 0; bool f_pending = false, f_resets = false, f_obs = false, f_robs = false, f_mt = false;
+    } epi;
+    // clothhip_render_obs scratch (api_observe.hip) for ONE chunk of images, sized on demand: finished images (when the caller gives no device
+    // buffer), raw depth, uploaded '1d' rows, valid + swap flags
+    struct RenderScratch { Buffer<void> d_ro_img, d_ro_depth, d_ro_src, d_ro_flags; } ro;
+    std::vector<unsigned char> stage;   // host staging for layout conversion
+    std::vector<double> flat_rest;
+    // The policy network and its population (api_policy.hip); outside it only mlp is read: fill_fused copies it, clothhip_run_actions_begin asks
+    // whether a network exists.
+    struct Policy {
+        // clothhip_set_policy_mlp: the handle's network (n_layers 0: none; mlp.params = d_mlp) and clothhip_policy_eval's scratch for ONE chunk of rows
+        MlpDesc mlp = {};
+        Buffer<float> d_mlp, d_pe_rows;
+        Buffer<double> d_pe_out;
+        // clothhip_set_policy_population / clothhip_policy_population_perturb: pop_rows blobs at mlp.stride floats in d_pop (mlp.params = d_pop) and
+        // the env slots' map d_member (mlp.member; its host mirror pop_member). pop_rows 0: no population (a shared network counts as ONE row for
+        // clothhip_policy_eval_members and clothhip_get_policy_mlp). pop_generated: the rows were made from (pop_seed, pop_sigma, pop_flags) around row
+        // pop_rows - 1 = theta, so clothhip_policy_population_combine can make the same eps again
+        Buffer<float> d_pop, d_pop_center, d_pop_coef, d_pop_out;
+        Buffer<int32_t> d_member, d_pe_mem;
+        int64_t pop_rows = 0;
+        size_t mlp_n_params = 0;
+        bool pop_generated = false;
+        uint64_t pop_seed = 0;
+        float pop_sigma = 0.0f;
+        int32_t pop_flags = 0;
+    } pol;
+};
+
+// f(float{}) or f(double{}) by the handle's precision: a launch that exists in both precisions is written once, as a generic lambda
+template <typename F> static auto by_precision(const clothhip_handle *h, F &&f) { return h->precision == CLOTHHIP_F64 ? f(double{}) : f(float{}); }
+
+// The helpers more than one unit calls, each defined in the unit named
+namespace clothhip {
+int check_params(const ClothParams *p);                                                          // api_core.hip
+int check_idle(const clothhip_handle *h);
+int check_material(const ClothParams &prm, const ClothMaterial &m, int idx);                     // api_state.hip
+SpecPhys phys_of(const ClothParams &p);
+SpecPhys phys_of(const ClothParams &p, const ClothMaterial &m);
+ClothMaterial material_of(const ClothParams &p);
+int drop_in_flight(clothhip_handle *h, const uint8_t *d_mask, const ClothSchedule *d_sched);
+int plan_steppers(clothhip_handle *h);                                                           // api_run.hip, for clothhip_create
+}  // namespace clothhip
+#pragma GCC visibility pop

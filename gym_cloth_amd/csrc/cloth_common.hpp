@@ -338,7 +338,7 @@ template <typename T, int NS = 0> __device__ __forceinline__ DevConsts<T> load_c
 // count, hash-table size, window-table size, the whole LDS carve-up, "all phases on", whether the cell-ordered copy exists -- so none of it occupies
 // registers across the substep loop (the generic build holds ~30 loop-invariant VGPRs of LDS base addresses and constants: headline +1.9 %, the
 // six-per-CU build +3.3 %). NS = 0 is the generic build (any grid, debug phase masks). The host picks the specialised kernel only when every constant
-// below equals what it computed for the handle (clothhip_api.hip::spec_ns); the names are used inside the kernel body, where NS and the Variant V are in scope.
+// below equals what it computed for the handle (api_run.hip::spec_ns); the names are used inside the kernel body, where NS and the Variant V are in scope.
 constexpr int spec_p(int ns) { return ns * ns; }
 constexpr int spec_ppad(int ns) { return (ns * ns + 63) / 64 * 64; }
 // hash-table slots: the smallest power of two above 1.5 P -- except the two-cloths-per-CU layout of 50x50, whose table is sized to the LDS left
@@ -407,9 +407,31 @@ struct LdsLayout {
         total = o;
     }
 };
-// the carve-up of variant v: the one place a Variant becomes an LdsLayout (kernel, and the host's plan: clothhip_api.hip)
+// the carve-up of variant v: the one place a Variant becomes an LdsLayout (kernel, and the host's plan: layout_plan.hpp)
 __host__ __device__ __forceinline__ LdsLayout lds_layout(Variant v, int Ppad, int Spad, int HT, int cell_copy) {
     return LdsLayout(v.tsz, Ppad, Spad, HT, v.lds_table_mode(), cell_copy, v.lean64() ? 1 : 0);
+}
+
+// LEAN variant (Variant::lean): the 12-slot gather stencil of a particle is recomputed from its grid position
+// instead of being held in 36 registers, and rest lengths come from a three-value palette instead of 36 more: the stepper is then
+// compiled for 168 VGPRs (three cloths share a CU) down to 80 (six). Position k of the stencil = the k-th incident spring in ascending list index when
+// all twelve exist (cloth.pyx:134-146: the six springs the point owns, then those its later neighbours own):
+//   k      0    1    2      3      4     5    6   7    8      9    10     11
+//   nbr   -N   -1   -N-1   -N+1   -2N   -2   +1  +2   +N-1   +N   +N+1   +2N      (index i = r*N + c)
+//   type   S    S    Sh     Sh     B     B    S   B    Sh     S    Sh     B
+// (the host checks this against the gather table it builds from the reference's spring list before choosing the variant).
+__host__ __device__ __forceinline__ int lean_off(int k, int N) {
+    switch (k) {
+        case 0: return -N; case 1: return -1; case 2: return -N - 1; case 3: return -N + 1; case 4: return -2 * N; case 5: return -2;
+        case 6: return 1; case 7: return 2; case 8: return N - 1; case 9: return N; case 10: return N + 1; default: return 2 * N;
+    }
+}
+__host__ __device__ constexpr bool lean_bend(int k) { return k == 4 || k == 5 || k == 7 || k == 11; }
+__host__ __device__ constexpr bool lean_shear(int k) { return k == 2 || k == 3 || k == 8 || k == 10; }
+__host__ __device__ inline uint32_t lean_valid_mask(int r, int c, int N) {
+    const bool u1 = r >= 1, u2 = r >= 2, d1 = r + 1 < N, d2 = r + 2 < N, l1 = c >= 1, l2 = c >= 2, r1 = c + 1 < N, r2 = c + 2 < N;
+    return (u1 ? 1u : 0u) | (l1 ? 2u : 0u) | ((u1 && l1) ? 4u : 0u) | ((u1 && r1) ? 8u : 0u) | (u2 ? 16u : 0u) | (l2 ? 32u : 0u) |
+           (r1 ? 64u : 0u) | (r2 ? 128u : 0u) | ((d1 && l1) ? 256u : 0u) | (d1 ? 512u : 0u) | ((d1 && r1) ? 1024u : 0u) | (d2 ? 2048u : 0u);
 }
 
 // Accumulators of the profiling / census builds (per-phase cycles, counters): in LDS, written by thread 0 alone -- as twelve 64-bit

@@ -21,7 +21,7 @@
 //                                             predecessors in the window (static per-slot dependency masks) is over-stretched
 // DESIGN.md section 4 has the exactness argument of every phase.
 // The code is split by phase: cloth_common.hpp (shared types and wave primitives), phase_strain.hpp, phase_collide.hpp,
-// cloth_metrics.hpp, episode_loop.hpp (k_run_schedule), cloth_aux_kernels.hpp.
+// cloth_metrics.hpp, episode_loop.hpp (k_run_schedule); the small kernels around the stepper are with the api_*.hip unit that launches them.
 #pragma once
 
 #include "cloth_common.hpp"
@@ -29,4 +29,3 @@
 #include "phase_collide.hpp"
 #include "cloth_metrics.hpp"
 #include "episode_loop.hpp"
-#include "cloth_aux_kernels.hpp"

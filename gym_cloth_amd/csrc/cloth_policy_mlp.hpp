@@ -1,6 +1,6 @@
 // cloth_policy_mlp.hpp -- a small fully-connected policy network over the '1d' observation (no reference counterpart: the policy kind a
 // learner brings), evaluated by ONE device function that the episode launch (episode_plan.inc.hpp, CLOTHHIP_POLICY_MLP) and the stand-alone
-// kernel (k_policy_eval in clothhip_api.hip, behind clothhip_policy_eval) share, so the host loop and the launch compute the same bits.
+// kernel (k_policy_eval in cloth_policy_eval.hpp, behind clothhip_policy_eval) share, so the host loop and the launch compute the same bits.
 // One network for all cloths, or one per env slot out of a population of blobs (MlpDesc::member; cloth_policy_population.hpp makes one).
 //
 //   L weight layers (1 <= L <= MLP_MAX_LAYERS), widths[0] = 3 P (the observation), widths[L] = 4 (the action), hidden widths in

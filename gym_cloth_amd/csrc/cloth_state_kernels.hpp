@@ -1,9 +1,8 @@
-// cloth_aux_kernels.hpp -- the small kernels around the stepper: Gripper.grab_top / grab (gripper.pyx:23-53), release, observation and
-// metrics read-back, flat reset, self-tests.
+// cloth_state_kernels.hpp -- the small kernels that change a handle's state from outside the stepper (api_state.hip, which alone includes this):
+// Gripper.grab_top / grab (gripper.pyx:23-53), release, flat reset, dropping parked time-slice operations, forks.
 #pragma once
 
 #include "cloth_common.hpp"
-#include "cloth_metrics.hpp"
 
 namespace clothhip {
 
@@ -65,33 +64,6 @@ __global__ void k_release(uint8_t *cnt, const uint8_t *active, int Ppad) {
     if (active && !active[e]) return;
     uint8_t *c = cnt + (size_t)e * Ppad;
     for (int i = threadIdx.x; i < Ppad; i += blockDim.x) if (c[i] & CNT_GRAB_MASK) c[i] = 0;
-}
-
-// '1d' observation (cloth_env.py:196-200) as float32 [E][3P], from SoA device state
-template <typename T> __global__ void k_write_obs(const T *pos, float *out, int P, int Ppad) {
-    const int e = blockIdx.x;
-    const T *p = pos + (size_t)e * 3 * Ppad;
-    float *o = out + (size_t)e * 3 * P;
-    for (int t = threadIdx.x; t < 3 * P; t += blockDim.x) {
-        const int i = t / 3, ax = t - 3 * i;
-        o[t] = (float)p[ax * Ppad + i];
-    }
-}
-
-// ---- per-env metrics kernel: one 256-thread workgroup per env over the SoA state in HBM (metrics_block above)
-template <typename T>
-__global__ __launch_bounds__(256) void k_metrics(const T *pos, int P, int Ppad, int NS, int NH, double *cov, double *vinv, uint8_t *oob,
-                                                 int32_t *hcnt, double half_thick) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int e = blockIdx.x;
-    const T *px = pos + (size_t)e * 3 * Ppad, *py = px + Ppad, *pz = py + Ppad;
-    auto src = [&](int i, double &x, double &y, double &z) { x = (double)px[i]; y = (double)py[i]; z = (double)pz[i]; };
-    double out[4];
-    metrics_block<256, T>(src, P, NS, NH, smem, (int)threadIdx.x, half_thick, out);
-    if (threadIdx.x == 0) {
-        cov[e] = out[0]; vinv[e] = out[1]; oob[e] = out[2] != 0.0 ? 1 : 0;
-        if (hcnt) hcnt[e] = (int32_t)out[3];
-    }
 }
 
 // Cloth(...) rebuilt on reset (cloth_env.py:737-746) for the flat tiers 1/3: masked envs <- the flat grid (pos = prev),
@@ -179,17 +151,6 @@ __global__ __launch_bounds__(256) void k_fork(ForkArgs A) {
 // A handle that leaves its one shared rest table for per-env tables: rows 1 .. E-1 <- row 0 (one workgroup per row)
 __global__ __launch_bounds__(256) void k_replicate_rest(unsigned char *rest, size_t row_bytes) {
     fork_copy(rest + ((size_t)blockIdx.x + 1) * row_bytes, rest, row_bytes);
-}
-
-__global__ void k_selftest(int op, const double *a, const double *b, double *out, long long n) {
-    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    double x = a[i], y = b ? b[i] : 0.0, r;
-    if (op == 0) r = x / y;
-    else if (op == 1) r = sqrt(x);
-    else if (op == 2) r = x * y + y;
-    else r = floor(x / y);
-    out[i] = r;
 }
 
 }  // namespace clothhip

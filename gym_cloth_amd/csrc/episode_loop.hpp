@@ -18,28 +18,6 @@ namespace clothhip {
 //   FUSED: 0 = one externally decoded schedule per env (clothhip_run); 1 = whole episodes per launch (clothhip_run_actions)
 //          with the resets of the flat tiers 1 and 3; 2 = also tier-2 resets. (The tier-2 reset code is cold, but its presence
 //          costs the substep loop registers: -7 % on the headline workload, so it is compiled in only where it is asked for.)
-// LEAN variant (Variant::lean): the 12-slot gather stencil of a particle is recomputed from its grid position
-// instead of being held in 36 registers, and rest lengths come from a three-value palette instead of 36 more: the stepper is then
-// compiled for 168 VGPRs (three cloths share a CU) down to 80 (six). Position k of the stencil = the k-th incident spring in ascending list index when
-// all twelve exist (cloth.pyx:134-146: the six springs the point owns, then those its later neighbours own):
-//   k      0    1    2      3      4     5    6   7    8      9    10     11
-//   nbr   -N   -1   -N-1   -N+1   -2N   -2   +1  +2   +N-1   +N   +N+1   +2N      (index i = r*N + c)
-//   type   S    S    Sh     Sh     B     B    S   B    Sh     S    Sh     B
-// (the host checks this against the gather table it builds from the reference's spring list before choosing the variant).
-__host__ __device__ __forceinline__ int lean_off(int k, int N) {
-    switch (k) {
-        case 0: return -N; case 1: return -1; case 2: return -N - 1; case 3: return -N + 1; case 4: return -2 * N; case 5: return -2;
-        case 6: return 1; case 7: return 2; case 8: return N - 1; case 9: return N; case 10: return N + 1; default: return 2 * N;
-    }
-}
-__host__ __device__ constexpr bool lean_bend(int k) { return k == 4 || k == 5 || k == 7 || k == 11; }
-__host__ __device__ constexpr bool lean_shear(int k) { return k == 2 || k == 3 || k == 8 || k == 10; }
-__host__ __device__ inline uint32_t lean_valid_mask(int r, int c, int N) {
-    const bool u1 = r >= 1, u2 = r >= 2, d1 = r + 1 < N, d2 = r + 2 < N, l1 = c >= 1, l2 = c >= 2, r1 = c + 1 < N, r2 = c + 2 < N;
-    return (u1 ? 1u : 0u) | (l1 ? 2u : 0u) | ((u1 && l1) ? 4u : 0u) | ((u1 && r1) ? 8u : 0u) | (u2 ? 16u : 0u) | (l2 ? 32u : 0u) |
-           (r1 ? 64u : 0u) | (r2 ? 128u : 0u) | ((d1 && l1) ? 256u : 0u) | (d1 ? 512u : 0u) | ((d1 && r1) ? 1024u : 0u) | (d2 ? 2048u : 0u);
-}
-
 // NS: 0 = any grid (sizes from the kernel arguments); 25 / 50 = a BASELINE grid known at compile time (cloth_common.hpp: spec_*)
 template <typename T, int NT, int PPT, int TAB, bool REST_REG, int FUSED, int NS = 0>
 __global__ __launch_bounds__(NT, (Variant{(int)sizeof(T), NT, PPT, TAB, REST_REG}.waves_per_eu())) void k_run_schedule(StepArgs<T> A) {

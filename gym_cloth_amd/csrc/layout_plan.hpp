@@ -5,10 +5,16 @@
 #include <climits>
 #include <cstdlib>
 
-#include "stepper_variants.hpp"
+#include "cloth_common.hpp"
+#include "cloth_tables.hpp"
 #include "lean_rates.hpp"
 
 namespace clothhip {
+// What a stepper launch runs: the variant (stepper_traits.hpp) and its LDS
+// carve-up (plan_layouts). scratch_have / scratch_need: the LDS behind the hash table that the in-kernel metrics of
+// the episode launches borrow, and what they need.
+struct Layout { Variant v; int cell_copy, lds_bytes, HT, ht_bits, scratch_have, scratch_need; };
+
 // metrics_block (cloth_metrics.hpp) for a grid of P points: it sorts NS values (the next power of two >= P) and its hull's monotone chain holds
 // at most m + 1 <= P + 1 points (NH)
 struct MetricsDims { int NS, NH; };
@@ -119,7 +125,7 @@ template <typename F> static int walk_stencil(const HostPlan *h, int i, F &&body
 // lay_lean, lean and lean_r.
 // max_r: the highest residency the pick may choose (clothhip_create lowers it when the device's occupancy query grants the chosen LEAN
 // build fewer workgroups per CU than it was planned for).
-static void plan_layouts(HostPlan *h, int cus, int max_r = 6) {
+static inline void plan_layouts(HostPlan *h, int cus, int max_r = 6) {
     const DebugKnobs &dbg = h->dbg;
     const int tsz = (int)h->tsz, precision = h->precision;
     // threads per cloth x particles per thread (compile-time variants of the stepper)
@@ -231,7 +237,7 @@ static void plan_layouts(HostPlan *h, int cus, int max_r = 6) {
 
 // The host fields of a handle -- grid, topology, window and gather tables, debug switches: nothing here touches a device (clothhip_create,
 // and clothhip_selftest_layout, which plans on a HostPlan that is no handle)
-static void init_host_fields(HostPlan *h, const ClothParams &p, int n_envs, int precision) {
+static inline void init_host_fields(HostPlan *h, const ClothParams &p, int n_envs, int precision) {
     h->prm = p; h->E = n_envs; h->precision = precision;
     h->N = p.n_side; h->P = h->N * h->N; h->Ppad = (h->P + 63) / 64 * 64;
     h->tsz = precision == CLOTHHIP_F64 ? 8 : 4;
@@ -243,7 +249,7 @@ static void init_host_fields(HostPlan *h, const ClothParams &p, int n_envs, int 
 }
 
 // Every layout the handle may run (the standard one always; the LEAN one while its palette holds) holds the in-kernel metrics' scratch
-static bool fused_supported(const HostPlan &h) {
+static inline bool fused_supported(const HostPlan &h) {
     return h.lay_std.scratch_have >= h.lay_std.scratch_need && (!h.lean || h.lay_lean.scratch_have >= h.lay_lean.scratch_need);
 }
 }  // namespace clothhip

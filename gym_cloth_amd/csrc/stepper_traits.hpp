@@ -1,6 +1,6 @@
 // stepper_traits.hpp -- what ONE compile-time variant of the stepper kernel (episode_loop.hpp: k_run_schedule<T, NT, PPT, TAB, REST_REG, ...>) is:
 // the names of the TAB codes and the questions kernel and host ask about a variant, each answered in one place. The kernel forms
-// `static constexpr Variant V{sizeof(T), NT, PPT, TAB, REST_REG}` once; the host keeps the same value in Layout / StepperRow (stepper_variants.hpp).
+// `static constexpr Variant V{sizeof(T), NT, PPT, TAB, REST_REG}` once; the host keeps the same value in Layout (layout_plan.hpp) / StepperRow (stepper_variants.hpp).
 #pragma once
 
 namespace clothhip {

@@ -2,7 +2,7 @@
 // the table the host picks them from.
 //
 // The library has 100 instantiations of one kernel template; compiled in one translation unit they took three minutes. They are split into
-// GROUPS, one object file each (stepper_inst.hip compiled with -DCLOTHHIP_INST_GROUP=g, in parallel by make); clothhip_api.hip sees them as
+// GROUPS, one object file each (stepper_inst.hip compiled with -DCLOTHHIP_INST_GROUP=g, in parallel by make); api_run.hip sees them as
 // `extern template` declarations and only takes their addresses, through STEPPER_ROWS / find_stepper below (a kernel launch across
 // translation units needs no relocatable device code: the host stub is an ordinary symbol, the device code is registered by the object that
 // defines it).
@@ -13,7 +13,7 @@
 #include "episode_loop.hpp"
 
 // standard arithmetic: the 25x25 class, then the large grids. Rest lengths in registers and the 1024 x 4 variant are fp32 only: the plan
-// (clothhip_api.hip: plan_layouts) keeps REST_REG to fp32, and fp64 grids of more than 3 072 points exceed the CU's LDS.
+// (layout_plan.hpp: plan_layouts) keeps REST_REG to fp32, and fp64 grids of more than 3 072 points exceed the CU's LDS.
 #define CLOTH_VARIANTS_SMALL_F32(X) X(float, 512, 2, 1, false) X(float, 512, 2, 0, false) X(float, 256, 3, 1, true) X(float, 256, 3, 1, false) X(float, 256, 3, 0, false)
 #define CLOTH_VARIANTS_SMALL_F64(X) X(double, 512, 2, 1, false) X(double, 512, 2, 0, false) X(double, 256, 3, 1, false) X(double, 256, 3, 0, false)
 #ifdef CLOTHHIP_FAST_BUILD           // development builds: the 25x25-class variants only (make fast)
@@ -74,17 +74,12 @@
 #define CLOTH_GROUP_5(M) CLOTH_VARIANTS_LEAN_LARGE(M, float) CLOTH_VARIANTS_LEAN64(M, double)
 #define CLOTH_RELAXED(KW) KW template __global__ void clothhip::k_run_schedule<float, 512, 2, 2, true, 3>(clothhip::StepArgs<float>);
 
-#ifndef CLOTHHIP_INST_GROUP          // a user of the kernels (clothhip_api.hip): nothing is instantiated here
+#ifndef CLOTHHIP_INST_GROUP          // the user of the kernels (api_run.hip): nothing is instantiated here
 CLOTH_GROUP_0(CLOTH_DECL) CLOTH_GROUP_1(CLOTH_DECL) CLOTH_GROUP_2(CLOTH_DECL) CLOTH_GROUP_3(CLOTH_DECL) CLOTH_GROUP_4(CLOTH_DECL) CLOTH_GROUP_5(CLOTH_DECL)
 CLOTH_SPEC_F32(CLOTH_DECL_S) CLOTH_SPEC_F64(CLOTH_DECL_S)
 CLOTH_RELAXED(extern)
 
 namespace clothhip {
-// What a stepper launch runs: the variant (stepper_traits.hpp) and its LDS
-// carve-up (clothhip_api.hip: plan_layouts). scratch_have / scratch_need: the LDS behind the hash table that the in-kernel metrics of
-// the episode launches borrow, and what they need.
-struct Layout { Variant v; int cell_copy, lds_bytes, HT, ht_bits, scratch_have, scratch_need; };
-
 // Every instantiation above as one row {Variant{sizeof(T), NT, PPT, TAB, REST_REG}, NS, FUSED, kernel}: the only place the host names a kernel.
 struct StepperRow { Variant v; int ns, fused; const void *fn; };
 #define CLOTH_ROW(T, NT, PPT, TAB, RR, NS_, F) {{(int)sizeof(T), NT, PPT, TAB, RR}, NS_, F, (const void *)k_run_schedule<T, NT, PPT, TAB, RR, F, NS_>},

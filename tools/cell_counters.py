@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """Counters of the self-collision phase over the bench workload (dev tool, GPU box). Needs the counter build:
-    cd gym_cloth_amd/csrc && hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -DCLOTHHIP_CELL_COUNTERS \
-        -shared -o ../libclothhip_cnt.so clothhip_api.hip
+    make -C gym_cloth_amd/csrc cnt      (-DCLOTHHIP_CELL_COUNTERS: the api_*.hip units and the stepper objects -> libclothhip_cnt.so)
     CLOTHHIP_LIB=$PWD/gym_cloth_amd/libclothhip_cnt.so python tools/cell_counters.py
 Wave 0 of every cloth counts what IT did (about a quarter of the cells): big cells (> 16 members) swept, their members and
 visits, small-cell tickets (up to four cells each), the pre-check's trip bound, active / occupied cells."""
