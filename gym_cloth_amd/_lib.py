@@ -78,6 +78,7 @@ OBS_STATE, OBS_SLOTS, OBS_RESETS, OBS_HOST = 0, 1, 2, 3                 # ... an
 OBS_SOURCES = {'state': OBS_STATE, 'slots': OBS_SLOTS, 'resets': OBS_RESETS, 'host': OBS_HOST}
 
 POLICY_TABLE, POLICY_ORACLE_CORNER, POLICY_HIGHEST_POINT, POLICY_MLP = 0, 1, 2, 3
+EXPERTS = {'oracle_corner': POLICY_ORACLE_CORNER, 'highest_point': POLICY_HIGHEST_POINT}   # clothhip_run_actions_expert / clothhip_policy_label
 MLP_MAX_LAYERS, MLP_MAX_WIDTH = 4, 256   # clothhip_set_policy_mlp (csrc/cloth_policy_mlp.hpp)
 POP_ANTITHETIC = 1                       # clothhip_policy_population_perturb flags (csrc/cloth_policy_population.hpp)
 POP_ROW_ALIGN, POP_MAX_G = 64, 65534     # floats a population's row stride is rounded up to; the most perturbations of one call
@@ -144,6 +145,9 @@ SYMBOLS = [
     ("clothhip_policy_population_perturb", C.c_int, [_vp, C.c_int32, _i32p, C.POINTER(C.c_float), C.c_int32, C.c_float, C.c_uint64,
                                                      C.c_int32, _i32p]),
     ("clothhip_policy_population_combine", C.c_int, [_vp, C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_float)]),
+    ("clothhip_run_actions_expert", C.c_int, [_vp, C.c_int32, C.c_int32, _u8p, _i32p]),
+    ("clothhip_run_actions_labels", C.c_int, [_vp, _dp, C.POINTER(_vp)]),
+    ("clothhip_policy_label", C.c_int, [_vp, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_int64, _i32p, _i32p, _dp]),
     ("clothhip_update", C.c_int, [_vp, C.c_int32, _dp]),
     ("clothhip_metrics", C.c_int, [_vp, _dp, _dp, _u8p, _u8p]),
     ("clothhip_metrics_ex", C.c_int, [_vp, _dp, _dp, _u8p, _u8p, _i32p]),

@@ -344,10 +344,15 @@ class ClothBatch(object):
 
     def run_actions_begin(self, ep, n_actions, num_steps, done, actions=None, policy=None, policy_arg=None, scripts=None,
                           want_resets=True, want_obs=False, actions_device_ptr=None, time_budget_ms=0.0,
-                          rng_states=None, rng_tier=0, domrand_words=0, reset_capacity=0):
+                          rng_states=None, rng_tier=0, domrand_words=0, reset_capacity=0, expert=None, expert_mix=None,
+                          expert_choices=None):
         """First half of clothhip_run_actions (see include/clothhip.h): upload + launch, returns while the kernel runs.
-        ep: _lib.ClothEpisodeParams; scripts: RESET_SCRIPT_DTYPE[E, R], each env's next R resets in order."""
+        ep: _lib.ClothEpisodeParams; scripts: RESET_SCRIPT_DTYPE[E, R], each env's next R resets in order.
+        expert ('oracle_corner' | 'highest_point' or its CLOTHHIP_POLICY_* code) arms this launch with a silent expert
+        (clothhip_run_actions_expert): expert_mix bool[T, E] (None: it never acts), expert_choices int[T, E] (highest point);
+        run_actions_labels() gives its labels after run_actions_end()."""
         T = int(n_actions)
+        mix, cho = self._expert_tables(expert, expert_mix, expert_choices, T)
         pol = _lib.POLICY_TABLE if policy is None else int(policy)
         on_dev = 0
         ap = None
@@ -379,6 +384,8 @@ class ClothBatch(object):
         have_rst = bool(want_resets and have_src)
         have_robs = bool(want_obs and have_src)
         vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        if expert is not None:                           # (the library copies both tables; the arming is for the very next launch alone)
+            check(self._L.clothhip_run_actions_expert(self._h, _lib.EXPERTS.get(expert, expert), T, _lib.u8p(mix), _lib.i32p(cho)))
         check(self._L.clothhip_run_actions_begin(self._h, C.byref(ep), T, pol, ap, on_dev, _lib.i32p(parg), vp(scripts), R,
                                                  _lib.i32p(num_steps), _lib.u8p(done), vp(rng_states), int(rng_tier),
                                                  int(domrand_words), int(have_rst), int(bool(want_obs)), int(have_robs),
@@ -401,6 +408,68 @@ class ClothBatch(object):
         check(self._L.clothhip_run_actions_end(self._h, _lib.i32p(num_steps), _lib.u8p(done), vp(rec), vp(rst), vp(obs),
                                                vp(robs), vp(rng_states)))
         return rec, rst, obs, robs
+
+    def _expert_tables(self, expert, expert_mix, expert_choices, T):
+        """(mix uint8[T, E] or None, choices int32[T, E] or None) as clothhip_run_actions_expert takes them. ValueError for an unknown
+        expert, tables without an expert, a wrong shape, and expert_choices with or without expert='highest_point' as it must not / must be."""
+        if expert is None:
+            if expert_mix is not None or expert_choices is not None:
+                raise ValueError("expert_mix / expert_choices go with expert='oracle_corner' or 'highest_point'")
+            return None, None
+        code = _lib.EXPERTS.get(expert, expert)
+        if code not in _lib.EXPERTS.values():
+            raise ValueError("expert must be None, 'oracle_corner' or 'highest_point' (got %r)" % (expert,))
+        mix = cho = None
+        if expert_mix is not None:
+            mix = np.asarray(expert_mix)
+            if mix.shape != (T, self.E):
+                raise ValueError("expert_mix must have shape (%d, %d) (got %r)" % (T, self.E, mix.shape))
+            mix = np.ascontiguousarray(mix != 0, dtype=np.uint8)
+        if (expert_choices is not None) != (code == _lib.POLICY_HIGHEST_POINT):
+            raise ValueError("expert_choices int[T, E] goes with expert='highest_point', and only with it")
+        if expert_choices is not None:
+            cho = np.asarray(expert_choices)
+            if cho.shape != (T, self.E) or not np.issubdtype(cho.dtype, np.integer):
+                raise ValueError("expert_choices must be integers of shape (%d, %d)" % (T, self.E))
+            cho = np.ascontiguousarray(cho, dtype=np.int32)
+        return mix, cho
+
+    def run_actions_labels(self, n_actions=None):
+        """float64[T, E, 4]: the expert's labels of the last, armed episode launch (clothhip_run_actions_labels), NaN where the slot's
+        `ran` is 0. ClothHipError when that launch was not armed."""
+        T = int(self._last_launch[0] if n_actions is None else n_actions)
+        out = np.zeros((T, self.E, 4), dtype=np.float64)
+        check(self._L.clothhip_run_actions_labels(self._h, _lib.dp(out), None))
+        return out
+
+    def policy_label(self, expert, obs=None, side=None, choices=None, clip_act_space=True):
+        """The analytic expert ('oracle_corner' | 'highest_point') on float32 '1d' observations obs [n, 3P], or with obs=None on every
+        env's present state: float64 [n, 4], what an episode launch with that policy records as its action (unclipped; in clip space
+        with clip_act_space) -- clothhip_policy_label. side int[n]: 0 flat tiers, 1 / 2 tier 2 with init_side False / True (None: 0);
+        choices int[n]: which of the highest points."""
+        code = _lib.EXPERTS.get(expert, expert)
+        if code not in _lib.EXPERTS.values():
+            raise ValueError("expert must be 'oracle_corner' or 'highest_point' (got %r)" % (expert,))
+        if obs is None:
+            n, ptr = self.E, None
+        else:
+            obs = np.ascontiguousarray(obs, dtype=np.float32)
+            if obs.ndim != 2 or obs.shape[1] != 3 * self.P:
+                raise ValueError("obs must have shape (n, %d)" % (3 * self.P))
+            n, ptr = obs.shape[0], self._fp(obs)
+        tabs = []
+        for name, a in (('side', side), ('choices', choices)):
+            if a is not None:
+                a = np.asarray(a)
+                if a.shape != (n,):
+                    raise ValueError("%s must have shape (%d,)" % (name, n))
+                a = np.ascontiguousarray(a, dtype=np.int32)
+            tabs.append(a)
+        if (tabs[1] is not None) != (code == _lib.POLICY_HIGHEST_POINT):
+            raise ValueError("choices int[n] goes with expert='highest_point', and only with it")
+        out = np.zeros((n, 4), dtype=np.float64)
+        check(self._L.clothhip_policy_label(self._h, code, int(bool(clip_act_space)), ptr, n, _lib.i32p(tabs[0]), _lib.i32p(tabs[1]), _lib.dp(out)))
+        return out
 
     def run_summary(self):
         """float64[E, 4] written by the last episode launch: actions executed, episode over, coverage after the env's last

@@ -73,6 +73,16 @@ struct clothhip_handle : HostPlan {
         Buffer<double> d_fsum;          // [E][4] per-env summary of the last episode launch (what the multi-GPU driver all-gathers)
         Buffer<uint64_t> d_fticks;      // [E][8] per-operation-class ticks and update() counts of the last episode launch
         int f_T = 0; size_t f_nscr = 0; bool f_pending = false, f_resets = false, f_obs = false, f_robs = false, f_mt = false;
+        // the expert beside the acting policy: what clothhip_run_actions_expert armed for the NEXT launch (host copies of its tables), the
+        // armed launch's device tables, and whether the last launch was armed (f_labels: clothhip_run_actions_labels, and the label an action
+        // cut by its time slice carries over)
+        int arm_expert = 0, arm_T = 0;
+        bool arm_mix = false, f_labels = false;
+        std::vector<uint8_t> h_arm_mix;
+        std::vector<int32_t> h_arm_choice;
+        Buffer<double> d_flab;
+        Buffer<uint8_t> d_fmix;
+        Buffer<int32_t> d_fchoice;
     } epi;
     // clothhip_render_obs scratch (api_observe.hip) for ONE chunk of images, sized on demand: finished images (when the caller gives no device
     // buffer), raw depth, uploaded '1d' rows, valid + swap flags
@@ -86,6 +96,7 @@ struct clothhip_handle : HostPlan {
         MlpDesc mlp = {};
         Buffer<float> d_mlp, d_pe_rows;
         Buffer<double> d_pe_out;
+        Buffer<int32_t> d_pl_side, d_pl_choice;   // clothhip_policy_label's per-row tables for ONE chunk (rows and results share d_pe_rows / d_pe_out)
         // clothhip_set_policy_population / clothhip_policy_population_perturb: pop_rows blobs at mlp.stride floats in d_pop (mlp.params = d_pop) and
         // the env slots' map d_member (mlp.member; its host mirror pop_member). pop_rows 0: no population (a shared network counts as ONE row for
         // clothhip_policy_eval_members and clothhip_get_policy_mlp). pop_generated: the rows were made from (pop_seed, pop_sigma, pop_flags) around row

@@ -1,10 +1,12 @@
-// api_policy.hip -- a learned policy on the handle: the network, a population of networks, their stand-alone evaluation.
+// api_policy.hip -- a learned policy on the handle: the network, a population of networks, their stand-alone evaluation; the analytic experts' stand-alone labelling.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 
 #include "api_handle.hpp"
 #include "cloth_policy_eval.hpp"
+#include "cloth_policy_label.hpp"
 #include "cloth_policy_population.hpp"
 
 // ---- a learned policy: the handle's network (cloth_policy_mlp.hpp) ----------------------------------------------------------------------
@@ -226,4 +228,63 @@ extern "C" int clothhip_policy_eval_members(clothhip_handle *h, const float *obs
     if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
     if (!members && n > 0) return fail(CLOTHHIP_EINVAL, "members is NULL");
     return policy_eval_rows(h, obs_rows, n, members, actions_out);
+}
+
+// ---- the analytic experts on stored observations or on the present state (cloth_policy_label.hpp) -----------------------------------------
+extern "C" int clothhip_policy_label(clothhip_handle *h, int32_t expert, int32_t clip_act_space, const float *obs_rows, int64_t n,
+                                     const int32_t *side, const int32_t *choice, double *actions_out) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (expert != CLOTHHIP_POLICY_ORACLE_CORNER && expert != CLOTHHIP_POLICY_HIGHEST_POINT)
+        return fail(CLOTHHIP_EINVAL, "unknown expert %d (CLOTHHIP_POLICY_ORACLE_CORNER or CLOTHHIP_POLICY_HIGHEST_POINT)", expert);
+    if (n < 0) return fail(CLOTHHIP_EINVAL, "n < 0");
+    if (!obs_rows && n != h->E) return fail(CLOTHHIP_EINVAL, "n = %lld, the handle's state holds %d cloths", (long long)n, h->E);
+    if (expert == CLOTHHIP_POLICY_HIGHEST_POINT && !choice && n > 0) return fail(CLOTHHIP_EINVAL, "the highest-point expert needs choice[n]: which of the highest points per row");
+    if (!actions_out && n > 0) return fail(CLOTHHIP_EINVAL, "actions_out is NULL");
+    if (int rc = check_idle(h)) return rc;
+    if (expert == CLOTHHIP_POLICY_ORACLE_CORNER && h->N != 25)
+        return fail(CLOTHHIP_ESTATE, "the oracle-corner policy is defined for 25x25 cloths only (analytic.py:106)");
+    if (n == 0) return 0;
+    HIPCHECK(hipSetDevice(h->device));
+    const bool hp = expert == CLOTHHIP_POLICY_HIGHEST_POINT;
+    const size_t row = (size_t)3 * h->P, chunk = policy_eval_chunk(h->P), cmax = (size_t)n < chunk ? (size_t)n : chunk;
+    if (obs_rows) if (int rc = h->pol.d_pe_rows.reserve(cmax * row * 4)) return rc;
+    if (int rc = h->pol.d_pe_out.reserve(cmax * 4 * 8)) return rc;
+    if (side) if (int rc = h->pol.d_pl_side.reserve(cmax * 4)) return rc;
+    if (hp) if (int rc = h->pol.d_pl_choice.reserve(cmax * 4)) return rc;
+    PolicyLabelArgs a;
+    memset(&a, 0, sizeof(a));
+    a.P = h->P; a.Ppad = h->Ppad; a.N = h->N; a.expert = expert; a.clip_act_space = clip_act_space; a.out = h->pol.d_pe_out;
+    a.grid_dx = h->prm.width * 1.0 / (h->N - 1); a.grid_dy = h->prm.height * 1.0 / (h->N - 1);      // as fill_fused (api_run.hip)
+    // the waves of a workgroup: as many rows' heights as 64 KB of LDS hold, four at the most (oracle corner stages nothing)
+    const size_t zsize = obs_rows ? 4 : (h->precision == CLOTHHIP_F64 ? 8 : 4), zrow = (size_t)h->P * zsize;
+    const int rpb = (int)std::min<size_t>(4, std::max<size_t>(1, ((size_t)64 << 10) / zrow));
+    a.rows_per_block = rpb;
+    const size_t lds = hp ? (size_t)rpb * zrow : 0;
+    if (lds > ((size_t)64 << 10)) return fail(CLOTHHIP_ESTATE, "n_side %d: one row of heights needs %zu B of LDS (> 64 KiB)", h->N, lds);
+    for (size_t i0 = 0; i0 < (size_t)n; i0 += chunk) {
+        const size_t m = (size_t)n - i0 < chunk ? (size_t)n - i0 : chunk;
+        a.n = (int64_t)m;
+        if (side) { HIPCHECK(hipMemcpyAsync(h->pol.d_pl_side, side + i0, m * 4, hipMemcpyHostToDevice, h->stream)); a.side = h->pol.d_pl_side; }
+        if (hp) { HIPCHECK(hipMemcpyAsync(h->pol.d_pl_choice, choice + i0, m * 4, hipMemcpyHostToDevice, h->stream)); a.choice = h->pol.d_pl_choice; }
+        const dim3 grid((unsigned)((m + rpb - 1) / rpb)), block(64 * rpb);
+        if (obs_rows) {
+            HIPCHECK(hipMemcpyAsync(h->pol.d_pe_rows, obs_rows + i0 * row, m * row * 4, hipMemcpyHostToDevice, h->stream));
+            a.rows = h->pol.d_pe_rows;
+            HIPCHECK(hipEventRecord(h->ev0, h->stream));
+            hipLaunchKernelGGL((k_policy_label<float, float>), grid, block, lds, h->stream, a);
+        } else {
+            HIPCHECK(hipEventRecord(h->ev0, h->stream));
+            by_precision(h, [&](auto t) {
+                using T = decltype(t);
+                a.pos = (const T *)h->d_pos + i0 * 3 * h->Ppad;
+                hipLaunchKernelGGL((k_policy_label<T, T>), grid, block, lds, h->stream, a);
+            });
+        }
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipEventRecord(h->ev1, h->stream));
+        h->have_timing = true;
+        HIPCHECK(hipMemcpyAsync(actions_out + i0 * 4, h->pol.d_pe_out, m * 4 * 8, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    return 0;
 }

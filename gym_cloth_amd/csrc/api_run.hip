@@ -255,7 +255,7 @@ extern "C" int clothhip_run(clothhip_handle *h, const ClothSchedule *sched, int3
 template <typename T> static void fill_fused(clothhip_handle *h, FusedArgs<T> &f, const ClothEpisodeParams *ep, int T_, int policy,
                                              const double *d_actions, bool have_parg, bool have_scripts, bool have_resets, bool have_obs,
                                              bool have_robs, int n_scripts, uint64_t budget_ticks, bool have_mt, int rng_tier,
-                                             uint64_t domrand_words, int NS, int NH) {
+                                             uint64_t domrand_words, int NS, int NH, int expert, bool resume_labelled) {
     memset(&f, 0, sizeof(f));
     f.nT = T_; f.policy = policy; f.NS = NS; f.NH = NH;
     f.actions = d_actions;
@@ -278,6 +278,48 @@ template <typename T> static void fill_fused(clothhip_handle *h, FusedArgs<T> &f
     f.two_thickness = 2 * h->prm.thickness; f.half_thickness = h->prm.thickness / 2.0;
     f.ep = *ep;
     f.mlp = h->pol.mlp;
+    if (expert) {
+        f.expert = expert; f.resume_labelled = resume_labelled ? 1 : 0;
+        f.labels = h->epi.d_flab;
+        f.expert_mix = h->epi.arm_mix ? (const uint8_t *)h->epi.d_fmix : nullptr;
+        f.expert_choice = expert == CLOTHHIP_POLICY_HIGHEST_POINT ? (const int32_t *)h->epi.d_fchoice : nullptr;
+    }
+}
+
+// ---- an expert beside the acting policy (clothhip.h: clothhip_run_actions_expert) ----------------------------------------------------
+static bool known_expert(int32_t x) { return x == CLOTHHIP_POLICY_ORACLE_CORNER || x == CLOTHHIP_POLICY_HIGHEST_POINT; }
+
+extern "C" int clothhip_run_actions_expert(clothhip_handle *h, int32_t expert, int32_t T_, const uint8_t *mix, const int32_t *choice) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    h->epi.arm_expert = 0;                              // whatever happens below, an earlier arming is gone
+    if (h->epi.f_pending) return fail(CLOTHHIP_ESTATE, "a clothhip_run_actions_begin is in flight: arm the expert before the launch");
+    if (!known_expert(expert)) return fail(CLOTHHIP_EINVAL, "unknown expert %d (CLOTHHIP_POLICY_ORACLE_CORNER or CLOTHHIP_POLICY_HIGHEST_POINT)", expert);
+    if (T_ < 1 || T_ > 4096) return fail(CLOTHHIP_EINVAL, "T must be in [1, 4096]");
+    if (expert == CLOTHHIP_POLICY_HIGHEST_POINT && !choice) return fail(CLOTHHIP_EINVAL, "the highest-point expert needs choice[T][E]: which of the highest points per slot");
+    if (h->relaxed) return fail(CLOTHHIP_ESTATE, "clothhip_set_relaxed_order: the relaxed-order companion is a bench-only kernel without an expert");
+    for (const Layout *L : {&h->lay_std, &h->lay_lean})
+        if ((L == &h->lay_std || h->lean) && !find_stepper(L->v, 0, 2)) return fail(CLOTHHIP_ESTATE, "this handle's stepper variant has no build with the cold policies");
+    if (expert == CLOTHHIP_POLICY_ORACLE_CORNER && h->N != 25)
+        return fail(CLOTHHIP_ESTATE, "the oracle-corner policy is defined for 25x25 cloths only (analytic.py:106)");
+    const size_t n = (size_t)T_ * h->E;
+    h->epi.arm_mix = mix != nullptr;
+    if (mix) h->epi.h_arm_mix.assign(mix, mix + n);
+    if (expert == CLOTHHIP_POLICY_HIGHEST_POINT) h->epi.h_arm_choice.assign(choice, choice + n);
+    h->epi.arm_T = T_; h->epi.arm_expert = expert;
+    return 0;
+}
+
+extern "C" int clothhip_run_actions_labels(clothhip_handle *h, double *labels, void **d_labels) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (h->epi.f_pending) return fail(CLOTHHIP_ESTATE, "a clothhip_run_actions_begin is in flight: call clothhip_run_actions_end first");
+    if (!h->epi.f_labels) return fail(CLOTHHIP_ESTATE, "the last episode launch on this handle was not armed with an expert (clothhip_run_actions_expert)");
+    if (d_labels) *d_labels = h->epi.d_flab;
+    if (labels) {
+        HIPCHECK(hipSetDevice(h->device));
+        HIPCHECK(hipMemcpyAsync(labels, h->epi.d_flab, (size_t)h->epi.f_T * h->E * 4 * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHECK(hipStreamSynchronize(h->stream));
+    }
+    return 0;
 }
 
 extern "C" int clothhip_run_actions_begin(clothhip_handle *h, const ClothEpisodeParams *ep, int32_t T_, int32_t policy,
@@ -286,8 +328,17 @@ extern "C" int clothhip_run_actions_begin(clothhip_handle *h, const ClothEpisode
                                           const uint8_t *done, const uint32_t *rng_states, int32_t rng_tier, uint64_t domrand_words,
                                           int32_t want_resets, int32_t want_obs, int32_t want_reset_obs,
                                           double time_budget_ms) {
-    if (!h || !ep || !num_steps || !done) return fail(CLOTHHIP_EINVAL, "NULL argument");
+    if (!h) return fail(CLOTHHIP_EINVAL, "NULL argument");
+    // an arming (clothhip_run_actions_expert) is for this call alone, whatever becomes of it
+    const int expert = h->epi.arm_expert;
+    const bool resume_labelled = h->epi.f_labels;       // the previous launch was armed: an action it cut left its label in EpResume
+    h->epi.arm_expert = 0;
+    if (!ep || !num_steps || !done) return fail(CLOTHHIP_EINVAL, "NULL argument");
     if (h->epi.f_pending) return fail(CLOTHHIP_ESTATE, "a clothhip_run_actions_begin is already in flight");
+    if (expert && T_ != h->epi.arm_T) return fail(CLOTHHIP_EINVAL, "T = %d, the expert was armed for %d slots", T_, h->epi.arm_T);
+    if (expert && policy != CLOTHHIP_POLICY_TABLE && policy != CLOTHHIP_POLICY_MLP)
+        return fail(CLOTHHIP_EINVAL, "only CLOTHHIP_POLICY_TABLE and CLOTHHIP_POLICY_MLP may act beside an expert (policy %d)", policy);
+    if (expert && h->relaxed) return fail(CLOTHHIP_ESTATE, "clothhip_set_relaxed_order: the relaxed-order companion is a bench-only kernel without an expert");
     const bool resets = want_resets != 0, obs = want_obs != 0, reset_obs = want_reset_obs != 0;
     if (T_ < 1 || T_ > 4096) return fail(CLOTHHIP_EINVAL, "T must be in [1, 4096]");
     if (policy != CLOTHHIP_POLICY_TABLE && policy != CLOTHHIP_POLICY_ORACLE_CORNER && policy != CLOTHHIP_POLICY_HIGHEST_POINT && policy != CLOTHHIP_POLICY_MLP)
@@ -357,6 +408,18 @@ extern "C" int clothhip_run_actions_begin(clothhip_handle *h, const ClothEpisode
         if (int rc = h->epi.d_fparg.reserve(nb)) return rc;
         HIPCHECK(hipMemcpyAsync(h->epi.d_fparg, policy_arg, nb, hipMemcpyHostToDevice, h->stream));
     }
+    if (expert) {                                       // labels start as all-ones NaNs: a slot without an action keeps them
+        if (int rc = h->epi.d_flab.reserve(nrec * 4 * 8)) return rc;
+        HIPCHECK(hipMemsetAsync(h->epi.d_flab, 0xFF, nrec * 4 * 8, h->stream));
+        if (h->epi.arm_mix) {
+            if (int rc = h->epi.d_fmix.reserve(nrec)) return rc;
+            HIPCHECK(hipMemcpyAsync(h->epi.d_fmix, h->epi.h_arm_mix.data(), nrec, hipMemcpyHostToDevice, h->stream));
+        }
+        if (expert == CLOTHHIP_POLICY_HIGHEST_POINT) {
+            if (int rc = h->epi.d_fchoice.reserve(nrec * 4)) return rc;
+            HIPCHECK(hipMemcpyAsync(h->epi.d_fchoice, h->epi.h_arm_choice.data(), nrec * 4, hipMemcpyHostToDevice, h->stream));
+        }
+    }
     if (scripts) HIPCHECK(hipMemcpyAsync(h->epi.d_fscr, scripts, nscr * sizeof(ClothResetScript), hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipMemcpyAsync(h->epi.d_fsteps, num_steps, E * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipMemcpyAsync(h->epi.d_fdone, done, E, hipMemcpyHostToDevice, h->stream));
@@ -368,7 +431,7 @@ extern "C" int clothhip_run_actions_begin(clothhip_handle *h, const ClothEpisode
     const MetricsDims md = metrics_dims(h->P, h->Ppad);
     by_precision(h, [&](auto t) {
         fill_fused(h, *reinterpret_cast<FusedArgs<decltype(t)> *>(fzbuf), ep, T_, policy, d_actions, policy_arg != nullptr, scripts != nullptr, resets, obs, reset_obs, n_scripts,
-                   budget_ticks, rng_states != nullptr, rng_tier, domrand_words, md.NS, md.NH);
+                   budget_ticks, rng_states != nullptr, rng_tier, domrand_words, md.NS, md.NH, expert, resume_labelled);
     });
     HIPCHECK(hipMemcpyAsync(h->epi.d_fz, fzbuf, 1024, hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipStreamSynchronize(h->stream));          // fzbuf is on this stack frame
@@ -376,14 +439,14 @@ extern "C" int clothhip_run_actions_begin(clothhip_handle *h, const ClothEpisode
         return fail(CLOTHHIP_ESTATE, "clothhip_set_relaxed_order: the relaxed-order companion exists for the eight-wave LEAN layout only (fp32, flat tiers, 25x25 class, <= 512 cloths)");
     HIPCHECK(hipEventRecord(h->ev0, h->stream));
     // (FUSED 2: the variant that also carries the tier-2 reset code and the cold policies; the relaxed-order companion is one launch)
-    const int fused = h->relaxed ? 3 : (tier2 || policy == CLOTHHIP_POLICY_HIGHEST_POINT || policy == CLOTHHIP_POLICY_MLP || read_debug_knobs().cold_build) ? 2 : 1;
+    const int fused = h->relaxed ? 3 : (tier2 || policy == CLOTHHIP_POLICY_HIGHEST_POINT || policy == CLOTHHIP_POLICY_MLP || expert != 0 || read_debug_knobs().cold_build) ? 2 : 1;
     if (int rc = launch_run(h, fused, h->d_sched, h->epi.d_fz, !h->relaxed && budget_ticks != 0)) return rc;
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipEventRecord(h->ev1, h->stream));
     h->have_timing = true;
     h->pending_exec = true;
     h->epi.f_T = T_; h->epi.f_nscr = nscr; h->epi.f_resets = resets; h->epi.f_obs = obs; h->epi.f_robs = reset_obs; h->epi.f_mt = rng_states != nullptr;
-    h->epi.f_pending = true;
+    h->epi.f_pending = true; h->epi.f_labels = expert != 0;
     return 0;
 }
 
@@ -435,7 +498,7 @@ extern "C" int clothhip_run_actions(clothhip_handle *h, const ClothEpisodeParams
                                     const ClothResetScript *scripts, int32_t n_scripts, int32_t *num_steps, uint8_t *done,
                                     ClothStepRecord *records, ClothResetRecord *resets, float *obs, float *reset_obs,
                                     double time_budget_ms) {
-    if (!records) return fail(CLOTHHIP_EINVAL, "NULL argument");
+    if (!records) { if (h) h->epi.arm_expert = 0; return fail(CLOTHHIP_EINVAL, "NULL argument"); }      // (also a call that fails here consumes an arming)
     if (int rc = clothhip_run_actions_begin(h, ep, T_, policy, actions, actions_on_device, policy_arg, scripts, n_scripts,
                                             num_steps, done, nullptr, 0, 0, resets != nullptr, obs != nullptr,
                                             reset_obs != nullptr, time_budget_ms))

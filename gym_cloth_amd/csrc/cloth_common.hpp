@@ -62,6 +62,12 @@ template <typename T> struct FusedArgs {
     double two_thickness, half_thickness;
     ClothEpisodeParams ep;
     MlpDesc mlp;                      // CLOTHHIP_POLICY_MLP: the handle's network (cloth_policy_mlp.hpp); `actions` is then the optional noise table
+    // the silent expert of an armed launch (clothhip_run_actions_expert; FUSED == 2 builds only, at the end so that every other field keeps its place)
+    int32_t expert;                   // 0 none, CLOTHHIP_POLICY_ORACLE_CORNER or CLOTHHIP_POLICY_HIGHEST_POINT: evaluated where the acting policy is, on the same state
+    int32_t resume_labelled;          // 1: the previous launch was armed too, so an action it cut left its label in EpResume; 0: such an action's label is NaN
+    double *labels;                   // [nT][E][4] what a launch with `expert` as its acting policy would have recorded as the slot's action (all-ones NaN: no action in the slot)
+    const uint8_t *expert_mix;        // [nT][E] or nullptr: != 0 -> the label IS the slot's action (no noise, no network)
+    const int32_t *expert_choice;     // [nT][E] HIGHEST_POINT: which of the highest points
 };
 
 // episode state of one cloth between the operations of the fused loop: kept in LDS, not in registers, so that nothing of it
@@ -103,6 +109,7 @@ struct EpResume {
     ClothSchedule sc;
     EpState eps;
     ClothResetRecord rr;       // the partly filled record of the reset in flight (eps.rp >= 0)
+    double label[4];           // an armed launch's label of the action in flight (it >= 0, eps.rp < 0): the resuming launch writes it to its labels[0][e]
 };
 
 template <typename T> struct StepArgs {

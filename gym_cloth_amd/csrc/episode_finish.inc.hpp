@@ -17,6 +17,11 @@
                         ClothResetRecord *rr_ = F.resets + ((size_t)e * F.n_scripts + eps->n_resets);
                         rs_->rr = *rr_; rr_->consumed = 2;
                     }
+                    if constexpr (with_tier2) if (F.expert != 0 && eps->rp < 0) {
+                        // an armed launch: the cut action's label leaves with it and comes back in the slot of its record (slot 0 of the launch that completes it)
+                        double *lp = F.labels + ((size_t)eps->t_slot * F.E + e) * 4;
+                        for (int q = 0; q < 4; q++) { rs_->label[q] = lp[q]; lp[q] = __longlong_as_double(-1LL); }
+                    }
                 }
                 __syncthreads();
                 break;

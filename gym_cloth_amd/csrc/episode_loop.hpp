@@ -226,6 +226,8 @@ __global__ __launch_bounds__(NT, (Variant{(int)sizeof(T), NT, PPT, TAB, REST_REG
                 eps->decode_err = o.decode_err; eps->side = o.side; eps->pull = o.pull; eps->choice = o.choice; eps->swap = o.swap;
                 eps->act[0] = o.act[0]; eps->act[1] = o.act[1]; eps->act[2] = o.act[2]; eps->act[3] = o.act[3];
                 if (o.rp >= 0 && Fp->resets != nullptr) Fp->resets[(size_t)e * Fp->n_scripts] = rs_->rr;   // its record, now slot 0
+                if constexpr (with_tier2)                  // an armed launch: the label of the action in flight, beside its record
+                    if (Fp->expert != 0 && o.rp < 0 && rs_->it >= 0) { double *lp = Fp->labels + 4 * (size_t)e; for (int q = 0; q < 4; q++) lp[q] = Fp->resume_labelled ? rs_->label[q] : __longlong_as_double(-1LL); }
             }
         }
         __syncthreads();

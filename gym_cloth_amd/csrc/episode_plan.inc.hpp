@@ -116,91 +116,105 @@
                     continue;
                 }
                 do_decode = true;
-                if (F.policy == CLOTHHIP_POLICY_ORACLE_CORNER) {
-                    // examples/analytic.py:105-155 ('distance' method, delta actions): pull the inset corner that is
-                    // farthest from its plane corner; candidates in the order ur, lr, ll, ul, the first maximum wins
-                    const bool sw = eps->swap == 1;                                       // tier 2, init_side False (:108-114)
-                    double best = -1.0;
+                // ONE copy of the policies serves two purposes. An armed launch (F.expert, FUSED == 2 builds only) runs this twice: first
+                // as the silent expert -- the analytic policy F.expert on the same LDS-resident state, its `act` is the slot's label and
+                // goes to global memory now (nothing of it is kept in LDS or across the substep loop; a time slice that cuts the action
+                // carries it over in EpResume, episode_finish.inc.hpp) --, then, unless the mixture makes the label the action, as the
+                // acting policy. Every other launch runs it once, as before.
+                for (bool as_expert = with_tier2 && F.expert != 0;; as_expert = false) {
+                    const int pol = as_expert ? F.expert : F.policy;
+                    if (pol == CLOTHHIP_POLICY_ORACLE_CORNER) {
+                        // examples/analytic.py:105-155 ('distance' method, delta actions): pull the inset corner that is
+                        // farthest from its plane corner; candidates in the order ur, lr, ll, ul, the first maximum wins
+                        const bool sw = eps->swap == 1;                                       // tier 2, init_side False (:108-114)
+                        double best = -1.0;
 #pragma unroll
-                    for (int c = 0; c < 4; c++) {
-                        const int ci = c == 0 ? (sw ? 48 : 598) : (c == 1 ? (sw ? 26 : 576) : (c == 2 ? (sw ? 576 : 26) : (sw ? 598 : 48)));
-                        const double tgx = c < 2 ? 1.0 : 0.0, tgy = (c == 0 || c == 3) ? 1.0 : 0.0;
-                        const Pt<T> pc = cur[ci];
-                        const double x = (double)pc.x, y = (double)pc.y;
-                        const double cx = (x - 0.5) * 2.0, cy = (y - 0.5) * 2.0;                 // analytic.py:53-54
-                        double dx = tgx - x, dy = tgy - y;                                        // :55-56
-                        const double dist = sqrt((x - tgx) * (x - tgx) + (y - tgy) * (y - tgy)); // :57
-                        dx = dx * 0.90; dy = dy * 0.90;                                           // :64-66
-                        if (dist > best) {
-                            best = dist;
-                            act[0] = F.ep.clip_act_space ? cx : x; act[1] = F.ep.clip_act_space ? cy : y;   // :151-154
-                            act[2] = dx; act[3] = dy;
-                        }
-                    }
-                } else if (with_tier2 && F.policy == CLOTHHIP_POLICY_HIGHEST_POINT) {
-                    // examples/analytic.py:792-808: sorted(pts, key=z, reverse=True)[k] -- a stable sort, so equal heights keep
-                    // their index order -- with k (the reference: np.random.randint(top_k)) from the caller's table, pulled to
-                    // where that point sits on the flat cloth (:742-789). k + 1 rounds of a workgroup arg-max over (z, -index),
-                    // each excluding what the earlier rounds took; the per-wave results go through the member list (scratch
-                    // between substeps).
-                    struct Cand { T z; int i; int pad; };
-                    Cand *red = reinterpret_cast<Cand *>(memb);
-                    int kc = F.policy_arg[(size_t)(1 + t_slot) * F.E + e];
-                    kc = kc < 0 ? 0 : (kc > P - 1 ? P - 1 : kc);
-                    T lastz = (T)0; int lasti = -1;
-                    const auto better = [](T z1, int i1, T z0, int i0) { return i1 != 0x7fffffff && (i0 == 0x7fffffff || z1 > z0 || (z1 == z0 && i1 < i0)); };
-                    for (int round = 0; round <= kc; round++) {
-                        T bz = (T)0; int bi = 0x7fffffff;
-#pragma unroll
-                        for (int q = 0; q < PPT; q++) {
-                            const int i = tid + q * NT;
-                            if (i < P) {
-                                const T z = cur[i].z;
-                                const bool ok = lasti < 0 || z < lastz || (z == lastz && i > lasti);
-                                if (ok && better(z, i, bz, bi)) { bz = z; bi = i; }
+                        for (int c = 0; c < 4; c++) {
+                            const int ci = c == 0 ? (sw ? 48 : 598) : (c == 1 ? (sw ? 26 : 576) : (c == 2 ? (sw ? 576 : 26) : (sw ? 598 : 48)));
+                            const double tgx = c < 2 ? 1.0 : 0.0, tgy = (c == 0 || c == 3) ? 1.0 : 0.0;
+                            const Pt<T> pc = cur[ci];
+                            const double x = (double)pc.x, y = (double)pc.y;
+                            const double cx = (x - 0.5) * 2.0, cy = (y - 0.5) * 2.0;                 // analytic.py:53-54
+                            double dx = tgx - x, dy = tgy - y;                                        // :55-56
+                            const double dist = sqrt((x - tgx) * (x - tgx) + (y - tgy) * (y - tgy)); // :57
+                            dx = dx * 0.90; dy = dy * 0.90;                                           // :64-66
+                            if (dist > best) {
+                                best = dist;
+                                act[0] = F.ep.clip_act_space ? cx : x; act[1] = F.ep.clip_act_space ? cy : y;   // :151-154
+                                act[2] = dx; act[3] = dy;
                             }
                         }
-                        for (int o = 32; o > 0; o >>= 1) {
-                            const T oz = __shfl_xor(bz, o); const int oi = __shfl_xor(bi, o);
-                            if (better(oz, oi, bz, bi)) { bz = oz; bi = oi; }
-                        }
-                        if (lane == 0) { red[tid >> 6].z = bz; red[tid >> 6].i = bi; }
-                        __syncthreads();
-                        bz = red[0].z; bi = red[0].i;
-                        for (int w = 1; w < NT / 64; w++) { const T oz = red[w].z; const int oi = red[w].i; if (better(oz, oi, bz, bi)) { bz = oz; bi = oi; } }
-                        lastz = bz; lasti = bi;
-                        __syncthreads();
-                    }
-                    const int pr = lasti / KA_N(&A), pc_ = lasti - pr * KA_N(&A);
-                    const Pt<T> pp = cur[lasti];
-                    const double x = (double)pp.x, y = (double)pp.y;
-                    double tgx, tgy;
-                    if (eps->swap == 0) { tgx = F.grid_dx * pr; tgy = F.grid_dy * pc_; }                   // pt.orig_x, pt.orig_y of the flat grid (cloth.pyx:122-124)
-                    else { tgx = eps->swap == 2 ? F.grid_dy * pr : 1.0 - F.grid_dy * pr; tgy = F.grid_dx * pc_; }   // :781-788 (orig_z, orig_y)
-                    const double cx = (x - 0.5) * 2.0, cy = (y - 0.5) * 2.0;                     // analytic.py:53-54
-                    const double dx = (tgx - x) * 0.90, dy = (tgy - y) * 0.90;                    // :55-56, :64-66
-                    act[0] = F.ep.clip_act_space ? cx : x; act[1] = F.ep.clip_act_space ? cy : y; // :803-806
-                    act[2] = dx; act[3] = dy;
-                } else if (with_tier2 && F.policy == CLOTHHIP_POLICY_MLP) {
-                    // the handle's network (with a population: this env slot's, MlpDesc::member) on this cloth's '1d' observation
-                    // (cloth_policy_mlp.hpp: the order of its arithmetic does not depend on NT), + the caller's noise for this slot. The two hidden vectors borrow the head of the scratch the in-kernel metrics
-                    // borrow (on a small grid `misc` lies inside it: the tear flag is carried over), which is rebuilt as after the metrics.
-                    if constexpr (with_tier2) {
-                        const int tear_keep = misc[0];
-                        __syncthreads();
-                        float *mbuf = reinterpret_cast<float *>(smem + lay.hkey);
-                        mlp_eval_records<Pt<T>>(&F.mlp, e, cur, mbuf, tid, NT);
-                        const float *y = mbuf + mlp_out_offset(F.mlp.n_layers);
-                        const double *nz = F.actions != nullptr ? F.actions + ((size_t)t_slot * F.E + e) * 4 : nullptr;
+                    } else if (with_tier2 && pol == CLOTHHIP_POLICY_HIGHEST_POINT) {
+                        // examples/analytic.py:792-808: sorted(pts, key=z, reverse=True)[k] -- a stable sort, so equal heights keep
+                        // their index order -- with k (the reference: np.random.randint(top_k)) from the caller's table, pulled to
+                        // where that point sits on the flat cloth (:742-789). k + 1 rounds of a workgroup arg-max over (z, -index),
+                        // each excluding what the earlier rounds took; the per-wave results go through the member list (scratch
+                        // between substeps).
+                        struct Cand { T z; int i; int pad; };
+                        Cand *red = reinterpret_cast<Cand *>(memb);
+                        int kc = as_expert ? F.expert_choice[(size_t)t_slot * F.E + e] : F.policy_arg[(size_t)(1 + t_slot) * F.E + e];
+                        kc = kc < 0 ? 0 : (kc > P - 1 ? P - 1 : kc);
+                        T lastz = (T)0; int lasti = -1;
+                        const auto better = [](T z1, int i1, T z0, int i0) { return i1 != 0x7fffffff && (i0 == 0x7fffffff || z1 > z0 || (z1 == z0 && i1 < i0)); };
+                        for (int round = 0; round <= kc; round++) {
+                            T bz = (T)0; int bi = 0x7fffffff;
 #pragma unroll
-                        for (int k = 0; k < 4; k++) act[k] = (double)y[k] + (nz != nullptr ? nz[k] : 0.0);
-                        __syncthreads();
-                        init_lds(tear_keep, nullptr, nullptr);
-                        __syncthreads();
+                            for (int q = 0; q < PPT; q++) {
+                                const int i = tid + q * NT;
+                                if (i < P) {
+                                    const T z = cur[i].z;
+                                    const bool ok = lasti < 0 || z < lastz || (z == lastz && i > lasti);
+                                    if (ok && better(z, i, bz, bi)) { bz = z; bi = i; }
+                                }
+                            }
+                            for (int o = 32; o > 0; o >>= 1) {
+                                const T oz = __shfl_xor(bz, o); const int oi = __shfl_xor(bi, o);
+                                if (better(oz, oi, bz, bi)) { bz = oz; bi = oi; }
+                            }
+                            if (lane == 0) { red[tid >> 6].z = bz; red[tid >> 6].i = bi; }
+                            __syncthreads();
+                            bz = red[0].z; bi = red[0].i;
+                            for (int w = 1; w < NT / 64; w++) { const T oz = red[w].z; const int oi = red[w].i; if (better(oz, oi, bz, bi)) { bz = oz; bi = oi; } }
+                            lastz = bz; lasti = bi;
+                            __syncthreads();
+                        }
+                        const int pr = lasti / KA_N(&A), pc_ = lasti - pr * KA_N(&A);
+                        const Pt<T> pp = cur[lasti];
+                        const double x = (double)pp.x, y = (double)pp.y;
+                        double tgx, tgy;
+                        if (eps->swap == 0) { tgx = F.grid_dx * pr; tgy = F.grid_dy * pc_; }                   // pt.orig_x, pt.orig_y of the flat grid (cloth.pyx:122-124)
+                        else { tgx = eps->swap == 2 ? F.grid_dy * pr : 1.0 - F.grid_dy * pr; tgy = F.grid_dx * pc_; }   // :781-788 (orig_z, orig_y)
+                        const double cx = (x - 0.5) * 2.0, cy = (y - 0.5) * 2.0;                     // analytic.py:53-54
+                        const double dx = (tgx - x) * 0.90, dy = (tgy - y) * 0.90;                    // :55-56, :64-66
+                        act[0] = F.ep.clip_act_space ? cx : x; act[1] = F.ep.clip_act_space ? cy : y; // :803-806
+                        act[2] = dx; act[3] = dy;
+                    } else if (with_tier2 && pol == CLOTHHIP_POLICY_MLP) {
+                        // the handle's network (with a population: this env slot's, MlpDesc::member) on this cloth's '1d' observation
+                        // (cloth_policy_mlp.hpp: the order of its arithmetic does not depend on NT), + the caller's noise for this slot. The two hidden vectors borrow the head of the scratch the in-kernel metrics
+                        // borrow (on a small grid `misc` lies inside it: the tear flag is carried over), which is rebuilt as after the metrics.
+                        if constexpr (with_tier2) {
+                            const int tear_keep = misc[0];
+                            __syncthreads();
+                            float *mbuf = reinterpret_cast<float *>(smem + lay.hkey);
+                            mlp_eval_records<Pt<T>>(&F.mlp, e, cur, mbuf, tid, NT);
+                            const float *y = mbuf + mlp_out_offset(F.mlp.n_layers);
+                            const double *nz = F.actions != nullptr ? F.actions + ((size_t)t_slot * F.E + e) * 4 : nullptr;
+#pragma unroll
+                            for (int k = 0; k < 4; k++) act[k] = (double)y[k] + (nz != nullptr ? nz[k] : 0.0);
+                            __syncthreads();
+                            init_lds(tear_keep, nullptr, nullptr);
+                            __syncthreads();
+                        }
+                    } else {
+                        const double *ap = F.actions + ((size_t)t_slot * F.E + e) * 4;
+                        act[0] = ap[0]; act[1] = ap[1]; act[2] = ap[2]; act[3] = ap[3];
                     }
-                } else {
-                    const double *ap = F.actions + ((size_t)t_slot * F.E + e) * 4;
-                    act[0] = ap[0]; act[1] = ap[1]; act[2] = ap[2]; act[3] = ap[3];
+                    if (!as_expert) break;
+                    if constexpr (with_tier2) {
+                        const size_t te = (size_t)t_slot * F.E + e;
+                        if (tid == 0) { double *lp = F.labels + te * 4; lp[0] = act[0]; lp[1] = act[1]; lp[2] = act[2]; lp[3] = act[3]; }
+                        if (F.expert_mix != nullptr && F.expert_mix[te] != 0) break;     // the expert acts: act = label, no noise, no network
+                    }
                 }
             } else {
                 if (eps->stop && F.resume != nullptr) {  // the slice ends between two operations of a reset

@@ -144,3 +144,27 @@ def collect_demos(env, policy='oracle_corner', max_episodes=10, slots_per_launch
         with open(path, 'wb') as fh:
             pickle.dump(episodes, fh)
     return episodes
+
+
+def dagger_mixture(n_actions, n_envs, beta, seed):
+    """DAgger's beta-mixture as a table: bool[T, E], True where the expert takes the action -- Bernoulli(beta) per (t, e) from
+    numpy.random.default_rng(seed). beta = 0: all False; beta = 1: all True."""
+    if not 0.0 <= float(beta) <= 1.0:
+        raise ValueError("beta must lie in [0, 1] (got %r)" % (beta,))
+    return np.random.default_rng(seed).random((int(n_actions), int(n_envs))) < float(beta)
+
+
+def dagger_rollout(env, expert='oracle_corner', n_actions=12, beta=0.5, seed=0, policy_noise=None, expert_choices=None):
+    """One DAgger data-collection pass in ONE episode launch: the env's network (set_policy: an MLPPolicy's, or an MLPPopulation, every
+    env under its own) drives the cloths for n_actions slots, the expert labels every state they reach, and takes the action over
+    where dagger_mixture(n_actions, E, beta, seed) says so (ClothVecEnv.step_many(policy='mlp', expert=..., expert_mix=...)); episodes
+    that end are reset inside the launch. Returns dict(obs float32[T, E, 3P]: what each slot's policy saw (envs.slot_start_obs),
+    labels float64[T, E, 4]: the expert's action there (NaN where ran is False), took bool[T, E]: the expert acted, ran bool[T, E],
+    out: step_many's dict). The caller aggregates (obs[ran], labels[ran]) over iterations and fits; nothing is trained here."""
+    from .envs import slot_start_obs
+    mix = dagger_mixture(n_actions, env.E, beta, seed)
+    obs_before = np.asarray(env.state, dtype=np.float32).reshape(env.E, -1)
+    out = env.step_many(policy='mlp', n_actions=int(n_actions), want_obs=True, policy_noise=policy_noise, expert=expert,
+                        expert_mix=mix, expert_choices=expert_choices)
+    return {'obs': slot_start_obs(out, obs_before), 'labels': out['expert_actions'], 'took': out['expert_took'], 'ran': out['ran'],
+            'out': out}

@@ -62,6 +62,22 @@ class Box(object):
         return x.shape == self.shape and bool(np.all(x >= self.low) and np.all(x <= self.high))
 
 
+def slot_start_obs(out, obs_before):
+    """float32[T, E, 3P]: the observation each slot's policy saw in a step_many(want_obs=True) launch without a time budget. Slot (t, e)
+    began on reset_obs[e, reset_before - 1] where an in-kernel reset preceded it (reset_before[t, e] > 0), else on obs_before[e] --
+    the observation before the launch -- for t = 0, else on obs_t[t - 1, e]. Rows of slots that did not run are whatever that rule gives."""
+    obs_t = np.asarray(out['obs_t'], dtype=np.float32)
+    T, E = obs_t.shape[:2]
+    start = np.empty_like(obs_t)
+    start[0] = np.asarray(obs_before, dtype=np.float32).reshape(E, -1)
+    start[1:] = obs_t[:-1]
+    rb = np.asarray(out['reset_before']).astype(np.int64)
+    t_, e_ = np.nonzero(rb > 0)
+    if len(t_):
+        start[t_, e_] = np.asarray(out['reset_obs'])[e_, rb[t_, e_] - 1]
+    return start
+
+
 def load_cfg(cfg):
     if isinstance(cfg, dict):
         return copy.deepcopy(cfg)
@@ -487,6 +503,31 @@ class ClothVecEnv(object):
             return self.batch.policy_eval_members(rows, member)
         return self.batch.policy_eval(rows)
 
+    def expert_actions(self, expert, obs=None, choices=None, init_side=None):
+        """What the analytic policy `expert` ('oracle_corner' | 'highest_point') does, float64[n, 4] as step_many(policy=expert) records its
+        actions (unclipped; in clip space when the env clips): for float32 '1d' observations obs [n, 3P] -- rows collect_demos or
+        step_many(want_obs=True) wrote -- or with obs=None for every env's present state, computed on the device with the launch's
+        arithmetic (ClothBatch.policy_label). choices int[n]: which of the highest points ('highest_point'). init_side bool[n]: on tier
+        2, the side each row's cloth was dropped from (default with obs=None: the envs' own; with rows it must be given)."""
+        if obs is None:
+            rows, n = None, self.E
+        else:
+            rows = np.asarray(obs, dtype=np.float32)
+            rows = rows.reshape(-1, rows.shape[-1])
+            n = rows.shape[0]
+        side = None
+        if self._init_type == 'tier2':
+            if init_side is None:
+                if obs is not None:
+                    raise ValueError("tier 2: init_side bool[n] says which side each row's cloth was dropped from")
+                init_side = self.init_side
+            side = np.where(np.asarray(init_side, dtype=bool).reshape(n), 2, 1).astype(np.int32)      # as step_many's policy_arg
+        elif init_side is not None:
+            raise ValueError("init_side goes with tier 2")
+        if choices is not None:
+            choices = np.asarray(choices).reshape(n)
+        return self.batch.policy_label(expert, rows, side=side, choices=choices, clip_act_space=self._clip_act_space)
+
     def _require_whole_actions(self, what):
         if self.batch.in_flight().any():
             raise RuntimeError("%s: a time-sliced step_many left operations in flight on env(s) %s; take it between whole actions "
@@ -710,7 +751,7 @@ class ClothVecEnv(object):
 
     def step_many(self, actions=None, n_actions=None, policy=None, auto_reset=True, want_obs=False, reset_tail=False,
                   actions_device_ptr=None, max_resets=None, time_budget_ms=0.0, device_rng=True, policy_choices=None,
-                  images=None, image_kw=None, policy_noise=None):
+                  images=None, image_kw=None, policy_noise=None, expert=None, expert_mix=None, expert_choices=None):
         """T consecutive `step(a_t, auto_reset=auto_reset)` calls for every env in ONE device launch
         (clothhip_run_actions): decoding, grab, the substep loop, metrics, the terminal test and the episode resets all
         run in the kernel, envs never wait for each other, and the host only does the reward / info bookkeeping below.
@@ -730,6 +771,15 @@ class ClothVecEnv(object):
         later scripts are void (the RNG stream forked) and it idles after its next episode until the launch ends.
         An episode that ends in the last slot is reset by the NEXT launch, or here on the host with reset_tail=True (then
         the returned obs is what T sequential steps return).
+
+        expert='oracle_corner' | 'highest_point' (beside actions or policy='mlp' only) runs that analytic policy as a silent second policy
+        of the launch: when a slot begins it is evaluated where the acting policy is, on the same state, and out['expert_actions']
+        float64[T, E, 4] holds what a launch with policy=expert would have recorded as that slot's action (NaN where `ran` is False) --
+        the DAgger label of every state the learner reached. expert_mix bool[T, E] lets it act: where True the label IS the slot's action
+        (no policy_noise added, the network not evaluated); out['expert_took'] bool[T, E] says where that happened. expert_choices
+        int[T, E]: which of the highest points, for 'highest_point' (as policy_choices). out['init_side_t'] bool[T, E] is init_side as it
+        stood when each slot began (tier 2: what expert_actions needs beside stored rows). With a time budget the caller passes the unused
+        expert_mix / expert_choices rows again, as for policy_noise, and arms every launch of the sequence.
 
         time_budget_ms > 0 turns the launch into a time slice: an env starts no further action once the launch has run that
         long, so envs advance at their own pace instead of waiting for the one with the most work (episode resets make
@@ -785,6 +835,11 @@ class ClothVecEnv(object):
             raise ValueError(policy)
         if policy_noise is not None and policy != 'mlp':
             raise ValueError("policy_noise goes with policy='mlp'")
+        if expert is not None and pol not in (_lib.POLICY_TABLE, _lib.POLICY_MLP):
+            raise ValueError("an expert runs beside actions or policy='mlp' only (got policy=%r)" % (policy,))
+        if expert == 'oracle_corner' and self.num_points != 625:
+            raise ValueError("the oracle-corner expert is defined for 25x25 cloths only (analytic.py:106)")
+        expert_mix, expert_choices = self.batch._expert_tables(expert, expert_mix, expert_choices, T)
         if not self._delta_actions:
             raise NotImplementedError("non-delta actions are decoded on the host only (cos/sin, cloth_env.py:452-453)")
         if images is not None:
@@ -815,7 +870,7 @@ class ClothVecEnv(object):
                     mt[e, :624], mt[e, 624], gauss[e] = st[1], st[2], st[3:]
             mt_before = mt.copy()
         parg = None
-        if pol != _lib.POLICY_TABLE and self._init_type == 'tier2':
+        if (pol != _lib.POLICY_TABLE or expert is not None) and self._init_type == 'tier2':
             parg = np.where(self.init_side, 2, 1).astype(np.int32)                       # analytic.py:108-114, :781-788
         if pol == _lib.POLICY_HIGHEST_POINT:
             parg = np.concatenate([(np.zeros(E, dtype=np.int32) if parg is None else parg)[None, :], policy_choices], axis=0)
@@ -827,7 +882,7 @@ class ClothVecEnv(object):
                                      actions_device_ptr=actions_device_ptr, time_budget_ms=time_budget_ms,
                                      rng_states=mt, rng_tier={'tier1': 1, 'tier2': 2, 'tier3': 3}.get(self._init_type, 0),
                                      domrand_words=2 * (3 + self._wd * self._hd * 3) if self._consume_domrand else 0,
-                                     reset_capacity=R)
+                                     reset_capacity=R, expert=expert, expert_mix=expert_mix, expert_choices=expert_choices)
         _lap('launch')
         if dev_reset and not use_rng:                                 # while the kernel runs: draw ahead for the NEXT launch
             for e in range(E):
@@ -835,6 +890,7 @@ class ClothVecEnv(object):
         _lap('draw_ahead(overlapped)')
         rec, rst, obs_t, robs = self.batch.run_actions_end()
         op_ticks, op_substeps = self.batch.op_ticks()
+        labels = self.batch.run_actions_labels(T) if expert is not None else None
         _lap('wait+download')
         if (rec['ran'] == 2).any():
             raise FloatingPointError("iters_pull does not terminate (non-finite action?)")
@@ -844,6 +900,10 @@ class ClothVecEnv(object):
         for k in ('executed', 'n_grabbed', 'num_steps', 'num_sim_steps', 'reset_before', 'reset_substeps'):
             out[k] = np.zeros((T, E), dtype=np.int64)
         out['actions'] = rec['action'].copy()
+        if expert is not None:
+            ran_ = rec['ran'] == 1
+            out['expert_actions'] = np.where(ran_[:, :, None], labels, np.nan)
+            out['expert_took'] = ran_ & (expert_mix != 0 if expert_mix is not None else False)
         # per env: 100 MHz ticks of this launch spent in {actions, reset pulls, reset settling, the rest} and the update() calls of each
         out['op_ticks'], out['op_substeps'] = op_ticks, op_substeps
         n_consumed = np.zeros(E, dtype=np.int64)
@@ -929,6 +989,8 @@ class ClothVecEnv(object):
         if reset_tail and auto_reset and self._ep_done.any():
             obs = self.reset(mask=self._ep_done.copy())
         out['obs'] = obs
+        if expert is not None:                                        # (an un-armed launch returns exactly the keys it always did)
+            out['init_side_t'] = side_t                               # tier 2: the side each slot's cloth was dropped from (expert_actions on stored rows)
         if want_obs:
             out['obs_t'], out['reset_obs'] = obs_t, robs
         return out

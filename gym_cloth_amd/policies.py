@@ -6,6 +6,9 @@ OracleCornerPolicy   examples/analytic.py:70-155  (distance method, delta action
 HighestPointPolicy   examples/analytic.py:723-808
 RandomPolicy         examples/analytic.py:811-823 (the reference samples from an UNSEEDED space RNG,
                      cloth_env.py:1004; here each env gets its own RandomState so runs are reproducible)
+                     Both also run on the device as an EXPERT beside another acting policy (ClothVecEnv.step_many(expert=...): labels for
+                     every state a learner reaches, DAgger's beta-mixture per slot) and stand-alone on stored observations
+                     (ClothVecEnv.expert_actions); demos.dagger_rollout is the data-collection pass built on that
 LookaheadPolicy      no reference counterpart: one-step greedy action selection over K candidates per env, evaluated on
                      device-side forks of the env's state (ClothVecEnv.lookahead)
 MLPPolicy            no reference counterpart: a small fully-connected network over the '1d' observation, evaluated on the device -- by

@@ -413,6 +413,42 @@ int clothhip_policy_population_perturb(clothhip_handle *h, int32_t n_layers, con
  * CLOTHHIP_EINVAL. CLOTHHIP_ESTATE without a population, or with one that was uploaded rather than generated. clothhip_last_kernel_ms
  * gives the kernel's time. */
 int clothhip_policy_population_combine(clothhip_handle *h, const float *coef, int32_t K, float *out);
+
+/* An EXPERT beside the acting policy (DAgger: examples/analytic.py's oracle says what it would have done in every state the learner
+ * reached, and may take some of the actions over). clothhip_run_actions_expert arms the NEXT clothhip_run_actions / _begin on this handle,
+ * and only that one: any such call consumes the arming, also one that fails. expert: CLOTHHIP_POLICY_ORACLE_CORNER or
+ * CLOTHHIP_POLICY_HIGHEST_POINT. The armed launch evaluates the expert when a slot begins, where its acting policy is evaluated (after an
+ * in-kernel reset: on the new episode's first state), on the same resident state and with the arithmetic a launch with that policy as its
+ * acting policy performs -- policy_arg row 0 says how each cloth was built, exactly as for the acting policies; the highest-point k comes
+ * from choice[t][e], not from policy_arg -- and writes labels[t][e][4]: what that launch would have put into ClothStepRecord.action,
+ * unclipped, in clip space when clip_act_space is set. THE BITS: labels[t][e] of an armed launch == the `action` record of slot t of a
+ * launch from the same state whose acting policy is the expert, as long as both executed the same actions before that slot (so always
+ * for t = 0), and == clothhip_policy_label on the handle's state at that moment; on an fp32 handle also == clothhip_policy_label on the
+ * float32 observation the slot's policy saw (on an fp64 handle that observation has rounded the positions, the label has not).
+ * mix[T][E] (host, NULL = the expert never acts): mix[t][e] != 0 makes the label the slot's action -- act = label, no noise added, the
+ * network not evaluated; otherwise the acting policy's action is taken as in an unarmed launch, whose records, states and observations an
+ * armed launch with mix == 0 reproduces bit for bit. Only CLOTHHIP_POLICY_TABLE and CLOTHHIP_POLICY_MLP may act beside an expert.
+ * choice[T][E] (host): HIGHEST_POINT only. Both tables are copied by this call. Time slices: an action a slice cuts is not planned
+ * again and its label is not computed again; the label appears in the slot of its record, slot 0 of that env in the launch that
+ * completes the action, provided that launch is armed too (the caller passes the unused mix / choice rows again, as for actions).
+ * CLOTHHIP_EINVAL: an unknown expert, T < 1, HIGHEST_POINT without choice; at the armed _begin a T other than the armed one or an acting
+ * policy other than TABLE / MLP. CLOTHHIP_ESTATE: arming with a launch in flight, a relaxed-order handle, a variant without the build
+ * that carries the cold policies, ORACLE_CORNER on a grid other than 25x25. In all these cases nothing on the handle changes except that
+ * the arming is gone. No reference counterpart. */
+int clothhip_run_actions_expert(clothhip_handle *h, int32_t expert, int32_t T, const uint8_t *mix, const int32_t *choice);
+/* After the armed launch (clothhip_run_actions_end or the synchronous form): labels[T][E][4], NaN where the slot's `ran` is 0. `labels` (host,
+ * may be NULL) receives a copy, `d_labels` (may be NULL) the device address, as clothhip_run_actions_summary's d_summary. CLOTHHIP_ESTATE
+ * with a launch in flight or when the last launch was not armed. */
+int clothhip_run_actions_labels(clothhip_handle *h, double *labels, void **d_labels);
+/* The expert on stored observations obs_rows[n][3P] (host float32, element 3 i + ax), or with obs_rows == NULL and n == E on the handle's
+ * present state: actions_out[n][4] as above (clip_act_space: the launch's ClothEpisodeParams field). Positions go float -> double (the
+ * state: handle precision -> double), from there the arithmetic is the launch's. side: int32[n] as policy_arg row 0 (0 flat tiers, 1 / 2
+ * tier 2 with init_side False / True; NULL = all 0). choice: int32[n], HIGHEST_POINT only (clamped to [0, P - 1] as in the launch). One
+ * 64-lane wave per row, the rows in bounded chunks as clothhip_policy_eval. CLOTHHIP_EINVAL: an unknown expert, n < 0, n != E with
+ * obs_rows == NULL, HIGHEST_POINT without choice, actions_out == NULL with n > 0. CLOTHHIP_ESTATE: a launch in flight, ORACLE_CORNER on a
+ * grid other than 25x25, HIGHEST_POINT on a grid whose row of heights exceeds 64 KiB of LDS (more than 16 384 points in float32). Synchronous; clothhip_last_kernel_ms gives the kernel's time (the last chunk's). Leaves an arming alone. */
+int clothhip_policy_label(clothhip_handle *h, int32_t expert, int32_t clip_act_space, const float *obs_rows, int64_t n,
+                          const int32_t *side, const int32_t *choice, double *actions_out);
 int clothhip_run_actions(clothhip_handle *h, const ClothEpisodeParams *ep, int32_t T, int32_t policy,
                          const double *actions, int32_t actions_on_device, const int32_t *policy_arg,
                          const ClothResetScript *scripts, int32_t n_scripts, int32_t *num_steps, uint8_t *done,

@@ -1,0 +1,81 @@
+#!/usr/bin/env python3
+"""DAgger with the expert inside the episode launch, end to end and small: a one-layer (linear) policy over the '1d' observation, a few
+iterations of  roll out under the beta-mixture (demos.dagger_rollout: ONE launch per iteration) -> aggregate (observation, label) ->
+refit by numpy.linalg.lstsq on everything gathered so far,  with beta = 0.5^i (iteration 0 is half the expert's). No torch. It prints
+the mean coverage after each env's last action per iteration (and with --out FILE also appends the lines there); profiles/dagger.txt
+holds a run. That record claims nothing: a linear map of 1875 positions is a poor smoother, the point is that the loop runs and what
+it costs.
+    python3 tools/dagger_demo.py [--envs 64] [--slots 12] [--iters 4] [--out FILE]"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import bench                                          # noqa: E402
+from gym_cloth_amd.demos import dagger_rollout        # noqa: E402
+from gym_cloth_amd.envs import ClothVecEnv            # noqa: E402
+from gym_cloth_amd.policies import MLPPolicy          # noqa: E402
+
+LINES = []
+
+
+def say(s=""):
+    print(s, flush=True)
+    LINES.append(s)
+
+
+def fit_linear(obs, labels):
+    """Least squares [obs, 1] @ X = labels -> one (W [4, 3P], b [4]) layer, float32."""
+    A = np.concatenate([obs.astype(np.float64), np.ones((len(obs), 1))], axis=1)
+    X = np.linalg.lstsq(A, labels, rcond=None)[0]
+    return [(X[:-1].T.astype(np.float32), X[-1].astype(np.float32))]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=64)
+    ap.add_argument("--slots", type=int, default=12)
+    ap.add_argument("--iters", type=int, default=4)
+    ap.add_argument("--out", default=None, help="also append the printed lines to this file")
+    args = ap.parse_args()
+    E, T = args.envs, args.slots
+    cfg = bench.bench_cfg(25, 0.02, "tier1")
+    cfg["env"]["force_grab"] = True
+    env = ClothVecEnv(cfg, n_envs=E, precision="f32", consume_domrand_draws=False)
+    env.seed([2000 + e for e in range(E)])
+    P = env.P
+    layers = [(np.zeros((4, 3 * P), dtype=np.float32), np.zeros(4, dtype=np.float32))]
+    data_obs, data_lab = [], []
+    say("DAgger demo: %d cloths 25x25 fp32 tier 1 (force_grab), linear policy, %d slots per launch, beta = 0.5^i, expert oracle_corner" % (E, T))
+    for i in range(args.iters):
+        env.seed([2000 + e for e in range(E)])
+        env.reset()
+        env.set_policy(MLPPolicy(env, layers))
+        t0 = time.perf_counter()
+        roll = dagger_rollout(env, expert="oracle_corner", n_actions=T, beta=0.5 ** i, seed=i)
+        dt = time.perf_counter() - t0
+        ran = roll["ran"]
+        data_obs.append(roll["obs"][ran]); data_lab.append(roll["labels"][ran])
+        cov = roll["out"]["actual_coverage"]
+        last = np.array([cov[np.nonzero(ran[:, e])[0][-1], e] for e in range(E) if ran[:, e].any()])
+        err = np.abs(roll["out"]["actions"][ran & ~roll["took"]] - roll["labels"][ran & ~roll["took"]])
+        t0 = time.perf_counter()
+        layers = fit_linear(np.concatenate(data_obs), np.concatenate(data_lab))
+        df = time.perf_counter() - t0
+        say("iteration %d: beta %.3f, %4d labelled states (%4d acted by the expert), mean coverage after the last action %.4f, "
+            "mean |learner action - label| %.4f, rollout %.0f ms (kernel %.0f ms), fit on %d rows %.0f ms" % (
+                i, 0.5 ** i, int(ran.sum()), int(roll["took"].sum()), float(last.mean()), float(err.mean()) if err.size else float("nan"),
+                dt * 1e3, env.batch.last_kernel_ms, sum(len(o) for o in data_obs), df * 1e3))
+    env.close()
+    if args.out:
+        with open(args.out, "a") as fh:
+            fh.write("\n".join(LINES) + "\n")
+
+
+if __name__ == "__main__":
+    main()
