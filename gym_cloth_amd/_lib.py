@@ -99,6 +99,18 @@ assert RESET_PULL_DTYPE.itemsize == 56 and RESET_SCRIPT_DTYPE.itemsize == 184
 assert STEP_RECORD_DTYPE.itemsize == 72 and RESET_RECORD_DTYPE.itemsize == 144
 assert C.sizeof(ClothEpisodeParams) == 144
 
+
+class ClothFitParams(C.Structure):
+    """clothhip_policy_fit's optimizer: six floats, `optimizer` one of FIT_OPTIMIZERS' codes."""
+    _fields_ = [("optimizer", C.c_float), ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
+                ("momentum", C.c_float)]
+
+
+FIT_ADAM, FIT_SGD = 0, 1
+FIT_OPTIMIZERS = {'adam': FIT_ADAM, 'sgd': FIT_SGD}
+FIT_MAX_BATCH = 4096                # CLOTHHIP_FIT_MAX_BATCH: the most rows of one minibatch
+assert C.sizeof(ClothFitParams) == 24
+
 # every symbol include/clothhip.h declares: (name, restype, argtypes)
 _vp, _dp, _u8p, _i32p = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(C.c_int32)
 _PP = C.POINTER(ClothParams)
@@ -148,6 +160,12 @@ SYMBOLS = [
     ("clothhip_run_actions_expert", C.c_int, [_vp, C.c_int32, C.c_int32, _u8p, _i32p]),
     ("clothhip_run_actions_labels", C.c_int, [_vp, _dp, C.POINTER(_vp)]),
     ("clothhip_policy_label", C.c_int, [_vp, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.c_int64, _i32p, _i32p, _dp]),
+    ("clothhip_fit_data_append", C.c_int, [_vp, C.POINTER(C.c_float), _dp, C.c_int64]),
+    ("clothhip_fit_data_clear", C.c_int, [_vp]),
+    ("clothhip_fit_data_size", C.c_int, [_vp, C.POINTER(C.c_int64)]),
+    ("clothhip_policy_fit_grad", C.c_int, [_vp, _i32p, C.c_int32, C.POINTER(C.c_float), _dp]),
+    ("clothhip_policy_fit", C.c_int, [_vp, C.POINTER(ClothFitParams), _i32p, C.c_int32, C.c_int32, _dp]),
+    ("clothhip_policy_fit_reset", C.c_int, [_vp]),
     ("clothhip_update", C.c_int, [_vp, C.c_int32, _dp]),
     ("clothhip_metrics", C.c_int, [_vp, _dp, _dp, _u8p, _u8p]),
     ("clothhip_metrics_ex", C.c_int, [_vp, _dp, _dp, _u8p, _u8p, _i32p]),

@@ -501,12 +501,14 @@ class ClothBatch(object):
         """The handle's policy network (clothhip_set_policy_mlp): `layers` is a list of (W, b) with W [out, in] (torch.nn.Linear.weight's
         layout) and b [out], ReLU between them, the first `in` = 3 P, the last `out` = 4; None or [] clears it. The values are
         uploaded as float32; every env of the batch evaluates the same network. ValueError for shapes the library refuses."""
+        self._mlp_n_params = 0                     # (fit_grad sizes its result by it: the shared network's parameters, 0 without one)
         if not layers:
             check(self._L.clothhip_set_policy_mlp(self._h, 0, None, None, 0))
             return
         from .policies import pack_mlp
         widths, blob = pack_mlp(layers)
         check(self._L.clothhip_set_policy_mlp(self._h, len(widths) - 1, _lib.i32p(widths), blob.ctypes.data_as(C.POINTER(C.c_float)), blob.size))
+        self._mlp_n_params = int(blob.size)
 
     def policy_eval(self, obs=None):
         """The handle's network on float32 '1d' observations obs [n, 3P], or with obs=None on every env's present state: float64
@@ -613,6 +615,83 @@ class ClothBatch(object):
         out = np.zeros(getattr(self, '_pop_n_params', 0), dtype=np.float32)      # (set by the last perturb that succeeded: the one the library sums, or it refuses before it writes)
         check(self._L.clothhip_policy_population_combine(self._h, self._fp(c), c.size, self._fp(out)))
         return out
+
+    def fit_append(self, obs, labels):
+        """Append (observation row, action label) pairs to the handle's device-resident dataset (clothhip_fit_data_append): obs [n, 3P]
+        (stored as float32), labels [n, 4] (stored as float32). ValueError for other shapes or non-finite values (dagger_rollout gives
+        NaN labels where a slot did not run: pass the [ran] rows); nothing is appended then. Returns the dataset's size."""
+        obs = np.ascontiguousarray(obs, dtype=np.float32)
+        lab = np.ascontiguousarray(labels, dtype=np.float64)
+        if obs.ndim != 2 or obs.shape[1] != 3 * self.P:
+            raise ValueError("obs must have shape (n, %d)" % (3 * self.P))
+        if lab.shape != (obs.shape[0], 4):
+            raise ValueError("labels must have shape (%d, 4)" % obs.shape[0])
+        if not (np.isfinite(obs).all() and np.isfinite(lab).all() and (np.abs(lab) <= np.finfo(np.float32).max).all()):
+            raise ValueError("obs and labels must be finite (float32)")
+        check(self._L.clothhip_fit_data_append(self._h, self._fp(obs), _lib.dp(lab), obs.shape[0]))
+        return self.fit_size()
+
+    def fit_clear(self):
+        """Empty the dataset (clothhip_fit_data_clear); the device memory stays with the handle."""
+        check(self._L.clothhip_fit_data_clear(self._h))
+
+    def fit_size(self):
+        """Rows in the dataset (clothhip_fit_data_size)."""
+        n = C.c_int64(0)
+        check(self._L.clothhip_fit_data_size(self._h, C.byref(n)))
+        return int(n.value)
+
+    @staticmethod
+    def _fit_idx(idx, ndim):
+        """A minibatch index table as int32, C order: integers, `ndim` dimensions, at least one row per step, at most FIT_MAX_BATCH."""
+        a = np.asarray(idx)
+        if a.ndim != ndim or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("idx must be a %d-d integer array" % ndim)
+        if not 1 <= a.shape[-1] <= _lib.FIT_MAX_BATCH:
+            raise ValueError("a minibatch has 1 to %d rows (got %d)" % (_lib.FIT_MAX_BATCH, a.shape[-1]))
+        if a.size and (a.min() < 0 or a.max() > np.iinfo(np.int32).max):
+            raise ValueError("idx must hold row numbers of the dataset")
+        return np.ascontiguousarray(a, dtype=np.int32)
+
+    def fit_grad(self, idx):
+        """(loss float, grad float32[n_params] in the blob's layout) of the handle's shared network over the dataset rows idx [B]
+        (repeats count as often), at the present weights; nothing is updated (clothhip_policy_fit_grad). The loss is
+        1 / (4 B) sum (y - label)^2, torch.nn.MSELoss()."""
+        ix = self._fit_idx(idx, 1)
+        n_params = self._fit_n_params()
+        grad = np.zeros(n_params, dtype=np.float32)
+        loss = np.zeros(1, dtype=np.float64)
+        check(self._L.clothhip_policy_fit_grad(self._h, _lib.i32p(ix), ix.size, self._fp(grad), _lib.dp(loss)))
+        return float(loss[0]), grad
+
+    def _fit_n_params(self):
+        n = getattr(self, '_mlp_n_params', 0)
+        if not n:
+            raise _lib.ClothHipError("no shared network on this batch: call set_policy_mlp first")
+        return n
+
+    def fit(self, idx_table, optimizer='adam', lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, momentum=0.0):
+        """n_steps optimizer steps on the handle's shared network, in place on the device (clothhip_policy_fit): step s uses the dataset
+        rows idx_table[s] (int [n_steps, B]). optimizer 'adam' (lr, beta1, beta2, eps) or 'sgd' (lr, momentum); the hyper-parameters are
+        rounded to float32. The moments and the step count persist across calls (fit_reset, or a new network, restarts them). Returns
+        float64[n_steps]: each step's loss BEFORE its update. The next step_many(policy='mlp') runs the fitted weights."""
+        ix = self._fit_idx(idx_table, 2)
+        if optimizer not in _lib.FIT_OPTIMIZERS:
+            raise ValueError("optimizer must be one of %r (got %r)" % (sorted(_lib.FIT_OPTIMIZERS), optimizer))
+        hyper = dict(lr=lr, beta1=beta1, beta2=beta2, eps=eps, momentum=momentum)
+        for k, v in hyper.items():
+            v = float(np.float32(v))
+            if not (np.isfinite(v) and v >= 0.0) or (k.startswith('beta') and v >= 1.0):
+                raise ValueError("%s = %r: hyper-parameters are finite and >= 0, the betas below 1" % (k, hyper[k]))
+        self._fit_n_params()
+        p = _lib.ClothFitParams(float(_lib.FIT_OPTIMIZERS[optimizer]), lr, beta1, beta2, eps, momentum)
+        loss = np.zeros(ix.shape[0], dtype=np.float64)
+        check(self._L.clothhip_policy_fit(self._h, C.byref(p), _lib.i32p(ix), ix.shape[0], ix.shape[1], _lib.dp(loss)))
+        return loss
+
+    def fit_reset(self):
+        """Zero the optimizer's moments and its step count (clothhip_policy_fit_reset)."""
+        check(self._L.clothhip_policy_fit_reset(self._h))
 
     def update(self, n=1, delta=None):
         """n x Cloth.update() (cloth.pyx:169), each preceded by Gripper.adjust(*delta) if delta is given."""

@@ -110,6 +110,24 @@ struct clothhip_handle : HostPlan {
         float pop_sigma = 0.0f;
         int32_t pop_flags = 0;
     } pol;
+    // The supervised trainer of the shared network (api_fit.hip: clothhip_fit_data_*, clothhip_policy_fit*); a new network
+    // (api_policy.hip's drop_network) restarts the optimizer through fit_forget below, nothing else outside api_fit.hip touches it.
+    struct Fit {
+        // the dataset: n rows of cap allocated, d_obs [cap][3P] and d_lab [cap][4] float32 (grown geometrically, contents kept)
+        Buffer<float> d_obs, d_lab;
+        int64_t n = 0, cap = 0;
+        // the optimizer: moments d_m, d_v [n_params] (SGD's u is d_m) and the 1-based count of steps taken. opt_zero: the moments are to
+        // be read as zeros (the next step clears them first) -- what a reset is, so that a reset needs no device work
+        Buffer<float> d_m, d_v;
+        int64_t opt_t = 0;
+        bool opt_zero = true;
+        // one step's scratch, sized on demand: the index table of a call, the hidden activations and y, the two dZ tables, the split batch
+        // sums of a weight gradient, the gradient (blob layout), the losses of a call
+        Buffer<int32_t> d_idx;
+        Buffer<float> d_act, d_dz, d_part, d_grad;
+        Buffer<double> d_loss;
+    } fit;
+    void fit_forget() { fit.opt_t = 0; fit.opt_zero = true; }
 };
 
 // f(float{}) or f(double{}) by the handle's precision: a launch that exists in both precisions is written once, as a generic lambda

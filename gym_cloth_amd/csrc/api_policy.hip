@@ -26,8 +26,8 @@ static int check_members(const int32_t *member, int64_t n, int64_t rows, const c
         if (member[e] < 0 || member[e] >= rows) return fail(CLOTHHIP_EINVAL, "%s[%lld] = %d outside [0, %lld)", what, (long long)e, member[e], (long long)rows);
     return 0;
 }
-// the handle without a network of either kind (the memory stays with the handle for the next one)
-static void drop_network(clothhip_handle *h) { h->pol.mlp = MlpDesc{}; h->pol.pop_rows = 0; h->pol.mlp_n_params = 0; h->pol.pop_generated = false; }
+// the handle without a network of either kind (the memory stays with the handle for the next one); the trainer's moments belonged to the old one
+static void drop_network(clothhip_handle *h) { h->fit_forget(); h->pol.mlp = MlpDesc{}; h->pol.pop_rows = 0; h->pol.mlp_n_params = 0; h->pol.pop_generated = false; }
 static MlpDesc mlp_desc(int32_t n_layers, const int32_t *widths, const float *params, const int32_t *member, size_t stride) {
     MlpDesc d = {};
     d.n_layers = n_layers;

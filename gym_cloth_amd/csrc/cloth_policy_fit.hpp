@@ -1,0 +1,177 @@
+// cloth_policy_fit.hpp -- the supervised trainer of the handle's shared policy network (cloth_policy_mlp.hpp: the blob it updates in place):
+// forward, backward and one optimizer step over a minibatch of stored (observation row, action label) pairs (no reference counterpart: the
+// refit half of a DAgger / behaviour-cloning iteration). Included only by api_fit.hip, which owns the order of the launches.
+//
+//   L = 1 / (4 B) sum_r sum_k (y_rk - a_rk)^2,  dL/dy = (y - a) / (2 B);  ReLU' = 1 where the pre-activation is > 0, else 0 (the mask is read
+//   from the stored activation: relu(z) > 0 exactly when z > 0).
+//
+// ONE tiled matrix product, fit_gemm, does the three products of every layer on the f32-input matrix instruction
+// v_mfma_f32_32x32x2_f32 (exact float32: per output element a k-ascending fmaf chain, one rounding per product -- the fit minimises the loss
+// of the very float32 function the launch evaluates):
+//   forward          H_l   = act(H_l-1 W_l^T + b_l)      A = H_l-1 [B][in]  k-contiguous, B = W_l [out][in] k-contiguous   (NT), bias (+ ReLU)
+//   weight gradient  dW_l  = dZ_l^T H_l-1                A = dZ_l  [B][out] m-contiguous, B = H_l-1 [B][in] n-contiguous   (TN), none
+//   input gradient   dZ_l-1 = (dZ_l W_l) * [H_l-1 > 0]   A = dZ_l  [B][out] k-contiguous, B = W_l [out][in] n-contiguous   (NN), mask
+//   Layer 0's H_-1 is the dataset read through the minibatch's index table (`rows`): no gathered copy.
+//
+// THE ORDER OF THE ARITHMETIC (fixed; no floating-point atomics anywhere)
+//   * an output element is ONE accumulator: products added for k ascending from 0 within its k range, out-of-range elements of a tile are
+//     zeros in LDS (a + 0 * 0 leaves a finite accumulator's bits alone), then the epilogue (+ b, ReLU / mask);
+//   * the batch sum of a weight gradient is split into FIT_SPLIT_ROWS-row ranges (a function of B alone), each range one accumulator
+//     written to its own slab; k_fit_reduce adds the slabs in ascending range order. B <= FIT_SPLIT_ROWS: one range, written directly;
+//   * db_l[j] = sum_r dZ_l[r][j], r ascending, one thread per j (k_fit_colsum);
+//   * dZ_L-1 = fl(fl(y - a) / fl(2 B)); the loss sums (double)(y - a)^2 in double: thread t of 256 takes elements t, t + 256, ... ascending,
+//     the 256 sums are added by a halving tree in LDS (k_fit_loss, one workgroup);
+//   * the optimizer (k_fit_adam / k_fit_sgd) is elementwise, each operation one float32 rounding (the library is built with
+//     -ffp-contract=off; division and sqrtf are the correctly rounded ones, no fast-math flag reaches this unit).
+//   The forward's summation order differs from mlp_eval's (64 interleaved lane sums and a butterfly there), so the trainer's y need not equal
+//   clothhip_policy_eval's bits; the blob it writes is evaluated by mlp_eval as any uploaded blob is.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace clothhip {
+
+constexpr int FIT_MAX_BATCH = 4096;       // = CLOTHHIP_FIT_MAX_BATCH
+constexpr int FIT_SPLIT_ROWS = 256;       // rows of the batch one accumulator of a weight gradient sums
+constexpr int FIT_TILE = 64, FIT_BK = 16, FIT_THREADS = 256;      // a workgroup: 64 x 64 outputs, 4 waves of 32 x 32, k in steps of 16
+constexpr int FIT_LDS_LD = FIT_TILE + 1;  // LDS images are [k][m] / [k][n], rows padded by one float
+
+enum { FIT_EPI_NONE = 0, FIT_EPI_BIAS = 1, FIT_EPI_BIAS_RELU = 2, FIT_EPI_MASK = 3 };
+
+// C[M][N] (+ z * c_slab) = sum_{k in the z-th range of k_chunk} A(m, k) B(k, n)
+struct FitGemmArgs {
+    const float *A, *B;         // A_KC: A(m, k) = A[row(m) * lda + k], else A[k * lda + m];  B_KC: B(k, n) = B[n * ldb + k], else B[row(k) * ldb + n]
+    const int32_t *rows;        // optional indirection of the storage row of the operand that is the dataset (A when A_KC, B when !B_KC)
+    const float *bias;          // [N]   FIT_EPI_BIAS*
+    const float *mask;          // [M][ldc]  FIT_EPI_MASK: C = mask > 0 ? C : 0
+    float *C;
+    int64_t lda, ldb, ldc, c_slab;
+    int32_t M, N, K, k_chunk;
+};
+
+typedef float fit_f32x16 __attribute__((ext_vector_type(16)));
+
+template <bool A_KC, bool B_KC, int EPI, bool ROWS> __global__ __launch_bounds__(FIT_THREADS) void k_fit_gemm(FitGemmArgs a) {
+    __shared__ float As[FIT_BK][FIT_LDS_LD], Bs[FIT_BK][FIT_LDS_LD];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int m0 = blockIdx.y * FIT_TILE, n0 = blockIdx.x * FIT_TILE;
+    const int k_begin = blockIdx.z * a.k_chunk, k_end = min(a.K, k_begin + a.k_chunk);
+    const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;      // this wave's 32 x 32 corner of the tile
+    fit_f32x16 acc;
+    for (int i = 0; i < 16; i++) acc[i] = 0.0f;
+    // staging: 64 x 16 of each operand, zeros outside the matrices, 4 elements per thread and operand with the contiguous index on the
+    // lanes. The next tile's elements are loaded into registers while this tile's products run (the arithmetic and its order are untouched).
+    int ar[4], ak[4], br[4], bk[4];      // r: the m (or n) index in the tile, k: the k index
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        if (A_KC) { ak[i] = tid & 15; ar[i] = (tid >> 4) + 16 * i; } else { ar[i] = tid & 63; ak[i] = (tid >> 6) + 4 * i; }
+        if (B_KC) { bk[i] = tid & 15; br[i] = (tid >> 4) + 16 * i; } else { br[i] = tid & 63; bk[i] = (tid >> 6) + 4 * i; }
+    }
+    float va[4], vb[4];
+    auto fetch = [&](int k0) {
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int m = m0 + ar[i], k = k0 + ak[i];
+            va[i] = 0.0f;
+            if (m < a.M && k < k_end) va[i] = A_KC ? a.A[(size_t)(ROWS ? a.rows[m] : m) * a.lda + k] : a.A[(size_t)k * a.lda + m];
+            const int n = n0 + br[i], kb = k0 + bk[i];
+            vb[i] = 0.0f;
+            if (n < a.N && kb < k_end) vb[i] = B_KC ? a.B[(size_t)n * a.ldb + kb] : a.B[(size_t)(ROWS ? a.rows[kb] : kb) * a.ldb + n];
+        }
+    };
+    fetch(k_begin);
+    for (int k0 = k_begin; k0 < k_end; k0 += FIT_BK) {
+#pragma unroll
+        for (int i = 0; i < 4; i++) { As[ak[i]][ar[i]] = va[i]; Bs[bk[i]][br[i]] = vb[i]; }
+        __syncthreads();
+        if (k0 + FIT_BK < k_end) fetch(k0 + FIT_BK);
+        // lane l holds A[i = l & 31][k = l >> 5] and B[k = l >> 5][j = l & 31] of each 32 x 32 x 2 step
+#pragma unroll
+        for (int ks = 0; ks < FIT_BK; ks += 2) {
+            const float av = As[ks + (lane >> 5)][wm + (lane & 31)], bv = Bs[ks + (lane >> 5)][wn + (lane & 31)];
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc, 0, 0, 0);
+        }
+        __syncthreads();
+    }
+    // C/D: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
+    float *C = a.C + (size_t)blockIdx.z * a.c_slab;
+    const int n = n0 + wn + (lane & 31);
+    if (n >= a.N) return;
+    float bj = 0.0f;
+    if (EPI == FIT_EPI_BIAS || EPI == FIT_EPI_BIAS_RELU) bj = a.bias[n];
+#pragma unroll
+    for (int reg = 0; reg < 16; reg++) {
+        const int m = m0 + wm + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
+        if (m >= a.M) continue;
+        float v = acc[reg];
+        if (EPI == FIT_EPI_BIAS || EPI == FIT_EPI_BIAS_RELU) v = v + bj;
+        if (EPI == FIT_EPI_BIAS_RELU) v = v < 0.0f ? 0.0f : v;
+        if (EPI == FIT_EPI_MASK) v = a.mask[(size_t)m * a.ldc + n] > 0.0f ? v : 0.0f;
+        C[(size_t)m * a.ldc + n] = v;
+    }
+}
+
+// out[i] = slab_0[i] + slab_1[i] + ... in ascending order, i < n (the split batch sum of a weight gradient)
+__global__ __launch_bounds__(256) void k_fit_reduce(const float *part, int64_t slab, int32_t n_slabs, float *out, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float s = part[i];
+    for (int z = 1; z < n_slabs; z++) s = s + part[(size_t)z * slab + i];
+    out[i] = s;
+}
+
+// db[j] = sum_r dz[r][j], r ascending
+__global__ __launch_bounds__(64) void k_fit_colsum(const float *dz, int32_t B, int32_t n_out, float *db) {
+    const int j = blockIdx.x * 64 + threadIdx.x;
+    if (j >= n_out) return;
+    float s = 0.0f;
+    for (int r = 0; r < B; r++) s = s + dz[(size_t)r * n_out + j];
+    db[j] = s;
+}
+
+// dz[r][k] = fl(fl(y - a) / fl(2 B)) with a = lab[rows[r]][k]; *loss = sum (double)(y - a)^2 / (4 B). One workgroup of 256.
+__global__ __launch_bounds__(256) void k_fit_loss(const float *y, const float *lab, const int32_t *rows, int32_t B, float *dz, double *loss) {
+    __shared__ double red[256];
+    const int tid = threadIdx.x, n = 4 * B;
+    const float two_b = (float)(2 * B);
+    double s = 0.0;
+    for (int i = tid; i < n; i += 256) {
+        const float yv = y[i], av = lab[(size_t)rows[i >> 2] * 4 + (i & 3)];
+        const float d = yv - av;
+        dz[i] = d / two_b;
+        const double dd = (double)yv - (double)av;
+        s = s + dd * dd;
+    }
+    red[tid] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) red[tid] = red[tid] + red[tid + o];
+        __syncthreads();
+    }
+    if (tid == 0) *loss = red[0] / (double)(4 * (int64_t)B);
+}
+
+// Adam, every line one float32 operation: a_t = (float)(lr sqrt(1 - beta2^t) / (1 - beta1^t)), omb1 = (float)(1 - beta1), omb2 = (float)(1 - beta2)
+__global__ __launch_bounds__(256) void k_fit_adam(float *theta, float *m, float *v, const float *g, int64_t n, float a_t, float beta1, float omb1,
+                                                  float beta2, float omb2, float eps) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float gi = g[i];
+    const float m1 = beta1 * m[i], m2 = omb1 * gi, mi = m1 + m2;
+    const float gg = gi * gi, v1 = beta2 * v[i], v2 = omb2 * gg, vi = v1 + v2;
+    const float den = __builtin_sqrtf(vi) + eps, q = mi / den, step = a_t * q;
+    m[i] = mi; v[i] = vi;
+    theta[i] = theta[i] - step;
+}
+
+// SGD with momentum: u = fl(fl(mu u) + g); theta = fl(theta - fl(lr u))
+__global__ __launch_bounds__(256) void k_fit_sgd(float *theta, float *u, const float *g, int64_t n, float lr, float mu) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float u1 = mu * u[i], ui = u1 + g[i], step = lr * ui;
+    u[i] = ui;
+    theta[i] = theta[i] - step;
+}
+
+}  // namespace clothhip

@@ -160,7 +160,7 @@ def dagger_rollout(env, expert='oracle_corner', n_actions=12, beta=0.5, seed=0, 
     where dagger_mixture(n_actions, E, beta, seed) says so (ClothVecEnv.step_many(policy='mlp', expert=..., expert_mix=...)); episodes
     that end are reset inside the launch. Returns dict(obs float32[T, E, 3P]: what each slot's policy saw (envs.slot_start_obs),
     labels float64[T, E, 4]: the expert's action there (NaN where ran is False), took bool[T, E]: the expert acted, ran bool[T, E],
-    out: step_many's dict). The caller aggregates (obs[ran], labels[ran]) over iterations and fits; nothing is trained here."""
+    out: step_many's dict). Nothing is trained here: dagger_fit below aggregates (obs[ran], labels[ran]) and refits on the device."""
     from .envs import slot_start_obs
     mix = dagger_mixture(n_actions, env.E, beta, seed)
     obs_before = np.asarray(env.state, dtype=np.float32).reshape(env.E, -1)
@@ -168,3 +168,16 @@ def dagger_rollout(env, expert='oracle_corner', n_actions=12, beta=0.5, seed=0, 
                         expert_mix=mix, expert_choices=expert_choices)
     return {'obs': slot_start_obs(out, obs_before), 'labels': out['expert_actions'], 'took': out['expert_took'], 'ran': out['ran'],
             'out': out}
+
+
+def dagger_fit(env, trainer, roll, n_steps=100, batch_size=64, seed=0):
+    """The refit half of a DAgger iteration, on the device: append the rows of `roll` (dagger_rollout's dict) that ran --
+    roll['obs'][ran], roll['labels'][ran] -- to `trainer`'s dataset (policies.MLPTrainer on `env`; D <- D u D_i), then take n_steps
+    optimizer steps on minibatches of batch_size rows of everything gathered so far (MLPTrainer.step(n_steps, batch_size, seed)). The
+    env's network is updated in place: the next dagger_rollout runs the fitted weights. Returns dict(losses float64[n_steps]: each
+    step's loss before its update, rows: the dataset's size, appended: the rows this call added)."""
+    if trainer.env is not env:
+        raise ValueError("the trainer belongs to another env")
+    ran = np.asarray(roll['ran'], dtype=bool)
+    rows = trainer.append(roll['obs'][ran], roll['labels'][ran]) if ran.any() else trainer.size()
+    return {'losses': trainer.step(n_steps, batch_size, seed), 'rows': rows, 'appended': int(ran.sum())}

@@ -16,6 +16,8 @@ MLPPolicy            no reference counterpart: a small fully-connected network o
 MLPPopulation        no reference counterpart: one MLP per env slot -- G perturbed copies of a centre network made on the device
                      (ClothBatch.population_perturb), rolled out in ONE episode launch, and the evolution-strategies update summed on
                      the device (ClothBatch.population_combine)
+MLPTrainer           no reference counterpart: the supervised refit of the shared network on the device (ClothBatch.fit_*), Adam or SGD over a
+                     device-resident dataset of (observation, label) rows; fit_reference is its float64 numpy yardstick
 """
 import numpy as np
 
@@ -413,3 +415,111 @@ class MLPPopulation(object):
         self._blob = (self._blob + d).astype(np.float32)
         self.center = unpack_mlp(self.widths, self._blob)
         self.perturb(self.generation + 1)
+
+
+def fit_reference(layers, obs, labels, idx):
+    """Pure-numpy float64 loss and gradient of the trainer's objective, for tests and for users who want to check a fit:
+    L = 1 / (4 B) sum_r sum_k (y_rk - a_rk)^2 over the rows idx [B] of (obs [n, in], labels [n, 4]) -- torch.nn.MSELoss() -- with ReLU
+    after every layer but the last and ReLU' = 1 where the pre-activation is > 0, else 0. obs, labels and the weights are rounded to
+    float32 first (what the device stores), the arithmetic is float64. Returns (loss, [(dW, db), ...]) in `layers`' shapes."""
+    ix = np.asarray(idx, dtype=np.int64).reshape(-1)
+    Ws = [np.asarray(W, dtype=np.float32).astype(np.float64) for W, _ in layers]
+    bs = [np.asarray(b, dtype=np.float32).astype(np.float64) for _, b in layers]
+    x = np.asarray(obs, dtype=np.float32).astype(np.float64)[ix]
+    a = np.asarray(labels, dtype=np.float64).astype(np.float32).astype(np.float64)[ix]
+    B, L = len(ix), len(Ws)
+    hs = [x]
+    for l in range(L):
+        z = hs[-1] @ Ws[l].T + bs[l]
+        hs.append(np.maximum(z, 0.0) if l + 1 < L else z)
+    d = hs[-1] - a
+    loss = float((d * d).sum() / (4.0 * B))
+    g = d / (2.0 * B)
+    grads = [None] * L
+    for l in range(L - 1, -1, -1):
+        grads[l] = (g.T @ hs[l], g.sum(axis=0))
+        if l:
+            g = (g @ Ws[l]) * (hs[l] > 0.0)
+    return loss, grads
+
+
+def adam_reference(theta, m, v, g, t, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8):
+    """The device's Adam step restated in numpy float32, operation by operation (include/clothhip.h, clothhip_policy_fit): t is the
+    1-based step count. Returns the new (theta, m, v), float32."""
+    f = np.float32
+    b1, b2, g = f(beta1), f(beta2), np.asarray(g, dtype=f)
+    a_t = f(float(f(lr)) * np.sqrt(1.0 - float(b2) ** t) / (1.0 - float(b1) ** t))
+    omb1, omb2 = f(1.0 - float(b1)), f(1.0 - float(b2))
+    m = (b1 * np.asarray(m, dtype=f)).astype(f) + (omb1 * g).astype(f)
+    v = (b2 * np.asarray(v, dtype=f)).astype(f) + (omb2 * (g * g).astype(f)).astype(f)
+    q = m / (np.sqrt(v).astype(f) + f(eps)).astype(f)
+    return (np.asarray(theta, dtype=f) - (a_t * q.astype(f)).astype(f)).astype(f), m.astype(f), v.astype(f)
+
+
+def sgd_reference(theta, u, g, lr=1e-3, momentum=0.0):
+    """The device's SGD step in numpy float32: u = fl(fl(mu u) + g), theta = fl(theta - fl(lr u)). Returns the new (theta, u)."""
+    f = np.float32
+    u = ((f(momentum) * np.asarray(u, dtype=f)).astype(f) + np.asarray(g, dtype=f)).astype(f)
+    return (np.asarray(theta, dtype=f) - (f(lr) * u).astype(f)).astype(f), u
+
+
+class MLPTrainer(object):
+    """Supervised training of the env's shared network ON THE DEVICE (no reference counterpart; ClothBatch.fit_*): a mean-squared-error
+    fit of (observation row, action label) pairs by Adam or SGD with momentum, the refit half of a DAgger / behaviour-cloning iteration.
+    `policy_or_layers` is a policies.MLPPolicy or a list of (W, b) layers; the constructor puts it on the env (ClothVecEnv.set_policy,
+    which also restarts the optimizer). The dataset lives on the device and grows by append (DAgger's D <- D u D_i); step trains the
+    network in place, so the next step_many(policy='mlp') and policy_actions run the fitted weights with no download and no upload;
+    layers() downloads them. Whoever puts another network on the env afterwards replaces the fitted one.
+
+    The minibatches are a table: step(n_steps, batch_size, seed) draws RandomState(seed).randint(0, n, size=(n_steps, batch_size)) as
+    int32 -- a function of (seed, n, n_steps, batch_size) alone."""
+
+    def __init__(self, env, policy_or_layers, optimizer='adam', lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, momentum=0.0):
+        from . import _lib
+        if optimizer not in _lib.FIT_OPTIMIZERS:
+            raise ValueError("optimizer must be one of %r (got %r)" % (sorted(_lib.FIT_OPTIMIZERS), optimizer))
+        self.env = env
+        self.hyper = dict(optimizer=optimizer, lr=float(lr), beta1=float(beta1), beta2=float(beta2), eps=float(eps), momentum=float(momentum))
+        layers = getattr(policy_or_layers, 'layers', policy_or_layers)
+        self.widths, blob = pack_mlp(layers, n_in=3 * env.P)
+        self.n_params = int(blob.size)
+        env.set_policy(policy_or_layers)
+        env.batch.fit_clear()
+
+    @staticmethod
+    def index_table(n, n_steps, batch_size, seed):
+        """int32[n_steps, batch_size] rows of a dataset of n: RandomState(seed).randint(0, n, size=(n_steps, batch_size))."""
+        if int(n) < 1 or int(n_steps) < 0 or int(batch_size) < 1:
+            raise ValueError("index_table needs n >= 1, n_steps >= 0, batch_size >= 1")
+        return np.random.RandomState(seed).randint(0, int(n), size=(int(n_steps), int(batch_size))).astype(np.int32)
+
+    def append(self, obs, labels):
+        """Add rows to the dataset (obs [n, 3P], labels [n, 4], finite); returns its size."""
+        return self.env.batch.fit_append(obs, labels)
+
+    def size(self):
+        return self.env.batch.fit_size()
+
+    def clear(self):
+        self.env.batch.fit_clear()
+
+    def step(self, n_steps, batch_size, seed):
+        """n_steps optimizer steps on minibatches of batch_size rows drawn by index_table(size(), n_steps, batch_size, seed); returns
+        float64[n_steps], each step's loss before its update."""
+        n = self.size()
+        if n < 1:
+            raise ValueError("the dataset is empty: append first")
+        return self.env.batch.fit(self.index_table(n, n_steps, batch_size, seed), **self.hyper)
+
+    def grad(self, idx):
+        """(loss, [(dW, db), ...]) over the dataset rows idx at the present weights, float32 from the device; nothing is updated."""
+        loss, g = self.env.batch.fit_grad(idx)
+        return loss, unpack_mlp(self.widths, g)
+
+    def layers(self):
+        """The network as the device holds it now: [(W, b), ...] float32, by download (clothhip_get_policy_mlp)."""
+        return unpack_mlp(self.widths, self.env.batch.get_policy_mlp(0, self.n_params))
+
+    def reset(self):
+        """Zero the optimizer's moments and step count; the weights and the dataset stay."""
+        self.env.batch.fit_reset()

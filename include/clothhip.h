@@ -449,6 +449,52 @@ int clothhip_run_actions_labels(clothhip_handle *h, double *labels, void **d_lab
  * grid other than 25x25, HIGHEST_POINT on a grid whose row of heights exceeds 64 KiB of LDS (more than 16 384 points in float32). Synchronous; clothhip_last_kernel_ms gives the kernel's time (the last chunk's). Leaves an arming alone. */
 int clothhip_policy_label(clothhip_handle *h, int32_t expert, int32_t clip_act_space, const float *obs_rows, int64_t n,
                           const int32_t *side, const int32_t *choice, double *actions_out);
+
+/* FIT the handle's shared network ON THE DEVICE (no reference counterpart: the refit half of a DAgger / behaviour-cloning iteration):
+ * a mean-squared-error fit of (observation row, action label) pairs that updates the float32 blob of clothhip_set_policy_mlp in place,
+ * so the next episode launch runs the new weights with no download and no upload. csrc/cloth_policy_fit.hpp has the kernels and the
+ * order of the arithmetic.
+ * THE DATASET lives on the handle's device and survives across calls (DAgger's D <- D u D_i). clothhip_fit_data_append adds n pairs:
+ * obs_rows[n][3P] (host float32, element 3 i + ax as clothhip_policy_eval reads it) and labels[n][4] (host doubles, stored as
+ * (float)label). CLOTHHIP_EINVAL for n < 0, a NULL table with n > 0, or a non-finite observation or label (after the rounding to
+ * float) -- nothing is appended then; the rows of slots that did not run carry NaN labels (clothhip_run_actions_labels), so the
+ * caller passes the rows that ran. The storage grows geometrically. _clear empties it (the memory stays), _size reports the rows.
+ * The dataset belongs to the handle: clothhip_fork does not carry it and clothhip_set_policy_* leave it alone. */
+int clothhip_fit_data_append(clothhip_handle *h, const float *obs_rows, const double *labels, int64_t n);
+int clothhip_fit_data_clear(clothhip_handle *h);
+int clothhip_fit_data_size(clothhip_handle *h, int64_t *n);
+/* THE LOSS over a minibatch of B dataset rows idx[0 .. B) (host int32, repeats allowed and counted as often), with y the network's
+ * float32 output and a the stored label:   L = 1 / (4 B) sum_r sum_k (y_rk - a_rk)^2   (torch.nn.MSELoss()), so dL/dy = (y - a) / (2 B);
+ * ReLU's derivative is 1 where the pre-activation is > 0, else 0. clothhip_policy_fit_grad computes L (a double: the squares are summed
+ * in double in a fixed order) and dL/dtheta (grad_out[n_params] float32, the blob's layout) at the handle's present weights and updates
+ * nothing. All arithmetic is float32, on an fp64 handle too, on the f32-input matrix instructions; every reduction has one fixed order
+ * and there are no floating-point atomics, so two runs give the same bits. The trainer's forward sums in another order than
+ * clothhip_policy_eval, so its y need not equal that function's bits. */
+int clothhip_policy_fit_grad(clothhip_handle *h, const int32_t *idx, int32_t B, float *grad_out, double *loss_out);
+/* The optimizer. All fields are floats; lr, eps, momentum finite and >= 0, beta1 and beta2 in [0, 1).
+ *   CLOTHHIP_FIT_ADAM  with t the 1-based count of steps since the last reset, the host computes in double
+ *        a_t = lr sqrt(1 - beta2^t) / (1 - beta1^t)  and hands the device (float)a_t, (float)(1 - beta1), (float)(1 - beta2); per parameter,
+ *        every fl one float32 operation (no contraction; division and square root correctly rounded):
+ *        m = fl(fl(beta1 m) + fl((1 - beta1) g));  v = fl(fl(beta2 v) + fl((1 - beta2) fl(g g)));
+ *        theta = fl(theta - fl(a_t fl(m / fl(sqrtf(v) + eps))))
+ *   CLOTHHIP_FIT_SGD   u = fl(fl(momentum u) + g);  theta = fl(theta - fl(lr u))
+ * No weight decay, no per-row weights. SGD's u and Adam's m are ONE table: change the optimizer through clothhip_policy_fit_reset. */
+enum { CLOTHHIP_FIT_ADAM = 0, CLOTHHIP_FIT_SGD = 1 };
+typedef struct ClothFitParams { float optimizer /* CLOTHHIP_FIT_* */, lr, beta1, beta2, eps, momentum; } ClothFitParams;
+/* n_steps optimizer steps; step s uses the rows idx[s][0 .. B) (host int32 [n_steps][B]: which rows a step uses is the caller's table)
+ * and loss_out[s] (may be NULL) is the loss BEFORE that step's update. The gradient inside a step is bit for bit what
+ * clothhip_policy_fit_grad returns for the same weights and rows (the same kernels). The moments and the step count persist across
+ * calls; clothhip_policy_fit_reset zeroes them, and so do clothhip_set_policy_mlp and clothhip_set_policy_population. Synchronous;
+ * clothhip_last_kernel_ms gives the time of all n_steps steps on the device.
+ * CLOTHHIP_ESTATE (both calls): no shared network on the handle, a population on it (the fit trains the ONE shared network), a launch
+ * in flight, an empty dataset. CLOTHHIP_EINVAL: B < 1 or B > CLOTHHIP_FIT_MAX_BATCH (the activations of one step: at most 4 hidden and
+ * 2 gradient tables of B x 256 floats and the split batch sums of the weight gradients, some 60 MB at the cap), n_steps < 0, an index
+ * outside [0, dataset size), an unknown optimizer, a non-finite or negative hyper-parameter or a beta outside [0, 1), a NULL table.
+ * A refused call changes nothing: not the network, not the moments, not the step count. */
+#define CLOTHHIP_FIT_MAX_BATCH 4096
+int clothhip_policy_fit(clothhip_handle *h, const ClothFitParams *p, const int32_t *idx, int32_t n_steps, int32_t B, double *loss_out);
+int clothhip_policy_fit_reset(clothhip_handle *h);
+
 int clothhip_run_actions(clothhip_handle *h, const ClothEpisodeParams *ep, int32_t T, int32_t policy,
                          const double *actions, int32_t actions_on_device, const int32_t *policy_arg,
                          const ClothResetScript *scripts, int32_t n_scripts, int32_t *num_steps, uint8_t *done,

@@ -5,7 +5,10 @@ refit by numpy.linalg.lstsq on everything gathered so far,  with beta = 0.5^i (i
 the mean coverage after each env's last action per iteration (and with --out FILE also appends the lines there); profiles/dagger.txt
 holds a run. That record claims nothing: a linear map of 1875 positions is a poor smoother, the point is that the loop runs and what
 it costs.
-    python3 tools/dagger_demo.py [--envs 64] [--slots 12] [--iters 4] [--out FILE]"""
+With --hidden 64,64 --fit device the policy is an MLP with those hidden widths and the refit runs ON THE DEVICE (policies.MLPTrainer
+through demos.dagger_fit: the rows are appended to the handle's dataset and Adam steps update the network in place, so the next
+iteration's launch runs the fitted weights with no upload); each iteration's line then splits its time into rollout / append / fit.
+    python3 tools/dagger_demo.py [--envs 64] [--slots 12] [--iters 4] [--out FILE] [--hidden 64,64 --fit device [--fit-steps 200] [--batch 256]]"""
 import argparse
 import os
 import sys
@@ -17,9 +20,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import bench                                          # noqa: E402
-from gym_cloth_amd.demos import dagger_rollout        # noqa: E402
+from gym_cloth_amd.demos import dagger_fit, dagger_rollout        # noqa: E402
 from gym_cloth_amd.envs import ClothVecEnv            # noqa: E402
-from gym_cloth_amd.policies import MLPPolicy          # noqa: E402
+from gym_cloth_amd.policies import MLPPolicy, MLPTrainer          # noqa: E402
 
 LINES = []
 
@@ -36,13 +39,70 @@ def fit_linear(obs, labels):
     return [(X[:-1].T.astype(np.float32), X[-1].astype(np.float32))]
 
 
+def run_device(args):
+    """The MLP / device-fit variant: one MLPTrainer for the whole run, its dataset and its network stay on the device."""
+    E, T = args.envs, args.slots
+    hidden = [int(w) for w in args.hidden.split(",") if w]
+    cfg = bench.bench_cfg(25, 0.02, "tier1")
+    cfg["env"]["force_grab"] = True
+    env = ClothVecEnv(cfg, n_envs=E, precision="f32", consume_domrand_draws=False)
+    widths = [3 * env.P] + hidden + [4]
+    r = np.random.RandomState(0)
+    layers = [((r.normal(size=(widths[l + 1], widths[l])) / np.sqrt(widths[l])).astype(np.float32), np.zeros(widths[l + 1], dtype=np.float32))
+              for l in range(len(widths) - 1)]
+    trainer = MLPTrainer(env, MLPPolicy(env, layers), optimizer="adam", lr=args.lr)
+    say("DAgger demo: %d cloths 25x25 fp32 tier 1 (force_grab), MLP policy hidden %r fitted on the device (Adam, lr %g, %d steps of %d rows per "
+        "iteration), %d slots per launch, beta = 0.5^i, expert oracle_corner" % (E, hidden, args.lr, args.fit_steps, args.batch, T))
+    for i in range(args.iters):
+        env.seed([2000 + e for e in range(E)])
+        env.reset()
+        t0 = time.perf_counter()
+        roll = dagger_rollout(env, expert="oracle_corner", n_actions=T, beta=0.5 ** i, seed=i)
+        dt = time.perf_counter() - t0
+        kernel_ms = env.batch.last_kernel_ms
+        ran = roll["ran"]
+        cov = roll["out"]["actual_coverage"]
+        last = np.array([cov[np.nonzero(ran[:, e])[0][-1], e] for e in range(E) if ran[:, e].any()])
+        err = np.abs(roll["out"]["actions"][ran & ~roll["took"]] - roll["labels"][ran & ~roll["took"]])
+        t0 = time.perf_counter()
+        rows = trainer.append(roll["obs"][ran], roll["labels"][ran])
+        da = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        fit = dagger_fit(env, trainer, {"ran": np.zeros_like(ran), "obs": roll["obs"], "labels": roll["labels"]}, n_steps=args.fit_steps,
+                         batch_size=args.batch, seed=i)
+        df = time.perf_counter() - t0
+        say("iteration %d: beta %.3f, %4d labelled states (%4d acted by the expert), mean coverage after the last action %.4f, "
+            "mean |learner action - label| %.4f, rollout %.0f ms (kernel %.0f ms), append %.1f ms, fit on %d rows %.0f ms (device %.0f ms), "
+            "loss %.4f -> %.4f" % (i, 0.5 ** i, int(ran.sum()), int(roll["took"].sum()), float(last.mean()),
+                                  float(err.mean()) if err.size else float("nan"), dt * 1e3, kernel_ms, da * 1e3, rows, df * 1e3,
+                                  env.batch.last_kernel_ms, fit["losses"][0], fit["losses"][-1]))
+    env.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=64)
     ap.add_argument("--slots", type=int, default=12)
     ap.add_argument("--iters", type=int, default=4)
     ap.add_argument("--out", default=None, help="also append the printed lines to this file")
+    ap.add_argument("--hidden", default="", help="hidden widths of an MLP policy, e.g. 64,64 (needs --fit device); default: the linear policy")
+    ap.add_argument("--fit", choices=("lstsq", "device"), default="lstsq", help="lstsq: numpy on the host (linear policy); device: MLPTrainer")
+    ap.add_argument("--fit-steps", type=int, default=200)
+    ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--lr", type=float, default=1e-3)
     args = ap.parse_args()
+    if (args.fit == "device") != bool(args.hidden):
+        ap.error("--hidden WIDTHS and --fit device go together (the lstsq refit is for the linear policy)")
+    if args.fit == "device":
+        run_device(args)
+    else:
+        run_linear(args)
+    if args.out:
+        with open(args.out, "a") as fh:
+            fh.write("\n".join(LINES) + "\n")
+
+
+def run_linear(args):
     E, T = args.envs, args.slots
     cfg = bench.bench_cfg(25, 0.02, "tier1")
     cfg["env"]["force_grab"] = True
@@ -72,9 +132,6 @@ def main():
                 i, 0.5 ** i, int(ran.sum()), int(roll["took"].sum()), float(last.mean()), float(err.mean()) if err.size else float("nan"),
                 dt * 1e3, env.batch.last_kernel_ms, sum(len(o) for o in data_obs), df * 1e3))
     env.close()
-    if args.out:
-        with open(args.out, "a") as fh:
-            fh.write("\n".join(LINES) + "\n")
 
 
 if __name__ == "__main__":

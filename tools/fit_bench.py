@@ -1,0 +1,115 @@
+#!/usr/bin/env python3
+"""What a step of the device trainer (clothhip_policy_fit, csrc/cloth_policy_fit.hpp) costs, measured. It prints its figures (and with
+--out FILE also appends them there); a run of it is quoted, with the command, in profiles/policy_fit.txt and DESIGN 4.3.4.
+
+One ClothBatch of one 25x25 cloth (3P = 1875 inputs), a dataset of 8192 uniform rows with uniform labels, networks with hidden widths
+[64, 64] and [256, 256, 256], minibatches of B = 256 and 4096 rows:
+  * ms per Adam step: `--steps` steps in ONE clothhip_policy_fit call (no host work between the steps), device time by HIP events
+    (clothhip_last_kernel_ms) and wall time of the call, the median of `--rounds` calls after one warm-up call;
+  * the f32 FLOP/s that is: 6 B sum_l in_l out_l per step (forward, weight gradient, input gradient: 2 B in out each; the input gradient of
+    layer 0 is not computed, so 4 B in_0 out_0 there), beside the 157 TF f32-matrix peak of the MI355X;
+  * the same steps in numpy float32 (BLAS matmuls, the same Adam) on the host, wall time.
+The smaller shapes are launch- and latency-bound (a step is 4 to 6 kernel launches per layer): the tool says what a step costs there, it
+does not claim a rate.
+    python3 tools/fit_bench.py [--steps 20] [--rounds 5] [--out FILE]"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import bench                                                    # noqa: E402
+from gym_cloth_amd.batch import ClothBatch                      # noqa: E402
+
+LINES = []
+PEAK_TF = 157.0
+
+
+def say(s=""):
+    print(s, flush=True)
+    LINES.append(s)
+
+
+def layers_of(widths, seed=7):
+    r = np.random.RandomState(seed)
+    return [((r.normal(size=(widths[l + 1], widths[l])) / np.sqrt(widths[l])).astype(np.float32),
+             (r.normal(size=widths[l + 1]) / np.sqrt(widths[l])).astype(np.float32)) for l in range(len(widths) - 1)]
+
+
+def flop_per_step(widths, B):
+    return sum((4 if l == 0 else 6) * B * widths[l] * widths[l + 1] for l in range(len(widths) - 1))
+
+
+def numpy_steps(layers, rows, labels, table, lr=1e-3, b1=0.9, b2=0.999, eps=1e-8):
+    """The same Adam steps in numpy float32 (BLAS); returns the wall seconds."""
+    f = np.float32
+    Ws, bs = [W.copy() for W, _ in layers], [b.copy() for _, b in layers]
+    par = Ws + bs
+    ms, vs = [np.zeros_like(p) for p in par], [np.zeros_like(p) for p in par]
+    L = len(Ws)
+    t0 = time.perf_counter()
+    for t, idx in enumerate(table, start=1):
+        hs = [rows[idx]]
+        for l in range(L):
+            z = hs[-1] @ Ws[l].T + bs[l]
+            hs.append(np.maximum(z, 0) if l + 1 < L else z)
+        g = (hs[-1] - labels[idx]) / f(2 * len(idx))
+        gW, gb = [None] * L, [None] * L
+        for l in range(L - 1, -1, -1):
+            gW[l], gb[l] = g.T @ hs[l], g.sum(axis=0)
+            if l:
+                g = (g @ Ws[l]) * (hs[l] > 0)
+        a_t = f(lr * np.sqrt(1 - b2 ** t) / (1 - b1 ** t))
+        for p, m, v, gr in zip(par, ms, vs, gW + gb):
+            m *= f(b1); m += f(1 - b1) * gr
+            v *= f(b2); v += f(1 - b2) * gr * gr
+            p -= a_t * m / (np.sqrt(v) + f(eps))
+    return time.perf_counter() - t0
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--rows", type=int, default=8192)
+    ap.add_argument("--out", default=None, help="also append the printed lines to this file")
+    args = ap.parse_args()
+    b = ClothBatch(bench.bench_cfg(25, 0.02, "tier1"), n_envs=1, precision="f32")
+    r = np.random.RandomState(3)
+    rows = r.uniform(-1, 1, size=(args.rows, 3 * b.P)).astype(np.float32)
+    labels = r.uniform(-1, 1, size=(args.rows, 4)).astype(np.float32)
+    t0 = time.perf_counter()
+    b.fit_append(rows, labels)
+    say("fit_bench: 25x25 (1875 inputs), dataset %d rows appended in %.1f ms; %d Adam steps per call, median of %d calls; f32-matrix peak %.0f TF"
+        % (args.rows, (time.perf_counter() - t0) * 1e3, args.steps, args.rounds, PEAK_TF))
+    for hidden in ([64, 64], [256, 256, 256]):
+        widths = [3 * b.P] + hidden + [4]
+        layers = layers_of(widths)
+        for B in (256, 4096):
+            table = r.randint(0, args.rows, size=(args.steps, B)).astype(np.int32)
+            b.set_policy_mlp(layers)
+            b.fit(table)                                        # warm-up (allocations, first launches)
+            dev, wall = [], []
+            for _ in range(args.rounds):
+                t0 = time.perf_counter()
+                b.fit(table)
+                wall.append((time.perf_counter() - t0) * 1e3 / args.steps)
+                dev.append(b.last_kernel_ms / args.steps)
+            host = numpy_steps(layers, rows, labels, table) * 1e3 / args.steps
+            fl = flop_per_step(widths, B)
+            d = float(np.median(dev))
+            say("hidden %-15r B %4d: device %.3f ms/step (min %.3f, max %.3f), wall %.3f ms/step, %.2f GFLOP/step -> %.2f TF (%.1f %% of peak); "
+                "numpy float32 on the host %.2f ms/step" % (hidden, B, d, min(dev), max(dev), float(np.median(wall)), fl / 1e9, fl / d / 1e9,
+                                                          100.0 * fl / d / 1e9 / PEAK_TF, host))
+    b.close()
+    if args.out:
+        with open(args.out, "a") as fh:
+            fh.write("\n".join(LINES) + "\n")
+
+
+if __name__ == "__main__":
+    main()
