@@ -384,9 +384,11 @@ struct LdsLayout {
     // LDS_TABLE_SLOTS (the eight-wave LEAN build): like LDS_TABLE, plus the table slots of every particle's six own springs (u16 [6][Ppad]): the strain
     // pre-pass of the LEAN arithmetic needs the slot of a flagged spring, and read it from the L2-resident gather table otherwise
     // lst 1 (the fp64 LEAN build): the per-particle stencil constants (StepArgs::lstc, 16 bytes each) resident in LDS
-    __host__ __device__ LdsLayout(int tsz, int Ppad, int Spad, int HT, int table, int cp, int lst) {
+    // front: unused records in front of `cur` (Variant::cur_front_pad_records: the LEAN-native gather reads an absent neighbour there)
+    __host__ __device__ LdsLayout(int tsz, int Ppad, int Spad, int HT, int table, int cp, int lst, int front = 0) {
         int o = 0;
         auto take = [&](int bytes) { int r = o; o += (bytes + 15) / 16 * 16; return r; };
+        take(4 * front * tsz);
         cur = take(4 * Ppad * tsz);
         eps = take(EPSTATE_LDS_BYTES);   // EpState (fused episodes)
         wtab = take(table != LDS_TABLE_NONE ? Spad * (tsz == 8 ? 16 : 8) : 0);   // WEnt<T>[Spad]
@@ -416,7 +418,7 @@ struct LdsLayout {
 };
 // the carve-up of variant v: the one place a Variant becomes an LdsLayout (kernel, and the host's plan: layout_plan.hpp)
 __host__ __device__ __forceinline__ LdsLayout lds_layout(Variant v, int Ppad, int Spad, int HT, int cell_copy) {
-    return LdsLayout(v.tsz, Ppad, Spad, HT, v.lds_table_mode(), cell_copy, v.lean64() ? 1 : 0);
+    return LdsLayout(v.tsz, Ppad, Spad, HT, v.lds_table_mode(), cell_copy, v.lean64() ? 1 : 0, v.cur_front_pad_records());
 }
 
 // LEAN variant (Variant::lean): the 12-slot gather stencil of a particle is recomputed from its grid position

@@ -88,6 +88,10 @@ __global__ __launch_bounds__(NT, (Variant{(int)sizeof(T), NT, PPT, TAB, REST_REG
     };
     (void)lean_rest64; (void)lstc;
     uint32_t rc[RELAXED ? PPT : 1];         // RELAXED: the particle's grid position, r | c << 8 (parities of the colour classes)
+    // Hooke gather and strain pre-pass without gather entries (stepper_traits.hpp: lean_native_gather). The variant exists for the 25x25 class only
+    // (layout_plan.hpp: up to 768 points, n_side <= 27), which is what the records in front of `cur` cover; a specialised build checks its own grid
+    constexpr bool LEAN_NATIVE = LEAN && !LEAN64 && V.lean_native_gather();
+    static_assert(!LEAN_NATIVE || (2 * NS <= V.cur_front_pad_records() && 2 * 27 <= V.cur_front_pad_records()), "the records in front of `cur` must cover the stencil's reach (two rows)");
     auto lean_entry = [&](int i, uint32_t vmq, int sl) -> uint32_t {      // a gather entry without its table-slot field
         const bool ok = ((vmq >> sl) & 1u) != 0u;
         return (uint32_t)(ok ? i + lean_off(sl, KA_N(&A)) : i) | (ok ? HK_VALID : 0u) | (sl < HK_SLOTS / 2 ? HK_ASB : 0u) |
@@ -101,6 +105,10 @@ __global__ __launch_bounds__(NT, (Variant{(int)sizeof(T), NT, PPT, TAB, REST_REG
     {   // HBM -> LDS / registers, coalesced
         const T *gp = A.pos + (size_t)e * 3 * Ppad, *gq = A.prev + (size_t)e * 3 * Ppad;
         const uint8_t *gc = A.cnt + (size_t)e * Ppad;
+        if constexpr (V.cur_front_pad_records() > 0) {       // (no loop: a variant without them keeps its code to the last instruction)
+            static_assert(V.cur_front_pad_records() <= NT, "one thread per record in front of `cur`");
+            if (tid < V.cur_front_pad_records()) cur[tid - V.cur_front_pad_records()] = Pt<T>{(T)0, (T)0, (T)0, (T)0};
+        }
         for (int i = tid; i < Ppad; i += NT)
             cur[i] = Pt<T>{gp[i], gp[Ppad + i], gp[2 * Ppad + i], w_make<T>(gc[i])};
 #pragma unroll

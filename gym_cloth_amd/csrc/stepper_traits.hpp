@@ -53,6 +53,15 @@ struct Variant {
     // self-collision, register-lean form: a thread's owned particles one per trip of the member loop; two per trip where the register cap
     // is 80 (six per CU): 23 fewer spill reloads, +1.6 % at 1 536 cloths
     constexpr bool collide_two_visits_per_trip() const { return tab <= TAB_LEAN_6; }
+    // The eight-wave fp32 LEAN build (the headline): waves 0 and 1 own two particles per lane, so every parallel phase lasts as long as their
+    // instruction stream (profiles/seed_gather_ab.txt).
+    // Its Hooke gather and strain pre-pass: the neighbour of stencil position k is read at the owner's LDS address plus the position's offset (a
+    // compile-time constant, the DS instruction's immediate, in the grid-specialised builds), its validity is bit k of the particle's mask -- no
+    // table-format gather entry is built and taken apart per slot.
+    // An absent position's read (value discarded) must stay inside the cloth's LDS: `cur` gets that many unused records in front of it
+    // (2 N <= 54 for the 25x25 class this build exists for; behind `cur` the layout's own regions follow)
+    constexpr bool lean_native_gather() const { return tsz == 4 && tab == TAB_LDS_SLOTS; }
+    constexpr int cur_front_pad_records() const { return lean_native_gather() ? 64 : 0; }
     // the grid-specialised builds (cloth_common.hpp: spec_*): 50x50 at two cloths per CU has a hash table sized to the LDS left (not a power of
     // two); every specialised 25x25 layout but the builds for five / six per CU has the cell-ordered record copy
     constexpr bool spec_ht_fitted() const { return tab == TAB_LARGE_2; }

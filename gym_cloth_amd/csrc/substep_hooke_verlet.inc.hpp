@@ -2,7 +2,7 @@
 // A FRAGMENT of k_run_schedule (episode_loop.hpp), included at its place in the kernel body: not a function. Turning the substep's phases into
 // __forceinline__ functions over a context struct was tried (round 5): same instructions, but the register allocation of the 128-VGPR variants
 // shifts -- three more scratch reloads in the substep loop, -1.4 % on the headline -- so the split is textual and the ISA is bit-identical to the
-// one-file kernel's. Names it uses from the kernel body: pm, Ak_, tid, cur, pvx/pvy/pvz, gt, rr, vm, lean_entry, lean_rest, rest_at.
+// one-file kernel's. Names it uses from the kernel body: pm, Ak_, tid, cur, pvx/pvy/pvz, gt, rr, vm, lean_entry, lean_rest, rest_at, LEAN_NATIVE.
         // ---- gravity + Hooke gather + Verlet (cloth.pyx:216-256) ----------------------------------
         if (pm & PH_HOOKE) {
             CLOTH_PHASE_ARGS()
@@ -23,9 +23,12 @@
                     uint32_t gl[HK_SLOTS];
                     int iq_ = tid + q * NT; uint4 lw_ = uint4{0u, 0u, 0u, 0u}; if constexpr (LEAN64) lw_ = lstc[iq_]; uint32_t vq_ = LEAN64 ? lw_.x : vm[(LEAN && !LEAN64) ? q : 0];
                     if (LEAN) asm volatile("" : "+v"(iq_), "+v"(vq_));     // opaque: the stencil is recomputed every substep, not hoisted and held
+                    // LEAN_NATIVE: no gather entries. Stencil position sl is read at the owner's address + the position's offset (in a specialised build the
+                    // DS instruction's immediate: `cur` lies two rows and more behind the start of LDS, so every immediate is >= 0), valid = bit sl of the mask. An absent position's read lands in the
+                    // records in front of `cur` or in the layout's regions behind it; the selects below discard it
 #pragma unroll
                     for (int sl = 0; sl < HK_SLOTS; sl++)
-                        gl[sl] = LEAN ? lean_entry(iq_, vq_, sl) : (GT_REG ? gt[GT_REG ? q : 0][sl] : Ak_->gather[sl * Ppad + tid + q * NT]);
+                        gl[sl] = LEAN_NATIVE ? 0u : LEAN ? lean_entry(iq_, vq_, sl) : (GT_REG ? gt[GT_REG ? q : 0][sl] : Ak_->gather[sl * Ppad + tid + q * NT]);
 #if defined(CLOTHHIP_MUTATE) && CLOTHHIP_MUTATE == 1
                     // MUTANT 1 (tools/run_mutants.sh; never a product build): ONE particle adds two of its incident springs in swapped list
                     // order (stencil positions 2 and 3: both shearing springs, same rest-length class) -- cloth.pyx:221-237 keeps list order
@@ -41,20 +44,26 @@
                     Pt<T> nbq[HK_AHEAD];
 #pragma unroll
                     for (int sl = 0; sl < HK_AHEAD; sl++) {
+                        if constexpr (LEAN_NATIVE) nbq[sl] = cur[iq_ + lean_off(sl, KA_N(Ak_))];
+                        else {
                         uint32_t g = gl[sl];
                         asm volatile("" : "+v"(g));         // opaque: keeps the address math inside the substep loop
                         gl[sl] = g;
                         nbq[sl] = cur[g & HK_NBR_MASK];
+                        }
                     }
 #pragma unroll
                     for (int sl = 0; sl < HK_SLOTS; sl++) {
                         const uint32_t g = gl[sl];
                         const Pt<T> nb = nbq[sl % HK_AHEAD];
                         if (sl + HK_AHEAD < HK_SLOTS) {
+                            if constexpr (LEAN_NATIVE) nbq[sl % HK_AHEAD] = cur[iq_ + lean_off(sl + HK_AHEAD, KA_N(Ak_))];
+                            else {
                             uint32_t gn = gl[sl + HK_AHEAD];
                             asm volatile("" : "+v"(gn));
                             gl[sl + HK_AHEAD] = gn;
                             nbq[sl % HK_AHEAD] = cur[gn & HK_NBR_MASK];
+                            }
                         }
                         __builtin_amdgcn_sched_barrier(0);  // the reads above stay above the arithmetic below
                         const T r = LEAN64 ? lean_rest64(sl, lw_) : LEAN ? lean_rest(sl) : (REST_R ? rr[REST_R ? q : 0][sl] : rest_at((g >> HK_POS_SHIFT) & HK_POS_MASK));
@@ -62,7 +71,7 @@
                         const T dx = nb.x - me.x, dy = nb.y - me.y, dz = nb.z - me.z;
                         const T l = fastnorm<T>(dx, dy, dz);                                      // :231
                         const T fm = dev_div<T>(kk * (l - r), l);                                 // :232
-                        const bool valid = (g & HK_VALID) != 0u;
+                        const bool valid = LEAN_NATIVE ? (vq_ & (1u << sl)) != 0u : (g & HK_VALID) != 0u;
                         fx = valid ? mad<T>(fm, dx, fx) : fx; fy = valid ? mad<T>(fm, dy, fy) : fy; fz = valid ? mad<T>(fm, dz, fz) : fz;   // :236-237
                     }
                     nx[q] = mad<T>(fx, k.dsm, mad<T>(k.damp, me.x - pvx[q], me.x));               // :249

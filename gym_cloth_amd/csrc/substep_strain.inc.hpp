@@ -2,7 +2,7 @@
 // A FRAGMENT of k_run_schedule (episode_loop.hpp), included at its place in the kernel body: not a function. Turning the substep's phases into
 // __forceinline__ functions over a context struct was tried (round 5): same instructions, but the register allocation of the 128-VGPR variants
 // shifts -- three more scratch reloads in the substep loop, -1.4 % on the headline -- so the split is textual and the ISA is bit-identical to the
-// one-file kernel's. Names it uses from the kernel body: pm, Ak_, tid, lane, cur, misc, wtab, g_rest, pslot, gt, rr, vm, rc, lean_entry, lean_rest, rest_at, st_*, tph / TSTAMP, mode (census build).
+// one-file kernel's. Names it uses from the kernel body: pm, Ak_, tid, lane, cur, misc, wtab, g_rest, pslot, gt, rr, vm, rc, lean_entry, lean_rest, rest_at, LEAN_NATIVE, st_*, tph / TSTAMP, mode (census build).
         // ---- strain limit + tear (cloth.pyx:258-296) ---------------------------------------------------
         // (1) all threads: which springs would stretch/tear at the CURRENT positions? Only the first and the last of them
         //     (in window-table order) are kept: a spring untouched by earlier corrections of the sweep behaves exactly as
@@ -66,18 +66,22 @@
                         uint32_t gl[HK_SLOTS / 2];
                         int iq_ = tid + q * NT; uint4 lw_ = uint4{0u, 0u, 0u, 0u}; if constexpr (LEAN64) lw_ = lstc[iq_]; uint32_t vq_ = LEAN64 ? lw_.x : vm[(LEAN && !LEAN64) ? q : 0];
                         if (LEAN) asm volatile("" : "+v"(iq_), "+v"(vq_));
+                        // LEAN_NATIVE, as in the Hooke phase: the owner's address + the position's offset, valid = bit sl of the mask
 #pragma unroll
                         for (int sl = 0; sl < HK_SLOTS / 2; sl++)
-                            gl[sl] = LEAN ? lean_entry(iq_, vq_, sl) : (GT_REG ? gt[GT_REG ? q : 0][sl] : Ak_->gather[sl * Ppad + tid + q * NT]);
+                            gl[sl] = LEAN_NATIVE ? 0u : LEAN ? lean_entry(iq_, vq_, sl) : (GT_REG ? gt[GT_REG ? q : 0][sl] : Ak_->gather[sl * Ppad + tid + q * NT]);
                         // software pipeline, as in the Hooke phase: two neighbour reads in flight ahead of the test
                         constexpr int PP_AHEAD = 2;
                         Pt<T> nbq[PP_AHEAD];
 #pragma unroll
                         for (int sl = 0; sl < PP_AHEAD; sl++) {
+                            if constexpr (LEAN_NATIVE) nbq[sl] = cur[iq_ + lean_off(sl, KA_N(Ak_))];
+                            else {
                             uint32_t g = gl[sl];
                             asm volatile("" : "+v"(g));
                             gl[sl] = g;
                             nbq[sl] = cur[g & HK_NBR_MASK];
+                            }
                         }
                         // (a) branch-free: which of the six springs come within the slack band of their limit at all?
                         uint32_t cand = 0u;
@@ -87,10 +91,13 @@
                             const uint32_t g = gl[sl];
                             const Pt<T> nb = nbq[sl % PP_AHEAD];
                             if (sl + PP_AHEAD < HK_SLOTS / 2) {
+                                if constexpr (LEAN_NATIVE) nbq[sl % PP_AHEAD] = cur[iq_ + lean_off(sl + PP_AHEAD, KA_N(Ak_))];
+                                else {
                                 uint32_t gn = gl[sl + PP_AHEAD];
                                 asm volatile("" : "+v"(gn));
                                 gl[sl + PP_AHEAD] = gn;
                                 nbq[sl % PP_AHEAD] = cur[gn & HK_NBR_MASK];
+                                }
                             }
                             __builtin_amdgcn_sched_barrier(0);
                             T r = LEAN64 ? lean_rest64(sl, lw_) : LEAN ? lean_rest(sl) : (REST_R ? rr[REST_R ? q : 0][sl] : rest_at((g >> HK_POS_SHIFT) & HK_POS_MASK));
@@ -102,10 +109,10 @@
                             const T t11 = r * k.c11, tt = r * k.tear_thresh;
                             const T tmin = t11 < tt ? t11 : tt;
 #if defined(CLOTHHIP_MUTATE) && CLOTHHIP_MUTATE == 4       // MUTANT 4 (see strain_sweep_lean): the pre-pass flags both-pinned springs too
-                            const bool pre = ((g & (HK_VALID | HK_ASB)) == (HK_VALID | HK_ASB)) &
+                            const bool pre = (LEAN_NATIVE ? (vq_ & (1u << sl)) != 0u : (g & (HK_VALID | HK_ASB)) == (HK_VALID | HK_ASB)) &
                                              (len2 > tmin * tmin * ((T)1 - filt_slack<T>()));
 #else
-                            const bool pre = ((g & (HK_VALID | HK_ASB)) == (HK_VALID | HK_ASB)) &
+                            const bool pre = (LEAN_NATIVE ? (vq_ & (1u << sl)) != 0u : (g & (HK_VALID | HK_ASB)) == (HK_VALID | HK_ASB)) &
                                              !((cme_ != 0) & (w_cnt(nb.w) != 0)) &
                                              (len2 > tmin * tmin * ((T)1 - filt_slack<T>()));
 #endif
