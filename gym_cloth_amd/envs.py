@@ -12,14 +12,16 @@ What is mirrored here is exactly what sits between the gym API and the physics h
 Blender observations, the OpenGL viewer, logging-to-file and pickle I/O are out of scope (SURVEY.md section 2);
 obs_type is forced to the '1d' observation (cloth_env.py:196-200).
 """
+import collections
 import copy
+import time
 
 import numpy as np
-import ctypes as _ctypes
 import yaml
 
 from . import _lib, seeding
 from .batch import ClothBatch, make_schedules
+from .reset_streams import ScriptChain, domrand_draws, export_mt, import_mt, prevent_oob, randval_minabs
 
 _REWARD_THRESHOLDS = {           # cloth_env.py:42-50
     'coverage': 0.92, 'coverage-delta': 0.92, 'height': 0.85, 'height-delta': 0.85,
@@ -27,19 +29,14 @@ _REWARD_THRESHOLDS = {           # cloth_env.py:42-50
 }
 _EPS = 1e-5                      # cloth_env.py:52
 
+# What step_many's arguments come to (ClothVecEnv._parse_launch): the policy code, T, the actions / noise table, policy_arg, the expert
+# and its tables, the reset capacity R and where resets come from, what to return.
+_Launch = collections.namedtuple('_Launch', 'pol T actions actions_device_ptr policy_arg expert expert_mix expert_choices R dev_reset '
+                                            'use_rng want_obs images image_kw time_budget_ms')
+# What goes to the device with a launch and comes back changed in place (ClothVecEnv._export_streams): reset scripts or MT19937
+# images (+ their copy from before, export_mt's token), the envs' step counters and episode-over flags.
+_Flight = collections.namedtuple('_Flight', 'scripts mt mt_before mt_token nsteps done_io')
 
-
-def _mt_state_address(rng):
-    """Address of numpy's `mt19937_state { uint32 key[624]; int pos; }` behind a RandomState (its MT19937 bit generator exports
-    it for exactly this kind of access), or None: then get_state() / set_state() are used. Copying 2 500 bytes per env this way
-    instead of building state tuples takes the per-launch RNG hand-over of 512 envs from ~30 ms to ~1 ms."""
-    try:
-        bg = rng._bit_generator
-        if type(bg).__name__ != 'MT19937':
-            return None
-        return int(bg.ctypes.state_address)
-    except Exception:
-        return None
 
 class Box(object):
     """Minimal stand-in for gym.spaces.Box (gym is not a dependency of the hot path)."""
@@ -269,7 +266,7 @@ class ClothVecEnv(object):
         self.last_grabbed = np.zeros(E, dtype=np.int64)
         self.last_iters_pull = np.zeros(E, dtype=np.int64)
         self._ep_done = np.zeros(E, dtype=bool)                      # episode over, reset pending (step_many's auto-reset)
-        self._pending = [None] * E                                   # pre-drawn reset scripts of step_many, per env
+        self._pending = [None] * E                                   # pre-drawn reset scripts of step_many: a ScriptChain per env, or None
         self.total_substeps = 0                                      # executed update() calls, all envs
         self._version = 0                                            # counts the calls that change the env (commit checks it)
         self._policy_mlp = None                                      # the network on the batch (set_policy): an MLPPolicy or its layers
@@ -639,95 +636,30 @@ class ClothVecEnv(object):
         ep.coverage_done = float(_REWARD_THRESHOLDS[self.reward_type])
         return ep
 
-    def _domrand_draws(self, rng):
-        """cloth_env.py:786-789: the draws every reset makes after the scripted actions."""
-        rng.uniform(low=40, high=50)
-        rng.uniform(low=0.7, high=1.3)
-        lim = rng.uniform(low=-15.0, high=15.0)
-        rng.uniform(low=-lim, high=lim, size=(self._wd, self._hd, 3))
-
-    def _draw_script(self, rng, tier, out):
-        """Draw ONE reset from `rng` in the reference's order (cloth.pyx:75; cloth_env.py:851-877 / :959-978) into the
-        script record `out`. Returns (init_side, rng state if the reset runs 2 pulls, rng state if it runs 3 (tier 1))."""
-        init_side = bool(rng.rand() > 0.5)                                               # cloth.pyx:75
-        out['valid'], out['_pad'] = 1, 0
-        if tier == 1:
-            lim = 0.20
-            out['n_pulls'], out['settle_after'] = 3, 0
-            s2 = None
-            for k in range(3):
-                if k == 2:
-                    s2 = rng.get_state()                          # the third pull's draws happen only if coverage >= 0.90
-                pl = out['pull'][k]
-                pl['point'] = rng.randint(self.P)
-                pl['dx'] = self._randval_minabs(rng, -lim, lim, 0.08)
-                pl['dy'] = self._randval_minabs(rng, -lim, lim, 0.08)
-                pl['x'] = pl['y'] = 0.0
-                pl['need_coverage'], pl['coverage_min'] = int(k == 2), 0.90
-                pl['iters_up'] = float(self.iters_up)
-            return init_side, s2, rng.get_state()
-        lim = 0.25                                                                       # tier 3
-        out['n_pulls'], out['settle_after'] = 1, 800
-        pl = out['pull'][0]
-        pl['iters_up'] = rng.uniform(low=200, high=280)
-        pl['x'] = self._randval_minabs(rng, 0.30, 0.70)
-        pl['y'] = self._randval_minabs(rng, 0.30, 0.70)
-        pl['dx'] = self._randval_minabs(rng, -lim, lim, 0.10)
-        pl['dy'] = self._randval_minabs(rng, -lim, lim, 0.10)
-        pl['point'], pl['need_coverage'], pl['coverage_min'] = -1, 0, 0.0
-        st = rng.get_state()
-        return init_side, st, st
+    @property
+    def _tier(self):
+        """1, 2, 3 for init type 'tier1' .. 'tier3', 0 for anything else."""
+        return {'tier1': 1, 'tier2': 2, 'tier3': 3}.get(self._init_type, 0)
 
     def _drop_pending(self, e):
         """Give back the draws of the env's pre-drawn reset scripts (the RNG is parked at the first one's start)."""
         self._pending[e] = None
 
     def _extend_chain(self, e, n):
-        """Make env e's chain of pre-drawn resets at least n long (see _prepare_scripts); the RandomState stays parked.
-        A chain is {'nodes': [{before, after: (state after the unconditional pulls, state after all pulls)}], 'recs':
-        RESET_SCRIPT_DTYPE[n], 'sides': bool[n]}."""
-        from ._lib import RESET_SCRIPT_DTYPE
-        chain = self._pending[e]
-        if chain is None:
-            chain = self._pending[e] = {'nodes': [], 'recs': np.zeros(0, dtype=RESET_SCRIPT_DTYPE), 'sides': np.zeros(0, dtype=bool)}
-        nodes = chain['nodes']
-        if len(nodes) >= n:
-            return chain
-        tier = {'tier1': 1, 'tier3': 3}[self._init_type]
-        rng = self.np_randoms[e]
-        s_start = rng.get_state()
-        if nodes:
-            rng.set_state(nodes[-1]['after'][0])
-            if self._consume_domrand:
-                self._domrand_draws(rng)
-        k0 = len(nodes)
-        recs = np.zeros(n, dtype=RESET_SCRIPT_DTYPE)
-        sides = np.zeros(n, dtype=bool)
-        recs[:k0], sides[:k0] = chain['recs'], chain['sides']
-        for k in range(k0, n):
-            before = rng.get_state()
-            sides[k], s2, s3 = self._draw_script(rng, tier, recs[k])
-            nodes.append({'before': before, 'after': (s2, s3)})
-            rng.set_state(s2)                                     # the chain continues as if only the unconditional pulls ran
-            if self._consume_domrand:
-                self._domrand_draws(rng)
-        chain['recs'], chain['sides'] = recs, sides
-        rng.set_state(s_start)
-        return chain
+        """Make env e's ScriptChain of pre-drawn resets at least n long (see _prepare_scripts); the RandomState stays parked."""
+        if self._pending[e] is None:
+            self._pending[e] = ScriptChain(self._tier, self.P, self.iters_up, (self._wd, self._hd) if self._consume_domrand else None)
+        self._pending[e].extend(self.np_randoms[e], n)
+        return self._pending[e]
 
     def _prepare_scripts(self, n_scripts):
-        """The next `n_scripts` resets of every env, [E, R]. Script k+1 is drawn from the RNG state script k leaves when
-        only its unconditional pulls run (tier 1: two pulls; the third, coverage-conditional one draws further numbers and
-        forks the stream, cloth_env.py:866-877). Scripts that were not consumed stay cached for the next launch; each env's
-        RandomState stays parked where its first pending script starts, so a host-side reset() simply re-draws."""
-        from ._lib import RESET_SCRIPT_DTYPE
+        """The next `n_scripts` resets of every env, [E, R] (reset_streams.ScriptChain). Scripts that were not consumed stay cached
+        for the next launch; each env's RandomState stays parked where its first pending script starts."""
         R = int(n_scripts)
-        scripts = np.zeros((self.E, R), dtype=RESET_SCRIPT_DTYPE)
+        scripts = np.zeros((self.E, R), dtype=_lib.RESET_SCRIPT_DTYPE)
         self._script_sides = np.zeros((self.E, R), dtype=bool)        # Cloth.init_side of each scripted reset (cloth.pyx:75)
         for e in range(self.E):
-            chain = self._extend_chain(e, R)
-            scripts[e] = chain['recs'][:R]
-            self._script_sides[e] = chain['sides'][:R]
+            scripts[e], self._script_sides[e] = self._extend_chain(e, R).take(R)
         return scripts
 
     def _apply_reset_records(self, ie, rb, rst, n_consumed, substeps_out, device_rng):
@@ -795,16 +727,53 @@ class ClothVecEnv(object):
         image_obs takes them): 'img_t' uint8 [T, E, H, W, C], what image_obs would have returned after that step, zeros where
         `ran` is False, and 'reset_img' [E, R, H, W, C] beside 'reset_obs' (None without in-kernel resets), zeros for the resets
         the launch did not consume. A tier-2 image swaps the side colours by the init_side its episode was dropped with."""
-        from . import _lib
-        import time as _time
         self._version += 1
-        _tp = [_time.perf_counter()]
+        tp = [time.perf_counter()]
         prof = self.__dict__.setdefault('host_prof', {})
 
         def _lap(name):
-            now = _time.perf_counter()
-            prof[name] = prof.get(name, 0.0) + now - _tp[0]
-            _tp[0] = now
+            now = time.perf_counter()
+            prof[name] = prof.get(name, 0.0) + now - tp[0]
+            tp[0] = now
+        a = self._parse_launch(actions, n_actions, policy, auto_reset, want_obs, actions_device_ptr, max_resets, time_budget_ms,
+                               device_rng, policy_choices, images, image_kw, policy_noise, expert, expert_mix, expert_choices)
+        fl = self._export_streams(a)
+        _lap('prepare_resets')
+        self._launch(a, fl)
+        _lap('launch')
+        if a.dev_reset and not a.use_rng:                             # while the kernel runs: draw ahead for the NEXT launch
+            for e in range(self.E):
+                self._extend_chain(e, 2 * a.R)
+        _lap('draw_ahead(overlapped)')
+        rec, rst, obs_t, robs = self.batch.run_actions_end()
+        op = self.batch.op_ticks()
+        labels = self.batch.run_actions_labels(a.T) if a.expert is not None else None
+        _lap('wait+download')
+        out, n_consumed, side_t = self._account_launch(rec, rst, fl.nsteps, fl.done_io, a.dev_reset, a.use_rng, op, labels, a.expert_mix)
+        _lap('bookkeeping')
+        self._commit_streams(a, fl, rst, n_consumed)
+        _lap('rng_commit')
+        if a.images is not None:                                      # the launch's tables are still on the device
+            self._render_launch(a, out, rst, robs is not None, n_consumed, side_t)
+            _lap('images')
+        obs = self.state
+        _lap('obs_download')
+        if reset_tail and auto_reset and self._ep_done.any():
+            obs = self.reset(mask=self._ep_done.copy())
+        out['obs'] = obs
+        if expert is not None:                                        # (an un-armed launch returns exactly the keys it always did)
+            out['init_side_t'] = side_t                               # tier 2: the side each slot's cloth was dropped from (expert_actions on stored rows)
+        if a.want_obs:
+            out['obs_t'], out['reset_obs'] = obs_t, robs
+        return out
+
+    # ---- the stages of step_many: parse, begin (export streams, launch), account, commit streams, images ------------------------
+    def _parse_launch(self, actions, n_actions, policy, auto_reset, want_obs, actions_device_ptr, max_resets, time_budget_ms,
+                      device_rng, policy_choices, images, image_kw, policy_noise, expert, expert_mix, expert_choices):
+        """step_many's arguments -> a _Launch; every refusal, in a fixed order. The ORDER IS BEHAVIOUR: callers get a ValueError for bad
+        arguments before anything reaches a device, so up to and including batch._expert_tables this reads nothing of the env but E,
+        _policy_mlp, num_points and _delta_actions, and of the batch nothing but E (tests/test_dagger_host.py's _bare_env has no
+        more); _init_type and init_side are read only after the refusals that need neither."""
         E = self.E
         if policy in (None, 'table'):
             pol = _lib.POLICY_TABLE
@@ -846,95 +815,65 @@ class ClothVecEnv(object):
             if images not in _lib.IMG_FORMATS:
                 raise ValueError("images must be None, 'rgb', 'depth' or 'rgbd' (got %r)" % (images,))
             want_obs = True
-        dev_reset = auto_reset and (self._init_type in ('tier1', 'tier3') or (self._init_type == 'tier2' and device_rng))
+        dev_reset = bool(auto_reset and (self._tier in (1, 3) or (self._tier == 2 and device_rng)))
         R = min(T, 255) if max_resets is None else int(max_resets)      # clothhip_run_actions: n_scripts in [1, 255]
         if dev_reset and not 1 <= R <= 255:
             raise ValueError("max_resets must be in [1, 255] (got %d)" % R)
-        use_rng = dev_reset and device_rng
-        scripts = self._prepare_scripts(R) if (dev_reset and not use_rng) else None
-        mt = gauss = None
-        if use_rng:                                                   # every env's numpy stream, as RandomState.get_state() has it
-            if self._init_type == 'tier2':
-                self.batch.ensure_per_env_rest()                      # the kernel rebuilds each env's rest lengths at a reset
-            for e in range(E):
-                self._drop_pending(e)
-            mt = np.zeros((E, _lib.MT_WORDS), dtype=np.uint32)
-            gauss = [None] * E
-            mt_addr = [_mt_state_address(self.np_randoms[e]) for e in range(E)]
-            row0, row_bytes = mt.ctypes.data, mt.strides[0]
-            for e in range(E):
-                if mt_addr[e]:                                        # key[624] + pos, straight out of numpy's generator state
-                    _ctypes.memmove(row0 + e * row_bytes, mt_addr[e], 625 * 4)
-                else:
-                    st = self.np_randoms[e].get_state()
-                    mt[e, :624], mt[e, 624], gauss[e] = st[1], st[2], st[3:]
-            mt_before = mt.copy()
         parg = None
-        if (pol != _lib.POLICY_TABLE or expert is not None) and self._init_type == 'tier2':
+        if (pol != _lib.POLICY_TABLE or expert is not None) and self._tier == 2:
             parg = np.where(self.init_side, 2, 1).astype(np.int32)                       # analytic.py:108-114, :781-788
         if pol == _lib.POLICY_HIGHEST_POINT:
             parg = np.concatenate([(np.zeros(E, dtype=np.int32) if parg is None else parg)[None, :], policy_choices], axis=0)
-        nsteps = np.ascontiguousarray(self.num_steps, dtype=np.int32)
-        done_io = np.ascontiguousarray(self._ep_done, dtype=np.uint8)
-        _lap('prepare_resets')
-        self.batch.run_actions_begin(self._episode_params(), T, nsteps, done_io, actions=actions, policy=pol,
-                                     policy_arg=parg, scripts=scripts, want_obs=want_obs,
-                                     actions_device_ptr=actions_device_ptr, time_budget_ms=time_budget_ms,
-                                     rng_states=mt, rng_tier={'tier1': 1, 'tier2': 2, 'tier3': 3}.get(self._init_type, 0),
+        return _Launch(pol, T, actions, actions_device_ptr, parg, expert, expert_mix, expert_choices, R, dev_reset,
+                       bool(dev_reset and device_rng), want_obs, images, dict(image_kw or {}), time_budget_ms)
+
+    def _export_streams(self, a):
+        """Where the launch's resets come from, ready for the device: the next R scripts of every env (host-drawn), or every env's
+        numpy stream as RandomState.get_state() has it (device-drawn; pending scripts give their draws back first). -> _Flight."""
+        scripts = mt = mt_before = token = None
+        if a.use_rng:
+            if self._tier == 2:
+                self.batch.ensure_per_env_rest()                      # the kernel rebuilds each env's rest lengths at a reset
+            self._pending = [None] * self.E
+            mt, token = export_mt(self.np_randoms)
+            mt_before = mt.copy()
+        elif a.dev_reset:
+            scripts = self._prepare_scripts(a.R)
+        return _Flight(scripts, mt, mt_before, token, np.ascontiguousarray(self.num_steps, dtype=np.int32),
+                       np.ascontiguousarray(self._ep_done, dtype=np.uint8))
+
+    def _launch(self, a, fl):
+        self.batch.run_actions_begin(self._episode_params(), a.T, fl.nsteps, fl.done_io, actions=a.actions, policy=a.pol,
+                                     policy_arg=a.policy_arg, scripts=fl.scripts, want_obs=a.want_obs,
+                                     actions_device_ptr=a.actions_device_ptr, time_budget_ms=a.time_budget_ms,
+                                     rng_states=fl.mt, rng_tier=self._tier,
                                      domrand_words=2 * (3 + self._wd * self._hd * 3) if self._consume_domrand else 0,
-                                     reset_capacity=R, expert=expert, expert_mix=expert_mix, expert_choices=expert_choices)
-        _lap('launch')
-        if dev_reset and not use_rng:                                 # while the kernel runs: draw ahead for the NEXT launch
-            for e in range(E):
-                self._extend_chain(e, 2 * R)
-        _lap('draw_ahead(overlapped)')
-        rec, rst, obs_t, robs = self.batch.run_actions_end()
-        op_ticks, op_substeps = self.batch.op_ticks()
-        labels = self.batch.run_actions_labels(T) if expert is not None else None
-        _lap('wait+download')
+                                     reset_capacity=a.R, expert=a.expert, expert_mix=a.expert_mix, expert_choices=a.expert_choices)
+
+    def _account_launch(self, rec, rst, nsteps, done_io, dev_reset, use_rng, op, labels=None, expert_mix=None):
+        """The host's bookkeeping of a launch, from what it returned alone (no device access, no call on self.batch): the step records
+        rec[T, E] and reset records rst[E, R] (or None) of run_actions_end, the counters nsteps[E] / flags done_io[E] it updated, op =
+        op_ticks(), the expert's labels and mix table. Advances the env's host arrays and returns (out, n_consumed[E]: resets of
+        the launch the host has accounted, side_t[T, E]: init_side as it stood at each slot)."""
         if (rec['ran'] == 2).any():
             raise FloatingPointError("iters_pull does not terminate (non-finite action?)")
+        T, E = rec.shape[0], self.E
         out = {k: np.zeros((T, E)) for k in ('rew', 'actual_coverage', 'start_coverage', 'variance_inv', 'start_variance_inv')}
         for k in ('done', 'ran', 'have_tear', 'out_of_bounds'):
             out[k] = np.zeros((T, E), dtype=bool)
         for k in ('executed', 'n_grabbed', 'num_steps', 'num_sim_steps', 'reset_before', 'reset_substeps'):
             out[k] = np.zeros((T, E), dtype=np.int64)
         out['actions'] = rec['action'].copy()
-        if expert is not None:
+        if labels is not None:
             ran_ = rec['ran'] == 1
             out['expert_actions'] = np.where(ran_[:, :, None], labels, np.nan)
             out['expert_took'] = ran_ & (expert_mix != 0 if expert_mix is not None else False)
         # per env: 100 MHz ticks of this launch spent in {actions, reset pulls, reset settling, the rest} and the update() calls of each
-        out['op_ticks'], out['op_substeps'] = op_ticks, op_substeps
+        out['op_ticks'], out['op_substeps'] = op
         n_consumed = np.zeros(E, dtype=np.int64)
         side_t = np.zeros((T, E), dtype=bool)                         # init_side as it stands at each slot (images of tier 2)
         for t in range(T):
-            r = rec[t]
-            rb = r['reset_before'].astype(np.int64)
-            self._apply_reset_records(np.nonzero(rb)[0], rb, rst, n_consumed, out['reset_substeps'][t], use_rng)
-            side_t[t] = self.init_side
-            ran = r['ran'] == 1
-            executed = np.where(ran, r['executed'], 0).astype(np.int64)
-            self.total_substeps += int(executed.sum())
-            self.have_tear |= ran & (r['tear'] != 0)
-            self.num_sim_steps[ran] += executed[ran]
-            self.num_steps[ran] += 1
-            oob = r['oob'] != 0
-            rew = self._reward(r['action'], ran & (r['n_grabbed'] == 0), r['coverage'], r['variance_inv'], oob, ran,
-                               height=r['n_below_half_thickness'] / float(self.P))
-            term = self._terminal(oob, ran)
-            if not np.array_equal(term[ran], (r['done'] != 0)[ran]):
-                raise RuntimeError("device and host disagree on the terminal test")
-            self._ep_done = np.where(ran, term, self._ep_done)
-            self.last_executed = np.where(ran, executed, self.last_executed)
-            self.last_grabbed = np.where(ran, r['n_grabbed'], self.last_grabbed)
-            self.last_iters_pull = np.where(ran, r['iters_pull'], self.last_iters_pull)
-            out['rew'][t], out['done'][t], out['ran'][t] = rew, term, ran
-            out['executed'][t], out['n_grabbed'][t], out['reset_before'][t] = executed, r['n_grabbed'], rb
-            out['num_steps'][t], out['num_sim_steps'][t] = self.num_steps, self.num_sim_steps
-            out['actual_coverage'][t], out['start_coverage'][t] = self._current_coverage, self._start_coverage
-            out['variance_inv'][t], out['start_variance_inv'][t] = r['variance_inv'], self._start_variance_inv
-            out['have_tear'][t], out['out_of_bounds'][t] = self.have_tear, oob
+            self._account_slot(t, rec[t], rst, out, n_consumed, side_t, use_rng)
         if dev_reset:                                                 # a time slice may end right after a reset
             tail = np.nonzero((rst['consumed'] == 1).sum(axis=1) > n_consumed)[0]
             if len(tail):
@@ -948,52 +887,59 @@ class ClothVecEnv(object):
         settled = np.ones(E, dtype=bool) if rst is None else ~(rst['consumed'] == 2).any(axis=1)
         assert np.array_equal(self.num_steps.astype(np.int32)[settled], nsteps[settled])
         assert np.array_equal(self._ep_done[settled], (done_io != 0)[settled])
-        _lap('bookkeeping')
-        if use_rng:                                                   # the streams as the device left them (a reset cut by the
-            for e in np.nonzero((mt != mt_before).any(axis=1))[0]:    # time slice has drawn too, before any record of it is complete)
-                if mt_addr[e]:                                        # (the cached gaussian of RandomState is not the device's business)
-                    _ctypes.memmove(mt_addr[e], row0 + int(e) * row_bytes, 625 * 4)
-                else:
-                    self.np_randoms[e].set_state(('MT19937', mt[e, :624], int(mt[e, 624])) + tuple(gauss[e]))
-        elif dev_reset:                                               # commit the RNG draws the device consumed
+        return out, n_consumed, side_t
+
+    def _account_slot(self, t, r, rst, out, n_consumed, side_t, use_rng):
+        """Slot t of a launch, r = rec[t]: the resets that preceded it, then what step() does on the host after an action -- for the envs
+        whose slot ran."""
+        rb = r['reset_before'].astype(np.int64)
+        self._apply_reset_records(np.nonzero(rb)[0], rb, rst, n_consumed, out['reset_substeps'][t], use_rng)
+        side_t[t] = self.init_side
+        ran = r['ran'] == 1
+        executed = np.where(ran, r['executed'], 0).astype(np.int64)
+        self.total_substeps += int(executed.sum())
+        self.have_tear |= ran & (r['tear'] != 0)
+        self.num_sim_steps[ran] += executed[ran]
+        self.num_steps[ran] += 1
+        oob = r['oob'] != 0
+        rew = self._reward(r['action'], ran & (r['n_grabbed'] == 0), r['coverage'], r['variance_inv'], oob, ran,
+                           height=r['n_below_half_thickness'] / float(self.P))
+        term = self._terminal(oob, ran)
+        if not np.array_equal(term[ran], (r['done'] != 0)[ran]):
+            raise RuntimeError("device and host disagree on the terminal test")
+        self._ep_done = np.where(ran, term, self._ep_done)
+        self.last_executed = np.where(ran, executed, self.last_executed)
+        self.last_grabbed = np.where(ran, r['n_grabbed'], self.last_grabbed)
+        self.last_iters_pull = np.where(ran, r['iters_pull'], self.last_iters_pull)
+        out['rew'][t], out['done'][t], out['ran'][t] = rew, term, ran
+        out['executed'][t], out['n_grabbed'][t], out['reset_before'][t] = executed, r['n_grabbed'], rb
+        out['num_steps'][t], out['num_sim_steps'][t] = self.num_steps, self.num_sim_steps
+        out['actual_coverage'][t], out['start_coverage'][t] = self._current_coverage, self._start_coverage
+        out['variance_inv'][t], out['start_variance_inv'][t] = r['variance_inv'], self._start_variance_inv
+        out['have_tear'][t], out['out_of_bounds'][t] = self.have_tear, oob
+
+    def _commit_streams(self, a, fl, rst, n_consumed):
+        """Move every env's RandomState past the draws the launch consumed: the streams as the device left them (a reset cut by the
+        time slice has drawn too, before any record of it is complete), or the scripts it ran (ScriptChain.commit)."""
+        if a.use_rng:
+            import_mt(self.np_randoms, fl.mt, fl.mt_before, fl.mt_token)
+        elif a.dev_reset:
             for e in np.nonzero(n_consumed)[0]:
-                chain, c = self._pending[e], int(n_consumed[e])
-                nodes, last_rec = chain['nodes'], chain['recs'][c - 1]
-                n_uncond = int((last_rec['pull']['need_coverage'][:int(last_rec['n_pulls'])] == 0).sum())
-                forked = int(rst[e, c - 1]['pulls_run']) > n_uncond
-                rng = self.np_randoms[e]
-                if forked or c >= len(nodes):                         # forked: the conditional pull ran, later scripts are void
-                    rng.set_state(nodes[c - 1]['after'][1 if forked else 0])
-                    if self._consume_domrand:
-                        self._domrand_draws(rng)
-                    self._pending[e] = None
-                else:
-                    rng.set_state(nodes[c]['before'])
-                    self._pending[e] = {'nodes': nodes[c:], 'recs': chain['recs'][c:], 'sides': chain['sides'][c:]}
-        _lap('rng_commit')
-        if images is not None:                                        # the launch's tables are still on the device
-            tier2 = self._init_type == 'tier2'
-            kw = dict(image_kw or {})
-            img = self.batch.render_obs('slots', valid=out['ran'].reshape(-1), swap_sides=(~side_t).reshape(-1) if tier2 else None,
-                                        fmt=images, **kw)
-            out['img_t'] = img.reshape((T, E) + img.shape[1:])
-            out['reset_img'] = None
-            if robs is not None:
-                sides = (rst['init_side'] != 0) if use_rng else self._script_sides
-                rimg = self.batch.render_obs('resets', valid=(np.arange(R)[None, :] < n_consumed[:, None]).reshape(-1),
-                                             swap_sides=(~sides).reshape(-1) if tier2 else None, fmt=images, **kw)
-                out['reset_img'] = rimg.reshape((E, R) + rimg.shape[1:])
-            _lap('images')
-        obs = self.state
-        _lap('obs_download')
-        if reset_tail and auto_reset and self._ep_done.any():
-            obs = self.reset(mask=self._ep_done.copy())
-        out['obs'] = obs
-        if expert is not None:                                        # (an un-armed launch returns exactly the keys it always did)
-            out['init_side_t'] = side_t                               # tier 2: the side each slot's cloth was dropped from (expert_actions on stored rows)
-        if want_obs:
-            out['obs_t'], out['reset_obs'] = obs_t, robs
-        return out
+                c = int(n_consumed[e])
+                self._pending[e].commit(self.np_randoms[e], c, rst[e, c - 1]['pulls_run'])
+
+    def _render_launch(self, a, out, rst, have_reset_obs, n_consumed, side_t):
+        """out['img_t'] / out['reset_img']: every slot's and every consumed reset's image, from the launch's tables on the device."""
+        tier2 = self._tier == 2
+        img = self.batch.render_obs('slots', valid=out['ran'].reshape(-1), swap_sides=(~side_t).reshape(-1) if tier2 else None,
+                                    fmt=a.images, **a.image_kw)
+        out['img_t'] = img.reshape((a.T, self.E) + img.shape[1:])
+        out['reset_img'] = None
+        if have_reset_obs:
+            sides = (rst['init_side'] != 0) if a.use_rng else self._script_sides
+            rimg = self.batch.render_obs('resets', valid=(np.arange(a.R)[None, :] < n_consumed[:, None]).reshape(-1),
+                                         swap_sides=(~sides).reshape(-1) if tier2 else None, fmt=a.images, **a.image_kw)
+            out['reset_img'] = rimg.reshape((self.E, a.R) + rimg.shape[1:])
 
     # ---- reward / terminal (cloth_env.py:536-715) ------------------------------------------------------------
     def _height_fraction(self):
@@ -1061,8 +1007,8 @@ class ClothVecEnv(object):
         self._version += 1
         m = np.ones(E, dtype=bool) if mask is None else np.asarray(mask, dtype=bool)
         idx = np.nonzero(m)[0]
-        tier = {'tier1': 1, 'tier2': 2, 'tier3': 3}.get(self._init_type)
-        if tier is None:
+        tier = self._tier
+        if not tier:
             raise ValueError(self._init_type)                         # cloth.pyx:131-132
         if not self._delta_actions:
             raise NotImplementedError()                               # cloth_env.py:862, :917, :968
@@ -1107,30 +1053,11 @@ class ClothVecEnv(object):
         self._current_coverage = np.where(m, 0.0, self._current_coverage)
         if self._consume_domrand:                                     # cloth_env.py:786-789 advance the env RNG
             for e in idx:
-                rng = self.np_randoms[e]
-                rng.uniform(low=40, high=50)
-                rng.uniform(low=0.7, high=1.3)
-                lim = rng.uniform(low=-15.0, high=15.0)
-                rng.uniform(low=-lim, high=lim, size=(self._wd, self._hd, 3))
+                domrand_draws(self.np_randoms[e], self._wd, self._hd)
         return self.state
 
-    @staticmethod
-    def _randval_minabs(rng, low, high, minabs=None):                 # cloth_env.py:824-832
-        val = rng.uniform(low=low, high=high)
-        if minabs is not None:
-            assert minabs > 0, minabs
-            assert low < -minabs or high > minabs
-            while np.abs(val) < minabs:
-                val = rng.uniform(low=low, high=high)
-        return val
-
-    @staticmethod
-    def _prevent_oob(val, dval, lower=0.0, upper=1.0):                # cloth_env.py:834-840
-        if val + dval < lower:
-            dval = lower - val
-        elif val + dval > upper:
-            dval = upper - val
-        return dval
+    _randval_minabs = staticmethod(randval_minabs)                    # cloth_env.py:824-832
+    _prevent_oob = staticmethod(prevent_oob)                          # cloth_env.py:834-840
 
     def _reset_actions(self, m, idx, tier):
         E = self.E
@@ -1272,10 +1199,7 @@ class ClothEnv(object):
             v._prev_reward[:] = cov; v._start_coverage[:] = cov; v._start_variance_inv[:] = vinv
             v._current_coverage[:] = 0.0
             if v._consume_domrand:                                     # cloth_env.py:786-789, as in the normal reset
-                rng.uniform(low=40, high=50)
-                rng.uniform(low=0.7, high=1.3)
-                lim = rng.uniform(low=-15.0, high=15.0)
-                rng.uniform(low=-lim, high=lim, size=(v._wd, v._hd, 3))
+                domrand_draws(rng, v._wd, v._hd)
             return self.state
         obs = self._vec.reset()[0]
         self.cloth.init_side = bool(self._vec.init_side[0])

@@ -87,7 +87,9 @@ def test_dagger_mixture_is_seeded_and_degenerates_at_the_ends():
 
 
 def _bare_env(E=3):
-    """A ClothVecEnv's host-only pieces: enough for step_many's argument checks, which come before anything touches a device."""
+    """A ClothVecEnv's host-only pieces: enough for step_many's argument checks, which come before anything touches a device.
+    The order of those checks is behaviour (ClothVecEnv._parse_launch): nothing beyond what is set here may be read before the
+    refusals test_step_many_rejects_bad_expert_arguments expects."""
     from gym_cloth_amd.batch import ClothBatch
     from gym_cloth_amd.envs import ClothVecEnv
     v = ClothVecEnv.__new__(ClothVecEnv)

@@ -65,6 +65,43 @@ def test_step_many_equals_sequential_steps_f64(tier, T, E, device_rng):
     a.close(); b.close()
 
 
+@pytest.mark.parametrize("device_rng", [True, False])
+def test_accounting_stage_replays_a_real_launch_f64(device_rng):
+    """The records of a real launch with in-kernel resets, replayed through step_many's accounting stage on a bare env (host arrays
+    as they stood before the launch, a batch that refuses every access): the launch's `out` and the env's host arrays afterwards,
+    array by array. Ties the hand-written records of tests/test_episode_host.py to the device's."""
+    from test_episode_host import bare_accounting_env
+    E, T = 6, 4
+    acts = np.stack([np.random.RandomState(2000 + e).uniform(-1, 1, size=(T, 4)) for e in range(E)], axis=1)
+    v = _bench_env(E, "f64"); v.reset()
+    w = bare_accounting_env(E, P=v.P, reward_type=v.reward_type, max_actions=v.max_actions, clip_act_space=v._clip_act_space)
+    w.action_space = v.action_space
+    for k in v._SNAP_ARRAYS:
+        setattr(w, k, np.array(getattr(v, k), copy=True))
+    w.total_substeps = v.total_substeps
+    kept, end = {}, v.batch.run_actions_end
+
+    def keeping_end():
+        nsteps, done_io = v.batch._fused[2], v.batch._fused[3]
+        r = end()
+        kept.update(rec=r[0].copy(), rst=r[1].copy(), nsteps=nsteps.copy(), done_io=done_io.copy())
+        return r
+    v.batch.run_actions_end = keeping_end
+    out = v.step_many(acts, device_rng=device_rng)
+    assert out["reset_before"].sum() > 0, "the workload must exercise the in-kernel reset"
+    if not device_rng:
+        w._script_sides = v._script_sides.copy()                   # the sides drawn with the launch's scripts, host data too
+    got, n_consumed, side_t = w._account_launch(kept["rec"], kept["rst"], kept["nsteps"], kept["done_io"], True, device_rng,
+                                                (out["op_ticks"], out["op_substeps"]))
+    assert set(got) == set(out) - {"obs"} and (n_consumed > 0).any()
+    for k in got:
+        assert np.array_equal(got[k], out[k]), k
+    for k in v._SNAP_ARRAYS:
+        assert np.array_equal(getattr(w, k), getattr(v, k)), k
+    assert w.total_substeps == v.total_substeps
+    v.close()
+
+
 @pytest.mark.parametrize("fixture,tier,seed", [("g_env_tier1_1337.npz", "tier1", 1337),
                                                ("g_env_tier3_1337.npz", "tier3", 1337),
                                                ("g_env_tier3_1339.npz", "tier3", 1339)])
