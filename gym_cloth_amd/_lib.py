@@ -109,6 +109,7 @@ class ClothFitParams(C.Structure):
 FIT_ADAM, FIT_SGD = 0, 1
 FIT_OPTIMIZERS = {'adam': FIT_ADAM, 'sgd': FIT_SGD}
 FIT_MAX_BATCH = 4096                # CLOTHHIP_FIT_MAX_BATCH: the most rows of one minibatch
+FIT_SRC_SLOTS, FIT_SRC_RESETS, FIT_SRC_HELD = 0, 1, 2   # CLOTHHIP_FIT_SRC_*: where a row of clothhip_fit_hold / _append_launch lies
 assert C.sizeof(ClothFitParams) == 24
 
 # every symbol include/clothhip.h declares: (name, restype, argtypes)
@@ -163,7 +164,11 @@ SYMBOLS = [
     ("clothhip_fit_data_append", C.c_int, [_vp, C.POINTER(C.c_float), _dp, C.c_int64]),
     ("clothhip_fit_data_clear", C.c_int, [_vp]),
     ("clothhip_fit_data_size", C.c_int, [_vp, C.POINTER(C.c_int64)]),
+    ("clothhip_fit_data_get", C.c_int, [_vp, C.c_int64, C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    ("clothhip_fit_hold", C.c_int, [_vp, _i32p]),
+    ("clothhip_fit_data_append_launch", C.c_int, [_vp, _i32p, C.c_int64]),
     ("clothhip_policy_fit_grad", C.c_int, [_vp, _i32p, C.c_int32, C.POINTER(C.c_float), _dp]),
+    ("clothhip_policy_fit_loss", C.c_int, [_vp, _i32p, C.c_int64, _dp]),
     ("clothhip_policy_fit", C.c_int, [_vp, C.POINTER(ClothFitParams), _i32p, C.c_int32, C.c_int32, _dp]),
     ("clothhip_policy_fit_reset", C.c_int, [_vp]),
     ("clothhip_update", C.c_int, [_vp, C.c_int32, _dp]),

@@ -350,8 +350,12 @@ class ClothBatch(object):
         ep: _lib.ClothEpisodeParams; scripts: RESET_SCRIPT_DTYPE[E, R], each env's next R resets in order.
         expert ('oracle_corner' | 'highest_point' or its CLOTHHIP_POLICY_* code) arms this launch with a silent expert
         (clothhip_run_actions_expert): expert_mix bool[T, E] (None: it never acts), expert_choices int[T, E] (highest point);
-        run_actions_labels() gives its labels after run_actions_end()."""
+        run_actions_labels() gives its labels after run_actions_end(). want_obs='device' writes the observation tables as True does but
+        keeps them on the device (run_actions_end returns None for them): render_obs('slots' / 'resets') and fit_append_launch read them."""
         T = int(n_actions)
+        keep = isinstance(want_obs, str)
+        if keep and want_obs != 'device':
+            raise ValueError("want_obs must be False, True or 'device' (got %r)" % (want_obs,))
         mix, cho = self._expert_tables(expert, expert_mix, expert_choices, T)
         pol = _lib.POLICY_TABLE if policy is None else int(policy)
         on_dev = 0
@@ -388,9 +392,9 @@ class ClothBatch(object):
             check(self._L.clothhip_run_actions_expert(self._h, _lib.EXPERTS.get(expert, expert), T, _lib.u8p(mix), _lib.i32p(cho)))
         check(self._L.clothhip_run_actions_begin(self._h, C.byref(ep), T, pol, ap, on_dev, _lib.i32p(parg), vp(scripts), R,
                                                  _lib.i32p(num_steps), _lib.u8p(done), vp(rng_states), int(rng_tier),
-                                                 int(domrand_words), int(have_rst), int(bool(want_obs)), int(have_robs),
-                                                 float(time_budget_ms)))
-        self._fused = (T, R, num_steps, done, have_rst, bool(want_obs), have_robs, rng_states)
+                                                 int(domrand_words), int(have_rst), 2 if keep else int(bool(want_obs)),
+                                                 2 if keep and have_robs else int(have_robs), float(time_budget_ms)))
+        self._fused = (T, R, num_steps, done, have_rst, bool(want_obs) and not keep, have_robs and not keep, rng_states)
         self._last_launch = (T, R)                       # the shapes of the tables render_obs('slots' / 'resets') reads
 
     def run_actions_end(self):
@@ -630,6 +634,53 @@ class ClothBatch(object):
             raise ValueError("obs and labels must be finite (float32)")
         check(self._L.clothhip_fit_data_append(self._h, self._fp(obs), _lib.dp(lab), obs.shape[0]))
         return self.fit_size()
+
+    def fit_hold(self, src=None):
+        """Fill the handle's held rows (clothhip_fit_hold): src=None -> held[e] = the float32 '1d' observation of env e's present state;
+        src int[E, 2] = (source, row) with _lib.FIT_SRC_* -> held[e] = that row of the last launch's tables ((FIT_SRC_HELD, e) keeps it)."""
+        if src is not None:
+            src = np.asarray(src)
+            if src.shape != (self.E, 2) or not np.issubdtype(src.dtype, np.integer):
+                raise ValueError("src must be integers of shape (%d, 2)" % self.E)
+            src = np.ascontiguousarray(src, dtype=np.int32)
+        check(self._L.clothhip_fit_hold(self._h, _lib.i32p(src)))
+
+    def fit_append_launch(self, rows):
+        """Append pairs that lie on the device (clothhip_fit_data_append_launch): rows int[n, 3] = (source, row, label_row) -- the
+        observation is that row of the last launch's tables or of the held rows, the label row label_row = t * E + e of the last armed
+        launch's labels. ValueError when a named value is not finite (a slot that did not run); nothing is appended then. Returns the
+        dataset's size."""
+        rows = np.asarray(rows)
+        if rows.ndim != 2 or rows.shape[1] != 3 or not np.issubdtype(rows.dtype, np.integer):
+            raise ValueError("rows must be integers of shape (n, 3)")
+        rows = np.ascontiguousarray(rows, dtype=np.int32)
+        check(self._L.clothhip_fit_data_append_launch(self._h, _lib.i32p(rows), rows.shape[0]))
+        return self.fit_size()
+
+    def fit_data(self, first=0, n=None):
+        """(obs float32[n, 3P], labels float32[n, 4]): the stored rows [first, first + n), n=None: to the end (clothhip_fit_data_get)."""
+        first = int(first)
+        n = self.fit_size() - first if n is None else int(n)
+        if first < 0 or n < 0:
+            raise ValueError("first and n must be >= 0 and lie within the dataset")
+        obs = np.zeros((n, 3 * self.P), dtype=np.float32)
+        lab = np.zeros((n, 4), dtype=np.float32)
+        check(self._L.clothhip_fit_data_get(self._h, first, n, self._fp(obs), self._fp(lab)))
+        return obs, lab
+
+    def fit_loss(self, idx):
+        """The MSE of the handle's shared network over the dataset rows idx [n], any n >= 1 (a held-out split by index), forward only
+        (clothhip_policy_fit_loss); for n <= FIT_MAX_BATCH it is fit_grad's loss bit for bit."""
+        a = np.asarray(idx)
+        if a.ndim != 1 or a.size < 1 or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("idx must be a non-empty 1-d integer array")
+        if a.min() < 0 or a.max() > np.iinfo(np.int32).max:
+            raise ValueError("idx must hold row numbers of the dataset")
+        self._fit_n_params()
+        ix = np.ascontiguousarray(a, dtype=np.int32)
+        loss = np.zeros(1, dtype=np.float64)
+        check(self._L.clothhip_policy_fit_loss(self._h, _lib.i32p(ix), ix.size, _lib.dp(loss)))
+        return float(loss[0])
 
     def fit_clear(self):
         """Empty the dataset (clothhip_fit_data_clear); the device memory stays with the handle."""

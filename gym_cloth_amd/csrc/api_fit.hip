@@ -7,13 +7,34 @@
 #include <vector>
 
 #include "api_handle.hpp"
+#include "cloth_fit_gather.hpp"
 #include "cloth_policy_fit.hpp"
 #include "cloth_policy_mlp.hpp"
 
 static_assert(FIT_MAX_BATCH == CLOTHHIP_FIT_MAX_BATCH, "the batch cap of the header and of the kernels");
 static_assert(sizeof(ClothFitParams) == 24, "ClothFitParams is six floats");
+static_assert(FIT_SRC_SLOTS == CLOTHHIP_FIT_SRC_SLOTS && FIT_SRC_RESETS == CLOTHHIP_FIT_SRC_RESETS && FIT_SRC_HELD == CLOTHHIP_FIT_SRC_HELD,
+              "the row sources of the header and of the kernel");
 
 // ---- the dataset (clothhip.h: clothhip_fit_data_*) ------------------------------------------------------------------------------------
+// room for n more rows: grow geometrically into new tables, keep the rows (Buffer::reserve would not), swap them in
+static int grow_dataset(clothhip_handle *h, int64_t n) {
+    auto &f = h->fit;
+    if (f.n + n <= f.cap) return 0;
+    const size_t row = (size_t)3 * h->P;
+    const int64_t cap = std::max<int64_t>(std::max<int64_t>(f.n + n, 2 * f.cap), 64);
+    Buffer<float> obs, lb;
+    if (int rc = obs.reserve((size_t)cap * row * 4)) return rc;
+    if (int rc = lb.reserve((size_t)cap * 4 * 4)) return rc;
+    if (f.n > 0) {
+        HIPCHECK(hipMemcpyAsync(obs, f.d_obs, (size_t)f.n * row * 4, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHECK(hipMemcpyAsync(lb, f.d_lab, (size_t)f.n * 4 * 4, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHECK(hipStreamSynchronize(h->stream));
+    }
+    f.d_obs = std::move(obs); f.d_lab = std::move(lb); f.cap = cap;
+    return 0;
+}
+
 extern "C" int clothhip_fit_data_append(clothhip_handle *h, const float *obs_rows, const double *labels, int64_t n) {
     if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
     if (int rc = check_idle(h)) return rc;
@@ -32,18 +53,7 @@ extern "C" int clothhip_fit_data_append(clothhip_handle *h, const float *obs_row
         if (!std::isfinite(lab[i])) return fail(CLOTHHIP_EINVAL, "labels[%zu][%zu] is not a finite float (a slot that did not run? pass the rows that ran)", i / 4, i % 4);
     }
     HIPCHECK(hipSetDevice(h->device));
-    if (f.n + n > f.cap) {      // grow geometrically into new tables, keep the rows (Buffer::reserve would not), swap them in
-        const int64_t cap = std::max<int64_t>(std::max<int64_t>(f.n + n, 2 * f.cap), 64);
-        Buffer<float> obs, lb;
-        if (int rc = obs.reserve((size_t)cap * row * 4)) return rc;
-        if (int rc = lb.reserve((size_t)cap * 4 * 4)) return rc;
-        if (f.n > 0) {
-            HIPCHECK(hipMemcpyAsync(obs, f.d_obs, (size_t)f.n * row * 4, hipMemcpyDeviceToDevice, h->stream));
-            HIPCHECK(hipMemcpyAsync(lb, f.d_lab, (size_t)f.n * 4 * 4, hipMemcpyDeviceToDevice, h->stream));
-            HIPCHECK(hipStreamSynchronize(h->stream));
-        }
-        f.d_obs = std::move(obs); f.d_lab = std::move(lb); f.cap = cap;
-    }
+    if (int rc = grow_dataset(h, n)) return rc;
     HIPCHECK(hipMemcpyAsync(f.d_obs + (size_t)f.n * row, obs_rows, (size_t)n * row * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipMemcpyAsync(f.d_lab + (size_t)f.n * 4, lab.data(), (size_t)n * 4 * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipStreamSynchronize(h->stream));      // the host tables are never retained; only now do the rows count
@@ -61,6 +71,144 @@ extern "C" int clothhip_fit_data_clear(clothhip_handle *h) {
 extern "C" int clothhip_fit_data_size(clothhip_handle *h, int64_t *n) {
     if (!h || !n) return fail(CLOTHHIP_EINVAL, "NULL argument");
     *n = h->fit.n;
+    return 0;
+}
+
+extern "C" int clothhip_fit_data_get(clothhip_handle *h, int64_t first, int64_t n, float *obs, float *labels) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (int rc = check_idle(h)) return rc;
+    if (first < 0 || n < 0 || first > h->fit.n || n > h->fit.n - first)
+        return fail(CLOTHHIP_EINVAL, "rows [%lld, %lld + %lld) outside the dataset's %lld", (long long)first, (long long)first, (long long)n, (long long)h->fit.n);
+    if (n == 0 || (!obs && !labels)) return 0;
+    const size_t row = (size_t)3 * h->P;
+    HIPCHECK(hipSetDevice(h->device));
+    if (obs) HIPCHECK(hipMemcpyAsync(obs, h->fit.d_obs + (size_t)first * row, (size_t)n * row * 4, hipMemcpyDeviceToHost, h->stream));
+    if (labels) HIPCHECK(hipMemcpyAsync(labels, h->fit.d_lab + (size_t)first * 4, (size_t)n * 4 * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// ---- rows named by where they lie on the device (cloth_fit_gather.hpp) ------------------------------------------------------------------
+// One (source, row) of a caller's table against what the handle holds now; the launch tables are valid under clothhip_render_obs's rule.
+static int check_source(const clothhip_handle *h, int64_t i, int32_t src, int32_t row) {
+    const auto &e = h->epi;
+    int64_t rows = 0;
+    switch (src) {
+    case CLOTHHIP_FIT_SRC_SLOTS:
+        if (e.f_T < 1) return fail(CLOTHHIP_ESTATE, "no clothhip_run_actions launch yet");
+        if (!e.f_obs) return fail(CLOTHHIP_ESTATE, "the last clothhip_run_actions launch was not given want_obs");
+        rows = (int64_t)e.f_T * h->E;
+        break;
+    case CLOTHHIP_FIT_SRC_RESETS:
+        if (e.f_T < 1) return fail(CLOTHHIP_ESTATE, "no clothhip_run_actions launch yet");
+        if (!e.f_robs) return fail(CLOTHHIP_ESTATE, "the last clothhip_run_actions launch was not given want_reset_obs");
+        rows = (int64_t)e.f_nscr;
+        break;
+    case CLOTHHIP_FIT_SRC_HELD:
+        if (!h->fit.held_valid) return fail(CLOTHHIP_ESTATE, "no held rows on this handle: call clothhip_fit_hold first");
+        rows = h->E;
+        break;
+    default:
+        return fail(CLOTHHIP_EINVAL, "entry %lld: unknown row source %d", (long long)i, src);
+    }
+    if (row < 0 || row >= rows) return fail(CLOTHHIP_EINVAL, "entry %lld: row %d outside [0, %lld) of source %d", (long long)i, row, (long long)rows, src);
+    return 0;
+}
+
+// upload n index entries [n][4] and run k_fit_gather over them; *bad: the kernel met a value that is not finite. Synchronous.
+static int run_gather(clothhip_handle *h, const std::vector<int32_t> &tab, int64_t n, float *dst_obs, float *dst_lab, bool with_labels, bool *bad) {
+    auto &f = h->fit;
+    if (int rc = f.d_rows.reserve((size_t)n * 16)) return rc;
+    if (int rc = f.d_flag.reserve(4)) return rc;
+    HIPCHECK(hipMemcpyAsync(f.d_rows, tab.data(), (size_t)n * 16, hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipMemsetAsync(f.d_flag, 0, 4, h->stream));
+    FitGatherArgs a = {};
+    a.table[FIT_SRC_SLOTS] = (const float *)h->epi.d_fobs; a.table[FIT_SRC_RESETS] = (const float *)h->epi.d_frobs; a.table[FIT_SRC_HELD] = f.d_held;
+    a.rows = f.d_rows; a.labels = with_labels ? (const double *)h->epi.d_flab : nullptr;
+    a.dst_obs = dst_obs; a.dst_lab = dst_lab; a.flag = f.d_flag; a.n = n; a.L = 3 * h->P;
+    HIPCHECK(hipEventRecord(h->ev0, h->stream));
+    hipLaunchKernelGGL(k_fit_gather, dim3((unsigned)std::min<int64_t>(n, 1 << 20)), dim3(FIT_GATHER_THREADS), 0, h->stream, a);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipEventRecord(h->ev1, h->stream));
+    h->have_timing = true;
+    int32_t flag = 0;
+    HIPCHECK(hipMemcpyAsync(&flag, f.d_flag, 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    *bad = flag != 0;
+    return 0;
+}
+
+// The refusal of an append whose kernel raised the flag, with clothhip_fit_data_append's message: what the kernel wrote behind the rows
+// that count is read back and searched in that entry's order (observations first, then the rounded labels).
+static int bad_value(clothhip_handle *h, int64_t n) {
+    auto &f = h->fit;
+    const size_t row = (size_t)3 * h->P;
+    std::vector<float> buf;
+    try { buf.resize((size_t)n * std::max<size_t>(row, 4)); } catch (const std::bad_alloc &) { return fail(CLOTHHIP_EINVAL, "an observation or a label is not a finite float"); }
+    HIPCHECK(hipMemcpy(buf.data(), f.d_obs + (size_t)f.n * row, (size_t)n * row * 4, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < (size_t)n * row; i++)
+        if (!std::isfinite(buf[i])) return fail(CLOTHHIP_EINVAL, "obs_rows[%zu][%zu] is not finite", i / row, i % row);
+    HIPCHECK(hipMemcpy(buf.data(), f.d_lab + (size_t)f.n * 4, (size_t)n * 4 * 4, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < (size_t)n * 4; i++)
+        if (!std::isfinite(buf[i])) return fail(CLOTHHIP_EINVAL, "labels[%zu][%zu] is not a finite float (a slot that did not run? pass the rows that ran)", i / 4, i % 4);
+    return fail(CLOTHHIP_EINVAL, "an observation or a label is not a finite float");
+}
+
+extern "C" int clothhip_fit_hold(clothhip_handle *h, const int32_t *src) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (int rc = check_idle(h)) return rc;
+    auto &f = h->fit;
+    const size_t row = (size_t)3 * h->P;
+    std::vector<int32_t> tab;
+    if (src) {
+        for (int e = 0; e < h->E; e++) {
+            const int32_t s = src[2 * e], r = src[2 * e + 1];
+            if (int rc = check_source(h, e, s, r)) return rc;
+            if (s == CLOTHHIP_FIT_SRC_HELD) {     // only its own row, which stays: another env's may be overwritten by this very call
+                if (r != e) return fail(CLOTHHIP_EINVAL, "entry %d: a held row can only be kept (row %d), not moved to another env", e, r);
+                continue;
+            }
+            try { tab.insert(tab.end(), {s, r, -1, (int32_t)e}); } catch (const std::bad_alloc &) { return fail(CLOTHHIP_ENOMEM, "out of host memory"); }
+        }
+    }
+    HIPCHECK(hipSetDevice(h->device));
+    if (int rc = f.d_held.reserve((size_t)h->E * row * 4)) return rc;      // (no earlier contents to keep: a table named HELD rows only if it existed)
+    if (!src) {
+        if (int rc = clothhip_write_obs_f32_device(h, f.d_held)) return rc;
+        HIPCHECK(hipStreamSynchronize(h->stream));
+    } else if (!tab.empty()) {
+        bool bad = false;      // (a held row is not checked here: clothhip_fit_data_append_launch checks what it appends)
+        if (int rc = run_gather(h, tab, (int64_t)tab.size() / 4, f.d_held, nullptr, false, &bad)) return rc;
+    }
+    f.held_valid = true;
+    return 0;
+}
+
+extern "C" int clothhip_fit_data_append_launch(clothhip_handle *h, const int32_t *rows, int64_t n) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (int rc = check_idle(h)) return rc;
+    if (n < 0) return fail(CLOTHHIP_EINVAL, "n < 0");
+    if (n == 0) return 0;
+    if (!rows) return fail(CLOTHHIP_EINVAL, "NULL argument");
+    auto &f = h->fit;
+    if (f.n + n > INT32_MAX) return fail(CLOTHHIP_EINVAL, "%lld + %lld rows: a minibatch names its rows by int32", (long long)f.n, (long long)n);
+    if (!h->epi.f_labels || h->epi.f_T < 1) return fail(CLOTHHIP_ESTATE, "the last episode launch on this handle was not armed with an expert (clothhip_run_actions_expert)");
+    const int64_t n_lab = (int64_t)h->epi.f_T * h->E;
+    std::vector<int32_t> tab;
+    try { tab.resize((size_t)n * 4); } catch (const std::bad_alloc &) { return fail(CLOTHHIP_ENOMEM, "out of host memory (%lld rows)", (long long)n); }
+    for (int64_t i = 0; i < n; i++) {
+        const int32_t s = rows[3 * i], r = rows[3 * i + 1], l = rows[3 * i + 2];
+        if (int rc = check_source(h, i, s, r)) return rc;
+        if (l < 0 || l >= n_lab) return fail(CLOTHHIP_EINVAL, "entry %lld: label row %d outside [0, %lld)", (long long)i, l, (long long)n_lab);
+        tab[4 * i] = s; tab[4 * i + 1] = r; tab[4 * i + 2] = l; tab[4 * i + 3] = (int32_t)(f.n + i);
+    }
+    HIPCHECK(hipSetDevice(h->device));
+    if (int rc = grow_dataset(h, n)) return rc;
+    // the kernel writes behind the n rows that count; they count only if every value it wrote is finite
+    bool bad = false;
+    if (int rc = run_gather(h, tab, n, f.d_obs, f.d_lab, true, &bad)) return rc;
+    if (bad) return bad_value(h, n);
+    f.n += n;
     return 0;
 }
 
@@ -99,6 +247,9 @@ static int reserve_fit(clothhip_handle *h, int32_t B) {
     return h->fit.d_grad.reserve(h->pol.mlp_n_params * 4);
 }
 
+static int enqueue_forward(clothhip_handle *h, const int32_t *d_idx, int32_t B, const float *const *W, const float *const *H);
+static int enqueue_backward(clothhip_handle *h, const int32_t *d_idx, int32_t B, const float *const *W, const float *const *H, float *const *gW, float *const *dz);
+
 // enqueue loss and gradient of the present weights over rows d_idx[0 .. B): h->fit.d_grad (blob layout), *d_loss
 static int enqueue_grad(clothhip_handle *h, const int32_t *d_idx, int32_t B, double *d_loss) {
     const MlpDesc &D = h->pol.mlp;
@@ -118,7 +269,17 @@ static int enqueue_grad(clothhip_handle *h, const int32_t *d_idx, int32_t B, dou
         }
     }
     float *dz[2] = {f.d_dz, f.d_dz + (size_t)B * maxw};
-    // forward
+    if (int rc = enqueue_forward(h, d_idx, B, W, H)) return rc;
+    hipLaunchKernelGGL(k_fit_loss, dim3(1), dim3(256), 0, h->stream, H[L - 1], (const float *)f.d_lab, d_idx, B, dz[(L - 1) & 1], d_loss);
+    HIPCHECK(hipGetLastError());
+    return enqueue_backward(h, d_idx, B, W, H, gW, dz);
+}
+
+// the forward pass over rows d_idx[0 .. B): layer l's output into H[l] (H[L - 1] = y), the dataset read through the index table
+static int enqueue_forward(clothhip_handle *h, const int32_t *d_idx, int32_t B, const float *const *W, const float *const *H) {
+    const MlpDesc &D = h->pol.mlp;
+    const int L = D.n_layers;
+    auto &f = h->fit;
     for (int l = 0; l < L; l++) {
         const int n_in = D.widths[l], n_out = D.widths[l + 1];
         FitGemmArgs a = {};
@@ -132,9 +293,14 @@ static int enqueue_grad(clothhip_handle *h, const int32_t *d_idx, int32_t B, dou
         else launch_gemm<true, true, FIT_EPI_BIAS, false>(h->stream, a);
         HIPCHECK(hipGetLastError());
     }
-    hipLaunchKernelGGL(k_fit_loss, dim3(1), dim3(256), 0, h->stream, H[L - 1], (const float *)f.d_lab, d_idx, B, dz[(L - 1) & 1], d_loss);
-    HIPCHECK(hipGetLastError());
-    // backward
+    return 0;
+}
+
+// the backward pass from dz[(L - 1) & 1] = dL/dy: h->fit.d_grad (blob layout)
+static int enqueue_backward(clothhip_handle *h, const int32_t *d_idx, int32_t B, const float *const *W, const float *const *H, float *const *gW, float *const *dz) {
+    const MlpDesc &D = h->pol.mlp;
+    const int L = D.n_layers;
+    auto &f = h->fit;
     const int n_split = (B + FIT_SPLIT_ROWS - 1) / FIT_SPLIT_ROWS;
     for (int l = L - 1; l >= 0; l--) {
         const int n_in = D.widths[l], n_out = D.widths[l + 1];
@@ -185,6 +351,50 @@ extern "C" int clothhip_policy_fit_grad(clothhip_handle *h, const int32_t *idx, 
     if (grad_out) HIPCHECK(hipMemcpyAsync(grad_out, f.d_grad, h->pol.mlp_n_params * 4, hipMemcpyDeviceToHost, h->stream));
     if (loss_out) HIPCHECK(hipMemcpyAsync(loss_out, f.d_loss, 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// The loss alone over any number of rows: chunks of at most FIT_MAX_BATCH through the forward above, each chunk's sum of squares in
+// k_fit_loss's order (k_fit_sqsum), the chunk sums added in ascending order in double on the host, divided once by 4 n.
+extern "C" int clothhip_policy_fit_loss(clothhip_handle *h, const int32_t *idx, int64_t n, double *loss) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (n < 1 || n > INT32_MAX) return fail(CLOTHHIP_EINVAL, "n = %lld outside [1, %d]", (long long)n, INT32_MAX);
+    const int32_t Bmax = (int32_t)std::min<int64_t>(n, FIT_MAX_BATCH);
+    if (int rc = check_fit(h, idx, n, Bmax)) return rc;
+    if (!idx || !loss) return fail(CLOTHHIP_EINVAL, "NULL argument");
+    auto &f = h->fit;
+    const MlpDesc &D = h->pol.mlp;
+    const int L = D.n_layers;
+    const int64_t n_chunks = (n + FIT_MAX_BATCH - 1) / FIT_MAX_BATCH;
+    std::vector<double> sums;
+    try { sums.resize((size_t)n_chunks); } catch (const std::bad_alloc &) { return fail(CLOTHHIP_ENOMEM, "out of host memory (%lld chunks)", (long long)n_chunks); }
+    HIPCHECK(hipSetDevice(h->device));
+    if (int rc = reserve_fit(h, Bmax)) return rc;
+    if (int rc = f.d_idx.reserve((size_t)n * 4)) return rc;
+    if (int rc = f.d_loss.reserve((size_t)n_chunks * 8)) return rc;
+    HIPCHECK(hipMemcpyAsync(f.d_idx, idx, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipEventRecord(h->ev0, h->stream));
+    for (int64_t c = 0; c < n_chunks; c++) {
+        const int32_t B = (int32_t)std::min<int64_t>(FIT_MAX_BATCH, n - c * FIT_MAX_BATCH);
+        const float *W[MLP_MAX_LAYERS], *H[MLP_MAX_LAYERS];
+        const float *w = D.params;
+        float *a = f.d_act;
+        for (int l = 0; l < L; l++) {
+            W[l] = w; H[l] = a;
+            w += (size_t)D.widths[l + 1] * D.widths[l] + D.widths[l + 1]; a += (size_t)B * D.widths[l + 1];
+        }
+        const int32_t *d_idx = f.d_idx + (size_t)c * FIT_MAX_BATCH;
+        if (int rc = enqueue_forward(h, d_idx, B, W, H)) return rc;
+        hipLaunchKernelGGL(k_fit_sqsum, dim3(1), dim3(256), 0, h->stream, H[L - 1], (const float *)f.d_lab, d_idx, B, f.d_loss + c);
+        HIPCHECK(hipGetLastError());
+    }
+    HIPCHECK(hipEventRecord(h->ev1, h->stream));
+    h->have_timing = true;
+    HIPCHECK(hipMemcpyAsync(sums.data(), f.d_loss, (size_t)n_chunks * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    double s = sums[0];
+    for (int64_t c = 1; c < n_chunks; c++) s = s + sums[c];
+    *loss = s / (double)(4 * n);
     return 0;
 }
 

@@ -63,7 +63,8 @@ struct clothhip_handle : HostPlan {
     Buffer<int32_t> d_hcnt;         // per env: #points with z < thickness/2 (height reward, cloth_env.py:1047-1073)
     int n_grab_levels = 0;
     // clothhip_run_actions staging (device), sized on demand: written by clothhip_run_actions_begin / _end alone (api_run.hip). Read elsewhere:
-    // f_pending (check_idle), f_T, f_nscr, f_obs, f_robs, d_fobs, d_frobs (clothhip_render_obs); d_resume is cleared by drop_in_flight* and clothhip_fork
+    // f_pending (check_idle), f_T, f_nscr, f_obs, f_robs, d_fobs, d_frobs (clothhip_render_obs; the row sources of api_fit.hip, which also reads
+    // f_labels and d_flab); d_resume is cleared by drop_in_flight* and clothhip_fork
     struct EpisodeStaging {
         Buffer<void> d_fz, d_fact, d_fscr, d_frec, d_frst, d_fobs, d_frobs;
         Buffer<int32_t> d_fsteps, d_fparg;
@@ -73,6 +74,7 @@ struct clothhip_handle : HostPlan {
         Buffer<double> d_fsum;          // [E][4] per-env summary of the last episode launch (what the multi-GPU driver all-gathers)
         Buffer<uint64_t> d_fticks;      // [E][8] per-operation-class ticks and update() counts of the last episode launch
         int f_T = 0; size_t f_nscr = 0; bool f_pending = false, f_resets = false, f_obs = false, f_robs = false, f_mt = false;
+        bool f_obs_kept = false, f_robs_kept = false;   // want_obs / want_reset_obs == 2: the table is written and stays here, _end downloads none
         // the expert beside the acting policy: what clothhip_run_actions_expert armed for the NEXT launch (host copies of its tables), the
         // armed launch's device tables, and whether the last launch was armed (f_labels: clothhip_run_actions_labels, and the label an action
         // cut by its time slice carries over)
@@ -116,6 +118,11 @@ struct clothhip_handle : HostPlan {
         // the dataset: n rows of cap allocated, d_obs [cap][3P] and d_lab [cap][4] float32 (grown geometrically, contents kept)
         Buffer<float> d_obs, d_lab;
         int64_t n = 0, cap = 0;
+        // rows named by where they lie (clothhip_fit_hold, clothhip_fit_data_append_launch): held [E][3P], one row per env that outlives
+        // the launch tables (held_valid: some clothhip_fit_hold has filled it); the index table of one call and its not-finite flag
+        Buffer<float> d_held;
+        bool held_valid = false;
+        Buffer<int32_t> d_rows, d_flag;
         // the optimizer: moments d_m, d_v [n_params] (SGD's u is d_m) and the 1-based count of steps taken. opt_zero: the moments are to
         // be read as zeros (the next step clears them first) -- what a reset is, so that a reset needs no device work
         Buffer<float> d_m, d_v;

@@ -393,6 +393,9 @@ extern "C" int clothhip_run_actions_begin(clothhip_handle *h, const ClothEpisode
             d_actions = (const double *)h->epi.d_fact;
         }
     }
+    // from here on the previous launch's observation tables may be reallocated or overwritten: they stop being readable now, also if this
+    // call fails further down (clothhip_render_obs, clothhip_fit_hold and clothhip_fit_data_append_launch then refuse them)
+    h->epi.f_obs = h->epi.f_robs = false;
     if (obs) if (int rc = h->epi.d_fobs.reserve(nrec * 3 * h->P * 4)) return rc;
     if ((reset_obs || resets) && !scripts && !rng_states) return fail(CLOTHHIP_EINVAL, "reset outputs without a reset source");
     if (reset_obs) {
@@ -446,6 +449,7 @@ extern "C" int clothhip_run_actions_begin(clothhip_handle *h, const ClothEpisode
     h->have_timing = true;
     h->pending_exec = true;
     h->epi.f_T = T_; h->epi.f_nscr = nscr; h->epi.f_resets = resets; h->epi.f_obs = obs; h->epi.f_robs = reset_obs; h->epi.f_mt = rng_states != nullptr;
+    h->epi.f_obs_kept = want_obs == 2; h->epi.f_robs_kept = want_reset_obs == 2;
     h->epi.f_pending = true; h->epi.f_labels = expert != 0;
     return 0;
 }
@@ -454,7 +458,9 @@ extern "C" int clothhip_run_actions_end(clothhip_handle *h, int32_t *num_steps, 
                                         ClothResetRecord *resets, float *obs, float *reset_obs, uint32_t *rng_states) {
     if (!h || !num_steps || !done || !records) return fail(CLOTHHIP_EINVAL, "NULL argument");
     if (!h->epi.f_pending) return fail(CLOTHHIP_ESTATE, "no clothhip_run_actions_begin in flight");
-    if ((resets != nullptr) != h->epi.f_resets || (obs != nullptr) != h->epi.f_obs || (reset_obs != nullptr) != h->epi.f_robs)
+    // (a table announced with 2 stays on the device: no buffer for it)
+    if ((resets != nullptr) != h->epi.f_resets || (obs != nullptr) != (h->epi.f_obs && !h->epi.f_obs_kept) ||
+        (reset_obs != nullptr) != (h->epi.f_robs && !h->epi.f_robs_kept))
         return fail(CLOTHHIP_EINVAL, "the output buffers must match the ones announced to clothhip_run_actions_begin");
     if ((rng_states != nullptr) != h->epi.f_mt) return fail(CLOTHHIP_EINVAL, "rng_states must be given to both halves or to neither");
     HIPCHECK(hipSetDevice(h->device));

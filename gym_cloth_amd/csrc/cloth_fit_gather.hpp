@@ -1,0 +1,85 @@
+// cloth_fit_gather.hpp -- rows of the trainer's dataset named by where they lie on the device (clothhip_fit_hold,
+// clothhip_fit_data_append_launch; no reference counterpart): ONE kernel copies observation rows of 3P floats from the last episode launch's
+// tables (or the handle's held rows) to the dataset's spare capacity (or to the held rows), and converts the expert's labels alongside.
+// Included only by api_fit.hip.
+//
+// A row is 3P floats and 3P is odd for every odd grid (3 * 625 = 1875), so a row starts at 4-byte alignment only: row r of a table begins
+// 12 r bytes (mod 16) into a 16-byte line, and since the source row and the destination row are unrelated numbers, the two sides are in
+// different 16-byte phases for three row pairs of four. A 16-byte access can then be aligned on one side at most; the other side would need
+// its data shifted across lanes or split again. The copy is DWORD accesses instead: lane i of a wave reads and writes base + 4 i, so each
+// wave instruction covers 256 contiguous bytes on both sides whatever the phases are, and a thread keeps FIT_GATHER_DEPTH independent loads
+// in flight before its first store. What that costs against a device-to-device copy of the same bytes is measured (profiles/dagger.txt).
+// All offsets are 64-bit: a table of 2^31 rows of 7 500 bytes is far past 2^32.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace clothhip {
+
+constexpr int FIT_GATHER_THREADS = 256, FIT_GATHER_DEPTH = 4;
+enum { FIT_SRC_SLOTS = 0, FIT_SRC_RESETS = 1, FIT_SRC_HELD = 2 };      // = CLOTHHIP_FIT_SRC_*
+
+struct FitGatherArgs {
+    const float *table[3];      // by source: obs [T * E][L], reset_obs [E * n_scripts][L], held [E][L] (the host has checked every index)
+    const int32_t *rows;        // [n][4] = (source, row, label row or -1, destination row)
+    const double *labels;       // [T * E][4] of the last armed launch, or NULL when no entry names a label
+    float *dst_obs, *dst_lab;   // destination tables [..][L], [..][4] (dst_lab may be NULL then)
+    int32_t *flag;              // raised (integer atomic OR) when a copied observation value or a rounded label is not finite
+    int64_t n;
+    int32_t L;                  // 3P
+};
+
+__device__ __forceinline__ bool fit_not_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
+
+// one workgroup per entry (grid-stride over the entries), a thread per element in passes of FIT_GATHER_THREADS * FIT_GATHER_DEPTH
+__global__ __launch_bounds__(FIT_GATHER_THREADS) void k_fit_gather(FitGatherArgs a) {
+    const int tid = threadIdx.x;
+    bool bad = false;
+    for (int64_t r = blockIdx.x; r < a.n; r += gridDim.x) {
+        const int32_t *q = a.rows + 4 * r;
+        const int32_t src = q[0], row = q[1], lrow = q[2], drow = q[3];
+        const float *s = a.table[src] + (int64_t)row * a.L;
+        float *d = a.dst_obs + (int64_t)drow * a.L;
+        for (int i0 = tid; i0 < a.L; i0 += FIT_GATHER_THREADS * FIT_GATHER_DEPTH) {
+            float v[FIT_GATHER_DEPTH];
+#pragma unroll
+            for (int k = 0; k < FIT_GATHER_DEPTH; k++) {
+                const int i = i0 + k * FIT_GATHER_THREADS;
+                v[k] = i < a.L ? s[i] : 0.0f;
+            }
+#pragma unroll
+            for (int k = 0; k < FIT_GATHER_DEPTH; k++) {
+                const int i = i0 + k * FIT_GATHER_THREADS;
+                if (i < a.L) { d[i] = v[k]; bad |= fit_not_finite(v[k]); }
+            }
+        }
+        if (lrow >= 0 && tid < 4) {      // the rounding of clothhip_fit_data_append: (float)label
+            const float lv = (float)a.labels[(int64_t)lrow * 4 + tid];
+            a.dst_lab[(int64_t)drow * 4 + tid] = lv;
+            bad |= fit_not_finite(lv);
+        }
+    }
+    if (bad) atomicOr(a.flag, 1);
+}
+
+// the sum of (double)(y - a)^2 over a minibatch, in k_fit_loss's order (cloth_policy_fit.hpp: thread t of 256 takes elements t, t + 256, ...
+// ascending, a halving tree over the 256 sums) and nothing else: clothhip_policy_fit_loss divides on the host
+__global__ __launch_bounds__(256) void k_fit_sqsum(const float *y, const float *lab, const int32_t *rows, int32_t B, double *sum) {
+    __shared__ double red[256];
+    const int tid = threadIdx.x, n = 4 * B;
+    double s = 0.0;
+    for (int i = tid; i < n; i += 256) {
+        const double dd = (double)y[i] - (double)lab[(size_t)rows[i >> 2] * 4 + (i & 3)];
+        s = s + dd * dd;
+    }
+    red[tid] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) red[tid] = red[tid] + red[tid + o];
+        __syncthreads();
+    }
+    if (tid == 0) *sum = red[0];
+}
+
+}  // namespace clothhip

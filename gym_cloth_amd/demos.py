@@ -181,3 +181,78 @@ def dagger_fit(env, trainer, roll, n_steps=100, batch_size=64, seed=0):
     ran = np.asarray(roll['ran'], dtype=bool)
     rows = trainer.append(roll['obs'][ran], roll['labels'][ran]) if ran.any() else trainer.size()
     return {'losses': trainer.step(n_steps, batch_size, seed), 'rows': rows, 'appended': int(ran.sum())}
+
+
+def dagger_collect(env, trainer, expert='oracle_corner', n_actions=12, beta=0.5, seed=0, slots_per_launch=12, time_budget_ms=0.0,
+                   policy_noise=None, expert_choices=None, max_launches=None):
+    """dagger_rollout and dagger_fit's append without the observation tables ever leaving the device, and therefore also in TIME SLICES:
+    armed launches of slots_per_launch slots (step_many(policy='mlp', want_obs='device', time_budget_ms=...)) until every env has run
+    n_actions slots. Slot i of env e -- counted over the launches -- takes row i of dagger_mixture(n_actions, E, beta, seed), of
+    policy_noise [n_actions, E, 4] and of expert_choices [n_actions, E]; what a launch leaves unused goes to the next one. Per launch:
+    the rows that ran are appended to `trainer`'s dataset by index (envs.slot_start_sources -> MLPTrainer.append_launch), then every
+    env's held row moves on (envs.hold_sources -> ClothBatch.fit_hold); before the first launch the held rows are the present states.
+    The env must hold no operation parked by an earlier time-sliced launch (ValueError): the held rows start as the present states, and
+    a cloth in the middle of an action does not show the state that action was planned on. max_launches bounds the loop (RuntimeError
+    when the envs have not all run n_actions slots by then; None: no bound).
+    An env that has its n_actions keeps acting on its last table rows while the others catch up; those slots are not appended.
+    Returns dict(appended: rows added, rows: the dataset's size, launches, row_env / row_slot int[appended]: the env and the per-env
+    slot number of every appended row in dataset order, count int[E]: slots each env ran (>= n_actions), took: seconds in the launches,
+    appends and holds, kernel_ms: of that the launches' kernels, substeps: Cloth.update() calls of the launches' actions and resets,
+    op_ticks: per launch step_many's uint64[E, 4] time accounting, records: per launch the [T, E] arrays 'ran',
+    'done', 'rew', 'actual_coverage', 'expert_took' and 'slot' (the per-env slot number) for coverage curves, with 'n_resets' int[E] and
+    'parked' bool[E]: the env holds an operation the slice cut). Nothing is trained here."""
+    import time
+    from .envs import hold_sources, slot_start_sources
+    if trainer.env is not env:
+        raise ValueError("the trainer belongs to another env")
+    E, N, T = env.E, int(n_actions), int(slots_per_launch)
+    if N < 1 or T < 1:
+        raise ValueError("n_actions and slots_per_launch must be >= 1")
+    if env.batch.in_flight().any():
+        raise ValueError("an earlier time-sliced launch left operations parked on this env: complete or drop them before collecting")
+    mix = dagger_mixture(N, E, beta, seed)
+    noise = None if policy_noise is None else np.asarray(policy_noise, dtype=np.float64)
+    if noise is not None and noise.shape != (N, E, 4):
+        raise ValueError("policy_noise must have shape (%d, %d, 4)" % (N, E))
+    choices = None if expert_choices is None else np.asarray(expert_choices)
+    if choices is not None and choices.shape != (N, E):
+        raise ValueError("expert_choices must have shape (%d, %d)" % (N, E))
+    used = np.zeros(E, dtype=np.int64)
+    ee = np.arange(E)[None, :]
+    res = {'appended': 0, 'launches': 0, 'row_env': [], 'row_slot': [], 'took': 0.0, 'substeps': 0, 'kernel_ms': 0.0, 'op_ticks': [], 'records': []}
+    before = env.total_substeps
+    t0 = time.perf_counter()
+    env.batch.fit_hold()
+    while (used < N).any():
+        if max_launches is not None and res['launches'] >= int(max_launches):
+            raise RuntimeError("%d launches and the envs have run %r of %d slots" % (res['launches'], used.tolist(), N))
+        slot = used[None, :] + np.arange(T)[:, None]                        # [T, E]: the per-env slot number of every slot of this launch
+        idx = np.minimum(slot, N - 1)                                       # past the end: the last row again (not appended)
+        out = env.step_many(policy='mlp', n_actions=T, want_obs='device', time_budget_ms=time_budget_ms,
+                            policy_noise=None if noise is None else noise[idx, ee], expert=expert, expert_mix=mix[idx, ee],
+                            expert_choices=None if choices is None else choices[idx, ee])
+        res['kernel_ms'] += float(env.batch.last_kernel_ms)
+        res['op_ticks'].append(out['op_ticks'])
+        ran = out['ran']
+        keep = ran & (slot < N)
+        t_, e_ = np.nonzero(keep)                                           # [t][e] order
+        if len(t_):
+            rows = np.concatenate([slot_start_sources(out)[t_, e_], (t_ * E + e_)[:, None].astype(np.int32)], axis=1)
+            trainer.append_launch(rows)
+            res['row_env'].append(e_); res['row_slot'].append(slot[t_, e_])
+            res['appended'] += len(t_)
+        env.batch.fit_hold(hold_sources(out))
+        used += ran.sum(axis=0)
+        res['launches'] += 1
+        parked = env.batch.in_flight()                                      # operations the slice cut: the next launch continues them
+        res['records'].append({'ran': ran, 'done': out['done'], 'rew': out['rew'], 'actual_coverage': out['actual_coverage'],
+                               'expert_took': out['expert_took'], 'slot': slot, 'n_resets': out['n_resets'], 'parked': parked})
+        if not ran.any() and not parked.any() and not (out['n_resets'] > 0).any():
+            raise RuntimeError("a launch made no progress (time_budget_ms = %r too short for one substep?)" % (time_budget_ms,))
+    res['took'] = time.perf_counter() - t0
+    res['substeps'] = int(env.total_substeps - before)
+    res['row_env'] = np.concatenate(res['row_env']) if res['row_env'] else np.zeros(0, dtype=np.int64)
+    res['row_slot'] = np.concatenate(res['row_slot']) if res['row_slot'] else np.zeros(0, dtype=np.int64)
+    res['count'] = used
+    res['rows'] = trainer.size()
+    return res

@@ -75,6 +75,60 @@ def slot_start_obs(out, obs_before):
     return start
 
 
+def _reset_capacity(out):
+    """R of the launch `out` came from: the row stride of its reset-observation table per env."""
+    if out.get('reset_obs') is not None:
+        return int(np.asarray(out['reset_obs']).shape[1])
+    return int(out.get('reset_capacity', 0))
+
+
+def slot_start_sources(out, held_valid=True):
+    """int32[T, E, 2]: slot_start_obs's rule stated as indices -- the (source, row) of the observation each slot began on, as
+    ClothBatch.fit_append_launch and fit_hold name rows that lie on the device (_lib.FIT_SRC_*). Slot (t, e) began on RESETS row
+    e * R + reset_before - 1 where an in-kernel reset preceded it, else on HELD row e -- what the env showed before the launch, kept by
+    fit_hold -- for t = 0, else on SLOTS row (t - 1) * E + e. `out` is step_many's dict (want_obs='device' or True); held_valid (bool or
+    bool[E]) False marks an env without a held row: its t = 0 entry is (-1, -1), which the library refuses. Unlike slot_start_obs this
+    holds for time-sliced launches too, given hold_sources between them: an action a slice cut is recorded in slot 0 of the launch that
+    completes it, and was planned on exactly the row held then."""
+    rb = np.asarray(out['reset_before']).astype(np.int64)
+    T, E = rb.shape
+    R = _reset_capacity(out)
+    e_ = np.arange(E, dtype=np.int64)
+    src = np.empty((T, E, 2), dtype=np.int64)
+    src[1:, :, 0] = _lib.FIT_SRC_SLOTS
+    src[1:, :, 1] = (np.arange(T - 1, dtype=np.int64)[:, None] * E + e_[None, :])
+    ok = np.broadcast_to(np.asarray(held_valid, dtype=bool), (E,))
+    src[0, :, 0] = np.where(ok, _lib.FIT_SRC_HELD, -1)
+    src[0, :, 1] = np.where(ok, e_, -1)
+    t_, k_ = np.nonzero(rb > 0)
+    if len(t_):
+        src[t_, k_, 0] = _lib.FIT_SRC_RESETS
+        src[t_, k_, 1] = k_ * R + rb[t_, k_] - 1
+    return src.astype(np.int32)
+
+
+def hold_sources(out):
+    """int32[E, 2]: what every env's held row becomes after the launch `out` (ClothBatch.fit_hold's table) -- the last thing that
+    completed in it. That is the reset observation of the env's last fully consumed reset when no record carries it as reset_before
+    (out['n_resets'][e] > max_t reset_before[t, e]: a time slice ended right after the reset), else the row of its last executed slot,
+    else the row it holds already. `out` needs 'ran', 'reset_before' and 'n_resets' (step_many(want_obs='device') gives it)."""
+    ran = np.asarray(out['ran'], dtype=bool)
+    rb = np.asarray(out['reset_before']).astype(np.int64)
+    T, E = ran.shape
+    R = _reset_capacity(out)
+    n_res = np.asarray(out['n_resets']).astype(np.int64)
+    e_ = np.arange(E, dtype=np.int64)
+    src = np.stack([np.full(E, _lib.FIT_SRC_HELD, dtype=np.int64), e_], axis=1)
+    any_ran = ran.any(axis=0)
+    last = T - 1 - np.argmax(ran[::-1], axis=0)
+    src[any_ran, 0] = _lib.FIT_SRC_SLOTS
+    src[any_ran, 1] = (last * E + e_)[any_ran]
+    tail = n_res > rb.max(axis=0)
+    src[tail, 0] = _lib.FIT_SRC_RESETS
+    src[tail, 1] = (e_ * R + n_res - 1)[tail]
+    return src.astype(np.int32)
+
+
 def load_cfg(cfg):
     if isinstance(cfg, dict):
         return copy.deepcopy(cfg)
@@ -720,7 +774,10 @@ class ClothVecEnv(object):
 
         Returns a dict of arrays [T, E] (rew, done, ran, executed, n_grabbed, reset_before, and the info keys of step())
         plus 'obs' [E, 3P] (state after the launch), 'actions' [T, E, 4], with want_obs 'obs_t' [T, E, 3P], and the launch's time
-        accounting 'op_ticks' / 'op_substeps' uint64[E, 4] (ClothBatch.op_ticks).
+        accounting 'op_ticks' / 'op_substeps' uint64[E, 4] (ClothBatch.op_ticks). want_obs='device' writes both observation tables as
+        True does but leaves them on the device until the next launch and downloads neither: no 'obs_t' / 'reset_obs', instead
+        'n_resets' int[E] (the resets of this launch each env consumed completely) and 'reset_capacity' (the reset table's rows per env) --
+        what slot_start_sources and hold_sources need to name the rows for ClothBatch.fit_append_launch / fit_hold.
 
         images='rgb' | 'depth' | 'rgbd' (implies want_obs) adds the image observation of every slot, rendered on the device from
         the launch's resident observation tables after the bookkeeping (ClothBatch.render_obs; image_kw: render parameters, as
@@ -754,7 +811,7 @@ class ClothVecEnv(object):
         self._commit_streams(a, fl, rst, n_consumed)
         _lap('rng_commit')
         if a.images is not None:                                      # the launch's tables are still on the device
-            self._render_launch(a, out, rst, robs is not None, n_consumed, side_t)
+            self._render_launch(a, out, rst, robs is not None or (a.want_obs == 'device' and a.dev_reset), n_consumed, side_t)
             _lap('images')
         obs = self.state
         _lap('obs_download')
@@ -763,7 +820,10 @@ class ClothVecEnv(object):
         out['obs'] = obs
         if expert is not None:                                        # (an un-armed launch returns exactly the keys it always did)
             out['init_side_t'] = side_t                               # tier 2: the side each slot's cloth was dropped from (expert_actions on stored rows)
-        if a.want_obs:
+        if a.want_obs == 'device':                                    # both tables stay on the device; what names their rows instead
+            out['n_resets'] = n_consumed                              # resets of this launch each env consumed completely
+            out['reset_capacity'] = a.R if a.dev_reset else 0         # the reset table's rows per env
+        elif a.want_obs:
             out['obs_t'], out['reset_obs'] = obs_t, robs
         return out
 
@@ -814,7 +874,7 @@ class ClothVecEnv(object):
         if images is not None:
             if images not in _lib.IMG_FORMATS:
                 raise ValueError("images must be None, 'rgb', 'depth' or 'rgbd' (got %r)" % (images,))
-            want_obs = True
+            want_obs = want_obs or True
         dev_reset = bool(auto_reset and (self._tier in (1, 3) or (self._tier == 2 and device_rng)))
         R = min(T, 255) if max_resets is None else int(max_resets)      # clothhip_run_actions: n_scripts in [1, 255]
         if dev_reset and not 1 <= R <= 255:

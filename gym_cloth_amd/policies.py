@@ -497,6 +497,19 @@ class MLPTrainer(object):
         """Add rows to the dataset (obs [n, 3P], labels [n, 4], finite); returns its size."""
         return self.env.batch.fit_append(obs, labels)
 
+    def append_launch(self, rows):
+        """Add rows that lie on the device (ClothBatch.fit_append_launch): rows int[n, 3] = (source, row, label_row) into the last armed
+        launch's tables and the held rows, as envs.slot_start_sources names them; returns the dataset's size."""
+        return self.env.batch.fit_append_launch(rows)
+
+    def data(self, first=0, n=None):
+        """(obs float32[n, 3P], labels float32[n, 4]): the stored rows [first, first + n) by download, n=None: to the end."""
+        return self.env.batch.fit_data(first, n)
+
+    def loss(self, idx):
+        """The MSE over the dataset rows idx (any number: a held-out split by index) at the present weights, forward only."""
+        return self.env.batch.fit_loss(idx)
+
     def size(self):
         return self.env.batch.fit_size()
 

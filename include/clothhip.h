@@ -331,7 +331,9 @@ typedef struct ClothResetRecord {
  * of resets per env and launch up to that capacity, no void scripts.
  * The same in two halves, so that the caller can work (e.g. draw the next reset scripts) while the launch runs:
  * _begin uploads the inputs and launches (the host input arrays are not retained), _end waits and downloads. The want_*
- * flags of _begin announce which of the optional output buffers _end will be given. One launch in flight per handle. */
+ * flags of _begin announce which of the optional output buffers _end will be given. One launch in flight per handle.
+ * want_obs == 2 / want_reset_obs == 2: the table is written and kept on the device exactly as with 1, but not downloaded -- _end must be
+ * given NULL for it (clothhip_render_obs and clothhip_fit_data_append_launch read it there). */
 int clothhip_run_actions_begin(clothhip_handle *h, const ClothEpisodeParams *ep, int32_t T, int32_t policy,
                                const double *actions, int32_t actions_on_device, const int32_t *policy_arg,
                                const ClothResetScript *scripts, int32_t n_scripts, const int32_t *num_steps,
@@ -463,6 +465,35 @@ int clothhip_policy_label(clothhip_handle *h, int32_t expert, int32_t clip_act_s
 int clothhip_fit_data_append(clothhip_handle *h, const float *obs_rows, const double *labels, int64_t n);
 int clothhip_fit_data_clear(clothhip_handle *h);
 int clothhip_fit_data_size(clothhip_handle *h, int64_t *n);
+/* Download stored rows [first, first + n): obs[n][3P] and labels[n][4], float32 as stored; either pointer may be NULL. For tests, and for
+ * whoever checkpoints a dataset that grew without the host ever seeing it. CLOTHHIP_EINVAL for a range outside the dataset. */
+int clothhip_fit_data_get(clothhip_handle *h, int64_t first, int64_t n, float *obs, float *labels);
+/* ROWS NAMED BY WHERE THEY LIE ON THE DEVICE (csrc/cloth_fit_gather.hpp): a DAgger collection appends what each slot's policy saw without
+ * the observation tables ever leaving the device. A row is (source, row):
+ *   CLOTHHIP_FIT_SRC_SLOTS   row t * E + e of the last launch's observation table (the state after slot t of env e);
+ *   CLOTHHIP_FIT_SRC_RESETS  row e * n_scripts + k of its reset-observation table (the first state of env e's k-th episode of the launch);
+ *   CLOTHHIP_FIT_SRC_HELD    row e of held[E][3P] float32, a table of the handle that outlives the launch tables.
+ * The launch tables are valid as for clothhip_render_obs: from the _end of a launch that was given want_obs / want_reset_obs (1, or 2 =
+ * kept on the device and not downloaded) until the next clothhip_run_actions* call on the handle, which overwrites them -- also one that
+ * fails after its argument checks: the tables are then gone and these calls refuse them; no other call touches
+ * them (clothhip_set_state, clothhip_fork, resets and the fit leave them alone -- they describe the launch, not the present state).
+ * The label table is that of the last launch and exists only if that launch was armed (clothhip_run_actions_expert).
+ * clothhip_fit_hold fills held: with src == NULL, held[e] = the float32 '1d' observation of env e's PRESENT state (the arithmetic of
+ * clothhip_write_obs_f32_device); else src[E][2] = (source, row) and held[e] = the named row, where (CLOTHHIP_FIT_SRC_HELD, e) for env e
+ * keeps the row it has (another env's held row cannot be named). The copy has completed when the call returns, so the next launch may
+ * overwrite the launch tables.
+ * clothhip_fit_data_append_launch appends n pairs in the order given, rows[n][3] = (source, row, label_row): the observation is the named
+ * row, the label (float)labels[label_row][0..3] of the last armed launch's table (label_row = t * E + e; the rounding of
+ * clothhip_fit_data_append). The storage grows as there. The kernel writes into the spare capacity behind the stored rows and raises a
+ * flag when an observation value or a rounded label is not finite (the label of a slot that did not run is NaN): the rows count only if
+ * the flag stayed clear, else CLOTHHIP_EINVAL with clothhip_fit_data_append's message for the first such value (entry and element) and
+ * the dataset is what it was. Synchronous; clothhip_last_kernel_ms gives the kernel's time.
+ * Refused before anything is touched -- CLOTHHIP_ESTATE: a launch in flight, SLOTS / RESETS when the last launch kept no such table (or
+ * there was none), a label row when the last launch was not armed, HELD before any clothhip_fit_hold; CLOTHHIP_EINVAL: an unknown source,
+ * a row outside its table, n < 0, rows == NULL with n > 0, more than INT32_MAX rows in all. */
+enum { CLOTHHIP_FIT_SRC_SLOTS = 0, CLOTHHIP_FIT_SRC_RESETS = 1, CLOTHHIP_FIT_SRC_HELD = 2 };
+int clothhip_fit_hold(clothhip_handle *h, const int32_t *src);
+int clothhip_fit_data_append_launch(clothhip_handle *h, const int32_t *rows, int64_t n);
 /* THE LOSS over a minibatch of B dataset rows idx[0 .. B) (host int32, repeats allowed and counted as often), with y the network's
  * float32 output and a the stored label:   L = 1 / (4 B) sum_r sum_k (y_rk - a_rk)^2   (torch.nn.MSELoss()), so dL/dy = (y - a) / (2 B);
  * ReLU's derivative is 1 where the pre-activation is > 0, else 0. clothhip_policy_fit_grad computes L (a double: the squares are summed
@@ -471,6 +502,12 @@ int clothhip_fit_data_size(clothhip_handle *h, int64_t *n);
  * and there are no floating-point atomics, so two runs give the same bits. The trainer's forward sums in another order than
  * clothhip_policy_eval, so its y need not equal that function's bits. */
 int clothhip_policy_fit_grad(clothhip_handle *h, const int32_t *idx, int32_t B, float *grad_out, double *loss_out);
+/* THE LOSS ALONE over any number n >= 1 of dataset rows idx[0 .. n) (a held-out split by index), forward only, nothing updated:
+ * L = 1 / (4 n) sum_r sum_k (y_rk - a_rk)^2. The rows go through the trainer's forward in chunks of at most CLOTHHIP_FIT_MAX_BATCH, in
+ * order; a chunk's squares are summed as clothhip_policy_fit_grad sums them, the chunk sums are added in ascending order in double, and
+ * the total is divided once by 4 n -- so for n <= CLOTHHIP_FIT_MAX_BATCH the result is clothhip_policy_fit_grad's loss bit for bit.
+ * The refusals of clothhip_policy_fit_grad, with n in place of B and no upper limit but INT32_MAX. */
+int clothhip_policy_fit_loss(clothhip_handle *h, const int32_t *idx, int64_t n, double *loss);
 /* The optimizer. All fields are floats; lr, eps, momentum finite and >= 0, beta1 and beta2 in [0, 1).
  *   CLOTHHIP_FIT_ADAM  with t the 1-based count of steps since the last reset, the host computes in double
  *        a_t = lr sqrt(1 - beta2^t) / (1 - beta1^t)  and hands the device (float)a_t, (float)(1 - beta1), (float)(1 - beta2); per parameter,

@@ -8,7 +8,10 @@ it costs.
 With --hidden 64,64 --fit device the policy is an MLP with those hidden widths and the refit runs ON THE DEVICE (policies.MLPTrainer
 through demos.dagger_fit: the rows are appended to the handle's dataset and Adam steps update the network in place, so the next
 iteration's launch runs the fitted weights with no upload); each iteration's line then splits its time into rollout / append / fit.
-    python3 tools/dagger_demo.py [--envs 64] [--slots 12] [--iters 4] [--out FILE] [--hidden 64,64 --fit device [--fit-steps 200] [--batch 256]]"""
+With --collect device (beside --fit device) the rollout's rows never leave the device either: demos.dagger_collect appends them by index
+from the launch's resident tables, and with --time-budget-ms X it collects in time slices of X ms instead of whole-slot launches.
+    python3 tools/dagger_demo.py [--envs 64] [--slots 12] [--iters 4] [--out FILE] [--hidden 64,64 --fit device [--fit-steps 200] [--batch 256]
+                                 [--collect device [--time-budget-ms X]]]"""
 import argparse
 import os
 import sys
@@ -20,7 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import bench                                          # noqa: E402
-from gym_cloth_amd.demos import dagger_fit, dagger_rollout        # noqa: E402
+from gym_cloth_amd.demos import dagger_collect, dagger_fit, dagger_rollout        # noqa: E402
 from gym_cloth_amd.envs import ClothVecEnv            # noqa: E402
 from gym_cloth_amd.policies import MLPPolicy, MLPTrainer          # noqa: E402
 
@@ -56,6 +59,9 @@ def run_device(args):
     for i in range(args.iters):
         env.seed([2000 + e for e in range(E)])
         env.reset()
+        if args.collect == "device":
+            collect_iteration(args, env, trainer, i)
+            continue
         t0 = time.perf_counter()
         roll = dagger_rollout(env, expert="oracle_corner", n_actions=T, beta=0.5 ** i, seed=i)
         dt = time.perf_counter() - t0
@@ -79,6 +85,28 @@ def run_device(args):
     env.close()
 
 
+def collect_iteration(args, env, trainer, i):
+    """One iteration with the rows appended on the device (demos.dagger_collect), in whole-slot launches or in time slices."""
+    E, T = args.envs, args.slots
+    t0 = time.perf_counter()
+    col = dagger_collect(env, trainer, "oracle_corner", n_actions=T, beta=0.5 ** i, seed=i, slots_per_launch=T, time_budget_ms=args.time_budget_ms)
+    dt = time.perf_counter() - t0
+    last, took = np.full(E, np.nan), 0
+    for rec in col["records"]:                                               # launches in order: the last counted slot of every env wins
+        counted = rec["ran"] & (rec["slot"] < T)
+        took += int((rec["expert_took"] & counted).sum())
+        for t, e in zip(*np.nonzero(counted)):
+            last[e] = rec["actual_coverage"][t, e]
+    t0 = time.perf_counter()
+    losses = trainer.step(args.fit_steps, args.batch, i)
+    df = time.perf_counter() - t0
+    say("iteration %d: beta %.3f, %4d labelled states (%4d acted by the expert), mean coverage after the last action %.4f, "
+        "collect on the device %.0f ms in %d launches%s (kernels %.0f ms; rows appended by index), fit on %d rows %.0f ms (device %.0f ms), "
+        "loss %.4f -> %.4f" % (i, 0.5 ** i, col["appended"], took, float(np.nanmean(last)), dt * 1e3, col["launches"],
+                              " of %.1f ms slices" % args.time_budget_ms if args.time_budget_ms > 0 else "", col["kernel_ms"], col["rows"],
+                              df * 1e3, env.batch.last_kernel_ms, losses[0], losses[-1]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=64)
@@ -90,7 +118,13 @@ def main():
     ap.add_argument("--fit-steps", type=int, default=200)
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--lr", type=float, default=1e-3)
+    ap.add_argument("--collect", choices=("host", "device"), default="host", help="device: demos.dagger_collect, the rows stay on the device (needs --fit device)")
+    ap.add_argument("--time-budget-ms", type=float, default=0.0, help="--collect device: collect in time slices of this length")
     args = ap.parse_args()
+    if args.collect == "device" and args.fit != "device":
+        ap.error("--collect device appends to the device-resident dataset: it needs --fit device")
+    if args.time_budget_ms and args.collect != "device":
+        ap.error("--time-budget-ms goes with --collect device")
     if (args.fit == "device") != bool(args.hidden):
         ap.error("--hidden WIDTHS and --fit device go together (the lstsq refit is for the linear policy)")
     if args.fit == "device":
