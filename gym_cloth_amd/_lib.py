@@ -112,6 +112,17 @@ FIT_MAX_BATCH = 4096                # CLOTHHIP_FIT_MAX_BATCH: the most rows of o
 FIT_SRC_SLOTS, FIT_SRC_RESETS, FIT_SRC_HELD = 0, 1, 2   # CLOTHHIP_FIT_SRC_*: where a row of clothhip_fit_hold / _append_launch lies
 assert C.sizeof(ClothFitParams) == 24
 
+
+class ClothPlanParams(C.Structure):
+    """clothhip_plan_cem's planner constants (clothhip.h: PLAN ACTIONS ON THE DEVICE)."""
+    _fields_ = [("horizon", C.c_int32), ("n_candidates", C.c_int32), ("n_elite", C.c_int32), ("n_iters", C.c_int32),
+                ("seed", C.c_uint64), ("iter0", C.c_uint32), ("_pad", C.c_int32), ("alpha", C.c_double), ("penalty", C.c_double),
+                ("min_std", C.c_double * 4)]
+
+
+PLAN_MAX_H, PLAN_MAX_K = 8, 1024    # csrc/cloth_plan.hpp: the longest horizon, the most candidates per env
+assert C.sizeof(ClothPlanParams) == 80
+
 # every symbol include/clothhip.h declares: (name, restype, argtypes)
 _vp, _dp, _u8p, _i32p = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(C.c_int32)
 _PP = C.POINTER(ClothParams)
@@ -171,6 +182,10 @@ SYMBOLS = [
     ("clothhip_policy_fit_loss", C.c_int, [_vp, _i32p, C.c_int64, _dp]),
     ("clothhip_policy_fit", C.c_int, [_vp, C.POINTER(ClothFitParams), _i32p, C.c_int32, C.c_int32, _dp]),
     ("clothhip_policy_fit_reset", C.c_int, [_vp]),
+    ("clothhip_plan_cem", C.c_int, [_vp, _vp, C.POINTER(ClothEpisodeParams), C.POINTER(ClothPlanParams), _i32p, _u8p, _dp, _dp, _dp, _dp,
+                                    _dp, _dp]),
+    ("clothhip_plan_sample", C.c_int, [_vp, C.POINTER(ClothPlanParams), _dp, _dp, C.c_int32, C.c_int32, _dp, _dp, _dp]),
+    ("clothhip_plan_refit", C.c_int, [_vp, C.POINTER(ClothPlanParams), C.c_int32, _dp, _dp, _u8p, _dp, _dp, _u8p, _i32p]),
     ("clothhip_update", C.c_int, [_vp, C.c_int32, _dp]),
     ("clothhip_metrics", C.c_int, [_vp, _dp, _dp, _u8p, _u8p]),
     ("clothhip_metrics_ex", C.c_int, [_vp, _dp, _dp, _u8p, _u8p, _i32p]),

@@ -135,6 +135,15 @@ struct clothhip_handle : HostPlan {
         Buffer<double> d_loss;
     } fit;
     void fit_forget() { fit.opt_t = 0; fit.opt_zero = true; }
+    // The cross-entropy planner (api_plan.hip: clothhip_plan_cem on the SCRATCH handle, clothhip_plan_sample / _refit on the handle given), all
+    // sized on demand: the distribution d_mean, d_std [E][H][4], the best so far d_best_a [E][H][4], d_best_s [E], the source's done flags, the
+    // action tables d_x [H][E K][4] (one, or one per iteration when the caller wants them back), d_scores [n_iters][E][K], the elite flags and
+    // top indices of the stand-alone refit
+    struct Plan {
+        Buffer<double> d_mean, d_std, d_best_a, d_best_s, d_x, d_scores;
+        Buffer<uint8_t> d_done, d_elite;
+        Buffer<int32_t> d_top;
+    } plan;
 };
 
 // f(float{}) or f(double{}) by the handle's precision: a launch that exists in both precisions is written once, as a generic lambda
@@ -150,5 +159,6 @@ SpecPhys phys_of(const ClothParams &p, const ClothMaterial &m);
 ClothMaterial material_of(const ClothParams &p);
 int drop_in_flight(clothhip_handle *h, const uint8_t *d_mask, const ClothSchedule *d_sched);
 int plan_steppers(clothhip_handle *h);                                                           // api_run.hip, for clothhip_create
+int run_actions_end_on_device(clothhip_handle *h);                                               // api_run.hip, for clothhip_plan_cem
 }  // namespace clothhip
 #pragma GCC visibility pop

@@ -477,6 +477,15 @@ extern "C" int clothhip_run_actions_end(clothhip_handle *h, int32_t *num_steps, 
     return 0;
 }
 
+// clothhip_run_actions_end without its downloads, for a caller inside the library that reads the launch's tables where they lie
+// (clothhip_plan_cem scores epi.d_frec on the device): the launch is no longer in flight as far as the handle's state goes; its work is
+// still on the handle's stream, and whatever reads its tables is enqueued there after it. No wait, nothing crosses PCIe.
+int clothhip::run_actions_end_on_device(clothhip_handle *h) {
+    if (!h->epi.f_pending) return fail(CLOTHHIP_ESTATE, "no clothhip_run_actions_begin in flight");
+    h->epi.f_pending = false;
+    return 0;
+}
+
 extern "C" int clothhip_run_actions_summary(clothhip_handle *h, double *summary, void **d_summary) {
     if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
     if (!h->epi.d_fsum) return fail(CLOTHHIP_ESTATE, "no clothhip_run_actions launch yet");

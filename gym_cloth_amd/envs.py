@@ -326,12 +326,16 @@ class ClothVecEnv(object):
         self._policy_mlp = None                                      # the network on the batch (set_policy): an MLPPolicy or its layers
         self._scratch = None                                         # lookahead's ClothBatch of E*K cloths
         self._look = None                                            # the last lookahead, for commit
+        self._plan_scratch = None                                    # plan's ClothBatch of E*K cloths (its own, not lookahead's)
 
     def close(self):
         self.batch.close()
         if self._scratch is not None:
             self._scratch.close()
             self._scratch = None
+        if getattr(self, '_plan_scratch', None) is not None:
+            self._plan_scratch.close()
+            self._plan_scratch = None
 
     # ------------------------------------------------------------------------------------------------
     def seed(self, seed=None):
@@ -674,6 +678,43 @@ class ClothVecEnv(object):
         self.batch.fork_from(self._scratch, sel, np.arange(E))
         r = {k: (None if v is None else np.array(v[sel], copy=True)) for k, v in L['r'].items()}
         return self._finish_step(L['actions'][np.arange(E), c], r, np.ones(E, dtype=bool), False, auto_reset)
+
+    def plan(self, horizon, n_candidates, n_elite, n_iters, mean=None, std=None, init_std=0.5, min_std=0.01, alpha=1.0, penalty=1.0,
+             seed=0, iter0=0, want_scores=False, want_candidates=False):
+        """Search for good actions with the simulator itself as the model: the cross-entropy method over action sequences of
+        `horizon` actions, WITHOUT changing the env (clothhip_plan_cem; include/clothhip.h has the definition). Per iteration,
+        n_candidates sequences per env are sampled around (mean, std) on the device -- candidate 0 is the clipped mean itself --, env
+        e is forked into n_candidates slots of a scratch ClothBatch of E * n_candidates cloths (this method's own, kept for the next
+        call with the same n_candidates), all branches run `horizon` actions in ONE episode launch exactly as step_many(actions,
+        auto_reset=False) would run them, each is scored by the coverage after its last executed action minus `penalty` if it tore or
+        left the bounds, and (mean, std) are refit to the n_elite best (mean <- alpha mu + (1 - alpha) mean, std likewise, not below
+        min_std). mean, std: float64 [E, horizon, 4] in the action space (clip space with clip_act_space); None = zeros / init_std.
+        The noise is a function of (seed, iter0 + iteration, table index): the same arguments give the same plan.
+        An env whose episode is over (reset pending) is not planned. Returns a dict: actions [E, H, 4] and score [E] of the best
+        sequence seen over all iterations (NaN where not planned), mean, std [E, H, 4] after the last refit, planned bool[E], and with
+        want_scores / want_candidates scores [n_iters, E, K] / candidates [n_iters, H, E K, 4]. Like lookahead, it is taken between
+        whole actions: it raises if a time-sliced step_many left operations in flight."""
+        if not self._delta_actions:
+            raise NotImplementedError("non-delta actions are decoded on the host only (cos/sin, cloth_env.py:452-453)")
+        E, K, H = self.E, int(n_candidates), int(horizon)
+        kw = dict(horizon=H, n_candidates=K, n_elite=n_elite, n_iters=n_iters, alpha=alpha, penalty=penalty, min_std=min_std, seed=seed,
+                  iter0=iter0)
+        ClothBatch.plan_params(**kw)                                   # refuse bad arguments before anything is created
+        mean = np.zeros((E, H, 4)) if mean is None else mean
+        std = np.broadcast_to(np.asarray(init_std, dtype=np.float64), (E, H, 4)) if std is None else std
+        planned = ~np.asarray(self._ep_done, dtype=bool)
+        m, s = ClothBatch._plan_dist(mean, std, E, H)
+        if not (np.isfinite(m[planned]).all() and np.isfinite(s[planned]).all() and (s[planned] >= 0).all()):
+            raise ValueError("mean must be finite, std finite and >= 0")
+        self._require_whole_actions("plan")
+        if self._plan_scratch is None or self._plan_scratch.E != E * K:
+            if self._plan_scratch is not None:
+                self._plan_scratch.close()
+            self._plan_scratch = ClothBatch(self.cfg, n_envs=E * K, device=self.batch.device, precision=self.batch.precision)
+        out = self._plan_scratch.plan_cem(self.batch, self._episode_params(), self.num_steps, ~planned, m, s, want_scores=want_scores,
+                                          want_candidates=want_candidates, **kw)
+        out['planned'] = planned
+        return out
 
     # ---- whole episodes on the device (clothhip_run_actions) ------------------------------------------------------
     def _episode_params(self):

@@ -16,6 +16,9 @@ MLPPolicy            no reference counterpart: a small fully-connected network o
 MLPPopulation        no reference counterpart: one MLP per env slot -- G perturbed copies of a centre network made on the device
                      (ClothBatch.population_perturb), rolled out in ONE episode launch, and the evolution-strategies update summed on
                      the device (ClothBatch.population_combine)
+CEMPolicy            no reference counterpart: model-predictive control with the simulator as the model -- the cross-entropy method over action
+                     sequences, every candidate rolled out on a device-side fork of the env (ClothVecEnv.plan, clothhip_plan_cem);
+                     plan_sample_reference / plan_refit_reference / cem_reference restate the planner in numpy, bit for bit
 MLPTrainer           no reference counterpart: the supervised refit of the shared network on the device (ClothBatch.fit_*), Adam or SGD over a
                      device-resident dataset of (observation, label) rows; fit_reference is its float64 numpy yardstick
 """
@@ -536,3 +539,180 @@ class MLPTrainer(object):
     def reset(self):
         """Zero the optimizer's moments and step count; the weights and the dataset stay."""
         self.env.batch.fit_reset()
+
+
+# ---- the cross-entropy planner (clothhip.h: PLAN ACTIONS ON THE DEVICE; csrc/cloth_plan.hpp) ----------------------------------------------
+_PHILOX_M0, _PHILOX_M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
+_PHILOX_W0, _PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
+_U32 = np.uint64(0xFFFFFFFF)
+_EPS_SCALE = np.array([0x33DDB3D7], dtype=np.uint32).view(np.float32)[0]      # (float)(sqrt(3) / 2^24)
+
+
+def philox4x32_10(ctr, key):
+    """Philox4x32-10 (standard constants). ctr: four arrays of uint32 values of one shape, key: two ints. Returns the four output words
+    as uint64 arrays below 2^32."""
+    c = list(np.broadcast_arrays(*[np.asarray(x, dtype=np.uint64) & _U32 for x in ctr]))
+    k0, k1 = int(key[0]) & 0xFFFFFFFF, int(key[1]) & 0xFFFFFFFF
+    for r in range(10):
+        if r:
+            k0, k1 = (k0 + _PHILOX_W0) & 0xFFFFFFFF, (k1 + _PHILOX_W1) & 0xFFFFFFFF
+        p0, p1 = _PHILOX_M0 * c[0], _PHILOX_M1 * c[2]                  # 32 x 32 -> 64 bits: no overflow in uint64
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ np.uint64(k0), p1 & _U32, (p0 >> np.uint64(32)) ^ c[3] ^ np.uint64(k1), p0 & _U32]
+    return c
+
+
+def philox_eps(seed, k, i):
+    """population_eps(seed, k, i) of csrc/cloth_philox.hpp as float32, i an integer array: Philox4x32-10 keyed by the two halves of seed
+    on the counter (i lo, i hi, k, 0); the four words' top 24 bits summed and centred, times (float)(sqrt(3) / 2^24). Zero mean, unit
+    variance, |eps| <= 3.47 -- the variate of the MLP population and of the planner's candidates."""
+    i = np.asarray(i, dtype=np.uint64)
+    seed = int(seed)
+    r = philox4x32_10((i & _U32, i >> np.uint64(32), np.uint64(int(k) & 0xFFFFFFFF), np.uint64(0)), (seed & 0xFFFFFFFF, seed >> 32))
+    S = sum(x >> np.uint64(8) for x in r)
+    D = S.astype(np.int64) - (2 ** 25 - 2)
+    return D.astype(np.int32).astype(np.float32) * _EPS_SCALE
+
+
+def _plan_clip(v, lo, hi):
+    """clip(v, lo, hi) = v < lo ? lo : (v > hi ? hi : v), lo / hi per action component (the last axis)."""
+    return np.where(v < lo, lo, np.where(v > hi, hi, v))
+
+
+def plan_sample_reference(mean, std, act_low, act_high, n_candidates, seed=0, iteration=0):
+    """k_plan_sample in numpy, bit for bit: mean, std float64 [E, H, 4] -> the action table [H, E K, 4];
+    x[h][e K + k][a] = clip(mean + std * (double)eps(seed, iteration, ((e K + k) H + h) 4 + a)), candidate k = 0 = clip(mean).
+    iteration is iter0 + it."""
+    mean, std = np.asarray(mean, dtype=np.float64), np.asarray(std, dtype=np.float64)
+    E, H, _ = mean.shape
+    K = int(n_candidates)
+    lo = np.broadcast_to(np.asarray(act_low, dtype=np.float64), (4,))
+    hi = np.broadcast_to(np.asarray(act_high, dtype=np.float64), (4,))
+    slot = np.arange(E * K, dtype=np.int64)[None, :, None]
+    h = np.arange(H, dtype=np.int64)[:, None, None]
+    a = np.arange(4, dtype=np.int64)[None, None, :]
+    eps = philox_eps(seed, iteration, (slot * H + h) * 4 + a).astype(np.float64)            # [H, E K, 4]
+    m = np.repeat(mean.transpose(1, 0, 2), K, axis=1)                                      # [H, E K, 4]: row e K + k is env e's
+    sd = np.repeat(std.transpose(1, 0, 2), K, axis=1)
+    step = sd * eps
+    v = np.where((slot % K) == 0, m, m + step)
+    return np.ascontiguousarray(_plan_clip(v, lo, hi))
+
+
+def plan_score_reference(records, penalty=1.0):
+    """The planner's score of every branch from a launch's records [H, n]: the coverage of the last executed slot (ran != 0), minus
+    `penalty` when any executed slot has oob or tear; -inf for a column without an executed slot. float64 [n]."""
+    ran = records['ran'] != 0
+    H, n = ran.shape
+    last = np.where(ran.any(axis=0), H - 1 - np.argmax(ran[::-1], axis=0), -1)
+    bad = (ran & ((records['oob'] != 0) | (records['tear'] != 0))).any(axis=0)
+    cov = records['coverage'][np.maximum(last, 0), np.arange(n)]
+    return np.where(last < 0, -np.inf, np.where(bad, cov - float(penalty), cov))
+
+
+def plan_refit_reference(x, scores, mean, std, n_elite, alpha=1.0, min_std=0.0, done=None):
+    """k_plan_refit in numpy, bit for bit: the action table x [H, E K, 4] and scores [E, K] -> (mean, std after the refit, elite
+    bool[E, K], top int32[E]). Candidates are ranked by (score descending, k ascending); per (h, a) the elites are summed in
+    ascending k: mu = sum / M, var = sum (x - mu)^2 / M, sd = sqrt(var); mean <- alpha mu + beta mean, std <- max(min_std, alpha sd +
+    beta std), beta = 1 - alpha. An env with done set keeps its rows, has no elites and top -1."""
+    x = np.asarray(x, dtype=np.float64)
+    scores = np.asarray(scores, dtype=np.float64)
+    E, K = scores.shape
+    H, M = x.shape[0], int(n_elite)
+    mean = np.array(np.broadcast_to(np.asarray(mean, dtype=np.float64), (E, H, 4)))
+    std = np.array(np.broadcast_to(np.asarray(std, dtype=np.float64), (E, H, 4)))
+    ms = np.broadcast_to(np.asarray(min_std, dtype=np.float64), (4,))
+    alpha = np.float64(alpha)
+    beta = np.float64(1.0) - alpha
+    Md = np.float64(M)
+    elite = np.zeros((E, K), dtype=bool)
+    top = np.full(E, -1, dtype=np.int32)
+    for e in range(E):
+        if done is not None and done[e]:
+            continue
+        order = np.lexsort((np.arange(K), -scores[e]))                # score descending, then k ascending
+        top[e] = order[0]
+        elite[e, order[:M]] = True
+        ks = np.nonzero(elite[e])[0]                                  # ascending k
+        xe = x[:, e * K + ks, :]                                      # [H, M, 4]
+        tot = np.zeros((H, 4))
+        for j in range(M):
+            tot = tot + xe[:, j, :]
+        mu = tot / Md
+        sq = np.zeros((H, 4))
+        for j in range(M):
+            d = xe[:, j, :] - mu
+            sq = sq + d * d
+        sd = np.sqrt(sq / Md)
+        mean[e] = alpha * mu + beta * mean[e]
+        ns = alpha * sd + beta * std[e]
+        std[e] = np.where(ns < ms, ms, ns)
+    return mean, std, elite, top
+
+
+def cem_reference(env, scratch_batch, horizon, n_candidates, n_elite, n_iters, mean, std, min_std=0.0, alpha=1.0, penalty=1.0, seed=0,
+                  iter0=0):
+    """clothhip_plan_cem's loop on the host, from its parts: plan_sample_reference, scratch_batch.fork_from(env.batch), the host-table
+    run_actions launch on scratch_batch (E K cloths), plan_score_reference, plan_refit_reference, and the best-so-far rule. Returns the
+    dict ClothBatch.plan_cem returns with want_scores and want_candidates. On one scratch batch both routes run the same kernels on
+    the same states, so every table agrees bit for bit."""
+    E, K, H, n = env.E, int(n_candidates), int(horizon), int(n_iters)
+    mean = np.array(np.broadcast_to(np.asarray(mean, dtype=np.float64), (E, H, 4)))
+    std = np.array(np.broadcast_to(np.asarray(std, dtype=np.float64), (E, H, 4)))
+    done = np.asarray(env._ep_done, dtype=bool)
+    rep = np.repeat(np.arange(E), K)
+    ep = env._episode_params()
+    lo, hi = env.action_space.low, env.action_space.high
+    best_a, best_s = np.full((E, H, 4), np.nan), np.full(E, np.nan)
+    scores, cands = np.zeros((n, E, K)), np.zeros((n, H, E * K, 4))
+    for it in range(n):
+        x = plan_sample_reference(mean, std, lo, hi, K, seed=seed, iteration=iter0 + it)
+        scratch_batch.fork_from(env.batch, rep)
+        ns = np.ascontiguousarray(env.num_steps[rep], dtype=np.int32)
+        dn = np.ascontiguousarray(done[rep], dtype=np.uint8)
+        rec = scratch_batch.run_actions(ep, H, ns, dn, actions=x)[0]
+        sc = plan_score_reference(rec, penalty).reshape(E, K)
+        mean, std, _, top = plan_refit_reference(x, sc, mean, std, n_elite, alpha=alpha, min_std=min_std, done=done)
+        for e in np.nonzero(~done)[0]:
+            if it == 0 or sc[e, top[e]] > best_s[e]:
+                best_s[e] = sc[e, top[e]]
+                best_a[e] = x[:, e * K + top[e], :]
+        scores[it], cands[it] = sc, x
+    return dict(mean=mean, std=std, actions=best_a, score=best_s, scores=scores, candidates=cands)
+
+
+class CEMPolicy(object):
+    """Model-predictive control by the cross-entropy method, the simulator itself as the model: every get_action plans `horizon`
+    actions ahead on device-side forks of the env's present state (ClothVecEnv.plan: n_iters iterations of n_candidates action
+    sequences per env, refit to the n_elite best) and returns the first action of the best sequence seen. The env does not move.
+    warm_start: another policy (get_action(obs, t)) whose proposal becomes mean[:, 0]; candidate 0 of iteration 0 is the clipped
+    mean itself, so the plan's score is never below what that proposal (followed by the rest of the mean) scores. Between calls the
+    mean is the last plan's mean shifted by one action with the last row repeated, std goes back to init_std, and iter0 advances by
+    n_iters (fresh noise each call, the same stream for the same seed). last_plan keeps the dict plan() returned. An env whose
+    episode is over is not planned; it gets the clipped mean's first action."""
+
+    def __init__(self, env, horizon=1, n_candidates=16, n_elite=4, n_iters=2, init_std=0.5, min_std=0.01, alpha=1.0, penalty=1.0, seed=0,
+                 warm_start=None):
+        from .batch import ClothBatch
+        ClothBatch.plan_params(horizon, n_candidates, n_elite, n_iters, alpha=alpha, penalty=penalty, min_std=min_std, seed=seed)
+        self.env, self.warm_start = env, warm_start
+        self.horizon, self.n_candidates, self.n_elite, self.n_iters = int(horizon), int(n_candidates), int(n_elite), int(n_iters)
+        self.init_std, self.min_std, self.alpha, self.penalty, self.seed = init_std, min_std, float(alpha), float(penalty), int(seed)
+        self.iter0 = 0
+        self.mean = np.zeros((env.E, self.horizon, 4))
+        self.last_plan = None
+
+    def get_action(self, obs=None, t=0):
+        E, H = self.env.E, self.horizon
+        mean = self.mean.copy()
+        if self.warm_start is not None:
+            mean[:, 0] = np.asarray(self.warm_start.get_action(obs, t), dtype=np.float64)
+        std = np.array(np.broadcast_to(np.asarray(self.init_std, dtype=np.float64), (E, H, 4)))
+        plan = self.env.plan(H, self.n_candidates, self.n_elite, self.n_iters, mean=mean, std=std, min_std=self.min_std, alpha=self.alpha,
+                             penalty=self.penalty, seed=self.seed, iter0=self.iter0)
+        self.iter0 += self.n_iters
+        self.last_plan = plan
+        m = plan['mean']
+        self.mean = np.concatenate([m[:, 1:], m[:, -1:]], axis=1)
+        sp = self.env.action_space
+        fallback = _plan_clip(mean[:, 0], sp.low, sp.high)
+        return np.where(plan['planned'][:, None], plan['actions'][:, 0], fallback)

@@ -538,6 +538,68 @@ int clothhip_run_actions(clothhip_handle *h, const ClothEpisodeParams *ep, int32
                          ClothStepRecord *records, ClothResetRecord *resets, float *obs, float *reset_obs,
                          double time_budget_ms);
 
+/* ---- PLAN ACTIONS ON THE DEVICE: the cross-entropy method over forked cloths, the simulator itself as the model (no reference counterpart;
+ * gym-cloth's follow-up work plans with CEM over a learned model). csrc/cloth_plan.hpp has the two kernels.
+ * NAMES. E = envs of the SOURCE handle `src`, K = candidates per env, H = horizon in actions, M = elites, it = iteration in [0, n_iters). The
+ * SCRATCH handle has exactly E K cloths on src's device, in its precision, grid and ClothParams (the caller creates it); branch (e, k) lives
+ * in its slot e K + k. All planner arithmetic is float64 on both precisions (action tables are doubles), one operation per fl(), no
+ * contraction. mean[E][H][4] and std[E][H][4] are in/out. done[e] != 0 marks env e as NOT PLANNED: its mean / std rows stay untouched, its
+ * best_actions rows and best_score are NaN; its branches are forked and launched like the others (a done env executes nothing) and ignored.
+ * SAMPLE (k_plan_sample).  x[h][e K + k][a] = clip(fl(mean[e][h][a] + fl(std[e][h][a] * (double)eps)), act_low[a], act_high[a]) with
+ *   eps = population_eps(seed, iter0 + it, ((e K + k) H + h) 4 + a) -- the exact variate of clothhip_policy_population_perturb (Philox4x32-10 keyed
+ *   by seed on the counter (index lo, index hi, iter0 + it, 0); zero mean, unit variance, |eps| <= 3.47) --, clip(v, lo, hi) = v < lo ? lo :
+ *   (v > hi ? hi : v), act_low / act_high those of ClothEpisodeParams. Candidate k = 0 is clip(mean) itself, without noise. The table has
+ *   clothhip_run_actions' [T = H][E K][4] layout and is written into the device buffer the launch reads.
+ * ROLL OUT.  One clothhip_fork: src env e -> scratch slots e K .. e K + K - 1, materials included. Then ONE episode launch on the scratch handle:
+ *   CLOTHHIP_POLICY_TABLE, T = H, actions_on_device, no reset scripts, no time budget, num_steps[e] and done[e] of the source replicated K times
+ *   -- so max_actions, a tear or leaving the bounds end a branch where they would end the episode.
+ * SCORE.  Branch (e, k) is scored on the device from its record column: its executed slots are those with ran != 0;
+ *   score = coverage of the last executed slot, minus `penalty` when any executed slot has oob or tear; a branch without an executed slot scores
+ *   -infinity (a branch of a planned env whose episode has actions left always executes slot 0).
+ * ELITES.  rank_k = #{j : score_j > score_k or (score_j == score_k and j < k)}: candidates ordered by (score descending, k ascending), a counting
+ *   rank, so equal scores have one defined order. The M candidates of rank < M are the elites, the one of rank 0 is the top candidate.
+ * REFIT (k_plan_refit: one workgroup per env, its scores in LDS).  For each (h, a) one thread loops over the elites in ascending k, x the clipped
+ *   table values:  mu = (sum x_k) / M;  var = (sum (x_k - mu)^2) / M;  sd = sqrt(var) (division and square root correctly rounded);
+ *   mean <- fl(fl(alpha mu) + fl(beta mean));  std <- max(min_std[a], fl(fl(alpha sd) + fl(beta std)));  beta = 1 - alpha, made once on the host.
+ * BEST SO FAR.  The iteration's top candidate replaces best_actions[e][H][4] / best_score[e] only if its score is strictly greater than
+ *   best_score[e]; iteration 0 always sets them. So best_score[e] is the running maximum of the top scores.
+ * BOUNDS.  horizon in [1, 8], n_candidates in [2, 1024], n_elite in [1, n_candidates], n_iters >= 1, iter0 + n_iters <= 2^31, alpha in (0, 1],
+ *   penalty finite, min_std finite and >= 0, std finite and >= 0, mean finite. */
+typedef struct ClothPlanParams {
+    int32_t horizon, n_candidates, n_elite, n_iters;
+    uint64_t seed;
+    uint32_t iter0;
+    int32_t _pad;
+    double alpha, penalty;
+    double min_std[4];
+} ClothPlanParams;
+/* The whole loop, n_iters x { sample, fork, launch, score + refit }, in one call. ep, num_steps[E], done[E] as clothhip_run_actions takes them
+ * for the source (read only). mean / std [E][H][4]: in the initial distribution, out the last refit's. best_actions[E][H][4], best_score[E].
+ * scores_out[n_iters][E][K] and cands_out[n_iters][H][E K][4] (the clipped tables) are optional (NULL), for tests and diagnostics; they are
+ * gathered on the device and downloaded with the results after the last iteration. The launch's records are scored where they lie (the
+ * planner ends the launch through a library-internal path instead of clothhip_run_actions_end, which would download them): between
+ * iterations nothing comes back from the device, and what goes up is what clothhip_fork (its index lists) and clothhip_run_actions_begin
+ * (the replicated counters and flags, the argument block) upload on every call.
+ * CLOTHHIP_EINVAL: anything outside the bounds, a NULL table, bad episode parameters, scratch == src, a scratch handle of another size,
+ * precision, grid, device or ClothParams. CLOTHHIP_ESTATE: a clothhip_run_actions_begin in flight on either handle, a parked time-slice
+ * operation on a planned source env (clothhip_in_flight), a scratch handle that cannot run fused (clothhip_fused_supported), a relaxed-order
+ * scratch handle. A refused call changes nothing; the source handle's state is never written. Synchronous; the scratch handle's cloths, its
+ * last-launch tables and clothhip_last_kernel_ms (the last iteration's launch) are the planner's afterwards. */
+int clothhip_plan_cem(clothhip_handle *scratch, clothhip_handle *src, const ClothEpisodeParams *ep, const ClothPlanParams *params,
+                      const int32_t *num_steps, const uint8_t *done, double *mean, double *std, double *best_actions, double *best_score,
+                      double *scores_out, double *cands_out);
+/* The two kernels alone, on host tables and without a cloth (h gives the device and the stream only; E >= 1 is the caller's).
+ * _sample: iteration `it` of params (iter = iter0 + it; n_elite, n_iters, alpha, penalty, min_std are not read): mean, std [E][H][4] ->
+ *   x_out[H][E K][4].
+ * _refit: the action table x[H][E K][4] and a score table scores[E][K] (no NaN; +-infinity allowed) -> mean, std (in/out), elite[E][K] (1 for
+ *   an elite, else 0; all 0 for an env that is not planned) and top[E] (the top candidate's k, -1 for an env that is not planned). done[E] or
+ *   NULL = every env planned. elite and top may be NULL.
+ * The bounds and CLOTHHIP_EINVAL as above; CLOTHHIP_ESTATE with a launch in flight on h. */
+int clothhip_plan_sample(clothhip_handle *h, const ClothPlanParams *params, const double act_low[4], const double act_high[4], int32_t E,
+                         int32_t it, const double *mean, const double *std, double *x_out);
+int clothhip_plan_refit(clothhip_handle *h, const ClothPlanParams *params, int32_t E, const double *x, const double *scores,
+                        const uint8_t *done, double *mean, double *std, uint8_t *elite, int32_t *top);
+
 /* Convenience: n x Cloth.update() on every env (cloth_env.py:902-903, :948-949, :980-981), optionally
  * preceded each time by Gripper.adjust(delta) when delta != NULL ([3] doubles, same for all envs). */
 int clothhip_update(clothhip_handle *h, int32_t n_sub, const double *delta);
