@@ -109,6 +109,7 @@ class ClothFitParams(C.Structure):
 FIT_ADAM, FIT_SGD = 0, 1
 FIT_OPTIMIZERS = {'adam': FIT_ADAM, 'sgd': FIT_SGD}
 FIT_MAX_BATCH = 4096                # CLOTHHIP_FIT_MAX_BATCH: the most rows of one minibatch
+FIT_MAX_MEMBER_ROWS = 65536         # CLOTHHIP_FIT_MAX_MEMBER_ROWS: the most members x rows of one grouped call (clothhip_policy_fit_members)
 FIT_SRC_SLOTS, FIT_SRC_RESETS, FIT_SRC_HELD = 0, 1, 2   # CLOTHHIP_FIT_SRC_*: where a row of clothhip_fit_hold / _append_launch lies
 assert C.sizeof(ClothFitParams) == 24
 
@@ -182,6 +183,9 @@ SYMBOLS = [
     ("clothhip_policy_fit_loss", C.c_int, [_vp, _i32p, C.c_int64, _dp]),
     ("clothhip_policy_fit", C.c_int, [_vp, C.POINTER(ClothFitParams), _i32p, C.c_int32, C.c_int32, _dp]),
     ("clothhip_policy_fit_reset", C.c_int, [_vp]),
+    ("clothhip_policy_fit_grad_members", C.c_int, [_vp, _i32p, C.c_int32, _i32p, C.c_int32, C.POINTER(C.c_float), _dp]),
+    ("clothhip_policy_fit_members", C.c_int, [_vp, C.POINTER(ClothFitParams), _i32p, C.c_int32, _i32p, C.c_int32, C.c_int32, _dp]),
+    ("clothhip_policy_fit_reset_members", C.c_int, [_vp, _i32p, C.c_int32]),
     ("clothhip_plan_cem", C.c_int, [_vp, _vp, C.POINTER(ClothEpisodeParams), C.POINTER(ClothPlanParams), _i32p, _u8p, _dp, _dp, _dp, _dp,
                                     _dp, _dp]),
     ("clothhip_plan_sample", C.c_int, [_vp, C.POINTER(ClothPlanParams), _dp, _dp, C.c_int32, C.c_int32, _dp, _dp, _dp]),

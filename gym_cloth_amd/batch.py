@@ -506,6 +506,7 @@ class ClothBatch(object):
         layout) and b [out], ReLU between them, the first `in` = 3 P, the last `out` = 4; None or [] clears it. The values are
         uploaded as float32; every env of the batch evaluates the same network. ValueError for shapes the library refuses."""
         self._mlp_n_params = 0                     # (fit_grad sizes its result by it: the shared network's parameters, 0 without one)
+        self._pop_shape = None                     # (a shared network replaces a population)
         if not layers:
             check(self._L.clothhip_set_policy_mlp(self._h, 0, None, None, 0))
             return
@@ -549,6 +550,7 @@ class ClothBatch(object):
         layers as set_policy_mlp takes them, `member` int[E] with env e running members[member[e]]. None or [] clears the handle's
         network. Replaces a shared network (and set_policy_mlp replaces a population). The networks belong to the env slots: resets and
         uploads leave them alone; forks and snapshots do not carry them."""
+        self._pop_shape = None                     # (fit_grad_members sizes its result by it: (rows, n_params) of the population)
         if not members:
             check(self._L.clothhip_set_policy_population(self._h, 0, None, None, 0, None))
             return
@@ -556,6 +558,7 @@ class ClothBatch(object):
         widths, blob = pack_population(members, n_in=3 * self.P)
         m = self._member_map(member, blob.shape[0])
         check(self._L.clothhip_set_policy_population(self._h, len(widths) - 1, _lib.i32p(widths), self._fp(blob), blob.shape[0], _lib.i32p(m)))
+        self._pop_shape = (int(blob.shape[0]), int(blob.shape[1]))
 
     def set_policy_members(self, member):
         """The map alone (clothhip_set_policy_members): member int[E], each below the population's number of rows."""
@@ -608,6 +611,7 @@ class ClothBatch(object):
         check(self._L.clothhip_policy_population_perturb(self._h, len(widths) - 1, _lib.i32p(widths), self._fp(blob), G, float(np.float32(sigma)),
                                                          int(seed), _lib.POP_ANTITHETIC if antithetic else 0, _lib.i32p(m)))
         self._pop_n_params = blob.size
+        self._pop_shape = (G + 1, int(blob.size))
         return widths, blob.size
 
     def population_combine(self, coef):
@@ -743,6 +747,82 @@ class ClothBatch(object):
     def fit_reset(self):
         """Zero the optimizer's moments and its step count (clothhip_policy_fit_reset)."""
         check(self._L.clothhip_policy_fit_reset(self._h))
+
+    # ---- the grouped trainer: rows of the population fitted in the launches of one network (clothhip_policy_fit*_members) ----------
+    def _fit_members(self, members):
+        """members as int32[n_m]: distinct rows of the batch's population ((rows, n_params) from the call that made it)."""
+        shape = getattr(self, '_pop_shape', None)
+        if shape is None:
+            raise _lib.ClothHipError("no population on this batch: call set_policy_population or population_perturb first")
+        m = np.asarray(members)
+        if m.ndim != 1 or m.size < 1 or not np.issubdtype(m.dtype, np.integer):
+            raise ValueError("members must be a non-empty 1-d integer array")
+        if m.min() < 0 or m.max() >= shape[0]:
+            raise ValueError("members must lie in [0, %d)" % shape[0])
+        if np.unique(m).size != m.size:
+            raise ValueError("members must be distinct: a call fits a row once")
+        return np.ascontiguousarray(m, dtype=np.int32), shape[1]
+
+    def _fit_members_idx(self, idx, n_m, ndim):
+        ix = self._fit_idx(idx, ndim)
+        if ix.shape[-2] != n_m:
+            raise ValueError("idx must have %d rows of minibatch per step, one per member (got shape %r)" % (n_m, ix.shape))
+        if n_m * ix.shape[-1] > _lib.FIT_MAX_MEMBER_ROWS:
+            raise ValueError("%d members x %d rows in one call, at most %d" % (n_m, ix.shape[-1], _lib.FIT_MAX_MEMBER_ROWS))
+        return ix
+
+    def fit_grad_members(self, members, idx):
+        """(loss float64[n_m], grad float32[n_m, n_params]) of the population rows `members` (distinct ints) over their own minibatches
+        idx [n_m, B] of the batch's one dataset, at the present weights; nothing is updated (clothhip_policy_fit_grad_members). Member
+        j's result is bit for bit fit_grad's on a batch that carries row members[j] as its shared network."""
+        m, n_params = self._fit_members(members)
+        ix = self._fit_members_idx(idx, m.size, 2)
+        grad = np.zeros((m.size, n_params), dtype=np.float32)
+        loss = np.zeros(m.size, dtype=np.float64)
+        check(self._L.clothhip_policy_fit_grad_members(self._h, _lib.i32p(m), m.size, _lib.i32p(ix), ix.shape[1], self._fp(grad), _lib.dp(loss)))
+        return loss, grad
+
+    def fit_members(self, members, idx_table, hyper=None):
+        """n_steps optimizer steps on the population rows `members`, in place on the device, all members in the launches of one
+        (clothhip_policy_fit_members): step s of member j uses the dataset rows idx_table[s, j] (int [n_steps, n_m, B]). hyper: a dict
+        with fit's keywords (optimizer, lr, beta1, beta2, eps, momentum), each value a scalar for all members or a sequence of n_m;
+        the optimizer is one for the call. Every row keeps its own moments and step count across calls (fit_reset_members, or a new
+        population, restarts them). Returns float64[n_steps, n_m]: each member's loss BEFORE each step's update -- the bits fit gives
+        on a batch that carries the row as its shared network."""
+        m, _ = self._fit_members(members)
+        ix = self._fit_members_idx(idx_table, m.size, 3)
+        hyper = dict(hyper or {})
+        optimizer = hyper.pop('optimizer', 'adam')
+        if optimizer not in _lib.FIT_OPTIMIZERS:
+            raise ValueError("optimizer must be one of %r (got %r)" % (sorted(_lib.FIT_OPTIMIZERS), optimizer))
+        vals = dict(lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, momentum=0.0)
+        unknown = sorted(set(hyper) - set(vals))
+        if unknown:
+            raise ValueError("unknown hyper-parameters %r" % unknown)
+        vals.update(hyper)
+        p = (_lib.ClothFitParams * m.size)()
+        for k, v in vals.items():
+            v = np.asarray(v, dtype=np.float64)
+            if v.ndim > 1 or (v.ndim == 1 and v.size != m.size):
+                raise ValueError("%s must be a scalar or %d values, one per member" % (k, m.size))
+            v = np.broadcast_to(v, (m.size,)).astype(np.float32)
+            if not (np.isfinite(v).all() and (v >= 0.0).all()) or (k.startswith('beta') and (v >= 1.0).any()):
+                raise ValueError("%s = %r: hyper-parameters are finite and >= 0, the betas below 1" % (k, vals[k]))
+            for j in range(m.size):
+                setattr(p[j], k, float(v[j]))
+        for j in range(m.size):
+            p[j].optimizer = float(_lib.FIT_OPTIMIZERS[optimizer])
+        loss = np.zeros((ix.shape[0], m.size), dtype=np.float64)
+        check(self._L.clothhip_policy_fit_members(self._h, p, _lib.i32p(m), m.size, _lib.i32p(ix), ix.shape[0], ix.shape[2], _lib.dp(loss)))
+        return loss
+
+    def fit_reset_members(self, members=None):
+        """Zero the moments and the step count of the population rows `members`, None: of all rows (clothhip_policy_fit_reset_members)."""
+        if members is None:
+            check(self._L.clothhip_policy_fit_reset_members(self._h, None, 0))
+            return
+        m, _ = self._fit_members(members)
+        check(self._L.clothhip_policy_fit_reset_members(self._h, _lib.i32p(m), m.size))
 
     # ---- the cross-entropy planner over forked cloths (clothhip_plan_*) ------------------------------------------
     @staticmethod

@@ -457,3 +457,280 @@ extern "C" int clothhip_policy_fit_reset(clothhip_handle *h) {
     h->fit_forget();
     return 0;
 }
+
+// ---- the grouped trainer: rows of the population fitted in the launches of one network (clothhip.h: clothhip_policy_fit*_members) --------
+static_assert(CLOTHHIP_FIT_MAX_MEMBER_ROWS == 65536, "the header's cap on n_m * B of one call");
+
+// What the entries refuse before anything is touched, in the style of check_fit: the member list of a call ...
+static int check_fit_members(const clothhip_handle *h, const int32_t *members, int32_t n_m) {
+    if (n_m < 1) return fail(CLOTHHIP_EINVAL, "n_m = %d: a call names at least one member", n_m);
+    if (!members) return fail(CLOTHHIP_EINVAL, "members is NULL");
+    std::vector<uint8_t> seen;
+    try { seen.assign((size_t)h->pol.pop_rows, 0); } catch (const std::bad_alloc &) { return fail(CLOTHHIP_ENOMEM, "out of host memory (%lld rows)", (long long)h->pol.pop_rows); }
+    for (int32_t j = 0; j < n_m; j++) {
+        if (members[j] < 0 || members[j] >= h->pol.pop_rows)
+            return fail(CLOTHHIP_EINVAL, "members[%d] = %d outside [0, %lld)", j, members[j], (long long)h->pol.pop_rows);
+        if (seen[members[j]]) return fail(CLOTHHIP_EINVAL, "members[%d] = %d is named twice: a call fits a row once", j, members[j]);
+        seen[members[j]] = 1;
+    }
+    return 0;
+}
+// ... and its minibatches
+static int check_fit_members_rows(const clothhip_handle *h, int32_t n_m, const int32_t *idx, int64_t n_steps, int32_t B) {
+    if (B < 1 || B > FIT_MAX_BATCH) return fail(CLOTHHIP_EINVAL, "B = %d outside [1, %d]", B, FIT_MAX_BATCH);
+    if ((int64_t)n_m * B > CLOTHHIP_FIT_MAX_MEMBER_ROWS)
+        return fail(CLOTHHIP_EINVAL, "n_m * B = %d * %d rows in one call, at most %d", n_m, B, CLOTHHIP_FIT_MAX_MEMBER_ROWS);
+    const int64_t n_idx = n_steps * n_m * B;
+    if (!idx && n_idx > 0) return fail(CLOTHHIP_EINVAL, "idx is NULL");
+    for (int64_t i = 0; i < n_idx; i++)
+        if (idx[i] < 0 || idx[i] >= h->fit.n) return fail(CLOTHHIP_EINVAL, "idx[%lld] = %d outside [0, %lld)", (long long)i, idx[i], (long long)h->fit.n);
+    return 0;
+}
+// the state refusals come first, whatever else is wrong with the call
+static int check_fit_members_state(const clothhip_handle *h) {
+    if (int rc = check_idle(h)) return rc;
+    if (h->pol.mlp.n_layers < 1) return fail(CLOTHHIP_ESTATE, "no network on this handle: call clothhip_set_policy_population first");
+    if (!h->pol.pop_rows) return fail(CLOTHHIP_ESTATE, "this handle holds ONE shared network, not a population: use clothhip_policy_fit");
+    if (h->fit.n < 1) return fail(CLOTHHIP_ESTATE, "the dataset is empty: call clothhip_fit_data_append first");
+    return 0;
+}
+
+// Where member j's tables lie: the per-member sizes of the scratch tables (floats) for minibatches of B rows, and the offsets of every
+// layer inside a blob (weights, gradient) and inside a member's activations.
+struct MembersPlan {
+    size_t act, dz, part, grad, maxw;       // per member: activations, the two dZ tables, the slabs (0 without a split), the gradient
+    int n_split;
+    size_t w_off[MLP_MAX_LAYERS], h_off[MLP_MAX_LAYERS];
+};
+static MembersPlan members_plan(const clothhip_handle *h, int32_t B) {
+    const MlpDesc &D = h->pol.mlp;
+    MembersPlan p = {};
+    size_t maxmat = 0;
+    p.maxw = MLP_OUT;
+    for (int l = 0; l < D.n_layers; l++) {
+        p.w_off[l] = p.grad; p.h_off[l] = p.act;
+        p.grad += (size_t)D.widths[l + 1] * D.widths[l] + D.widths[l + 1];
+        p.act += (size_t)B * D.widths[l + 1];
+        p.maxw = std::max<size_t>(p.maxw, D.widths[l + 1]);
+        maxmat = std::max<size_t>(maxmat, (size_t)D.widths[l + 1] * D.widths[l]);
+    }
+    p.dz = 2 * (size_t)B * p.maxw;
+    p.n_split = (B + FIT_SPLIT_ROWS - 1) / FIT_SPLIT_ROWS;
+    p.part = p.n_split > 1 ? (size_t)p.n_split * maxmat : 0;
+    return p;
+}
+static int reserve_fit_members(clothhip_handle *h, const MembersPlan &p, int32_t n_m) {
+    auto &f = h->fit;
+    if (int rc = f.d_members.reserve((size_t)n_m * 4)) return rc;
+    if (int rc = f.d_act.reserve((size_t)n_m * p.act * 4)) return rc;
+    if (int rc = f.d_dz.reserve((size_t)n_m * p.dz * 4)) return rc;
+    if (p.part) if (int rc = f.d_part.reserve((size_t)n_m * p.part * 4)) return rc;
+    return f.d_grad.reserve((size_t)n_m * p.grad * 4);
+}
+
+template <bool A_KC, bool B_KC, int EPI, bool ROWS> static void launch_gemm_members(hipStream_t s, FitGemmMembersArgs &m, int32_t n_m) {
+    const FitGemmArgs &a = m.g;
+    m.tiles_n = (a.N + FIT_TILE - 1) / FIT_TILE;
+    const dim3 grid((unsigned)m.tiles_n * (unsigned)n_m, (unsigned)((a.M + FIT_TILE - 1) / FIT_TILE), (unsigned)((a.K + a.k_chunk - 1) / a.k_chunk));
+    hipLaunchKernelGGL((k_fit_gemm_members<A_KC, B_KC, EPI, ROWS>), grid, dim3(FIT_THREADS), 0, s, m);
+}
+
+// enqueue_grad for n_m members: every launch of one network's step, each over all members. d_idx [n_m][B], d_loss [n_m]; the gradients
+// land in h->fit.d_grad [n_m][n_params]
+static int enqueue_grad_members(clothhip_handle *h, const MembersPlan &p, int32_t n_m, const int32_t *d_idx, int32_t B, double *d_loss) {
+    const MlpDesc &D = h->pol.mlp;
+    const int L = D.n_layers;
+    auto &f = h->fit;
+    float *act = f.d_act, *grad = f.d_grad, *dz[2] = {f.d_dz, f.d_dz + (size_t)B * p.maxw};
+    FitGemmMembersArgs m0 = {};
+    m0.members = f.d_members; m0.stride = D.stride; m0.rows_step = B;
+    for (int l = 0; l < L; l++) {
+        const int n_in = D.widths[l], n_out = D.widths[l + 1];
+        FitGemmMembersArgs m = m0;
+        FitGemmArgs &a = m.g;
+        a.A = l ? act + p.h_off[l - 1] : (const float *)f.d_obs; a.lda = n_in; a.rows = l ? nullptr : d_idx; m.a_step = l ? (int64_t)p.act : 0;
+        a.B = D.params + p.w_off[l]; a.ldb = n_in; a.bias = a.B + (size_t)n_out * n_in; m.b_weights = 1;
+        a.C = act + p.h_off[l]; a.ldc = n_out; m.c_step = (int64_t)p.act;
+        a.M = B; a.N = n_out; a.K = n_in; a.k_chunk = n_in;
+        if (l == 0 && l + 1 < L) launch_gemm_members<true, true, FIT_EPI_BIAS_RELU, true>(h->stream, m, n_m);
+        else if (l == 0) launch_gemm_members<true, true, FIT_EPI_BIAS, true>(h->stream, m, n_m);
+        else if (l + 1 < L) launch_gemm_members<true, true, FIT_EPI_BIAS_RELU, false>(h->stream, m, n_m);
+        else launch_gemm_members<true, true, FIT_EPI_BIAS, false>(h->stream, m, n_m);
+        HIPCHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_fit_loss_members, dim3((unsigned)n_m), dim3(256), 0, h->stream, (const float *)(act + p.h_off[L - 1]), (const float *)f.d_lab, d_idx, B,
+                       dz[(L - 1) & 1], d_loss, (int64_t)p.act, (int64_t)p.dz, (int64_t)B);
+    HIPCHECK(hipGetLastError());
+    for (int l = L - 1; l >= 0; l--) {
+        const int n_in = D.widths[l], n_out = D.widths[l + 1];
+        const float *dzl = dz[l & 1];
+        float *gWl = grad + p.w_off[l];
+        FitGemmMembersArgs m = m0;
+        FitGemmArgs &a = m.g;
+        a.A = dzl; a.lda = n_out; m.a_step = (int64_t)p.dz;
+        a.B = l ? act + p.h_off[l - 1] : (const float *)f.d_obs; a.ldb = n_in; a.rows = l ? nullptr : d_idx; m.b_step = l ? (int64_t)p.act : 0;
+        a.C = p.n_split > 1 ? (float *)f.d_part : gWl; a.ldc = n_in; a.c_slab = (int64_t)n_out * n_in; m.c_step = (int64_t)(p.n_split > 1 ? p.part : p.grad);
+        a.M = n_out; a.N = n_in; a.K = B; a.k_chunk = FIT_SPLIT_ROWS;
+        if (l == 0) launch_gemm_members<false, false, FIT_EPI_NONE, true>(h->stream, m, n_m);
+        else launch_gemm_members<false, false, FIT_EPI_NONE, false>(h->stream, m, n_m);
+        HIPCHECK(hipGetLastError());
+        if (p.n_split > 1) {
+            const int64_t n = (int64_t)n_out * n_in;
+            const int32_t blocks = (int32_t)((n + 255) / 256);
+            hipLaunchKernelGGL(k_fit_reduce_members, dim3((unsigned)blocks * (unsigned)n_m), dim3(256), 0, h->stream, (const float *)f.d_part, n, p.n_split, gWl, n,
+                               (int64_t)p.part, (int64_t)p.grad, blocks);
+            HIPCHECK(hipGetLastError());
+        }
+        const int32_t cblocks = (n_out + 63) / 64;
+        hipLaunchKernelGGL(k_fit_colsum_members, dim3((unsigned)cblocks * (unsigned)n_m), dim3(64), 0, h->stream, dzl, B, n_out, gWl + (size_t)n_out * n_in,
+                           (int64_t)p.dz, (int64_t)p.grad, cblocks);
+        HIPCHECK(hipGetLastError());
+        if (l > 0) {
+            FitGemmMembersArgs mb = m0;
+            FitGemmArgs &b = mb.g;
+            b.A = dzl; b.lda = n_out; mb.a_step = (int64_t)p.dz;
+            b.B = D.params + p.w_off[l]; b.ldb = n_in; mb.b_weights = 1;
+            b.mask = act + p.h_off[l - 1]; mb.mask_step = (int64_t)p.act;
+            b.C = dz[(l - 1) & 1]; b.ldc = n_in; mb.c_step = (int64_t)p.dz;
+            b.M = B; b.N = n_in; b.K = n_out; b.k_chunk = n_out;
+            launch_gemm_members<true, false, FIT_EPI_MASK, false>(h->stream, mb, n_m);
+            HIPCHECK(hipGetLastError());
+        }
+    }
+    return 0;
+}
+
+extern "C" int clothhip_policy_fit_grad_members(clothhip_handle *h, const int32_t *members, int32_t n_m, const int32_t *idx, int32_t B, float *grad_out,
+                                                double *loss_out) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (int rc = check_fit_members_state(h)) return rc;
+    if (int rc = check_fit_members(h, members, n_m)) return rc;
+    if (int rc = check_fit_members_rows(h, n_m, idx, 1, B)) return rc;
+    if (!idx) return fail(CLOTHHIP_EINVAL, "idx is NULL");
+    auto &f = h->fit;
+    const MembersPlan p = members_plan(h, B);
+    HIPCHECK(hipSetDevice(h->device));
+    if (int rc = reserve_fit_members(h, p, n_m)) return rc;
+    if (int rc = f.d_idx.reserve((size_t)n_m * B * 4)) return rc;
+    if (int rc = f.d_loss.reserve((size_t)n_m * 8)) return rc;
+    HIPCHECK(hipMemcpyAsync(f.d_members, members, (size_t)n_m * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipMemcpyAsync(f.d_idx, idx, (size_t)n_m * B * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipEventRecord(h->ev0, h->stream));
+    if (int rc = enqueue_grad_members(h, p, n_m, f.d_idx, B, f.d_loss)) return rc;
+    HIPCHECK(hipEventRecord(h->ev1, h->stream));
+    h->have_timing = true;
+    if (grad_out) HIPCHECK(hipMemcpyAsync(grad_out, f.d_grad, (size_t)n_m * p.grad * 4, hipMemcpyDeviceToHost, h->stream));
+    if (loss_out) HIPCHECK(hipMemcpyAsync(loss_out, f.d_loss, (size_t)n_m * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// clothhip_policy_fit's refusals of an optimizer, for member j of a grouped call
+static int check_fit_params(const ClothFitParams *p, int32_t j) {
+    if (p->optimizer != (float)CLOTHHIP_FIT_ADAM && p->optimizer != (float)CLOTHHIP_FIT_SGD)
+        return fail(CLOTHHIP_EINVAL, "p[%d]: unknown optimizer %g (CLOTHHIP_FIT_ADAM or CLOTHHIP_FIT_SGD)", j, (double)p->optimizer);
+    if (!hyper_ok(p->lr) || !hyper_ok(p->eps) || !hyper_ok(p->momentum) || !hyper_ok(p->beta1) || !hyper_ok(p->beta2))
+        return fail(CLOTHHIP_EINVAL, "p[%d]: a hyper-parameter is negative or not finite (lr %g, beta1 %g, beta2 %g, eps %g, momentum %g)", j, (double)p->lr,
+                    (double)p->beta1, (double)p->beta2, (double)p->eps, (double)p->momentum);
+    if (p->beta1 >= 1.0f || p->beta2 >= 1.0f) return fail(CLOTHHIP_EINVAL, "p[%d]: beta1 %g, beta2 %g: both lie in [0, 1)", j, (double)p->beta1, (double)p->beta2);
+    return 0;
+}
+
+// the per-row optimizer state exists from the first grouped call after a new network: every row fresh
+static int ensure_row_state(clothhip_handle *h) {
+    auto &f = h->fit;
+    const size_t rows = (size_t)h->pol.pop_rows;
+    if (f.row_t.size() == rows && f.row_zero.size() == rows) return 0;
+    try { f.row_t.assign(rows, 0); f.row_zero.assign(rows, 1); } catch (const std::bad_alloc &) {
+        f.row_t.clear(); f.row_zero.clear();
+        return fail(CLOTHHIP_ENOMEM, "out of host memory (%zu rows)", rows);
+    }
+    return 0;
+}
+
+extern "C" int clothhip_policy_fit_members(clothhip_handle *h, const ClothFitParams *p, const int32_t *members, int32_t n_m, const int32_t *idx,
+                                           int32_t n_steps, int32_t B, double *loss_out) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (int rc = check_fit_members_state(h)) return rc;
+    if (!p) return fail(CLOTHHIP_EINVAL, "NULL argument");
+    if (n_steps < 0) return fail(CLOTHHIP_EINVAL, "n_steps < 0");
+    if (int rc = check_fit_members(h, members, n_m)) return rc;
+    if (int rc = check_fit_members_rows(h, n_m, idx, n_steps, B)) return rc;
+    for (int32_t j = 0; j < n_m; j++) {
+        if (int rc = check_fit_params(p + j, j)) return rc;
+        if (p[j].optimizer != p[0].optimizer) return fail(CLOTHHIP_EINVAL, "p[%d].optimizer = %g, p[0].optimizer = %g: one optimizer per call", j, (double)p[j].optimizer, (double)p[0].optimizer);
+    }
+    if (n_steps == 0) return 0;
+    const bool adam = p[0].optimizer == (float)CLOTHHIP_FIT_ADAM;
+    auto &f = h->fit;
+    const MlpDesc &D = h->pol.mlp;
+    const MembersPlan pl = members_plan(h, B);
+    const size_t n = h->pol.mlp_n_params, stride = (size_t)D.stride, rows = (size_t)h->pol.pop_rows, n_sm = (size_t)n_steps * n_m;
+    // the step constants of every (step, member), in double on the host as clothhip_policy_fit makes them; nothing of the handle changes yet
+    std::vector<float> hyper;
+    try { hyper.assign(n_sm * FIT_HYPER, 0.0f); } catch (const std::bad_alloc &) { return fail(CLOTHHIP_ENOMEM, "out of host memory (%zu step constants)", n_sm * FIT_HYPER); }
+    if (int rc = ensure_row_state(h)) return rc;
+    for (int s = 0; s < n_steps; s++)
+        for (int32_t j = 0; j < n_m; j++) {
+            float *q = hyper.data() + ((size_t)s * n_m + j) * FIT_HYPER;
+            const ClothFitParams &pj = p[j];
+            if (adam) {
+                const double b1 = (double)pj.beta1, b2 = (double)pj.beta2, t = (double)(f.row_t[members[j]] + s + 1);
+                const double a_t = (double)pj.lr * std::sqrt(1.0 - std::pow(b2, t)) / (1.0 - std::pow(b1, t));
+                q[0] = (float)a_t; q[1] = pj.beta1; q[2] = (float)(1.0 - b1); q[3] = pj.beta2; q[4] = (float)(1.0 - b2); q[5] = pj.eps;
+            } else {
+                q[0] = pj.lr; q[1] = pj.momentum;
+            }
+        }
+    HIPCHECK(hipSetDevice(h->device));
+    if (int rc = reserve_fit_members(h, pl, n_m)) return rc;
+    if (int rc = f.d_idx.reserve(n_sm * B * 4)) return rc;
+    if (int rc = f.d_loss.reserve(n_sm * 8)) return rc;
+    if (int rc = f.d_hyper.reserve(n_sm * FIT_HYPER * 4)) return rc;
+    // the moments of the whole population, [pop_rows][stride]: a table of the shared trainer's size (or none) holds no row's state, so
+    // growing it loses nothing -- every row is still flagged read-as-zeros then
+    if (int rc = f.d_m.reserve(rows * stride * 4)) return rc;
+    if (int rc = f.d_v.reserve(rows * stride * 4)) return rc;
+    // from here on the call goes through (but for a failure of the runtime itself)
+    for (int32_t j = 0; j < n_m; j++) {
+        const int32_t g = members[j];
+        if (f.row_zero[g]) {
+            HIPCHECK(hipMemsetAsync(f.d_m + (size_t)g * stride, 0, n * 4, h->stream));
+            HIPCHECK(hipMemsetAsync(f.d_v + (size_t)g * stride, 0, n * 4, h->stream));
+            f.row_zero[g] = 0;
+        }
+        f.row_t[g] += n_steps;
+    }
+    HIPCHECK(hipMemcpyAsync(f.d_members, members, (size_t)n_m * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipMemcpyAsync(f.d_idx, idx, n_sm * B * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipMemcpyAsync(f.d_hyper, hyper.data(), n_sm * FIT_HYPER * 4, hipMemcpyHostToDevice, h->stream));
+    FitOptMembersArgs o = {};
+    o.theta = h->pol.d_pop; o.m = f.d_m; o.v = f.d_v; o.g = f.d_grad; o.members = f.d_members; o.stride = (int64_t)stride; o.n = (int64_t)n;
+    o.blocks = (int32_t)((n + 255) / 256);
+    const dim3 ogrid((unsigned)o.blocks * (unsigned)n_m);
+    HIPCHECK(hipEventRecord(h->ev0, h->stream));
+    for (int s = 0; s < n_steps; s++) {
+        if (int rc = enqueue_grad_members(h, pl, n_m, f.d_idx + (size_t)s * n_m * B, B, f.d_loss + (size_t)s * n_m)) return rc;
+        o.hyper = f.d_hyper + (size_t)s * n_m * FIT_HYPER;
+        if (adam) hipLaunchKernelGGL(k_fit_adam_members, ogrid, dim3(256), 0, h->stream, o);
+        else hipLaunchKernelGGL(k_fit_sgd_members, ogrid, dim3(256), 0, h->stream, o);
+        HIPCHECK(hipGetLastError());
+    }
+    HIPCHECK(hipEventRecord(h->ev1, h->stream));
+    h->have_timing = true;
+    if (loss_out) HIPCHECK(hipMemcpyAsync(loss_out, f.d_loss, n_sm * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));      // (the host tables are never retained)
+    return 0;
+}
+
+extern "C" int clothhip_policy_fit_reset_members(clothhip_handle *h, const int32_t *members, int32_t n_m) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (int rc = check_idle(h)) return rc;
+    if (h->pol.mlp.n_layers < 1) return fail(CLOTHHIP_ESTATE, "no network on this handle: call clothhip_set_policy_population first");
+    if (!h->pol.pop_rows) return fail(CLOTHHIP_ESTATE, "this handle holds ONE shared network, not a population: use clothhip_policy_fit_reset");
+    if (!members) { h->fit_forget(); return 0; }      // all rows
+    if (int rc = check_fit_members(h, members, n_m)) return rc;
+    if (h->fit.row_t.empty()) return 0;               // every row is fresh already
+    for (int32_t j = 0; j < n_m; j++) { h->fit.row_t[members[j]] = 0; h->fit.row_zero[members[j]] = 1; }
+    return 0;
+}

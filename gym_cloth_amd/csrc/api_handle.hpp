@@ -128,13 +128,18 @@ struct clothhip_handle : HostPlan {
         Buffer<float> d_m, d_v;
         int64_t opt_t = 0;
         bool opt_zero = true;
+        // the grouped trainer of a population (clothhip_policy_fit*_members): d_m, d_v are then [pop_rows][stride], and every row has its
+        // own step count and its own read-as-zeros flag (both empty until the first grouped call after a new network: all rows fresh)
+        std::vector<int64_t> row_t;
+        std::vector<uint8_t> row_zero;
         // one step's scratch, sized on demand: the index table of a call, the hidden activations and y, the two dZ tables, the split batch
-        // sums of a weight gradient, the gradient (blob layout), the losses of a call
-        Buffer<int32_t> d_idx;
-        Buffer<float> d_act, d_dz, d_part, d_grad;
+        // sums of a weight gradient, the gradient (blob layout), the losses of a call; the grouped trainer holds one of each per member
+        // of the call, with the call's member rows and its table of per-member, per-step optimizer constants
+        Buffer<int32_t> d_idx, d_members;
+        Buffer<float> d_act, d_dz, d_part, d_grad, d_hyper;
         Buffer<double> d_loss;
     } fit;
-    void fit_forget() { fit.opt_t = 0; fit.opt_zero = true; }
+    void fit_forget() { fit.opt_t = 0; fit.opt_zero = true; fit.row_t.clear(); fit.row_zero.clear(); }
     // The cross-entropy planner (api_plan.hip: clothhip_plan_cem on the SCRATCH handle, clothhip_plan_sample / _refit on the handle given), all
     // sized on demand: the distribution d_mean, d_std [E][H][4], the best so far d_best_a [E][H][4], d_best_s [E], the source's done flags, the
     // action tables d_x [H][E K][4] (one, or one per iteration when the caller wants them back), d_scores [n_iters][E][K], the elite flags and

@@ -55,10 +55,10 @@ def collect_demos(env, policy='oracle_corner', max_episodes=10, slots_per_launch
     episodes = []
     E = env.E
     obs = env.reset()
-    from .policies import HighestPointPolicy, MLPPolicy, MLPPopulation
+    from .policies import HighestPointPolicy, MLPEnsemble, MLPPolicy, MLPPopulation
     hp = policy if (on_device and isinstance(policy, HighestPointPolicy)) else None
-    mlp = policy if (on_device and isinstance(policy, (MLPPolicy, MLPPopulation))) else None
-    if mlp is not None:
+    mlp = policy if (on_device and isinstance(policy, (MLPPolicy, MLPPopulation, MLPEnsemble))) else None
+    if mlp is not None and not (isinstance(mlp, MLPEnsemble) and env._policy_mlp is mlp):      # (an ensemble on the env holds FITTED rows: an upload would undo the fit)
         env.set_policy(mlp)
     if isinstance(policy, str) or hp is not None or mlp is not None:
         if hp is None and mlp is None and policy != 'oracle_corner':

@@ -532,8 +532,8 @@ class ClothVecEnv(object):
         PER ENV SLOT there instead (its present generation, made on the device). Either way snapshot / restore, forks, the lookahead's
         scratch batch and resets neither carry nor touch networks. On several GPUs every rank sets it itself (dist.py broadcasts no
         weights)."""
-        from .policies import MLPPopulation
-        if isinstance(mlp, MLPPopulation):
+        from .policies import MLPEnsemble, MLPPopulation
+        if isinstance(mlp, (MLPPopulation, MLPEnsemble)):      # (an MLPEnsemble: its G networks as uploaded rows, one per env slot)
             self._policy_mlp = None                # a failed upload leaves the batch without a network
             mlp._upload(self.batch)
             self._policy_mlp = mlp

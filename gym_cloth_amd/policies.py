@@ -21,6 +21,8 @@ CEMPolicy            no reference counterpart: model-predictive control with the
                      plan_sample_reference / plan_refit_reference / cem_reference restate the planner in numpy, bit for bit
 MLPTrainer           no reference counterpart: the supervised refit of the shared network on the device (ClothBatch.fit_*), Adam or SGD over a
                      device-resident dataset of (observation, label) rows; fit_reference is its float64 numpy yardstick
+MLPEnsemble          no reference counterpart: G networks, one per env slot, fitted together on the device in the launches of one
+                     (ClothBatch.fit_members): a bootstrapped ensemble whose disagreement is a novelty signal, a learning-rate sweep
 """
 import numpy as np
 
@@ -539,6 +541,154 @@ class MLPTrainer(object):
     def reset(self):
         """Zero the optimizer's moments and step count; the weights and the dataset stay."""
         self.env.batch.fit_reset()
+
+
+def ensemble_disagreement(actions):
+    """float64[n] from actions [G, n, 4]: the mean over the four action components of the population variance over the G members
+    (numpy float64, var with ddof = 0) -- the novelty signal of a bootstrapped ensemble."""
+    a = np.asarray(actions, dtype=np.float64)
+    if a.ndim != 3 or a.shape[2] != 4 or a.shape[0] < 1:
+        raise ValueError("actions must have shape (G, n, 4) (got %r)" % (a.shape,))
+    return a.var(axis=0).mean(axis=1)
+
+
+class MLPEnsemble(object):
+    """G networks of ONE shape, one per env slot, FITTED TOGETHER ON THE DEVICE (no reference counterpart; ClothBatch.fit_*_members): a
+    bootstrapped ensemble for DAgger (disagreement(obs) is the novelty signal), a learning-rate sweep, population-based training.
+    `members_layers` is a list of G networks, each a list of (W, b) layers as MLPPolicy takes them; the constructor puts them on the env
+    as a population (ClothVecEnv.set_policy -> ClothBatch.set_policy_population, which also restarts every row's optimizer) and empties
+    the dataset. `member` int[E] says which network env e runs (default e % G). step_many(policy='mlp'), collect_demos(on_device=True)
+    and an armed launch take it as they take an MLPPopulation. The dataset is the env's ONE device-resident dataset, with MLPTrainer's
+    methods over it, so demos.dagger_fit and demos.dagger_collect take an ensemble where they take a trainer; step trains every member
+    on ITS OWN minibatches (the bootstrap), all members in the launches of one network, each row in place: the next launch runs the
+    fitted weights with no download and no upload. Member g's weights are bit for bit those of an MLPTrainer that fits network g alone
+    on the same rows. Whoever puts another network on the env afterwards replaces the fitted rows (putting THIS ensemble back uploads
+    the constructor's weights again, not the fitted ones: keep layers(g) if the fit is to survive that).
+
+    Hyper-parameters (lr, beta1, beta2, eps, momentum) are scalars or sequences of G, one per member; the optimizer is one."""
+
+    noise_std = 0.0        # (collect_demos: no exploration noise)
+
+    def __init__(self, env, members_layers, member=None, optimizer='adam', lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, momentum=0.0):
+        from . import _lib
+        if optimizer not in _lib.FIT_OPTIMIZERS:
+            raise ValueError("optimizer must be one of %r (got %r)" % (sorted(_lib.FIT_OPTIMIZERS), optimizer))
+        self.env = env
+        self.nets = [[(np.array(W, dtype=np.float32), np.array(b, dtype=np.float32)) for W, b in layers] for layers in members_layers]
+        self.widths, blob = pack_population(self.nets, n_in=3 * env.P)
+        self.G, self.n_params = int(blob.shape[0]), int(blob.shape[1])
+        self.hyper = {'optimizer': optimizer}
+        for k, v in (('lr', lr), ('beta1', beta1), ('beta2', beta2), ('eps', eps), ('momentum', momentum)):
+            v = np.asarray(v, dtype=np.float64)
+            if v.ndim > 1 or (v.ndim == 1 and v.size != self.G):
+                raise ValueError("%s must be a scalar or %d values, one per member" % (k, self.G))
+            v32 = v.astype(np.float32)
+            if not (np.isfinite(v32).all() and (v32 >= 0.0).all()) or (k.startswith('beta') and (v32 >= 1.0).any()):
+                raise ValueError("%s = %r: hyper-parameters are finite and >= 0, the betas below 1" % (k, v.tolist()))
+            self.hyper[k] = np.broadcast_to(v, (self.G,)).copy()
+        m = np.arange(env.E) % self.G if member is None else np.asarray(member)
+        if m.shape != (env.E,):
+            raise ValueError("member must have shape (%d,) (got %r)" % (env.E, m.shape))
+        if not np.issubdtype(m.dtype, np.integer) or m.min() < 0 or m.max() >= self.G:
+            raise ValueError("member must hold integers in [0, %d)" % self.G)
+        self.member = m.astype(np.int32)
+        env.set_policy(self)
+        env.batch.fit_clear()
+
+    def _upload(self, batch):
+        batch.set_policy_population(self.nets, self.member)
+
+    def _on_env(self):
+        if self.env._policy_mlp is not self:
+            raise ValueError("another network was put on the env: the ensemble's fitted rows are gone (env.set_policy(ensemble) uploads "
+                             "the constructor's weights again)")
+
+    def _members(self, members):
+        """members (None: all G) as a checked int array of distinct rows."""
+        m = np.arange(self.G) if members is None else np.asarray(members)
+        if m.ndim != 1 or m.size < 1 or not np.issubdtype(m.dtype, np.integer) or m.min() < 0 or m.max() >= self.G:
+            raise ValueError("members must be a non-empty 1-d array of integers in [0, %d)" % self.G)
+        if np.unique(m).size != m.size:
+            raise ValueError("members must be distinct")
+        return m.astype(np.int32)
+
+    # the dataset: MLPTrainer's methods over the env's one dataset
+    def append(self, obs, labels):
+        """Add rows to the dataset (obs [n, 3P], labels [n, 4], finite); returns its size."""
+        return self.env.batch.fit_append(obs, labels)
+
+    def append_launch(self, rows):
+        """Add rows that lie on the device (ClothBatch.fit_append_launch), as MLPTrainer.append_launch; returns the dataset's size."""
+        return self.env.batch.fit_append_launch(rows)
+
+    def data(self, first=0, n=None):
+        """(obs float32[n, 3P], labels float32[n, 4]): the stored rows [first, first + n) by download, n=None: to the end."""
+        return self.env.batch.fit_data(first, n)
+
+    def size(self):
+        return self.env.batch.fit_size()
+
+    def clear(self):
+        self.env.batch.fit_clear()
+
+    def index_table(self, n, n_steps, batch_size, seed, bootstrap=True):
+        """int32[n_steps, G, batch_size] rows of a dataset of n, a function of the arguments (and G) alone. bootstrap=True:
+        RandomState(seed).randint(0, n, size=(n_steps, G, batch_size)) -- every member draws its own minibatches; bootstrap=False:
+        MLPTrainer.index_table(n, n_steps, batch_size, seed) repeated along the member axis -- every member sees the same rows."""
+        if int(n) < 1 or int(n_steps) < 0 or int(batch_size) < 1:
+            raise ValueError("index_table needs n >= 1, n_steps >= 0, batch_size >= 1")
+        if bootstrap:
+            return np.random.RandomState(seed).randint(0, int(n), size=(int(n_steps), self.G, int(batch_size))).astype(np.int32)
+        one = MLPTrainer.index_table(n, n_steps, batch_size, seed)
+        return np.ascontiguousarray(np.repeat(one[:, None, :], self.G, axis=1))
+
+    def step(self, n_steps, batch_size, seed, members=None, bootstrap=True):
+        """n_steps optimizer steps of the rows `members` (None: all G) on the minibatches index_table(size(), n_steps, batch_size, seed,
+        bootstrap)[:, members]; returns float64[n_steps, n_m], each member's loss before each step's update."""
+        n = self.size()
+        if n < 1:
+            raise ValueError("the dataset is empty: append first")
+        m = self._members(members)
+        self._on_env()
+        table = np.ascontiguousarray(self.index_table(n, n_steps, batch_size, seed, bootstrap)[:, m])
+        hyper = {k: (v if k == 'optimizer' else v[m]) for k, v in self.hyper.items()}
+        return self.env.batch.fit_members(m, table, hyper)
+
+    def grad(self, idx, members=None):
+        """(loss float64[n_m], [[(dW, db), ...] per member]) over the dataset rows idx [n_m, B] at the present weights, float32 from the
+        device; nothing is updated."""
+        m = self._members(members)
+        self._on_env()
+        loss, g = self.env.batch.fit_grad_members(m, idx)
+        return loss, [unpack_mlp(self.widths, g[j]) for j in range(m.size)]
+
+    def layers(self, g):
+        """Network g as the device holds it now: [(W, b), ...] float32, by download (clothhip_get_policy_mlp)."""
+        self._on_env()
+        return unpack_mlp(self.widths, self.env.batch.get_policy_mlp(int(g), self.n_params))
+
+    def reset(self, members=None):
+        """Zero the moments and step counts of the rows `members` (None: all); the weights and the dataset stay."""
+        self._on_env()
+        self.env.batch.fit_reset_members(None if members is None else self._members(members))
+
+    def get_action(self, obs, t=0):
+        """float64[E, 4]: env e's network member[e] on obs[e], on the device -- the bits the launch computes."""
+        self._on_env()
+        return self.env.batch.policy_eval_members(np.asarray(obs).reshape(self.env.E, -1).astype(np.float32), self.member)
+
+    def actions(self, obs):
+        """float64[G, n, 4]: every member on every row of obs [n, 3P], on the device (ClothBatch.policy_eval_members on the rows tiled G
+        times)."""
+        self._on_env()
+        rows = np.ascontiguousarray(obs, dtype=np.float32).reshape(-1, int(self.widths[0]))
+        n = rows.shape[0]
+        out = self.env.batch.policy_eval_members(np.tile(rows, (self.G, 1)), np.repeat(np.arange(self.G, dtype=np.int32), n))
+        return out.reshape(self.G, n, 4)
+
+    def disagreement(self, obs):
+        """float64[n]: ensemble_disagreement(actions(obs)) -- per row the mean over the action components of the members' variance."""
+        return ensemble_disagreement(self.actions(obs))
 
 
 # ---- the cross-entropy planner (clothhip.h: PLAN ACTIONS ON THE DEVICE; csrc/cloth_plan.hpp) ----------------------------------------------

@@ -413,7 +413,8 @@ int clothhip_policy_population_perturb(clothhip_handle *h, int32_t n_layers, con
 /* out[i] = (float) sum_{k ascending} (double)coef[k] * (double)eps_k[i], i < n_params, eps made again from the remembered seed: the
  * evolution-strategies update without a second copy of the noise. K = G / 2 with the antithetic flag, G without; anything else is
  * CLOTHHIP_EINVAL. CLOTHHIP_ESTATE without a population, or with one that was uploaded rather than generated. clothhip_last_kernel_ms
- * gives the kernel's time. */
+ * gives the kernel's time. The rows themselves are not read: after clothhip_policy_fit_members has trained them the sum is still that
+ * of the last perturb's noise. */
 int clothhip_policy_population_combine(clothhip_handle *h, const float *coef, int32_t K, float *out);
 
 /* An EXPERT beside the acting policy (DAgger: examples/analytic.py's oracle says what it would have done in every state the learner
@@ -531,6 +532,40 @@ typedef struct ClothFitParams { float optimizer /* CLOTHHIP_FIT_* */, lr, beta1,
 #define CLOTHHIP_FIT_MAX_BATCH 4096
 int clothhip_policy_fit(clothhip_handle *h, const ClothFitParams *p, const int32_t *idx, int32_t n_steps, int32_t B, double *loss_out);
 int clothhip_policy_fit_reset(clothhip_handle *h);
+/* FIT ROWS OF A POPULATION in the launches of one network (no reference counterpart: a bootstrapped ensemble for DAgger, a learning-rate
+ * sweep, population-based training). members[n_m] (host int32) are DISTINCT rows of the handle's population (clothhip_set_policy_population
+ * or clothhip_policy_population_perturb, whose centre row may be named too), in any order, a subset or all. The dataset is the handle's
+ * one dataset; member j has its own minibatches: idx[n_steps][n_m][B] (for the gradient idx[n_m][B]) -- the bootstrap -- and its own
+ * hyper-parameters p[j] (p[n_m]; the `optimizer` fields of one call must all be equal). Row members[j] is updated in place where it
+ * lies, so the next episode launch with CLOTHHIP_POLICY_MLP, clothhip_policy_eval_members and clothhip_get_policy_mlp see the new weights
+ * with no upload. Rows not named keep their bytes, and no call writes the pad floats of a row (n_params .. stride).
+ * THE BITS. After any sequence of these calls, row g and its optimizer state are what a second handle holds that was given g as its
+ * shared network (clothhip_set_policy_mlp), stores the same dataset and received the same sequence of
+ * clothhip_policy_fit(p[j], idx[:, j, :]) calls: every kernel of the shared trainer has a grouped form with one more grid index, the
+ * member, and every output element is the same accumulator in the same order (csrc/cloth_policy_fit.hpp). So EVERY ROW has its own Adam
+ * m, v (SGD u) and its own 1-based step count t: a row trained in two calls of 2 steps equals one trained in one call of 4, and a row
+ * that joins later starts at t = 1. a_t = lr sqrt(1 - beta2^t) / (1 - beta1^t) is made in double on the host per member and step, as for
+ * clothhip_policy_fit, and goes up as one table per call. clothhip_policy_fit_grad_members returns for member j the gradient
+ * (grad_out[j][n_params], may be NULL) and the loss (loss_out[j], may be NULL) that clothhip_policy_fit_grad returns on that handle and
+ * updates nothing. clothhip_policy_fit_members: loss_out[s][j] (may be NULL) is member j's loss BEFORE step s. All n_steps are enqueued
+ * behind one upload of the tables; synchronous; clothhip_last_kernel_ms gives the time of all steps on the device.
+ * THE OPTIMIZER STATE lives with the population: clothhip_set_policy_mlp, clothhip_set_policy_population and
+ * clothhip_policy_population_perturb restart every row (the rule of the shared trainer); clothhip_set_policy_members (the map alone)
+ * restarts nothing; clothhip_policy_fit_reset_members restarts the rows named (members == NULL: all rows; n_m is then ignored).
+ * clothhip_policy_population_combine is untouched by a fit: it sums the noise of the last perturb from its seed, whatever the rows hold now.
+ * SCRATCH is sized on demand: per member the activations, two dZ tables, the gradient and (B > 256) the split batch sums, hence the
+ * cap on n_m * B.
+ * Refused before anything is touched -- CLOTHHIP_ESTATE: a launch in flight, no network, a shared network (use clothhip_policy_fit), an
+ * empty dataset (not for the reset). CLOTHHIP_EINVAL: n_m < 1, a member outside [0, rows), a member named twice, B outside
+ * [1, CLOTHHIP_FIT_MAX_BATCH], n_m * B > CLOTHHIP_FIT_MAX_MEMBER_ROWS, n_steps < 0, an index outside the dataset, a hyper-parameter
+ * clothhip_policy_fit would refuse, differing optimizer fields, NULL where a table is needed. n_steps == 0 returns 0 and changes
+ * nothing. clothhip_policy_fit, _fit_grad, _fit_loss and _fit_reset keep refusing a population. */
+#define CLOTHHIP_FIT_MAX_MEMBER_ROWS 65536   /* n_m * B of one call */
+int clothhip_policy_fit_grad_members(clothhip_handle *h, const int32_t *members, int32_t n_m, const int32_t *idx, int32_t B, float *grad_out,
+                                     double *loss_out);
+int clothhip_policy_fit_members(clothhip_handle *h, const ClothFitParams *p, const int32_t *members, int32_t n_m, const int32_t *idx,
+                                int32_t n_steps, int32_t B, double *loss_out);
+int clothhip_policy_fit_reset_members(clothhip_handle *h, const int32_t *members, int32_t n_m);
 
 int clothhip_run_actions(clothhip_handle *h, const ClothEpisodeParams *ep, int32_t T, int32_t policy,
                          const double *actions, int32_t actions_on_device, const int32_t *policy_arg,

@@ -11,7 +11,10 @@ One ClothBatch of one 25x25 cloth (3P = 1875 inputs), a dataset of 8192 uniform 
   * the same steps in numpy float32 (BLAS matmuls, the same Adam) on the host, wall time.
 The smaller shapes are launch- and latency-bound (a step is 4 to 6 kernel launches per layer): the tool says what a step costs there, it
 does not claim a rate.
-    python3 tools/fit_bench.py [--steps 20] [--rounds 5] [--out FILE]"""
+    python3 tools/fit_bench.py [--steps 20] [--rounds 5] [--out FILE]
+--members runs the members section instead (clothhip_policy_fit_members; profiles/fit_members.txt): a grouped Adam step of
+G = 1, 4, 16, 64 networks at B = 256 against G single-network steps timed in the same process.
+    python3 tools/fit_bench.py --members [--steps 20] [--rounds 5] [--out FILE]"""
 import argparse
 import os
 import sys
@@ -71,17 +74,69 @@ def numpy_steps(layers, rows, labels, table, lr=1e-3, b1=0.9, b2=0.999, eps=1e-8
     return time.perf_counter() - t0
 
 
+def members_section(args, rows, labels):
+    """The grouped trainer (clothhip_policy_fit_members): ms per grouped Adam step of G networks at B = 256 against G times
+    the ms of a single-network step -- clothhip_policy_fit on a shared-network handle in this very process, `--rounds` repetitions, so
+    its own spread is known."""
+    single, group = (ClothBatch(bench.bench_cfg(25, 0.02, "tier1"), n_envs=1, precision="f32") for _ in range(2))
+    for x in (single, group):
+        x.fit_append(rows, labels)
+    B = 256
+    r = np.random.RandomState(5)
+    say("fit_bench members: 25x25, B = %d, Adam, %d steps per call, %d calls after one warm-up call; device ms by HIP events around all steps of a call"
+        % (B, args.steps, args.rounds))
+    for hidden in ([64, 64], [256, 256, 256]):
+        widths = [3 * single.P] + hidden + [4]
+        single.set_policy_mlp(layers_of(widths))
+        table = r.randint(0, args.rows, size=(args.steps, B)).astype(np.int32)
+        single.fit(table)
+        dev1, wall1 = [], []
+        for _ in range(args.rounds):
+            t0 = time.perf_counter()
+            single.fit(table)
+            wall1.append((time.perf_counter() - t0) * 1e3 / args.steps)
+            dev1.append(single.last_kernel_ms / args.steps)
+        s1, spread = float(np.median(dev1)), max(dev1) - min(dev1)
+        say("hidden %-15r single network: device %.3f ms/step (the %d calls: %s; spread %.3f), wall %.3f ms/step"
+            % (hidden, s1, args.rounds, " ".join("%.3f" % d for d in dev1), spread, float(np.median(wall1))))
+        for G in (1, 4, 16, 64):
+            group.set_policy_population([layers_of(widths, seed=7 + g) for g in range(G)], np.zeros(1, dtype=np.int32))
+            members = np.arange(G)
+            tbl = r.randint(0, args.rows, size=(args.steps, G, B)).astype(np.int32)
+            group.fit_members(members, tbl)
+            dev, wall = [], []
+            for _ in range(args.rounds):
+                t0 = time.perf_counter()
+                group.fit_members(members, tbl)
+                wall.append((time.perf_counter() - t0) * 1e3 / args.steps)
+                dev.append(group.last_kernel_ms / args.steps)
+            d = float(np.median(dev))
+            say("hidden %-15r G %2d grouped: device %.3f ms/step (min %.3f, max %.3f), wall %.3f ms/step; G single steps %.3f ms (+- %.3f) -> "
+                "grouped / (G x single) = %.3f, %.2f TF" % (hidden, G, d, min(dev), max(dev), float(np.median(wall)), G * s1, G * spread, d / (G * s1),
+                                                            G * flop_per_step(widths, B) / d / 1e9))
+    single.close()
+    group.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--rows", type=int, default=8192)
+    ap.add_argument("--members", action="store_true", help="run the members section (the grouped trainer) instead of the single-network one")
     ap.add_argument("--out", default=None, help="also append the printed lines to this file")
     args = ap.parse_args()
     b = ClothBatch(bench.bench_cfg(25, 0.02, "tier1"), n_envs=1, precision="f32")
     r = np.random.RandomState(3)
     rows = r.uniform(-1, 1, size=(args.rows, 3 * b.P)).astype(np.float32)
     labels = r.uniform(-1, 1, size=(args.rows, 4)).astype(np.float32)
+    if args.members:
+        b.close()
+        members_section(args, rows, labels)
+        if args.out:
+            with open(args.out, "a") as fh:
+                fh.write("\n".join(LINES) + "\n")
+        return
     t0 = time.perf_counter()
     b.fit_append(rows, labels)
     say("fit_bench: 25x25 (1875 inputs), dataset %d rows appended in %.1f ms; %d Adam steps per call, median of %d calls; f32-matrix peak %.0f TF"
