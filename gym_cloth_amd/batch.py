@@ -725,23 +725,43 @@ class ClothBatch(object):
             raise _lib.ClothHipError("no shared network on this batch: call set_policy_mlp first")
         return n
 
+    @staticmethod
+    def _fit_params(hyper, n_m):
+        """_lib.ClothFitParams[n_m] from a dict with fit's keywords (optimizer, lr, beta1, beta2, eps, momentum), each value a scalar for
+        all members or a sequence of n_m, rounded to float32; what the library would refuse is a ValueError here first."""
+        hyper = dict(hyper or {})
+        optimizer = hyper.pop('optimizer', 'adam')
+        if optimizer not in _lib.FIT_OPTIMIZERS:
+            raise ValueError("optimizer must be one of %r (got %r)" % (sorted(_lib.FIT_OPTIMIZERS), optimizer))
+        vals = dict(lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, momentum=0.0)
+        unknown = sorted(set(hyper) - set(vals))
+        if unknown:
+            raise ValueError("unknown hyper-parameters %r" % unknown)
+        vals.update(hyper)
+        p = (_lib.ClothFitParams * n_m)()
+        for k, v in vals.items():
+            v = np.asarray(v, dtype=np.float64)
+            if v.ndim > 1 or (v.ndim == 1 and v.size != n_m):
+                raise ValueError("%s must be a scalar or %d values, one per member" % (k, n_m))
+            v = np.broadcast_to(v, (n_m,)).astype(np.float32)
+            if not (np.isfinite(v).all() and (v >= 0.0).all()) or (k.startswith('beta') and (v >= 1.0).any()):
+                raise ValueError("%s = %r: hyper-parameters are finite and >= 0, the betas below 1" % (k, vals[k]))
+            for j in range(n_m):
+                setattr(p[j], k, float(v[j]))
+        for j in range(n_m):
+            p[j].optimizer = float(_lib.FIT_OPTIMIZERS[optimizer])
+        return p
+
     def fit(self, idx_table, optimizer='adam', lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, momentum=0.0):
         """n_steps optimizer steps on the handle's shared network, in place on the device (clothhip_policy_fit): step s uses the dataset
         rows idx_table[s] (int [n_steps, B]). optimizer 'adam' (lr, beta1, beta2, eps) or 'sgd' (lr, momentum); the hyper-parameters are
         rounded to float32. The moments and the step count persist across calls (fit_reset, or a new network, restarts them). Returns
         float64[n_steps]: each step's loss BEFORE its update. The next step_many(policy='mlp') runs the fitted weights."""
         ix = self._fit_idx(idx_table, 2)
-        if optimizer not in _lib.FIT_OPTIMIZERS:
-            raise ValueError("optimizer must be one of %r (got %r)" % (sorted(_lib.FIT_OPTIMIZERS), optimizer))
-        hyper = dict(lr=lr, beta1=beta1, beta2=beta2, eps=eps, momentum=momentum)
-        for k, v in hyper.items():
-            v = float(np.float32(v))
-            if not (np.isfinite(v) and v >= 0.0) or (k.startswith('beta') and v >= 1.0):
-                raise ValueError("%s = %r: hyper-parameters are finite and >= 0, the betas below 1" % (k, hyper[k]))
+        p = self._fit_params(dict(optimizer=optimizer, lr=lr, beta1=beta1, beta2=beta2, eps=eps, momentum=momentum), 1)
         self._fit_n_params()
-        p = _lib.ClothFitParams(float(_lib.FIT_OPTIMIZERS[optimizer]), lr, beta1, beta2, eps, momentum)
         loss = np.zeros(ix.shape[0], dtype=np.float64)
-        check(self._L.clothhip_policy_fit(self._h, C.byref(p), _lib.i32p(ix), ix.shape[0], ix.shape[1], _lib.dp(loss)))
+        check(self._L.clothhip_policy_fit(self._h, p, _lib.i32p(ix), ix.shape[0], ix.shape[1], _lib.dp(loss)))
         return loss
 
     def fit_reset(self):
@@ -791,27 +811,7 @@ class ClothBatch(object):
         on a batch that carries the row as its shared network."""
         m, _ = self._fit_members(members)
         ix = self._fit_members_idx(idx_table, m.size, 3)
-        hyper = dict(hyper or {})
-        optimizer = hyper.pop('optimizer', 'adam')
-        if optimizer not in _lib.FIT_OPTIMIZERS:
-            raise ValueError("optimizer must be one of %r (got %r)" % (sorted(_lib.FIT_OPTIMIZERS), optimizer))
-        vals = dict(lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, momentum=0.0)
-        unknown = sorted(set(hyper) - set(vals))
-        if unknown:
-            raise ValueError("unknown hyper-parameters %r" % unknown)
-        vals.update(hyper)
-        p = (_lib.ClothFitParams * m.size)()
-        for k, v in vals.items():
-            v = np.asarray(v, dtype=np.float64)
-            if v.ndim > 1 or (v.ndim == 1 and v.size != m.size):
-                raise ValueError("%s must be a scalar or %d values, one per member" % (k, m.size))
-            v = np.broadcast_to(v, (m.size,)).astype(np.float32)
-            if not (np.isfinite(v).all() and (v >= 0.0).all()) or (k.startswith('beta') and (v >= 1.0).any()):
-                raise ValueError("%s = %r: hyper-parameters are finite and >= 0, the betas below 1" % (k, vals[k]))
-            for j in range(m.size):
-                setattr(p[j], k, float(v[j]))
-        for j in range(m.size):
-            p[j].optimizer = float(_lib.FIT_OPTIMIZERS[optimizer])
+        p = self._fit_params(hyper, m.size)
         loss = np.zeros((ix.shape[0], m.size), dtype=np.float64)
         check(self._L.clothhip_policy_fit_members(self._h, p, _lib.i32p(m), m.size, _lib.i32p(ix), ix.shape[0], ix.shape[2], _lib.dp(loss)))
         return loss

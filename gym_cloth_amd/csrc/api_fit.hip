@@ -1,8 +1,9 @@
-// api_fit.hip -- the supervised trainer of the handle's shared network: the device-resident dataset, the loss and its gradient over a minibatch, the optimizer steps.
+// api_fit.hip -- the supervised trainer of the handle's networks: the device-resident dataset, the loss and its gradient over a minibatch, the optimizer steps.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <new>
 #include <vector>
 
@@ -212,256 +213,30 @@ extern "C" int clothhip_fit_data_append_launch(clothhip_handle *h, const int32_t
     return 0;
 }
 
-// ---- the gradient (cloth_policy_fit.hpp has the definition and the order) ---------------------------------------------------------------
-// what both entries refuse before anything is touched
-static int check_fit(const clothhip_handle *h, const int32_t *idx, int64_t n_idx, int32_t B) {
-    if (int rc = check_idle(h)) return rc;
-    if (h->pol.pop_rows) return fail(CLOTHHIP_ESTATE, "this handle holds a population of networks: the fit trains the ONE shared network of clothhip_set_policy_mlp");
-    if (h->pol.mlp.n_layers < 1) return fail(CLOTHHIP_ESTATE, "no network on this handle: call clothhip_set_policy_mlp first");
-    if (h->fit.n < 1) return fail(CLOTHHIP_ESTATE, "the dataset is empty: call clothhip_fit_data_append first");
-    if (B < 1 || B > FIT_MAX_BATCH) return fail(CLOTHHIP_EINVAL, "B = %d outside [1, %d]", B, FIT_MAX_BATCH);
-    if (!idx && n_idx > 0) return fail(CLOTHHIP_EINVAL, "idx is NULL");
-    for (int64_t i = 0; i < n_idx; i++)
-        if (idx[i] < 0 || idx[i] >= h->fit.n) return fail(CLOTHHIP_EINVAL, "idx[%lld] = %d outside [0, %lld)", (long long)i, idx[i], (long long)h->fit.n);
-    return 0;
-}
-
-template <bool A_KC, bool B_KC, int EPI, bool ROWS> static void launch_gemm(hipStream_t s, const FitGemmArgs &a) {
-    const dim3 grid((unsigned)((a.N + FIT_TILE - 1) / FIT_TILE), (unsigned)((a.M + FIT_TILE - 1) / FIT_TILE), (unsigned)((a.K + a.k_chunk - 1) / a.k_chunk));
-    hipLaunchKernelGGL((k_fit_gemm<A_KC, B_KC, EPI, ROWS>), grid, dim3(FIT_THREADS), 0, s, a);
-}
-
-// this step's scratch for minibatches of B rows; the widest layer and the largest weight matrix size the shared tables
-static int reserve_fit(clothhip_handle *h, int32_t B) {
-    const MlpDesc &D = h->pol.mlp;
-    size_t act = (size_t)B * MLP_OUT, maxw = MLP_OUT, maxmat = 0;
-    for (int l = 0; l < D.n_layers; l++) {
-        if (l + 1 < D.n_layers) act += (size_t)B * D.widths[l + 1];
-        maxw = std::max<size_t>(maxw, D.widths[l + 1]);
-        maxmat = std::max<size_t>(maxmat, (size_t)D.widths[l + 1] * D.widths[l]);
-    }
-    const size_t n_split = ((size_t)B + FIT_SPLIT_ROWS - 1) / FIT_SPLIT_ROWS;
-    if (int rc = h->fit.d_act.reserve(act * 4)) return rc;
-    if (int rc = h->fit.d_dz.reserve(2 * (size_t)B * maxw * 4)) return rc;
-    if (n_split > 1) if (int rc = h->fit.d_part.reserve(n_split * maxmat * 4)) return rc;
-    return h->fit.d_grad.reserve(h->pol.mlp_n_params * 4);
-}
-
-static int enqueue_forward(clothhip_handle *h, const int32_t *d_idx, int32_t B, const float *const *W, const float *const *H);
-static int enqueue_backward(clothhip_handle *h, const int32_t *d_idx, int32_t B, const float *const *W, const float *const *H, float *const *gW, float *const *dz);
-
-// enqueue loss and gradient of the present weights over rows d_idx[0 .. B): h->fit.d_grad (blob layout), *d_loss
-static int enqueue_grad(clothhip_handle *h, const int32_t *d_idx, int32_t B, double *d_loss) {
-    const MlpDesc &D = h->pol.mlp;
-    const int L = D.n_layers;
-    auto &f = h->fit;
-    const float *W[MLP_MAX_LAYERS], *H[MLP_MAX_LAYERS];      // H[l]: layer l's output; H[L - 1] = y
-    float *act = f.d_act, *gW[MLP_MAX_LAYERS];
-    size_t maxw = MLP_OUT;
-    {
-        const float *w = D.params;
-        float *g = f.d_grad, *a = act;
-        for (int l = 0; l < L; l++) {
-            W[l] = w; gW[l] = g; H[l] = a;
-            const size_t n = (size_t)D.widths[l + 1] * D.widths[l] + D.widths[l + 1];
-            w += n; g += n; a += (size_t)B * D.widths[l + 1];
-            maxw = std::max<size_t>(maxw, D.widths[l + 1]);
-        }
-    }
-    float *dz[2] = {f.d_dz, f.d_dz + (size_t)B * maxw};
-    if (int rc = enqueue_forward(h, d_idx, B, W, H)) return rc;
-    hipLaunchKernelGGL(k_fit_loss, dim3(1), dim3(256), 0, h->stream, H[L - 1], (const float *)f.d_lab, d_idx, B, dz[(L - 1) & 1], d_loss);
-    HIPCHECK(hipGetLastError());
-    return enqueue_backward(h, d_idx, B, W, H, gW, dz);
-}
-
-// the forward pass over rows d_idx[0 .. B): layer l's output into H[l] (H[L - 1] = y), the dataset read through the index table
-static int enqueue_forward(clothhip_handle *h, const int32_t *d_idx, int32_t B, const float *const *W, const float *const *H) {
-    const MlpDesc &D = h->pol.mlp;
-    const int L = D.n_layers;
-    auto &f = h->fit;
-    for (int l = 0; l < L; l++) {
-        const int n_in = D.widths[l], n_out = D.widths[l + 1];
-        FitGemmArgs a = {};
-        a.A = l ? H[l - 1] : (const float *)f.d_obs; a.lda = n_in; a.rows = l ? nullptr : d_idx;
-        a.B = W[l]; a.ldb = n_in; a.bias = W[l] + (size_t)n_out * n_in;
-        a.C = const_cast<float *>(H[l]); a.ldc = n_out;
-        a.M = B; a.N = n_out; a.K = n_in; a.k_chunk = n_in;
-        if (l == 0 && l + 1 < L) launch_gemm<true, true, FIT_EPI_BIAS_RELU, true>(h->stream, a);
-        else if (l == 0) launch_gemm<true, true, FIT_EPI_BIAS, true>(h->stream, a);
-        else if (l + 1 < L) launch_gemm<true, true, FIT_EPI_BIAS_RELU, false>(h->stream, a);
-        else launch_gemm<true, true, FIT_EPI_BIAS, false>(h->stream, a);
-        HIPCHECK(hipGetLastError());
-    }
-    return 0;
-}
-
-// the backward pass from dz[(L - 1) & 1] = dL/dy: h->fit.d_grad (blob layout)
-static int enqueue_backward(clothhip_handle *h, const int32_t *d_idx, int32_t B, const float *const *W, const float *const *H, float *const *gW, float *const *dz) {
-    const MlpDesc &D = h->pol.mlp;
-    const int L = D.n_layers;
-    auto &f = h->fit;
-    const int n_split = (B + FIT_SPLIT_ROWS - 1) / FIT_SPLIT_ROWS;
-    for (int l = L - 1; l >= 0; l--) {
-        const int n_in = D.widths[l], n_out = D.widths[l + 1];
-        const float *dzl = dz[l & 1];
-        FitGemmArgs a = {};
-        a.A = dzl; a.lda = n_out;
-        a.B = l ? H[l - 1] : (const float *)f.d_obs; a.ldb = n_in; a.rows = l ? nullptr : d_idx;
-        a.C = n_split > 1 ? (float *)f.d_part : gW[l]; a.ldc = n_in; a.c_slab = (int64_t)n_out * n_in;
-        a.M = n_out; a.N = n_in; a.K = B; a.k_chunk = FIT_SPLIT_ROWS;
-        if (l == 0) launch_gemm<false, false, FIT_EPI_NONE, true>(h->stream, a);
-        else launch_gemm<false, false, FIT_EPI_NONE, false>(h->stream, a);
-        HIPCHECK(hipGetLastError());
-        if (n_split > 1) {
-            const int64_t n = (int64_t)n_out * n_in;
-            hipLaunchKernelGGL(k_fit_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (const float *)f.d_part, n, n_split, gW[l], n);
-            HIPCHECK(hipGetLastError());
-        }
-        hipLaunchKernelGGL(k_fit_colsum, dim3((unsigned)((n_out + 63) / 64)), dim3(64), 0, h->stream, dzl, B, n_out, gW[l] + (size_t)n_out * n_in);
-        HIPCHECK(hipGetLastError());
-        if (l > 0) {
-            FitGemmArgs b = {};
-            b.A = dzl; b.lda = n_out;
-            b.B = W[l]; b.ldb = n_in;
-            b.mask = H[l - 1];
-            b.C = dz[(l - 1) & 1]; b.ldc = n_in;
-            b.M = B; b.N = n_in; b.K = n_out; b.k_chunk = n_out;
-            launch_gemm<true, false, FIT_EPI_MASK, false>(h->stream, b);
-            HIPCHECK(hipGetLastError());
-        }
-    }
-    return 0;
-}
-
-extern "C" int clothhip_policy_fit_grad(clothhip_handle *h, const int32_t *idx, int32_t B, float *grad_out, double *loss_out) {
-    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
-    if (int rc = check_fit(h, idx, B > 0 ? B : 0, B)) return rc;
-    if (!idx) return fail(CLOTHHIP_EINVAL, "idx is NULL");
-    auto &f = h->fit;
-    HIPCHECK(hipSetDevice(h->device));
-    if (int rc = reserve_fit(h, B)) return rc;
-    if (int rc = f.d_idx.reserve((size_t)B * 4)) return rc;
-    if (int rc = f.d_loss.reserve(8)) return rc;
-    HIPCHECK(hipMemcpyAsync(f.d_idx, idx, (size_t)B * 4, hipMemcpyHostToDevice, h->stream));
-    HIPCHECK(hipEventRecord(h->ev0, h->stream));
-    if (int rc = enqueue_grad(h, f.d_idx, B, f.d_loss)) return rc;
-    HIPCHECK(hipEventRecord(h->ev1, h->stream));
-    h->have_timing = true;
-    if (grad_out) HIPCHECK(hipMemcpyAsync(grad_out, f.d_grad, h->pol.mlp_n_params * 4, hipMemcpyDeviceToHost, h->stream));
-    if (loss_out) HIPCHECK(hipMemcpyAsync(loss_out, f.d_loss, 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHECK(hipStreamSynchronize(h->stream));
-    return 0;
-}
-
-// The loss alone over any number of rows: chunks of at most FIT_MAX_BATCH through the forward above, each chunk's sum of squares in
-// k_fit_loss's order (k_fit_sqsum), the chunk sums added in ascending order in double on the host, divided once by 4 n.
-extern "C" int clothhip_policy_fit_loss(clothhip_handle *h, const int32_t *idx, int64_t n, double *loss) {
-    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
-    if (n < 1 || n > INT32_MAX) return fail(CLOTHHIP_EINVAL, "n = %lld outside [1, %d]", (long long)n, INT32_MAX);
-    const int32_t Bmax = (int32_t)std::min<int64_t>(n, FIT_MAX_BATCH);
-    if (int rc = check_fit(h, idx, n, Bmax)) return rc;
-    if (!idx || !loss) return fail(CLOTHHIP_EINVAL, "NULL argument");
-    auto &f = h->fit;
-    const MlpDesc &D = h->pol.mlp;
-    const int L = D.n_layers;
-    const int64_t n_chunks = (n + FIT_MAX_BATCH - 1) / FIT_MAX_BATCH;
-    std::vector<double> sums;
-    try { sums.resize((size_t)n_chunks); } catch (const std::bad_alloc &) { return fail(CLOTHHIP_ENOMEM, "out of host memory (%lld chunks)", (long long)n_chunks); }
-    HIPCHECK(hipSetDevice(h->device));
-    if (int rc = reserve_fit(h, Bmax)) return rc;
-    if (int rc = f.d_idx.reserve((size_t)n * 4)) return rc;
-    if (int rc = f.d_loss.reserve((size_t)n_chunks * 8)) return rc;
-    HIPCHECK(hipMemcpyAsync(f.d_idx, idx, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
-    HIPCHECK(hipEventRecord(h->ev0, h->stream));
-    for (int64_t c = 0; c < n_chunks; c++) {
-        const int32_t B = (int32_t)std::min<int64_t>(FIT_MAX_BATCH, n - c * FIT_MAX_BATCH);
-        const float *W[MLP_MAX_LAYERS], *H[MLP_MAX_LAYERS];
-        const float *w = D.params;
-        float *a = f.d_act;
-        for (int l = 0; l < L; l++) {
-            W[l] = w; H[l] = a;
-            w += (size_t)D.widths[l + 1] * D.widths[l] + D.widths[l + 1]; a += (size_t)B * D.widths[l + 1];
-        }
-        const int32_t *d_idx = f.d_idx + (size_t)c * FIT_MAX_BATCH;
-        if (int rc = enqueue_forward(h, d_idx, B, W, H)) return rc;
-        hipLaunchKernelGGL(k_fit_sqsum, dim3(1), dim3(256), 0, h->stream, H[L - 1], (const float *)f.d_lab, d_idx, B, f.d_loss + c);
-        HIPCHECK(hipGetLastError());
-    }
-    HIPCHECK(hipEventRecord(h->ev1, h->stream));
-    h->have_timing = true;
-    HIPCHECK(hipMemcpyAsync(sums.data(), f.d_loss, (size_t)n_chunks * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHECK(hipStreamSynchronize(h->stream));
-    double s = sums[0];
-    for (int64_t c = 1; c < n_chunks; c++) s = s + sums[c];
-    *loss = s / (double)(4 * n);
-    return 0;
-}
-
-// ---- the optimizer ----------------------------------------------------------------------------------------------------------------------
-static bool hyper_ok(float v) { return std::isfinite(v) && v >= 0.0f; }
-
-extern "C" int clothhip_policy_fit(clothhip_handle *h, const ClothFitParams *p, const int32_t *idx, int32_t n_steps, int32_t B, double *loss_out) {
-    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
-    if (!p) return fail(CLOTHHIP_EINVAL, "NULL argument");
-    if (n_steps < 0) return fail(CLOTHHIP_EINVAL, "n_steps < 0");
-    if (int rc = check_fit(h, idx, B > 0 ? (int64_t)n_steps * B : 0, B)) return rc;
-    const bool adam = p->optimizer == (float)CLOTHHIP_FIT_ADAM;
-    if (!adam && p->optimizer != (float)CLOTHHIP_FIT_SGD) return fail(CLOTHHIP_EINVAL, "unknown optimizer %g (CLOTHHIP_FIT_ADAM or CLOTHHIP_FIT_SGD)", (double)p->optimizer);
-    if (!hyper_ok(p->lr) || !hyper_ok(p->eps) || !hyper_ok(p->momentum) || !hyper_ok(p->beta1) || !hyper_ok(p->beta2))
-        return fail(CLOTHHIP_EINVAL, "a hyper-parameter is negative or not finite (lr %g, beta1 %g, beta2 %g, eps %g, momentum %g)", (double)p->lr,
-                    (double)p->beta1, (double)p->beta2, (double)p->eps, (double)p->momentum);
-    if (p->beta1 >= 1.0f || p->beta2 >= 1.0f) return fail(CLOTHHIP_EINVAL, "beta1 %g, beta2 %g: both lie in [0, 1)", (double)p->beta1, (double)p->beta2);
-    if (n_steps == 0) return 0;
-    auto &f = h->fit;
-    const size_t n = h->pol.mlp_n_params;
-    HIPCHECK(hipSetDevice(h->device));
-    if (int rc = reserve_fit(h, B)) return rc;
-    if (int rc = f.d_idx.reserve((size_t)n_steps * B * 4)) return rc;
-    if (int rc = f.d_loss.reserve((size_t)n_steps * 8)) return rc;
-    if (int rc = f.d_m.reserve(n * 4)) return rc;
-    if (int rc = f.d_v.reserve(n * 4)) return rc;
-    // from here on the call goes through (but for a failure of the runtime itself)
-    if (f.opt_zero) {
-        HIPCHECK(hipMemsetAsync(f.d_m, 0, n * 4, h->stream));
-        HIPCHECK(hipMemsetAsync(f.d_v, 0, n * 4, h->stream));
-        f.opt_zero = false;
-    }
-    HIPCHECK(hipMemcpyAsync(f.d_idx, idx, (size_t)n_steps * B * 4, hipMemcpyHostToDevice, h->stream));
-    float *theta = h->pol.d_mlp;
-    const double b1 = (double)p->beta1, b2 = (double)p->beta2;
-    const unsigned blocks = (unsigned)((n + 255) / 256);
-    HIPCHECK(hipEventRecord(h->ev0, h->stream));
-    for (int s = 0; s < n_steps; s++) {
-        if (int rc = enqueue_grad(h, f.d_idx + (size_t)s * B, B, f.d_loss + s)) return rc;
-        const double t = (double)(++f.opt_t);
-        if (adam) {
-            const double a_t = (double)p->lr * std::sqrt(1.0 - std::pow(b2, t)) / (1.0 - std::pow(b1, t));
-            hipLaunchKernelGGL(k_fit_adam, dim3(blocks), dim3(256), 0, h->stream, theta, (float *)f.d_m, (float *)f.d_v, (const float *)f.d_grad, (int64_t)n,
-                               (float)a_t, p->beta1, (float)(1.0 - b1), p->beta2, (float)(1.0 - b2), p->eps);
-        } else {
-            hipLaunchKernelGGL(k_fit_sgd, dim3(blocks), dim3(256), 0, h->stream, theta, (float *)f.d_m, (const float *)f.d_grad, (int64_t)n, p->lr, p->momentum);
-        }
-        HIPCHECK(hipGetLastError());
-    }
-    HIPCHECK(hipEventRecord(h->ev1, h->stream));
-    h->have_timing = true;
-    if (loss_out) HIPCHECK(hipMemcpyAsync(loss_out, f.d_loss, (size_t)n_steps * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHECK(hipStreamSynchronize(h->stream));
-    return 0;
-}
-
-extern "C" int clothhip_policy_fit_reset(clothhip_handle *h) {
-    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
-    if (int rc = check_idle(h)) return rc;
-    h->fit_forget();
-    return 0;
-}
-
-// ---- the grouped trainer: rows of the population fitted in the launches of one network (clothhip.h: clothhip_policy_fit*_members) --------
+// ---- the trainer (cloth_policy_fit.hpp has the definition and the order) ----------------------------------------------------------------
+// ONE path: a call fits n_m rows of the handle's weight table in the launches of one network. The table is the population d_pop
+// [pop_rows][mlp.stride], or the shared network d_mlp as a table of one row: the shared entries are the call members = {0}, n_m = 1 (row
+// 0 lies at offset 0 whatever mlp.stride holds). The extern "C" entries below only refuse what each of them refuses and call it.
 static_assert(CLOTHHIP_FIT_MAX_MEMBER_ROWS == 65536, "the header's cap on n_m * B of one call");
 
-// What the entries refuse before anything is touched, in the style of check_fit: the member list of a call ...
+static const int32_t SHARED_ROW[1] = {0};      // the member list of the shared network
+static size_t fit_rows(const clothhip_handle *h) { return h->pol.pop_rows ? (size_t)h->pol.pop_rows : 1; }
+
+// What the entries refuse before anything is touched, each in the order it always had. The state; `population`: the entry trains rows of
+// a population (which puts these refusals first, whatever else is wrong with the call), else the shared network
+static int check_fit_state(const clothhip_handle *h, bool population) {
+    if (int rc = check_idle(h)) return rc;
+    if (population) {
+        if (h->pol.mlp.n_layers < 1) return fail(CLOTHHIP_ESTATE, "no network on this handle: call clothhip_set_policy_population first");
+        if (!h->pol.pop_rows) return fail(CLOTHHIP_ESTATE, "this handle holds ONE shared network, not a population: use clothhip_policy_fit");
+    } else {
+        if (h->pol.pop_rows) return fail(CLOTHHIP_ESTATE, "this handle holds a population of networks: the fit trains the ONE shared network of clothhip_set_policy_mlp");
+        if (h->pol.mlp.n_layers < 1) return fail(CLOTHHIP_ESTATE, "no network on this handle: call clothhip_set_policy_mlp first");
+    }
+    if (h->fit.n < 1) return fail(CLOTHHIP_ESTATE, "the dataset is empty: call clothhip_fit_data_append first");
+    return 0;
+}
+// the member list of a call ...
 static int check_fit_members(const clothhip_handle *h, const int32_t *members, int32_t n_m) {
     if (n_m < 1) return fail(CLOTHHIP_EINVAL, "n_m = %d: a call names at least one member", n_m);
     if (!members) return fail(CLOTHHIP_EINVAL, "members is NULL");
@@ -475,36 +250,40 @@ static int check_fit_members(const clothhip_handle *h, const int32_t *members, i
     }
     return 0;
 }
-// ... and its minibatches
-static int check_fit_members_rows(const clothhip_handle *h, int32_t n_m, const int32_t *idx, int64_t n_steps, int32_t B) {
+// ... its minibatches: n_idx entries of idx in all, B rows per member and step ...
+static int check_fit_rows(const clothhip_handle *h, int32_t n_m, const int32_t *idx, int64_t n_idx, int32_t B) {
     if (B < 1 || B > FIT_MAX_BATCH) return fail(CLOTHHIP_EINVAL, "B = %d outside [1, %d]", B, FIT_MAX_BATCH);
     if ((int64_t)n_m * B > CLOTHHIP_FIT_MAX_MEMBER_ROWS)
         return fail(CLOTHHIP_EINVAL, "n_m * B = %d * %d rows in one call, at most %d", n_m, B, CLOTHHIP_FIT_MAX_MEMBER_ROWS);
-    const int64_t n_idx = n_steps * n_m * B;
     if (!idx && n_idx > 0) return fail(CLOTHHIP_EINVAL, "idx is NULL");
     for (int64_t i = 0; i < n_idx; i++)
         if (idx[i] < 0 || idx[i] >= h->fit.n) return fail(CLOTHHIP_EINVAL, "idx[%lld] = %d outside [0, %lld)", (long long)i, idx[i], (long long)h->fit.n);
     return 0;
 }
-// the state refusals come first, whatever else is wrong with the call
-static int check_fit_members_state(const clothhip_handle *h) {
-    if (int rc = check_idle(h)) return rc;
-    if (h->pol.mlp.n_layers < 1) return fail(CLOTHHIP_ESTATE, "no network on this handle: call clothhip_set_policy_population first");
-    if (!h->pol.pop_rows) return fail(CLOTHHIP_ESTATE, "this handle holds ONE shared network, not a population: use clothhip_policy_fit");
-    if (h->fit.n < 1) return fail(CLOTHHIP_ESTATE, "the dataset is empty: call clothhip_fit_data_append first");
+// ... and the optimizer of member j (j < 0: the one of the shared network, named without an index)
+static bool hyper_ok(float v) { return std::isfinite(v) && v >= 0.0f; }
+static int check_fit_params(const ClothFitParams *p, int32_t j) {
+    char who[24] = "";
+    if (j >= 0) snprintf(who, sizeof(who), "p[%d]: ", j);
+    if (p->optimizer != (float)CLOTHHIP_FIT_ADAM && p->optimizer != (float)CLOTHHIP_FIT_SGD)
+        return fail(CLOTHHIP_EINVAL, "%sunknown optimizer %g (CLOTHHIP_FIT_ADAM or CLOTHHIP_FIT_SGD)", who, (double)p->optimizer);
+    if (!hyper_ok(p->lr) || !hyper_ok(p->eps) || !hyper_ok(p->momentum) || !hyper_ok(p->beta1) || !hyper_ok(p->beta2))
+        return fail(CLOTHHIP_EINVAL, "%sa hyper-parameter is negative or not finite (lr %g, beta1 %g, beta2 %g, eps %g, momentum %g)", who, (double)p->lr,
+                    (double)p->beta1, (double)p->beta2, (double)p->eps, (double)p->momentum);
+    if (p->beta1 >= 1.0f || p->beta2 >= 1.0f) return fail(CLOTHHIP_EINVAL, "%sbeta1 %g, beta2 %g: both lie in [0, 1)", who, (double)p->beta1, (double)p->beta2);
     return 0;
 }
 
 // Where member j's tables lie: the per-member sizes of the scratch tables (floats) for minibatches of B rows, and the offsets of every
 // layer inside a blob (weights, gradient) and inside a member's activations.
-struct MembersPlan {
+struct FitPlan {
     size_t act, dz, part, grad, maxw;       // per member: activations, the two dZ tables, the slabs (0 without a split), the gradient
     int n_split;
     size_t w_off[MLP_MAX_LAYERS], h_off[MLP_MAX_LAYERS];
 };
-static MembersPlan members_plan(const clothhip_handle *h, int32_t B) {
+static FitPlan fit_plan(const clothhip_handle *h, int32_t B) {
     const MlpDesc &D = h->pol.mlp;
-    MembersPlan p = {};
+    FitPlan p = {};
     size_t maxmat = 0;
     p.maxw = MLP_OUT;
     for (int l = 0; l < D.n_layers; l++) {
@@ -519,7 +298,8 @@ static MembersPlan members_plan(const clothhip_handle *h, int32_t B) {
     p.part = p.n_split > 1 ? (size_t)p.n_split * maxmat : 0;
     return p;
 }
-static int reserve_fit_members(clothhip_handle *h, const MembersPlan &p, int32_t n_m) {
+// one step's scratch for n_m members
+static int fit_reserve(clothhip_handle *h, const FitPlan &p, int32_t n_m) {
     auto &f = h->fit;
     if (int rc = f.d_members.reserve((size_t)n_m * 4)) return rc;
     if (int rc = f.d_act.reserve((size_t)n_m * p.act * 4)) return rc;
@@ -528,95 +308,88 @@ static int reserve_fit_members(clothhip_handle *h, const MembersPlan &p, int32_t
     return f.d_grad.reserve((size_t)n_m * p.grad * 4);
 }
 
-template <bool A_KC, bool B_KC, int EPI, bool ROWS> static void launch_gemm_members(hipStream_t s, FitGemmMembersArgs &m, int32_t n_m) {
-    const FitGemmArgs &a = m.g;
-    m.tiles_n = (a.N + FIT_TILE - 1) / FIT_TILE;
-    const dim3 grid((unsigned)m.tiles_n * (unsigned)n_m, (unsigned)((a.M + FIT_TILE - 1) / FIT_TILE), (unsigned)((a.K + a.k_chunk - 1) / a.k_chunk));
-    hipLaunchKernelGGL((k_fit_gemm_members<A_KC, B_KC, EPI, ROWS>), grid, dim3(FIT_THREADS), 0, s, m);
+template <bool A_KC, bool B_KC, int EPI, bool ROWS> static void launch_gemm(hipStream_t s, FitGemmArgs &a, int32_t n_m) {
+    a.tiles_n = (a.N + FIT_TILE - 1) / FIT_TILE;
+    const dim3 grid((unsigned)a.tiles_n * (unsigned)n_m, (unsigned)((a.M + FIT_TILE - 1) / FIT_TILE), (unsigned)((a.K + a.k_chunk - 1) / a.k_chunk));
+    hipLaunchKernelGGL((k_fit_gemm<A_KC, B_KC, EPI, ROWS>), grid, dim3(FIT_THREADS), 0, s, a);
 }
 
-// enqueue_grad for n_m members: every launch of one network's step, each over all members. d_idx [n_m][B], d_loss [n_m]; the gradients
-// land in h->fit.d_grad [n_m][n_params]
-static int enqueue_grad_members(clothhip_handle *h, const MembersPlan &p, int32_t n_m, const int32_t *d_idx, int32_t B, double *d_loss) {
+// Enqueue every launch of one network's step, each over all n_m members: loss and gradient of the present weights over rows d_idx
+// [n_m][B] into d_loss [n_m] and h->fit.d_grad [n_m][n_params] (blob layout). d_loss NULL: the forward pass alone -- member j's y is
+// then at h->fit.d_act + j * p.act + p.h_off[L - 1]
+static int enqueue_grad(clothhip_handle *h, const FitPlan &p, int32_t n_m, const int32_t *d_idx, int32_t B, double *d_loss) {
     const MlpDesc &D = h->pol.mlp;
     const int L = D.n_layers;
     auto &f = h->fit;
     float *act = f.d_act, *grad = f.d_grad, *dz[2] = {f.d_dz, f.d_dz + (size_t)B * p.maxw};
-    FitGemmMembersArgs m0 = {};
+    FitGemmArgs m0 = {};
     m0.members = f.d_members; m0.stride = D.stride; m0.rows_step = B;
     for (int l = 0; l < L; l++) {
         const int n_in = D.widths[l], n_out = D.widths[l + 1];
-        FitGemmMembersArgs m = m0;
-        FitGemmArgs &a = m.g;
-        a.A = l ? act + p.h_off[l - 1] : (const float *)f.d_obs; a.lda = n_in; a.rows = l ? nullptr : d_idx; m.a_step = l ? (int64_t)p.act : 0;
-        a.B = D.params + p.w_off[l]; a.ldb = n_in; a.bias = a.B + (size_t)n_out * n_in; m.b_weights = 1;
-        a.C = act + p.h_off[l]; a.ldc = n_out; m.c_step = (int64_t)p.act;
+        FitGemmArgs a = m0;
+        a.A = l ? act + p.h_off[l - 1] : (const float *)f.d_obs; a.lda = n_in; a.rows = l ? nullptr : d_idx; a.a_step = l ? (int64_t)p.act : 0;
+        a.B = D.params + p.w_off[l]; a.ldb = n_in; a.bias = a.B + (size_t)n_out * n_in; a.b_weights = 1;
+        a.C = act + p.h_off[l]; a.ldc = n_out; a.c_step = (int64_t)p.act;
         a.M = B; a.N = n_out; a.K = n_in; a.k_chunk = n_in;
-        if (l == 0 && l + 1 < L) launch_gemm_members<true, true, FIT_EPI_BIAS_RELU, true>(h->stream, m, n_m);
-        else if (l == 0) launch_gemm_members<true, true, FIT_EPI_BIAS, true>(h->stream, m, n_m);
-        else if (l + 1 < L) launch_gemm_members<true, true, FIT_EPI_BIAS_RELU, false>(h->stream, m, n_m);
-        else launch_gemm_members<true, true, FIT_EPI_BIAS, false>(h->stream, m, n_m);
+        if (l == 0 && l + 1 < L) launch_gemm<true, true, FIT_EPI_BIAS_RELU, true>(h->stream, a, n_m);
+        else if (l == 0) launch_gemm<true, true, FIT_EPI_BIAS, true>(h->stream, a, n_m);
+        else if (l + 1 < L) launch_gemm<true, true, FIT_EPI_BIAS_RELU, false>(h->stream, a, n_m);
+        else launch_gemm<true, true, FIT_EPI_BIAS, false>(h->stream, a, n_m);
         HIPCHECK(hipGetLastError());
     }
-    hipLaunchKernelGGL(k_fit_loss_members, dim3((unsigned)n_m), dim3(256), 0, h->stream, (const float *)(act + p.h_off[L - 1]), (const float *)f.d_lab, d_idx, B,
+    if (!d_loss) return 0;
+    hipLaunchKernelGGL(k_fit_loss, dim3((unsigned)n_m), dim3(256), 0, h->stream, (const float *)(act + p.h_off[L - 1]), (const float *)f.d_lab, d_idx, B,
                        dz[(L - 1) & 1], d_loss, (int64_t)p.act, (int64_t)p.dz, (int64_t)B);
     HIPCHECK(hipGetLastError());
     for (int l = L - 1; l >= 0; l--) {
         const int n_in = D.widths[l], n_out = D.widths[l + 1];
         const float *dzl = dz[l & 1];
         float *gWl = grad + p.w_off[l];
-        FitGemmMembersArgs m = m0;
-        FitGemmArgs &a = m.g;
-        a.A = dzl; a.lda = n_out; m.a_step = (int64_t)p.dz;
-        a.B = l ? act + p.h_off[l - 1] : (const float *)f.d_obs; a.ldb = n_in; a.rows = l ? nullptr : d_idx; m.b_step = l ? (int64_t)p.act : 0;
-        a.C = p.n_split > 1 ? (float *)f.d_part : gWl; a.ldc = n_in; a.c_slab = (int64_t)n_out * n_in; m.c_step = (int64_t)(p.n_split > 1 ? p.part : p.grad);
+        FitGemmArgs a = m0;
+        a.A = dzl; a.lda = n_out; a.a_step = (int64_t)p.dz;
+        a.B = l ? act + p.h_off[l - 1] : (const float *)f.d_obs; a.ldb = n_in; a.rows = l ? nullptr : d_idx; a.b_step = l ? (int64_t)p.act : 0;
+        a.C = p.n_split > 1 ? (float *)f.d_part : gWl; a.ldc = n_in; a.c_slab = (int64_t)n_out * n_in; a.c_step = (int64_t)(p.n_split > 1 ? p.part : p.grad);
         a.M = n_out; a.N = n_in; a.K = B; a.k_chunk = FIT_SPLIT_ROWS;
-        if (l == 0) launch_gemm_members<false, false, FIT_EPI_NONE, true>(h->stream, m, n_m);
-        else launch_gemm_members<false, false, FIT_EPI_NONE, false>(h->stream, m, n_m);
+        if (l == 0) launch_gemm<false, false, FIT_EPI_NONE, true>(h->stream, a, n_m);
+        else launch_gemm<false, false, FIT_EPI_NONE, false>(h->stream, a, n_m);
         HIPCHECK(hipGetLastError());
         if (p.n_split > 1) {
             const int64_t n = (int64_t)n_out * n_in;
             const int32_t blocks = (int32_t)((n + 255) / 256);
-            hipLaunchKernelGGL(k_fit_reduce_members, dim3((unsigned)blocks * (unsigned)n_m), dim3(256), 0, h->stream, (const float *)f.d_part, n, p.n_split, gWl, n,
+            hipLaunchKernelGGL(k_fit_reduce, dim3((unsigned)blocks * (unsigned)n_m), dim3(256), 0, h->stream, (const float *)f.d_part, n, p.n_split, gWl, n,
                                (int64_t)p.part, (int64_t)p.grad, blocks);
             HIPCHECK(hipGetLastError());
         }
         const int32_t cblocks = (n_out + 63) / 64;
-        hipLaunchKernelGGL(k_fit_colsum_members, dim3((unsigned)cblocks * (unsigned)n_m), dim3(64), 0, h->stream, dzl, B, n_out, gWl + (size_t)n_out * n_in,
+        hipLaunchKernelGGL(k_fit_colsum, dim3((unsigned)cblocks * (unsigned)n_m), dim3(64), 0, h->stream, dzl, B, n_out, gWl + (size_t)n_out * n_in,
                            (int64_t)p.dz, (int64_t)p.grad, cblocks);
         HIPCHECK(hipGetLastError());
         if (l > 0) {
-            FitGemmMembersArgs mb = m0;
-            FitGemmArgs &b = mb.g;
-            b.A = dzl; b.lda = n_out; mb.a_step = (int64_t)p.dz;
-            b.B = D.params + p.w_off[l]; b.ldb = n_in; mb.b_weights = 1;
-            b.mask = act + p.h_off[l - 1]; mb.mask_step = (int64_t)p.act;
-            b.C = dz[(l - 1) & 1]; b.ldc = n_in; mb.c_step = (int64_t)p.dz;
+            FitGemmArgs b = m0;
+            b.A = dzl; b.lda = n_out; b.a_step = (int64_t)p.dz;
+            b.B = D.params + p.w_off[l]; b.ldb = n_in; b.b_weights = 1;
+            b.mask = act + p.h_off[l - 1]; b.mask_step = (int64_t)p.act;
+            b.C = dz[(l - 1) & 1]; b.ldc = n_in; b.c_step = (int64_t)p.dz;
             b.M = B; b.N = n_in; b.K = n_out; b.k_chunk = n_out;
-            launch_gemm_members<true, false, FIT_EPI_MASK, false>(h->stream, mb, n_m);
+            launch_gemm<true, false, FIT_EPI_MASK, false>(h->stream, b, n_m);
             HIPCHECK(hipGetLastError());
         }
     }
     return 0;
 }
 
-extern "C" int clothhip_policy_fit_grad_members(clothhip_handle *h, const int32_t *members, int32_t n_m, const int32_t *idx, int32_t B, float *grad_out,
-                                                double *loss_out) {
-    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
-    if (int rc = check_fit_members_state(h)) return rc;
-    if (int rc = check_fit_members(h, members, n_m)) return rc;
-    if (int rc = check_fit_members_rows(h, n_m, idx, 1, B)) return rc;
-    if (!idx) return fail(CLOTHHIP_EINVAL, "idx is NULL");
+// loss and gradient of `members` over idx [n_m][B], nothing updated; the call is valid
+static int run_grad(clothhip_handle *h, const int32_t *members, int32_t n_m, const int32_t *idx, int32_t B, float *grad_out, double *loss_out) {
     auto &f = h->fit;
-    const MembersPlan p = members_plan(h, B);
+    const FitPlan p = fit_plan(h, B);
     HIPCHECK(hipSetDevice(h->device));
-    if (int rc = reserve_fit_members(h, p, n_m)) return rc;
+    if (int rc = fit_reserve(h, p, n_m)) return rc;
     if (int rc = f.d_idx.reserve((size_t)n_m * B * 4)) return rc;
     if (int rc = f.d_loss.reserve((size_t)n_m * 8)) return rc;
     HIPCHECK(hipMemcpyAsync(f.d_members, members, (size_t)n_m * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipMemcpyAsync(f.d_idx, idx, (size_t)n_m * B * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipEventRecord(h->ev0, h->stream));
-    if (int rc = enqueue_grad_members(h, p, n_m, f.d_idx, B, f.d_loss)) return rc;
+    if (int rc = enqueue_grad(h, p, n_m, f.d_idx, B, f.d_loss)) return rc;
     HIPCHECK(hipEventRecord(h->ev1, h->stream));
     h->have_timing = true;
     if (grad_out) HIPCHECK(hipMemcpyAsync(grad_out, f.d_grad, (size_t)n_m * p.grad * 4, hipMemcpyDeviceToHost, h->stream));
@@ -625,21 +398,67 @@ extern "C" int clothhip_policy_fit_grad_members(clothhip_handle *h, const int32_
     return 0;
 }
 
-// clothhip_policy_fit's refusals of an optimizer, for member j of a grouped call
-static int check_fit_params(const ClothFitParams *p, int32_t j) {
-    if (p->optimizer != (float)CLOTHHIP_FIT_ADAM && p->optimizer != (float)CLOTHHIP_FIT_SGD)
-        return fail(CLOTHHIP_EINVAL, "p[%d]: unknown optimizer %g (CLOTHHIP_FIT_ADAM or CLOTHHIP_FIT_SGD)", j, (double)p->optimizer);
-    if (!hyper_ok(p->lr) || !hyper_ok(p->eps) || !hyper_ok(p->momentum) || !hyper_ok(p->beta1) || !hyper_ok(p->beta2))
-        return fail(CLOTHHIP_EINVAL, "p[%d]: a hyper-parameter is negative or not finite (lr %g, beta1 %g, beta2 %g, eps %g, momentum %g)", j, (double)p->lr,
-                    (double)p->beta1, (double)p->beta2, (double)p->eps, (double)p->momentum);
-    if (p->beta1 >= 1.0f || p->beta2 >= 1.0f) return fail(CLOTHHIP_EINVAL, "p[%d]: beta1 %g, beta2 %g: both lie in [0, 1)", j, (double)p->beta1, (double)p->beta2);
+extern "C" int clothhip_policy_fit_grad(clothhip_handle *h, const int32_t *idx, int32_t B, float *grad_out, double *loss_out) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (int rc = check_fit_state(h, false)) return rc;
+    if (int rc = check_fit_rows(h, 1, idx, B, B)) return rc;
+    return run_grad(h, SHARED_ROW, 1, idx, B, grad_out, loss_out);
+}
+
+extern "C" int clothhip_policy_fit_grad_members(clothhip_handle *h, const int32_t *members, int32_t n_m, const int32_t *idx, int32_t B, float *grad_out,
+                                                double *loss_out) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (int rc = check_fit_state(h, true)) return rc;
+    if (int rc = check_fit_members(h, members, n_m)) return rc;
+    if (int rc = check_fit_rows(h, n_m, idx, (int64_t)n_m * B, B)) return rc;
+    return run_grad(h, members, n_m, idx, B, grad_out, loss_out);
+}
+
+// The loss alone of the shared network over any number of rows: chunks of at most FIT_MAX_BATCH through the forward pass above, each
+// chunk's sum of squares in k_fit_loss's order (k_fit_sqsum), the chunk sums added in ascending order in double on the host, divided
+// once by 4 n.
+extern "C" int clothhip_policy_fit_loss(clothhip_handle *h, const int32_t *idx, int64_t n, double *loss) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (n < 1 || n > INT32_MAX) return fail(CLOTHHIP_EINVAL, "n = %lld outside [1, %d]", (long long)n, INT32_MAX);
+    const int32_t Bmax = (int32_t)std::min<int64_t>(n, FIT_MAX_BATCH);
+    if (int rc = check_fit_state(h, false)) return rc;
+    if (int rc = check_fit_rows(h, 1, idx, n, Bmax)) return rc;
+    if (!loss) return fail(CLOTHHIP_EINVAL, "NULL argument");
+    auto &f = h->fit;
+    const int L = h->pol.mlp.n_layers;
+    const int64_t n_chunks = (n + FIT_MAX_BATCH - 1) / FIT_MAX_BATCH;
+    std::vector<double> sums;
+    try { sums.resize((size_t)n_chunks); } catch (const std::bad_alloc &) { return fail(CLOTHHIP_ENOMEM, "out of host memory (%lld chunks)", (long long)n_chunks); }
+    HIPCHECK(hipSetDevice(h->device));
+    if (int rc = fit_reserve(h, fit_plan(h, Bmax), 1)) return rc;
+    if (int rc = f.d_idx.reserve((size_t)n * 4)) return rc;
+    if (int rc = f.d_loss.reserve((size_t)n_chunks * 8)) return rc;
+    HIPCHECK(hipMemcpyAsync(f.d_members, SHARED_ROW, 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipMemcpyAsync(f.d_idx, idx, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipEventRecord(h->ev0, h->stream));
+    for (int64_t c = 0; c < n_chunks; c++) {
+        const int32_t B = (int32_t)std::min<int64_t>(FIT_MAX_BATCH, n - c * FIT_MAX_BATCH);
+        const FitPlan p = fit_plan(h, B);
+        const int32_t *d_idx = f.d_idx + (size_t)c * FIT_MAX_BATCH;
+        if (int rc = enqueue_grad(h, p, 1, d_idx, B, nullptr)) return rc;
+        hipLaunchKernelGGL(k_fit_sqsum, dim3(1), dim3(256), 0, h->stream, (const float *)(f.d_act + p.h_off[L - 1]), (const float *)f.d_lab, d_idx, B, f.d_loss + c);
+        HIPCHECK(hipGetLastError());
+    }
+    HIPCHECK(hipEventRecord(h->ev1, h->stream));
+    h->have_timing = true;
+    HIPCHECK(hipMemcpyAsync(sums.data(), f.d_loss, (size_t)n_chunks * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    double s = sums[0];
+    for (int64_t c = 1; c < n_chunks; c++) s = s + sums[c];
+    *loss = s / (double)(4 * n);
     return 0;
 }
 
-// the per-row optimizer state exists from the first grouped call after a new network: every row fresh
+// ---- the optimizer ----------------------------------------------------------------------------------------------------------------------
+// the per-row optimizer state exists from the first step after a new network: every row fresh
 static int ensure_row_state(clothhip_handle *h) {
     auto &f = h->fit;
-    const size_t rows = (size_t)h->pol.pop_rows;
+    const size_t rows = fit_rows(h);
     if (f.row_t.size() == rows && f.row_zero.size() == rows) return 0;
     try { f.row_t.assign(rows, 0); f.row_zero.assign(rows, 1); } catch (const std::bad_alloc &) {
         f.row_t.clear(); f.row_zero.clear();
@@ -648,25 +467,16 @@ static int ensure_row_state(clothhip_handle *h) {
     return 0;
 }
 
-extern "C" int clothhip_policy_fit_members(clothhip_handle *h, const ClothFitParams *p, const int32_t *members, int32_t n_m, const int32_t *idx,
-                                           int32_t n_steps, int32_t B, double *loss_out) {
-    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
-    if (int rc = check_fit_members_state(h)) return rc;
-    if (!p) return fail(CLOTHHIP_EINVAL, "NULL argument");
-    if (n_steps < 0) return fail(CLOTHHIP_EINVAL, "n_steps < 0");
-    if (int rc = check_fit_members(h, members, n_m)) return rc;
-    if (int rc = check_fit_members_rows(h, n_m, idx, n_steps, B)) return rc;
-    for (int32_t j = 0; j < n_m; j++) {
-        if (int rc = check_fit_params(p + j, j)) return rc;
-        if (p[j].optimizer != p[0].optimizer) return fail(CLOTHHIP_EINVAL, "p[%d].optimizer = %g, p[0].optimizer = %g: one optimizer per call", j, (double)p[j].optimizer, (double)p[0].optimizer);
-    }
-    if (n_steps == 0) return 0;
+// n_steps optimizer steps of `members` with the optimizers p [n_m] over idx [n_steps][n_m][B]; the call is valid and n_steps >= 1
+static int run_fit(clothhip_handle *h, const ClothFitParams *p, const int32_t *members, int32_t n_m, const int32_t *idx, int32_t n_steps, int32_t B,
+                   double *loss_out) {
     const bool adam = p[0].optimizer == (float)CLOTHHIP_FIT_ADAM;
     auto &f = h->fit;
     const MlpDesc &D = h->pol.mlp;
-    const MembersPlan pl = members_plan(h, B);
-    const size_t n = h->pol.mlp_n_params, stride = (size_t)D.stride, rows = (size_t)h->pol.pop_rows, n_sm = (size_t)n_steps * n_m;
-    // the step constants of every (step, member), in double on the host as clothhip_policy_fit makes them; nothing of the handle changes yet
+    const FitPlan pl = fit_plan(h, B);
+    const size_t n = h->pol.mlp_n_params, stride = (size_t)D.stride, n_sm = (size_t)n_steps * n_m;
+    const size_t n_moments = h->pol.pop_rows ? (size_t)h->pol.pop_rows * stride : n;
+    // the step constants of every (step, member), in double on the host, then rounded to float; nothing of the handle changes yet
     std::vector<float> hyper;
     try { hyper.assign(n_sm * FIT_HYPER, 0.0f); } catch (const std::bad_alloc &) { return fail(CLOTHHIP_ENOMEM, "out of host memory (%zu step constants)", n_sm * FIT_HYPER); }
     if (int rc = ensure_row_state(h)) return rc;
@@ -683,14 +493,14 @@ extern "C" int clothhip_policy_fit_members(clothhip_handle *h, const ClothFitPar
             }
         }
     HIPCHECK(hipSetDevice(h->device));
-    if (int rc = reserve_fit_members(h, pl, n_m)) return rc;
+    if (int rc = fit_reserve(h, pl, n_m)) return rc;
     if (int rc = f.d_idx.reserve(n_sm * B * 4)) return rc;
     if (int rc = f.d_loss.reserve(n_sm * 8)) return rc;
     if (int rc = f.d_hyper.reserve(n_sm * FIT_HYPER * 4)) return rc;
-    // the moments of the whole population, [pop_rows][stride]: a table of the shared trainer's size (or none) holds no row's state, so
-    // growing it loses nothing -- every row is still flagged read-as-zeros then
-    if (int rc = f.d_m.reserve(rows * stride * 4)) return rc;
-    if (int rc = f.d_v.reserve(rows * stride * 4)) return rc;
+    // the moments of the whole table. A table of another network's size holds no row's state (every row is flagged read-as-zeros by
+    // fit_forget when the network changes), so growing it loses nothing
+    if (int rc = f.d_m.reserve(n_moments * 4)) return rc;
+    if (int rc = f.d_v.reserve(n_moments * 4)) return rc;
     // from here on the call goes through (but for a failure of the runtime itself)
     for (int32_t j = 0; j < n_m; j++) {
         const int32_t g = members[j];
@@ -704,22 +514,56 @@ extern "C" int clothhip_policy_fit_members(clothhip_handle *h, const ClothFitPar
     HIPCHECK(hipMemcpyAsync(f.d_members, members, (size_t)n_m * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipMemcpyAsync(f.d_idx, idx, n_sm * B * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipMemcpyAsync(f.d_hyper, hyper.data(), n_sm * FIT_HYPER * 4, hipMemcpyHostToDevice, h->stream));
-    FitOptMembersArgs o = {};
-    o.theta = h->pol.d_pop; o.m = f.d_m; o.v = f.d_v; o.g = f.d_grad; o.members = f.d_members; o.stride = (int64_t)stride; o.n = (int64_t)n;
-    o.blocks = (int32_t)((n + 255) / 256);
+    FitOptArgs o = {};
+    o.theta = h->pol.pop_rows ? h->pol.d_pop : h->pol.d_mlp; o.m = f.d_m; o.v = f.d_v; o.g = f.d_grad; o.members = f.d_members;
+    o.stride = (int64_t)stride; o.n = (int64_t)n; o.blocks = (int32_t)((n + 255) / 256);
     const dim3 ogrid((unsigned)o.blocks * (unsigned)n_m);
     HIPCHECK(hipEventRecord(h->ev0, h->stream));
     for (int s = 0; s < n_steps; s++) {
-        if (int rc = enqueue_grad_members(h, pl, n_m, f.d_idx + (size_t)s * n_m * B, B, f.d_loss + (size_t)s * n_m)) return rc;
+        if (int rc = enqueue_grad(h, pl, n_m, f.d_idx + (size_t)s * n_m * B, B, f.d_loss + (size_t)s * n_m)) return rc;
         o.hyper = f.d_hyper + (size_t)s * n_m * FIT_HYPER;
-        if (adam) hipLaunchKernelGGL(k_fit_adam_members, ogrid, dim3(256), 0, h->stream, o);
-        else hipLaunchKernelGGL(k_fit_sgd_members, ogrid, dim3(256), 0, h->stream, o);
+        if (adam) hipLaunchKernelGGL(k_fit_adam, ogrid, dim3(256), 0, h->stream, o);
+        else hipLaunchKernelGGL(k_fit_sgd, ogrid, dim3(256), 0, h->stream, o);
         HIPCHECK(hipGetLastError());
     }
     HIPCHECK(hipEventRecord(h->ev1, h->stream));
     h->have_timing = true;
     if (loss_out) HIPCHECK(hipMemcpyAsync(loss_out, f.d_loss, n_sm * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(hipStreamSynchronize(h->stream));      // (the host tables are never retained)
+    return 0;
+}
+
+extern "C" int clothhip_policy_fit(clothhip_handle *h, const ClothFitParams *p, const int32_t *idx, int32_t n_steps, int32_t B, double *loss_out) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (!p) return fail(CLOTHHIP_EINVAL, "NULL argument");
+    if (n_steps < 0) return fail(CLOTHHIP_EINVAL, "n_steps < 0");
+    if (int rc = check_fit_state(h, false)) return rc;
+    if (int rc = check_fit_rows(h, 1, idx, (int64_t)n_steps * B, B)) return rc;
+    if (int rc = check_fit_params(p, -1)) return rc;
+    if (n_steps == 0) return 0;
+    return run_fit(h, p, SHARED_ROW, 1, idx, n_steps, B, loss_out);
+}
+
+extern "C" int clothhip_policy_fit_members(clothhip_handle *h, const ClothFitParams *p, const int32_t *members, int32_t n_m, const int32_t *idx,
+                                           int32_t n_steps, int32_t B, double *loss_out) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (int rc = check_fit_state(h, true)) return rc;
+    if (!p) return fail(CLOTHHIP_EINVAL, "NULL argument");
+    if (n_steps < 0) return fail(CLOTHHIP_EINVAL, "n_steps < 0");
+    if (int rc = check_fit_members(h, members, n_m)) return rc;
+    if (int rc = check_fit_rows(h, n_m, idx, (int64_t)n_steps * n_m * B, B)) return rc;
+    for (int32_t j = 0; j < n_m; j++) {
+        if (int rc = check_fit_params(p + j, j)) return rc;
+        if (p[j].optimizer != p[0].optimizer) return fail(CLOTHHIP_EINVAL, "p[%d].optimizer = %g, p[0].optimizer = %g: one optimizer per call", j, (double)p[j].optimizer, (double)p[0].optimizer);
+    }
+    if (n_steps == 0) return 0;
+    return run_fit(h, p, members, n_m, idx, n_steps, B, loss_out);
+}
+
+extern "C" int clothhip_policy_fit_reset(clothhip_handle *h) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (int rc = check_idle(h)) return rc;
+    h->fit_forget();
     return 0;
 }
 

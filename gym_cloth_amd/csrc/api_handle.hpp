@@ -112,8 +112,8 @@ struct clothhip_handle : HostPlan {
         float pop_sigma = 0.0f;
         int32_t pop_flags = 0;
     } pol;
-    // The supervised trainer of the shared network (api_fit.hip: clothhip_fit_data_*, clothhip_policy_fit*); a new network
-    // (api_policy.hip's drop_network) restarts the optimizer through fit_forget below, nothing else outside api_fit.hip touches it.
+    // The supervised trainer of the handle's networks (api_fit.hip: clothhip_fit_data_*, clothhip_policy_fit*); a new network of either
+    // kind (api_policy.hip's drop_network) restarts the optimizer through fit_forget below, nothing else outside api_fit.hip touches it.
     struct Fit {
         // the dataset: n rows of cap allocated, d_obs [cap][3P] and d_lab [cap][4] float32 (grown geometrically, contents kept)
         Buffer<float> d_obs, d_lab;
@@ -123,23 +123,21 @@ struct clothhip_handle : HostPlan {
         Buffer<float> d_held;
         bool held_valid = false;
         Buffer<int32_t> d_rows, d_flag;
-        // the optimizer: moments d_m, d_v [n_params] (SGD's u is d_m) and the 1-based count of steps taken. opt_zero: the moments are to
-        // be read as zeros (the next step clears them first) -- what a reset is, so that a reset needs no device work
+        // the optimizer, per row of the weight table (max(pop_rows, 1) rows: a shared network counts as ONE row here too): moments d_m,
+        // d_v [pop_rows][stride], [n_params] for a shared network (SGD's u is d_m), the count of steps taken and the read-as-zeros flag
+        // (the row's next step clears its moments first -- what a reset is, so that a reset needs no device work). Both vectors are empty
+        // until the first step after a new network: all rows fresh
         Buffer<float> d_m, d_v;
-        int64_t opt_t = 0;
-        bool opt_zero = true;
-        // the grouped trainer of a population (clothhip_policy_fit*_members): d_m, d_v are then [pop_rows][stride], and every row has its
-        // own step count and its own read-as-zeros flag (both empty until the first grouped call after a new network: all rows fresh)
         std::vector<int64_t> row_t;
         std::vector<uint8_t> row_zero;
-        // one step's scratch, sized on demand: the index table of a call, the hidden activations and y, the two dZ tables, the split batch
-        // sums of a weight gradient, the gradient (blob layout), the losses of a call; the grouped trainer holds one of each per member
-        // of the call, with the call's member rows and its table of per-member, per-step optimizer constants
+        // one step's scratch, sized on demand, one of each per member of the call: the index table, the hidden activations and y, the
+        // two dZ tables, the split batch sums of a weight gradient, the gradient (blob layout), the losses; the call's member rows and
+        // its table of per-member, per-step optimizer constants
         Buffer<int32_t> d_idx, d_members;
         Buffer<float> d_act, d_dz, d_part, d_grad, d_hyper;
         Buffer<double> d_loss;
     } fit;
-    void fit_forget() { fit.opt_t = 0; fit.opt_zero = true; fit.row_t.clear(); fit.row_zero.clear(); }
+    void fit_forget() { fit.row_t.clear(); fit.row_zero.clear(); }
     // The cross-entropy planner (api_plan.hip: clothhip_plan_cem on the SCRATCH handle, clothhip_plan_sample / _refit on the handle given), all
     // sized on demand: the distribution d_mean, d_std [E][H][4], the best so far d_best_a [E][H][4], d_best_s [E], the source's done flags, the
     // action tables d_x [H][E K][4] (one, or one per iteration when the caller wants them back), d_scores [n_iters][E][K], the elite flags and

@@ -1,18 +1,25 @@
-// cloth_policy_fit.hpp -- the supervised trainer of the handle's shared policy network (cloth_policy_mlp.hpp: the blob it updates in place):
+// cloth_policy_fit.hpp -- the supervised trainer of the handle's policy networks (cloth_policy_mlp.hpp: the blobs it updates in place):
 // forward, backward and one optimizer step over a minibatch of stored (observation row, action label) pairs (no reference counterpart: the
-// refit half of a DAgger / behaviour-cloning iteration), and its grouped form that fits rows of a population in the launches of one network
-// (the k_fit_*_members kernels below). Included only by api_fit.hip, which owns the order of the launches.
+// refit half of a DAgger / behaviour-cloning iteration). ONE trainer: a call fits n_m rows of a weight table in the launches of one
+// network, every row on its own minibatches; the handle's shared network is the table of one row, fitted by the call members = {0},
+// n_m = 1. Included only by api_fit.hip, which owns the order of the launches.
 //
 //   L = 1 / (4 B) sum_r sum_k (y_rk - a_rk)^2,  dL/dy = (y - a) / (2 B);  ReLU' = 1 where the pre-activation is > 0, else 0 (the mask is read
 //   from the stored activation: relu(z) > 0 exactly when z > 0).
 //
-// ONE tiled matrix product, fit_gemm, does the three products of every layer on the f32-input matrix instruction
+// ONE tiled matrix product, k_fit_gemm, does the three products of every layer on the f32-input matrix instruction
 // v_mfma_f32_32x32x2_f32 (exact float32: per output element a k-ascending fmaf chain, one rounding per product -- the fit minimises the loss
 // of the very float32 function the launch evaluates):
 //   forward          H_l   = act(H_l-1 W_l^T + b_l)      A = H_l-1 [B][in]  k-contiguous, B = W_l [out][in] k-contiguous   (NT), bias (+ ReLU)
 //   weight gradient  dW_l  = dZ_l^T H_l-1                A = dZ_l  [B][out] m-contiguous, B = H_l-1 [B][in] n-contiguous   (TN), none
 //   input gradient   dZ_l-1 = (dZ_l W_l) * [H_l-1 > 0]   A = dZ_l  [B][out] k-contiguous, B = W_l [out][in] n-contiguous   (NN), mask
 //   Layer 0's H_-1 is the dataset read through the minibatch's index table (`rows`): no gathered copy.
+//
+// THE MEMBER INDEX. Every kernel carries the member j of the call folded into gridDim.x (a call may name up to 65 536 members, more than
+// gridDim.y / z hold): blockIdx.x = j * (blocks of one member) + the block's own x index. Member j's weights and moments lie at
+// members[j] * stride of a [rows][stride] table (members: a device table), its scratch tables (activations, dZ, slabs, gradient, index
+// rows, loss) at j times the table's per-member size. No element's arithmetic depends on j, n_m or the row, so member j's bits are those
+// of that network fitted alone on a handle of its own.
 //
 // THE ORDER OF THE ARITHMETIC (fixed; no floating-point atomics anywhere)
 //   * an output element is ONE accumulator: products added for k ascending from 0 within its k range, out-of-range elements of a tile are
@@ -21,7 +28,7 @@
 //     written to its own slab; k_fit_reduce adds the slabs in ascending range order. B <= FIT_SPLIT_ROWS: one range, written directly;
 //   * db_l[j] = sum_r dZ_l[r][j], r ascending, one thread per j (k_fit_colsum);
 //   * dZ_L-1 = fl(fl(y - a) / fl(2 B)); the loss sums (double)(y - a)^2 in double: thread t of 256 takes elements t, t + 256, ... ascending,
-//     the 256 sums are added by a halving tree in LDS (k_fit_loss, one workgroup);
+//     the 256 sums are added by a halving tree in LDS (k_fit_loss, one workgroup per member);
 //   * the optimizer (k_fit_adam / k_fit_sgd) is elementwise, each operation one float32 rounding (the library is built with
 //     -ffp-contract=off; division and sqrtf are the correctly rounded ones, no fast-math flag reaches this unit).
 //   The forward's summation order differs from mlp_eval's (64 interleaved lane sums and a butterfly there), so the trainer's y need not equal
@@ -40,7 +47,8 @@ constexpr int FIT_LDS_LD = FIT_TILE + 1;  // LDS images are [k][m] / [k][n], row
 
 enum { FIT_EPI_NONE = 0, FIT_EPI_BIAS = 1, FIT_EPI_BIAS_RELU = 2, FIT_EPI_MASK = 3 };
 
-// C[M][N] (+ z * c_slab) = sum_{k in the z-th range of k_chunk} A(m, k) B(k, n)
+// Member j: C[M][N] (+ z * c_slab) = sum_{k in the z-th range of k_chunk} A(m, k) B(k, n). The pointers are member 0's scratch tables;
+// B (when b_weights) and bias are relative to row 0 of the weight table.
 struct FitGemmArgs {
     const float *A, *B;         // A_KC: A(m, k) = A[row(m) * lda + k], else A[k * lda + m];  B_KC: B(k, n) = B[n * ldb + k], else B[row(k) * ldb + n]
     const int32_t *rows;        // optional indirection of the storage row of the operand that is the dataset (A when A_KC, B when !B_KC)
@@ -49,89 +57,18 @@ struct FitGemmArgs {
     float *C;
     int64_t lda, ldb, ldc, c_slab;
     int32_t M, N, K, k_chunk;
-};
-
-typedef float fit_f32x16 __attribute__((ext_vector_type(16)));
-
-template <bool A_KC, bool B_KC, int EPI, bool ROWS> __global__ __launch_bounds__(FIT_THREADS) void k_fit_gemm(FitGemmArgs a) {
-    __shared__ float As[FIT_BK][FIT_LDS_LD], Bs[FIT_BK][FIT_LDS_LD];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int m0 = blockIdx.y * FIT_TILE, n0 = blockIdx.x * FIT_TILE;
-    const int k_begin = blockIdx.z * a.k_chunk, k_end = min(a.K, k_begin + a.k_chunk);
-    const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;      // this wave's 32 x 32 corner of the tile
-    fit_f32x16 acc;
-    for (int i = 0; i < 16; i++) acc[i] = 0.0f;
-    // staging: 64 x 16 of each operand, zeros outside the matrices, 4 elements per thread and operand with the contiguous index on the
-    // lanes. The next tile's elements are loaded into registers while this tile's products run (the arithmetic and its order are untouched).
-    int ar[4], ak[4], br[4], bk[4];      // r: the m (or n) index in the tile, k: the k index
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        if (A_KC) { ak[i] = tid & 15; ar[i] = (tid >> 4) + 16 * i; } else { ar[i] = tid & 63; ak[i] = (tid >> 6) + 4 * i; }
-        if (B_KC) { bk[i] = tid & 15; br[i] = (tid >> 4) + 16 * i; } else { br[i] = tid & 63; bk[i] = (tid >> 6) + 4 * i; }
-    }
-    float va[4], vb[4];
-    auto fetch = [&](int k0) {
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const int m = m0 + ar[i], k = k0 + ak[i];
-            va[i] = 0.0f;
-            if (m < a.M && k < k_end) va[i] = A_KC ? a.A[(size_t)(ROWS ? a.rows[m] : m) * a.lda + k] : a.A[(size_t)k * a.lda + m];
-            const int n = n0 + br[i], kb = k0 + bk[i];
-            vb[i] = 0.0f;
-            if (n < a.N && kb < k_end) vb[i] = B_KC ? a.B[(size_t)n * a.ldb + kb] : a.B[(size_t)(ROWS ? a.rows[kb] : kb) * a.ldb + n];
-        }
-    };
-    fetch(k_begin);
-    for (int k0 = k_begin; k0 < k_end; k0 += FIT_BK) {
-#pragma unroll
-        for (int i = 0; i < 4; i++) { As[ak[i]][ar[i]] = va[i]; Bs[bk[i]][br[i]] = vb[i]; }
-        __syncthreads();
-        if (k0 + FIT_BK < k_end) fetch(k0 + FIT_BK);
-        // lane l holds A[i = l & 31][k = l >> 5] and B[k = l >> 5][j = l & 31] of each 32 x 32 x 2 step
-#pragma unroll
-        for (int ks = 0; ks < FIT_BK; ks += 2) {
-            const float av = As[ks + (lane >> 5)][wm + (lane & 31)], bv = Bs[ks + (lane >> 5)][wn + (lane & 31)];
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc, 0, 0, 0);
-        }
-        __syncthreads();
-    }
-    // C/D: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
-    float *C = a.C + (size_t)blockIdx.z * a.c_slab;
-    const int n = n0 + wn + (lane & 31);
-    if (n >= a.N) return;
-    float bj = 0.0f;
-    if (EPI == FIT_EPI_BIAS || EPI == FIT_EPI_BIAS_RELU) bj = a.bias[n];
-#pragma unroll
-    for (int reg = 0; reg < 16; reg++) {
-        const int m = m0 + wm + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
-        if (m >= a.M) continue;
-        float v = acc[reg];
-        if (EPI == FIT_EPI_BIAS || EPI == FIT_EPI_BIAS_RELU) v = v + bj;
-        if (EPI == FIT_EPI_BIAS_RELU) v = v < 0.0f ? 0.0f : v;
-        if (EPI == FIT_EPI_MASK) v = a.mask[(size_t)m * a.ldc + n] > 0.0f ? v : 0.0f;
-        C[(size_t)m * a.ldc + n] = v;
-    }
-}
-
-// THE GROUPED TRAINER (clothhip_policy_fit*_members): n_m rows of the handle's population fitted in the launches of one network. Every
-// kernel below is its single-network kernel with ONE more index, the member j of the call, folded into gridDim.x (a call may name up to
-// 65 536 members, more than gridDim.y / z hold): blockIdx.x = j * (blocks of one member) + the single kernel's blockIdx.x. Member j's
-// weights, moments lie at members[j] * stride of a [pop_rows][stride] table (members: a device table), its scratch tables (activations,
-// dZ, slabs, gradient, index rows, loss) at j times the table's per-member size. An element's arithmetic is the single kernel's -- one
-// device function serves both forms (the tile: the same text, see fit_gemm_tile) --, so member j's bits are those of that network
-// fitted alone on a handle of its own.
-struct FitGemmMembersArgs {
-    FitGemmArgs g;              // member 0's scratch tables; B (when b_weights) and bias relative to row 0 of the population
-    const int32_t *members;     // [n_m] population rows
-    int64_t stride;             // floats between two population rows
+    const int32_t *members;     // [n_m] rows of the weight table
+    int64_t stride;             // floats between two rows of the weight table
     int64_t a_step, b_step, c_step, mask_step, rows_step;      // per-member sizes of the scratch tables (0: one table for all, the dataset)
     int32_t b_weights;          // B is the weight matrix of row members[j], else a scratch table
     int32_t tiles_n;            // blocks of one member along x
 };
 
-// k_fit_gemm's tile with the block indices as arguments: tile (bx, by) of the bz-th k range. The SAME text as k_fit_gemm's body but for those
-// three names -- k_fit_gemm itself keeps its own copy, because calling this function from it changed the registers the compiler gave
-// one of its instantiations, and the shared trainer's code objects are to stay what they were.
+typedef float fit_f32x16 __attribute__((ext_vector_type(16)));
+
+// Tile (bx, by) of the bz-th k range of the product `a` describes, its pointers already those of the member: k_fit_gemm below does the
+// member's addressing, this function the tile. (It stays a function of its own although it has one caller: with its text written into
+// the kernel, <false, false, 0, true> takes 37 VGPRs instead of 34.)
 template <bool A_KC, bool B_KC, int EPI, bool ROWS> __device__ __forceinline__ void fit_gemm_tile(const FitGemmArgs &a, const int bx, const int by, const int bz) {
     __shared__ float As[FIT_BK][FIT_LDS_LD], Bs[FIT_BK][FIT_LDS_LD];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -192,10 +129,10 @@ template <bool A_KC, bool B_KC, int EPI, bool ROWS> __device__ __forceinline__ v
     }
 }
 
-template <bool A_KC, bool B_KC, int EPI, bool ROWS> __global__ __launch_bounds__(FIT_THREADS) void k_fit_gemm_members(FitGemmMembersArgs p) {
+template <bool A_KC, bool B_KC, int EPI, bool ROWS> __global__ __launch_bounds__(FIT_THREADS) void k_fit_gemm(FitGemmArgs p) {
     const int j = blockIdx.x / p.tiles_n, bx = blockIdx.x - j * p.tiles_n;
     const int64_t w = (int64_t)p.members[j] * p.stride;
-    FitGemmArgs a = p.g;
+    FitGemmArgs a = p;
     a.A += (int64_t)j * p.a_step;
     a.B += p.b_weights ? w : (int64_t)j * p.b_step;
     a.C += (int64_t)j * p.c_step;
@@ -205,41 +142,37 @@ template <bool A_KC, bool B_KC, int EPI, bool ROWS> __global__ __launch_bounds__
     fit_gemm_tile<A_KC, B_KC, EPI, ROWS>(a, bx, blockIdx.y, blockIdx.z);
 }
 
-// out[i] = slab_0[i] + slab_1[i] + ... in ascending order, i < n (the split batch sum of a weight gradient)
-__device__ __forceinline__ void fit_reduce_at(const float *part, int64_t slab, int32_t n_slabs, float *out, int64_t n, const int64_t i) {
+// out[i] = slab_0[i] + slab_1[i] + ... in ascending order, i < n (the split batch sum of a weight gradient). Member j: part + j * part_step
+// -> out + j * out_step; `blocks` blocks per member
+__global__ __launch_bounds__(256) void k_fit_reduce(const float *part, int64_t slab, int32_t n_slabs, float *out, int64_t n, int64_t part_step,
+                                                    int64_t out_step, int32_t blocks) {
+    const int j = blockIdx.x / blocks, bx = blockIdx.x - j * blocks;
+    const int64_t i = (int64_t)bx * 256 + threadIdx.x;
     if (i >= n) return;
+    part += (int64_t)j * part_step;
     float s = part[i];
     for (int z = 1; z < n_slabs; z++) s = s + part[(size_t)z * slab + i];
-    out[i] = s;
-}
-__global__ __launch_bounds__(256) void k_fit_reduce(const float *part, int64_t slab, int32_t n_slabs, float *out, int64_t n) {
-    fit_reduce_at(part, slab, n_slabs, out, n, (int64_t)blockIdx.x * 256 + threadIdx.x);
-}
-// member j: part + j * part_step -> out + j * out_step; `blocks` blocks per member
-__global__ __launch_bounds__(256) void k_fit_reduce_members(const float *part, int64_t slab, int32_t n_slabs, float *out, int64_t n, int64_t part_step,
-                                                            int64_t out_step, int32_t blocks) {
-    const int j = blockIdx.x / blocks, bx = blockIdx.x - j * blocks;
-    fit_reduce_at(part + (int64_t)j * part_step, slab, n_slabs, out + (int64_t)j * out_step, n, (int64_t)bx * 256 + threadIdx.x);
+    out[(int64_t)j * out_step + i] = s;
 }
 
-// db[j] = sum_r dz[r][j], r ascending
-__device__ __forceinline__ void fit_colsum_at(const float *dz, int32_t B, int32_t n_out, float *db, const int j) {
-    if (j >= n_out) return;
+// db[c] = sum_r dz[r][c], r ascending. Member j: dz + j * dz_step -> db + j * db_step; `blocks` blocks per member
+__global__ __launch_bounds__(64) void k_fit_colsum(const float *dz, int32_t B, int32_t n_out, float *db, int64_t dz_step, int64_t db_step, int32_t blocks) {
+    const int j = blockIdx.x / blocks, bx = blockIdx.x - j * blocks;
+    const int c = bx * 64 + threadIdx.x;
+    if (c >= n_out) return;
+    dz += (int64_t)j * dz_step;
     float s = 0.0f;
-    for (int r = 0; r < B; r++) s = s + dz[(size_t)r * n_out + j];
-    db[j] = s;
-}
-__global__ __launch_bounds__(64) void k_fit_colsum(const float *dz, int32_t B, int32_t n_out, float *db) {
-    fit_colsum_at(dz, B, n_out, db, blockIdx.x * 64 + threadIdx.x);
-}
-__global__ __launch_bounds__(64) void k_fit_colsum_members(const float *dz, int32_t B, int32_t n_out, float *db, int64_t dz_step, int64_t db_step, int32_t blocks) {
-    const int j = blockIdx.x / blocks, bx = blockIdx.x - j * blocks;
-    fit_colsum_at(dz + (int64_t)j * dz_step, B, n_out, db + (int64_t)j * db_step, bx * 64 + threadIdx.x);
+    for (int r = 0; r < B; r++) s = s + dz[(size_t)r * n_out + c];
+    db[(int64_t)j * db_step + c] = s;
 }
 
-// dz[r][k] = fl(fl(y - a) / fl(2 B)) with a = lab[rows[r]][k]; *loss = sum (double)(y - a)^2 / (4 B). One workgroup of 256.
-__device__ __forceinline__ void fit_loss_block(const float *y, const float *lab, const int32_t *rows, int32_t B, float *dz, double *loss) {
+// dz[r][k] = fl(fl(y - a) / fl(2 B)) with a = lab[rows[r]][k]; loss = sum (double)(y - a)^2 / (4 B). One workgroup of 256 per member: y, dz
+// and the index rows at j times their per-member sizes, the loss at loss[j]
+__global__ __launch_bounds__(256) void k_fit_loss(const float *y, const float *lab, const int32_t *rows, int32_t B, float *dz, double *loss,
+                                                  int64_t y_step, int64_t dz_step, int64_t rows_step) {
     __shared__ double red[256];
+    const int64_t j = blockIdx.x;
+    y += j * y_step; dz += j * dz_step; rows += j * rows_step;
     const int tid = threadIdx.x, n = 4 * B;
     const float two_b = (float)(2 * B);
     double s = 0.0;
@@ -256,67 +189,48 @@ __device__ __forceinline__ void fit_loss_block(const float *y, const float *lab,
         if (tid < o) red[tid] = red[tid] + red[tid + o];
         __syncthreads();
     }
-    if (tid == 0) *loss = red[0] / (double)(4 * (int64_t)B);
-}
-__global__ __launch_bounds__(256) void k_fit_loss(const float *y, const float *lab, const int32_t *rows, int32_t B, float *dz, double *loss) {
-    fit_loss_block(y, lab, rows, B, dz, loss);
-}
-// one workgroup per member: y, dz and the index rows at j times their per-member sizes, the loss at loss[j]
-__global__ __launch_bounds__(256) void k_fit_loss_members(const float *y, const float *lab, const int32_t *rows, int32_t B, float *dz, double *loss,
-                                                          int64_t y_step, int64_t dz_step, int64_t rows_step) {
-    const int64_t j = blockIdx.x;
-    fit_loss_block(y + j * y_step, lab, rows + j * rows_step, B, dz + j * dz_step, loss + j);
+    if (tid == 0) loss[j] = red[0] / (double)(4 * (int64_t)B);
 }
 
-// Adam, every line one float32 operation: a_t = (float)(lr sqrt(1 - beta2^t) / (1 - beta1^t)), omb1 = (float)(1 - beta1), omb2 = (float)(1 - beta2)
-__device__ __forceinline__ void fit_adam_at(float *theta, float *m, float *v, const float *g, int64_t n, const int64_t i, float a_t, float beta1,
-                                            float omb1, float beta2, float omb2, float eps) {
-    if (i >= n) return;
-    const float gi = g[i];
-    const float m1 = beta1 * m[i], m2 = omb1 * gi, mi = m1 + m2;
-    const float gg = gi * gi, v1 = beta2 * v[i], v2 = omb2 * gg, vi = v1 + v2;
-    const float den = __builtin_sqrtf(vi) + eps, q = mi / den, step = a_t * q;
-    m[i] = mi; v[i] = vi;
-    theta[i] = theta[i] - step;
-}
-__global__ __launch_bounds__(256) void k_fit_adam(float *theta, float *m, float *v, const float *g, int64_t n, float a_t, float beta1, float omb1,
-                                                  float beta2, float omb2, float eps) {
-    fit_adam_at(theta, m, v, g, n, (int64_t)blockIdx.x * 256 + threadIdx.x, a_t, beta1, omb1, beta2, omb2, eps);
-}
-
-// SGD with momentum: u = fl(fl(mu u) + g); theta = fl(theta - fl(lr u))
-__device__ __forceinline__ void fit_sgd_at(float *theta, float *u, const float *g, int64_t n, const int64_t i, float lr, float mu) {
-    if (i >= n) return;
-    const float u1 = mu * u[i], ui = u1 + g[i], step = lr * ui;
-    u[i] = ui;
-    theta[i] = theta[i] - step;
-}
-__global__ __launch_bounds__(256) void k_fit_sgd(float *theta, float *u, const float *g, int64_t n, float lr, float mu) {
-    fit_sgd_at(theta, u, g, n, (int64_t)blockIdx.x * 256 + threadIdx.x, lr, mu);
-}
-
-// The grouped optimizers: member j updates row members[j] of theta, m, v ([pop_rows][stride]) from g + j * n with ITS OWN step constants
-// hyper[j][FIT_HYPER] -- the floats the single kernel takes as arguments, made on the host per member and step: Adam {a_t, beta1,
-// 1 - beta1, beta2, 1 - beta2, eps}, SGD {lr, momentum}. Only the n parameters of a row are touched, never its pad.
+// The optimizers: member j updates row members[j] of theta, m, v ([rows][stride]) from g + j * n with ITS OWN step constants
+// hyper[j][FIT_HYPER], made on the host per member and step: Adam {a_t, beta1, 1 - beta1, beta2, 1 - beta2, eps} with
+// a_t = (float)(lr sqrt(1 - beta2^t) / (1 - beta1^t)), SGD {lr, momentum}. Only the n parameters of a row are touched, never its pad.
 constexpr int FIT_HYPER = 6;
-struct FitOptMembersArgs {
+struct FitOptArgs {
     float *theta, *m, *v;
     const float *g, *hyper;
     const int32_t *members;
     int64_t stride, n;
     int32_t blocks;             // blocks of one member
 };
-__global__ __launch_bounds__(256) void k_fit_adam_members(FitOptMembersArgs a) {
+
+// Adam, every line one float32 operation
+__global__ __launch_bounds__(256) void k_fit_adam(FitOptArgs a) {
     const int j = blockIdx.x / a.blocks, bx = blockIdx.x - j * a.blocks;
-    const int64_t row = (int64_t)a.members[j] * a.stride;
+    const int64_t row = (int64_t)a.members[j] * a.stride, i = (int64_t)bx * 256 + threadIdx.x;
     const float *h = a.hyper + (int64_t)j * FIT_HYPER;
-    fit_adam_at(a.theta + row, a.m + row, a.v + row, a.g + (int64_t)j * a.n, a.n, (int64_t)bx * 256 + threadIdx.x, h[0], h[1], h[2], h[3], h[4], h[5]);
+    const float a_t = h[0], beta1 = h[1], omb1 = h[2], beta2 = h[3], omb2 = h[4], eps = h[5];
+    if (i >= a.n) return;
+    float *theta = a.theta + row, *m = a.m + row, *v = a.v + row;
+    const float gi = a.g[(int64_t)j * a.n + i];
+    const float m1 = beta1 * m[i], m2 = omb1 * gi, mi = m1 + m2;
+    const float gg = gi * gi, v1 = beta2 * v[i], v2 = omb2 * gg, vi = v1 + v2;
+    const float den = __builtin_sqrtf(vi) + eps, q = mi / den, step = a_t * q;
+    m[i] = mi; v[i] = vi;
+    theta[i] = theta[i] - step;
 }
-__global__ __launch_bounds__(256) void k_fit_sgd_members(FitOptMembersArgs a) {
+
+// SGD with momentum: u = fl(fl(mu u) + g); theta = fl(theta - fl(lr u))
+__global__ __launch_bounds__(256) void k_fit_sgd(FitOptArgs a) {
     const int j = blockIdx.x / a.blocks, bx = blockIdx.x - j * a.blocks;
-    const int64_t row = (int64_t)a.members[j] * a.stride;
+    const int64_t row = (int64_t)a.members[j] * a.stride, i = (int64_t)bx * 256 + threadIdx.x;
     const float *h = a.hyper + (int64_t)j * FIT_HYPER;
-    fit_sgd_at(a.theta + row, a.m + row, a.g + (int64_t)j * a.n, a.n, (int64_t)bx * 256 + threadIdx.x, h[0], h[1]);
+    const float lr = h[0], mu = h[1];
+    if (i >= a.n) return;
+    float *theta = a.theta + row, *u = a.m + row;
+    const float u1 = mu * u[i], ui = u1 + a.g[(int64_t)j * a.n + i], step = lr * ui;
+    u[i] = ui;
+    theta[i] = theta[i] - step;
 }
 
 }  // namespace clothhip

@@ -541,8 +541,8 @@ int clothhip_policy_fit_reset(clothhip_handle *h);
  * with no upload. Rows not named keep their bytes, and no call writes the pad floats of a row (n_params .. stride).
  * THE BITS. After any sequence of these calls, row g and its optimizer state are what a second handle holds that was given g as its
  * shared network (clothhip_set_policy_mlp), stores the same dataset and received the same sequence of
- * clothhip_policy_fit(p[j], idx[:, j, :]) calls: every kernel of the shared trainer has a grouped form with one more grid index, the
- * member, and every output element is the same accumulator in the same order (csrc/cloth_policy_fit.hpp). So EVERY ROW has its own Adam
+ * clothhip_policy_fit(p[j], idx[:, j, :]) calls: there is one trainer, whose kernels carry the member as one more grid index (the
+ * shared network is its call members = {0}, n_m = 1), and no output element depends on it (csrc/cloth_policy_fit.hpp). So EVERY ROW has its own Adam
  * m, v (SGD u) and its own 1-based step count t: a row trained in two calls of 2 steps equals one trained in one call of 4, and a row
  * that joins later starts at t = 1. a_t = lr sqrt(1 - beta2^t) / (1 - beta1^t) is made in double on the host per member and step, as for
  * clothhip_policy_fit, and goes up as one table per call. clothhip_policy_fit_grad_members returns for member j the gradient

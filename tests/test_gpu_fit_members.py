@@ -1,9 +1,10 @@
-"""GPU tests of the grouped trainer (clothhip_policy_fit*_members, the k_fit_*_members kernels of csrc/cloth_policy_fit.hpp):
-rows of a population fitted in the launches of one network. Every comparison is array_equal on the bits, and the twin is always a SECOND
-handle that carries the member as its shared network and is fitted by the existing clothhip_policy_fit* (itself pinned to float64 numpy
-and to the restated optimizers by test_gpu_policy_fit.py): gradient and loss, the optimizers' steps with per-member learning rates, the
-per-row step count, the resets, the hand-over to the evaluation and to the episode launch, an fp64 handle, every refusal, and a DAgger
-collection into an MLPEnsemble."""
+"""GPU tests of the grouped calls of the trainer (clothhip_policy_fit*_members; the k_fit_* kernels of csrc/cloth_policy_fit.hpp, which
+carry the member index): rows of a population fitted in the launches of one network. Every comparison is array_equal on
+the bits, and the twin is always a SECOND handle that carries the member as its shared network and is fitted by clothhip_policy_fit* --
+the same kernels through members = {0}, n_m = 1, pinned to float64 numpy and to the restated optimizers by test_gpu_policy_fit.py:
+gradient and loss, the optimizers' steps with per-member learning rates, the per-row step count, the resets, one handle taken from a
+shared network to a population and back, the hand-over to the evaluation and to the episode launch, an fp64 handle, every refusal, and
+a DAgger collection into an MLPEnsemble."""
 import ctypes as C
 
 import numpy as np
@@ -215,6 +216,47 @@ def test_resets(handle):
     l1 = b.fit_members([1], tc[:1, 1:], hyper)
     _twin(t, now1, rows, labels)
     assert _same(l1[:, 0], t.fit(tc[:1, 1], **hyper)) and _same(_row(b, 1, n), t.get_policy_mlp(0, n))
+
+
+def test_one_handle_from_a_shared_network_to_a_population_and_back():
+    """ONE handle, a dataset of 320 small-integer rows, Adam: a shared network for 3 steps at B = 5; a population of 3 rows, 2 steps on
+    members [2, 0] and 1 step on member [1] alone (n_m = 1 on a row other than 0); a new shared network for 3 steps at B = 300 (two
+    256-row ranges). Every stage's losses and final weights are, bit for bit, those of a FRESH handle given that stage's calls alone: no
+    moment and no step count carries over, and the one moment table survives [n_params] -> [3][stride] -> [n_params]."""
+    widths, n_rows = [300, 5, 4], 320
+    n = _n_params(widths)
+    r = np.random.RandomState(16)
+    rows, labels = r.randint(-2, 3, size=(n_rows, 300)).astype(np.float32), r.randint(-3, 4, size=(n_rows, 4)).astype(np.float64)
+    nets, first, last = _nets(widths), _random_layers(widths, 50), _random_layers(widths, 51)
+    t1, t2, t2b, t3 = (r.randint(0, n_rows, size=s).astype(np.int32) for s in [(3, 5), (2, 2, 5), (1, 1, 5), (3, 300)])
+    hyper = dict(ADAM, lr=1e-2)
+
+    def shared(layers, table):
+        def stage(x):
+            x.set_policy_mlp(layers)
+            return [x.fit(table, **hyper)], [x.get_policy_mlp(0, n)]
+        return stage
+
+    def population(x):
+        x.set_policy_population(nets, np.zeros(x.E, dtype=np.int32))
+        losses = [x.fit_members([2, 0], t2, hyper), x.fit_members([1], t2b, hyper)]
+        return losses, [_row(x, g, n, pad=True) for g in range(G)]
+
+    b = _new_batch(10)
+    b.fit_append(rows, labels)
+    for name, stage in [("shared, B = 5", shared(first, t1)), ("population", population), ("shared, B = 300", shared(last, t3))]:
+        got_loss, got_w = stage(b)
+        fresh = _new_batch(10)
+        fresh.fit_append(rows, labels)
+        want_loss, want_w = stage(fresh)
+        fresh.close()
+        print("%s: losses %r, fresh handle %r" % (name, [l.tolist() for l in got_loss], [l.tolist() for l in want_loss]))
+        assert len(got_loss) == len(want_loss) and len(got_w) == len(want_w)
+        assert all(np.isfinite(l).all() and (l > 0).all() for l in want_loss)
+        assert all(_same(g, w) for g, w in zip(got_loss, want_loss)), name
+        assert all(_same(g, w) for g, w in zip(got_w, want_w)), name
+    assert not _same(got_w[0], np.concatenate([np.concatenate([W.reshape(-1), c]) for W, c in last]))      # (the last stage did train)
+    b.close()
 
 
 # ---- 5. the hand-over ---------------------------------------------------------------------------------------------------------------------

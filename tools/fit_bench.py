@@ -12,8 +12,10 @@ One ClothBatch of one 25x25 cloth (3P = 1875 inputs), a dataset of 8192 uniform 
 The smaller shapes are launch- and latency-bound (a step is 4 to 6 kernel launches per layer): the tool says what a step costs there, it
 does not claim a rate.
     python3 tools/fit_bench.py [--steps 20] [--rounds 5] [--out FILE]
---members runs the members section instead (clothhip_policy_fit_members; profiles/fit_members.txt): a grouped Adam step of
-G = 1, 4, 16, 64 networks at B = 256 against G single-network steps timed in the same process.
+--members runs the members section instead (clothhip_policy_fit_members; profiles/fit_members.txt, profiles/fit_unified.txt, DESIGN
+4.3.7): a grouped Adam step of G = 1, 4, 16, 64 networks at B = 256 against G single-network steps timed in the same process. Both
+calls run the same kernels (k_fit_gemm, k_fit_loss, k_fit_reduce, k_fit_colsum, k_fit_adam): the single network is the call
+members = {0}, n_m = 1.
     python3 tools/fit_bench.py --members [--steps 20] [--rounds 5] [--out FILE]"""
 import argparse
 import os
