@@ -280,6 +280,14 @@ def i32p(a):
     return None if a is None else a.ctypes.data_as(_i32p)
 
 
+def fp(a):
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def vp(a):
+    return None if a is None else a.ctypes.data_as(_vp)
+
+
 def params_from_cfg(cfg, gravity=-9.8, minimum_z=0.0):
     """cfg: the dict ClothEnv loads from cfg/*.yaml (cloth_env.py:87-118, cloth.pyx:53-56,175-186)."""
     c = cfg["cloth"]

@@ -4,11 +4,17 @@ This is the batched counterpart of the reference's `Cloth` + `Gripper` pair (gym
 gripper.pyx:8); the single-cloth façade with the reference's attribute names lives in physics.py.
 """
 import ctypes as C
+from collections import namedtuple
 
 import numpy as np
 
 from . import _lib
 from ._lib import F32, F64, SCHED_DTYPE, check
+
+# ClothBatch._launch, the last episode launch of a batch: T slots and R reset scripts per env (the shapes of the tables it left on the
+# device: render_obs('slots' / 'resets'), run_actions_labels), and between run_actions_begin and run_actions_end what the second half needs
+LastLaunch = namedtuple("LastLaunch", "T R pending")
+PendingLaunch = namedtuple("PendingLaunch", "num_steps done have_rst have_obs have_robs rng_states")
 
 
 def make_schedules(n, **fields):
@@ -260,7 +266,7 @@ class ClothBatch(object):
         dep = np.empty((self.E, p.height, p.width), dtype=np.float32) if want_depth else None
         sw = None if swap_sides is None else np.ascontiguousarray(np.broadcast_to(np.asarray(swap_sides, dtype=np.uint8), (self.E,)))
         check(self._L.clothhip_render(self._h, C.byref(p), _lib.u8p(sw), _lib.u8p(rgb),
-                                      None if dep is None else dep.ctypes.data_as(C.POINTER(C.c_float))))
+                                      _lib.fp(dep)))
         return rgb, dep
 
     def render_obs(self, source, obs=None, valid=None, swap_sides=None, fmt='rgbd', params=None, out_device_ptr=None, **render_kw):
@@ -281,12 +287,12 @@ class ClothBatch(object):
         elif src == _lib.OBS_STATE:
             n = self.E
         else:
-            last = getattr(self, '_last_launch', None)                # (T, R) of the last run_actions launch
-            n = 0 if last is None else (last[0] * self.E if src == _lib.OBS_SLOTS else self.E * last[1])
+            last = getattr(self, '_launch', None)                     # the last run_actions launch
+            n = 0 if last is None else (last.T * self.E if src == _lib.OBS_SLOTS else self.E * last.R)
         flag = lambda a: None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a).astype(bool).astype(np.uint8), (n,)))
         v, sw = flag(valid), flag(swap_sides)
         out = np.empty((n, p.height, p.width, 4 if f == _lib.IMG_RGBD else 3), dtype=np.uint8)
-        check(self._L.clothhip_render_obs(self._h, C.byref(p), src, None if obs is None else obs.ctypes.data_as(C.POINTER(C.c_float)),
+        check(self._L.clothhip_render_obs(self._h, C.byref(p), src, _lib.fp(obs),
                                           n, _lib.u8p(v), _lib.u8p(sw), f, _lib.u8p(out),
                                           None if out_device_ptr is None else C.c_void_p(int(out_device_ptr))))
         return out
@@ -387,30 +393,27 @@ class ClothBatch(object):
         R = scripts.shape[1] if scripts is not None else (int(reset_capacity) if rng_states is not None else 0)
         have_rst = bool(want_resets and have_src)
         have_robs = bool(want_obs and have_src)
-        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
         if expert is not None:                           # (the library copies both tables; the arming is for the very next launch alone)
             check(self._L.clothhip_run_actions_expert(self._h, _lib.EXPERTS.get(expert, expert), T, _lib.u8p(mix), _lib.i32p(cho)))
-        check(self._L.clothhip_run_actions_begin(self._h, C.byref(ep), T, pol, ap, on_dev, _lib.i32p(parg), vp(scripts), R,
-                                                 _lib.i32p(num_steps), _lib.u8p(done), vp(rng_states), int(rng_tier),
+        check(self._L.clothhip_run_actions_begin(self._h, C.byref(ep), T, pol, ap, on_dev, _lib.i32p(parg), _lib.vp(scripts), R,
+                                                 _lib.i32p(num_steps), _lib.u8p(done), _lib.vp(rng_states), int(rng_tier),
                                                  int(domrand_words), int(have_rst), 2 if keep else int(bool(want_obs)),
                                                  2 if keep and have_robs else int(have_robs), float(time_budget_ms)))
-        self._fused = (T, R, num_steps, done, have_rst, bool(want_obs) and not keep, have_robs and not keep, rng_states)
-        self._last_launch = (T, R)                       # the shapes of the tables render_obs('slots' / 'resets') reads
+        self._launch = LastLaunch(T, R, PendingLaunch(num_steps, done, have_rst, bool(want_obs) and not keep, have_robs and not keep, rng_states))
 
     def run_actions_end(self):
         """Second half: wait for the launch and fetch its outputs. num_steps / done given to _begin are updated in place.
         rng_states given to _begin (uint32[E, 626]) now hold the advanced streams.
         Returns (records[T, E], resets[E, R] or None, obs float32[T, E, 3P] or None, reset_obs float32[E, R, 3P] or None:
         the first observation of every episode started inside the launch)."""
-        T, R, num_steps, done, have_rst, have_obs, have_robs, rng_states = self._fused
-        self._fused = None
+        (T, R, p), vp = self._launch, _lib.vp
+        self._launch = LastLaunch(T, R, None)                # (the shapes stay: the tables the launch leaves on the device have them)
         rec = np.zeros((T, self.E), dtype=_lib.STEP_RECORD_DTYPE)
-        rst = np.zeros((self.E, R), dtype=_lib.RESET_RECORD_DTYPE) if have_rst else None
-        obs = np.empty((T, self.E, 3 * self.P), dtype=np.float32) if have_obs else None
-        robs = np.empty((self.E, R, 3 * self.P), dtype=np.float32) if have_robs else None
-        vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
-        check(self._L.clothhip_run_actions_end(self._h, _lib.i32p(num_steps), _lib.u8p(done), vp(rec), vp(rst), vp(obs),
-                                               vp(robs), vp(rng_states)))
+        rst = np.zeros((self.E, R), dtype=_lib.RESET_RECORD_DTYPE) if p.have_rst else None
+        obs = np.empty((T, self.E, 3 * self.P), dtype=np.float32) if p.have_obs else None
+        robs = np.empty((self.E, R, 3 * self.P), dtype=np.float32) if p.have_robs else None
+        check(self._L.clothhip_run_actions_end(self._h, _lib.i32p(p.num_steps), _lib.u8p(p.done), vp(rec), vp(rst), vp(obs),
+                                               vp(robs), vp(p.rng_states)))
         return rec, rst, obs, robs
 
     def _expert_tables(self, expert, expert_mix, expert_choices, T):
@@ -441,7 +444,7 @@ class ClothBatch(object):
     def run_actions_labels(self, n_actions=None):
         """float64[T, E, 4]: the expert's labels of the last, armed episode launch (clothhip_run_actions_labels), NaN where the slot's
         `ran` is 0. ClothHipError when that launch was not armed."""
-        T = int(self._last_launch[0] if n_actions is None else n_actions)
+        T = int(self._launch.T if n_actions is None else n_actions)
         out = np.zeros((T, self.E, 4), dtype=np.float64)
         check(self._L.clothhip_run_actions_labels(self._h, _lib.dp(out), None))
         return out
@@ -460,7 +463,7 @@ class ClothBatch(object):
             obs = np.ascontiguousarray(obs, dtype=np.float32)
             if obs.ndim != 2 or obs.shape[1] != 3 * self.P:
                 raise ValueError("obs must have shape (n, %d)" % (3 * self.P))
-            n, ptr = obs.shape[0], self._fp(obs)
+            n, ptr = obs.shape[0], _lib.fp(obs)
         tabs = []
         for name, a in (('side', side), ('choices', choices)):
             if a is not None:
@@ -530,10 +533,6 @@ class ClothBatch(object):
         check(self._L.clothhip_policy_eval(self._h, ptr, n, _lib.dp(out)))
         return out
 
-    @staticmethod
-    def _fp(a):
-        return a.ctypes.data_as(C.POINTER(C.c_float))
-
     def _member_map(self, member, rows):
         """member as int32[E], checked against [0, rows): what the library would refuse is refused here first."""
         m = np.asarray(member)
@@ -557,7 +556,7 @@ class ClothBatch(object):
         from .policies import pack_population
         widths, blob = pack_population(members, n_in=3 * self.P)
         m = self._member_map(member, blob.shape[0])
-        check(self._L.clothhip_set_policy_population(self._h, len(widths) - 1, _lib.i32p(widths), self._fp(blob), blob.shape[0], _lib.i32p(m)))
+        check(self._L.clothhip_set_policy_population(self._h, len(widths) - 1, _lib.i32p(widths), _lib.fp(blob), blob.shape[0], _lib.i32p(m)))
         self._pop_shape = (int(blob.shape[0]), int(blob.shape[1]))
 
     def set_policy_members(self, member):
@@ -571,7 +570,7 @@ class ClothBatch(object):
         """Blob g of the handle's population (g = 0: a shared network) as float32[n_params], downloaded (clothhip_get_policy_mlp). For a
         population n_params may be the row stride (policies.population_stride): the row with its pad."""
         out = np.zeros(int(n_params), dtype=np.float32)
-        check(self._L.clothhip_get_policy_mlp(self._h, int(g), self._fp(out), out.size))
+        check(self._L.clothhip_get_policy_mlp(self._h, int(g), _lib.fp(out), out.size))
         return out
 
     def policy_eval_members(self, obs, members):
@@ -584,7 +583,7 @@ class ClothBatch(object):
             obs = np.ascontiguousarray(obs, dtype=np.float32)
             if obs.ndim != 2 or obs.shape[1] != 3 * self.P:
                 raise ValueError("obs must have shape (n, %d)" % (3 * self.P))
-            n, ptr = obs.shape[0], self._fp(obs)
+            n, ptr = obs.shape[0], _lib.fp(obs)
         if m.shape != (n,):
             raise ValueError("members must have shape (%d,)" % n)
         out = np.zeros((n, 4), dtype=np.float64)
@@ -608,7 +607,7 @@ class ClothBatch(object):
         if not np.isfinite(np.float32(sigma)):
             raise ValueError("sigma is not finite")
         m = self._member_map(np.arange(self.E) % (G + 1) if member is None else member, G + 1)
-        check(self._L.clothhip_policy_population_perturb(self._h, len(widths) - 1, _lib.i32p(widths), self._fp(blob), G, float(np.float32(sigma)),
+        check(self._L.clothhip_policy_population_perturb(self._h, len(widths) - 1, _lib.i32p(widths), _lib.fp(blob), G, float(np.float32(sigma)),
                                                          int(seed), _lib.POP_ANTITHETIC if antithetic else 0, _lib.i32p(m)))
         self._pop_n_params = blob.size
         self._pop_shape = (G + 1, int(blob.size))
@@ -621,7 +620,7 @@ class ClothBatch(object):
         if c.ndim != 1:
             raise ValueError("coef must be one-dimensional")
         out = np.zeros(getattr(self, '_pop_n_params', 0), dtype=np.float32)      # (set by the last perturb that succeeded: the one the library sums, or it refuses before it writes)
-        check(self._L.clothhip_policy_population_combine(self._h, self._fp(c), c.size, self._fp(out)))
+        check(self._L.clothhip_policy_population_combine(self._h, _lib.fp(c), c.size, _lib.fp(out)))
         return out
 
     def fit_append(self, obs, labels):
@@ -636,7 +635,7 @@ class ClothBatch(object):
             raise ValueError("labels must have shape (%d, 4)" % obs.shape[0])
         if not (np.isfinite(obs).all() and np.isfinite(lab).all() and (np.abs(lab) <= np.finfo(np.float32).max).all()):
             raise ValueError("obs and labels must be finite (float32)")
-        check(self._L.clothhip_fit_data_append(self._h, self._fp(obs), _lib.dp(lab), obs.shape[0]))
+        check(self._L.clothhip_fit_data_append(self._h, _lib.fp(obs), _lib.dp(lab), obs.shape[0]))
         return self.fit_size()
 
     def fit_hold(self, src=None):
@@ -669,7 +668,7 @@ class ClothBatch(object):
             raise ValueError("first and n must be >= 0 and lie within the dataset")
         obs = np.zeros((n, 3 * self.P), dtype=np.float32)
         lab = np.zeros((n, 4), dtype=np.float32)
-        check(self._L.clothhip_fit_data_get(self._h, first, n, self._fp(obs), self._fp(lab)))
+        check(self._L.clothhip_fit_data_get(self._h, first, n, _lib.fp(obs), _lib.fp(lab)))
         return obs, lab
 
     def fit_loss(self, idx):
@@ -716,7 +715,7 @@ class ClothBatch(object):
         n_params = self._fit_n_params()
         grad = np.zeros(n_params, dtype=np.float32)
         loss = np.zeros(1, dtype=np.float64)
-        check(self._L.clothhip_policy_fit_grad(self._h, _lib.i32p(ix), ix.size, self._fp(grad), _lib.dp(loss)))
+        check(self._L.clothhip_policy_fit_grad(self._h, _lib.i32p(ix), ix.size, _lib.fp(grad), _lib.dp(loss)))
         return float(loss[0]), grad
 
     def _fit_n_params(self):
@@ -799,7 +798,7 @@ class ClothBatch(object):
         ix = self._fit_members_idx(idx, m.size, 2)
         grad = np.zeros((m.size, n_params), dtype=np.float32)
         loss = np.zeros(m.size, dtype=np.float64)
-        check(self._L.clothhip_policy_fit_grad_members(self._h, _lib.i32p(m), m.size, _lib.i32p(ix), ix.shape[1], self._fp(grad), _lib.dp(loss)))
+        check(self._L.clothhip_policy_fit_grad_members(self._h, _lib.i32p(m), m.size, _lib.i32p(ix), ix.shape[1], _lib.fp(grad), _lib.dp(loss)))
         return loss, grad
 
     def fit_members(self, members, idx_table, hyper=None):
@@ -881,7 +880,7 @@ class ClothBatch(object):
         cd = np.zeros((n, H, E * K, 4)) if want_candidates else None
         check(self._L.clothhip_plan_cem(self._h, src_batch._h, C.byref(ep), C.byref(p), _lib.i32p(ns), _lib.u8p(dn), _lib.dp(m), _lib.dp(s),
                                         _lib.dp(best_a), _lib.dp(best_s), _lib.dp(sc), _lib.dp(cd)))
-        self._last_launch = (H, 0)
+        self._launch = LastLaunch(H, 0, None)                # (the planner's last launch, ended on the device: H slots, no reset source)
         out = dict(mean=m, std=s, actions=best_a, score=best_s)
         if want_scores:
             out['scores'] = sc

@@ -145,7 +145,7 @@ extern "C" int clothhip_precision(const clothhip_handle *h) { return h ? h->prec
 extern "C" void *clothhip_stream(clothhip_handle *h) { return h ? (void *)h->stream : nullptr; }
 
 // no call that touches what an episode launch reads or writes between clothhip_run_actions_begin and _end
-int clothhip::check_idle(const clothhip_handle *h) { return h->epi.f_pending ? fail(CLOTHHIP_ESTATE, "clothhip_run_actions_begin still in flight: call clothhip_run_actions_end first") : 0; }
+int clothhip::check_idle(const clothhip_handle *h) { return h->epi.last.pending ? fail(CLOTHHIP_ESTATE, "clothhip_run_actions_begin still in flight: call clothhip_run_actions_end first") : 0; }
 
 extern "C" int clothhip_fused_supported(const clothhip_handle *h) { return h ? (fused_supported(*h) ? 1 : 0) : fail(CLOTHHIP_EINVAL, "handle is NULL"); }
 

@@ -90,20 +90,15 @@ extern "C" int clothhip_fit_data_get(clothhip_handle *h, int64_t first, int64_t 
 }
 
 // ---- rows named by where they lie on the device (cloth_fit_gather.hpp) ------------------------------------------------------------------
-// One (source, row) of a caller's table against what the handle holds now; the launch tables are valid under clothhip_render_obs's rule.
+// One (source, row) of a caller's table against what the handle holds now; the launch tables are valid under launch_table's rule.
 static int check_source(const clothhip_handle *h, int64_t i, int32_t src, int32_t row) {
-    const auto &e = h->epi;
     int64_t rows = 0;
     switch (src) {
     case CLOTHHIP_FIT_SRC_SLOTS:
-        if (e.f_T < 1) return fail(CLOTHHIP_ESTATE, "no clothhip_run_actions launch yet");
-        if (!e.f_obs) return fail(CLOTHHIP_ESTATE, "the last clothhip_run_actions launch was not given want_obs");
-        rows = (int64_t)e.f_T * h->E;
+        if (int rc = launch_table(h, LaunchTable::obs, nullptr, &rows)) return rc;
         break;
     case CLOTHHIP_FIT_SRC_RESETS:
-        if (e.f_T < 1) return fail(CLOTHHIP_ESTATE, "no clothhip_run_actions launch yet");
-        if (!e.f_robs) return fail(CLOTHHIP_ESTATE, "the last clothhip_run_actions launch was not given want_reset_obs");
-        rows = (int64_t)e.f_nscr;
+        if (int rc = launch_table(h, LaunchTable::reset_obs, nullptr, &rows)) return rc;
         break;
     case CLOTHHIP_FIT_SRC_HELD:
         if (!h->fit.held_valid) return fail(CLOTHHIP_ESTATE, "no held rows on this handle: call clothhip_fit_hold first");
@@ -193,8 +188,8 @@ extern "C" int clothhip_fit_data_append_launch(clothhip_handle *h, const int32_t
     if (!rows) return fail(CLOTHHIP_EINVAL, "NULL argument");
     auto &f = h->fit;
     if (f.n + n > INT32_MAX) return fail(CLOTHHIP_EINVAL, "%lld + %lld rows: a minibatch names its rows by int32", (long long)f.n, (long long)n);
-    if (!h->epi.f_labels || h->epi.f_T < 1) return fail(CLOTHHIP_ESTATE, "the last episode launch on this handle was not armed with an expert (clothhip_run_actions_expert)");
-    const int64_t n_lab = (int64_t)h->epi.f_T * h->E;
+    int64_t n_lab = 0;
+    if (int rc = launch_table(h, LaunchTable::labels, nullptr, &n_lab)) return rc;
     std::vector<int32_t> tab;
     try { tab.resize((size_t)n * 4); } catch (const std::bad_alloc &) { return fail(CLOTHHIP_ENOMEM, "out of host memory (%lld rows)", (long long)n); }
     for (int64_t i = 0; i < n; i++) {

@@ -1,5 +1,5 @@
 // api_handle.hpp -- private to the api_*.hip units that implement include/clothhip.h: the handle, and the few helpers more than one of them calls.
-// Each group of fields below names the one unit that writes it; a field another unit reads is read directly.
+// Each group of fields below names the one unit that writes it; a field another unit reads is read directly (the last episode launch's record: through launch_table).
 #pragma once
 #include <cstring>
 #include <vector>
@@ -10,6 +10,47 @@
 
 using namespace clothhip;
 #pragma GCC visibility push(hidden)      // the handle and the shared helpers are private to the library: nothing here reaches its dynamic symbol table
+
+// What ONE episode launch is asked to do (api_run.hip: begin_launch; clothhip.h: clothhip_run_actions_begin has the meaning of every field).
+// An optional output table is Absent, written and downloaded by _end, or written and kept on the device (want_* = 0 / 1 / 2).
+enum class TableMode { Absent, Download, Keep };
+enum class ResetSource { none, scripts, rng };
+struct LaunchRequest {
+    const ClothEpisodeParams *ep = nullptr;
+    int T = 0, policy = CLOTHHIP_POLICY_TABLE;
+    const double *actions = nullptr;        // [T][E][4] on the host, or on the device with actions_on_device
+    bool actions_on_device = false;
+    const int32_t *policy_arg = nullptr;
+    ResetSource reset_source = ResetSource::none;
+    const void *reset_data = nullptr;       // ClothResetScript [E][n_scripts] / the rng states uint32 [E][MT_WORDS]
+    bool two_reset_sources = false;         // the public entry was given scripts AND rng states: refused in its place (check_launch)
+    int n_scripts = 0, rng_tier = 0;        // (n_scripts 0 without a reset source)
+    uint64_t domrand_words = 0;
+    const int32_t *num_steps = nullptr;
+    const uint8_t *done = nullptr;
+    TableMode resets = TableMode::Absent, obs = TableMode::Absent, reset_obs = TableMode::Absent;      // (resets: never kept)
+    uint64_t budget_ticks = 0;              // the time slice in 100 MHz ticks, 0: none
+    // from the arming (next_request alone fills these): the expert beside the acting policy, whether it has a mix table, and whether the
+    // previous launch was armed -- an action it cut left its label in EpResume
+    int expert = 0;
+    bool expert_mix = false, resume_labelled = false;
+    bool tier2() const { return reset_source == ResetSource::rng && rng_tier == 2; }
+    bool action_table() const { return policy == CLOTHHIP_POLICY_TABLE || (policy == CLOTHHIP_POLICY_MLP && actions); }      // (MLP: the optional noise table)
+};
+
+// What the last episode launch left on the device (written by api_run.hip alone; the tables themselves are EpisodeStaging's buffers).
+struct LaunchRecord {
+    int T = 0;                  // action slots; 0: no launch yet
+    size_t reset_rows = 0;      // rows of the reset tables: E * max(n_scripts, 1)
+    bool pending = false;       // between _begin and _end
+    bool resets = false, rng = false;       // _end downloads reset records / the advanced rng states
+    TableMode obs = TableMode::Absent, reset_obs = TableMode::Absent;
+    bool armed = false;         // the label table exists (clothhip_run_actions_labels), and the label an action cut by its time slice carries over
+    // a _begin that has come to where the observation tables may be reallocated or overwritten: they stop being readable, whatever becomes
+    // of that call; everything else the record says stays (the next launch's resume_labelled reads `armed`)
+    void invalidate_obs_tables() { obs = reset_obs = TableMode::Absent; }
+};
+enum class LaunchTable { obs, reset_obs, labels };
 
 // The host fields (HostPlan: layout_plan.hpp) and everything the handle holds on its device. Each buffer frees itself; the stream and the
 // events are declared in front of the buffers, so they go after them.
@@ -63,8 +104,9 @@ struct clothhip_handle : HostPlan {
     Buffer<int32_t> d_hcnt;         // per env: #points with z < thickness/2 (height reward, cloth_env.py:1047-1073)
     int n_grab_levels = 0;
     // clothhip_run_actions staging (device), sized on demand: written by clothhip_run_actions_begin / _end alone (api_run.hip). Read elsewhere:
-    // f_pending (check_idle), f_T, f_nscr, f_obs, f_robs, d_fobs, d_frobs (clothhip_render_obs; the row sources of api_fit.hip, which also reads
-    // f_labels and d_flab); d_resume is cleared by drop_in_flight* and clothhip_fork
+    // last.pending (check_idle, clothhip_plan_cem); where a table of the last launch lies and how many rows it has, through launch_table below
+    // (clothhip_render_obs, the row sources of api_fit.hip, whose gather also takes d_fobs, d_frobs and d_flab as they are); d_frec
+    // (clothhip_plan_cem); d_resume is cleared by drop_in_flight* and clothhip_fork
     struct EpisodeStaging {
         Buffer<void> d_fz, d_fact, d_fscr, d_frec, d_frst, d_fobs, d_frobs;
         Buffer<int32_t> d_fsteps, d_fparg;
@@ -73,13 +115,11 @@ struct clothhip_handle : HostPlan {
         Buffer<uint8_t> d_fdone;
         Buffer<double> d_fsum;          // [E][4] per-env summary of the last episode launch (what the multi-GPU driver all-gathers)
         Buffer<uint64_t> d_fticks;      // [E][8] per-operation-class ticks and update() counts of the last episode launch
-        int f_T = 0; size_t f_nscr = 0; bool f_pending = false, f_resets = false, f_obs = false, f_robs = false, f_mt = false;
-        bool f_obs_kept = false, f_robs_kept = false;   // want_obs / want_reset_obs == 2: the table is written and stays here, _end downloads none
-        // the expert beside the acting policy: what clothhip_run_actions_expert armed for the NEXT launch (host copies of its tables), the
-        // armed launch's device tables, and whether the last launch was armed (f_labels: clothhip_run_actions_labels, and the label an action
-        // cut by its time slice carries over)
+        LaunchRecord last;
+        // the expert beside the acting policy: what clothhip_run_actions_expert armed for the NEXT launch (host copies of its tables) and the
+        // armed launch's device tables
         int arm_expert = 0, arm_T = 0;
-        bool arm_mix = false, f_labels = false;
+        bool arm_mix = false;
         std::vector<uint8_t> h_arm_mix;
         std::vector<int32_t> h_arm_choice;
         Buffer<double> d_flab;
@@ -91,7 +131,7 @@ struct clothhip_handle : HostPlan {
     struct RenderScratch { Buffer<void> d_ro_img, d_ro_depth, d_ro_src, d_ro_flags; } ro;
     std::vector<unsigned char> stage;   // host staging for layout conversion
     std::vector<double> flat_rest;
-    // The policy network and its population (api_policy.hip); outside it only mlp is read: fill_fused copies it, clothhip_run_actions_begin asks
+    // The policy network and its population (api_policy.hip); outside it only mlp is read: fill_fused copies it, check_launch asks
     // whether a network exists.
     struct Policy {
         // clothhip_set_policy_mlp: the handle's network (n_layers 0: none; mlp.params = d_mlp) and clothhip_policy_eval's scratch for ONE chunk of rows
@@ -162,6 +202,11 @@ SpecPhys phys_of(const ClothParams &p, const ClothMaterial &m);
 ClothMaterial material_of(const ClothParams &p);
 int drop_in_flight(clothhip_handle *h, const uint8_t *d_mask, const ClothSchedule *d_sched);
 int plan_steppers(clothhip_handle *h);                                                           // api_run.hip, for clothhip_create
+LaunchRequest next_request(clothhip_handle *h);      // api_run.hip: an empty request for h's next launch; TAKES the arming, which is gone whatever becomes of the request
+int begin_launch(clothhip_handle *h, const LaunchRequest &req);                                  // api_run.hip: clothhip_run_actions_begin behind its argument list
 int run_actions_end_on_device(clothhip_handle *h);                                               // api_run.hip, for clothhip_plan_cem
+// api_run.hip: where a table of the last launch lies and its rows ([T * E], reset_obs [E * n_scripts]; either result may be NULL), or
+// CLOTHHIP_ESTATE when the record says it is not there. Does not ask whether a launch is in flight: check_idle
+int launch_table(const clothhip_handle *h, LaunchTable which, const void **d_ptr, int64_t *rows);
 }  // namespace clothhip
 #pragma GCC visibility pop

@@ -141,14 +141,12 @@ extern "C" int clothhip_render_obs(clothhip_handle *h, const ClothRenderParams *
     if (source < CLOTHHIP_OBS_STATE || source > CLOTHHIP_OBS_HOST) return fail(CLOTHHIP_EINVAL, "unknown observation source %d", source);
     if (n < 0) return fail(CLOTHHIP_EINVAL, "n < 0");
     if (source == CLOTHHIP_OBS_HOST && !obs_host && n > 0) return fail(CLOTHHIP_EINVAL, "CLOTHHIP_OBS_HOST needs obs_host[n][3P]");
+    int64_t n_src = source == CLOTHHIP_OBS_STATE ? (int64_t)h->E : n;
+    const void *d_table = nullptr;      // a table of the last launch, where it lies
     if (source == CLOTHHIP_OBS_SLOTS || source == CLOTHHIP_OBS_RESETS) {
         if (int rc = check_idle(h)) return rc;
-        if (h->epi.f_T < 1) return fail(CLOTHHIP_ESTATE, "no clothhip_run_actions launch yet");
-        if (source == CLOTHHIP_OBS_SLOTS && !h->epi.f_obs) return fail(CLOTHHIP_ESTATE, "the last clothhip_run_actions launch was not given want_obs");
-        if (source == CLOTHHIP_OBS_RESETS && !h->epi.f_robs) return fail(CLOTHHIP_ESTATE, "the last clothhip_run_actions launch was not given want_reset_obs");
+        if (int rc = launch_table(h, source == CLOTHHIP_OBS_SLOTS ? LaunchTable::obs : LaunchTable::reset_obs, &d_table, &n_src)) return rc;
     }
-    const int64_t n_src = source == CLOTHHIP_OBS_STATE ? (int64_t)h->E : source == CLOTHHIP_OBS_SLOTS ? (int64_t)h->epi.f_T * h->E
-                        : source == CLOTHHIP_OBS_RESETS ? (int64_t)h->epi.f_nscr : n;
     if (n != n_src) return fail(CLOTHHIP_EINVAL, "n = %lld, the source holds %lld cloths", (long long)n, (long long)n_src);
     const RenderPlan plan = render_plan(h->Ppad, p->width, p->height, h->dbg.render_lds_kib * 1024);
     if (!plan.fits) return fail(CLOTHHIP_EINVAL, "a one-row band of width %d needs %d B of LDS beside the %d-point grid", p->width, plan.lds, h->P);
@@ -169,7 +167,6 @@ extern "C" int clothhip_render_obs(clothhip_handle *h, const ClothRenderParams *
     a.src_stride = soa ? 3LL * h->Ppad : 3LL * h->P;
     a.depth = need_depth ? (float *)h->ro.d_ro_depth : nullptr;
     const unsigned wg_per_image = h->dbg.render_walk ? 1 : plan.bands;      // one workgroup per band, or one that walks them all
-    const float *d_table = source == CLOTHHIP_OBS_SLOTS ? (const float *)h->epi.d_fobs : source == CLOTHHIP_OBS_RESETS ? (const float *)h->epi.d_frobs : nullptr;
     HIPCHECK(hipFuncSetAttribute((const void *)k_render_obs<float, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIPCHECK(hipFuncSetAttribute((const void *)k_render_obs<float, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     HIPCHECK(hipFuncSetAttribute((const void *)k_render_obs<double, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -189,7 +186,7 @@ extern "C" int clothhip_render_obs(clothhip_handle *h, const ClothRenderParams *
                 hipLaunchKernelGGL((k_render_obs<T, false>), grid, dim3(256), plan.lds, h->stream, (const T *)h->d_pos + i0 * 3 * h->Ppad, a);
             });
         } else {
-            const float *rows = d_table ? d_table + i0 * 3 * h->P : (const float *)h->ro.d_ro_src;
+            const float *rows = d_table ? (const float *)d_table + i0 * 3 * h->P : (const float *)h->ro.d_ro_src;
             if (!d_table) HIPCHECK(hipMemcpyAsync(h->ro.d_ro_src, obs_host + i0 * 3 * h->P, m * 3 * h->P * 4, hipMemcpyHostToDevice, h->stream));
             hipLaunchKernelGGL((k_render_obs<float, true>), grid, dim3(256), plan.lds, h->stream, rows, a);
         }

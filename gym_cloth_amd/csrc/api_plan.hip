@@ -1,6 +1,6 @@
 // api_plan.hip -- the cross-entropy planner over forked cloths (clothhip.h: clothhip_plan_cem, clothhip_plan_sample, clothhip_plan_refit): the
-// only unit that sees the planner's kernels (cloth_plan.hpp). The loop is made of entries that exist -- clothhip_fork, clothhip_run_actions_begin
-// on a device-resident table -- and the two kernels; it ends each launch through run_actions_end_on_device (api_run.hip), so the records are
+// only unit that sees the planner's kernels (cloth_plan.hpp). The loop is made of entries that exist -- clothhip_fork, an episode launch (begin_launch)
+// on a device-resident table -- and the two kernels; it ends each launch through run_actions_end_on_device (both api_run.hip), so the records are
 // scored where they lie and nothing comes back from the device before the last iteration is done.
 #include <hip/hip_runtime.h>
 
@@ -146,7 +146,7 @@ extern "C" int clothhip_plan_cem(clothhip_handle *scratch, clothhip_handle *src,
     if (!(ep->reduce_factor > 0) || ep->max_actions < 1) return fail(CLOTHHIP_EINVAL, "bad episode parameters");
     if (int rc = check_act_bounds(ep->act_low, ep->act_high)) return rc;
     if (int rc = check_distribution(mean, sdev, done, E, H)) return rc;
-    if (src->epi.f_pending || scratch->epi.f_pending) return fail(CLOTHHIP_ESTATE, "a clothhip_run_actions_begin is in flight on the %s handle: call clothhip_run_actions_end first", src->epi.f_pending ? "source" : "scratch");
+    if (src->epi.last.pending || scratch->epi.last.pending) return fail(CLOTHHIP_ESTATE, "a clothhip_run_actions_begin is in flight on the %s handle: call clothhip_run_actions_end first", src->epi.last.pending ? "source" : "scratch");
     if (scratch->relaxed) return fail(CLOTHHIP_ESTATE, "clothhip_set_relaxed_order: the relaxed-order companion is a bench-only kernel, not a model to plan with");
     if (!fused_supported(*scratch)) return fail(CLOTHHIP_ESTATE, "n_side %d: the scratch handle's stepper variant cannot run episode launches (clothhip_fused_supported)", scratch->N);
     {
@@ -182,9 +182,10 @@ extern "C" int clothhip_plan_cem(clothhip_handle *scratch, clothhip_handle *src,
         double *d_s = (double *)P.d_scores + (size_t)it * EK;
         if (int rc = launch_sample(scratch, params, ep->act_low, ep->act_high, E, params->iter0 + (uint32_t)it, d_x)) return rc;
         if (int rc = clothhip_fork(scratch, idx.data(), src, idx.data() + EK, (int32_t)EK, 0)) return rc;
-        if (int rc = clothhip_run_actions_begin(scratch, ep, H, CLOTHHIP_POLICY_TABLE, d_x, 1, nullptr, nullptr, 0, steps_rep.data(), done_rep.data(),
-                                                nullptr, 0, 0, 0, 0, 0, 0.0))
-            return rc;
+        LaunchRequest req = next_request(scratch);
+        req.ep = ep; req.T = H; req.actions = d_x; req.actions_on_device = true;      // (the table policy, no resets, no optional outputs, no time slice)
+        req.num_steps = steps_rep.data(); req.done = done_rep.data();
+        if (int rc = begin_launch(scratch, req)) return rc;
         if (int rc = run_actions_end_on_device(scratch)) return rc;
         if (int rc = launch_refit(scratch, params, E, d_x, (const ClothStepRecord *)scratch->epi.d_frec, d_s, true, true, false, it == 0)) return rc;
     }

@@ -252,37 +252,38 @@ extern "C" int clothhip_run(clothhip_handle *h, const ClothSchedule *sched, int3
 }
 
 // ---- whole episodes on the device ---------------------------------------------------------------------------------
-template <typename T> static void fill_fused(clothhip_handle *h, FusedArgs<T> &f, const ClothEpisodeParams *ep, int T_, int policy,
-                                             const double *d_actions, bool have_parg, bool have_scripts, bool have_resets, bool have_obs,
-                                             bool have_robs, int n_scripts, uint64_t budget_ticks, bool have_mt, int rng_tier,
-                                             uint64_t domrand_words, int NS, int NH, int expert, bool resume_labelled) {
+static size_t reset_rows(const clothhip_handle *h, const LaunchRequest &req) { return (size_t)h->E * (size_t)(req.n_scripts > 0 ? req.n_scripts : 1); }
+
+// the kernel's argument block of a request that stage_launch has staged: every table the request names, where it lies on the device
+template <typename T> static void fill_fused(clothhip_handle *h, const LaunchRequest &req, FusedArgs<T> &f) {
+    const MetricsDims md = metrics_dims(h->P, h->Ppad);
     memset(&f, 0, sizeof(f));
-    f.nT = T_; f.policy = policy; f.NS = NS; f.NH = NH;
-    f.actions = d_actions;
-    f.policy_arg = have_parg ? h->epi.d_fparg : nullptr;
-    f.scripts = have_scripts ? (const ClothResetScript *)h->epi.d_fscr : nullptr;
+    f.nT = req.T; f.policy = req.policy; f.NS = md.NS; f.NH = md.NH;
+    f.actions = !req.action_table() ? nullptr : req.actions_on_device ? req.actions : (const double *)h->epi.d_fact;
+    f.policy_arg = req.policy_arg ? h->epi.d_fparg : nullptr;
+    f.scripts = req.reset_source == ResetSource::scripts ? (const ClothResetScript *)h->epi.d_fscr : nullptr;
     f.num_steps = h->epi.d_fsteps; f.done = h->epi.d_fdone;
     f.records = (ClothStepRecord *)h->epi.d_frec;
-    f.resets = have_resets ? (ClothResetRecord *)h->epi.d_frst : nullptr;
-    f.obs = have_obs ? (float *)h->epi.d_fobs : nullptr;
-    f.reset_obs = have_robs ? (float *)h->epi.d_frobs : nullptr;
+    f.resets = req.resets != TableMode::Absent ? (ClothResetRecord *)h->epi.d_frst : nullptr;
+    f.obs = req.obs != TableMode::Absent ? (float *)h->epi.d_fobs : nullptr;
+    f.reset_obs = req.reset_obs != TableMode::Absent ? (float *)h->epi.d_frobs : nullptr;
     f.flat = (const T *)h->d_flat;
     f.wt_ent = h->d_wt_ent;
     f.rest = (const T *)h->d_rest; f.rest_rw = (T *)h->d_rest; f.rest_stride = h->rest_stride;
     f.grid_dx = h->prm.width * 1.0 / (h->N - 1); f.grid_dy = h->prm.height * 1.0 / (h->N - 1);
-    f.levels = h->d_levels; f.n_glevels = h->n_grab_levels; f.E = h->E; f.n_scripts = n_scripts; f.budget_ticks = budget_ticks;
+    f.levels = h->d_levels; f.n_glevels = h->n_grab_levels; f.E = h->E; f.n_scripts = req.n_scripts; f.budget_ticks = req.budget_ticks;
     f.resume = h->epi.d_resume;
     f.op_ticks = h->epi.d_fticks;
     f.summary = h->epi.d_fsum;
-    f.mt = have_mt ? h->epi.d_fmt : nullptr; f.rng_tier = rng_tier; f.domrand_words = domrand_words;
+    f.mt = req.reset_source == ResetSource::rng ? h->epi.d_fmt : nullptr; f.rng_tier = req.rng_tier; f.domrand_words = req.domrand_words;
     f.two_thickness = 2 * h->prm.thickness; f.half_thickness = h->prm.thickness / 2.0;
-    f.ep = *ep;
+    f.ep = *req.ep;
     f.mlp = h->pol.mlp;
-    if (expert) {
-        f.expert = expert; f.resume_labelled = resume_labelled ? 1 : 0;
+    if (req.expert) {
+        f.expert = req.expert; f.resume_labelled = req.resume_labelled ? 1 : 0;
         f.labels = h->epi.d_flab;
-        f.expert_mix = h->epi.arm_mix ? (const uint8_t *)h->epi.d_fmix : nullptr;
-        f.expert_choice = expert == CLOTHHIP_POLICY_HIGHEST_POINT ? (const int32_t *)h->epi.d_fchoice : nullptr;
+        f.expert_mix = req.expert_mix ? (const uint8_t *)h->epi.d_fmix : nullptr;
+        f.expert_choice = req.expert == CLOTHHIP_POLICY_HIGHEST_POINT ? (const int32_t *)h->epi.d_fchoice : nullptr;
     }
 }
 
@@ -292,7 +293,7 @@ static bool known_expert(int32_t x) { return x == CLOTHHIP_POLICY_ORACLE_CORNER 
 extern "C" int clothhip_run_actions_expert(clothhip_handle *h, int32_t expert, int32_t T_, const uint8_t *mix, const int32_t *choice) {
     if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
     h->epi.arm_expert = 0;                              // whatever happens below, an earlier arming is gone
-    if (h->epi.f_pending) return fail(CLOTHHIP_ESTATE, "a clothhip_run_actions_begin is in flight: arm the expert before the launch");
+    if (h->epi.last.pending) return fail(CLOTHHIP_ESTATE, "a clothhip_run_actions_begin is in flight: arm the expert before the launch");
     if (!known_expert(expert)) return fail(CLOTHHIP_EINVAL, "unknown expert %d (CLOTHHIP_POLICY_ORACLE_CORNER or CLOTHHIP_POLICY_HIGHEST_POINT)", expert);
     if (T_ < 1 || T_ > 4096) return fail(CLOTHHIP_EINVAL, "T must be in [1, 4096]");
     if (expert == CLOTHHIP_POLICY_HIGHEST_POINT && !choice) return fail(CLOTHHIP_EINVAL, "the highest-point expert needs choice[T][E]: which of the highest points per slot");
@@ -311,14 +312,157 @@ extern "C" int clothhip_run_actions_expert(clothhip_handle *h, int32_t expert, i
 
 extern "C" int clothhip_run_actions_labels(clothhip_handle *h, double *labels, void **d_labels) {
     if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
-    if (h->epi.f_pending) return fail(CLOTHHIP_ESTATE, "a clothhip_run_actions_begin is in flight: call clothhip_run_actions_end first");
-    if (!h->epi.f_labels) return fail(CLOTHHIP_ESTATE, "the last episode launch on this handle was not armed with an expert (clothhip_run_actions_expert)");
-    if (d_labels) *d_labels = h->epi.d_flab;
+    if (h->epi.last.pending) return fail(CLOTHHIP_ESTATE, "a clothhip_run_actions_begin is in flight: call clothhip_run_actions_end first");
+    const void *d_lab = nullptr;
+    int64_t rows = 0;
+    if (int rc = launch_table(h, LaunchTable::labels, &d_lab, &rows)) return rc;
+    if (d_labels) *d_labels = const_cast<void *>(d_lab);
     if (labels) {
         HIPCHECK(hipSetDevice(h->device));
-        HIPCHECK(hipMemcpyAsync(labels, h->epi.d_flab, (size_t)h->epi.f_T * h->E * 4 * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCHECK(hipMemcpyAsync(labels, d_lab, (size_t)rows * 4 * 8, hipMemcpyDeviceToHost, h->stream));
         HIPCHECK(hipStreamSynchronize(h->stream));
     }
+    return 0;
+}
+
+// ---- one episode launch: a request (api_handle.hpp), its refusals, its staging, the launch and its record ---------------------------------
+// an arming (clothhip_run_actions_expert) is for the next request alone, whatever becomes of it
+LaunchRequest clothhip::next_request(clothhip_handle *h) {
+    LaunchRequest req;
+    req.expert = h->epi.arm_expert; req.expert_mix = h->epi.arm_mix;
+    req.resume_labelled = h->epi.last.armed;
+    h->epi.arm_expert = 0;
+    return req;
+}
+static TableMode table_mode(int32_t want) { return want == 0 ? TableMode::Absent : want == 2 ? TableMode::Keep : TableMode::Download; }
+static uint64_t budget_ticks(double time_budget_ms) { return time_budget_ms > 0 ? (uint64_t)(time_budget_ms * 1e5) : 0; }      // s_memrealtime: 100 MHz
+
+// What a request is refused for before any table on the device is touched, in the order these refusals always had (two more come later,
+// each where it always stood: one in stage_launch, one in begin_launch).
+static int check_launch(clothhip_handle *h, const LaunchRequest &req) {
+    const int T_ = req.T, policy = req.policy, expert = req.expert;
+    const bool have_src = req.reset_source != ResetSource::none, tier2 = req.tier2();
+    if (!req.ep || !req.num_steps || !req.done) return fail(CLOTHHIP_EINVAL, "NULL argument");
+    if (h->epi.last.pending) return fail(CLOTHHIP_ESTATE, "a clothhip_run_actions_begin is already in flight");
+    if (expert && T_ != h->epi.arm_T) return fail(CLOTHHIP_EINVAL, "T = %d, the expert was armed for %d slots", T_, h->epi.arm_T);
+    if (expert && policy != CLOTHHIP_POLICY_TABLE && policy != CLOTHHIP_POLICY_MLP)
+        return fail(CLOTHHIP_EINVAL, "only CLOTHHIP_POLICY_TABLE and CLOTHHIP_POLICY_MLP may act beside an expert (policy %d)", policy);
+    if (expert && h->relaxed) return fail(CLOTHHIP_ESTATE, "clothhip_set_relaxed_order: the relaxed-order companion is a bench-only kernel without an expert");
+    if (T_ < 1 || T_ > 4096) return fail(CLOTHHIP_EINVAL, "T must be in [1, 4096]");
+    if (policy != CLOTHHIP_POLICY_TABLE && policy != CLOTHHIP_POLICY_ORACLE_CORNER && policy != CLOTHHIP_POLICY_HIGHEST_POINT && policy != CLOTHHIP_POLICY_MLP)
+        return fail(CLOTHHIP_EINVAL, "unknown policy %d", policy);
+    if (policy == CLOTHHIP_POLICY_MLP && h->pol.mlp.n_layers < 1) return fail(CLOTHHIP_ESTATE, "the MLP policy needs a network: call clothhip_set_policy_mlp or clothhip_set_policy_population first");
+    if (policy == CLOTHHIP_POLICY_MLP && h->relaxed)
+        return fail(CLOTHHIP_ESTATE, "clothhip_set_relaxed_order: the relaxed-order companion is a bench-only kernel without the MLP policy");
+    if (policy == CLOTHHIP_POLICY_HIGHEST_POINT && !req.policy_arg)
+        return fail(CLOTHHIP_EINVAL, "the highest-point policy needs policy_arg[1 + T][E] (construction codes + which of the highest points per slot)");
+    if (policy == CLOTHHIP_POLICY_TABLE && !req.actions) return fail(CLOTHHIP_EINVAL, "the table policy needs actions[T][E][4]");
+    if (policy == CLOTHHIP_POLICY_ORACLE_CORNER && h->N != 25)
+        return fail(CLOTHHIP_ESTATE, "the oracle-corner policy is defined for 25x25 cloths only (analytic.py:106)");
+    if (have_src && (req.n_scripts < 1 || req.n_scripts > 255)) return fail(CLOTHHIP_EINVAL, "n_scripts must be in [1, 255]");
+    if (req.two_reset_sources) return fail(CLOTHHIP_EINVAL, "resets come either from scripts or from the device-side RNG streams, not both");
+    if (req.reset_source == ResetSource::rng && (req.rng_tier < 1 || req.rng_tier > 3)) return fail(CLOTHHIP_EINVAL, "rng_tier must be 1, 2 or 3");
+    if (have_src && !tier2 && h->rest_stride != 0)
+        return fail(CLOTHHIP_ESTATE, "in-kernel resets of the flat tiers need the shared flat rest table; this handle has per-env rest lengths");
+    if (tier2 && h->rest_stride == 0)
+        return fail(CLOTHHIP_ESTATE, "in-kernel tier-2 resets rebuild per-env rest lengths; upload per-env rest tables first (clothhip_set_state without CLOTHHIP_REST_SHARED)");
+    if (tier2 && (size_t)3 * h->P * 8 > (size_t)160 * 1024) return fail(CLOTHHIP_ESTATE, "grid too large for the tier-2 reset scratch");
+    if (!(req.ep->reduce_factor > 0) || req.ep->max_actions < 1) return fail(CLOTHHIP_EINVAL, "bad episode parameters");
+    if (h->relaxed && h->n_mixed)
+        return fail(CLOTHHIP_ESTATE, "clothhip_set_relaxed_order: the relaxed-order companion is a bench-only kernel; this handle holds per-env materials (clothhip_set_material)");
+    HIPCHECK(hipSetDevice(h->device));
+    // which of the handle's two layouts runs now (may synchronise and read the rest table back: long before the timed events). A side
+    // effect among the checks, and it stays here: the scratch checks below are against THAT layout, not the previous launch's
+    if (int rc = lean_refresh(h)) return rc;
+    if (h->lay().scratch_have < h->lay().scratch_need)
+        return fail(CLOTHHIP_ESTATE, "n_side %d: the in-kernel metrics need %d B of LDS scratch, this variant has %d", h->N, h->lay().scratch_need, h->lay().scratch_have);
+    if (policy == CLOTHHIP_POLICY_MLP && h->lay().scratch_have < MLP_SCRATCH_BYTES)
+        return fail(CLOTHHIP_ESTATE, "n_side %d: the MLP policy's hidden vectors need %d B of LDS scratch, this variant has %d", h->N, MLP_SCRATCH_BYTES, h->lay().scratch_have);
+    return 0;
+}
+
+// Reserve, upload and clear every table the request names, and the kernel's argument block. Two things happen on the way, each in the
+// place it always had: the previous launch's observation tables stop being readable, and the one refusal that comes after that.
+static int stage_launch(clothhip_handle *h, const LaunchRequest &req) {
+    const int expert = req.expert;
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    const size_t E = h->E, nrec = (size_t)req.T * E, nscr = reset_rows(h, req);
+    if (int rc = h->epi.d_fz.reserve(1024)) return rc;
+    if (int rc = h->epi.d_fsteps.reserve(E * 4)) return rc;
+    if (int rc = h->epi.d_fdone.reserve(E)) return rc;
+    if (int rc = h->epi.d_fticks.reserve(E * 64)) return rc;
+    if (int rc = h->epi.d_fsum.reserve(E * 32)) return rc;
+    HIPCHECK(hipMemsetAsync(h->epi.d_fticks, 0, E * 64, h->stream));
+    if (int rc = h->epi.d_frec.reserve(nrec * sizeof(ClothStepRecord))) return rc;
+    if (int rc = h->epi.d_fscr.reserve(nscr * sizeof(ClothResetScript))) return rc;
+    if (int rc = h->epi.d_frst.reserve(nscr * sizeof(ClothResetRecord))) return rc;
+    if (req.action_table() && !req.actions_on_device) {
+        if (int rc = h->epi.d_fact.reserve(nrec * 4 * 8)) return rc;
+        HIPCHECK(hipMemcpyAsync(h->epi.d_fact, req.actions, nrec * 4 * 8, hipMemcpyHostToDevice, h->stream));
+    }
+    // from here on the previous launch's observation tables may be reallocated or overwritten: they stop being readable now, also if this
+    // call fails further down (launch_table then refuses them)
+    h->epi.last.invalidate_obs_tables();
+    if (req.obs != TableMode::Absent) if (int rc = h->epi.d_fobs.reserve(nrec * 3 * h->P * 4)) return rc;
+    // (a refusal behind the invalidation, and it stays there: a launch refused here has taken the tables with it, as clothhip.h says)
+    if ((req.reset_obs != TableMode::Absent || req.resets != TableMode::Absent) && req.reset_source == ResetSource::none)
+        return fail(CLOTHHIP_EINVAL, "reset outputs without a reset source");
+    if (req.reset_obs != TableMode::Absent) {
+        if (int rc = h->epi.d_frobs.reserve(nscr * 3 * h->P * 4)) return rc;
+        HIPCHECK(hipMemsetAsync(h->epi.d_frobs, 0, nscr * 3 * h->P * 4, h->stream));
+    }
+    if (req.reset_source == ResetSource::rng) {
+        if (int rc = h->epi.d_fmt.reserve(E * MT_WORDS * 4)) return rc;
+        HIPCHECK(hipMemcpyAsync(h->epi.d_fmt, req.reset_data, E * MT_WORDS * 4, hipMemcpyHostToDevice, h->stream));
+    }
+    if (req.policy_arg) {
+        const size_t nb = (req.policy == CLOTHHIP_POLICY_HIGHEST_POINT ? (size_t)(1 + req.T) : (size_t)1) * E * 4;
+        if (int rc = h->epi.d_fparg.reserve(nb)) return rc;
+        HIPCHECK(hipMemcpyAsync(h->epi.d_fparg, req.policy_arg, nb, hipMemcpyHostToDevice, h->stream));
+    }
+    if (expert) {                                       // labels start as all-ones NaNs: a slot without an action keeps them
+        if (int rc = h->epi.d_flab.reserve(nrec * 4 * 8)) return rc;
+        HIPCHECK(hipMemsetAsync(h->epi.d_flab, 0xFF, nrec * 4 * 8, h->stream));
+        if (req.expert_mix) {
+            if (int rc = h->epi.d_fmix.reserve(nrec)) return rc;
+            HIPCHECK(hipMemcpyAsync(h->epi.d_fmix, h->epi.h_arm_mix.data(), nrec, hipMemcpyHostToDevice, h->stream));
+        }
+        if (expert == CLOTHHIP_POLICY_HIGHEST_POINT) {
+            if (int rc = h->epi.d_fchoice.reserve(nrec * 4)) return rc;
+            HIPCHECK(hipMemcpyAsync(h->epi.d_fchoice, h->epi.h_arm_choice.data(), nrec * 4, hipMemcpyHostToDevice, h->stream));
+        }
+    }
+    if (req.reset_source == ResetSource::scripts) HIPCHECK(hipMemcpyAsync(h->epi.d_fscr, req.reset_data, nscr * sizeof(ClothResetScript), hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipMemcpyAsync(h->epi.d_fsteps, req.num_steps, E * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipMemcpyAsync(h->epi.d_fdone, req.done, E, hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipMemsetAsync(h->epi.d_frec, 0, nrec * sizeof(ClothStepRecord), h->stream));
+    if (req.resets != TableMode::Absent) HIPCHECK(hipMemsetAsync(h->epi.d_frst, 0, nscr * sizeof(ClothResetRecord), h->stream));
+    static_assert(sizeof(FusedArgs<double>) <= 1024 && sizeof(FusedArgs<float>) <= 1024, "fused argument block");
+    unsigned char fzbuf[1024];
+    by_precision(h, [&](auto t) { fill_fused(h, req, *reinterpret_cast<FusedArgs<decltype(t)> *>(fzbuf)); });
+    HIPCHECK(hipMemcpyAsync(h->epi.d_fz, fzbuf, 1024, hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));          // fzbuf is on this stack frame
+    return 0;
+}
+
+int clothhip::begin_launch(clothhip_handle *h, const LaunchRequest &req) {
+    if (int rc = check_launch(h, req)) return rc;
+    if (int rc = stage_launch(h, req)) return rc;
+    // (the last refusal, behind the staging, and it stays there: it asks about the layout lean_refresh chose, after every other refusal)
+    if (h->relaxed && !(find_stepper(h->lay().v, 0, 3) && h->lay().cell_copy && !req.tier2() && req.policy != CLOTHHIP_POLICY_HIGHEST_POINT))
+        return fail(CLOTHHIP_ESTATE, "clothhip_set_relaxed_order: the relaxed-order companion exists for the eight-wave LEAN layout only (fp32, flat tiers, 25x25 class, <= 512 cloths)");
+    HIPCHECK(hipEventRecord(h->ev0, h->stream));
+    // (FUSED 2: the variant that also carries the tier-2 reset code and the cold policies; the relaxed-order companion is one launch)
+    const bool cold = req.tier2() || req.policy == CLOTHHIP_POLICY_HIGHEST_POINT || req.policy == CLOTHHIP_POLICY_MLP || req.expert != 0 || read_debug_knobs().cold_build;
+    if (int rc = launch_run(h, h->relaxed ? 3 : cold ? 2 : 1, h->d_sched, h->epi.d_fz, !h->relaxed && req.budget_ticks != 0)) return rc;
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipEventRecord(h->ev1, h->stream));
+    h->have_timing = true;
+    h->pending_exec = true;
+    LaunchRecord &r = h->epi.last;
+    r.T = req.T; r.reset_rows = reset_rows(h, req); r.pending = true;
+    r.resets = req.resets != TableMode::Absent; r.rng = req.reset_source == ResetSource::rng;
+    r.obs = req.obs; r.reset_obs = req.reset_obs; r.armed = req.expert != 0;
     return 0;
 }
 
@@ -329,142 +473,53 @@ extern "C" int clothhip_run_actions_begin(clothhip_handle *h, const ClothEpisode
                                           int32_t want_resets, int32_t want_obs, int32_t want_reset_obs,
                                           double time_budget_ms) {
     if (!h) return fail(CLOTHHIP_EINVAL, "NULL argument");
-    // an arming (clothhip_run_actions_expert) is for this call alone, whatever becomes of it
-    const int expert = h->epi.arm_expert;
-    const bool resume_labelled = h->epi.f_labels;       // the previous launch was armed: an action it cut left its label in EpResume
-    h->epi.arm_expert = 0;
-    if (!ep || !num_steps || !done) return fail(CLOTHHIP_EINVAL, "NULL argument");
-    if (h->epi.f_pending) return fail(CLOTHHIP_ESTATE, "a clothhip_run_actions_begin is already in flight");
-    if (expert && T_ != h->epi.arm_T) return fail(CLOTHHIP_EINVAL, "T = %d, the expert was armed for %d slots", T_, h->epi.arm_T);
-    if (expert && policy != CLOTHHIP_POLICY_TABLE && policy != CLOTHHIP_POLICY_MLP)
-        return fail(CLOTHHIP_EINVAL, "only CLOTHHIP_POLICY_TABLE and CLOTHHIP_POLICY_MLP may act beside an expert (policy %d)", policy);
-    if (expert && h->relaxed) return fail(CLOTHHIP_ESTATE, "clothhip_set_relaxed_order: the relaxed-order companion is a bench-only kernel without an expert");
-    const bool resets = want_resets != 0, obs = want_obs != 0, reset_obs = want_reset_obs != 0;
-    if (T_ < 1 || T_ > 4096) return fail(CLOTHHIP_EINVAL, "T must be in [1, 4096]");
-    if (policy != CLOTHHIP_POLICY_TABLE && policy != CLOTHHIP_POLICY_ORACLE_CORNER && policy != CLOTHHIP_POLICY_HIGHEST_POINT && policy != CLOTHHIP_POLICY_MLP)
-        return fail(CLOTHHIP_EINVAL, "unknown policy %d", policy);
-    if (policy == CLOTHHIP_POLICY_MLP && h->pol.mlp.n_layers < 1) return fail(CLOTHHIP_ESTATE, "the MLP policy needs a network: call clothhip_set_policy_mlp or clothhip_set_policy_population first");
-    if (policy == CLOTHHIP_POLICY_MLP && h->relaxed)
-        return fail(CLOTHHIP_ESTATE, "clothhip_set_relaxed_order: the relaxed-order companion is a bench-only kernel without the MLP policy");
-    if (policy == CLOTHHIP_POLICY_HIGHEST_POINT && !policy_arg)
-        return fail(CLOTHHIP_EINVAL, "the highest-point policy needs policy_arg[1 + T][E] (construction codes + which of the highest points per slot)");
-    if (policy == CLOTHHIP_POLICY_TABLE && !actions) return fail(CLOTHHIP_EINVAL, "the table policy needs actions[T][E][4]");
-    if (policy == CLOTHHIP_POLICY_ORACLE_CORNER && h->N != 25)
-        return fail(CLOTHHIP_ESTATE, "the oracle-corner policy is defined for 25x25 cloths only (analytic.py:106)");
-    if ((scripts || rng_states) && (n_scripts < 1 || n_scripts > 255)) return fail(CLOTHHIP_EINVAL, "n_scripts must be in [1, 255]");
-    if (scripts && rng_states) return fail(CLOTHHIP_EINVAL, "resets come either from scripts or from the device-side RNG streams, not both");
-    if (rng_states && (rng_tier < 1 || rng_tier > 3)) return fail(CLOTHHIP_EINVAL, "rng_tier must be 1, 2 or 3");
-    if (!scripts && !rng_states) n_scripts = 0;
-    const bool tier2 = rng_states && rng_tier == 2;
-    if ((scripts || rng_states) && !tier2 && h->rest_stride != 0)
-        return fail(CLOTHHIP_ESTATE, "in-kernel resets of the flat tiers need the shared flat rest table; this handle has per-env rest lengths");
-    if (tier2 && h->rest_stride == 0)
-        return fail(CLOTHHIP_ESTATE, "in-kernel tier-2 resets rebuild per-env rest lengths; upload per-env rest tables first (clothhip_set_state without CLOTHHIP_REST_SHARED)");
-    if (tier2 && (size_t)3 * h->P * 8 > (size_t)160 * 1024) return fail(CLOTHHIP_ESTATE, "grid too large for the tier-2 reset scratch");
-    if (!(ep->reduce_factor > 0) || ep->max_actions < 1) return fail(CLOTHHIP_EINVAL, "bad episode parameters");
-    if (h->relaxed && h->n_mixed)
-        return fail(CLOTHHIP_ESTATE, "clothhip_set_relaxed_order: the relaxed-order companion is a bench-only kernel; this handle holds per-env materials (clothhip_set_material)");
-    HIPCHECK(hipSetDevice(h->device));
-    // which of the handle's two layouts runs now (may synchronise and read the rest table back: long before the timed events) -- the
-    // scratch check below is against THAT layout, not the previous launch's
-    if (int rc = lean_refresh(h)) return rc;
-    if (h->lay().scratch_have < h->lay().scratch_need)
-        return fail(CLOTHHIP_ESTATE, "n_side %d: the in-kernel metrics need %d B of LDS scratch, this variant has %d", h->N, h->lay().scratch_need, h->lay().scratch_have);
-    if (policy == CLOTHHIP_POLICY_MLP && h->lay().scratch_have < MLP_SCRATCH_BYTES)
-        return fail(CLOTHHIP_ESTATE, "n_side %d: the MLP policy's hidden vectors need %d B of LDS scratch, this variant has %d", h->N, MLP_SCRATCH_BYTES, h->lay().scratch_have);
-    HIPCHECK(hipStreamSynchronize(h->stream));
-    const size_t E = h->E, nrec = (size_t)T_ * E;
-    if (int rc = h->epi.d_fz.reserve(1024)) return rc;
-    if (int rc = h->epi.d_fsteps.reserve(E * 4)) return rc;
-    if (int rc = h->epi.d_fdone.reserve(E)) return rc;
-    if (int rc = h->epi.d_fticks.reserve(E * 64)) return rc;
-    if (int rc = h->epi.d_fsum.reserve(E * 32)) return rc;
-    HIPCHECK(hipMemsetAsync(h->epi.d_fticks, 0, E * 64, h->stream));
-    if (int rc = h->epi.d_frec.reserve(nrec * sizeof(ClothStepRecord))) return rc;
-    const size_t nscr = E * (size_t)(n_scripts > 0 ? n_scripts : 1);
-    if (int rc = h->epi.d_fscr.reserve(nscr * sizeof(ClothResetScript))) return rc;
-    if (int rc = h->epi.d_frst.reserve(nscr * sizeof(ClothResetRecord))) return rc;
-    const double *d_actions = nullptr;
-    if (policy == CLOTHHIP_POLICY_TABLE || (policy == CLOTHHIP_POLICY_MLP && actions)) {      // (MLP: the optional noise table)
-        if (actions_on_device) d_actions = actions;
-        else {
-            if (int rc = h->epi.d_fact.reserve(nrec * 4 * 8)) return rc;
-            HIPCHECK(hipMemcpyAsync(h->epi.d_fact, actions, nrec * 4 * 8, hipMemcpyHostToDevice, h->stream));
-            d_actions = (const double *)h->epi.d_fact;
+    LaunchRequest req = next_request(h);                // (takes the arming here, before any refusal: also a call that fails consumes it)
+    req.ep = ep; req.T = T_; req.policy = policy;
+    req.actions = actions; req.actions_on_device = actions_on_device != 0; req.policy_arg = policy_arg;
+    req.reset_source = scripts ? ResetSource::scripts : rng_states ? ResetSource::rng : ResetSource::none;
+    req.reset_data = scripts ? (const void *)scripts : (const void *)rng_states;
+    req.two_reset_sources = scripts && rng_states;
+    req.n_scripts = scripts || rng_states ? n_scripts : 0; req.rng_tier = rng_tier; req.domrand_words = domrand_words;
+    req.num_steps = num_steps; req.done = done;
+    req.resets = want_resets ? TableMode::Download : TableMode::Absent; req.obs = table_mode(want_obs); req.reset_obs = table_mode(want_reset_obs);
+    req.budget_ticks = budget_ticks(time_budget_ms);
+    return begin_launch(h, req);
+}
+
+// Where a table of the last launch lies, or why it is not there: the one place that knows the record's rule and the tables' row counts.
+int clothhip::launch_table(const clothhip_handle *h, LaunchTable which, const void **d_ptr, int64_t *rows) {
+    const LaunchRecord &r = h->epi.last;
+    const void *p = nullptr;
+    int64_t n = (int64_t)r.T * h->E;
+    if (which == LaunchTable::labels) {
+        if (!r.armed) return fail(CLOTHHIP_ESTATE, "the last episode launch on this handle was not armed with an expert (clothhip_run_actions_expert)");
+        p = h->epi.d_flab;
+    } else {
+        if (r.T < 1) return fail(CLOTHHIP_ESTATE, "no clothhip_run_actions launch yet");
+        if (which == LaunchTable::obs) {
+            if (r.obs == TableMode::Absent) return fail(CLOTHHIP_ESTATE, "the last clothhip_run_actions launch was not given want_obs");
+            p = h->epi.d_fobs;
+        } else {
+            if (r.reset_obs == TableMode::Absent) return fail(CLOTHHIP_ESTATE, "the last clothhip_run_actions launch was not given want_reset_obs");
+            p = h->epi.d_frobs; n = (int64_t)r.reset_rows;
         }
     }
-    // from here on the previous launch's observation tables may be reallocated or overwritten: they stop being readable now, also if this
-    // call fails further down (clothhip_render_obs, clothhip_fit_hold and clothhip_fit_data_append_launch then refuse them)
-    h->epi.f_obs = h->epi.f_robs = false;
-    if (obs) if (int rc = h->epi.d_fobs.reserve(nrec * 3 * h->P * 4)) return rc;
-    if ((reset_obs || resets) && !scripts && !rng_states) return fail(CLOTHHIP_EINVAL, "reset outputs without a reset source");
-    if (reset_obs) {
-        if (int rc = h->epi.d_frobs.reserve(nscr * 3 * h->P * 4)) return rc;
-        HIPCHECK(hipMemsetAsync(h->epi.d_frobs, 0, nscr * 3 * h->P * 4, h->stream));
-    }
-    if (rng_states) {
-        if (int rc = h->epi.d_fmt.reserve(E * MT_WORDS * 4)) return rc;
-        HIPCHECK(hipMemcpyAsync(h->epi.d_fmt, rng_states, E * MT_WORDS * 4, hipMemcpyHostToDevice, h->stream));
-    }
-    if (policy_arg) {
-        const size_t nb = (policy == CLOTHHIP_POLICY_HIGHEST_POINT ? (size_t)(1 + T_) : (size_t)1) * E * 4;
-        if (int rc = h->epi.d_fparg.reserve(nb)) return rc;
-        HIPCHECK(hipMemcpyAsync(h->epi.d_fparg, policy_arg, nb, hipMemcpyHostToDevice, h->stream));
-    }
-    if (expert) {                                       // labels start as all-ones NaNs: a slot without an action keeps them
-        if (int rc = h->epi.d_flab.reserve(nrec * 4 * 8)) return rc;
-        HIPCHECK(hipMemsetAsync(h->epi.d_flab, 0xFF, nrec * 4 * 8, h->stream));
-        if (h->epi.arm_mix) {
-            if (int rc = h->epi.d_fmix.reserve(nrec)) return rc;
-            HIPCHECK(hipMemcpyAsync(h->epi.d_fmix, h->epi.h_arm_mix.data(), nrec, hipMemcpyHostToDevice, h->stream));
-        }
-        if (expert == CLOTHHIP_POLICY_HIGHEST_POINT) {
-            if (int rc = h->epi.d_fchoice.reserve(nrec * 4)) return rc;
-            HIPCHECK(hipMemcpyAsync(h->epi.d_fchoice, h->epi.h_arm_choice.data(), nrec * 4, hipMemcpyHostToDevice, h->stream));
-        }
-    }
-    if (scripts) HIPCHECK(hipMemcpyAsync(h->epi.d_fscr, scripts, nscr * sizeof(ClothResetScript), hipMemcpyHostToDevice, h->stream));
-    HIPCHECK(hipMemcpyAsync(h->epi.d_fsteps, num_steps, E * 4, hipMemcpyHostToDevice, h->stream));
-    HIPCHECK(hipMemcpyAsync(h->epi.d_fdone, done, E, hipMemcpyHostToDevice, h->stream));
-    HIPCHECK(hipMemsetAsync(h->epi.d_frec, 0, nrec * sizeof(ClothStepRecord), h->stream));
-    if (resets) HIPCHECK(hipMemsetAsync(h->epi.d_frst, 0, nscr * sizeof(ClothResetRecord), h->stream));
-    const uint64_t budget_ticks = time_budget_ms > 0 ? (uint64_t)(time_budget_ms * 1e5) : 0;      // s_memrealtime: 100 MHz
-    static_assert(sizeof(FusedArgs<double>) <= 1024 && sizeof(FusedArgs<float>) <= 1024, "fused argument block");
-    unsigned char fzbuf[1024];
-    const MetricsDims md = metrics_dims(h->P, h->Ppad);
-    by_precision(h, [&](auto t) {
-        fill_fused(h, *reinterpret_cast<FusedArgs<decltype(t)> *>(fzbuf), ep, T_, policy, d_actions, policy_arg != nullptr, scripts != nullptr, resets, obs, reset_obs, n_scripts,
-                   budget_ticks, rng_states != nullptr, rng_tier, domrand_words, md.NS, md.NH, expert, resume_labelled);
-    });
-    HIPCHECK(hipMemcpyAsync(h->epi.d_fz, fzbuf, 1024, hipMemcpyHostToDevice, h->stream));
-    HIPCHECK(hipStreamSynchronize(h->stream));          // fzbuf is on this stack frame
-    if (h->relaxed && !(find_stepper(h->lay().v, 0, 3) && h->lay().cell_copy && !tier2 && policy != CLOTHHIP_POLICY_HIGHEST_POINT))
-        return fail(CLOTHHIP_ESTATE, "clothhip_set_relaxed_order: the relaxed-order companion exists for the eight-wave LEAN layout only (fp32, flat tiers, 25x25 class, <= 512 cloths)");
-    HIPCHECK(hipEventRecord(h->ev0, h->stream));
-    // (FUSED 2: the variant that also carries the tier-2 reset code and the cold policies; the relaxed-order companion is one launch)
-    const int fused = h->relaxed ? 3 : (tier2 || policy == CLOTHHIP_POLICY_HIGHEST_POINT || policy == CLOTHHIP_POLICY_MLP || expert != 0 || read_debug_knobs().cold_build) ? 2 : 1;
-    if (int rc = launch_run(h, fused, h->d_sched, h->epi.d_fz, !h->relaxed && budget_ticks != 0)) return rc;
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipEventRecord(h->ev1, h->stream));
-    h->have_timing = true;
-    h->pending_exec = true;
-    h->epi.f_T = T_; h->epi.f_nscr = nscr; h->epi.f_resets = resets; h->epi.f_obs = obs; h->epi.f_robs = reset_obs; h->epi.f_mt = rng_states != nullptr;
-    h->epi.f_obs_kept = want_obs == 2; h->epi.f_robs_kept = want_reset_obs == 2;
-    h->epi.f_pending = true; h->epi.f_labels = expert != 0;
+    if (d_ptr) *d_ptr = p;
+    if (rows) *rows = n;
     return 0;
 }
 
 extern "C" int clothhip_run_actions_end(clothhip_handle *h, int32_t *num_steps, uint8_t *done, ClothStepRecord *records,
                                         ClothResetRecord *resets, float *obs, float *reset_obs, uint32_t *rng_states) {
     if (!h || !num_steps || !done || !records) return fail(CLOTHHIP_EINVAL, "NULL argument");
-    if (!h->epi.f_pending) return fail(CLOTHHIP_ESTATE, "no clothhip_run_actions_begin in flight");
+    const LaunchRecord &r = h->epi.last;
+    if (!r.pending) return fail(CLOTHHIP_ESTATE, "no clothhip_run_actions_begin in flight");
     // (a table announced with 2 stays on the device: no buffer for it)
-    if ((resets != nullptr) != h->epi.f_resets || (obs != nullptr) != (h->epi.f_obs && !h->epi.f_obs_kept) ||
-        (reset_obs != nullptr) != (h->epi.f_robs && !h->epi.f_robs_kept))
+    if ((resets != nullptr) != r.resets || (obs != nullptr) != (r.obs == TableMode::Download) || (reset_obs != nullptr) != (r.reset_obs == TableMode::Download))
         return fail(CLOTHHIP_EINVAL, "the output buffers must match the ones announced to clothhip_run_actions_begin");
-    if ((rng_states != nullptr) != h->epi.f_mt) return fail(CLOTHHIP_EINVAL, "rng_states must be given to both halves or to neither");
+    if ((rng_states != nullptr) != r.rng) return fail(CLOTHHIP_EINVAL, "rng_states must be given to both halves or to neither");
     HIPCHECK(hipSetDevice(h->device));
-    const size_t E = h->E, nrec = (size_t)h->epi.f_T * E, nscr = h->epi.f_nscr;
+    const size_t E = h->E, nrec = (size_t)r.T * E, nscr = r.reset_rows;
     HIPCHECK(hipMemcpyAsync(records, h->epi.d_frec, nrec * sizeof(ClothStepRecord), hipMemcpyDeviceToHost, h->stream));
     if (resets) HIPCHECK(hipMemcpyAsync(resets, h->epi.d_frst, nscr * sizeof(ClothResetRecord), hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(hipMemcpyAsync(num_steps, h->epi.d_fsteps, E * 4, hipMemcpyDeviceToHost, h->stream));
@@ -473,7 +528,7 @@ extern "C" int clothhip_run_actions_end(clothhip_handle *h, int32_t *num_steps, 
     if (reset_obs) HIPCHECK(hipMemcpyAsync(reset_obs, h->epi.d_frobs, nscr * 3 * h->P * 4, hipMemcpyDeviceToHost, h->stream));
     if (rng_states) HIPCHECK(hipMemcpyAsync(rng_states, h->epi.d_fmt, E * MT_WORDS * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(hipStreamSynchronize(h->stream));
-    h->epi.f_pending = false;
+    h->epi.last.pending = false;
     return 0;
 }
 
@@ -481,8 +536,8 @@ extern "C" int clothhip_run_actions_end(clothhip_handle *h, int32_t *num_steps, 
 // (clothhip_plan_cem scores epi.d_frec on the device): the launch is no longer in flight as far as the handle's state goes; its work is
 // still on the handle's stream, and whatever reads its tables is enqueued there after it. No wait, nothing crosses PCIe.
 int clothhip::run_actions_end_on_device(clothhip_handle *h) {
-    if (!h->epi.f_pending) return fail(CLOTHHIP_ESTATE, "no clothhip_run_actions_begin in flight");
-    h->epi.f_pending = false;
+    if (!h->epi.last.pending) return fail(CLOTHHIP_ESTATE, "no clothhip_run_actions_begin in flight");
+    h->epi.last.pending = false;
     return 0;
 }
 
@@ -513,11 +568,17 @@ extern "C" int clothhip_run_actions(clothhip_handle *h, const ClothEpisodeParams
                                     const ClothResetScript *scripts, int32_t n_scripts, int32_t *num_steps, uint8_t *done,
                                     ClothStepRecord *records, ClothResetRecord *resets, float *obs, float *reset_obs,
                                     double time_budget_ms) {
-    if (!records) { if (h) h->epi.arm_expert = 0; return fail(CLOTHHIP_EINVAL, "NULL argument"); }      // (also a call that fails here consumes an arming)
-    if (int rc = clothhip_run_actions_begin(h, ep, T_, policy, actions, actions_on_device, policy_arg, scripts, n_scripts,
-                                            num_steps, done, nullptr, 0, 0, resets != nullptr, obs != nullptr,
-                                            reset_obs != nullptr, time_budget_ms))
-        return rc;
+    if (!h) return fail(CLOTHHIP_EINVAL, "NULL argument");
+    LaunchRequest req = next_request(h);                // (also a call that fails below consumes an arming)
+    if (!records) return fail(CLOTHHIP_EINVAL, "NULL argument");
+    req.ep = ep; req.T = T_; req.policy = policy;
+    req.actions = actions; req.actions_on_device = actions_on_device != 0; req.policy_arg = policy_arg;
+    if (scripts) { req.reset_source = ResetSource::scripts; req.reset_data = scripts; req.n_scripts = n_scripts; }
+    req.num_steps = num_steps; req.done = done;
+    req.resets = resets ? TableMode::Download : TableMode::Absent; req.obs = obs ? TableMode::Download : TableMode::Absent;
+    req.reset_obs = reset_obs ? TableMode::Download : TableMode::Absent;
+    req.budget_ticks = budget_ticks(time_budget_ms);
+    if (int rc = begin_launch(h, req)) return rc;
     return clothhip_run_actions_end(h, num_steps, done, records, resets, obs, reset_obs, nullptr);
 }
 

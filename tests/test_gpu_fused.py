@@ -82,7 +82,7 @@ def test_accounting_stage_replays_a_real_launch_f64(device_rng):
     kept, end = {}, v.batch.run_actions_end
 
     def keeping_end():
-        nsteps, done_io = v.batch._fused[2], v.batch._fused[3]
+        nsteps, done_io = v.batch._launch.pending.num_steps, v.batch._launch.pending.done
         r = end()
         kept.update(rec=r[0].copy(), rst=r[1].copy(), nsteps=nsteps.copy(), done_io=done_io.copy())
         return r
