@@ -136,8 +136,10 @@ __global__ __launch_bounds__(NT, (Variant{(int)sizeof(T), NT, PPT, TAB, REST_REG
         }
         for (int h = tid; h < HT; h += NT) { hkey[h] = KEY_EMPTY; hco[h] = 0; }
         if (tid == 0) { misc[0] = tear_flag; misc[1] = 0; misc[2] = 0; misc[3] = 0; misc[4] = 0; misc[5] = 0; misc[6] = 0; misc[10] = 0x7fffffff; misc[11] = -1; misc[12] = 0; misc[13] = 0; misc[14] = 0; misc[20] = 0; misc[21] = 0; misc[22] = 0; misc[23] = 0; }
+        if constexpr (V.sweep_starts_early()) { if (tid == 0) misc[17] = 0; }      // [17] waves whose pre-pass has published (the early walk)
     };
     if (tid == 0) misc[15] = 0;
+    if constexpr (V.sweep_starts_early()) { if (tid == 0 && A.stats) A.stats[16 * e + 4] = 0; }     // early walks that gave up waiting for the pre-pass (0 unless something is broken)
     init_lds(A.tear[e], A.wt_ent, g_rest);
     if (LEAN64) {
         uint4 *d_ = reinterpret_cast<uint4 *>(smem + lay.lstc);
@@ -181,6 +183,11 @@ __global__ __launch_bounds__(NT, (Variant{(int)sizeof(T), NT, PPT, TAB, REST_REG
     constexpr bool SWEEP_LEAN = true;   // the production walk (strain_sweep_lean)
 #else
     constexpr bool SWEEP_LEAN = false;  // (the sweep-stamps and census builds instrument strain_sweep)
+#endif
+#if defined(CLOTHHIP_PHASE_STAMPS)
+    constexpr bool SWEEP_EARLY = false; // (the stamps builds time pre-pass and sweep apart)
+#else
+    constexpr bool SWEEP_EARLY = SWEEP_LEAN && V.sweep_starts_early();   // wave 0 walks from window 0 beside the pre-pass (substep_strain.inc.hpp)
 #endif
     constexpr bool SWEEP_AHEAD = V.sweep_read_ahead();
     (void)SWEEP_AHEAD;
@@ -361,7 +368,7 @@ __global__ __launch_bounds__(NT, (Variant{(int)sizeof(T), NT, PPT, TAB, REST_REG
             A.tear[e] = misc[0]; A.executed[e] = done;
             if (A.stats) {
                 A.stats[16 * e] = misc[15]; A.stats[16 * e + 1] = st_windows; A.stats[16 * e + 2] = st_passes; A.stats[16 * e + 3] = st_commits;
-                for (int q = 0; q < 12; q++) A.stats[16 * e + 4 + q] = (int)((unsigned long long)tph[q] >> 6);
+                for (int q = SWEEP_EARLY ? 1 : 0; q < 12; q++) A.stats[16 * e + 4 + q] = (int)((unsigned long long)tph[q] >> 6);     // (SWEEP_EARLY: [4] counts given-up waits)
 #ifndef CLOTHHIP_PHASE_STAMPS
                 unsigned long long tend;
                 asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tend)::"memory");

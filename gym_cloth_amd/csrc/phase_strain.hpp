@@ -190,10 +190,21 @@ __device__ __forceinline__ int strain_sweep(Pt<T> *cur, const WEnt<T> *wt, const
 // Same walk, same passes, same results as strain_sweep (tear_thresh >= 1.1 only: the caller keeps strain_sweep for the other case).
 // (AHEAD false -- the high-residency builds, whose other waves hide the latency: a window's particle records are read when the window starts,
 //  not a window ahead: sixteen registers fewer across the walk)
-template <typename T, bool LDS_TAB, bool STATS, bool AHEAD = true>
+//
+// EARLY (Variant::sweep_starts_early) with `early` set: the walk runs BESIDE the pre-pass, not behind it. It enters at window 0 with no end of
+// its own (w_end < w0) and walks on in grants of EARLY_GRANT windows -- a quiet window is always exact, ~154 cycles -- until the seven waves of
+// the pre-pass have counted themselves done in misc[17]; only then are misc[1] / [10] / [11] (any flag, first and last flagged slot) final, and:
+// w_end = max(w_end, last flagged window), and, the walk's own reach being used up, it continues at max(w, first flagged window). The words are looked
+// at ONLY on this cold edge, where the reach is used up (an LDS read the compiler cannot move drains the read-ahead); the two register sets are
+// loaded again behind it. At the table's end with the count still short the wave sleeps and polls, at most EARLY_WAIT_POLLS times (~2 M cycles,
+// five hundred pre-passes): then it leaves -- every window has been walked, the result is exact -- and says so in bit 1 of what it returns (the caller counts it in the env's stats). DESIGN.md 4.1: why the
+// result is the sequential loop's although the pre-pass reads records this walk is correcting.
+constexpr int EARLY_GRANT = 4, EARLY_WAIT_POLLS = 4096;
+template <typename T, bool LDS_TAB, bool STATS, bool AHEAD = true, bool EARLY = false>
 __device__ __forceinline__ int strain_sweep_lean(Pt<T> *cur, const WEnt<T> *wt, const uint32_t *g_ent, const T *g_rest,
                                                  const unsigned long long *g_dep, int w0, int w_end, int rshift, const DevConsts<T> &k,
-                                                 int lane, int &st_windows, int &st_passes, int &st_commits) {
+                                                 int lane, int &st_windows, int &st_passes, int &st_commits,
+                                                 bool early = false, int *misc = nullptr, int nW = 0) {
     static_assert(WT_PAD_WINDOWS >= 3, "the entry stream reads two windows ahead, the particle reads one");
     int tear = 0;
     T c11 = k.c11, tth = k.tear_thresh;              // spring-test constants pinned in VGPRs
@@ -296,13 +307,50 @@ __device__ __forceinline__ int strain_sweep_lean(Pt<T> *cur, const WEnt<T> *wt, 
         load(w + 2, c);                                             // this set is free: the entry of the window after next
     };
     Set S0, S1;
-    load(w, S0); load(w + 1, S1);
-    if (AHEAD) decode_read(S0);
-    for (;;) {
-        step(S0, S1);
-        if (++w > w_end) break;
-        step(S1, S0);
-        if (++w > w_end) break;
+    if constexpr (!EARLY) {
+        load(w, S0); load(w + 1, S1);
+        if (AHEAD) decode_read(S0);
+        for (;;) {
+            step(S0, S1);
+            if (++w > w_end) break;
+            step(S1, S0);
+            if (++w > w_end) break;
+        }
+    } else {
+        constexpr int NPRE = 7;                                     // waves 1-7 run the pre-pass
+        auto peek = [&](int i) -> int { return __builtin_amdgcn_readfirstlane(__hip_atomic_load(&misc[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)); };
+        auto done = [&]() -> bool { return __builtin_amdgcn_readfirstlane(__hip_atomic_load(&misc[17], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)) >= NPRE; };
+        (void)peek;
+        bool known = !early;                                        // the pre-pass's bounds are in [w0, w_end] already
+        if (early) w_end = (EARLY_GRANT < nW ? EARLY_GRANT : nW) - 1;
+        for (;;) {
+            load(w, S0); load(w + 1, S1);
+            if (AHEAD) decode_read(S0);
+            for (;;) {
+                step(S0, S1);
+                if (++w > w_end) break;
+                step(S1, S0);
+                if (++w > w_end) break;
+            }
+            // ---- the cold edge: the walk's reach is used up ----
+            if (known) break;
+            if (!done()) {
+                if (w < nW) { w_end = (w + EARLY_GRANT < nW ? w + EARLY_GRANT : nW) - 1; continue; }
+                int polls = 0;
+                bool d_;
+                do { __builtin_amdgcn_s_sleep(8); d_ = done(); } while (!d_ && ++polls < EARLY_WAIT_POLLS);
+                if (!d_) { tear |= 2; break; }                     // never in a healthy launch: bit 1 of the result, counted by the caller
+            }
+            known = true;
+#if !(defined(CLOTHHIP_MUTATE) && CLOTHHIP_MUTATE == 5)             // MUTANT 5 (tools/run_mutants.sh; never a product build): the walk stops at its own reach
+            if (peek(1) != 0) {
+                const int wf = peek(10) >> 6, wl = peek(11) >> 6;
+                w_end = wl > w_end ? wl : w_end;
+                w = wf > w ? wf : w;
+            }
+#endif
+            if (w > w_end) break;
+        }
     }
     return tear;
 }

@@ -62,6 +62,11 @@ struct Variant {
     // (2 N <= 54 for the 25x25 class this build exists for; behind `cur` the layout's own regions follow)
     constexpr bool lean_native_gather() const { return tsz == 4 && tab == TAB_LDS_SLOTS; }
     constexpr int cur_front_pad_records() const { return lean_native_gather() ? 64 : 0; }
+    // The same build's strain phase: wave 0 enters the walk at window 0 right behind the plane barrier while waves 1-7 run the pre-pass over ALL
+    // particles (lanes take t and t + 448, t = tid - 64), and learns the pre-pass's bounds only where its own reach is used up (DESIGN.md 4.1,
+    // phase_strain.hpp). Production walk only (strain_sweep_lean, tear_thresh >= 1.1); the profiling builds keep pre-pass, barrier, sweep.
+    constexpr bool sweep_starts_early() const { return lean_native_gather() && nt == 512 && ppt == 2; }
+    constexpr int early_prepass_threads() const { return nt - 64; }
     // the grid-specialised builds (cloth_common.hpp: spec_*): 50x50 at two cloths per CU has a hash table sized to the LDS left (not a power of
     // two); every specialised 25x25 layout but the builds for five / six per CU has the cell-ordered record copy
     constexpr bool spec_ht_fitted() const { return tab == TAB_LARGE_2; }

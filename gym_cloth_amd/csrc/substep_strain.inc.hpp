@@ -2,7 +2,8 @@
 // A FRAGMENT of k_run_schedule (episode_loop.hpp), included at its place in the kernel body: not a function. Turning the substep's phases into
 // __forceinline__ functions over a context struct was tried (round 5): same instructions, but the register allocation of the 128-VGPR variants
 // shifts -- three more scratch reloads in the substep loop, -1.4 % on the headline -- so the split is textual and the ISA is bit-identical to the
-// one-file kernel's. Names it uses from the kernel body: pm, Ak_, tid, lane, cur, misc, wtab, g_rest, pslot, gt, rr, vm, rc, lean_entry, lean_rest, rest_at, LEAN_NATIVE, st_*, tph / TSTAMP, mode (census build).
+// one-file kernel's. The pre-pass's particle test is a fragment of its own (substep_strain_prepass.inc.hpp), shared with the early walk's order
+// (substep_strain_early.inc.hpp, SWEEP_EARLY builds). Names it uses from the kernel body: pm, Ak_, tid, lane, cur, misc, wtab, g_rest, pslot, gt, rr, vm, rc, lean_entry, lean_rest, rest_at, LEAN_NATIVE, st_*, tph / TSTAMP, mode (census build).
         // ---- strain limit + tear (cloth.pyx:258-296) ---------------------------------------------------
         // (1) all threads: which springs would stretch/tear at the CURRENT positions? Only the first and the last of them
         //     (in window-table order) are kept: a spring untouched by earlier corrections of the sweep behaves exactly as
@@ -53,98 +54,25 @@
         } else
         if (pm & PH_STRAIN) {
             CLOTH_PHASE_ARGS()
+#ifdef CLOTHHIP_CELL_COUNTERS
+            int swept_ = 0;
+#endif
+            // SWEEP_EARLY (Variant::sweep_starts_early, the eight-wave fp32 LEAN build): wave 0 walks beside the pre-pass, substep_strain_early.inc.hpp.
+            // Every other build keeps the text below to the token (if constexpr: the other branch is not instantiated), and so its ISA.
+            if constexpr (SWEEP_EARLY) {
+#include "substep_strain_early.inc.hpp"
+            } else {
             {
                 // Every spring is tested once, by the owner of its ptB (the particle the reference appended it for):
                 // the owner holds the spring's gather entry (neighbour = ptA, table slot) and, with
                 // REST_REG, its rest length in registers, so the pre-pass needs one 16-byte LDS read per spring.
                 int nact = 0, pmin = 0x7fffffff, pmax = -1;     // flagged springs; the first / last of them in table order
-#pragma unroll
-                for (int q = 0; q < PPT; q++) {
-                    if (tid + q * NT < P) {
-                        const Pt<T> me = cur[tid + q * NT];
-                        const uint32_t cme_ = w_cnt(me.w);
-                        uint32_t gl[HK_SLOTS / 2];
-                        int iq_ = tid + q * NT; uint4 lw_ = uint4{0u, 0u, 0u, 0u}; if constexpr (LEAN64) lw_ = lstc[iq_]; uint32_t vq_ = LEAN64 ? lw_.x : vm[(LEAN && !LEAN64) ? q : 0];
-                        if (LEAN) asm volatile("" : "+v"(iq_), "+v"(vq_));
-                        // LEAN_NATIVE, as in the Hooke phase: the owner's address + the position's offset, valid = bit sl of the mask
-#pragma unroll
-                        for (int sl = 0; sl < HK_SLOTS / 2; sl++)
-                            gl[sl] = LEAN_NATIVE ? 0u : LEAN ? lean_entry(iq_, vq_, sl) : (GT_REG ? gt[GT_REG ? q : 0][sl] : Ak_->gather[sl * Ppad + tid + q * NT]);
-                        // software pipeline, as in the Hooke phase: two neighbour reads in flight ahead of the test
-                        constexpr int PP_AHEAD = 2;
-                        Pt<T> nbq[PP_AHEAD];
-#pragma unroll
-                        for (int sl = 0; sl < PP_AHEAD; sl++) {
-                            if constexpr (LEAN_NATIVE) nbq[sl] = cur[iq_ + lean_off(sl, KA_N(Ak_))];
-                            else {
-                            uint32_t g = gl[sl];
-                            asm volatile("" : "+v"(g));
-                            gl[sl] = g;
-                            nbq[sl] = cur[g & HK_NBR_MASK];
-                            }
-                        }
-                        // (a) branch-free: which of the six springs come within the slack band of their limit at all?
-                        uint32_t cand = 0u;
-                        T l2s[HK_SLOTS / 2];
-#pragma unroll
-                        for (int sl = 0; sl < HK_SLOTS / 2; sl++) {       // own springs come first in ascending list order
-                            const uint32_t g = gl[sl];
-                            const Pt<T> nb = nbq[sl % PP_AHEAD];
-                            if (sl + PP_AHEAD < HK_SLOTS / 2) {
-                                if constexpr (LEAN_NATIVE) nbq[sl % PP_AHEAD] = cur[iq_ + lean_off(sl + PP_AHEAD, KA_N(Ak_))];
-                                else {
-                                uint32_t gn = gl[sl + PP_AHEAD];
-                                asm volatile("" : "+v"(gn));
-                                gl[sl + PP_AHEAD] = gn;
-                                nbq[sl % PP_AHEAD] = cur[gn & HK_NBR_MASK];
-                                }
-                            }
-                            __builtin_amdgcn_sched_barrier(0);
-                            T r = LEAN64 ? lean_rest64(sl, lw_) : LEAN ? lean_rest(sl) : (REST_R ? rr[REST_R ? q : 0][sl] : rest_at((g >> HK_POS_SHIFT) & HK_POS_MASK));
-                            asm volatile("" : "+v"(r));     // or the thresholds below are hoisted out of the substep loop
-                                                            // for all 18 springs and live in scratch
-                            const T dx = nb.x - me.x, dy = nb.y - me.y, dz = nb.z - me.z;   // (ptA - ptB), as :270
-                            const T len2 = sumsq<T>(dx, dy, dz);
-                            l2s[sl] = len2;
-                            const T t11 = r * k.c11, tt = r * k.tear_thresh;
-                            const T tmin = t11 < tt ? t11 : tt;
-#if defined(CLOTHHIP_MUTATE) && CLOTHHIP_MUTATE == 4       // MUTANT 4 (see strain_sweep_lean): the pre-pass flags both-pinned springs too
-                            const bool pre = (LEAN_NATIVE ? (vq_ & (1u << sl)) != 0u : (g & (HK_VALID | HK_ASB)) == (HK_VALID | HK_ASB)) &
-                                             (len2 > tmin * tmin * ((T)1 - filt_slack<T>()));
-#else
-                            const bool pre = (LEAN_NATIVE ? (vq_ & (1u << sl)) != 0u : (g & (HK_VALID | HK_ASB)) == (HK_VALID | HK_ASB)) &
-                                             !((cme_ != 0) & (w_cnt(nb.w) != 0)) &
-                                             (len2 > tmin * tmin * ((T)1 - filt_slack<T>()));
-#endif
-                            cand |= pre ? (1u << sl) : 0u;
-                        }
-                        // (b) those few: inside the slack band around the limit the sweep's exact test (:270-275) decides: a
-                        // spring that sits exactly ON its limit (left there by an earlier substep's correction) is then not
-                        // flagged, and a cloth at rest skips the sweep altogether
-                        if (cand) {
-#pragma unroll
-                            for (int sl = 0; sl < HK_SLOTS / 2; sl++) {
-                                if (cand & (1u << sl)) {
-                                    // (LEAN: the spring's table slot is read from the gather table only now that it is needed: the table
-                                    //  is compacted, the sl-th stencil position is the particle's popcount(valid below sl)-th entry)
-                                    const uint32_t pos_ = V.has_point_slots() ? (uint32_t)pslot[sl * Ppad + iq_] : ((LEAN ? Ak_->gather[__popc(vq_ & ((1u << sl) - 1u)) * Ppad + iq_] : gl[sl])      // (the opaque copies: nothing of this is hoisted out of the substep loop and held)
-                                                           >> HK_POS_SHIFT) & HK_POS_MASK;
-                                    T r = LEAN64 ? lean_rest64(sl, lw_) : LEAN ? lean_rest(sl) : (REST_R ? rr[REST_R ? q : 0][sl] : rest_at(pos_));
-                                    asm volatile("" : "+v"(r));
-                                    const T len2 = l2s[sl];
-                                    const T t11 = r * k.c11, tt = r * k.tear_thresh;
-                                    const T tmin = t11 < tt ? t11 : tt;
-                                    bool flag = len2 > tmin * tmin * ((T)1 + filt_slack<T>());
-                                    if (!flag) { const T len = dev_sqrt<T>(len2); flag = len > t11 || len > tt; }
-                                    if (flag) { nact++; pmin = (int)pos_ < pmin ? (int)pos_ : pmin; pmax = (int)pos_ > pmax ? (int)pos_ : pmax; }
-#ifdef CLOTHHIP_CELL_COUNTERS
-                                    if (flag) atomicOr(&misc[13 + (((int)pos_ >> 6) >> 5 & 1)], 1 << (((int)pos_ >> 6) & 31));
-#endif
-                                }
-                            }
-                        }
-                    }
-                }
+// (no parentheses around the index: the tokens, and so the ISA, of the builds that keep this order are the one-file text's)
+#define PP_IDX_(q_) tid + (q_) * NT
+#define PP_MASK_(q_)
+#include "substep_strain_prepass.inc.hpp"
+#undef PP_IDX_
+#undef PP_MASK_
                 if (__any(nact)) {
                     const int min_ = __builtin_amdgcn_readlane(wave_incl_min(pmin), 63);         // DPP: no LDS round trips
                     const int max_ = -__builtin_amdgcn_readlane(wave_incl_min(-pmax), 63);
@@ -153,9 +81,6 @@
             }
             __syncthreads();
             TSTAMP(8)
-#ifdef CLOTHHIP_CELL_COUNTERS
-            int swept_ = 0;
-#endif
             if (tid < 64 && (misc[1] || (pm & PH_NOSKIP))) {
                 __builtin_amdgcn_s_setprio(3);            // the serial sweep is the critical path of the whole cloth
                 const bool all_ = (pm & PH_NOSKIP) != 0;
@@ -167,6 +92,9 @@
 #ifdef CLOTHHIP_CELL_COUNTERS
                 const unsigned long long fmask_ = (unsigned long long)(uint32_t)misc[13] | ((unsigned long long)(uint32_t)misc[14] << 32);
                 swept_ = 1;
+                // census: where the walk starts. Sixteen stats words per env hold no histogram, so env e counts the sweeps whose first
+                // flagged window is (e mod 64), in the upper half of counter 0's word (tools/cell_counters.py puts the envs together)
+                if (w0 == (e & 63)) tph[0] += 1ull << 22;
 #else
                 const unsigned long long fmask_ = 0ull;
 #endif
@@ -184,6 +112,7 @@
                 __builtin_amdgcn_s_setprio(0);
             }
             __syncthreads();
+            }
 #ifndef CLOTHHIP_SWEEP_STAMPS          // (that build uses slots 9-11 for the sweep's passes)
             TSTAMP(9)
 #endif
