@@ -67,10 +67,18 @@ __device__ __forceinline__ void metrics_block(const Src &src, int P, int NS, int
             if (i < P) {
                 double z;
                 src(i, x, y, z);
+#if defined(CLOTHHIP_MUTATE) && CLOTHHIP_MUTATE == 8
+                nlow += z <= half_thick ? 1 : 0;                    // MUTANT 8 (tools/run_mutants.sh; never a product build): cloth_env.py:606 counts z < thickness/2
+#else
                 nlow += z < half_thick ? 1 : 0;
+#endif
                 mnx = fmin(mnx, x); mxx = fmax(mxx, x); mny = fmin(mny, y); mxy = fmax(mxy, y);
                 mnz = fmin(mnz, z); mxz = fmax(mxz, z); sum += z;
+#if defined(CLOTHHIP_MUTATE) && CLOTHHIP_MUTATE == 9
+                x = fmin(fmax(x, 0.0), 1.0);                        // MUTANT 9 (tools/run_mutants.sh; never a product build): y is not clipped
+#else
                 x = fmin(fmax(x, 0.0), 1.0); y = fmin(fmax(y, 0.0), 1.0);                         // cloth_env.py:629
+#endif
             }
             sx[i] = (K)x; sy[i] = (K)y;
         }
@@ -110,7 +118,11 @@ __device__ __forceinline__ void metrics_block(const Src &src, int P, int NS, int
             for (int t = tid; t < (NS >> 1); t += NT) {
                 const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
                 const K ax = sx[i], ay = sy[i], bx = sx[l], by = sy[l];
+#if defined(CLOTHHIP_MUTATE) && CLOTHHIP_MUTATE == 6
+                const bool gt = ax > bx;                            // MUTANT 6 (tools/run_mutants.sh; never a product build): the sort drops its y tie-break
+#else
                 const bool gt = ax > bx || (ax == bx && ay > by);
+#endif
                 if (gt == ((i & kk) == 0)) { sx[i] = bx; sy[i] = by; sx[l] = ax; sy[l] = ay; }
             }
         }
@@ -121,8 +133,14 @@ __device__ __forceinline__ void metrics_block(const Src &src, int P, int NS, int
         const int *nl = reinterpret_cast<const int *>(red + 32);
         red[43] = (double)(nl[0] + nl[1] + nl[2] + nl[3]);
         const double slack = 0.25;                                                             // cloth_env.py:1031-1036
+#if defined(CLOTHHIP_MUTATE) && CLOTHHIP_MUTATE == 7
+        // MUTANT 7 (tools/run_mutants.sh; never a product build): the upper x / y bound is exclusive (cloth_env.py:1031, :1033 have >=)
+        red[42] = (vals[1] > 1.0 + slack || vals[0] < -slack || vals[3] > 1.0 + slack || vals[2] < -slack ||
+                   vals[5] >= 1.0 || vals[4] < 0) ? 1.0 : 0.0;
+#else
         red[42] = (vals[1] >= 1.0 + slack || vals[0] < -slack || vals[3] >= 1.0 + slack || vals[2] < -slack ||
                    vals[5] >= 1.0 || vals[4] < 0) ? 1.0 : 0.0;
+#endif
         // dedupe (in place), then Andrew's monotone chain exactly as clothhip_hull_area
         int m = 0;
         for (int i = 0; i < P; i++)
