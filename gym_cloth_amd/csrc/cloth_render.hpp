@@ -12,8 +12,13 @@
 //                smooth-shaded two-sided Lambert colour; nearest fragment wins through a 64-bit atomicMax on
 //                (depth key << 32 | rgb)
 //   resolve   -> uint8 RGB [H][W][3] and float camera-space depth [H][W] (background: the bed plane z = 0)
-// It does not try to reproduce Blender's pixels (no renderer to compare with exists outside Blender); what it is pinned to is
-// oracle/render_oracle.py, a numpy restatement of exactly these rules in float32, bit for bit (tests/test_gpu_render.py).
+// It does not try to reproduce Blender's pixels (no renderer to compare with exists outside Blender). Two things pin it:
+//   the RULES  oracle/render_exact.py states them geometrically and computes them exactly (integers over a power of two) from the
+//              float32 inputs: coverage with the top-left tie rule, the winning face, side, perspective-correct depth, colour within a
+//              derived window -- at every grid class, on hand-made states whose vertices and edges sit on pixel centres, across the
+//              image borders, behind the camera, folded, degenerate (tests/test_gpu_render_exact.py; zero tolerance where float32 is exact)
+//   the BITS   oracle/render_oracle.py restates these expressions in numpy float32, bit for bit (tests/test_gpu_render.py); being the
+//              same expressions, it cannot tell a wrong rule from a right one -- that is the exact reference's part
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -120,18 +125,31 @@ __global__ __launch_bounds__(256) void k_render(const T *pos, RenderArgs A) {
         const float iw0 = 1.0f / vd[a], iw1 = 1.0f / vd[b], iw2 = 1.0f / vd[c];
         for (int iy = iy0; iy <= iy1; iy++)
             for (int ix = ix0; ix <= ix1; ix++) {
+#if defined(CLOTHHIP_MUTATE) && CLOTHHIP_MUTATE == 12
+                const float fxp = (float)ix + 0.0f, fyp = (float)iy + 0.0f;   // MUTANT 12 (tools/run_mutants.sh; never a product build): the pixel corner, not its centre
+#else
                 const float fxp = (float)ix + 0.5f, fyp = (float)iy + 0.5f;
+#endif
                 const float e0 = s * ((x2 - x1) * (fyp - y1) - (y2 - y1) * (fxp - x1));   // opposite vertex a
                 const float e1 = s * ((x0 - x2) * (fyp - y2) - (y0 - y2) * (fxp - x2));   // opposite vertex b
                 const float e2 = s * ((x1 - x0) * (fyp - y0) - (y1 - y0) * (fxp - x0));   // opposite vertex c
-                // top-left rule on exact zeros: an edge owns its pixels if it is a top or a left edge
-                const bool in0 = e0 > 0.0f || (e0 == 0.0f && ((s * (y2 - y1) > 0.0f) || (y2 == y1 && s * (x2 - x1) < 0.0f)));
-                const bool in1 = e1 > 0.0f || (e1 == 0.0f && ((s * (y0 - y2) > 0.0f) || (y0 == y2 && s * (x0 - x2) < 0.0f)));
-                const bool in2 = e2 > 0.0f || (e2 == 0.0f && ((s * (y1 - y0) > 0.0f) || (y1 == y0 && s * (x1 - x0) < 0.0f)));
+                // top-left rule on exact zeros, in image coordinates (y down): an edge owns the centres on it if the face lies to its right (a left
+                // edge: e grows with x, s * (y1 - y2) > 0), or, if it is horizontal, below it (a top edge: e grows with y, s * (x2 - x1) > 0)
+#if defined(CLOTHHIP_MUTATE) && CLOTHHIP_MUTATE == 10
+                const bool in0 = e0 > 0.0f || (e0 == 0.0f && ((s * (y2 - y1) > 0.0f) || (y2 == y1 && s * (x2 - x1) < 0.0f)));   // MUTANT 10 (tools/run_mutants.sh; never a product build): e0 owns its right / bottom ties
+#else
+                const bool in0 = e0 > 0.0f || (e0 == 0.0f && ((s * (y2 - y1) < 0.0f) || (y2 == y1 && s * (x2 - x1) > 0.0f)));
+#endif
+                const bool in1 = e1 > 0.0f || (e1 == 0.0f && ((s * (y0 - y2) < 0.0f) || (y0 == y2 && s * (x0 - x2) > 0.0f)));
+                const bool in2 = e2 > 0.0f || (e2 == 0.0f && ((s * (y1 - y0) < 0.0f) || (y1 == y0 && s * (x1 - x0) > 0.0f)));
                 if (!(in0 && in1 && in2)) continue;
                 const float sa = s * area;
                 const float b0 = e0 / sa, b1 = e1 / sa, b2 = e2 / sa;
+#if defined(CLOTHHIP_MUTATE) && CLOTHHIP_MUTATE == 11
+                const float inv_d = 1.0f / (b0 * vd[a] + b1 * vd[b] + b2 * vd[c]);             // MUTANT 11 (tools/run_mutants.sh; never a product build): depth mixed affinely
+#else
                 const float inv_d = b0 * iw0 + b1 * iw1 + b2 * iw2;                        // perspective-correct 1/depth
+#endif
                 const float inten = b0 * vi[a] + b1 * vi[b] + b2 * vi[c];
                 const unsigned long long key = ((unsigned long long)depth_key(inv_d) << 32) | (quant8(col[0] * inten) << 16) |
                                                (quant8(col[1] * inten) << 8) | quant8(col[2] * inten);

@@ -9,6 +9,8 @@
 //     culled against the band by their bounding box, and fragments merge with the LDS 64-bit max. No z-buffer in global memory
 //     and no global atomic per fragment: k_render's 8 B per pixel per image of hipMalloc'ed scratch is what keeps it from
 //     rendering thousands of images per call. The max is order-independent, so any band plan gives k_render's image.
+//     (tests/test_gpu_render_exact.py holds this kernel to the exact reference oracle/render_exact.py -- the rules -- and byte for byte
+//     to k_render -- the bits -- from every source, in every format, under one-band, one-row-band and walked plans.)
 //   * the uint8 image is finished on the device: RGB [H][W][3]; DEPTH [H][W][3], the 8-bit depth replicated; RGBD [H][W][4].
 //     The 8-bit depth normalises the camera-space depth over the WHOLE image (all bands), so the raw depth goes through a
 //     float scratch of a fixed chunk of images and k_depth8 finishes it: depth8() below, the float32 arithmetic of
@@ -149,18 +151,31 @@ __global__ __launch_bounds__(256) void k_render_obs(const T *src, RenderObsArgs 
             const float iw0 = 1.0f / vd[a], iw1 = 1.0f / vd[b], iw2 = 1.0f / vd[c];
             for (int iy = iy0; iy <= iy1; iy++)
                 for (int ix = ix0; ix <= ix1; ix++) {
+#if defined(CLOTHHIP_MUTATE) && CLOTHHIP_MUTATE == 12
+                    const float fxp = (float)ix + 0.0f, fyp = (float)iy + 0.0f;   // MUTANT 12 (tools/run_mutants.sh; never a product build): the pixel corner, not its centre
+#else
                     const float fxp = (float)ix + 0.5f, fyp = (float)iy + 0.5f;
+#endif
                     const float e0 = s * ((x2 - x1) * (fyp - y1) - (y2 - y1) * (fxp - x1));   // opposite vertex a
                     const float e1 = s * ((x0 - x2) * (fyp - y2) - (y0 - y2) * (fxp - x2));   // opposite vertex b
                     const float e2 = s * ((x1 - x0) * (fyp - y0) - (y1 - y0) * (fxp - x0));   // opposite vertex c
-                    // top-left rule on exact zeros: an edge owns its pixels if it is a top or a left edge
-                    const bool in0 = e0 > 0.0f || (e0 == 0.0f && ((s * (y2 - y1) > 0.0f) || (y2 == y1 && s * (x2 - x1) < 0.0f)));
-                    const bool in1 = e1 > 0.0f || (e1 == 0.0f && ((s * (y0 - y2) > 0.0f) || (y0 == y2 && s * (x0 - x2) < 0.0f)));
-                    const bool in2 = e2 > 0.0f || (e2 == 0.0f && ((s * (y1 - y0) > 0.0f) || (y1 == y0 && s * (x1 - x0) < 0.0f)));
+                    // top-left rule on exact zeros, in image coordinates (y down): an edge owns the centres on it if the face lies to its right (a left
+                    // edge: e grows with x, s * (y1 - y2) > 0), or, if it is horizontal, below it (a top edge: e grows with y, s * (x2 - x1) > 0)
+#if defined(CLOTHHIP_MUTATE) && CLOTHHIP_MUTATE == 10
+                    const bool in0 = e0 > 0.0f || (e0 == 0.0f && ((s * (y2 - y1) > 0.0f) || (y2 == y1 && s * (x2 - x1) < 0.0f)));   // MUTANT 10 (tools/run_mutants.sh; never a product build): e0 owns its right / bottom ties
+#else
+                    const bool in0 = e0 > 0.0f || (e0 == 0.0f && ((s * (y2 - y1) < 0.0f) || (y2 == y1 && s * (x2 - x1) > 0.0f)));
+#endif
+                    const bool in1 = e1 > 0.0f || (e1 == 0.0f && ((s * (y0 - y2) < 0.0f) || (y0 == y2 && s * (x0 - x2) > 0.0f)));
+                    const bool in2 = e2 > 0.0f || (e2 == 0.0f && ((s * (y1 - y0) < 0.0f) || (y1 == y0 && s * (x1 - x0) > 0.0f)));
                     if (!(in0 && in1 && in2)) continue;
                     const float sa = s * area;
                     const float b0 = e0 / sa, b1 = e1 / sa, b2 = e2 / sa;
+#if defined(CLOTHHIP_MUTATE) && CLOTHHIP_MUTATE == 11
+                    const float inv_d = 1.0f / (b0 * vd[a] + b1 * vd[b] + b2 * vd[c]);             // MUTANT 11 (tools/run_mutants.sh; never a product build): depth mixed affinely
+#else
                     const float inv_d = b0 * iw0 + b1 * iw1 + b2 * iw2;                        // perspective-correct 1/depth
+#endif
                     const float inten = b0 * vi[a] + b1 * vi[b] + b2 * vi[c];
                     const unsigned long long key = ((unsigned long long)depth_key(inv_d) << 32) | (quant8(col[0] * inten) << 16) |
                                                    (quant8(col[1] * inten) << 8) | quant8(col[2] * inten);

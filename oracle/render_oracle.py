@@ -1,9 +1,11 @@
 """numpy restatement of the cloth rasteriser (gym_cloth_amd/csrc/cloth_render.hpp), float32, same operation order.
 
-TEST INFRASTRUCTURE, NOT PRODUCT CODE (only tests/ import it). There is no renderer to pin the images to outside Blender, so
-what this oracle pins is the rasterisation rules themselves: projection, smooth normals in face-index order, the edge
+TEST INFRASTRUCTURE, NOT PRODUCT CODE (only tests/ import it). There is no renderer to pin the images to outside Blender. This
+file is a transliteration of the kernel, expression by expression: projection, smooth normals in face-index order, the edge
 functions with the top-left rule, perspective-correct depth, two-sided colours, nearest-fragment-wins with the
-(depth key, colour) tie-break. The scene parameters it is called with follow the reference's Blender script
+(depth key, colour) tie-break. It pins the kernels' BITS (tests/test_gpu_render.py, test_gpu_render_obs.py); a rule written wrongly
+the same way on both sides passes it. The RULES are pinned by oracle/render_exact.py, which states them geometrically and computes
+them exactly, and which this file must meet too (tests/test_render_exact_host.py). The scene parameters it is called with follow the reference's Blender script
 (gym_cloth/blender/get_image_rep_279.py: camera :114-122, lens :273-276, colours :249-257, bed :172)."""
 import numpy as np
 
@@ -96,9 +98,9 @@ def render(pos, n_side, width, height, cam_pos, world_to_cam, lens_mm, sensor_mm
         e0 = s * ((x2 - x1) * (fyp - y1) - (y2 - y1) * (fxp - x1))
         e1 = s * ((x0 - x2) * (fyp - y2) - (y0 - y2) * (fxp - x2))
         e2 = s * ((x1 - x0) * (fyp - y0) - (y1 - y0) * (fxp - x0))
-        tl0 = (s * (y2 - y1) > 0) or (y2 == y1 and s * (x2 - x1) < 0)
-        tl1 = (s * (y0 - y2) > 0) or (y0 == y2 and s * (x0 - x2) < 0)
-        tl2 = (s * (y1 - y0) > 0) or (y1 == y0 and s * (x1 - x0) < 0)
+        tl0 = (s * (y2 - y1) < 0) or (y2 == y1 and s * (x2 - x1) > 0)
+        tl1 = (s * (y0 - y2) < 0) or (y0 == y2 and s * (x0 - x2) > 0)
+        tl2 = (s * (y1 - y0) < 0) or (y1 == y0 and s * (x1 - x0) > 0)
         inside = ((e0 > 0) | ((e0 == 0) & tl0)) & ((e1 > 0) | ((e1 == 0) & tl1)) & ((e2 > 0) | ((e2 == 0) & tl2))
         if not inside.any():
             continue
