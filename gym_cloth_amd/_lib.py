@@ -111,6 +111,8 @@ FIT_OPTIMIZERS = {'adam': FIT_ADAM, 'sgd': FIT_SGD}
 FIT_MAX_BATCH = 4096                # CLOTHHIP_FIT_MAX_BATCH: the most rows of one minibatch
 FIT_MAX_MEMBER_ROWS = 65536         # CLOTHHIP_FIT_MAX_MEMBER_ROWS: the most members x rows of one grouped call (clothhip_policy_fit_members)
 FIT_SRC_SLOTS, FIT_SRC_RESETS, FIT_SRC_HELD = 0, 1, 2   # CLOTHHIP_FIT_SRC_*: where a row of clothhip_fit_hold / _append_launch lies
+FIT_LABEL_EXPERT, FIT_LABEL_ACTION = 0, 1               # CLOTHHIP_FIT_LABEL_*: where clothhip_fit_data_append_launch_ex takes a row's label from
+FIT_LABELS = {'expert': FIT_LABEL_EXPERT, 'action': FIT_LABEL_ACTION}
 assert C.sizeof(ClothFitParams) == 24
 
 
@@ -177,8 +179,14 @@ SYMBOLS = [
     ("clothhip_fit_data_clear", C.c_int, [_vp]),
     ("clothhip_fit_data_size", C.c_int, [_vp, C.POINTER(C.c_int64)]),
     ("clothhip_fit_data_get", C.c_int, [_vp, C.c_int64, C.c_int64, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    ("clothhip_fit_data_set_weights", C.c_int, [_vp, C.c_int64, C.c_int64, C.POINTER(C.c_float)]),
+    ("clothhip_fit_data_get_weights", C.c_int, [_vp, C.c_int64, C.c_int64, C.POINTER(C.c_float)]),
+    ("clothhip_fit_data_append_weighted", C.c_int, [_vp, C.POINTER(C.c_float), _dp, C.POINTER(C.c_float), C.c_int64]),
     ("clothhip_fit_hold", C.c_int, [_vp, _i32p]),
     ("clothhip_fit_data_append_launch", C.c_int, [_vp, _i32p, C.c_int64]),
+    ("clothhip_fit_data_append_launch_ex", C.c_int, [_vp, _i32p, C.c_int64, C.c_int32, C.POINTER(C.c_float)]),
+    ("clothhip_policy_fit_predict", C.c_int, [_vp, _i32p, C.c_int64, C.POINTER(C.c_float)]),
+    ("clothhip_policy_fit_predict_members", C.c_int, [_vp, _i32p, C.c_int32, _i32p, C.c_int64, C.POINTER(C.c_float)]),
     ("clothhip_policy_fit_grad", C.c_int, [_vp, _i32p, C.c_int32, C.POINTER(C.c_float), _dp]),
     ("clothhip_policy_fit_loss", C.c_int, [_vp, _i32p, C.c_int64, _dp]),
     ("clothhip_policy_fit", C.c_int, [_vp, C.POINTER(ClothFitParams), _i32p, C.c_int32, C.c_int32, _dp]),

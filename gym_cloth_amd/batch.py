@@ -623,9 +623,24 @@ class ClothBatch(object):
         check(self._L.clothhip_policy_population_combine(self._h, _lib.fp(c), c.size, _lib.fp(out)))
         return out
 
-    def fit_append(self, obs, labels):
+    @staticmethod
+    def _fit_weights(weights, n):
+        """A table of per-row loss weights as float32[n], finite (any sign, zero allowed); None stays None: 1 for every row."""
+        if weights is None:
+            return None
+        w64 = np.asarray(weights, dtype=np.float64)
+        if w64.shape != (n,):
+            raise ValueError("weights must have shape (%d,) (got %r)" % (n, w64.shape))
+        with np.errstate(over='ignore'):                  # (a double past float32's range becomes inf, refused below)
+            w = np.ascontiguousarray(w64, dtype=np.float32)
+        if not np.isfinite(w).all():
+            raise ValueError("weights must be finite (float32)")
+        return w
+
+    def fit_append(self, obs, labels, weights=None):
         """Append (observation row, action label) pairs to the handle's device-resident dataset (clothhip_fit_data_append): obs [n, 3P]
-        (stored as float32), labels [n, 4] (stored as float32). ValueError for other shapes or non-finite values (dagger_rollout gives
+        (stored as float32), labels [n, 4] (stored as float32), weights [n] (the rows' loss weights, float32, any finite value; None:
+        1 for every row -- clothhip_fit_data_append_weighted). ValueError for other shapes or non-finite values (dagger_rollout gives
         NaN labels where a slot did not run: pass the [ran] rows); nothing is appended then. Returns the dataset's size."""
         obs = np.ascontiguousarray(obs, dtype=np.float32)
         lab = np.ascontiguousarray(labels, dtype=np.float64)
@@ -635,8 +650,29 @@ class ClothBatch(object):
             raise ValueError("labels must have shape (%d, 4)" % obs.shape[0])
         if not (np.isfinite(obs).all() and np.isfinite(lab).all() and (np.abs(lab) <= np.finfo(np.float32).max).all()):
             raise ValueError("obs and labels must be finite (float32)")
-        check(self._L.clothhip_fit_data_append(self._h, _lib.fp(obs), _lib.dp(lab), obs.shape[0]))
+        w = self._fit_weights(weights, obs.shape[0])
+        if w is None:
+            check(self._L.clothhip_fit_data_append(self._h, _lib.fp(obs), _lib.dp(lab), obs.shape[0]))
+        else:
+            check(self._L.clothhip_fit_data_append_weighted(self._h, _lib.fp(obs), _lib.dp(lab), _lib.fp(w), obs.shape[0]))
         return self.fit_size()
+
+    def fit_set_weights(self, weights, first=0):
+        """Write the loss weights of the stored rows [first, first + len(weights)) (clothhip_fit_data_set_weights): any finite float32,
+        negative and zero allowed. The weight is the one column of a stored row that can be rewritten -- a row is appended when its
+        observation exists, its return is known when its episode ends."""
+        w = self._fit_weights(weights, len(weights))
+        check(self._L.clothhip_fit_data_set_weights(self._h, int(first), w.size, _lib.fp(w)))
+
+    def fit_get_weights(self, first=0, n=None):
+        """float32[n]: the loss weights of the stored rows [first, first + n), n=None: to the end (clothhip_fit_data_get_weights)."""
+        first = int(first)
+        n = self.fit_size() - first if n is None else int(n)
+        if first < 0 or n < 0:
+            raise ValueError("first and n must be >= 0 and lie within the dataset")
+        w = np.zeros(n, dtype=np.float32)
+        check(self._L.clothhip_fit_data_get_weights(self._h, first, n, _lib.fp(w)))
+        return w
 
     def fit_hold(self, src=None):
         """Fill the handle's held rows (clothhip_fit_hold): src=None -> held[e] = the float32 '1d' observation of env e's present state;
@@ -648,16 +684,21 @@ class ClothBatch(object):
             src = np.ascontiguousarray(src, dtype=np.int32)
         check(self._L.clothhip_fit_hold(self._h, _lib.i32p(src)))
 
-    def fit_append_launch(self, rows):
-        """Append pairs that lie on the device (clothhip_fit_data_append_launch): rows int[n, 3] = (source, row, label_row) -- the
-        observation is that row of the last launch's tables or of the held rows, the label row label_row = t * E + e of the last armed
-        launch's labels. ValueError when a named value is not finite (a slot that did not run); nothing is appended then. Returns the
-        dataset's size."""
+    def fit_append_launch(self, rows, labels="expert", weights=None):
+        """Append pairs that lie on the device (clothhip_fit_data_append_launch_ex): rows int[n, 3] = (source, row, label_row) -- the
+        observation is that row of the last launch's tables or of the held rows; the label is row label_row = t * E + e of the last
+        armed launch's labels (labels="expert"), or the action that slot of the last launch EXECUTED, (float32)out['actions'][t, e] read
+        from the launch's records on the device (labels="action": for policy='mlp' the network's output plus the caller's noise; no
+        expert needed). weights [n]: the rows' loss weights, None: 1. ValueError when a named value is not finite (a slot that did not
+        run); nothing is appended then. Returns the dataset's size."""
         rows = np.asarray(rows)
         if rows.ndim != 2 or rows.shape[1] != 3 or not np.issubdtype(rows.dtype, np.integer):
             raise ValueError("rows must be integers of shape (n, 3)")
+        if labels not in _lib.FIT_LABELS:
+            raise ValueError("labels must be one of %r (got %r)" % (sorted(_lib.FIT_LABELS), labels))
         rows = np.ascontiguousarray(rows, dtype=np.int32)
-        check(self._L.clothhip_fit_data_append_launch(self._h, _lib.i32p(rows), rows.shape[0]))
+        w = self._fit_weights(weights, rows.shape[0])
+        check(self._L.clothhip_fit_data_append_launch_ex(self._h, _lib.i32p(rows), rows.shape[0], _lib.FIT_LABELS[labels], _lib.fp(w)))
         return self.fit_size()
 
     def fit_data(self, first=0, n=None):
@@ -684,6 +725,27 @@ class ClothBatch(object):
         loss = np.zeros(1, dtype=np.float64)
         check(self._L.clothhip_policy_fit_loss(self._h, _lib.i32p(ix), ix.size, _lib.dp(loss)))
         return float(loss[0])
+
+    def fit_predict(self, idx, members=None):
+        """The trainer's forward on the stored rows idx [n], any n >= 1, nothing updated: float32[n, 4] of the shared network
+        (clothhip_policy_fit_predict), or with members (distinct population rows) float32[n_m, n, 4], the same rows under every member
+        (clothhip_policy_fit_predict_members). Row r is bit for bit the y fit_grad forms for dataset row idx[r] -- what the loss and its
+        gradient are made of, so weights computed from it (residuals, trust regions, an ensemble's disagreement) describe the fit itself."""
+        a = np.asarray(idx)
+        if a.ndim != 1 or a.size < 1 or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("idx must be a non-empty 1-d integer array")
+        if a.min() < 0 or a.max() > np.iinfo(np.int32).max:
+            raise ValueError("idx must hold row numbers of the dataset")
+        ix = np.ascontiguousarray(a, dtype=np.int32)
+        if members is None:
+            self._fit_n_params()
+            y = np.zeros((ix.size, 4), dtype=np.float32)
+            check(self._L.clothhip_policy_fit_predict(self._h, _lib.i32p(ix), ix.size, _lib.fp(y)))
+            return y
+        m, _ = self._fit_members(members)
+        y = np.zeros((m.size, ix.size, 4), dtype=np.float32)
+        check(self._L.clothhip_policy_fit_predict_members(self._h, _lib.i32p(m), m.size, _lib.i32p(ix), ix.size, _lib.fp(y)))
+        return y
 
     def fit_clear(self):
         """Empty the dataset (clothhip_fit_data_clear); the device memory stays with the handle."""

@@ -3,6 +3,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <new>
 #include <vector>
@@ -24,19 +25,33 @@ static int grow_dataset(clothhip_handle *h, int64_t n) {
     if (f.n + n <= f.cap) return 0;
     const size_t row = (size_t)3 * h->P;
     const int64_t cap = std::max<int64_t>(std::max<int64_t>(f.n + n, 2 * f.cap), 64);
-    Buffer<float> obs, lb;
+    Buffer<float> obs, lb, w;
     if (int rc = obs.reserve((size_t)cap * row * 4)) return rc;
     if (int rc = lb.reserve((size_t)cap * 4 * 4)) return rc;
+    if (int rc = w.reserve((size_t)cap * 4)) return rc;
     if (f.n > 0) {
         HIPCHECK(hipMemcpyAsync(obs, f.d_obs, (size_t)f.n * row * 4, hipMemcpyDeviceToDevice, h->stream));
         HIPCHECK(hipMemcpyAsync(lb, f.d_lab, (size_t)f.n * 4 * 4, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHECK(hipMemcpyAsync(w, f.d_w, (size_t)f.n * 4, hipMemcpyDeviceToDevice, h->stream));
         HIPCHECK(hipStreamSynchronize(h->stream));
     }
-    f.d_obs = std::move(obs); f.d_lab = std::move(lb); f.cap = cap;
+    f.d_obs = std::move(obs); f.d_lab = std::move(lb); f.d_w = std::move(w); f.cap = cap;
+    return 0;
+}
+
+// a caller's weight table: every value a finite float (NULL: none given, which every entry that takes one allows)
+static int check_weights(const float *w, int64_t n) {
+    if (w)
+        for (int64_t i = 0; i < n; i++)
+            if (!std::isfinite(w[i])) return fail(CLOTHHIP_EINVAL, "weights[%lld] is not finite", (long long)i);
     return 0;
 }
 
 extern "C" int clothhip_fit_data_append(clothhip_handle *h, const float *obs_rows, const double *labels, int64_t n) {
+    return clothhip_fit_data_append_weighted(h, obs_rows, labels, nullptr, n);
+}
+
+extern "C" int clothhip_fit_data_append_weighted(clothhip_handle *h, const float *obs_rows, const double *labels, const float *weights, int64_t n) {
     if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
     if (int rc = check_idle(h)) return rc;
     if (n < 0) return fail(CLOTHHIP_EINVAL, "n < 0");
@@ -53,12 +68,54 @@ extern "C" int clothhip_fit_data_append(clothhip_handle *h, const float *obs_row
         lab[i] = (float)labels[i];
         if (!std::isfinite(lab[i])) return fail(CLOTHHIP_EINVAL, "labels[%zu][%zu] is not a finite float (a slot that did not run? pass the rows that ran)", i / 4, i % 4);
     }
+    if (int rc = check_weights(weights, n)) return rc;
+    std::vector<float> ones;
+    if (!weights) {
+        try { ones.assign((size_t)n, 1.0f); } catch (const std::bad_alloc &) { return fail(CLOTHHIP_ENOMEM, "out of host memory (%lld weights)", (long long)n); }
+        weights = ones.data();
+    }
     HIPCHECK(hipSetDevice(h->device));
     if (int rc = grow_dataset(h, n)) return rc;
     HIPCHECK(hipMemcpyAsync(f.d_obs + (size_t)f.n * row, obs_rows, (size_t)n * row * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipMemcpyAsync(f.d_lab + (size_t)f.n * 4, lab.data(), (size_t)n * 4 * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipMemcpyAsync(f.d_w + (size_t)f.n, weights, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipStreamSynchronize(h->stream));      // the host tables are never retained; only now do the rows count
     f.n += n;
+    return 0;
+}
+
+// the rows [first, first + n) of a call lie within the dataset
+static int check_range(const clothhip_handle *h, int64_t first, int64_t n) {
+    if (first < 0 || n < 0 || first > h->fit.n || n > h->fit.n - first)
+        return fail(CLOTHHIP_EINVAL, "rows [%lld, %lld + %lld) outside the dataset's %lld", (long long)first, (long long)first, (long long)n, (long long)h->fit.n);
+    return 0;
+}
+
+extern "C" int clothhip_fit_data_set_weights(clothhip_handle *h, int64_t first, int64_t n, const float *w) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (int rc = check_idle(h)) return rc;
+    if (int rc = check_range(h, first, n)) return rc;
+    if (n == 0) return 0;
+    if (!w) return fail(CLOTHHIP_EINVAL, "NULL argument");
+    if (int rc = check_weights(w, n)) return rc;
+    HIPCHECK(hipSetDevice(h->device));
+    HIPCHECK(hipEventRecord(h->ev0, h->stream));
+    HIPCHECK(hipMemcpyAsync(h->fit.d_w + (size_t)first, w, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipEventRecord(h->ev1, h->stream));
+    h->have_timing = true;
+    HIPCHECK(hipStreamSynchronize(h->stream));      // (the host table is not retained)
+    return 0;
+}
+
+extern "C" int clothhip_fit_data_get_weights(clothhip_handle *h, int64_t first, int64_t n, float *w) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (int rc = check_idle(h)) return rc;
+    if (int rc = check_range(h, first, n)) return rc;
+    if (n == 0) return 0;
+    if (!w) return fail(CLOTHHIP_EINVAL, "NULL argument");
+    HIPCHECK(hipSetDevice(h->device));
+    HIPCHECK(hipMemcpyAsync(w, h->fit.d_w + (size_t)first, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
     return 0;
 }
 
@@ -78,8 +135,7 @@ extern "C" int clothhip_fit_data_size(clothhip_handle *h, int64_t *n) {
 extern "C" int clothhip_fit_data_get(clothhip_handle *h, int64_t first, int64_t n, float *obs, float *labels) {
     if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
     if (int rc = check_idle(h)) return rc;
-    if (first < 0 || n < 0 || first > h->fit.n || n > h->fit.n - first)
-        return fail(CLOTHHIP_EINVAL, "rows [%lld, %lld + %lld) outside the dataset's %lld", (long long)first, (long long)first, (long long)n, (long long)h->fit.n);
+    if (int rc = check_range(h, first, n)) return rc;
     if (n == 0 || (!obs && !labels)) return 0;
     const size_t row = (size_t)3 * h->P;
     HIPCHECK(hipSetDevice(h->device));
@@ -111,17 +167,27 @@ static int check_source(const clothhip_handle *h, int64_t i, int32_t src, int32_
     return 0;
 }
 
-// upload n index entries [n][4] and run k_fit_gather over them; *bad: the kernel met a value that is not finite. Synchronous.
-static int run_gather(clothhip_handle *h, const std::vector<int32_t> &tab, int64_t n, float *dst_obs, float *dst_lab, bool with_labels, bool *bad) {
+// upload n index entries [n][4] and run k_fit_gather over them; *bad: the kernel met a value that is not finite. label_src < 0: no
+// entry names a label and no weight is written (the held rows), else CLOTHHIP_FIT_LABEL_* and dst_w gets `weights` [n] (host; NULL:
+// ones). Synchronous.
+static int run_gather(clothhip_handle *h, const std::vector<int32_t> &tab, int64_t n, float *dst_obs, float *dst_lab, float *dst_w, int32_t label_src,
+                      const float *weights, bool *bad) {
     auto &f = h->fit;
     if (int rc = f.d_rows.reserve((size_t)n * 16)) return rc;
     if (int rc = f.d_flag.reserve(4)) return rc;
+    if (weights) {
+        if (int rc = f.d_wtab.reserve((size_t)n * 4)) return rc;
+        HIPCHECK(hipMemcpyAsync(f.d_wtab, weights, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+    }
     HIPCHECK(hipMemcpyAsync(f.d_rows, tab.data(), (size_t)n * 16, hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipMemsetAsync(f.d_flag, 0, 4, h->stream));
     FitGatherArgs a = {};
     a.table[FIT_SRC_SLOTS] = (const float *)h->epi.d_fobs; a.table[FIT_SRC_RESETS] = (const float *)h->epi.d_frobs; a.table[FIT_SRC_HELD] = f.d_held;
-    a.rows = f.d_rows; a.labels = with_labels ? (const double *)h->epi.d_flab : nullptr;
-    a.dst_obs = dst_obs; a.dst_lab = dst_lab; a.flag = f.d_flag; a.n = n; a.L = 3 * h->P;
+    a.rows = f.d_rows;
+    a.labels = label_src == CLOTHHIP_FIT_LABEL_EXPERT ? (const double *)h->epi.d_flab : nullptr;
+    a.records = label_src == CLOTHHIP_FIT_LABEL_ACTION ? (const unsigned char *)(const void *)h->epi.d_frec : nullptr;
+    a.weights = weights ? (const float *)f.d_wtab : nullptr;
+    a.dst_obs = dst_obs; a.dst_lab = dst_lab; a.dst_w = dst_w; a.flag = f.d_flag; a.n = n; a.L = 3 * h->P;
     HIPCHECK(hipEventRecord(h->ev0, h->stream));
     hipLaunchKernelGGL(k_fit_gather, dim3((unsigned)std::min<int64_t>(n, 1 << 20)), dim3(FIT_GATHER_THREADS), 0, h->stream, a);
     HIPCHECK(hipGetLastError());
@@ -174,22 +240,32 @@ extern "C" int clothhip_fit_hold(clothhip_handle *h, const int32_t *src) {
         HIPCHECK(hipStreamSynchronize(h->stream));
     } else if (!tab.empty()) {
         bool bad = false;      // (a held row is not checked here: clothhip_fit_data_append_launch checks what it appends)
-        if (int rc = run_gather(h, tab, (int64_t)tab.size() / 4, f.d_held, nullptr, false, &bad)) return rc;
+        if (int rc = run_gather(h, tab, (int64_t)tab.size() / 4, f.d_held, nullptr, nullptr, -1, nullptr, &bad)) return rc;
     }
     f.held_valid = true;
     return 0;
 }
 
 extern "C" int clothhip_fit_data_append_launch(clothhip_handle *h, const int32_t *rows, int64_t n) {
+    return clothhip_fit_data_append_launch_ex(h, rows, n, CLOTHHIP_FIT_LABEL_EXPERT, nullptr);
+}
+
+static_assert(sizeof(ClothStepRecord) == FIT_REC_BYTES && offsetof(ClothStepRecord, action) == 0 && offsetof(ClothStepRecord, ran) == FIT_REC_RAN,
+              "the record's layout as k_fit_gather reads it");
+
+extern "C" int clothhip_fit_data_append_launch_ex(clothhip_handle *h, const int32_t *rows, int64_t n, int32_t label_src, const float *weights) {
     if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
     if (int rc = check_idle(h)) return rc;
+    if (label_src != CLOTHHIP_FIT_LABEL_EXPERT && label_src != CLOTHHIP_FIT_LABEL_ACTION)
+        return fail(CLOTHHIP_EINVAL, "unknown label source %d (CLOTHHIP_FIT_LABEL_EXPERT or CLOTHHIP_FIT_LABEL_ACTION)", label_src);
     if (n < 0) return fail(CLOTHHIP_EINVAL, "n < 0");
     if (n == 0) return 0;
     if (!rows) return fail(CLOTHHIP_EINVAL, "NULL argument");
     auto &f = h->fit;
     if (f.n + n > INT32_MAX) return fail(CLOTHHIP_EINVAL, "%lld + %lld rows: a minibatch names its rows by int32", (long long)f.n, (long long)n);
     int64_t n_lab = 0;
-    if (int rc = launch_table(h, LaunchTable::labels, nullptr, &n_lab)) return rc;
+    if (int rc = launch_table(h, label_src == CLOTHHIP_FIT_LABEL_ACTION ? LaunchTable::records : LaunchTable::labels, nullptr, &n_lab)) return rc;
+    if (int rc = check_weights(weights, n)) return rc;
     std::vector<int32_t> tab;
     try { tab.resize((size_t)n * 4); } catch (const std::bad_alloc &) { return fail(CLOTHHIP_ENOMEM, "out of host memory (%lld rows)", (long long)n); }
     for (int64_t i = 0; i < n; i++) {
@@ -202,7 +278,7 @@ extern "C" int clothhip_fit_data_append_launch(clothhip_handle *h, const int32_t
     if (int rc = grow_dataset(h, n)) return rc;
     // the kernel writes behind the n rows that count; they count only if every value it wrote is finite
     bool bad = false;
-    if (int rc = run_gather(h, tab, n, f.d_obs, f.d_lab, true, &bad)) return rc;
+    if (int rc = run_gather(h, tab, n, f.d_obs, f.d_lab, f.d_w, label_src, weights, &bad)) return rc;
     if (bad) return bad_value(h, n);
     f.n += n;
     return 0;
@@ -311,14 +387,14 @@ template <bool A_KC, bool B_KC, int EPI, bool ROWS> static void launch_gemm(hipS
 
 // Enqueue every launch of one network's step, each over all n_m members: loss and gradient of the present weights over rows d_idx
 // [n_m][B] into d_loss [n_m] and h->fit.d_grad [n_m][n_params] (blob layout). d_loss NULL: the forward pass alone -- member j's y is
-// then at h->fit.d_act + j * p.act + p.h_off[L - 1]
-static int enqueue_grad(clothhip_handle *h, const FitPlan &p, int32_t n_m, const int32_t *d_idx, int32_t B, double *d_loss) {
+// then at h->fit.d_act + j * p.act + p.h_off[L - 1]; shared_rows (the forward alone): d_idx is ONE list [B] that every member reads
+static int enqueue_grad(clothhip_handle *h, const FitPlan &p, int32_t n_m, const int32_t *d_idx, int32_t B, double *d_loss, bool shared_rows = false) {
     const MlpDesc &D = h->pol.mlp;
     const int L = D.n_layers;
     auto &f = h->fit;
     float *act = f.d_act, *grad = f.d_grad, *dz[2] = {f.d_dz, f.d_dz + (size_t)B * p.maxw};
     FitGemmArgs m0 = {};
-    m0.members = f.d_members; m0.stride = D.stride; m0.rows_step = B;
+    m0.members = f.d_members; m0.stride = D.stride; m0.rows_step = shared_rows ? 0 : B;
     for (int l = 0; l < L; l++) {
         const int n_in = D.widths[l], n_out = D.widths[l + 1];
         FitGemmArgs a = m0;
@@ -333,8 +409,8 @@ static int enqueue_grad(clothhip_handle *h, const FitPlan &p, int32_t n_m, const
         HIPCHECK(hipGetLastError());
     }
     if (!d_loss) return 0;
-    hipLaunchKernelGGL(k_fit_loss, dim3((unsigned)n_m), dim3(256), 0, h->stream, (const float *)(act + p.h_off[L - 1]), (const float *)f.d_lab, d_idx, B,
-                       dz[(L - 1) & 1], d_loss, (int64_t)p.act, (int64_t)p.dz, (int64_t)B);
+    hipLaunchKernelGGL(k_fit_loss, dim3((unsigned)n_m), dim3(256), 0, h->stream, (const float *)(act + p.h_off[L - 1]), (const float *)f.d_lab, (const float *)f.d_w, d_idx,
+                       B, dz[(L - 1) & 1], d_loss, (int64_t)p.act, (int64_t)p.dz, (int64_t)B);
     HIPCHECK(hipGetLastError());
     for (int l = L - 1; l >= 0; l--) {
         const int n_in = D.widths[l], n_out = D.widths[l + 1];
@@ -410,7 +486,7 @@ extern "C" int clothhip_policy_fit_grad_members(clothhip_handle *h, const int32_
 }
 
 // The loss alone of the shared network over any number of rows: chunks of at most FIT_MAX_BATCH through the forward pass above, each
-// chunk's sum of squares in k_fit_loss's order (k_fit_sqsum), the chunk sums added in ascending order in double on the host, divided
+// chunk's weighted sum of squares in k_fit_loss's order (k_fit_sqsum), the chunk sums added in ascending order in double on the host, divided
 // once by 4 n.
 extern "C" int clothhip_policy_fit_loss(clothhip_handle *h, const int32_t *idx, int64_t n, double *loss) {
     if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
@@ -436,7 +512,8 @@ extern "C" int clothhip_policy_fit_loss(clothhip_handle *h, const int32_t *idx, 
         const FitPlan p = fit_plan(h, B);
         const int32_t *d_idx = f.d_idx + (size_t)c * FIT_MAX_BATCH;
         if (int rc = enqueue_grad(h, p, 1, d_idx, B, nullptr)) return rc;
-        hipLaunchKernelGGL(k_fit_sqsum, dim3(1), dim3(256), 0, h->stream, (const float *)(f.d_act + p.h_off[L - 1]), (const float *)f.d_lab, d_idx, B, f.d_loss + c);
+        hipLaunchKernelGGL(k_fit_sqsum, dim3(1), dim3(256), 0, h->stream, (const float *)(f.d_act + p.h_off[L - 1]), (const float *)f.d_lab, (const float *)f.d_w, d_idx, B,
+                           f.d_loss + c);
         HIPCHECK(hipGetLastError());
     }
     HIPCHECK(hipEventRecord(h->ev1, h->stream));
@@ -447,6 +524,55 @@ extern "C" int clothhip_policy_fit_loss(clothhip_handle *h, const int32_t *idx, 
     for (int64_t c = 1; c < n_chunks; c++) s = s + sums[c];
     *loss = s / (double)(4 * n);
     return 0;
+}
+
+// The forward alone on n stored rows, the same rows for every member: chunks through enqueue_grad, each chunk's y copied out to
+// d_pred [n_m][n][4] (k_fit_copy_y), one download. The call is valid.
+static int run_predict(clothhip_handle *h, const int32_t *members, int32_t n_m, const int32_t *idx, int64_t n, float *y_out) {
+    auto &f = h->fit;
+    const int L = h->pol.mlp.n_layers;
+    const int32_t Bmax = (int32_t)std::min<int64_t>(n, std::min<int64_t>(FIT_MAX_BATCH, CLOTHHIP_FIT_MAX_MEMBER_ROWS / n_m));
+    HIPCHECK(hipSetDevice(h->device));
+    if (int rc = fit_reserve(h, fit_plan(h, Bmax), n_m)) return rc;
+    if (int rc = f.d_idx.reserve((size_t)n * 4)) return rc;
+    if (int rc = f.d_pred.reserve((size_t)n_m * n * 4 * 4)) return rc;
+    HIPCHECK(hipMemcpyAsync(f.d_members, members, (size_t)n_m * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipMemcpyAsync(f.d_idx, idx, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipEventRecord(h->ev0, h->stream));
+    for (int64_t r0 = 0; r0 < n; r0 += Bmax) {
+        const int32_t B = (int32_t)std::min<int64_t>(Bmax, n - r0);
+        const FitPlan p = fit_plan(h, B);
+        if (int rc = enqueue_grad(h, p, n_m, f.d_idx + (size_t)r0, B, nullptr, true)) return rc;
+        const int32_t blocks = (4 * B + 255) / 256;
+        hipLaunchKernelGGL(k_fit_copy_y, dim3((unsigned)blocks * (unsigned)n_m), dim3(256), 0, h->stream, (const float *)(f.d_act + p.h_off[L - 1]), B,
+                           f.d_pred + (size_t)r0 * 4, (int64_t)p.act, (int64_t)n * 4, blocks);
+        HIPCHECK(hipGetLastError());
+    }
+    HIPCHECK(hipEventRecord(h->ev1, h->stream));
+    h->have_timing = true;
+    HIPCHECK(hipMemcpyAsync(y_out, f.d_pred, (size_t)n_m * n * 4 * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+extern "C" int clothhip_policy_fit_predict(clothhip_handle *h, const int32_t *idx, int64_t n, float *y_out) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (n < 1 || n > INT32_MAX) return fail(CLOTHHIP_EINVAL, "n = %lld outside [1, %d]", (long long)n, INT32_MAX);
+    if (int rc = check_fit_state(h, false)) return rc;
+    if (int rc = check_fit_rows(h, 1, idx, n, (int32_t)std::min<int64_t>(n, FIT_MAX_BATCH))) return rc;
+    if (!y_out) return fail(CLOTHHIP_EINVAL, "NULL argument");
+    return run_predict(h, SHARED_ROW, 1, idx, n, y_out);
+}
+
+extern "C" int clothhip_policy_fit_predict_members(clothhip_handle *h, const int32_t *members, int32_t n_m, const int32_t *idx, int64_t n, float *y_out) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (int rc = check_fit_state(h, true)) return rc;
+    if (n < 1 || n > INT32_MAX) return fail(CLOTHHIP_EINVAL, "n = %lld outside [1, %d]", (long long)n, INT32_MAX);
+    if (int rc = check_fit_members(h, members, n_m)) return rc;
+    if (n_m > CLOTHHIP_FIT_MAX_MEMBER_ROWS) return fail(CLOTHHIP_EINVAL, "n_m = %d members in one call, at most %d", n_m, CLOTHHIP_FIT_MAX_MEMBER_ROWS);
+    if (int rc = check_fit_rows(h, 1, idx, n, 1)) return rc;
+    if (!y_out) return fail(CLOTHHIP_EINVAL, "NULL argument");
+    return run_predict(h, members, n_m, idx, n, y_out);
 }
 
 // ---- the optimizer ----------------------------------------------------------------------------------------------------------------------

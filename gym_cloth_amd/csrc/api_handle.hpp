@@ -46,11 +46,12 @@ struct LaunchRecord {
     bool resets = false, rng = false;       // _end downloads reset records / the advanced rng states
     TableMode obs = TableMode::Absent, reset_obs = TableMode::Absent;
     bool armed = false;         // the label table exists (clothhip_run_actions_labels), and the label an action cut by its time slice carries over
+    bool records = false;       // the record table d_frec is this launch's: false from the moment a later _begin may reallocate it
     // a _begin that has come to where the observation tables may be reallocated or overwritten: they stop being readable, whatever becomes
     // of that call; everything else the record says stays (the next launch's resume_labelled reads `armed`)
     void invalidate_obs_tables() { obs = reset_obs = TableMode::Absent; }
 };
-enum class LaunchTable { obs, reset_obs, labels };
+enum class LaunchTable { obs, reset_obs, labels, records };
 
 // The host fields (HostPlan: layout_plan.hpp) and everything the handle holds on its device. Each buffer frees itself; the stream and the
 // events are declared in front of the buffers, so they go after them.
@@ -105,7 +106,7 @@ struct clothhip_handle : HostPlan {
     int n_grab_levels = 0;
     // clothhip_run_actions staging (device), sized on demand: written by clothhip_run_actions_begin / _end alone (api_run.hip). Read elsewhere:
     // last.pending (check_idle, clothhip_plan_cem); where a table of the last launch lies and how many rows it has, through launch_table below
-    // (clothhip_render_obs, the row sources of api_fit.hip, whose gather also takes d_fobs, d_frobs and d_flab as they are); d_frec
+    // (clothhip_render_obs, the row sources of api_fit.hip, whose gather also takes d_fobs, d_frobs, d_flab and d_frec as they are); d_frec
     // (clothhip_plan_cem); d_resume is cleared by drop_in_flight* and clothhip_fork
     struct EpisodeStaging {
         Buffer<void> d_fz, d_fact, d_fscr, d_frec, d_frst, d_fobs, d_frobs;
@@ -155,14 +156,16 @@ struct clothhip_handle : HostPlan {
     // The supervised trainer of the handle's networks (api_fit.hip: clothhip_fit_data_*, clothhip_policy_fit*); a new network of either
     // kind (api_policy.hip's drop_network) restarts the optimizer through fit_forget below, nothing else outside api_fit.hip touches it.
     struct Fit {
-        // the dataset: n rows of cap allocated, d_obs [cap][3P] and d_lab [cap][4] float32 (grown geometrically, contents kept)
-        Buffer<float> d_obs, d_lab;
+        // the dataset: n rows of cap allocated, d_obs [cap][3P], d_lab [cap][4] and the per-row loss weights d_w [cap] float32 (grown
+        // geometrically, contents kept; d_w is the one column a caller may rewrite: clothhip_fit_data_set_weights)
+        Buffer<float> d_obs, d_lab, d_w;
         int64_t n = 0, cap = 0;
         // rows named by where they lie (clothhip_fit_hold, clothhip_fit_data_append_launch): held [E][3P], one row per env that outlives
         // the launch tables (held_valid: some clothhip_fit_hold has filled it); the index table of one call and its not-finite flag
         Buffer<float> d_held;
         bool held_valid = false;
         Buffer<int32_t> d_rows, d_flag;
+        Buffer<float> d_wtab;        // the weights of one clothhip_fit_data_append_launch_ex call, [n]
         // the optimizer, per row of the weight table (max(pop_rows, 1) rows: a shared network counts as ONE row here too): moments d_m,
         // d_v [pop_rows][stride], [n_params] for a shared network (SGD's u is d_m), the count of steps taken and the read-as-zeros flag
         // (the row's next step clears its moments first -- what a reset is, so that a reset needs no device work). Both vectors are empty
@@ -176,6 +179,7 @@ struct clothhip_handle : HostPlan {
         Buffer<int32_t> d_idx, d_members;
         Buffer<float> d_act, d_dz, d_part, d_grad, d_hyper;
         Buffer<double> d_loss;
+        Buffer<float> d_pred;        // clothhip_policy_fit_predict*: y of every member and row, [n_m][n][4]
     } fit;
     void fit_forget() { fit.row_t.clear(); fit.row_zero.clear(); }
     // The cross-entropy planner (api_plan.hip: clothhip_plan_cem on the SCRATCH handle, clothhip_plan_sample / _refit on the handle given), all

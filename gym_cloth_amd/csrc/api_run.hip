@@ -393,6 +393,7 @@ static int stage_launch(clothhip_handle *h, const LaunchRequest &req) {
     if (int rc = h->epi.d_fticks.reserve(E * 64)) return rc;
     if (int rc = h->epi.d_fsum.reserve(E * 32)) return rc;
     HIPCHECK(hipMemsetAsync(h->epi.d_fticks, 0, E * 64, h->stream));
+    h->epi.last.records = false;                       // (the record table may be reallocated now, and is cleared below: the previous launch's is gone)
     if (int rc = h->epi.d_frec.reserve(nrec * sizeof(ClothStepRecord))) return rc;
     if (int rc = h->epi.d_fscr.reserve(nscr * sizeof(ClothResetScript))) return rc;
     if (int rc = h->epi.d_frst.reserve(nscr * sizeof(ClothResetRecord))) return rc;
@@ -462,7 +463,7 @@ int clothhip::begin_launch(clothhip_handle *h, const LaunchRequest &req) {
     LaunchRecord &r = h->epi.last;
     r.T = req.T; r.reset_rows = reset_rows(h, req); r.pending = true;
     r.resets = req.resets != TableMode::Absent; r.rng = req.reset_source == ResetSource::rng;
-    r.obs = req.obs; r.reset_obs = req.reset_obs; r.armed = req.expert != 0;
+    r.obs = req.obs; r.reset_obs = req.reset_obs; r.armed = req.expert != 0; r.records = true;
     return 0;
 }
 
@@ -494,6 +495,9 @@ int clothhip::launch_table(const clothhip_handle *h, LaunchTable which, const vo
     if (which == LaunchTable::labels) {
         if (!r.armed) return fail(CLOTHHIP_ESTATE, "the last episode launch on this handle was not armed with an expert (clothhip_run_actions_expert)");
         p = h->epi.d_flab;
+    } else if (which == LaunchTable::records) {
+        if (r.T < 1 || !r.records) return fail(CLOTHHIP_ESTATE, "no clothhip_run_actions launch whose record table is still on the device");
+        p = h->epi.d_frec;
     } else {
         if (r.T < 1) return fail(CLOTHHIP_ESTATE, "no clothhip_run_actions launch yet");
         if (which == LaunchTable::obs) {

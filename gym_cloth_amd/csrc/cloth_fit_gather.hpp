@@ -1,7 +1,8 @@
 // cloth_fit_gather.hpp -- rows of the trainer's dataset named by where they lie on the device (clothhip_fit_hold,
 // clothhip_fit_data_append_launch; no reference counterpart): ONE kernel copies observation rows of 3P floats from the last episode launch's
-// tables (or the handle's held rows) to the dataset's spare capacity (or to the held rows), and converts the expert's labels alongside.
-// Included only by api_fit.hip.
+// tables (or the handle's held rows) to the dataset's spare capacity (or to the held rows), and converts the label alongside: the expert's
+// from the label table, or the action the launch EXECUTED from its record table (clothhip_fit_data_append_launch_ex), and writes the
+// destination row's loss weight. Included only by api_fit.hip.
 //
 // A row is 3P floats and 3P is odd for every odd grid (3 * 625 = 1875), so a row starts at 4-byte alignment only: row r of a table begins
 // 12 r bytes (mod 16) into a 16-byte line, and since the source row and the destination row are unrelated numbers, the two sides are in
@@ -20,12 +21,20 @@ namespace clothhip {
 constexpr int FIT_GATHER_THREADS = 256, FIT_GATHER_DEPTH = 4;
 enum { FIT_SRC_SLOTS = 0, FIT_SRC_RESETS = 1, FIT_SRC_HELD = 2 };      // = CLOTHHIP_FIT_SRC_*
 
+// The record table as the gather reads it, in bytes: the action is four doubles at offset 0 of a record -- dword-pair loads at 8-byte
+// alignment, since a record's size is a multiple of 8 --, `ran` ONE byte near its end. api_fit.hip asserts both against ClothStepRecord.
+constexpr int FIT_REC_BYTES = 72, FIT_REC_RAN = 64;
+
 struct FitGatherArgs {
     const float *table[3];      // by source: obs [T * E][L], reset_obs [E * n_scripts][L], held [E][L] (the host has checked every index)
     const int32_t *rows;        // [n][4] = (source, row, label row or -1, destination row)
-    const double *labels;       // [T * E][4] of the last armed launch, or NULL when no entry names a label
+    const double *labels;       // [T * E][4] of the last armed launch, or NULL when no entry names a label or the labels are the records'
+    const unsigned char *records;   // [T * E] ClothStepRecord of the last launch: the label is (float)action[0..3], or NULL
+    const float *weights;       // [n] the destination rows' loss weights in entry order, or NULL: 1.0f
     float *dst_obs, *dst_lab;   // destination tables [..][L], [..][4] (dst_lab may be NULL then)
-    int32_t *flag;              // raised (integer atomic OR) when a copied observation value or a rounded label is not finite
+    float *dst_w;               // [..] (NULL: no weight is written -- the held rows have none)
+    int32_t *flag;              // raised (integer atomic OR) when a copied observation value or a rounded label is not finite, or a
+                                // named record did not run (its label is then stored as NaN, the label of a slot that did not run)
     int64_t n;
     int32_t L;                  // 3P
 };
@@ -55,23 +64,32 @@ __global__ __launch_bounds__(FIT_GATHER_THREADS) void k_fit_gather(FitGatherArgs
             }
         }
         if (lrow >= 0 && tid < 4) {      // the rounding of clothhip_fit_data_append: (float)label
-            const float lv = (float)a.labels[(int64_t)lrow * 4 + tid];
+            float lv;
+            if (a.records) {
+                const unsigned char *rec = a.records + (int64_t)lrow * FIT_REC_BYTES;
+                lv = rec[FIT_REC_RAN] == 1 ? (float)reinterpret_cast<const double *>(rec)[tid] : __uint_as_float(0x7fc00000u);
+            } else {
+                lv = (float)a.labels[(int64_t)lrow * 4 + tid];
+            }
             a.dst_lab[(int64_t)drow * 4 + tid] = lv;
             bad |= fit_not_finite(lv);
         }
+        if (a.dst_w && tid == 4) a.dst_w[drow] = a.weights ? a.weights[r] : 1.0f;      // (another lane than the labels': no second pass)
     }
     if (bad) atomicOr(a.flag, 1);
 }
 
-// the sum of (double)(y - a)^2 over a minibatch, in k_fit_loss's order (cloth_policy_fit.hpp: thread t of 256 takes elements t, t + 256, ...
-// ascending, a halving tree over the 256 sums) and nothing else: clothhip_policy_fit_loss divides on the host
-__global__ __launch_bounds__(256) void k_fit_sqsum(const float *y, const float *lab, const int32_t *rows, int32_t B, double *sum) {
+// the sum of (double)w (double)(y - a)^2 over a minibatch, in k_fit_loss's order and arithmetic (cloth_policy_fit.hpp: thread t of 256 takes
+// elements t, t + 256, ... ascending, a halving tree over the 256 sums) and nothing else: clothhip_policy_fit_loss divides on the host
+__global__ __launch_bounds__(256) void k_fit_sqsum(const float *y, const float *lab, const float *wgt, const int32_t *rows, int32_t B, double *sum) {
     __shared__ double red[256];
     const int tid = threadIdx.x, n = 4 * B;
     double s = 0.0;
     for (int i = tid; i < n; i += 256) {
-        const double dd = (double)y[i] - (double)lab[(size_t)rows[i >> 2] * 4 + (i & 3)];
-        s = s + dd * dd;
+        const size_t row = (size_t)rows[i >> 2];
+        const double dd = (double)y[i] - (double)lab[row * 4 + (i & 3)];
+        const double sq = dd * dd;
+        s = s + (double)wgt[row] * sq;
     }
     red[tid] = s;
     __syncthreads();
@@ -80,6 +98,14 @@ __global__ __launch_bounds__(256) void k_fit_sqsum(const float *y, const float *
         __syncthreads();
     }
     if (tid == 0) *sum = red[0];
+}
+
+// clothhip_policy_fit_predict*: member j's y of one chunk, [B][4] at y + j * y_step, to out + j * out_step -- 4 B contiguous floats, lane i
+// at base + 4 i on both sides. One workgroup per member and 256 elements
+__global__ __launch_bounds__(256) void k_fit_copy_y(const float *y, int32_t B, float *out, int64_t y_step, int64_t out_step, int32_t blocks) {
+    const int j = blockIdx.x / blocks, bx = blockIdx.x - j * blocks;
+    const int i = bx * 256 + threadIdx.x;
+    if (i < 4 * B) out[(int64_t)j * out_step + i] = y[(int64_t)j * y_step + i];
 }
 
 }  // namespace clothhip

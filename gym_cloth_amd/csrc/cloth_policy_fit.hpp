@@ -4,7 +4,8 @@
 // network, every row on its own minibatches; the handle's shared network is the table of one row, fitted by the call members = {0},
 // n_m = 1. Included only by api_fit.hip, which owns the order of the launches.
 //
-//   L = 1 / (4 B) sum_r sum_k (y_rk - a_rk)^2,  dL/dy = (y - a) / (2 B);  ReLU' = 1 where the pre-activation is > 0, else 0 (the mask is read
+//   L = 1 / (4 B) sum_r w_r sum_k (y_rk - a_rk)^2,  dL/dy_rk = w_r (y_rk - a_rk) / (2 B), w_r the stored row's weight (1.0f unless the caller
+//   wrote another: any finite float, the normaliser stays B);  ReLU' = 1 where the pre-activation is > 0, else 0 (the mask is read
 //   from the stored activation: relu(z) > 0 exactly when z > 0).
 //
 // ONE tiled matrix product, k_fit_gemm, does the three products of every layer on the f32-input matrix instruction
@@ -27,8 +28,9 @@
 //   * the batch sum of a weight gradient is split into FIT_SPLIT_ROWS-row ranges (a function of B alone), each range one accumulator
 //     written to its own slab; k_fit_reduce adds the slabs in ascending range order. B <= FIT_SPLIT_ROWS: one range, written directly;
 //   * db_l[j] = sum_r dZ_l[r][j], r ascending, one thread per j (k_fit_colsum);
-//   * dZ_L-1 = fl(fl(y - a) / fl(2 B)); the loss sums (double)(y - a)^2 in double: thread t of 256 takes elements t, t + 256, ... ascending,
-//     the 256 sums are added by a halving tree in LDS (k_fit_loss, one workgroup per member);
+//   * dZ_L-1 = fl(fl(w fl(y - a)) / fl(2 B)); the loss sums (double)w * (dd * dd), dd = (double)y - (double)a, each operation one double
+//     rounding: thread t of 256 takes elements t, t + 256, ... ascending, the 256 sums are added by a halving tree in LDS (k_fit_loss,
+//     one workgroup per member). Multiplying by 1.0f and by 1.0 is exact: a dataset whose weights are all 1 gives the unweighted bits;
 //   * the optimizer (k_fit_adam / k_fit_sgd) is elementwise, each operation one float32 rounding (the library is built with
 //     -ffp-contract=off; division and sqrtf are the correctly rounded ones, no fast-math flag reaches this unit).
 //   The forward's summation order differs from mlp_eval's (64 interleaved lane sums and a butterfly there), so the trainer's y need not equal
@@ -166,10 +168,11 @@ __global__ __launch_bounds__(64) void k_fit_colsum(const float *dz, int32_t B, i
     db[(int64_t)j * db_step + c] = s;
 }
 
-// dz[r][k] = fl(fl(y - a) / fl(2 B)) with a = lab[rows[r]][k]; loss = sum (double)(y - a)^2 / (4 B). One workgroup of 256 per member: y, dz
-// and the index rows at j times their per-member sizes, the loss at loss[j]
-__global__ __launch_bounds__(256) void k_fit_loss(const float *y, const float *lab, const int32_t *rows, int32_t B, float *dz, double *loss,
-                                                  int64_t y_step, int64_t dz_step, int64_t rows_step) {
+// dz[r][k] = fl(fl(w fl(y - a)) / fl(2 B)) with a = lab[rows[r]][k] and w = wgt[rows[r]]; loss = sum (double)w (double)(y - a)^2 / (4 B).
+// One workgroup of 256 per member: y, dz and the index rows at j times their per-member sizes, the loss at loss[j]. The four lanes of a
+// row read ONE weight (the same dword: one request); w = 1.0f leaves both products' bits alone, so an unweighted dataset keeps its bits.
+__global__ __launch_bounds__(256) void k_fit_loss(const float *y, const float *lab, const float *wgt, const int32_t *rows, int32_t B, float *dz,
+                                                  double *loss, int64_t y_step, int64_t dz_step, int64_t rows_step) {
     __shared__ double red[256];
     const int64_t j = blockIdx.x;
     y += j * y_step; dz += j * dz_step; rows += j * rows_step;
@@ -177,11 +180,14 @@ __global__ __launch_bounds__(256) void k_fit_loss(const float *y, const float *l
     const float two_b = (float)(2 * B);
     double s = 0.0;
     for (int i = tid; i < n; i += 256) {
-        const float yv = y[i], av = lab[(size_t)rows[i >> 2] * 4 + (i & 3)];
+        const size_t row = (size_t)rows[i >> 2];
+        const float yv = y[i], av = lab[row * 4 + (i & 3)], wv = wgt[row];
         const float d = yv - av;
-        dz[i] = d / two_b;
+        const float wd = wv * d;
+        dz[i] = wd / two_b;
         const double dd = (double)yv - (double)av;
-        s = s + dd * dd;
+        const double sq = dd * dd;
+        s = s + (double)wv * sq;
     }
     red[tid] = s;
     __syncthreads();

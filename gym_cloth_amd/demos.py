@@ -201,6 +201,23 @@ def dagger_collect(env, trainer, expert='oracle_corner', n_actions=12, beta=0.5,
     op_ticks: per launch step_many's uint64[E, 4] time accounting, records: per launch the [T, E] arrays 'ran',
     'done', 'rew', 'actual_coverage', 'expert_took' and 'slot' (the per-env slot number) for coverage curves, with 'n_resets' int[E] and
     'parked' bool[E]: the env holds an operation the slice cut). Nothing is trained here."""
+    mix = dagger_mixture(int(n_actions), env.E, beta, seed)
+    choices = None if expert_choices is None else np.asarray(expert_choices)
+    if choices is not None and choices.shape != (int(n_actions), env.E):
+        raise ValueError("expert_choices must have shape (%d, %d)" % (int(n_actions), env.E))
+
+    def launch_kw(idx, ee):
+        return dict(expert=expert, expert_mix=mix[idx, ee], expert_choices=None if choices is None else choices[idx, ee])
+
+    return _collect_loop(env, trainer, n_actions, slots_per_launch, time_budget_ms, policy_noise, max_launches, launch_kw,
+                         lambda rows, slot: trainer.append_launch(rows), ('expert_took',))
+
+
+def _collect_loop(env, trainer, n_actions, slots_per_launch, time_budget_ms, policy_noise, max_launches, launch_kw, append, record_keys):
+    """The loop dagger_collect and reward_collect share: policy='mlp' launches of slots_per_launch slots that keep their observation
+    tables on the device until every env has run n_actions slots; per launch the rows that ran (and lie within the n_actions) go to
+    append(rows int32[n, 3] in [t][e] order, slot int[n]: their per-env slot numbers), then the held rows move on. launch_kw(idx, ee):
+    further step_many keywords for the table rows idx [T, E]; record_keys: further [T, E] arrays of step_many's dict to keep per launch."""
     import time
     from .envs import hold_sources, slot_start_sources
     if trainer.env is not env:
@@ -210,13 +227,9 @@ def dagger_collect(env, trainer, expert='oracle_corner', n_actions=12, beta=0.5,
         raise ValueError("n_actions and slots_per_launch must be >= 1")
     if env.batch.in_flight().any():
         raise ValueError("an earlier time-sliced launch left operations parked on this env: complete or drop them before collecting")
-    mix = dagger_mixture(N, E, beta, seed)
     noise = None if policy_noise is None else np.asarray(policy_noise, dtype=np.float64)
     if noise is not None and noise.shape != (N, E, 4):
         raise ValueError("policy_noise must have shape (%d, %d, 4)" % (N, E))
-    choices = None if expert_choices is None else np.asarray(expert_choices)
-    if choices is not None and choices.shape != (N, E):
-        raise ValueError("expert_choices must have shape (%d, %d)" % (N, E))
     used = np.zeros(E, dtype=np.int64)
     ee = np.arange(E)[None, :]
     res = {'appended': 0, 'launches': 0, 'row_env': [], 'row_slot': [], 'took': 0.0, 'substeps': 0, 'kernel_ms': 0.0, 'op_ticks': [], 'records': []}
@@ -229,8 +242,7 @@ def dagger_collect(env, trainer, expert='oracle_corner', n_actions=12, beta=0.5,
         slot = used[None, :] + np.arange(T)[:, None]                        # [T, E]: the per-env slot number of every slot of this launch
         idx = np.minimum(slot, N - 1)                                       # past the end: the last row again (not appended)
         out = env.step_many(policy='mlp', n_actions=T, want_obs='device', time_budget_ms=time_budget_ms,
-                            policy_noise=None if noise is None else noise[idx, ee], expert=expert, expert_mix=mix[idx, ee],
-                            expert_choices=None if choices is None else choices[idx, ee])
+                            policy_noise=None if noise is None else noise[idx, ee], **launch_kw(idx, ee))
         res['kernel_ms'] += float(env.batch.last_kernel_ms)
         res['op_ticks'].append(out['op_ticks'])
         ran = out['ran']
@@ -238,15 +250,17 @@ def dagger_collect(env, trainer, expert='oracle_corner', n_actions=12, beta=0.5,
         t_, e_ = np.nonzero(keep)                                           # [t][e] order
         if len(t_):
             rows = np.concatenate([slot_start_sources(out)[t_, e_], (t_ * E + e_)[:, None].astype(np.int32)], axis=1)
-            trainer.append_launch(rows)
+            append(rows, slot[t_, e_])
             res['row_env'].append(e_); res['row_slot'].append(slot[t_, e_])
             res['appended'] += len(t_)
         env.batch.fit_hold(hold_sources(out))
         used += ran.sum(axis=0)
         res['launches'] += 1
         parked = env.batch.in_flight()                                      # operations the slice cut: the next launch continues them
-        res['records'].append({'ran': ran, 'done': out['done'], 'rew': out['rew'], 'actual_coverage': out['actual_coverage'],
-                               'expert_took': out['expert_took'], 'slot': slot, 'n_resets': out['n_resets'], 'parked': parked})
+        rec = {'ran': ran, 'done': out['done'], 'rew': out['rew'], 'actual_coverage': out['actual_coverage'], 'slot': slot,
+               'n_resets': out['n_resets'], 'parked': parked}
+        rec.update({k: out[k] for k in record_keys})
+        res['records'].append(rec)
         if not ran.any() and not parked.any() and not (out['n_resets'] > 0).any():
             raise RuntimeError("a launch made no progress (time_budget_ms = %r too short for one substep?)" % (time_budget_ms,))
     res['took'] = time.perf_counter() - t0
@@ -256,3 +270,158 @@ def dagger_collect(env, trainer, expert='oracle_corner', n_actions=12, beta=0.5,
     res['count'] = used
     res['rows'] = trainer.size()
     return res
+
+
+# ---- fitting from reward: returns, per-row weights, the collection that labels rows with the executed action ---------------------------
+def returns_to_go(rew, ran, done, reset_before, gamma=1.0, carry=None):
+    """(G float64[T, E], complete bool[T, E]) of one launch's record tables [T, E] (step_many's 'rew', 'ran', 'done', 'reset_before'):
+    G[t, e] = rew[t, e] + gamma G[t + 1, e] while slot t + 1 of env e continues slot t's episode -- slot t + 1 ran, has
+    reset_before == 0, and done[t, e] is False --, else G[t, e] = rew[t, e]; G is 0 where the slot did not run. complete[t, e]: the
+    slot's episode reached `done` inside the table(s). carry = (G_next float[E], complete_next bool[E], continues bool[E]) chains the
+    table that FOLLOWS this one (returns_carry of it): the last slot of env e that ran, if nothing ran after it in this table and its
+    done is False, continues into that table where continues[e] says its first executed slot has reset_before == 0. Without a carry
+    such a slot ends an open episode (complete False, G the rewards so far). Plain float64 numpy, one multiplication and one addition
+    per slot."""
+    rew = np.asarray(rew, dtype=np.float64)
+    ran = np.asarray(ran, dtype=bool)
+    done = np.asarray(done, dtype=bool)
+    rb = np.asarray(reset_before).astype(np.int64)
+    if not (rew.ndim == 2 and rew.shape == ran.shape == done.shape == rb.shape):
+        raise ValueError("rew, ran, done and reset_before must be [T, E] tables of one shape")
+    T, E = rew.shape
+    gamma = float(gamma)
+    if carry is None:
+        nG, nC, nK = np.zeros(E), np.zeros(E, dtype=bool), np.zeros(E, dtype=bool)
+    else:
+        nG, nC, nK = (np.array(carry[0], dtype=np.float64).reshape(E), np.array(carry[1], dtype=bool).reshape(E),
+                      np.array(carry[2], dtype=bool).reshape(E))
+    G, complete = np.zeros((T, E)), np.zeros((T, E), dtype=bool)
+    tail = np.ones(E, dtype=bool)                                           # nothing has run after slot t in this table
+    for t in range(T - 1, -1, -1):
+        if t + 1 < T:
+            cont = np.where(tail, nK, ran[t + 1] & (rb[t + 1] == 0)) & ~done[t]
+        else:
+            cont = nK & ~done[t]
+        G[t] = np.where(ran[t], rew[t] + np.where(cont, gamma * nG, 0.0), 0.0)
+        complete[t] = ran[t] & (done[t] | (cont & nC))
+        nG, nC = np.where(ran[t], G[t], nG), np.where(ran[t], complete[t], nC)
+        tail &= ~ran[t]
+    return G, complete
+
+
+def returns_carry(G, complete, ran, reset_before, carry=None):
+    """What a table gives the table BEFORE it as returns_to_go's carry: per env (G, complete) of its first slot that ran and whether
+    that slot continues an episode (reset_before == 0); an env with no slot that ran passes on the carry it was given itself."""
+    ran = np.asarray(ran, dtype=bool)
+    T, E = ran.shape
+    first = np.argmax(ran, axis=0)
+    e_ = np.arange(E)
+    some = ran.any(axis=0)
+    if carry is None:
+        carry = (np.zeros(E), np.zeros(E, dtype=bool), np.zeros(E, dtype=bool))
+    return (np.where(some, np.asarray(G, dtype=np.float64)[first, e_], carry[0]), np.where(some, np.asarray(complete, dtype=bool)[first, e_], carry[1]),
+            np.where(some, np.asarray(reset_before)[first, e_] == 0, carry[2]))
+
+
+def reward_weights(G, scheme='filter', **kw):
+    """float32[n] loss weights from the returns G [n] of completed-episode rows. scheme 'advantage': (G - mean) / (std + 1e-8);
+    'exp' (temperature=1.0, w_max=20.0): min(exp((G - mean) / temperature), w_max); 'filter' (q=0.25): 1 where G >= the (1 - q)
+    quantile of G (numpy.quantile's linear interpolation; ties at the quantile included), else 0; a callable: scheme(G, **kw). Float64
+    arithmetic, rounded once. The trainer divides by the batch size, not by the weights' sum: a scheme that should average to 1 must
+    be scaled by the caller."""
+    G = np.asarray(G, dtype=np.float64).reshape(-1)
+    if callable(scheme):
+        w = np.asarray(scheme(G, **kw), dtype=np.float64)
+        if w.shape != G.shape:
+            raise ValueError("the weighting callable must return one weight per return")
+    elif G.size == 0:
+        w = np.zeros(0)
+    elif scheme == 'advantage':
+        _no_kw(scheme, kw, ())
+        w = (G - G.mean()) / (G.std() + 1e-8)
+    elif scheme == 'exp':
+        _no_kw(scheme, kw, ('temperature', 'w_max'))
+        temperature, w_max = float(kw.get('temperature', 1.0)), float(kw.get('w_max', 20.0))
+        if not temperature > 0.0:
+            raise ValueError("temperature must be > 0")
+        w = np.minimum(np.exp(np.minimum((G - G.mean()) / temperature, 700.0)), w_max)
+    elif scheme == 'filter':
+        _no_kw(scheme, kw, ('q',))
+        q = float(kw.get('q', 0.25))
+        if not 0.0 < q <= 1.0:
+            raise ValueError("q must lie in (0, 1]")
+        w = (G >= np.quantile(G, 1.0 - q)).astype(np.float64)
+    else:
+        raise ValueError("scheme must be 'advantage', 'exp', 'filter' or a callable (got %r)" % (scheme,))
+    w = w.astype(np.float32)
+    if not np.isfinite(w).all():
+        raise ValueError("the scheme gave a weight that is not a finite float32")
+    return w
+
+
+def _no_kw(scheme, kw, allowed):
+    unknown = sorted(set(kw) - set(allowed))
+    if unknown:
+        raise ValueError("scheme %r takes no %r" % (scheme, unknown))
+
+
+def reward_collect(env, trainer, n_actions=12, gamma=1.0, scheme='filter', policy_noise=None, slots_per_launch=12, time_budget_ms=0.0,
+                   max_launches=None, **scheme_kw):
+    """Collect rows to FIT FROM REWARD: dagger_collect's loop with no expert armed. The env's network (plus policy_noise [n_actions, E,
+    4], the exploration) drives the cloths in launches of slots_per_launch slots until every env has run n_actions slots; per launch
+    the rows that ran are appended where they lie (envs.slot_start_sources) with the action the slot EXECUTED as the label
+    (append_launch(labels="action")) and weight 0, then the held rows move on. A row's return is known when its episode ends, possibly
+    launches later: the host keeps the per-launch records, and when the loop ends the returns-to-go of the collection's slots
+    (returns_to_go with `gamma`, the launches chained by returns_carry; slots an env ran beyond its n_actions are not part of the
+    collection) give reward_weights(G[complete], scheme, **scheme_kw), written over the appended range in ONE set_weights call. Rows of
+    episodes still open when the collection ends keep weight 0 and are counted in 'open_rows'. Returns dagger_collect's dict (without
+    'expert_took' in the records, with 'reset_before') plus first: the dataset index of the first appended row, returns float64[appended]
+    and complete bool[appended] in dataset order, weights float32[appended] as written, open_rows, episode_return float64[episodes]: the
+    return from the first collected slot of every episode that completed, t_append / t_set_weights: seconds in those calls. Nothing is
+    trained here: reward_fit below steps the trainer."""
+    import time
+    first = trainer.size()
+    spent = {'append': 0.0}
+
+    def append(rows, slot):
+        t0 = time.perf_counter()
+        trainer.append_launch(rows, labels="action", weights=np.zeros(len(rows), dtype=np.float32))
+        spent['append'] += time.perf_counter() - t0
+
+    res = _collect_loop(env, trainer, n_actions, slots_per_launch, time_budget_ms, policy_noise, max_launches, lambda idx, ee: {}, append,
+                        ('reset_before',))
+    N, carry, per_launch = int(n_actions), None, []
+    for rec in reversed(res['records']):                                    # the later launch first: a return looks ahead
+        ran = rec['ran'] & (rec['slot'] < N)
+        G, complete = returns_to_go(rec['rew'], ran, rec['done'], rec['reset_before'], gamma, carry)
+        carry = returns_carry(G, complete, ran, rec['reset_before'], carry)
+        t_, e_ = np.nonzero(ran)                                            # the order the rows were appended in
+        per_launch.append((G[t_, e_], complete[t_, e_], rec['done'][t_, e_]))
+    per_launch.reverse()
+    cat = lambda k, dt: np.concatenate([p[k] for p in per_launch]).astype(dt) if per_launch else np.zeros(0, dtype=dt)
+    G, complete, done = cat(0, np.float64), cat(1, bool), cat(2, bool)
+    # an episode starts at an env's first collected slot and after every slot that ended one (a reset a time slice completed without a
+    # record of its own shows in no reset_before)
+    ended = np.zeros((N + 1, env.E), dtype=bool)
+    ended[0] = True
+    ended[res['row_slot'] + 1, res['row_env']] = done
+    starts = ended[res['row_slot'], res['row_env']]
+    w = np.zeros(len(G), dtype=np.float32)
+    w[complete] = reward_weights(G[complete], scheme, **scheme_kw)
+    t0 = time.perf_counter()
+    if len(w):
+        trainer.set_weights(w, first)
+    res.update(first=first, returns=G, complete=complete, weights=w, open_rows=int((~complete).sum()), episode_return=G[starts & complete],
+               t_append=spent['append'], t_set_weights=time.perf_counter() - t0)
+    return res
+
+
+def reward_fit(env, trainer, col, n_steps=100, batch_size=64, seed=0):
+    """The refit after reward_collect, on the device: n_steps optimizer steps on minibatches of batch_size rows of everything in the
+    dataset (MLPTrainer.step(n_steps, batch_size, seed)), under the weights `col` (reward_collect's dict) wrote. The env's network is
+    updated in place: the next reward_collect rolls out the fitted weights. Returns dict(losses float64[n_steps]: each step's weighted
+    loss before its update, rows: the dataset's size, appended: the rows `col` added, weighted: those of them with a non-zero weight)."""
+    if trainer.env is not env:
+        raise ValueError("the trainer belongs to another env")
+    return {'losses': trainer.step(n_steps, batch_size, seed), 'rows': trainer.size(), 'appended': int(col['appended']),
+            'weighted': int(np.count_nonzero(col['weights']))}

@@ -422,11 +422,12 @@ class MLPPopulation(object):
         self.perturb(self.generation + 1)
 
 
-def fit_reference(layers, obs, labels, idx):
+def fit_reference(layers, obs, labels, idx, weights=None):
     """Pure-numpy float64 loss and gradient of the trainer's objective, for tests and for users who want to check a fit:
-    L = 1 / (4 B) sum_r sum_k (y_rk - a_rk)^2 over the rows idx [B] of (obs [n, in], labels [n, 4]) -- torch.nn.MSELoss() -- with ReLU
-    after every layer but the last and ReLU' = 1 where the pre-activation is > 0, else 0. obs, labels and the weights are rounded to
-    float32 first (what the device stores), the arithmetic is float64. Returns (loss, [(dW, db), ...]) in `layers`' shapes."""
+    L = 1 / (4 B) sum_r w_r sum_k (y_rk - a_rk)^2 over the rows idx [B] of (obs [n, in], labels [n, 4], weights [n] or None: all 1 --
+    then torch.nn.MSELoss()) with ReLU after every layer but the last and ReLU' = 1 where the pre-activation is > 0, else 0. The
+    normaliser is B, whatever the weights sum to. obs, labels, the per-row weights and the network's weights are rounded to float32
+    first (what the device stores), the arithmetic is float64. Returns (loss, [(dW, db), ...]) in `layers`' shapes."""
     ix = np.asarray(idx, dtype=np.int64).reshape(-1)
     Ws = [np.asarray(W, dtype=np.float32).astype(np.float64) for W, _ in layers]
     bs = [np.asarray(b, dtype=np.float32).astype(np.float64) for _, b in layers]
@@ -438,8 +439,13 @@ def fit_reference(layers, obs, labels, idx):
         z = hs[-1] @ Ws[l].T + bs[l]
         hs.append(np.maximum(z, 0.0) if l + 1 < L else z)
     d = hs[-1] - a
-    loss = float((d * d).sum() / (4.0 * B))
-    g = d / (2.0 * B)
+    if weights is None:
+        loss = float((d * d).sum() / (4.0 * B))
+        g = d / (2.0 * B)
+    else:
+        w = np.asarray(weights, dtype=np.float64).astype(np.float32).astype(np.float64).reshape(-1)[ix][:, None]
+        loss = float((w * (d * d)).sum() / (4.0 * B))
+        g = w * d / (2.0 * B)
     grads = [None] * L
     for l in range(L - 1, -1, -1):
         grads[l] = (g.T @ hs[l], g.sum(axis=0))
@@ -498,18 +504,31 @@ class MLPTrainer(object):
             raise ValueError("index_table needs n >= 1, n_steps >= 0, batch_size >= 1")
         return np.random.RandomState(seed).randint(0, int(n), size=(int(n_steps), int(batch_size))).astype(np.int32)
 
-    def append(self, obs, labels):
-        """Add rows to the dataset (obs [n, 3P], labels [n, 4], finite); returns its size."""
-        return self.env.batch.fit_append(obs, labels)
+    def append(self, obs, labels, weights=None):
+        """Add rows to the dataset (obs [n, 3P], labels [n, 4], finite; weights [n]: their loss weights, None: 1); returns its size."""
+        return self.env.batch.fit_append(obs, labels, weights)
 
-    def append_launch(self, rows):
-        """Add rows that lie on the device (ClothBatch.fit_append_launch): rows int[n, 3] = (source, row, label_row) into the last armed
-        launch's tables and the held rows, as envs.slot_start_sources names them; returns the dataset's size."""
-        return self.env.batch.fit_append_launch(rows)
+    def append_launch(self, rows, labels="expert", weights=None):
+        """Add rows that lie on the device (ClothBatch.fit_append_launch): rows int[n, 3] = (source, row, label_row) into the last
+        launch's tables and the held rows, as envs.slot_start_sources names them; labels="expert": the last armed launch's label,
+        labels="action": the action that slot executed; weights [n]: the rows' loss weights, None: 1. Returns the dataset's size."""
+        return self.env.batch.fit_append_launch(rows, labels, weights)
 
     def data(self, first=0, n=None):
         """(obs float32[n, 3P], labels float32[n, 4]): the stored rows [first, first + n) by download, n=None: to the end."""
         return self.env.batch.fit_data(first, n)
+
+    def set_weights(self, weights, first=0):
+        """Write the loss weights of the stored rows [first, first + len(weights)): any finite float32 (ClothBatch.fit_set_weights)."""
+        self.env.batch.fit_set_weights(weights, first)
+
+    def weights(self, first=0, n=None):
+        """float32[n]: the loss weights of the stored rows [first, first + n), n=None: to the end."""
+        return self.env.batch.fit_get_weights(first, n)
+
+    def predict(self, idx):
+        """float32[n, 4]: the trainer's forward on the dataset rows idx at the present weights -- the y of grad and step, bit for bit."""
+        return self.env.batch.fit_predict(idx)
 
     def loss(self, idx):
         """The MSE over the dataset rows idx (any number: a held-out split by index) at the present weights, forward only."""
@@ -613,17 +632,32 @@ class MLPEnsemble(object):
         return m.astype(np.int32)
 
     # the dataset: MLPTrainer's methods over the env's one dataset
-    def append(self, obs, labels):
-        """Add rows to the dataset (obs [n, 3P], labels [n, 4], finite); returns its size."""
-        return self.env.batch.fit_append(obs, labels)
+    def append(self, obs, labels, weights=None):
+        """Add rows to the dataset (obs [n, 3P], labels [n, 4], finite; weights [n]: their loss weights, None: 1); returns its size."""
+        return self.env.batch.fit_append(obs, labels, weights)
 
-    def append_launch(self, rows):
+    def append_launch(self, rows, labels="expert", weights=None):
         """Add rows that lie on the device (ClothBatch.fit_append_launch), as MLPTrainer.append_launch; returns the dataset's size."""
-        return self.env.batch.fit_append_launch(rows)
+        return self.env.batch.fit_append_launch(rows, labels, weights)
 
     def data(self, first=0, n=None):
         """(obs float32[n, 3P], labels float32[n, 4]): the stored rows [first, first + n) by download, n=None: to the end."""
         return self.env.batch.fit_data(first, n)
+
+    def set_weights(self, weights, first=0):
+        """Write the loss weights of the stored rows [first, first + len(weights)): any finite float32 (ClothBatch.fit_set_weights)."""
+        self.env.batch.fit_set_weights(weights, first)
+
+    def weights(self, first=0, n=None):
+        """float32[n]: the loss weights of the stored rows [first, first + n), n=None: to the end."""
+        return self.env.batch.fit_get_weights(first, n)
+
+    def predict(self, idx, members=None):
+        """float32[n_m, n, 4]: the trainer's forward of the rows `members` (None: all G) on the dataset rows idx [n], the same rows for
+        every member -- each member's y of grad and step, bit for bit; nothing is updated."""
+        m = self._members(members)
+        self._on_env()
+        return self.env.batch.fit_predict(idx, m)
 
     def size(self):
         return self.env.batch.fit_size()
@@ -687,7 +721,12 @@ class MLPEnsemble(object):
         return out.reshape(self.G, n, 4)
 
     def disagreement(self, obs):
-        """float64[n]: ensemble_disagreement(actions(obs)) -- per row the mean over the action components of the members' variance."""
+        """float64[n]: per row the mean over the action components of the members' variance. obs float[n, 3P]: host rows, through
+        ensemble_disagreement(actions(obs)); obs int[n]: rows of the DATASET by index, through predict -- the trainer's forward on rows
+        the host need not hold."""
+        a = np.asarray(obs)
+        if a.ndim == 1 and np.issubdtype(a.dtype, np.integer):
+            return ensemble_disagreement(self.predict(a))
         return ensemble_disagreement(self.actions(obs))
 
 

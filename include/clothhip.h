@@ -469,6 +469,20 @@ int clothhip_fit_data_size(clothhip_handle *h, int64_t *n);
 /* Download stored rows [first, first + n): obs[n][3P] and labels[n][4], float32 as stored; either pointer may be NULL. For tests, and for
  * whoever checkpoints a dataset that grew without the host ever seeing it. CLOTHHIP_EINVAL for a range outside the dataset. */
 int clothhip_fit_data_get(clothhip_handle *h, int64_t first, int64_t n, float *obs, float *labels);
+/* PER-ROW LOSS WEIGHTS (fitting from reward: reward- or advantage-weighted regression, imitation of the best rollouts, and with
+ * w_r = 2 A_r / sigma^2 the REINFORCE step of a fixed-sigma Gaussian policy, whose gradient the weighted MSE gradient then is). The
+ * dataset has a third column w[n], float32, and the trainer's loss multiplies row r's squares by w_r (THE LOSS below). Every row
+ * appended by clothhip_fit_data_append or clothhip_fit_data_append_launch gets 1.0f; the column grows with the rows and
+ * clothhip_fit_data_clear empties it. The column is MUTABLE where the rows are not: a row has to be appended before the next launch
+ * overwrites the observation it was taken on, while its return is known only when its episode ends, possibly several launches later
+ * -- so the weight is written after the row. _set_weights writes w[0 .. n) to the stored rows [first, first + n), _get_weights reads
+ * them. A weight is any finite float: negative and zero are allowed. CLOTHHIP_EINVAL for a range outside the dataset, a NULL table
+ * with n > 0 or a non-finite weight -- nothing is written then; CLOTHHIP_ESTATE with a launch in flight. Synchronous.
+ * clothhip_fit_data_append_weighted is clothhip_fit_data_append with weights[n] (NULL: 1.0f for every row) and its refusals, and a
+ * non-finite weight refused as there. */
+int clothhip_fit_data_set_weights(clothhip_handle *h, int64_t first, int64_t n, const float *w);
+int clothhip_fit_data_get_weights(clothhip_handle *h, int64_t first, int64_t n, float *w);
+int clothhip_fit_data_append_weighted(clothhip_handle *h, const float *obs_rows, const double *labels, const float *weights, int64_t n);
 /* ROWS NAMED BY WHERE THEY LIE ON THE DEVICE (csrc/cloth_fit_gather.hpp): a DAgger collection appends what each slot's policy saw without
  * the observation tables ever leaving the device. A row is (source, row):
  *   CLOTHHIP_FIT_SRC_SLOTS   row t * E + e of the last launch's observation table (the state after slot t of env e);
@@ -491,12 +505,29 @@ int clothhip_fit_data_get(clothhip_handle *h, int64_t first, int64_t n, float *o
  * the dataset is what it was. Synchronous; clothhip_last_kernel_ms gives the kernel's time.
  * Refused before anything is touched -- CLOTHHIP_ESTATE: a launch in flight, SLOTS / RESETS when the last launch kept no such table (or
  * there was none), a label row when the last launch was not armed, HELD before any clothhip_fit_hold; CLOTHHIP_EINVAL: an unknown source,
- * a row outside its table, n < 0, rows == NULL with n > 0, more than INT32_MAX rows in all. */
+ * a row outside its table, n < 0, rows == NULL with n > 0, more than INT32_MAX rows in all.
+ * clothhip_fit_data_append_launch_ex is that call with a LABEL SOURCE and the rows' weights (weights[n] in entry order, host, any finite
+ * float, NULL: 1.0f); clothhip_fit_data_append_launch(h, rows, n) IS _ex(h, rows, n, CLOTHHIP_FIT_LABEL_EXPERT, NULL).
+ *   CLOTHHIP_FIT_LABEL_EXPERT  the label table of the last armed launch, as above;
+ *   CLOTHHIP_FIT_LABEL_ACTION  label_row = t * E + e names the last launch's ClothStepRecord ON THE DEVICE and the label is
+ *        (float)record.action[0..3]: what step() was passed, before clipping -- for CLOTHHIP_POLICY_MLP the network's output plus the
+ *        caller's noise, the sample the launch EXECUTED. No armed expert is needed. The record table is valid under the rule of the
+ *        observation tables: from a launch's _end (or the synchronous form) until the next clothhip_run_actions* call. A named record
+ *        with ran != 1 is the NaN label of a slot that did not run: the flag is raised, CLOTHHIP_EINVAL, the dataset is what it was.
+ * The refusals are those above; besides, CLOTHHIP_ESTATE for LABEL_ACTION with no launch since creation (or none whose record table
+ * is still there), CLOTHHIP_EINVAL for an unknown label_src or a non-finite weight. */
 enum { CLOTHHIP_FIT_SRC_SLOTS = 0, CLOTHHIP_FIT_SRC_RESETS = 1, CLOTHHIP_FIT_SRC_HELD = 2 };
+enum { CLOTHHIP_FIT_LABEL_EXPERT = 0, CLOTHHIP_FIT_LABEL_ACTION = 1 };
 int clothhip_fit_hold(clothhip_handle *h, const int32_t *src);
 int clothhip_fit_data_append_launch(clothhip_handle *h, const int32_t *rows, int64_t n);
+int clothhip_fit_data_append_launch_ex(clothhip_handle *h, const int32_t *rows, int64_t n, int32_t label_src, const float *weights);
 /* THE LOSS over a minibatch of B dataset rows idx[0 .. B) (host int32, repeats allowed and counted as often), with y the network's
- * float32 output and a the stored label:   L = 1 / (4 B) sum_r sum_k (y_rk - a_rk)^2   (torch.nn.MSELoss()), so dL/dy = (y - a) / (2 B);
+ * float32 output, a the stored label and w_r the stored weight of row r:   L = 1 / (4 B) sum_r w_r sum_k (y_rk - a_rk)^2   (with every
+ * weight 1: torch.nn.MSELoss()), so dL/dy_rk = w_r (y_rk - a_rk) / (2 B). The normaliser is B, not sum w: the caller normalises the
+ * weights. The arithmetic: dz_rk = fl(fl(w_r fl(y - a)) / fl(2 B)) in float32; the loss adds (double)w_r * (dd * dd) with
+ * dd = (double)y - (double)a, each operation one double rounding, thread t of 256 taking elements t, t + 256, ... of the [B][4] table
+ * in ascending order, the 256 sums added by a halving tree, the total divided by 4 B. Multiplying by 1.0f and by 1.0 is exact, so a
+ * dataset whose weights are all 1 -- every dataset that no weight was written to -- gives the bits of the unweighted loss.
  * ReLU's derivative is 1 where the pre-activation is > 0, else 0. clothhip_policy_fit_grad computes L (a double: the squares are summed
  * in double in a fixed order) and dL/dtheta (grad_out[n_params] float32, the blob's layout) at the handle's present weights and updates
  * nothing. All arithmetic is float32, on an fp64 handle too, on the f32-input matrix instructions; every reduction has one fixed order
@@ -504,11 +535,20 @@ int clothhip_fit_data_append_launch(clothhip_handle *h, const int32_t *rows, int
  * clothhip_policy_eval, so its y need not equal that function's bits. */
 int clothhip_policy_fit_grad(clothhip_handle *h, const int32_t *idx, int32_t B, float *grad_out, double *loss_out);
 /* THE LOSS ALONE over any number n >= 1 of dataset rows idx[0 .. n) (a held-out split by index), forward only, nothing updated:
- * L = 1 / (4 n) sum_r sum_k (y_rk - a_rk)^2. The rows go through the trainer's forward in chunks of at most CLOTHHIP_FIT_MAX_BATCH, in
+ * L = 1 / (4 n) sum_r w_r sum_k (y_rk - a_rk)^2, weighted as above. The rows go through the trainer's forward in chunks of at most CLOTHHIP_FIT_MAX_BATCH, in
  * order; a chunk's squares are summed as clothhip_policy_fit_grad sums them, the chunk sums are added in ascending order in double, and
  * the total is divided once by 4 n -- so for n <= CLOTHHIP_FIT_MAX_BATCH the result is clothhip_policy_fit_grad's loss bit for bit.
  * The refusals of clothhip_policy_fit_grad, with n in place of B and no upper limit but INT32_MAX. */
 int clothhip_policy_fit_loss(clothhip_handle *h, const int32_t *idx, int64_t n, double *loss);
+/* THE TRAINER'S FORWARD on stored rows named by index, nothing updated: y_out[r][0..3] (host float32 [n][4]) is bit for bit the y that
+ * clothhip_policy_fit_grad forms for row idx[r] (which clothhip_policy_eval's need not be: another summation order). It lets the host
+ * compute weights from the network's own outputs on rows it never downloaded: residuals, trust-region masks, an ensemble's
+ * disagreement on the dataset. Any n >= 1, in chunks of at most CLOTHHIP_FIT_MAX_BATCH (an output row depends on its own row alone,
+ * so the chunking shows nowhere). clothhip_policy_fit_predict: the shared network, the refusals of clothhip_policy_fit_loss.
+ * clothhip_policy_fit_predict_members: y_out[n_m][n][4], the SAME rows idx[n] for every member, the refusals of the _members calls
+ * (the cap on n_m * B applies to a chunk: n_m <= CLOTHHIP_FIT_MAX_MEMBER_ROWS, and the chunks shorten to fit). */
+int clothhip_policy_fit_predict(clothhip_handle *h, const int32_t *idx, int64_t n, float *y_out);
+int clothhip_policy_fit_predict_members(clothhip_handle *h, const int32_t *members, int32_t n_m, const int32_t *idx, int64_t n, float *y_out);
 /* The optimizer. All fields are floats; lr, eps, momentum finite and >= 0, beta1 and beta2 in [0, 1).
  *   CLOTHHIP_FIT_ADAM  with t the 1-based count of steps since the last reset, the host computes in double
  *        a_t = lr sqrt(1 - beta2^t) / (1 - beta1^t)  and hands the device (float)a_t, (float)(1 - beta1), (float)(1 - beta2); per parameter,
@@ -516,7 +556,8 @@ int clothhip_policy_fit_loss(clothhip_handle *h, const int32_t *idx, int64_t n, 
  *        m = fl(fl(beta1 m) + fl((1 - beta1) g));  v = fl(fl(beta2 v) + fl((1 - beta2) fl(g g)));
  *        theta = fl(theta - fl(a_t fl(m / fl(sqrtf(v) + eps))))
  *   CLOTHHIP_FIT_SGD   u = fl(fl(momentum u) + g);  theta = fl(theta - fl(lr u))
- * No weight decay, no per-row weights. SGD's u and Adam's m are ONE table: change the optimizer through clothhip_policy_fit_reset. */
+ * No weight decay. The per-row weights are the dataset's (PER-ROW LOSS WEIGHTS above), not the optimizer's. SGD's u and Adam's m are
+ * ONE table: change the optimizer through clothhip_policy_fit_reset. */
 enum { CLOTHHIP_FIT_ADAM = 0, CLOTHHIP_FIT_SGD = 1 };
 typedef struct ClothFitParams { float optimizer /* CLOTHHIP_FIT_* */, lr, beta1, beta2, eps, momentum; } ClothFitParams;
 /* n_steps optimizer steps; step s uses the rows idx[s][0 .. B) (host int32 [n_steps][B]: which rows a step uses is the caller's table)
