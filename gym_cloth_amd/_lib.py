@@ -113,7 +113,18 @@ FIT_MAX_MEMBER_ROWS = 65536         # CLOTHHIP_FIT_MAX_MEMBER_ROWS: the most mem
 FIT_SRC_SLOTS, FIT_SRC_RESETS, FIT_SRC_HELD = 0, 1, 2   # CLOTHHIP_FIT_SRC_*: where a row of clothhip_fit_hold / _append_launch lies
 FIT_LABEL_EXPERT, FIT_LABEL_ACTION = 0, 1               # CLOTHHIP_FIT_LABEL_*: where clothhip_fit_data_append_launch_ex takes a row's label from
 FIT_LABELS = {'expert': FIT_LABEL_EXPERT, 'action': FIT_LABEL_ACTION}
+FIT_LABEL_ZERO = 3                                      # ... or (0, 0, 0, 0) from no table at all: how a leaf of the actor-critic is appended
+FIT_NEXT_TERMINAL, FIT_NEXT_NONE = -1, -2               # CLOTHHIP_FIT_NEXT_*: a row's successor column besides a dataset index
+GAE_WRITE_WEIGHTS, GAE_NORMALIZE = 1, 2                 # CLOTHHIP_GAE_*: clothhip_fit_data_gae's flags
 assert C.sizeof(ClothFitParams) == 24
+
+
+class ClothGaeParams(C.Structure):
+    """clothhip_fit_data_gae's constants: the discount, GAE's lambda, the scale of the written weights, GAE_* flags."""
+    _fields_ = [("gamma", C.c_double), ("lambda_", C.c_double), ("w_scale", C.c_float), ("flags", C.c_int32)]
+
+
+assert C.sizeof(ClothGaeParams) == 24
 
 
 class ClothPlanParams(C.Structure):
@@ -194,6 +205,17 @@ SYMBOLS = [
     ("clothhip_policy_fit_grad_members", C.c_int, [_vp, _i32p, C.c_int32, _i32p, C.c_int32, C.POINTER(C.c_float), _dp]),
     ("clothhip_policy_fit_members", C.c_int, [_vp, C.POINTER(ClothFitParams), _i32p, C.c_int32, _i32p, C.c_int32, C.c_int32, _dp]),
     ("clothhip_policy_fit_reset_members", C.c_int, [_vp, _i32p, C.c_int32]),
+    ("clothhip_set_value_mlp", C.c_int, [_vp, C.c_int32, _i32p, C.POINTER(C.c_float), C.c_size_t]),
+    ("clothhip_get_value_mlp", C.c_int, [_vp, C.POINTER(C.c_float), C.c_size_t]),
+    ("clothhip_fit_data_set_transitions", C.c_int, [_vp, C.c_int64, C.c_int64, C.POINTER(C.c_float), _i32p]),
+    ("clothhip_fit_data_get_transitions", C.c_int, [_vp, C.c_int64, C.c_int64, C.POINTER(C.c_float), _i32p]),
+    ("clothhip_fit_data_set_returns", C.c_int, [_vp, C.c_int64, C.c_int64, C.POINTER(C.c_float)]),
+    ("clothhip_fit_data_get_returns", C.c_int, [_vp, C.c_int64, C.c_int64, C.POINTER(C.c_float)]),
+    ("clothhip_value_fit_grad", C.c_int, [_vp, _i32p, C.c_int32, C.POINTER(C.c_float), _dp]),
+    ("clothhip_value_fit", C.c_int, [_vp, C.POINTER(ClothFitParams), _i32p, C.c_int32, C.c_int32, _dp]),
+    ("clothhip_value_fit_reset", C.c_int, [_vp]),
+    ("clothhip_value_predict", C.c_int, [_vp, _i32p, C.c_int64, C.POINTER(C.c_float)]),
+    ("clothhip_fit_data_gae", C.c_int, [_vp, C.c_int64, C.c_int64, C.POINTER(ClothGaeParams), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     ("clothhip_plan_cem", C.c_int, [_vp, _vp, C.POINTER(ClothEpisodeParams), C.POINTER(ClothPlanParams), _i32p, _u8p, _dp, _dp, _dp, _dp,
                                     _dp, _dp]),
     ("clothhip_plan_sample", C.c_int, [_vp, C.POINTER(ClothPlanParams), _dp, _dp, C.c_int32, C.c_int32, _dp, _dp, _dp]),

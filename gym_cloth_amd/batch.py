@@ -624,17 +624,18 @@ class ClothBatch(object):
         return out
 
     @staticmethod
-    def _fit_weights(weights, n):
-        """A table of per-row loss weights as float32[n], finite (any sign, zero allowed); None stays None: 1 for every row."""
+    def _fit_weights(weights, n, what="weights"):
+        """A table of per-row loss weights (or, by `what`, another float32 column of the dataset) as float32[n], finite (any sign, zero
+        allowed); None stays None: 1 for every row."""
         if weights is None:
             return None
         w64 = np.asarray(weights, dtype=np.float64)
         if w64.shape != (n,):
-            raise ValueError("weights must have shape (%d,) (got %r)" % (n, w64.shape))
+            raise ValueError("%s must have shape (%d,) (got %r)" % (what, n, w64.shape))
         with np.errstate(over='ignore'):                  # (a double past float32's range becomes inf, refused below)
             w = np.ascontiguousarray(w64, dtype=np.float32)
         if not np.isfinite(w).all():
-            raise ValueError("weights must be finite (float32)")
+            raise ValueError("%s must be finite (float32)" % what)
         return w
 
     def fit_append(self, obs, labels, weights=None):
@@ -689,16 +690,18 @@ class ClothBatch(object):
         observation is that row of the last launch's tables or of the held rows; the label is row label_row = t * E + e of the last
         armed launch's labels (labels="expert"), or the action that slot of the last launch EXECUTED, (float32)out['actions'][t, e] read
         from the launch's records on the device (labels="action": for policy='mlp' the network's output plus the caller's noise; no
-        expert needed). weights [n]: the rows' loss weights, None: 1. ValueError when a named value is not finite (a slot that did not
+        expert needed), or with labels="zero" (0, 0, 0, 0) and label_row ignored: a leaf of the actor-critic, appended for its state alone.
+        weights [n]: the rows' loss weights, None: 1. ValueError when a named value is not finite (a slot that did not
         run); nothing is appended then. Returns the dataset's size."""
         rows = np.asarray(rows)
         if rows.ndim != 2 or rows.shape[1] != 3 or not np.issubdtype(rows.dtype, np.integer):
             raise ValueError("rows must be integers of shape (n, 3)")
-        if labels not in _lib.FIT_LABELS:
-            raise ValueError("labels must be one of %r (got %r)" % (sorted(_lib.FIT_LABELS), labels))
+        if labels != "zero" and labels not in _lib.FIT_LABELS:
+            raise ValueError("labels must be one of %r or 'zero' (got %r)" % (sorted(_lib.FIT_LABELS), labels))
         rows = np.ascontiguousarray(rows, dtype=np.int32)
         w = self._fit_weights(weights, rows.shape[0])
-        check(self._L.clothhip_fit_data_append_launch_ex(self._h, _lib.i32p(rows), rows.shape[0], _lib.FIT_LABELS[labels], _lib.fp(w)))
+        src = _lib.FIT_LABEL_ZERO if labels == "zero" else _lib.FIT_LABELS[labels]
+        check(self._L.clothhip_fit_data_append_launch_ex(self._h, _lib.i32p(rows), rows.shape[0], src, _lib.fp(w)))
         return self.fit_size()
 
     def fit_data(self, first=0, n=None):
@@ -884,6 +887,126 @@ class ClothBatch(object):
             return
         m, _ = self._fit_members(members)
         check(self._L.clothhip_policy_fit_reset_members(self._h, _lib.i32p(m), m.size))
+
+    # ---- actor-critic from reward: the value network, the transition columns, the critic's fit, GAE (clothhip.h: ACTOR-CRITIC FROM REWARD) ----
+    def set_value_mlp(self, layers):
+        """The handle's value network (clothhip_set_value_mlp): `layers` as set_policy_mlp takes them with a last `out` of 1; None or []
+        drops it. It lives beside the policy network or population and independent of it; no launch evaluates it."""
+        self._val_n_params = 0
+        if not layers:
+            check(self._L.clothhip_set_value_mlp(self._h, 0, None, None, 0))
+            return
+        from .policies import pack_mlp
+        widths, blob = pack_mlp(layers, n_out=1)
+        check(self._L.clothhip_set_value_mlp(self._h, len(widths) - 1, _lib.i32p(widths), _lib.fp(blob), blob.size))
+        self._val_n_params = int(blob.size)
+
+    def _value_n_params(self):
+        n = getattr(self, '_val_n_params', 0)
+        if not n:
+            raise _lib.ClothHipError("no value network on this batch: call set_value_mlp first")
+        return n
+
+    def get_value_mlp(self):
+        """The value network's blob as the device holds it, float32[n_params] (clothhip_get_value_mlp)."""
+        out = np.zeros(self._value_n_params(), dtype=np.float32)
+        check(self._L.clothhip_get_value_mlp(self._h, _lib.fp(out), out.size))
+        return out
+
+    def _fit_range(self, first, n):
+        first = int(first)
+        n = self.fit_size() - first if n is None else int(n)
+        if first < 0 or n < 0:
+            raise ValueError("first and n must be >= 0 and lie within the dataset")
+        return first, n
+
+    def fit_set_transitions(self, rew, next, first=0):
+        """Write the reward and the successor of the stored rows [first, first + len(rew)) (clothhip_fit_data_set_transitions): rew
+        finite float32, next int: the dataset index of the row with the successor state (greater than the row's own), or
+        _lib.FIT_NEXT_TERMINAL (the episode ended), or _lib.FIT_NEXT_NONE (a leaf: the row has no transition, it only bootstraps)."""
+        r = self._fit_weights(rew, len(rew), "rew")
+        nx = np.asarray(next)
+        if nx.shape != r.shape or not np.issubdtype(nx.dtype, np.integer):
+            raise ValueError("next must hold %d integers" % r.size)
+        if nx.size and (nx.min() < _lib.FIT_NEXT_NONE or nx.max() > np.iinfo(np.int32).max):
+            raise ValueError("next must hold row numbers of the dataset, FIT_NEXT_TERMINAL or FIT_NEXT_NONE")
+        nx = np.ascontiguousarray(nx, dtype=np.int32)
+        check(self._L.clothhip_fit_data_set_transitions(self._h, int(first), r.size, _lib.fp(r), _lib.i32p(nx)))
+
+    def fit_get_transitions(self, first=0, n=None):
+        """(rew float32[n], next int32[n]) of the stored rows [first, first + n), n=None: to the end (clothhip_fit_data_get_transitions)."""
+        first, n = self._fit_range(first, n)
+        rew, nx = np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.int32)
+        check(self._L.clothhip_fit_data_get_transitions(self._h, first, n, _lib.fp(rew), _lib.i32p(nx)))
+        return rew, nx
+
+    def fit_set_returns(self, ret, first=0):
+        """Write the value targets of the stored rows [first, first + len(ret)) (clothhip_fit_data_set_returns): finite float32."""
+        r = self._fit_weights(ret, len(ret), "ret")
+        check(self._L.clothhip_fit_data_set_returns(self._h, int(first), r.size, _lib.fp(r)))
+
+    def fit_get_returns(self, first=0, n=None):
+        """float32[n]: the value targets of the stored rows [first, first + n), n=None: to the end (clothhip_fit_data_get_returns)."""
+        first, n = self._fit_range(first, n)
+        ret = np.zeros(n, dtype=np.float32)
+        check(self._L.clothhip_fit_data_get_returns(self._h, first, n, _lib.fp(ret)))
+        return ret
+
+    def value_grad(self, idx):
+        """(loss float, grad float32[n_params] in the blob's layout) of the value network over the dataset rows idx [B], at the present
+        weights; nothing is updated (clothhip_value_fit_grad). The loss is 1 / (2 B) sum (v - ret)^2, unweighted."""
+        ix = self._fit_idx(idx, 1)
+        grad = np.zeros(self._value_n_params(), dtype=np.float32)
+        loss = np.zeros(1, dtype=np.float64)
+        check(self._L.clothhip_value_fit_grad(self._h, _lib.i32p(ix), ix.size, _lib.fp(grad), _lib.dp(loss)))
+        return float(loss[0]), grad
+
+    def value_fit(self, idx_table, optimizer='adam', lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, momentum=0.0):
+        """fit for the value network (clothhip_value_fit): n_steps optimizer steps in place on the device, step s on the dataset rows
+        idx_table[s] (int [n_steps, B]), with its own moments and step count (value_fit_reset, or a new value network, restarts them).
+        Returns float64[n_steps]: each step's loss BEFORE its update. The policy's network and optimizer keep their bits."""
+        ix = self._fit_idx(idx_table, 2)
+        p = self._fit_params(dict(optimizer=optimizer, lr=lr, beta1=beta1, beta2=beta2, eps=eps, momentum=momentum), 1)
+        self._value_n_params()
+        loss = np.zeros(ix.shape[0], dtype=np.float64)
+        check(self._L.clothhip_value_fit(self._h, p, _lib.i32p(ix), ix.shape[0], ix.shape[1], _lib.dp(loss)))
+        return loss
+
+    def value_predict(self, idx):
+        """float32[n]: the value network on the stored rows idx [n], any n >= 1, nothing updated (clothhip_value_predict) -- row r is bit
+        for bit the v value_grad forms for dataset row idx[r]."""
+        a = np.asarray(idx)
+        if a.ndim != 1 or a.size < 1 or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("idx must be a non-empty 1-d integer array")
+        if a.min() < 0 or a.max() > np.iinfo(np.int32).max:
+            raise ValueError("idx must hold row numbers of the dataset")
+        self._value_n_params()
+        ix = np.ascontiguousarray(a, dtype=np.int32)
+        v = np.zeros(ix.size, dtype=np.float32)
+        check(self._L.clothhip_value_predict(self._h, _lib.i32p(ix), ix.size, _lib.fp(v)))
+        return v
+
+    def value_fit_reset(self):
+        """Zero the value network's moments and its step count (clothhip_value_fit_reset)."""
+        check(self._L.clothhip_value_fit_reset(self._h))
+
+    def fit_gae(self, gamma, lam, first=0, n=None, write_weights=True, normalize=False, w_scale=1.0, want=True):
+        """Generalised advantage estimation over the stored rows [first, first + n) ON THE DEVICE (clothhip_fit_data_gae): the value
+        network's forward over the range, then per non-leaf row A = sum_k (gamma lam)^k delta_k along its chain of successors,
+        delta = rew + gamma V(next) - V (V(next) = 0 at a terminal row, the critic's value at a leaf); the value-target column gets
+        (float32)(A + V), a leaf's gets V. write_weights: the weight column gets (float32)(w_scale A), or with normalize
+        w_scale (A - mean) / (std + 1e-8) over the non-leaf rows; a leaf gets 0. Returns (adv float32[n], ret float32[n]), or None
+        with want=False (nothing is downloaded). policies.gae_reference states the arithmetic."""
+        first, n = self._fit_range(first, n)
+        g, l, ws = float(gamma), float(lam), float(np.float32(w_scale))
+        if not (np.isfinite(g) and np.isfinite(l) and np.isfinite(ws)) or not (0.0 <= g <= 1.0 and 0.0 <= l <= 1.0):
+            raise ValueError("gamma and lam lie in [0, 1], w_scale is a finite float32 (got %r, %r, %r)" % (gamma, lam, w_scale))
+        self._value_n_params()
+        p = _lib.ClothGaeParams(g, l, ws, (_lib.GAE_WRITE_WEIGHTS if write_weights else 0) | (_lib.GAE_NORMALIZE if normalize else 0))
+        adv = np.zeros(n, dtype=np.float32) if want else None
+        ret = np.zeros(n, dtype=np.float32) if want else None
+        check(self._L.clothhip_fit_data_gae(self._h, first, n, C.byref(p), _lib.fp(adv), _lib.fp(ret)))
+        return (adv, ret) if want else None
 
     # ---- the cross-entropy planner over forked cloths (clothhip_plan_*) ------------------------------------------
     @staticmethod

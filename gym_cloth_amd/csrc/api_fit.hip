@@ -1,4 +1,4 @@
-// api_fit.hip -- the supervised trainer of the handle's networks: the device-resident dataset, the loss and its gradient over a minibatch, the optimizer steps.
+// api_fit.hip -- the supervised trainer of the handle's networks, policy and critic: the device-resident dataset and its columns, the loss and its gradient over a minibatch, the optimizer steps, advantages from the critic's values.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "api_handle.hpp"
+#include "cloth_fit_gae.hpp"
 #include "cloth_fit_gather.hpp"
 #include "cloth_policy_fit.hpp"
 #include "cloth_policy_mlp.hpp"
@@ -17,6 +18,8 @@ static_assert(FIT_MAX_BATCH == CLOTHHIP_FIT_MAX_BATCH, "the batch cap of the hea
 static_assert(sizeof(ClothFitParams) == 24, "ClothFitParams is six floats");
 static_assert(FIT_SRC_SLOTS == CLOTHHIP_FIT_SRC_SLOTS && FIT_SRC_RESETS == CLOTHHIP_FIT_SRC_RESETS && FIT_SRC_HELD == CLOTHHIP_FIT_SRC_HELD,
               "the row sources of the header and of the kernel");
+static_assert(GAE_NEXT_NONE == CLOTHHIP_FIT_NEXT_NONE && CLOTHHIP_FIT_NEXT_TERMINAL < 0 && CLOTHHIP_FIT_NEXT_NONE < 0, "the leaf mark of the header and of the kernels");
+static_assert(sizeof(ClothGaeParams) == 24, "ClothGaeParams is two doubles, a float and an int32");
 
 // ---- the dataset (clothhip.h: clothhip_fit_data_*) ------------------------------------------------------------------------------------
 // room for n more rows: grow geometrically into new tables, keep the rows (Buffer::reserve would not), swap them in
@@ -25,17 +28,38 @@ static int grow_dataset(clothhip_handle *h, int64_t n) {
     if (f.n + n <= f.cap) return 0;
     const size_t row = (size_t)3 * h->P;
     const int64_t cap = std::max<int64_t>(std::max<int64_t>(f.n + n, 2 * f.cap), 64);
-    Buffer<float> obs, lb, w;
+    Buffer<float> obs, lb, w, rew, ret;
+    Buffer<int32_t> next;
     if (int rc = obs.reserve((size_t)cap * row * 4)) return rc;
     if (int rc = lb.reserve((size_t)cap * 4 * 4)) return rc;
     if (int rc = w.reserve((size_t)cap * 4)) return rc;
+    if (int rc = rew.reserve((size_t)cap * 4)) return rc;
+    if (int rc = ret.reserve((size_t)cap * 4)) return rc;
+    if (int rc = next.reserve((size_t)cap * 4)) return rc;
     if (f.n > 0) {
         HIPCHECK(hipMemcpyAsync(obs, f.d_obs, (size_t)f.n * row * 4, hipMemcpyDeviceToDevice, h->stream));
         HIPCHECK(hipMemcpyAsync(lb, f.d_lab, (size_t)f.n * 4 * 4, hipMemcpyDeviceToDevice, h->stream));
         HIPCHECK(hipMemcpyAsync(w, f.d_w, (size_t)f.n * 4, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHECK(hipMemcpyAsync(rew, f.d_rew, (size_t)f.n * 4, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHECK(hipMemcpyAsync(ret, f.d_ret, (size_t)f.n * 4, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHECK(hipMemcpyAsync(next, f.d_next, (size_t)f.n * 4, hipMemcpyDeviceToDevice, h->stream));
         HIPCHECK(hipStreamSynchronize(h->stream));
     }
-    f.d_obs = std::move(obs); f.d_lab = std::move(lb); f.d_w = std::move(w); f.cap = cap;
+    f.d_obs = std::move(obs); f.d_lab = std::move(lb); f.d_w = std::move(w); f.d_rew = std::move(rew); f.d_ret = std::move(ret); f.d_next = std::move(next);
+    f.cap = cap;
+    return 0;
+}
+
+// The n rows behind the ones that count get the defaults of the transition columns (reward 0, no successor: a leaf, value target 0), on
+// the device and in the host mirror of `next`; enqueued, the caller synchronises before the rows count. After grow_dataset.
+static int default_transitions(clothhip_handle *h, int64_t n) {
+    auto &f = h->fit;
+    try { f.h_next.resize((size_t)f.n); f.h_next.resize((size_t)(f.n + n), CLOTHHIP_FIT_NEXT_NONE); } catch (const std::bad_alloc &) {
+        return fail(CLOTHHIP_ENOMEM, "out of host memory (%lld rows)", (long long)(f.n + n));
+    }
+    HIPCHECK(hipMemsetAsync(f.d_rew + (size_t)f.n, 0, (size_t)n * 4, h->stream));
+    HIPCHECK(hipMemsetAsync(f.d_ret + (size_t)f.n, 0, (size_t)n * 4, h->stream));
+    HIPCHECK(hipMemsetD32Async((hipDeviceptr_t)(f.d_next + (size_t)f.n), CLOTHHIP_FIT_NEXT_NONE, (size_t)n, h->stream));
     return 0;
 }
 
@@ -76,6 +100,7 @@ extern "C" int clothhip_fit_data_append_weighted(clothhip_handle *h, const float
     }
     HIPCHECK(hipSetDevice(h->device));
     if (int rc = grow_dataset(h, n)) return rc;
+    if (int rc = default_transitions(h, n)) return rc;
     HIPCHECK(hipMemcpyAsync(f.d_obs + (size_t)f.n * row, obs_rows, (size_t)n * row * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipMemcpyAsync(f.d_lab + (size_t)f.n * 4, lab.data(), (size_t)n * 4 * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipMemcpyAsync(f.d_w + (size_t)f.n, weights, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
@@ -119,10 +144,73 @@ extern "C" int clothhip_fit_data_get_weights(clothhip_handle *h, int64_t first, 
     return 0;
 }
 
+// ---- the episode structure and the value targets (clothhip.h: ACTOR-CRITIC FROM REWARD) ---------------------------------------------------
+extern "C" int clothhip_fit_data_set_transitions(clothhip_handle *h, int64_t first, int64_t n, const float *rew, const int32_t *next) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (int rc = check_idle(h)) return rc;
+    if (int rc = check_range(h, first, n)) return rc;
+    if (n == 0) return 0;
+    if (!rew || !next) return fail(CLOTHHIP_EINVAL, "NULL argument");
+    auto &f = h->fit;
+    for (int64_t i = 0; i < n; i++) {
+        if (!std::isfinite(rew[i])) return fail(CLOTHHIP_EINVAL, "rew[%lld] is not finite", (long long)i);
+        const int64_t nx = next[i];
+        if (nx != CLOTHHIP_FIT_NEXT_TERMINAL && nx != CLOTHHIP_FIT_NEXT_NONE && (nx <= first + i || nx >= f.n))
+            return fail(CLOTHHIP_EINVAL, "next[%lld] = %lld: a successor lies behind its row %lld and inside the dataset's %lld (or CLOTHHIP_FIT_NEXT_TERMINAL, CLOTHHIP_FIT_NEXT_NONE)",
+                        (long long)i, (long long)nx, (long long)(first + i), (long long)f.n);
+    }
+    HIPCHECK(hipSetDevice(h->device));
+    HIPCHECK(hipMemcpyAsync(f.d_rew + (size_t)first, rew, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipMemcpyAsync(f.d_next + (size_t)first, next, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));      // (the host tables are not retained)
+    std::copy(next, next + n, f.h_next.begin() + first);
+    return 0;
+}
+
+extern "C" int clothhip_fit_data_get_transitions(clothhip_handle *h, int64_t first, int64_t n, float *rew, int32_t *next) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (int rc = check_idle(h)) return rc;
+    if (int rc = check_range(h, first, n)) return rc;
+    if (n == 0) return 0;
+    if (!rew || !next) return fail(CLOTHHIP_EINVAL, "NULL argument");
+    HIPCHECK(hipSetDevice(h->device));
+    HIPCHECK(hipMemcpyAsync(rew, h->fit.d_rew + (size_t)first, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipMemcpyAsync(next, h->fit.d_next + (size_t)first, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+extern "C" int clothhip_fit_data_set_returns(clothhip_handle *h, int64_t first, int64_t n, const float *ret) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (int rc = check_idle(h)) return rc;
+    if (int rc = check_range(h, first, n)) return rc;
+    if (n == 0) return 0;
+    if (!ret) return fail(CLOTHHIP_EINVAL, "NULL argument");
+    for (int64_t i = 0; i < n; i++)
+        if (!std::isfinite(ret[i])) return fail(CLOTHHIP_EINVAL, "ret[%lld] is not finite", (long long)i);
+    HIPCHECK(hipSetDevice(h->device));
+    HIPCHECK(hipMemcpyAsync(h->fit.d_ret + (size_t)first, ret, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));      // (the host table is not retained)
+    return 0;
+}
+
+extern "C" int clothhip_fit_data_get_returns(clothhip_handle *h, int64_t first, int64_t n, float *ret) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (int rc = check_idle(h)) return rc;
+    if (int rc = check_range(h, first, n)) return rc;
+    if (n == 0) return 0;
+    if (!ret) return fail(CLOTHHIP_EINVAL, "NULL argument");
+    HIPCHECK(hipSetDevice(h->device));
+    HIPCHECK(hipMemcpyAsync(ret, h->fit.d_ret + (size_t)first, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
 extern "C" int clothhip_fit_data_clear(clothhip_handle *h) {
     if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
     if (int rc = check_idle(h)) return rc;
     h->fit.n = 0;
+    h->fit.h_next.clear();
     return 0;
 }
 
@@ -256,26 +344,28 @@ static_assert(sizeof(ClothStepRecord) == FIT_REC_BYTES && offsetof(ClothStepReco
 extern "C" int clothhip_fit_data_append_launch_ex(clothhip_handle *h, const int32_t *rows, int64_t n, int32_t label_src, const float *weights) {
     if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
     if (int rc = check_idle(h)) return rc;
-    if (label_src != CLOTHHIP_FIT_LABEL_EXPERT && label_src != CLOTHHIP_FIT_LABEL_ACTION)
-        return fail(CLOTHHIP_EINVAL, "unknown label source %d (CLOTHHIP_FIT_LABEL_EXPERT or CLOTHHIP_FIT_LABEL_ACTION)", label_src);
+    if (label_src != CLOTHHIP_FIT_LABEL_EXPERT && label_src != CLOTHHIP_FIT_LABEL_ACTION && label_src != CLOTHHIP_FIT_LABEL_ZERO)
+        return fail(CLOTHHIP_EINVAL, "unknown label source %d (CLOTHHIP_FIT_LABEL_EXPERT, CLOTHHIP_FIT_LABEL_ACTION or CLOTHHIP_FIT_LABEL_ZERO)", label_src);
+    const bool zero = label_src == CLOTHHIP_FIT_LABEL_ZERO;      // no label table is read: label_row is ignored (the kernel is told row 0 of no table)
     if (n < 0) return fail(CLOTHHIP_EINVAL, "n < 0");
     if (n == 0) return 0;
     if (!rows) return fail(CLOTHHIP_EINVAL, "NULL argument");
     auto &f = h->fit;
     if (f.n + n > INT32_MAX) return fail(CLOTHHIP_EINVAL, "%lld + %lld rows: a minibatch names its rows by int32", (long long)f.n, (long long)n);
     int64_t n_lab = 0;
-    if (int rc = launch_table(h, label_src == CLOTHHIP_FIT_LABEL_ACTION ? LaunchTable::records : LaunchTable::labels, nullptr, &n_lab)) return rc;
+    if (!zero) if (int rc = launch_table(h, label_src == CLOTHHIP_FIT_LABEL_ACTION ? LaunchTable::records : LaunchTable::labels, nullptr, &n_lab)) return rc;
     if (int rc = check_weights(weights, n)) return rc;
     std::vector<int32_t> tab;
     try { tab.resize((size_t)n * 4); } catch (const std::bad_alloc &) { return fail(CLOTHHIP_ENOMEM, "out of host memory (%lld rows)", (long long)n); }
     for (int64_t i = 0; i < n; i++) {
         const int32_t s = rows[3 * i], r = rows[3 * i + 1], l = rows[3 * i + 2];
         if (int rc = check_source(h, i, s, r)) return rc;
-        if (l < 0 || l >= n_lab) return fail(CLOTHHIP_EINVAL, "entry %lld: label row %d outside [0, %lld)", (long long)i, l, (long long)n_lab);
-        tab[4 * i] = s; tab[4 * i + 1] = r; tab[4 * i + 2] = l; tab[4 * i + 3] = (int32_t)(f.n + i);
+        if (!zero && (l < 0 || l >= n_lab)) return fail(CLOTHHIP_EINVAL, "entry %lld: label row %d outside [0, %lld)", (long long)i, l, (long long)n_lab);
+        tab[4 * i] = s; tab[4 * i + 1] = r; tab[4 * i + 2] = zero ? 0 : l; tab[4 * i + 3] = (int32_t)(f.n + i);
     }
     HIPCHECK(hipSetDevice(h->device));
     if (int rc = grow_dataset(h, n)) return rc;
+    if (int rc = default_transitions(h, n)) return rc;
     // the kernel writes behind the n rows that count; they count only if every value it wrote is finite
     bool bad = false;
     if (int rc = run_gather(h, tab, n, f.d_obs, f.d_lab, f.d_w, label_src, weights, &bad)) return rc;
@@ -290,8 +380,30 @@ extern "C" int clothhip_fit_data_append_launch_ex(clothhip_handle *h, const int3
 // 0 lies at offset 0 whatever mlp.stride holds). The extern "C" entries below only refuse what each of them refuses and call it.
 static_assert(CLOTHHIP_FIT_MAX_MEMBER_ROWS == 65536, "the header's cap on n_m * B of one call");
 
-static const int32_t SHARED_ROW[1] = {0};      // the member list of the shared network
-static size_t fit_rows(const clothhip_handle *h) { return h->pol.pop_rows ? (size_t)h->pol.pop_rows : 1; }
+static const int32_t SHARED_ROW[1] = {0};      // the member list of the shared network, and of the value network
+
+// The weight table a call trains, and what belongs to it: the policy's (shared network or population) or the value network's one row.
+// The launches below read nothing else of the handle's networks.
+struct FitNet {
+    const MlpDesc &D;
+    float *theta;                       // the table, [max(pop_rows, 1)][D.stride]
+    size_t n_params;
+    int64_t pop_rows;                   // 0: a table of one row at offset 0
+    Buffer<float> &d_m, &d_v;           // its optimizer: the moments, per row the step count and the read-as-zeros flag
+    std::vector<int64_t> &row_t;
+    std::vector<uint8_t> &row_zero;
+    bool value;                         // output width 1, fitted unweighted to the column of value targets; else width 4, to the labels under the weights
+    int out() const { return value ? 1 : MLP_OUT; }
+    size_t rows() const { return pop_rows ? (size_t)pop_rows : 1; }
+};
+static FitNet policy_net(clothhip_handle *h) {
+    auto &f = h->fit;
+    return {h->pol.mlp, h->pol.pop_rows ? h->pol.d_pop : h->pol.d_mlp, h->pol.mlp_n_params, h->pol.pop_rows, f.d_m, f.d_v, f.row_t, f.row_zero, false};
+}
+static FitNet value_net(clothhip_handle *h) {
+    auto &f = h->fit;
+    return {h->val.mlp, h->val.d_mlp, h->val.n_params, 0, f.d_val_m, f.d_val_v, f.val_t, f.val_zero, true};
+}
 
 // What the entries refuse before anything is touched, each in the order it always had. The state; `population`: the entry trains rows of
 // a population (which puts these refusals first, whatever else is wrong with the call), else the shared network
@@ -304,6 +416,13 @@ static int check_fit_state(const clothhip_handle *h, bool population) {
         if (h->pol.pop_rows) return fail(CLOTHHIP_ESTATE, "this handle holds a population of networks: the fit trains the ONE shared network of clothhip_set_policy_mlp");
         if (h->pol.mlp.n_layers < 1) return fail(CLOTHHIP_ESTATE, "no network on this handle: call clothhip_set_policy_mlp first");
     }
+    if (h->fit.n < 1) return fail(CLOTHHIP_ESTATE, "the dataset is empty: call clothhip_fit_data_append first");
+    return 0;
+}
+// ... and of the entries that train or evaluate the value network (a population is no obstacle: the critic is not the policy)
+static int check_value_state(const clothhip_handle *h) {
+    if (int rc = check_idle(h)) return rc;
+    if (h->val.mlp.n_layers < 1) return fail(CLOTHHIP_ESTATE, "no value network on this handle: call clothhip_set_value_mlp first");
     if (h->fit.n < 1) return fail(CLOTHHIP_ESTATE, "the dataset is empty: call clothhip_fit_data_append first");
     return 0;
 }
@@ -352,8 +471,8 @@ struct FitPlan {
     int n_split;
     size_t w_off[MLP_MAX_LAYERS], h_off[MLP_MAX_LAYERS];
 };
-static FitPlan fit_plan(const clothhip_handle *h, int32_t B) {
-    const MlpDesc &D = h->pol.mlp;
+static FitPlan fit_plan(const FitNet &net, int32_t B) {
+    const MlpDesc &D = net.D;
     FitPlan p = {};
     size_t maxmat = 0;
     p.maxw = MLP_OUT;
@@ -388,8 +507,8 @@ template <bool A_KC, bool B_KC, int EPI, bool ROWS> static void launch_gemm(hipS
 // Enqueue every launch of one network's step, each over all n_m members: loss and gradient of the present weights over rows d_idx
 // [n_m][B] into d_loss [n_m] and h->fit.d_grad [n_m][n_params] (blob layout). d_loss NULL: the forward pass alone -- member j's y is
 // then at h->fit.d_act + j * p.act + p.h_off[L - 1]; shared_rows (the forward alone): d_idx is ONE list [B] that every member reads
-static int enqueue_grad(clothhip_handle *h, const FitPlan &p, int32_t n_m, const int32_t *d_idx, int32_t B, double *d_loss, bool shared_rows = false) {
-    const MlpDesc &D = h->pol.mlp;
+static int enqueue_grad(clothhip_handle *h, const FitNet &net, const FitPlan &p, int32_t n_m, const int32_t *d_idx, int32_t B, double *d_loss, bool shared_rows = false) {
+    const MlpDesc &D = net.D;
     const int L = D.n_layers;
     auto &f = h->fit;
     float *act = f.d_act, *grad = f.d_grad, *dz[2] = {f.d_dz, f.d_dz + (size_t)B * p.maxw};
@@ -409,8 +528,12 @@ static int enqueue_grad(clothhip_handle *h, const FitPlan &p, int32_t n_m, const
         HIPCHECK(hipGetLastError());
     }
     if (!d_loss) return 0;
-    hipLaunchKernelGGL(k_fit_loss, dim3((unsigned)n_m), dim3(256), 0, h->stream, (const float *)(act + p.h_off[L - 1]), (const float *)f.d_lab, (const float *)f.d_w, d_idx,
-                       B, dz[(L - 1) & 1], d_loss, (int64_t)p.act, (int64_t)p.dz, (int64_t)B);
+    if (net.value)
+        hipLaunchKernelGGL(k_fit_loss<1>, dim3((unsigned)n_m), dim3(256), 0, h->stream, (const float *)(act + p.h_off[L - 1]), (const float *)f.d_ret, (const float *)nullptr,
+                           d_idx, B, dz[(L - 1) & 1], d_loss, (int64_t)p.act, (int64_t)p.dz, (int64_t)B);
+    else
+        hipLaunchKernelGGL(k_fit_loss<4>, dim3((unsigned)n_m), dim3(256), 0, h->stream, (const float *)(act + p.h_off[L - 1]), (const float *)f.d_lab, (const float *)f.d_w,
+                           d_idx, B, dz[(L - 1) & 1], d_loss, (int64_t)p.act, (int64_t)p.dz, (int64_t)B);
     HIPCHECK(hipGetLastError());
     for (int l = L - 1; l >= 0; l--) {
         const int n_in = D.widths[l], n_out = D.widths[l + 1];
@@ -450,9 +573,9 @@ static int enqueue_grad(clothhip_handle *h, const FitPlan &p, int32_t n_m, const
 }
 
 // loss and gradient of `members` over idx [n_m][B], nothing updated; the call is valid
-static int run_grad(clothhip_handle *h, const int32_t *members, int32_t n_m, const int32_t *idx, int32_t B, float *grad_out, double *loss_out) {
+static int run_grad(clothhip_handle *h, const FitNet &net, const int32_t *members, int32_t n_m, const int32_t *idx, int32_t B, float *grad_out, double *loss_out) {
     auto &f = h->fit;
-    const FitPlan p = fit_plan(h, B);
+    const FitPlan p = fit_plan(net, B);
     HIPCHECK(hipSetDevice(h->device));
     if (int rc = fit_reserve(h, p, n_m)) return rc;
     if (int rc = f.d_idx.reserve((size_t)n_m * B * 4)) return rc;
@@ -460,7 +583,7 @@ static int run_grad(clothhip_handle *h, const int32_t *members, int32_t n_m, con
     HIPCHECK(hipMemcpyAsync(f.d_members, members, (size_t)n_m * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipMemcpyAsync(f.d_idx, idx, (size_t)n_m * B * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipEventRecord(h->ev0, h->stream));
-    if (int rc = enqueue_grad(h, p, n_m, f.d_idx, B, f.d_loss)) return rc;
+    if (int rc = enqueue_grad(h, net, p, n_m, f.d_idx, B, f.d_loss)) return rc;
     HIPCHECK(hipEventRecord(h->ev1, h->stream));
     h->have_timing = true;
     if (grad_out) HIPCHECK(hipMemcpyAsync(grad_out, f.d_grad, (size_t)n_m * p.grad * 4, hipMemcpyDeviceToHost, h->stream));
@@ -473,7 +596,7 @@ extern "C" int clothhip_policy_fit_grad(clothhip_handle *h, const int32_t *idx, 
     if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
     if (int rc = check_fit_state(h, false)) return rc;
     if (int rc = check_fit_rows(h, 1, idx, B, B)) return rc;
-    return run_grad(h, SHARED_ROW, 1, idx, B, grad_out, loss_out);
+    return run_grad(h, policy_net(h), SHARED_ROW, 1, idx, B, grad_out, loss_out);
 }
 
 extern "C" int clothhip_policy_fit_grad_members(clothhip_handle *h, const int32_t *members, int32_t n_m, const int32_t *idx, int32_t B, float *grad_out,
@@ -482,7 +605,7 @@ extern "C" int clothhip_policy_fit_grad_members(clothhip_handle *h, const int32_
     if (int rc = check_fit_state(h, true)) return rc;
     if (int rc = check_fit_members(h, members, n_m)) return rc;
     if (int rc = check_fit_rows(h, n_m, idx, (int64_t)n_m * B, B)) return rc;
-    return run_grad(h, members, n_m, idx, B, grad_out, loss_out);
+    return run_grad(h, policy_net(h), members, n_m, idx, B, grad_out, loss_out);
 }
 
 // The loss alone of the shared network over any number of rows: chunks of at most FIT_MAX_BATCH through the forward pass above, each
@@ -496,12 +619,13 @@ extern "C" int clothhip_policy_fit_loss(clothhip_handle *h, const int32_t *idx, 
     if (int rc = check_fit_rows(h, 1, idx, n, Bmax)) return rc;
     if (!loss) return fail(CLOTHHIP_EINVAL, "NULL argument");
     auto &f = h->fit;
+    const FitNet net = policy_net(h);
     const int L = h->pol.mlp.n_layers;
     const int64_t n_chunks = (n + FIT_MAX_BATCH - 1) / FIT_MAX_BATCH;
     std::vector<double> sums;
     try { sums.resize((size_t)n_chunks); } catch (const std::bad_alloc &) { return fail(CLOTHHIP_ENOMEM, "out of host memory (%lld chunks)", (long long)n_chunks); }
     HIPCHECK(hipSetDevice(h->device));
-    if (int rc = fit_reserve(h, fit_plan(h, Bmax), 1)) return rc;
+    if (int rc = fit_reserve(h, fit_plan(net, Bmax), 1)) return rc;
     if (int rc = f.d_idx.reserve((size_t)n * 4)) return rc;
     if (int rc = f.d_loss.reserve((size_t)n_chunks * 8)) return rc;
     HIPCHECK(hipMemcpyAsync(f.d_members, SHARED_ROW, 4, hipMemcpyHostToDevice, h->stream));
@@ -509,9 +633,9 @@ extern "C" int clothhip_policy_fit_loss(clothhip_handle *h, const int32_t *idx, 
     HIPCHECK(hipEventRecord(h->ev0, h->stream));
     for (int64_t c = 0; c < n_chunks; c++) {
         const int32_t B = (int32_t)std::min<int64_t>(FIT_MAX_BATCH, n - c * FIT_MAX_BATCH);
-        const FitPlan p = fit_plan(h, B);
+        const FitPlan p = fit_plan(net, B);
         const int32_t *d_idx = f.d_idx + (size_t)c * FIT_MAX_BATCH;
-        if (int rc = enqueue_grad(h, p, 1, d_idx, B, nullptr)) return rc;
+        if (int rc = enqueue_grad(h, net, p, 1, d_idx, B, nullptr)) return rc;
         hipLaunchKernelGGL(k_fit_sqsum, dim3(1), dim3(256), 0, h->stream, (const float *)(f.d_act + p.h_off[L - 1]), (const float *)f.d_lab, (const float *)f.d_w, d_idx, B,
                            f.d_loss + c);
         HIPCHECK(hipGetLastError());
@@ -527,30 +651,35 @@ extern "C" int clothhip_policy_fit_loss(clothhip_handle *h, const int32_t *idx, 
 }
 
 // The forward alone on n stored rows, the same rows for every member: chunks through enqueue_grad, each chunk's y copied out to
-// d_pred [n_m][n][4] (k_fit_copy_y), one download. The call is valid.
-static int run_predict(clothhip_handle *h, const int32_t *members, int32_t n_m, const int32_t *idx, int64_t n, float *y_out) {
+// d_pred [n_m][n][net.out()] (k_fit_copy_y), where it stays: enqueued between the timing events, not synchronised. The call is valid.
+static int enqueue_predict(clothhip_handle *h, const FitNet &net, const int32_t *members, int32_t n_m, const int32_t *idx, int64_t n) {
     auto &f = h->fit;
-    const int L = h->pol.mlp.n_layers;
+    const int L = net.D.n_layers, W = net.out();
     const int32_t Bmax = (int32_t)std::min<int64_t>(n, std::min<int64_t>(FIT_MAX_BATCH, CLOTHHIP_FIT_MAX_MEMBER_ROWS / n_m));
     HIPCHECK(hipSetDevice(h->device));
-    if (int rc = fit_reserve(h, fit_plan(h, Bmax), n_m)) return rc;
+    if (int rc = fit_reserve(h, fit_plan(net, Bmax), n_m)) return rc;
     if (int rc = f.d_idx.reserve((size_t)n * 4)) return rc;
-    if (int rc = f.d_pred.reserve((size_t)n_m * n * 4 * 4)) return rc;
+    if (int rc = f.d_pred.reserve((size_t)n_m * n * W * 4)) return rc;
     HIPCHECK(hipMemcpyAsync(f.d_members, members, (size_t)n_m * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipMemcpyAsync(f.d_idx, idx, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipEventRecord(h->ev0, h->stream));
     for (int64_t r0 = 0; r0 < n; r0 += Bmax) {
         const int32_t B = (int32_t)std::min<int64_t>(Bmax, n - r0);
-        const FitPlan p = fit_plan(h, B);
-        if (int rc = enqueue_grad(h, p, n_m, f.d_idx + (size_t)r0, B, nullptr, true)) return rc;
-        const int32_t blocks = (4 * B + 255) / 256;
-        hipLaunchKernelGGL(k_fit_copy_y, dim3((unsigned)blocks * (unsigned)n_m), dim3(256), 0, h->stream, (const float *)(f.d_act + p.h_off[L - 1]), B,
-                           f.d_pred + (size_t)r0 * 4, (int64_t)p.act, (int64_t)n * 4, blocks);
+        const FitPlan p = fit_plan(net, B);
+        if (int rc = enqueue_grad(h, net, p, n_m, f.d_idx + (size_t)r0, B, nullptr, true)) return rc;
+        const int32_t blocks = (W * B + 255) / 256;
+        hipLaunchKernelGGL(k_fit_copy_y, dim3((unsigned)blocks * (unsigned)n_m), dim3(256), 0, h->stream, (const float *)(f.d_act + p.h_off[L - 1]), W * B,
+                           f.d_pred + (size_t)r0 * W, (int64_t)p.act, (int64_t)n * W, blocks);
         HIPCHECK(hipGetLastError());
     }
     HIPCHECK(hipEventRecord(h->ev1, h->stream));
     h->have_timing = true;
-    HIPCHECK(hipMemcpyAsync(y_out, f.d_pred, (size_t)n_m * n * 4 * 4, hipMemcpyDeviceToHost, h->stream));
+    return 0;
+}
+// ... and one download
+static int run_predict(clothhip_handle *h, const FitNet &net, const int32_t *members, int32_t n_m, const int32_t *idx, int64_t n, float *y_out) {
+    if (int rc = enqueue_predict(h, net, members, n_m, idx, n)) return rc;
+    HIPCHECK(hipMemcpyAsync(y_out, h->fit.d_pred, (size_t)n_m * n * net.out() * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(hipStreamSynchronize(h->stream));
     return 0;
 }
@@ -561,7 +690,7 @@ extern "C" int clothhip_policy_fit_predict(clothhip_handle *h, const int32_t *id
     if (int rc = check_fit_state(h, false)) return rc;
     if (int rc = check_fit_rows(h, 1, idx, n, (int32_t)std::min<int64_t>(n, FIT_MAX_BATCH))) return rc;
     if (!y_out) return fail(CLOTHHIP_EINVAL, "NULL argument");
-    return run_predict(h, SHARED_ROW, 1, idx, n, y_out);
+    return run_predict(h, policy_net(h), SHARED_ROW, 1, idx, n, y_out);
 }
 
 extern "C" int clothhip_policy_fit_predict_members(clothhip_handle *h, const int32_t *members, int32_t n_m, const int32_t *idx, int64_t n, float *y_out) {
@@ -572,41 +701,40 @@ extern "C" int clothhip_policy_fit_predict_members(clothhip_handle *h, const int
     if (n_m > CLOTHHIP_FIT_MAX_MEMBER_ROWS) return fail(CLOTHHIP_EINVAL, "n_m = %d members in one call, at most %d", n_m, CLOTHHIP_FIT_MAX_MEMBER_ROWS);
     if (int rc = check_fit_rows(h, 1, idx, n, 1)) return rc;
     if (!y_out) return fail(CLOTHHIP_EINVAL, "NULL argument");
-    return run_predict(h, members, n_m, idx, n, y_out);
+    return run_predict(h, policy_net(h), members, n_m, idx, n, y_out);
 }
 
 // ---- the optimizer ----------------------------------------------------------------------------------------------------------------------
 // the per-row optimizer state exists from the first step after a new network: every row fresh
-static int ensure_row_state(clothhip_handle *h) {
-    auto &f = h->fit;
-    const size_t rows = fit_rows(h);
-    if (f.row_t.size() == rows && f.row_zero.size() == rows) return 0;
-    try { f.row_t.assign(rows, 0); f.row_zero.assign(rows, 1); } catch (const std::bad_alloc &) {
-        f.row_t.clear(); f.row_zero.clear();
+static int ensure_row_state(const FitNet &net) {
+    const size_t rows = net.rows();
+    if (net.row_t.size() == rows && net.row_zero.size() == rows) return 0;
+    try { net.row_t.assign(rows, 0); net.row_zero.assign(rows, 1); } catch (const std::bad_alloc &) {
+        net.row_t.clear(); net.row_zero.clear();
         return fail(CLOTHHIP_ENOMEM, "out of host memory (%zu rows)", rows);
     }
     return 0;
 }
 
 // n_steps optimizer steps of `members` with the optimizers p [n_m] over idx [n_steps][n_m][B]; the call is valid and n_steps >= 1
-static int run_fit(clothhip_handle *h, const ClothFitParams *p, const int32_t *members, int32_t n_m, const int32_t *idx, int32_t n_steps, int32_t B,
-                   double *loss_out) {
+static int run_fit(clothhip_handle *h, const FitNet &net, const ClothFitParams *p, const int32_t *members, int32_t n_m, const int32_t *idx, int32_t n_steps,
+                   int32_t B, double *loss_out) {
     const bool adam = p[0].optimizer == (float)CLOTHHIP_FIT_ADAM;
     auto &f = h->fit;
-    const MlpDesc &D = h->pol.mlp;
-    const FitPlan pl = fit_plan(h, B);
-    const size_t n = h->pol.mlp_n_params, stride = (size_t)D.stride, n_sm = (size_t)n_steps * n_m;
-    const size_t n_moments = h->pol.pop_rows ? (size_t)h->pol.pop_rows * stride : n;
+    const MlpDesc &D = net.D;
+    const FitPlan pl = fit_plan(net, B);
+    const size_t n = net.n_params, stride = (size_t)D.stride, n_sm = (size_t)n_steps * n_m;
+    const size_t n_moments = net.pop_rows ? (size_t)net.pop_rows * stride : n;
     // the step constants of every (step, member), in double on the host, then rounded to float; nothing of the handle changes yet
     std::vector<float> hyper;
     try { hyper.assign(n_sm * FIT_HYPER, 0.0f); } catch (const std::bad_alloc &) { return fail(CLOTHHIP_ENOMEM, "out of host memory (%zu step constants)", n_sm * FIT_HYPER); }
-    if (int rc = ensure_row_state(h)) return rc;
+    if (int rc = ensure_row_state(net)) return rc;
     for (int s = 0; s < n_steps; s++)
         for (int32_t j = 0; j < n_m; j++) {
             float *q = hyper.data() + ((size_t)s * n_m + j) * FIT_HYPER;
             const ClothFitParams &pj = p[j];
             if (adam) {
-                const double b1 = (double)pj.beta1, b2 = (double)pj.beta2, t = (double)(f.row_t[members[j]] + s + 1);
+                const double b1 = (double)pj.beta1, b2 = (double)pj.beta2, t = (double)(net.row_t[members[j]] + s + 1);
                 const double a_t = (double)pj.lr * std::sqrt(1.0 - std::pow(b2, t)) / (1.0 - std::pow(b1, t));
                 q[0] = (float)a_t; q[1] = pj.beta1; q[2] = (float)(1.0 - b1); q[3] = pj.beta2; q[4] = (float)(1.0 - b2); q[5] = pj.eps;
             } else {
@@ -620,28 +748,28 @@ static int run_fit(clothhip_handle *h, const ClothFitParams *p, const int32_t *m
     if (int rc = f.d_hyper.reserve(n_sm * FIT_HYPER * 4)) return rc;
     // the moments of the whole table. A table of another network's size holds no row's state (every row is flagged read-as-zeros by
     // fit_forget when the network changes), so growing it loses nothing
-    if (int rc = f.d_m.reserve(n_moments * 4)) return rc;
-    if (int rc = f.d_v.reserve(n_moments * 4)) return rc;
+    if (int rc = net.d_m.reserve(n_moments * 4)) return rc;
+    if (int rc = net.d_v.reserve(n_moments * 4)) return rc;
     // from here on the call goes through (but for a failure of the runtime itself)
     for (int32_t j = 0; j < n_m; j++) {
         const int32_t g = members[j];
-        if (f.row_zero[g]) {
-            HIPCHECK(hipMemsetAsync(f.d_m + (size_t)g * stride, 0, n * 4, h->stream));
-            HIPCHECK(hipMemsetAsync(f.d_v + (size_t)g * stride, 0, n * 4, h->stream));
-            f.row_zero[g] = 0;
+        if (net.row_zero[g]) {
+            HIPCHECK(hipMemsetAsync(net.d_m + (size_t)g * stride, 0, n * 4, h->stream));
+            HIPCHECK(hipMemsetAsync(net.d_v + (size_t)g * stride, 0, n * 4, h->stream));
+            net.row_zero[g] = 0;
         }
-        f.row_t[g] += n_steps;
+        net.row_t[g] += n_steps;
     }
     HIPCHECK(hipMemcpyAsync(f.d_members, members, (size_t)n_m * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipMemcpyAsync(f.d_idx, idx, n_sm * B * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipMemcpyAsync(f.d_hyper, hyper.data(), n_sm * FIT_HYPER * 4, hipMemcpyHostToDevice, h->stream));
     FitOptArgs o = {};
-    o.theta = h->pol.pop_rows ? h->pol.d_pop : h->pol.d_mlp; o.m = f.d_m; o.v = f.d_v; o.g = f.d_grad; o.members = f.d_members;
+    o.theta = net.theta; o.m = net.d_m; o.v = net.d_v; o.g = f.d_grad; o.members = f.d_members;
     o.stride = (int64_t)stride; o.n = (int64_t)n; o.blocks = (int32_t)((n + 255) / 256);
     const dim3 ogrid((unsigned)o.blocks * (unsigned)n_m);
     HIPCHECK(hipEventRecord(h->ev0, h->stream));
     for (int s = 0; s < n_steps; s++) {
-        if (int rc = enqueue_grad(h, pl, n_m, f.d_idx + (size_t)s * n_m * B, B, f.d_loss + (size_t)s * n_m)) return rc;
+        if (int rc = enqueue_grad(h, net, pl, n_m, f.d_idx + (size_t)s * n_m * B, B, f.d_loss + (size_t)s * n_m)) return rc;
         o.hyper = f.d_hyper + (size_t)s * n_m * FIT_HYPER;
         if (adam) hipLaunchKernelGGL(k_fit_adam, ogrid, dim3(256), 0, h->stream, o);
         else hipLaunchKernelGGL(k_fit_sgd, ogrid, dim3(256), 0, h->stream, o);
@@ -662,7 +790,7 @@ extern "C" int clothhip_policy_fit(clothhip_handle *h, const ClothFitParams *p, 
     if (int rc = check_fit_rows(h, 1, idx, (int64_t)n_steps * B, B)) return rc;
     if (int rc = check_fit_params(p, -1)) return rc;
     if (n_steps == 0) return 0;
-    return run_fit(h, p, SHARED_ROW, 1, idx, n_steps, B, loss_out);
+    return run_fit(h, policy_net(h), p, SHARED_ROW, 1, idx, n_steps, B, loss_out);
 }
 
 extern "C" int clothhip_policy_fit_members(clothhip_handle *h, const ClothFitParams *p, const int32_t *members, int32_t n_m, const int32_t *idx,
@@ -678,7 +806,7 @@ extern "C" int clothhip_policy_fit_members(clothhip_handle *h, const ClothFitPar
         if (p[j].optimizer != p[0].optimizer) return fail(CLOTHHIP_EINVAL, "p[%d].optimizer = %g, p[0].optimizer = %g: one optimizer per call", j, (double)p[j].optimizer, (double)p[0].optimizer);
     }
     if (n_steps == 0) return 0;
-    return run_fit(h, p, members, n_m, idx, n_steps, B, loss_out);
+    return run_fit(h, policy_net(h), p, members, n_m, idx, n_steps, B, loss_out);
 }
 
 extern "C" int clothhip_policy_fit_reset(clothhip_handle *h) {
@@ -697,5 +825,89 @@ extern "C" int clothhip_policy_fit_reset_members(clothhip_handle *h, const int32
     if (int rc = check_fit_members(h, members, n_m)) return rc;
     if (h->fit.row_t.empty()) return 0;               // every row is fresh already
     for (int32_t j = 0; j < n_m; j++) { h->fit.row_t[members[j]] = 0; h->fit.row_zero[members[j]] = 1; }
+    return 0;
+}
+
+// ---- the critic: the value network as one more one-row table of the trainer above (clothhip.h: FITTING THE CRITIC) ------------------------
+extern "C" int clothhip_value_fit_grad(clothhip_handle *h, const int32_t *idx, int32_t B, float *grad_out, double *loss_out) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (int rc = check_value_state(h)) return rc;
+    if (int rc = check_fit_rows(h, 1, idx, B, B)) return rc;
+    return run_grad(h, value_net(h), SHARED_ROW, 1, idx, B, grad_out, loss_out);
+}
+
+extern "C" int clothhip_value_fit(clothhip_handle *h, const ClothFitParams *p, const int32_t *idx, int32_t n_steps, int32_t B, double *loss_out) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (!p) return fail(CLOTHHIP_EINVAL, "NULL argument");
+    if (n_steps < 0) return fail(CLOTHHIP_EINVAL, "n_steps < 0");
+    if (int rc = check_value_state(h)) return rc;
+    if (int rc = check_fit_rows(h, 1, idx, (int64_t)n_steps * B, B)) return rc;
+    if (int rc = check_fit_params(p, -1)) return rc;
+    if (n_steps == 0) return 0;
+    return run_fit(h, value_net(h), p, SHARED_ROW, 1, idx, n_steps, B, loss_out);
+}
+
+extern "C" int clothhip_value_fit_reset(clothhip_handle *h) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (int rc = check_idle(h)) return rc;
+    h->value_forget();
+    return 0;
+}
+
+extern "C" int clothhip_value_predict(clothhip_handle *h, const int32_t *idx, int64_t n, float *v_out) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (n < 1 || n > INT32_MAX) return fail(CLOTHHIP_EINVAL, "n = %lld outside [1, %d]", (long long)n, INT32_MAX);
+    if (int rc = check_value_state(h)) return rc;
+    if (int rc = check_fit_rows(h, 1, idx, n, (int32_t)std::min<int64_t>(n, FIT_MAX_BATCH))) return rc;
+    if (!v_out) return fail(CLOTHHIP_EINVAL, "NULL argument");
+    return run_predict(h, value_net(h), SHARED_ROW, 1, idx, n, v_out);
+}
+
+// ---- advantages and value targets on the device (cloth_fit_gae.hpp has the definition and the order) ------------------------------------
+extern "C" int clothhip_fit_data_gae(clothhip_handle *h, int64_t first, int64_t n, const ClothGaeParams *p, float *adv_out, float *ret_out) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (int rc = check_idle(h)) return rc;
+    if (h->val.mlp.n_layers < 1) return fail(CLOTHHIP_ESTATE, "no value network on this handle: call clothhip_set_value_mlp first");
+    if (int rc = check_range(h, first, n)) return rc;
+    if (!p) return fail(CLOTHHIP_EINVAL, "NULL argument");
+    if (!std::isfinite(p->gamma) || !std::isfinite(p->lambda) || !std::isfinite(p->w_scale))
+        return fail(CLOTHHIP_EINVAL, "gamma %g, lambda %g, w_scale %g: all three are finite", p->gamma, p->lambda, (double)p->w_scale);
+    if (p->gamma < 0.0 || p->gamma > 1.0 || p->lambda < 0.0 || p->lambda > 1.0)
+        return fail(CLOTHHIP_EINVAL, "gamma %g, lambda %g: both lie in [0, 1]", p->gamma, p->lambda);
+    if (p->flags & ~(CLOTHHIP_GAE_WRITE_WEIGHTS | CLOTHHIP_GAE_NORMALIZE)) return fail(CLOTHHIP_EINVAL, "unknown flags 0x%x", p->flags);
+    auto &f = h->fit;
+    for (int64_t i = 0; i < n; i++) {
+        const int32_t nx = f.h_next[(size_t)(first + i)];      // (greater than first + i where it is a row: clothhip_fit_data_set_transitions)
+        if (nx >= 0 && nx >= first + n)
+            return fail(CLOTHHIP_EINVAL, "row %lld: its successor %d lies outside the rows [%lld, %lld + %lld)", (long long)(first + i), nx, (long long)first, (long long)first, (long long)n);
+    }
+    if (n == 0) return 0;
+    std::vector<int32_t> idx;
+    try { idx.resize((size_t)n); } catch (const std::bad_alloc &) { return fail(CLOTHHIP_ENOMEM, "out of host memory (%lld rows)", (long long)n); }
+    for (int64_t i = 0; i < n; i++) idx[(size_t)i] = (int32_t)(first + i);
+    HIPCHECK(hipSetDevice(h->device));
+    if (int rc = f.d_gae_a.reserve((size_t)n * 8)) return rc;
+    if (int rc = f.d_gae_stat.reserve(16)) return rc;
+    if (int rc = f.d_adv.reserve((size_t)n * 4)) return rc;
+    if (int rc = enqueue_predict(h, value_net(h), SHARED_ROW, 1, idx.data(), n)) return rc;      // (records ev0; the scan moves ev1 behind itself)
+    const bool write_w = (p->flags & CLOTHHIP_GAE_WRITE_WEIGHTS) != 0, normalize = (p->flags & CLOTHHIP_GAE_NORMALIZE) != 0;
+    GaeArgs a = {};
+    a.v = f.d_pred; a.rew = f.d_rew; a.next = f.d_next; a.ret = f.d_ret; a.w = f.d_w; a.A = f.d_gae_a; a.adv = f.d_adv; a.stat = f.d_gae_stat;
+    a.first = first; a.n = n; a.gamma = p->gamma; a.c = p->gamma * p->lambda; a.w_scale = (double)p->w_scale; a.normalize = normalize ? 1 : 0;
+    const dim3 grid((unsigned)((n + GAE_THREADS - 1) / GAE_THREADS));
+    hipLaunchKernelGGL(k_gae_rows, grid, dim3(GAE_THREADS), 0, h->stream, a);
+    HIPCHECK(hipGetLastError());
+    if (write_w) {
+        if (normalize) {
+            hipLaunchKernelGGL(k_gae_stats, dim3(1), dim3(GAE_THREADS), 0, h->stream, a);
+            HIPCHECK(hipGetLastError());
+        }
+        hipLaunchKernelGGL(k_gae_weights, grid, dim3(GAE_THREADS), 0, h->stream, a);
+        HIPCHECK(hipGetLastError());
+    }
+    HIPCHECK(hipEventRecord(h->ev1, h->stream));
+    if (adv_out) HIPCHECK(hipMemcpyAsync(adv_out, f.d_adv, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+    if (ret_out) HIPCHECK(hipMemcpyAsync(ret_out, f.d_ret + (size_t)first, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));      // (idx, a host table the upload read, goes out of scope)
     return 0;
 }

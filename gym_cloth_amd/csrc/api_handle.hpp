@@ -153,13 +153,27 @@ struct clothhip_handle : HostPlan {
         float pop_sigma = 0.0f;
         int32_t pop_flags = 0;
     } pol;
-    // The supervised trainer of the handle's networks (api_fit.hip: clothhip_fit_data_*, clothhip_policy_fit*); a new network of either
-    // kind (api_policy.hip's drop_network) restarts the optimizer through fit_forget below, nothing else outside api_fit.hip touches it.
+    // The value network (api_policy.hip: clothhip_set_value_mlp), beside the policy and independent of it: n_layers 0: none; mlp.params =
+    // d_mlp, no member map, stride 0 -- to the trainer (api_fit.hip) a weight table of ONE row. No launch evaluates it.
+    struct Value {
+        MlpDesc mlp = {};
+        Buffer<float> d_mlp;
+        size_t n_params = 0;
+    } val;
+    // The supervised trainer of the handle's networks (api_fit.hip: clothhip_fit_data_*, clothhip_policy_fit*, clothhip_value_fit*); a new
+    // network of either kind (api_policy.hip's drop_network) restarts the policy's optimizer through fit_forget below, a new value network
+    // the critic's through value_forget; nothing else outside api_fit.hip touches it.
     struct Fit {
         // the dataset: n rows of cap allocated, d_obs [cap][3P], d_lab [cap][4] and the per-row loss weights d_w [cap] float32 (grown
         // geometrically, contents kept; d_w is the one column a caller may rewrite: clothhip_fit_data_set_weights)
         Buffer<float> d_obs, d_lab, d_w;
         int64_t n = 0, cap = 0;
+        // the episode structure and the value targets (clothhip_fit_data_set_transitions / _set_returns; they grow with the rows): the
+        // reward d_rew [cap], the successor row d_next [cap] (or CLOTHHIP_FIT_NEXT_*) with its host mirror h_next [n], against which
+        // clothhip_fit_data_gae checks a range without a download, and the value target d_ret [cap]
+        Buffer<float> d_rew, d_ret;
+        Buffer<int32_t> d_next;
+        std::vector<int32_t> h_next;
         // rows named by where they lie (clothhip_fit_hold, clothhip_fit_data_append_launch): held [E][3P], one row per env that outlives
         // the launch tables (held_valid: some clothhip_fit_hold has filled it); the index table of one call and its not-finite flag
         Buffer<float> d_held;
@@ -179,9 +193,18 @@ struct clothhip_handle : HostPlan {
         Buffer<int32_t> d_idx, d_members;
         Buffer<float> d_act, d_dz, d_part, d_grad, d_hyper;
         Buffer<double> d_loss;
-        Buffer<float> d_pred;        // clothhip_policy_fit_predict*: y of every member and row, [n_m][n][4]
+        Buffer<float> d_pred;        // clothhip_policy_fit_predict*: y of every member and row, [n_m][n][4]; clothhip_value_predict and clothhip_fit_data_gae: v [n]
+        // the value network's optimizer: its own moments [n_params], step count and read-as-zeros flag (vectors of ONE row, empty until
+        // the first step after a new value network), under the rules of the policy's above
+        Buffer<float> d_val_m, d_val_v;
+        std::vector<int64_t> val_t;
+        std::vector<uint8_t> val_zero;
+        // clothhip_fit_data_gae: A of every row of the range as a double, the advantages as floats, {mean, std} of the normalisation
+        Buffer<double> d_gae_a, d_gae_stat;
+        Buffer<float> d_adv;
     } fit;
     void fit_forget() { fit.row_t.clear(); fit.row_zero.clear(); }
+    void value_forget() { fit.val_t.clear(); fit.val_zero.clear(); }
     // The cross-entropy planner (api_plan.hip: clothhip_plan_cem on the SCRATCH handle, clothhip_plan_sample / _refit on the handle given), all
     // sized on demand: the distribution d_mean, d_std [E][H][4], the best so far d_best_a [E][H][4], d_best_s [E], the source's done flags, the
     // action tables d_x [H][E K][4] (one, or one per iteration when the caller wants them back), d_scores [n_iters][E][K], the elite flags and

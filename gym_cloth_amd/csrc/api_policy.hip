@@ -11,11 +11,12 @@
 
 // ---- a learned policy: the handle's network (cloth_policy_mlp.hpp) ----------------------------------------------------------------------
 // the shape rules of every entry that takes a network
-static int check_mlp_shape(const clothhip_handle *h, int32_t n_layers, const int32_t *widths) {
+static int check_mlp_shape(const clothhip_handle *h, int32_t n_layers, const int32_t *widths, int32_t n_out = MLP_OUT) {
     if (n_layers < 1 || n_layers > MLP_MAX_LAYERS) return fail(CLOTHHIP_EINVAL, "n_layers %d outside [0, %d]", n_layers, MLP_MAX_LAYERS);
     if (!widths) return fail(CLOTHHIP_EINVAL, "NULL argument");
     if (widths[0] != 3 * h->P) return fail(CLOTHHIP_EINVAL, "the network's input width is %d, the '1d' observation has %d values", widths[0], 3 * h->P);
-    if (widths[n_layers] != MLP_OUT) return fail(CLOTHHIP_EINVAL, "the network's output width is %d, an action has %d values", widths[n_layers], MLP_OUT);
+    if (widths[n_layers] != n_out)
+        return fail(CLOTHHIP_EINVAL, n_out == MLP_OUT ? "the network's output width is %d, an action has %d values" : "the network's output width is %d, a value is %d number", widths[n_layers], n_out);
     for (int l = 1; l < n_layers; l++)
         if (widths[l] < 1 || widths[l] > MLP_MAX_WIDTH) return fail(CLOTHHIP_EINVAL, "hidden width %d (layer %d) outside [1, %d]", widths[l], l, MLP_MAX_WIDTH);
     return 0;
@@ -52,6 +53,39 @@ extern "C" int clothhip_set_policy_mlp(clothhip_handle *h, int32_t n_layers, con
     HIPCHECK(hipStreamSynchronize(h->stream));      // the host blob is never retained
     h->pol.mlp = mlp_desc(n_layers, widths, h->pol.d_mlp, nullptr, 0);
     h->pol.mlp_n_params = need;
+    return 0;
+}
+
+// ---- the value network (clothhip.h: ACTOR-CRITIC FROM REWARD): the policy's shape rules with ONE output; the handle's other network ------------
+extern "C" int clothhip_set_value_mlp(clothhip_handle *h, int32_t n_layers, const int32_t *widths, const float *params, size_t n_params) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (int rc = check_idle(h)) return rc;
+    auto drop = [h] { h->value_forget(); h->val.mlp = MlpDesc{}; h->val.n_params = 0; };
+    if (n_layers == 0) { drop(); return 0; }
+    if (int rc = check_mlp_shape(h, n_layers, widths, 1)) return rc;
+    if (!params) return fail(CLOTHHIP_EINVAL, "NULL argument");
+    const size_t need = mlp_param_count(n_layers, widths);
+    if (n_params != need) return fail(CLOTHHIP_EINVAL, "n_params = %zu, these widths hold %zu parameters", n_params, need);
+    HIPCHECK(hipSetDevice(h->device));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    drop();                                         // as clothhip_set_policy_mlp: a failure below leaves the handle without a value network
+    if (int rc = h->val.d_mlp.reserve(need * 4)) return rc;
+    HIPCHECK(hipMemcpyAsync(h->val.d_mlp, params, need * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    h->val.mlp = mlp_desc(n_layers, widths, h->val.d_mlp, nullptr, 0);
+    h->val.n_params = need;
+    return 0;
+}
+
+extern "C" int clothhip_get_value_mlp(clothhip_handle *h, float *out, size_t n_params) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (int rc = check_idle(h)) return rc;
+    if (h->val.mlp.n_layers < 1) return fail(CLOTHHIP_ESTATE, "no value network on this handle: call clothhip_set_value_mlp first");
+    if (!out) return fail(CLOTHHIP_EINVAL, "out is NULL");
+    if (n_params != h->val.n_params) return fail(CLOTHHIP_EINVAL, "n_params = %zu, the value network holds %zu parameters", n_params, h->val.n_params);
+    HIPCHECK(hipSetDevice(h->device));
+    HIPCHECK(hipMemcpyAsync(out, h->val.d_mlp, n_params * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
     return 0;
 }
 

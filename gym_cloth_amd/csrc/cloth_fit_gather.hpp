@@ -29,6 +29,7 @@ struct FitGatherArgs {
     const float *table[3];      // by source: obs [T * E][L], reset_obs [E * n_scripts][L], held [E][L] (the host has checked every index)
     const int32_t *rows;        // [n][4] = (source, row, label row or -1, destination row)
     const double *labels;       // [T * E][4] of the last armed launch, or NULL when no entry names a label or the labels are the records'
+                                // (an entry that names a label row with both tables NULL gets the label (0, 0, 0, 0))
     const unsigned char *records;   // [T * E] ClothStepRecord of the last launch: the label is (float)action[0..3], or NULL
     const float *weights;       // [n] the destination rows' loss weights in entry order, or NULL: 1.0f
     float *dst_obs, *dst_lab;   // destination tables [..][L], [..][4] (dst_lab may be NULL then)
@@ -68,8 +69,10 @@ __global__ __launch_bounds__(FIT_GATHER_THREADS) void k_fit_gather(FitGatherArgs
             if (a.records) {
                 const unsigned char *rec = a.records + (int64_t)lrow * FIT_REC_BYTES;
                 lv = rec[FIT_REC_RAN] == 1 ? (float)reinterpret_cast<const double *>(rec)[tid] : __uint_as_float(0x7fc00000u);
-            } else {
+            } else if (a.labels) {
                 lv = (float)a.labels[(int64_t)lrow * 4 + tid];
+            } else {
+                lv = 0.0f;      // CLOTHHIP_FIT_LABEL_ZERO: a leaf, no table is read
             }
             a.dst_lab[(int64_t)drow * 4 + tid] = lv;
             bad |= fit_not_finite(lv);
@@ -100,12 +103,12 @@ __global__ __launch_bounds__(256) void k_fit_sqsum(const float *y, const float *
     if (tid == 0) *sum = red[0];
 }
 
-// clothhip_policy_fit_predict*: member j's y of one chunk, [B][4] at y + j * y_step, to out + j * out_step -- 4 B contiguous floats, lane i
-// at base + 4 i on both sides. One workgroup per member and 256 elements
-__global__ __launch_bounds__(256) void k_fit_copy_y(const float *y, int32_t B, float *out, int64_t y_step, int64_t out_step, int32_t blocks) {
+// clothhip_policy_fit_predict* / clothhip_value_predict: member j's y of one chunk, n_vals = B * (output width) contiguous floats at
+// y + j * y_step, to out + j * out_step, lane i at base + 4 i on both sides. One workgroup per member and 256 elements
+__global__ __launch_bounds__(256) void k_fit_copy_y(const float *y, int32_t n_vals, float *out, int64_t y_step, int64_t out_step, int32_t blocks) {
     const int j = blockIdx.x / blocks, bx = blockIdx.x - j * blocks;
     const int i = bx * 256 + threadIdx.x;
-    if (i < 4 * B) out[(int64_t)j * out_step + i] = y[(int64_t)j * y_step + i];
+    if (i < n_vals) out[(int64_t)j * out_step + i] = y[(int64_t)j * y_step + i];
 }
 
 }  // namespace clothhip

@@ -33,6 +33,9 @@
 //     one workgroup per member). Multiplying by 1.0f and by 1.0 is exact: a dataset whose weights are all 1 gives the unweighted bits;
 //   * the optimizer (k_fit_adam / k_fit_sgd) is elementwise, each operation one float32 rounding (the library is built with
 //     -ffp-contract=off; division and sqrtf are the correctly rounded ones, no fast-math flag reaches this unit).
+//   * the value network (output width 1, clothhip.h: FITTING THE CRITIC) is one more table of one row for the same kernels: N = 1 in
+//     its last forward product, M = 1 in that layer's weight gradient, K = 1 in its input gradient -- each a tile whose other 63 rows,
+//     columns or 15 k are the zeros in LDS above; k_fit_loss<1> sums B squares in the order k_fit_loss<4> sums 4 B;
 //   The forward's summation order differs from mlp_eval's (64 interleaved lane sums and a butterfly there), so the trainer's y need not equal
 //   clothhip_policy_eval's bits; the blob it writes is evaluated by mlp_eval as any uploaded blob is.
 #pragma once
@@ -171,23 +174,33 @@ __global__ __launch_bounds__(64) void k_fit_colsum(const float *dz, int32_t B, i
 // dz[r][k] = fl(fl(w fl(y - a)) / fl(2 B)) with a = lab[rows[r]][k] and w = wgt[rows[r]]; loss = sum (double)w (double)(y - a)^2 / (4 B).
 // One workgroup of 256 per member: y, dz and the index rows at j times their per-member sizes, the loss at loss[j]. The four lanes of a
 // row read ONE weight (the same dword: one request); w = 1.0f leaves both products' bits alone, so an unweighted dataset keeps its bits.
-__global__ __launch_bounds__(256) void k_fit_loss(const float *y, const float *lab, const float *wgt, const int32_t *rows, int32_t B, float *dz,
-                                                  double *loss, int64_t y_step, int64_t dz_step, int64_t rows_step) {
+// W is the network's output width: 4, the policy, as above; 1, the value network (clothhip.h: FITTING THE CRITIC) -- lab is then the
+// column of value targets [n], there is no weight (wgt is not read), dz[r] = fl(fl(v - ret) / fl(B)) and loss = sum (double)(v - ret)^2 / (2 B):
+// the same order over B elements.
+template <int W> __global__ __launch_bounds__(256) void k_fit_loss(const float *y, const float *lab, const float *wgt, const int32_t *rows, int32_t B, float *dz,
+                                                                   double *loss, int64_t y_step, int64_t dz_step, int64_t rows_step) {
+    static_assert(W == 4 || W == 1, "an action or a value");
     __shared__ double red[256];
     const int64_t j = blockIdx.x;
     y += j * y_step; dz += j * dz_step; rows += j * rows_step;
-    const int tid = threadIdx.x, n = 4 * B;
-    const float two_b = (float)(2 * B);
+    const int tid = threadIdx.x, n = W * B;
+    const float den = (float)(W == 4 ? 2 * B : B);
     double s = 0.0;
     for (int i = tid; i < n; i += 256) {
-        const size_t row = (size_t)rows[i >> 2];
-        const float yv = y[i], av = lab[row * 4 + (i & 3)], wv = wgt[row];
+        const size_t row = (size_t)rows[i / W];
+        const float yv = y[i], av = lab[row * W + (i % W)];
         const float d = yv - av;
-        const float wd = wv * d;
-        dz[i] = wd / two_b;
         const double dd = (double)yv - (double)av;
         const double sq = dd * dd;
-        s = s + (double)wv * sq;
+        if (W == 4) {
+            const float wv = wgt[row];
+            const float wd = wv * d;
+            dz[i] = wd / den;
+            s = s + (double)wv * sq;
+        } else {
+            dz[i] = d / den;
+            s = s + sq;
+        }
     }
     red[tid] = s;
     __syncthreads();
@@ -195,7 +208,7 @@ __global__ __launch_bounds__(256) void k_fit_loss(const float *y, const float *l
         if (tid < o) red[tid] = red[tid] + red[tid + o];
         __syncthreads();
     }
-    if (tid == 0) loss[j] = red[0] / (double)(4 * (int64_t)B);
+    if (tid == 0) loss[j] = red[0] / (double)((W == 4 ? 4 : 2) * (int64_t)B);
 }
 
 // The optimizers: member j updates row members[j] of theta, m, v ([rows][stride]) from g + j * n with ITS OWN step constants

@@ -210,13 +210,14 @@ def dagger_collect(env, trainer, expert='oracle_corner', n_actions=12, beta=0.5,
         return dict(expert=expert, expert_mix=mix[idx, ee], expert_choices=None if choices is None else choices[idx, ee])
 
     return _collect_loop(env, trainer, n_actions, slots_per_launch, time_budget_ms, policy_noise, max_launches, launch_kw,
-                         lambda rows, slot: trainer.append_launch(rows), ('expert_took',))
+                         lambda rows, slot, out: trainer.append_launch(rows), ('expert_took',))
 
 
 def _collect_loop(env, trainer, n_actions, slots_per_launch, time_budget_ms, policy_noise, max_launches, launch_kw, append, record_keys):
     """The loop dagger_collect and reward_collect share: policy='mlp' launches of slots_per_launch slots that keep their observation
     tables on the device until every env has run n_actions slots; per launch the rows that ran (and lie within the n_actions) go to
-    append(rows int32[n, 3] in [t][e] order, slot int[n]: their per-env slot numbers), then the held rows move on. launch_kw(idx, ee):
+    append(rows int32[n, 3] in [t][e] order, slot int[n]: their per-env slot numbers, out: the launch's step_many dict), then the held
+    rows move on. launch_kw(idx, ee):
     further step_many keywords for the table rows idx [T, E]; record_keys: further [T, E] arrays of step_many's dict to keep per launch."""
     import time
     from .envs import hold_sources, slot_start_sources
@@ -250,7 +251,7 @@ def _collect_loop(env, trainer, n_actions, slots_per_launch, time_budget_ms, pol
         t_, e_ = np.nonzero(keep)                                           # [t][e] order
         if len(t_):
             rows = np.concatenate([slot_start_sources(out)[t_, e_], (t_ * E + e_)[:, None].astype(np.int32)], axis=1)
-            append(rows, slot[t_, e_])
+            append(rows, slot[t_, e_], out)
             res['row_env'].append(e_); res['row_slot'].append(slot[t_, e_])
             res['appended'] += len(t_)
         env.batch.fit_hold(hold_sources(out))
@@ -365,6 +366,28 @@ def _no_kw(scheme, kw, allowed):
         raise ValueError("scheme %r takes no %r" % (scheme, unknown))
 
 
+def _collection_returns(res, n_actions, gamma, n_envs):
+    """(G float64[n], complete bool[n], done bool[n], starts bool[n]) of the slots a _collect_loop run collected (res: its dict, with
+    'reset_before' in the records), in the order they were appended: the return-to-go of every slot, whether its episode completed
+    inside the collection, whether the slot ended it, whether the slot is the first collected one of its episode."""
+    N, carry, per_launch = int(n_actions), None, []
+    for rec in reversed(res['records']):                                    # the later launch first: a return looks ahead
+        ran = rec['ran'] & (rec['slot'] < N)
+        G, complete = returns_to_go(rec['rew'], ran, rec['done'], rec['reset_before'], gamma, carry)
+        carry = returns_carry(G, complete, ran, rec['reset_before'], carry)
+        t_, e_ = np.nonzero(ran)                                            # the order the rows were appended in
+        per_launch.append((G[t_, e_], complete[t_, e_], rec['done'][t_, e_]))
+    per_launch.reverse()
+    cat = lambda k, dt: np.concatenate([p[k] for p in per_launch]).astype(dt) if per_launch else np.zeros(0, dtype=dt)
+    G, complete, done = cat(0, np.float64), cat(1, bool), cat(2, bool)
+    # an episode starts at an env's first collected slot and after every slot that ended one (a reset a time slice completed without a
+    # record of its own shows in no reset_before)
+    ended = np.zeros((N + 1, int(n_envs)), dtype=bool)
+    ended[0] = True
+    ended[res['row_slot'] + 1, res['row_env']] = done
+    return G, complete, done, ended[res['row_slot'], res['row_env']]
+
+
 def reward_collect(env, trainer, n_actions=12, gamma=1.0, scheme='filter', policy_noise=None, slots_per_launch=12, time_budget_ms=0.0,
                    max_launches=None, **scheme_kw):
     """Collect rows to FIT FROM REWARD: dagger_collect's loop with no expert armed. The env's network (plus policy_noise [n_actions, E,
@@ -383,29 +406,14 @@ def reward_collect(env, trainer, n_actions=12, gamma=1.0, scheme='filter', polic
     first = trainer.size()
     spent = {'append': 0.0}
 
-    def append(rows, slot):
+    def append(rows, slot, out):
         t0 = time.perf_counter()
         trainer.append_launch(rows, labels="action", weights=np.zeros(len(rows), dtype=np.float32))
         spent['append'] += time.perf_counter() - t0
 
     res = _collect_loop(env, trainer, n_actions, slots_per_launch, time_budget_ms, policy_noise, max_launches, lambda idx, ee: {}, append,
                         ('reset_before',))
-    N, carry, per_launch = int(n_actions), None, []
-    for rec in reversed(res['records']):                                    # the later launch first: a return looks ahead
-        ran = rec['ran'] & (rec['slot'] < N)
-        G, complete = returns_to_go(rec['rew'], ran, rec['done'], rec['reset_before'], gamma, carry)
-        carry = returns_carry(G, complete, ran, rec['reset_before'], carry)
-        t_, e_ = np.nonzero(ran)                                            # the order the rows were appended in
-        per_launch.append((G[t_, e_], complete[t_, e_], rec['done'][t_, e_]))
-    per_launch.reverse()
-    cat = lambda k, dt: np.concatenate([p[k] for p in per_launch]).astype(dt) if per_launch else np.zeros(0, dtype=dt)
-    G, complete, done = cat(0, np.float64), cat(1, bool), cat(2, bool)
-    # an episode starts at an env's first collected slot and after every slot that ended one (a reset a time slice completed without a
-    # record of its own shows in no reset_before)
-    ended = np.zeros((N + 1, env.E), dtype=bool)
-    ended[0] = True
-    ended[res['row_slot'] + 1, res['row_env']] = done
-    starts = ended[res['row_slot'], res['row_env']]
+    G, complete, done, starts = _collection_returns(res, n_actions, gamma, env.E)
     w = np.zeros(len(G), dtype=np.float32)
     w[complete] = reward_weights(G[complete], scheme, **scheme_kw)
     t0 = time.perf_counter()
@@ -425,3 +433,102 @@ def reward_fit(env, trainer, col, n_steps=100, batch_size=64, seed=0):
         raise ValueError("the trainer belongs to another env")
     return {'losses': trainer.step(n_steps, batch_size, seed), 'rows': trainer.size(), 'appended': int(col['appended']),
             'weighted': int(np.count_nonzero(col['weights']))}
+
+
+# ---- actor-critic from reward: the episode structure of a collection, a critic's value targets, GAE weights ------------------
+def episode_links(row_env, row_slot, done, n_envs, first):
+    """int32[n]: the successor column (ClothBatch.fit_set_transitions' `next`) of a collection's rows in append order, the first of them
+    dataset row `first`. row_env / row_slot int[n]: the env and the per-env slot number of every row, done bool[n]: the row's slot ended
+    its episode. The rule reward_collect uses for episode starts, read forwards: a row whose slot ended its episode is
+    _lib.FIT_NEXT_TERMINAL; otherwise its successor is the same env's NEXT collected row (rows are appended in time order, so it lies
+    later; row_slot must ascend per env); the last row of an env, if it is not done, has none: _lib.FIT_NEXT_NONE, a leaf --
+    actor_critic_collect appends the state behind an env's last open slot as exactly such a row."""
+    from ._lib import FIT_NEXT_NONE, FIT_NEXT_TERMINAL
+    env_ = np.asarray(row_env).astype(np.int64).reshape(-1)
+    slot = np.asarray(row_slot).astype(np.int64).reshape(-1)
+    done = np.asarray(done, dtype=bool).reshape(-1)
+    n = len(env_)
+    if not (len(slot) == len(done) == n):
+        raise ValueError("row_env, row_slot and done must have one length")
+    if n and (env_.min() < 0 or env_.max() >= int(n_envs)):
+        raise ValueError("row_env must lie in [0, %d)" % int(n_envs))
+    nxt = np.full(n, FIT_NEXT_NONE, dtype=np.int64)
+    later = np.full(int(n_envs), -1, dtype=np.int64)                        # per env: the row met last, walking backwards
+    for i in range(n - 1, -1, -1):
+        e, k = env_[i], later[env_[i]]
+        if k >= 0 and slot[k] <= slot[i]:
+            raise ValueError("the rows of env %d are not in time order" % e)
+        if done[i]:
+            nxt[i] = FIT_NEXT_TERMINAL
+        elif k >= 0:
+            nxt[i] = int(first) + k
+        later[e] = i
+    return nxt.astype(np.int32)
+
+
+def actor_critic_collect(env, trainer, n_actions=12, policy_noise=None, slots_per_launch=12, time_budget_ms=0.0, max_launches=None):
+    """Collect rows for an ACTOR-CRITIC step: reward_collect's loop (labels = the action the slot executed, weight 0), which also
+    writes the transitions. Per launch the rows that ran are appended where they lie; and where an env's LAST collected slot (its slot
+    n_actions - 1) left its episode open, the state after that slot -- row t * E + e of that launch's observation table -- is appended
+    behind them as a LEAF (labels="zero", weight 0): a row with no transition of its own whose value bootstraps the rows before it. No
+    row is discarded. When the loop ends, ONE fit_set_transitions call writes every row's reward and successor (episode_links).
+    Returns _collect_loop's dict plus first: the dataset index of the first appended row, ds_env / ds_slot int[n], leaf / done bool[n],
+    rew float32[n], next int32[n]: the env, per-env slot number (a leaf: n_actions), kind, reward and successor of every appended row
+    in DATASET order (n = appended + open_rows), open_rows: the leaves, nonleaf int[appended]: the dataset indices of the other rows,
+    episode_return float64[episodes]: the undiscounted return from the first collected slot of every episode that completed,
+    t_append / t_set_transitions: seconds in those calls. Nothing is trained here: actor_critic_fit below does."""
+    import time
+    from ._lib import FIT_SRC_SLOTS
+    first, N, E = trainer.size(), int(n_actions), env.E
+    spent = {'append': 0.0}
+    cols = {'env': [], 'slot': [], 'leaf': [], 'done': [], 'rew': []}
+
+    def append(rows, slot, out):
+        t_, e_ = rows[:, 2] // E, rows[:, 2] % E
+        done = np.asarray(out['done'], dtype=bool)[t_, e_]
+        open_ = (slot == N - 1) & ~done
+        t0 = time.perf_counter()
+        trainer.append_launch(rows, labels="action", weights=np.zeros(len(rows), dtype=np.float32))
+        if open_.any():
+            leaves = np.stack([np.full(int(open_.sum()), FIT_SRC_SLOTS), rows[open_, 2], np.zeros(int(open_.sum()), dtype=np.int64)], axis=1)
+            trainer.append_launch(leaves, labels="zero", weights=np.zeros(len(leaves), dtype=np.float32))
+        spent['append'] += time.perf_counter() - t0
+        k = int(open_.sum())
+        cols['env'] += [e_, e_[open_]]; cols['slot'] += [slot, np.full(k, N)]
+        cols['leaf'] += [np.zeros(len(rows), dtype=bool), np.ones(k, dtype=bool)]
+        cols['done'] += [done, np.zeros(k, dtype=bool)]
+        cols['rew'] += [np.asarray(out['rew'], dtype=np.float64)[t_, e_], np.zeros(k)]
+
+    res = _collect_loop(env, trainer, N, slots_per_launch, time_budget_ms, policy_noise, max_launches, lambda idx, ee: {}, append,
+                        ('reset_before',))
+    cat = lambda k, dt: np.concatenate(cols[k]).astype(dt) if cols[k] else np.zeros(0, dtype=dt)
+    ds_env, ds_slot, leaf, done, rew = cat('env', np.int64), cat('slot', np.int64), cat('leaf', bool), cat('done', bool), cat('rew', np.float32)
+    nxt = episode_links(ds_env, ds_slot, done, E, first)
+    t0 = time.perf_counter()
+    if len(nxt):
+        env.batch.fit_set_transitions(rew, nxt, first)
+    G, complete, _, starts = _collection_returns(res, N, 1.0, E)
+    res.update(first=first, ds_env=ds_env, ds_slot=ds_slot, leaf=leaf, done=done, rew=rew, next=nxt, open_rows=int(leaf.sum()),
+               nonleaf=first + np.nonzero(~leaf)[0], episode_return=G[starts & complete], t_append=spent['append'],
+               t_set_transitions=time.perf_counter() - t0, rows=trainer.size())
+    return res
+
+
+def actor_critic_fit(env, trainer, critic, col, gamma=0.99, lam=0.95, n_value_steps=100, n_policy_steps=100, batch_size=64, seed=0,
+                     normalize=True, w_scale=1.0):
+    """The refit after actor_critic_collect, on the device: ONE fit_gae call over the rows `col` added writes their value targets
+    (A + V under the present critic) and their loss weights (w_scale A^, A^ the advantage, normalised over the non-leaf rows with
+    normalize; a leaf gets 0); then n_value_steps steps of `critic` (policies.ValueTrainer on `env`) on the NON-LEAF rows of the whole
+    dataset, then n_policy_steps steps of `trainer` (policies.MLPTrainer) on everything under the written weights -- advantage-weighted
+    regression onto the executed actions. Rows of earlier collections keep the targets and weights their own call wrote. Returns
+    dict(adv, ret float32[n]: fit_gae's, value_losses, policy_losses float64: each step's loss before its update, rows)."""
+    if trainer.env is not env or critic.env is not env:
+        raise ValueError("the trainer or the critic belongs to another env")
+    n = int(col['appended']) + int(col['open_rows'])
+    adv, ret = env.batch.fit_gae(gamma, lam, first=col['first'], n=n, write_weights=True, normalize=normalize, w_scale=w_scale)
+    rew, nxt = env.batch.fit_get_transitions()
+    from ._lib import FIT_NEXT_NONE
+    rows = np.nonzero(nxt != FIT_NEXT_NONE)[0]
+    vl = critic.step(n_value_steps, batch_size, seed, rows=rows) if len(rows) else np.zeros(0)
+    pl = trainer.step(n_policy_steps, batch_size, seed)
+    return {'adv': adv, 'ret': ret, 'value_losses': vl, 'policy_losses': pl, 'rows': trainer.size()}

@@ -163,11 +163,11 @@ class LookaheadPolicy(object):
 MLP_MAX_LAYERS, MLP_MAX_WIDTH = 4, 256
 
 
-def pack_mlp(layers, n_in=None):
+def pack_mlp(layers, n_in=None, n_out=4):
     """[(W, b), ...] -> (widths int32[L + 1], blob float32): for every layer W [out, in] row-major (torch.nn.Linear.weight's layout),
     then b [out] -- what clothhip_set_policy_mlp takes. ValueError for anything the library would refuse: no or more than four layers,
     a W that is not 2-d or a b that is not [out], widths that do not chain, an input width other than n_in (when given), a last width
-    other than 4, a hidden width outside [1, 256], non-finite values."""
+    other than 4 (n_out: 1 for a value network, clothhip_set_value_mlp), a hidden width outside [1, 256], non-finite values."""
     layers = list(layers)
     if not 1 <= len(layers) <= MLP_MAX_LAYERS:
         raise ValueError("an MLP policy has 1 to %d weight layers (got %d)" % (MLP_MAX_LAYERS, len(layers)))
@@ -190,8 +190,8 @@ def pack_mlp(layers, n_in=None):
         parts += [np.ascontiguousarray(W).reshape(-1), b]
     if n_in is not None and widths[0] != int(n_in):
         raise ValueError("the network's input width is %d, the '1d' observation has %d values" % (widths[0], int(n_in)))
-    if widths[-1] != 4:
-        raise ValueError("the network's output width is %d, an action has 4 values" % widths[-1])
+    if widths[-1] != int(n_out):
+        raise ValueError("the network's output width is %d, %s" % (widths[-1], "an action has 4 values" if int(n_out) == 4 else "this network has %d" % int(n_out)))
     for l in range(1, len(widths) - 1):
         if not 1 <= widths[l] <= MLP_MAX_WIDTH:
             raise ValueError("hidden width %d (layer %d) outside [1, %d]" % (widths[l], l, MLP_MAX_WIDTH))
@@ -454,6 +454,100 @@ def fit_reference(layers, obs, labels, idx, weights=None):
     return loss, grads
 
 
+def value_fit_reference(layers, obs, ret, idx):
+    """Pure-numpy float64 loss and gradient of the critic's objective (clothhip_value_fit_grad): L_V = 1 / (2 B) sum_r (v_r - ret_r)^2
+    over the rows idx [B] of (obs [n, in], ret [n]), UNWEIGHTED, the network as fit_reference takes it with a last width of 1. obs, ret
+    and the network's weights are rounded to float32 first (what the device stores), the arithmetic is float64. Returns
+    (loss, [(dW, db), ...]) in `layers`' shapes."""
+    ix = np.asarray(idx, dtype=np.int64).reshape(-1)
+    Ws = [np.asarray(W, dtype=np.float32).astype(np.float64) for W, _ in layers]
+    bs = [np.asarray(b, dtype=np.float32).astype(np.float64) for _, b in layers]
+    if Ws[-1].shape[0] != 1:
+        raise ValueError("a value network ends in ONE output (got %d)" % Ws[-1].shape[0])
+    x = np.asarray(obs, dtype=np.float32).astype(np.float64)[ix]
+    a = np.asarray(ret, dtype=np.float64).astype(np.float32).astype(np.float64).reshape(-1)[ix][:, None]
+    B, L = len(ix), len(Ws)
+    hs = [x]
+    for l in range(L):
+        z = hs[-1] @ Ws[l].T + bs[l]
+        hs.append(np.maximum(z, 0.0) if l + 1 < L else z)
+    d = hs[-1] - a
+    loss = float((d * d).sum() / (2.0 * B))
+    g = d / float(B)
+    grads = [None] * L
+    for l in range(L - 1, -1, -1):
+        grads[l] = (g.T @ hs[l], g.sum(axis=0))
+        if l:
+            g = (g @ Ws[l]) * (hs[l] > 0.0)
+    return loss, grads
+
+
+NEXT_TERMINAL, NEXT_NONE = -1, -2          # _lib.FIT_NEXT_*: a row's successor column besides a row number
+
+
+def _house_sum(x):
+    """The device's reduction order over x [n] float64: thread t of 256 adds elements t, t + 256, ... in ascending order from +0.0, then a
+    halving tree adds the 256 sums. (Elements that do not take part are passed as +0.0: s + 0.0 keeps the bits of a sum that began at +0.0.)"""
+    x = np.asarray(x, dtype=np.float64)
+    k = (len(x) + 255) // 256
+    tab = np.zeros((max(k, 1), 256))
+    tab.reshape(-1)[:len(x)] = x
+    red = np.zeros(256)
+    for row in tab:
+        red = red + row
+    o = 128
+    while o > 0:
+        red[:o] = red[:o] + red[o:2 * o]
+        o >>= 1
+    return red[0]
+
+
+def gae_reference(v, rew, next, gamma, lam, w_scale=1.0, normalize=False):
+    """clothhip_fit_data_gae restated in float64 numpy, operation by operation (include/clothhip.h: ADVANTAGES AND VALUE TARGETS ON THE
+    DEVICE): v [n] float32 the critic on the rows of a range, rew [n] float32, next [n] int with successors as indices INTO THE RANGE
+    (the dataset's column minus `first` where it is >= 0), NEXT_TERMINAL or NEXT_NONE (a leaf). For a non-leaf row the chain r, next[r],
+    ... stops after a row whose next is TERMINAL or whose successor is a leaf; delta = (rew + gamma nv) - v, A = sum (gamma lam)^k
+    delta_k accumulated for k ascending with coef = coef c. Returns (adv float32[n], ret float32[n], w float32[n]): adv = (float)A,
+    ret = (float)(A + v), w = (float)((float32)w_scale A^) with A^ = A, or normalised (A - mean) / (std + 1e-8) over the non-leaf rows in
+    the device's reduction order; a leaf has adv 0, ret v, w 0. Bit for bit what the device writes."""
+    v64 = np.asarray(v, dtype=np.float32).astype(np.float64).reshape(-1)
+    r64 = np.asarray(rew, dtype=np.float32).astype(np.float64).reshape(-1)
+    nx = np.asarray(next).astype(np.int64).reshape(-1)
+    n = len(v64)
+    if not (len(r64) == len(nx) == n):
+        raise ValueError("v, rew and next must have one length")
+    if ((nx >= 0) & ((nx <= np.arange(n)) | (nx >= n))).any() or (nx < NEXT_NONE).any():
+        raise ValueError("a successor lies behind its row and inside the range (or is NEXT_TERMINAL / NEXT_NONE)")
+    gamma, c = float(gamma), float(gamma) * float(lam)
+    leaf = nx == NEXT_NONE
+    A = np.zeros(n)
+    for r in np.nonzero(~leaf)[0]:
+        acc, coef, cur = 0.0, 1.0, int(r)
+        while True:
+            k = int(nx[cur])
+            nv = 0.0 if k < 0 else v64[k]
+            delta = (r64[cur] + gamma * nv) - v64[cur]
+            acc = acc + coef * delta
+            coef = coef * c
+            if k < 0 or leaf[k]:
+                break
+            cur = k
+        A[r] = acc
+    with np.errstate(over='ignore'):
+        adv = A.astype(np.float32)
+        ret = np.where(leaf, v64, A + v64).astype(np.float32)
+    hat = A
+    cnt = int((~leaf).sum())
+    if normalize and cnt:
+        mean = _house_sum(np.where(leaf, 0.0, A)) / float(cnt)
+        d = A - mean
+        std = np.sqrt(_house_sum(np.where(leaf, 0.0, d * d)) / float(cnt))
+        hat = d / (std + 1e-8)
+    with np.errstate(over='ignore', invalid='ignore'):
+        w = np.where(leaf, 0.0, float(np.float32(w_scale)) * hat).astype(np.float32)
+    return adv, ret, w
+
+
 def adam_reference(theta, m, v, g, t, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8):
     """The device's Adam step restated in numpy float32, operation by operation (include/clothhip.h, clothhip_policy_fit): t is the
     1-based step count. Returns the new (theta, m, v), float32."""
@@ -560,6 +654,57 @@ class MLPTrainer(object):
     def reset(self):
         """Zero the optimizer's moments and step count; the weights and the dataset stay."""
         self.env.batch.fit_reset()
+
+
+class ValueTrainer(object):
+    """The critic of an actor-critic ON THE DEVICE (no reference counterpart; ClothBatch.value_*): a network V(s) with ONE output over
+    the rows of the env's dataset -- the dataset an MLPTrainer on the same env fills --, fitted to the column of value targets
+    (ClothBatch.fit_set_returns, or fit_gae's ret) by the trainer's kernels under L_V = 1 / (2 B) sum (v - ret)^2, unweighted. `layers`
+    is a list of (W, b) with a last width of 1; the constructor puts it on the env's batch beside the policy, which it leaves alone (as
+    every step here does, and the policy's steps leave the critic alone). The dataset is not cleared."""
+
+    def __init__(self, env, layers, optimizer='adam', lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, momentum=0.0):
+        from . import _lib
+        if optimizer not in _lib.FIT_OPTIMIZERS:
+            raise ValueError("optimizer must be one of %r (got %r)" % (sorted(_lib.FIT_OPTIMIZERS), optimizer))
+        self.env = env
+        self.hyper = dict(optimizer=optimizer, lr=float(lr), beta1=float(beta1), beta2=float(beta2), eps=float(eps), momentum=float(momentum))
+        self.widths, blob = pack_mlp(layers, n_in=3 * env.P, n_out=1)
+        self.n_params = int(blob.size)
+        env.batch.set_value_mlp(layers)
+
+    def step(self, n_steps, batch_size, seed, rows=None):
+        """n_steps optimizer steps on minibatches of batch_size rows drawn by MLPTrainer.index_table(n, n_steps, batch_size, seed) with n
+        the dataset's size, or with rows (int [m]: a subset of the dataset, e.g. its non-leaf rows) n = m and the table's entries name
+        rows[...]. Returns float64[n_steps], each step's loss before its update."""
+        if rows is None:
+            n = self.env.batch.fit_size()
+            if n < 1:
+                raise ValueError("the dataset is empty: append first")
+            table = MLPTrainer.index_table(n, n_steps, batch_size, seed)
+        else:
+            rows = np.asarray(rows)
+            if rows.ndim != 1 or rows.size < 1 or not np.issubdtype(rows.dtype, np.integer):
+                raise ValueError("rows must be a non-empty 1-d integer array")
+            table = rows.astype(np.int32)[MLPTrainer.index_table(rows.size, n_steps, batch_size, seed)]
+        return self.env.batch.value_fit(table, **self.hyper)
+
+    def predict(self, idx):
+        """float32[n]: the critic on the dataset rows idx at the present weights -- the v of grad and step, bit for bit."""
+        return self.env.batch.value_predict(idx)
+
+    def grad(self, idx):
+        """(loss, [(dW, db), ...]) over the dataset rows idx at the present weights, float32 from the device; nothing is updated."""
+        loss, g = self.env.batch.value_grad(idx)
+        return loss, unpack_mlp(self.widths, g)
+
+    def layers(self):
+        """The critic as the device holds it now: [(W, b), ...] float32, by download (clothhip_get_value_mlp)."""
+        return unpack_mlp(self.widths, self.env.batch.get_value_mlp())
+
+    def reset(self):
+        """Zero the critic's moments and step count; its weights, the policy's optimizer and the dataset stay."""
+        self.env.batch.value_fit_reset()
 
 
 def ensemble_disagreement(actions):

@@ -517,7 +517,7 @@ int clothhip_fit_data_append_weighted(clothhip_handle *h, const float *obs_rows,
  * The refusals are those above; besides, CLOTHHIP_ESTATE for LABEL_ACTION with no launch since creation (or none whose record table
  * is still there), CLOTHHIP_EINVAL for an unknown label_src or a non-finite weight. */
 enum { CLOTHHIP_FIT_SRC_SLOTS = 0, CLOTHHIP_FIT_SRC_RESETS = 1, CLOTHHIP_FIT_SRC_HELD = 2 };
-enum { CLOTHHIP_FIT_LABEL_EXPERT = 0, CLOTHHIP_FIT_LABEL_ACTION = 1 };
+enum { CLOTHHIP_FIT_LABEL_EXPERT = 0, CLOTHHIP_FIT_LABEL_ACTION = 1, CLOTHHIP_FIT_LABEL_ZERO = 3 /* ACTOR-CRITIC below; 2 names no source and stays refused */ };
 int clothhip_fit_hold(clothhip_handle *h, const int32_t *src);
 int clothhip_fit_data_append_launch(clothhip_handle *h, const int32_t *rows, int64_t n);
 int clothhip_fit_data_append_launch_ex(clothhip_handle *h, const int32_t *rows, int64_t n, int32_t label_src, const float *weights);
@@ -607,6 +607,65 @@ int clothhip_policy_fit_grad_members(clothhip_handle *h, const int32_t *members,
 int clothhip_policy_fit_members(clothhip_handle *h, const ClothFitParams *p, const int32_t *members, int32_t n_m, const int32_t *idx,
                                 int32_t n_steps, int32_t B, double *loss_out);
 int clothhip_policy_fit_reset_members(clothhip_handle *h, const int32_t *members, int32_t n_m);
+
+/* ACTOR-CRITIC FROM REWARD (no reference counterpart): a VALUE NETWORK V(s) over the stored observation rows, fitted to
+ * value targets by the one trainer, and generalised advantage estimation written into the dataset's weight column on the device.
+ * THE VALUE NETWORK. clothhip_set_value_mlp takes the shape rules and the blob layout of clothhip_set_policy_mlp, except that
+ * widths[n_layers] == 1. It belongs to the handle, beside the policy and independent of it: setting or dropping a policy network or a
+ * population leaves it (and its optimizer state) alone, and the reverse; n_layers == 0 drops it; a refused call keeps the earlier one;
+ * clothhip_fork does not carry it; no episode launch evaluates it. clothhip_get_value_mlp downloads the blob (out[n_params]).
+ * CLOTHHIP_ESTATE with a launch in flight, and from _get without a value network.
+ * EPISODE STRUCTURE AND VALUE TARGETS are three more columns of the dataset beside the weights; they grow with the rows and
+ * clothhip_fit_data_clear empties them:
+ *   rew[n]  float32  the reward of the action executed from the row's state. Default 0.
+ *   next[n] int32    the dataset index of the row that holds the successor state of the same episode; or
+ *                    CLOTHHIP_FIT_NEXT_TERMINAL: the episode ended there, the successor's value is 0; or CLOTHHIP_FIT_NEXT_NONE (the
+ *                    default): the row is a LEAF -- it has no transition of its own and serves only as a successor whose value bootstraps.
+ *   ret[n]  float32  the value target. Default 0.
+ * clothhip_fit_data_set_transitions writes rew and next of the rows [first, first + n), _set_returns writes ret; the _get calls download
+ * them. A successor index must be STRICTLY GREATER than the row's own index and below the dataset's size (rows are appended in time
+ * order, so a successor lies later: every chain is finite and acyclic without a check on the device). Refused, nothing written --
+ * CLOTHHIP_EINVAL: a range outside the dataset, a value that is not finite, a next that is none of the three, a NULL table with n > 0;
+ * CLOTHHIP_ESTATE: a launch in flight.
+ * CLOTHHIP_FIT_LABEL_ZERO is a third label source of clothhip_fit_data_append_launch_ex: the label is (0, 0, 0, 0), label_row is
+ * ignored, and neither an armed expert nor a record that ran is needed -- how a leaf is appended from where it lies on the device.
+ * FITTING THE CRITIC. The value network is one more one-row weight table of the trainer above (the same kernels, its own moments, its
+ * own step count, the same lazy reset):  L_V = 1 / (2 B) sum_r (v_r - ret_r)^2, UNWEIGHTED (the weight column belongs to the policy),
+ * dz_r = fl(fl(v_r - ret_r) / fl(B)); the loss adds dd * dd, dd = (double)v - (double)ret, in the order of clothhip_policy_fit_grad
+ * (thread t of 256 takes rows t, t + 256, ..., then the halving tree) and divides by 2 B. clothhip_value_fit_grad, clothhip_value_fit
+ * and clothhip_value_fit_reset are clothhip_policy_fit_grad, clothhip_policy_fit and clothhip_policy_fit_reset for it, with their
+ * refusals and "no value network" in place of "no shared network"; a population on the handle is no obstacle (the critic is not the
+ * policy). clothhip_value_predict: v_out[n] float32 for any n >= 1 stored rows, in chunks of at most CLOTHHIP_FIT_MAX_BATCH, bit for
+ * bit the v of clothhip_value_fit_grad. No critic call changes a bit of the policy's blob, moments or step count, and the reverse.
+ * ADVANTAGES AND VALUE TARGETS ON THE DEVICE. clothhip_fit_data_gae runs the critic's forward over the rows [first, first + n) (the
+ * launches of clothhip_value_predict, the values stay on the device), then for a NON-LEAF row r walks the chain r_0 = r,
+ * r_k+1 = next[r_k], which stops after a row whose next is TERMINAL or whose successor is a leaf. Every operation is one double rounding:
+ *   nv = (double)v[next] (0 when next is TERMINAL);  delta = ((double)rew + gamma nv) - (double)v;
+ *   A = 0, coef = 1; for k ascending: A = A + coef delta_k, then coef = coef c, with c = gamma lambda formed once in double on the host;
+ *   adv_r = (float)A;  ret[r] <- (float)(A + (double)v_r).
+ * A LEAF row: adv = 0, ret <- v of the leaf. With CLOTHHIP_GAE_WRITE_WEIGHTS the weight column of the range is written too:
+ * w[r] <- (float)((double)w_scale A^), 0 for a leaf, where A^ = A, or with CLOTHHIP_GAE_NORMALIZE A^ = (A - mean) / (std + 1e-8), mean and
+ * population standard deviation over the non-leaf rows of the range, in double, in two passes (the sum of A, then the sum of
+ * (A - mean)^2, each divided by the count), each pass in the order above: thread t of 256 takes rows t, t + 256, ... of the range, then
+ * the halving tree. Without CLOTHHIP_GAE_WRITE_WEIGHTS the weight column is untouched. adv_out[n] and ret_out[n] (host float32) may be
+ * NULL. No floating-point atomics: two runs give the same bits. Synchronous; clothhip_last_kernel_ms gives the forward and the scan.
+ * Refused before anything is touched -- CLOTHHIP_ESTATE: no value network, a launch in flight; CLOTHHIP_EINVAL: a range outside the
+ * dataset, gamma, lambda or w_scale not finite, gamma or lambda outside [0, 1], unknown flags, p == NULL, a row of the range whose
+ * successor lies outside the range. n == 0 returns 0. */
+enum { CLOTHHIP_FIT_NEXT_TERMINAL = -1, CLOTHHIP_FIT_NEXT_NONE = -2 };
+enum { CLOTHHIP_GAE_WRITE_WEIGHTS = 1, CLOTHHIP_GAE_NORMALIZE = 2 };
+typedef struct ClothGaeParams { double gamma, lambda; float w_scale; int32_t flags /* CLOTHHIP_GAE_* */; } ClothGaeParams;
+int clothhip_set_value_mlp(clothhip_handle *h, int32_t n_layers, const int32_t *widths, const float *params, size_t n_params);
+int clothhip_get_value_mlp(clothhip_handle *h, float *out, size_t n_params);
+int clothhip_fit_data_set_transitions(clothhip_handle *h, int64_t first, int64_t n, const float *rew, const int32_t *next);
+int clothhip_fit_data_get_transitions(clothhip_handle *h, int64_t first, int64_t n, float *rew, int32_t *next);
+int clothhip_fit_data_set_returns(clothhip_handle *h, int64_t first, int64_t n, const float *ret);
+int clothhip_fit_data_get_returns(clothhip_handle *h, int64_t first, int64_t n, float *ret);
+int clothhip_value_fit_grad(clothhip_handle *h, const int32_t *idx, int32_t B, float *grad_out, double *loss_out);
+int clothhip_value_fit(clothhip_handle *h, const ClothFitParams *p, const int32_t *idx, int32_t n_steps, int32_t B, double *loss_out);
+int clothhip_value_fit_reset(clothhip_handle *h);
+int clothhip_value_predict(clothhip_handle *h, const int32_t *idx, int64_t n, float *v_out);
+int clothhip_fit_data_gae(clothhip_handle *h, int64_t first, int64_t n, const ClothGaeParams *p, float *adv_out, float *ret_out);
 
 int clothhip_run_actions(clothhip_handle *h, const ClothEpisodeParams *ep, int32_t T, int32_t policy,
                          const double *actions, int32_t actions_on_device, const int32_t *policy_arg,
