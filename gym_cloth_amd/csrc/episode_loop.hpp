@@ -136,10 +136,16 @@ __global__ __launch_bounds__(NT, (Variant{(int)sizeof(T), NT, PPT, TAB, REST_REG
         }
         for (int h = tid; h < HT; h += NT) { hkey[h] = KEY_EMPTY; hco[h] = 0; }
         if (tid == 0) { misc[0] = tear_flag; misc[1] = 0; misc[2] = 0; misc[3] = 0; misc[4] = 0; misc[5] = 0; misc[6] = 0; misc[10] = 0x7fffffff; misc[11] = -1; misc[12] = 0; misc[13] = 0; misc[14] = 0; misc[20] = 0; misc[21] = 0; misc[22] = 0; misc[23] = 0; }
-        if constexpr (V.sweep_starts_early()) { if (tid == 0) misc[17] = 0; }      // [17] waves whose pre-pass has published (the early walk)
+        if constexpr (V.sweep_starts_early()) {      // the early walk's window masks (phase_strain.hpp): [24..27] F, a flagged spring; [28..31] D, tested
+            if (tid < 2 * EARLY_MASK_WORDS) misc[EARLY_F_WORD + tid] = 0;
+            static_assert(EARLY_D_WORD == EARLY_F_WORD + EARLY_MASK_WORDS && EARLY_D_WORD + EARLY_MASK_WORDS <= 64, "the masks lie side by side in misc");
+        }
     };
     if (tid == 0) misc[15] = 0;
-    if constexpr (V.sweep_starts_early()) { if (tid == 0 && A.stats) A.stats[16 * e + 4] = 0; }     // early walks that gave up waiting for the pre-pass (0 unless something is broken)
+#ifdef CLOTHHIP_EARLY_COUNTS
+    if (tid == 0) { misc[18] = 0; misc[19] = 0; }     // profiling build: jumps of the early walk, windows jumped over
+#endif
+    if constexpr (V.sweep_starts_early()) { if (tid == 0 && A.stats) A.stats[16 * e + 4] = 0; }     // was: early walks that gave up waiting for the pre-pass. The walk no longer waits: the word stays 0
     init_lds(A.tear[e], A.wt_ent, g_rest);
     if (LEAN64) {
         uint4 *d_ = reinterpret_cast<uint4 *>(smem + lay.lstc);
@@ -187,11 +193,17 @@ __global__ __launch_bounds__(NT, (Variant{(int)sizeof(T), NT, PPT, TAB, REST_REG
 #if defined(CLOTHHIP_PHASE_STAMPS)
     constexpr bool SWEEP_EARLY = false; // (the stamps builds time pre-pass and sweep apart)
 #else
-    constexpr bool SWEEP_EARLY = SWEEP_LEAN && V.sweep_starts_early();   // wave 0 walks from window 0 beside the pre-pass (substep_strain.inc.hpp)
+    // wave 0 walks from window 0 beside the pre-pass (substep_strain.inc.hpp), which also does the collision phase's hash-table reset then
+    // (not the relaxed-order companion: it has no sweep, so nobody would do that reset)
+    constexpr bool SWEEP_EARLY = SWEEP_LEAN && V.sweep_starts_early() && !RELAXED;
 #endif
     constexpr bool SWEEP_AHEAD = V.sweep_read_ahead();
     (void)SWEEP_AHEAD;
-#if defined(CLOTHHIP_PHASE_STAMPS) || defined(CLOTHHIP_CELL_COUNTERS)   // the sweep's window / pass / correction counters cost its loop three instructions per pass:
+    // EARLY_ORDER_(k): this substep takes the early order (wave-uniform; substep_strain_early.inc.hpp, and substep_collision.inc.hpp, whose
+    // hash-table reset moves behind the pre-pass then -- its counters are reset behind the end-of-substep barrier, so the Hooke phase's barrier
+    // must lie between that and the next hash insert: PH_HOOKE). Not with PH_NOSKIP, tear_thresh < 1.1 or more windows than the masks hold.
+#define EARLY_ORDER_(k_) ((pm & (PH_STRAIN | PH_HOOKE)) == (PH_STRAIN | PH_HOOKE) && !((k_).tear_thresh < (k_).c11) && !(pm & PH_NOSKIP) && KA_NW(Ak_) <= 32 * EARLY_MASK_WORDS)
+#if defined(CLOTHHIP_PHASE_STAMPS) || defined(CLOTHHIP_CELL_COUNTERS) || defined(CLOTHHIP_EARLY_COUNTS)   // the sweep's window / pass / correction counters cost its loop three instructions per pass:
     constexpr bool SWEEP_STATS = true;  // profiling builds only (the production build counts sweeps)
 #else
     constexpr bool SWEEP_STATS = false;
@@ -340,6 +352,7 @@ __global__ __launch_bounds__(NT, (Variant{(int)sizeof(T), NT, PPT, TAB, REST_REG
     const int done = fused ? eps->done_total : done_nf;
 
 #undef TSTAMP
+#undef EARLY_ORDER_
     {   // LDS / registers -> HBM
         __syncthreads();
         T *gp = A.pos + (size_t)e * 3 * Ppad, *gq = A.prev + (size_t)e * 3 * Ppad;
@@ -368,7 +381,10 @@ __global__ __launch_bounds__(NT, (Variant{(int)sizeof(T), NT, PPT, TAB, REST_REG
             A.tear[e] = misc[0]; A.executed[e] = done;
             if (A.stats) {
                 A.stats[16 * e] = misc[15]; A.stats[16 * e + 1] = st_windows; A.stats[16 * e + 2] = st_passes; A.stats[16 * e + 3] = st_commits;
-                for (int q = SWEEP_EARLY ? 1 : 0; q < 12; q++) A.stats[16 * e + 4 + q] = (int)((unsigned long long)tph[q] >> 6);     // (SWEEP_EARLY: [4] counts given-up waits)
+                for (int q = SWEEP_EARLY ? 1 : 0; q < 12; q++) A.stats[16 * e + 4 + q] = (int)((unsigned long long)tph[q] >> 6);     // (SWEEP_EARLY: [4] stays 0, the early walk never waits)
+#ifdef CLOTHHIP_EARLY_COUNTS             // profiling build of the early walk (never a product build): [1..3] windows / passes / correcting passes as counted above
+                A.stats[16 * e + 5] = misc[18]; A.stats[16 * e + 6] = misc[19];
+#endif
 #ifndef CLOTHHIP_PHASE_STAMPS
                 unsigned long long tend;
                 asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tend)::"memory");

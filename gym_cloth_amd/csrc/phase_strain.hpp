@@ -191,15 +191,18 @@ __device__ __forceinline__ int strain_sweep(Pt<T> *cur, const WEnt<T> *wt, const
 // (AHEAD false -- the high-residency builds, whose other waves hide the latency: a window's particle records are read when the window starts,
 //  not a window ahead: sixteen registers fewer across the walk)
 //
-// EARLY (Variant::sweep_starts_early) with `early` set: the walk runs BESIDE the pre-pass, not behind it. It enters at window 0 with no end of
-// its own (w_end < w0) and walks on in grants of EARLY_GRANT windows -- a quiet window is always exact, ~154 cycles -- until the seven waves of
-// the pre-pass have counted themselves done in misc[17]; only then are misc[1] / [10] / [11] (any flag, first and last flagged slot) final, and:
-// w_end = max(w_end, last flagged window), and, the walk's own reach being used up, it continues at max(w, first flagged window). The words are looked
-// at ONLY on this cold edge, where the reach is used up (an LDS read the compiler cannot move drains the read-ahead); the two register sets are
-// loaded again behind it. At the table's end with the count still short the wave sleeps and polls, at most EARLY_WAIT_POLLS times (~2 M cycles,
-// five hundred pre-passes): then it leaves -- every window has been walked, the result is exact -- and says so in bit 1 of what it returns (the caller counts it in the env's stats). DESIGN.md 4.1: why the
-// result is the sequential loop's although the pre-pass reads records this walk is correcting.
-constexpr int EARLY_GRANT = 4, EARLY_WAIT_POLLS = 4096;
+// EARLY (Variant::sweep_starts_early) with `early` set: the walk runs BESIDE the pre-pass, not behind it. Waves 1-7 test whole windows with this
+// walk's own quiet-window test (substep_strain_early.inc.hpp) and publish one bit per window in two masks of 32-bit LDS words: F (the window holds
+// an over-stretched spring), then, with release order, D (the window has been tested). The walk enters at window 0 with no end of its own and a
+// first grant of EARLY_GRANT windows (1, 2, 4, 6, 8 measured within 0.4 % of one another) -- a quiet window is always exact, ~154 cycles. The masks are looked at ONLY on the cold edge, where
+// the reach is used up (w > w_end): D with acquire order, then F; the next window to walk is the first w' >= w whose bit is set in ~D | F
+// (untested or flagged). Everything in between is tested, unflagged and beyond the reach of every correction made so far: jumped over. No such
+// window below nW: the sweep is over. An untested w' is walked with a grant of EARLY_GRANT windows; a flagged one to the end of the run of flagged
+// windows it begins (every correction pushes w_end out as ever). The two register sets are loaded again behind the edge. A walk that has reached
+// nW is exact whatever D says: there is no wait. Bit 2 of what it returns: a correction was made (the caller's count of sweeps run).
+// why the result is the sequential loop's although the pre-pass reads records this walk is correcting.
+// misc words of the masks (episode_loop.hpp): EARLY_MASK_WORDS each, so the order serves tables of up to 128 windows.
+constexpr int EARLY_GRANT = 4, EARLY_MASK_WORDS = 4, EARLY_F_WORD = 24, EARLY_D_WORD = 28;
 template <typename T, bool LDS_TAB, bool STATS, bool AHEAD = true, bool EARLY = false>
 __device__ __forceinline__ int strain_sweep_lean(Pt<T> *cur, const WEnt<T> *wt, const uint32_t *g_ent, const T *g_rest,
                                                  const unsigned long long *g_dep, int w0, int w_end, int rshift, const DevConsts<T> &k,
@@ -223,6 +226,7 @@ __device__ __forceinline__ int strain_sweep_lean(Pt<T> *cur, const WEnt<T> *wt, 
         s.A = cur[s.a]; s.B = cur[s.b];
     };
     int w = w0;
+    int corr = 0; (void)corr;                                       // EARLY: bit 2 of the result, a correction was made
     // one window: `c` holds it (entry decoded, particle records read or in flight), `n` the next one's entry
     auto step = [&](Set &c, Set &n) {
         if (AHEAD) decode_read(n);                                  // speculative: valid unless this window corrects something
@@ -263,6 +267,7 @@ __device__ __forceinline__ int strain_sweep_lean(Pt<T> *cur, const WEnt<T> *wt, 
                 // every correction of the window may move particles whose springs sit as far as the window's reach
                 const int reach = w + ((int)((uint32_t)__builtin_amdgcn_readfirstlane((int)c.ab) >> WT_REACH_SHIFT) << rshift);
                 w_end = reach > w_end ? reach : w_end;
+                if constexpr (EARLY) corr = 4;
                 bool pl = true;
                 unsigned long long plm = ~0ull;
                 for (;;) {
@@ -317,11 +322,29 @@ __device__ __forceinline__ int strain_sweep_lean(Pt<T> *cur, const WEnt<T> *wt, 
             if (++w > w_end) break;
         }
     } else {
-        constexpr int NPRE = 7;                                     // waves 1-7 run the pre-pass
-        auto peek = [&](int i) -> int { return __builtin_amdgcn_readfirstlane(__hip_atomic_load(&misc[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)); };
-        auto done = [&]() -> bool { return __builtin_amdgcn_readfirstlane(__hip_atomic_load(&misc[17], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)) >= NPRE; };
-        (void)peek;
-        bool known = !early;                                        // the pre-pass's bounds are in [w0, w_end] already
+        using M128 = unsigned __int128;                             // one bit per window (nW <= 32 * EARLY_MASK_WORDS: the caller's condition)
+        static_assert(EARLY_MASK_WORDS == 4, "the masks are taken as one 128-bit value");
+        constexpr int NWORDS_MAX = EARLY_MASK_WORDS;
+        const int nwords = (nW + 31) >> 5;
+        // the masks as this moment shows them: D first, F behind an acquire fence -- a window whose D bit is seen has its F bit final
+        auto masks = [&](M128 &Dm, M128 &Fm) {
+            uint32_t d_[NWORDS_MAX], f_[NWORDS_MAX];
+#pragma unroll
+            for (int j = 0; j < NWORDS_MAX; j++) d_[j] = j < nwords ? (uint32_t)__hip_atomic_load(&misc[EARLY_D_WORD + j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : 0u;
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+#pragma unroll
+            for (int j = 0; j < NWORDS_MAX; j++) f_[j] = j < nwords ? (uint32_t)__hip_atomic_load(&misc[EARLY_F_WORD + j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : 0u;
+            Dm = 0; Fm = 0;
+#pragma unroll
+            for (int j = NWORDS_MAX - 1; j >= 0; j--) {
+                Dm = (Dm << 32) | (M128)(uint32_t)__builtin_amdgcn_readfirstlane((int)d_[j]);
+                Fm = (Fm << 32) | (M128)(uint32_t)__builtin_amdgcn_readfirstlane((int)f_[j]);
+            }
+        };
+        auto ctz128 = [](M128 m) -> int {                           // (m != 0)
+            const unsigned long long lo = (unsigned long long)m, hi = (unsigned long long)(m >> 64);
+            return lo ? __builtin_ctzll(lo) : 64 + __builtin_ctzll(hi);
+        };
         if (early) w_end = (EARLY_GRANT < nW ? EARLY_GRANT : nW) - 1;
         for (;;) {
             load(w, S0); load(w + 1, S1);
@@ -333,25 +356,31 @@ __device__ __forceinline__ int strain_sweep_lean(Pt<T> *cur, const WEnt<T> *wt, 
                 if (++w > w_end) break;
             }
             // ---- the cold edge: the walk's reach is used up ----
-            if (known) break;
-            if (!done()) {
-                if (w < nW) { w_end = (w + EARLY_GRANT < nW ? w + EARLY_GRANT : nW) - 1; continue; }
-                int polls = 0;
-                bool d_;
-                do { __builtin_amdgcn_s_sleep(8); d_ = done(); } while (!d_ && ++polls < EARLY_WAIT_POLLS);
-                if (!d_) { tear |= 2; break; }                     // never in a healthy launch: bit 1 of the result, counted by the caller
-            }
-            known = true;
-#if !(defined(CLOTHHIP_MUTATE) && CLOTHHIP_MUTATE == 5)             // MUTANT 5 (tools/run_mutants.sh; never a product build): the walk stops at its own reach
-            if (peek(1) != 0) {
-                const int wf = peek(10) >> 6, wl = peek(11) >> 6;
-                w_end = wl > w_end ? wl : w_end;
-                w = wf > w ? wf : w;
-            }
+            if (!early || w >= nW) break;                           // (a walk that has reached the table's end is exact whatever D says)
+            M128 Dm, Fm;
+            masks(Dm, Fm);
+#if defined(CLOTHHIP_MUTATE) && CLOTHHIP_MUTATE == 5                // MUTANT 5 (tools/run_mutants.sh; never a product build): the walk jumps over a tested window without looking at its F bit
+            Fm = 0;
 #endif
-            if (w > w_end) break;
+            // the next window to walk: the first one at or behind w that is untested or flagged; everything in between is tested, unflagged
+            // and beyond the reach of every correction made so far
+            M128 cand = (~Dm | Fm) & ~(((M128)1 << w) - 1);         // (w < nW <= 128)
+            if (nW < 128) cand &= ((M128)1 << nW) - 1;
+            if (cand == 0) break;                                   // nothing left: the sweep is over
+            const int wn = ctz128(cand);
+#ifdef CLOTHHIP_EARLY_COUNTS                                        // profiling build (never a product build): jumps taken, windows jumped over
+            if (wn > w && lane == 0) { misc[18]++; misc[19] += wn - w; }
+#endif
+            w = wn;
+            if (!((Dm >> wn) & 1)) w_end = (wn + EARLY_GRANT < nW ? wn + EARLY_GRANT : nW) - 1;    // untested: a grant from there (a quiet window is always exact)
+            else {                                                  // flagged: to the end of the run of flagged windows it begins
+                const M128 rest_ = ~(Fm >> wn);                     // (0 only where all 128 windows are flagged)
+                w_end = wn + (rest_ ? ctz128(rest_) : 128) - 1;
+                w_end = w_end < nW ? w_end : nW - 1;
+            }
         }
     }
+    if constexpr (EARLY) tear |= corr;
     return tear;
 }
 

@@ -322,8 +322,17 @@
             }   // (exact order)
             __syncthreads();
             TSTAMP(6)
+            // SWEEP_EARLY builds in the early order: the reset below is done by waves 1-7 behind their strain pre-pass (substep_strain_early.inc.hpp),
+            // where they idle, instead of here by the two-particle waves in front of the plane phase. Every other build keeps its text to the token.
+            if constexpr (SWEEP_EARLY) {
+                if (!EARLY_ORDER_(k)) {
+                    for (int t = tid; t < nocc; t += NT) { const int h = (int)olist[t]; hkey[h] = KEY_EMPTY; hco[h] = 0; }
+                    if (tid == 0) { misc[2] = 0; misc[3] = 0; misc[4] = 0; misc[5] = 0; misc[6] = 0; }
+                }
+            } else {
             for (int t = tid; t < nocc; t += NT) { const int h = (int)olist[t]; hkey[h] = KEY_EMPTY; hco[h] = 0; }   // ready for the next substep
             if (tid == 0) { misc[2] = 0; misc[3] = 0; misc[4] = 0; misc[5] = 0; misc[6] = 0; }
+            }
         } else {
             __syncthreads();
         }

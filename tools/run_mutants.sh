@@ -8,13 +8,13 @@
 #   MUTANTS="10 11 12" SEL="tests/test_gpu_render_exact.py tests/test_render_exact_host.py" bash tools/run_mutants.sh
 # A run that ends in a time limit (124, 137), an abort (134) or a segmentation fault (139) ends the loop: nothing more is started on that GPU.
 OUT=gpurun_out/mutants; mkdir -p $OUT
-SEL=${SEL:-'tests/test_gpu_parity.py tests/test_gpu_fullsize.py tests/test_gpu_lean.py tests/test_gpu_large2.py tests/test_gpu_soak.py tests/test_gpu_env.py tests/test_gpu_fused.py tests/test_gpu_refpins.py tests/test_gpu_early_walk.py tests/test_gpu_metrics_exact.py tests/test_metrics_exact_host.py tests/test_gpu_render_exact.py tests/test_render_exact_host.py'}
+SEL=${SEL:-'tests/test_gpu_parity.py tests/test_gpu_fullsize.py tests/test_gpu_lean.py tests/test_gpu_large2.py tests/test_gpu_soak.py tests/test_gpu_env.py tests/test_gpu_fused.py tests/test_gpu_refpins.py tests/test_gpu_early_walk.py tests/test_gpu_window_flags.py tests/test_gpu_metrics_exact.py tests/test_metrics_exact_host.py tests/test_gpu_render_exact.py tests/test_render_exact_host.py'}
 MUTANTS=${MUTANTS:-'1 2 3 4 5 6 7 8 9 10 11 12'}
 DESC=("" "1: ONE particle adds two of its incident springs in swapped list order (Hooke, cloth.pyx:221-237)"
          "2: the first two visits of a collision cell swapped (cloth.pyx:324-343)"
          "3: the second over-stretched spring of a pass committed with the first whether or not it depends on it (cloth.pyx:265-296)"
          "4: the both-pinned skip of the strain limit dropped (cloth.pyx:268)"
-         "5: the early walk (eight-wave fp32 LEAN build) stops at its own reach without taking the pre-pass's last flagged window (cloth.pyx:265-296)"
+         "5: the early walk (eight-wave fp32 LEAN build) jumps over a tested window without looking at its flag bit (cloth.pyx:265-296)"
          "6: metrics: the sort of the clipped points drops its y tie-break (cloth_metrics.hpp)"
          "7: metrics: the upper x / y out-of-bounds test is > instead of >= (cloth_env.py:1031, :1033)"
          "8: metrics: the height count tests z <= thickness/2 instead of < (cloth_env.py:606)"
