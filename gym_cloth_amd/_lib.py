@@ -127,6 +127,15 @@ class ClothGaeParams(C.Structure):
 assert C.sizeof(ClothGaeParams) == 24
 
 
+class ClothPpoParams(C.Structure):
+    """clothhip_policy_fit_ppo*'s constants: the standard deviation of the fixed-sigma Gaussian policy, the clip range epsilon."""
+    _fields_ = [("sigma", C.c_double), ("clip", C.c_double)]
+
+
+PPO_STATS = 3                       # CLOTHHIP_PPO_STATS: loss, clip_fraction, kl
+assert C.sizeof(ClothPpoParams) == 16
+
+
 class ClothPlanParams(C.Structure):
     """clothhip_plan_cem's planner constants (clothhip.h: PLAN ACTIONS ON THE DEVICE)."""
     _fields_ = [("horizon", C.c_int32), ("n_candidates", C.c_int32), ("n_elite", C.c_int32), ("n_iters", C.c_int32),
@@ -216,6 +225,11 @@ SYMBOLS = [
     ("clothhip_value_fit_reset", C.c_int, [_vp]),
     ("clothhip_value_predict", C.c_int, [_vp, _i32p, C.c_int64, C.POINTER(C.c_float)]),
     ("clothhip_fit_data_gae", C.c_int, [_vp, C.c_int64, C.c_int64, C.POINTER(ClothGaeParams), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    ("clothhip_fit_data_snapshot_policy", C.c_int, [_vp, C.c_int64, C.c_int64]),
+    ("clothhip_fit_data_set_old_means", C.c_int, [_vp, C.c_int64, C.c_int64, C.POINTER(C.c_float)]),
+    ("clothhip_fit_data_get_old_means", C.c_int, [_vp, C.c_int64, C.c_int64, C.POINTER(C.c_float)]),
+    ("clothhip_policy_fit_ppo_grad", C.c_int, [_vp, C.POINTER(ClothPpoParams), _i32p, C.c_int32, C.POINTER(C.c_float), _dp, C.POINTER(C.c_float)]),
+    ("clothhip_policy_fit_ppo", C.c_int, [_vp, C.POINTER(ClothFitParams), C.POINTER(ClothPpoParams), _i32p, C.c_int32, C.c_int32, _dp]),
     ("clothhip_plan_cem", C.c_int, [_vp, _vp, C.POINTER(ClothEpisodeParams), C.POINTER(ClothPlanParams), _i32p, _u8p, _dp, _dp, _dp, _dp,
                                     _dp, _dp]),
     ("clothhip_plan_sample", C.c_int, [_vp, C.POINTER(ClothPlanParams), _dp, _dp, C.c_int32, C.c_int32, _dp, _dp, _dp]),
@@ -250,6 +264,7 @@ SYMBOLS = [
     ("clothhip_selftest_layout", C.c_int, [_PP, C.c_int32, C.c_int32, C.c_int32, _i32p, C.c_int32]),
     ("clothhip_selftest_rng", C.c_int, [_vp, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, _dp]),
     ("clothhip_selftest_depth8", C.c_int, [C.POINTER(C.c_float), C.c_int32, C.c_int64, _u8p]),
+    ("clothhip_selftest_exp_fixed", C.c_int, [_dp, C.c_int64, _dp]),
     ("clothhip_selftest_render_plan", C.c_int, [_PP, C.c_int32, C.c_int32, _i32p]),
     ("clothhip_selftest_arith", C.c_int, [C.c_int32, C.c_int32, _dp, _dp, _dp, C.c_int64]),
 ]

@@ -1008,6 +1008,70 @@ class ClothBatch(object):
         check(self._L.clothhip_fit_data_gae(self._h, first, n, C.byref(p), _lib.fp(adv), _lib.fp(ret)))
         return (adv, ret) if want else None
 
+    # ---- PPO: the old means and the clipped surrogate (clothhip.h: PPO ON THE DEVICE) ----------------------------------------------
+    def fit_snapshot_policy(self, first=0, n=None):
+        """Write the shared network's present output on the stored rows [first, first + n) (n=None: to the end) into the dataset's
+        old-mean column, on the device (clothhip_fit_data_snapshot_policy): the bytes fit_predict returns for these rows, never
+        downloaded. The rows then have an old mean, which fit_ppo / fit_ppo_grad need of every row they name."""
+        first, n = self._fit_range(first, n)
+        self._fit_n_params()
+        check(self._L.clothhip_fit_data_snapshot_policy(self._h, first, n))
+
+    def fit_set_old_means(self, mu, first=0):
+        """Write the old means of the stored rows [first, first + len(mu)) from the host (clothhip_fit_data_set_old_means): mu [n, 4],
+        finite float32."""
+        m = np.asarray(mu, dtype=np.float64)
+        if m.ndim != 2 or m.shape[1] != 4:
+            raise ValueError("mu must have shape (n, 4)")
+        if not (np.isfinite(m).all() and (np.abs(m) <= np.finfo(np.float32).max).all()):
+            raise ValueError("mu must be finite (float32)")
+        m = np.ascontiguousarray(m, dtype=np.float32)
+        check(self._L.clothhip_fit_data_set_old_means(self._h, int(first), m.shape[0], _lib.fp(m)))
+
+    def fit_get_old_means(self, first=0, n=None):
+        """float32[n, 4]: the old means of the stored rows [first, first + n), n=None: to the end (clothhip_fit_data_get_old_means);
+        zeros for a row that has none."""
+        first, n = self._fit_range(first, n)
+        mu = np.zeros((n, 4), dtype=np.float32)
+        check(self._L.clothhip_fit_data_get_old_means(self._h, first, n, _lib.fp(mu)))
+        return mu
+
+    @staticmethod
+    def _ppo_params(sigma, clip):
+        s, c = float(sigma), float(clip)
+        if not (np.isfinite(s) and s > 0.0 and s * s > 0.0 and np.isfinite(1.0 / (s * s))):
+            raise ValueError("sigma = %r: the policy's standard deviation is finite and > 0" % (sigma,))
+        if not (np.isfinite(c) and 0.0 <= c < 1.0):
+            raise ValueError("clip = %r: the clip range lies in [0, 1)" % (clip,))
+        return _lib.ClothPpoParams(s, c)
+
+    def fit_ppo_grad(self, idx, sigma, clip=0.2):
+        """(stats float64[3] = loss, clip_fraction, kl; grad float32[n_params] in the blob's layout; ratio float32[B]) of PPO's clipped
+        surrogate over the dataset rows idx [B] at the present weights; nothing is updated (clothhip_policy_fit_ppo_grad). The policy
+        is Gaussian with the fixed standard deviation sigma around the shared network's output; a row's action is its label, its
+        advantage its weight, its old mean what fit_snapshot_policy / fit_set_old_means stored. policies.ppo_reference is the float64
+        yardstick, policies.ppo_loss_reference the kernel's arithmetic."""
+        ix = self._fit_idx(idx, 1)
+        q = self._ppo_params(sigma, clip)
+        grad = np.zeros(self._fit_n_params(), dtype=np.float32)
+        stats = np.zeros(_lib.PPO_STATS, dtype=np.float64)
+        ratio = np.zeros(ix.size, dtype=np.float32)
+        check(self._L.clothhip_policy_fit_ppo_grad(self._h, C.byref(q), _lib.i32p(ix), ix.size, _lib.fp(grad), _lib.dp(stats), _lib.fp(ratio)))
+        return stats, grad, ratio
+
+    def fit_ppo(self, idx_table, sigma, clip=0.2, optimizer='adam', lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, momentum=0.0):
+        """fit with PPO's clipped surrogate as the loss (clothhip_policy_fit_ppo): n_steps optimizer steps on the shared network in
+        place, step s on the dataset rows idx_table[s] (int [n_steps, B]), every row with an old mean. The optimizer is the policy's:
+        fit and fit_ppo share the moments and the step count, fit_reset restarts both. Returns float64[n_steps, 3]: each step's
+        (loss, clip_fraction, kl) BEFORE its update."""
+        ix = self._fit_idx(idx_table, 2)
+        p = self._fit_params(dict(optimizer=optimizer, lr=lr, beta1=beta1, beta2=beta2, eps=eps, momentum=momentum), 1)
+        q = self._ppo_params(sigma, clip)
+        self._fit_n_params()
+        stats = np.zeros((ix.shape[0], _lib.PPO_STATS), dtype=np.float64)
+        check(self._L.clothhip_policy_fit_ppo(self._h, p, C.byref(q), _lib.i32p(ix), ix.shape[0], ix.shape[1], _lib.dp(stats)))
+        return stats
+
     # ---- the cross-entropy planner over forked cloths (clothhip_plan_*) ------------------------------------------
     @staticmethod
     def plan_params(horizon, n_candidates, n_elite=1, n_iters=1, alpha=1.0, penalty=1.0, min_std=0.0, seed=0, iter0=0):

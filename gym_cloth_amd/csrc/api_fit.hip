@@ -1,4 +1,4 @@
-// api_fit.hip -- the supervised trainer of the handle's networks, policy and critic: the device-resident dataset and its columns, the loss and its gradient over a minibatch, the optimizer steps, advantages from the critic's values.
+// api_fit.hip -- the supervised trainer of the handle's networks, policy and critic: the device-resident dataset and its columns, the loss and its gradient over a minibatch, the optimizer steps, advantages from the critic's values, the old means and PPO's clipped surrogate.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -28,7 +28,7 @@ static int grow_dataset(clothhip_handle *h, int64_t n) {
     if (f.n + n <= f.cap) return 0;
     const size_t row = (size_t)3 * h->P;
     const int64_t cap = std::max<int64_t>(std::max<int64_t>(f.n + n, 2 * f.cap), 64);
-    Buffer<float> obs, lb, w, rew, ret;
+    Buffer<float> obs, lb, w, rew, ret, old;
     Buffer<int32_t> next;
     if (int rc = obs.reserve((size_t)cap * row * 4)) return rc;
     if (int rc = lb.reserve((size_t)cap * 4 * 4)) return rc;
@@ -36,6 +36,7 @@ static int grow_dataset(clothhip_handle *h, int64_t n) {
     if (int rc = rew.reserve((size_t)cap * 4)) return rc;
     if (int rc = ret.reserve((size_t)cap * 4)) return rc;
     if (int rc = next.reserve((size_t)cap * 4)) return rc;
+    if (int rc = old.reserve((size_t)cap * 4 * 4)) return rc;
     if (f.n > 0) {
         HIPCHECK(hipMemcpyAsync(obs, f.d_obs, (size_t)f.n * row * 4, hipMemcpyDeviceToDevice, h->stream));
         HIPCHECK(hipMemcpyAsync(lb, f.d_lab, (size_t)f.n * 4 * 4, hipMemcpyDeviceToDevice, h->stream));
@@ -43,20 +44,27 @@ static int grow_dataset(clothhip_handle *h, int64_t n) {
         HIPCHECK(hipMemcpyAsync(rew, f.d_rew, (size_t)f.n * 4, hipMemcpyDeviceToDevice, h->stream));
         HIPCHECK(hipMemcpyAsync(ret, f.d_ret, (size_t)f.n * 4, hipMemcpyDeviceToDevice, h->stream));
         HIPCHECK(hipMemcpyAsync(next, f.d_next, (size_t)f.n * 4, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHECK(hipMemcpyAsync(old, f.d_old, (size_t)f.n * 4 * 4, hipMemcpyDeviceToDevice, h->stream));
         HIPCHECK(hipStreamSynchronize(h->stream));
     }
     f.d_obs = std::move(obs); f.d_lab = std::move(lb); f.d_w = std::move(w); f.d_rew = std::move(rew); f.d_ret = std::move(ret); f.d_next = std::move(next);
+    f.d_old = std::move(old);
     f.cap = cap;
     return 0;
 }
 
-// The n rows behind the ones that count get the defaults of the transition columns (reward 0, no successor: a leaf, value target 0), on
-// the device and in the host mirror of `next`; enqueued, the caller synchronises before the rows count. After grow_dataset.
+// The n rows behind the ones that count get the defaults of the transition columns (reward 0, no successor: a leaf, value target 0) and
+// of the old means (zeros, not set), on the device and in the host mirrors of `next` and of the set marks; enqueued, the caller
+// synchronises before the rows count. After grow_dataset.
 static int default_transitions(clothhip_handle *h, int64_t n) {
     auto &f = h->fit;
-    try { f.h_next.resize((size_t)f.n); f.h_next.resize((size_t)(f.n + n), CLOTHHIP_FIT_NEXT_NONE); } catch (const std::bad_alloc &) {
+    try {
+        f.h_next.resize((size_t)f.n); f.h_next.resize((size_t)(f.n + n), CLOTHHIP_FIT_NEXT_NONE);
+        f.h_old_set.resize((size_t)f.n); f.h_old_set.resize((size_t)(f.n + n), 0);
+    } catch (const std::bad_alloc &) {
         return fail(CLOTHHIP_ENOMEM, "out of host memory (%lld rows)", (long long)(f.n + n));
     }
+    HIPCHECK(hipMemsetAsync(f.d_old + (size_t)f.n * 4, 0, (size_t)n * 4 * 4, h->stream));
     HIPCHECK(hipMemsetAsync(f.d_rew + (size_t)f.n, 0, (size_t)n * 4, h->stream));
     HIPCHECK(hipMemsetAsync(f.d_ret + (size_t)f.n, 0, (size_t)n * 4, h->stream));
     HIPCHECK(hipMemsetD32Async((hipDeviceptr_t)(f.d_next + (size_t)f.n), CLOTHHIP_FIT_NEXT_NONE, (size_t)n, h->stream));
@@ -211,6 +219,7 @@ extern "C" int clothhip_fit_data_clear(clothhip_handle *h) {
     if (int rc = check_idle(h)) return rc;
     h->fit.n = 0;
     h->fit.h_next.clear();
+    h->fit.h_old_set.clear();
     return 0;
 }
 
@@ -506,8 +515,12 @@ template <bool A_KC, bool B_KC, int EPI, bool ROWS> static void launch_gemm(hipS
 
 // Enqueue every launch of one network's step, each over all n_m members: loss and gradient of the present weights over rows d_idx
 // [n_m][B] into d_loss [n_m] and h->fit.d_grad [n_m][n_params] (blob layout). d_loss NULL: the forward pass alone -- member j's y is
-// then at h->fit.d_act + j * p.act + p.h_off[L - 1]; shared_rows (the forward alone): d_idx is ONE list [B] that every member reads
-static int enqueue_grad(clothhip_handle *h, const FitNet &net, const FitPlan &p, int32_t n_m, const int32_t *d_idx, int32_t B, double *d_loss, bool shared_rows = false) {
+// then at h->fit.d_act + j * p.act + p.h_off[L - 1]; shared_rows (the forward alone): d_idx is ONE list [B] that every member reads.
+// ppo (the policy's table only): the loss launch is k_fit_loss_ppo with these constants, d_loss is then [n_m][FIT_PPO_STATS] and
+// d_ratio (may be NULL) [n_m][B]; every other launch is the same
+struct FitPpo { double inv_s2, half_inv_s2, lo, hi; };
+static int enqueue_grad(clothhip_handle *h, const FitNet &net, const FitPlan &p, int32_t n_m, const int32_t *d_idx, int32_t B, double *d_loss, bool shared_rows = false,
+                        const FitPpo *ppo = nullptr, float *d_ratio = nullptr) {
     const MlpDesc &D = net.D;
     const int L = D.n_layers;
     auto &f = h->fit;
@@ -528,7 +541,13 @@ static int enqueue_grad(clothhip_handle *h, const FitNet &net, const FitPlan &p,
         HIPCHECK(hipGetLastError());
     }
     if (!d_loss) return 0;
-    if (net.value)
+    if (ppo) {
+        FitPpoArgs q = {};
+        q.y = act + p.h_off[L - 1]; q.lab = f.d_lab; q.old = f.d_old; q.wgt = f.d_w; q.rows = d_idx; q.dz = dz[(L - 1) & 1]; q.ratio = d_ratio; q.stats = d_loss;
+        q.inv_s2 = ppo->inv_s2; q.half_inv_s2 = ppo->half_inv_s2; q.lo = ppo->lo; q.hi = ppo->hi;
+        q.y_step = (int64_t)p.act; q.dz_step = (int64_t)p.dz; q.rows_step = (int64_t)B; q.B = B;
+        hipLaunchKernelGGL(k_fit_loss_ppo, dim3((unsigned)n_m), dim3(256), 0, h->stream, q);
+    } else if (net.value)
         hipLaunchKernelGGL(k_fit_loss<1>, dim3((unsigned)n_m), dim3(256), 0, h->stream, (const float *)(act + p.h_off[L - 1]), (const float *)f.d_ret, (const float *)nullptr,
                            d_idx, B, dz[(L - 1) & 1], d_loss, (int64_t)p.act, (int64_t)p.dz, (int64_t)B);
     else
@@ -572,22 +591,27 @@ static int enqueue_grad(clothhip_handle *h, const FitNet &net, const FitPlan &p,
     return 0;
 }
 
-// loss and gradient of `members` over idx [n_m][B], nothing updated; the call is valid
-static int run_grad(clothhip_handle *h, const FitNet &net, const int32_t *members, int32_t n_m, const int32_t *idx, int32_t B, float *grad_out, double *loss_out) {
+// loss and gradient of `members` over idx [n_m][B], nothing updated; the call is valid. ppo: the clipped surrogate in the place of the
+// squared error, loss_out is then [n_m][FIT_PPO_STATS] and ratio_out (may be NULL) [n_m][B]
+static int run_grad(clothhip_handle *h, const FitNet &net, const int32_t *members, int32_t n_m, const int32_t *idx, int32_t B, float *grad_out, double *loss_out,
+                    const FitPpo *ppo = nullptr, float *ratio_out = nullptr) {
     auto &f = h->fit;
     const FitPlan p = fit_plan(net, B);
+    const size_t n_loss = (size_t)n_m * (ppo ? FIT_PPO_STATS : 1);
     HIPCHECK(hipSetDevice(h->device));
     if (int rc = fit_reserve(h, p, n_m)) return rc;
     if (int rc = f.d_idx.reserve((size_t)n_m * B * 4)) return rc;
-    if (int rc = f.d_loss.reserve((size_t)n_m * 8)) return rc;
+    if (int rc = f.d_loss.reserve(n_loss * 8)) return rc;
+    if (ratio_out) if (int rc = f.d_ratio.reserve((size_t)n_m * B * 4)) return rc;
     HIPCHECK(hipMemcpyAsync(f.d_members, members, (size_t)n_m * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipMemcpyAsync(f.d_idx, idx, (size_t)n_m * B * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipEventRecord(h->ev0, h->stream));
-    if (int rc = enqueue_grad(h, net, p, n_m, f.d_idx, B, f.d_loss)) return rc;
+    if (int rc = enqueue_grad(h, net, p, n_m, f.d_idx, B, f.d_loss, false, ppo, ratio_out ? (float *)f.d_ratio : nullptr)) return rc;
     HIPCHECK(hipEventRecord(h->ev1, h->stream));
     h->have_timing = true;
     if (grad_out) HIPCHECK(hipMemcpyAsync(grad_out, f.d_grad, (size_t)n_m * p.grad * 4, hipMemcpyDeviceToHost, h->stream));
-    if (loss_out) HIPCHECK(hipMemcpyAsync(loss_out, f.d_loss, (size_t)n_m * 8, hipMemcpyDeviceToHost, h->stream));
+    if (loss_out) HIPCHECK(hipMemcpyAsync(loss_out, f.d_loss, n_loss * 8, hipMemcpyDeviceToHost, h->stream));
+    if (ratio_out) HIPCHECK(hipMemcpyAsync(ratio_out, f.d_ratio, (size_t)n_m * B * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(hipStreamSynchronize(h->stream));
     return 0;
 }
@@ -652,14 +676,18 @@ extern "C" int clothhip_policy_fit_loss(clothhip_handle *h, const int32_t *idx, 
 
 // The forward alone on n stored rows, the same rows for every member: chunks through enqueue_grad, each chunk's y copied out to
 // d_pred [n_m][n][net.out()] (k_fit_copy_y), where it stays: enqueued between the timing events, not synchronised. The call is valid.
-static int enqueue_predict(clothhip_handle *h, const FitNet &net, const int32_t *members, int32_t n_m, const int32_t *idx, int64_t n) {
+// dst (n_m == 1): the table that gets y in the place of d_pred, [n][net.out()] -- a dataset column that is written where it lies.
+static int enqueue_predict(clothhip_handle *h, const FitNet &net, const int32_t *members, int32_t n_m, const int32_t *idx, int64_t n, float *dst = nullptr) {
     auto &f = h->fit;
     const int L = net.D.n_layers, W = net.out();
     const int32_t Bmax = (int32_t)std::min<int64_t>(n, std::min<int64_t>(FIT_MAX_BATCH, CLOTHHIP_FIT_MAX_MEMBER_ROWS / n_m));
     HIPCHECK(hipSetDevice(h->device));
     if (int rc = fit_reserve(h, fit_plan(net, Bmax), n_m)) return rc;
     if (int rc = f.d_idx.reserve((size_t)n * 4)) return rc;
-    if (int rc = f.d_pred.reserve((size_t)n_m * n * W * 4)) return rc;
+    if (!dst) {
+        if (int rc = f.d_pred.reserve((size_t)n_m * n * W * 4)) return rc;
+        dst = f.d_pred;
+    }
     HIPCHECK(hipMemcpyAsync(f.d_members, members, (size_t)n_m * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipMemcpyAsync(f.d_idx, idx, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipEventRecord(h->ev0, h->stream));
@@ -669,7 +697,7 @@ static int enqueue_predict(clothhip_handle *h, const FitNet &net, const int32_t 
         if (int rc = enqueue_grad(h, net, p, n_m, f.d_idx + (size_t)r0, B, nullptr, true)) return rc;
         const int32_t blocks = (W * B + 255) / 256;
         hipLaunchKernelGGL(k_fit_copy_y, dim3((unsigned)blocks * (unsigned)n_m), dim3(256), 0, h->stream, (const float *)(f.d_act + p.h_off[L - 1]), W * B,
-                           f.d_pred + (size_t)r0 * W, (int64_t)p.act, (int64_t)n * W, blocks);
+                           dst + (size_t)r0 * W, (int64_t)p.act, (int64_t)n * W, blocks);
         HIPCHECK(hipGetLastError());
     }
     HIPCHECK(hipEventRecord(h->ev1, h->stream));
@@ -716,15 +744,17 @@ static int ensure_row_state(const FitNet &net) {
     return 0;
 }
 
-// n_steps optimizer steps of `members` with the optimizers p [n_m] over idx [n_steps][n_m][B]; the call is valid and n_steps >= 1
+// n_steps optimizer steps of `members` with the optimizers p [n_m] over idx [n_steps][n_m][B]; the call is valid and n_steps >= 1.
+// ppo: every step's gradient is the clipped surrogate's, loss_out is then [n_steps][n_m][FIT_PPO_STATS]; the optimizer is the net's one
 static int run_fit(clothhip_handle *h, const FitNet &net, const ClothFitParams *p, const int32_t *members, int32_t n_m, const int32_t *idx, int32_t n_steps,
-                   int32_t B, double *loss_out) {
+                   int32_t B, double *loss_out, const FitPpo *ppo = nullptr) {
     const bool adam = p[0].optimizer == (float)CLOTHHIP_FIT_ADAM;
     auto &f = h->fit;
     const MlpDesc &D = net.D;
     const FitPlan pl = fit_plan(net, B);
     const size_t n = net.n_params, stride = (size_t)D.stride, n_sm = (size_t)n_steps * n_m;
     const size_t n_moments = net.pop_rows ? (size_t)net.pop_rows * stride : n;
+    const size_t per_loss = ppo ? FIT_PPO_STATS : 1;
     // the step constants of every (step, member), in double on the host, then rounded to float; nothing of the handle changes yet
     std::vector<float> hyper;
     try { hyper.assign(n_sm * FIT_HYPER, 0.0f); } catch (const std::bad_alloc &) { return fail(CLOTHHIP_ENOMEM, "out of host memory (%zu step constants)", n_sm * FIT_HYPER); }
@@ -744,7 +774,7 @@ static int run_fit(clothhip_handle *h, const FitNet &net, const ClothFitParams *
     HIPCHECK(hipSetDevice(h->device));
     if (int rc = fit_reserve(h, pl, n_m)) return rc;
     if (int rc = f.d_idx.reserve(n_sm * B * 4)) return rc;
-    if (int rc = f.d_loss.reserve(n_sm * 8)) return rc;
+    if (int rc = f.d_loss.reserve(n_sm * per_loss * 8)) return rc;
     if (int rc = f.d_hyper.reserve(n_sm * FIT_HYPER * 4)) return rc;
     // the moments of the whole table. A table of another network's size holds no row's state (every row is flagged read-as-zeros by
     // fit_forget when the network changes), so growing it loses nothing
@@ -769,7 +799,7 @@ static int run_fit(clothhip_handle *h, const FitNet &net, const ClothFitParams *
     const dim3 ogrid((unsigned)o.blocks * (unsigned)n_m);
     HIPCHECK(hipEventRecord(h->ev0, h->stream));
     for (int s = 0; s < n_steps; s++) {
-        if (int rc = enqueue_grad(h, net, pl, n_m, f.d_idx + (size_t)s * n_m * B, B, f.d_loss + (size_t)s * n_m)) return rc;
+        if (int rc = enqueue_grad(h, net, pl, n_m, f.d_idx + (size_t)s * n_m * B, B, f.d_loss + (size_t)s * n_m * per_loss, false, ppo)) return rc;
         o.hyper = f.d_hyper + (size_t)s * n_m * FIT_HYPER;
         if (adam) hipLaunchKernelGGL(k_fit_adam, ogrid, dim3(256), 0, h->stream, o);
         else hipLaunchKernelGGL(k_fit_sgd, ogrid, dim3(256), 0, h->stream, o);
@@ -777,7 +807,7 @@ static int run_fit(clothhip_handle *h, const FitNet &net, const ClothFitParams *
     }
     HIPCHECK(hipEventRecord(h->ev1, h->stream));
     h->have_timing = true;
-    if (loss_out) HIPCHECK(hipMemcpyAsync(loss_out, f.d_loss, n_sm * 8, hipMemcpyDeviceToHost, h->stream));
+    if (loss_out) HIPCHECK(hipMemcpyAsync(loss_out, f.d_loss, n_sm * per_loss * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(hipStreamSynchronize(h->stream));      // (the host tables are never retained)
     return 0;
 }
@@ -825,6 +855,105 @@ extern "C" int clothhip_policy_fit_reset_members(clothhip_handle *h, const int32
     if (int rc = check_fit_members(h, members, n_m)) return rc;
     if (h->fit.row_t.empty()) return 0;               // every row is fresh already
     for (int32_t j = 0; j < n_m; j++) { h->fit.row_t[members[j]] = 0; h->fit.row_zero[members[j]] = 1; }
+    return 0;
+}
+
+// ---- PPO: the old means and the clipped surrogate as one more loss mode of the trainer above (clothhip.h: PPO ON THE DEVICE) --------------
+static_assert(FIT_PPO_STATS == CLOTHHIP_PPO_STATS, "the statistics of the header and of the kernel");
+static_assert(sizeof(ClothPpoParams) == 16, "ClothPpoParams is two doubles");
+
+extern "C" int clothhip_fit_data_snapshot_policy(clothhip_handle *h, int64_t first, int64_t n) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (int rc = check_fit_state(h, false)) return rc;
+    if (int rc = check_range(h, first, n)) return rc;
+    if (n == 0) return 0;
+    auto &f = h->fit;
+    std::vector<int32_t> idx;
+    try { idx.resize((size_t)n); } catch (const std::bad_alloc &) { return fail(CLOTHHIP_ENOMEM, "out of host memory (%lld rows)", (long long)n); }
+    for (int64_t i = 0; i < n; i++) idx[(size_t)i] = (int32_t)(first + i);
+    // the launches of clothhip_policy_fit_predict; each chunk's y goes to its rows of the column, which are consecutive
+    if (int rc = enqueue_predict(h, policy_net(h), SHARED_ROW, 1, idx.data(), n, f.d_old + (size_t)first * 4)) return rc;
+    HIPCHECK(hipStreamSynchronize(h->stream));      // (idx, a host table the upload read, goes out of scope)
+    std::fill(f.h_old_set.begin() + first, f.h_old_set.begin() + first + n, (uint8_t)1);
+    return 0;
+}
+
+extern "C" int clothhip_fit_data_set_old_means(clothhip_handle *h, int64_t first, int64_t n, const float *mu) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (int rc = check_idle(h)) return rc;
+    if (int rc = check_range(h, first, n)) return rc;
+    if (n == 0) return 0;
+    if (!mu) return fail(CLOTHHIP_EINVAL, "NULL argument");
+    for (int64_t i = 0; i < 4 * n; i++)
+        if (!std::isfinite(mu[i])) return fail(CLOTHHIP_EINVAL, "mu[%lld][%lld] is not finite", (long long)(i / 4), (long long)(i % 4));
+    auto &f = h->fit;
+    HIPCHECK(hipSetDevice(h->device));
+    HIPCHECK(hipMemcpyAsync(f.d_old + (size_t)first * 4, mu, (size_t)n * 4 * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));      // (the host table is not retained)
+    std::fill(f.h_old_set.begin() + first, f.h_old_set.begin() + first + n, (uint8_t)1);
+    return 0;
+}
+
+extern "C" int clothhip_fit_data_get_old_means(clothhip_handle *h, int64_t first, int64_t n, float *mu) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (int rc = check_idle(h)) return rc;
+    if (int rc = check_range(h, first, n)) return rc;
+    if (n == 0) return 0;
+    if (!mu) return fail(CLOTHHIP_EINVAL, "NULL argument");
+    HIPCHECK(hipSetDevice(h->device));
+    HIPCHECK(hipMemcpyAsync(mu, h->fit.d_old + (size_t)first * 4, (size_t)n * 4 * 4, hipMemcpyDeviceToHost, h->stream));      // (an unset row holds zeros)
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// the constants of a PPO call and the rows of its minibatches, after everything clothhip_policy_fit refuses: -> the kernel's constants
+static int check_ppo(const clothhip_handle *h, const ClothPpoParams *q, const int32_t *idx, int64_t n_idx, FitPpo *out) {
+    if (!std::isfinite(q->sigma) || q->sigma <= 0.0) return fail(CLOTHHIP_EINVAL, "sigma = %g: the policy's standard deviation is finite and > 0", q->sigma);
+    if (!std::isfinite(q->clip) || q->clip < 0.0 || q->clip >= 1.0) return fail(CLOTHHIP_EINVAL, "clip = %g: the clip range lies in [0, 1)", q->clip);
+    const double s2 = q->sigma * q->sigma;
+    out->inv_s2 = 1.0 / s2;
+    out->half_inv_s2 = 0.5 * out->inv_s2;
+    out->lo = 1.0 - q->clip;
+    out->hi = 1.0 + q->clip;
+    if (!std::isfinite(out->inv_s2)) return fail(CLOTHHIP_EINVAL, "sigma = %g: 1 / sigma^2 is not a finite double", q->sigma);
+    for (int64_t i = 0; i < n_idx; i++)
+        if (!h->fit.h_old_set[(size_t)idx[i]])
+            return fail(CLOTHHIP_ESTATE, "idx[%lld] = row %d has no old mean: call clothhip_fit_data_snapshot_policy or clothhip_fit_data_set_old_means on it first",
+                        (long long)i, idx[i]);
+    return 0;
+}
+
+extern "C" int clothhip_policy_fit_ppo_grad(clothhip_handle *h, const ClothPpoParams *q, const int32_t *idx, int32_t B, float *grad_out, double *stats_out,
+                                            float *ratio_out) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (!q) return fail(CLOTHHIP_EINVAL, "NULL argument");
+    if (int rc = check_fit_state(h, false)) return rc;
+    if (int rc = check_fit_rows(h, 1, idx, B, B)) return rc;
+    FitPpo ppo;
+    if (int rc = check_ppo(h, q, idx, B, &ppo)) return rc;
+    return run_grad(h, policy_net(h), SHARED_ROW, 1, idx, B, grad_out, stats_out, &ppo, ratio_out);
+}
+
+extern "C" int clothhip_policy_fit_ppo(clothhip_handle *h, const ClothFitParams *p, const ClothPpoParams *q, const int32_t *idx, int32_t n_steps, int32_t B,
+                                       double *stats_out) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (!p || !q) return fail(CLOTHHIP_EINVAL, "NULL argument");
+    if (n_steps < 0) return fail(CLOTHHIP_EINVAL, "n_steps < 0");
+    if (int rc = check_fit_state(h, false)) return rc;
+    if (int rc = check_fit_rows(h, 1, idx, (int64_t)n_steps * B, B)) return rc;
+    if (int rc = check_fit_params(p, -1)) return rc;
+    FitPpo ppo;
+    if (int rc = check_ppo(h, q, idx, (int64_t)n_steps * B, &ppo)) return rc;
+    if (n_steps == 0) return 0;
+    return run_fit(h, policy_net(h), p, SHARED_ROW, 1, idx, n_steps, B, stats_out, &ppo);
+}
+
+extern "C" int clothhip_selftest_exp_fixed(const double *x, int64_t n, double *out) {
+    if (n < 0 || (n > 0 && (!x || !out))) return fail(CLOTHHIP_EINVAL, "bad argument");
+    for (int64_t i = 0; i < n; i++) {
+        if (x[i] != x[i]) return fail(CLOTHHIP_EINVAL, "x[%lld] is NaN", (long long)i);
+        out[i] = exp_fixed(x[i]);
+    }
     return 0;
 }
 

@@ -174,6 +174,12 @@ struct clothhip_handle : HostPlan {
         Buffer<float> d_rew, d_ret;
         Buffer<int32_t> d_next;
         std::vector<int32_t> h_next;
+        // the old means of PPO (clothhip_fit_data_snapshot_policy / _set_old_means; the column grows with the rows): d_old [cap][4], what
+        // the shared network's mean was when the row was collected, zeros until written, and the host mirror h_old_set [n], one byte per
+        // row: whether it has been written -- against which clothhip_policy_fit_ppo* check a minibatch without a download
+        Buffer<float> d_old;
+        std::vector<uint8_t> h_old_set;
+        Buffer<float> d_ratio;       // clothhip_policy_fit_ppo_grad: (float)rho of the minibatch's rows, [B]
         // rows named by where they lie (clothhip_fit_hold, clothhip_fit_data_append_launch): held [E][3P], one row per env that outlives
         // the launch tables (held_valid: some clothhip_fit_hold has filled it); the index table of one call and its not-finite flag
         Buffer<float> d_held;

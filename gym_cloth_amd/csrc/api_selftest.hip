@@ -1,5 +1,5 @@
 // api_selftest.hip -- clothhip_selftest_*: host and device pieces exposed to the test suite. (The two that test cloth_render_obs.hpp are
-// beside its kernels in api_observe.hip: a header with a non-template kernel has one includer.)
+// beside its kernels in api_observe.hip, and clothhip_selftest_exp_fixed beside cloth_policy_fit.hpp's in api_fit.hip: a header with a non-template kernel has one includer.)
 #include <hip/hip_runtime.h>
 
 #include "api_handle.hpp"

@@ -36,6 +36,9 @@
 //   * the value network (output width 1, clothhip.h: FITTING THE CRITIC) is one more table of one row for the same kernels: N = 1 in
 //     its last forward product, M = 1 in that layer's weight gradient, K = 1 in its input gradient -- each a tile whose other 63 rows,
 //     columns or 15 k are the zeros in LDS above; k_fit_loss<1> sums B squares in the order k_fit_loss<4> sums 4 B;
+//   * PPO's clipped surrogate (clothhip.h: PPO ON THE DEVICE) is one more loss launch of the policy's table, k_fit_loss_ppo in the place of
+//     k_fit_loss<4>: per row a probability ratio against the dataset's stored old mean through exp_fixed, dZ in double with one rounding
+//     to float32, three sums over ROWS in the order above; forward, backward and optimizer are the launches of the squared error;
 //   The forward's summation order differs from mlp_eval's (64 interleaved lane sums and a butterfly there), so the trainer's y need not equal
 //   clothhip_policy_eval's bits; the blob it writes is evaluated by mlp_eval as any uploaded blob is.
 #pragma once
@@ -209,6 +212,110 @@ template <int W> __global__ __launch_bounds__(256) void k_fit_loss(const float *
         __syncthreads();
     }
     if (tid == 0) loss[j] = red[0] / (double)((W == 4 ? 4 : 2) * (int64_t)B);
+}
+
+// exp(x) for x clamped to [-40, 40], made of plain double operations, each ONE rounding (no library exp, no contraction), so that numpy
+// restates it bit for bit (policies.exp_fixed_reference) and the host runs the very function (clothhip_selftest_exp_fixed):
+//   k = rint(x log2e);  r = (x - k ln2_hi) - k ln2_lo  (fdlibm's two constants: k ln2_hi is exact for |k| <= 58);  p = Horner over the
+//   Taylor coefficients 1 / i!, i = 13 .. 0 (|r| <= 0.3466: the remainder is below 4e-18 of p);  p 2^k, the power built from its bits.
+// Within 2.2e-16 relative of exp over [-40, 40]; exp_fixed(0) == 1.0 exactly (k = 0, r = 0, p = 1). x must not be NaN.
+__host__ __device__ inline double exp_fixed(double x) {
+    x = x < -40.0 ? -40.0 : x;
+    x = x > 40.0 ? 40.0 : x;
+    const double k = __builtin_rint(x * 1.44269504088896338700e+00);
+    const double hi = k * 6.93147180369123816490e-01, lo = k * 1.90821492927058770002e-10;
+    const double xh = x - hi, r = xh - lo;
+    const double c[14] = {1.0, 1.0, 1.0 / 2.0, 1.0 / 6.0, 1.0 / 24.0, 1.0 / 120.0, 1.0 / 720.0, 1.0 / 5040.0, 1.0 / 40320.0, 1.0 / 362880.0,
+                          1.0 / 3628800.0, 1.0 / 39916800.0, 1.0 / 479001600.0, 1.0 / 6227020800.0};
+    double p = c[13];
+#pragma unroll
+    for (int i = 12; i >= 0; i--) {
+        const double pr = p * r;
+        p = pr + c[i];
+    }
+    const uint64_t bits = (uint64_t)(1023 + (int)k) << 52;      // 2^k, k in [-58, 58]
+    double scale;
+    __builtin_memcpy(&scale, &bits, 8);
+    return p * scale;
+}
+
+// PPO's clipped surrogate of a fixed-sigma Gaussian policy in the place of k_fit_loss<4> (clothhip.h: PPO ON THE DEVICE has the
+// arithmetic operation by operation): the same launch shape, one workgroup of 256 per member, but a thread owns whole ROWS -- thread t
+// takes minibatch rows t, t + 256, ... ascending -- since a row's ratio needs its four components. lab, old (16-byte rows of the
+// dataset's tables) are read as one 16-byte load each; y and dz lie at B-dependent offsets of the scratch tables that need not be
+// 16-byte aligned, so their four floats move under a 4-byte alignment promise and the compiler picks the widest legal access. Three
+// sums (surrogate, rows not active, kl) in the house order: per thread over its rows ascending, then a halving tree each in LDS.
+// stats[j] = {-sum surrogate / B, not active / B, sum kl / B}; ratio (may be NULL) [n_m][B] gets (float)rho. Ordinary stores only.
+struct FitPpoArgs {
+    const float *y, *lab, *old, *wgt;
+    const int32_t *rows;
+    float *dz, *ratio;
+    double *stats;
+    double inv_s2, half_inv_s2, lo, hi;     // 1 / sigma^2, 0.5 / sigma^2, 1 - eps, 1 + eps: formed once in double on the host
+    int64_t y_step, dz_step, rows_step;
+    int32_t B;
+};
+constexpr int FIT_PPO_STATS = 3;            // = CLOTHHIP_PPO_STATS
+
+__global__ __launch_bounds__(256) void k_fit_loss_ppo(FitPpoArgs a) {
+    __shared__ double red[FIT_PPO_STATS][256];
+    const int64_t j = blockIdx.x;
+    const float *y = a.y + j * a.y_step;
+    float *dz = a.dz + j * a.dz_step;
+    const int32_t *rows = a.rows + j * a.rows_step;
+    const int tid = threadIdx.x;
+    const double Bd = (double)a.B;
+    double s_sur = 0.0, s_clip = 0.0, s_kl = 0.0;
+    for (int r = tid; r < a.B; r += 256) {
+        const size_t row = (size_t)rows[r];
+        float mu[4], out[4];
+        __builtin_memcpy(mu, y + (size_t)4 * r, 16);
+        const float4 av = reinterpret_cast<const float4 *>(a.lab)[row], ov = reinterpret_cast<const float4 *>(a.old)[row];
+        const float act[4] = {av.x, av.y, av.z, av.w}, mo[4] = {ov.x, ov.y, ov.z, ov.w};
+        double q = 0.0, kl = 0.0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const double d_old = (double)act[k] - (double)mo[k], d_new = (double)act[k] - (double)mu[k];
+            const double sq_old = d_old * d_old, sq_new = d_new * d_new;
+            const double t = sq_old - sq_new;
+            q = q + t;
+            const double e = (double)mu[k] - (double)mo[k];
+            const double ee = e * e;
+            kl = kl + ee;
+        }
+        const double x = q * a.half_inv_s2;
+        const double rho = exp_fixed(x);
+        const double A = (double)a.wgt[row];
+        const double s1 = rho * A;
+        double rc = rho < a.lo ? a.lo : rho;
+        rc = rc > a.hi ? a.hi : rc;
+        const double s2 = rc * A;
+        const bool active = s1 <= s2;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const double d = (double)mu[k] - (double)act[k];
+            const double g1 = s1 * d, g2 = g1 * a.inv_s2, g3 = g2 / Bd;
+            out[k] = active ? (float)g3 : 0.0f;
+        }
+        __builtin_memcpy(dz + (size_t)4 * r, out, 16);
+        if (a.ratio) a.ratio[j * a.B + r] = (float)rho;
+        s_sur = s_sur + (active ? s1 : s2);
+        s_clip = s_clip + (active ? 0.0 : 1.0);
+        s_kl = s_kl + kl * a.half_inv_s2;
+    }
+    red[0][tid] = s_sur; red[1][tid] = s_clip; red[2][tid] = s_kl;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) {
+#pragma unroll
+            for (int i = 0; i < FIT_PPO_STATS; i++) red[i][tid] = red[i][tid] + red[i][tid + o];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        double *st = a.stats + j * FIT_PPO_STATS;
+        st[0] = -red[0][0] / Bd; st[1] = red[1][0] / Bd; st[2] = red[2][0] / Bd;
+    }
 }
 
 // The optimizers: member j updates row members[j] of theta, m, v ([rows][stride]) from g + j * n with ITS OWN step constants

@@ -532,3 +532,29 @@ def actor_critic_fit(env, trainer, critic, col, gamma=0.99, lam=0.95, n_value_st
     vl = critic.step(n_value_steps, batch_size, seed, rows=rows) if len(rows) else np.zeros(0)
     pl = trainer.step(n_policy_steps, batch_size, seed)
     return {'adv': adv, 'ret': ret, 'value_losses': vl, 'policy_losses': pl, 'rows': trainer.size()}
+
+
+def ppo_fit(env, trainer, critic, col, sigma, gamma=0.99, lam=0.95, clip=0.2, n_value_steps=100, n_epochs=10, batch_size=64, seed=0,
+            target_kl=None, normalize=True):
+    """The refit after actor_critic_collect with PPO's clipped surrogate in the place of actor_critic_fit's weighted regression, on the
+    device: ONE fit_gae call over the rows `col` added writes their value targets and, as loss weights with w_scale = 1, their
+    advantages (normalised over the non-leaf rows with normalize; a leaf gets 0); ONE trainer.snapshot_old over the same rows stores
+    the present policy's means as their old means, BEFORE any policy step; then n_value_steps steps of `critic` on the non-leaf rows of
+    the whole dataset; then trainer.ppo_step on the COLLECTION's non-leaf rows: up to n_epochs epochs of minibatches of batch_size,
+    stopped by target_kl. Because a row's gradient is switched off once its ratio has left [1 - clip, 1 + clip] in the direction of its
+    advantage, many epochs on one collection stay bounded where actor_critic_fit's steps diverge. sigma is the standard deviation of
+    the policy_noise the collection ACTED with -- the caller's number: the launch draws the noise, the library does not record it, and
+    a wrong sigma gives wrong ratios. Returns dict(adv, ret float32[n]: fit_gae's, value_losses float64, ppo_stats float64[steps, 3]:
+    loss, clip_fraction, kl of every policy step before its update, epochs: the epochs run, rows)."""
+    if trainer.env is not env or critic.env is not env:
+        raise ValueError("the trainer or the critic belongs to another env")
+    n = int(col['appended']) + int(col['open_rows'])
+    adv, ret = env.batch.fit_gae(gamma, lam, first=col['first'], n=n, write_weights=True, normalize=normalize, w_scale=1.0)
+    trainer.snapshot_old(col['first'], n)
+    rew, nxt = env.batch.fit_get_transitions()
+    from ._lib import FIT_NEXT_NONE
+    rows = np.nonzero(nxt != FIT_NEXT_NONE)[0]
+    vl = critic.step(n_value_steps, batch_size, seed, rows=rows) if len(rows) else np.zeros(0)
+    mine = np.asarray(col['nonleaf'], dtype=np.int64)
+    stats, epochs = trainer.ppo_step(n_epochs, batch_size, seed, sigma, clip=clip, target_kl=target_kl, rows=mine) if len(mine) else (np.zeros((0, 3)), 0)
+    return {'adv': adv, 'ret': ret, 'value_losses': vl, 'ppo_stats': stats, 'epochs': epochs, 'rows': trainer.size()}

@@ -24,6 +24,8 @@ MLPTrainer           no reference counterpart: the supervised refit of the share
 MLPEnsemble          no reference counterpart: G networks, one per env slot, fitted together on the device in the launches of one
                      (ClothBatch.fit_members): a bootstrapped ensemble whose disagreement is a novelty signal, a learning-rate sweep
 """
+import math
+
 import numpy as np
 
 
@@ -548,6 +550,84 @@ def gae_reference(v, rew, next, gamma, lam, w_scale=1.0, normalize=False):
     return adv, ret, w
 
 
+_LOG2E, _LN2_HI, _LN2_LO = float.fromhex('0x1.71547652b82fep+0'), float.fromhex('0x1.62e42feep-1'), float.fromhex('0x1.a39ef35793c76p-33')
+_EXP_COEF = [1.0 / math.factorial(i) for i in range(14)]      # correctly rounded quotients of exact integers, as the compiler folds them
+
+
+def exp_fixed_reference(x):
+    """The device's exponential restated in float64 numpy, operation by operation (include/clothhip.h: PPO ON THE DEVICE; csrc/
+    cloth_policy_fit.hpp exp_fixed): x clamped to [-40, 40], k = rint(x log2e), r = (x - k ln2_hi) - k ln2_lo with fdlibm's constants,
+    Horner over 1 / i! for i = 13 .. 0 with a rounded product and a rounded sum per step, the result scaled by 2^k exactly. Bit for bit
+    what the kernel and clothhip_selftest_exp_fixed compute; within 2.2e-16 relative of math.exp, and exactly 1.0 at 0."""
+    x = np.minimum(np.maximum(np.asarray(x, dtype=np.float64), -40.0), 40.0)
+    k = np.rint(x * _LOG2E)
+    r = (x - k * _LN2_HI) - k * _LN2_LO
+    p = np.full_like(x, _EXP_COEF[13])
+    for i in range(12, -1, -1):
+        p = p * r + _EXP_COEF[i]
+    return np.ldexp(p, k.astype(np.int64))
+
+
+def ppo_loss_reference(y, actions, old, adv, sigma, clip, B):
+    """k_fit_loss_ppo restated in float64 numpy from a given float32 y, bit for bit, reduction order included (include/clothhip.h: PPO
+    ON THE DEVICE): y, actions, old [B, 4] and adv [B] are the minibatch's rows in order (the network's output, the stored labels, old
+    means and weights, all float32). Returns (stats float64[3] = loss, clip_fraction, kl; dz float32[B, 4]; ratio float32[B]; active
+    bool[B])."""
+    f64 = lambda v: np.asarray(v, dtype=np.float32).astype(np.float64)
+    mu, a, mo, A = f64(y).reshape(-1, 4), f64(actions).reshape(-1, 4), f64(old).reshape(-1, 4), f64(adv).reshape(-1)
+    if not (len(mu) == len(a) == len(mo) == len(A) == int(B)):
+        raise ValueError("y, actions, old [B, 4] and adv [B] must hold the B rows of the minibatch")
+    inv_s2 = 1.0 / (float(sigma) * float(sigma))
+    half, lo, hi, Bd = 0.5 * inv_s2, 1.0 - float(clip), 1.0 + float(clip), float(int(B))
+    q, kl = np.zeros(len(A)), np.zeros(len(A))
+    for k in range(4):
+        d_old, d_new, e = a[:, k] - mo[:, k], a[:, k] - mu[:, k], mu[:, k] - mo[:, k]
+        q = q + (d_old * d_old - d_new * d_new)
+        kl = kl + e * e
+    rho = exp_fixed_reference(q * half)
+    s1, s2 = rho * A, np.minimum(np.maximum(rho, lo), hi) * A
+    active = s1 <= s2
+    with np.errstate(over='ignore'):
+        dz = np.where(active[:, None], (((s1[:, None] * (mu - a)) * inv_s2) / Bd).astype(np.float32), np.float32(0.0)).astype(np.float32)
+    stats = np.array([-_house_sum(np.where(active, s1, s2)) / Bd, _house_sum(np.where(active, 0.0, 1.0)) / Bd, _house_sum(kl * half) / Bd])
+    return stats, dz, rho.astype(np.float32), active
+
+
+def ppo_reference(layers, obs, actions, old, adv, idx, sigma, clip):
+    """Pure-numpy float64 loss and gradient of PPO's clipped surrogate for a Gaussian policy of fixed standard deviation sigma whose
+    mean is the network's output, beside fit_reference and with its conventions (obs [n, in], actions [n, 4], old [n, 4] the old
+    means, adv [n] the advantages, all rounded to float32 first; idx [B] the minibatch; math.exp):
+        rho_r = exp((|a - mu_old|^2 - |a - mu|^2) / (2 sigma^2))   (the exponent clamped to [-40, 40], as the device does),
+        L = -1 / B sum_r min(rho_r A_r, clip(rho_r, 1 - eps, 1 + eps) A_r),
+    a row is ACTIVE when rho A <= clip(rho) A (the first term is the minimum: its gradient counts; inside the interval both are equal),
+    dL/dmu_rk = A rho (mu_rk - a_rk) / (sigma^2 B) on active rows, else 0. Returns (stats, [(dW, db), ...], rho float64[B], active
+    bool[B]) with stats = (loss, clip_fraction = share of rows not active, kl = 1 / B sum_r |mu - mu_old|^2 / (2 sigma^2))."""
+    ix = np.asarray(idx, dtype=np.int64).reshape(-1)
+    Ws = [np.asarray(W, dtype=np.float32).astype(np.float64) for W, _ in layers]
+    bs = [np.asarray(b, dtype=np.float32).astype(np.float64) for _, b in layers]
+    f64 = lambda v: np.asarray(v, dtype=np.float64).astype(np.float32).astype(np.float64)
+    x, a, mo, A = f64(obs)[ix], f64(actions)[ix], f64(old)[ix], f64(adv).reshape(-1)[ix]
+    B, L = len(ix), len(Ws)
+    hs = [x]
+    for l in range(L):
+        z = hs[-1] @ Ws[l].T + bs[l]
+        hs.append(np.maximum(z, 0.0) if l + 1 < L else z)
+    mu = hs[-1]
+    inv_s2 = 1.0 / (float(sigma) * float(sigma))
+    q = ((a - mo) ** 2 - (a - mu) ** 2).sum(axis=1)
+    rho = np.array([math.exp(min(max(v, -40.0), 40.0)) for v in q * (0.5 * inv_s2)])
+    s1, s2 = rho * A, np.clip(rho, 1.0 - float(clip), 1.0 + float(clip)) * A
+    active = s1 <= s2
+    stats = (float(-np.where(active, s1, s2).sum() / B), float((~active).sum() / float(B)), float((((mu - mo) ** 2).sum(axis=1) * (0.5 * inv_s2)).sum() / B))
+    g = np.where(active[:, None], (s1[:, None] * (mu - a)) * inv_s2 / B, 0.0)
+    grads = [None] * L
+    for l in range(L - 1, -1, -1):
+        grads[l] = (g.T @ hs[l], g.sum(axis=0))
+        if l:
+            g = (g @ Ws[l]) * (hs[l] > 0.0)
+    return stats, grads, rho, active
+
+
 def adam_reference(theta, m, v, g, t, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8):
     """The device's Adam step restated in numpy float32, operation by operation (include/clothhip.h, clothhip_policy_fit): t is the
     1-based step count. Returns the new (theta, m, v), float32."""
@@ -646,6 +726,47 @@ class MLPTrainer(object):
         """(loss, [(dW, db), ...]) over the dataset rows idx at the present weights, float32 from the device; nothing is updated."""
         loss, g = self.env.batch.fit_grad(idx)
         return loss, unpack_mlp(self.widths, g)
+
+    def snapshot_old(self, first=0, n=None):
+        """Store the network's present output on the dataset rows [first, first + n) (n=None: to the end) as their OLD MEANS, on the
+        device (ClothBatch.fit_snapshot_policy): what ppo_step's probability ratios are taken against. Call it after a collection and
+        before the first policy step on it."""
+        self.env.batch.fit_snapshot_policy(first, n)
+
+    @staticmethod
+    def ppo_epoch_tables(rows, n_epochs, batch_size, seed):
+        """The minibatches of ppo_step: a list of n_epochs int32 tables [n_minibatches, B]. ONE RandomState(seed) draws a permutation of
+        `rows` (int [m]) per epoch, which is cut into minibatches of batch_size in order; the short tail is dropped when there is more
+        than one minibatch, and m < batch_size gives one minibatch of all m rows. A function of the arguments alone."""
+        rows = np.asarray(rows)
+        if rows.ndim != 1 or rows.size < 1 or not np.issubdtype(rows.dtype, np.integer):
+            raise ValueError("rows must be a non-empty 1-d integer array")
+        if int(n_epochs) < 0 or int(batch_size) < 1:
+            raise ValueError("ppo_epoch_tables needs n_epochs >= 0, batch_size >= 1")
+        m, B = rows.size, min(int(batch_size), rows.size)
+        r = np.random.RandomState(seed)
+        return [rows[r.permutation(m)][:(m // B) * B].reshape(m // B, B).astype(np.int32) for _ in range(int(n_epochs))]
+
+    def ppo_step(self, n_epochs, batch_size, seed, sigma, clip=0.2, target_kl=None, rows=None):
+        """PPO on the device (ClothBatch.fit_ppo): up to n_epochs epochs over `rows` (int [m] dataset rows, None: all), each the
+        minibatches of ppo_epoch_tables in ONE fit_ppo call -- optimizer steps on the clipped surrogate with the advantages in the
+        weight column and the old means of snapshot_old, under this trainer's optimizer (shared with step). sigma is the standard
+        deviation of the noise the rows' actions were drawn with, clip the range epsilon. With target_kl the loop stops after the first
+        epoch whose mean kl exceeds it. Returns (stats float64[steps, 3]: loss, clip_fraction, kl of every step before its update;
+        epochs run)."""
+        if rows is None:
+            n = self.size()
+            if n < 1:
+                raise ValueError("the dataset is empty: append first")
+            rows = np.arange(n)
+        out, epochs = [], 0
+        for table in self.ppo_epoch_tables(rows, n_epochs, batch_size, seed):
+            stats = self.env.batch.fit_ppo(table, sigma, clip, **self.hyper)
+            out.append(stats)
+            epochs += 1
+            if target_kl is not None and float(np.mean(stats[:, 2])) > float(target_kl):
+                break
+        return (np.concatenate(out) if out else np.zeros((0, 3))), epochs
 
     def layers(self):
         """The network as the device holds it now: [(W, b), ...] float32, by download (clothhip_get_policy_mlp)."""

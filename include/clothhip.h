@@ -667,6 +667,54 @@ int clothhip_value_fit_reset(clothhip_handle *h);
 int clothhip_value_predict(clothhip_handle *h, const int32_t *idx, int64_t n, float *v_out);
 int clothhip_fit_data_gae(clothhip_handle *h, int64_t first, int64_t n, const ClothGaeParams *p, float *adv_out, float *ret_out);
 
+/* PPO ON THE DEVICE (no reference counterpart): the clipped surrogate of a Gaussian policy with a fixed standard
+ * deviation sigma and the shared network's output as its mean, over stored OLD MEANS. A weighted squared error under a negative weight
+ * has no minimum, so a collection paid for one policy-gradient step; the clipped surrogate switches a row's gradient off once its
+ * probability ratio has left [1 - eps, 1 + eps] in the direction its advantage pushes, so many steps on one collection stay bounded.
+ * The advantages are the dataset's weight column (clothhip_fit_data_gae with w_scale 1 writes them), the actions its labels.
+ * THE OLD MEANS are a fifth column of the dataset, old[n][4] float32: what the policy's mean was when the row was collected. It grows
+ * with the rows, keeps its contents on growth and clothhip_fit_data_clear empties it. A row appended by any entry has NO old mean
+ * until one is written (the handle keeps one byte per row). clothhip_fit_data_snapshot_policy runs the trainer's forward of the shared
+ * network over the rows [first, first + n) -- the launches of clothhip_policy_fit_predict, in chunks of at most
+ * CLOTHHIP_FIT_MAX_BATCH -- and stores y into the column where it lies: nothing is downloaded, and the stored bytes are those
+ * clothhip_policy_fit_predict returns for these rows. Its refusals are clothhip_policy_fit_predict's (CLOTHHIP_ESTATE: a launch in
+ * flight, no shared network, a population on the handle -- per-member old means do not exist --, an empty dataset) and CLOTHHIP_EINVAL
+ * for a range outside the dataset; n == 0 returns 0. clothhip_fit_data_set_old_means writes mu[n][4] (host float32) to the rows and
+ * marks them, _get_old_means downloads the column (zeros for a row without an old mean); both are refused as
+ * clothhip_fit_data_set_returns is: a range outside the dataset, a value that is not finite, a NULL table with n > 0, a launch in flight.
+ * THE LOSS over a minibatch of B rows, with mu = y the network's float32 output, a the stored label, mo the stored old mean and A the
+ * stored weight of the row. The host forms in double, once: inv_s2 = 1 / (sigma sigma), half_inv_s2 = 0.5 inv_s2, lo = 1 - clip,
+ * hi = 1 + clip. Per row, every operation ONE double rounding on the (double) of the float32 values, no contraction:
+ *   q = 0; for k = 0 .. 3: q = q + (((a_k - mo_k) (a_k - mo_k)) - ((a_k - mu_k) (a_k - mu_k)))
+ *   x = q half_inv_s2;  rho = exp_fixed(x)            the probability ratio pi(a) / pi_old(a); exp_fixed clamps x to [-40, 40] first
+ *   s1 = rho A;  s2 = min(max(rho, lo), hi) A;  active = s1 <= s2           (inside the interval s1 == s2: active)
+ *   dz_k = active ? (float)((((s1 (mu_k - a_k)) inv_s2) / (double)B) : 0.0f       = d(-s1 / B) / d mu_k
+ *   surrogate = active ? s1 : s2  (= min(s1, s2));   kl = 0; for k = 0 .. 3: kl = kl + (mu_k - mo_k) (mu_k - mo_k);  kl_row = kl half_inv_s2
+ * exp_fixed(x): x clamped to [-40, 40]; k = rint(x log2e); r = (x - k ln2_hi) - k ln2_lo with fdlibm's log2e = 1.44269504088896338700e+00,
+ * ln2_hi = 6.93147180369123816490e-01, ln2_lo = 1.90821492927058770002e-10; p = 1 / 13!, then p = p r + 1 / i! for i = 12 .. 0 (a
+ * product and a sum, each rounded; 1 / i! the correctly rounded quotient); the result p 2^k, exact. No library exp is called:
+ * policies.exp_fixed_reference restates it in numpy bit for bit, and clothhip_selftest_exp_fixed runs the same function on the host
+ * (out[i] = exp_fixed(x[i]); CLOTHHIP_EINVAL for a NaN). It is within 2.2e-16 relative of exp, and exp_fixed(0) == 1.0.
+ * Three sums over the minibatch in the order of clothhip_policy_fit_grad's loss, over ROWS: thread t of 256 adds its rows t, t + 256,
+ * ... ascending, the 256 sums are added by a halving tree. stats[0] = loss = -(sum surrogate) / B; stats[1] = clip_fraction = (rows
+ * not active) / B; stats[2] = kl = (sum kl_row) / B. A caller stops its epochs on the last two. Everything behind dz is the
+ * trainer's backward pass, unchanged; no floating-point atomics. With mo == mu and A = w sigma^2 / 2 the gradient is that of the
+ * weighted squared error.
+ * clothhip_policy_fit_ppo_grad is clothhip_policy_fit_grad for this loss: grad_out[n_params] (may be NULL), stats_out[3] (may be
+ * NULL), ratio_out[B] (may be NULL) = (float)rho per minibatch row; nothing is updated. clothhip_policy_fit_ppo is
+ * clothhip_policy_fit for it: stats_out[n_steps][3] (may be NULL) are each step's statistics BEFORE its update. It uses the POLICY'S
+ * optimizer: a squared-error step and a PPO step of one handle share the moments and the step count, and clothhip_policy_fit_reset
+ * restarts both. Refused before the first launch, nothing changed -- everything clothhip_policy_fit refuses (with q == NULL as a NULL
+ * table); CLOTHHIP_EINVAL: sigma not finite or <= 0 (or so small that 1 / sigma^2 is not finite), clip not finite, < 0 or >= 1;
+ * CLOTHHIP_ESTATE: an idx entry whose row has no old mean (the message names the row). Shared network only. */
+typedef struct ClothPpoParams { double sigma, clip; } ClothPpoParams;
+#define CLOTHHIP_PPO_STATS 3      /* loss, clip_fraction, kl */
+int clothhip_fit_data_snapshot_policy(clothhip_handle *h, int64_t first, int64_t n);
+int clothhip_fit_data_set_old_means(clothhip_handle *h, int64_t first, int64_t n, const float *mu);
+int clothhip_fit_data_get_old_means(clothhip_handle *h, int64_t first, int64_t n, float *mu);
+int clothhip_policy_fit_ppo_grad(clothhip_handle *h, const ClothPpoParams *q, const int32_t *idx, int32_t B, float *grad_out, double *stats_out, float *ratio_out);
+int clothhip_policy_fit_ppo(clothhip_handle *h, const ClothFitParams *p, const ClothPpoParams *q, const int32_t *idx, int32_t n_steps, int32_t B, double *stats_out);
+
 int clothhip_run_actions(clothhip_handle *h, const ClothEpisodeParams *ep, int32_t T, int32_t policy,
                          const double *actions, int32_t actions_on_device, const int32_t *policy_arg,
                          const ClothResetScript *scripts, int32_t n_scripts, int32_t *num_steps, uint8_t *done,
@@ -898,6 +946,9 @@ int clothhip_selftest_rng(uint32_t *state, int32_t kind, int32_t n, double a, do
  * (out[2] is then what that band would need) and clothhip_render_obs returns CLOTHHIP_EINVAL for that size. */
 int clothhip_selftest_depth8(const float *depth, int32_t n_images, int64_t npx, uint8_t *out);
 int clothhip_selftest_render_plan(const ClothParams *params, int32_t width, int32_t height, int32_t out[4]);
+/* Host-side self-test of PPO's exponential (PPO ON THE DEVICE above): out[i] = exp_fixed(x[i]), the inline function k_fit_loss_ppo runs
+ * (csrc/cloth_policy_fit.hpp), computed on the host; no device needed. CLOTHHIP_EINVAL for n < 0, a NULL table with n > 0 or a NaN. */
+int clothhip_selftest_exp_fixed(const double *x, int64_t n, double *out);
 int clothhip_selftest_arith(int32_t device, int32_t op, const double *a, const double *b, double *out,
                             int64_t n);
 

@@ -16,7 +16,11 @@ does not claim a rate.
 4.3.7): a grouped Adam step of G = 1, 4, 16, 64 networks at B = 256 against G single-network steps timed in the same process. Both
 calls run the same kernels (k_fit_gemm, k_fit_loss, k_fit_reduce, k_fit_colsum, k_fit_adam): the single network is the call
 members = {0}, n_m = 1.
-    python3 tools/fit_bench.py --members [--steps 20] [--rounds 5] [--out FILE]"""
+    python3 tools/fit_bench.py --members [--steps 20] [--rounds 5] [--out FILE]
+--ppo runs the PPO section instead (clothhip_policy_fit_ppo; profiles/ppo.txt): on the four shapes above, an Adam step
+of the clipped surrogate beside the squared-error step timed in the same process on the same handle and rows. The two differ in ONE
+launch per step: k_fit_loss_ppo in the place of k_fit_loss.
+    python3 tools/fit_bench.py --ppo [--steps 20] [--rounds 5] [--out FILE]"""
 import argparse
 import os
 import sys
@@ -120,12 +124,40 @@ def members_section(args, rows, labels):
     group.close()
 
 
+def ppo_section(args, b, rows, labels):
+    """A PPO Adam step beside the squared-error step: the same handle, network, rows and minibatch table, `--rounds` calls of `--steps`
+    steps each after one warm-up call, alternated; Gaussian advantages in the weight column, old means from one snapshot."""
+    r = np.random.RandomState(3)
+    b.fit_append(rows, labels, weights=np.random.RandomState(9).normal(size=len(rows)).astype(np.float32))
+    say("fit_bench ppo: 25x25 (1875 inputs), dataset %d rows, Gaussian advantages, sigma 0.5, clip 0.2; %d Adam steps per call, %d calls of each kind "
+        "alternated after one warm-up call; device ms by HIP events around all steps of a call" % (args.rows, args.steps, args.rounds))
+    for hidden in ([64, 64], [256, 256, 256]):
+        widths = [3 * b.P] + hidden + [4]
+        for B in (256, 4096):
+            table = r.randint(0, args.rows, size=(args.steps, B)).astype(np.int32)
+            b.set_policy_mlp(layers_of(widths))
+            b.fit_snapshot_policy()
+            b.fit(table, lr=1e-5)
+            b.fit_ppo(table, 0.5, 0.2, lr=1e-5)
+            mse, ppo = [], []
+            for _ in range(args.rounds):
+                b.fit(table, lr=1e-5)
+                mse.append(b.last_kernel_ms / args.steps)
+                stats = b.fit_ppo(table, 0.5, 0.2, lr=1e-5)
+                ppo.append(b.last_kernel_ms / args.steps)
+            m, p = float(np.median(mse)), float(np.median(ppo))
+            say("hidden %-15r B %4d: squared error %.3f ms/step (min %.3f, max %.3f) | PPO %.3f ms/step (min %.3f, max %.3f) | PPO - squared error "
+                "%+.3f ms (%+.1f %%); last clip_fraction %.3f, kl %.5f" % (hidden, B, m, min(mse), max(mse), p, min(ppo), max(ppo), p - m,
+                                                                        100.0 * (p - m) / m, stats[-1, 1], stats[-1, 2]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--rows", type=int, default=8192)
     ap.add_argument("--members", action="store_true", help="run the members section (the grouped trainer) instead of the single-network one")
+    ap.add_argument("--ppo", action="store_true", help="run the PPO section (a clipped-surrogate step beside the squared-error step) instead")
     ap.add_argument("--out", default=None, help="also append the printed lines to this file")
     args = ap.parse_args()
     b = ClothBatch(bench.bench_cfg(25, 0.02, "tier1"), n_envs=1, precision="f32")
@@ -135,6 +167,13 @@ def main():
     if args.members:
         b.close()
         members_section(args, rows, labels)
+        if args.out:
+            with open(args.out, "a") as fh:
+                fh.write("\n".join(LINES) + "\n")
+        return
+    if args.ppo:
+        ppo_section(args, b, rows, labels)
+        b.close()
         if args.out:
             with open(args.out, "a") as fh:
                 fh.write("\n".join(LINES) + "\n")

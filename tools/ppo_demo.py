@@ -1,0 +1,181 @@
+#!/usr/bin/env python3
+"""PPO on the device, end to end and small: tools/actor_critic_demo.py's loop with the clipped surrogate in the place of
+the advantage-weighted regression, and MANY policy steps per collection. Per iteration: collect under the present network plus Gaussian
+exploration noise (demos.actor_critic_collect) -> ONE clothhip_fit_data_gae call writes the value targets and the normalised advantages
+-> ONE clothhip_fit_data_snapshot_policy call stores the present means as the rows' old means -> Adam steps of the critic, then
+--epochs epochs of PPO minibatches over the collection (demos.ppo_fit). Beside it, from the same seeds and the same noise, on an env of
+its own, demos.actor_critic_fit with the SAME number of policy steps. It prints, per iteration, the mean return of the episodes that
+completed in both runs, PPO's clip_fraction and kl per epoch, and how far each run's mean has moved from the executed actions; with
+--out FILE it also appends the lines there. profiles/ppo.txt holds a run. The tool claims nothing about learning curves: it says what
+came out. What it is for is the other column: the weighted regression under these many steps runs away, the clipped surrogate does not.
+With --bench it measures instead: clothhip_fit_data_snapshot_policy over the rows of one --envs x --slots collection, kernels and call,
+beside the host route it replaces in the same run (fit_predict with its download, fit_set_old_means with its upload).
+    python3 tools/ppo_demo.py [--envs 64] [--slots 12] [--iters 4] [--epochs 10] [--sigma 0.1] [--clip 0.2] [--target-kl X] [--out FILE]
+    python3 tools/ppo_demo.py --bench [--envs 512] [--slots 12] [--out FILE]"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import bench                                          # noqa: E402
+from gym_cloth_amd.demos import actor_critic_collect, actor_critic_fit, ppo_fit      # noqa: E402
+from gym_cloth_amd.envs import ClothVecEnv            # noqa: E402
+from gym_cloth_amd.policies import MLPPolicy, MLPTrainer, ValueTrainer                # noqa: E402
+
+LINES = []
+
+
+def say(s=""):
+    print(s, flush=True)
+    LINES.append(s)
+
+
+def make_env(E):
+    cfg = bench.bench_cfg(25, 0.02, "tier1")
+    cfg["env"]["force_grab"] = True
+    return ClothVecEnv(cfg, n_envs=E, precision="f32", consume_domrand_draws=False)
+
+
+def make_layers(widths, seed=0):
+    r = np.random.RandomState(seed)
+    return [((r.normal(size=(widths[l + 1], widths[l])) / np.sqrt(widths[l])).astype(np.float32), np.zeros(widths[l + 1], dtype=np.float32))
+            for l in range(len(widths) - 1)]
+
+
+def stats(xs):
+    xs = np.asarray(xs) * 1e3
+    return "%.3f ms (min %.3f, max %.3f)" % (np.median(xs), xs.min(), xs.max())
+
+
+def mean(x):
+    return float(np.mean(x)) if len(x) else float("nan")
+
+
+def moved(trainer, col):
+    """Mean |mean - executed action|^2 over the collection's non-leaf rows at the present weights."""
+    rows = np.asarray(col["nonleaf"])
+    y = trainer.predict(rows).astype(np.float64)
+    a = trainer.env.batch.fit_data(int(col["first"]), int(col["appended"]) + int(col["open_rows"]))[1].astype(np.float64)[rows - int(col["first"])]
+    return float(((y - a) ** 2).sum(axis=1).mean())
+
+
+def run(args):
+    E, T = args.envs, args.slots
+    hidden = [int(w) for w in args.hidden.split(",") if w]
+    envs = [make_env(E), make_env(E)]
+    widths = [3 * envs[0].P] + hidden
+    pol = [MLPTrainer(v, MLPPolicy(v, make_layers(widths + [4])), optimizer="adam", lr=args.lr) for v in envs]
+    critic = [ValueTrainer(v, make_layers(widths + [1], seed=1), optimizer="adam", lr=args.lr) for v in envs]
+    say("ppo demo: %d cloths 25x25 fp32 tier 1 (force_grab), MLP policy and critic hidden %r, %d slots per iteration in one launch, Gaussian "
+        "exploration noise sigma %g; GAE gamma %g lambda %g, normalised advantages; Adam lr %g, %d critic steps, then %d epochs of minibatches "
+        "of %d rows over the collection: PPO (clip %g, target_kl %r) beside actor_critic_fit with as many policy steps, same seeds and noise"
+        % (E, hidden, T, args.sigma, args.gamma, args.lam, args.lr, args.value_steps, args.epochs, args.batch, args.clip, args.target_kl))
+    for i in range(args.iters):
+        noise = np.random.RandomState(100 + i).normal(size=(T, E, 4)) * args.sigma
+        for v in envs:
+            v.seed([2000 + e for e in range(E)])                              # every iteration from the same start states
+            v.reset()
+        try:
+            cols = [actor_critic_collect(v, tr, n_actions=T, policy_noise=noise, slots_per_launch=T) for v, tr in zip(envs, pol)]
+        except ValueError as e:                                               # a network that ran away acts with values that are not finite
+            say("iteration %d: a collection was refused (%s): the run ends here" % (i, e))
+            break
+        before = [moved(tr, c) for tr, c in zip(pol, cols)]
+        t0 = time.perf_counter()
+        fit = ppo_fit(envs[0], pol[0], critic[0], cols[0], sigma=args.sigma, gamma=args.gamma, lam=args.lam, clip=args.clip,
+                      n_value_steps=args.value_steps, n_epochs=args.epochs, batch_size=args.batch, seed=i, target_kl=args.target_kl)
+        dp = time.perf_counter() - t0
+        n_mb = max(1, len(cols[1]["nonleaf"]) // args.batch)
+        t0 = time.perf_counter()
+        with np.errstate(all="ignore"):
+            acf = actor_critic_fit(envs[1], pol[1], critic[1], cols[1], gamma=args.gamma, lam=args.lam, n_value_steps=args.value_steps,
+                                   n_policy_steps=args.epochs * n_mb, batch_size=args.batch, seed=i)
+            after = [moved(tr, c) for tr, c in zip(pol, cols)]
+        da = time.perf_counter() - t0
+        say("iteration %d: PPO %4d rows + %d leaves, %3d completed episodes, mean return %.4f | weighted regression %4d rows + %d leaves, %3d "
+            "completed episodes, mean return %.4f" % (i, cols[0]["appended"], cols[0]["open_rows"], len(cols[0]["episode_return"]),
+                                                      mean(cols[0]["episode_return"]), cols[1]["appended"], cols[1]["open_rows"],
+                                                      len(cols[1]["episode_return"]), mean(cols[1]["episode_return"])))
+        per = fit["ppo_stats"].reshape(fit["epochs"], -1, 3).mean(axis=1) if fit["epochs"] else np.zeros((0, 3))
+        say("    PPO: %d epochs, %d steps, fit %.0f ms; per epoch clip_fraction %s | kl %s | surrogate loss %s" % (
+            fit["epochs"], len(fit["ppo_stats"]), dp * 1e3, " ".join("%.3f" % c for c in per[:, 1]), " ".join("%.4f" % k for k in per[:, 2]),
+            " ".join("%.4f" % l for l in per[:, 0])))
+        say("    mean |mean - executed action|^2 over the collection: PPO %.5f -> %.5f | weighted regression (%d steps, %.0f ms) %.5f -> %.5g, its "
+            "weighted loss %.5g -> %.5g" % (before[0], after[0], len(acf["policy_losses"]), da * 1e3, before[1], after[1], acf["policy_losses"][0],
+                                           acf["policy_losses"][-1]))
+    for v in envs:
+        v.close()
+
+
+def bench_section(args, reps=10):
+    E, T = args.envs, args.slots
+    env = make_env(E)
+    for e in range(E):
+        env.np_randoms[e] = np.random.RandomState(1000 + e)
+    env.reset()
+    tr = MLPTrainer(env, MLPPolicy(env, make_layers([3 * env.P, 64, 64, 4], seed=7)))
+    b = env.batch
+    col = actor_critic_collect(env, tr, n_actions=T, slots_per_launch=T)
+    n = col["appended"] + col["open_rows"]
+    say("snapshot bench: the %d rows (%d of them leaves) of one %d x %d-slot collection (25x25, policy hidden [64, 64]); %d repetitions each, "
+        "medians" % (n, col["open_rows"], E, T, reps))
+    b.fit_snapshot_policy(0, n)                                               # (allocates the scratch)
+    kern, wall = [], []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        b.fit_snapshot_policy(0, n)
+        wall.append(time.perf_counter() - t0)
+        kern.append(b.last_kernel_ms * 1e-3)
+    say("    clothhip_fit_data_snapshot_policy, nothing downloaded: device (the policy's forward + the copies) %s, call %s" % (stats(kern), stats(wall)))
+    dev = b.fit_get_old_means()
+    parts = {"predict": [], "upload": [], "all": []}
+    idx = np.arange(n)
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        y = b.fit_predict(idx)
+        t1 = time.perf_counter()
+        b.fit_set_old_means(y)
+        t2 = time.perf_counter()
+        for k, d in zip(("predict", "upload", "all"), (t1 - t0, t2 - t1, t2 - t0)):
+            parts[k].append(d)
+    say("    the host route: fit_predict with its download %s, fit_set_old_means %s; together %s" % tuple(stats(parts[k]) for k in ("predict", "upload", "all")))
+    say("    both routes leave the same bytes in the old-mean column: %s" % (dev.tobytes() == b.fit_get_old_means().tobytes()))
+    env.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=None)
+    ap.add_argument("--slots", type=int, default=12)
+    ap.add_argument("--iters", type=int, default=4)
+    ap.add_argument("--epochs", type=int, default=10, help="epochs over the collection per iteration; the weighted regression takes as many steps")
+    ap.add_argument("--sigma", type=float, default=0.1, help="standard deviation of the exploration noise: the policy's sigma")
+    ap.add_argument("--clip", type=float, default=0.2)
+    ap.add_argument("--target-kl", type=float, default=None)
+    ap.add_argument("--gamma", type=float, default=0.99)
+    ap.add_argument("--lam", type=float, default=0.95)
+    ap.add_argument("--hidden", default="64,64")
+    ap.add_argument("--value-steps", type=int, default=200)
+    ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--lr", type=float, default=1e-3)
+    ap.add_argument("--bench", action="store_true", help="measure the snapshot on the device against the host route")
+    ap.add_argument("--out", default=None, help="also append the printed lines to this file")
+    args = ap.parse_args()
+    if args.envs is None:
+        args.envs = 512 if args.bench else 64
+    if args.bench:
+        bench_section(args)
+    else:
+        run(args)
+    if args.out:
+        with open(args.out, "a") as fh:
+            fh.write("\n".join(LINES) + "\n")
+
+
+if __name__ == "__main__":
+    main()
