@@ -667,10 +667,7 @@ class ClothBatch(object):
 
     def fit_get_weights(self, first=0, n=None):
         """float32[n]: the loss weights of the stored rows [first, first + n), n=None: to the end (clothhip_fit_data_get_weights)."""
-        first = int(first)
-        n = self.fit_size() - first if n is None else int(n)
-        if first < 0 or n < 0:
-            raise ValueError("first and n must be >= 0 and lie within the dataset")
+        first, n = self._fit_range(first, n)
         w = np.zeros(n, dtype=np.float32)
         check(self._L.clothhip_fit_data_get_weights(self._h, first, n, _lib.fp(w)))
         return w
@@ -706,10 +703,7 @@ class ClothBatch(object):
 
     def fit_data(self, first=0, n=None):
         """(obs float32[n, 3P], labels float32[n, 4]): the stored rows [first, first + n), n=None: to the end (clothhip_fit_data_get)."""
-        first = int(first)
-        n = self.fit_size() - first if n is None else int(n)
-        if first < 0 or n < 0:
-            raise ValueError("first and n must be >= 0 and lie within the dataset")
+        first, n = self._fit_range(first, n)
         obs = np.zeros((n, 3 * self.P), dtype=np.float32)
         lab = np.zeros((n, 4), dtype=np.float32)
         check(self._L.clothhip_fit_data_get(self._h, first, n, _lib.fp(obs), _lib.fp(lab)))
@@ -718,13 +712,8 @@ class ClothBatch(object):
     def fit_loss(self, idx):
         """The MSE of the handle's shared network over the dataset rows idx [n], any n >= 1 (a held-out split by index), forward only
         (clothhip_policy_fit_loss); for n <= FIT_MAX_BATCH it is fit_grad's loss bit for bit."""
-        a = np.asarray(idx)
-        if a.ndim != 1 or a.size < 1 or not np.issubdtype(a.dtype, np.integer):
-            raise ValueError("idx must be a non-empty 1-d integer array")
-        if a.min() < 0 or a.max() > np.iinfo(np.int32).max:
-            raise ValueError("idx must hold row numbers of the dataset")
+        ix = self._fit_rows(idx)
         self._fit_n_params()
-        ix = np.ascontiguousarray(a, dtype=np.int32)
         loss = np.zeros(1, dtype=np.float64)
         check(self._L.clothhip_policy_fit_loss(self._h, _lib.i32p(ix), ix.size, _lib.dp(loss)))
         return float(loss[0])
@@ -734,12 +723,7 @@ class ClothBatch(object):
         (clothhip_policy_fit_predict), or with members (distinct population rows) float32[n_m, n, 4], the same rows under every member
         (clothhip_policy_fit_predict_members). Row r is bit for bit the y fit_grad forms for dataset row idx[r] -- what the loss and its
         gradient are made of, so weights computed from it (residuals, trust regions, an ensemble's disagreement) describe the fit itself."""
-        a = np.asarray(idx)
-        if a.ndim != 1 or a.size < 1 or not np.issubdtype(a.dtype, np.integer):
-            raise ValueError("idx must be a non-empty 1-d integer array")
-        if a.min() < 0 or a.max() > np.iinfo(np.int32).max:
-            raise ValueError("idx must hold row numbers of the dataset")
-        ix = np.ascontiguousarray(a, dtype=np.int32)
+        ix = self._fit_rows(idx)
         if members is None:
             self._fit_n_params()
             y = np.zeros((ix.size, 4), dtype=np.float32)
@@ -759,6 +743,16 @@ class ClothBatch(object):
         n = C.c_int64(0)
         check(self._L.clothhip_fit_data_size(self._h, C.byref(n)))
         return int(n.value)
+
+    @staticmethod
+    def _fit_rows(idx):
+        """Any number >= 1 of dataset rows as int32: a 1-d integer list (fit_loss, fit_predict, value_predict)."""
+        a = np.asarray(idx)
+        if a.ndim != 1 or a.size < 1 or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("idx must be a non-empty 1-d integer array")
+        if a.min() < 0 or a.max() > np.iinfo(np.int32).max:
+            raise ValueError("idx must hold row numbers of the dataset")
+        return np.ascontiguousarray(a, dtype=np.int32)
 
     @staticmethod
     def _fit_idx(idx, ndim):
@@ -975,13 +969,8 @@ class ClothBatch(object):
     def value_predict(self, idx):
         """float32[n]: the value network on the stored rows idx [n], any n >= 1, nothing updated (clothhip_value_predict) -- row r is bit
         for bit the v value_grad forms for dataset row idx[r]."""
-        a = np.asarray(idx)
-        if a.ndim != 1 or a.size < 1 or not np.issubdtype(a.dtype, np.integer):
-            raise ValueError("idx must be a non-empty 1-d integer array")
-        if a.min() < 0 or a.max() > np.iinfo(np.int32).max:
-            raise ValueError("idx must hold row numbers of the dataset")
+        ix = self._fit_rows(idx)
         self._value_n_params()
-        ix = np.ascontiguousarray(a, dtype=np.int32)
         v = np.zeros(ix.size, dtype=np.float32)
         check(self._L.clothhip_value_predict(self._h, _lib.i32p(ix), ix.size, _lib.fp(v)))
         return v

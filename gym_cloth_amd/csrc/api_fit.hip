@@ -1,387 +1,21 @@
-// api_fit.hip -- the supervised trainer of the handle's networks, policy and critic: the device-resident dataset and its columns, the loss and its gradient over a minibatch, the optimizer steps, advantages from the critic's values, the old means and PPO's clipped surrogate.
+// api_fit.hip -- the supervised trainer of the handle's networks, policy and critic, over the dataset of api_fit_data.hip: the loss and its gradient over a minibatch, the optimizer steps, advantages from the critic's values, the snapshot of the old means and PPO's clipped surrogate.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
-#include <cstddef>
 #include <cstdio>
 #include <new>
 #include <vector>
 
 #include "api_handle.hpp"
 #include "cloth_fit_gae.hpp"
-#include "cloth_fit_gather.hpp"
 #include "cloth_policy_fit.hpp"
 #include "cloth_policy_mlp.hpp"
 
 static_assert(FIT_MAX_BATCH == CLOTHHIP_FIT_MAX_BATCH, "the batch cap of the header and of the kernels");
 static_assert(sizeof(ClothFitParams) == 24, "ClothFitParams is six floats");
-static_assert(FIT_SRC_SLOTS == CLOTHHIP_FIT_SRC_SLOTS && FIT_SRC_RESETS == CLOTHHIP_FIT_SRC_RESETS && FIT_SRC_HELD == CLOTHHIP_FIT_SRC_HELD,
-              "the row sources of the header and of the kernel");
 static_assert(GAE_NEXT_NONE == CLOTHHIP_FIT_NEXT_NONE && CLOTHHIP_FIT_NEXT_TERMINAL < 0 && CLOTHHIP_FIT_NEXT_NONE < 0, "the leaf mark of the header and of the kernels");
 static_assert(sizeof(ClothGaeParams) == 24, "ClothGaeParams is two doubles, a float and an int32");
-
-// ---- the dataset (clothhip.h: clothhip_fit_data_*) ------------------------------------------------------------------------------------
-// room for n more rows: grow geometrically into new tables, keep the rows (Buffer::reserve would not), swap them in
-static int grow_dataset(clothhip_handle *h, int64_t n) {
-    auto &f = h->fit;
-    if (f.n + n <= f.cap) return 0;
-    const size_t row = (size_t)3 * h->P;
-    const int64_t cap = std::max<int64_t>(std::max<int64_t>(f.n + n, 2 * f.cap), 64);
-    Buffer<float> obs, lb, w, rew, ret, old;
-    Buffer<int32_t> next;
-    if (int rc = obs.reserve((size_t)cap * row * 4)) return rc;
-    if (int rc = lb.reserve((size_t)cap * 4 * 4)) return rc;
-    if (int rc = w.reserve((size_t)cap * 4)) return rc;
-    if (int rc = rew.reserve((size_t)cap * 4)) return rc;
-    if (int rc = ret.reserve((size_t)cap * 4)) return rc;
-    if (int rc = next.reserve((size_t)cap * 4)) return rc;
-    if (int rc = old.reserve((size_t)cap * 4 * 4)) return rc;
-    if (f.n > 0) {
-        HIPCHECK(hipMemcpyAsync(obs, f.d_obs, (size_t)f.n * row * 4, hipMemcpyDeviceToDevice, h->stream));
-        HIPCHECK(hipMemcpyAsync(lb, f.d_lab, (size_t)f.n * 4 * 4, hipMemcpyDeviceToDevice, h->stream));
-        HIPCHECK(hipMemcpyAsync(w, f.d_w, (size_t)f.n * 4, hipMemcpyDeviceToDevice, h->stream));
-        HIPCHECK(hipMemcpyAsync(rew, f.d_rew, (size_t)f.n * 4, hipMemcpyDeviceToDevice, h->stream));
-        HIPCHECK(hipMemcpyAsync(ret, f.d_ret, (size_t)f.n * 4, hipMemcpyDeviceToDevice, h->stream));
-        HIPCHECK(hipMemcpyAsync(next, f.d_next, (size_t)f.n * 4, hipMemcpyDeviceToDevice, h->stream));
-        HIPCHECK(hipMemcpyAsync(old, f.d_old, (size_t)f.n * 4 * 4, hipMemcpyDeviceToDevice, h->stream));
-        HIPCHECK(hipStreamSynchronize(h->stream));
-    }
-    f.d_obs = std::move(obs); f.d_lab = std::move(lb); f.d_w = std::move(w); f.d_rew = std::move(rew); f.d_ret = std::move(ret); f.d_next = std::move(next);
-    f.d_old = std::move(old);
-    f.cap = cap;
-    return 0;
-}
-
-// The n rows behind the ones that count get the defaults of the transition columns (reward 0, no successor: a leaf, value target 0) and
-// of the old means (zeros, not set), on the device and in the host mirrors of `next` and of the set marks; enqueued, the caller
-// synchronises before the rows count. After grow_dataset.
-static int default_transitions(clothhip_handle *h, int64_t n) {
-    auto &f = h->fit;
-    try {
-        f.h_next.resize((size_t)f.n); f.h_next.resize((size_t)(f.n + n), CLOTHHIP_FIT_NEXT_NONE);
-        f.h_old_set.resize((size_t)f.n); f.h_old_set.resize((size_t)(f.n + n), 0);
-    } catch (const std::bad_alloc &) {
-        return fail(CLOTHHIP_ENOMEM, "out of host memory (%lld rows)", (long long)(f.n + n));
-    }
-    HIPCHECK(hipMemsetAsync(f.d_old + (size_t)f.n * 4, 0, (size_t)n * 4 * 4, h->stream));
-    HIPCHECK(hipMemsetAsync(f.d_rew + (size_t)f.n, 0, (size_t)n * 4, h->stream));
-    HIPCHECK(hipMemsetAsync(f.d_ret + (size_t)f.n, 0, (size_t)n * 4, h->stream));
-    HIPCHECK(hipMemsetD32Async((hipDeviceptr_t)(f.d_next + (size_t)f.n), CLOTHHIP_FIT_NEXT_NONE, (size_t)n, h->stream));
-    return 0;
-}
-
-// a caller's weight table: every value a finite float (NULL: none given, which every entry that takes one allows)
-static int check_weights(const float *w, int64_t n) {
-    if (w)
-        for (int64_t i = 0; i < n; i++)
-            if (!std::isfinite(w[i])) return fail(CLOTHHIP_EINVAL, "weights[%lld] is not finite", (long long)i);
-    return 0;
-}
-
-extern "C" int clothhip_fit_data_append(clothhip_handle *h, const float *obs_rows, const double *labels, int64_t n) {
-    return clothhip_fit_data_append_weighted(h, obs_rows, labels, nullptr, n);
-}
-
-extern "C" int clothhip_fit_data_append_weighted(clothhip_handle *h, const float *obs_rows, const double *labels, const float *weights, int64_t n) {
-    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
-    if (int rc = check_idle(h)) return rc;
-    if (n < 0) return fail(CLOTHHIP_EINVAL, "n < 0");
-    if (n == 0) return 0;
-    if (!obs_rows || !labels) return fail(CLOTHHIP_EINVAL, "NULL argument");
-    auto &f = h->fit;
-    const size_t row = (size_t)3 * h->P;
-    if (f.n + n > INT32_MAX) return fail(CLOTHHIP_EINVAL, "%lld + %lld rows: a minibatch names its rows by int32", (long long)f.n, (long long)n);
-    for (size_t i = 0; i < (size_t)n * row; i++)
-        if (!std::isfinite(obs_rows[i])) return fail(CLOTHHIP_EINVAL, "obs_rows[%zu][%zu] is not finite", i / row, i % row);
-    std::vector<float> lab;
-    try { lab.resize((size_t)n * 4); } catch (const std::bad_alloc &) { return fail(CLOTHHIP_ENOMEM, "out of host memory (%lld labels)", (long long)n); }
-    for (size_t i = 0; i < (size_t)n * 4; i++) {
-        lab[i] = (float)labels[i];
-        if (!std::isfinite(lab[i])) return fail(CLOTHHIP_EINVAL, "labels[%zu][%zu] is not a finite float (a slot that did not run? pass the rows that ran)", i / 4, i % 4);
-    }
-    if (int rc = check_weights(weights, n)) return rc;
-    std::vector<float> ones;
-    if (!weights) {
-        try { ones.assign((size_t)n, 1.0f); } catch (const std::bad_alloc &) { return fail(CLOTHHIP_ENOMEM, "out of host memory (%lld weights)", (long long)n); }
-        weights = ones.data();
-    }
-    HIPCHECK(hipSetDevice(h->device));
-    if (int rc = grow_dataset(h, n)) return rc;
-    if (int rc = default_transitions(h, n)) return rc;
-    HIPCHECK(hipMemcpyAsync(f.d_obs + (size_t)f.n * row, obs_rows, (size_t)n * row * 4, hipMemcpyHostToDevice, h->stream));
-    HIPCHECK(hipMemcpyAsync(f.d_lab + (size_t)f.n * 4, lab.data(), (size_t)n * 4 * 4, hipMemcpyHostToDevice, h->stream));
-    HIPCHECK(hipMemcpyAsync(f.d_w + (size_t)f.n, weights, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
-    HIPCHECK(hipStreamSynchronize(h->stream));      // the host tables are never retained; only now do the rows count
-    f.n += n;
-    return 0;
-}
-
-// the rows [first, first + n) of a call lie within the dataset
-static int check_range(const clothhip_handle *h, int64_t first, int64_t n) {
-    if (first < 0 || n < 0 || first > h->fit.n || n > h->fit.n - first)
-        return fail(CLOTHHIP_EINVAL, "rows [%lld, %lld + %lld) outside the dataset's %lld", (long long)first, (long long)first, (long long)n, (long long)h->fit.n);
-    return 0;
-}
-
-extern "C" int clothhip_fit_data_set_weights(clothhip_handle *h, int64_t first, int64_t n, const float *w) {
-    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
-    if (int rc = check_idle(h)) return rc;
-    if (int rc = check_range(h, first, n)) return rc;
-    if (n == 0) return 0;
-    if (!w) return fail(CLOTHHIP_EINVAL, "NULL argument");
-    if (int rc = check_weights(w, n)) return rc;
-    HIPCHECK(hipSetDevice(h->device));
-    HIPCHECK(hipEventRecord(h->ev0, h->stream));
-    HIPCHECK(hipMemcpyAsync(h->fit.d_w + (size_t)first, w, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
-    HIPCHECK(hipEventRecord(h->ev1, h->stream));
-    h->have_timing = true;
-    HIPCHECK(hipStreamSynchronize(h->stream));      // (the host table is not retained)
-    return 0;
-}
-
-extern "C" int clothhip_fit_data_get_weights(clothhip_handle *h, int64_t first, int64_t n, float *w) {
-    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
-    if (int rc = check_idle(h)) return rc;
-    if (int rc = check_range(h, first, n)) return rc;
-    if (n == 0) return 0;
-    if (!w) return fail(CLOTHHIP_EINVAL, "NULL argument");
-    HIPCHECK(hipSetDevice(h->device));
-    HIPCHECK(hipMemcpyAsync(w, h->fit.d_w + (size_t)first, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHECK(hipStreamSynchronize(h->stream));
-    return 0;
-}
-
-// ---- the episode structure and the value targets (clothhip.h: ACTOR-CRITIC FROM REWARD) ---------------------------------------------------
-extern "C" int clothhip_fit_data_set_transitions(clothhip_handle *h, int64_t first, int64_t n, const float *rew, const int32_t *next) {
-    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
-    if (int rc = check_idle(h)) return rc;
-    if (int rc = check_range(h, first, n)) return rc;
-    if (n == 0) return 0;
-    if (!rew || !next) return fail(CLOTHHIP_EINVAL, "NULL argument");
-    auto &f = h->fit;
-    for (int64_t i = 0; i < n; i++) {
-        if (!std::isfinite(rew[i])) return fail(CLOTHHIP_EINVAL, "rew[%lld] is not finite", (long long)i);
-        const int64_t nx = next[i];
-        if (nx != CLOTHHIP_FIT_NEXT_TERMINAL && nx != CLOTHHIP_FIT_NEXT_NONE && (nx <= first + i || nx >= f.n))
-            return fail(CLOTHHIP_EINVAL, "next[%lld] = %lld: a successor lies behind its row %lld and inside the dataset's %lld (or CLOTHHIP_FIT_NEXT_TERMINAL, CLOTHHIP_FIT_NEXT_NONE)",
-                        (long long)i, (long long)nx, (long long)(first + i), (long long)f.n);
-    }
-    HIPCHECK(hipSetDevice(h->device));
-    HIPCHECK(hipMemcpyAsync(f.d_rew + (size_t)first, rew, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
-    HIPCHECK(hipMemcpyAsync(f.d_next + (size_t)first, next, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
-    HIPCHECK(hipStreamSynchronize(h->stream));      // (the host tables are not retained)
-    std::copy(next, next + n, f.h_next.begin() + first);
-    return 0;
-}
-
-extern "C" int clothhip_fit_data_get_transitions(clothhip_handle *h, int64_t first, int64_t n, float *rew, int32_t *next) {
-    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
-    if (int rc = check_idle(h)) return rc;
-    if (int rc = check_range(h, first, n)) return rc;
-    if (n == 0) return 0;
-    if (!rew || !next) return fail(CLOTHHIP_EINVAL, "NULL argument");
-    HIPCHECK(hipSetDevice(h->device));
-    HIPCHECK(hipMemcpyAsync(rew, h->fit.d_rew + (size_t)first, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHECK(hipMemcpyAsync(next, h->fit.d_next + (size_t)first, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHECK(hipStreamSynchronize(h->stream));
-    return 0;
-}
-
-extern "C" int clothhip_fit_data_set_returns(clothhip_handle *h, int64_t first, int64_t n, const float *ret) {
-    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
-    if (int rc = check_idle(h)) return rc;
-    if (int rc = check_range(h, first, n)) return rc;
-    if (n == 0) return 0;
-    if (!ret) return fail(CLOTHHIP_EINVAL, "NULL argument");
-    for (int64_t i = 0; i < n; i++)
-        if (!std::isfinite(ret[i])) return fail(CLOTHHIP_EINVAL, "ret[%lld] is not finite", (long long)i);
-    HIPCHECK(hipSetDevice(h->device));
-    HIPCHECK(hipMemcpyAsync(h->fit.d_ret + (size_t)first, ret, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
-    HIPCHECK(hipStreamSynchronize(h->stream));      // (the host table is not retained)
-    return 0;
-}
-
-extern "C" int clothhip_fit_data_get_returns(clothhip_handle *h, int64_t first, int64_t n, float *ret) {
-    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
-    if (int rc = check_idle(h)) return rc;
-    if (int rc = check_range(h, first, n)) return rc;
-    if (n == 0) return 0;
-    if (!ret) return fail(CLOTHHIP_EINVAL, "NULL argument");
-    HIPCHECK(hipSetDevice(h->device));
-    HIPCHECK(hipMemcpyAsync(ret, h->fit.d_ret + (size_t)first, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHECK(hipStreamSynchronize(h->stream));
-    return 0;
-}
-
-extern "C" int clothhip_fit_data_clear(clothhip_handle *h) {
-    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
-    if (int rc = check_idle(h)) return rc;
-    h->fit.n = 0;
-    h->fit.h_next.clear();
-    h->fit.h_old_set.clear();
-    return 0;
-}
-
-extern "C" int clothhip_fit_data_size(clothhip_handle *h, int64_t *n) {
-    if (!h || !n) return fail(CLOTHHIP_EINVAL, "NULL argument");
-    *n = h->fit.n;
-    return 0;
-}
-
-extern "C" int clothhip_fit_data_get(clothhip_handle *h, int64_t first, int64_t n, float *obs, float *labels) {
-    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
-    if (int rc = check_idle(h)) return rc;
-    if (int rc = check_range(h, first, n)) return rc;
-    if (n == 0 || (!obs && !labels)) return 0;
-    const size_t row = (size_t)3 * h->P;
-    HIPCHECK(hipSetDevice(h->device));
-    if (obs) HIPCHECK(hipMemcpyAsync(obs, h->fit.d_obs + (size_t)first * row, (size_t)n * row * 4, hipMemcpyDeviceToHost, h->stream));
-    if (labels) HIPCHECK(hipMemcpyAsync(labels, h->fit.d_lab + (size_t)first * 4, (size_t)n * 4 * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHECK(hipStreamSynchronize(h->stream));
-    return 0;
-}
-
-// ---- rows named by where they lie on the device (cloth_fit_gather.hpp) ------------------------------------------------------------------
-// One (source, row) of a caller's table against what the handle holds now; the launch tables are valid under launch_table's rule.
-static int check_source(const clothhip_handle *h, int64_t i, int32_t src, int32_t row) {
-    int64_t rows = 0;
-    switch (src) {
-    case CLOTHHIP_FIT_SRC_SLOTS:
-        if (int rc = launch_table(h, LaunchTable::obs, nullptr, &rows)) return rc;
-        break;
-    case CLOTHHIP_FIT_SRC_RESETS:
-        if (int rc = launch_table(h, LaunchTable::reset_obs, nullptr, &rows)) return rc;
-        break;
-    case CLOTHHIP_FIT_SRC_HELD:
-        if (!h->fit.held_valid) return fail(CLOTHHIP_ESTATE, "no held rows on this handle: call clothhip_fit_hold first");
-        rows = h->E;
-        break;
-    default:
-        return fail(CLOTHHIP_EINVAL, "entry %lld: unknown row source %d", (long long)i, src);
-    }
-    if (row < 0 || row >= rows) return fail(CLOTHHIP_EINVAL, "entry %lld: row %d outside [0, %lld) of source %d", (long long)i, row, (long long)rows, src);
-    return 0;
-}
-
-// upload n index entries [n][4] and run k_fit_gather over them; *bad: the kernel met a value that is not finite. label_src < 0: no
-// entry names a label and no weight is written (the held rows), else CLOTHHIP_FIT_LABEL_* and dst_w gets `weights` [n] (host; NULL:
-// ones). Synchronous.
-static int run_gather(clothhip_handle *h, const std::vector<int32_t> &tab, int64_t n, float *dst_obs, float *dst_lab, float *dst_w, int32_t label_src,
-                      const float *weights, bool *bad) {
-    auto &f = h->fit;
-    if (int rc = f.d_rows.reserve((size_t)n * 16)) return rc;
-    if (int rc = f.d_flag.reserve(4)) return rc;
-    if (weights) {
-        if (int rc = f.d_wtab.reserve((size_t)n * 4)) return rc;
-        HIPCHECK(hipMemcpyAsync(f.d_wtab, weights, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
-    }
-    HIPCHECK(hipMemcpyAsync(f.d_rows, tab.data(), (size_t)n * 16, hipMemcpyHostToDevice, h->stream));
-    HIPCHECK(hipMemsetAsync(f.d_flag, 0, 4, h->stream));
-    FitGatherArgs a = {};
-    a.table[FIT_SRC_SLOTS] = (const float *)h->epi.d_fobs; a.table[FIT_SRC_RESETS] = (const float *)h->epi.d_frobs; a.table[FIT_SRC_HELD] = f.d_held;
-    a.rows = f.d_rows;
-    a.labels = label_src == CLOTHHIP_FIT_LABEL_EXPERT ? (const double *)h->epi.d_flab : nullptr;
-    a.records = label_src == CLOTHHIP_FIT_LABEL_ACTION ? (const unsigned char *)(const void *)h->epi.d_frec : nullptr;
-    a.weights = weights ? (const float *)f.d_wtab : nullptr;
-    a.dst_obs = dst_obs; a.dst_lab = dst_lab; a.dst_w = dst_w; a.flag = f.d_flag; a.n = n; a.L = 3 * h->P;
-    HIPCHECK(hipEventRecord(h->ev0, h->stream));
-    hipLaunchKernelGGL(k_fit_gather, dim3((unsigned)std::min<int64_t>(n, 1 << 20)), dim3(FIT_GATHER_THREADS), 0, h->stream, a);
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipEventRecord(h->ev1, h->stream));
-    h->have_timing = true;
-    int32_t flag = 0;
-    HIPCHECK(hipMemcpyAsync(&flag, f.d_flag, 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHECK(hipStreamSynchronize(h->stream));
-    *bad = flag != 0;
-    return 0;
-}
-
-// The refusal of an append whose kernel raised the flag, with clothhip_fit_data_append's message: what the kernel wrote behind the rows
-// that count is read back and searched in that entry's order (observations first, then the rounded labels).
-static int bad_value(clothhip_handle *h, int64_t n) {
-    auto &f = h->fit;
-    const size_t row = (size_t)3 * h->P;
-    std::vector<float> buf;
-    try { buf.resize((size_t)n * std::max<size_t>(row, 4)); } catch (const std::bad_alloc &) { return fail(CLOTHHIP_EINVAL, "an observation or a label is not a finite float"); }
-    HIPCHECK(hipMemcpy(buf.data(), f.d_obs + (size_t)f.n * row, (size_t)n * row * 4, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < (size_t)n * row; i++)
-        if (!std::isfinite(buf[i])) return fail(CLOTHHIP_EINVAL, "obs_rows[%zu][%zu] is not finite", i / row, i % row);
-    HIPCHECK(hipMemcpy(buf.data(), f.d_lab + (size_t)f.n * 4, (size_t)n * 4 * 4, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < (size_t)n * 4; i++)
-        if (!std::isfinite(buf[i])) return fail(CLOTHHIP_EINVAL, "labels[%zu][%zu] is not a finite float (a slot that did not run? pass the rows that ran)", i / 4, i % 4);
-    return fail(CLOTHHIP_EINVAL, "an observation or a label is not a finite float");
-}
-
-extern "C" int clothhip_fit_hold(clothhip_handle *h, const int32_t *src) {
-    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
-    if (int rc = check_idle(h)) return rc;
-    auto &f = h->fit;
-    const size_t row = (size_t)3 * h->P;
-    std::vector<int32_t> tab;
-    if (src) {
-        for (int e = 0; e < h->E; e++) {
-            const int32_t s = src[2 * e], r = src[2 * e + 1];
-            if (int rc = check_source(h, e, s, r)) return rc;
-            if (s == CLOTHHIP_FIT_SRC_HELD) {     // only its own row, which stays: another env's may be overwritten by this very call
-                if (r != e) return fail(CLOTHHIP_EINVAL, "entry %d: a held row can only be kept (row %d), not moved to another env", e, r);
-                continue;
-            }
-            try { tab.insert(tab.end(), {s, r, -1, (int32_t)e}); } catch (const std::bad_alloc &) { return fail(CLOTHHIP_ENOMEM, "out of host memory"); }
-        }
-    }
-    HIPCHECK(hipSetDevice(h->device));
-    if (int rc = f.d_held.reserve((size_t)h->E * row * 4)) return rc;      // (no earlier contents to keep: a table named HELD rows only if it existed)
-    if (!src) {
-        if (int rc = clothhip_write_obs_f32_device(h, f.d_held)) return rc;
-        HIPCHECK(hipStreamSynchronize(h->stream));
-    } else if (!tab.empty()) {
-        bool bad = false;      // (a held row is not checked here: clothhip_fit_data_append_launch checks what it appends)
-        if (int rc = run_gather(h, tab, (int64_t)tab.size() / 4, f.d_held, nullptr, nullptr, -1, nullptr, &bad)) return rc;
-    }
-    f.held_valid = true;
-    return 0;
-}
-
-extern "C" int clothhip_fit_data_append_launch(clothhip_handle *h, const int32_t *rows, int64_t n) {
-    return clothhip_fit_data_append_launch_ex(h, rows, n, CLOTHHIP_FIT_LABEL_EXPERT, nullptr);
-}
-
-static_assert(sizeof(ClothStepRecord) == FIT_REC_BYTES && offsetof(ClothStepRecord, action) == 0 && offsetof(ClothStepRecord, ran) == FIT_REC_RAN,
-              "the record's layout as k_fit_gather reads it");
-
-extern "C" int clothhip_fit_data_append_launch_ex(clothhip_handle *h, const int32_t *rows, int64_t n, int32_t label_src, const float *weights) {
-    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
-    if (int rc = check_idle(h)) return rc;
-    if (label_src != CLOTHHIP_FIT_LABEL_EXPERT && label_src != CLOTHHIP_FIT_LABEL_ACTION && label_src != CLOTHHIP_FIT_LABEL_ZERO)
-        return fail(CLOTHHIP_EINVAL, "unknown label source %d (CLOTHHIP_FIT_LABEL_EXPERT, CLOTHHIP_FIT_LABEL_ACTION or CLOTHHIP_FIT_LABEL_ZERO)", label_src);
-    const bool zero = label_src == CLOTHHIP_FIT_LABEL_ZERO;      // no label table is read: label_row is ignored (the kernel is told row 0 of no table)
-    if (n < 0) return fail(CLOTHHIP_EINVAL, "n < 0");
-    if (n == 0) return 0;
-    if (!rows) return fail(CLOTHHIP_EINVAL, "NULL argument");
-    auto &f = h->fit;
-    if (f.n + n > INT32_MAX) return fail(CLOTHHIP_EINVAL, "%lld + %lld rows: a minibatch names its rows by int32", (long long)f.n, (long long)n);
-    int64_t n_lab = 0;
-    if (!zero) if (int rc = launch_table(h, label_src == CLOTHHIP_FIT_LABEL_ACTION ? LaunchTable::records : LaunchTable::labels, nullptr, &n_lab)) return rc;
-    if (int rc = check_weights(weights, n)) return rc;
-    std::vector<int32_t> tab;
-    try { tab.resize((size_t)n * 4); } catch (const std::bad_alloc &) { return fail(CLOTHHIP_ENOMEM, "out of host memory (%lld rows)", (long long)n); }
-    for (int64_t i = 0; i < n; i++) {
-        const int32_t s = rows[3 * i], r = rows[3 * i + 1], l = rows[3 * i + 2];
-        if (int rc = check_source(h, i, s, r)) return rc;
-        if (!zero && (l < 0 || l >= n_lab)) return fail(CLOTHHIP_EINVAL, "entry %lld: label row %d outside [0, %lld)", (long long)i, l, (long long)n_lab);
-        tab[4 * i] = s; tab[4 * i + 1] = r; tab[4 * i + 2] = zero ? 0 : l; tab[4 * i + 3] = (int32_t)(f.n + i);
-    }
-    HIPCHECK(hipSetDevice(h->device));
-    if (int rc = grow_dataset(h, n)) return rc;
-    if (int rc = default_transitions(h, n)) return rc;
-    // the kernel writes behind the n rows that count; they count only if every value it wrote is finite
-    bool bad = false;
-    if (int rc = run_gather(h, tab, n, f.d_obs, f.d_lab, f.d_w, label_src, weights, &bad)) return rc;
-    if (bad) return bad_value(h, n);
-    f.n += n;
-    return 0;
-}
 
 // ---- the trainer (cloth_policy_fit.hpp has the definition and the order) ----------------------------------------------------------------
 // ONE path: a call fits n_m rows of the handle's weight table in the launches of one network. The table is the population d_pop
@@ -398,21 +32,15 @@ struct FitNet {
     float *theta;                       // the table, [max(pop_rows, 1)][D.stride]
     size_t n_params;
     int64_t pop_rows;                   // 0: a table of one row at offset 0
-    Buffer<float> &d_m, &d_v;           // its optimizer: the moments, per row the step count and the read-as-zeros flag
-    std::vector<int64_t> &row_t;
-    std::vector<uint8_t> &row_zero;
+    OptState &opt;                      // its optimizer
     bool value;                         // output width 1, fitted unweighted to the column of value targets; else width 4, to the labels under the weights
     int out() const { return value ? 1 : MLP_OUT; }
     size_t rows() const { return pop_rows ? (size_t)pop_rows : 1; }
 };
 static FitNet policy_net(clothhip_handle *h) {
-    auto &f = h->fit;
-    return {h->pol.mlp, h->pol.pop_rows ? h->pol.d_pop : h->pol.d_mlp, h->pol.mlp_n_params, h->pol.pop_rows, f.d_m, f.d_v, f.row_t, f.row_zero, false};
+    return {h->pol.mlp, h->pol.pop_rows ? h->pol.d_pop : h->pol.d_mlp, h->pol.mlp_n_params, h->pol.pop_rows, h->fit.opt_policy, false};
 }
-static FitNet value_net(clothhip_handle *h) {
-    auto &f = h->fit;
-    return {h->val.mlp, h->val.d_mlp, h->val.n_params, 0, f.d_val_m, f.d_val_v, f.val_t, f.val_zero, true};
-}
+static FitNet value_net(clothhip_handle *h) { return {h->val.mlp, h->val.d_mlp, h->val.n_params, 0, h->fit.opt_value, true}; }
 
 // What the entries refuse before anything is touched, each in the order it always had. The state; `population`: the entry trains rows of
 // a population (which puts these refusals first, whatever else is wrong with the call), else the shared network
@@ -425,14 +53,14 @@ static int check_fit_state(const clothhip_handle *h, bool population) {
         if (h->pol.pop_rows) return fail(CLOTHHIP_ESTATE, "this handle holds a population of networks: the fit trains the ONE shared network of clothhip_set_policy_mlp");
         if (h->pol.mlp.n_layers < 1) return fail(CLOTHHIP_ESTATE, "no network on this handle: call clothhip_set_policy_mlp first");
     }
-    if (h->fit.n < 1) return fail(CLOTHHIP_ESTATE, "the dataset is empty: call clothhip_fit_data_append first");
+    if (h->dataset.n < 1) return fail(CLOTHHIP_ESTATE, "the dataset is empty: call clothhip_fit_data_append first");
     return 0;
 }
 // ... and of the entries that train or evaluate the value network (a population is no obstacle: the critic is not the policy)
 static int check_value_state(const clothhip_handle *h) {
     if (int rc = check_idle(h)) return rc;
     if (h->val.mlp.n_layers < 1) return fail(CLOTHHIP_ESTATE, "no value network on this handle: call clothhip_set_value_mlp first");
-    if (h->fit.n < 1) return fail(CLOTHHIP_ESTATE, "the dataset is empty: call clothhip_fit_data_append first");
+    if (h->dataset.n < 1) return fail(CLOTHHIP_ESTATE, "the dataset is empty: call clothhip_fit_data_append first");
     return 0;
 }
 // the member list of a call ...
@@ -456,7 +84,7 @@ static int check_fit_rows(const clothhip_handle *h, int32_t n_m, const int32_t *
         return fail(CLOTHHIP_EINVAL, "n_m * B = %d * %d rows in one call, at most %d", n_m, B, CLOTHHIP_FIT_MAX_MEMBER_ROWS);
     if (!idx && n_idx > 0) return fail(CLOTHHIP_EINVAL, "idx is NULL");
     for (int64_t i = 0; i < n_idx; i++)
-        if (idx[i] < 0 || idx[i] >= h->fit.n) return fail(CLOTHHIP_EINVAL, "idx[%lld] = %d outside [0, %lld)", (long long)i, idx[i], (long long)h->fit.n);
+        if (idx[i] < 0 || idx[i] >= h->dataset.n) return fail(CLOTHHIP_EINVAL, "idx[%lld] = %d outside [0, %lld)", (long long)i, idx[i], (long long)h->dataset.n);
     return 0;
 }
 // ... and the optimizer of member j (j < 0: the one of the shared network, named without an index)
@@ -524,13 +152,14 @@ static int enqueue_grad(clothhip_handle *h, const FitNet &net, const FitPlan &p,
     const MlpDesc &D = net.D;
     const int L = D.n_layers;
     auto &f = h->fit;
+    const auto &d = h->dataset;
     float *act = f.d_act, *grad = f.d_grad, *dz[2] = {f.d_dz, f.d_dz + (size_t)B * p.maxw};
     FitGemmArgs m0 = {};
     m0.members = f.d_members; m0.stride = D.stride; m0.rows_step = shared_rows ? 0 : B;
     for (int l = 0; l < L; l++) {
         const int n_in = D.widths[l], n_out = D.widths[l + 1];
         FitGemmArgs a = m0;
-        a.A = l ? act + p.h_off[l - 1] : (const float *)f.d_obs; a.lda = n_in; a.rows = l ? nullptr : d_idx; a.a_step = l ? (int64_t)p.act : 0;
+        a.A = l ? act + p.h_off[l - 1] : (const float *)d.obs(); a.lda = n_in; a.rows = l ? nullptr : d_idx; a.a_step = l ? (int64_t)p.act : 0;
         a.B = D.params + p.w_off[l]; a.ldb = n_in; a.bias = a.B + (size_t)n_out * n_in; a.b_weights = 1;
         a.C = act + p.h_off[l]; a.ldc = n_out; a.c_step = (int64_t)p.act;
         a.M = B; a.N = n_out; a.K = n_in; a.k_chunk = n_in;
@@ -543,15 +172,15 @@ static int enqueue_grad(clothhip_handle *h, const FitNet &net, const FitPlan &p,
     if (!d_loss) return 0;
     if (ppo) {
         FitPpoArgs q = {};
-        q.y = act + p.h_off[L - 1]; q.lab = f.d_lab; q.old = f.d_old; q.wgt = f.d_w; q.rows = d_idx; q.dz = dz[(L - 1) & 1]; q.ratio = d_ratio; q.stats = d_loss;
+        q.y = act + p.h_off[L - 1]; q.lab = d.lab(); q.old = d.old(); q.wgt = d.w(); q.rows = d_idx; q.dz = dz[(L - 1) & 1]; q.ratio = d_ratio; q.stats = d_loss;
         q.inv_s2 = ppo->inv_s2; q.half_inv_s2 = ppo->half_inv_s2; q.lo = ppo->lo; q.hi = ppo->hi;
         q.y_step = (int64_t)p.act; q.dz_step = (int64_t)p.dz; q.rows_step = (int64_t)B; q.B = B;
         hipLaunchKernelGGL(k_fit_loss_ppo, dim3((unsigned)n_m), dim3(256), 0, h->stream, q);
     } else if (net.value)
-        hipLaunchKernelGGL(k_fit_loss<1>, dim3((unsigned)n_m), dim3(256), 0, h->stream, (const float *)(act + p.h_off[L - 1]), (const float *)f.d_ret, (const float *)nullptr,
+        hipLaunchKernelGGL(k_fit_loss<1>, dim3((unsigned)n_m), dim3(256), 0, h->stream, (const float *)(act + p.h_off[L - 1]), (const float *)d.ret(), (const float *)nullptr,
                            d_idx, B, dz[(L - 1) & 1], d_loss, (int64_t)p.act, (int64_t)p.dz, (int64_t)B);
     else
-        hipLaunchKernelGGL(k_fit_loss<4>, dim3((unsigned)n_m), dim3(256), 0, h->stream, (const float *)(act + p.h_off[L - 1]), (const float *)f.d_lab, (const float *)f.d_w,
+        hipLaunchKernelGGL(k_fit_loss<4>, dim3((unsigned)n_m), dim3(256), 0, h->stream, (const float *)(act + p.h_off[L - 1]), (const float *)d.lab(), (const float *)d.w(),
                            d_idx, B, dz[(L - 1) & 1], d_loss, (int64_t)p.act, (int64_t)p.dz, (int64_t)B);
     HIPCHECK(hipGetLastError());
     for (int l = L - 1; l >= 0; l--) {
@@ -560,7 +189,7 @@ static int enqueue_grad(clothhip_handle *h, const FitNet &net, const FitPlan &p,
         float *gWl = grad + p.w_off[l];
         FitGemmArgs a = m0;
         a.A = dzl; a.lda = n_out; a.a_step = (int64_t)p.dz;
-        a.B = l ? act + p.h_off[l - 1] : (const float *)f.d_obs; a.ldb = n_in; a.rows = l ? nullptr : d_idx; a.b_step = l ? (int64_t)p.act : 0;
+        a.B = l ? act + p.h_off[l - 1] : (const float *)d.obs(); a.ldb = n_in; a.rows = l ? nullptr : d_idx; a.b_step = l ? (int64_t)p.act : 0;
         a.C = p.n_split > 1 ? (float *)f.d_part : gWl; a.ldc = n_in; a.c_slab = (int64_t)n_out * n_in; a.c_step = (int64_t)(p.n_split > 1 ? p.part : p.grad);
         a.M = n_out; a.N = n_in; a.K = B; a.k_chunk = FIT_SPLIT_ROWS;
         if (l == 0) launch_gemm<false, false, FIT_EPI_NONE, true>(h->stream, a, n_m);
@@ -660,8 +289,7 @@ extern "C" int clothhip_policy_fit_loss(clothhip_handle *h, const int32_t *idx, 
         const FitPlan p = fit_plan(net, B);
         const int32_t *d_idx = f.d_idx + (size_t)c * FIT_MAX_BATCH;
         if (int rc = enqueue_grad(h, net, p, 1, d_idx, B, nullptr)) return rc;
-        hipLaunchKernelGGL(k_fit_sqsum, dim3(1), dim3(256), 0, h->stream, (const float *)(f.d_act + p.h_off[L - 1]), (const float *)f.d_lab, (const float *)f.d_w, d_idx, B,
-                           f.d_loss + c);
+        launch_fit_sqsum(h->stream, f.d_act + p.h_off[L - 1], h->dataset.lab(), h->dataset.w(), d_idx, B, f.d_loss + c);
         HIPCHECK(hipGetLastError());
     }
     HIPCHECK(hipEventRecord(h->ev1, h->stream));
@@ -696,8 +324,7 @@ static int enqueue_predict(clothhip_handle *h, const FitNet &net, const int32_t 
         const FitPlan p = fit_plan(net, B);
         if (int rc = enqueue_grad(h, net, p, n_m, f.d_idx + (size_t)r0, B, nullptr, true)) return rc;
         const int32_t blocks = (W * B + 255) / 256;
-        hipLaunchKernelGGL(k_fit_copy_y, dim3((unsigned)blocks * (unsigned)n_m), dim3(256), 0, h->stream, (const float *)(f.d_act + p.h_off[L - 1]), W * B,
-                           dst + (size_t)r0 * W, (int64_t)p.act, (int64_t)n * W, blocks);
+        launch_fit_copy_y(h->stream, n_m, f.d_act + p.h_off[L - 1], W * B, dst + (size_t)r0 * W, (int64_t)p.act, (int64_t)n * W, blocks);
         HIPCHECK(hipGetLastError());
     }
     HIPCHECK(hipEventRecord(h->ev1, h->stream));
@@ -736,9 +363,10 @@ extern "C" int clothhip_policy_fit_predict_members(clothhip_handle *h, const int
 // the per-row optimizer state exists from the first step after a new network: every row fresh
 static int ensure_row_state(const FitNet &net) {
     const size_t rows = net.rows();
-    if (net.row_t.size() == rows && net.row_zero.size() == rows) return 0;
-    try { net.row_t.assign(rows, 0); net.row_zero.assign(rows, 1); } catch (const std::bad_alloc &) {
-        net.row_t.clear(); net.row_zero.clear();
+    OptState &o = net.opt;
+    if (o.t.size() == rows && o.zero.size() == rows) return 0;
+    try { o.t.assign(rows, 0); o.zero.assign(rows, 1); } catch (const std::bad_alloc &) {
+        o.forget();
         return fail(CLOTHHIP_ENOMEM, "out of host memory (%zu rows)", rows);
     }
     return 0;
@@ -764,7 +392,7 @@ static int run_fit(clothhip_handle *h, const FitNet &net, const ClothFitParams *
             float *q = hyper.data() + ((size_t)s * n_m + j) * FIT_HYPER;
             const ClothFitParams &pj = p[j];
             if (adam) {
-                const double b1 = (double)pj.beta1, b2 = (double)pj.beta2, t = (double)(net.row_t[members[j]] + s + 1);
+                const double b1 = (double)pj.beta1, b2 = (double)pj.beta2, t = (double)(net.opt.t[members[j]] + s + 1);
                 const double a_t = (double)pj.lr * std::sqrt(1.0 - std::pow(b2, t)) / (1.0 - std::pow(b1, t));
                 q[0] = (float)a_t; q[1] = pj.beta1; q[2] = (float)(1.0 - b1); q[3] = pj.beta2; q[4] = (float)(1.0 - b2); q[5] = pj.eps;
             } else {
@@ -777,24 +405,24 @@ static int run_fit(clothhip_handle *h, const FitNet &net, const ClothFitParams *
     if (int rc = f.d_loss.reserve(n_sm * per_loss * 8)) return rc;
     if (int rc = f.d_hyper.reserve(n_sm * FIT_HYPER * 4)) return rc;
     // the moments of the whole table. A table of another network's size holds no row's state (every row is flagged read-as-zeros by
-    // fit_forget when the network changes), so growing it loses nothing
-    if (int rc = net.d_m.reserve(n_moments * 4)) return rc;
-    if (int rc = net.d_v.reserve(n_moments * 4)) return rc;
+    // OptState::forget when the network changes), so growing it loses nothing
+    if (int rc = net.opt.m.reserve(n_moments * 4)) return rc;
+    if (int rc = net.opt.v.reserve(n_moments * 4)) return rc;
     // from here on the call goes through (but for a failure of the runtime itself)
     for (int32_t j = 0; j < n_m; j++) {
         const int32_t g = members[j];
-        if (net.row_zero[g]) {
-            HIPCHECK(hipMemsetAsync(net.d_m + (size_t)g * stride, 0, n * 4, h->stream));
-            HIPCHECK(hipMemsetAsync(net.d_v + (size_t)g * stride, 0, n * 4, h->stream));
-            net.row_zero[g] = 0;
+        if (net.opt.zero[g]) {
+            HIPCHECK(hipMemsetAsync(net.opt.m + (size_t)g * stride, 0, n * 4, h->stream));
+            HIPCHECK(hipMemsetAsync(net.opt.v + (size_t)g * stride, 0, n * 4, h->stream));
+            net.opt.zero[g] = 0;
         }
-        net.row_t[g] += n_steps;
+        net.opt.t[g] += n_steps;
     }
     HIPCHECK(hipMemcpyAsync(f.d_members, members, (size_t)n_m * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipMemcpyAsync(f.d_idx, idx, n_sm * B * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipMemcpyAsync(f.d_hyper, hyper.data(), n_sm * FIT_HYPER * 4, hipMemcpyHostToDevice, h->stream));
     FitOptArgs o = {};
-    o.theta = net.theta; o.m = net.d_m; o.v = net.d_v; o.g = f.d_grad; o.members = f.d_members;
+    o.theta = net.theta; o.m = net.opt.m; o.v = net.opt.v; o.g = f.d_grad; o.members = f.d_members;
     o.stride = (int64_t)stride; o.n = (int64_t)n; o.blocks = (int32_t)((n + 255) / 256);
     const dim3 ogrid((unsigned)o.blocks * (unsigned)n_m);
     HIPCHECK(hipEventRecord(h->ev0, h->stream));
@@ -842,7 +470,7 @@ extern "C" int clothhip_policy_fit_members(clothhip_handle *h, const ClothFitPar
 extern "C" int clothhip_policy_fit_reset(clothhip_handle *h) {
     if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
     if (int rc = check_idle(h)) return rc;
-    h->fit_forget();
+    h->fit.opt_policy.forget();
     return 0;
 }
 
@@ -851,10 +479,10 @@ extern "C" int clothhip_policy_fit_reset_members(clothhip_handle *h, const int32
     if (int rc = check_idle(h)) return rc;
     if (h->pol.mlp.n_layers < 1) return fail(CLOTHHIP_ESTATE, "no network on this handle: call clothhip_set_policy_population first");
     if (!h->pol.pop_rows) return fail(CLOTHHIP_ESTATE, "this handle holds ONE shared network, not a population: use clothhip_policy_fit_reset");
-    if (!members) { h->fit_forget(); return 0; }      // all rows
+    if (!members) { h->fit.opt_policy.forget(); return 0; }      // all rows
     if (int rc = check_fit_members(h, members, n_m)) return rc;
-    if (h->fit.row_t.empty()) return 0;               // every row is fresh already
-    for (int32_t j = 0; j < n_m; j++) { h->fit.row_t[members[j]] = 0; h->fit.row_zero[members[j]] = 1; }
+    if (h->fit.opt_policy.t.empty()) return 0;               // every row is fresh already
+    for (int32_t j = 0; j < n_m; j++) { h->fit.opt_policy.t[members[j]] = 0; h->fit.opt_policy.zero[members[j]] = 1; }
     return 0;
 }
 
@@ -867,42 +495,13 @@ extern "C" int clothhip_fit_data_snapshot_policy(clothhip_handle *h, int64_t fir
     if (int rc = check_fit_state(h, false)) return rc;
     if (int rc = check_range(h, first, n)) return rc;
     if (n == 0) return 0;
-    auto &f = h->fit;
     std::vector<int32_t> idx;
     try { idx.resize((size_t)n); } catch (const std::bad_alloc &) { return fail(CLOTHHIP_ENOMEM, "out of host memory (%lld rows)", (long long)n); }
     for (int64_t i = 0; i < n; i++) idx[(size_t)i] = (int32_t)(first + i);
     // the launches of clothhip_policy_fit_predict; each chunk's y goes to its rows of the column, which are consecutive
-    if (int rc = enqueue_predict(h, policy_net(h), SHARED_ROW, 1, idx.data(), n, f.d_old + (size_t)first * 4)) return rc;
+    if (int rc = enqueue_predict(h, policy_net(h), SHARED_ROW, 1, idx.data(), n, h->dataset.old() + (size_t)first * 4)) return rc;
     HIPCHECK(hipStreamSynchronize(h->stream));      // (idx, a host table the upload read, goes out of scope)
-    std::fill(f.h_old_set.begin() + first, f.h_old_set.begin() + first + n, (uint8_t)1);
-    return 0;
-}
-
-extern "C" int clothhip_fit_data_set_old_means(clothhip_handle *h, int64_t first, int64_t n, const float *mu) {
-    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
-    if (int rc = check_idle(h)) return rc;
-    if (int rc = check_range(h, first, n)) return rc;
-    if (n == 0) return 0;
-    if (!mu) return fail(CLOTHHIP_EINVAL, "NULL argument");
-    for (int64_t i = 0; i < 4 * n; i++)
-        if (!std::isfinite(mu[i])) return fail(CLOTHHIP_EINVAL, "mu[%lld][%lld] is not finite", (long long)(i / 4), (long long)(i % 4));
-    auto &f = h->fit;
-    HIPCHECK(hipSetDevice(h->device));
-    HIPCHECK(hipMemcpyAsync(f.d_old + (size_t)first * 4, mu, (size_t)n * 4 * 4, hipMemcpyHostToDevice, h->stream));
-    HIPCHECK(hipStreamSynchronize(h->stream));      // (the host table is not retained)
-    std::fill(f.h_old_set.begin() + first, f.h_old_set.begin() + first + n, (uint8_t)1);
-    return 0;
-}
-
-extern "C" int clothhip_fit_data_get_old_means(clothhip_handle *h, int64_t first, int64_t n, float *mu) {
-    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
-    if (int rc = check_idle(h)) return rc;
-    if (int rc = check_range(h, first, n)) return rc;
-    if (n == 0) return 0;
-    if (!mu) return fail(CLOTHHIP_EINVAL, "NULL argument");
-    HIPCHECK(hipSetDevice(h->device));
-    HIPCHECK(hipMemcpyAsync(mu, h->fit.d_old + (size_t)first * 4, (size_t)n * 4 * 4, hipMemcpyDeviceToHost, h->stream));      // (an unset row holds zeros)
-    HIPCHECK(hipStreamSynchronize(h->stream));
+    h->dataset.mark_old_set(first, n);
     return 0;
 }
 
@@ -917,7 +516,7 @@ static int check_ppo(const clothhip_handle *h, const ClothPpoParams *q, const in
     out->hi = 1.0 + q->clip;
     if (!std::isfinite(out->inv_s2)) return fail(CLOTHHIP_EINVAL, "sigma = %g: 1 / sigma^2 is not a finite double", q->sigma);
     for (int64_t i = 0; i < n_idx; i++)
-        if (!h->fit.h_old_set[(size_t)idx[i]])
+        if (!h->dataset.h_old_set[(size_t)idx[i]])
             return fail(CLOTHHIP_ESTATE, "idx[%lld] = row %d has no old mean: call clothhip_fit_data_snapshot_policy or clothhip_fit_data_set_old_means on it first",
                         (long long)i, idx[i]);
     return 0;
@@ -979,7 +578,7 @@ extern "C" int clothhip_value_fit(clothhip_handle *h, const ClothFitParams *p, c
 extern "C" int clothhip_value_fit_reset(clothhip_handle *h) {
     if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
     if (int rc = check_idle(h)) return rc;
-    h->value_forget();
+    h->fit.opt_value.forget();
     return 0;
 }
 
@@ -1005,8 +604,9 @@ extern "C" int clothhip_fit_data_gae(clothhip_handle *h, int64_t first, int64_t 
         return fail(CLOTHHIP_EINVAL, "gamma %g, lambda %g: both lie in [0, 1]", p->gamma, p->lambda);
     if (p->flags & ~(CLOTHHIP_GAE_WRITE_WEIGHTS | CLOTHHIP_GAE_NORMALIZE)) return fail(CLOTHHIP_EINVAL, "unknown flags 0x%x", p->flags);
     auto &f = h->fit;
+    const auto &d = h->dataset;
     for (int64_t i = 0; i < n; i++) {
-        const int32_t nx = f.h_next[(size_t)(first + i)];      // (greater than first + i where it is a row: clothhip_fit_data_set_transitions)
+        const int32_t nx = d.h_next[(size_t)(first + i)];      // (greater than first + i where it is a row: clothhip_fit_data_set_transitions)
         if (nx >= 0 && nx >= first + n)
             return fail(CLOTHHIP_EINVAL, "row %lld: its successor %d lies outside the rows [%lld, %lld + %lld)", (long long)(first + i), nx, (long long)first, (long long)first, (long long)n);
     }
@@ -1021,7 +621,7 @@ extern "C" int clothhip_fit_data_gae(clothhip_handle *h, int64_t first, int64_t 
     if (int rc = enqueue_predict(h, value_net(h), SHARED_ROW, 1, idx.data(), n)) return rc;      // (records ev0; the scan moves ev1 behind itself)
     const bool write_w = (p->flags & CLOTHHIP_GAE_WRITE_WEIGHTS) != 0, normalize = (p->flags & CLOTHHIP_GAE_NORMALIZE) != 0;
     GaeArgs a = {};
-    a.v = f.d_pred; a.rew = f.d_rew; a.next = f.d_next; a.ret = f.d_ret; a.w = f.d_w; a.A = f.d_gae_a; a.adv = f.d_adv; a.stat = f.d_gae_stat;
+    a.v = f.d_pred; a.rew = d.rew(); a.next = d.next(); a.ret = d.ret(); a.w = d.w(); a.A = f.d_gae_a; a.adv = f.d_adv; a.stat = f.d_gae_stat;
     a.first = first; a.n = n; a.gamma = p->gamma; a.c = p->gamma * p->lambda; a.w_scale = (double)p->w_scale; a.normalize = normalize ? 1 : 0;
     const dim3 grid((unsigned)((n + GAE_THREADS - 1) / GAE_THREADS));
     hipLaunchKernelGGL(k_gae_rows, grid, dim3(GAE_THREADS), 0, h->stream, a);
@@ -1036,7 +636,7 @@ extern "C" int clothhip_fit_data_gae(clothhip_handle *h, int64_t first, int64_t 
     }
     HIPCHECK(hipEventRecord(h->ev1, h->stream));
     if (adv_out) HIPCHECK(hipMemcpyAsync(adv_out, f.d_adv, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
-    if (ret_out) HIPCHECK(hipMemcpyAsync(ret_out, f.d_ret + (size_t)first, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+    if (ret_out) HIPCHECK(hipMemcpyAsync(ret_out, d.ret() + (size_t)first, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(hipStreamSynchronize(h->stream));      // (idx, a host table the upload read, goes out of scope)
     return 0;
 }

@@ -1,6 +1,7 @@
 // api_handle.hpp -- private to the api_*.hip units that implement include/clothhip.h: the handle, and the few helpers more than one of them calls.
 // Each group of fields below names the one unit that writes it; a field another unit reads is read directly (the last episode launch's record: through launch_table).
 #pragma once
+#include <algorithm>
 #include <cstring>
 #include <vector>
 
@@ -52,6 +53,40 @@ struct LaunchRecord {
     void invalidate_obs_tables() { obs = reset_obs = TableMode::Absent; }
 };
 enum class LaunchTable { obs, reset_obs, labels, records };
+
+// The columns of the trainer's dataset (clothhip_handle::FitData), each a device table of 4-byte elements, float or int32: obs [3P], the
+// label [4], the loss weight, the reward, the value target, the successor row (or CLOTHHIP_FIT_NEXT_*) and PPO's old mean [4]. A column is
+// described HERE and nowhere else: its width in elements per row (per_particle * P + fixed), and whether a new row gets a default -- the
+// 32-bit pattern `fill` -- or is written by every append. A new column is one enumerator plus one entry, plus whatever reads it: growth,
+// the defaults, clear and the range reader and writer of api_fit_data.hip are loops over this table and name no column.
+enum FitCol { COL_OBS, COL_LAB, COL_W, COL_REW, COL_RET, COL_NEXT, COL_OLD, FIT_COLS };
+struct FitColDesc {
+    int per_particle, fixed;
+    bool defaulted;
+    uint32_t fill;
+    size_t width(int P) const { return (size_t)per_particle * P + fixed; }
+};
+constexpr FitColDesc FIT_COL[] = {
+    {3, 0, false, 0},                                     // COL_OBS
+    {0, 4, false, 0},                                     // COL_LAB
+    {0, 1, false, 0},                                     // COL_W
+    {0, 1, true, 0},                                      // COL_REW: 0.0f
+    {0, 1, true, 0},                                      // COL_RET: 0.0f
+    {0, 1, true, (uint32_t)CLOTHHIP_FIT_NEXT_NONE},       // COL_NEXT: no successor, a leaf
+    {0, 4, true, 0},                                      // COL_OLD: zeros, and not set (FitData::h_old_set)
+};
+static_assert(sizeof(FIT_COL) / sizeof(FIT_COL[0]) == FIT_COLS, "one description per column");
+
+// An optimizer's state, per row of the weight table it trains (max(pop_rows, 1) rows: a shared network counts as ONE row): the moments
+// m, v [pop_rows][stride], [n_params] for one row (SGD's u is m), the count of steps taken and the read-as-zeros flag (the row's next
+// step clears its moments first -- what a reset is, so that a reset needs no device work). Both vectors are empty until the first step
+// after a new network: all rows fresh, which is what forget() makes them
+struct OptState {
+    Buffer<float> m, v;
+    std::vector<int64_t> t;
+    std::vector<uint8_t> zero;
+    void forget() { t.clear(); zero.clear(); }
+};
 
 // The host fields (HostPlan: layout_plan.hpp) and everything the handle holds on its device. Each buffer frees itself; the stream and the
 // events are declared in front of the buffers, so they go after them.
@@ -106,7 +141,7 @@ struct clothhip_handle : HostPlan {
     int n_grab_levels = 0;
     // clothhip_run_actions staging (device), sized on demand: written by clothhip_run_actions_begin / _end alone (api_run.hip). Read elsewhere:
     // last.pending (check_idle, clothhip_plan_cem); where a table of the last launch lies and how many rows it has, through launch_table below
-    // (clothhip_render_obs, the row sources of api_fit.hip, whose gather also takes d_fobs, d_frobs, d_flab and d_frec as they are); d_frec
+    // (clothhip_render_obs, the row sources of api_fit_data.hip, whose gather also takes d_fobs, d_frobs, d_flab and d_frec as they are); d_frec
     // (clothhip_plan_cem); d_resume is cleared by drop_in_flight* and clothhip_fork
     struct EpisodeStaging {
         Buffer<void> d_fz, d_fact, d_fscr, d_frec, d_frst, d_fobs, d_frobs;
@@ -160,39 +195,38 @@ struct clothhip_handle : HostPlan {
         Buffer<float> d_mlp;
         size_t n_params = 0;
     } val;
-    // The supervised trainer of the handle's networks (api_fit.hip: clothhip_fit_data_*, clothhip_policy_fit*, clothhip_value_fit*); a new
-    // network of either kind (api_policy.hip's drop_network) restarts the policy's optimizer through fit_forget below, a new value network
-    // the critic's through value_forget; nothing else outside api_fit.hip touches it.
-    struct Fit {
-        // the dataset: n rows of cap allocated, d_obs [cap][3P], d_lab [cap][4] and the per-row loss weights d_w [cap] float32 (grown
-        // geometrically, contents kept; d_w is the one column a caller may rewrite: clothhip_fit_data_set_weights)
-        Buffer<float> d_obs, d_lab, d_w;
-        int64_t n = 0, cap = 0;
-        // the episode structure and the value targets (clothhip_fit_data_set_transitions / _set_returns; they grow with the rows): the
-        // reward d_rew [cap], the successor row d_next [cap] (or CLOTHHIP_FIT_NEXT_*) with its host mirror h_next [n], against which
-        // clothhip_fit_data_gae checks a range without a download, and the value target d_ret [cap]
-        Buffer<float> d_rew, d_ret;
-        Buffer<int32_t> d_next;
+    // The device-resident dataset of the trainer and its row sources (api_fit_data.hip: clothhip_fit_data_append*, the column accessors,
+    // clothhip_fit_hold, clothhip_fit_data_append_launch*). api_fit.hip reads the columns through the accessors below, lets its kernels
+    // write ret and w (clothhip_fit_data_gae) and old (clothhip_fit_data_snapshot_policy) where they lie, and reads n and the two mirrors.
+    struct FitData {
+        Buffer<uint32_t> col[FIT_COLS];      // one table per column (FIT_COL above), [cap][width], grown geometrically with the contents kept
+        int64_t n = 0, cap = 0;              // rows that count, rows allocated
+        float *obs() const { return (float *)col[COL_OBS]; }
+        float *lab() const { return (float *)col[COL_LAB]; }
+        float *w() const { return (float *)col[COL_W]; }
+        float *rew() const { return (float *)col[COL_REW]; }
+        float *ret() const { return (float *)col[COL_RET]; }
+        int32_t *next() const { return (int32_t *)col[COL_NEXT]; }
+        float *old() const { return (float *)col[COL_OLD]; }
+        // host mirrors [n] that grow and clear with the rows: of `next`, against which clothhip_fit_data_gae checks a range without a
+        // download, and one byte per row: whether its old mean has been written -- against which clothhip_policy_fit_ppo* check a minibatch
         std::vector<int32_t> h_next;
-        // the old means of PPO (clothhip_fit_data_snapshot_policy / _set_old_means; the column grows with the rows): d_old [cap][4], what
-        // the shared network's mean was when the row was collected, zeros until written, and the host mirror h_old_set [n], one byte per
-        // row: whether it has been written -- against which clothhip_policy_fit_ppo* check a minibatch without a download
-        Buffer<float> d_old;
         std::vector<uint8_t> h_old_set;
-        Buffer<float> d_ratio;       // clothhip_policy_fit_ppo_grad: (float)rho of the minibatch's rows, [B]
+        void mark_old_set(int64_t first, int64_t rows) { std::fill(h_old_set.begin() + first, h_old_set.begin() + first + rows, (uint8_t)1); }
         // rows named by where they lie (clothhip_fit_hold, clothhip_fit_data_append_launch): held [E][3P], one row per env that outlives
-        // the launch tables (held_valid: some clothhip_fit_hold has filled it); the index table of one call and its not-finite flag
+        // the launch tables (held_valid: some clothhip_fit_hold has filled it); the gather's scratch: the index table of one call, its
+        // not-finite flag and the weights of one clothhip_fit_data_append_launch_ex call, [n]
         Buffer<float> d_held;
         bool held_valid = false;
         Buffer<int32_t> d_rows, d_flag;
-        Buffer<float> d_wtab;        // the weights of one clothhip_fit_data_append_launch_ex call, [n]
-        // the optimizer, per row of the weight table (max(pop_rows, 1) rows: a shared network counts as ONE row here too): moments d_m,
-        // d_v [pop_rows][stride], [n_params] for a shared network (SGD's u is d_m), the count of steps taken and the read-as-zeros flag
-        // (the row's next step clears its moments first -- what a reset is, so that a reset needs no device work). Both vectors are empty
-        // until the first step after a new network: all rows fresh
-        Buffer<float> d_m, d_v;
-        std::vector<int64_t> row_t;
-        std::vector<uint8_t> row_zero;
+        Buffer<float> d_wtab;
+    } dataset;
+    // The trainer of the handle's networks (api_fit.hip: clothhip_policy_fit*, clothhip_value_*, clothhip_fit_data_gae, _snapshot_policy).
+    // A new network of either kind (api_policy.hip's drop_network) restarts the policy's optimizer by opt_policy.forget(), a new value
+    // network the critic's by opt_value.forget(); nothing else outside api_fit.hip touches it.
+    struct Fit {
+        // the two optimizers: the policy's, per row of its weight table, and the value network's of ONE row
+        OptState opt_policy, opt_value;
         // one step's scratch, sized on demand, one of each per member of the call: the index table, the hidden activations and y, the
         // two dZ tables, the split batch sums of a weight gradient, the gradient (blob layout), the losses; the call's member rows and
         // its table of per-member, per-step optimizer constants
@@ -200,17 +234,11 @@ struct clothhip_handle : HostPlan {
         Buffer<float> d_act, d_dz, d_part, d_grad, d_hyper;
         Buffer<double> d_loss;
         Buffer<float> d_pred;        // clothhip_policy_fit_predict*: y of every member and row, [n_m][n][4]; clothhip_value_predict and clothhip_fit_data_gae: v [n]
-        // the value network's optimizer: its own moments [n_params], step count and read-as-zeros flag (vectors of ONE row, empty until
-        // the first step after a new value network), under the rules of the policy's above
-        Buffer<float> d_val_m, d_val_v;
-        std::vector<int64_t> val_t;
-        std::vector<uint8_t> val_zero;
+        Buffer<float> d_ratio;       // clothhip_policy_fit_ppo_grad: (float)rho of the minibatch's rows, [B]
         // clothhip_fit_data_gae: A of every row of the range as a double, the advantages as floats, {mean, std} of the normalisation
         Buffer<double> d_gae_a, d_gae_stat;
         Buffer<float> d_adv;
     } fit;
-    void fit_forget() { fit.row_t.clear(); fit.row_zero.clear(); }
-    void value_forget() { fit.val_t.clear(); fit.val_zero.clear(); }
     // The cross-entropy planner (api_plan.hip: clothhip_plan_cem on the SCRATCH handle, clothhip_plan_sample / _refit on the handle given), all
     // sized on demand: the distribution d_mean, d_std [E][H][4], the best so far d_best_a [E][H][4], d_best_s [E], the source's done flags, the
     // action tables d_x [H][E K][4] (one, or one per iteration when the caller wants them back), d_scores [n_iters][E][K], the elite flags and
@@ -229,6 +257,11 @@ template <typename F> static auto by_precision(const clothhip_handle *h, F &&f) 
 namespace clothhip {
 int check_params(const ClothParams *p);                                                          // api_core.hip
 int check_idle(const clothhip_handle *h);
+int check_range(const clothhip_handle *h, int64_t first, int64_t n);                             // api_fit_data.hip: rows [first, first + n) lie within the dataset
+// api_fit_data.hip, the one includer of cloth_fit_gather.hpp, for the trainer: that header's k_fit_sqsum over one block and k_fit_copy_y over
+// blocks * n_m, argument for argument
+void launch_fit_sqsum(hipStream_t s, const float *y, const float *lab, const float *wgt, const int32_t *rows, int32_t B, double *sum);
+void launch_fit_copy_y(hipStream_t s, int32_t n_m, const float *y, int32_t n_vals, float *out, int64_t y_step, int64_t out_step, int32_t blocks);
 int check_material(const ClothParams &prm, const ClothMaterial &m, int idx);                     // api_state.hip
 SpecPhys phys_of(const ClothParams &p);
 SpecPhys phys_of(const ClothParams &p, const ClothMaterial &m);

@@ -28,7 +28,7 @@ static int check_members(const int32_t *member, int64_t n, int64_t rows, const c
     return 0;
 }
 // the handle without a network of either kind (the memory stays with the handle for the next one); the trainer's moments belonged to the old one
-static void drop_network(clothhip_handle *h) { h->fit_forget(); h->pol.mlp = MlpDesc{}; h->pol.pop_rows = 0; h->pol.mlp_n_params = 0; h->pol.pop_generated = false; }
+static void drop_network(clothhip_handle *h) { h->fit.opt_policy.forget(); h->pol.mlp = MlpDesc{}; h->pol.pop_rows = 0; h->pol.mlp_n_params = 0; h->pol.pop_generated = false; }
 static MlpDesc mlp_desc(int32_t n_layers, const int32_t *widths, const float *params, const int32_t *member, size_t stride) {
     MlpDesc d = {};
     d.n_layers = n_layers;
@@ -60,7 +60,7 @@ extern "C" int clothhip_set_policy_mlp(clothhip_handle *h, int32_t n_layers, con
 extern "C" int clothhip_set_value_mlp(clothhip_handle *h, int32_t n_layers, const int32_t *widths, const float *params, size_t n_params) {
     if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
     if (int rc = check_idle(h)) return rc;
-    auto drop = [h] { h->value_forget(); h->val.mlp = MlpDesc{}; h->val.n_params = 0; };
+    auto drop = [h] { h->fit.opt_value.forget(); h->val.mlp = MlpDesc{}; h->val.n_params = 0; };
     if (n_layers == 0) { drop(); return 0; }
     if (int rc = check_mlp_shape(h, n_layers, widths, 1)) return rc;
     if (!params) return fail(CLOTHHIP_EINVAL, "NULL argument");
