@@ -5,6 +5,7 @@ is missing, or no HIP device is visible, the calls below raise -- loudly -- inst
 """
 import ctypes as C
 import os
+from collections import namedtuple
 
 import numpy as np
 
@@ -98,6 +99,12 @@ RESET_RECORD_DTYPE = np.dtype([("consumed", "<i4"), ("pulls_run", "<i4"), ("exec
 assert RESET_PULL_DTYPE.itemsize == 56 and RESET_SCRIPT_DTYPE.itemsize == 184
 assert STEP_RECORD_DTYPE.itemsize == 72 and RESET_RECORD_DTYPE.itemsize == 144
 assert C.sizeof(ClothEpisodeParams) == 144
+
+# ClothBatch._launch, the last episode launch of a batch: T slots and R reset scripts per env (the shapes of the tables it left on the
+# device: render_obs('slots' / 'resets'), run_actions_labels), and between run_actions_begin and run_actions_end what the second half needs
+# (here, beside the records' dtypes, because batch.py's launches and batch_plan.py's planner both write it)
+LastLaunch = namedtuple("LastLaunch", "T R pending")
+PendingLaunch = namedtuple("PendingLaunch", "num_steps done have_rst have_obs have_robs rng_states")
 
 
 class ClothFitParams(C.Structure):

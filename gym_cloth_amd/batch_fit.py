@@ -1,0 +1,449 @@
+"""ClothBatch's bindings of the trainer on the handle (clothhip.h, csrc/api_fit_data.hip and api_fit.hip): the device-resident dataset
+and its columns, the fit of the shared network and of population rows, the value network, GAE and PPO. A mixin of batch.ClothBatch: it
+reads self._L, self._h, self.E and self.P, and the sizes batch_policy.py's setters leave (_mlp_n_params, _pop_shape)."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import check
+from .mlp import pack_mlp
+
+
+class FitBindings(object):
+    @staticmethod
+    def _fit_weights(weights, n, what="weights"):
+        """A table of per-row loss weights (or, by `what`, another float32 column of the dataset) as float32[n], finite (any sign, zero
+        allowed); None stays None: 1 for every row."""
+        if weights is None:
+            return None
+        w64 = np.asarray(weights, dtype=np.float64)
+        if w64.shape != (n,):
+            raise ValueError("%s must have shape (%d,) (got %r)" % (what, n, w64.shape))
+        with np.errstate(over='ignore'):                  # (a double past float32's range becomes inf, refused below)
+            w = np.ascontiguousarray(w64, dtype=np.float32)
+        if not np.isfinite(w).all():
+            raise ValueError("%s must be finite (float32)" % what)
+        return w
+
+    def fit_append(self, obs, labels, weights=None):
+        """Append (observation row, action label) pairs to the handle's device-resident dataset (clothhip_fit_data_append): obs [n, 3P]
+        (stored as float32), labels [n, 4] (stored as float32), weights [n] (the rows' loss weights, float32, any finite value; None:
+        1 for every row -- clothhip_fit_data_append_weighted). ValueError for other shapes or non-finite values (dagger_rollout gives
+        NaN labels where a slot did not run: pass the [ran] rows); nothing is appended then. Returns the dataset's size."""
+        obs = np.ascontiguousarray(obs, dtype=np.float32)
+        lab = np.ascontiguousarray(labels, dtype=np.float64)
+        if obs.ndim != 2 or obs.shape[1] != 3 * self.P:
+            raise ValueError("obs must have shape (n, %d)" % (3 * self.P))
+        if lab.shape != (obs.shape[0], 4):
+            raise ValueError("labels must have shape (%d, 4)" % obs.shape[0])
+        if not (np.isfinite(obs).all() and np.isfinite(lab).all() and (np.abs(lab) <= np.finfo(np.float32).max).all()):
+            raise ValueError("obs and labels must be finite (float32)")
+        w = self._fit_weights(weights, obs.shape[0])
+        if w is None:
+            check(self._L.clothhip_fit_data_append(self._h, _lib.fp(obs), _lib.dp(lab), obs.shape[0]))
+        else:
+            check(self._L.clothhip_fit_data_append_weighted(self._h, _lib.fp(obs), _lib.dp(lab), _lib.fp(w), obs.shape[0]))
+        return self.fit_size()
+
+    def fit_set_weights(self, weights, first=0):
+        """Write the loss weights of the stored rows [first, first + len(weights)) (clothhip_fit_data_set_weights): any finite float32,
+        negative and zero allowed. The weight is the one column of a stored row that can be rewritten -- a row is appended when its
+        observation exists, its return is known when its episode ends."""
+        w = self._fit_weights(weights, len(weights))
+        check(self._L.clothhip_fit_data_set_weights(self._h, int(first), w.size, _lib.fp(w)))
+
+    def fit_get_weights(self, first=0, n=None):
+        """float32[n]: the loss weights of the stored rows [first, first + n), n=None: to the end (clothhip_fit_data_get_weights)."""
+        first, n = self._fit_range(first, n)
+        w = np.zeros(n, dtype=np.float32)
+        check(self._L.clothhip_fit_data_get_weights(self._h, first, n, _lib.fp(w)))
+        return w
+
+    def fit_hold(self, src=None):
+        """Fill the handle's held rows (clothhip_fit_hold): src=None -> held[e] = the float32 '1d' observation of env e's present state;
+        src int[E, 2] = (source, row) with _lib.FIT_SRC_* -> held[e] = that row of the last launch's tables ((FIT_SRC_HELD, e) keeps it)."""
+        if src is not None:
+            src = np.asarray(src)
+            if src.shape != (self.E, 2) or not np.issubdtype(src.dtype, np.integer):
+                raise ValueError("src must be integers of shape (%d, 2)" % self.E)
+            src = np.ascontiguousarray(src, dtype=np.int32)
+        check(self._L.clothhip_fit_hold(self._h, _lib.i32p(src)))
+
+    def fit_append_launch(self, rows, labels="expert", weights=None):
+        """Append pairs that lie on the device (clothhip_fit_data_append_launch_ex): rows int[n, 3] = (source, row, label_row) -- the
+        observation is that row of the last launch's tables or of the held rows; the label is row label_row = t * E + e of the last
+        armed launch's labels (labels="expert"), or the action that slot of the last launch EXECUTED, (float32)out['actions'][t, e] read
+        from the launch's records on the device (labels="action": for policy='mlp' the network's output plus the caller's noise; no
+        expert needed), or with labels="zero" (0, 0, 0, 0) and label_row ignored: a leaf of the actor-critic, appended for its state alone.
+        weights [n]: the rows' loss weights, None: 1. ValueError when a named value is not finite (a slot that did not
+        run); nothing is appended then. Returns the dataset's size."""
+        rows = np.asarray(rows)
+        if rows.ndim != 2 or rows.shape[1] != 3 or not np.issubdtype(rows.dtype, np.integer):
+            raise ValueError("rows must be integers of shape (n, 3)")
+        if labels != "zero" and labels not in _lib.FIT_LABELS:
+            raise ValueError("labels must be one of %r or 'zero' (got %r)" % (sorted(_lib.FIT_LABELS), labels))
+        rows = np.ascontiguousarray(rows, dtype=np.int32)
+        w = self._fit_weights(weights, rows.shape[0])
+        src = _lib.FIT_LABEL_ZERO if labels == "zero" else _lib.FIT_LABELS[labels]
+        check(self._L.clothhip_fit_data_append_launch_ex(self._h, _lib.i32p(rows), rows.shape[0], src, _lib.fp(w)))
+        return self.fit_size()
+
+    def fit_data(self, first=0, n=None):
+        """(obs float32[n, 3P], labels float32[n, 4]): the stored rows [first, first + n), n=None: to the end (clothhip_fit_data_get)."""
+        first, n = self._fit_range(first, n)
+        obs = np.zeros((n, 3 * self.P), dtype=np.float32)
+        lab = np.zeros((n, 4), dtype=np.float32)
+        check(self._L.clothhip_fit_data_get(self._h, first, n, _lib.fp(obs), _lib.fp(lab)))
+        return obs, lab
+
+    def fit_loss(self, idx):
+        """The MSE of the handle's shared network over the dataset rows idx [n], any n >= 1 (a held-out split by index), forward only
+        (clothhip_policy_fit_loss); for n <= FIT_MAX_BATCH it is fit_grad's loss bit for bit."""
+        ix = self._fit_rows(idx)
+        self._fit_n_params()
+        loss = np.zeros(1, dtype=np.float64)
+        check(self._L.clothhip_policy_fit_loss(self._h, _lib.i32p(ix), ix.size, _lib.dp(loss)))
+        return float(loss[0])
+
+    def fit_predict(self, idx, members=None):
+        """The trainer's forward on the stored rows idx [n], any n >= 1, nothing updated: float32[n, 4] of the shared network
+        (clothhip_policy_fit_predict), or with members (distinct population rows) float32[n_m, n, 4], the same rows under every member
+        (clothhip_policy_fit_predict_members). Row r is bit for bit the y fit_grad forms for dataset row idx[r] -- what the loss and its
+        gradient are made of, so weights computed from it (residuals, trust regions, an ensemble's disagreement) describe the fit itself."""
+        ix = self._fit_rows(idx)
+        if members is None:
+            self._fit_n_params()
+            y = np.zeros((ix.size, 4), dtype=np.float32)
+            check(self._L.clothhip_policy_fit_predict(self._h, _lib.i32p(ix), ix.size, _lib.fp(y)))
+            return y
+        m, _ = self._fit_members(members)
+        y = np.zeros((m.size, ix.size, 4), dtype=np.float32)
+        check(self._L.clothhip_policy_fit_predict_members(self._h, _lib.i32p(m), m.size, _lib.i32p(ix), ix.size, _lib.fp(y)))
+        return y
+
+    def fit_clear(self):
+        """Empty the dataset (clothhip_fit_data_clear); the device memory stays with the handle."""
+        check(self._L.clothhip_fit_data_clear(self._h))
+
+    def fit_size(self):
+        """Rows in the dataset (clothhip_fit_data_size)."""
+        n = C.c_int64(0)
+        check(self._L.clothhip_fit_data_size(self._h, C.byref(n)))
+        return int(n.value)
+
+    @staticmethod
+    def _fit_rows(idx):
+        """Any number >= 1 of dataset rows as int32: a 1-d integer list (fit_loss, fit_predict, value_predict)."""
+        a = np.asarray(idx)
+        if a.ndim != 1 or a.size < 1 or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("idx must be a non-empty 1-d integer array")
+        if a.min() < 0 or a.max() > np.iinfo(np.int32).max:
+            raise ValueError("idx must hold row numbers of the dataset")
+        return np.ascontiguousarray(a, dtype=np.int32)
+
+    @staticmethod
+    def _fit_idx(idx, ndim):
+        """A minibatch index table as int32, C order: integers, `ndim` dimensions, at least one row per step, at most FIT_MAX_BATCH."""
+        a = np.asarray(idx)
+        if a.ndim != ndim or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("idx must be a %d-d integer array" % ndim)
+        if not 1 <= a.shape[-1] <= _lib.FIT_MAX_BATCH:
+            raise ValueError("a minibatch has 1 to %d rows (got %d)" % (_lib.FIT_MAX_BATCH, a.shape[-1]))
+        if a.size and (a.min() < 0 or a.max() > np.iinfo(np.int32).max):
+            raise ValueError("idx must hold row numbers of the dataset")
+        return np.ascontiguousarray(a, dtype=np.int32)
+
+    def fit_grad(self, idx):
+        """(loss float, grad float32[n_params] in the blob's layout) of the handle's shared network over the dataset rows idx [B]
+        (repeats count as often), at the present weights; nothing is updated (clothhip_policy_fit_grad). The loss is
+        1 / (4 B) sum (y - label)^2, torch.nn.MSELoss()."""
+        ix = self._fit_idx(idx, 1)
+        n_params = self._fit_n_params()
+        grad = np.zeros(n_params, dtype=np.float32)
+        loss = np.zeros(1, dtype=np.float64)
+        check(self._L.clothhip_policy_fit_grad(self._h, _lib.i32p(ix), ix.size, _lib.fp(grad), _lib.dp(loss)))
+        return float(loss[0]), grad
+
+    def _fit_n_params(self):
+        n = getattr(self, '_mlp_n_params', 0)
+        if not n:
+            raise _lib.ClothHipError("no shared network on this batch: call set_policy_mlp first")
+        return n
+
+    @staticmethod
+    def _fit_params(hyper, n_m):
+        """_lib.ClothFitParams[n_m] from a dict with fit's keywords (optimizer, lr, beta1, beta2, eps, momentum), each value a scalar for
+        all members or a sequence of n_m, rounded to float32; what the library would refuse is a ValueError here first."""
+        hyper = dict(hyper or {})
+        optimizer = hyper.pop('optimizer', 'adam')
+        if optimizer not in _lib.FIT_OPTIMIZERS:
+            raise ValueError("optimizer must be one of %r (got %r)" % (sorted(_lib.FIT_OPTIMIZERS), optimizer))
+        vals = dict(lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, momentum=0.0)
+        unknown = sorted(set(hyper) - set(vals))
+        if unknown:
+            raise ValueError("unknown hyper-parameters %r" % unknown)
+        vals.update(hyper)
+        p = (_lib.ClothFitParams * n_m)()
+        for k, v in vals.items():
+            v = np.asarray(v, dtype=np.float64)
+            if v.ndim > 1 or (v.ndim == 1 and v.size != n_m):
+                raise ValueError("%s must be a scalar or %d values, one per member" % (k, n_m))
+            v = np.broadcast_to(v, (n_m,)).astype(np.float32)
+            if not (np.isfinite(v).all() and (v >= 0.0).all()) or (k.startswith('beta') and (v >= 1.0).any()):
+                raise ValueError("%s = %r: hyper-parameters are finite and >= 0, the betas below 1" % (k, vals[k]))
+            for j in range(n_m):
+                setattr(p[j], k, float(v[j]))
+        for j in range(n_m):
+            p[j].optimizer = float(_lib.FIT_OPTIMIZERS[optimizer])
+        return p
+
+    def fit(self, idx_table, optimizer='adam', lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, momentum=0.0):
+        """n_steps optimizer steps on the handle's shared network, in place on the device (clothhip_policy_fit): step s uses the dataset
+        rows idx_table[s] (int [n_steps, B]). optimizer 'adam' (lr, beta1, beta2, eps) or 'sgd' (lr, momentum); the hyper-parameters are
+        rounded to float32. The moments and the step count persist across calls (fit_reset, or a new network, restarts them). Returns
+        float64[n_steps]: each step's loss BEFORE its update. The next step_many(policy='mlp') runs the fitted weights."""
+        ix = self._fit_idx(idx_table, 2)
+        p = self._fit_params(dict(optimizer=optimizer, lr=lr, beta1=beta1, beta2=beta2, eps=eps, momentum=momentum), 1)
+        self._fit_n_params()
+        loss = np.zeros(ix.shape[0], dtype=np.float64)
+        check(self._L.clothhip_policy_fit(self._h, p, _lib.i32p(ix), ix.shape[0], ix.shape[1], _lib.dp(loss)))
+        return loss
+
+    def fit_reset(self):
+        """Zero the optimizer's moments and its step count (clothhip_policy_fit_reset)."""
+        check(self._L.clothhip_policy_fit_reset(self._h))
+
+    # ---- the grouped trainer: rows of the population fitted in the launches of one network (clothhip_policy_fit*_members) ----------
+    def _fit_members(self, members):
+        """members as int32[n_m]: distinct rows of the batch's population ((rows, n_params) from the call that made it)."""
+        shape = getattr(self, '_pop_shape', None)
+        if shape is None:
+            raise _lib.ClothHipError("no population on this batch: call set_policy_population or population_perturb first")
+        m = np.asarray(members)
+        if m.ndim != 1 or m.size < 1 or not np.issubdtype(m.dtype, np.integer):
+            raise ValueError("members must be a non-empty 1-d integer array")
+        if m.min() < 0 or m.max() >= shape[0]:
+            raise ValueError("members must lie in [0, %d)" % shape[0])
+        if np.unique(m).size != m.size:
+            raise ValueError("members must be distinct: a call fits a row once")
+        return np.ascontiguousarray(m, dtype=np.int32), shape[1]
+
+    def _fit_members_idx(self, idx, n_m, ndim):
+        ix = self._fit_idx(idx, ndim)
+        if ix.shape[-2] != n_m:
+            raise ValueError("idx must have %d rows of minibatch per step, one per member (got shape %r)" % (n_m, ix.shape))
+        if n_m * ix.shape[-1] > _lib.FIT_MAX_MEMBER_ROWS:
+            raise ValueError("%d members x %d rows in one call, at most %d" % (n_m, ix.shape[-1], _lib.FIT_MAX_MEMBER_ROWS))
+        return ix
+
+    def fit_grad_members(self, members, idx):
+        """(loss float64[n_m], grad float32[n_m, n_params]) of the population rows `members` (distinct ints) over their own minibatches
+        idx [n_m, B] of the batch's one dataset, at the present weights; nothing is updated (clothhip_policy_fit_grad_members). Member
+        j's result is bit for bit fit_grad's on a batch that carries row members[j] as its shared network."""
+        m, n_params = self._fit_members(members)
+        ix = self._fit_members_idx(idx, m.size, 2)
+        grad = np.zeros((m.size, n_params), dtype=np.float32)
+        loss = np.zeros(m.size, dtype=np.float64)
+        check(self._L.clothhip_policy_fit_grad_members(self._h, _lib.i32p(m), m.size, _lib.i32p(ix), ix.shape[1], _lib.fp(grad), _lib.dp(loss)))
+        return loss, grad
+
+    def fit_members(self, members, idx_table, hyper=None):
+        """n_steps optimizer steps on the population rows `members`, in place on the device, all members in the launches of one
+        (clothhip_policy_fit_members): step s of member j uses the dataset rows idx_table[s, j] (int [n_steps, n_m, B]). hyper: a dict
+        with fit's keywords (optimizer, lr, beta1, beta2, eps, momentum), each value a scalar for all members or a sequence of n_m;
+        the optimizer is one for the call. Every row keeps its own moments and step count across calls (fit_reset_members, or a new
+        population, restarts them). Returns float64[n_steps, n_m]: each member's loss BEFORE each step's update -- the bits fit gives
+        on a batch that carries the row as its shared network."""
+        m, _ = self._fit_members(members)
+        ix = self._fit_members_idx(idx_table, m.size, 3)
+        p = self._fit_params(hyper, m.size)
+        loss = np.zeros((ix.shape[0], m.size), dtype=np.float64)
+        check(self._L.clothhip_policy_fit_members(self._h, p, _lib.i32p(m), m.size, _lib.i32p(ix), ix.shape[0], ix.shape[2], _lib.dp(loss)))
+        return loss
+
+    def fit_reset_members(self, members=None):
+        """Zero the moments and the step count of the population rows `members`, None: of all rows (clothhip_policy_fit_reset_members)."""
+        if members is None:
+            check(self._L.clothhip_policy_fit_reset_members(self._h, None, 0))
+            return
+        m, _ = self._fit_members(members)
+        check(self._L.clothhip_policy_fit_reset_members(self._h, _lib.i32p(m), m.size))
+
+    # ---- actor-critic from reward: the value network, the transition columns, the critic's fit, GAE (clothhip.h: ACTOR-CRITIC FROM REWARD) ----
+    def set_value_mlp(self, layers):
+        """The handle's value network (clothhip_set_value_mlp): `layers` as set_policy_mlp takes them with a last `out` of 1; None or []
+        drops it. It lives beside the policy network or population and independent of it; no launch evaluates it."""
+        self._val_n_params = 0
+        if not layers:
+            check(self._L.clothhip_set_value_mlp(self._h, 0, None, None, 0))
+            return
+        widths, blob = pack_mlp(layers, n_out=1)
+        check(self._L.clothhip_set_value_mlp(self._h, len(widths) - 1, _lib.i32p(widths), _lib.fp(blob), blob.size))
+        self._val_n_params = int(blob.size)
+
+    def _value_n_params(self):
+        n = getattr(self, '_val_n_params', 0)
+        if not n:
+            raise _lib.ClothHipError("no value network on this batch: call set_value_mlp first")
+        return n
+
+    def get_value_mlp(self):
+        """The value network's blob as the device holds it, float32[n_params] (clothhip_get_value_mlp)."""
+        out = np.zeros(self._value_n_params(), dtype=np.float32)
+        check(self._L.clothhip_get_value_mlp(self._h, _lib.fp(out), out.size))
+        return out
+
+    def _fit_range(self, first, n):
+        first = int(first)
+        n = self.fit_size() - first if n is None else int(n)
+        if first < 0 or n < 0:
+            raise ValueError("first and n must be >= 0 and lie within the dataset")
+        return first, n
+
+    def fit_set_transitions(self, rew, next, first=0):
+        """Write the reward and the successor of the stored rows [first, first + len(rew)) (clothhip_fit_data_set_transitions): rew
+        finite float32, next int: the dataset index of the row with the successor state (greater than the row's own), or
+        _lib.FIT_NEXT_TERMINAL (the episode ended), or _lib.FIT_NEXT_NONE (a leaf: the row has no transition, it only bootstraps)."""
+        r = self._fit_weights(rew, len(rew), "rew")
+        nx = np.asarray(next)
+        if nx.shape != r.shape or not np.issubdtype(nx.dtype, np.integer):
+            raise ValueError("next must hold %d integers" % r.size)
+        if nx.size and (nx.min() < _lib.FIT_NEXT_NONE or nx.max() > np.iinfo(np.int32).max):
+            raise ValueError("next must hold row numbers of the dataset, FIT_NEXT_TERMINAL or FIT_NEXT_NONE")
+        nx = np.ascontiguousarray(nx, dtype=np.int32)
+        check(self._L.clothhip_fit_data_set_transitions(self._h, int(first), r.size, _lib.fp(r), _lib.i32p(nx)))
+
+    def fit_get_transitions(self, first=0, n=None):
+        """(rew float32[n], next int32[n]) of the stored rows [first, first + n), n=None: to the end (clothhip_fit_data_get_transitions)."""
+        first, n = self._fit_range(first, n)
+        rew, nx = np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.int32)
+        check(self._L.clothhip_fit_data_get_transitions(self._h, first, n, _lib.fp(rew), _lib.i32p(nx)))
+        return rew, nx
+
+    def fit_set_returns(self, ret, first=0):
+        """Write the value targets of the stored rows [first, first + len(ret)) (clothhip_fit_data_set_returns): finite float32."""
+        r = self._fit_weights(ret, len(ret), "ret")
+        check(self._L.clothhip_fit_data_set_returns(self._h, int(first), r.size, _lib.fp(r)))
+
+    def fit_get_returns(self, first=0, n=None):
+        """float32[n]: the value targets of the stored rows [first, first + n), n=None: to the end (clothhip_fit_data_get_returns)."""
+        first, n = self._fit_range(first, n)
+        ret = np.zeros(n, dtype=np.float32)
+        check(self._L.clothhip_fit_data_get_returns(self._h, first, n, _lib.fp(ret)))
+        return ret
+
+    def value_grad(self, idx):
+        """(loss float, grad float32[n_params] in the blob's layout) of the value network over the dataset rows idx [B], at the present
+        weights; nothing is updated (clothhip_value_fit_grad). The loss is 1 / (2 B) sum (v - ret)^2, unweighted."""
+        ix = self._fit_idx(idx, 1)
+        grad = np.zeros(self._value_n_params(), dtype=np.float32)
+        loss = np.zeros(1, dtype=np.float64)
+        check(self._L.clothhip_value_fit_grad(self._h, _lib.i32p(ix), ix.size, _lib.fp(grad), _lib.dp(loss)))
+        return float(loss[0]), grad
+
+    def value_fit(self, idx_table, optimizer='adam', lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, momentum=0.0):
+        """fit for the value network (clothhip_value_fit): n_steps optimizer steps in place on the device, step s on the dataset rows
+        idx_table[s] (int [n_steps, B]), with its own moments and step count (value_fit_reset, or a new value network, restarts them).
+        Returns float64[n_steps]: each step's loss BEFORE its update. The policy's network and optimizer keep their bits."""
+        ix = self._fit_idx(idx_table, 2)
+        p = self._fit_params(dict(optimizer=optimizer, lr=lr, beta1=beta1, beta2=beta2, eps=eps, momentum=momentum), 1)
+        self._value_n_params()
+        loss = np.zeros(ix.shape[0], dtype=np.float64)
+        check(self._L.clothhip_value_fit(self._h, p, _lib.i32p(ix), ix.shape[0], ix.shape[1], _lib.dp(loss)))
+        return loss
+
+    def value_predict(self, idx):
+        """float32[n]: the value network on the stored rows idx [n], any n >= 1, nothing updated (clothhip_value_predict) -- row r is bit
+        for bit the v value_grad forms for dataset row idx[r]."""
+        ix = self._fit_rows(idx)
+        self._value_n_params()
+        v = np.zeros(ix.size, dtype=np.float32)
+        check(self._L.clothhip_value_predict(self._h, _lib.i32p(ix), ix.size, _lib.fp(v)))
+        return v
+
+    def value_fit_reset(self):
+        """Zero the value network's moments and its step count (clothhip_value_fit_reset)."""
+        check(self._L.clothhip_value_fit_reset(self._h))
+
+    def fit_gae(self, gamma, lam, first=0, n=None, write_weights=True, normalize=False, w_scale=1.0, want=True):
+        """Generalised advantage estimation over the stored rows [first, first + n) ON THE DEVICE (clothhip_fit_data_gae): the value
+        network's forward over the range, then per non-leaf row A = sum_k (gamma lam)^k delta_k along its chain of successors,
+        delta = rew + gamma V(next) - V (V(next) = 0 at a terminal row, the critic's value at a leaf); the value-target column gets
+        (float32)(A + V), a leaf's gets V. write_weights: the weight column gets (float32)(w_scale A), or with normalize
+        w_scale (A - mean) / (std + 1e-8) over the non-leaf rows; a leaf gets 0. Returns (adv float32[n], ret float32[n]), or None
+        with want=False (nothing is downloaded). policies.gae_reference states the arithmetic."""
+        first, n = self._fit_range(first, n)
+        g, l, ws = float(gamma), float(lam), float(np.float32(w_scale))
+        if not (np.isfinite(g) and np.isfinite(l) and np.isfinite(ws)) or not (0.0 <= g <= 1.0 and 0.0 <= l <= 1.0):
+            raise ValueError("gamma and lam lie in [0, 1], w_scale is a finite float32 (got %r, %r, %r)" % (gamma, lam, w_scale))
+        self._value_n_params()
+        p = _lib.ClothGaeParams(g, l, ws, (_lib.GAE_WRITE_WEIGHTS if write_weights else 0) | (_lib.GAE_NORMALIZE if normalize else 0))
+        adv = np.zeros(n, dtype=np.float32) if want else None
+        ret = np.zeros(n, dtype=np.float32) if want else None
+        check(self._L.clothhip_fit_data_gae(self._h, first, n, C.byref(p), _lib.fp(adv), _lib.fp(ret)))
+        return (adv, ret) if want else None
+
+    # ---- PPO: the old means and the clipped surrogate (clothhip.h: PPO ON THE DEVICE) ----------------------------------------------
+    def fit_snapshot_policy(self, first=0, n=None):
+        """Write the shared network's present output on the stored rows [first, first + n) (n=None: to the end) into the dataset's
+        old-mean column, on the device (clothhip_fit_data_snapshot_policy): the bytes fit_predict returns for these rows, never
+        downloaded. The rows then have an old mean, which fit_ppo / fit_ppo_grad need of every row they name."""
+        first, n = self._fit_range(first, n)
+        self._fit_n_params()
+        check(self._L.clothhip_fit_data_snapshot_policy(self._h, first, n))
+
+    def fit_set_old_means(self, mu, first=0):
+        """Write the old means of the stored rows [first, first + len(mu)) from the host (clothhip_fit_data_set_old_means): mu [n, 4],
+        finite float32."""
+        m = np.asarray(mu, dtype=np.float64)
+        if m.ndim != 2 or m.shape[1] != 4:
+            raise ValueError("mu must have shape (n, 4)")
+        if not (np.isfinite(m).all() and (np.abs(m) <= np.finfo(np.float32).max).all()):
+            raise ValueError("mu must be finite (float32)")
+        m = np.ascontiguousarray(m, dtype=np.float32)
+        check(self._L.clothhip_fit_data_set_old_means(self._h, int(first), m.shape[0], _lib.fp(m)))
+
+    def fit_get_old_means(self, first=0, n=None):
+        """float32[n, 4]: the old means of the stored rows [first, first + n), n=None: to the end (clothhip_fit_data_get_old_means);
+        zeros for a row that has none."""
+        first, n = self._fit_range(first, n)
+        mu = np.zeros((n, 4), dtype=np.float32)
+        check(self._L.clothhip_fit_data_get_old_means(self._h, first, n, _lib.fp(mu)))
+        return mu
+
+    @staticmethod
+    def _ppo_params(sigma, clip):
+        s, c = float(sigma), float(clip)
+        if not (np.isfinite(s) and s > 0.0 and s * s > 0.0 and np.isfinite(1.0 / (s * s))):
+            raise ValueError("sigma = %r: the policy's standard deviation is finite and > 0" % (sigma,))
+        if not (np.isfinite(c) and 0.0 <= c < 1.0):
+            raise ValueError("clip = %r: the clip range lies in [0, 1)" % (clip,))
+        return _lib.ClothPpoParams(s, c)
+
+    def fit_ppo_grad(self, idx, sigma, clip=0.2):
+        """(stats float64[3] = loss, clip_fraction, kl; grad float32[n_params] in the blob's layout; ratio float32[B]) of PPO's clipped
+        surrogate over the dataset rows idx [B] at the present weights; nothing is updated (clothhip_policy_fit_ppo_grad). The policy
+        is Gaussian with the fixed standard deviation sigma around the shared network's output; a row's action is its label, its
+        advantage its weight, its old mean what fit_snapshot_policy / fit_set_old_means stored. policies.ppo_reference is the float64
+        yardstick, policies.ppo_loss_reference the kernel's arithmetic."""
+        ix = self._fit_idx(idx, 1)
+        q = self._ppo_params(sigma, clip)
+        grad = np.zeros(self._fit_n_params(), dtype=np.float32)
+        stats = np.zeros(_lib.PPO_STATS, dtype=np.float64)
+        ratio = np.zeros(ix.size, dtype=np.float32)
+        check(self._L.clothhip_policy_fit_ppo_grad(self._h, C.byref(q), _lib.i32p(ix), ix.size, _lib.fp(grad), _lib.dp(stats), _lib.fp(ratio)))
+        return stats, grad, ratio
+
+    def fit_ppo(self, idx_table, sigma, clip=0.2, optimizer='adam', lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, momentum=0.0):
+        """fit with PPO's clipped surrogate as the loss (clothhip_policy_fit_ppo): n_steps optimizer steps on the shared network in
+        place, step s on the dataset rows idx_table[s] (int [n_steps, B]), every row with an old mean. The optimizer is the policy's:
+        fit and fit_ppo share the moments and the step count, fit_reset restarts both. Returns float64[n_steps, 3]: each step's
+        (loss, clip_fraction, kl) BEFORE its update."""
+        ix = self._fit_idx(idx_table, 2)
+        p = self._fit_params(dict(optimizer=optimizer, lr=lr, beta1=beta1, beta2=beta2, eps=eps, momentum=momentum), 1)
+        q = self._ppo_params(sigma, clip)
+        self._fit_n_params()
+        stats = np.zeros((ix.shape[0], _lib.PPO_STATS), dtype=np.float64)
+        check(self._L.clothhip_policy_fit_ppo(self._h, p, C.byref(q), _lib.i32p(ix), ix.shape[0], ix.shape[1], _lib.dp(stats)))
+        return stats

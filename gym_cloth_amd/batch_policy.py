@@ -1,0 +1,128 @@
+"""ClothBatch's bindings of the policy networks on the handle (clothhip.h, csrc/api_policy.hip): the shared MLP, a population with one
+network per env slot, their evaluation and the perturbations made on the device. A mixin of batch.ClothBatch: it reads self._L,
+self._h, self.E and self.P and keeps no state but what the methods below say."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import check
+from .mlp import pack_mlp, pack_population
+
+
+class PolicyBindings(object):
+    def set_policy_mlp(self, layers):
+        """The handle's policy network (clothhip_set_policy_mlp): `layers` is a list of (W, b) with W [out, in] (torch.nn.Linear.weight's
+        layout) and b [out], ReLU between them, the first `in` = 3 P, the last `out` = 4; None or [] clears it. The values are
+        uploaded as float32; every env of the batch evaluates the same network. ValueError for shapes the library refuses."""
+        self._mlp_n_params = 0                     # (fit_grad sizes its result by it: the shared network's parameters, 0 without one)
+        self._pop_shape = None                     # (a shared network replaces a population)
+        if not layers:
+            check(self._L.clothhip_set_policy_mlp(self._h, 0, None, None, 0))
+            return
+        widths, blob = pack_mlp(layers)
+        check(self._L.clothhip_set_policy_mlp(self._h, len(widths) - 1, _lib.i32p(widths), blob.ctypes.data_as(C.POINTER(C.c_float)), blob.size))
+        self._mlp_n_params = int(blob.size)
+
+    def policy_eval(self, obs=None):
+        """The handle's network on float32 '1d' observations obs [n, 3P], or with obs=None on every env's present state: float64
+        [n, 4], the network's output before noise and clipping, computed by the device function the episode launch runs
+        (clothhip_policy_eval) -- the same bits."""
+        if obs is None:
+            n, ptr = self.E, None
+        else:
+            obs = np.ascontiguousarray(obs, dtype=np.float32)
+            if obs.ndim != 2 or obs.shape[1] != 3 * self.P:
+                raise ValueError("obs must have shape (n, %d)" % (3 * self.P))
+            n, ptr = obs.shape[0], obs.ctypes.data_as(C.POINTER(C.c_float))
+        out = np.zeros((n, 4), dtype=np.float64)
+        check(self._L.clothhip_policy_eval(self._h, ptr, n, _lib.dp(out)))
+        return out
+
+    def _member_map(self, member, rows):
+        """member as int32[E], checked against [0, rows): what the library would refuse is refused here first."""
+        m = np.asarray(member)
+        if m.shape != (self.E,):
+            raise ValueError("member must have shape (%d,) (got %r)" % (self.E, m.shape))
+        if not np.issubdtype(m.dtype, np.integer):
+            raise ValueError("member must hold integers")
+        if m.size and (m.min() < 0 or m.max() >= rows):
+            raise ValueError("member values must lie in [0, %d)" % rows)
+        return np.ascontiguousarray(m, dtype=np.int32)
+
+    def set_policy_population(self, members, member):
+        """A network per env slot (clothhip_set_policy_population): `members` is a list of G networks of ONE shape, each a list of (W, b)
+        layers as set_policy_mlp takes them, `member` int[E] with env e running members[member[e]]. None or [] clears the handle's
+        network. Replaces a shared network (and set_policy_mlp replaces a population). The networks belong to the env slots: resets and
+        uploads leave them alone; forks and snapshots do not carry them."""
+        self._pop_shape = None                     # (fit_grad_members sizes its result by it: (rows, n_params) of the population)
+        if not members:
+            check(self._L.clothhip_set_policy_population(self._h, 0, None, None, 0, None))
+            return
+        widths, blob = pack_population(members, n_in=3 * self.P)
+        m = self._member_map(member, blob.shape[0])
+        check(self._L.clothhip_set_policy_population(self._h, len(widths) - 1, _lib.i32p(widths), _lib.fp(blob), blob.shape[0], _lib.i32p(m)))
+        self._pop_shape = (int(blob.shape[0]), int(blob.shape[1]))
+
+    def set_policy_members(self, member):
+        """The map alone (clothhip_set_policy_members): member int[E], each below the population's number of rows."""
+        m = np.asarray(member)
+        if m.shape != (self.E,) or not np.issubdtype(m.dtype, np.integer):
+            raise ValueError("member must be %d integers" % self.E)
+        check(self._L.clothhip_set_policy_members(self._h, _lib.i32p(np.ascontiguousarray(m, dtype=np.int32))))
+
+    def get_policy_mlp(self, g, n_params):
+        """Blob g of the handle's population (g = 0: a shared network) as float32[n_params], downloaded (clothhip_get_policy_mlp). For a
+        population n_params may be the row stride (policies.population_stride): the row with its pad."""
+        out = np.zeros(int(n_params), dtype=np.float32)
+        check(self._L.clothhip_get_policy_mlp(self._h, int(g), _lib.fp(out), out.size))
+        return out
+
+    def policy_eval_members(self, obs, members):
+        """policy_eval with a network per row: row r under blob members[r] (clothhip_policy_eval_members); obs=None: every env's present
+        state, members int[E]. float64 [n, 4], the bits the episode launch computes for an env slot that runs that blob."""
+        m = np.ascontiguousarray(members, dtype=np.int32)
+        if obs is None:
+            n, ptr = self.E, None
+        else:
+            obs = np.ascontiguousarray(obs, dtype=np.float32)
+            if obs.ndim != 2 or obs.shape[1] != 3 * self.P:
+                raise ValueError("obs must have shape (n, %d)" % (3 * self.P))
+            n, ptr = obs.shape[0], _lib.fp(obs)
+        if m.shape != (n,):
+            raise ValueError("members must have shape (%d,)" % n)
+        out = np.zeros((n, 4), dtype=np.float64)
+        check(self._L.clothhip_policy_eval_members(self._h, ptr, n, _lib.i32p(m), _lib.dp(out)))
+        return out
+
+    def population_perturb(self, center_layers, n_members, sigma, seed, antithetic=True, member=None):
+        """G = n_members perturbed copies of one network made on the device (clothhip_policy_population_perturb;
+        csrc/cloth_policy_population.hpp defines the noise): rows 2k, 2k + 1 = theta +- sigma eps_k with antithetic=True (G even), else row
+        g = theta + sigma eps_g; row G = theta. member int[E] in [0, G], default e % (G + 1). sigma is rounded to float32; seed is an
+        integer in [0, 2^64). Returns (widths, n_params)."""
+        widths, blob = pack_mlp(center_layers, n_in=3 * self.P)
+        G = int(n_members)
+        if not 1 <= G <= _lib.POP_MAX_G:
+            raise ValueError("n_members = %d outside [1, %d]" % (G, _lib.POP_MAX_G))
+        if antithetic and G % 2:
+            raise ValueError("n_members = %d: antithetic perturbations come in pairs, n_members must be even" % G)
+        if not 0 <= int(seed) < 2 ** 64:
+            raise ValueError("seed must lie in [0, 2^64)")
+        if not np.isfinite(np.float32(sigma)):
+            raise ValueError("sigma is not finite")
+        m = self._member_map(np.arange(self.E) % (G + 1) if member is None else member, G + 1)
+        check(self._L.clothhip_policy_population_perturb(self._h, len(widths) - 1, _lib.i32p(widths), _lib.fp(blob), G, float(np.float32(sigma)),
+                                                         int(seed), _lib.POP_ANTITHETIC if antithetic else 0, _lib.i32p(m)))
+        self._pop_n_params = blob.size
+        self._pop_shape = (G + 1, int(blob.size))
+        return widths, blob.size
+
+    def population_combine(self, coef):
+        """float32[n_params] of the last population_perturb: sum_k coef[k] eps_k, accumulated in float64 in ascending k, eps made again on the device from the seed of
+        the last population_perturb (clothhip_policy_population_combine). len(coef) = G / 2 with antithetic, else G."""
+        c = np.ascontiguousarray(coef, dtype=np.float32)
+        if c.ndim != 1:
+            raise ValueError("coef must be one-dimensional")
+        out = np.zeros(getattr(self, '_pop_n_params', 0), dtype=np.float32)      # (set by the last perturb that succeeded: the one the library sums, or it refuses before it writes)
+        check(self._L.clothhip_policy_population_combine(self._h, _lib.fp(c), c.size, _lib.fp(out)))
+        return out

@@ -55,7 +55,8 @@ def collect_demos(env, policy='oracle_corner', max_episodes=10, slots_per_launch
     episodes = []
     E = env.E
     obs = env.reset()
-    from .policies import HighestPointPolicy, MLPEnsemble, MLPPolicy, MLPPopulation
+    from .policies import HighestPointPolicy, MLPPolicy, MLPPopulation
+    from .trainers import MLPEnsemble
     hp = policy if (on_device and isinstance(policy, HighestPointPolicy)) else None
     mlp = policy if (on_device and isinstance(policy, (MLPPolicy, MLPPopulation, MLPEnsemble))) else None
     if mlp is not None and not (isinstance(mlp, MLPEnsemble) and env._policy_mlp is mlp):      # (an ensemble on the env holds FITTED rows: an upload would undo the fit)

@@ -532,7 +532,8 @@ class ClothVecEnv(object):
         PER ENV SLOT there instead (its present generation, made on the device). Either way snapshot / restore, forks, the lookahead's
         scratch batch and resets neither carry nor touch networks. On several GPUs every rank sets it itself (dist.py broadcasts no
         weights)."""
-        from .policies import MLPEnsemble, MLPPopulation
+        from .policies import MLPPopulation
+        from .trainers import MLPEnsemble
         if isinstance(mlp, (MLPPopulation, MLPEnsemble)):      # (an MLPEnsemble: its G networks as uploaded rows, one per env slot)
             self._policy_mlp = None                # a failed upload leaves the batch without a network
             mlp._upload(self.batch)
@@ -540,7 +541,7 @@ class ClothVecEnv(object):
             return
         layers = None if mlp is None else getattr(mlp, 'layers', mlp)
         if layers:
-            from .policies import pack_mlp
+            from .mlp import pack_mlp
             pack_mlp(layers, n_in=3 * self.P)      # a malformed network is refused here and the earlier one stays ...
         self._policy_mlp = None                    # ... a failed upload leaves the batch without one (clothhip_set_policy_mlp)
         self.batch.set_policy_mlp(layers)
