@@ -143,6 +143,15 @@ PPO_STATS = 3                       # CLOTHHIP_PPO_STATS: loss, clip_fraction, k
 assert C.sizeof(ClothPpoParams) == 16
 
 
+class ClothPpoSigmaParams(C.Structure):
+    """clothhip_policy_fit_ppo_sigma*'s constants: the clip range epsilon, the coefficient of the entropy bonus (sigma is the handle's head)."""
+    _fields_ = [("clip", C.c_double), ("ent_coef", C.c_double)]
+
+
+PPO_SIGMA_STATS = 4                 # CLOTHHIP_PPO_SIGMA_STATS: loss, clip_fraction, kl, entropy
+assert C.sizeof(ClothPpoSigmaParams) == 16
+
+
 class ClothPlanParams(C.Structure):
     """clothhip_plan_cem's planner constants (clothhip.h: PLAN ACTIONS ON THE DEVICE)."""
     _fields_ = [("horizon", C.c_int32), ("n_candidates", C.c_int32), ("n_elite", C.c_int32), ("n_iters", C.c_int32),
@@ -237,6 +246,14 @@ SYMBOLS = [
     ("clothhip_fit_data_get_old_means", C.c_int, [_vp, C.c_int64, C.c_int64, C.POINTER(C.c_float)]),
     ("clothhip_policy_fit_ppo_grad", C.c_int, [_vp, C.POINTER(ClothPpoParams), _i32p, C.c_int32, C.POINTER(C.c_float), _dp, C.POINTER(C.c_float)]),
     ("clothhip_policy_fit_ppo", C.c_int, [_vp, C.POINTER(ClothFitParams), C.POINTER(ClothPpoParams), _i32p, C.c_int32, C.c_int32, _dp]),
+    ("clothhip_set_policy_log_sigma", C.c_int, [_vp, C.POINTER(C.c_float)]),
+    ("clothhip_get_policy_log_sigma", C.c_int, [_vp, C.POINTER(C.c_float)]),
+    ("clothhip_fit_data_set_old_log_sigma", C.c_int, [_vp, C.c_int64, C.c_int64, C.POINTER(C.c_float)]),
+    ("clothhip_fit_data_get_old_log_sigma", C.c_int, [_vp, C.c_int64, C.c_int64, C.POINTER(C.c_float)]),
+    ("clothhip_policy_fit_ppo_sigma_grad", C.c_int, [_vp, C.POINTER(ClothPpoSigmaParams), _i32p, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float), _dp,
+                                                     C.POINTER(C.c_float)]),
+    ("clothhip_policy_fit_ppo_sigma", C.c_int, [_vp, C.POINTER(ClothFitParams), C.POINTER(ClothPpoSigmaParams), _i32p, C.c_int32, C.c_int32, _dp,
+                                                C.POINTER(C.c_float)]),
     ("clothhip_plan_cem", C.c_int, [_vp, _vp, C.POINTER(ClothEpisodeParams), C.POINTER(ClothPlanParams), _i32p, _u8p, _dp, _dp, _dp, _dp,
                                     _dp, _dp]),
     ("clothhip_plan_sample", C.c_int, [_vp, C.POINTER(ClothPlanParams), _dp, _dp, C.c_int32, C.c_int32, _dp, _dp, _dp]),

@@ -447,3 +447,65 @@ class FitBindings(object):
         stats = np.zeros((ix.shape[0], _lib.PPO_STATS), dtype=np.float64)
         check(self._L.clothhip_policy_fit_ppo(self._h, p, C.byref(q), _lib.i32p(ix), ix.shape[0], ix.shape[1], _lib.dp(stats)))
         return stats
+
+    # ---- PPO with a learned sigma: the old log sigma and the surrogate over the handle's head (clothhip.h: PPO WITH A LEARNED SIGMA) ----
+    def fit_set_old_log_sigma(self, log_sigma, first=0):
+        """Write the old log sigma of the stored rows [first, first + len(log_sigma)) from the host
+        (clothhip_fit_data_set_old_log_sigma): log_sigma [n, 4], finite float32. (fit_snapshot_policy writes the present head on the
+        device when the batch has one.)"""
+        m = np.asarray(log_sigma, dtype=np.float64)
+        if m.ndim != 2 or m.shape[1] != 4:
+            raise ValueError("log_sigma must have shape (n, 4)")
+        if not (np.isfinite(m).all() and (np.abs(m) <= np.finfo(np.float32).max).all()):
+            raise ValueError("log_sigma must be finite (float32)")
+        m = np.ascontiguousarray(m, dtype=np.float32)
+        check(self._L.clothhip_fit_data_set_old_log_sigma(self._h, int(first), m.shape[0], _lib.fp(m)))
+
+    def fit_get_old_log_sigma(self, first=0, n=None):
+        """float32[n, 4]: the old log sigma of the stored rows [first, first + n), n=None: to the end
+        (clothhip_fit_data_get_old_log_sigma); zeros for a row that has none."""
+        first, n = self._fit_range(first, n)
+        ls = np.zeros((n, 4), dtype=np.float32)
+        check(self._L.clothhip_fit_data_get_old_log_sigma(self._h, first, n, _lib.fp(ls)))
+        return ls
+
+    @staticmethod
+    def _ppo_sigma_params(clip, ent_coef):
+        c, e = float(clip), float(ent_coef)
+        if not (np.isfinite(c) and 0.0 <= c < 1.0):
+            raise ValueError("clip = %r: the clip range lies in [0, 1)" % (clip,))
+        if not (np.isfinite(e) and e >= 0.0):
+            raise ValueError("ent_coef = %r: the entropy coefficient is finite and >= 0" % (ent_coef,))
+        return _lib.ClothPpoSigmaParams(c, e)
+
+    def fit_ppo_sigma_grad(self, idx, clip=0.2, ent_coef=0.0):
+        """(stats float64[4] = loss, clip_fraction, kl, entropy; grad float32[n_params] in the blob's layout; grad_ls float32[4], the
+        head's gradient; ratio float32[B]) of PPO's clipped surrogate minus ent_coef times the entropy, over the dataset rows idx [B]
+        at the present weights and the present head; nothing is updated (clothhip_policy_fit_ppo_sigma_grad). The policy is Gaussian
+        around the shared network's output with the standard deviation exp(head); every row needs an old mean and an old log sigma
+        (fit_snapshot_policy stores both). policies.ppo_sigma_reference is the float64 yardstick, policies.ppo_sigma_loss_reference the
+        kernel's arithmetic."""
+        ix = self._fit_idx(idx, 1)
+        q = self._ppo_sigma_params(clip, ent_coef)
+        grad = np.zeros(self._fit_n_params(), dtype=np.float32)
+        grad_ls = np.zeros(4, dtype=np.float32)
+        stats = np.zeros(_lib.PPO_SIGMA_STATS, dtype=np.float64)
+        ratio = np.zeros(ix.size, dtype=np.float32)
+        check(self._L.clothhip_policy_fit_ppo_sigma_grad(self._h, C.byref(q), _lib.i32p(ix), ix.size, _lib.fp(grad), _lib.fp(grad_ls), _lib.dp(stats),
+                                                         _lib.fp(ratio)))
+        return stats, grad, grad_ls, ratio
+
+    def fit_ppo_sigma(self, idx_table, clip=0.2, ent_coef=0.0, optimizer='adam', lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, momentum=0.0):
+        """fit_ppo with the learned head in the place of a fixed sigma (clothhip_policy_fit_ppo_sigma): n_steps optimizer steps on the
+        shared network AND on the head, step s on the dataset rows idx_table[s] (int [n_steps, B]). The network's optimizer is the
+        policy's (shared with fit and fit_ppo); the head has its own moments and step count under the same hyper-parameters
+        (fit_reset restarts both, set_policy_log_sigma the head's alone). Returns (float64[n_steps, 4]: each step's loss,
+        clip_fraction, kl, entropy; float32[n_steps, 4]: the head) -- both BEFORE that step's update."""
+        ix = self._fit_idx(idx_table, 2)
+        p = self._fit_params(dict(optimizer=optimizer, lr=lr, beta1=beta1, beta2=beta2, eps=eps, momentum=momentum), 1)
+        q = self._ppo_sigma_params(clip, ent_coef)
+        self._fit_n_params()
+        stats = np.zeros((ix.shape[0], _lib.PPO_SIGMA_STATS), dtype=np.float64)
+        heads = np.zeros((ix.shape[0], 4), dtype=np.float32)
+        check(self._L.clothhip_policy_fit_ppo_sigma(self._h, p, C.byref(q), _lib.i32p(ix), ix.shape[0], ix.shape[1], _lib.dp(stats), _lib.fp(heads)))
+        return stats, heads

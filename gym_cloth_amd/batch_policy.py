@@ -24,6 +24,27 @@ class PolicyBindings(object):
         check(self._L.clothhip_set_policy_mlp(self._h, len(widths) - 1, _lib.i32p(widths), blob.ctypes.data_as(C.POINTER(C.c_float)), blob.size))
         self._mlp_n_params = int(blob.size)
 
+    def set_policy_log_sigma(self, log_sigma):
+        """The head of a learned standard deviation (clothhip_set_policy_log_sigma): log_sigma [4] float32, one per action component,
+        finite and within [-10, 10]; None drops it. It lies beside the shared network (setting a network leaves it alone), no launch
+        reads it, fit_ppo_sigma trains it; setting it restarts the head's optimizer state and nothing else."""
+        if log_sigma is None:
+            check(self._L.clothhip_set_policy_log_sigma(self._h, None))
+            return
+        ls64 = np.asarray(log_sigma, dtype=np.float64)
+        if ls64.shape != (4,):
+            raise ValueError("log_sigma must have shape (4,) (got %r)" % (ls64.shape,))
+        if not (np.isfinite(ls64).all() and (np.abs(ls64) <= 10.0).all()):
+            raise ValueError("log_sigma must be finite and lie in [-10, 10] (got %r)" % (ls64.tolist(),))
+        ls = np.ascontiguousarray(ls64, dtype=np.float32)
+        check(self._L.clothhip_set_policy_log_sigma(self._h, _lib.fp(ls)))
+
+    def get_policy_log_sigma(self):
+        """float32[4]: the head as the device holds it now (clothhip_get_policy_log_sigma); ClothHipError without one."""
+        out = np.zeros(4, dtype=np.float32)
+        check(self._L.clothhip_get_policy_log_sigma(self._h, _lib.fp(out)))
+        return out
+
     def policy_eval(self, obs=None):
         """The handle's network on float32 '1d' observations obs [n, 3P], or with obs=None on every env's present state: float64
         [n, 4], the network's output before noise and clipping, computed by the device function the episode launch runs

@@ -1,4 +1,4 @@
-// api_fit.hip -- the supervised trainer of the handle's networks, policy and critic, over the dataset of api_fit_data.hip: the loss and its gradient over a minibatch, the optimizer steps, advantages from the critic's values, the snapshot of the old means and PPO's clipped surrogate.
+// api_fit.hip -- the supervised trainer of the handle's networks, policy and critic, over the dataset of api_fit_data.hip: the loss and its gradient over a minibatch, the optimizer steps, advantages from the critic's values, the snapshot of the old means (and, with a log-sigma head, of the old log sigma) and PPO's clipped surrogate under a fixed or a learned sigma.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -145,8 +145,16 @@ template <bool A_KC, bool B_KC, int EPI, bool ROWS> static void launch_gemm(hipS
 // [n_m][B] into d_loss [n_m] and h->fit.d_grad [n_m][n_params] (blob layout). d_loss NULL: the forward pass alone -- member j's y is
 // then at h->fit.d_act + j * p.act + p.h_off[L - 1]; shared_rows (the forward alone): d_idx is ONE list [B] that every member reads.
 // ppo (the policy's table only): the loss launch is k_fit_loss_ppo with these constants, d_loss is then [n_m][FIT_PPO_STATS] and
-// d_ratio (may be NULL) [n_m][B]; every other launch is the same
-struct FitPpo { double inv_s2, half_inv_s2, lo, hi; };
+// d_ratio (may be NULL) [n_m][B]; every other launch is the same. ppo->head: the loss launch is k_fit_loss_ppo_sigma, which reads the
+// handle's log-sigma head where it lies; d_loss is [n_m][FIT_PPO_SIGMA_STATS], the head's gradient goes to h->fit.d_grad_ls and the
+// head the launch read to ls_out (may be NULL)
+struct FitPpo {
+    double inv_s2, half_inv_s2, lo, hi;
+    bool head = false;
+    double ent_coef = 0.0;
+    float *ls_out = nullptr;
+    int stats() const { return head ? FIT_PPO_SIGMA_STATS : FIT_PPO_STATS; }
+};
 static int enqueue_grad(clothhip_handle *h, const FitNet &net, const FitPlan &p, int32_t n_m, const int32_t *d_idx, int32_t B, double *d_loss, bool shared_rows = false,
                         const FitPpo *ppo = nullptr, float *d_ratio = nullptr) {
     const MlpDesc &D = net.D;
@@ -170,7 +178,14 @@ static int enqueue_grad(clothhip_handle *h, const FitNet &net, const FitPlan &p,
         HIPCHECK(hipGetLastError());
     }
     if (!d_loss) return 0;
-    if (ppo) {
+    if (ppo && ppo->head) {
+        FitPpoSigmaArgs q = {};
+        q.y = act + p.h_off[L - 1]; q.lab = d.lab(); q.old = d.old(); q.old_ls = d.old_ls(); q.wgt = d.w(); q.ls = h->pol.d_log_sigma; q.rows = d_idx;
+        q.dz = dz[(L - 1) & 1]; q.ratio = d_ratio; q.grad_ls = f.d_grad_ls; q.ls_out = ppo->ls_out; q.stats = d_loss;
+        q.lo = ppo->lo; q.hi = ppo->hi; q.ent_coef = ppo->ent_coef;
+        q.y_step = (int64_t)p.act; q.dz_step = (int64_t)p.dz; q.rows_step = (int64_t)B; q.B = B;
+        hipLaunchKernelGGL(k_fit_loss_ppo_sigma, dim3((unsigned)n_m), dim3(256), 0, h->stream, q);
+    } else if (ppo) {
         FitPpoArgs q = {};
         q.y = act + p.h_off[L - 1]; q.lab = d.lab(); q.old = d.old(); q.wgt = d.w(); q.rows = d_idx; q.dz = dz[(L - 1) & 1]; q.ratio = d_ratio; q.stats = d_loss;
         q.inv_s2 = ppo->inv_s2; q.half_inv_s2 = ppo->half_inv_s2; q.lo = ppo->lo; q.hi = ppo->hi;
@@ -223,12 +238,13 @@ static int enqueue_grad(clothhip_handle *h, const FitNet &net, const FitPlan &p,
 // loss and gradient of `members` over idx [n_m][B], nothing updated; the call is valid. ppo: the clipped surrogate in the place of the
 // squared error, loss_out is then [n_m][FIT_PPO_STATS] and ratio_out (may be NULL) [n_m][B]
 static int run_grad(clothhip_handle *h, const FitNet &net, const int32_t *members, int32_t n_m, const int32_t *idx, int32_t B, float *grad_out, double *loss_out,
-                    const FitPpo *ppo = nullptr, float *ratio_out = nullptr) {
+                    const FitPpo *ppo = nullptr, float *ratio_out = nullptr, float *grad_ls_out = nullptr) {
     auto &f = h->fit;
     const FitPlan p = fit_plan(net, B);
-    const size_t n_loss = (size_t)n_m * (ppo ? FIT_PPO_STATS : 1);
+    const size_t n_loss = (size_t)n_m * (ppo ? ppo->stats() : 1);
     HIPCHECK(hipSetDevice(h->device));
     if (int rc = fit_reserve(h, p, n_m)) return rc;
+    if (ppo && ppo->head) if (int rc = f.d_grad_ls.reserve((size_t)n_m * MLP_OUT * 4)) return rc;
     if (int rc = f.d_idx.reserve((size_t)n_m * B * 4)) return rc;
     if (int rc = f.d_loss.reserve(n_loss * 8)) return rc;
     if (ratio_out) if (int rc = f.d_ratio.reserve((size_t)n_m * B * 4)) return rc;
@@ -241,6 +257,7 @@ static int run_grad(clothhip_handle *h, const FitNet &net, const int32_t *member
     if (grad_out) HIPCHECK(hipMemcpyAsync(grad_out, f.d_grad, (size_t)n_m * p.grad * 4, hipMemcpyDeviceToHost, h->stream));
     if (loss_out) HIPCHECK(hipMemcpyAsync(loss_out, f.d_loss, n_loss * 8, hipMemcpyDeviceToHost, h->stream));
     if (ratio_out) HIPCHECK(hipMemcpyAsync(ratio_out, f.d_ratio, (size_t)n_m * B * 4, hipMemcpyDeviceToHost, h->stream));
+    if (grad_ls_out) HIPCHECK(hipMemcpyAsync(grad_ls_out, f.d_grad_ls, (size_t)n_m * MLP_OUT * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(hipStreamSynchronize(h->stream));
     return 0;
 }
@@ -373,37 +390,57 @@ static int ensure_row_state(const FitNet &net) {
 }
 
 // n_steps optimizer steps of `members` with the optimizers p [n_m] over idx [n_steps][n_m][B]; the call is valid and n_steps >= 1.
-// ppo: every step's gradient is the clipped surrogate's, loss_out is then [n_steps][n_m][FIT_PPO_STATS]; the optimizer is the net's one
+// ppo: every step's gradient is the clipped surrogate's, loss_out is then [n_steps][n_m][ppo->stats()]; the optimizer is the net's one.
+// ppo->head (n_m == 1): the same optimizer kernel runs a second time per step over the log-sigma head, a table of one row of four
+// elements with its own state h->fit.opt_sigma and its own step constants (made from p[0]); ls_out (may be NULL) [n_steps][4] gets the
+// head before each step's update
 static int run_fit(clothhip_handle *h, const FitNet &net, const ClothFitParams *p, const int32_t *members, int32_t n_m, const int32_t *idx, int32_t n_steps,
-                   int32_t B, double *loss_out, const FitPpo *ppo = nullptr) {
+                   int32_t B, double *loss_out, const FitPpo *ppo = nullptr, float *ls_out = nullptr) {
     const bool adam = p[0].optimizer == (float)CLOTHHIP_FIT_ADAM;
     auto &f = h->fit;
     const MlpDesc &D = net.D;
     const FitPlan pl = fit_plan(net, B);
     const size_t n = net.n_params, stride = (size_t)D.stride, n_sm = (size_t)n_steps * n_m;
     const size_t n_moments = net.pop_rows ? (size_t)net.pop_rows * stride : n;
-    const size_t per_loss = ppo ? FIT_PPO_STATS : 1;
-    // the step constants of every (step, member), in double on the host, then rounded to float; nothing of the handle changes yet
+    const size_t per_loss = ppo ? ppo->stats() : 1;
+    const bool head = ppo && ppo->head;
+    OptState &os = h->fit.opt_sigma;
+    // the step constants of every (step, member), in double on the host, then rounded to float; nothing of the handle changes yet.
+    // With a head its n_steps rows follow the members' n_steps * n_m
+    const size_t n_hyper = (n_sm + (head ? (size_t)n_steps : 0)) * FIT_HYPER;
     std::vector<float> hyper;
-    try { hyper.assign(n_sm * FIT_HYPER, 0.0f); } catch (const std::bad_alloc &) { return fail(CLOTHHIP_ENOMEM, "out of host memory (%zu step constants)", n_sm * FIT_HYPER); }
+    try { hyper.assign(n_hyper, 0.0f); } catch (const std::bad_alloc &) { return fail(CLOTHHIP_ENOMEM, "out of host memory (%zu step constants)", n_hyper); }
     if (int rc = ensure_row_state(net)) return rc;
-    for (int s = 0; s < n_steps; s++)
-        for (int32_t j = 0; j < n_m; j++) {
-            float *q = hyper.data() + ((size_t)s * n_m + j) * FIT_HYPER;
-            const ClothFitParams &pj = p[j];
-            if (adam) {
-                const double b1 = (double)pj.beta1, b2 = (double)pj.beta2, t = (double)(net.opt.t[members[j]] + s + 1);
-                const double a_t = (double)pj.lr * std::sqrt(1.0 - std::pow(b2, t)) / (1.0 - std::pow(b1, t));
-                q[0] = (float)a_t; q[1] = pj.beta1; q[2] = (float)(1.0 - b1); q[3] = pj.beta2; q[4] = (float)(1.0 - b2); q[5] = pj.eps;
-            } else {
-                q[0] = pj.lr; q[1] = pj.momentum;
-            }
+    if (head && (os.t.size() != 1 || os.zero.size() != 1)) {
+        try { os.t.assign(1, 0); os.zero.assign(1, 1); } catch (const std::bad_alloc &) {
+            os.forget();
+            return fail(CLOTHHIP_ENOMEM, "out of host memory (the head's optimizer state)");
         }
+    }
+    auto step_constants = [adam](float *q, const ClothFitParams &pj, int64_t t1) {      // t1: the 1-based step count of this step
+        if (adam) {
+            const double b1 = (double)pj.beta1, b2 = (double)pj.beta2, t = (double)t1;
+            const double a_t = (double)pj.lr * std::sqrt(1.0 - std::pow(b2, t)) / (1.0 - std::pow(b1, t));
+            q[0] = (float)a_t; q[1] = pj.beta1; q[2] = (float)(1.0 - b1); q[3] = pj.beta2; q[4] = (float)(1.0 - b2); q[5] = pj.eps;
+        } else {
+            q[0] = pj.lr; q[1] = pj.momentum;
+        }
+    };
+    for (int s = 0; s < n_steps; s++) {
+        for (int32_t j = 0; j < n_m; j++) step_constants(hyper.data() + ((size_t)s * n_m + j) * FIT_HYPER, p[j], net.opt.t[members[j]] + s + 1);
+        if (head) step_constants(hyper.data() + (n_sm + s) * FIT_HYPER, p[0], os.t[0] + s + 1);
+    }
     HIPCHECK(hipSetDevice(h->device));
     if (int rc = fit_reserve(h, pl, n_m)) return rc;
     if (int rc = f.d_idx.reserve(n_sm * B * 4)) return rc;
     if (int rc = f.d_loss.reserve(n_sm * per_loss * 8)) return rc;
-    if (int rc = f.d_hyper.reserve(n_sm * FIT_HYPER * 4)) return rc;
+    if (int rc = f.d_hyper.reserve(n_hyper * 4)) return rc;
+    if (head) {
+        if (int rc = f.d_grad_ls.reserve(MLP_OUT * 4)) return rc;
+        if (int rc = f.d_ls_hist.reserve((size_t)n_steps * MLP_OUT * 4)) return rc;
+        if (int rc = os.m.reserve(MLP_OUT * 4)) return rc;
+        if (int rc = os.v.reserve(MLP_OUT * 4)) return rc;
+    }
     // the moments of the whole table. A table of another network's size holds no row's state (every row is flagged read-as-zeros by
     // OptState::forget when the network changes), so growing it loses nothing
     if (int rc = net.opt.m.reserve(n_moments * 4)) return rc;
@@ -418,24 +455,45 @@ static int run_fit(clothhip_handle *h, const FitNet &net, const ClothFitParams *
         }
         net.opt.t[g] += n_steps;
     }
+    if (head) {
+        if (os.zero[0]) {
+            HIPCHECK(hipMemsetAsync(os.m, 0, MLP_OUT * 4, h->stream));
+            HIPCHECK(hipMemsetAsync(os.v, 0, MLP_OUT * 4, h->stream));
+            os.zero[0] = 0;
+        }
+        os.t[0] += n_steps;
+    }
     HIPCHECK(hipMemcpyAsync(f.d_members, members, (size_t)n_m * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipMemcpyAsync(f.d_idx, idx, n_sm * B * 4, hipMemcpyHostToDevice, h->stream));
-    HIPCHECK(hipMemcpyAsync(f.d_hyper, hyper.data(), n_sm * FIT_HYPER * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipMemcpyAsync(f.d_hyper, hyper.data(), n_hyper * 4, hipMemcpyHostToDevice, h->stream));
     FitOptArgs o = {};
     o.theta = net.theta; o.m = net.opt.m; o.v = net.opt.v; o.g = f.d_grad; o.members = f.d_members;
     o.stride = (int64_t)stride; o.n = (int64_t)n; o.blocks = (int32_t)((n + 255) / 256);
     const dim3 ogrid((unsigned)o.blocks * (unsigned)n_m);
+    // the head as a table of one row (members = {0}, offset 0) of MLP_OUT elements
+    FitOptArgs oh = {};
+    FitPpo step_ppo;
+    if (ppo) step_ppo = *ppo;
+    if (head) { oh.theta = h->pol.d_log_sigma; oh.m = os.m; oh.v = os.v; oh.g = f.d_grad_ls; oh.members = f.d_members; oh.stride = 0; oh.n = MLP_OUT; oh.blocks = 1; }
     HIPCHECK(hipEventRecord(h->ev0, h->stream));
     for (int s = 0; s < n_steps; s++) {
-        if (int rc = enqueue_grad(h, net, pl, n_m, f.d_idx + (size_t)s * n_m * B, B, f.d_loss + (size_t)s * n_m * per_loss, false, ppo)) return rc;
+        if (head) step_ppo.ls_out = f.d_ls_hist + (size_t)s * MLP_OUT;
+        if (int rc = enqueue_grad(h, net, pl, n_m, f.d_idx + (size_t)s * n_m * B, B, f.d_loss + (size_t)s * n_m * per_loss, false, ppo ? &step_ppo : nullptr)) return rc;
         o.hyper = f.d_hyper + (size_t)s * n_m * FIT_HYPER;
         if (adam) hipLaunchKernelGGL(k_fit_adam, ogrid, dim3(256), 0, h->stream, o);
         else hipLaunchKernelGGL(k_fit_sgd, ogrid, dim3(256), 0, h->stream, o);
         HIPCHECK(hipGetLastError());
+        if (head) {
+            oh.hyper = f.d_hyper + (n_sm + (size_t)s) * FIT_HYPER;
+            if (adam) hipLaunchKernelGGL(k_fit_adam, dim3(1), dim3(256), 0, h->stream, oh);
+            else hipLaunchKernelGGL(k_fit_sgd, dim3(1), dim3(256), 0, h->stream, oh);
+            HIPCHECK(hipGetLastError());
+        }
     }
     HIPCHECK(hipEventRecord(h->ev1, h->stream));
     h->have_timing = true;
     if (loss_out) HIPCHECK(hipMemcpyAsync(loss_out, f.d_loss, n_sm * per_loss * 8, hipMemcpyDeviceToHost, h->stream));
+    if (head && ls_out) HIPCHECK(hipMemcpyAsync(ls_out, f.d_ls_hist, (size_t)n_steps * MLP_OUT * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(hipStreamSynchronize(h->stream));      // (the host tables are never retained)
     return 0;
 }
@@ -471,6 +529,7 @@ extern "C" int clothhip_policy_fit_reset(clothhip_handle *h) {
     if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
     if (int rc = check_idle(h)) return rc;
     h->fit.opt_policy.forget();
+    h->fit.opt_sigma.forget();      // the head is trained with the policy
     return 0;
 }
 
@@ -500,8 +559,16 @@ extern "C" int clothhip_fit_data_snapshot_policy(clothhip_handle *h, int64_t fir
     for (int64_t i = 0; i < n; i++) idx[(size_t)i] = (int32_t)(first + i);
     // the launches of clothhip_policy_fit_predict; each chunk's y goes to its rows of the column, which are consecutive
     if (int rc = enqueue_predict(h, policy_net(h), SHARED_ROW, 1, idx.data(), n, h->dataset.old() + (size_t)first * 4)) return rc;
+    // with a head: the present log sigma into the same rows of its column, on the device (the predict moved ev1 behind itself; so does this)
+    if (h->pol.has_log_sigma) {
+        const int64_t n4 = n * MLP_OUT;
+        hipLaunchKernelGGL(k_fit_fill_ls, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, h->stream, h->dataset.old_ls() + (size_t)first * MLP_OUT, (const float *)h->pol.d_log_sigma, n4);
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipEventRecord(h->ev1, h->stream));
+    }
     HIPCHECK(hipStreamSynchronize(h->stream));      // (idx, a host table the upload read, goes out of scope)
     h->dataset.mark_old_set(first, n);
+    if (h->pol.has_log_sigma) h->dataset.mark_old_ls_set(first, n);
     return 0;
 }
 
@@ -545,6 +612,62 @@ extern "C" int clothhip_policy_fit_ppo(clothhip_handle *h, const ClothFitParams 
     if (int rc = check_ppo(h, q, idx, (int64_t)n_steps * B, &ppo)) return rc;
     if (n_steps == 0) return 0;
     return run_fit(h, policy_net(h), p, SHARED_ROW, 1, idx, n_steps, B, stats_out, &ppo);
+}
+
+// ---- PPO with a learned sigma: one more loss mode, and the head as one more table of the optimizer (clothhip.h: PPO WITH A LEARNED SIGMA) ----
+static_assert(FIT_PPO_SIGMA_STATS == CLOTHHIP_PPO_SIGMA_STATS, "the statistics of the header and of the kernel");
+static_assert(sizeof(ClothPpoSigmaParams) == 16, "ClothPpoSigmaParams is two doubles");
+
+// the constants of such a call and the rows of its minibatches, after everything clothhip_policy_fit refuses: -> the kernel's constants
+static int check_ppo_sigma(const clothhip_handle *h, const ClothPpoSigmaParams *q, const int32_t *idx, int64_t n_idx, FitPpo *out) {
+    if (!std::isfinite(q->clip) || q->clip < 0.0 || q->clip >= 1.0) return fail(CLOTHHIP_EINVAL, "clip = %g: the clip range lies in [0, 1)", q->clip);
+    if (!std::isfinite(q->ent_coef) || q->ent_coef < 0.0) return fail(CLOTHHIP_EINVAL, "ent_coef = %g: the entropy coefficient is finite and >= 0", q->ent_coef);
+    *out = FitPpo{};
+    out->inv_s2 = 1.0; out->half_inv_s2 = 0.5;      // (not read: the kernel forms 1 / sigma^2 from the head)
+    out->lo = 1.0 - q->clip;
+    out->hi = 1.0 + q->clip;
+    out->head = true;
+    out->ent_coef = q->ent_coef;
+    for (int64_t i = 0; i < n_idx; i++) {
+        if (!h->dataset.h_old_set[(size_t)idx[i]])
+            return fail(CLOTHHIP_ESTATE, "idx[%lld] = row %d has no old mean: call clothhip_fit_data_snapshot_policy or clothhip_fit_data_set_old_means on it first",
+                        (long long)i, idx[i]);
+        if (!h->dataset.h_old_ls_set[(size_t)idx[i]])
+            return fail(CLOTHHIP_ESTATE, "idx[%lld] = row %d has no old log sigma: call clothhip_fit_data_snapshot_policy (with the head on the handle) or clothhip_fit_data_set_old_log_sigma on it first",
+                        (long long)i, idx[i]);
+    }
+    return 0;
+}
+static int check_head(const clothhip_handle *h) {
+    if (!h->pol.has_log_sigma) return fail(CLOTHHIP_ESTATE, "no log-sigma head on this handle: call clothhip_set_policy_log_sigma first");
+    return 0;
+}
+
+extern "C" int clothhip_policy_fit_ppo_sigma_grad(clothhip_handle *h, const ClothPpoSigmaParams *q, const int32_t *idx, int32_t B, float *grad_out, float *grad_ls_out,
+                                                  double *stats_out, float *ratio_out) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (!q) return fail(CLOTHHIP_EINVAL, "NULL argument");
+    if (int rc = check_fit_state(h, false)) return rc;
+    if (int rc = check_head(h)) return rc;
+    if (int rc = check_fit_rows(h, 1, idx, B, B)) return rc;
+    FitPpo ppo;
+    if (int rc = check_ppo_sigma(h, q, idx, B, &ppo)) return rc;
+    return run_grad(h, policy_net(h), SHARED_ROW, 1, idx, B, grad_out, stats_out, &ppo, ratio_out, grad_ls_out);
+}
+
+extern "C" int clothhip_policy_fit_ppo_sigma(clothhip_handle *h, const ClothFitParams *p, const ClothPpoSigmaParams *q, const int32_t *idx, int32_t n_steps, int32_t B,
+                                             double *stats_out, float *log_sigma_out) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (!p || !q) return fail(CLOTHHIP_EINVAL, "NULL argument");
+    if (n_steps < 0) return fail(CLOTHHIP_EINVAL, "n_steps < 0");
+    if (int rc = check_fit_state(h, false)) return rc;
+    if (int rc = check_head(h)) return rc;
+    if (int rc = check_fit_rows(h, 1, idx, (int64_t)n_steps * B, B)) return rc;
+    if (int rc = check_fit_params(p, -1)) return rc;
+    FitPpo ppo;
+    if (int rc = check_ppo_sigma(h, q, idx, (int64_t)n_steps * B, &ppo)) return rc;
+    if (n_steps == 0) return 0;
+    return run_fit(h, policy_net(h), p, SHARED_ROW, 1, idx, n_steps, B, stats_out, &ppo, log_sigma_out);
 }
 
 extern "C" int clothhip_selftest_exp_fixed(const double *x, int64_t n, double *out) {

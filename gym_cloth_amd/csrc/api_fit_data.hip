@@ -39,13 +39,14 @@ static int grow_dataset(clothhip_handle *h, int64_t n) {
 }
 
 // The n rows behind the ones that count get the defaults of every column that has one (reward 0, no successor: a leaf, value target 0,
-// old mean zeros), on the device, and the host mirrors theirs (no successor, old mean not set); enqueued, the caller synchronises before
+// old mean and old log sigma zeros), on the device, and the host mirrors theirs (no successor, neither old column set); enqueued, the caller synchronises before
 // the rows count. After grow_dataset.
 static int default_rows(clothhip_handle *h, int64_t n) {
     auto &d = h->dataset;
     try {
         d.h_next.resize((size_t)d.n); d.h_next.resize((size_t)(d.n + n), CLOTHHIP_FIT_NEXT_NONE);
         d.h_old_set.resize((size_t)d.n); d.h_old_set.resize((size_t)(d.n + n), 0);
+        d.h_old_ls_set.resize((size_t)d.n); d.h_old_ls_set.resize((size_t)(d.n + n), 0);
     } catch (const std::bad_alloc &) {
         return fail(CLOTHHIP_ENOMEM, "out of host memory (%lld rows)", (long long)(d.n + n));
     }
@@ -201,12 +202,23 @@ extern "C" int clothhip_fit_data_set_old_means(clothhip_handle *h, int64_t first
 // (an unset row holds zeros)
 extern "C" int clothhip_fit_data_get_old_means(clothhip_handle *h, int64_t first, int64_t n, float *mu) { return read_rows(h, first, n, {{COL_OLD, mu}}); }
 
+// ---- the old log sigma of PPO with a learned head (clothhip.h: PPO WITH A LEARNED SIGMA): the host route of the column ---------------------
+extern "C" int clothhip_fit_data_set_old_log_sigma(clothhip_handle *h, int64_t first, int64_t n, const float *ls) {
+    if (int rc = write_rows(h, first, n, {{COL_OLD_LS, ls}}, [=] { return check_finite(ls, n, 4, "ls"); })) return rc;
+    h->dataset.mark_old_ls_set(first, n);
+    return 0;
+}
+
+// (an unset row holds zeros)
+extern "C" int clothhip_fit_data_get_old_log_sigma(clothhip_handle *h, int64_t first, int64_t n, float *ls) { return read_rows(h, first, n, {{COL_OLD_LS, ls}}); }
+
 extern "C" int clothhip_fit_data_clear(clothhip_handle *h) {
     if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
     if (int rc = check_idle(h)) return rc;
     h->dataset.n = 0;
     h->dataset.h_next.clear();
     h->dataset.h_old_set.clear();
+    h->dataset.h_old_ls_set.clear();
     return 0;
 }
 

@@ -55,11 +55,11 @@ struct LaunchRecord {
 enum class LaunchTable { obs, reset_obs, labels, records };
 
 // The columns of the trainer's dataset (clothhip_handle::FitData), each a device table of 4-byte elements, float or int32: obs [3P], the
-// label [4], the loss weight, the reward, the value target, the successor row (or CLOTHHIP_FIT_NEXT_*) and PPO's old mean [4]. A column is
+// label [4], the loss weight, the reward, the value target, the successor row (or CLOTHHIP_FIT_NEXT_*), PPO's old mean [4] and its old log sigma [4]. A column is
 // described HERE and nowhere else: its width in elements per row (per_particle * P + fixed), and whether a new row gets a default -- the
 // 32-bit pattern `fill` -- or is written by every append. A new column is one enumerator plus one entry, plus whatever reads it: growth,
 // the defaults, clear and the range reader and writer of api_fit_data.hip are loops over this table and name no column.
-enum FitCol { COL_OBS, COL_LAB, COL_W, COL_REW, COL_RET, COL_NEXT, COL_OLD, FIT_COLS };
+enum FitCol { COL_OBS, COL_LAB, COL_W, COL_REW, COL_RET, COL_NEXT, COL_OLD, COL_OLD_LS, FIT_COLS };
 struct FitColDesc {
     int per_particle, fixed;
     bool defaulted;
@@ -74,6 +74,7 @@ constexpr FitColDesc FIT_COL[] = {
     {0, 1, true, 0},                                      // COL_RET: 0.0f
     {0, 1, true, (uint32_t)CLOTHHIP_FIT_NEXT_NONE},       // COL_NEXT: no successor, a leaf
     {0, 4, true, 0},                                      // COL_OLD: zeros, and not set (FitData::h_old_set)
+    {0, 4, true, 0},                                      // COL_OLD_LS: zeros, and not set (FitData::h_old_ls_set)
 };
 static_assert(sizeof(FIT_COL) / sizeof(FIT_COL[0]) == FIT_COLS, "one description per column");
 
@@ -187,6 +188,10 @@ struct clothhip_handle : HostPlan {
         uint64_t pop_seed = 0;
         float pop_sigma = 0.0f;
         int32_t pop_flags = 0;
+        // clothhip_set_policy_log_sigma: the head of a learned standard deviation, log_sigma[4] float32 BESIDE the blob (no blob layout knows
+        // it); setting or dropping a network leaves it alone, no launch reads it: the trainer's loss kernel and its optimizer do (api_fit.hip)
+        Buffer<float> d_log_sigma;
+        bool has_log_sigma = false;
     } pol;
     // The value network (api_policy.hip: clothhip_set_value_mlp), beside the policy and independent of it: n_layers 0: none; mlp.params =
     // d_mlp, no member map, stride 0 -- to the trainer (api_fit.hip) a weight table of ONE row. No launch evaluates it.
@@ -208,11 +213,14 @@ struct clothhip_handle : HostPlan {
         float *ret() const { return (float *)col[COL_RET]; }
         int32_t *next() const { return (int32_t *)col[COL_NEXT]; }
         float *old() const { return (float *)col[COL_OLD]; }
+        float *old_ls() const { return (float *)col[COL_OLD_LS]; }
         // host mirrors [n] that grow and clear with the rows: of `next`, against which clothhip_fit_data_gae checks a range without a
-        // download, and one byte per row: whether its old mean has been written -- against which clothhip_policy_fit_ppo* check a minibatch
+        // download, and one byte per row and old column: whether its old mean / its old log sigma has been written -- against which
+        // clothhip_policy_fit_ppo* (the first) and clothhip_policy_fit_ppo_sigma* (both) check a minibatch
         std::vector<int32_t> h_next;
-        std::vector<uint8_t> h_old_set;
+        std::vector<uint8_t> h_old_set, h_old_ls_set;
         void mark_old_set(int64_t first, int64_t rows) { std::fill(h_old_set.begin() + first, h_old_set.begin() + first + rows, (uint8_t)1); }
+        void mark_old_ls_set(int64_t first, int64_t rows) { std::fill(h_old_ls_set.begin() + first, h_old_ls_set.begin() + first + rows, (uint8_t)1); }
         // rows named by where they lie (clothhip_fit_hold, clothhip_fit_data_append_launch): held [E][3P], one row per env that outlives
         // the launch tables (held_valid: some clothhip_fit_hold has filled it); the gather's scratch: the index table of one call, its
         // not-finite flag and the weights of one clothhip_fit_data_append_launch_ex call, [n]
@@ -223,10 +231,12 @@ struct clothhip_handle : HostPlan {
     } dataset;
     // The trainer of the handle's networks (api_fit.hip: clothhip_policy_fit*, clothhip_value_*, clothhip_fit_data_gae, _snapshot_policy).
     // A new network of either kind (api_policy.hip's drop_network) restarts the policy's optimizer by opt_policy.forget(), a new value
-    // network the critic's by opt_value.forget(); nothing else outside api_fit.hip touches it.
+    // network the critic's by opt_value.forget(), clothhip_set_policy_log_sigma the head's by opt_sigma.forget(); nothing else outside
+    // api_fit.hip touches it.
     struct Fit {
-        // the two optimizers: the policy's, per row of its weight table, and the value network's of ONE row
-        OptState opt_policy, opt_value;
+        // the three optimizers: the policy's, per row of its weight table, the value network's of ONE row, and the one of the policy's
+        // log-sigma head, a table of one row of four elements
+        OptState opt_policy, opt_value, opt_sigma;
         // one step's scratch, sized on demand, one of each per member of the call: the index table, the hidden activations and y, the
         // two dZ tables, the split batch sums of a weight gradient, the gradient (blob layout), the losses; the call's member rows and
         // its table of per-member, per-step optimizer constants
@@ -235,6 +245,7 @@ struct clothhip_handle : HostPlan {
         Buffer<double> d_loss;
         Buffer<float> d_pred;        // clothhip_policy_fit_predict*: y of every member and row, [n_m][n][4]; clothhip_value_predict and clothhip_fit_data_gae: v [n]
         Buffer<float> d_ratio;       // clothhip_policy_fit_ppo_grad: (float)rho of the minibatch's rows, [B]
+        Buffer<float> d_grad_ls, d_ls_hist;      // clothhip_policy_fit_ppo_sigma*: the head's gradient [4]; the head before every step, [n_steps][4]
         // clothhip_fit_data_gae: A of every row of the range as a double, the advantages as floats, {mean, std} of the normalisation
         Buffer<double> d_gae_a, d_gae_stat;
         Buffer<float> d_adv;

@@ -56,6 +56,33 @@ extern "C" int clothhip_set_policy_mlp(clothhip_handle *h, int32_t n_layers, con
     return 0;
 }
 
+// ---- the log-sigma head (clothhip.h: PPO WITH A LEARNED SIGMA): four floats beside the blob, which no network entry above touches ---------
+extern "C" int clothhip_set_policy_log_sigma(clothhip_handle *h, const float *ls) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (int rc = check_idle(h)) return rc;
+    if (!ls) { h->pol.has_log_sigma = false; h->fit.opt_sigma.forget(); return 0; }
+    for (int k = 0; k < MLP_OUT; k++)
+        if (!std::isfinite(ls[k]) || std::fabs(ls[k]) > 10.0f) return fail(CLOTHHIP_EINVAL, "ls[%d] = %g: a log sigma is finite and lies in [-10, 10]", k, (double)ls[k]);
+    HIPCHECK(hipSetDevice(h->device));
+    if (int rc = h->pol.d_log_sigma.reserve(MLP_OUT * 4)) return rc;
+    HIPCHECK(hipMemcpyAsync(h->pol.d_log_sigma, ls, MLP_OUT * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));      // the host values are never retained
+    h->pol.has_log_sigma = true;
+    h->fit.opt_sigma.forget();                      // the head's moments belonged to the old values; the blob's optimizer is not touched
+    return 0;
+}
+
+extern "C" int clothhip_get_policy_log_sigma(clothhip_handle *h, float *out) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (int rc = check_idle(h)) return rc;
+    if (!h->pol.has_log_sigma) return fail(CLOTHHIP_ESTATE, "no log-sigma head on this handle: call clothhip_set_policy_log_sigma first");
+    if (!out) return fail(CLOTHHIP_EINVAL, "out is NULL");
+    HIPCHECK(hipSetDevice(h->device));
+    HIPCHECK(hipMemcpyAsync(out, h->pol.d_log_sigma, MLP_OUT * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
 // ---- the value network (clothhip.h: ACTOR-CRITIC FROM REWARD): the policy's shape rules with ONE output; the handle's other network ------------
 extern "C" int clothhip_set_value_mlp(clothhip_handle *h, int32_t n_layers, const int32_t *widths, const float *params, size_t n_params) {
     if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");

@@ -39,6 +39,9 @@
 //   * PPO's clipped surrogate (clothhip.h: PPO ON THE DEVICE) is one more loss launch of the policy's table, k_fit_loss_ppo in the place of
 //     k_fit_loss<4>: per row a probability ratio against the dataset's stored old mean through exp_fixed, dZ in double with one rounding
 //     to float32, three sums over ROWS in the order above; forward, backward and optimizer are the launches of the squared error;
+//   * PPO with a LEARNED sigma (clothhip.h: PPO WITH A LEARNED SIGMA) is one more loss launch again, k_fit_loss_ppo_sigma: the head
+//     log_sigma[4] read from device memory, the row's old log sigma beside its old mean, nine exp_fixed per row, seven sums over ROWS;
+//     the head is one more table of one row of four elements for k_fit_adam / k_fit_sgd, launched a second time per step;
 //   The forward's summation order differs from mlp_eval's (64 interleaved lane sums and a butterfly there), so the trainer's y need not equal
 //   clothhip_policy_eval's bits; the blob it writes is evaluated by mlp_eval as any uploaded blob is.
 #pragma once
@@ -316,6 +319,131 @@ __global__ __launch_bounds__(256) void k_fit_loss_ppo(FitPpoArgs a) {
         double *st = a.stats + j * FIT_PPO_STATS;
         st[0] = -red[0][0] / Bd; st[1] = red[1][0] / Bd; st[2] = red[2][0] / Bd;
     }
+}
+
+// PPO's clipped surrogate of a Gaussian policy whose log sigma is LEARNED (clothhip.h: PPO WITH A LEARNED SIGMA has the arithmetic
+// operation by operation): k_fit_loss_ppo's launch shape and row ownership, with the head ls[4] read from DEVICE memory (the steps of a
+// call are enqueued without a host round trip, and the optimizer moves the head between them) and the row's stored old log sigma
+// beside its old mean. Nine exp_fixed per row: 1 / sigma_old^2 and sigma_old^2 per component and the ratio; 1 / sigma^2 per component
+// once per thread. Seven sums in the house order: the surrogate, the rows not active, kl and the four row terms of the head's
+// gradient. stats[j] = {-sum surrogate / B - ent_coef H, not active / B, sum kl / B, H}; grad_ls[j][4] = (float)(-(sum h_k) / B -
+// ent_coef); ls_out (may be NULL) [n_m][4] gets the head this launch read; ratio as above. With ls == old log sigma == 0 every product
+// by inv / invo / so2 is a product by 1.0 and every (lo - ls) a +0.0: rho, dz and the first three statistics (ent_coef 0) are
+// k_fit_loss_ppo's bits at sigma = 1. Ordinary stores only.
+struct FitPpoSigmaArgs {
+    const float *y, *lab, *old, *old_ls, *wgt, *ls;
+    const int32_t *rows;
+    float *dz, *ratio, *grad_ls, *ls_out;
+    double *stats;
+    double lo, hi, ent_coef;                // 1 - eps, 1 + eps: formed once in double on the host
+    int64_t y_step, dz_step, rows_step;
+    int32_t B;
+};
+constexpr int FIT_PPO_SIGMA_STATS = 4;      // = CLOTHHIP_PPO_SIGMA_STATS
+constexpr int FIT_PPO_SIGMA_SUMS = 7;
+constexpr double FIT_ENTROPY_C = 5.675754132818691;      // 2 (1 + ln 2 pi): the entropy of four unit Gaussians
+
+__global__ __launch_bounds__(256) void k_fit_loss_ppo_sigma(FitPpoSigmaArgs a) {
+    __shared__ double red[FIT_PPO_SIGMA_SUMS][256];
+    const int64_t j = blockIdx.x;
+    const float *y = a.y + j * a.y_step;
+    float *dz = a.dz + j * a.dz_step;
+    const int32_t *rows = a.rows + j * a.rows_step;
+    const int tid = threadIdx.x;
+    const double Bd = (double)a.B;
+    double ls[4], inv[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        ls[k] = (double)a.ls[k];
+        const double m2 = -2.0 * ls[k];
+        inv[k] = exp_fixed(m2);
+    }
+    double s_sur = 0.0, s_clip = 0.0, s_kl = 0.0, s_h[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int r = tid; r < a.B; r += 256) {
+        const size_t row = (size_t)rows[r];
+        float mu[4], out[4];
+        __builtin_memcpy(mu, y + (size_t)4 * r, 16);
+        const float4 av = reinterpret_cast<const float4 *>(a.lab)[row], ov = reinterpret_cast<const float4 *>(a.old)[row];
+        const float4 lv = reinterpret_cast<const float4 *>(a.old_ls)[row];
+        const float act[4] = {av.x, av.y, av.z, av.w}, mo[4] = {ov.x, ov.y, ov.z, ov.w}, lo4[4] = {lv.x, lv.y, lv.z, lv.w};
+        double q = 0.0, klq = 0.0, kld = 0.0, t_new[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const double lo = (double)lo4[k];
+            const double m2 = -2.0 * lo, p2 = 2.0 * lo;
+            const double invo = exp_fixed(m2), so2 = exp_fixed(p2);
+            const double d_old = (double)act[k] - (double)mo[k], d_new = (double)act[k] - (double)mu[k];
+            const double sq_old = d_old * d_old, sq_new = d_new * d_new;
+            const double t_old = sq_old * invo;
+            t_new[k] = sq_new * inv[k];
+            const double t = t_old - t_new[k];
+            const double th = t * 0.5;
+            const double dl = lo - ls[k];
+            const double u = th + dl;
+            q = q + u;
+            const double e = (double)mu[k] - (double)mo[k];
+            const double ee = e * e;
+            const double c1 = so2 * inv[k], c2 = c1 - 1.0, c3 = ee * inv[k], c4 = c2 + c3;
+            klq = klq + c4;
+            const double dk = ls[k] - lo;
+            kld = kld + dk;
+        }
+        const double klh = klq * 0.5;
+        const double kl = kld + klh;
+        const double rho = exp_fixed(q);
+        const double A = (double)a.wgt[row];
+        const double s1 = rho * A;
+        double rc = rho < a.lo ? a.lo : rho;
+        rc = rc > a.hi ? a.hi : rc;
+        const double s2 = rc * A;
+        const bool active = s1 <= s2;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const double d = (double)mu[k] - (double)act[k];
+            const double g1 = s1 * d, g2 = g1 * inv[k], g3 = g2 / Bd;
+            out[k] = active ? (float)g3 : 0.0f;
+            const double m1 = t_new[k] - 1.0, hk = s1 * m1;
+            s_h[k] = s_h[k] + (active ? hk : 0.0);
+        }
+        __builtin_memcpy(dz + (size_t)4 * r, out, 16);
+        if (a.ratio) a.ratio[j * a.B + r] = (float)rho;
+        s_sur = s_sur + (active ? s1 : s2);
+        s_clip = s_clip + (active ? 0.0 : 1.0);
+        s_kl = s_kl + kl;
+    }
+    red[0][tid] = s_sur; red[1][tid] = s_clip; red[2][tid] = s_kl;
+#pragma unroll
+    for (int k = 0; k < 4; k++) red[3 + k][tid] = s_h[k];
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) {
+#pragma unroll
+            for (int i = 0; i < FIT_PPO_SIGMA_SUMS; i++) red[i][tid] = red[i][tid] + red[i][tid + o];
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        double hs = 0.0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) hs = hs + ls[k];
+        const double H = hs + FIT_ENTROPY_C;
+        const double l0 = -red[0][0] / Bd, eh = a.ent_coef * H;
+        double *st = a.stats + j * FIT_PPO_SIGMA_STATS;
+        st[0] = l0 - eh; st[1] = red[1][0] / Bd; st[2] = red[2][0] / Bd; st[3] = H;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const double g0 = -red[3 + k][0] / Bd, g = g0 - a.ent_coef;
+            a.grad_ls[j * 4 + k] = (float)g;
+            if (a.ls_out) a.ls_out[j * 4 + k] = a.ls[k];
+        }
+    }
+}
+
+// dst[i] = ls[i & 3], i < n4 (= 4 n): the present head into n consecutive rows of the dataset's old-log-sigma column
+// (clothhip_fit_data_snapshot_policy on a handle with a head)
+__global__ __launch_bounds__(256) void k_fit_fill_ls(float *dst, const float *ls, int64_t n4) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n4) dst[i] = ls[i & 3];
 }
 
 // The optimizers: member j updates row members[j] of theta, m, v ([rows][stride]) from g + j * n with ITS OWN step constants

@@ -535,8 +535,8 @@ def actor_critic_fit(env, trainer, critic, col, gamma=0.99, lam=0.95, n_value_st
     return {'adv': adv, 'ret': ret, 'value_losses': vl, 'policy_losses': pl, 'rows': trainer.size()}
 
 
-def ppo_fit(env, trainer, critic, col, sigma, gamma=0.99, lam=0.95, clip=0.2, n_value_steps=100, n_epochs=10, batch_size=64, seed=0,
-            target_kl=None, normalize=True):
+def ppo_fit(env, trainer, critic, col, sigma=None, gamma=0.99, lam=0.95, clip=0.2, n_value_steps=100, n_epochs=10, batch_size=64, seed=0,
+            target_kl=None, normalize=True, ent_coef=0.0):
     """The refit after actor_critic_collect with PPO's clipped surrogate in the place of actor_critic_fit's weighted regression, on the
     device: ONE fit_gae call over the rows `col` added writes their value targets and, as loss weights with w_scale = 1, their
     advantages (normalised over the non-leaf rows with normalize; a leaf gets 0); ONE trainer.snapshot_old over the same rows stores
@@ -546,7 +546,11 @@ def ppo_fit(env, trainer, critic, col, sigma, gamma=0.99, lam=0.95, clip=0.2, n_
     advantage, many epochs on one collection stay bounded where actor_critic_fit's steps diverge. sigma is the standard deviation of
     the policy_noise the collection ACTED with -- the caller's number: the launch draws the noise, the library does not record it, and
     a wrong sigma gives wrong ratios. Returns dict(adv, ret float32[n]: fit_gae's, value_losses float64, ppo_stats float64[steps, 3]:
-    loss, clip_fraction, kl of every policy step before its update, epochs: the epochs run, rows)."""
+    loss, clip_fraction, kl of every policy step before its update, epochs: the epochs run, rows).
+    sigma=None: the trainer's LEARNED head (MLPTrainer.set_log_sigma; the collection acted with trainer.sigma()): the one snapshot
+    stores the old means and the old log sigmas, the policy steps train network and head on the surrogate minus ent_coef times the
+    entropy; ppo_stats is float64[steps, 4] (the entropy last) and the dict also holds log_sigma float32[steps, 4], the head before
+    every step, and log_sigma_after float32[4]."""
     if trainer.env is not env or critic.env is not env:
         raise ValueError("the trainer or the critic belongs to another env")
     n = int(col['appended']) + int(col['open_rows'])
@@ -557,5 +561,12 @@ def ppo_fit(env, trainer, critic, col, sigma, gamma=0.99, lam=0.95, clip=0.2, n_
     rows = np.nonzero(nxt != FIT_NEXT_NONE)[0]
     vl = critic.step(n_value_steps, batch_size, seed, rows=rows) if len(rows) else np.zeros(0)
     mine = np.asarray(col['nonleaf'], dtype=np.int64)
-    stats, epochs = trainer.ppo_step(n_epochs, batch_size, seed, sigma, clip=clip, target_kl=target_kl, rows=mine) if len(mine) else (np.zeros((0, 3)), 0)
-    return {'adv': adv, 'ret': ret, 'value_losses': vl, 'ppo_stats': stats, 'epochs': epochs, 'rows': trainer.size()}
+    if len(mine):
+        stats, epochs = trainer.ppo_step(n_epochs, batch_size, seed, sigma, clip=clip, target_kl=target_kl, rows=mine, ent_coef=ent_coef)
+    else:
+        stats, epochs = np.zeros((0, 3 if sigma is not None else 4)), 0
+    out = {'adv': adv, 'ret': ret, 'value_losses': vl, 'ppo_stats': stats, 'epochs': epochs, 'rows': trainer.size()}
+    if sigma is None:
+        out['log_sigma'] = trainer.last_log_sigma if len(mine) else np.zeros((0, 4), dtype=np.float32)
+        out['log_sigma_after'] = trainer.log_sigma()
+    return out

@@ -29,7 +29,8 @@ import numpy as np
 from .mlp import MLP_MAX_LAYERS, MLP_MAX_WIDTH, mlp_float64, mlp_forward, pack_mlp, pack_population, population_stride, unpack_mlp  # noqa: F401
 from .references import (NEXT_NONE, NEXT_TERMINAL, _house_sum, _plan_clip, adam_reference, cem_reference, exp_fixed_reference,  # noqa: F401
                          fit_reference, gae_reference, philox4x32_10, philox_eps, plan_refit_reference, plan_sample_reference,
-                         plan_score_reference, ppo_loss_reference, ppo_reference, sgd_reference, value_fit_reference)
+                         plan_score_reference, ppo_loss_reference, ppo_reference, ppo_sigma_loss_reference, ppo_sigma_reference, sgd_reference,
+                         value_fit_reference)
 from .trainers import MLPEnsemble, MLPTrainer, ValueTrainer, ensemble_disagreement  # noqa: F401
 
 
@@ -176,14 +177,20 @@ class MLPPolicy(object):
     the episode launch runs, so that ClothVecEnv.step(policy.get_action(obs)) and step_many(policy='mlp') compute the same bits;
     reference(obs) is a float64 numpy evaluation of the same float32 weights, for tests. noise_std > 0 adds N(0, noise_std^2)
     exploration noise to every action component, drawn from one RandomState(seed + e) per env: draw(e) is the next [4] of env e, which
-    collect_demos(on_device=True) hands to the launch slot by slot (step_many(policy_noise=...)). The constructor uploads the network
+    collect_demos(on_device=True) hands to the launch slot by slot (step_many(policy_noise=...)). noise_std may be a length-4 vector,
+    one standard deviation per action component (MLPTrainer.sigma() of a learned head): the unit draws are those of a scalar, scaled
+    per component, and the policy is noisy when any component is > 0. The constructor uploads the network
     to env's batch (ClothVecEnv.set_policy); on several GPUs every rank does so itself."""
 
     def __init__(self, env, layers, noise_std=0.0, seed=0):
         self.env = env
         self.layers = [(np.ascontiguousarray(W, dtype=np.float32), np.ascontiguousarray(b, dtype=np.float32)) for W, b in layers]
         self.widths, self._blob = pack_mlp(self.layers, n_in=3 * env.P)
-        self.noise_std = float(noise_std)
+        std = np.asarray(noise_std, dtype=np.float64)
+        if std.shape not in ((), (4,)) or not np.isfinite(std).all() or (std < 0.0).any():
+            raise ValueError("noise_std must be a finite scalar or 4 values >= 0 (got %r)" % (noise_std,))
+        self.noise_std = float(std) if std.ndim == 0 else float(std.max())      # (what collect_demos asks: is there noise at all)
+        self._noise_scale = self.noise_std if std.ndim == 0 else std.copy()
         self.rngs = [np.random.RandomState(seed + e) for e in range(env.E)]
         env.set_policy(self)
 
@@ -200,7 +207,7 @@ class MLPPolicy(object):
         """The next noise vector [4] of env e (zeros without noise; the stream then does not advance)."""
         if self.noise_std <= 0.0:
             return np.zeros(4)
-        return self.rngs[e].normal(size=4) * self.noise_std
+        return self.rngs[e].normal(size=4) * self._noise_scale
 
     def get_action(self, obs, t=0):
         E = self.env.E

@@ -1,6 +1,6 @@
 """The numpy restatements the GPU tests pin the device to, and that a user can check a fit against: the trainer's three objectives in
-float64 over the one pass of mlp.py (fit_reference, value_fit_reference, ppo_reference), and what the device computes restated operation
-by operation, bit for bit (gae_reference, exp_fixed_reference, ppo_loss_reference, adam_reference, sgd_reference, Philox and the
+float64 over the one pass of mlp.py (fit_reference, value_fit_reference, ppo_reference, ppo_sigma_reference), and what the device computes
+restated operation by operation, bit for bit (gae_reference, exp_fixed_reference, ppo_loss_reference, ppo_sigma_loss_reference, adam_reference, sgd_reference, Philox and the
 cross-entropy planner's sampling, scoring and refit). numpy and math only; nothing here touches the library."""
 import math
 
@@ -184,6 +184,81 @@ def ppo_reference(layers, obs, actions, old, adv, idx, sigma, clip):
     stats = (float(-np.where(active, s1, s2).sum() / B), float((~active).sum() / float(B)), float((((mu - mo) ** 2).sum(axis=1) * (0.5 * inv_s2)).sum() / B))
     g = np.where(active[:, None], (s1[:, None] * (mu - a)) * inv_s2 / B, 0.0)
     return stats, mlp_backward(Ws, hs, g), rho, active
+
+
+ENTROPY_C = 5.675754132818691          # 2 (1 + ln 2 pi): the entropy of four unit Gaussians (csrc/cloth_policy_fit.hpp FIT_ENTROPY_C)
+
+
+def ppo_sigma_loss_reference(y, actions, old, old_ls, adv, ls, clip, ent_coef, B):
+    """k_fit_loss_ppo_sigma restated in float64 numpy from a given float32 y, bit for bit, reduction order included (include/clothhip.h:
+    PPO WITH A LEARNED SIGMA): y, actions, old, old_ls [B, 4] and adv [B] are the minibatch's rows in order (the network's output, the
+    stored labels, old means, old log sigmas and weights), ls [4] the head, all float32. Returns (stats float64[4] = loss,
+    clip_fraction, kl, entropy; dz float32[B, 4]; grad_ls float32[4]; ratio float32[B]; active bool[B])."""
+    f64 = lambda v: np.asarray(v, dtype=np.float32).astype(np.float64)
+    mu, a, mo, lo, A = f64(y).reshape(-1, 4), f64(actions).reshape(-1, 4), f64(old).reshape(-1, 4), f64(old_ls).reshape(-1, 4), f64(adv).reshape(-1)
+    lsd = f64(ls).reshape(4)
+    if not (len(mu) == len(a) == len(mo) == len(lo) == len(A) == int(B)):
+        raise ValueError("y, actions, old, old_ls [B, 4] and adv [B] must hold the B rows of the minibatch")
+    lo_c, hi_c, Bd, ent = 1.0 - float(clip), 1.0 + float(clip), float(int(B)), float(ent_coef)
+    inv = exp_fixed_reference(-2.0 * lsd)
+    q, klq, kld = np.zeros(len(A)), np.zeros(len(A)), np.zeros(len(A))
+    t_new = np.zeros_like(mu)
+    for k in range(4):
+        invo, so2 = exp_fixed_reference(-2.0 * lo[:, k]), exp_fixed_reference(2.0 * lo[:, k])
+        d_old, d_new, e = a[:, k] - mo[:, k], a[:, k] - mu[:, k], mu[:, k] - mo[:, k]
+        t_old = (d_old * d_old) * invo
+        t_new[:, k] = (d_new * d_new) * inv[k]
+        q = q + (((t_old - t_new[:, k]) * 0.5) + (lo[:, k] - lsd[k]))
+        klq = klq + (((so2 * inv[k]) - 1.0) + ((e * e) * inv[k]))
+        kld = kld + (lsd[k] - lo[:, k])
+    kl = kld + klq * 0.5
+    rho = exp_fixed_reference(q)
+    s1, s2 = rho * A, np.minimum(np.maximum(rho, lo_c), hi_c) * A
+    active = s1 <= s2
+    with np.errstate(over='ignore'):
+        dz = np.where(active[:, None], (((s1[:, None] * (mu - a)) * inv[None, :]) / Bd).astype(np.float32), np.float32(0.0)).astype(np.float32)
+    hk = np.where(active[:, None], s1[:, None] * (t_new - 1.0), 0.0)
+    hs = 0.0
+    for k in range(4):
+        hs = hs + lsd[k]
+    H = hs + ENTROPY_C
+    stats = np.array([(-_house_sum(np.where(active, s1, s2)) / Bd) - (ent * H), _house_sum(np.where(active, 0.0, 1.0)) / Bd, _house_sum(kl) / Bd, H])
+    with np.errstate(over='ignore'):
+        grad_ls = np.array([(-_house_sum(hk[:, k]) / Bd) - ent for k in range(4)]).astype(np.float32)
+    return stats, dz, grad_ls, rho.astype(np.float32), active
+
+
+def ppo_sigma_reference(layers, obs, actions, old, old_ls, adv, idx, ls, clip, ent_coef=0.0):
+    """Pure-numpy float64 loss and gradients of PPO's clipped surrogate for a Gaussian policy whose mean is the network's output and
+    whose standard deviation is exp(ls), ls [4] a state-independent head, minus ent_coef times the policy's entropy; beside
+    ppo_reference and with its conventions (obs [n, in], actions, old, old_ls [n, 4] the old means and old log sigmas, adv [n], all
+    rounded to float32 first, as is ls; idx [B] the minibatch; math.exp):
+        log rho_r = sum_k [ ((a - mo)^2 exp(-2 lo) - (a - mu)^2 exp(-2 ls)) / 2 + (lo - ls) ]      (clamped to [-40, 40])
+        L = -1 / B sum_r min(rho_r A_r, clip(rho_r, 1 - eps, 1 + eps) A_r) - ent_coef H,   H = sum_k ls_k + 2 (1 + ln 2 pi),
+    a row ACTIVE when rho A <= clip(rho) A; on active rows dL/dmu_rk = A rho (mu_rk - a_rk) exp(-2 ls_k) / B and the row adds
+    -A rho ((a - mu)^2 exp(-2 ls_k) - 1) / B to dL/dls_k, which also gets -ent_coef. kl = 1 / B sum_r KL(old || new) of the two diagonal
+    Gaussians. Returns (stats = (loss, clip_fraction, kl, H), [(dW, db), ...], grad_ls float64[4], rho float64[B], active bool[B])."""
+    ix = np.asarray(idx, dtype=np.int64).reshape(-1)
+    Ws, bs = mlp_float64(layers)
+    f64 = lambda v: np.asarray(v, dtype=np.float64).astype(np.float32).astype(np.float64)
+    x, a, mo, lo, A = f64(obs)[ix], f64(actions)[ix], f64(old)[ix], f64(old_ls)[ix], f64(adv).reshape(-1)[ix]
+    lsd = f64(ls).reshape(4)
+    B = len(ix)
+    hs = mlp_forward(Ws, bs, x)
+    mu = hs[-1]
+    exp = np.vectorize(math.exp, otypes=[np.float64])      # ONE exponential for the head and the old heads: equal inputs, equal values
+    inv, invo = exp(-2.0 * lsd), exp(-2.0 * lo)
+    t_new = (a - mu) ** 2 * inv
+    q = ((((a - mo) ** 2) * invo - t_new) / 2.0 + (lo - lsd)).sum(axis=1)
+    rho = np.array([math.exp(min(max(v, -40.0), 40.0)) for v in q])
+    s1, s2 = rho * A, np.clip(rho, 1.0 - float(clip), 1.0 + float(clip)) * A
+    active = s1 <= s2
+    H = float(lsd.sum() + 2.0 * (1.0 + math.log(2.0 * math.pi)))
+    kl = ((lsd - lo) + ((exp(2.0 * lo) + (mu - mo) ** 2) * inv - 1.0) / 2.0).sum(axis=1)
+    stats = (float(-np.where(active, s1, s2).sum() / B - float(ent_coef) * H), float((~active).sum() / float(B)), float(kl.sum() / B), H)
+    g = np.where(active[:, None], (s1[:, None] * (mu - a)) * inv / B, 0.0)
+    grad_ls = -np.where(active[:, None], s1[:, None] * (t_new - 1.0), 0.0).sum(axis=0) / B - float(ent_coef)
+    return stats, mlp_backward(Ws, hs, g), grad_ls, rho, active
 
 
 def adam_reference(theta, m, v, g, t, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8):

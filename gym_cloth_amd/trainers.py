@@ -108,7 +108,8 @@ class MLPTrainer(_EnvDataset):
     def snapshot_old(self, first=0, n=None):
         """Store the network's present output on the dataset rows [first, first + n) (n=None: to the end) as their OLD MEANS, on the
         device (ClothBatch.fit_snapshot_policy): what ppo_step's probability ratios are taken against. Call it after a collection and
-        before the first policy step on it."""
+        before the first policy step on it. With a head on the batch (set_log_sigma) the same call stores the present head as the
+        rows' OLD LOG SIGMA."""
         self.env.batch.fit_snapshot_policy(first, n)
 
     @staticmethod
@@ -123,26 +124,51 @@ class MLPTrainer(_EnvDataset):
         r = np.random.RandomState(seed)
         return [rows[r.permutation(m)][:(m // B) * B].reshape(m // B, B).astype(np.int32) for _ in range(int(n_epochs))]
 
-    def ppo_step(self, n_epochs, batch_size, seed, sigma, clip=0.2, target_kl=None, rows=None):
+    def set_log_sigma(self, log_sigma):
+        """Put a head of a learned standard deviation on the env's batch (ClothBatch.set_policy_log_sigma): log_sigma [4] or a scalar
+        for all four components; None drops it. Restarts the head's optimizer state alone."""
+        self.env.batch.set_policy_log_sigma(None if log_sigma is None else np.broadcast_to(np.asarray(log_sigma, dtype=np.float64), (4,)))
+
+    def log_sigma(self):
+        """float32[4]: the head as the device holds it now, by download."""
+        return self.env.batch.get_policy_log_sigma()
+
+    def sigma(self):
+        """float64[4]: exp(log_sigma()) -- the per-component standard deviation a collection acts with (MLPPolicy(noise_std=...), or
+        unit noise times it as step_many's policy_noise)."""
+        return np.exp(self.log_sigma().astype(np.float64))
+
+    def ppo_step(self, n_epochs, batch_size, seed, sigma=None, clip=0.2, target_kl=None, rows=None, ent_coef=0.0):
         """PPO on the device (ClothBatch.fit_ppo): up to n_epochs epochs over `rows` (int [m] dataset rows, None: all), each the
         minibatches of ppo_epoch_tables in ONE fit_ppo call -- optimizer steps on the clipped surrogate with the advantages in the
         weight column and the old means of snapshot_old, under this trainer's optimizer (shared with step). sigma is the standard
         deviation of the noise the rows' actions were drawn with, clip the range epsilon. With target_kl the loop stops after the first
         epoch whose mean kl exceeds it. Returns (stats float64[steps, 3]: loss, clip_fraction, kl of every step before its update;
-        epochs run)."""
+        epochs run).
+        sigma=None: the LEARNED head (set_log_sigma) in the place of a number -- ClothBatch.fit_ppo_sigma trains the network and the
+        head on the surrogate minus ent_coef times the entropy, against the old means AND old log sigmas of snapshot_old; stats is then
+        float64[steps, 4] (loss, clip_fraction, kl, entropy) and self.last_log_sigma float32[steps, 4] the head before every step."""
         if rows is None:
             n = self.size()
             if n < 1:
                 raise ValueError("the dataset is empty: append first")
             rows = np.arange(n)
-        out, epochs = [], 0
+        if sigma is not None and float(ent_coef) != 0.0:
+            raise ValueError("ent_coef belongs to the learned head: pass sigma=None")
+        out, heads, epochs = [], [], 0
         for table in self.ppo_epoch_tables(rows, n_epochs, batch_size, seed):
-            stats = self.env.batch.fit_ppo(table, sigma, clip, **self.hyper)
+            if sigma is None:
+                stats, ls = self.env.batch.fit_ppo_sigma(table, clip, ent_coef, **self.hyper)
+                heads.append(ls)
+            else:
+                stats = self.env.batch.fit_ppo(table, sigma, clip, **self.hyper)
             out.append(stats)
             epochs += 1
             if target_kl is not None and float(np.mean(stats[:, 2])) > float(target_kl):
                 break
-        return (np.concatenate(out) if out else np.zeros((0, 3))), epochs
+        if sigma is None:
+            self.last_log_sigma = np.concatenate(heads) if heads else np.zeros((0, 4), dtype=np.float32)
+        return (np.concatenate(out) if out else np.zeros((0, 3 if sigma is not None else 4))), epochs
 
     def layers(self):
         """The network as the device holds it now: [(W, b), ...] float32, by download (clothhip_get_policy_mlp)."""

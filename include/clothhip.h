@@ -715,6 +715,57 @@ int clothhip_fit_data_get_old_means(clothhip_handle *h, int64_t first, int64_t n
 int clothhip_policy_fit_ppo_grad(clothhip_handle *h, const ClothPpoParams *q, const int32_t *idx, int32_t B, float *grad_out, double *stats_out, float *ratio_out);
 int clothhip_policy_fit_ppo(clothhip_handle *h, const ClothFitParams *p, const ClothPpoParams *q, const int32_t *idx, int32_t n_steps, int32_t B, double *stats_out);
 
+/* PPO WITH A LEARNED SIGMA (additive, ABI 7; no reference counterpart): the policy above with a state-independent
+ * log sigma per action component that the same surrogate trains, and an entropy bonus that keeps it from collapsing. Every entry
+ * above keeps its bytes; a handle that never calls an entry below behaves as before.
+ * THE HEAD is log_sigma[4] float32 on the handle, beside the shared network's blob and not in it (the blob layout, n_params and
+ * clothhip_get_policy_mlp are unchanged). clothhip_set_policy_log_sigma sets it (ls == NULL drops it) and restarts the head's
+ * optimizer state, and that alone; CLOTHHIP_EINVAL for a value that is not finite or |ls_k| > 10, CLOTHHIP_ESTATE with a launch in
+ * flight. clothhip_get_policy_log_sigma downloads it (CLOTHHIP_ESTATE without a head). Setting or dropping a network or a population
+ * leaves the head's values alone; clothhip_fork and snapshots do not carry it (they carry no network either). NO EPISODE LAUNCH READS
+ * IT: the action stays y + noise[t][e], and the caller scales unit noise by exp(log_sigma) on the host.
+ * THE OLD LOG SIGMA is a sixth column of the dataset, old_ls[n][4] float32, default zeros, with its own byte per row on the handle: a
+ * row appended by any entry has none. On a handle WITH a head clothhip_fit_data_snapshot_policy also writes the present head into the
+ * rows of its range (a fill on the device, nothing downloaded) and marks them; without a head it does exactly what it did.
+ * clothhip_fit_data_set_old_log_sigma / _get_old_log_sigma are the host route, refused as clothhip_fit_data_set_old_means is.
+ * THE LOSS over a minibatch of B rows: ls the head, lo the row's old log sigma, mu = y, mo, a, A as above; lo_c = 1 - clip,
+ * hi_c = 1 + clip formed once in double on the host. Every operation ONE double rounding on the (double) of the float32 values, no
+ * contraction; the only exponential is exp_fixed. Once per launch: inv_k = exp_fixed(-2 ls_k). Per row:
+ *   for k = 0 .. 3: invo_k = exp_fixed(-2 lo_k);  so2_k = exp_fixed(2 lo_k);
+ *     t_old = ((a_k - mo_k) (a_k - mo_k)) invo_k;  t_new_k = ((a_k - mu_k) (a_k - mu_k)) inv_k;
+ *     q = q + (((t_old - t_new_k) 0.5) + (lo_k - ls_k))                                   (q = 0 before k = 0)
+ *     klq = klq + (((so2_k inv_k) - 1) + (((mu_k - mo_k) (mu_k - mo_k)) inv_k));  kld = kld + (ls_k - lo_k)      (both 0 before k = 0)
+ *   kl_row = kld + (klq 0.5)            KL(old || new) of the two diagonal Gaussians
+ *   rho = exp_fixed(q);  s1 = rho A;  s2 = min(max(rho, lo_c), hi_c) A;  active = s1 <= s2
+ *   dz_k = active ? (float)((((s1 (mu_k - a_k)) inv_k) / (double)B) : 0.0f
+ *   h_k = active ? s1 (t_new_k - 1) : 0            the row's term of d(s1) / d ls_k
+ *   surrogate = active ? s1 : s2
+ * Seven sums over the rows in the order above (thread t of 256 its rows t, t + 256, ... ascending, then a halving tree each): the
+ * surrogate, the rows not active, kl_row and the four h_k. With hs = ((ls_0 + ls_1) + ls_2) + ls_3 (from 0) the entropy is
+ * H = hs + 5.675754132818691 (= 2 (1 + ln 2 pi)), and
+ *   stats[0] = (-(sum surrogate) / B) - (ent_coef H);  stats[1] = (rows not active) / B;  stats[2] = (sum kl_row) / B;  stats[3] = H;
+ *   grad_ls_k = (float)((-(sum h_k) / B) - ent_coef).
+ * With ls == lo == 0 (exp_fixed(0) == 1.0, products by 1.0 and 0.5 are exact, a sum of halves is half the sum) a row's rho, dz, the
+ * surrogate and -- with ent_coef 0 -- the first three statistics are the bytes clothhip_policy_fit_ppo_grad gives at sigma = 1.
+ * Outside [-20, 20] the clamp inside exp_fixed (its argument to [-40, 40]) defines the arithmetic; the optimizer does not clamp the head.
+ * THE ENTRIES. clothhip_policy_fit_ppo_sigma_grad: grad_out[n_params], grad_ls_out[4], stats_out[4], ratio_out[B], each may be
+ * NULL; nothing is updated. clothhip_policy_fit_ppo_sigma: n_steps steps; stats_out[n_steps][4] and log_sigma_out[n_steps][4] (both
+ * may be NULL) are the statistics and the head BEFORE each step's update. Forward, backward, the blob's optimizer, its moments and step
+ * count are clothhip_policy_fit_ppo's. The head is updated by the SAME optimizer kernel, launched a second time over a table of one row
+ * of four elements, under the call's ClothFitParams, with its own moments and its own 1-based step count (a_t formed in double on the
+ * host from that count). clothhip_policy_fit_reset restarts the head's optimizer state too; clothhip_set_policy_log_sigma restarts
+ * it alone. Refused before the first launch, nothing changed -- everything clothhip_policy_fit_ppo refuses (a population among it);
+ * CLOTHHIP_ESTATE: no head on the handle, an idx entry whose row has no old mean or no old log sigma (the message names the row);
+ * CLOTHHIP_EINVAL: clip not finite, < 0 or >= 1, ent_coef not finite or < 0. */
+typedef struct ClothPpoSigmaParams { double clip, ent_coef; } ClothPpoSigmaParams;
+#define CLOTHHIP_PPO_SIGMA_STATS 4      /* loss, clip_fraction, kl, entropy */
+int clothhip_set_policy_log_sigma(clothhip_handle *h, const float *ls);
+int clothhip_get_policy_log_sigma(clothhip_handle *h, float *out);
+int clothhip_fit_data_set_old_log_sigma(clothhip_handle *h, int64_t first, int64_t n, const float *ls);
+int clothhip_fit_data_get_old_log_sigma(clothhip_handle *h, int64_t first, int64_t n, float *ls);
+int clothhip_policy_fit_ppo_sigma_grad(clothhip_handle *h, const ClothPpoSigmaParams *q, const int32_t *idx, int32_t B, float *grad_out, float *grad_ls_out, double *stats_out, float *ratio_out);
+int clothhip_policy_fit_ppo_sigma(clothhip_handle *h, const ClothFitParams *p, const ClothPpoSigmaParams *q, const int32_t *idx, int32_t n_steps, int32_t B, double *stats_out, float *log_sigma_out);
+
 int clothhip_run_actions(clothhip_handle *h, const ClothEpisodeParams *ep, int32_t T, int32_t policy,
                          const double *actions, int32_t actions_on_device, const int32_t *policy_arg,
                          const ClothResetScript *scripts, int32_t n_scripts, int32_t *num_steps, uint8_t *done,

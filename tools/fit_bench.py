@@ -20,7 +20,11 @@ members = {0}, n_m = 1.
 --ppo runs the PPO section instead (clothhip_policy_fit_ppo; profiles/ppo.txt): on the four shapes above, an Adam step
 of the clipped surrogate beside the squared-error step timed in the same process on the same handle and rows. The two differ in ONE
 launch per step: k_fit_loss_ppo in the place of k_fit_loss.
-    python3 tools/fit_bench.py --ppo [--steps 20] [--rounds 5] [--out FILE]"""
+    python3 tools/fit_bench.py --ppo [--steps 20] [--rounds 5] [--out FILE]
+--ppo-sigma runs the learned-sigma section instead (clothhip_policy_fit_ppo_sigma; profiles/ppo_sigma.txt): on the four
+shapes, an Adam step with the log-sigma head beside the fixed-sigma PPO step, alternated on one handle. The two differ in the loss launch
+(k_fit_loss_ppo_sigma: nine exp_fixed per row in one workgroup, seven reductions) and in one more optimizer launch over the head.
+    python3 tools/fit_bench.py --ppo-sigma [--steps 20] [--rounds 5] [--out FILE]"""
 import argparse
 import os
 import sys
@@ -151,6 +155,37 @@ def ppo_section(args, b, rows, labels):
                                                                         100.0 * (p - m) / m, stats[-1, 1], stats[-1, 2]))
 
 
+def ppo_sigma_section(args, b, rows, labels):
+    """A learned-sigma PPO Adam step beside the fixed-sigma one: the same handle, network, rows and minibatch table, `--rounds` calls of
+    `--steps` steps each after one warm-up call, alternated; Gaussian advantages, old means and old log sigmas from one snapshot."""
+    r = np.random.RandomState(3)
+    b.fit_append(rows, labels, weights=np.random.RandomState(9).normal(size=len(rows)).astype(np.float32))
+    say("fit_bench ppo-sigma: 25x25 (1875 inputs), dataset %d rows, Gaussian advantages, sigma 0.5 / head log 0.5, clip 0.2, ent_coef 0.01; %d Adam "
+        "steps per call, %d calls of each kind alternated after one warm-up call; device ms by HIP events around all steps of a call"
+        % (args.rows, args.steps, args.rounds))
+    head = np.full(4, np.log(0.5))
+    for hidden in ([64, 64], [256, 256, 256]):
+        widths = [3 * b.P] + hidden + [4]
+        for B in (256, 4096):
+            table = r.randint(0, args.rows, size=(args.steps, B)).astype(np.int32)
+            b.set_policy_mlp(layers_of(widths))
+            b.set_policy_log_sigma(head)
+            b.fit_snapshot_policy()
+            b.fit_ppo(table, 0.5, 0.2, lr=1e-5)
+            b.fit_ppo_sigma(table, 0.2, 0.01, lr=1e-5)
+            fixed, learned = [], []
+            for _ in range(args.rounds):
+                b.fit_ppo(table, 0.5, 0.2, lr=1e-5)
+                fixed.append(b.last_kernel_ms / args.steps)
+                stats, _ = b.fit_ppo_sigma(table, 0.2, 0.01, lr=1e-5)
+                learned.append(b.last_kernel_ms / args.steps)
+            m, p = float(np.median(fixed)), float(np.median(learned))
+            say("hidden %-15r B %4d: fixed sigma %.3f ms/step (min %.3f, max %.3f) | learned sigma %.3f ms/step (min %.3f, max %.3f) | learned - fixed "
+                "%+.3f ms (%+.1f %%), the fixed step's spread %.3f ms; last clip_fraction %.3f, kl %.5f, entropy %.4f"
+                % (hidden, B, m, min(fixed), max(fixed), p, min(learned), max(learned), p - m, 100.0 * (p - m) / m, max(fixed) - min(fixed),
+                   stats[-1, 1], stats[-1, 2], stats[-1, 3]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
@@ -158,6 +193,7 @@ def main():
     ap.add_argument("--rows", type=int, default=8192)
     ap.add_argument("--members", action="store_true", help="run the members section (the grouped trainer) instead of the single-network one")
     ap.add_argument("--ppo", action="store_true", help="run the PPO section (a clipped-surrogate step beside the squared-error step) instead")
+    ap.add_argument("--ppo-sigma", action="store_true", help="run the learned-sigma section (a step with the log-sigma head beside the fixed-sigma PPO step) instead")
     ap.add_argument("--out", default=None, help="also append the printed lines to this file")
     args = ap.parse_args()
     b = ClothBatch(bench.bench_cfg(25, 0.02, "tier1"), n_envs=1, precision="f32")
@@ -171,8 +207,8 @@ def main():
             with open(args.out, "a") as fh:
                 fh.write("\n".join(LINES) + "\n")
         return
-    if args.ppo:
-        ppo_section(args, b, rows, labels)
+    if args.ppo or args.ppo_sigma:
+        (ppo_sigma_section if args.ppo_sigma else ppo_section)(args, b, rows, labels)
         b.close()
         if args.out:
             with open(args.out, "a") as fh:

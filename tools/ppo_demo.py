@@ -10,7 +10,12 @@ completed in both runs, PPO's clip_fraction and kl per epoch, and how far each r
 came out. What it is for is the other column: the weighted regression under these many steps runs away, the clipped surrogate does not.
 With --bench it measures instead: clothhip_fit_data_snapshot_policy over the rows of one --envs x --slots collection, kernels and call,
 beside the host route it replaces in the same run (fit_predict with its download, fit_set_old_means with its upload).
+With --learn-sigma the PPO run carries a log-sigma head that starts at log(--sigma) and is trained by the same surrogate
+minus --ent-coef times the entropy: its collections act with unit noise times the head's present sigma, the one snapshot stores the old
+means and the old log sigmas, and every iteration's line adds the sigma it acted with; the weighted regression beside it keeps --sigma.
+--bench then also times the snapshot with a head on the handle (one more fill kernel). profiles/ppo_sigma.txt holds runs.
     python3 tools/ppo_demo.py [--envs 64] [--slots 12] [--iters 4] [--epochs 10] [--sigma 0.1] [--clip 0.2] [--target-kl X] [--out FILE]
+    python3 tools/ppo_demo.py --learn-sigma [--ent-coef 0.01] [...]
     python3 tools/ppo_demo.py --bench [--envs 512] [--slots 12] [--out FILE]"""
 import argparse
 import os
@@ -75,20 +80,27 @@ def run(args):
         "exploration noise sigma %g; GAE gamma %g lambda %g, normalised advantages; Adam lr %g, %d critic steps, then %d epochs of minibatches "
         "of %d rows over the collection: PPO (clip %g, target_kl %r) beside actor_critic_fit with as many policy steps, same seeds and noise"
         % (E, hidden, T, args.sigma, args.gamma, args.lam, args.lr, args.value_steps, args.epochs, args.batch, args.clip, args.target_kl))
+    if args.learn_sigma:
+        pol[0].set_log_sigma(np.log(args.sigma))
+        say("    --learn-sigma: the PPO run's sigma is a head of four log sigmas that starts at log %g and is trained with the network, entropy "
+            "coefficient %g; its collections act with unit noise times the head's sigma" % (args.sigma, args.ent_coef))
     for i in range(args.iters):
-        noise = np.random.RandomState(100 + i).normal(size=(T, E, 4)) * args.sigma
+        unit = np.random.RandomState(100 + i).normal(size=(T, E, 4))
+        acted = pol[0].sigma() if args.learn_sigma else np.full(4, args.sigma)
+        noises = [unit * acted, unit * args.sigma]
         for v in envs:
             v.seed([2000 + e for e in range(E)])                              # every iteration from the same start states
             v.reset()
         try:
-            cols = [actor_critic_collect(v, tr, n_actions=T, policy_noise=noise, slots_per_launch=T) for v, tr in zip(envs, pol)]
+            cols = [actor_critic_collect(v, tr, n_actions=T, policy_noise=nz, slots_per_launch=T) for v, tr, nz in zip(envs, pol, noises)]
         except ValueError as e:                                               # a network that ran away acts with values that are not finite
             say("iteration %d: a collection was refused (%s): the run ends here" % (i, e))
             break
         before = [moved(tr, c) for tr, c in zip(pol, cols)]
         t0 = time.perf_counter()
-        fit = ppo_fit(envs[0], pol[0], critic[0], cols[0], sigma=args.sigma, gamma=args.gamma, lam=args.lam, clip=args.clip,
-                      n_value_steps=args.value_steps, n_epochs=args.epochs, batch_size=args.batch, seed=i, target_kl=args.target_kl)
+        fit = ppo_fit(envs[0], pol[0], critic[0], cols[0], sigma=None if args.learn_sigma else args.sigma, gamma=args.gamma, lam=args.lam,
+                      clip=args.clip, n_value_steps=args.value_steps, n_epochs=args.epochs, batch_size=args.batch, seed=i, target_kl=args.target_kl,
+                      ent_coef=args.ent_coef if args.learn_sigma else 0.0)
         dp = time.perf_counter() - t0
         n_mb = max(1, len(cols[1]["nonleaf"]) // args.batch)
         t0 = time.perf_counter()
@@ -101,7 +113,11 @@ def run(args):
             "completed episodes, mean return %.4f" % (i, cols[0]["appended"], cols[0]["open_rows"], len(cols[0]["episode_return"]),
                                                       mean(cols[0]["episode_return"]), cols[1]["appended"], cols[1]["open_rows"],
                                                       len(cols[1]["episode_return"]), mean(cols[1]["episode_return"])))
-        per = fit["ppo_stats"].reshape(fit["epochs"], -1, 3).mean(axis=1) if fit["epochs"] else np.zeros((0, 3))
+        n_stats = fit["ppo_stats"].shape[1]
+        per = fit["ppo_stats"].reshape(fit["epochs"], -1, n_stats).mean(axis=1) if fit["epochs"] else np.zeros((0, n_stats))
+        if args.learn_sigma:
+            say("    sigma acted with %s -> after the fit %s; entropy per epoch %s" % (
+                " ".join("%.5f" % s for s in acted), " ".join("%.5f" % s for s in pol[0].sigma()), " ".join("%.4f" % h for h in per[:, 3])))
         say("    PPO: %d epochs, %d steps, fit %.0f ms; per epoch clip_fraction %s | kl %s | surrogate loss %s" % (
             fit["epochs"], len(fit["ppo_stats"]), dp * 1e3, " ".join("%.3f" % c for c in per[:, 1]), " ".join("%.4f" % k for k in per[:, 2]),
             " ".join("%.4f" % l for l in per[:, 0])))
@@ -145,6 +161,17 @@ def bench_section(args, reps=10):
             parts[k].append(d)
     say("    the host route: fit_predict with its download %s, fit_set_old_means %s; together %s" % tuple(stats(parts[k]) for k in ("predict", "upload", "all")))
     say("    both routes leave the same bytes in the old-mean column: %s" % (dev.tobytes() == b.fit_get_old_means().tobytes()))
+    # with a head on the handle the same call also fills the old-log-sigma column
+    tr.set_log_sigma(np.log(0.1))
+    b.fit_snapshot_policy(0, n)
+    kern, wall = [], []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        b.fit_snapshot_policy(0, n)
+        wall.append(time.perf_counter() - t0)
+        kern.append(b.last_kernel_ms * 1e-3)
+    say("    with a log-sigma head (the fill of the old-log-sigma column behind the forward): device %s, call %s; the column holds the head in "
+        "every row: %s" % (stats(kern), stats(wall), b.fit_get_old_log_sigma().tobytes() == np.tile(tr.log_sigma(), (n, 1)).tobytes()))
     env.close()
 
 
@@ -163,6 +190,8 @@ def main():
     ap.add_argument("--value-steps", type=int, default=200)
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--lr", type=float, default=1e-3)
+    ap.add_argument("--learn-sigma", action="store_true", help="the PPO run trains a log-sigma head that starts at log(--sigma)")
+    ap.add_argument("--ent-coef", type=float, default=0.0, help="with --learn-sigma: the coefficient of the entropy bonus")
     ap.add_argument("--bench", action="store_true", help="measure the snapshot on the device against the host route")
     ap.add_argument("--out", default=None, help="also append the printed lines to this file")
     args = ap.parse_args()
