@@ -254,6 +254,11 @@ SYMBOLS = [
                                                      C.POINTER(C.c_float)]),
     ("clothhip_policy_fit_ppo_sigma", C.c_int, [_vp, C.POINTER(ClothFitParams), C.POINTER(ClothPpoSigmaParams), _i32p, C.c_int32, C.c_int32, _dp,
                                                 C.POINTER(C.c_float)]),
+    ("clothhip_fit_data_snapshot_policy_members", C.c_int, [_vp, C.c_int64, C.c_int64, _i32p]),
+    ("clothhip_policy_fit_ppo_grad_members", C.c_int, [_vp, C.POINTER(ClothPpoParams), _i32p, C.c_int32, _i32p, C.c_int32, C.POINTER(C.c_float), _dp,
+                                                       C.POINTER(C.c_float)]),
+    ("clothhip_policy_fit_ppo_members", C.c_int, [_vp, C.POINTER(ClothFitParams), C.POINTER(ClothPpoParams), _i32p, C.c_int32, _i32p, C.c_int32, C.c_int32,
+                                                  _dp]),
     ("clothhip_plan_cem", C.c_int, [_vp, _vp, C.POINTER(ClothEpisodeParams), C.POINTER(ClothPlanParams), _i32p, _u8p, _dp, _dp, _dp, _dp,
                                     _dp, _dp]),
     ("clothhip_plan_sample", C.c_int, [_vp, C.POINTER(ClothPlanParams), _dp, _dp, C.c_int32, C.c_int32, _dp, _dp, _dp]),

@@ -448,6 +448,70 @@ class FitBindings(object):
         check(self._L.clothhip_policy_fit_ppo(self._h, p, C.byref(q), _lib.i32p(ix), ix.shape[0], ix.shape[1], _lib.dp(stats)))
         return stats
 
+    # ---- PPO for a population: the snapshot by member and the grouped surrogate (clothhip.h: PPO FOR A POPULATION) --------------------
+    def fit_snapshot_policy_members(self, member_of_row, first=0):
+        """Write into the old-mean column of the stored rows [first, first + len(member_of_row)) the present output of the population
+        row that ACTED there, on the device (clothhip_fit_data_snapshot_policy_members): member_of_row int[n] names a population row
+        per stored row, -1 skips the row (its bytes and its mark stay). A named row gets the bytes fit_predict([row], [g]) returns and
+        then has an old mean; nothing is downloaded."""
+        m = np.asarray(member_of_row)
+        if m.ndim != 1 or not (np.issubdtype(m.dtype, np.integer) or m.size == 0):
+            raise ValueError("member_of_row must be a 1-d integer array")
+        shape = getattr(self, '_pop_shape', None)
+        if shape is None:
+            raise _lib.ClothHipError("no population on this batch: call set_policy_population or population_perturb first")
+        if m.size and (m.min() < -1 or m.max() >= shape[0]):
+            raise ValueError("member_of_row must hold -1 or population rows in [0, %d)" % shape[0])
+        if int(first) < 0:
+            raise ValueError("first must be >= 0 and lie within the dataset")
+        m = np.ascontiguousarray(m, dtype=np.int32)
+        check(self._L.clothhip_fit_data_snapshot_policy_members(self._h, int(first), m.size, _lib.i32p(m)))
+
+    @classmethod
+    def _ppo_params_members(cls, sigma, clip, n_m):
+        """_lib.ClothPpoParams[n_m] from sigma and clip, each a scalar for all members or n_m values."""
+        q = (_lib.ClothPpoParams * n_m)()
+        vals = {}
+        for k, v in (('sigma', sigma), ('clip', clip)):
+            v = np.asarray(v, dtype=np.float64)
+            if v.ndim > 1 or (v.ndim == 1 and v.size != n_m):
+                raise ValueError("%s must be a scalar or %d values, one per member" % (k, n_m))
+            vals[k] = np.broadcast_to(v, (n_m,))
+        for j in range(n_m):
+            one = cls._ppo_params(vals['sigma'][j], vals['clip'][j])
+            q[j].sigma, q[j].clip = one.sigma, one.clip
+        return q
+
+    def fit_ppo_grad_members(self, members, idx, sigma, clip=0.2):
+        """(stats float64[n_m, 3] = loss, clip_fraction, kl; grad float32[n_m, n_params]; ratio float32[n_m, B]) of PPO's clipped
+        surrogate of the population rows `members` over their own minibatches idx [n_m, B], member j under its own sigma[j] and clip[j]
+        (scalars: the same for all); nothing is updated (clothhip_policy_fit_ppo_grad_members). Member j's result is bit for bit
+        fit_ppo_grad's on a batch that carries row members[j] as its shared network over the same dataset, weights and old means."""
+        m, n_params = self._fit_members(members)
+        ix = self._fit_members_idx(idx, m.size, 2)
+        q = self._ppo_params_members(sigma, clip, m.size)
+        grad = np.zeros((m.size, n_params), dtype=np.float32)
+        stats = np.zeros((m.size, _lib.PPO_STATS), dtype=np.float64)
+        ratio = np.zeros((m.size, ix.shape[1]), dtype=np.float32)
+        check(self._L.clothhip_policy_fit_ppo_grad_members(self._h, q, _lib.i32p(m), m.size, _lib.i32p(ix), ix.shape[1], _lib.fp(grad), _lib.dp(stats),
+                                                           _lib.fp(ratio)))
+        return stats, grad, ratio
+
+    def fit_ppo_members(self, members, idx_table, sigma, clip=0.2, hyper=None):
+        """fit_members with PPO's clipped surrogate as the loss (clothhip_policy_fit_ppo_members): n_steps optimizer steps on the
+        population rows `members` in place, all members in the launches of one, step s of member j on the dataset rows
+        idx_table[s, j] (int [n_steps, n_m, B]), every row with an old mean; sigma and clip are scalars or n_m values, hyper as
+        fit_members takes it. The optimizer state is the rows' own: fit_members and fit_ppo_members share a row's moments and step
+        count, fit_reset_members restarts both. Returns float64[n_steps, n_m, 3]: each member's (loss, clip_fraction, kl) BEFORE each
+        step's update -- the bits fit_ppo gives on a batch that carries the row as its shared network."""
+        m, _ = self._fit_members(members)
+        ix = self._fit_members_idx(idx_table, m.size, 3)
+        p = self._fit_params(hyper, m.size)
+        q = self._ppo_params_members(sigma, clip, m.size)
+        stats = np.zeros((ix.shape[0], m.size, _lib.PPO_STATS), dtype=np.float64)
+        check(self._L.clothhip_policy_fit_ppo_members(self._h, p, q, _lib.i32p(m), m.size, _lib.i32p(ix), ix.shape[0], ix.shape[2], _lib.dp(stats)))
+        return stats
+
     # ---- PPO with a learned sigma: the old log sigma and the surrogate over the handle's head (clothhip.h: PPO WITH A LEARNED SIGMA) ----
     def fit_set_old_log_sigma(self, log_sigma, first=0):
         """Write the old log sigma of the stored rows [first, first + len(log_sigma)) from the host

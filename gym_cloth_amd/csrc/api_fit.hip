@@ -1,10 +1,11 @@
-// api_fit.hip -- the supervised trainer of the handle's networks, policy and critic, over the dataset of api_fit_data.hip: the loss and its gradient over a minibatch, the optimizer steps, advantages from the critic's values, the snapshot of the old means (and, with a log-sigma head, of the old log sigma) and PPO's clipped surrogate under a fixed or a learned sigma.
+// api_fit.hip -- the supervised trainer of the handle's networks, policy and critic, over the dataset of api_fit_data.hip: the loss and its gradient over a minibatch, the optimizer steps, advantages from the critic's values, the snapshot of the old means (and, with a log-sigma head, of the old log sigma; for a population by the member that acted) and PPO's clipped surrogate under a fixed or a learned sigma, of the shared network or of population rows under their own constants.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <new>
+#include <utility>
 #include <vector>
 
 #include "api_handle.hpp"
@@ -147,12 +148,14 @@ template <bool A_KC, bool B_KC, int EPI, bool ROWS> static void launch_gemm(hipS
 // ppo (the policy's table only): the loss launch is k_fit_loss_ppo with these constants, d_loss is then [n_m][FIT_PPO_STATS] and
 // d_ratio (may be NULL) [n_m][B]; every other launch is the same. ppo->head: the loss launch is k_fit_loss_ppo_sigma, which reads the
 // handle's log-sigma head where it lies; d_loss is [n_m][FIT_PPO_SIGMA_STATS], the head's gradient goes to h->fit.d_grad_ls and the
-// head the launch read to ls_out (may be NULL)
+// head the launch read to ls_out (may be NULL). ppo->member_q: the loss launch is k_fit_loss_ppo_members, which reads member j's
+// constants from row j of h->fit.d_ppo_q (the caller has uploaded the table)
 struct FitPpo {
     double inv_s2, half_inv_s2, lo, hi;
     bool head = false;
     double ent_coef = 0.0;
     float *ls_out = nullptr;
+    const double *member_q = nullptr;      // host [n_m][4] {inv_s2, half_inv_s2, lo, hi}: member j's constants in the place of the four above
     int stats() const { return head ? FIT_PPO_SIGMA_STATS : FIT_PPO_STATS; }
 };
 static int enqueue_grad(clothhip_handle *h, const FitNet &net, const FitPlan &p, int32_t n_m, const int32_t *d_idx, int32_t B, double *d_loss, bool shared_rows = false,
@@ -190,7 +193,8 @@ static int enqueue_grad(clothhip_handle *h, const FitNet &net, const FitPlan &p,
         q.y = act + p.h_off[L - 1]; q.lab = d.lab(); q.old = d.old(); q.wgt = d.w(); q.rows = d_idx; q.dz = dz[(L - 1) & 1]; q.ratio = d_ratio; q.stats = d_loss;
         q.inv_s2 = ppo->inv_s2; q.half_inv_s2 = ppo->half_inv_s2; q.lo = ppo->lo; q.hi = ppo->hi;
         q.y_step = (int64_t)p.act; q.dz_step = (int64_t)p.dz; q.rows_step = (int64_t)B; q.B = B;
-        hipLaunchKernelGGL(k_fit_loss_ppo, dim3((unsigned)n_m), dim3(256), 0, h->stream, q);
+        if (ppo->member_q) hipLaunchKernelGGL(k_fit_loss_ppo_members, dim3((unsigned)n_m), dim3(256), 0, h->stream, q, (const double *)f.d_ppo_q);
+        else hipLaunchKernelGGL(k_fit_loss_ppo, dim3((unsigned)n_m), dim3(256), 0, h->stream, q);
     } else if (net.value)
         hipLaunchKernelGGL(k_fit_loss<1>, dim3((unsigned)n_m), dim3(256), 0, h->stream, (const float *)(act + p.h_off[L - 1]), (const float *)d.ret(), (const float *)nullptr,
                            d_idx, B, dz[(L - 1) & 1], d_loss, (int64_t)p.act, (int64_t)p.dz, (int64_t)B);
@@ -248,6 +252,10 @@ static int run_grad(clothhip_handle *h, const FitNet &net, const int32_t *member
     if (int rc = f.d_idx.reserve((size_t)n_m * B * 4)) return rc;
     if (int rc = f.d_loss.reserve(n_loss * 8)) return rc;
     if (ratio_out) if (int rc = f.d_ratio.reserve((size_t)n_m * B * 4)) return rc;
+    if (ppo && ppo->member_q) {
+        if (int rc = f.d_ppo_q.reserve((size_t)n_m * 32)) return rc;
+        HIPCHECK(hipMemcpyAsync(f.d_ppo_q, ppo->member_q, (size_t)n_m * 32, hipMemcpyHostToDevice, h->stream));
+    }
     HIPCHECK(hipMemcpyAsync(f.d_members, members, (size_t)n_m * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipMemcpyAsync(f.d_idx, idx, (size_t)n_m * B * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipEventRecord(h->ev0, h->stream));
@@ -435,6 +443,7 @@ static int run_fit(clothhip_handle *h, const FitNet &net, const ClothFitParams *
     if (int rc = f.d_idx.reserve(n_sm * B * 4)) return rc;
     if (int rc = f.d_loss.reserve(n_sm * per_loss * 8)) return rc;
     if (int rc = f.d_hyper.reserve(n_hyper * 4)) return rc;
+    if (ppo && ppo->member_q) if (int rc = f.d_ppo_q.reserve((size_t)n_m * 32)) return rc;
     if (head) {
         if (int rc = f.d_grad_ls.reserve(MLP_OUT * 4)) return rc;
         if (int rc = f.d_ls_hist.reserve((size_t)n_steps * MLP_OUT * 4)) return rc;
@@ -466,6 +475,7 @@ static int run_fit(clothhip_handle *h, const FitNet &net, const ClothFitParams *
     HIPCHECK(hipMemcpyAsync(f.d_members, members, (size_t)n_m * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipMemcpyAsync(f.d_idx, idx, n_sm * B * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipMemcpyAsync(f.d_hyper, hyper.data(), n_hyper * 4, hipMemcpyHostToDevice, h->stream));
+    if (ppo && ppo->member_q) HIPCHECK(hipMemcpyAsync(f.d_ppo_q, ppo->member_q, (size_t)n_m * 32, hipMemcpyHostToDevice, h->stream));
     FitOptArgs o = {};
     o.theta = net.theta; o.m = net.opt.m; o.v = net.opt.v; o.g = f.d_grad; o.members = f.d_members;
     o.stride = (int64_t)stride; o.n = (int64_t)n; o.blocks = (int32_t)((n + 255) / 256);
@@ -572,16 +582,23 @@ extern "C" int clothhip_fit_data_snapshot_policy(clothhip_handle *h, int64_t fir
     return 0;
 }
 
-// the constants of a PPO call and the rows of its minibatches, after everything clothhip_policy_fit refuses: -> the kernel's constants
-static int check_ppo(const clothhip_handle *h, const ClothPpoParams *q, const int32_t *idx, int64_t n_idx, FitPpo *out) {
-    if (!std::isfinite(q->sigma) || q->sigma <= 0.0) return fail(CLOTHHIP_EINVAL, "sigma = %g: the policy's standard deviation is finite and > 0", q->sigma);
-    if (!std::isfinite(q->clip) || q->clip < 0.0 || q->clip >= 1.0) return fail(CLOTHHIP_EINVAL, "clip = %g: the clip range lies in [0, 1)", q->clip);
+// the constants of member j of a PPO call (j < 0: of the shared network, named without an index) -> the kernel's constants
+static int check_ppo_consts(const ClothPpoParams *q, int32_t j, FitPpo *out) {
+    char who[24] = "";
+    if (j >= 0) snprintf(who, sizeof(who), "q[%d]: ", j);
+    if (!std::isfinite(q->sigma) || q->sigma <= 0.0) return fail(CLOTHHIP_EINVAL, "%ssigma = %g: the policy's standard deviation is finite and > 0", who, q->sigma);
+    if (!std::isfinite(q->clip) || q->clip < 0.0 || q->clip >= 1.0) return fail(CLOTHHIP_EINVAL, "%sclip = %g: the clip range lies in [0, 1)", who, q->clip);
     const double s2 = q->sigma * q->sigma;
     out->inv_s2 = 1.0 / s2;
     out->half_inv_s2 = 0.5 * out->inv_s2;
     out->lo = 1.0 - q->clip;
     out->hi = 1.0 + q->clip;
-    if (!std::isfinite(out->inv_s2)) return fail(CLOTHHIP_EINVAL, "sigma = %g: 1 / sigma^2 is not a finite double", q->sigma);
+    if (!std::isfinite(out->inv_s2)) return fail(CLOTHHIP_EINVAL, "%ssigma = %g: 1 / sigma^2 is not a finite double", who, q->sigma);
+    return 0;
+}
+// the constants of a PPO call and the rows of its minibatches, after everything clothhip_policy_fit refuses: -> the kernel's constants
+static int check_ppo(const clothhip_handle *h, const ClothPpoParams *q, const int32_t *idx, int64_t n_idx, FitPpo *out) {
+    if (int rc = check_ppo_consts(q, -1, out)) return rc;
     for (int64_t i = 0; i < n_idx; i++)
         if (!h->dataset.h_old_set[(size_t)idx[i]])
             return fail(CLOTHHIP_ESTATE, "idx[%lld] = row %d has no old mean: call clothhip_fit_data_snapshot_policy or clothhip_fit_data_set_old_means on it first",
@@ -612,6 +629,136 @@ extern "C" int clothhip_policy_fit_ppo(clothhip_handle *h, const ClothFitParams 
     if (int rc = check_ppo(h, q, idx, (int64_t)n_steps * B, &ppo)) return rc;
     if (n_steps == 0) return 0;
     return run_fit(h, policy_net(h), p, SHARED_ROW, 1, idx, n_steps, B, stats_out, &ppo);
+}
+
+// ---- PPO for a population (clothhip.h: PPO FOR A POPULATION): the snapshot by member, and the two entries above as grouped calls ---------
+// The forward of n_m members on THEIR OWN rows, scattered to the old-mean column. The rows named are grouped by member; member lists
+// longer than CLOTHHIP_FIT_MAX_BATCH are cut into segments, and the k-th segments of all members that have one are launched together,
+// longest first, as many as CLOTHHIP_FIT_MAX_MEMBER_ROWS holds at the longest one's length B. A shorter segment is padded to B with its
+// own first row (a valid row of the same member: the layer-0 gather stays in range), which k_fit_scatter_y does not store.
+struct SnapChunk { size_t m0, idx0; int32_t n_m, B; };      // offsets into the call's member / length tables and its index table
+
+extern "C" int clothhip_fit_data_snapshot_policy_members(clothhip_handle *h, int64_t first, int64_t n, const int32_t *member_of_row) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (int rc = check_fit_state(h, true)) return rc;
+    if (int rc = check_range(h, first, n)) return rc;
+    if (n == 0) return 0;
+    if (!member_of_row) return fail(CLOTHHIP_EINVAL, "member_of_row is NULL");
+    for (int64_t i = 0; i < n; i++)
+        if (member_of_row[i] < -1 || member_of_row[i] >= h->pol.pop_rows)
+            return fail(CLOTHHIP_EINVAL, "member_of_row[%lld] = %d outside [-1, %lld)", (long long)i, member_of_row[i], (long long)h->pol.pop_rows);
+    auto &f = h->fit;
+    const FitNet net = policy_net(h);
+    const int L = net.D.n_layers;
+    std::vector<int32_t> mem, len, idx;      // per chunk member: the population row and its real positions; the index tables [n_m][B], chunk after chunk
+    std::vector<SnapChunk> chunks;
+    try {
+        // the rows of every member, ascending, as one table sorted by (member, row): start[g] .. start[g + 1]
+        std::vector<int64_t> start((size_t)h->pol.pop_rows + 1, 0);
+        for (int64_t i = 0; i < n; i++) if (member_of_row[i] >= 0) start[(size_t)member_of_row[i] + 1]++;
+        for (size_t g = 0; g < (size_t)h->pol.pop_rows; g++) start[g + 1] += start[g];
+        const int64_t named = start[(size_t)h->pol.pop_rows];
+        if (named == 0) return 0;
+        std::vector<int32_t> by_member((size_t)named);
+        std::vector<int64_t> at(start.begin(), start.end() - 1);
+        for (int64_t i = 0; i < n; i++) if (member_of_row[i] >= 0) by_member[(size_t)at[(size_t)member_of_row[i]]++] = (int32_t)(first + i);
+        for (int64_t k = 0;; k++) {          // the k-th segments
+            std::vector<std::pair<int32_t, int32_t>> seg;      // (length, member), longest first
+            for (int64_t g = 0; g < h->pol.pop_rows; g++) {
+                const int64_t rest = start[(size_t)g + 1] - start[(size_t)g] - k * FIT_MAX_BATCH;
+                if (rest > 0) seg.push_back({(int32_t)std::min<int64_t>(rest, FIT_MAX_BATCH), (int32_t)g});
+            }
+            if (seg.empty()) break;
+            std::stable_sort(seg.begin(), seg.end(), [](const std::pair<int32_t, int32_t> &a, const std::pair<int32_t, int32_t> &b) { return a.first > b.first; });
+            for (size_t s0 = 0; s0 < seg.size();) {
+                const int32_t B = seg[s0].first;
+                const size_t n_m = std::min<size_t>(seg.size() - s0, (size_t)(CLOTHHIP_FIT_MAX_MEMBER_ROWS / B));
+                chunks.push_back({mem.size(), idx.size(), (int32_t)n_m, B});
+                for (size_t j = s0; j < s0 + n_m; j++) {
+                    const int32_t *rows = by_member.data() + start[(size_t)seg[j].second] + k * FIT_MAX_BATCH;
+                    mem.push_back(seg[j].second); len.push_back(seg[j].first);
+                    idx.insert(idx.end(), rows, rows + seg[j].first);
+                    idx.insert(idx.end(), (size_t)(B - seg[j].first), rows[0]);
+                }
+                s0 += n_m;
+            }
+        }
+    } catch (const std::bad_alloc &) { return fail(CLOTHHIP_ENOMEM, "out of host memory (%lld rows)", (long long)n); }
+    HIPCHECK(hipSetDevice(h->device));
+    // every chunk's scratch before the first launch: a buffer that grows is freed first
+    for (const SnapChunk &c : chunks) if (int rc = fit_reserve(h, fit_plan(net, c.B), c.n_m)) return rc;
+    if (int rc = f.d_len.reserve(len.size() * 4)) return rc;
+    if (int rc = f.d_idx.reserve(idx.size() * 4)) return rc;
+    HIPCHECK(hipMemcpyAsync(f.d_len, len.data(), len.size() * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipMemcpyAsync(f.d_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipEventRecord(h->ev0, h->stream));
+    for (const SnapChunk &c : chunks) {
+        const FitPlan p = fit_plan(net, c.B);
+        // (the launches read the chunk's members at the head of d_members: stream order keeps the chunks apart)
+        HIPCHECK(hipMemcpyAsync(f.d_members, mem.data() + c.m0, (size_t)c.n_m * 4, hipMemcpyHostToDevice, h->stream));
+        if (int rc = enqueue_grad(h, net, p, c.n_m, f.d_idx + c.idx0, c.B, nullptr)) return rc;
+        launch_fit_scatter_y(h->stream, c.n_m, f.d_act + p.h_off[L - 1], f.d_idx + c.idx0, f.d_len + c.m0, h->dataset.old(), c.B, (int64_t)p.act);
+        HIPCHECK(hipGetLastError());
+    }
+    HIPCHECK(hipEventRecord(h->ev1, h->stream));
+    h->have_timing = true;
+    HIPCHECK(hipStreamSynchronize(h->stream));      // (the host tables the uploads read go out of scope)
+    for (int64_t i = 0; i < n; i++) if (member_of_row[i] >= 0) h->dataset.h_old_set[(size_t)(first + i)] = 1;
+    return 0;
+}
+
+// the constants q [n_m] of a grouped PPO call and the rows of its minibatches idx [n_steps][n_m][B], after everything
+// clothhip_policy_fit_members refuses: -> tab [n_m][4], the table k_fit_loss_ppo_members reads
+static int check_ppo_members(const clothhip_handle *h, const ClothPpoParams *q, const int32_t *members, int32_t n_m, const int32_t *idx, int32_t n_steps, int32_t B, std::vector<double> *tab) {
+    try { tab->resize((size_t)n_m * 4); } catch (const std::bad_alloc &) { return fail(CLOTHHIP_ENOMEM, "out of host memory (%d members)", n_m); }
+    for (int32_t j = 0; j < n_m; j++) {
+        FitPpo c;
+        if (int rc = check_ppo_consts(q + j, j, &c)) return rc;
+        double *t = tab->data() + (size_t)j * 4;
+        t[0] = c.inv_s2; t[1] = c.half_inv_s2; t[2] = c.lo; t[3] = c.hi;
+    }
+    const int64_t n_idx = (int64_t)n_steps * n_m * B;
+    for (int64_t i = 0; i < n_idx; i++)
+        if (!h->dataset.h_old_set[(size_t)idx[i]])
+            return fail(CLOTHHIP_ESTATE, "idx[%lld] = row %d of member %lld has no old mean: call clothhip_fit_data_snapshot_policy_members or clothhip_fit_data_set_old_means on it first",
+                        (long long)i, idx[i], (long long)members[(i / B) % n_m]);
+    return 0;
+}
+
+extern "C" int clothhip_policy_fit_ppo_grad_members(clothhip_handle *h, const ClothPpoParams *q, const int32_t *members, int32_t n_m, const int32_t *idx, int32_t B,
+                                                    float *grad_out, double *stats_out, float *ratio_out) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (int rc = check_fit_state(h, true)) return rc;
+    if (!q) return fail(CLOTHHIP_EINVAL, "NULL argument");
+    if (int rc = check_fit_members(h, members, n_m)) return rc;
+    if (int rc = check_fit_rows(h, n_m, idx, (int64_t)n_m * B, B)) return rc;
+    std::vector<double> tab;
+    if (int rc = check_ppo_members(h, q, members, n_m, idx, 1, B, &tab)) return rc;
+    FitPpo ppo;
+    ppo.inv_s2 = ppo.half_inv_s2 = ppo.lo = ppo.hi = 0.0;      // (not read: the kernel takes the table's)
+    ppo.member_q = tab.data();
+    return run_grad(h, policy_net(h), members, n_m, idx, B, grad_out, stats_out, &ppo, ratio_out);
+}
+
+extern "C" int clothhip_policy_fit_ppo_members(clothhip_handle *h, const ClothFitParams *p, const ClothPpoParams *q, const int32_t *members, int32_t n_m,
+                                               const int32_t *idx, int32_t n_steps, int32_t B, double *stats_out) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (int rc = check_fit_state(h, true)) return rc;
+    if (!p || !q) return fail(CLOTHHIP_EINVAL, "NULL argument");
+    if (n_steps < 0) return fail(CLOTHHIP_EINVAL, "n_steps < 0");
+    if (int rc = check_fit_members(h, members, n_m)) return rc;
+    if (int rc = check_fit_rows(h, n_m, idx, (int64_t)n_steps * n_m * B, B)) return rc;
+    for (int32_t j = 0; j < n_m; j++) {
+        if (int rc = check_fit_params(p + j, j)) return rc;
+        if (p[j].optimizer != p[0].optimizer) return fail(CLOTHHIP_EINVAL, "p[%d].optimizer = %g, p[0].optimizer = %g: one optimizer per call", j, (double)p[j].optimizer, (double)p[0].optimizer);
+    }
+    std::vector<double> tab;
+    if (int rc = check_ppo_members(h, q, members, n_m, idx, n_steps, B, &tab)) return rc;
+    if (n_steps == 0) return 0;
+    FitPpo ppo;
+    ppo.inv_s2 = ppo.half_inv_s2 = ppo.lo = ppo.hi = 0.0;      // (not read: the kernel takes the table's)
+    ppo.member_q = tab.data();
+    return run_fit(h, policy_net(h), p, members, n_m, idx, n_steps, B, stats_out, &ppo);
 }
 
 // ---- PPO with a learned sigma: one more loss mode, and the head as one more table of the optimizer (clothhip.h: PPO WITH A LEARNED SIGMA) ----

@@ -370,10 +370,14 @@ extern "C" int clothhip_fit_data_append_launch_ex(clothhip_handle *h, const int3
     return 0;
 }
 
-// ---- the two kernels of cloth_fit_gather.hpp that the trainer enqueues (a header with a non-template kernel has one includer) -----------
+// ---- the three kernels of cloth_fit_gather.hpp that the trainer enqueues (a header with a non-template kernel has one includer) -----------
 void clothhip::launch_fit_sqsum(hipStream_t s, const float *y, const float *lab, const float *wgt, const int32_t *rows, int32_t B, double *sum) {
     hipLaunchKernelGGL(k_fit_sqsum, dim3(1), dim3(256), 0, s, y, lab, wgt, rows, B, sum);
 }
 void clothhip::launch_fit_copy_y(hipStream_t s, int32_t n_m, const float *y, int32_t n_vals, float *out, int64_t y_step, int64_t out_step, int32_t blocks) {
     hipLaunchKernelGGL(k_fit_copy_y, dim3((unsigned)blocks * (unsigned)n_m), dim3(256), 0, s, y, n_vals, out, y_step, out_step, blocks);
+}
+void clothhip::launch_fit_scatter_y(hipStream_t s, int32_t n_m, const float *y, const int32_t *rows, const int32_t *len, float *col, int32_t B, int64_t y_step) {
+    const int32_t blocks = (B + 255) / 256;
+    hipLaunchKernelGGL(k_fit_scatter_y, dim3((unsigned)blocks * (unsigned)n_m), dim3(256), 0, s, y, rows, len, col, B, y_step, blocks);
 }

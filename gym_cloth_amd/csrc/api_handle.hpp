@@ -246,6 +246,8 @@ struct clothhip_handle : HostPlan {
         Buffer<float> d_pred;        // clothhip_policy_fit_predict*: y of every member and row, [n_m][n][4]; clothhip_value_predict and clothhip_fit_data_gae: v [n]
         Buffer<float> d_ratio;       // clothhip_policy_fit_ppo_grad: (float)rho of the minibatch's rows, [B]
         Buffer<float> d_grad_ls, d_ls_hist;      // clothhip_policy_fit_ppo_sigma*: the head's gradient [4]; the head before every step, [n_steps][4]
+        Buffer<double> d_ppo_q;      // clothhip_policy_fit_ppo*_members: the members' constants {inv_s2, half_inv_s2, lo, hi}, [n_m][4]
+        Buffer<int32_t> d_len;       // clothhip_fit_data_snapshot_policy_members: the real positions of every member's index row, per chunk
         // clothhip_fit_data_gae: A of every row of the range as a double, the advantages as floats, {mean, std} of the normalisation
         Buffer<double> d_gae_a, d_gae_stat;
         Buffer<float> d_adv;
@@ -273,6 +275,8 @@ int check_range(const clothhip_handle *h, int64_t first, int64_t n);            
 // blocks * n_m, argument for argument
 void launch_fit_sqsum(hipStream_t s, const float *y, const float *lab, const float *wgt, const int32_t *rows, int32_t B, double *sum);
 void launch_fit_copy_y(hipStream_t s, int32_t n_m, const float *y, int32_t n_vals, float *out, int64_t y_step, int64_t out_step, int32_t blocks);
+// ... and k_fit_scatter_y over n_m members of B positions each, len[j] of them real
+void launch_fit_scatter_y(hipStream_t s, int32_t n_m, const float *y, const int32_t *rows, const int32_t *len, float *col, int32_t B, int64_t y_step);
 int check_material(const ClothParams &prm, const ClothMaterial &m, int idx);                     // api_state.hip
 SpecPhys phys_of(const ClothParams &p);
 SpecPhys phys_of(const ClothParams &p, const ClothMaterial &m);

@@ -111,4 +111,19 @@ __global__ __launch_bounds__(256) void k_fit_copy_y(const float *y, int32_t n_va
     if (i < n_vals) out[(int64_t)j * out_step + i] = y[(int64_t)j * y_step + i];
 }
 
+// clothhip_fit_data_snapshot_policy_members: member j's y of one chunk, [B][4] at y + j * y_step, SCATTERED to a dataset column of
+// 16-byte rows -- position r of member j goes to row rows[j * B + r] of col. A thread owns one (member, position): y lies at a
+// B-dependent offset of the scratch table, so its four floats move under a 4-byte alignment promise (as k_fit_loss_ppo reads them);
+// the column's row is ONE 16-byte store. Member j's index row is padded to B behind its len[j] real positions (the host repeats a valid
+// row there, for the layer-0 gather): nothing is stored for a padded position, so no row of the column is written twice. One workgroup
+// per member and 256 positions; ordinary vector stores only
+__global__ __launch_bounds__(256) void k_fit_scatter_y(const float *y, const int32_t *rows, const int32_t *len, float *col, int32_t B, int64_t y_step, int32_t blocks) {
+    const int j = blockIdx.x / blocks, bx = blockIdx.x - j * blocks;
+    const int r = bx * 256 + threadIdx.x;
+    if (r >= len[j]) return;      // (len[j] <= B)
+    float v[4];
+    __builtin_memcpy(v, y + (int64_t)j * y_step + (size_t)4 * r, 16);
+    reinterpret_cast<float4 *>(col)[(size_t)rows[(int64_t)j * B + r]] = make_float4(v[0], v[1], v[2], v[3]);
+}
+
 }  // namespace clothhip

@@ -39,6 +39,8 @@
 //   * PPO's clipped surrogate (clothhip.h: PPO ON THE DEVICE) is one more loss launch of the policy's table, k_fit_loss_ppo in the place of
 //     k_fit_loss<4>: per row a probability ratio against the dataset's stored old mean through exp_fixed, dZ in double with one rounding
 //     to float32, three sums over ROWS in the order above; forward, backward and optimizer are the launches of the squared error;
+//     for rows of a population (clothhip.h: PPO FOR A POPULATION) k_fit_loss_ppo_members runs the same body with member j's own
+//     constants, row j of a table the host made;
 //   * PPO with a LEARNED sigma (clothhip.h: PPO WITH A LEARNED SIGMA) is one more loss launch again, k_fit_loss_ppo_sigma: the head
 //     log_sigma[4] read from device memory, the row's old log sigma beside its old mean, nine exp_fixed per row, seven sums over ROWS;
 //     the head is one more table of one row of four elements for k_fit_adam / k_fit_sgd, launched a second time per step;
@@ -260,7 +262,8 @@ struct FitPpoArgs {
 };
 constexpr int FIT_PPO_STATS = 3;            // = CLOTHHIP_PPO_STATS
 
-__global__ __launch_bounds__(256) void k_fit_loss_ppo(FitPpoArgs a) {
+// Member blockIdx.x's rows under the four constants given: the body of both kernels below, which differ only in where the constants come from
+__device__ __forceinline__ void fit_loss_ppo_member(const FitPpoArgs &a, const double inv_s2, const double half_inv_s2, const double lo, const double hi) {
     __shared__ double red[FIT_PPO_STATS][256];
     const int64_t j = blockIdx.x;
     const float *y = a.y + j * a.y_step;
@@ -286,25 +289,25 @@ __global__ __launch_bounds__(256) void k_fit_loss_ppo(FitPpoArgs a) {
             const double ee = e * e;
             kl = kl + ee;
         }
-        const double x = q * a.half_inv_s2;
+        const double x = q * half_inv_s2;
         const double rho = exp_fixed(x);
         const double A = (double)a.wgt[row];
         const double s1 = rho * A;
-        double rc = rho < a.lo ? a.lo : rho;
-        rc = rc > a.hi ? a.hi : rc;
+        double rc = rho < lo ? lo : rho;
+        rc = rc > hi ? hi : rc;
         const double s2 = rc * A;
         const bool active = s1 <= s2;
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             const double d = (double)mu[k] - (double)act[k];
-            const double g1 = s1 * d, g2 = g1 * a.inv_s2, g3 = g2 / Bd;
+            const double g1 = s1 * d, g2 = g1 * inv_s2, g3 = g2 / Bd;
             out[k] = active ? (float)g3 : 0.0f;
         }
         __builtin_memcpy(dz + (size_t)4 * r, out, 16);
         if (a.ratio) a.ratio[j * a.B + r] = (float)rho;
         s_sur = s_sur + (active ? s1 : s2);
         s_clip = s_clip + (active ? 0.0 : 1.0);
-        s_kl = s_kl + kl * a.half_inv_s2;
+        s_kl = s_kl + kl * half_inv_s2;
     }
     red[0][tid] = s_sur; red[1][tid] = s_clip; red[2][tid] = s_kl;
     __syncthreads();
@@ -319,6 +322,16 @@ __global__ __launch_bounds__(256) void k_fit_loss_ppo(FitPpoArgs a) {
         double *st = a.stats + j * FIT_PPO_STATS;
         st[0] = -red[0][0] / Bd; st[1] = red[1][0] / Bd; st[2] = red[2][0] / Bd;
     }
+}
+
+__global__ __launch_bounds__(256) void k_fit_loss_ppo(FitPpoArgs a) { fit_loss_ppo_member(a, a.inv_s2, a.half_inv_s2, a.lo, a.hi); }
+
+// ... with PER-MEMBER constants (clothhip_policy_fit_ppo*_members): member j's workgroup takes row j of q [n_m][4] = {inv_s2, half_inv_s2,
+// lo, hi}, formed on the host as above, and never a's four. The row index is the block's, uniform over the workgroup, so the four
+// doubles are scalar loads; every operation on a row of the minibatch is the one above.
+__global__ __launch_bounds__(256) void k_fit_loss_ppo_members(FitPpoArgs a, const double *q) {
+    const double *c = q + (int64_t)blockIdx.x * 4;
+    fit_loss_ppo_member(a, c[0], c[1], c[2], c[3]);
 }
 
 // PPO's clipped surrogate of a Gaussian policy whose log sigma is LEARNED (clothhip.h: PPO WITH A LEARNED SIGMA has the arithmetic

@@ -550,9 +550,19 @@ def ppo_fit(env, trainer, critic, col, sigma=None, gamma=0.99, lam=0.95, clip=0.
     sigma=None: the trainer's LEARNED head (MLPTrainer.set_log_sigma; the collection acted with trainer.sigma()): the one snapshot
     stores the old means and the old log sigmas, the policy steps train network and head on the surrogate minus ent_coef times the
     entropy; ppo_stats is float64[steps, 4] (the entropy last) and the dict also holds log_sigma float32[steps, 4], the head before
-    every step, and log_sigma_after float32[4]."""
+    every step, and log_sigma_after float32[4].
+    `trainer` an MLPEnsemble (a population): every member learns from the rows ITS OWN envs collected, all members in
+    the launches of one. ONE fit_gae call (normalize=False, w_scale=1) under the shared critic; with normalize the advantages are
+    normalised per member on the host over that member's non-leaf rows (member_normalize) and ONE set_weights call writes them; ONE
+    trainer.snapshot_old call with member_of_row = ensemble.member[col['ds_env']], -1 for a leaf; the critic's steps; then
+    trainer.ppo_step on each member's non-leaf rows of the collection. sigma and clip are a scalar or G values, the caller's numbers (a
+    collection scales its unit noise by sigma[ensemble.member] per env); sigma=None and ent_coef belong to the shared network's head.
+    ppo_stats is then float64[steps, G', 3] with NaN where a retired member did not run, epochs int[G'], and the dict also holds
+    members int[G']: the members that have rows in the collection, and member_of_row int[n]."""
     if trainer.env is not env or critic.env is not env:
         raise ValueError("the trainer or the critic belongs to another env")
+    if hasattr(trainer, 'member'):
+        return _ppo_fit_members(env, trainer, critic, col, sigma, gamma, lam, clip, n_value_steps, n_epochs, batch_size, seed, target_kl, normalize, ent_coef)
     n = int(col['appended']) + int(col['open_rows'])
     adv, ret = env.batch.fit_gae(gamma, lam, first=col['first'], n=n, write_weights=True, normalize=normalize, w_scale=1.0)
     trainer.snapshot_old(col['first'], n)
@@ -570,3 +580,46 @@ def ppo_fit(env, trainer, critic, col, sigma=None, gamma=0.99, lam=0.95, clip=0.
         out['log_sigma'] = trainer.last_log_sigma if len(mine) else np.zeros((0, 4), dtype=np.float32)
         out['log_sigma_after'] = trainer.log_sigma()
     return out
+
+
+def member_normalize(adv, member_of_row):
+    """float32[n]: the advantages adv [n] normalised PER MEMBER, over the rows member_of_row [n] gives that member (-1: a leaf, which
+    gets 0) -- references.gae_reference's formula on each member's rows, in float64 on the (double) of the float32 values:
+    (A - mean) / (std + 1e-8), mean and population standard deviation over the member's rows; rounded once."""
+    A = np.asarray(adv, dtype=np.float32).astype(np.float64).reshape(-1)
+    mor = np.asarray(member_of_row).astype(np.int64).reshape(-1)
+    if mor.shape != A.shape:
+        raise ValueError("adv and member_of_row must have one length")
+    hat = np.zeros(len(A))
+    for g in np.unique(mor[mor >= 0]):
+        mine = mor == g
+        cnt = int(mine.sum())
+        mean = A[mine].sum() / float(cnt)
+        d = A[mine] - mean
+        std = np.sqrt((d * d).sum() / float(cnt))
+        hat[mine] = d / (std + 1e-8)
+    return hat.astype(np.float32)
+
+
+def _ppo_fit_members(env, ens, critic, col, sigma, gamma, lam, clip, n_value_steps, n_epochs, batch_size, seed, target_kl, normalize, ent_coef):
+    """ppo_fit for an MLPEnsemble (its docstring has the steps)."""
+    if sigma is None or float(ent_coef) != 0.0:
+        raise ValueError("a population has no learned head: pass sigma (a scalar or one per member) and ent_coef=0")
+    first, n = int(col['first']), int(col['appended']) + int(col['open_rows'])
+    adv, ret = env.batch.fit_gae(gamma, lam, first=first, n=n, write_weights=True, normalize=False, w_scale=1.0)
+    mor = np.where(np.asarray(col['leaf'], dtype=bool), -1, ens.member[np.asarray(col['ds_env'], dtype=np.int64)]).astype(np.int32)
+    if normalize and n:
+        ens.set_weights(member_normalize(adv, mor), first)
+    ens.snapshot_old(mor, first)
+    rew, nxt = env.batch.fit_get_transitions()
+    from ._lib import FIT_NEXT_NONE
+    rows = np.nonzero(nxt != FIT_NEXT_NONE)[0]
+    vl = critic.step(n_value_steps, batch_size, seed, rows=rows) if len(rows) else np.zeros(0)
+    members = np.unique(mor[mor >= 0]).astype(np.int32)
+    if len(members):
+        stats, epochs = ens.ppo_step(n_epochs, batch_size, seed, sigma, clip=clip, target_kl=target_kl,
+                                     rows_by_member=[first + np.nonzero(mor == g)[0] for g in members], members=members)
+    else:
+        stats, epochs = np.zeros((0, 0, 3)), np.zeros(0, dtype=np.int64)
+    return {'adv': adv, 'ret': ret, 'value_losses': vl, 'ppo_stats': stats, 'epochs': epochs, 'rows': ens.size(), 'members': members,
+            'member_of_row': mor}

@@ -3,7 +3,8 @@ MLPTrainer           the supervised refit of the shared network on the device (C
                      rows, and PPO's clipped surrogate over the same rows; references.fit_reference / ppo_reference are its yardsticks
 ValueTrainer         the critic of an actor-critic (ClothBatch.value_*; references.value_fit_reference, gae_reference)
 MLPEnsemble          G networks, one per env slot, fitted together on the device in the launches of one (ClothBatch.fit_members): a
-                     bootstrapped ensemble whose disagreement is a novelty signal, a learning-rate sweep"""
+                     bootstrapped ensemble whose disagreement is a novelty signal, a learning-rate sweep -- also of PPO, every member
+                     under its own sigma, clip and optimizer (ClothBatch.fit_ppo_members)"""
 import numpy as np
 
 from . import _lib
@@ -328,6 +329,78 @@ class MLPEnsemble(_EnvDataset):
         self._on_env()
         loss, g = self.env.batch.fit_grad_members(m, idx)
         return loss, [unpack_mlp(self.widths, g[j]) for j in range(m.size)]
+
+    # ---- PPO for the population (ClothBatch.fit_*_members) -------------------------------------------------------------
+    def snapshot_old(self, member_of_row, first=0):
+        """Store as the OLD MEANS of the dataset rows [first, first + len(member_of_row)) the present output of the member that ACTED
+        there, on the device (ClothBatch.fit_snapshot_policy_members): member_of_row int[n] holds a member per row -- for a
+        collection ensemble.member[env of the row] -- and -1 for a row to skip (a leaf). What ppo_step's probability ratios are taken
+        against: call it after a collection and before the first policy step on it."""
+        self._on_env()
+        self.env.batch.fit_snapshot_policy_members(member_of_row, first)
+
+    @staticmethod
+    def ppo_epoch_tables(rows_by_member, n_epochs, batch_size, seed):
+        """The minibatches of ppo_step: int32[n_epochs, steps, G', B] from ONE RandomState(seed). rows_by_member is a list of G' 1-d
+        integer arrays, member j's dataset rows. Per epoch, per member in ascending order, one permutation of that member's rows is
+        drawn and cut into steps = min_j(len(rows_j)) // B minibatches of B = batch_size in order; the rest of the permutation is
+        dropped for that epoch. ValueError for a member with fewer than B rows. A function of the arguments alone."""
+        lists = [_check_rows(rows) for rows in rows_by_member]
+        B = int(batch_size)
+        if not lists or int(n_epochs) < 0 or B < 1:
+            raise ValueError("ppo_epoch_tables needs at least one member, n_epochs >= 0, batch_size >= 1")
+        for j, rows in enumerate(lists):
+            if rows.size < B:
+                raise ValueError("member %d of the call has %d rows, fewer than a minibatch of %d" % (j, rows.size, B))
+        steps = min(rows.size for rows in lists) // B
+        r = np.random.RandomState(seed)
+        out = np.zeros((int(n_epochs), steps, len(lists), B), dtype=np.int32)
+        for e in range(int(n_epochs)):
+            for j, rows in enumerate(lists):
+                out[e, :, j, :] = rows[r.permutation(rows.size)][:steps * B].reshape(steps, B)
+        return out
+
+    def _per_member(self, v, what):
+        """v, a scalar or G values, as float64[G]."""
+        v = np.asarray(v, dtype=np.float64)
+        if v.ndim > 1 or (v.ndim == 1 and v.size != self.G):
+            raise ValueError("%s must be a scalar or %d values, one per member" % (what, self.G))
+        return np.broadcast_to(v, (self.G,))
+
+    def ppo_step(self, n_epochs, batch_size, seed, sigma, clip=0.2, target_kl=None, rows_by_member=None, members=None):
+        """PPO of the rows `members` (None: all G) on the device, all members in the launches of one (ClothBatch.fit_ppo_members): up
+        to n_epochs epochs, each ONE fit_ppo_members call over the members still live, on the minibatches
+        ppo_epoch_tables(rows_by_member, n_epochs, batch_size, seed) -- rows_by_member[j] the dataset rows of members[j] (None: every
+        member takes all rows of the dataset). sigma and clip are a scalar or G values (member g's is the g-th), the optimizer's
+        hyper-parameters the ensemble's. With target_kl a member whose mean kl over an epoch exceeds it is RETIRED: later calls name
+        the rest, its row stays as that epoch left it. Returns (stats float64[n_epochs * steps, G', 3]: loss, clip_fraction, kl of
+        every member before each step's update, NaN where the member did not run; epochs int[G']: the epochs each member ran)."""
+        m = self._members(members)
+        sig, clp = self._per_member(sigma, "sigma")[m], self._per_member(clip, "clip")[m]
+        if rows_by_member is None:
+            n = self.size()
+            if n < 1:
+                raise ValueError("the dataset is empty: append first")
+            rows_by_member = [np.arange(n)] * m.size
+        if len(rows_by_member) != m.size:
+            raise ValueError("rows_by_member must hold %d lists of rows, one per member of the call" % m.size)
+        self._on_env()
+        tables = self.ppo_epoch_tables(rows_by_member, n_epochs, batch_size, seed)
+        steps = tables.shape[1]
+        stats = np.full((int(n_epochs) * steps, m.size, 3), np.nan)
+        epochs, live = np.zeros(m.size, dtype=np.int64), np.ones(m.size, dtype=bool)
+        for e in range(int(n_epochs)):
+            if not live.any() or steps == 0:
+                break
+            hyper = {k: (v if k == 'optimizer' else v[m[live]]) for k, v in self.hyper.items()}
+            got = self.env.batch.fit_ppo_members(m[live], np.ascontiguousarray(tables[e][:, live]), sig[live], clp[live], hyper)
+            stats[e * steps:(e + 1) * steps, live] = got
+            epochs[live] += 1
+            if target_kl is not None:
+                over = np.zeros(m.size, dtype=bool)
+                over[live] = np.mean(got[:, :, 2], axis=0) > float(target_kl)
+                live &= ~over
+        return stats, epochs
 
     def layers(self, g):
         """Network g as the device holds it now: [(W, b), ...] float32, by download (clothhip_get_policy_mlp)."""

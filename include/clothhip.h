@@ -678,7 +678,7 @@ int clothhip_fit_data_gae(clothhip_handle *h, int64_t first, int64_t n, const Cl
  * network over the rows [first, first + n) -- the launches of clothhip_policy_fit_predict, in chunks of at most
  * CLOTHHIP_FIT_MAX_BATCH -- and stores y into the column where it lies: nothing is downloaded, and the stored bytes are those
  * clothhip_policy_fit_predict returns for these rows. Its refusals are clothhip_policy_fit_predict's (CLOTHHIP_ESTATE: a launch in
- * flight, no shared network, a population on the handle -- per-member old means do not exist --, an empty dataset) and CLOTHHIP_EINVAL
+ * flight, no shared network, a population on the handle -- clothhip_fit_data_snapshot_policy_members below is its snapshot --, an empty dataset) and CLOTHHIP_EINVAL
  * for a range outside the dataset; n == 0 returns 0. clothhip_fit_data_set_old_means writes mu[n][4] (host float32) to the rows and
  * marks them, _get_old_means downloads the column (zeros for a row without an old mean); both are refused as
  * clothhip_fit_data_set_returns is: a range outside the dataset, a value that is not finite, a NULL table with n > 0, a launch in flight.
@@ -765,6 +765,43 @@ int clothhip_fit_data_set_old_log_sigma(clothhip_handle *h, int64_t first, int64
 int clothhip_fit_data_get_old_log_sigma(clothhip_handle *h, int64_t first, int64_t n, float *ls);
 int clothhip_policy_fit_ppo_sigma_grad(clothhip_handle *h, const ClothPpoSigmaParams *q, const int32_t *idx, int32_t B, float *grad_out, float *grad_ls_out, double *stats_out, float *ratio_out);
 int clothhip_policy_fit_ppo_sigma(clothhip_handle *h, const ClothFitParams *p, const ClothPpoSigmaParams *q, const int32_t *idx, int32_t n_steps, int32_t B, double *stats_out, float *log_sigma_out);
+
+/* PPO FOR A POPULATION (additive, ABI 7; no reference counterpart): PPO ON THE DEVICE for rows of a population, every
+ * member under its own sigma, clip range and optimizer, all members in the launches of one network -- a sweep over learning rate,
+ * sigma, clip and seed at the cost of one configuration's collection and one grouped fit. Every entry above keeps its bytes and its
+ * refusals (the shared-network entries still refuse a population); a handle that never calls an entry below behaves as before.
+ * THE OLD MEAN OF A ROW is the mean of its BEHAVIOUR policy: of the member that ran the env the row was collected from. The ratio
+ * pi_new / pi_behaviour is defined for any learner, so the dataset's ONE old-mean column serves every member; there is no column per
+ * member and nothing records which member owns a row.
+ * clothhip_fit_data_snapshot_policy_members: member_of_row[n] (host int32) names for every row of [first, first + n) a population
+ * row g >= 0 -- row first + i then gets the trainer's forward of row g on it, the bytes
+ * clothhip_policy_fit_predict_members({g}, 1, {first + i}, 1) returns, and is marked as having an old mean -- or -1: the row is
+ * skipped, its bytes and its mark stay. Nothing is downloaded. The host groups the rows by member (members without rows take no part),
+ * cuts a member's list into segments of at most CLOTHHIP_FIT_MAX_BATCH rows and launches the forward of
+ * clothhip_policy_fit_grad_members over as many segments as CLOTHHIP_FIT_MAX_MEMBER_ROWS holds, shorter segments padded with a row of
+ * their own; one more kernel scatters each member's y to its rows of the column, a 16-byte store per row, nothing for a padded
+ * position. With a log-sigma head on the handle the old-log-sigma column is NOT touched. Refused before the first launch, nothing
+ * changed -- CLOTHHIP_ESTATE: a launch in flight, no network, a shared network, an empty dataset; CLOTHHIP_EINVAL: a range outside the
+ * dataset, member_of_row == NULL with n > 0, an entry < -1 or >= the population's rows (the message names its position). n == 0 or
+ * all entries -1 returns 0.
+ * THE LOSS is PPO ON THE DEVICE's, operation by operation, with member j's own q[j] = {sigma, clip}: the host forms inv_s2,
+ * half_inv_s2, lo, hi of every member in double by the expressions above, and they go up as one table [n_m][4] of which member j's
+ * workgroup reads row j. clothhip_policy_fit_ppo_grad_members is clothhip_policy_fit_grad_members for it: grad_out[n_m][n_params],
+ * stats_out[n_m][3], ratio_out[n_m][B], each may be NULL; nothing is updated. clothhip_policy_fit_ppo_members is
+ * clothhip_policy_fit_members for it: idx[n_steps][n_m][B], stats_out[n_steps][n_m][3] (may be NULL) each member's statistics BEFORE
+ * each step. They use the population's per-row optimizer state: a squared-error group step and a PPO group step of one row share its
+ * moments and its step count, and clothhip_policy_fit_reset_members restarts both.
+ * THE BITS are the twin's, as for FIT ROWS OF A POPULATION: after any sequence of calls, row g, its moments and its step count are
+ * what a second handle holds that carries g as its shared network, stores the same dataset, weights and old means and received
+ * clothhip_policy_fit_ppo(p[j], q[j], idx[:, j, :]).
+ * Refused before the first launch, nothing changed -- everything clothhip_policy_fit_members refuses; CLOTHHIP_EINVAL: q == NULL,
+ * sigma_j or clip_j outside clothhip_policy_fit_ppo's domain (the message names j); CLOTHHIP_ESTATE: an idx entry whose row has no
+ * old mean (the message names the row and the member). n_steps == 0 returns 0.
+ * OUT OF SCOPE: per-member log-sigma heads, per-member critics, a clipped value loss, per-member normalisation of the advantages on
+ * the device (the host normalises: demos.ppo_fit), noise drawn inside the launch. */
+int clothhip_fit_data_snapshot_policy_members(clothhip_handle *h, int64_t first, int64_t n, const int32_t *member_of_row /* [n] */);
+int clothhip_policy_fit_ppo_grad_members(clothhip_handle *h, const ClothPpoParams *q, const int32_t *members, int32_t n_m, const int32_t *idx, int32_t B, float *grad_out, double *stats_out, float *ratio_out);
+int clothhip_policy_fit_ppo_members(clothhip_handle *h, const ClothFitParams *p, const ClothPpoParams *q, const int32_t *members, int32_t n_m, const int32_t *idx, int32_t n_steps, int32_t B, double *stats_out);
 
 int clothhip_run_actions(clothhip_handle *h, const ClothEpisodeParams *ep, int32_t T, int32_t policy,
                          const double *actions, int32_t actions_on_device, const int32_t *policy_arg,

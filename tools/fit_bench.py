@@ -24,7 +24,12 @@ launch per step: k_fit_loss_ppo in the place of k_fit_loss.
 --ppo-sigma runs the learned-sigma section instead (clothhip_policy_fit_ppo_sigma; profiles/ppo_sigma.txt): on the four
 shapes, an Adam step with the log-sigma head beside the fixed-sigma PPO step, alternated on one handle. The two differ in the loss launch
 (k_fit_loss_ppo_sigma: nine exp_fixed per row in one workgroup, seven reductions) and in one more optimizer launch over the head.
-    python3 tools/fit_bench.py --ppo-sigma [--steps 20] [--rounds 5] [--out FILE]"""
+    python3 tools/fit_bench.py --ppo-sigma [--steps 20] [--rounds 5] [--out FILE]
+--ppo-members runs the grouped PPO section instead (clothhip_policy_fit_ppo_members; profiles/ppo_members.txt): a grouped
+PPO Adam step of G = 1, 4, 16, 64 networks at B = 256, every member under its own sigma and clip, beside the grouped squared-error step
+(--members' call) alternated on the same handle, and beside G single-network PPO steps timed in the same process. The grouped steps
+differ in ONE launch: k_fit_loss_ppo_members in the place of k_fit_loss, one workgroup per member either way.
+    python3 tools/fit_bench.py --ppo-members [--steps 20] [--rounds 5] [--out FILE]"""
 import argparse
 import os
 import sys
@@ -128,6 +133,55 @@ def members_section(args, rows, labels):
     group.close()
 
 
+def ppo_members_section(args, rows, labels):
+    """The grouped PPO step (clothhip_policy_fit_ppo_members) at B = 256: ms per grouped Adam step of G networks beside
+    the grouped squared-error step of the same handle, rows and tables (alternated), and beside G times the single-network PPO step
+    (clothhip_policy_fit_ppo on a shared-network handle in this process). Old means from one member snapshot, row i under member i % G."""
+    single, group = (ClothBatch(bench.bench_cfg(25, 0.02, "tier1"), n_envs=1, precision="f32") for _ in range(2))
+    adv = np.random.RandomState(9).normal(size=len(rows)).astype(np.float32)
+    for x in (single, group):
+        x.fit_append(rows, labels, weights=adv)
+    B = 256
+    r = np.random.RandomState(5)
+    say("fit_bench ppo-members: 25x25, B = %d, Adam lr 1e-5, Gaussian advantages, member j under sigma 0.5 + 0.01 j and clip 0.2; %d steps per call, "
+        "%d calls of each kind alternated after one warm-up call; device ms by HIP events around all steps of a call" % (B, args.steps, args.rounds))
+    for hidden in ([64, 64], [256, 256, 256]):
+        widths = [3 * single.P] + hidden + [4]
+        single.set_policy_mlp(layers_of(widths))
+        single.fit_snapshot_policy()
+        table = r.randint(0, args.rows, size=(args.steps, B)).astype(np.int32)
+        single.fit_ppo(table, 0.5, 0.2, lr=1e-5)
+        dev1 = []
+        for _ in range(args.rounds):
+            single.fit_ppo(table, 0.5, 0.2, lr=1e-5)
+            dev1.append(single.last_kernel_ms / args.steps)
+        s1, spread = float(np.median(dev1)), max(dev1) - min(dev1)
+        say("hidden %-15r single-network PPO: device %.3f ms/step (the %d calls: %s; spread %.3f)"
+            % (hidden, s1, args.rounds, " ".join("%.3f" % d for d in dev1), spread))
+        for G in (1, 4, 16, 64):
+            group.set_policy_population([layers_of(widths, seed=7 + g) for g in range(G)], np.zeros(1, dtype=np.int32))
+            group.fit_snapshot_policy_members(np.arange(args.rows, dtype=np.int32) % G)
+            snap_ms = group.last_kernel_ms
+            members, sigma = np.arange(G), 0.5 + 0.01 * np.arange(G)
+            tbl = r.randint(0, args.rows, size=(args.steps, G, B)).astype(np.int32)
+            hyper = dict(lr=1e-5)
+            group.fit_members(members, tbl, hyper)
+            group.fit_ppo_members(members, tbl, sigma, 0.2, hyper)
+            mse, ppo = [], []
+            for _ in range(args.rounds):
+                group.fit_members(members, tbl, hyper)
+                mse.append(group.last_kernel_ms / args.steps)
+                stats = group.fit_ppo_members(members, tbl, sigma, 0.2, hyper)
+                ppo.append(group.last_kernel_ms / args.steps)
+            m, p = float(np.median(mse)), float(np.median(ppo))
+            say("hidden %-15r G %2d: grouped squared error %.3f ms/step (min %.3f, max %.3f) | grouped PPO %.3f ms/step (min %.3f, max %.3f) | PPO / "
+                "squared error = %.3f | G single PPO steps %.3f ms (+- %.3f) -> grouped / (G x single) = %.3f; member snapshot of %d rows %.3f ms; "
+                "last mean clip_fraction %.3f, kl %.5f" % (hidden, G, m, min(mse), max(mse), p, min(ppo), max(ppo), p / m, G * s1, G * spread,
+                                                         p / (G * s1), args.rows, snap_ms, stats[-1, :, 1].mean(), stats[-1, :, 2].mean()))
+    single.close()
+    group.close()
+
+
 def ppo_section(args, b, rows, labels):
     """A PPO Adam step beside the squared-error step: the same handle, network, rows and minibatch table, `--rounds` calls of `--steps`
     steps each after one warm-up call, alternated; Gaussian advantages in the weight column, old means from one snapshot."""
@@ -194,15 +248,16 @@ def main():
     ap.add_argument("--members", action="store_true", help="run the members section (the grouped trainer) instead of the single-network one")
     ap.add_argument("--ppo", action="store_true", help="run the PPO section (a clipped-surrogate step beside the squared-error step) instead")
     ap.add_argument("--ppo-sigma", action="store_true", help="run the learned-sigma section (a step with the log-sigma head beside the fixed-sigma PPO step) instead")
+    ap.add_argument("--ppo-members", action="store_true", help="run the grouped PPO section (a grouped clipped-surrogate step beside the grouped squared-error step) instead")
     ap.add_argument("--out", default=None, help="also append the printed lines to this file")
     args = ap.parse_args()
     b = ClothBatch(bench.bench_cfg(25, 0.02, "tier1"), n_envs=1, precision="f32")
     r = np.random.RandomState(3)
     rows = r.uniform(-1, 1, size=(args.rows, 3 * b.P)).astype(np.float32)
     labels = r.uniform(-1, 1, size=(args.rows, 4)).astype(np.float32)
-    if args.members:
+    if args.members or args.ppo_members:
         b.close()
-        members_section(args, rows, labels)
+        (ppo_members_section if args.ppo_members else members_section)(args, rows, labels)
         if args.out:
             with open(args.out, "a") as fh:
                 fh.write("\n".join(LINES) + "\n")

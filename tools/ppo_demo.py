@@ -14,9 +14,16 @@ With --learn-sigma the PPO run carries a log-sigma head that sta
 minus --ent-coef times the entropy: its collections act with unit noise times the head's present sigma, the one snapshot stores the old
 means and the old log sigmas, and every iteration's line adds the sigma it acted with; the weighted regression beside it keeps --sigma.
 --bench then also times the snapshot with a head on the handle (one more fill kernel). profiles/ppo_sigma.txt holds runs.
+With --members G it runs a SWEEP instead: G = len(--lrs) x len(--sigmas) x len(--seeds) configurations as the members of
+ONE MLPEnsemble on one env of G x --envs cloths, member g on every G-th env. Per iteration ONE collection (unit noise times the member's
+sigma per env), one fit_gae under a shared critic, one member snapshot and one grouped PPO fit (demos.ppo_fit with the ensemble); it
+prints one return curve per member: the mean return of the episodes its envs completed, per iteration, with the epochs it ran. With
+--bench --members G it times the member snapshot of one collection beside the host route. profiles/ppo_members.txt holds runs.
     python3 tools/ppo_demo.py [--envs 64] [--slots 12] [--iters 4] [--epochs 10] [--sigma 0.1] [--clip 0.2] [--target-kl X] [--out FILE]
     python3 tools/ppo_demo.py --learn-sigma [--ent-coef 0.01] [...]
-    python3 tools/ppo_demo.py --bench [--envs 512] [--slots 12] [--out FILE]"""
+    python3 tools/ppo_demo.py --bench [--envs 512] [--slots 12] [--out FILE]
+    python3 tools/ppo_demo.py --members 8 --lrs 1e-3,3e-4,1e-4,3e-5 --sigmas 0.1 --seeds 0,1 [--envs 64] [--iters 4] [--target-kl X] [--out FILE]
+    python3 tools/ppo_demo.py --bench --members 16 [--envs 512] [--slots 12] [--out FILE]"""
 import argparse
 import os
 import sys
@@ -30,7 +37,7 @@ sys.path.insert(0, ROOT)
 import bench                                          # noqa: E402
 from gym_cloth_amd.demos import actor_critic_collect, actor_critic_fit, ppo_fit      # noqa: E402
 from gym_cloth_amd.envs import ClothVecEnv            # noqa: E402
-from gym_cloth_amd.policies import MLPPolicy, MLPTrainer, ValueTrainer                # noqa: E402
+from gym_cloth_amd.policies import MLPEnsemble, MLPPolicy, MLPTrainer, ValueTrainer   # noqa: E402
 
 LINES = []
 
@@ -128,6 +135,94 @@ def run(args):
         v.close()
 
 
+def sweep(args):
+    """--members: the configurations lr x sigma x seed as the members of one ensemble; one return curve per member."""
+    from gym_cloth_amd.demos import _collection_returns
+    lrs, sigmas, seeds = ([t(x) for x in v.split(",") if x] for v, t in ((args.lrs, float), (args.sigmas, float), (args.seeds, int)))
+    configs = [(lr, sg, sd) for lr in lrs for sg in sigmas for sd in seeds]
+    G = len(configs)
+    if G != args.members:
+        raise SystemExit("--members %d, but --lrs x --sigmas x --seeds names %d configurations" % (args.members, G))
+    per, T = args.envs, args.slots
+    E = G * per
+    hidden = [int(w) for w in args.hidden.split(",") if w]
+    env = make_env(E)
+    widths = [3 * env.P] + hidden
+    lr, sigma = np.array([c[0] for c in configs]), np.array([c[1] for c in configs])
+    ens = MLPEnsemble(env, [make_layers(widths + [4], seed=c[2]) for c in configs], optimizer="adam", lr=lr)
+    critic = ValueTrainer(env, make_layers(widths + [1], seed=1), optimizer="adam", lr=args.lr)
+    say("ppo sweep: %d members x %d cloths 25x25 fp32 tier 1 (force_grab) on ONE env, member g on envs g, g + %d, ...; policy and shared critic hidden "
+        "%r, %d slots per iteration in one launch; GAE gamma %g lambda %g, advantages normalised per member on the host; critic Adam lr %g, %d steps; "
+        "then up to %d epochs of minibatches of %d rows per member in grouped launches (clip %g, target_kl %r)"
+        % (G, per, G, hidden, T, args.gamma, args.lam, args.lr, args.value_steps, args.epochs, args.batch, args.clip, args.target_kl))
+    curves, ran = np.full((G, args.iters), np.nan), np.zeros((G, args.iters), dtype=int)
+    for i in range(args.iters):
+        unit = np.random.RandomState(100 + i).normal(size=(T, E, 4))
+        env.seed([2000 + e // G for e in range(E)])                           # every iteration from the same start states, the same ones for every member
+        env.reset()
+        try:
+            col = actor_critic_collect(env, ens, n_actions=T, policy_noise=unit * sigma[ens.member][None, :, None], slots_per_launch=T)
+        except ValueError as e:
+            say("iteration %d: the collection was refused (%s): the run ends here" % (i, e))
+            break
+        Gt, complete, _, starts = _collection_returns(col, T, 1.0, E)
+        who = ens.member[col["row_env"]]
+        t0 = time.perf_counter()
+        fit = ppo_fit(env, ens, critic, col, sigma=sigma, gamma=args.gamma, lam=args.lam, clip=args.clip, n_value_steps=args.value_steps,
+                      n_epochs=args.epochs, batch_size=args.batch, seed=i, target_kl=args.target_kl)
+        dt = time.perf_counter() - t0
+        for j, g in enumerate(fit["members"]):
+            curves[g, i], ran[g, i] = mean(Gt[starts & complete & (who == g)]), fit["epochs"][j]
+        kl = np.nanmean(fit["ppo_stats"][:, :, 2], axis=0) if len(fit["ppo_stats"]) else np.zeros(0)
+        say("iteration %d: %d rows + %d leaves, %d completed episodes, fit %.0f ms (collection %.0f ms); mean kl per member %s"
+            % (i, col["appended"], col["open_rows"], len(col["episode_return"]), dt * 1e3, col["took"] * 1e3, " ".join("%.4f" % k for k in kl)))
+    for g, (l, sg, sd) in enumerate(configs):
+        say("member %2d lr %-8g sigma %-6g seed %d: mean return per iteration %s | epochs %s"
+            % (g, l, sg, sd, " ".join("%.4f" % c for c in curves[g]), " ".join("%d" % e for e in ran[g])))
+    env.close()
+
+
+def bench_members_section(args, reps=10):
+    """--bench --members G: the member snapshot of one collection beside fit_predict per member plus ONE fit_set_old_means through the host."""
+    E, T, G = args.envs, args.slots, args.members
+    env = make_env(E)
+    for e in range(E):
+        env.np_randoms[e] = np.random.RandomState(1000 + e)
+    env.reset()
+    ens = MLPEnsemble(env, [make_layers([3 * env.P, 64, 64, 4], seed=7 + g) for g in range(G)])
+    b = env.batch
+    col = actor_critic_collect(env, ens, n_actions=T, slots_per_launch=T)
+    n = col["appended"] + col["open_rows"]
+    mor = np.where(col["leaf"], -1, ens.member[col["ds_env"]]).astype(np.int32)
+    say("member snapshot bench: the %d rows (%d of them leaves, skipped) of one %d x %d-slot collection (25x25, policy hidden [64, 64]) under G = %d "
+        "members; %d repetitions each, medians" % (n, col["open_rows"], E, T, G, reps))
+    b.fit_snapshot_policy_members(mor)
+    kern, wall = [], []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        b.fit_snapshot_policy_members(mor)
+        wall.append(time.perf_counter() - t0)
+        kern.append(b.last_kernel_ms * 1e-3)
+    say("    clothhip_fit_data_snapshot_policy_members, nothing downloaded: device (the grouped forward + the scatter) %s, call %s" % (stats(kern), stats(wall)))
+    dev = b.fit_get_old_means()
+    parts = {"predict": [], "upload": [], "all": []}
+    lists = [np.nonzero(mor == g)[0] for g in range(G)]
+    for _ in range(reps):
+        y = np.zeros((n, 4), dtype=np.float32)
+        t0 = time.perf_counter()
+        for g, mine in enumerate(lists):
+            if len(mine):
+                y[mine] = b.fit_predict(mine, [g])[0]
+        t1 = time.perf_counter()
+        b.fit_set_old_means(y)                                               # (the leaves get zeros and a mark on this route)
+        t2 = time.perf_counter()
+        for k, d in zip(("predict", "upload", "all"), (t1 - t0, t2 - t1, t2 - t0)):
+            parts[k].append(d)
+    say("    the host route: G fit_predict calls with their downloads %s, fit_set_old_means %s; together %s" % tuple(stats(parts[k]) for k in ("predict", "upload", "all")))
+    say("    both routes leave the same bytes in the old-mean column: %s" % (dev.tobytes() == b.fit_get_old_means().tobytes()))
+    env.close()
+
+
 def bench_section(args, reps=10):
     E, T = args.envs, args.slots
     env = make_env(E)
@@ -193,12 +288,20 @@ def main():
     ap.add_argument("--learn-sigma", action="store_true", help="the PPO run trains a log-sigma head that starts at log(--sigma)")
     ap.add_argument("--ent-coef", type=float, default=0.0, help="with --learn-sigma: the coefficient of the entropy bonus")
     ap.add_argument("--bench", action="store_true", help="measure the snapshot on the device against the host route")
+    ap.add_argument("--members", type=int, default=0, help="run a sweep of this many configurations as the members of one ensemble (--lrs x --sigmas x --seeds)")
+    ap.add_argument("--lrs", default="1e-3", help="with --members: the members' Adam learning rates, comma-separated")
+    ap.add_argument("--sigmas", default="0.1", help="with --members: the members' exploration sigmas, comma-separated")
+    ap.add_argument("--seeds", default="0", help="with --members: the seeds of the members' initial networks, comma-separated")
     ap.add_argument("--out", default=None, help="also append the printed lines to this file")
     args = ap.parse_args()
     if args.envs is None:
         args.envs = 512 if args.bench else 64
-    if args.bench:
+    if args.bench and args.members:
+        bench_members_section(args)
+    elif args.bench:
         bench_section(args)
+    elif args.members:
+        sweep(args)
     else:
         run(args)
     if args.out:
