@@ -259,6 +259,8 @@ SYMBOLS = [
                                                        C.POINTER(C.c_float)]),
     ("clothhip_policy_fit_ppo_members", C.c_int, [_vp, C.POINTER(ClothFitParams), C.POINTER(ClothPpoParams), _i32p, C.c_int32, _i32p, C.c_int32, C.c_int32,
                                                   _dp]),
+    ("clothhip_policy_noise_fill", C.c_int, [_vp, C.c_uint64, C.c_int32, C.POINTER(C.c_int64), _dp, C.c_int32, C.POINTER(_vp)]),
+    ("clothhip_policy_noise_get", C.c_int, [_vp, C.c_int32, _dp]),
     ("clothhip_plan_cem", C.c_int, [_vp, _vp, C.POINTER(ClothEpisodeParams), C.POINTER(ClothPlanParams), _i32p, _u8p, _dp, _dp, _dp, _dp,
                                     _dp, _dp]),
     ("clothhip_plan_sample", C.c_int, [_vp, C.POINTER(ClothPlanParams), _dp, _dp, C.c_int32, C.c_int32, _dp, _dp, _dp]),
@@ -294,6 +296,7 @@ SYMBOLS = [
     ("clothhip_selftest_rng", C.c_int, [_vp, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, _dp]),
     ("clothhip_selftest_depth8", C.c_int, [C.POINTER(C.c_float), C.c_int32, C.c_int64, _u8p]),
     ("clothhip_selftest_exp_fixed", C.c_int, [_dp, C.c_int64, _dp]),
+    ("clothhip_selftest_normal_fixed", C.c_int, [C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_int64, _dp]),
     ("clothhip_selftest_render_plan", C.c_int, [_PP, C.c_int32, C.c_int32, _i32p]),
     ("clothhip_selftest_arith", C.c_int, [C.c_int32, C.c_int32, _dp, _dp, _dp, C.c_int64]),
 ]

@@ -45,6 +45,54 @@ class PolicyBindings(object):
         check(self._L.clothhip_get_policy_log_sigma(self._h, _lib.fp(out)))
         return out
 
+    def policy_noise_fill(self, seed, n_actions, sigma=None, slot_base=None):
+        """Fill the handle's exploration-noise table float64 [n_actions, E, 4] on the device (clothhip_policy_noise_fill) and return
+        where it lies, an int: what run_actions_begin(policy=POLICY_MLP, actions_device_ptr=...) takes. [t, e, k] = sigma[e, k] *
+        z_k(seed, e, slot_base[e] + t), z the standard normals of references.normal_fixed_reference -- policy_noise_reference restates
+        the table bit for bit. sigma: a scalar, [4] or [E, 4], finite and >= 0; None: the log-sigma head of set_policy_log_sigma, read
+        where it lies as exp_fixed of its float32 values (ClothHipError without one). slot_base int[E] >= 0, None: zeros. The fill runs
+        on the batch's stream, so the launch that follows needs no synchronisation; the table belongs to the batch and stays valid
+        until the next fill. Refused (ClothHipError) while a launch is in flight."""
+        seed, T = int(seed), int(n_actions)
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError("seed must lie in [0, 2^64)")
+        if T < 1 or T * self.E > 2 ** 31 - 1:
+            raise ValueError("n_actions = %d: at least 1, and n_actions * E at most 2^31 - 1" % T)
+        sg, rows = None, 0
+        if sigma is not None:
+            sg = np.asarray(sigma, dtype=np.float64)
+            if sg.ndim == 0:
+                sg = np.full(4, float(sg))
+            if sg.shape not in ((4,), (self.E, 4)):
+                raise ValueError("sigma must be a scalar, [4] or [%d, 4] (got shape %r)" % (self.E, sg.shape))
+            if not np.isfinite(sg).all() or (sg < 0.0).any():
+                raise ValueError("sigma must be finite and >= 0")
+            rows = 1 if sg.ndim == 1 else self.E
+            sg = np.ascontiguousarray(sg)
+        base = None
+        if slot_base is not None:
+            b = np.asarray(slot_base)
+            if b.shape != (self.E,) or not np.issubdtype(b.dtype, np.integer):
+                raise ValueError("slot_base must be %d integers" % self.E)
+            if b.size and (int(b.min()) < 0 or int(b.max()) > 2 ** 63 - 1 - T):
+                raise ValueError("slot_base must be >= 0 (and slot_base + n_actions below 2^63)")
+            base = np.ascontiguousarray(b, dtype=np.int64)
+        ptr = C.c_void_p()
+        check(self._L.clothhip_policy_noise_fill(self._h, seed, T, None if base is None else base.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                 _lib.dp(sg), rows, C.byref(ptr)))
+        self._noise_T = T
+        return int(ptr.value)
+
+    def policy_noise_get(self):
+        """float64 [n_actions, E, 4]: the table of the last policy_noise_fill, downloaded (clothhip_policy_noise_get). ValueError before
+        any fill."""
+        T = getattr(self, '_noise_T', 0)
+        if T < 1:
+            raise ValueError("no noise table on this batch: call policy_noise_fill first")
+        out = np.zeros((T, self.E, 4), dtype=np.float64)
+        check(self._L.clothhip_policy_noise_get(self._h, T, _lib.dp(out)))
+        return out
+
     def policy_eval(self, obs=None):
         """The handle's network on float32 '1d' observations obs [n, 3P], or with obs=None on every env's present state: float64
         [n, 4], the network's output before noise and clipping, computed by the device function the episode launch runs

@@ -192,6 +192,12 @@ struct clothhip_handle : HostPlan {
         // it); setting or dropping a network leaves it alone, no launch reads it: the trainer's loss kernel and its optimizer do (api_fit.hip)
         Buffer<float> d_log_sigma;
         bool has_log_sigma = false;
+        // clothhip_policy_noise_fill: the exploration noise double [noise_T][E][4] (noise_T 0: none), which the next episode launch may be
+        // given as its device-resident table, and the uploaded sigma [rows][4] and slot_base [E] of the last fill; valid until the next
+        // fill or destroy. clothhip_policy_noise_fill reads d_log_sigma where it lies.
+        Buffer<double> d_noise, d_noise_sigma;
+        Buffer<int64_t> d_noise_base;
+        int32_t noise_T = 0;
     } pol;
     // The value network (api_policy.hip: clothhip_set_value_mlp), beside the policy and independent of it: n_layers 0: none; mlp.params =
     // d_mlp, no member map, stride 0 -- to the trainer (api_fit.hip) a weight table of ONE row. No launch evaluates it.

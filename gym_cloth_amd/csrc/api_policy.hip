@@ -2,11 +2,13 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 
 #include "api_handle.hpp"
 #include "cloth_policy_eval.hpp"
 #include "cloth_policy_label.hpp"
+#include "cloth_policy_noise.hpp"
 #include "cloth_policy_population.hpp"
 
 // ---- a learned policy: the handle's network (cloth_policy_mlp.hpp) ----------------------------------------------------------------------
@@ -79,6 +81,63 @@ extern "C" int clothhip_get_policy_log_sigma(clothhip_handle *h, float *out) {
     if (!out) return fail(CLOTHHIP_EINVAL, "out is NULL");
     HIPCHECK(hipSetDevice(h->device));
     HIPCHECK(hipMemcpyAsync(out, h->pol.d_log_sigma, MLP_OUT * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// ---- the exploration noise (clothhip.h: EXPLORATION NOISE ON THE DEVICE; cloth_policy_noise.hpp): the handle's table, filled on its stream --
+extern "C" int clothhip_policy_noise_fill(clothhip_handle *h, uint64_t seed, int32_t T, const int64_t *slot_base, const double *sigma,
+                                          int32_t sigma_rows, void **d_noise) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (int rc = check_idle(h)) return rc;          // (that launch may be reading the table)
+    if (T < 1) return fail(CLOTHHIP_EINVAL, "T = %d: a table has at least one slot", T);
+    const int64_t n = (int64_t)T * h->E;
+    if (n > INT32_MAX) return fail(CLOTHHIP_EINVAL, "T * E = %lld slots: more than 2^31 - 1", (long long)n);
+    const bool head = !sigma;
+    if (head && sigma_rows != 0) return fail(CLOTHHIP_EINVAL, "sigma_rows = %d without a sigma table (0: the handle's log-sigma head)", sigma_rows);
+    if (!head && sigma_rows != 1 && sigma_rows != h->E)
+        return fail(CLOTHHIP_EINVAL, "sigma_rows = %d: 1 (one sigma[4] for all envs) or %d (one per env)", sigma_rows, h->E);
+    for (int64_t i = 0; !head && i < (int64_t)sigma_rows * MLP_OUT; i++)
+        if (!std::isfinite(sigma[i]) || sigma[i] < 0.0) return fail(CLOTHHIP_EINVAL, "sigma[%lld][%d] = %g: a sigma is finite and not negative", (long long)(i / MLP_OUT), (int)(i % MLP_OUT), sigma[i]);
+    if (head && !h->pol.has_log_sigma) return fail(CLOTHHIP_ESTATE, "no log-sigma head on this handle: call clothhip_set_policy_log_sigma first, or pass sigma");
+    for (int e = 0; slot_base && e < h->E; e++)
+        if (slot_base[e] < 0 || slot_base[e] > INT64_MAX - T) return fail(CLOTHHIP_EINVAL, "slot_base[%d] = %lld: a slot number is not negative (and slot_base + T fits 63 bits)", e, (long long)slot_base[e]);
+    HIPCHECK(hipSetDevice(h->device));
+    h->pol.noise_T = 0;                             // from here on the old table is gone: a failure below leaves the handle without one
+    if (int rc = h->pol.d_noise.reserve((size_t)n * MLP_OUT * 8)) return rc;
+    PolicyNoiseArgs a;
+    memset(&a, 0, sizeof(a));
+    a.out = h->pol.d_noise; a.seed = seed; a.n = n; a.E = h->E; a.sigma_rows = sigma_rows;
+    if (head) a.log_sigma = h->pol.d_log_sigma;
+    else {
+        if (int rc = h->pol.d_noise_sigma.reserve((size_t)sigma_rows * MLP_OUT * 8)) return rc;
+        HIPCHECK(hipMemcpyAsync(h->pol.d_noise_sigma, sigma, (size_t)sigma_rows * MLP_OUT * 8, hipMemcpyHostToDevice, h->stream));
+        a.sigma = h->pol.d_noise_sigma;
+    }
+    if (slot_base) {
+        if (int rc = h->pol.d_noise_base.reserve((size_t)h->E * 8)) return rc;
+        HIPCHECK(hipMemcpyAsync(h->pol.d_noise_base, slot_base, (size_t)h->E * 8, hipMemcpyHostToDevice, h->stream));
+        a.slot_base = h->pol.d_noise_base;
+    }
+    if (!head || slot_base) HIPCHECK(hipStreamSynchronize(h->stream));      // the host tables are never retained (the head route uploads nothing and waits for nothing)
+    HIPCHECK(hipEventRecord(h->ev0, h->stream));
+    hipLaunchKernelGGL(k_policy_noise_fill, dim3((unsigned)((n + NOISE_THREADS - 1) / NOISE_THREADS)), dim3(NOISE_THREADS), 0, h->stream, a);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipEventRecord(h->ev1, h->stream));
+    h->have_timing = true;                          // clothhip_last_kernel_ms: this kernel
+    h->pol.noise_T = T;
+    if (d_noise) *d_noise = (double *)h->pol.d_noise;
+    return 0;
+}
+
+extern "C" int clothhip_policy_noise_get(clothhip_handle *h, int32_t T, double *out) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (int rc = check_idle(h)) return rc;
+    if (h->pol.noise_T < 1) return fail(CLOTHHIP_ESTATE, "no noise table on this handle: call clothhip_policy_noise_fill first");
+    if (T != h->pol.noise_T) return fail(CLOTHHIP_EINVAL, "T = %d, the last clothhip_policy_noise_fill made %d slots", T, h->pol.noise_T);
+    if (!out) return fail(CLOTHHIP_EINVAL, "out is NULL");
+    HIPCHECK(hipSetDevice(h->device));
+    HIPCHECK(hipMemcpyAsync(out, h->pol.d_noise, (size_t)T * h->E * MLP_OUT * 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(hipStreamSynchronize(h->stream));
     return 0;
 }

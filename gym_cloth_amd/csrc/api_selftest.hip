@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "api_handle.hpp"
+#include "cloth_philox.hpp"
 #include "cloth_selftest_kernel.hpp"
 
 extern "C" int clothhip_selftest_windows(const ClothParams *p, int32_t *n_windows, int32_t *n_slots, int32_t *reach_shift,
@@ -67,6 +68,12 @@ extern "C" int clothhip_selftest_rng(uint32_t *state, int32_t kind, int32_t n, d
         }
     }
     if (kind == 5) mt_skip_serial(state, (uint64_t)a);
+    return 0;
+}
+
+extern "C" int clothhip_selftest_normal_fixed(uint64_t seed, const uint32_t *env, const uint64_t *slot, int64_t n, double *out) {
+    if (n < 0 || (n > 0 && (!env || !slot || !out))) return fail(CLOTHHIP_EINVAL, "bad argument");
+    for (int64_t i = 0; i < n; i++) normal_fixed(seed, env[i], slot[i], out + 4 * i);
     return 0;
 }
 

@@ -51,6 +51,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "cloth_exp_fixed.hpp"      // exp_fixed: the one exponential of the PPO losses below
+
 namespace clothhip {
 
 constexpr int FIT_MAX_BATCH = 4096;       // = CLOTHHIP_FIT_MAX_BATCH
@@ -217,31 +219,6 @@ template <int W> __global__ __launch_bounds__(256) void k_fit_loss(const float *
         __syncthreads();
     }
     if (tid == 0) loss[j] = red[0] / (double)((W == 4 ? 4 : 2) * (int64_t)B);
-}
-
-// exp(x) for x clamped to [-40, 40], made of plain double operations, each ONE rounding (no library exp, no contraction), so that numpy
-// restates it bit for bit (policies.exp_fixed_reference) and the host runs the very function (clothhip_selftest_exp_fixed):
-//   k = rint(x log2e);  r = (x - k ln2_hi) - k ln2_lo  (fdlibm's two constants: k ln2_hi is exact for |k| <= 58);  p = Horner over the
-//   Taylor coefficients 1 / i!, i = 13 .. 0 (|r| <= 0.3466: the remainder is below 4e-18 of p);  p 2^k, the power built from its bits.
-// Within 2.2e-16 relative of exp over [-40, 40]; exp_fixed(0) == 1.0 exactly (k = 0, r = 0, p = 1). x must not be NaN.
-__host__ __device__ inline double exp_fixed(double x) {
-    x = x < -40.0 ? -40.0 : x;
-    x = x > 40.0 ? 40.0 : x;
-    const double k = __builtin_rint(x * 1.44269504088896338700e+00);
-    const double hi = k * 6.93147180369123816490e-01, lo = k * 1.90821492927058770002e-10;
-    const double xh = x - hi, r = xh - lo;
-    const double c[14] = {1.0, 1.0, 1.0 / 2.0, 1.0 / 6.0, 1.0 / 24.0, 1.0 / 120.0, 1.0 / 720.0, 1.0 / 5040.0, 1.0 / 40320.0, 1.0 / 362880.0,
-                          1.0 / 3628800.0, 1.0 / 39916800.0, 1.0 / 479001600.0, 1.0 / 6227020800.0};
-    double p = c[13];
-#pragma unroll
-    for (int i = 12; i >= 0; i--) {
-        const double pr = p * r;
-        p = pr + c[i];
-    }
-    const uint64_t bits = (uint64_t)(1023 + (int)k) << 52;      // 2^k, k in [-58, 58]
-    double scale;
-    __builtin_memcpy(&scale, &bits, 8);
-    return p * scale;
 }
 
 // PPO's clipped surrogate of a fixed-sigma Gaussian policy in the place of k_fit_loss<4> (clothhip.h: PPO ON THE DEVICE has the

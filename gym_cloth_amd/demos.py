@@ -12,6 +12,7 @@ with the '1d' observation (cloth_env.py:196-200) as float32[3P] on the device pa
 obs='rgb' / 'depth' / 'rgbd', the image observation the reference's shipped configurations record (uint8 [H, W, C], rendered on
 the device for every slot of a launch: ClothVecEnv.step_many(images=...)).
 """
+import copy
 import pickle
 
 import numpy as np
@@ -219,7 +220,10 @@ def _collect_loop(env, trainer, n_actions, slots_per_launch, time_budget_ms, pol
     tables on the device until every env has run n_actions slots; per launch the rows that ran (and lie within the n_actions) go to
     append(rows int32[n, 3] in [t][e] order, slot int[n]: their per-env slot numbers, out: the launch's step_many dict), then the held
     rows move on. launch_kw(idx, ee):
-    further step_many keywords for the table rows idx [T, E]; record_keys: further [T, E] arrays of step_many's dict to keep per launch."""
+    further step_many keywords for the table rows idx [T, E]; record_keys: further [T, E] arrays of step_many's dict to keep per launch.
+    policy_noise: float64 [n_actions, E, 4], or a policies.DeviceNoise -- then every launch's table is filled on the device with
+    slot_base = the slots each env has run, so the noise of env e's slot i is the same whatever slots_per_launch and time_budget_ms cut the
+    collection into (a slot past n_actions, which is not appended, gets the noise of its own number, not the last row again)."""
     import time
     from .envs import hold_sources, slot_start_sources
     if trainer.env is not env:
@@ -229,6 +233,9 @@ def _collect_loop(env, trainer, n_actions, slots_per_launch, time_budget_ms, pol
         raise ValueError("n_actions and slots_per_launch must be >= 1")
     if env.batch.in_flight().any():
         raise ValueError("an earlier time-sliced launch left operations parked on this env: complete or drop them before collecting")
+    device_noise = None
+    if hasattr(policy_noise, 'fill') and hasattr(policy_noise, 'advance'):      # policies.DeviceNoise: this collection's slots 0 .. of every env, numbered on
+        device_noise, policy_noise = copy.copy(policy_noise), None               # a copy of it -- the caller's running slot_base is left alone
     noise = None if policy_noise is None else np.asarray(policy_noise, dtype=np.float64)
     if noise is not None and noise.shape != (N, E, 4):
         raise ValueError("policy_noise must have shape (%d, %d, 4)" % (N, E))
@@ -243,8 +250,10 @@ def _collect_loop(env, trainer, n_actions, slots_per_launch, time_budget_ms, pol
             raise RuntimeError("%d launches and the envs have run %r of %d slots" % (res['launches'], used.tolist(), N))
         slot = used[None, :] + np.arange(T)[:, None]                        # [T, E]: the per-env slot number of every slot of this launch
         idx = np.minimum(slot, N - 1)                                       # past the end: the last row again (not appended)
+        if device_noise is not None:
+            device_noise.slot_base = used.copy()                                # row t of env e is ITS slot used[e] + t, whatever the launches before ran
         out = env.step_many(policy='mlp', n_actions=T, want_obs='device', time_budget_ms=time_budget_ms,
-                            policy_noise=None if noise is None else noise[idx, ee], **launch_kw(idx, ee))
+                            policy_noise=device_noise if noise is None else noise[idx, ee], **launch_kw(idx, ee))
         res['kernel_ms'] += float(env.batch.last_kernel_ms)
         res['op_ticks'].append(out['op_ticks'])
         ran = out['ran']

@@ -29,13 +29,18 @@ _REWARD_THRESHOLDS = {           # cloth_env.py:42-50
 }
 _EPS = 1e-5                      # cloth_env.py:52
 
-# What step_many's arguments come to (ClothVecEnv._parse_launch): the policy code, T, the actions / noise table, policy_arg, the expert
+# What step_many's arguments come to (ClothVecEnv._parse_launch): the policy code, T, the actions / noise table (or the DeviceNoise that makes it), policy_arg, the expert
 # and its tables, the reset capacity R and where resets come from, what to return.
 _Launch = collections.namedtuple('_Launch', 'pol T actions actions_device_ptr policy_arg expert expert_mix expert_choices R dev_reset '
-                                            'use_rng want_obs images image_kw time_budget_ms')
+                                            'use_rng want_obs images image_kw time_budget_ms device_noise')
 # What goes to the device with a launch and comes back changed in place (ClothVecEnv._export_streams): reset scripts or MT19937
 # images (+ their copy from before, export_mt's token), the envs' step counters and episode-over flags.
 _Flight = collections.namedtuple('_Flight', 'scripts mt mt_before mt_token nsteps done_io')
+
+
+def _is_device_noise(x):
+    """policies.DeviceNoise (or anything with its fill / advance): noise made on the device, not an ndarray table."""
+    return hasattr(x, 'fill') and hasattr(x, 'advance')
 
 
 class Box(object):
@@ -790,7 +795,10 @@ class ClothVecEnv(object):
         pulls in its t-th slot, or policy='mlp' (the network of set_policy, evaluated in the kernel on the cloth's '1d' observation when
         the slot begins -- after an in-kernel reset on the new episode's first state) with n_actions=T and optionally policy_noise
         float64[T, E, 4], added to the network's output of that slot before clipping (exploration noise comes from the caller's table, so
-        the launch stays deterministic; with a time budget the caller passes the unused rows again, as for actions). With auto_reset=False an env whose episode ends idles for the rest of the launch (`ran` False). Up to `max_resets` (default min(T, 255), the
+        the launch stays deterministic; with a time budget the caller passes the unused rows again, as for actions), or a
+        policies.DeviceNoise: the table of this launch's T slots is filled on the device in front of the launch (ClothBatch.policy_noise_fill),
+        row t of env e being that env's slot slot_base[e] + t, and slot_base then moves on by the slots each env ran -- with a time budget
+        the next launch continues every env's own stream, nothing is passed again. With auto_reset=False an env whose episode ends idles for the rest of the launch (`ran` False). Up to `max_resets` (default min(T, 255), the
         launch's limit) resets per env and launch; an env that has used them idles until the launch ends. The resets are drawn on the device from
         each env's numpy RandomState stream (device_rng=True: the states are uploaded before and read back after the
         launch; csrc/cloth_rng.hpp reproduces numpy's MT19937 draws bit for bit; all three tiers, tier 2 rebuilding the
@@ -850,6 +858,8 @@ class ClothVecEnv(object):
         _lap('wait+download')
         out, n_consumed, side_t = self._account_launch(rec, rst, fl.nsteps, fl.done_io, a.dev_reset, a.use_rng, op, labels, a.expert_mix)
         _lap('bookkeeping')
+        if a.device_noise is not None:
+            a.device_noise.advance(out['ran'])                        # every env's next launch goes on with its own next slot
         self._commit_streams(a, fl, rst, n_consumed)
         _lap('rng_commit')
         if a.images is not None:                                      # the launch's tables are still on the device
@@ -877,6 +887,7 @@ class ClothVecEnv(object):
         _policy_mlp, num_points and _delta_actions, and of the batch nothing but E (tests/test_dagger_host.py's _bare_env has no
         more); _init_type and init_side are read only after the refusals that need neither."""
         E = self.E
+        device_noise = None
         if policy in (None, 'table'):
             pol = _lib.POLICY_TABLE
             if actions_device_ptr is None:
@@ -898,7 +909,9 @@ class ClothVecEnv(object):
                 raise ValueError("policy='mlp' needs a network: call set_policy(MLPPolicy(...)) first")
             if actions is not None or actions_device_ptr is not None:
                 raise ValueError("policy='mlp' takes no actions: the network gives them; exploration noise goes into policy_noise")
-            if policy_noise is not None:
+            if _is_device_noise(policy_noise):                                           # policies.DeviceNoise: the table is made on the device (_launch)
+                device_noise = policy_noise
+            elif policy_noise is not None:
                 actions = np.ascontiguousarray(policy_noise, dtype=np.float64)
                 if actions.shape != (T, E, 4):
                     raise ValueError("policy_noise must have shape (%d, %d, 4)" % (T, E))
@@ -927,7 +940,7 @@ class ClothVecEnv(object):
         if pol == _lib.POLICY_HIGHEST_POINT:
             parg = np.concatenate([(np.zeros(E, dtype=np.int32) if parg is None else parg)[None, :], policy_choices], axis=0)
         return _Launch(pol, T, actions, actions_device_ptr, parg, expert, expert_mix, expert_choices, R, dev_reset,
-                       bool(dev_reset and device_rng), want_obs, images, dict(image_kw or {}), time_budget_ms)
+                       bool(dev_reset and device_rng), want_obs, images, dict(image_kw or {}), time_budget_ms, device_noise)
 
     def _export_streams(self, a):
         """Where the launch's resets come from, ready for the device: the next R scripts of every env (host-drawn), or every env's
@@ -945,9 +958,12 @@ class ClothVecEnv(object):
                        np.ascontiguousarray(self._ep_done, dtype=np.uint8))
 
     def _launch(self, a, fl):
+        ptr = a.actions_device_ptr
+        if a.device_noise is not None:                                # this launch's T slots of every env, filled on the batch's stream in front of the launch
+            ptr = a.device_noise.fill(self.batch, a.T)
         self.batch.run_actions_begin(self._episode_params(), a.T, fl.nsteps, fl.done_io, actions=a.actions, policy=a.pol,
                                      policy_arg=a.policy_arg, scripts=fl.scripts, want_obs=a.want_obs,
-                                     actions_device_ptr=a.actions_device_ptr, time_budget_ms=a.time_budget_ms,
+                                     actions_device_ptr=ptr, time_budget_ms=a.time_budget_ms,
                                      rng_states=fl.mt, rng_tier=self._tier,
                                      domrand_words=2 * (3 + self._wd * self._hd * 3) if self._consume_domrand else 0,
                                      reset_capacity=a.R, expert=a.expert, expert_mix=a.expert_mix, expert_choices=a.expert_choices)

@@ -19,17 +19,20 @@ MLPPopulation        no reference counterpart: one MLP per env slot -- G perturb
 CEMPolicy            no reference counterpart: model-predictive control with the simulator as the model -- the cross-entropy method over action
                      sequences, every candidate rolled out on a device-side fork of the env (ClothVecEnv.plan, clothhip_plan_cem);
                      plan_sample_reference / plan_refit_reference / cem_reference restate the planner in numpy, bit for bit
+DeviceNoise          no reference counterpart: the Gaussian exploration noise of an MLP policy made on the device, a pure function of
+                     (seed, env, that env's slot number) -- step_many(policy='mlp', policy_noise=DeviceNoise(seed, sigma)) and the
+                     collections of demos.py; normal_fixed_reference / policy_noise_reference restate it in numpy, bit for bit
 
 The rest lives beside this module and is re-exported here under its old name: mlp.py packs a network for the library and holds the one
 float64 pass of the numpy references; references.py holds those references (fit, value, GAE, exp_fixed, PPO, Adam, SGD, Philox, the
-planner); trainers.py holds MLPTrainer, ValueTrainer and MLPEnsemble, the drivers of the fit on the device.
+planner, the exploration noise); trainers.py holds MLPTrainer, ValueTrainer and MLPEnsemble, the drivers of the fit on the device.
 """
 import numpy as np
 
 from .mlp import MLP_MAX_LAYERS, MLP_MAX_WIDTH, mlp_float64, mlp_forward, pack_mlp, pack_population, population_stride, unpack_mlp  # noqa: F401
 from .references import (NEXT_NONE, NEXT_TERMINAL, _house_sum, _plan_clip, adam_reference, cem_reference, exp_fixed_reference,  # noqa: F401
-                         fit_reference, gae_reference, philox4x32_10, philox_eps, plan_refit_reference, plan_sample_reference,
-                         plan_score_reference, ppo_loss_reference, ppo_reference, ppo_sigma_loss_reference, ppo_sigma_reference, sgd_reference,
+                         fit_reference, gae_reference, log_fixed_reference, normal_fixed_reference, philox4x32_10, philox_eps,
+                         plan_refit_reference, plan_sample_reference, plan_score_reference, policy_noise_reference, ppo_loss_reference, ppo_reference, ppo_sigma_loss_reference, ppo_sigma_reference, sgd_reference,
                          value_fit_reference)
 from .trainers import MLPEnsemble, MLPTrainer, ValueTrainer, ensemble_disagreement  # noqa: F401
 
@@ -217,6 +220,48 @@ class MLPPolicy(object):
         if self.noise_std > 0.0:
             act = act + np.stack([self.draw(e) for e in range(E)])
         return act
+
+
+class DeviceNoise(object):
+    """Gaussian exploration noise made ON THE DEVICE (ClothBatch.policy_noise_fill, clothhip_policy_noise_fill) instead of an ndarray
+    policy_noise: the noise of env e in ITS slot s is sigma[e] * z(seed, e, s), a pure function of (seed, env, slot number) --
+    references.policy_noise_reference restates the table bit for bit. sigma is a scalar, [4] (one per action component), [E, 4] (one
+    row per env: with an MLPEnsemble, DeviceNoise(seed, sigma=sigma_g[ens.member]) gives every member its own), or None: the handle's
+    log-sigma head, read where it lies as exp_fixed of its float32 values -- the sigma PPO's surrogate differentiates; nothing is
+    downloaded. slot_base int64[E] (zeros at first, made on first use) numbers the next slot of every env: step_many fills a launch's
+    T rows from it and then advances it by the slots each env RAN, so successive launches continue one stream per env; the
+    collections of demos.py (dagger_collect, reward_collect, actor_critic_collect) number the slots of one collection 0 .. n_actions - 1
+    themselves and leave slot_base alone. A value object: it holds no device memory, the table belongs to the batch."""
+
+    def __init__(self, seed, sigma=None):
+        self.seed = int(seed)
+        if not 0 <= self.seed < 2 ** 64:
+            raise ValueError("seed must lie in [0, 2^64)")
+        if sigma is not None:
+            sigma = np.array(sigma, dtype=np.float64)
+            if sigma.ndim > 2 or (sigma.ndim >= 1 and sigma.shape[-1] != 4):
+                raise ValueError("sigma must be a scalar, [4] or [E, 4] (got shape %r)" % (sigma.shape,))
+            if not np.isfinite(sigma).all() or (sigma < 0.0).any():
+                raise ValueError("sigma must be finite and >= 0")
+        self.sigma = sigma
+        self.slot_base = None
+
+    def base(self, E):
+        """slot_base as int64[E], zeros before the first launch."""
+        if self.slot_base is None:
+            self.slot_base = np.zeros(int(E), dtype=np.int64)
+        if self.slot_base.shape != (int(E),):
+            raise ValueError("this DeviceNoise has numbered the slots of %d envs, the batch holds %d" % (self.slot_base.size, E))
+        return self.slot_base
+
+    def fill(self, batch, T, slot_base=None):
+        """Fill batch's table for T slots from slot_base (None: the running one) and return the device pointer."""
+        return batch.policy_noise_fill(self.seed, T, sigma=self.sigma, slot_base=self.base(batch.E) if slot_base is None else slot_base)
+
+    def advance(self, ran):
+        """ran bool[T, E] of a launch: every env's slot_base moves on by the slots it ran."""
+        r = np.asarray(ran, dtype=bool)
+        self.slot_base = self.base(r.shape[1]) + r.sum(axis=0).astype(np.int64)
 
 
 def es_coefficients(fitness, sigma, antithetic=True, shaping="centered_rank"):

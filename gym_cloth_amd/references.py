@@ -1,7 +1,8 @@
 """The numpy restatements the GPU tests pin the device to, and that a user can check a fit against: the trainer's three objectives in
 float64 over the one pass of mlp.py (fit_reference, value_fit_reference, ppo_reference, ppo_sigma_reference), and what the device computes
-restated operation by operation, bit for bit (gae_reference, exp_fixed_reference, ppo_loss_reference, ppo_sigma_loss_reference, adam_reference, sgd_reference, Philox and the
-cross-entropy planner's sampling, scoring and refit). numpy and math only; nothing here touches the library."""
+restated operation by operation, bit for bit (gae_reference, exp_fixed_reference, ppo_loss_reference, ppo_sigma_loss_reference, adam_reference, sgd_reference, Philox, the
+cross-entropy planner's sampling, scoring and refit, and the exploration noise made on the device: log_fixed_reference,
+normal_fixed_reference, policy_noise_reference). numpy and math only; nothing here touches the library."""
 import math
 
 import numpy as np
@@ -123,7 +124,7 @@ _EXP_COEF = [1.0 / math.factorial(i) for i in range(14)]      # correctly rounde
 
 def exp_fixed_reference(x):
     """The device's exponential restated in float64 numpy, operation by operation (include/clothhip.h: PPO ON THE DEVICE; csrc/
-    cloth_policy_fit.hpp exp_fixed): x clamped to [-40, 40], k = rint(x log2e), r = (x - k ln2_hi) - k ln2_lo with fdlibm's constants,
+    cloth_exp_fixed.hpp exp_fixed): x clamped to [-40, 40], k = rint(x log2e), r = (x - k ln2_hi) - k ln2_lo with fdlibm's constants,
     Horner over 1 / i! for i = 13 .. 0 with a rounded product and a rounded sum per step, the result scaled by 2^k exactly. Bit for bit
     what the kernel and clothhip_selftest_exp_fixed compute; within 2.2e-16 relative of math.exp, and exactly 1.0 at 0."""
     x = np.minimum(np.maximum(np.asarray(x, dtype=np.float64), -40.0), 40.0)
@@ -311,6 +312,81 @@ def philox_eps(seed, k, i):
     S = sum(x >> np.uint64(8) for x in r)
     D = S.astype(np.int64) - (2 ** 25 - 2)
     return D.astype(np.int32).astype(np.float32) * _EPS_SCALE
+
+
+# ---- the exploration noise (clothhip.h: EXPLORATION NOISE ON THE DEVICE; csrc/cloth_philox.hpp normal_fixed) ------------------------------
+_NORMAL_TAG = 0x4E000000
+_HALF_PI, _SQRT2 = 1.5707963267948966, 1.4142135623730951
+_COS_COEF = [(-1.0) ** i / math.factorial(2 * i) for i in range(11)]          # correctly rounded quotients of exact integers (20!, 21!
+_SIN_COEF = [(-1.0) ** i / math.factorial(2 * i + 1) for i in range(11)]      # are doubles), as the compiler folds them
+_LOG_COEF = [1.0 / (2 * i + 1) for i in range(14)]
+
+
+def log_fixed_reference(u):
+    """log_fixed of csrc/cloth_philox.hpp in float64 numpy, operation by operation, for positive normal u: m 2^k from the bits with m
+    brought into [1/sqrt2, sqrt2), s = (m - 1) / (m + 1), 2 s P(s^2) with P Horner over 1 / (2 i + 1) for i = 13 .. 0, plus k ln2_lo,
+    then plus k ln2_hi. Within 6.2 * 2^-53 relative of log."""
+    u = np.ascontiguousarray(u, dtype=np.float64)            # (a scalar becomes [1])
+    bits = u.view(np.uint64)
+    k = (bits >> np.uint64(52)).astype(np.int64) - 1023
+    m = ((bits & np.uint64(0x000FFFFFFFFFFFFF)) | np.uint64(0x3FF0000000000000)).view(np.float64)
+    big = m >= _SQRT2
+    m = np.where(big, m * 0.5, m)
+    k = np.where(big, k + 1, k)
+    s = (m - 1.0) / (m + 1.0)
+    z = s * s
+    p = np.full_like(z, _LOG_COEF[13])
+    for i in range(12, -1, -1):
+        p = p * z + _LOG_COEF[i]
+    kd = k.astype(np.float64)
+    return ((2.0 * s) * p + kd * _LN2_LO) + kd * _LN2_HI
+
+
+def normal_uniforms(seed, env, slot):
+    """The integers of normal_fixed for (seed, env, slot), arrays of one shape: (n1, n2) uint64 [..., 2], pair j = 0, 1 in the last axis --
+    the top 52 bits of the first and of the last two words of Philox4x32-10 at counter (slot lo, slot hi, env, 0x4E000000 + j)."""
+    seed = int(seed)
+    env, slot = np.broadcast_arrays(np.asarray(env, dtype=np.uint64), np.asarray(slot, dtype=np.uint64))
+    n1, n2 = [], []
+    for j in range(2):
+        r = philox4x32_10((slot & _U32, slot >> np.uint64(32), env & _U32, np.uint64(_NORMAL_TAG + j)), (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF))
+        n1.append((r[0] << np.uint64(20)) | (r[1] >> np.uint64(12)))
+        n2.append((r[2] << np.uint64(20)) | (r[3] >> np.uint64(12)))
+    return np.stack(n1, axis=-1), np.stack(n2, axis=-1)
+
+
+def normal_fixed_reference(seed, env, slot):
+    """normal_fixed of csrc/cloth_philox.hpp in float64 numpy, bit for bit: float64 [..., 4], four independent standard normals of (seed,
+    env, slot) by Box-Muller over Philox, every operation one IEEE double rounding (include/clothhip.h: EXPLORATION NOISE ON THE DEVICE
+    has it operation by operation). seed in [0, 2^64), env in [0, 2^32), slot in [0, 2^64), env and slot arrays of one shape."""
+    n1, n2 = normal_uniforms(seed, env, slot)
+    u1 = (n1.astype(np.float64) + 0.5) * 2.0 ** -52
+    q = (n2 >> np.uint64(50)).astype(np.int64)
+    t = ((n2 & np.uint64(2 ** 50 - 1)).astype(np.float64) + 0.5) * 2.0 ** -50 - 0.5
+    x = t * _HALF_PI
+    x2 = x * x
+    c, s = np.full_like(x, _COS_COEF[10]), np.full_like(x, _SIN_COEF[10])
+    for i in range(9, -1, -1):
+        c = c * x2 + _COS_COEF[i]
+        s = s * x2 + _SIN_COEF[i]
+    s = x * s
+    qc = np.where(q == 0, c, np.where(q == 1, -s, np.where(q == 2, -c, s)))
+    qs = np.where(q == 0, s, np.where(q == 1, c, np.where(q == 2, -s, -c)))
+    rad = np.sqrt(-2.0 * log_fixed_reference(u1))
+    return np.stack([rad * qc, rad * qs], axis=-1).reshape(n1.shape[:-1] + (4,))
+
+
+def policy_noise_reference(seed, T, E, sigma, slot_base=None):
+    """The table clothhip_policy_noise_fill makes, bit for bit: float64 [T, E, 4] with [t, e, k] = sigma[e, k] * z_k(seed, e,
+    slot_base[e] + t). sigma is a scalar, [4] or [E, 4] of float64 (for a log-sigma head pass exp_fixed_reference of the float32 head);
+    slot_base int[E], None: zeros."""
+    T, E = int(T), int(E)
+    sg = np.asarray(sigma, dtype=np.float64)
+    sg = np.broadcast_to(sg if sg.ndim else sg.reshape(1), (E, 4))
+    base = np.zeros(E, dtype=np.uint64) if slot_base is None else np.asarray(slot_base).astype(np.uint64).reshape(E)
+    slot = base[None, :] + np.arange(T, dtype=np.uint64)[:, None]
+    env = np.broadcast_to(np.arange(E, dtype=np.uint64)[None, :], (T, E))
+    return np.ascontiguousarray(sg[None] * normal_fixed_reference(seed, env, slot))
 
 
 def _plan_clip(v, lo, hi):

@@ -139,6 +139,12 @@ class MLPTrainer(_EnvDataset):
         unit noise times it as step_many's policy_noise)."""
         return np.exp(self.log_sigma().astype(np.float64))
 
+    def device_noise(self, seed):
+        """policies.DeviceNoise(seed) under the head: the collection's noise is made on the device from the head where it lies, sigma =
+        exp_fixed(log_sigma) as the surrogate forms it -- no sigma and no noise table passes through the host."""
+        from .policies import DeviceNoise
+        return DeviceNoise(seed)
+
     def ppo_step(self, n_epochs, batch_size, seed, sigma=None, clip=0.2, target_kl=None, rows=None, ent_coef=0.0):
         """PPO on the device (ClothBatch.fit_ppo): up to n_epochs epochs over `rows` (int [m] dataset rows, None: all), each the
         minibatches of ppo_epoch_tables in ONE fit_ppo call -- optimizer steps on the clipped surrogate with the advantages in the
@@ -277,6 +283,13 @@ class MLPEnsemble(_EnvDataset):
 
     def _upload(self, batch):
         batch.set_policy_population(self.nets, self.member)
+
+    def device_noise(self, seed, sigma):
+        """policies.DeviceNoise for a collection of the ensemble: sigma [G] (or a scalar), one standard deviation per member -- env e
+        explores with sigma[member[e]] in all four components, the noise made on the device."""
+        from .policies import DeviceNoise
+        sg = np.broadcast_to(np.asarray(sigma, dtype=np.float64), (self.G,))
+        return DeviceNoise(seed, sigma=np.repeat(sg[self.member][:, None], 4, axis=1))
 
     def _on_env(self):
         if self.env._policy_mlp is not self:

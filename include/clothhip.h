@@ -723,7 +723,8 @@ int clothhip_policy_fit_ppo(clothhip_handle *h, const ClothFitParams *p, const C
  * optimizer state, and that alone; CLOTHHIP_EINVAL for a value that is not finite or |ls_k| > 10, CLOTHHIP_ESTATE with a launch in
  * flight. clothhip_get_policy_log_sigma downloads it (CLOTHHIP_ESTATE without a head). Setting or dropping a network or a population
  * leaves the head's values alone; clothhip_fork and snapshots do not carry it (they carry no network either). NO EPISODE LAUNCH READS
- * IT: the action stays y + noise[t][e], and the caller scales unit noise by exp(log_sigma) on the host.
+ * IT: the action stays y + noise[t][e], and the caller scales unit noise by exp(log_sigma) on the host -- or lets
+ * clothhip_policy_noise_fill (EXPLORATION NOISE ON THE DEVICE below) make the table from the head where it lies.
  * THE OLD LOG SIGMA is a sixth column of the dataset, old_ls[n][4] float32, default zeros, with its own byte per row on the handle: a
  * row appended by any entry has none. On a handle WITH a head clothhip_fit_data_snapshot_policy also writes the present head into the
  * rows of its range (a fill on the device, nothing downloaded) and marks them; without a head it does exactly what it did.
@@ -802,6 +803,44 @@ int clothhip_policy_fit_ppo_sigma(clothhip_handle *h, const ClothFitParams *p, c
 int clothhip_fit_data_snapshot_policy_members(clothhip_handle *h, int64_t first, int64_t n, const int32_t *member_of_row /* [n] */);
 int clothhip_policy_fit_ppo_grad_members(clothhip_handle *h, const ClothPpoParams *q, const int32_t *members, int32_t n_m, const int32_t *idx, int32_t B, float *grad_out, double *stats_out, float *ratio_out);
 int clothhip_policy_fit_ppo_members(clothhip_handle *h, const ClothFitParams *p, const ClothPpoParams *q, const int32_t *members, int32_t n_m, const int32_t *idx, int32_t n_steps, int32_t B, double *stats_out);
+
+/* EXPLORATION NOISE ON THE DEVICE (additive, ABI 7; no reference counterpart): the table double [T][E][4] that an episode
+ * launch under CLOTHHIP_POLICY_MLP adds to the network's output, made on the handle's device by one fill kernel
+ * (csrc/cloth_policy_noise.hpp) and handed to clothhip_run_actions_begin as its device-resident table (actions_on_device = 1). Every
+ * entry above keeps its bytes; no stepper kernel and no launch record changes; a handle that never calls an entry below behaves as
+ * before.
+ * THE KEY. noise[t][e][k] = sigma[e][k] z_k(seed, e, slot_base[e] + t), ONE double multiplication; z depends on (seed, env, that env's
+ * slot number) and nothing else -- not T, not E, not the launch, not how a collection is cut into launches.
+ * THE VARIATE z[0..3] = normal_fixed(seed, e, s) (csrc/cloth_philox.hpp; references.normal_fixed_reference restates it bit for bit): four
+ * independent standard normals by Box-Muller, every operation ONE IEEE double rounding, no contraction, no library log / sin / cos;
+ * division and sqrt are the correctly rounded ones. For pair j = 0, 1:
+ *   r[0..3] = Philox4x32-10(counter = ((uint32)s, (uint32)(s >> 32), e, 0x4E000000 + j), key = ((uint32)seed, (uint32)(seed >> 32)))
+ *            (the tag in the fourth word keeps these counters apart from population_eps', whose fourth word is 0)
+ *   n1 = ((uint64)r[0] << 20) | (r[1] >> 12);  u1 = ((double)n1 + 0.5) 2^-52                      exact, in (0, 1)
+ *   n2 = ((uint64)r[2] << 20) | (r[3] >> 12);  q = n2 >> 50;  t = (((double)(n2 mod 2^50) + 0.5) 2^-50) - 0.5      exact, in (-1/2, 1/2)
+ *   x = t * 1.5707963267948966;  x2 = x x
+ *   C = Horner in x2 over (-1)^i / (2 i)!, i = 10 .. 0;  S = Horner in x2 over (-1)^i / (2 i + 1)!, i = 10 .. 0 (p = (p x2) + c_i each);
+ *   c = C;  s = x S;  (c, s) <- (c, s), (-s, c), (-c, -s), (s, -c) for q = 0 .. 3
+ *   log_fixed(u1): u1 = m 2^k from its bits, m in [1, 2);  if m >= 1.4142135623730951: m = m 0.5, k = k + 1;
+ *     f = m - 1;  g = m + 1;  v = f / g;  w = v v;  P = Horner in w over 1 / (2 i + 1), i = 13 .. 0;
+ *     L = (((2 v) P) + ((double)k ln2_lo)) + ((double)k ln2_hi)          (exp_fixed's two fdlibm constants)
+ *   rad = sqrt(-2 L);  z[2 j] = rad c;  z[2 j + 1] = rad s
+ * |z| reaches 8.57. Every constant is a correctly rounded quotient of exact integers, pi / 2 or a half of ln 2.
+ * clothhip_policy_noise_fill fills the handle's table for T slots on the handle's stream -- the launch that follows is ordered behind
+ * it without a synchronisation -- and returns where it lies in *d_noise (may be NULL); the table belongs to the handle and stays
+ * valid until the next fill or clothhip_destroy. slot_base[E] (host, may be NULL: zeros) numbers row t of env e as slot
+ * slot_base[e] + t. sigma (host) is [4] for all envs with sigma_rows = 1, or [E][4] with sigma_rows = E; sigma == NULL with
+ * sigma_rows = 0 takes the handle's log-sigma head: every thread reads log_sigma[4] where it lies and forms
+ * exp_fixed((double)log_sigma[k]) -- the sigma that acts is bit for bit the one PPO WITH A LEARNED SIGMA differentiates, and nothing is
+ * downloaded. One thread per (t, e), workgroups of 256, two 16-byte stores per thread; clothhip_last_kernel_ms times it.
+ * Refused, nothing changed -- CLOTHHIP_ESTATE: a clothhip_run_actions_begin in flight (that launch may be reading the table), no head
+ * on the handle when the head is asked for; CLOTHHIP_EINVAL: T < 1 or T E > 2^31 - 1, sigma_rows not 1 or E with a table (not 0
+ * without one), a sigma that is not finite or negative, a negative slot_base (or one whose slot_base + T leaves 63 bits).
+ * clothhip_policy_noise_get downloads the table of the last fill into out[T][E][4], for tests and for callers that want the host
+ * array: CLOTHHIP_ESTATE before any fill or with a launch in flight, CLOTHHIP_EINVAL for a T other than the last fill's.
+ * OUT OF SCOPE: drawing inside the stepper kernel, a state-dependent sigma, replacing population_eps in the population and the planner. */
+int clothhip_policy_noise_fill(clothhip_handle *h, uint64_t seed, int32_t T, const int64_t *slot_base, const double *sigma, int32_t sigma_rows, void **d_noise);
+int clothhip_policy_noise_get(clothhip_handle *h, int32_t T, double *out);
 
 int clothhip_run_actions(clothhip_handle *h, const ClothEpisodeParams *ep, int32_t T, int32_t policy,
                          const double *actions, int32_t actions_on_device, const int32_t *policy_arg,
@@ -1035,8 +1074,12 @@ int clothhip_selftest_rng(uint32_t *state, int32_t kind, int32_t n, double a, do
 int clothhip_selftest_depth8(const float *depth, int32_t n_images, int64_t npx, uint8_t *out);
 int clothhip_selftest_render_plan(const ClothParams *params, int32_t width, int32_t height, int32_t out[4]);
 /* Host-side self-test of PPO's exponential (PPO ON THE DEVICE above): out[i] = exp_fixed(x[i]), the inline function k_fit_loss_ppo runs
- * (csrc/cloth_policy_fit.hpp), computed on the host; no device needed. CLOTHHIP_EINVAL for n < 0, a NULL table with n > 0 or a NaN. */
+ * (csrc/cloth_exp_fixed.hpp), computed on the host; no device needed. CLOTHHIP_EINVAL for n < 0, a NULL table with n > 0 or a NaN. */
 int clothhip_selftest_exp_fixed(const double *x, int64_t n, double *out);
+/* Host-side self-test of the exploration noise's variate (EXPLORATION NOISE ON THE DEVICE above): out[i][0..3] = normal_fixed(seed, env[i],
+ * slot[i]), the inline function k_policy_noise_fill runs (csrc/cloth_philox.hpp), computed on the host; no device needed.
+ * CLOTHHIP_EINVAL for n < 0 or a NULL table with n > 0. */
+int clothhip_selftest_normal_fixed(uint64_t seed, const uint32_t *env, const uint64_t *slot, int64_t n, double *out);
 int clothhip_selftest_arith(int32_t device, int32_t op, const double *a, const double *b, double *out,
                             int64_t n);
 

@@ -14,13 +14,17 @@ With --learn-sigma the PPO run carries a log-sigma head that sta
 minus --ent-coef times the entropy: its collections act with unit noise times the head's present sigma, the one snapshot stores the old
 means and the old log sigmas, and every iteration's line adds the sigma it acted with; the weighted regression beside it keeps --sigma.
 --bench then also times the snapshot with a head on the handle (one more fill kernel). profiles/ppo_sigma.txt holds runs.
+With --device-noise the PPO run's exploration noise is a policies.DeviceNoise: the table is made on the device in front of
+the launch, and with --learn-sigma under the head where it lies (MLPTrainer.device_noise) -- an iteration then moves no sigma and no
+noise through the host. The run beside it keeps its host noise, so the two no longer act with the same noise. In a sweep
+(--members) every member's sigma goes down as one [E, 4] table (MLPEnsemble.device_noise). profiles/policy_noise.txt holds runs.
 With --members G it runs a SWEEP instead: G = len(--lrs) x len(--sigmas) x len(--seeds) configurations as the members of
 ONE MLPEnsemble on one env of G x --envs cloths, member g on every G-th env. Per iteration ONE collection (unit noise times the member's
 sigma per env), one fit_gae under a shared critic, one member snapshot and one grouped PPO fit (demos.ppo_fit with the ensemble); it
 prints one return curve per member: the mean return of the episodes its envs completed, per iteration, with the epochs it ran. With
 --bench --members G it times the member snapshot of one collection beside the host route. profiles/ppo_members.txt holds runs.
     python3 tools/ppo_demo.py [--envs 64] [--slots 12] [--iters 4] [--epochs 10] [--sigma 0.1] [--clip 0.2] [--target-kl X] [--out FILE]
-    python3 tools/ppo_demo.py --learn-sigma [--ent-coef 0.01] [...]
+    python3 tools/ppo_demo.py --learn-sigma [--ent-coef 0.01] [--device-noise] [...]
     python3 tools/ppo_demo.py --bench [--envs 512] [--slots 12] [--out FILE]
     python3 tools/ppo_demo.py --members 8 --lrs 1e-3,3e-4,1e-4,3e-5 --sigmas 0.1 --seeds 0,1 [--envs 64] [--iters 4] [--target-kl X] [--out FILE]
     python3 tools/ppo_demo.py --bench --members 16 [--envs 512] [--slots 12] [--out FILE]"""
@@ -37,7 +41,7 @@ sys.path.insert(0, ROOT)
 import bench                                          # noqa: E402
 from gym_cloth_amd.demos import actor_critic_collect, actor_critic_fit, ppo_fit      # noqa: E402
 from gym_cloth_amd.envs import ClothVecEnv            # noqa: E402
-from gym_cloth_amd.policies import MLPEnsemble, MLPPolicy, MLPTrainer, ValueTrainer   # noqa: E402
+from gym_cloth_amd.policies import DeviceNoise, MLPEnsemble, MLPPolicy, MLPTrainer, ValueTrainer   # noqa: E402
 
 LINES = []
 
@@ -92,9 +96,14 @@ def run(args):
         say("    --learn-sigma: the PPO run's sigma is a head of four log sigmas that starts at log %g and is trained with the network, entropy "
             "coefficient %g; its collections act with unit noise times the head's sigma" % (args.sigma, args.ent_coef))
     for i in range(args.iters):
+        t0 = time.perf_counter()
         unit = np.random.RandomState(100 + i).normal(size=(T, E, 4))
         acted = pol[0].sigma() if args.learn_sigma else np.full(4, args.sigma)
         noises = [unit * acted, unit * args.sigma]
+        if args.device_noise:                                                 # the PPO run's noise is made on the device, under the head where there is one
+            t0 = time.perf_counter()
+            noises[0] = pol[0].device_noise(100 + i) if args.learn_sigma else DeviceNoise(100 + i, sigma=args.sigma)
+        prep = time.perf_counter() - t0
         for v in envs:
             v.seed([2000 + e for e in range(E)])                              # every iteration from the same start states
             v.reset()
@@ -120,6 +129,9 @@ def run(args):
             "completed episodes, mean return %.4f" % (i, cols[0]["appended"], cols[0]["open_rows"], len(cols[0]["episode_return"]),
                                                       mean(cols[0]["episode_return"]), cols[1]["appended"], cols[1]["open_rows"],
                                                       len(cols[1]["episode_return"]), mean(cols[1]["episode_return"])))
+        say("    PPO's exploration noise: %s, %.3f ms on the host before the collection; the collection took %.1f ms (kernels %.1f ms)"
+            % ("made on the device in front of the launch (DeviceNoise)" if args.device_noise else "drawn and scaled on the host, uploaded by the launch",
+               prep * 1e3, cols[0]["took"] * 1e3, cols[0]["kernel_ms"]))
         n_stats = fit["ppo_stats"].shape[1]
         per = fit["ppo_stats"].reshape(fit["epochs"], -1, n_stats).mean(axis=1) if fit["epochs"] else np.zeros((0, n_stats))
         if args.learn_sigma:
@@ -161,7 +173,8 @@ def sweep(args):
         env.seed([2000 + e // G for e in range(E)])                           # every iteration from the same start states, the same ones for every member
         env.reset()
         try:
-            col = actor_critic_collect(env, ens, n_actions=T, policy_noise=unit * sigma[ens.member][None, :, None], slots_per_launch=T)
+            noise = ens.device_noise(100 + i, sigma) if args.device_noise else unit * sigma[ens.member][None, :, None]
+            col = actor_critic_collect(env, ens, n_actions=T, policy_noise=noise, slots_per_launch=T)
         except ValueError as e:
             say("iteration %d: the collection was refused (%s): the run ends here" % (i, e))
             break
@@ -287,6 +300,7 @@ def main():
     ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--learn-sigma", action="store_true", help="the PPO run trains a log-sigma head that starts at log(--sigma)")
     ap.add_argument("--ent-coef", type=float, default=0.0, help="with --learn-sigma: the coefficient of the entropy bonus")
+    ap.add_argument("--device-noise", action="store_true", help="the PPO run's (the sweep's) exploration noise is made on the device: policies.DeviceNoise")
     ap.add_argument("--bench", action="store_true", help="measure the snapshot on the device against the host route")
     ap.add_argument("--members", type=int, default=0, help="run a sweep of this many configurations as the members of one ensemble (--lrs x --sigmas x --seeds)")
     ap.add_argument("--lrs", default="1e-3", help="with --members: the members' Adam learning rates, comma-separated")
