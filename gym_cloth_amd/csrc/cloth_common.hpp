@@ -12,6 +12,18 @@
 
 namespace clothhip {
 
+// The two strict tests of Gripper.grab_top / grab (gripper.pyx:35-36), shared by k_grab (cloth_state_kernels.hpp) and the episode launch's
+// grab (episode_plan.inc.hpp). MUTANTS 13 / 14 (tools/run_mutants.sh; never a product build) make one of them <= in both grabs.
+#if defined(CLOTHHIP_MUTATE) && CLOTHHIP_MUTATE == 13
+#define GRAB_IN_CYLINDER(d2, rad) ((d2) <= (rad))
+#else
+#define GRAB_IN_CYLINDER(d2, rad) ((d2) < (rad))
+#endif
+#if defined(CLOTHHIP_MUTATE) && CLOTHHIP_MUTATE == 14
+#define GRAB_IN_BAND(d, tt) ((d) <= (tt))
+#else
+#define GRAB_IN_BAND(d, tt) ((d) < (tt))
+#endif
 
 template <typename T> struct DevConsts {
     T mg;              // mass * gravity                         cloth.pyx:179

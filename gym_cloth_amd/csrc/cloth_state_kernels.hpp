@@ -29,25 +29,41 @@ template <typename T> __global__ __launch_bounds__(64) void k_grab(GrabArgs<T> A
     int best = 0x7fffffff;
     if (A.top) {
         // first level (scanning down from `height`) at which any in-cylinder point lies in the band
+#if defined(CLOTHHIP_MUTATE) && CLOTHHIP_MUTATE == 15                // MUTANT 15: the LAST level that hits, not the first
+        int last = -1;
         for (int i = lane; i < A.P; i += 64) {
             const T dx = px[i] - gx, dy = py[i] - gy;
-            if (dx * dx + dy * dy < rad) {                              // gripper.pyx:35 (radius not squared)
+            if (dx * dx + dy * dy < rad) {
+                const T z = pz[i];
+                for (int l = 0; l < A.n_levels; l++) {
+                    T d = z - (T)A.levels[l]; d = d < 0 ? -d : d;
+                    if (d < tt && l > last) last = l;
+                }
+            }
+        }
+        for (int o = 32; o > 0; o >>= 1) { int v = __shfl_xor(last, o); last = v > last ? v : last; }
+        if (last >= 0) best = last;
+#else
+        for (int i = lane; i < A.P; i += 64) {
+            const T dx = px[i] - gx, dy = py[i] - gy;
+            if (GRAB_IN_CYLINDER(dx * dx + dy * dy, rad)) {             // gripper.pyx:35 (radius not squared)
                 const T z = pz[i];
                 for (int l = 0; l < A.n_levels && l < best; l++) {
                     T d = z - (T)A.levels[l]; d = d < 0 ? -d : d;
-                    if (d < tt) { best = l; break; }                    // gripper.pyx:36
+                    if (GRAB_IN_BAND(d, tt)) { best = l; break; }       // gripper.pyx:36
                 }
             }
         }
         for (int o = 32; o > 0; o >>= 1) { int v = __shfl_xor(best, o); best = v < best ? v : best; }
+#endif
         if (best == 0x7fffffff) { if (lane == 0) A.n_grabbed[e] = 0; return; }
     }
     int n = 0;
     for (int i = lane; i < A.P; i += 64) {
         const T dx = px[i] - gx, dy = py[i] - gy;
-        if (dx * dx + dy * dy < rad) {
+        if (GRAB_IN_CYLINDER(dx * dx + dy * dy, rad)) {
             bool hit = true;
-            if (A.top) { T d = pz[i] - (T)A.levels[best]; d = d < 0 ? -d : d; hit = d < tt; }
+            if (A.top) { T d = pz[i] - (T)A.levels[best]; d = d < 0 ? -d : d; hit = GRAB_IN_BAND(d, tt); }
             if (hit) {                                                  // pinned = True ; grabbed_pts.append
                 uint8_t c = cnt[i];
                 if ((c & CNT_GRAB_MASK) < CNT_GRAB_MASK) c = (uint8_t)(c + 1);

@@ -313,10 +313,13 @@
             if (do_decode) {
                 // ---- action -> schedule (cloth_env.py:396-475), in double, every thread the same arithmetic
                 const ClothEpisodeParams &ep = F.ep;
-                double a0 = fmax(fmin(act[0], ep.act_high[0]), ep.act_low[0]);                    // :402-415
-                double a1 = fmax(fmin(act[1], ep.act_high[1]), ep.act_low[1]);
-                const double c2 = fmax(fmin(act[2], ep.act_high[2]), ep.act_low[2]);
-                const double c3 = fmax(fmin(act[3], ep.act_high[3]), ep.act_low[3]);
+                // max(min(x, high), low) as Python evaluates it (:402-415): a NaN stays a NaN (fmin / fmax would clip it to a bound and the launch
+                // would pull), so a NaN delta reaches the guard of the loop below and a NaN coordinate grabs nothing, as in step()
+                auto clip = [](double x, double lo, double hi) { const double m = hi < x ? hi : x; return lo > m ? lo : m; };
+                double a0 = clip(act[0], ep.act_low[0], ep.act_high[0]);
+                double a1 = clip(act[1], ep.act_low[1], ep.act_high[1]);
+                const double c2 = clip(act[2], ep.act_low[2], ep.act_high[2]);
+                const double c3 = clip(act[3], ep.act_low[3], ep.act_high[3]);
                 if (ep.clip_act_space) { a0 = (a0 / 2.0) + 0.5; a1 = (a1 / 2.0) + 0.5; }          // :417-426
                 const double tl = sqrt(c2 * c2 + c3 * c3);                                        // :449
                 const double xd = c2 / (tl + 1e-5), yd = c3 / (tl + 1e-5);                        // :450-451
@@ -341,7 +344,11 @@
                 sc.dz_up = ep.dz_up; sc.dx_pull = xr; sc.dy_pull = yr; sc.dz_pull = 0.0;
                 // ---- Gripper.grab_top (gripper.pyx:23-42) on the LDS-resident state, + force_grab (cloth_env.py:434-444)
                 const T gx = (T)a0, gy = (T)a1, tt = (T)F.two_thickness;
+#if defined(CLOTHHIP_MUTATE) && CLOTHHIP_MUTATE == 16                // MUTANT 16: the force_grab radius accumulated in T, not in double
+                T radius = (T)ep.grip_radius;
+#else
                 double radius = ep.grip_radius;
+#endif
                 for (int tries = 0;; tries++) {
                     const T rad = (T)radius;
                     __syncthreads();
@@ -356,12 +363,19 @@
                         if (i < P) {
                             const Pt<T> c = cur[i];
                             const T dx = c.x - gx, dy = c.y - gy;
-                            if (dx * dx + dy * dy < rad) {                                        // gripper.pyx:35 (radius not squared)
+                            if (GRAB_IN_CYLINDER(dx * dx + dy * dy, rad)) {                       // gripper.pyx:35 (radius not squared)
                                 incyl[q] = true;
+#if defined(CLOTHHIP_MUTATE) && CLOTHHIP_MUTATE == 15                // MUTANT 15: the LAST level that hits, not the first (best counts down from -2 - l)
+                                for (int l = 0; l < F.n_glevels; l++) {
+                                    T d = c.z - (T)F.levels[l]; d = d < 0 ? -d : d;
+                                    if (d < tt && -2 - l < best) best = -2 - l;
+                                }
+#else
                                 for (int l = 0; l < F.n_glevels && l < best; l++) {
                                     T d = c.z - (T)F.levels[l]; d = d < 0 ? -d : d;
-                                    if (d < tt) { best = l; break; }                              // gripper.pyx:36
+                                    if (GRAB_IN_BAND(d, tt)) { best = l; break; }                 // gripper.pyx:36
                                 }
+#endif
                             }
                         }
                     }
@@ -369,6 +383,9 @@
                     if (lane == 0 && best != 0x7fffffff) atomicMin(&misc[8], best);
                     __syncthreads();
                     best = misc[8];
+#if defined(CLOTHHIP_MUTATE) && CLOTHHIP_MUTATE == 15
+                    if (best < 0) best = -2 - best;
+#endif
                     int n = 0;
                     if (best != 0x7fffffff) {
                         const T lz = (T)F.levels[best];
@@ -378,7 +395,7 @@
                                 const int i = tid + q * NT;
                                 Pt<T> c = cur[i];
                                 T d = c.z - lz; d = d < 0 ? -d : d;
-                                if (d < tt) {                                                     // pinned = True ; grabbed_pts.append
+                                if (GRAB_IN_BAND(d, tt)) {                                        // pinned = True ; grabbed_pts.append
                                     uint32_t w = w_cnt(c.w);
                                     if ((w & CNT_GRAB_MASK) < CNT_GRAB_MASK) w++;
                                     c.w = w_make<T>(w); cur[i] = c; n++;
@@ -391,7 +408,11 @@
                     __syncthreads();
                     n_grab = misc[9];
                     if (n_grab > 0 || !ep.force_grab || tries >= 10000) break;
+#if defined(CLOTHHIP_MUTATE) && CLOTHHIP_MUTATE == 16
+                    radius += (T)ep.radius_inc;
+#else
                     radius += ep.radius_inc;                                                      // cloth_env.py:439
+#endif
                 }
                 do_run = n_grab > 0 && !decode_err;                                               // cloth_env.py:490-493
             }

@@ -3,17 +3,10 @@ index sets on flat, lifted and FOLDED states (two layers under the gripper), in 
 import numpy as np
 import pytest
 
+from oracle import gripper_exact
 from test_gpu_parity import cfg_from_golden
 
 pytestmark = pytest.mark.gpu
-
-
-def _margins(pos, xy, radius, levels, tt):
-    """distance of every point from the two decision boundaries of the grab tests (for the fp32 comparison)."""
-    d2 = (pos[:, 0] - xy[0]) ** 2 + (pos[:, 1] - xy[1]) ** 2
-    m_r = np.abs(d2 - radius)
-    m_z = np.min(np.abs(np.abs(pos[:, 2][:, None] - levels[None, :]) - tt), axis=1)
-    return m_r, m_z
 
 
 @pytest.mark.parametrize("prec", ["f64", "f32"])
@@ -28,17 +21,18 @@ def test_grab_sets_match_reference(prec, top, oracle_lib):
     pin = b.get_state()[2].astype(bool)
     want = g["grab_top"] if top else g["grab"]
     assert any(len(w) > 5 for w in want), "the fixture must contain a multi-layer grab"
-    tt, radius = 2 * g["cfg"]["thickness"], g["cfg"]["grip_radius"]
+    radius, pos = g["cfg"]["grip_radius"], b.positions()
+    lv = gripper_exact.levels(g["cfg"]["height"], g["cfg"]["thickness"])
     for q in range(n):
         got = set(np.nonzero(pin[q])[0].tolist())
         ref = set(want[q])
         if prec == "f64":
             assert got == ref and cnt[q] == len(ref), (q, sorted(got ^ ref))
-        else:
-            # fp32 positions: a point may flip only if it sits within fp32 rounding of a decision boundary
-            m_r, m_z = _margins(g["pos"][q], g["xy"][q], radius, g["levels"], tt)
-            for i in got ^ ref:
-                assert m_r[i] < 1e-6 or m_z[i] < 1e-6, (q, i, m_r[i], m_z[i])
+        # both precisions: the exact reference (oracle/gripper_exact.py: every operation one rounding in the handle's type) on the positions
+        # the handle holds -- in fp32 a point near a boundary may differ from the fp64 fixture, and the reference says which way
+        exact = (gripper_exact.grab_top(pos[q], g["xy"][q], radius, lv, g["cfg"]["thickness"], prec)[0] if top
+                 else gripper_exact.grab(pos[q], g["xy"][q], radius, prec))
+        assert got == set(exact.tolist()) and cnt[q] == len(exact), (q, sorted(got ^ set(exact.tolist())))
     # grabbing again appends the same points a second time (multiplicity): release clears both
     cnt2 = (b.grab_top if top else b.grab)(g["xy"])
     assert np.array_equal(cnt2 > 0, cnt > 0)
