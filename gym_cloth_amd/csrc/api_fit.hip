@@ -102,6 +102,15 @@ static int check_fit_params(const ClothFitParams *p, int32_t j) {
     return 0;
 }
 
+// ... and the optimizers p [n_m] of a grouped step entry: each valid by its index, and one optimizer per call
+static int check_fit_params_members(const ClothFitParams *p, int32_t n_m) {
+    for (int32_t j = 0; j < n_m; j++) {
+        if (int rc = check_fit_params(p + j, j)) return rc;
+        if (p[j].optimizer != p[0].optimizer) return fail(CLOTHHIP_EINVAL, "p[%d].optimizer = %g, p[0].optimizer = %g: one optimizer per call", j, (double)p[j].optimizer, (double)p[0].optimizer);
+    }
+    return 0;
+}
+
 // Where member j's tables lie: the per-member sizes of the scratch tables (floats) for minibatches of B rows, and the offsets of every
 // layer inside a blob (weights, gradient) and inside a member's activations.
 struct FitPlan {
@@ -142,35 +151,37 @@ template <bool A_KC, bool B_KC, int EPI, bool ROWS> static void launch_gemm(hipS
     hipLaunchKernelGGL((k_fit_gemm<A_KC, B_KC, EPI, ROWS>), grid, dim3(FIT_THREADS), 0, s, a);
 }
 
-// Enqueue every launch of one network's step, each over all n_m members: loss and gradient of the present weights over rows d_idx
-// [n_m][B] into d_loss [n_m] and h->fit.d_grad [n_m][n_params] (blob layout). d_loss NULL: the forward pass alone -- member j's y is
-// then at h->fit.d_act + j * p.act + p.h_off[L - 1]; shared_rows (the forward alone): d_idx is ONE list [B] that every member reads.
-// ppo (the policy's table only): the loss launch is k_fit_loss_ppo with these constants, d_loss is then [n_m][FIT_PPO_STATS] and
-// d_ratio (may be NULL) [n_m][B]; every other launch is the same. ppo->head: the loss launch is k_fit_loss_ppo_sigma, which reads the
-// handle's log-sigma head where it lies; d_loss is [n_m][FIT_PPO_SIGMA_STATS], the head's gradient goes to h->fit.d_grad_ls and the
-// head the launch read to ls_out (may be NULL). ppo->member_q: the loss launch is k_fit_loss_ppo_members, which reads member j's
-// constants from row j of h->fit.d_ppo_q (the caller has uploaded the table)
-struct FitPpo {
-    double inv_s2, half_inv_s2, lo, hi;
-    bool head = false;
-    double ent_coef = 0.0;
-    float *ls_out = nullptr;
-    const double *member_q = nullptr;      // host [n_m][4] {inv_s2, half_inv_s2, lo, hi}: member j's constants in the place of the four above
-    int stats() const { return head ? FIT_PPO_SIGMA_STATS : FIT_PPO_STATS; }
+// What a step minimises, with the fields that loss reads and no others. The width of the squared error comes from FitNet; both
+// surrogates are the policy's table only. A new loss is one more kind, its fields, and its case in enqueue_loss.
+struct FitLoss {
+    enum Kind { SQUARED_ERROR, PPO, PPO_SIGMA } kind;
+    int stats;                                      // doubles per member and step in the loss table: the loss, or the surrogate's statistics
+    union {
+        const double *q;                            // PPO: host [n_m][4] {inv_s2, half_inv_s2, lo, hi}, row j member j's (check_ppo makes it)
+        struct { double lo, hi, ent_coef; } s;      // PPO_SIGMA: 1 - eps, 1 + eps and the entropy coefficient; 1 / sigma^2 comes from the head
+    };
 };
-static int enqueue_grad(clothhip_handle *h, const FitNet &net, const FitPlan &p, int32_t n_m, const int32_t *d_idx, int32_t B, double *d_loss, bool shared_rows = false,
-                        const FitPpo *ppo = nullptr, float *d_ratio = nullptr) {
+static FitLoss squared_error() { FitLoss l = {}; l.kind = FitLoss::SQUARED_ERROR; l.stats = 1; return l; }
+static FitLoss ppo_loss(const double *q) { FitLoss l = {}; l.kind = FitLoss::PPO; l.stats = FIT_PPO_STATS; l.q = q; return l; }
+static FitLoss ppo_sigma_loss(double lo, double hi, double ent_coef) { FitLoss l = {}; l.kind = FitLoss::PPO_SIGMA; l.stats = FIT_PPO_SIGMA_STATS; l.s = {lo, hi, ent_coef}; return l; }
+
+// Where a call's results go on the host, each NULL when the caller does not want it: loss [n_steps][n_m][stats]; of a gradient call grad
+// [n_m][n_params], ratio [n_m][B] (the surrogates), grad_ls [4] (PPO_SIGMA); of a PPO_SIGMA fit ls [n_steps][4], the head before each update
+struct FitOut { double *loss; float *grad, *ratio, *grad_ls, *ls; };
+
+// The launches of one network's step, each over all n_m members: forward, loss, backward. The forward of the present weights over rows
+// d_idx [n_m][B]: member j's y is then at h->fit.d_act + j * p.act + p.h_off[L - 1].
+// shared_rows: d_idx is ONE list [B] that every member reads
+static int enqueue_forward(clothhip_handle *h, const FitNet &net, const FitPlan &p, int32_t n_m, const int32_t *d_idx, int32_t B, bool shared_rows) {
     const MlpDesc &D = net.D;
     const int L = D.n_layers;
-    auto &f = h->fit;
-    const auto &d = h->dataset;
-    float *act = f.d_act, *grad = f.d_grad, *dz[2] = {f.d_dz, f.d_dz + (size_t)B * p.maxw};
+    float *act = h->fit.d_act;
     FitGemmArgs m0 = {};
-    m0.members = f.d_members; m0.stride = D.stride; m0.rows_step = shared_rows ? 0 : B;
+    m0.members = h->fit.d_members; m0.stride = D.stride; m0.rows_step = shared_rows ? 0 : B;
     for (int l = 0; l < L; l++) {
         const int n_in = D.widths[l], n_out = D.widths[l + 1];
         FitGemmArgs a = m0;
-        a.A = l ? act + p.h_off[l - 1] : (const float *)d.obs(); a.lda = n_in; a.rows = l ? nullptr : d_idx; a.a_step = l ? (int64_t)p.act : 0;
+        a.A = l ? act + p.h_off[l - 1] : (const float *)h->dataset.obs(); a.lda = n_in; a.rows = l ? nullptr : d_idx; a.a_step = l ? (int64_t)p.act : 0;
         a.B = D.params + p.w_off[l]; a.ldb = n_in; a.bias = a.B + (size_t)n_out * n_in; a.b_weights = 1;
         a.C = act + p.h_off[l]; a.ldc = n_out; a.c_step = (int64_t)p.act;
         a.M = B; a.N = n_out; a.K = n_in; a.k_chunk = n_in;
@@ -180,35 +191,52 @@ static int enqueue_grad(clothhip_handle *h, const FitNet &net, const FitPlan &p,
         else launch_gemm<true, true, FIT_EPI_BIAS, false>(h->stream, a, n_m);
         HIPCHECK(hipGetLastError());
     }
-    if (!d_loss) return 0;
-    if (ppo && ppo->head) {
+    return 0;
+}
+// The loss of the forward's y and its dZ of the last layer: d_stats [n_m][loss.stats]. The surrogates: d_ratio (may be NULL) [n_m][B];
+// PPO reads member j's constants from row j of h->fit.d_ppo_q (the caller has uploaded loss.q); PPO_SIGMA reads the handle's log-sigma
+// head where it lies, writes the head's gradient to h->fit.d_grad_ls and the head it read to d_ls (may be NULL)
+static int enqueue_loss(clothhip_handle *h, const FitNet &net, const FitPlan &p, const FitLoss &loss, int32_t n_m, const int32_t *d_idx, int32_t B, double *d_stats,
+                        float *d_ratio, float *d_ls) {
+    auto &f = h->fit;
+    const auto &d = h->dataset;
+    const int L = net.D.n_layers;
+    const float *y = f.d_act + p.h_off[L - 1];
+    float *dz = f.d_dz + ((L - 1) & 1) * (size_t)B * p.maxw;
+    const dim3 grid((unsigned)n_m), block(256);
+    if (loss.kind == FitLoss::PPO_SIGMA) {
         FitPpoSigmaArgs q = {};
-        q.y = act + p.h_off[L - 1]; q.lab = d.lab(); q.old = d.old(); q.old_ls = d.old_ls(); q.wgt = d.w(); q.ls = h->pol.d_log_sigma; q.rows = d_idx;
-        q.dz = dz[(L - 1) & 1]; q.ratio = d_ratio; q.grad_ls = f.d_grad_ls; q.ls_out = ppo->ls_out; q.stats = d_loss;
-        q.lo = ppo->lo; q.hi = ppo->hi; q.ent_coef = ppo->ent_coef;
+        q.y = y; q.lab = d.lab(); q.old = d.old(); q.old_ls = d.old_ls(); q.wgt = d.w(); q.ls = h->pol.d_log_sigma; q.rows = d_idx;
+        q.dz = dz; q.ratio = d_ratio; q.grad_ls = f.d_grad_ls; q.ls_out = d_ls; q.stats = d_stats;
+        q.lo = loss.s.lo; q.hi = loss.s.hi; q.ent_coef = loss.s.ent_coef;
         q.y_step = (int64_t)p.act; q.dz_step = (int64_t)p.dz; q.rows_step = (int64_t)B; q.B = B;
-        hipLaunchKernelGGL(k_fit_loss_ppo_sigma, dim3((unsigned)n_m), dim3(256), 0, h->stream, q);
-    } else if (ppo) {
+        hipLaunchKernelGGL(k_fit_loss_ppo_sigma, grid, block, 0, h->stream, q);
+    } else if (loss.kind == FitLoss::PPO) {
         FitPpoArgs q = {};
-        q.y = act + p.h_off[L - 1]; q.lab = d.lab(); q.old = d.old(); q.wgt = d.w(); q.rows = d_idx; q.dz = dz[(L - 1) & 1]; q.ratio = d_ratio; q.stats = d_loss;
-        q.inv_s2 = ppo->inv_s2; q.half_inv_s2 = ppo->half_inv_s2; q.lo = ppo->lo; q.hi = ppo->hi;
+        q.y = y; q.lab = d.lab(); q.old = d.old(); q.wgt = d.w(); q.rows = d_idx; q.dz = dz; q.ratio = d_ratio; q.stats = d_stats; q.q = f.d_ppo_q;
         q.y_step = (int64_t)p.act; q.dz_step = (int64_t)p.dz; q.rows_step = (int64_t)B; q.B = B;
-        if (ppo->member_q) hipLaunchKernelGGL(k_fit_loss_ppo_members, dim3((unsigned)n_m), dim3(256), 0, h->stream, q, (const double *)f.d_ppo_q);
-        else hipLaunchKernelGGL(k_fit_loss_ppo, dim3((unsigned)n_m), dim3(256), 0, h->stream, q);
-    } else if (net.value)
-        hipLaunchKernelGGL(k_fit_loss<1>, dim3((unsigned)n_m), dim3(256), 0, h->stream, (const float *)(act + p.h_off[L - 1]), (const float *)d.ret(), (const float *)nullptr,
-                           d_idx, B, dz[(L - 1) & 1], d_loss, (int64_t)p.act, (int64_t)p.dz, (int64_t)B);
+        hipLaunchKernelGGL(k_fit_loss_ppo, grid, block, 0, h->stream, q);
+    } else if (net.value)      // SQUARED_ERROR, at the net's width
+        hipLaunchKernelGGL(k_fit_loss<1>, grid, block, 0, h->stream, y, (const float *)d.ret(), (const float *)nullptr, d_idx, B, dz, d_stats, (int64_t)p.act, (int64_t)p.dz, (int64_t)B);
     else
-        hipLaunchKernelGGL(k_fit_loss<4>, dim3((unsigned)n_m), dim3(256), 0, h->stream, (const float *)(act + p.h_off[L - 1]), (const float *)d.lab(), (const float *)d.w(),
-                           d_idx, B, dz[(L - 1) & 1], d_loss, (int64_t)p.act, (int64_t)p.dz, (int64_t)B);
+        hipLaunchKernelGGL(k_fit_loss<4>, grid, block, 0, h->stream, y, (const float *)d.lab(), (const float *)d.w(), d_idx, B, dz, d_stats, (int64_t)p.act, (int64_t)p.dz, (int64_t)B);
     HIPCHECK(hipGetLastError());
-    for (int l = L - 1; l >= 0; l--) {
+    return 0;
+}
+// The backward from the loss launch's dZ: the gradient of every member into h->fit.d_grad [n_m][n_params] (blob layout)
+static int enqueue_backward(clothhip_handle *h, const FitNet &net, const FitPlan &p, int32_t n_m, const int32_t *d_idx, int32_t B) {
+    const MlpDesc &D = net.D;
+    auto &f = h->fit;
+    float *act = f.d_act, *grad = f.d_grad, *dz[2] = {f.d_dz, f.d_dz + (size_t)B * p.maxw};
+    FitGemmArgs m0 = {};
+    m0.members = f.d_members; m0.stride = D.stride; m0.rows_step = B;
+    for (int l = D.n_layers - 1; l >= 0; l--) {
         const int n_in = D.widths[l], n_out = D.widths[l + 1];
         const float *dzl = dz[l & 1];
         float *gWl = grad + p.w_off[l];
         FitGemmArgs a = m0;
         a.A = dzl; a.lda = n_out; a.a_step = (int64_t)p.dz;
-        a.B = l ? act + p.h_off[l - 1] : (const float *)d.obs(); a.ldb = n_in; a.rows = l ? nullptr : d_idx; a.b_step = l ? (int64_t)p.act : 0;
+        a.B = l ? act + p.h_off[l - 1] : (const float *)h->dataset.obs(); a.ldb = n_in; a.rows = l ? nullptr : d_idx; a.b_step = l ? (int64_t)p.act : 0;
         a.C = p.n_split > 1 ? (float *)f.d_part : gWl; a.ldc = n_in; a.c_slab = (int64_t)n_out * n_in; a.c_step = (int64_t)(p.n_split > 1 ? p.part : p.grad);
         a.M = n_out; a.N = n_in; a.K = B; a.k_chunk = FIT_SPLIT_ROWS;
         if (l == 0) launch_gemm<false, false, FIT_EPI_NONE, true>(h->stream, a, n_m);
@@ -238,34 +266,39 @@ static int enqueue_grad(clothhip_handle *h, const FitNet &net, const FitPlan &p,
     }
     return 0;
 }
+// ... and all three: loss and gradient of the present weights over rows d_idx [n_m][B], every member on its own rows
+static int enqueue_grad(clothhip_handle *h, const FitNet &net, const FitPlan &p, const FitLoss &loss, int32_t n_m, const int32_t *d_idx, int32_t B, double *d_stats,
+                        float *d_ratio, float *d_ls) {
+    if (int rc = enqueue_forward(h, net, p, n_m, d_idx, B, false)) return rc;
+    if (int rc = enqueue_loss(h, net, p, loss, n_m, d_idx, B, d_stats, d_ratio, d_ls)) return rc;
+    return enqueue_backward(h, net, p, n_m, d_idx, B);
+}
 
-// loss and gradient of `members` over idx [n_m][B], nothing updated; the call is valid. ppo: the clipped surrogate in the place of the
-// squared error, loss_out is then [n_m][FIT_PPO_STATS] and ratio_out (may be NULL) [n_m][B]
-static int run_grad(clothhip_handle *h, const FitNet &net, const int32_t *members, int32_t n_m, const int32_t *idx, int32_t B, float *grad_out, double *loss_out,
-                    const FitPpo *ppo = nullptr, float *ratio_out = nullptr, float *grad_ls_out = nullptr) {
+// loss and gradient of `members` over idx [n_m][B], nothing updated; the call is valid
+static int run_grad(clothhip_handle *h, const FitNet &net, const FitLoss &loss, const int32_t *members, int32_t n_m, const int32_t *idx, int32_t B, const FitOut &out) {
     auto &f = h->fit;
     const FitPlan p = fit_plan(net, B);
-    const size_t n_loss = (size_t)n_m * (ppo ? ppo->stats() : 1);
+    const size_t n_loss = (size_t)n_m * loss.stats;
     HIPCHECK(hipSetDevice(h->device));
     if (int rc = fit_reserve(h, p, n_m)) return rc;
-    if (ppo && ppo->head) if (int rc = f.d_grad_ls.reserve((size_t)n_m * MLP_OUT * 4)) return rc;
+    if (loss.kind == FitLoss::PPO_SIGMA) if (int rc = f.d_grad_ls.reserve((size_t)n_m * MLP_OUT * 4)) return rc;
     if (int rc = f.d_idx.reserve((size_t)n_m * B * 4)) return rc;
     if (int rc = f.d_loss.reserve(n_loss * 8)) return rc;
-    if (ratio_out) if (int rc = f.d_ratio.reserve((size_t)n_m * B * 4)) return rc;
-    if (ppo && ppo->member_q) {
+    if (out.ratio) if (int rc = f.d_ratio.reserve((size_t)n_m * B * 4)) return rc;
+    if (loss.kind == FitLoss::PPO) {      // the members' constants, one row for the shared network
         if (int rc = f.d_ppo_q.reserve((size_t)n_m * 32)) return rc;
-        HIPCHECK(hipMemcpyAsync(f.d_ppo_q, ppo->member_q, (size_t)n_m * 32, hipMemcpyHostToDevice, h->stream));
+        HIPCHECK(hipMemcpyAsync(f.d_ppo_q, loss.q, (size_t)n_m * 32, hipMemcpyHostToDevice, h->stream));
     }
     HIPCHECK(hipMemcpyAsync(f.d_members, members, (size_t)n_m * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipMemcpyAsync(f.d_idx, idx, (size_t)n_m * B * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipEventRecord(h->ev0, h->stream));
-    if (int rc = enqueue_grad(h, net, p, n_m, f.d_idx, B, f.d_loss, false, ppo, ratio_out ? (float *)f.d_ratio : nullptr)) return rc;
+    if (int rc = enqueue_grad(h, net, p, loss, n_m, f.d_idx, B, f.d_loss, out.ratio ? (float *)f.d_ratio : nullptr, nullptr)) return rc;
     HIPCHECK(hipEventRecord(h->ev1, h->stream));
     h->have_timing = true;
-    if (grad_out) HIPCHECK(hipMemcpyAsync(grad_out, f.d_grad, (size_t)n_m * p.grad * 4, hipMemcpyDeviceToHost, h->stream));
-    if (loss_out) HIPCHECK(hipMemcpyAsync(loss_out, f.d_loss, n_loss * 8, hipMemcpyDeviceToHost, h->stream));
-    if (ratio_out) HIPCHECK(hipMemcpyAsync(ratio_out, f.d_ratio, (size_t)n_m * B * 4, hipMemcpyDeviceToHost, h->stream));
-    if (grad_ls_out) HIPCHECK(hipMemcpyAsync(grad_ls_out, f.d_grad_ls, (size_t)n_m * MLP_OUT * 4, hipMemcpyDeviceToHost, h->stream));
+    if (out.grad) HIPCHECK(hipMemcpyAsync(out.grad, f.d_grad, (size_t)n_m * p.grad * 4, hipMemcpyDeviceToHost, h->stream));
+    if (out.loss) HIPCHECK(hipMemcpyAsync(out.loss, f.d_loss, n_loss * 8, hipMemcpyDeviceToHost, h->stream));
+    if (out.ratio) HIPCHECK(hipMemcpyAsync(out.ratio, f.d_ratio, (size_t)n_m * B * 4, hipMemcpyDeviceToHost, h->stream));
+    if (out.grad_ls) HIPCHECK(hipMemcpyAsync(out.grad_ls, f.d_grad_ls, (size_t)n_m * MLP_OUT * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(hipStreamSynchronize(h->stream));
     return 0;
 }
@@ -274,7 +307,7 @@ extern "C" int clothhip_policy_fit_grad(clothhip_handle *h, const int32_t *idx, 
     if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
     if (int rc = check_fit_state(h, false)) return rc;
     if (int rc = check_fit_rows(h, 1, idx, B, B)) return rc;
-    return run_grad(h, policy_net(h), SHARED_ROW, 1, idx, B, grad_out, loss_out);
+    return run_grad(h, policy_net(h), squared_error(), SHARED_ROW, 1, idx, B, {loss_out, grad_out});
 }
 
 extern "C" int clothhip_policy_fit_grad_members(clothhip_handle *h, const int32_t *members, int32_t n_m, const int32_t *idx, int32_t B, float *grad_out,
@@ -283,7 +316,7 @@ extern "C" int clothhip_policy_fit_grad_members(clothhip_handle *h, const int32_
     if (int rc = check_fit_state(h, true)) return rc;
     if (int rc = check_fit_members(h, members, n_m)) return rc;
     if (int rc = check_fit_rows(h, n_m, idx, (int64_t)n_m * B, B)) return rc;
-    return run_grad(h, policy_net(h), members, n_m, idx, B, grad_out, loss_out);
+    return run_grad(h, policy_net(h), squared_error(), members, n_m, idx, B, {loss_out, grad_out});
 }
 
 // The loss alone of the shared network over any number of rows: chunks of at most FIT_MAX_BATCH through the forward pass above, each
@@ -313,7 +346,7 @@ extern "C" int clothhip_policy_fit_loss(clothhip_handle *h, const int32_t *idx, 
         const int32_t B = (int32_t)std::min<int64_t>(FIT_MAX_BATCH, n - c * FIT_MAX_BATCH);
         const FitPlan p = fit_plan(net, B);
         const int32_t *d_idx = f.d_idx + (size_t)c * FIT_MAX_BATCH;
-        if (int rc = enqueue_grad(h, net, p, 1, d_idx, B, nullptr)) return rc;
+        if (int rc = enqueue_forward(h, net, p, 1, d_idx, B, false)) return rc;
         launch_fit_sqsum(h->stream, f.d_act + p.h_off[L - 1], h->dataset.lab(), h->dataset.w(), d_idx, B, f.d_loss + c);
         HIPCHECK(hipGetLastError());
     }
@@ -327,10 +360,10 @@ extern "C" int clothhip_policy_fit_loss(clothhip_handle *h, const int32_t *idx, 
     return 0;
 }
 
-// The forward alone on n stored rows, the same rows for every member: chunks through enqueue_grad, each chunk's y copied out to
+// The forward alone on n stored rows, the same rows for every member: chunks through enqueue_forward, each chunk's y copied out to
 // d_pred [n_m][n][net.out()] (k_fit_copy_y), where it stays: enqueued between the timing events, not synchronised. The call is valid.
-// dst (n_m == 1): the table that gets y in the place of d_pred, [n][net.out()] -- a dataset column that is written where it lies.
-static int enqueue_predict(clothhip_handle *h, const FitNet &net, const int32_t *members, int32_t n_m, const int32_t *idx, int64_t n, float *dst = nullptr) {
+// dst (NULL: d_pred; else n_m == 1): the table that gets y in the place of d_pred, [n][net.out()] -- a dataset column that is written where it lies.
+static int enqueue_predict(clothhip_handle *h, const FitNet &net, const int32_t *members, int32_t n_m, const int32_t *idx, int64_t n, float *dst) {
     auto &f = h->fit;
     const int L = net.D.n_layers, W = net.out();
     const int32_t Bmax = (int32_t)std::min<int64_t>(n, std::min<int64_t>(FIT_MAX_BATCH, CLOTHHIP_FIT_MAX_MEMBER_ROWS / n_m));
@@ -347,7 +380,7 @@ static int enqueue_predict(clothhip_handle *h, const FitNet &net, const int32_t 
     for (int64_t r0 = 0; r0 < n; r0 += Bmax) {
         const int32_t B = (int32_t)std::min<int64_t>(Bmax, n - r0);
         const FitPlan p = fit_plan(net, B);
-        if (int rc = enqueue_grad(h, net, p, n_m, f.d_idx + (size_t)r0, B, nullptr, true)) return rc;
+        if (int rc = enqueue_forward(h, net, p, n_m, f.d_idx + (size_t)r0, B, true)) return rc;
         const int32_t blocks = (W * B + 255) / 256;
         launch_fit_copy_y(h->stream, n_m, f.d_act + p.h_off[L - 1], W * B, dst + (size_t)r0 * W, (int64_t)p.act, (int64_t)n * W, blocks);
         HIPCHECK(hipGetLastError());
@@ -358,7 +391,7 @@ static int enqueue_predict(clothhip_handle *h, const FitNet &net, const int32_t 
 }
 // ... and one download
 static int run_predict(clothhip_handle *h, const FitNet &net, const int32_t *members, int32_t n_m, const int32_t *idx, int64_t n, float *y_out) {
-    if (int rc = enqueue_predict(h, net, members, n_m, idx, n)) return rc;
+    if (int rc = enqueue_predict(h, net, members, n_m, idx, n, nullptr)) return rc;
     HIPCHECK(hipMemcpyAsync(y_out, h->fit.d_pred, (size_t)n_m * n * net.out() * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(hipStreamSynchronize(h->stream));
     return 0;
@@ -385,125 +418,116 @@ extern "C" int clothhip_policy_fit_predict_members(clothhip_handle *h, const int
 }
 
 // ---- the optimizer ----------------------------------------------------------------------------------------------------------------------
-// the per-row optimizer state exists from the first step after a new network: every row fresh
-static int ensure_row_state(const FitNet &net) {
-    const size_t rows = net.rows();
-    OptState &o = net.opt;
-    if (o.t.size() == rows && o.zero.size() == rows) return 0;
-    try { o.t.assign(rows, 0); o.zero.assign(rows, 1); } catch (const std::bad_alloc &) {
-        o.forget();
-        return fail(CLOTHHIP_ENOMEM, "out of host memory (%zu rows)", rows);
-    }
-    return 0;
+// the per-row optimizer state exists from the first step after a new network: every row fresh. false: out of host memory, and forgotten
+static bool ensure_row_state(OptState &o, size_t rows) {
+    if (o.t.size() == rows && o.zero.size() == rows) return true;
+    try { o.t.assign(rows, 0); o.zero.assign(rows, 1); } catch (const std::bad_alloc &) { o.forget(); return false; }
+    return true;
 }
 
-// n_steps optimizer steps of `members` with the optimizers p [n_m] over idx [n_steps][n_m][B]; the call is valid and n_steps >= 1.
-// ppo: every step's gradient is the clipped surrogate's, loss_out is then [n_steps][n_m][ppo->stats()]; the optimizer is the net's one.
-// ppo->head (n_m == 1): the same optimizer kernel runs a second time per step over the log-sigma head, a table of one row of four
-// elements with its own state h->fit.opt_sigma and its own step constants (made from p[0]); ls_out (may be NULL) [n_steps][4] gets the
-// head before each step's update
-static int run_fit(clothhip_handle *h, const FitNet &net, const ClothFitParams *p, const int32_t *members, int32_t n_m, const int32_t *idx, int32_t n_steps,
-                   int32_t B, double *loss_out, const FitPpo *ppo = nullptr, float *ls_out = nullptr) {
+// One table the optimizer updates in a step of a call: the rows `members` [n_m] of theta, n elements each at members[j] * stride, with
+// the moments and step counts of `opt`; row j's gradient lies at grad + j * n, and its step constants are made from p[j].
+struct FitTarget {
+    float *theta;
+    OptState &opt;
+    size_t moments;                     // floats of each moment table
+    int64_t stride, n;
+    const int32_t *members;             // host
+    int32_t n_m;
+    const Buffer<float> &grad;          // (a pointer only after the call's reserves)
+    const ClothFitParams *p;
+};
+
+// n_steps optimizer steps of `members` with the optimizers p [n_m] over idx [n_steps][n_m][B]; the call is valid and n_steps >= 1. The
+// optimizer walks one target, the net's rows, and under PPO_SIGMA (n_m == 1) a second one: the log-sigma head, a table of one row of
+// four elements at offset 0 with its own state h->fit.opt_sigma and its own step constants, made from p[0]. Target k's step constants
+// follow those of the targets before it in ONE table, [n_steps][its n_m][FIT_HYPER] each
+static int run_fit(clothhip_handle *h, const FitNet &net, const FitLoss &loss, const ClothFitParams *p, const int32_t *members, int32_t n_m, const int32_t *idx,
+                   int32_t n_steps, int32_t B, const FitOut &out) {
     const bool adam = p[0].optimizer == (float)CLOTHHIP_FIT_ADAM;
     auto &f = h->fit;
-    const MlpDesc &D = net.D;
     const FitPlan pl = fit_plan(net, B);
-    const size_t n = net.n_params, stride = (size_t)D.stride, n_sm = (size_t)n_steps * n_m;
-    const size_t n_moments = net.pop_rows ? (size_t)net.pop_rows * stride : n;
-    const size_t per_loss = ppo ? ppo->stats() : 1;
-    const bool head = ppo && ppo->head;
-    OptState &os = h->fit.opt_sigma;
-    // the step constants of every (step, member), in double on the host, then rounded to float; nothing of the handle changes yet.
-    // With a head its n_steps rows follow the members' n_steps * n_m
-    const size_t n_hyper = (n_sm + (head ? (size_t)n_steps : 0)) * FIT_HYPER;
+    const size_t n_sm = (size_t)n_steps * n_m;
+    const bool head = loss.kind == FitLoss::PPO_SIGMA;
+    const FitTarget targets[2] = {
+        {net.theta, net.opt, net.pop_rows ? (size_t)net.pop_rows * net.D.stride : net.n_params, (int64_t)net.D.stride, (int64_t)net.n_params, members, n_m, f.d_grad, p},
+        {h->pol.d_log_sigma, f.opt_sigma, MLP_OUT, 0, MLP_OUT, SHARED_ROW, 1, f.d_grad_ls, p}};
+    const int n_targets = head ? 2 : 1;
+    // the step constants of every (target, step, member), in double on the host, then rounded to float; nothing of the handle changes yet
+    size_t hyper_at[2], n_hyper = 0;
+    for (int k = 0; k < n_targets; k++) { hyper_at[k] = n_hyper; n_hyper += (size_t)n_steps * targets[k].n_m * FIT_HYPER; }
     std::vector<float> hyper;
     try { hyper.assign(n_hyper, 0.0f); } catch (const std::bad_alloc &) { return fail(CLOTHHIP_ENOMEM, "out of host memory (%zu step constants)", n_hyper); }
-    if (int rc = ensure_row_state(net)) return rc;
-    if (head && (os.t.size() != 1 || os.zero.size() != 1)) {
-        try { os.t.assign(1, 0); os.zero.assign(1, 1); } catch (const std::bad_alloc &) {
-            os.forget();
-            return fail(CLOTHHIP_ENOMEM, "out of host memory (the head's optimizer state)");
-        }
-    }
-    auto step_constants = [adam](float *q, const ClothFitParams &pj, int64_t t1) {      // t1: the 1-based step count of this step
-        if (adam) {
-            const double b1 = (double)pj.beta1, b2 = (double)pj.beta2, t = (double)t1;
-            const double a_t = (double)pj.lr * std::sqrt(1.0 - std::pow(b2, t)) / (1.0 - std::pow(b1, t));
-            q[0] = (float)a_t; q[1] = pj.beta1; q[2] = (float)(1.0 - b1); q[3] = pj.beta2; q[4] = (float)(1.0 - b2); q[5] = pj.eps;
-        } else {
-            q[0] = pj.lr; q[1] = pj.momentum;
-        }
-    };
-    for (int s = 0; s < n_steps; s++) {
-        for (int32_t j = 0; j < n_m; j++) step_constants(hyper.data() + ((size_t)s * n_m + j) * FIT_HYPER, p[j], net.opt.t[members[j]] + s + 1);
-        if (head) step_constants(hyper.data() + (n_sm + s) * FIT_HYPER, p[0], os.t[0] + s + 1);
+    if (!ensure_row_state(net.opt, net.rows())) return fail(CLOTHHIP_ENOMEM, "out of host memory (%zu rows)", net.rows());
+    if (head && !ensure_row_state(f.opt_sigma, 1)) return fail(CLOTHHIP_ENOMEM, "out of host memory (the head's optimizer state)");
+    for (int k = 0; k < n_targets; k++) {
+        const FitTarget &t = targets[k];
+        for (int s = 0; s < n_steps; s++)
+            for (int32_t j = 0; j < t.n_m; j++) {
+                float *q = hyper.data() + hyper_at[k] + ((size_t)s * t.n_m + j) * FIT_HYPER;
+                const ClothFitParams &pj = t.p[j];
+                if (adam) {
+                    const double b1 = (double)pj.beta1, b2 = (double)pj.beta2, t1 = (double)(t.opt.t[t.members[j]] + s + 1);      // t1: the 1-based step count of this step
+                    const double a_t = (double)pj.lr * std::sqrt(1.0 - std::pow(b2, t1)) / (1.0 - std::pow(b1, t1));
+                    q[0] = (float)a_t; q[1] = pj.beta1; q[2] = (float)(1.0 - b1); q[3] = pj.beta2; q[4] = (float)(1.0 - b2); q[5] = pj.eps;
+                } else {
+                    q[0] = pj.lr; q[1] = pj.momentum;
+                }
+            }
     }
     HIPCHECK(hipSetDevice(h->device));
     if (int rc = fit_reserve(h, pl, n_m)) return rc;
     if (int rc = f.d_idx.reserve(n_sm * B * 4)) return rc;
-    if (int rc = f.d_loss.reserve(n_sm * per_loss * 8)) return rc;
+    if (int rc = f.d_loss.reserve(n_sm * loss.stats * 8)) return rc;
     if (int rc = f.d_hyper.reserve(n_hyper * 4)) return rc;
-    if (ppo && ppo->member_q) if (int rc = f.d_ppo_q.reserve((size_t)n_m * 32)) return rc;
+    if (loss.kind == FitLoss::PPO) if (int rc = f.d_ppo_q.reserve((size_t)n_m * 32)) return rc;
     if (head) {
         if (int rc = f.d_grad_ls.reserve(MLP_OUT * 4)) return rc;
         if (int rc = f.d_ls_hist.reserve((size_t)n_steps * MLP_OUT * 4)) return rc;
-        if (int rc = os.m.reserve(MLP_OUT * 4)) return rc;
-        if (int rc = os.v.reserve(MLP_OUT * 4)) return rc;
     }
-    // the moments of the whole table. A table of another network's size holds no row's state (every row is flagged read-as-zeros by
-    // OptState::forget when the network changes), so growing it loses nothing
-    if (int rc = net.opt.m.reserve(n_moments * 4)) return rc;
-    if (int rc = net.opt.v.reserve(n_moments * 4)) return rc;
+    // the moments of each target's whole table. A table of another network's size holds no row's state (every row is flagged
+    // read-as-zeros by OptState::forget when the network changes), so growing it loses nothing
+    for (int k = 0; k < n_targets; k++) {
+        if (int rc = targets[k].opt.m.reserve(targets[k].moments * 4)) return rc;
+        if (int rc = targets[k].opt.v.reserve(targets[k].moments * 4)) return rc;
+    }
     // from here on the call goes through (but for a failure of the runtime itself)
-    for (int32_t j = 0; j < n_m; j++) {
-        const int32_t g = members[j];
-        if (net.opt.zero[g]) {
-            HIPCHECK(hipMemsetAsync(net.opt.m + (size_t)g * stride, 0, n * 4, h->stream));
-            HIPCHECK(hipMemsetAsync(net.opt.v + (size_t)g * stride, 0, n * 4, h->stream));
-            net.opt.zero[g] = 0;
+    for (int k = 0; k < n_targets; k++) {
+        const FitTarget &t = targets[k];
+        for (int32_t j = 0; j < t.n_m; j++) {
+            const int32_t g = t.members[j];
+            if (t.opt.zero[g]) {
+                HIPCHECK(hipMemsetAsync(t.opt.m + (size_t)g * (size_t)t.stride, 0, (size_t)t.n * 4, h->stream));
+                HIPCHECK(hipMemsetAsync(t.opt.v + (size_t)g * (size_t)t.stride, 0, (size_t)t.n * 4, h->stream));
+                t.opt.zero[g] = 0;
+            }
+            t.opt.t[g] += n_steps;
         }
-        net.opt.t[g] += n_steps;
-    }
-    if (head) {
-        if (os.zero[0]) {
-            HIPCHECK(hipMemsetAsync(os.m, 0, MLP_OUT * 4, h->stream));
-            HIPCHECK(hipMemsetAsync(os.v, 0, MLP_OUT * 4, h->stream));
-            os.zero[0] = 0;
-        }
-        os.t[0] += n_steps;
     }
     HIPCHECK(hipMemcpyAsync(f.d_members, members, (size_t)n_m * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipMemcpyAsync(f.d_idx, idx, n_sm * B * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipMemcpyAsync(f.d_hyper, hyper.data(), n_hyper * 4, hipMemcpyHostToDevice, h->stream));
-    if (ppo && ppo->member_q) HIPCHECK(hipMemcpyAsync(f.d_ppo_q, ppo->member_q, (size_t)n_m * 32, hipMemcpyHostToDevice, h->stream));
-    FitOptArgs o = {};
-    o.theta = net.theta; o.m = net.opt.m; o.v = net.opt.v; o.g = f.d_grad; o.members = f.d_members;
-    o.stride = (int64_t)stride; o.n = (int64_t)n; o.blocks = (int32_t)((n + 255) / 256);
-    const dim3 ogrid((unsigned)o.blocks * (unsigned)n_m);
-    // the head as a table of one row (members = {0}, offset 0) of MLP_OUT elements
-    FitOptArgs oh = {};
-    FitPpo step_ppo;
-    if (ppo) step_ppo = *ppo;
-    if (head) { oh.theta = h->pol.d_log_sigma; oh.m = os.m; oh.v = os.v; oh.g = f.d_grad_ls; oh.members = f.d_members; oh.stride = 0; oh.n = MLP_OUT; oh.blocks = 1; }
+    if (loss.kind == FitLoss::PPO) HIPCHECK(hipMemcpyAsync(f.d_ppo_q, loss.q, (size_t)n_m * 32, hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipEventRecord(h->ev0, h->stream));
     for (int s = 0; s < n_steps; s++) {
-        if (head) step_ppo.ls_out = f.d_ls_hist + (size_t)s * MLP_OUT;
-        if (int rc = enqueue_grad(h, net, pl, n_m, f.d_idx + (size_t)s * n_m * B, B, f.d_loss + (size_t)s * n_m * per_loss, false, ppo ? &step_ppo : nullptr)) return rc;
-        o.hyper = f.d_hyper + (size_t)s * n_m * FIT_HYPER;
-        if (adam) hipLaunchKernelGGL(k_fit_adam, ogrid, dim3(256), 0, h->stream, o);
-        else hipLaunchKernelGGL(k_fit_sgd, ogrid, dim3(256), 0, h->stream, o);
-        HIPCHECK(hipGetLastError());
-        if (head) {
-            oh.hyper = f.d_hyper + (n_sm + (size_t)s) * FIT_HYPER;
-            if (adam) hipLaunchKernelGGL(k_fit_adam, dim3(1), dim3(256), 0, h->stream, oh);
-            else hipLaunchKernelGGL(k_fit_sgd, dim3(1), dim3(256), 0, h->stream, oh);
+        if (int rc = enqueue_grad(h, net, pl, loss, n_m, f.d_idx + (size_t)s * n_m * B, B, f.d_loss + (size_t)s * n_m * loss.stats, nullptr,
+                                  head ? f.d_ls_hist + (size_t)s * MLP_OUT : nullptr)) return rc;
+        for (int k = 0; k < n_targets; k++) {      // (the head names its row 0 by the call's own member table: n_m == 1, members = {0})
+            const FitTarget &t = targets[k];
+            FitOptArgs o = {};
+            o.theta = t.theta; o.m = t.opt.m; o.v = t.opt.v; o.g = t.grad; o.members = f.d_members;
+            o.hyper = f.d_hyper + hyper_at[k] + (size_t)s * t.n_m * FIT_HYPER;
+            o.stride = t.stride; o.n = t.n; o.blocks = (int32_t)((t.n + 255) / 256);
+            const dim3 ogrid((unsigned)o.blocks * (unsigned)t.n_m);
+            if (adam) hipLaunchKernelGGL(k_fit_adam, ogrid, dim3(256), 0, h->stream, o);
+            else hipLaunchKernelGGL(k_fit_sgd, ogrid, dim3(256), 0, h->stream, o);
             HIPCHECK(hipGetLastError());
         }
     }
     HIPCHECK(hipEventRecord(h->ev1, h->stream));
     h->have_timing = true;
-    if (loss_out) HIPCHECK(hipMemcpyAsync(loss_out, f.d_loss, n_sm * per_loss * 8, hipMemcpyDeviceToHost, h->stream));
-    if (head && ls_out) HIPCHECK(hipMemcpyAsync(ls_out, f.d_ls_hist, (size_t)n_steps * MLP_OUT * 4, hipMemcpyDeviceToHost, h->stream));
+    if (out.loss) HIPCHECK(hipMemcpyAsync(out.loss, f.d_loss, n_sm * loss.stats * 8, hipMemcpyDeviceToHost, h->stream));
+    if (head && out.ls) HIPCHECK(hipMemcpyAsync(out.ls, f.d_ls_hist, (size_t)n_steps * MLP_OUT * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(hipStreamSynchronize(h->stream));      // (the host tables are never retained)
     return 0;
 }
@@ -516,7 +540,7 @@ extern "C" int clothhip_policy_fit(clothhip_handle *h, const ClothFitParams *p, 
     if (int rc = check_fit_rows(h, 1, idx, (int64_t)n_steps * B, B)) return rc;
     if (int rc = check_fit_params(p, -1)) return rc;
     if (n_steps == 0) return 0;
-    return run_fit(h, policy_net(h), p, SHARED_ROW, 1, idx, n_steps, B, loss_out);
+    return run_fit(h, policy_net(h), squared_error(), p, SHARED_ROW, 1, idx, n_steps, B, {loss_out});
 }
 
 extern "C" int clothhip_policy_fit_members(clothhip_handle *h, const ClothFitParams *p, const int32_t *members, int32_t n_m, const int32_t *idx,
@@ -527,12 +551,9 @@ extern "C" int clothhip_policy_fit_members(clothhip_handle *h, const ClothFitPar
     if (n_steps < 0) return fail(CLOTHHIP_EINVAL, "n_steps < 0");
     if (int rc = check_fit_members(h, members, n_m)) return rc;
     if (int rc = check_fit_rows(h, n_m, idx, (int64_t)n_steps * n_m * B, B)) return rc;
-    for (int32_t j = 0; j < n_m; j++) {
-        if (int rc = check_fit_params(p + j, j)) return rc;
-        if (p[j].optimizer != p[0].optimizer) return fail(CLOTHHIP_EINVAL, "p[%d].optimizer = %g, p[0].optimizer = %g: one optimizer per call", j, (double)p[j].optimizer, (double)p[0].optimizer);
-    }
+    if (int rc = check_fit_params_members(p, n_m)) return rc;
     if (n_steps == 0) return 0;
-    return run_fit(h, policy_net(h), p, members, n_m, idx, n_steps, B, loss_out);
+    return run_fit(h, policy_net(h), squared_error(), p, members, n_m, idx, n_steps, B, {loss_out});
 }
 
 extern "C" int clothhip_policy_fit_reset(clothhip_handle *h) {
@@ -582,28 +603,44 @@ extern "C" int clothhip_fit_data_snapshot_policy(clothhip_handle *h, int64_t fir
     return 0;
 }
 
-// the constants of member j of a PPO call (j < 0: of the shared network, named without an index) -> the kernel's constants
-static int check_ppo_consts(const ClothPpoParams *q, int32_t j, FitPpo *out) {
+// the constants of member j of a PPO call (j < 0: of the shared network, named without an index) -> row [4], the kernel's constants
+static int check_ppo_consts(const ClothPpoParams *q, int32_t j, double *row) {
     char who[24] = "";
     if (j >= 0) snprintf(who, sizeof(who), "q[%d]: ", j);
     if (!std::isfinite(q->sigma) || q->sigma <= 0.0) return fail(CLOTHHIP_EINVAL, "%ssigma = %g: the policy's standard deviation is finite and > 0", who, q->sigma);
     if (!std::isfinite(q->clip) || q->clip < 0.0 || q->clip >= 1.0) return fail(CLOTHHIP_EINVAL, "%sclip = %g: the clip range lies in [0, 1)", who, q->clip);
     const double s2 = q->sigma * q->sigma;
-    out->inv_s2 = 1.0 / s2;
-    out->half_inv_s2 = 0.5 * out->inv_s2;
-    out->lo = 1.0 - q->clip;
-    out->hi = 1.0 + q->clip;
-    if (!std::isfinite(out->inv_s2)) return fail(CLOTHHIP_EINVAL, "%ssigma = %g: 1 / sigma^2 is not a finite double", who, q->sigma);
+    row[0] = 1.0 / s2;
+    row[1] = 0.5 * row[0];
+    row[2] = 1.0 - q->clip;
+    row[3] = 1.0 + q->clip;
+    if (!std::isfinite(row[0])) return fail(CLOTHHIP_EINVAL, "%ssigma = %g: 1 / sigma^2 is not a finite double", who, q->sigma);
     return 0;
 }
-// the constants of a PPO call and the rows of its minibatches, after everything clothhip_policy_fit refuses: -> the kernel's constants
-static int check_ppo(const clothhip_handle *h, const ClothPpoParams *q, const int32_t *idx, int64_t n_idx, FitPpo *out) {
-    if (int rc = check_ppo_consts(q, -1, out)) return rc;
-    for (int64_t i = 0; i < n_idx; i++)
-        if (!h->dataset.h_old_set[(size_t)idx[i]])
-            return fail(CLOTHHIP_ESTATE, "idx[%lld] = row %d has no old mean: call clothhip_fit_data_snapshot_policy or clothhip_fit_data_set_old_means on it first",
+// every row of the minibatches idx [n_steps][n_m][B] (n_idx entries) has its old mean and, log_sigma: its old log sigma. members
+// NULL: the shared network's call (n_m == 1), else the refusal names the member whose row it is
+static int check_old_set(const clothhip_handle *h, const int32_t *members, int32_t n_m, const int32_t *idx, int64_t n_idx, int32_t B, bool log_sigma) {
+    for (int64_t i = 0; i < n_idx; i++) {
+        if (!h->dataset.h_old_set[(size_t)idx[i]]) {
+            char who[40] = "";
+            if (members) snprintf(who, sizeof(who), " of member %lld", (long long)members[(i / B) % n_m]);
+            return fail(CLOTHHIP_ESTATE, "idx[%lld] = row %d%s has no old mean: call clothhip_fit_data_snapshot_policy%s or clothhip_fit_data_set_old_means on it first",
+                        (long long)i, idx[i], who, members ? "_members" : "");
+        }
+        if (log_sigma && !h->dataset.h_old_ls_set[(size_t)idx[i]])
+            return fail(CLOTHHIP_ESTATE, "idx[%lld] = row %d has no old log sigma: call clothhip_fit_data_snapshot_policy (with the head on the handle) or clothhip_fit_data_set_old_log_sigma on it first",
                         (long long)i, idx[i]);
+    }
     return 0;
+}
+// the constants q [n_m] of a PPO call and the rows of its minibatches, after everything clothhip_policy_fit / _members refuses:
+// -> tab [n_m][4], the table k_fit_loss_ppo reads. members NULL: the shared network's call, a table of one row
+static int check_ppo(const clothhip_handle *h, const ClothPpoParams *q, const int32_t *members, int32_t n_m, const int32_t *idx, int64_t n_idx, int32_t B,
+                     std::vector<double> *tab) {
+    try { tab->resize((size_t)n_m * 4); } catch (const std::bad_alloc &) { return fail(CLOTHHIP_ENOMEM, "out of host memory (%d members)", n_m); }
+    for (int32_t j = 0; j < n_m; j++)
+        if (int rc = check_ppo_consts(q + j, members ? j : -1, tab->data() + (size_t)j * 4)) return rc;
+    return check_old_set(h, members, n_m, idx, n_idx, B, false);
 }
 
 extern "C" int clothhip_policy_fit_ppo_grad(clothhip_handle *h, const ClothPpoParams *q, const int32_t *idx, int32_t B, float *grad_out, double *stats_out,
@@ -612,9 +649,9 @@ extern "C" int clothhip_policy_fit_ppo_grad(clothhip_handle *h, const ClothPpoPa
     if (!q) return fail(CLOTHHIP_EINVAL, "NULL argument");
     if (int rc = check_fit_state(h, false)) return rc;
     if (int rc = check_fit_rows(h, 1, idx, B, B)) return rc;
-    FitPpo ppo;
-    if (int rc = check_ppo(h, q, idx, B, &ppo)) return rc;
-    return run_grad(h, policy_net(h), SHARED_ROW, 1, idx, B, grad_out, stats_out, &ppo, ratio_out);
+    std::vector<double> tab;
+    if (int rc = check_ppo(h, q, nullptr, 1, idx, B, B, &tab)) return rc;
+    return run_grad(h, policy_net(h), ppo_loss(tab.data()), SHARED_ROW, 1, idx, B, {stats_out, grad_out, ratio_out});
 }
 
 extern "C" int clothhip_policy_fit_ppo(clothhip_handle *h, const ClothFitParams *p, const ClothPpoParams *q, const int32_t *idx, int32_t n_steps, int32_t B,
@@ -625,10 +662,10 @@ extern "C" int clothhip_policy_fit_ppo(clothhip_handle *h, const ClothFitParams 
     if (int rc = check_fit_state(h, false)) return rc;
     if (int rc = check_fit_rows(h, 1, idx, (int64_t)n_steps * B, B)) return rc;
     if (int rc = check_fit_params(p, -1)) return rc;
-    FitPpo ppo;
-    if (int rc = check_ppo(h, q, idx, (int64_t)n_steps * B, &ppo)) return rc;
+    std::vector<double> tab;
+    if (int rc = check_ppo(h, q, nullptr, 1, idx, (int64_t)n_steps * B, B, &tab)) return rc;
     if (n_steps == 0) return 0;
-    return run_fit(h, policy_net(h), p, SHARED_ROW, 1, idx, n_steps, B, stats_out, &ppo);
+    return run_fit(h, policy_net(h), ppo_loss(tab.data()), p, SHARED_ROW, 1, idx, n_steps, B, {stats_out});
 }
 
 // ---- PPO for a population (clothhip.h: PPO FOR A POPULATION): the snapshot by member, and the two entries above as grouped calls ---------
@@ -637,6 +674,47 @@ extern "C" int clothhip_policy_fit_ppo(clothhip_handle *h, const ClothFitParams 
 // longest first, as many as CLOTHHIP_FIT_MAX_MEMBER_ROWS holds at the longest one's length B. A shorter segment is padded to B with its
 // own first row (a valid row of the same member: the layer-0 gather stays in range), which k_fit_scatter_y does not store.
 struct SnapChunk { size_t m0, idx0; int32_t n_m, B; };      // offsets into the call's member / length tables and its index table
+struct SnapPlan {
+    std::vector<int32_t> mem, len, idx;      // per chunk member: the population row and its real positions; the index tables [n_m][B], chunk after chunk
+    std::vector<SnapChunk> chunks;           // none: no row names a member
+};
+// the plan of rows [first, first + n) under member_of_row (every entry in [-1, pop_rows))
+static int plan_snapshot(int64_t pop_rows, int64_t first, int64_t n, const int32_t *member_of_row, SnapPlan *out) {
+    std::vector<int32_t> &mem = out->mem, &len = out->len, &idx = out->idx;
+    try {
+        // the rows of every member, ascending, as one table sorted by (member, row): start[g] .. start[g + 1]
+        std::vector<int64_t> start((size_t)pop_rows + 1, 0);
+        for (int64_t i = 0; i < n; i++) if (member_of_row[i] >= 0) start[(size_t)member_of_row[i] + 1]++;
+        for (size_t g = 0; g < (size_t)pop_rows; g++) start[g + 1] += start[g];
+        const int64_t named = start[(size_t)pop_rows];
+        if (named == 0) return 0;
+        std::vector<int32_t> by_member((size_t)named);
+        std::vector<int64_t> at(start.begin(), start.end() - 1);
+        for (int64_t i = 0; i < n; i++) if (member_of_row[i] >= 0) by_member[(size_t)at[(size_t)member_of_row[i]]++] = (int32_t)(first + i);
+        for (int64_t k = 0;; k++) {          // the k-th segments
+            std::vector<std::pair<int32_t, int32_t>> seg;      // (length, member), longest first
+            for (int64_t g = 0; g < pop_rows; g++) {
+                const int64_t rest = start[(size_t)g + 1] - start[(size_t)g] - k * FIT_MAX_BATCH;
+                if (rest > 0) seg.push_back({(int32_t)std::min<int64_t>(rest, FIT_MAX_BATCH), (int32_t)g});
+            }
+            if (seg.empty()) break;
+            std::stable_sort(seg.begin(), seg.end(), [](const std::pair<int32_t, int32_t> &a, const std::pair<int32_t, int32_t> &b) { return a.first > b.first; });
+            for (size_t s0 = 0; s0 < seg.size();) {
+                const int32_t B = seg[s0].first;
+                const size_t n_m = std::min<size_t>(seg.size() - s0, (size_t)(CLOTHHIP_FIT_MAX_MEMBER_ROWS / B));
+                out->chunks.push_back({mem.size(), idx.size(), (int32_t)n_m, B});
+                for (size_t j = s0; j < s0 + n_m; j++) {
+                    const int32_t *rows = by_member.data() + start[(size_t)seg[j].second] + k * FIT_MAX_BATCH;
+                    mem.push_back(seg[j].second); len.push_back(seg[j].first);
+                    idx.insert(idx.end(), rows, rows + seg[j].first);
+                    idx.insert(idx.end(), (size_t)(B - seg[j].first), rows[0]);
+                }
+                s0 += n_m;
+            }
+        }
+    } catch (const std::bad_alloc &) { return fail(CLOTHHIP_ENOMEM, "out of host memory (%lld rows)", (long long)n); }
+    return 0;
+}
 
 extern "C" int clothhip_fit_data_snapshot_policy_members(clothhip_handle *h, int64_t first, int64_t n, const int32_t *member_of_row) {
     if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
@@ -650,53 +728,22 @@ extern "C" int clothhip_fit_data_snapshot_policy_members(clothhip_handle *h, int
     auto &f = h->fit;
     const FitNet net = policy_net(h);
     const int L = net.D.n_layers;
-    std::vector<int32_t> mem, len, idx;      // per chunk member: the population row and its real positions; the index tables [n_m][B], chunk after chunk
-    std::vector<SnapChunk> chunks;
-    try {
-        // the rows of every member, ascending, as one table sorted by (member, row): start[g] .. start[g + 1]
-        std::vector<int64_t> start((size_t)h->pol.pop_rows + 1, 0);
-        for (int64_t i = 0; i < n; i++) if (member_of_row[i] >= 0) start[(size_t)member_of_row[i] + 1]++;
-        for (size_t g = 0; g < (size_t)h->pol.pop_rows; g++) start[g + 1] += start[g];
-        const int64_t named = start[(size_t)h->pol.pop_rows];
-        if (named == 0) return 0;
-        std::vector<int32_t> by_member((size_t)named);
-        std::vector<int64_t> at(start.begin(), start.end() - 1);
-        for (int64_t i = 0; i < n; i++) if (member_of_row[i] >= 0) by_member[(size_t)at[(size_t)member_of_row[i]]++] = (int32_t)(first + i);
-        for (int64_t k = 0;; k++) {          // the k-th segments
-            std::vector<std::pair<int32_t, int32_t>> seg;      // (length, member), longest first
-            for (int64_t g = 0; g < h->pol.pop_rows; g++) {
-                const int64_t rest = start[(size_t)g + 1] - start[(size_t)g] - k * FIT_MAX_BATCH;
-                if (rest > 0) seg.push_back({(int32_t)std::min<int64_t>(rest, FIT_MAX_BATCH), (int32_t)g});
-            }
-            if (seg.empty()) break;
-            std::stable_sort(seg.begin(), seg.end(), [](const std::pair<int32_t, int32_t> &a, const std::pair<int32_t, int32_t> &b) { return a.first > b.first; });
-            for (size_t s0 = 0; s0 < seg.size();) {
-                const int32_t B = seg[s0].first;
-                const size_t n_m = std::min<size_t>(seg.size() - s0, (size_t)(CLOTHHIP_FIT_MAX_MEMBER_ROWS / B));
-                chunks.push_back({mem.size(), idx.size(), (int32_t)n_m, B});
-                for (size_t j = s0; j < s0 + n_m; j++) {
-                    const int32_t *rows = by_member.data() + start[(size_t)seg[j].second] + k * FIT_MAX_BATCH;
-                    mem.push_back(seg[j].second); len.push_back(seg[j].first);
-                    idx.insert(idx.end(), rows, rows + seg[j].first);
-                    idx.insert(idx.end(), (size_t)(B - seg[j].first), rows[0]);
-                }
-                s0 += n_m;
-            }
-        }
-    } catch (const std::bad_alloc &) { return fail(CLOTHHIP_ENOMEM, "out of host memory (%lld rows)", (long long)n); }
+    SnapPlan s;
+    if (int rc = plan_snapshot(h->pol.pop_rows, first, n, member_of_row, &s)) return rc;
+    if (s.chunks.empty()) return 0;
     HIPCHECK(hipSetDevice(h->device));
     // every chunk's scratch before the first launch: a buffer that grows is freed first
-    for (const SnapChunk &c : chunks) if (int rc = fit_reserve(h, fit_plan(net, c.B), c.n_m)) return rc;
-    if (int rc = f.d_len.reserve(len.size() * 4)) return rc;
-    if (int rc = f.d_idx.reserve(idx.size() * 4)) return rc;
-    HIPCHECK(hipMemcpyAsync(f.d_len, len.data(), len.size() * 4, hipMemcpyHostToDevice, h->stream));
-    HIPCHECK(hipMemcpyAsync(f.d_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, h->stream));
+    for (const SnapChunk &c : s.chunks) if (int rc = fit_reserve(h, fit_plan(net, c.B), c.n_m)) return rc;
+    if (int rc = f.d_len.reserve(s.len.size() * 4)) return rc;
+    if (int rc = f.d_idx.reserve(s.idx.size() * 4)) return rc;
+    HIPCHECK(hipMemcpyAsync(f.d_len, s.len.data(), s.len.size() * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipMemcpyAsync(f.d_idx, s.idx.data(), s.idx.size() * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHECK(hipEventRecord(h->ev0, h->stream));
-    for (const SnapChunk &c : chunks) {
+    for (const SnapChunk &c : s.chunks) {
         const FitPlan p = fit_plan(net, c.B);
         // (the launches read the chunk's members at the head of d_members: stream order keeps the chunks apart)
-        HIPCHECK(hipMemcpyAsync(f.d_members, mem.data() + c.m0, (size_t)c.n_m * 4, hipMemcpyHostToDevice, h->stream));
-        if (int rc = enqueue_grad(h, net, p, c.n_m, f.d_idx + c.idx0, c.B, nullptr)) return rc;
+        HIPCHECK(hipMemcpyAsync(f.d_members, s.mem.data() + c.m0, (size_t)c.n_m * 4, hipMemcpyHostToDevice, h->stream));
+        if (int rc = enqueue_forward(h, net, p, c.n_m, f.d_idx + c.idx0, c.B, false)) return rc;
         launch_fit_scatter_y(h->stream, c.n_m, f.d_act + p.h_off[L - 1], f.d_idx + c.idx0, f.d_len + c.m0, h->dataset.old(), c.B, (int64_t)p.act);
         HIPCHECK(hipGetLastError());
     }
@@ -704,24 +751,6 @@ extern "C" int clothhip_fit_data_snapshot_policy_members(clothhip_handle *h, int
     h->have_timing = true;
     HIPCHECK(hipStreamSynchronize(h->stream));      // (the host tables the uploads read go out of scope)
     for (int64_t i = 0; i < n; i++) if (member_of_row[i] >= 0) h->dataset.h_old_set[(size_t)(first + i)] = 1;
-    return 0;
-}
-
-// the constants q [n_m] of a grouped PPO call and the rows of its minibatches idx [n_steps][n_m][B], after everything
-// clothhip_policy_fit_members refuses: -> tab [n_m][4], the table k_fit_loss_ppo_members reads
-static int check_ppo_members(const clothhip_handle *h, const ClothPpoParams *q, const int32_t *members, int32_t n_m, const int32_t *idx, int32_t n_steps, int32_t B, std::vector<double> *tab) {
-    try { tab->resize((size_t)n_m * 4); } catch (const std::bad_alloc &) { return fail(CLOTHHIP_ENOMEM, "out of host memory (%d members)", n_m); }
-    for (int32_t j = 0; j < n_m; j++) {
-        FitPpo c;
-        if (int rc = check_ppo_consts(q + j, j, &c)) return rc;
-        double *t = tab->data() + (size_t)j * 4;
-        t[0] = c.inv_s2; t[1] = c.half_inv_s2; t[2] = c.lo; t[3] = c.hi;
-    }
-    const int64_t n_idx = (int64_t)n_steps * n_m * B;
-    for (int64_t i = 0; i < n_idx; i++)
-        if (!h->dataset.h_old_set[(size_t)idx[i]])
-            return fail(CLOTHHIP_ESTATE, "idx[%lld] = row %d of member %lld has no old mean: call clothhip_fit_data_snapshot_policy_members or clothhip_fit_data_set_old_means on it first",
-                        (long long)i, idx[i], (long long)members[(i / B) % n_m]);
     return 0;
 }
 
@@ -733,11 +762,8 @@ extern "C" int clothhip_policy_fit_ppo_grad_members(clothhip_handle *h, const Cl
     if (int rc = check_fit_members(h, members, n_m)) return rc;
     if (int rc = check_fit_rows(h, n_m, idx, (int64_t)n_m * B, B)) return rc;
     std::vector<double> tab;
-    if (int rc = check_ppo_members(h, q, members, n_m, idx, 1, B, &tab)) return rc;
-    FitPpo ppo;
-    ppo.inv_s2 = ppo.half_inv_s2 = ppo.lo = ppo.hi = 0.0;      // (not read: the kernel takes the table's)
-    ppo.member_q = tab.data();
-    return run_grad(h, policy_net(h), members, n_m, idx, B, grad_out, stats_out, &ppo, ratio_out);
+    if (int rc = check_ppo(h, q, members, n_m, idx, (int64_t)n_m * B, B, &tab)) return rc;
+    return run_grad(h, policy_net(h), ppo_loss(tab.data()), members, n_m, idx, B, {stats_out, grad_out, ratio_out});
 }
 
 extern "C" int clothhip_policy_fit_ppo_members(clothhip_handle *h, const ClothFitParams *p, const ClothPpoParams *q, const int32_t *members, int32_t n_m,
@@ -748,42 +774,23 @@ extern "C" int clothhip_policy_fit_ppo_members(clothhip_handle *h, const ClothFi
     if (n_steps < 0) return fail(CLOTHHIP_EINVAL, "n_steps < 0");
     if (int rc = check_fit_members(h, members, n_m)) return rc;
     if (int rc = check_fit_rows(h, n_m, idx, (int64_t)n_steps * n_m * B, B)) return rc;
-    for (int32_t j = 0; j < n_m; j++) {
-        if (int rc = check_fit_params(p + j, j)) return rc;
-        if (p[j].optimizer != p[0].optimizer) return fail(CLOTHHIP_EINVAL, "p[%d].optimizer = %g, p[0].optimizer = %g: one optimizer per call", j, (double)p[j].optimizer, (double)p[0].optimizer);
-    }
+    if (int rc = check_fit_params_members(p, n_m)) return rc;
     std::vector<double> tab;
-    if (int rc = check_ppo_members(h, q, members, n_m, idx, n_steps, B, &tab)) return rc;
+    if (int rc = check_ppo(h, q, members, n_m, idx, (int64_t)n_steps * n_m * B, B, &tab)) return rc;
     if (n_steps == 0) return 0;
-    FitPpo ppo;
-    ppo.inv_s2 = ppo.half_inv_s2 = ppo.lo = ppo.hi = 0.0;      // (not read: the kernel takes the table's)
-    ppo.member_q = tab.data();
-    return run_fit(h, policy_net(h), p, members, n_m, idx, n_steps, B, stats_out, &ppo);
+    return run_fit(h, policy_net(h), ppo_loss(tab.data()), p, members, n_m, idx, n_steps, B, {stats_out});
 }
 
 // ---- PPO with a learned sigma: one more loss mode, and the head as one more table of the optimizer (clothhip.h: PPO WITH A LEARNED SIGMA) ----
 static_assert(FIT_PPO_SIGMA_STATS == CLOTHHIP_PPO_SIGMA_STATS, "the statistics of the header and of the kernel");
 static_assert(sizeof(ClothPpoSigmaParams) == 16, "ClothPpoSigmaParams is two doubles");
 
-// the constants of such a call and the rows of its minibatches, after everything clothhip_policy_fit refuses: -> the kernel's constants
-static int check_ppo_sigma(const clothhip_handle *h, const ClothPpoSigmaParams *q, const int32_t *idx, int64_t n_idx, FitPpo *out) {
+// the constants of such a call and the rows of its minibatches, after everything clothhip_policy_fit refuses: -> the loss
+static int check_ppo_sigma(const clothhip_handle *h, const ClothPpoSigmaParams *q, const int32_t *idx, int64_t n_idx, int32_t B, FitLoss *out) {
     if (!std::isfinite(q->clip) || q->clip < 0.0 || q->clip >= 1.0) return fail(CLOTHHIP_EINVAL, "clip = %g: the clip range lies in [0, 1)", q->clip);
     if (!std::isfinite(q->ent_coef) || q->ent_coef < 0.0) return fail(CLOTHHIP_EINVAL, "ent_coef = %g: the entropy coefficient is finite and >= 0", q->ent_coef);
-    *out = FitPpo{};
-    out->inv_s2 = 1.0; out->half_inv_s2 = 0.5;      // (not read: the kernel forms 1 / sigma^2 from the head)
-    out->lo = 1.0 - q->clip;
-    out->hi = 1.0 + q->clip;
-    out->head = true;
-    out->ent_coef = q->ent_coef;
-    for (int64_t i = 0; i < n_idx; i++) {
-        if (!h->dataset.h_old_set[(size_t)idx[i]])
-            return fail(CLOTHHIP_ESTATE, "idx[%lld] = row %d has no old mean: call clothhip_fit_data_snapshot_policy or clothhip_fit_data_set_old_means on it first",
-                        (long long)i, idx[i]);
-        if (!h->dataset.h_old_ls_set[(size_t)idx[i]])
-            return fail(CLOTHHIP_ESTATE, "idx[%lld] = row %d has no old log sigma: call clothhip_fit_data_snapshot_policy (with the head on the handle) or clothhip_fit_data_set_old_log_sigma on it first",
-                        (long long)i, idx[i]);
-    }
-    return 0;
+    *out = ppo_sigma_loss(1.0 - q->clip, 1.0 + q->clip, q->ent_coef);
+    return check_old_set(h, nullptr, 1, idx, n_idx, B, true);
 }
 static int check_head(const clothhip_handle *h) {
     if (!h->pol.has_log_sigma) return fail(CLOTHHIP_ESTATE, "no log-sigma head on this handle: call clothhip_set_policy_log_sigma first");
@@ -797,9 +804,9 @@ extern "C" int clothhip_policy_fit_ppo_sigma_grad(clothhip_handle *h, const Clot
     if (int rc = check_fit_state(h, false)) return rc;
     if (int rc = check_head(h)) return rc;
     if (int rc = check_fit_rows(h, 1, idx, B, B)) return rc;
-    FitPpo ppo;
-    if (int rc = check_ppo_sigma(h, q, idx, B, &ppo)) return rc;
-    return run_grad(h, policy_net(h), SHARED_ROW, 1, idx, B, grad_out, stats_out, &ppo, ratio_out, grad_ls_out);
+    FitLoss loss;
+    if (int rc = check_ppo_sigma(h, q, idx, B, B, &loss)) return rc;
+    return run_grad(h, policy_net(h), loss, SHARED_ROW, 1, idx, B, {stats_out, grad_out, ratio_out, grad_ls_out});
 }
 
 extern "C" int clothhip_policy_fit_ppo_sigma(clothhip_handle *h, const ClothFitParams *p, const ClothPpoSigmaParams *q, const int32_t *idx, int32_t n_steps, int32_t B,
@@ -811,10 +818,10 @@ extern "C" int clothhip_policy_fit_ppo_sigma(clothhip_handle *h, const ClothFitP
     if (int rc = check_head(h)) return rc;
     if (int rc = check_fit_rows(h, 1, idx, (int64_t)n_steps * B, B)) return rc;
     if (int rc = check_fit_params(p, -1)) return rc;
-    FitPpo ppo;
-    if (int rc = check_ppo_sigma(h, q, idx, (int64_t)n_steps * B, &ppo)) return rc;
+    FitLoss loss;
+    if (int rc = check_ppo_sigma(h, q, idx, (int64_t)n_steps * B, B, &loss)) return rc;
     if (n_steps == 0) return 0;
-    return run_fit(h, policy_net(h), p, SHARED_ROW, 1, idx, n_steps, B, stats_out, &ppo, log_sigma_out);
+    return run_fit(h, policy_net(h), loss, p, SHARED_ROW, 1, idx, n_steps, B, {stats_out, nullptr, nullptr, nullptr, log_sigma_out});
 }
 
 extern "C" int clothhip_selftest_exp_fixed(const double *x, int64_t n, double *out) {
@@ -831,7 +838,7 @@ extern "C" int clothhip_value_fit_grad(clothhip_handle *h, const int32_t *idx, i
     if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
     if (int rc = check_value_state(h)) return rc;
     if (int rc = check_fit_rows(h, 1, idx, B, B)) return rc;
-    return run_grad(h, value_net(h), SHARED_ROW, 1, idx, B, grad_out, loss_out);
+    return run_grad(h, value_net(h), squared_error(), SHARED_ROW, 1, idx, B, {loss_out, grad_out});
 }
 
 extern "C" int clothhip_value_fit(clothhip_handle *h, const ClothFitParams *p, const int32_t *idx, int32_t n_steps, int32_t B, double *loss_out) {
@@ -842,7 +849,7 @@ extern "C" int clothhip_value_fit(clothhip_handle *h, const ClothFitParams *p, c
     if (int rc = check_fit_rows(h, 1, idx, (int64_t)n_steps * B, B)) return rc;
     if (int rc = check_fit_params(p, -1)) return rc;
     if (n_steps == 0) return 0;
-    return run_fit(h, value_net(h), p, SHARED_ROW, 1, idx, n_steps, B, loss_out);
+    return run_fit(h, value_net(h), squared_error(), p, SHARED_ROW, 1, idx, n_steps, B, {loss_out});
 }
 
 extern "C" int clothhip_value_fit_reset(clothhip_handle *h) {
@@ -888,7 +895,7 @@ extern "C" int clothhip_fit_data_gae(clothhip_handle *h, int64_t first, int64_t 
     if (int rc = f.d_gae_a.reserve((size_t)n * 8)) return rc;
     if (int rc = f.d_gae_stat.reserve(16)) return rc;
     if (int rc = f.d_adv.reserve((size_t)n * 4)) return rc;
-    if (int rc = enqueue_predict(h, value_net(h), SHARED_ROW, 1, idx.data(), n)) return rc;      // (records ev0; the scan moves ev1 behind itself)
+    if (int rc = enqueue_predict(h, value_net(h), SHARED_ROW, 1, idx.data(), n, nullptr)) return rc;      // (records ev0; the scan moves ev1 behind itself)
     const bool write_w = (p->flags & CLOTHHIP_GAE_WRITE_WEIGHTS) != 0, normalize = (p->flags & CLOTHHIP_GAE_NORMALIZE) != 0;
     GaeArgs a = {};
     a.v = f.d_pred; a.rew = d.rew(); a.next = d.next(); a.ret = d.ret(); a.w = d.w(); a.A = f.d_gae_a; a.adv = f.d_adv; a.stat = f.d_gae_stat;

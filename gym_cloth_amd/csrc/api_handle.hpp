@@ -250,9 +250,9 @@ struct clothhip_handle : HostPlan {
         Buffer<float> d_act, d_dz, d_part, d_grad, d_hyper;
         Buffer<double> d_loss;
         Buffer<float> d_pred;        // clothhip_policy_fit_predict*: y of every member and row, [n_m][n][4]; clothhip_value_predict and clothhip_fit_data_gae: v [n]
-        Buffer<float> d_ratio;       // clothhip_policy_fit_ppo_grad: (float)rho of the minibatch's rows, [B]
-        Buffer<float> d_grad_ls, d_ls_hist;      // clothhip_policy_fit_ppo_sigma*: the head's gradient [4]; the head before every step, [n_steps][4]
-        Buffer<double> d_ppo_q;      // clothhip_policy_fit_ppo*_members: the members' constants {inv_s2, half_inv_s2, lo, hi}, [n_m][4]
+        Buffer<float> d_ratio;       // clothhip_policy_fit_ppo*_grad*: (float)rho of every member's minibatch rows, [n_m][B]
+        Buffer<float> d_grad_ls, d_ls_hist;      // clothhip_policy_fit_ppo_sigma*: the head's gradient [4], the optimizer's second table; the head before every step, [n_steps][4]
+        Buffer<double> d_ppo_q;      // every fixed-sigma PPO call: member j's constants {inv_s2, half_inv_s2, lo, hi} in row j, [n_m][4]; ONE row for the shared network
         Buffer<int32_t> d_len;       // clothhip_fit_data_snapshot_policy_members: the real positions of every member's index row, per chunk
         // clothhip_fit_data_gae: A of every row of the range as a double, the advantages as floats, {mean, std} of the normalisation
         Buffer<double> d_gae_a, d_gae_stat;

@@ -38,9 +38,9 @@
 //     columns or 15 k are the zeros in LDS above; k_fit_loss<1> sums B squares in the order k_fit_loss<4> sums 4 B;
 //   * PPO's clipped surrogate (clothhip.h: PPO ON THE DEVICE) is one more loss launch of the policy's table, k_fit_loss_ppo in the place of
 //     k_fit_loss<4>: per row a probability ratio against the dataset's stored old mean through exp_fixed, dZ in double with one rounding
-//     to float32, three sums over ROWS in the order above; forward, backward and optimizer are the launches of the squared error;
-//     for rows of a population (clothhip.h: PPO FOR A POPULATION) k_fit_loss_ppo_members runs the same body with member j's own
-//     constants, row j of a table the host made;
+//     to float32, three sums over ROWS in the order above; forward, backward and optimizer are the launches of the squared error.
+//     Member j's constants are row j of a table the host made: one row for the shared network, a row per member for rows of a
+//     population (clothhip.h: PPO FOR A POPULATION);
 //   * PPO with a LEARNED sigma (clothhip.h: PPO WITH A LEARNED SIGMA) is one more loss launch again, k_fit_loss_ppo_sigma: the head
 //     log_sigma[4] read from device memory, the row's old log sigma beside its old mean, nine exp_fixed per row, seven sums over ROWS;
 //     the head is one more table of one row of four elements for k_fit_adam / k_fit_sgd, launched a second time per step;
@@ -181,6 +181,19 @@ __global__ __launch_bounds__(64) void k_fit_colsum(const float *dz, int32_t B, i
     db[(int64_t)j * db_step + c] = s;
 }
 
+// The halving tree of the three loss kernels below: each of the N rows of red holds the 256 per-thread sums of one quantity, written by
+// its thread; afterwards red[i][0] is row i's sum, red[i][t] + red[i][t + o] for o = 128, 64, ... 1. Every thread of the 256 calls it.
+template <int N> __device__ __forceinline__ void fit_tree_sums(double (&red)[N][256], const int tid) {
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) {
+#pragma unroll
+            for (int i = 0; i < N; i++) red[i][tid] = red[i][tid] + red[i][tid + o];
+        }
+        __syncthreads();
+    }
+}
+
 // dz[r][k] = fl(fl(w fl(y - a)) / fl(2 B)) with a = lab[rows[r]][k] and w = wgt[rows[r]]; loss = sum (double)w (double)(y - a)^2 / (4 B).
 // One workgroup of 256 per member: y, dz and the index rows at j times their per-member sizes, the loss at loss[j]. The four lanes of a
 // row read ONE weight (the same dword: one request); w = 1.0f leaves both products' bits alone, so an unweighted dataset keeps its bits.
@@ -190,7 +203,7 @@ __global__ __launch_bounds__(64) void k_fit_colsum(const float *dz, int32_t B, i
 template <int W> __global__ __launch_bounds__(256) void k_fit_loss(const float *y, const float *lab, const float *wgt, const int32_t *rows, int32_t B, float *dz,
                                                                    double *loss, int64_t y_step, int64_t dz_step, int64_t rows_step) {
     static_assert(W == 4 || W == 1, "an action or a value");
-    __shared__ double red[256];
+    __shared__ double red[1][256];
     const int64_t j = blockIdx.x;
     y += j * y_step; dz += j * dz_step; rows += j * rows_step;
     const int tid = threadIdx.x, n = W * B;
@@ -212,13 +225,9 @@ template <int W> __global__ __launch_bounds__(256) void k_fit_loss(const float *
             s = s + sq;
         }
     }
-    red[tid] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) red[tid] = red[tid] + red[tid + o];
-        __syncthreads();
-    }
-    if (tid == 0) loss[j] = red[0] / (double)((W == 4 ? 4 : 2) * (int64_t)B);
+    red[0][tid] = s;
+    fit_tree_sums(red, tid);
+    if (tid == 0) loss[j] = red[0][0] / (double)((W == 4 ? 4 : 2) * (int64_t)B);
 }
 
 // PPO's clipped surrogate of a fixed-sigma Gaussian policy in the place of k_fit_loss<4> (clothhip.h: PPO ON THE DEVICE has the
@@ -228,21 +237,25 @@ template <int W> __global__ __launch_bounds__(256) void k_fit_loss(const float *
 // 16-byte aligned, so their four floats move under a 4-byte alignment promise and the compiler picks the widest legal access. Three
 // sums (surrogate, rows not active, kl) in the house order: per thread over its rows ascending, then a halving tree each in LDS.
 // stats[j] = {-sum surrogate / B, not active / B, sum kl / B}; ratio (may be NULL) [n_m][B] gets (float)rho. Ordinary stores only.
+// Member j's workgroup takes ITS constants from row j of q: the shared network is a table of one row, rows of a population
+// (clothhip_policy_fit_ppo*_members) have a row each. The row index is the block's, uniform over the workgroup, so the four doubles are
+// scalar loads.
 struct FitPpoArgs {
     const float *y, *lab, *old, *wgt;
     const int32_t *rows;
     float *dz, *ratio;
     double *stats;
-    double inv_s2, half_inv_s2, lo, hi;     // 1 / sigma^2, 0.5 / sigma^2, 1 - eps, 1 + eps: formed once in double on the host
+    const double *q;                        // [n_m][4] {1 / sigma^2, 0.5 / sigma^2, 1 - eps, 1 + eps}: formed once in double on the host
     int64_t y_step, dz_step, rows_step;
     int32_t B;
 };
 constexpr int FIT_PPO_STATS = 3;            // = CLOTHHIP_PPO_STATS
 
-// Member blockIdx.x's rows under the four constants given: the body of both kernels below, which differ only in where the constants come from
-__device__ __forceinline__ void fit_loss_ppo_member(const FitPpoArgs &a, const double inv_s2, const double half_inv_s2, const double lo, const double hi) {
+__global__ __launch_bounds__(256) void k_fit_loss_ppo(FitPpoArgs a) {
     __shared__ double red[FIT_PPO_STATS][256];
     const int64_t j = blockIdx.x;
+    const double *c = a.q + j * 4;
+    const double inv_s2 = c[0], half_inv_s2 = c[1], lo = c[2], hi = c[3];
     const float *y = a.y + j * a.y_step;
     float *dz = a.dz + j * a.dz_step;
     const int32_t *rows = a.rows + j * a.rows_step;
@@ -287,28 +300,11 @@ __device__ __forceinline__ void fit_loss_ppo_member(const FitPpoArgs &a, const d
         s_kl = s_kl + kl * half_inv_s2;
     }
     red[0][tid] = s_sur; red[1][tid] = s_clip; red[2][tid] = s_kl;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) {
-#pragma unroll
-            for (int i = 0; i < FIT_PPO_STATS; i++) red[i][tid] = red[i][tid] + red[i][tid + o];
-        }
-        __syncthreads();
-    }
+    fit_tree_sums(red, tid);
     if (tid == 0) {
         double *st = a.stats + j * FIT_PPO_STATS;
         st[0] = -red[0][0] / Bd; st[1] = red[1][0] / Bd; st[2] = red[2][0] / Bd;
     }
-}
-
-__global__ __launch_bounds__(256) void k_fit_loss_ppo(FitPpoArgs a) { fit_loss_ppo_member(a, a.inv_s2, a.half_inv_s2, a.lo, a.hi); }
-
-// ... with PER-MEMBER constants (clothhip_policy_fit_ppo*_members): member j's workgroup takes row j of q [n_m][4] = {inv_s2, half_inv_s2,
-// lo, hi}, formed on the host as above, and never a's four. The row index is the block's, uniform over the workgroup, so the four
-// doubles are scalar loads; every operation on a row of the minibatch is the one above.
-__global__ __launch_bounds__(256) void k_fit_loss_ppo_members(FitPpoArgs a, const double *q) {
-    const double *c = q + (int64_t)blockIdx.x * 4;
-    fit_loss_ppo_member(a, c[0], c[1], c[2], c[3]);
 }
 
 // PPO's clipped surrogate of a Gaussian policy whose log sigma is LEARNED (clothhip.h: PPO WITH A LEARNED SIGMA has the arithmetic
@@ -404,14 +400,7 @@ __global__ __launch_bounds__(256) void k_fit_loss_ppo_sigma(FitPpoSigmaArgs a) {
     red[0][tid] = s_sur; red[1][tid] = s_clip; red[2][tid] = s_kl;
 #pragma unroll
     for (int k = 0; k < 4; k++) red[3 + k][tid] = s_h[k];
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) {
-#pragma unroll
-            for (int i = 0; i < FIT_PPO_SIGMA_SUMS; i++) red[i][tid] = red[i][tid] + red[i][tid + o];
-        }
-        __syncthreads();
-    }
+    fit_tree_sums(red, tid);
     if (tid == 0) {
         double hs = 0.0;
 #pragma unroll

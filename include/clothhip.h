@@ -787,7 +787,7 @@ int clothhip_policy_fit_ppo_sigma(clothhip_handle *h, const ClothFitParams *p, c
  * all entries -1 returns 0.
  * THE LOSS is PPO ON THE DEVICE's, operation by operation, with member j's own q[j] = {sigma, clip}: the host forms inv_s2,
  * half_inv_s2, lo, hi of every member in double by the expressions above, and they go up as one table [n_m][4] of which member j's
- * workgroup reads row j. clothhip_policy_fit_ppo_grad_members is clothhip_policy_fit_grad_members for it: grad_out[n_m][n_params],
+ * workgroup reads row j (the shared network's entries send a table of one row to the same kernel). clothhip_policy_fit_ppo_grad_members is clothhip_policy_fit_grad_members for it: grad_out[n_m][n_params],
  * stats_out[n_m][3], ratio_out[n_m][B], each may be NULL; nothing is updated. clothhip_policy_fit_ppo_members is
  * clothhip_policy_fit_members for it: idx[n_steps][n_m][B], stats_out[n_steps][n_m][3] (may be NULL) each member's statistics BEFORE
  * each step. They use the population's per-row optimizer state: a squared-error group step and a PPO group step of one row share its
@@ -1073,7 +1073,8 @@ int clothhip_selftest_rng(uint32_t *state, int32_t kind, int32_t n, double a, do
  * (out[2] is then what that band would need) and clothhip_render_obs returns CLOTHHIP_EINVAL for that size. */
 int clothhip_selftest_depth8(const float *depth, int32_t n_images, int64_t npx, uint8_t *out);
 int clothhip_selftest_render_plan(const ClothParams *params, int32_t width, int32_t height, int32_t out[4]);
-/* Host-side self-test of PPO's exponential (PPO ON THE DEVICE above): out[i] = exp_fixed(x[i]), the inline function k_fit_loss_ppo runs
+/* Host-side self-test of PPO's exponential (PPO ON THE DEVICE above): out[i] = exp_fixed(x[i]), the inline function the two surrogate kernels run,
+ * k_fit_loss_ppo (the ONE fixed-sigma kernel, of the shared network and of population rows) and k_fit_loss_ppo_sigma
  * (csrc/cloth_exp_fixed.hpp), computed on the host; no device needed. CLOTHHIP_EINVAL for n < 0, a NULL table with n > 0 or a NaN. */
 int clothhip_selftest_exp_fixed(const double *x, int64_t n, double *out);
 /* Host-side self-test of the exploration noise's variate (EXPLORATION NOISE ON THE DEVICE above): out[i][0..3] = normal_fixed(seed, env[i],

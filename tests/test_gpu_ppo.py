@@ -1,4 +1,4 @@
-"""GPU tests of PPO on the device: the clipped surrogate (k_fit_loss_ppo) on exactly representable data, by bytes against
+"""GPU tests of PPO on the device: the clipped surrogate (k_fit_loss_ppo, here as the call with a one-row table of constants) on exactly representable data, by bytes against
 the numpy restatement of its arithmetic, and within an a-priori bound of the float64 reference on Gaussian data; the old-mean column and
 its snapshot on the device; the step, its determinism and what it leaves alone; a fit that freezes where the weighted regression runs
 away; every refusal; demos.ppo_fit. Every comparison is array_equal or by bytes unless it says otherwise. Shapes and helpers are those

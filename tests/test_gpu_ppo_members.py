@@ -1,5 +1,6 @@
 """GPU tests of PPO for a population (clothhip_fit_data_snapshot_policy_members, clothhip_policy_fit_ppo_grad_members,
-clothhip_policy_fit_ppo_members; k_fit_scatter_y, k_fit_loss_ppo_members). Every comparison is array_equal or by bytes, and the twin is
+clothhip_policy_fit_ppo_members; k_fit_scatter_y, and k_fit_loss_ppo reading member j's constants from row j of the call's table, the
+kernel of the shared-network entries too, which send one row). Every comparison is array_equal or by bytes, and the twin is
 always a SECOND handle that carries the member as its shared network, stores the same dataset, weights and old means and is driven by
 the shared-network entries (fit_ppo_grad, fit_ppo, fit), which tests/test_gpu_ppo.py pins to the numpy restatement of the arithmetic.
 Shapes and helpers are those of tests/test_gpu_ppo.py and tests/test_gpu_fit_members.py."""
@@ -422,6 +423,59 @@ def test_fit_members_keeps_its_bytes_beside_the_new_entries(handle):
     for g in range(G):
         assert _same(_row(new, g, n, pad=True), _row(twin, g, n, pad=True))
     assert new.fit_get_old_means().tobytes() != twin.fit_get_old_means().tobytes()
+
+
+def test_a_shared_call_after_a_grouped_call_reads_its_own_row_of_constants():
+    """ONE handle, the file's 40 rows, Adam. The shared network's constants are row 0 of the table every fixed-sigma call uploads, and a
+    grouped call leaves that table longer and different: a shared network at sigma 0.5, gradient and 2 steps at B = 5; a population of
+    3, a snapshot by member and 2 steps of members [2, 0] under sigma (0.7, 0.3), clip (0.1, 0.3); a new shared network, a snapshot, the
+    gradient and 3 steps at sigma 1.0, B = 300 (two 256-row ranges). Every stage's statistics, gradients, ratios and final weights are,
+    byte for byte, those of a FRESH handle given that stage's calls alone (test_gpu_fit_members.py has the squared-error walk)."""
+    widths = [300, 5, 4]
+    n = _n_params(widths)
+    nets, rows, act, old, adv = _case(widths)
+    first, last = nets[0], _random_layers(widths, 51)
+    r = np.random.RandomState(17)
+    i1, t1, t2, i3, t3 = (r.randint(0, N_ROWS, size=s).astype(np.int32) for s in [(5,), (2, 5), (2, 2, 5), (300,), (3, 300)])
+    adam = dict(OPTIMIZERS["adam"], lr=1e-2)
+
+    def shared(layers, idx, table, sigma, snapshot):
+        def stage(x):
+            x.set_policy_mlp(layers)
+            if snapshot:
+                x.fit_snapshot_policy()
+            grad = x.fit_ppo_grad(idx, sigma, 0.2)                         # (statistics, gradient, ratios)
+            return [x.fit_ppo(table, sigma, 0.2, **adam)] + list(grad), [x.get_policy_mlp(0, n)]
+        return stage
+
+    def population(x):
+        x.set_policy_population(nets, np.zeros(x.E, dtype=np.int32))
+        x.fit_snapshot_policy_members(np.arange(N_ROWS, dtype=np.int32) % G)
+        got = [x.fit_ppo_members([2, 0], t2, [0.7, 0.3], [0.1, 0.3], adam), x.fit_get_old_means()]
+        return got, [_row(x, g, n, pad=True) for g in range(G)]
+
+    def dataset(x):
+        x.fit_append(rows, act.astype(np.float64), weights=adv)
+        x.fit_set_old_means(old)
+        return x
+
+    b = dataset(_new_batch(10))
+    stages = [("shared, sigma 0.5, B = 5", shared(first, i1, t1, 0.5, False)), ("population", population), ("shared, sigma 1.0, B = 300", shared(last, i3, t3, 1.0, True))]
+    for name, stage in stages:
+        got, got_w = stage(b)
+        fresh = dataset(_new_batch(10))
+        want, want_w = stage(fresh)
+        fresh.close()
+        print("%s: the steps' statistics %r, fresh handle %r" % (name, got[0].tolist(), want[0].tolist()))
+        assert len(got) == len(want) and len(got_w) == len(want_w)
+        assert all(np.isfinite(w).all() for w in want) and all(np.isfinite(w).all() for w in want_w)
+        assert all(_same(g, w) for g, w in zip(got, want)), name
+        assert all(_same(g, w) for g, w in zip(got_w, want_w)), name
+        assert (want[0][1:, ..., 2] > 0).all()                              # the steps moved off the old means
+        if name != "population":
+            assert np.abs(want[2]).max() > 0 and want[3].shape == (len(want[3]),) and want[3].dtype == np.float32
+    assert not _same(got_w[0], _flat(last))                                  # (the last stage did train)
+    b.close()
 
 
 # ---- 6. every refusal -----------------------------------------------------------------------------------------------------------------------

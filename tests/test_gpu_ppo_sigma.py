@@ -1,4 +1,4 @@
-"""GPU tests of PPO with a learned sigma: k_fit_loss_ppo_sigma at a zero head against the fixed-sigma kernel by bytes on
+"""GPU tests of PPO with a learned sigma: k_fit_loss_ppo_sigma at a zero head against the fixed-sigma kernel (k_fit_loss_ppo under a one-row table) by bytes on
 exactly representable data, by bytes against the numpy restatement of its arithmetic, and within an a-priori bound of the float64
 reference on Gaussian data; the old-log-sigma column and its snapshot on the device; the head's optimizer beside the blob's; a fit that
 the growing head freezes; what the new entries leave alone, every refusal, demos.ppo_fit(sigma=None). Every comparison is array_equal or

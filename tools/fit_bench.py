@@ -19,7 +19,7 @@ members = {0}, n_m = 1.
     python3 tools/fit_bench.py --members [--steps 20] [--rounds 5] [--out FILE]
 --ppo runs the PPO section instead (clothhip_policy_fit_ppo; profiles/ppo.txt): on the four shapes above, an Adam step
 of the clipped surrogate beside the squared-error step timed in the same process on the same handle and rows. The two differ in ONE
-launch per step: k_fit_loss_ppo in the place of k_fit_loss.
+launch per step: k_fit_loss_ppo in the place of k_fit_loss, reading its constants from a table of one row (profiles/fit_loss_modes.txt).
     python3 tools/fit_bench.py --ppo [--steps 20] [--rounds 5] [--out FILE]
 --ppo-sigma runs the learned-sigma section instead (clothhip_policy_fit_ppo_sigma; profiles/ppo_sigma.txt): on the four
 shapes, an Adam step with the log-sigma head beside the fixed-sigma PPO step, alternated on one handle. The two differ in the loss launch
@@ -28,7 +28,8 @@ shapes, an Adam step with the log-sigma head beside the fixed-sigma PPO step, al
 --ppo-members runs the grouped PPO section instead (clothhip_policy_fit_ppo_members; profiles/ppo_members.txt): a grouped
 PPO Adam step of G = 1, 4, 16, 64 networks at B = 256, every member under its own sigma and clip, beside the grouped squared-error step
 (--members' call) alternated on the same handle, and beside G single-network PPO steps timed in the same process. The grouped steps
-differ in ONE launch: k_fit_loss_ppo_members in the place of k_fit_loss, one workgroup per member either way.
+differ in ONE launch: k_fit_loss_ppo (the single-network step's kernel, member j under row j of the table) in the place of k_fit_loss, one
+workgroup per member either way.
     python3 tools/fit_bench.py --ppo-members [--steps 20] [--rounds 5] [--out FILE]"""
 import argparse
 import os
