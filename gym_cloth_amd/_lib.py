@@ -152,6 +152,15 @@ PPO_SIGMA_STATS = 4                 # CLOTHHIP_PPO_SIGMA_STATS: loss, clip_fract
 assert C.sizeof(ClothPpoSigmaParams) == 16
 
 
+class ClothDdpgParams(C.Structure):
+    """The DDPG entries' constants: the discount, the soft-update rate of the targets, the action bound of the clamp (inf: none), flags (0)."""
+    _fields_ = [("gamma", C.c_double), ("tau", C.c_double), ("act_bound", C.c_float), ("flags", C.c_int32)]
+
+
+Q_STATS, DPG_STATS, DDPG_STATS = 3, 3, 6      # CLOTHHIP_*_STATS: loss, mean q, mean y; -mean q, gated fraction, mean |dL/da|; both
+assert C.sizeof(ClothDdpgParams) == 24
+
+
 class ClothPlanParams(C.Structure):
     """clothhip_plan_cem's planner constants (clothhip.h: PLAN ACTIONS ON THE DEVICE)."""
     _fields_ = [("horizon", C.c_int32), ("n_candidates", C.c_int32), ("n_elite", C.c_int32), ("n_iters", C.c_int32),
@@ -261,6 +270,19 @@ SYMBOLS = [
                                                   _dp]),
     ("clothhip_policy_noise_fill", C.c_int, [_vp, C.c_uint64, C.c_int32, C.POINTER(C.c_int64), _dp, C.c_int32, C.POINTER(_vp)]),
     ("clothhip_policy_noise_get", C.c_int, [_vp, C.c_int32, _dp]),
+    ("clothhip_set_q_mlp", C.c_int, [_vp, C.c_int32, _i32p, C.POINTER(C.c_float), C.c_size_t]),
+    ("clothhip_get_q_mlp", C.c_int, [_vp, C.POINTER(C.c_float), C.c_size_t]),
+    ("clothhip_ddpg_sync_targets", C.c_int, [_vp]),
+    ("clothhip_ddpg_get_targets", C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    ("clothhip_ddpg_set_targets", C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    ("clothhip_q_fit_grad", C.c_int, [_vp, C.POINTER(ClothDdpgParams), _i32p, C.c_int32, C.POINTER(C.c_float), _dp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    ("clothhip_q_fit", C.c_int, [_vp, C.POINTER(ClothFitParams), C.POINTER(ClothDdpgParams), _i32p, C.c_int32, C.c_int32, _dp]),
+    ("clothhip_q_fit_reset", C.c_int, [_vp]),
+    ("clothhip_policy_fit_dpg_grad", C.c_int, [_vp, C.POINTER(ClothDdpgParams), _i32p, C.c_int32, C.POINTER(C.c_float), _dp, C.POINTER(C.c_float)]),
+    ("clothhip_policy_fit_dpg", C.c_int, [_vp, C.POINTER(ClothFitParams), C.POINTER(ClothDdpgParams), _i32p, C.c_int32, C.c_int32, _dp]),
+    ("clothhip_ddpg_polyak", C.c_int, [_vp, C.c_double]),
+    ("clothhip_ddpg_last_tables", C.c_int, [_vp, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    ("clothhip_ddpg_fit", C.c_int, [_vp, C.POINTER(ClothFitParams), C.POINTER(ClothFitParams), C.POINTER(ClothDdpgParams), _i32p, C.c_int32, C.c_int32, _dp]),
     ("clothhip_plan_cem", C.c_int, [_vp, _vp, C.POINTER(ClothEpisodeParams), C.POINTER(ClothPlanParams), _i32p, _u8p, _dp, _dp, _dp, _dp,
                                     _dp, _dp]),
     ("clothhip_plan_sample", C.c_int, [_vp, C.POINTER(ClothPlanParams), _dp, _dp, C.c_int32, C.c_int32, _dp, _dp, _dp]),

@@ -573,3 +573,143 @@ class FitBindings(object):
         heads = np.zeros((ix.shape[0], 4), dtype=np.float32)
         check(self._L.clothhip_policy_fit_ppo_sigma(self._h, p, C.byref(q), _lib.i32p(ix), ix.shape[0], ix.shape[1], _lib.dp(stats), _lib.fp(heads)))
         return stats, heads
+
+    # ---- DDPG: a Q critic, target networks, the deterministic policy gradient (clothhip.h: DDPG ON THE DEVICE) ------------------------
+    def set_q_mlp(self, layers):
+        """The handle's Q network (clothhip_set_q_mlp): `layers` as set_value_mlp takes them, with an input width of 3P + 4 -- a row is the
+        '1d' observation followed by the four action components -- and a last `out` of 1; None or [] drops it. It lives beside the
+        policy, the value network and the head, independent of them; a new one drops the target Q and restarts its optimizer."""
+        self._q_n_params = 0
+        if not layers:
+            check(self._L.clothhip_set_q_mlp(self._h, 0, None, None, 0))
+            return
+        widths, blob = pack_mlp(layers, n_out=1)
+        check(self._L.clothhip_set_q_mlp(self._h, len(widths) - 1, _lib.i32p(widths), _lib.fp(blob), blob.size))
+        self._q_n_params = int(blob.size)
+
+    def _q_params(self):
+        n = getattr(self, '_q_n_params', 0)
+        if not n:
+            raise _lib.ClothHipError("no Q network on this batch: call set_q_mlp first")
+        return n
+
+    def get_q_mlp(self):
+        """The Q network's blob as the device holds it, float32[n_params] (clothhip_get_q_mlp)."""
+        out = np.zeros(self._q_params(), dtype=np.float32)
+        check(self._L.clothhip_get_q_mlp(self._h, _lib.fp(out), out.size))
+        return out
+
+    def q_fit_reset(self):
+        """Zero the Q network's moments and its step count (clothhip_q_fit_reset)."""
+        check(self._L.clothhip_q_fit_reset(self._h))
+
+    def ddpg_sync_targets(self):
+        """Copy the present shared policy network and Q network into the target copies, on the device (clothhip_ddpg_sync_targets)."""
+        check(self._L.clothhip_ddpg_sync_targets(self._h))
+
+    def ddpg_targets(self):
+        """(policy float32[n_params], q float32[n_params]): the two target blobs by download (clothhip_ddpg_get_targets)."""
+        pol, q = np.zeros(self._fit_n_params(), dtype=np.float32), np.zeros(self._q_params(), dtype=np.float32)
+        check(self._L.clothhip_ddpg_get_targets(self._h, _lib.fp(pol), _lib.fp(q)))
+        return pol, q
+
+    def ddpg_set_targets(self, policy_layers=None, q_layers=None):
+        """Upload target copies from the host, as a checkpoint restores them (clothhip_ddpg_set_targets): each a list of (W, b) of the
+        shape of the network it shadows, None: that target stays as it is."""
+        pol = q = None
+        if policy_layers is not None:
+            pol = pack_mlp(policy_layers, n_in=3 * self.P)[1]
+            if pol.size != self._fit_n_params():
+                raise ValueError("the target policy has %d parameters, the policy network %d" % (pol.size, self._fit_n_params()))
+        if q_layers is not None:
+            q = pack_mlp(q_layers, n_in=3 * self.P + 4, n_out=1)[1]
+            if q.size != self._q_params():
+                raise ValueError("the target Q network has %d parameters, the Q network %d" % (q.size, self._q_params()))
+        check(self._L.clothhip_ddpg_set_targets(self._h, _lib.fp(pol), _lib.fp(q)))
+
+    @staticmethod
+    def _ddpg_params(gamma, tau, act_bound):
+        g, t, b = float(gamma), float(tau), float(np.float32(act_bound))
+        if not (np.isfinite(g) and np.isfinite(t) and 0.0 <= g <= 1.0 and 0.0 <= t <= 1.0):
+            raise ValueError("gamma and tau lie in [0, 1] (got %r, %r)" % (gamma, tau))
+        if not b > 0.0:
+            raise ValueError("act_bound = %r: the action bound is > 0 (inf: no clamp)" % (act_bound,))
+        return _lib.ClothDdpgParams(g, t, b, 0)
+
+    def q_grad(self, idx, gamma, act_bound=1.0):
+        """(stats float64[3] = loss, mean q, mean y; grad float32[n_params] of the Q network in the blob's layout; y float32[B], the TD
+        targets; q float32[B], the critic on [s, clamp(label)]) over the dataset rows idx [B] at the present weights and targets;
+        nothing is updated (clothhip_q_fit_grad). y = rew + gamma Q'(s', clamp(mu'(s'))) through a row's successor, 0 behind a
+        terminal row; no row may be a leaf. references.q_fit_reference is the float64 yardstick, td_loss_reference the kernel's arithmetic."""
+        ix = self._fit_idx(idx, 1)
+        p = self._ddpg_params(gamma, 0.0, act_bound)
+        grad = np.zeros(self._q_params(), dtype=np.float32)
+        stats = np.zeros(_lib.Q_STATS, dtype=np.float64)
+        y, q = np.zeros(ix.size, dtype=np.float32), np.zeros(ix.size, dtype=np.float32)
+        check(self._L.clothhip_q_fit_grad(self._h, C.byref(p), _lib.i32p(ix), ix.size, _lib.fp(grad), _lib.dp(stats), _lib.fp(y), _lib.fp(q)))
+        return stats, grad, y, q
+
+    def q_fit(self, idx_table, gamma, act_bound=1.0, optimizer='adam', lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, momentum=0.0):
+        """n_steps optimizer steps of the Q network on the TD loss, in place (clothhip_q_fit): step s on the dataset rows idx_table[s]
+        (int [n_steps, B]), with the Q network's own moments and step count. No target moves. Returns float64[n_steps, 3]: each step's
+        (loss, mean q, mean y) BEFORE its update."""
+        ix = self._fit_idx(idx_table, 2)
+        p = self._fit_params(dict(optimizer=optimizer, lr=lr, beta1=beta1, beta2=beta2, eps=eps, momentum=momentum), 1)
+        q = self._ddpg_params(gamma, 0.0, act_bound)
+        self._q_params()
+        stats = np.zeros((ix.shape[0], _lib.Q_STATS), dtype=np.float64)
+        check(self._L.clothhip_q_fit(self._h, p, C.byref(q), _lib.i32p(ix), ix.shape[0], ix.shape[1], _lib.dp(stats)))
+        return stats
+
+    def dpg_grad(self, idx, act_bound=1.0):
+        """(stats float64[3] = loss -mean Q, gated fraction, mean |dL/da|; grad float32[n_params] of the POLICY in the blob's layout; da
+        float32[B, 4] = dL/da, the critic's input gradient at the action columns) of the deterministic policy gradient over the dataset
+        rows idx [B]; nothing is updated (clothhip_policy_fit_dpg_grad). references.dpg_reference is the float64 yardstick."""
+        ix = self._fit_idx(idx, 1)
+        p = self._ddpg_params(0.0, 0.0, act_bound)
+        self._q_params()
+        grad = np.zeros(self._fit_n_params(), dtype=np.float32)
+        stats = np.zeros(_lib.DPG_STATS, dtype=np.float64)
+        da = np.zeros((ix.size, 4), dtype=np.float32)
+        check(self._L.clothhip_policy_fit_dpg_grad(self._h, C.byref(p), _lib.i32p(ix), ix.size, _lib.fp(grad), _lib.dp(stats), _lib.fp(da)))
+        return stats, grad, da
+
+    def dpg_fit(self, idx_table, act_bound=1.0, optimizer='adam', lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, momentum=0.0):
+        """n_steps optimizer steps of the shared policy network on -mean Q(s, clamp(mu(s))), the critic held fixed
+        (clothhip_policy_fit_dpg): the policy's optimizer state, shared with fit and fit_ppo. Returns float64[n_steps, 3]."""
+        ix = self._fit_idx(idx_table, 2)
+        p = self._fit_params(dict(optimizer=optimizer, lr=lr, beta1=beta1, beta2=beta2, eps=eps, momentum=momentum), 1)
+        q = self._ddpg_params(0.0, 0.0, act_bound)
+        self._q_params()
+        self._fit_n_params()
+        stats = np.zeros((ix.shape[0], _lib.DPG_STATS), dtype=np.float64)
+        check(self._L.clothhip_policy_fit_dpg(self._h, p, C.byref(q), _lib.i32p(ix), ix.shape[0], ix.shape[1], _lib.dp(stats)))
+        return stats
+
+    def ddpg_polyak(self, tau):
+        """The soft update of both targets: target = (1 - tau) target + tau network, in float32 on the device (clothhip_ddpg_polyak)."""
+        self._ddpg_params(0.0, tau, 1.0)
+        check(self._L.clothhip_ddpg_polyak(self._h, float(tau)))
+
+    def ddpg_last_tables(self, B, want_qn=True):
+        """(x float32[B, 3P + 4], qn float32[B] or None, q float32[B]): what the last DDPG call of minibatches of B rows left in the Q
+        passes' scratch (clothhip_ddpg_last_tables) -- the critic's input rows of its last concat, the target critic's values (a
+        critic's call only: want_qn), the critic's output of its last forward. For tests of the elementwise kernels."""
+        x = np.zeros((int(B), 3 * self.P + 4), dtype=np.float32)
+        qn, q = (np.zeros(int(B), dtype=np.float32) if want_qn else None), np.zeros(int(B), dtype=np.float32)
+        check(self._L.clothhip_ddpg_last_tables(self._h, int(B), _lib.fp(x), _lib.fp(qn), _lib.fp(q)))
+        return x, qn, q
+
+    def ddpg_fit(self, idx_table, gamma, tau, act_bound=1.0, policy_hyper=None, q_hyper=None):
+        """n_steps DDPG steps in one call (clothhip_ddpg_fit): per step the critic's step on idx_table[s] (int [n_steps, B]), the actor's
+        step against the updated critic, the soft update of both targets by tau. policy_hyper and q_hyper are dicts with fit's
+        keywords (optimizer, lr, beta1, beta2, eps, momentum). By bytes what q_fit, dpg_fit and ddpg_polyak give one call at a time.
+        Returns float64[n_steps, 6]: the critic's (loss, mean q, mean y), then the actor's (loss, gated fraction, mean |dL/da|)."""
+        ix = self._fit_idx(idx_table, 2)
+        pp, pq = self._fit_params(policy_hyper, 1), self._fit_params(q_hyper, 1)
+        q = self._ddpg_params(gamma, tau, act_bound)
+        self._q_params()
+        self._fit_n_params()
+        stats = np.zeros((ix.shape[0], _lib.DDPG_STATS), dtype=np.float64)
+        check(self._L.clothhip_ddpg_fit(self._h, pp, pq, C.byref(q), _lib.i32p(ix), ix.shape[0], ix.shape[1], _lib.dp(stats)))
+        return stats

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "api_handle.hpp"
+#include "cloth_fit_ddpg.hpp"
 #include "cloth_fit_gae.hpp"
 #include "cloth_policy_fit.hpp"
 #include "cloth_policy_mlp.hpp"
@@ -145,6 +146,12 @@ static int fit_reserve(clothhip_handle *h, const FitPlan &p, int32_t n_m) {
     return f.d_grad.reserve((size_t)n_m * p.grad * 4);
 }
 
+// The tables a pass of one network works on: its activations, the two dZ tables, the slabs of a split batch sum, the gradient (each
+// NULL where the pass does not touch it), and its layer-0 input -- x NULL: the dataset's observation rows through the call's index
+// table, else dense rows [B][widths[0]] (the critic's [s, a] rows of DDPG). The trainer's own scratch is policy_work(h), valid after fit_reserve.
+struct FitWork { float *act, *dz, *part, *grad; const float *x; };
+static FitWork policy_work(clothhip_handle *h) { return {h->fit.d_act, h->fit.d_dz, h->fit.d_part, h->fit.d_grad, nullptr}; }
+
 template <bool A_KC, bool B_KC, int EPI, bool ROWS> static void launch_gemm(hipStream_t s, FitGemmArgs &a, int32_t n_m) {
     a.tiles_n = (a.N + FIT_TILE - 1) / FIT_TILE;
     const dim3 grid((unsigned)a.tiles_n * (unsigned)n_m, (unsigned)((a.M + FIT_TILE - 1) / FIT_TILE), (unsigned)((a.K + a.k_chunk - 1) / a.k_chunk));
@@ -172,21 +179,23 @@ struct FitOut { double *loss; float *grad, *ratio, *grad_ls, *ls; };
 // The launches of one network's step, each over all n_m members: forward, loss, backward. The forward of the present weights over rows
 // d_idx [n_m][B]: member j's y is then at h->fit.d_act + j * p.act + p.h_off[L - 1].
 // shared_rows: d_idx is ONE list [B] that every member reads
-static int enqueue_forward(clothhip_handle *h, const FitNet &net, const FitPlan &p, int32_t n_m, const int32_t *d_idx, int32_t B, bool shared_rows) {
+static int enqueue_forward(clothhip_handle *h, const FitNet &net, const FitPlan &p, int32_t n_m, const int32_t *d_idx, int32_t B, bool shared_rows,
+                           const FitWork &w) {
     const MlpDesc &D = net.D;
     const int L = D.n_layers;
-    float *act = h->fit.d_act;
+    float *act = w.act;
     FitGemmArgs m0 = {};
     m0.members = h->fit.d_members; m0.stride = D.stride; m0.rows_step = shared_rows ? 0 : B;
     for (int l = 0; l < L; l++) {
         const int n_in = D.widths[l], n_out = D.widths[l + 1];
         FitGemmArgs a = m0;
-        a.A = l ? act + p.h_off[l - 1] : (const float *)h->dataset.obs(); a.lda = n_in; a.rows = l ? nullptr : d_idx; a.a_step = l ? (int64_t)p.act : 0;
+        const bool gather = l == 0 && !w.x;      // layer 0 reads the dataset through the index table, unless the pass has its own input rows
+        a.A = l ? act + p.h_off[l - 1] : gather ? (const float *)h->dataset.obs() : w.x; a.lda = n_in; a.rows = gather ? d_idx : nullptr; a.a_step = l ? (int64_t)p.act : 0;
         a.B = D.params + p.w_off[l]; a.ldb = n_in; a.bias = a.B + (size_t)n_out * n_in; a.b_weights = 1;
         a.C = act + p.h_off[l]; a.ldc = n_out; a.c_step = (int64_t)p.act;
         a.M = B; a.N = n_out; a.K = n_in; a.k_chunk = n_in;
-        if (l == 0 && l + 1 < L) launch_gemm<true, true, FIT_EPI_BIAS_RELU, true>(h->stream, a, n_m);
-        else if (l == 0) launch_gemm<true, true, FIT_EPI_BIAS, true>(h->stream, a, n_m);
+        if (gather && l + 1 < L) launch_gemm<true, true, FIT_EPI_BIAS_RELU, true>(h->stream, a, n_m);
+        else if (gather) launch_gemm<true, true, FIT_EPI_BIAS, true>(h->stream, a, n_m);
         else if (l + 1 < L) launch_gemm<true, true, FIT_EPI_BIAS_RELU, false>(h->stream, a, n_m);
         else launch_gemm<true, true, FIT_EPI_BIAS, false>(h->stream, a, n_m);
         HIPCHECK(hipGetLastError());
@@ -224,10 +233,10 @@ static int enqueue_loss(clothhip_handle *h, const FitNet &net, const FitPlan &p,
     return 0;
 }
 // The backward from the loss launch's dZ: the gradient of every member into h->fit.d_grad [n_m][n_params] (blob layout)
-static int enqueue_backward(clothhip_handle *h, const FitNet &net, const FitPlan &p, int32_t n_m, const int32_t *d_idx, int32_t B) {
+static int enqueue_backward(clothhip_handle *h, const FitNet &net, const FitPlan &p, int32_t n_m, const int32_t *d_idx, int32_t B, const FitWork &w) {
     const MlpDesc &D = net.D;
     auto &f = h->fit;
-    float *act = f.d_act, *grad = f.d_grad, *dz[2] = {f.d_dz, f.d_dz + (size_t)B * p.maxw};
+    float *act = w.act, *grad = w.grad, *dz[2] = {w.dz, w.dz + (size_t)B * p.maxw};
     FitGemmArgs m0 = {};
     m0.members = f.d_members; m0.stride = D.stride; m0.rows_step = B;
     for (int l = D.n_layers - 1; l >= 0; l--) {
@@ -236,16 +245,17 @@ static int enqueue_backward(clothhip_handle *h, const FitNet &net, const FitPlan
         float *gWl = grad + p.w_off[l];
         FitGemmArgs a = m0;
         a.A = dzl; a.lda = n_out; a.a_step = (int64_t)p.dz;
-        a.B = l ? act + p.h_off[l - 1] : (const float *)h->dataset.obs(); a.ldb = n_in; a.rows = l ? nullptr : d_idx; a.b_step = l ? (int64_t)p.act : 0;
-        a.C = p.n_split > 1 ? (float *)f.d_part : gWl; a.ldc = n_in; a.c_slab = (int64_t)n_out * n_in; a.c_step = (int64_t)(p.n_split > 1 ? p.part : p.grad);
+        const bool gather = l == 0 && !w.x;
+        a.B = l ? act + p.h_off[l - 1] : gather ? (const float *)h->dataset.obs() : w.x; a.ldb = n_in; a.rows = gather ? d_idx : nullptr; a.b_step = l ? (int64_t)p.act : 0;
+        a.C = p.n_split > 1 ? w.part : gWl; a.ldc = n_in; a.c_slab = (int64_t)n_out * n_in; a.c_step = (int64_t)(p.n_split > 1 ? p.part : p.grad);
         a.M = n_out; a.N = n_in; a.K = B; a.k_chunk = FIT_SPLIT_ROWS;
-        if (l == 0) launch_gemm<false, false, FIT_EPI_NONE, true>(h->stream, a, n_m);
+        if (gather) launch_gemm<false, false, FIT_EPI_NONE, true>(h->stream, a, n_m);
         else launch_gemm<false, false, FIT_EPI_NONE, false>(h->stream, a, n_m);
         HIPCHECK(hipGetLastError());
         if (p.n_split > 1) {
             const int64_t n = (int64_t)n_out * n_in;
             const int32_t blocks = (int32_t)((n + 255) / 256);
-            hipLaunchKernelGGL(k_fit_reduce, dim3((unsigned)blocks * (unsigned)n_m), dim3(256), 0, h->stream, (const float *)f.d_part, n, p.n_split, gWl, n,
+            hipLaunchKernelGGL(k_fit_reduce, dim3((unsigned)blocks * (unsigned)n_m), dim3(256), 0, h->stream, (const float *)w.part, n, p.n_split, gWl, n,
                                (int64_t)p.part, (int64_t)p.grad, blocks);
             HIPCHECK(hipGetLastError());
         }
@@ -269,9 +279,9 @@ static int enqueue_backward(clothhip_handle *h, const FitNet &net, const FitPlan
 // ... and all three: loss and gradient of the present weights over rows d_idx [n_m][B], every member on its own rows
 static int enqueue_grad(clothhip_handle *h, const FitNet &net, const FitPlan &p, const FitLoss &loss, int32_t n_m, const int32_t *d_idx, int32_t B, double *d_stats,
                         float *d_ratio, float *d_ls) {
-    if (int rc = enqueue_forward(h, net, p, n_m, d_idx, B, false)) return rc;
+    if (int rc = enqueue_forward(h, net, p, n_m, d_idx, B, false, policy_work(h))) return rc;
     if (int rc = enqueue_loss(h, net, p, loss, n_m, d_idx, B, d_stats, d_ratio, d_ls)) return rc;
-    return enqueue_backward(h, net, p, n_m, d_idx, B);
+    return enqueue_backward(h, net, p, n_m, d_idx, B, policy_work(h));
 }
 
 // loss and gradient of `members` over idx [n_m][B], nothing updated; the call is valid
@@ -346,7 +356,7 @@ extern "C" int clothhip_policy_fit_loss(clothhip_handle *h, const int32_t *idx, 
         const int32_t B = (int32_t)std::min<int64_t>(FIT_MAX_BATCH, n - c * FIT_MAX_BATCH);
         const FitPlan p = fit_plan(net, B);
         const int32_t *d_idx = f.d_idx + (size_t)c * FIT_MAX_BATCH;
-        if (int rc = enqueue_forward(h, net, p, 1, d_idx, B, false)) return rc;
+        if (int rc = enqueue_forward(h, net, p, 1, d_idx, B, false, policy_work(h))) return rc;
         launch_fit_sqsum(h->stream, f.d_act + p.h_off[L - 1], h->dataset.lab(), h->dataset.w(), d_idx, B, f.d_loss + c);
         HIPCHECK(hipGetLastError());
     }
@@ -380,7 +390,7 @@ static int enqueue_predict(clothhip_handle *h, const FitNet &net, const int32_t 
     for (int64_t r0 = 0; r0 < n; r0 += Bmax) {
         const int32_t B = (int32_t)std::min<int64_t>(Bmax, n - r0);
         const FitPlan p = fit_plan(net, B);
-        if (int rc = enqueue_forward(h, net, p, n_m, f.d_idx + (size_t)r0, B, true)) return rc;
+        if (int rc = enqueue_forward(h, net, p, n_m, f.d_idx + (size_t)r0, B, true, policy_work(h))) return rc;
         const int32_t blocks = (W * B + 255) / 256;
         launch_fit_copy_y(h->stream, n_m, f.d_act + p.h_off[L - 1], W * B, dst + (size_t)r0 * W, (int64_t)p.act, (int64_t)n * W, blocks);
         HIPCHECK(hipGetLastError());
@@ -425,6 +435,30 @@ static bool ensure_row_state(OptState &o, size_t rows) {
     return true;
 }
 
+// The step constants q [FIT_HYPER] of ONE optimizer step under p, the t1-th of its row (1-based): made in double, then rounded to float
+static void step_constants(float *q, const ClothFitParams &p, bool adam, int64_t t1) {
+    if (adam) {
+        const double b1 = (double)p.beta1, b2 = (double)p.beta2, td = (double)t1;
+        const double a_t = (double)p.lr * std::sqrt(1.0 - std::pow(b2, td)) / (1.0 - std::pow(b1, td));
+        q[0] = (float)a_t; q[1] = p.beta1; q[2] = (float)(1.0 - b1); q[3] = p.beta2; q[4] = (float)(1.0 - b2); q[5] = p.eps;
+    } else {
+        q[0] = p.lr; q[1] = p.momentum;
+    }
+}
+// One optimizer launch: the rows h->fit.d_members [n_m] of theta ([rows][stride], n elements each) with the moments of opt, row j's
+// gradient at grad + j * n and its constants at d_hyper + j * FIT_HYPER (device)
+static int enqueue_optimizer(clothhip_handle *h, bool adam, float *theta, OptState &opt, const float *grad, const float *d_hyper, int64_t stride, int64_t n, int32_t n_m) {
+    FitOptArgs o = {};
+    o.theta = theta; o.m = opt.m; o.v = opt.v; o.g = grad; o.members = h->fit.d_members;
+    o.hyper = d_hyper;
+    o.stride = stride; o.n = n; o.blocks = (int32_t)((n + 255) / 256);
+    const dim3 ogrid((unsigned)o.blocks * (unsigned)n_m);
+    if (adam) hipLaunchKernelGGL(k_fit_adam, ogrid, dim3(256), 0, h->stream, o);
+    else hipLaunchKernelGGL(k_fit_sgd, ogrid, dim3(256), 0, h->stream, o);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+
 // One table the optimizer updates in a step of a call: the rows `members` [n_m] of theta, n elements each at members[j] * stride, with
 // the moments and step counts of `opt`; row j's gradient lies at grad + j * n, and its step constants are made from p[j].
 struct FitTarget {
@@ -464,15 +498,7 @@ static int run_fit(clothhip_handle *h, const FitNet &net, const FitLoss &loss, c
         const FitTarget &t = targets[k];
         for (int s = 0; s < n_steps; s++)
             for (int32_t j = 0; j < t.n_m; j++) {
-                float *q = hyper.data() + hyper_at[k] + ((size_t)s * t.n_m + j) * FIT_HYPER;
-                const ClothFitParams &pj = t.p[j];
-                if (adam) {
-                    const double b1 = (double)pj.beta1, b2 = (double)pj.beta2, t1 = (double)(t.opt.t[t.members[j]] + s + 1);      // t1: the 1-based step count of this step
-                    const double a_t = (double)pj.lr * std::sqrt(1.0 - std::pow(b2, t1)) / (1.0 - std::pow(b1, t1));
-                    q[0] = (float)a_t; q[1] = pj.beta1; q[2] = (float)(1.0 - b1); q[3] = pj.beta2; q[4] = (float)(1.0 - b2); q[5] = pj.eps;
-                } else {
-                    q[0] = pj.lr; q[1] = pj.momentum;
-                }
+                step_constants(hyper.data() + hyper_at[k] + ((size_t)s * t.n_m + j) * FIT_HYPER, t.p[j], adam, t.opt.t[t.members[j]] + s + 1);
             }
     }
     HIPCHECK(hipSetDevice(h->device));
@@ -514,14 +540,7 @@ static int run_fit(clothhip_handle *h, const FitNet &net, const FitLoss &loss, c
                                   head ? f.d_ls_hist + (size_t)s * MLP_OUT : nullptr)) return rc;
         for (int k = 0; k < n_targets; k++) {      // (the head names its row 0 by the call's own member table: n_m == 1, members = {0})
             const FitTarget &t = targets[k];
-            FitOptArgs o = {};
-            o.theta = t.theta; o.m = t.opt.m; o.v = t.opt.v; o.g = t.grad; o.members = f.d_members;
-            o.hyper = f.d_hyper + hyper_at[k] + (size_t)s * t.n_m * FIT_HYPER;
-            o.stride = t.stride; o.n = t.n; o.blocks = (int32_t)((t.n + 255) / 256);
-            const dim3 ogrid((unsigned)o.blocks * (unsigned)t.n_m);
-            if (adam) hipLaunchKernelGGL(k_fit_adam, ogrid, dim3(256), 0, h->stream, o);
-            else hipLaunchKernelGGL(k_fit_sgd, ogrid, dim3(256), 0, h->stream, o);
-            HIPCHECK(hipGetLastError());
+            if (int rc = enqueue_optimizer(h, adam, t.theta, t.opt, t.grad, f.d_hyper + hyper_at[k] + (size_t)s * t.n_m * FIT_HYPER, t.stride, t.n, t.n_m)) return rc;
         }
     }
     HIPCHECK(hipEventRecord(h->ev1, h->stream));
@@ -743,7 +762,7 @@ extern "C" int clothhip_fit_data_snapshot_policy_members(clothhip_handle *h, int
         const FitPlan p = fit_plan(net, c.B);
         // (the launches read the chunk's members at the head of d_members: stream order keeps the chunks apart)
         HIPCHECK(hipMemcpyAsync(f.d_members, s.mem.data() + c.m0, (size_t)c.n_m * 4, hipMemcpyHostToDevice, h->stream));
-        if (int rc = enqueue_forward(h, net, p, c.n_m, f.d_idx + c.idx0, c.B, false)) return rc;
+        if (int rc = enqueue_forward(h, net, p, c.n_m, f.d_idx + c.idx0, c.B, false, policy_work(h))) return rc;
         launch_fit_scatter_y(h->stream, c.n_m, f.d_act + p.h_off[L - 1], f.d_idx + c.idx0, f.d_len + c.m0, h->dataset.old(), c.B, (int64_t)p.act);
         HIPCHECK(hipGetLastError());
     }
@@ -915,5 +934,311 @@ extern "C" int clothhip_fit_data_gae(clothhip_handle *h, int64_t first, int64_t 
     if (adv_out) HIPCHECK(hipMemcpyAsync(adv_out, f.d_adv, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
     if (ret_out) HIPCHECK(hipMemcpyAsync(ret_out, d.ret() + (size_t)first, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(hipStreamSynchronize(h->stream));      // (idx, a host table the upload read, goes out of scope)
+    return 0;
+}
+
+// ---- DDPG: a Q critic, target networks, the deterministic policy gradient (clothhip.h: DDPG ON THE DEVICE; cloth_fit_ddpg.hpp) -------------
+// Two more loss modes of the trainer above: the TD loss of the Q network, a one-row table as the value network is, over dense input rows
+// X = [s, a] that k_fit_concat makes, and the policy's loss -1/B sum Q(s, clamp(mu(s))), whose dZ is the critic's input gradient. The Q
+// passes work on their own scratch (FitWork), so the policy's activations survive them.
+static_assert(sizeof(ClothDdpgParams) == 24, "ClothDdpgParams is two doubles, a float and an int32");
+static_assert(FIT_TD_STATS + FIT_DPG_STATS == CLOTHHIP_DDPG_STATS && FIT_TD_STATS == CLOTHHIP_Q_STATS && FIT_DPG_STATS == CLOTHHIP_DPG_STATS, "the statistics of the header and of the kernels");
+static_assert(FIT_NEXT_TERMINAL == CLOTHHIP_FIT_NEXT_TERMINAL, "the terminal mark of the header and of the kernel");
+
+static FitNet q_net(clothhip_handle *h) { return {h->qnet.mlp, h->qnet.d_mlp, h->qnet.n_params, 0, h->fit.opt_q, true}; }
+
+// What every DDPG entry refuses of the handle's state; targets: the entry reads or moves the target copies
+static int check_ddpg_state(const clothhip_handle *h, bool targets, bool dataset) {
+    if (int rc = check_idle(h)) return rc;
+    if (h->pol.pop_rows) return fail(CLOTHHIP_ESTATE, "this handle holds a population of networks: DDPG trains the ONE shared network of clothhip_set_policy_mlp");
+    if (h->pol.mlp.n_layers < 1) return fail(CLOTHHIP_ESTATE, "no network on this handle: call clothhip_set_policy_mlp first");
+    if (h->qnet.mlp.n_layers < 1) return fail(CLOTHHIP_ESTATE, "no Q network on this handle: call clothhip_set_q_mlp first");
+    if (targets && !h->tgt.policy_valid) return fail(CLOTHHIP_ESTATE, "no target policy on this handle (a new policy network drops it): call clothhip_ddpg_sync_targets first");
+    if (targets && !h->tgt.q_valid) return fail(CLOTHHIP_ESTATE, "no target Q network on this handle (a new Q network drops it): call clothhip_ddpg_sync_targets first");
+    if (dataset && h->dataset.n < 1) return fail(CLOTHHIP_ESTATE, "the dataset is empty: call clothhip_fit_data_append first");
+    return 0;
+}
+static int check_tau(double tau) {
+    if (!std::isfinite(tau) || tau < 0.0 || tau > 1.0) return fail(CLOTHHIP_EINVAL, "tau = %g: the soft-update rate is finite and lies in [0, 1]", tau);
+    return 0;
+}
+static int check_ddpg_params(const ClothDdpgParams *q) {
+    if (!std::isfinite(q->gamma) || q->gamma < 0.0 || q->gamma > 1.0) return fail(CLOTHHIP_EINVAL, "gamma = %g: the discount is finite and lies in [0, 1]", q->gamma);
+    if (int rc = check_tau(q->tau)) return rc;
+    if (!(q->act_bound > 0.0f)) return fail(CLOTHHIP_EINVAL, "act_bound = %g: the action bound is > 0 (+inf: no clamp)", (double)q->act_bound);
+    if (q->flags) return fail(CLOTHHIP_EINVAL, "unknown flags 0x%x", q->flags);
+    return 0;
+}
+// the minibatches idx [n_idx] of a DDPG call: check_fit_rows, no leaf among them -> succ (may be NULL) [n_idx], the row that holds each
+// row's successor state (a terminal row: the row itself, whose value the TD kernel ignores)
+static int check_ddpg_rows(const clothhip_handle *h, const int32_t *idx, int64_t n_idx, int32_t B, std::vector<int32_t> *succ) {
+    if (int rc = check_fit_rows(h, 1, idx, n_idx, B)) return rc;
+    if (succ) { try { succ->resize((size_t)n_idx); } catch (const std::bad_alloc &) { return fail(CLOTHHIP_ENOMEM, "out of host memory (%lld rows)", (long long)n_idx); } }
+    for (int64_t i = 0; i < n_idx; i++) {
+        const int32_t nx = h->dataset.h_next[(size_t)idx[i]];
+        if (nx == CLOTHHIP_FIT_NEXT_NONE) return fail(CLOTHHIP_EINVAL, "idx[%lld] = row %d is a leaf: it has no transition (clothhip_fit_data_set_transitions)", (long long)i, idx[i]);
+        if (succ) (*succ)[(size_t)i] = nx >= 0 ? nx : idx[i];
+    }
+    return 0;
+}
+
+static int enqueue_concat(clothhip_handle *h, bool label, const float *act, const int32_t *d_rows, int32_t B, float bound) {
+    FitConcatArgs c = {};
+    c.obs = h->dataset.obs(); c.lab = h->dataset.lab(); c.act = act; c.rows = d_rows; c.X = h->fit.d_qx; c.bound = bound; c.B = B; c.L = 3 * h->P;
+    if (label) hipLaunchKernelGGL(k_fit_concat<true>, dim3((unsigned)B), dim3(FIT_DDPG_THREADS), 0, h->stream, c);
+    else hipLaunchKernelGGL(k_fit_concat<false>, dim3((unsigned)B), dim3(FIT_DDPG_THREADS), 0, h->stream, c);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+static int enqueue_polyak(clothhip_handle *h, double tau) {
+    const float t = (float)tau, omt = (float)(1.0 - tau);
+    const int64_t n[2] = {(int64_t)h->pol.mlp_n_params, (int64_t)h->qnet.n_params};
+    float *target[2] = {h->tgt.d_policy, h->tgt.d_q};
+    const float *theta[2] = {h->pol.d_mlp, h->qnet.d_mlp};
+    for (int k = 0; k < 2; k++) {
+        hipLaunchKernelGGL(k_fit_polyak, dim3((unsigned)((n[k] + FIT_DDPG_THREADS - 1) / FIT_DDPG_THREADS)), dim3(FIT_DDPG_THREADS), 0, h->stream, target[k], theta[k], n[k], t, omt);
+        HIPCHECK(hipGetLastError());
+    }
+    return 0;
+}
+// dL/da [B][4] into h->fit.d_da from the dZ of the critic's last layer (in w.dz): the input gradients of the NN product with the mask
+// epilogue down to layer 0, then layer 0's for the four action columns alone. No weight gradient is formed.
+static int enqueue_action_grad(clothhip_handle *h, const FitNet &net, const FitPlan &p, int32_t B, const FitWork &w) {
+    const MlpDesc &D = net.D;
+    float *dz[2] = {w.dz, w.dz + (size_t)B * p.maxw};
+    FitGemmArgs m0 = {};
+    m0.members = h->fit.d_members; m0.stride = D.stride;
+    for (int l = D.n_layers - 1; l >= 0; l--) {
+        const int n_in = D.widths[l], n_out = D.widths[l + 1];
+        FitGemmArgs b = m0;
+        b.A = dz[l & 1]; b.lda = n_out;
+        b.ldb = n_in; b.b_weights = 1;
+        b.M = B; b.K = n_out; b.k_chunk = n_out;
+        if (l > 0) {
+            b.B = D.params + p.w_off[l];
+            b.mask = w.act + p.h_off[l - 1];
+            b.C = dz[(l - 1) & 1]; b.ldc = n_in; b.N = n_in;
+            launch_gemm<true, false, FIT_EPI_MASK, false>(h->stream, b, 1);
+        } else {
+            b.B = D.params + p.w_off[0] + (n_in - MLP_OUT);      // W_0's action columns: the last four of a row of 3P + 4
+            b.C = h->fit.d_da; b.ldc = MLP_OUT; b.N = MLP_OUT;
+            launch_gemm<true, false, FIT_EPI_NONE, false>(h->stream, b, 1);
+        }
+        HIPCHECK(hipGetLastError());
+    }
+    return 0;
+}
+
+enum { DDPG_CRITIC = 1, DDPG_ACTOR = 2, DDPG_POLYAK = 4 };
+// Where a DDPG call's results go on the host, each NULL when not wanted: stats [n_steps][3 per network stepped], the critic's first; of
+// a gradient call (n_steps 1, nothing updated) the one network's gradient, the critic's y [B] and q [B], the actor's dL/da [B][4]
+struct DdpgOut { double *stats; float *grad, *y, *q, *da; };
+
+// n_steps steps over idx [n_steps][B] (succ beside it, for the critic): per step the critic's (DDPG_CRITIC), the actor's against the
+// critic as it stands then (DDPG_ACTOR), the soft update of both targets (DDPG_POLYAK); update false: the gradients only. The call is valid.
+static int run_ddpg(clothhip_handle *h, int mode, bool update, const ClothFitParams *p_policy, const ClothFitParams *p_q, const ClothDdpgParams &q, const int32_t *idx,
+                    const int32_t *succ, int32_t n_steps, int32_t B, const DdpgOut &out) {
+    auto &f = h->fit;
+    const auto &d = h->dataset;
+    const bool critic = (mode & DDPG_CRITIC) != 0, actor = (mode & DDPG_ACTOR) != 0;
+    const FitNet pnet = policy_net(h), qnet = q_net(h);
+    MlpDesc tp_desc = h->pol.mlp, tq_desc = h->qnet.mlp;
+    tp_desc.params = h->tgt.d_policy; tq_desc.params = h->tgt.d_q;
+    const FitNet tpnet = {tp_desc, h->tgt.d_policy, pnet.n_params, 0, f.opt_policy, false}, tqnet = {tq_desc, h->tgt.d_q, qnet.n_params, 0, f.opt_q, true};
+    const FitPlan pp = fit_plan(pnet, B), qp = fit_plan(qnet, B);
+    const int Lp = pnet.D.n_layers, Lq = qnet.D.n_layers, n_stats = (critic ? FIT_TD_STATS : 0) + (actor ? FIT_DPG_STATS : 0);
+    const size_t n_rows = (size_t)n_steps * B, xw = (size_t)3 * h->P + MLP_OUT;
+    // the step constants of both optimizers, the critic's table first; nothing of the handle changes yet
+    struct Trained { const FitNet *net; const ClothFitParams *p; size_t hyper_at; } trained[2] = {};
+    int n_trained = 0;
+    if (update && critic) trained[n_trained++] = {&qnet, p_q, 0};
+    if (update && actor) trained[n_trained++] = {&pnet, p_policy, 0};
+    std::vector<float> hyper;
+    try { hyper.assign((size_t)n_trained * n_steps * FIT_HYPER, 0.0f); } catch (const std::bad_alloc &) { return fail(CLOTHHIP_ENOMEM, "out of host memory (%d step constants)", n_steps); }
+    for (int k = 0; k < n_trained; k++) {
+        Trained &t = trained[k];
+        if (!ensure_row_state(t.net->opt, 1)) return fail(CLOTHHIP_ENOMEM, "out of host memory (the optimizer's state)");
+        t.hyper_at = (size_t)k * n_steps * FIT_HYPER;
+        for (int s = 0; s < n_steps; s++)
+            step_constants(hyper.data() + t.hyper_at + (size_t)s * FIT_HYPER, *t.p, t.p->optimizer == (float)CLOTHHIP_FIT_ADAM, t.net->opt.t[0] + s + 1);
+    }
+    HIPCHECK(hipSetDevice(h->device));
+    if (int rc = fit_reserve(h, pp, 1)) return rc;
+    if (int rc = f.d_qx.reserve((size_t)B * xw * 4)) return rc;
+    if (int rc = f.d_qact.reserve(2 * qp.act * 4)) return rc;
+    if (int rc = f.d_qdz.reserve(qp.dz * 4)) return rc;
+    if (qp.part) if (int rc = f.d_qpart.reserve(qp.part * 4)) return rc;
+    if (int rc = f.d_qgrad.reserve(qp.grad * 4)) return rc;
+    if (int rc = f.d_da.reserve((size_t)B * MLP_OUT * 4)) return rc;
+    if (int rc = f.d_tdy.reserve((size_t)B * 4)) return rc;
+    if (int rc = f.d_idx.reserve(n_rows * 4)) return rc;
+    if (critic) if (int rc = f.d_succ.reserve(n_rows * 4)) return rc;
+    if (int rc = f.d_loss.reserve((size_t)n_steps * n_stats * 8)) return rc;
+    if (n_trained) if (int rc = f.d_hyper.reserve(hyper.size() * 4)) return rc;
+    for (int k = 0; k < n_trained; k++) {
+        if (int rc = trained[k].net->opt.m.reserve(trained[k].net->n_params * 4)) return rc;
+        if (int rc = trained[k].net->opt.v.reserve(trained[k].net->n_params * 4)) return rc;
+    }
+    const FitWork pw = policy_work(h);
+    const FitWork qw = {f.d_qact, f.d_qdz, f.d_qpart, f.d_qgrad, f.d_qx}, tqw = {f.d_qact + qp.act, nullptr, nullptr, nullptr, f.d_qx};
+    // from here on the call goes through (but for a failure of the runtime itself)
+    for (int k = 0; k < n_trained; k++) {
+        OptState &o = trained[k].net->opt;
+        if (o.zero[0]) {
+            HIPCHECK(hipMemsetAsync(o.m, 0, trained[k].net->n_params * 4, h->stream));
+            HIPCHECK(hipMemsetAsync(o.v, 0, trained[k].net->n_params * 4, h->stream));
+            o.zero[0] = 0;
+        }
+        o.t[0] += n_steps;
+    }
+    HIPCHECK(hipMemcpyAsync(f.d_members, SHARED_ROW, 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipMemcpyAsync(f.d_idx, idx, n_rows * 4, hipMemcpyHostToDevice, h->stream));
+    if (critic) HIPCHECK(hipMemcpyAsync(f.d_succ, succ, n_rows * 4, hipMemcpyHostToDevice, h->stream));
+    if (n_trained) HIPCHECK(hipMemcpyAsync(f.d_hyper, hyper.data(), hyper.size() * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipEventRecord(h->ev0, h->stream));
+    const float *qv = f.d_qact + qp.h_off[Lq - 1], *y = f.d_act + pp.h_off[Lp - 1];
+    float *q_dz = f.d_qdz + ((Lq - 1) & 1) * (size_t)B * qp.maxw;
+    const float seed_f = -1.0f / (float)B;      // the dZ of the critic's last layer under L = -1/B sum Q
+    int seed_bits;
+    memcpy(&seed_bits, &seed_f, 4);
+    for (int s = 0; s < n_steps; s++) {
+        const int32_t *d_idx = f.d_idx + (size_t)s * B, *d_succ = f.d_succ + (size_t)s * B;
+        double *st = f.d_loss + (size_t)s * n_stats;
+        int k = 0;
+        if (critic) {
+            // the target critic on [s', clamp(mu'(s'))]: the target policy over the successor rows, on the policy's scratch
+            if (int rc = enqueue_forward(h, tpnet, pp, 1, d_succ, B, false, pw)) return rc;
+            if (int rc = enqueue_concat(h, false, y, d_succ, B, q.act_bound)) return rc;
+            if (int rc = enqueue_forward(h, tqnet, qp, 1, nullptr, B, false, tqw)) return rc;
+            // the critic on [s, clamp(a)], a the action the row executed
+            if (int rc = enqueue_concat(h, true, nullptr, d_idx, B, q.act_bound)) return rc;
+            if (int rc = enqueue_forward(h, qnet, qp, 1, nullptr, B, false, qw)) return rc;
+            FitTdArgs t = {};
+            t.q = qv; t.qn = tqw.act + qp.h_off[Lq - 1]; t.rew = d.rew(); t.next = d.next(); t.rows = d_idx; t.dz = q_dz; t.y_out = f.d_tdy; t.stats = st;
+            t.gamma = q.gamma; t.B = B;
+            hipLaunchKernelGGL(k_fit_loss_td, dim3(1), dim3(FIT_DDPG_THREADS), 0, h->stream, t);
+            HIPCHECK(hipGetLastError());
+            if (int rc = enqueue_backward(h, qnet, qp, 1, nullptr, B, qw)) return rc;
+            if (update) {
+                const bool adam = p_q->optimizer == (float)CLOTHHIP_FIT_ADAM;
+                if (int rc = enqueue_optimizer(h, adam, qnet.theta, qnet.opt, f.d_qgrad, f.d_hyper + trained[k].hyper_at + (size_t)s * FIT_HYPER, 0, (int64_t)qnet.n_params, 1)) return rc;
+                k++;
+            }
+            st += FIT_TD_STATS;
+        }
+        if (actor) {
+            if (int rc = enqueue_forward(h, pnet, pp, 1, d_idx, B, false, pw)) return rc;
+            if (int rc = enqueue_concat(h, false, y, d_idx, B, q.act_bound)) return rc;
+            if (int rc = enqueue_forward(h, qnet, qp, 1, nullptr, B, false, qw)) return rc;
+            HIPCHECK(hipMemsetD32Async((hipDeviceptr_t)q_dz, seed_bits, (size_t)B, h->stream));
+            if (int rc = enqueue_action_grad(h, qnet, qp, B, qw)) return rc;
+            FitDpgArgs g = {};
+            g.dA = f.d_da; g.y = y; g.q = qv; g.dz = f.d_dz + ((Lp - 1) & 1) * (size_t)B * pp.maxw; g.stats = st; g.bound = q.act_bound; g.B = B;
+            hipLaunchKernelGGL(k_fit_dpg_dz, dim3(1), dim3(FIT_DDPG_THREADS), 0, h->stream, g);
+            HIPCHECK(hipGetLastError());
+            if (int rc = enqueue_backward(h, pnet, pp, 1, d_idx, B, pw)) return rc;
+            if (update) {
+                const bool adam = p_policy->optimizer == (float)CLOTHHIP_FIT_ADAM;
+                if (int rc = enqueue_optimizer(h, adam, pnet.theta, pnet.opt, f.d_grad, f.d_hyper + trained[k].hyper_at + (size_t)s * FIT_HYPER, 0, (int64_t)pnet.n_params, 1)) return rc;
+            }
+        }
+        if (mode & DDPG_POLYAK) if (int rc = enqueue_polyak(h, q.tau)) return rc;
+    }
+    HIPCHECK(hipEventRecord(h->ev1, h->stream));
+    h->have_timing = true;
+    f.ddpg_B = B; f.ddpg_critic = critic; f.ddpg_qn_at = qp.act + qp.h_off[Lq - 1]; f.ddpg_q_at = qp.h_off[Lq - 1];
+    if (out.stats) HIPCHECK(hipMemcpyAsync(out.stats, f.d_loss, (size_t)n_steps * n_stats * 8, hipMemcpyDeviceToHost, h->stream));
+    if (out.grad) HIPCHECK(hipMemcpyAsync(out.grad, critic ? f.d_qgrad : f.d_grad, (critic ? qp.grad : pp.grad) * 4, hipMemcpyDeviceToHost, h->stream));
+    if (out.y) HIPCHECK(hipMemcpyAsync(out.y, f.d_tdy, (size_t)B * 4, hipMemcpyDeviceToHost, h->stream));
+    if (out.q) HIPCHECK(hipMemcpyAsync(out.q, qv, (size_t)B * 4, hipMemcpyDeviceToHost, h->stream));
+    if (out.da) HIPCHECK(hipMemcpyAsync(out.da, f.d_da, (size_t)B * MLP_OUT * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));      // (the host tables are never retained)
+    return 0;
+}
+
+extern "C" int clothhip_q_fit_grad(clothhip_handle *h, const ClothDdpgParams *q, const int32_t *idx, int32_t B, float *grad_out, double *stats_out, float *y_out,
+                                   float *q_out) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (!q) return fail(CLOTHHIP_EINVAL, "NULL argument");
+    if (int rc = check_ddpg_state(h, true, true)) return rc;
+    std::vector<int32_t> succ;
+    if (int rc = check_ddpg_rows(h, idx, B, B, &succ)) return rc;
+    if (int rc = check_ddpg_params(q)) return rc;
+    return run_ddpg(h, DDPG_CRITIC, false, nullptr, nullptr, *q, idx, succ.data(), 1, B, {stats_out, grad_out, y_out, q_out, nullptr});
+}
+
+extern "C" int clothhip_policy_fit_dpg_grad(clothhip_handle *h, const ClothDdpgParams *q, const int32_t *idx, int32_t B, float *grad_out, double *stats_out,
+                                            float *da_out) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (!q) return fail(CLOTHHIP_EINVAL, "NULL argument");
+    if (int rc = check_ddpg_state(h, false, true)) return rc;
+    if (int rc = check_ddpg_rows(h, idx, B, B, nullptr)) return rc;
+    if (int rc = check_ddpg_params(q)) return rc;
+    return run_ddpg(h, DDPG_ACTOR, false, nullptr, nullptr, *q, idx, nullptr, 1, B, {stats_out, grad_out, nullptr, nullptr, da_out});
+}
+
+// the three step entries behind their argument lists: p_policy / p_q NULL where the mode does not train that network
+static int ddpg_steps(clothhip_handle *h, int mode, const ClothFitParams *p_policy, const ClothFitParams *p_q, const ClothDdpgParams *q, const int32_t *idx,
+                      int32_t n_steps, int32_t B, double *stats_out) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (!q || ((mode & DDPG_ACTOR) && !p_policy) || ((mode & DDPG_CRITIC) && !p_q)) return fail(CLOTHHIP_EINVAL, "NULL argument");
+    if (n_steps < 0) return fail(CLOTHHIP_EINVAL, "n_steps < 0");
+    if (int rc = check_ddpg_state(h, mode != DDPG_ACTOR, true)) return rc;
+    std::vector<int32_t> succ;
+    if (int rc = check_ddpg_rows(h, idx, (int64_t)n_steps * B, B, (mode & DDPG_CRITIC) ? &succ : nullptr)) return rc;
+    if (mode & DDPG_ACTOR) if (int rc = check_fit_params(p_policy, -1)) return rc;
+    if (mode & DDPG_CRITIC) if (int rc = check_fit_params(p_q, -1)) return rc;
+    if (int rc = check_ddpg_params(q)) return rc;
+    if (n_steps == 0) return 0;
+    return run_ddpg(h, mode, true, p_policy, p_q, *q, idx, succ.data(), n_steps, B, {stats_out, nullptr, nullptr, nullptr, nullptr});
+}
+
+extern "C" int clothhip_q_fit(clothhip_handle *h, const ClothFitParams *p, const ClothDdpgParams *q, const int32_t *idx, int32_t n_steps, int32_t B, double *stats_out) {
+    return ddpg_steps(h, DDPG_CRITIC, nullptr, p, q, idx, n_steps, B, stats_out);
+}
+
+extern "C" int clothhip_policy_fit_dpg(clothhip_handle *h, const ClothFitParams *p, const ClothDdpgParams *q, const int32_t *idx, int32_t n_steps, int32_t B,
+                                       double *stats_out) {
+    return ddpg_steps(h, DDPG_ACTOR, p, nullptr, q, idx, n_steps, B, stats_out);
+}
+
+extern "C" int clothhip_ddpg_fit(clothhip_handle *h, const ClothFitParams *p_policy, const ClothFitParams *p_q, const ClothDdpgParams *q, const int32_t *idx,
+                                 int32_t n_steps, int32_t B, double *stats_out) {
+    return ddpg_steps(h, DDPG_CRITIC | DDPG_ACTOR | DDPG_POLYAK, p_policy, p_q, q, idx, n_steps, B, stats_out);
+}
+
+extern "C" int clothhip_ddpg_polyak(clothhip_handle *h, double tau) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (int rc = check_ddpg_state(h, true, false)) return rc;
+    if (int rc = check_tau(tau)) return rc;
+    HIPCHECK(hipSetDevice(h->device));
+    HIPCHECK(hipEventRecord(h->ev0, h->stream));
+    if (int rc = enqueue_polyak(h, tau)) return rc;
+    HIPCHECK(hipEventRecord(h->ev1, h->stream));
+    h->have_timing = true;
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// what the last DDPG call left in the Q passes' scratch (clothhip.h: for tests of the elementwise kernels)
+extern "C" int clothhip_ddpg_last_tables(clothhip_handle *h, int32_t B, float *x_out, float *qn_out, float *q_out) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (int rc = check_idle(h)) return rc;
+    auto &f = h->fit;
+    if (f.ddpg_B < 1) return fail(CLOTHHIP_ESTATE, "no DDPG call has run on this handle's present Q network");
+    if (B != f.ddpg_B) return fail(CLOTHHIP_EINVAL, "B = %d, the last DDPG call ran minibatches of %d rows", B, f.ddpg_B);
+    if (qn_out && !f.ddpg_critic) return fail(CLOTHHIP_ESTATE, "the last DDPG call ran no critic's step: there are no target critic's values");
+    HIPCHECK(hipSetDevice(h->device));
+    if (x_out) HIPCHECK(hipMemcpyAsync(x_out, f.d_qx, (size_t)B * ((size_t)3 * h->P + MLP_OUT) * 4, hipMemcpyDeviceToHost, h->stream));
+    if (qn_out) HIPCHECK(hipMemcpyAsync(qn_out, f.d_qact + f.ddpg_qn_at, (size_t)B * 4, hipMemcpyDeviceToHost, h->stream));
+    if (q_out) HIPCHECK(hipMemcpyAsync(q_out, f.d_qact + f.ddpg_q_at, (size_t)B * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+extern "C" int clothhip_q_fit_reset(clothhip_handle *h) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (int rc = check_idle(h)) return rc;
+    h->fit.opt_q.forget();
     return 0;
 }

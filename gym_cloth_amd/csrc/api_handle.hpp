@@ -206,6 +206,21 @@ struct clothhip_handle : HostPlan {
         Buffer<float> d_mlp;
         size_t n_params = 0;
     } val;
+    // The Q network of DDPG (api_policy.hip: clothhip_set_q_mlp), a critic over (state, action): input
+    // width 3P + 4, ONE output; independent of the policy, the value network and the log-sigma head as the value network is, and to the
+    // trainer one more weight table of ONE row. No launch evaluates it.
+    struct QNet {
+        MlpDesc mlp = {};
+        Buffer<float> d_mlp;
+        size_t n_params = 0;
+    } qnet;
+    // DDPG's target copies (api_policy.hip: clothhip_ddpg_sync_targets, _get_targets) of the shared policy blob and of the Q blob, each
+    // valid from a sync until a new network of its kind (drop_network: a policy or a population; clothhip_set_q_mlp); api_fit.hip's
+    // k_fit_polyak moves them
+    struct DdpgTargets {
+        Buffer<float> d_policy, d_q;
+        bool policy_valid = false, q_valid = false;
+    } tgt;
     // The device-resident dataset of the trainer and its row sources (api_fit_data.hip: clothhip_fit_data_append*, the column accessors,
     // clothhip_fit_hold, clothhip_fit_data_append_launch*). api_fit.hip reads the columns through the accessors below, lets its kernels
     // write ret and w (clothhip_fit_data_gae) and old (clothhip_fit_data_snapshot_policy) where they lie, and reads n and the two mirrors.
@@ -243,6 +258,18 @@ struct clothhip_handle : HostPlan {
         // the three optimizers: the policy's, per row of its weight table, the value network's of ONE row, and the one of the policy's
         // log-sigma head, a table of one row of four elements
         OptState opt_policy, opt_value, opt_sigma;
+        // DDPG (clothhip_q_fit*, clothhip_policy_fit_dpg*, clothhip_ddpg_fit): the Q network's optimizer, restarted by a new Q network,
+        // and the Q passes' OWN scratch -- the policy's activations in d_act survive them --: the critic's input rows X [B][3P + 4],
+        // its activations (two networks' worth: the live critic, then the target), two dZ tables, the split batch sums, its gradient;
+        // the successor rows of a minibatch, dL/da [B][4], the TD targets y [B]
+        OptState opt_q;
+        Buffer<float> d_qx, d_qact, d_qdz, d_qpart, d_qgrad, d_da, d_tdy;
+        Buffer<int32_t> d_succ;
+        // what the last DDPG call left in that scratch, for clothhip_ddpg_last_tables: its B (0: nothing), whether it ran the
+        // critic (the target critic's values are then there), and where in d_qact the target critic's and the critic's outputs lie
+        int32_t ddpg_B = 0;
+        bool ddpg_critic = false;
+        size_t ddpg_qn_at = 0, ddpg_q_at = 0;
         // one step's scratch, sized on demand, one of each per member of the call: the index table, the hidden activations and y, the
         // two dZ tables, the split batch sums of a weight gradient, the gradient (blob layout), the losses; the call's member rows and
         // its table of per-member, per-step optimizer constants

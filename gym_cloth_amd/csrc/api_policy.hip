@@ -13,10 +13,13 @@
 
 // ---- a learned policy: the handle's network (cloth_policy_mlp.hpp) ----------------------------------------------------------------------
 // the shape rules of every entry that takes a network
-static int check_mlp_shape(const clothhip_handle *h, int32_t n_layers, const int32_t *widths, int32_t n_out = MLP_OUT) {
+// (n_act: the action components behind the observation in a row of the network's input -- 4 for the Q network, else none)
+static int check_mlp_shape(const clothhip_handle *h, int32_t n_layers, const int32_t *widths, int32_t n_out = MLP_OUT, int32_t n_act = 0) {
     if (n_layers < 1 || n_layers > MLP_MAX_LAYERS) return fail(CLOTHHIP_EINVAL, "n_layers %d outside [0, %d]", n_layers, MLP_MAX_LAYERS);
     if (!widths) return fail(CLOTHHIP_EINVAL, "NULL argument");
-    if (widths[0] != 3 * h->P) return fail(CLOTHHIP_EINVAL, "the network's input width is %d, the '1d' observation has %d values", widths[0], 3 * h->P);
+    if (n_act && widths[0] != 3 * h->P + n_act)
+        return fail(CLOTHHIP_EINVAL, "the network's input width is %d, the '1d' observation and an action have %d values", widths[0], 3 * h->P + n_act);
+    if (!n_act && widths[0] != 3 * h->P) return fail(CLOTHHIP_EINVAL, "the network's input width is %d, the '1d' observation has %d values", widths[0], 3 * h->P);
     if (widths[n_layers] != n_out)
         return fail(CLOTHHIP_EINVAL, n_out == MLP_OUT ? "the network's output width is %d, an action has %d values" : "the network's output width is %d, a value is %d number", widths[n_layers], n_out);
     for (int l = 1; l < n_layers; l++)
@@ -29,8 +32,12 @@ static int check_members(const int32_t *member, int64_t n, int64_t rows, const c
         if (member[e] < 0 || member[e] >= rows) return fail(CLOTHHIP_EINVAL, "%s[%lld] = %d outside [0, %lld)", what, (long long)e, member[e], (long long)rows);
     return 0;
 }
-// the handle without a network of either kind (the memory stays with the handle for the next one); the trainer's moments belonged to the old one
-static void drop_network(clothhip_handle *h) { h->fit.opt_policy.forget(); h->pol.mlp = MlpDesc{}; h->pol.pop_rows = 0; h->pol.mlp_n_params = 0; h->pol.pop_generated = false; }
+// the handle without a network of either kind (the memory stays with the handle for the next one); the trainer's moments belonged to the
+// old one, and so did DDPG's target policy
+static void drop_network(clothhip_handle *h) {
+    h->fit.opt_policy.forget(); h->pol.mlp = MlpDesc{}; h->pol.pop_rows = 0; h->pol.mlp_n_params = 0; h->pol.pop_generated = false;
+    h->tgt.policy_valid = false;
+}
 static MlpDesc mlp_desc(int32_t n_layers, const int32_t *widths, const float *params, const int32_t *member, size_t stride) {
     MlpDesc d = {};
     d.n_layers = n_layers;
@@ -171,6 +178,92 @@ extern "C" int clothhip_get_value_mlp(clothhip_handle *h, float *out, size_t n_p
     if (n_params != h->val.n_params) return fail(CLOTHHIP_EINVAL, "n_params = %zu, the value network holds %zu parameters", n_params, h->val.n_params);
     HIPCHECK(hipSetDevice(h->device));
     HIPCHECK(hipMemcpyAsync(out, h->val.d_mlp, n_params * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// ---- DDPG's networks (clothhip.h: DDPG ON THE DEVICE): the Q network over (observation, action), and the target copies ---------------------
+extern "C" int clothhip_set_q_mlp(clothhip_handle *h, int32_t n_layers, const int32_t *widths, const float *params, size_t n_params) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (int rc = check_idle(h)) return rc;
+    auto drop = [h] { h->fit.opt_q.forget(); h->fit.ddpg_B = 0; h->qnet.mlp = MlpDesc{}; h->qnet.n_params = 0; h->tgt.q_valid = false; };
+    if (n_layers == 0) { drop(); return 0; }
+    if (int rc = check_mlp_shape(h, n_layers, widths, 1, MLP_OUT)) return rc;
+    if (!params) return fail(CLOTHHIP_EINVAL, "NULL argument");
+    const size_t need = mlp_param_count(n_layers, widths);
+    if (n_params != need) return fail(CLOTHHIP_EINVAL, "n_params = %zu, these widths hold %zu parameters", n_params, need);
+    HIPCHECK(hipSetDevice(h->device));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    drop();                                         // as clothhip_set_value_mlp: a failure below leaves the handle without a Q network
+    if (int rc = h->qnet.d_mlp.reserve(need * 4)) return rc;
+    HIPCHECK(hipMemcpyAsync(h->qnet.d_mlp, params, need * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    h->qnet.mlp = mlp_desc(n_layers, widths, h->qnet.d_mlp, nullptr, 0);
+    h->qnet.n_params = need;
+    return 0;
+}
+
+extern "C" int clothhip_get_q_mlp(clothhip_handle *h, float *out, size_t n_params) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (int rc = check_idle(h)) return rc;
+    if (h->qnet.mlp.n_layers < 1) return fail(CLOTHHIP_ESTATE, "no Q network on this handle: call clothhip_set_q_mlp first");
+    if (!out) return fail(CLOTHHIP_EINVAL, "out is NULL");
+    if (n_params != h->qnet.n_params) return fail(CLOTHHIP_EINVAL, "n_params = %zu, the Q network holds %zu parameters", n_params, h->qnet.n_params);
+    HIPCHECK(hipSetDevice(h->device));
+    HIPCHECK(hipMemcpyAsync(out, h->qnet.d_mlp, n_params * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+extern "C" int clothhip_ddpg_sync_targets(clothhip_handle *h) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (int rc = check_idle(h)) return rc;
+    if (h->pol.pop_rows) return fail(CLOTHHIP_ESTATE, "this handle holds a population of networks: DDPG trains the ONE shared network of clothhip_set_policy_mlp");
+    if (h->pol.mlp.n_layers < 1) return fail(CLOTHHIP_ESTATE, "no network on this handle: call clothhip_set_policy_mlp first");
+    if (h->qnet.mlp.n_layers < 1) return fail(CLOTHHIP_ESTATE, "no Q network on this handle: call clothhip_set_q_mlp first");
+    HIPCHECK(hipSetDevice(h->device));
+    h->tgt.policy_valid = h->tgt.q_valid = false;   // a failure below leaves the handle without targets
+    if (int rc = h->tgt.d_policy.reserve(h->pol.mlp_n_params * 4)) return rc;
+    if (int rc = h->tgt.d_q.reserve(h->qnet.n_params * 4)) return rc;
+    HIPCHECK(hipMemcpyAsync(h->tgt.d_policy, h->pol.d_mlp, h->pol.mlp_n_params * 4, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHECK(hipMemcpyAsync(h->tgt.d_q, h->qnet.d_mlp, h->qnet.n_params * 4, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHECK(hipStreamSynchronize(h->stream));
+    h->tgt.policy_valid = h->tgt.q_valid = true;
+    return 0;
+}
+
+// the targets from the host (a checkpoint's): either blob may be NULL, which leaves that target as it is
+extern "C" int clothhip_ddpg_set_targets(clothhip_handle *h, const float *policy, const float *q) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (int rc = check_idle(h)) return rc;
+    if (h->pol.pop_rows) return fail(CLOTHHIP_ESTATE, "this handle holds a population of networks: DDPG trains the ONE shared network of clothhip_set_policy_mlp");
+    if (policy && h->pol.mlp.n_layers < 1) return fail(CLOTHHIP_ESTATE, "no network on this handle: call clothhip_set_policy_mlp first (the target policy has its shape)");
+    if (q && h->qnet.mlp.n_layers < 1) return fail(CLOTHHIP_ESTATE, "no Q network on this handle: call clothhip_set_q_mlp first (the target Q network has its shape)");
+    HIPCHECK(hipSetDevice(h->device));
+    if (policy) {
+        h->tgt.policy_valid = false;
+        if (int rc = h->tgt.d_policy.reserve(h->pol.mlp_n_params * 4)) return rc;
+        HIPCHECK(hipMemcpyAsync(h->tgt.d_policy, policy, h->pol.mlp_n_params * 4, hipMemcpyHostToDevice, h->stream));
+    }
+    if (q) {
+        h->tgt.q_valid = false;
+        if (int rc = h->tgt.d_q.reserve(h->qnet.n_params * 4)) return rc;
+        HIPCHECK(hipMemcpyAsync(h->tgt.d_q, q, h->qnet.n_params * 4, hipMemcpyHostToDevice, h->stream));
+    }
+    HIPCHECK(hipStreamSynchronize(h->stream));      // the host blobs are never retained
+    if (policy) h->tgt.policy_valid = true;
+    if (q) h->tgt.q_valid = true;
+    return 0;
+}
+
+extern "C" int clothhip_ddpg_get_targets(clothhip_handle *h, float *policy_out, float *q_out) {
+    if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
+    if (int rc = check_idle(h)) return rc;
+    if (policy_out && !h->tgt.policy_valid) return fail(CLOTHHIP_ESTATE, "no target policy on this handle: call clothhip_ddpg_sync_targets first");
+    if (q_out && !h->tgt.q_valid) return fail(CLOTHHIP_ESTATE, "no target Q network on this handle: call clothhip_ddpg_sync_targets first");
+    HIPCHECK(hipSetDevice(h->device));
+    if (policy_out) HIPCHECK(hipMemcpyAsync(policy_out, h->tgt.d_policy, h->pol.mlp_n_params * 4, hipMemcpyDeviceToHost, h->stream));
+    if (q_out) HIPCHECK(hipMemcpyAsync(q_out, h->tgt.d_q, h->qnet.n_params * 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHECK(hipStreamSynchronize(h->stream));
     return 0;
 }

@@ -544,6 +544,32 @@ def actor_critic_fit(env, trainer, critic, col, gamma=0.99, lam=0.95, n_value_st
     return {'adv': adv, 'ret': ret, 'value_losses': vl, 'policy_losses': pl, 'rows': trainer.size()}
 
 
+def ddpg_fit(env, trainer, qcritic, col, gamma=0.99, tau=0.005, n_steps=100, batch_size=64, seed=0, act_bound=1.0):
+    """The refit after actor_critic_collect under DDPG, on the device: n_steps steps of MLPTrainer.ddpg_step with
+    `qcritic` (policies.QTrainer on `env`), each a TD step of the critic, a step of the policy up the critic's action gradient and the
+    soft update of both targets. The minibatches are drawn from the non-leaf rows of the WHOLE dataset -- the replay buffer: rows of
+    earlier collections keep paying --, a function of (the dataset, n_steps, batch_size, seed) alone. The targets are synced on the
+    first use of this (trainer, qcritic) pair and whenever a new network dropped one. `col` is the collection that was just added (only
+    its row count is reported). Returns dict(stats float64[n_steps, 6]: the critic's loss, mean q, mean y, then the actor's loss,
+    gated fraction, mean |dL/da| of every step before its update; rows int32[n_steps, B]: the minibatches; replay: the non-leaf
+    rows sampled from; synced: whether this call synced the targets)."""
+    from ._lib import FIT_NEXT_NONE, ClothHipError
+    if trainer.env is not env or qcritic.env is not env:
+        raise ValueError("the trainer or the Q critic belongs to another env")
+    replay = np.nonzero(env.batch.fit_get_transitions()[1] != FIT_NEXT_NONE)[0]
+    if replay.size < 1:
+        raise ValueError("the dataset holds no row with a transition: collect first")
+    synced = False
+    try:
+        env.batch.ddpg_targets()
+    except ClothHipError:
+        qcritic.sync_targets()
+        synced = True
+    table = replay.astype(np.int32)[trainer.index_table(replay.size, n_steps, batch_size, seed)]
+    stats = env.batch.ddpg_fit(table, gamma, tau, act_bound, policy_hyper=trainer.hyper, q_hyper=qcritic.hyper)
+    return {'stats': stats, 'rows': table, 'replay': replay, 'synced': synced, 'collected': int(col['appended']) if col is not None else 0}
+
+
 def ppo_fit(env, trainer, critic, col, sigma=None, gamma=0.99, lam=0.95, clip=0.2, n_value_steps=100, n_epochs=10, batch_size=64, seed=0,
             target_kl=None, normalize=True, ent_coef=0.0):
     """The refit after actor_critic_collect with PPO's clipped surrogate in the place of actor_critic_fit's weighted regression, on the

@@ -34,7 +34,8 @@ from .references import (NEXT_NONE, NEXT_TERMINAL, _house_sum, _plan_clip, adam_
                          fit_reference, gae_reference, log_fixed_reference, normal_fixed_reference, philox4x32_10, philox_eps,
                          plan_refit_reference, plan_sample_reference, plan_score_reference, policy_noise_reference, ppo_loss_reference, ppo_reference, ppo_sigma_loss_reference, ppo_sigma_reference, sgd_reference,
                          value_fit_reference)
-from .trainers import MLPEnsemble, MLPTrainer, ValueTrainer, ensemble_disagreement  # noqa: F401
+from .references import concat_reference, dpg_dz_reference, dpg_reference, polyak_reference, q_fit_reference, td_loss_reference  # noqa: F401
+from .trainers import MLPEnsemble, MLPTrainer, QTrainer, ValueTrainer, ensemble_disagreement  # noqa: F401
 
 
 def _data_delta(x, y, targx, targy, shrink=True):

@@ -1,6 +1,6 @@
 """The numpy restatements the GPU tests pin the device to, and that a user can check a fit against: the trainer's three objectives in
-float64 over the one pass of mlp.py (fit_reference, value_fit_reference, ppo_reference, ppo_sigma_reference), and what the device computes
-restated operation by operation, bit for bit (gae_reference, exp_fixed_reference, ppo_loss_reference, ppo_sigma_loss_reference, adam_reference, sgd_reference, Philox, the
+float64 over the one pass of mlp.py (fit_reference, value_fit_reference, ppo_reference, ppo_sigma_reference, q_fit_reference, dpg_reference), and what the device computes
+restated operation by operation, bit for bit (gae_reference, DDPG's concat_reference, td_loss_reference, dpg_dz_reference and polyak_reference, exp_fixed_reference, ppo_loss_reference, ppo_sigma_loss_reference, adam_reference, sgd_reference, Philox, the
 cross-entropy planner's sampling, scoring and refit, and the exploration noise made on the device: log_fixed_reference,
 normal_fixed_reference, policy_noise_reference). numpy and math only; nothing here touches the library."""
 import math
@@ -116,6 +116,134 @@ def gae_reference(v, rew, next, gamma, lam, w_scale=1.0, normalize=False):
     with np.errstate(over='ignore', invalid='ignore'):
         w = np.where(leaf, 0.0, float(np.float32(w_scale)) * hat).astype(np.float32)
     return adv, ret, w
+
+
+def _clamp(a, bound):
+    """min(max(a, -bound), +bound), exact in any float format; bound = inf: a itself."""
+    b = float(np.float32(bound))
+    return np.minimum(np.maximum(a, -b), b)
+
+
+def ddpg_successors(next, idx):
+    """The successor table of a DDPG minibatch as the library makes it on the host: succ[r] = next[idx[r]], for a terminal row the row
+    itself (its value is ignored). ValueError for a leaf in idx (next == NEXT_NONE): it has no transition. `next` is the dataset's column."""
+    ix = np.asarray(idx, dtype=np.int64)
+    nx = np.asarray(next).astype(np.int64)[ix]
+    if (nx == NEXT_NONE).any():
+        raise ValueError("idx names a leaf row (no transition): position %d" % int(np.nonzero((nx == NEXT_NONE).reshape(-1))[0][0]))
+    return np.where(nx >= 0, nx, ix)
+
+
+def q_fit_reference(q_layers, target_q_layers, target_policy_layers, obs, labels, rew, next, idx, gamma, act_bound=np.inf):
+    """Pure-numpy float64 loss and gradient of DDPG's critic step (clothhip_q_fit_grad): over the rows idx [B] of the dataset (obs [n, 3P],
+    labels [n, 4] the executed actions, rew [n], next [n] its successor column)
+        y_r = rew_r + gamma Q'(s'_r, clamp(mu'(s'_r)))   (0 in the place of Q' behind a terminal row),   L = 1 / (2 B) sum_r (Q(s_r, clamp(a_r)) - y_r)^2
+    with Q the Q network over rows [s, a] of 3P + 4 values, Q' and mu' the target copies; y is a constant of the gradient. Every
+    stored value is rounded to float32 first, the arithmetic is float64 (y is NOT rounded to float32, as the device does: on exactly
+    representable data that is no difference). Returns (loss, [(dW, db), ...] of the Q network, y [B], q [B])."""
+    ix = np.asarray(idx, dtype=np.int64).reshape(-1)
+    succ = ddpg_successors(next, ix)
+    terminal = np.asarray(next).astype(np.int64)[ix] == NEXT_TERMINAL
+    x = np.asarray(obs, dtype=np.float32).astype(np.float64)
+    a = np.asarray(labels, dtype=np.float64).astype(np.float32).astype(np.float64)[ix]
+    r = np.asarray(rew, dtype=np.float64).astype(np.float32).astype(np.float64).reshape(-1)[ix]
+    B = len(ix)
+    mu_n = mlp_forward(*mlp_float64(target_policy_layers), x[succ])[-1]
+    qn = mlp_forward(*mlp_float64(target_q_layers), np.concatenate([x[succ], _clamp(mu_n, act_bound)], axis=1))[-1][:, 0]
+    y = r + float(gamma) * np.where(terminal, 0.0, qn)
+    Ws, bs = mlp_float64(q_layers)
+    hs = mlp_forward(Ws, bs, np.concatenate([x[ix], _clamp(a, act_bound)], axis=1))
+    d = hs[-1][:, 0] - y
+    loss = float((d * d).sum() / (2.0 * B))
+    return loss, mlp_backward(Ws, hs, (d / float(B))[:, None]), y, hs[-1][:, 0]
+
+
+def dpg_reference(policy_layers, q_layers, obs, idx, act_bound=np.inf):
+    """Pure-numpy float64 loss and gradient of DDPG's actor step (clothhip_policy_fit_dpg_grad): L = -1 / B sum_r Q(s_r, clamp(mu(s_r))) over
+    the policy's weights, the critic fixed. dA = dL/da is the critic's input gradient at its four action columns; the clamp's gate sets
+    dz_rk = 0 where (mu_rk >= bound and dA_rk < 0) or (mu_rk <= -bound and dA_rk > 0) and passes dA_rk otherwise. Returns
+    (stats = [loss, gated fraction, mean |dA|], [(dW, db), ...] of the policy, dA [B, 4])."""
+    ix = np.asarray(idx, dtype=np.int64).reshape(-1)
+    x = np.asarray(obs, dtype=np.float32).astype(np.float64)[ix]
+    B, b = len(ix), float(np.float32(act_bound))
+    Wp, bp = mlp_float64(policy_layers)
+    hp = mlp_forward(Wp, bp, x)
+    mu = hp[-1]
+    Wq, bq = mlp_float64(q_layers)
+    hq = mlp_forward(Wq, bq, np.concatenate([x, _clamp(mu, act_bound)], axis=1))
+    g = np.full((B, 1), -1.0 / B)
+    for l in range(len(Wq) - 1, 0, -1):
+        g = (g @ Wq[l]) * (hq[l] > 0.0)
+    dA = (g @ Wq[0])[:, -4:]
+    gated = ((mu >= b) & (dA < 0.0)) | ((mu <= -b) & (dA > 0.0))
+    stats = np.array([-hq[-1][:, 0].sum() / B, gated.sum() / (4.0 * B), np.abs(dA).sum() / (4.0 * B)])
+    return stats, mlp_backward(Wp, hp, np.where(gated, 0.0, dA)), dA
+
+
+def concat_reference(obs, act, idx, act_bound=np.inf):
+    """k_fit_concat restated, bit for bit: float32 [B, 3P + 4] = [obs[idx], min(max(act, -bound), +bound)]; act float32 [B, 4] is one
+    action per minibatch row -- the label column at idx (the critic's step), or a network's output on the minibatch."""
+    ix = np.asarray(idx, dtype=np.int64).reshape(-1)
+    x, a = np.asarray(obs, dtype=np.float32), np.asarray(act, dtype=np.float32)
+    if a.shape != (len(ix), 4):
+        raise ValueError("act must hold one action per minibatch row: shape (%d, 4)" % len(ix))
+    return np.concatenate([x[ix], _clamp(a, act_bound).astype(np.float32)], axis=1)
+
+
+def td_loss_reference(q, qn, rew, next, gamma):
+    """k_fit_loss_td restated in numpy from the float32 q [B] (the critic) and qn [B] (the target critic on the successors), bit for
+    bit, reduction order included: rew [B] and next [B] are the minibatch rows' reward and successor column. Returns (y float32[B], dz
+    float32[B], stats float64[3] = loss, mean q, mean y)."""
+    q32, qn32 = np.asarray(q, dtype=np.float32).reshape(-1), np.asarray(qn, dtype=np.float32).reshape(-1)
+    r64 = np.asarray(rew, dtype=np.float32).astype(np.float64).reshape(-1)
+    B = len(q32)
+    nv = np.where(np.asarray(next).reshape(-1) == NEXT_TERMINAL, 0.0, qn32.astype(np.float64))
+    with np.errstate(over='ignore'):
+        y = (r64 + float(gamma) * nv).astype(np.float32)
+        dz = (q32 - y) / np.float32(B)
+    dd = q32.astype(np.float64) - y.astype(np.float64)
+    stats = np.array([_house_sum(dd * dd) / float(2 * B), _house_sum(q32.astype(np.float64)) / float(B), _house_sum(y.astype(np.float64)) / float(B)])
+    return y, dz.astype(np.float32), stats
+
+
+def _house_sum_rows(x):
+    """The device's reduction order over x [B, 4] float64 where a thread owns whole ROWS: thread t of 256 adds its rows t, t + 256, ...
+    ascending, a row's four components in ascending order, from +0.0; then the halving tree."""
+    x = np.asarray(x, dtype=np.float64)
+    k = max((len(x) + 255) // 256, 1)
+    tab = np.zeros((k * 256, 4))
+    tab[:len(x)] = x
+    tab = tab.reshape(k, 256, 4)
+    red = np.zeros(256)
+    for kk in range(k):
+        for c in range(4):
+            red = red + tab[kk, :, c]
+    o = 128
+    while o > 0:
+        red[:o] = red[:o] + red[o:2 * o]
+        o >>= 1
+    return red[0]
+
+
+def dpg_dz_reference(dA, y, q, act_bound=np.inf):
+    """k_fit_dpg_dz restated in numpy, bit for bit, reduction order included: dA float32 [B, 4] the critic's input gradient at the
+    action columns, y float32 [B, 4] the policy's output, q float32 [B] the critic's. Returns (dz float32[B, 4], stats float64[3] =
+    -mean q, gated fraction, mean |dA|)."""
+    g, mu = np.asarray(dA, dtype=np.float32), np.asarray(y, dtype=np.float32)
+    b = np.float32(act_bound)
+    B = len(g)
+    gated = ((mu >= b) & (g < 0.0)) | ((mu <= -b) & (g > 0.0))
+    dz = np.where(gated, np.float32(0.0), g).astype(np.float32)
+    stats = np.array([-_house_sum(np.asarray(q, dtype=np.float32).astype(np.float64)) / float(B), _house_sum_rows(gated.astype(np.float64)) / float(4 * B),
+                      _house_sum_rows(np.abs(g).astype(np.float64)) / float(4 * B)])
+    return dz, stats
+
+
+def polyak_reference(target, theta, tau):
+    """k_fit_polyak restated, bit for bit: float32 fl(fl(omt target) + fl(t theta)) with t = (float32)tau, omt = (float32)(1 - tau)."""
+    t, omt = np.float32(float(tau)), np.float32(1.0 - float(tau))
+    tg, th = np.asarray(target, dtype=np.float32), np.asarray(theta, dtype=np.float32)
+    return ((omt * tg).astype(np.float32) + (t * th).astype(np.float32)).astype(np.float32)
 
 
 _LOG2E, _LN2_HI, _LN2_LO = float.fromhex('0x1.71547652b82fep+0'), float.fromhex('0x1.62e42feep-1'), float.fromhex('0x1.a39ef35793c76p-33')

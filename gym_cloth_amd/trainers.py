@@ -2,6 +2,8 @@
 MLPTrainer           the supervised refit of the shared network on the device (ClothBatch.fit_*), Adam or SGD over (observation, label)
                      rows, and PPO's clipped surrogate over the same rows; references.fit_reference / ppo_reference are its yardsticks
 ValueTrainer         the critic of an actor-critic (ClothBatch.value_*; references.value_fit_reference, gae_reference)
+QTrainer             the critic of DDPG over (state, action) with its target copies (ClothBatch.q_*, ddpg_*; references.q_fit_reference,
+                     dpg_reference); MLPTrainer.ddpg_step is the loop's step
 MLPEnsemble          G networks, one per env slot, fitted together on the device in the launches of one (ClothBatch.fit_members): a
                      bootstrapped ensemble whose disagreement is a novelty signal, a learning-rate sweep -- also of PPO, every member
                      under its own sigma, clip and optimizer (ClothBatch.fit_ppo_members)"""
@@ -177,6 +179,23 @@ class MLPTrainer(_EnvDataset):
             self.last_log_sigma = np.concatenate(heads) if heads else np.zeros((0, 4), dtype=np.float32)
         return (np.concatenate(out) if out else np.zeros((0, 3 if sigma is not None else 4))), epochs
 
+    def ddpg_step(self, qcritic, n_steps, batch_size, seed, gamma=0.99, tau=0.005, act_bound=1.0, rows=None):
+        """n_steps DDPG steps on the device in ONE call (ClothBatch.ddpg_fit): per step the TD step of `qcritic` (a
+        QTrainer on the same env), this network's step up the critic's action gradient, the soft update of both targets -- under this
+        trainer's optimizer for the policy and qcritic's for the critic. The minibatches are index_table(m, n_steps, batch_size, seed)
+        over `rows` (int [m] dataset rows WITH a transition; None: every non-leaf row of the dataset, old collections included). The
+        targets must have been synced (qcritic.sync_targets). Returns float64[n_steps, 6]: the critic's (loss, mean q, mean y), then
+        the actor's (loss = -mean q, gated fraction, mean |dL/da|), each before its update."""
+        if qcritic.env is not self.env:
+            raise ValueError("the Q critic belongs to another env")
+        if rows is None:
+            rows = np.nonzero(self.env.batch.fit_get_transitions()[1] != _lib.FIT_NEXT_NONE)[0]
+            if rows.size < 1:
+                raise ValueError("the dataset holds no row with a transition: collect first")
+        rows = _check_rows(rows)
+        table = rows.astype(np.int32)[self.index_table(rows.size, n_steps, batch_size, seed)]
+        return self.env.batch.ddpg_fit(table, gamma, tau, act_bound, policy_hyper=self.hyper, q_hyper=qcritic.hyper)
+
     def layers(self):
         """The network as the device holds it now: [(W, b), ...] float32, by download (clothhip_get_policy_mlp)."""
         return unpack_mlp(self.widths, self.env.batch.get_policy_mlp(0, self.n_params))
@@ -230,6 +249,50 @@ class ValueTrainer(object):
     def reset(self):
         """Zero the critic's moments and step count; its weights, the policy's optimizer and the dataset stay."""
         self.env.batch.value_fit_reset()
+
+
+class QTrainer(object):
+    """The critic of DDPG ON THE DEVICE (no reference counterpart; ClothBatch.q_*): a network Q(s, a) with ONE output
+    over rows of 3P + 4 values -- a dataset row's observation followed by an action --, fitted to the TD target
+    rew + gamma Q'(s', mu'(s')) through the row's successor, with target copies Q', mu' on the batch. `q_layers` is a list of (W, b)
+    with an input width of 3P + 4 and a last width of 1; the constructor puts it on the env's batch beside the policy, which it leaves
+    alone, and the dataset is not cleared. The targets exist from sync_targets on; a new policy or Q network drops its target."""
+
+    def __init__(self, env, q_layers, optimizer='adam', lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, momentum=0.0):
+        self.hyper = _hyper(optimizer, lr=lr, beta1=beta1, beta2=beta2, eps=eps, momentum=momentum)
+        self.env = env
+        self.widths, blob = pack_mlp(q_layers, n_in=3 * env.P + 4, n_out=1)
+        self.n_params = int(blob.size)
+        env.batch.set_q_mlp(q_layers)
+
+    def sync_targets(self):
+        """Copy the env's present policy network and this critic into the target copies (ClothBatch.ddpg_sync_targets)."""
+        self.env.batch.ddpg_sync_targets()
+
+    def step(self, n_steps, batch_size, seed, gamma=0.99, act_bound=1.0, rows=None):
+        """n_steps TD steps of the critic alone (ClothBatch.q_fit) on minibatches drawn as ValueTrainer.step draws them; rows None: the
+        non-leaf rows of the dataset. No target moves. Returns float64[n_steps, 3]: loss, mean q, mean y before each update."""
+        if rows is None:
+            rows = np.nonzero(self.env.batch.fit_get_transitions()[1] != _lib.FIT_NEXT_NONE)[0]
+            if rows.size < 1:
+                raise ValueError("the dataset holds no row with a transition: collect first")
+        rows = _check_rows(rows)
+        table = rows.astype(np.int32)[MLPTrainer.index_table(rows.size, n_steps, batch_size, seed)]
+        return self.env.batch.q_fit(table, gamma, act_bound, **self.hyper)
+
+    def grad(self, idx, gamma=0.99, act_bound=1.0):
+        """(stats float64[3], [(dW, db), ...], y float32[B], q float32[B]) over the dataset rows idx at the present weights and targets,
+        from the device; nothing is updated."""
+        stats, g, y, q = self.env.batch.q_grad(idx, gamma, act_bound)
+        return stats, unpack_mlp(self.widths, g), y, q
+
+    def layers(self):
+        """The critic as the device holds it now: [(W, b), ...] float32, by download (clothhip_get_q_mlp)."""
+        return unpack_mlp(self.widths, self.env.batch.get_q_mlp())
+
+    def reset(self):
+        """Zero the critic's moments and step count; its weights, the targets, the policy's optimizer and the dataset stay."""
+        self.env.batch.q_fit_reset()
 
 
 def ensemble_disagreement(actions):

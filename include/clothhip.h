@@ -842,6 +842,85 @@ int clothhip_policy_fit_ppo_members(clothhip_handle *h, const ClothFitParams *p,
 int clothhip_policy_noise_fill(clothhip_handle *h, uint64_t seed, int32_t T, const int64_t *slot_base, const double *sigma, int32_t sigma_rows, void **d_noise);
 int clothhip_policy_noise_get(clothhip_handle *h, int32_t T, double *out);
 
+/* DDPG ON THE DEVICE (additive, ABI 7; the off-policy loop of the reference's cfg/demo_baselines*.yaml, no kernel counterpart there;
+ * DESIGN 4.3.14): a Q CRITIC over (state, action), TARGET copies of the policy and of the critic with a soft update, the TD target read
+ * through a row's successor, and the deterministic policy gradient -- the actor's dZ taken from the critic's input gradient. The
+ * dataset is the replay buffer: a row's label is the action it executed (CLOTHHIP_FIT_LABEL_ACTION), rew and next are its transition,
+ * and old collections stay in it. Every entry above keeps its bytes; a handle that never calls an entry below behaves as before.
+ * THE Q NETWORK. clothhip_set_q_mlp takes the shape rules and the blob layout of clothhip_set_value_mlp, except widths[0] == 3 P + 4: a
+ * row of its input is the '1d' observation followed by the four action components; widths[n_layers] == 1. It is independent of the
+ * policy, the value network and the log-sigma head, and the reverse; n_layers == 0 drops it; a refused call keeps the earlier one;
+ * clothhip_fork does not carry it; no launch evaluates it. It has its own optimizer state (moments, 1-based step count, the lazy reset
+ * of the other tables), restarted by a new Q network and by clothhip_q_fit_reset. clothhip_get_q_mlp downloads the blob.
+ * THE TARGETS are a second policy blob and a second Q blob on the handle. clothhip_ddpg_sync_targets copies the present shared policy
+ * network and Q network into them, device to device; clothhip_ddpg_get_targets downloads them (either pointer may be NULL;
+ * policy_out[the policy's n_params], q_out[the Q network's n_params]); clothhip_ddpg_set_targets uploads them, as a checkpoint restores
+ * them (a NULL pointer leaves that target as it is; a blob has the layout and the size of the network it shadows, which must be there). A new policy network (or a population, or dropping it)
+ * invalidates the target policy, a new Q network the target Q; entries that read or move a target then return CLOTHHIP_ESTATE until the
+ * next sync. DDPG trains the ONE shared network: with a population on the handle every entry below returns CLOTHHIP_ESTATE.
+ * THE CRITIC'S INPUT. k_fit_concat writes X[r][0 .. 3P) = obs[idx[r]][.], X[r][3P .. 3P + 4) = min(max(a_r, -bound), +bound) with
+ * bound = act_bound (float32; +inf: no clamp; min and max are exact) and a_r the row's label (the critic's step) or a network's
+ * float32 output (the target policy on the successor; the policy in the actor's step). The Q network's products run over X with the
+ * kernels and the summation order of the value network's.
+ * THE CRITIC'S STEP over a minibatch idx[B]. The host makes succ[r] = next[idx[r]] from its mirror of the next column (a TERMINAL
+ * row: the row itself, whose value is ignored) and uploads it beside idx. mu' = target policy on obs[succ]; qn = target Q on
+ * [obs[succ], clamp(mu')]; q = Q on [obs[idx], clamp(label)]. Per row, every operation ONE double rounding:
+ *   nv = (double)qn_r, or 0 where next[idx[r]] is TERMINAL;  y_r = (float)((double)rew + (gamma nv))
+ * then in float32 dz_r = fl(fl(q_r - y_r) / fl(B)); the loss adds dd dd, dd = (double)q - (double)y, in the order of
+ * clothhip_value_fit_grad (thread t of 256 takes rows t, t + 256, ..., then the halving tree) and divides by 2 B.
+ *   stats = {loss, (sum q) / B, (sum y) / B}        (CLOTHHIP_Q_STATS)
+ * Everything behind dz is the trainer's backward pass. clothhip_q_fit_grad: grad_out[n_params of Q], stats_out[3], y_out[B],
+ * q_out[B], each may be NULL; nothing is updated. clothhip_q_fit: n_steps optimizer steps under p over idx[n_steps][B],
+ * stats_out[n_steps][3] (may be NULL) BEFORE each update. Neither moves a target.
+ * THE ACTOR'S STEP minimises L = -1/B sum_r Q(s_r, clamp(mu(s_r))) over the policy's weights, the critic held fixed: mu = policy on
+ * obs[idx]; Q's forward on [obs[idx], clamp(mu)]; the dZ of Q's last layer is the constant fl(-1.0f / fl(B)); Q's input gradients run
+ * down to layer 0 (the masked product of the trainer's backward), and layer 0's is formed for the four action columns alone:
+ * dA[B][4] = dZ_0 W_0[:, 3P .. 3P + 4), one accumulator per element, k ascending. No Q weight gradient is formed. The clamp's gate:
+ *   dz_rk = 0 where (mu_rk >= bound and dA_rk < 0) or (mu_rk <= -bound and dA_rk > 0), else dA_rk
+ * -- a component outside the box whose descent step would push it further out is held; inward moves pass.
+ *   stats = {-(sum q) / B, gated / (4 B), (sum |dA_rk|) / (4 B)}      (CLOTHHIP_DPG_STATS; sums in double, rows in the order above, k ascending)
+ * Everything behind dz is the trainer's backward pass of the policy. clothhip_policy_fit_dpg_grad: grad_out[n_params of the policy],
+ * stats_out[3], da_out[B][4] = dA, each may be NULL; nothing is updated. clothhip_policy_fit_dpg: n_steps steps under p with the
+ * POLICY'S optimizer state (shared with clothhip_policy_fit and clothhip_policy_fit_ppo; clothhip_policy_fit_reset restarts it);
+ * stats_out[n_steps][3]. It reads no target.
+ * THE SOFT UPDATE. clothhip_ddpg_polyak: target_i = fl(fl(omt target_i) + fl(t theta_i)) for both targets, t = (float)tau and
+ * omt = (float)(1 - tau) formed in double on the host.
+ * clothhip_ddpg_fit runs n_steps times: the critic's step under p_q, the actor's step under p_policy against the UPDATED critic, the
+ * soft update of both targets by q->tau -- all enqueued behind one upload, synchronous; stats_out[n_steps][6] (may be NULL): the
+ * critic's three, then the actor's three. It equals, by bytes, the same steps made of clothhip_q_fit (1 step),
+ * clothhip_policy_fit_dpg (1 step) and clothhip_ddpg_polyak: the same launches in the same order. The Q passes have scratch tables of
+ * their own, so the policy's activations survive them. No floating-point atomics anywhere: two runs give the same bits.
+ * Refused before anything is touched, no network, target, moment or step count changed -- CLOTHHIP_ESTATE: a launch in flight, no
+ * policy network, a population, no Q network, no valid target where the entry reads or moves one (clothhip_q_fit*, clothhip_ddpg_fit,
+ * clothhip_ddpg_polyak), an empty dataset (not for sync, polyak and reset); CLOTHHIP_EINVAL: B outside [1, CLOTHHIP_FIT_MAX_BATCH],
+ * n_steps < 0, an index outside the dataset, a LEAF row in idx (its next is CLOTHHIP_FIT_NEXT_NONE: it has no transition), gamma or tau
+ * not finite or outside [0, 1], act_bound <= 0 or NaN, flags != 0, an optimizer clothhip_policy_fit would refuse, a NULL table.
+ * n_steps == 0 returns 0.
+ * clothhip_ddpg_last_tables (for tests of the elementwise kernels; nothing is computed) downloads what the LAST DDPG call of minibatches
+ * of B rows left in the Q passes' scratch, each pointer may be NULL: x_out[B][3P + 4], the critic's input rows its last k_fit_concat
+ * wrote; q_out[B], the critic's output of its last forward; qn_out[B], the target critic's values -- there only when the call ran a
+ * critic's step (not after clothhip_policy_fit_dpg*), else CLOTHHIP_ESTATE. CLOTHHIP_ESTATE before any DDPG call on the present Q network,
+ * CLOTHHIP_EINVAL for another B.
+ * OUT OF SCOPE: twin critics, target smoothing, a delayed actor; DDPG for a population; prioritised replay, n-step targets; a tanh
+ * output; reading the dataset as a second operand of the product in the place of the copy X. */
+typedef struct ClothDdpgParams { double gamma, tau; float act_bound; int32_t flags /* none defined: 0 */; } ClothDdpgParams;
+#define CLOTHHIP_Q_STATS 3        /* loss, mean q, mean y */
+#define CLOTHHIP_DPG_STATS 3      /* loss = -mean q, gated fraction, mean |dL/da| */
+#define CLOTHHIP_DDPG_STATS 6     /* clothhip_ddpg_fit: the critic's, then the actor's */
+int clothhip_set_q_mlp(clothhip_handle *h, int32_t n_layers, const int32_t *widths, const float *params, size_t n_params);
+int clothhip_get_q_mlp(clothhip_handle *h, float *out, size_t n_params);
+int clothhip_ddpg_sync_targets(clothhip_handle *h);
+int clothhip_ddpg_get_targets(clothhip_handle *h, float *policy_out, float *q_out);
+int clothhip_ddpg_set_targets(clothhip_handle *h, const float *policy, const float *q);
+int clothhip_q_fit_grad(clothhip_handle *h, const ClothDdpgParams *q, const int32_t *idx, int32_t B, float *grad_out, double *stats_out, float *y_out, float *q_out);
+int clothhip_q_fit(clothhip_handle *h, const ClothFitParams *p, const ClothDdpgParams *q, const int32_t *idx, int32_t n_steps, int32_t B, double *stats_out);
+int clothhip_q_fit_reset(clothhip_handle *h);
+int clothhip_policy_fit_dpg_grad(clothhip_handle *h, const ClothDdpgParams *q, const int32_t *idx, int32_t B, float *grad_out, double *stats_out, float *da_out);
+int clothhip_policy_fit_dpg(clothhip_handle *h, const ClothFitParams *p, const ClothDdpgParams *q, const int32_t *idx, int32_t n_steps, int32_t B, double *stats_out);
+int clothhip_ddpg_polyak(clothhip_handle *h, double tau);
+int clothhip_ddpg_last_tables(clothhip_handle *h, int32_t B, float *x_out, float *qn_out, float *q_out);
+int clothhip_ddpg_fit(clothhip_handle *h, const ClothFitParams *p_policy, const ClothFitParams *p_q, const ClothDdpgParams *q, const int32_t *idx, int32_t n_steps, int32_t B, double *stats_out);
+
 int clothhip_run_actions(clothhip_handle *h, const ClothEpisodeParams *ep, int32_t T, int32_t policy,
                          const double *actions, int32_t actions_on_device, const int32_t *policy_arg,
                          const ClothResetScript *scripts, int32_t n_scripts, int32_t *num_steps, uint8_t *done,
