@@ -1,4 +1,4 @@
-"""ClothBatch's bindings of the trainer on the handle (clothhip.h, csrc/api_fit_data.hip and api_fit.hip): the device-resident dataset
+"""ClothBatch's bindings of the trainer on the handle (clothhip.h, csrc/api_fit_data.hip, api_fit.hip, api_fit_rollout.hip and api_fit_ddpg.hip): the device-resident dataset
 and its columns, the fit of the shared network and of population rows, the value network, GAE and PPO. A mixin of batch.ClothBatch: it
 reads self._L, self._h, self.E and self.P, and the sizes batch_policy.py's setters leave (_mlp_n_params, _pop_shape)."""
 import ctypes as C

@@ -222,8 +222,8 @@ struct clothhip_handle : HostPlan {
         bool policy_valid = false, q_valid = false;
     } tgt;
     // The device-resident dataset of the trainer and its row sources (api_fit_data.hip: clothhip_fit_data_append*, the column accessors,
-    // clothhip_fit_hold, clothhip_fit_data_append_launch*). api_fit.hip reads the columns through the accessors below, lets its kernels
-    // write ret and w (clothhip_fit_data_gae) and old (clothhip_fit_data_snapshot_policy) where they lie, and reads n and the two mirrors.
+    // clothhip_fit_hold, clothhip_fit_data_append_launch*). The trainer's units (fit_trainer.hpp) read the columns through the accessors below, let their kernels
+    // write ret and w (clothhip_fit_data_gae) and old (clothhip_fit_data_snapshot_policy) where they lie, and read n and the mirrors.
     struct FitData {
         Buffer<uint32_t> col[FIT_COLS];      // one table per column (FIT_COL above), [cap][width], grown geometrically with the contents kept
         int64_t n = 0, cap = 0;              // rows that count, rows allocated
@@ -250,31 +250,32 @@ struct clothhip_handle : HostPlan {
         Buffer<int32_t> d_rows, d_flag;
         Buffer<float> d_wtab;
     } dataset;
-    // The trainer of the handle's networks (api_fit.hip: clothhip_policy_fit*, clothhip_value_*, clothhip_fit_data_gae, _snapshot_policy).
-    // A new network of either kind (api_policy.hip's drop_network) restarts the policy's optimizer by opt_policy.forget(), a new value
-    // network the critic's by opt_value.forget(), clothhip_set_policy_log_sigma the head's by opt_sigma.forget(); nothing else outside
-    // api_fit.hip touches it.
+    // The trainer of the handle's networks (fit_trainer.hpp; api_fit.hip: clothhip_policy_fit*, clothhip_value_*; api_fit_rollout.hip:
+    // clothhip_fit_data_gae, _snapshot_policy*; api_fit_ddpg.hip: clothhip_q_fit*, clothhip_policy_fit_dpg*, clothhip_ddpg_*). A new
+    // network of either kind (api_policy.hip's drop_network) restarts the policy's optimizer by opt_policy.forget(), a new value network
+    // the critic's by opt_value.forget(), clothhip_set_policy_log_sigma the head's by opt_sigma.forget(), a new Q network opt_q; nothing
+    // else outside those three units touches it.
     struct Fit {
-        // the three optimizers: the policy's, per row of its weight table, the value network's of ONE row, and the one of the policy's
-        // log-sigma head, a table of one row of four elements
-        OptState opt_policy, opt_value, opt_sigma;
-        // DDPG (clothhip_q_fit*, clothhip_policy_fit_dpg*, clothhip_ddpg_fit): the Q network's optimizer, restarted by a new Q network,
-        // and the Q passes' OWN scratch -- the policy's activations in d_act survive them --: the critic's input rows X [B][3P + 4],
-        // its activations (two networks' worth: the live critic, then the target), two dZ tables, the split batch sums, its gradient;
-        // the successor rows of a minibatch, dL/da [B][4], the TD targets y [B]
-        OptState opt_q;
-        Buffer<float> d_qx, d_qact, d_qdz, d_qpart, d_qgrad, d_da, d_tdy;
+        // the four optimizers: the policy's, per row of its weight table, the value network's and the Q network's of ONE row each, and
+        // the one of the policy's log-sigma head, a table of one row of four elements
+        OptState opt_policy, opt_value, opt_sigma, opt_q;
+        // The four tables the passes of one network work on, sized on demand by fit_reserve alone and handed to the launches as a
+        // FitWork by fit_work alone: the hidden activations and y, the two dZ tables, the split batch sums of a weight gradient, the
+        // gradient (blob layout). `own`: the trainer's, one of each per member of the call. `qpass`: the Q passes' of DDPG -- the
+        // policy's activations in own survive them --, ONE of each but activations for two networks: the live critic, then the target.
+        struct Pass { Buffer<float> d_act, d_dz, d_part, d_grad; } own, qpass;
+        // DDPG's other scratch: the critic's input rows X [B][3P + 4], dL/da [B][4], the TD targets y [B], the successor rows of a minibatch
+        Buffer<float> d_qx, d_da, d_tdy;
         Buffer<int32_t> d_succ;
         // what the last DDPG call left in that scratch, for clothhip_ddpg_last_tables: its B (0: nothing), whether it ran the
-        // critic (the target critic's values are then there), and where in d_qact the target critic's and the critic's outputs lie
+        // critic (the target critic's values are then there), and where in qpass.d_act the target critic's and the critic's outputs lie
         int32_t ddpg_B = 0;
         bool ddpg_critic = false;
         size_t ddpg_qn_at = 0, ddpg_q_at = 0;
-        // one step's scratch, sized on demand, one of each per member of the call: the index table, the hidden activations and y, the
-        // two dZ tables, the split batch sums of a weight gradient, the gradient (blob layout), the losses; the call's member rows and
-        // its table of per-member, per-step optimizer constants
+        // one call's tables, sized on demand: the index table, the losses; the call's member rows and its table of per-target, per-step,
+        // per-member optimizer constants
         Buffer<int32_t> d_idx, d_members;
-        Buffer<float> d_act, d_dz, d_part, d_grad, d_hyper;
+        Buffer<float> d_hyper;
         Buffer<double> d_loss;
         Buffer<float> d_pred;        // clothhip_policy_fit_predict*: y of every member and row, [n_m][n][4]; clothhip_value_predict and clothhip_fit_data_gae: v [n]
         Buffer<float> d_ratio;       // clothhip_policy_fit_ppo*_grad*: (float)rho of every member's minibatch rows, [n_m][B]

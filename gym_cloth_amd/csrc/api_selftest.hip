@@ -1,8 +1,9 @@
 // api_selftest.hip -- clothhip_selftest_*: host and device pieces exposed to the test suite. (The two that test cloth_render_obs.hpp are
-// beside its kernels in api_observe.hip, and clothhip_selftest_exp_fixed beside cloth_policy_fit.hpp's in api_fit.hip: a header with a non-template kernel has one includer.)
+// beside its kernels in api_observe.hip: a header with a non-template kernel has one includer.)
 #include <hip/hip_runtime.h>
 
 #include "api_handle.hpp"
+#include "cloth_exp_fixed.hpp"
 #include "cloth_philox.hpp"
 #include "cloth_selftest_kernel.hpp"
 
@@ -90,5 +91,15 @@ extern "C" int clothhip_selftest_arith(int32_t device, int32_t op, const double 
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipDeviceSynchronize());
     HIPCHECK(hipMemcpy(out, dout, n * 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// the host runs the very function of the PPO losses and of the exploration noise (cloth_exp_fixed.hpp)
+extern "C" int clothhip_selftest_exp_fixed(const double *x, int64_t n, double *out) {
+    if (n < 0 || (n > 0 && (!x || !out))) return fail(CLOTHHIP_EINVAL, "bad argument");
+    for (int64_t i = 0; i < n; i++) {
+        if (x[i] != x[i]) return fail(CLOTHHIP_EINVAL, "x[%lld] is NaN", (long long)i);
+        out[i] = exp_fixed(x[i]);
+    }
     return 0;
 }

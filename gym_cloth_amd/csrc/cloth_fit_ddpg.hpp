@@ -2,7 +2,7 @@
 // arithmetic operation by operation; no reference counterpart): the critic's input rows, the TD loss, the gate of the deterministic
 // policy gradient and the soft update of the targets. Everything between them -- the forwards of four networks, the critic's backward,
 // its input-gradient chain, the policy's backward, the optimizers -- is k_fit_gemm, k_fit_reduce, k_fit_colsum, k_fit_adam and k_fit_sgd,
-// launched by api_fit.hip on the critic's own scratch tables. Included only by api_fit.hip, behind cloth_policy_fit.hpp.
+// launched by api_fit.hip (for api_fit_ddpg.hip, which owns the order) on the critic's own scratch tables. Included only by api_fit.hip, behind cloth_policy_fit.hpp.
 //
 // The house rules hold: no floating-point atomics; a reduction has ONE order -- thread t of 256 takes rows t, t + 256, ... ascending, then
 // fit_tree_sums --; every operation is one rounding (the unit is built with -ffp-contract=off); ordinary vector stores only. All four are

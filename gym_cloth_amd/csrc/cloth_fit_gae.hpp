@@ -1,5 +1,5 @@
 // cloth_fit_gae.hpp -- generalised advantage estimation over rows of the trainer's dataset (clothhip_fit_data_gae; no reference
-// counterpart: the step between a fitted critic and an advantage-weighted policy fit). Included only by api_fit.hip, which has run the value
+// counterpart: the step between a fitted critic and an advantage-weighted policy fit). Included only by api_fit_rollout.hip, which has run the value
 // network's forward over the range first: v [n] float32, row i of the range at v[i].
 //
 // A row's chain is r_0 = r, r_k+1 = next[r_k]; it stops after a row whose next is TERMINAL or whose successor is a LEAF (next == NONE).

@@ -291,6 +291,92 @@ def test_a_fit_is_its_steps_one_call_at_a_time(name, hyper):
     one.close(); steps.close()
 
 
+def _layers_of(blob, widths):
+    """_flat's inverse: the blob as [(W, b)] of a network of these widths."""
+    layers, at = [], 0
+    for n_in, n_out in zip(widths[:-1], widths[1:]):
+        layers.append((blob[at:at + n_out * n_in].reshape(n_out, n_in).copy(), blob[at + n_out * n_in:at + n_out * n_in + n_out].copy()))
+        at += n_out * n_in + n_out
+    assert at == blob.size
+    return layers
+
+
+@pytest.mark.parametrize("name,hyper", [OPTIMIZERS[0], OPTIMIZERS[2]], ids=["adam", "sgd_momentum"])
+def test_different_losses_continue_one_optimizers_step_count(name, hyper):
+    """On ONE handle: fit (2 steps), dpg_fit (1 step), fit_ppo (1 step, fixed sigma, after a snapshot), ddpg_fit (2 steps). Before every
+    step a second handle, a probe with the same dataset, is given the restated networks and targets and returns the corresponding
+    *_grad entry's gradient on the step's rows; after each call the policy's blob equals by bytes the restated optimizer step of that
+    gradient with t = 1 .. 6 and the moments carried over from loss to loss, and the Q blob the restated steps t = 1, 2 of its own
+    optimizer. After fit_reset the next DPG step is the t = 1 step from zero moments."""
+    from gym_cloth_amd.policies import polyak_reference
+    pw, qw, B, sigma, tau = [300, 5, 4], [304, 5, 1], 8, 0.3, 0.25
+    c, _ = D.gaussian_case(pw, qw, B, seed=7, n_rows=48)
+    table = np.random.RandomState(3).randint(0, 47, size=(7, B)).astype(np.int32)      # (row 47 is the leaf)
+    w = np.random.RandomState(1).normal(size=48).astype(np.float32)
+    q_hyper = dict(hyper, lr=2.0 * hyper['lr'])
+    b, probe = _load(_new_batch(10), c), _load(_new_batch(10), c)
+    for x in (b, probe):
+        x.fit_set_weights(w)
+    th = dict(zip(('p', 'q', 'tp', 'tq'), _states(b)))
+    mom = {k: (np.zeros_like(th[k]), np.zeros_like(th[k])) for k in ('p', 'q')}
+    t = {'p': 0, 'q': 0}
+
+    def put():
+        """the restated state on the probe (a new network drops its target: all four, in this order)"""
+        probe.set_policy_mlp(_layers_of(th['p'], pw))
+        probe.set_q_mlp(_layers_of(th['q'], qw))
+        probe.ddpg_set_targets(_layers_of(th['tp'], pw), _layers_of(th['tq'], qw))
+
+    def restate(k, hyp, g):
+        assert g.any()
+        t[k] += 1
+        before = th[k]
+        th[k], m, v = _restated_step(hyp, th[k], mom[k][0], mom[k][1], g, t[k])
+        mom[k] = (m, v)
+        assert not _same(th[k], before)
+
+    # 1. the squared error, two steps in one call: t = 1, 2
+    for s in (0, 1):
+        put()
+        restate('p', hyper, probe.fit_grad(table[s])[1])
+    b.fit(table[0:2], **hyper)
+    assert _same(_blob(b), th['p']), (name, "fit")
+    # 2. the deterministic policy gradient: t = 3
+    put()
+    restate('p', hyper, probe.dpg_grad(table[2], D.G_BOUND)[1])
+    b.dpg_fit(table[2:3], D.G_BOUND, **hyper)
+    assert _same(_blob(b), th['p']), (name, "dpg_fit")
+    # 3. PPO's clipped surrogate under a fixed sigma, after a snapshot of the present means: t = 4
+    put()
+    probe.fit_snapshot_policy()
+    b.fit_snapshot_policy()
+    assert b.fit_get_old_means().tobytes() == probe.fit_get_old_means().tobytes()
+    restate('p', hyper, probe.fit_ppo_grad(table[2], sigma)[1])
+    b.fit_ppo(table[2:3], sigma, **hyper)
+    assert _same(_blob(b), th['p']), (name, "fit_ppo")
+    # 4. DDPG, two steps in one call: the critic's t = 1, 2, the actor's t = 5, 6 against the updated critic, then the soft update
+    for s in (3, 4):
+        put()
+        restate('q', q_hyper, probe.q_grad(table[s], D.G_GAMMA, D.G_BOUND)[1])
+        put()
+        restate('p', hyper, probe.dpg_grad(table[s], D.G_BOUND)[1])
+        th['tp'], th['tq'] = polyak_reference(th['tp'], th['p'], tau), polyak_reference(th['tq'], th['q'], tau)
+    b.ddpg_fit(table[3:5], D.G_GAMMA, tau, D.G_BOUND, policy_hyper=hyper, q_hyper=q_hyper)
+    assert t == {'p': 6, 'q': 2}
+    for a, k in zip(_states(b), ('p', 'q', 'tp', 'tq')):
+        assert _same(a, th[k]), (name, "ddpg_fit", k)
+    # fit_reset: the next DPG step is the first step of a fresh optimizer
+    b.fit_reset()
+    put()
+    g = probe.dpg_grad(table[5], D.G_BOUND)[1]
+    b.dpg_fit(table[5:6], D.G_BOUND, **hyper)
+    fresh = _restated_step(hyper, th['p'], np.zeros_like(th['p']), np.zeros_like(th['p']), g, 1)[0]
+    assert _same(_blob(b), fresh)
+    restate('p', hyper, g)                                                       # ... and not the seventh of the old one
+    assert not _same(fresh, th['p'])
+    b.close(); probe.close()
+
+
 # ---- 6. the gate freezes ------------------------------------------------------------------------------------------------------------------
 def test_the_gate_freezes_a_policy_pushed_further_out(batch_of):
     """Twelve rows whose means lie beyond +bound under a critic that is linear in the action with positive coefficients: the step up

@@ -87,7 +87,7 @@ def run(args):
 
 
 def launches_per_step(pw, qw, B):
-    """Kernel launches of one clothhip_ddpg_fit step, counted from the order api_fit.hip enqueues (a forward layer is one launch; a
+    """Kernel launches of one clothhip_ddpg_fit step, counted from the order api_fit_ddpg.hip's run_ddpg enqueues (a forward layer is one launch; a
     backward layer is the weight gradient, with B > 256 its slab sum, the bias sum, and below the last layer the input gradient)."""
     Lp, Lq, split = len(pw) - 1, len(qw) - 1, 1 if B > 256 else 0
     back = lambda L: L * (2 + split) + (L - 1)
