@@ -121,6 +121,8 @@ FIT_SRC_SLOTS, FIT_SRC_RESETS, FIT_SRC_HELD = 0, 1, 2   # CLOTHHIP_FIT_SRC_*: wh
 FIT_LABEL_EXPERT, FIT_LABEL_ACTION = 0, 1               # CLOTHHIP_FIT_LABEL_*: where clothhip_fit_data_append_launch_ex takes a row's label from
 FIT_LABELS = {'expert': FIT_LABEL_EXPERT, 'action': FIT_LABEL_ACTION}
 FIT_LABEL_ZERO = 3                                      # ... or (0, 0, 0, 0) from no table at all: how a leaf of the actor-critic is appended
+FIT_LABEL_ACTION_EXPERT = 4                             # ... or the executed action as the label AND the armed expert's into the expert column (DDPG from demonstrations)
+FIT_NO_EXPERT_BITS = 0x7fc00000                         # the expert column's fill: component 0 a NaN means the row has no expert action
 FIT_NEXT_TERMINAL, FIT_NEXT_NONE = -1, -2               # CLOTHHIP_FIT_NEXT_*: a row's successor column besides a dataset index
 GAE_WRITE_WEIGHTS, GAE_NORMALIZE = 1, 2                 # CLOTHHIP_GAE_*: clothhip_fit_data_gae's flags
 assert C.sizeof(ClothFitParams) == 24
@@ -159,6 +161,16 @@ class ClothDdpgParams(C.Structure):
 
 Q_STATS, DPG_STATS, DDPG_STATS = 3, 3, 6      # CLOTHHIP_*_STATS: loss, mean q, mean y; -mean q, gated fraction, mean |dL/da|; both
 assert C.sizeof(ClothDdpgParams) == 24
+
+
+class ClothBcParams(C.Structure):
+    """The constants of DDPG from demonstrations: the coefficients of the policy gradient and of the behaviour-cloning term, BC_* flags, 0."""
+    _fields_ = [("q_coef", C.c_float), ("bc_coef", C.c_float), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+BC_QFILTER = 1                                # CLOTHHIP_BC_QFILTER: the cloning term counts only where the critic rates the expert's action above the policy's
+DPG_BC_STATS, DDPG_BC_STATS = 6, 9            # CLOTHHIP_DPG_BC_STATS: DPG's three, then bc_loss, labelled share, filter-pass share; the critic's three in front
+assert C.sizeof(ClothBcParams) == 16
 
 
 class ClothPlanParams(C.Structure):
@@ -283,6 +295,13 @@ SYMBOLS = [
     ("clothhip_ddpg_polyak", C.c_int, [_vp, C.c_double]),
     ("clothhip_ddpg_last_tables", C.c_int, [_vp, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     ("clothhip_ddpg_fit", C.c_int, [_vp, C.POINTER(ClothFitParams), C.POINTER(ClothFitParams), C.POINTER(ClothDdpgParams), _i32p, C.c_int32, C.c_int32, _dp]),
+    ("clothhip_fit_data_set_expert", C.c_int, [_vp, C.c_int64, C.c_int64, C.POINTER(C.c_float)]),
+    ("clothhip_fit_data_get_expert", C.c_int, [_vp, C.c_int64, C.c_int64, C.POINTER(C.c_float)]),
+    ("clothhip_policy_fit_dpg_bc_grad", C.c_int, [_vp, C.POINTER(ClothDdpgParams), C.POINTER(ClothBcParams), _i32p, C.c_int32, C.POINTER(C.c_float), _dp,
+                                                  C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    ("clothhip_policy_fit_dpg_bc", C.c_int, [_vp, C.POINTER(ClothFitParams), C.POINTER(ClothDdpgParams), C.POINTER(ClothBcParams), _i32p, C.c_int32, C.c_int32, _dp]),
+    ("clothhip_ddpg_fit_bc", C.c_int, [_vp, C.POINTER(ClothFitParams), C.POINTER(ClothFitParams), C.POINTER(ClothDdpgParams), C.POINTER(ClothBcParams), _i32p, C.c_int32,
+                                       C.c_int32, _dp]),
     ("clothhip_plan_cem", C.c_int, [_vp, _vp, C.POINTER(ClothEpisodeParams), C.POINTER(ClothPlanParams), _i32p, _u8p, _dp, _dp, _dp, _dp,
                                     _dp, _dp]),
     ("clothhip_plan_sample", C.c_int, [_vp, C.POINTER(ClothPlanParams), _dp, _dp, C.c_int32, C.c_int32, _dp, _dp, _dp]),

@@ -75,17 +75,20 @@ class FitBindings(object):
         observation is that row of the last launch's tables or of the held rows; the label is row label_row = t * E + e of the last
         armed launch's labels (labels="expert"), or the action that slot of the last launch EXECUTED, (float32)out['actions'][t, e] read
         from the launch's records on the device (labels="action": for policy='mlp' the network's output plus the caller's noise; no
-        expert needed), or with labels="zero" (0, 0, 0, 0) and label_row ignored: a leaf of the actor-critic, appended for its state alone.
+        expert needed), or with labels="zero" (0, 0, 0, 0) and label_row ignored: a leaf of the actor-critic, appended for its state alone,
+        or with labels="action+expert" the executed action as the label AND the armed launch's label into the row's expert column (DDPG
+        from demonstrations: fit_expert, dpg_bc_fit).
         weights [n]: the rows' loss weights, None: 1. ValueError when a named value is not finite (a slot that did not
         run); nothing is appended then. Returns the dataset's size."""
         rows = np.asarray(rows)
         if rows.ndim != 2 or rows.shape[1] != 3 or not np.issubdtype(rows.dtype, np.integer):
             raise ValueError("rows must be integers of shape (n, 3)")
-        if labels != "zero" and labels not in _lib.FIT_LABELS:
-            raise ValueError("labels must be one of %r or 'zero' (got %r)" % (sorted(_lib.FIT_LABELS), labels))
+        other = {"zero": _lib.FIT_LABEL_ZERO, "action+expert": _lib.FIT_LABEL_ACTION_EXPERT}
+        if labels not in other and labels not in _lib.FIT_LABELS:
+            raise ValueError("labels must be one of %r, 'zero' or 'action+expert' (got %r)" % (sorted(_lib.FIT_LABELS), labels))
         rows = np.ascontiguousarray(rows, dtype=np.int32)
         w = self._fit_weights(weights, rows.shape[0])
-        src = _lib.FIT_LABEL_ZERO if labels == "zero" else _lib.FIT_LABELS[labels]
+        src = other[labels] if labels in other else _lib.FIT_LABELS[labels]
         check(self._L.clothhip_fit_data_append_launch_ex(self._h, _lib.i32p(rows), rows.shape[0], src, _lib.fp(w)))
         return self.fit_size()
 
@@ -700,16 +703,106 @@ class FitBindings(object):
         check(self._L.clothhip_ddpg_last_tables(self._h, int(B), _lib.fp(x), _lib.fp(qn), _lib.fp(q)))
         return x, qn, q
 
-    def ddpg_fit(self, idx_table, gamma, tau, act_bound=1.0, policy_hyper=None, q_hyper=None):
+    def ddpg_fit(self, idx_table, gamma, tau, act_bound=1.0, policy_hyper=None, q_hyper=None, bc=None):
         """n_steps DDPG steps in one call (clothhip_ddpg_fit): per step the critic's step on idx_table[s] (int [n_steps, B]), the actor's
         step against the updated critic, the soft update of both targets by tau. policy_hyper and q_hyper are dicts with fit's
         keywords (optimizer, lr, beta1, beta2, eps, momentum). By bytes what q_fit, dpg_fit and ddpg_polyak give one call at a time.
-        Returns float64[n_steps, 6]: the critic's (loss, mean q, mean y), then the actor's (loss, gated fraction, mean |dL/da|)."""
+        Returns float64[n_steps, 6]: the critic's (loss, mean q, mean y), then the actor's (loss, gated fraction, mean |dL/da|).
+        bc = dict(q_coef=, bc_coef=, q_filter=): the actor's step of DDPG from demonstrations (clothhip_ddpg_fit_bc; dpg_bc_fit has
+        the loss); returns float64[n_steps, 9] then, the actor's six behind the critic's three."""
         ix = self._fit_idx(idx_table, 2)
         pp, pq = self._fit_params(policy_hyper, 1), self._fit_params(q_hyper, 1)
         q = self._ddpg_params(gamma, tau, act_bound)
         self._q_params()
         self._fit_n_params()
+        if bc is not None:
+            b = bc_params(**bc)
+            stats = np.zeros((ix.shape[0], _lib.DDPG_BC_STATS), dtype=np.float64)
+            check(self._L.clothhip_ddpg_fit_bc(self._h, pp, pq, C.byref(q), C.byref(b), _lib.i32p(ix), ix.shape[0], ix.shape[1], _lib.dp(stats)))
+            return stats
         stats = np.zeros((ix.shape[0], _lib.DDPG_STATS), dtype=np.float64)
         check(self._L.clothhip_ddpg_fit(self._h, pp, pq, C.byref(q), _lib.i32p(ix), ix.shape[0], ix.shape[1], _lib.dp(stats)))
         return stats
+
+    # ---- DDPG from demonstrations (clothhip.h: DDPG FROM DEMONSTRATIONS; DESIGN 4.3.15) --------------------------------------------------
+    def fit_set_expert(self, actions, first=0):
+        """Write the expert actions of the stored rows [first, first + len(actions)) from the host (clothhip_fit_data_set_expert):
+        actions [n, 4]; a row of four finite float32 sets the row's expert action, a row of four NaNs clears it; a row that mixes the
+        two, or an infinity, is a ValueError and nothing is written (expert_rows)."""
+        a = expert_rows(actions)
+        check(self._L.clothhip_fit_data_set_expert(self._h, int(first), a.shape[0], _lib.fp(a)))
+
+    def fit_expert(self, first=0, n=None):
+        """float32[n, 4]: the expert actions of the stored rows [first, first + n), n=None: to the end (clothhip_fit_data_get_expert);
+        a row without one is four NaNs of the pattern _lib.FIT_NO_EXPERT_BITS (has_expert tells which rows have one)."""
+        first, n = self._fit_range(first, n)
+        a = np.zeros((n, 4), dtype=np.float32)
+        check(self._L.clothhip_fit_data_get_expert(self._h, first, n, _lib.fp(a)))
+        return a
+
+    def dpg_bc_grad(self, idx, act_bound=1.0, q_coef=1.0, bc_coef=0.0, q_filter=True):
+        """dict(stats float64[6] = -mean Q, gated fraction, mean |dL/da|, bc_loss, labelled share, filter-pass share; grad float32[n_params]
+        of the POLICY; da float32[B, 4]; dz float32[B, 4], the dZ of the policy's last layer; q float32[B], the critic on the policy's
+        action; qe float32[B] or None, the critic on the expert's action -- q_filter only) of the actor's loss of DDPG from
+        demonstrations over the dataset rows idx [B]; nothing is updated (clothhip_policy_fit_dpg_bc_grad).
+        references.dpg_bc_reference is the float64 yardstick, dpg_bc_dz_reference the kernel's arithmetic."""
+        ix = self._fit_idx(idx, 1)
+        p, b = self._ddpg_params(0.0, 0.0, act_bound), bc_params(q_coef, bc_coef, q_filter)
+        self._q_params()
+        grad = np.zeros(self._fit_n_params(), dtype=np.float32)
+        stats = np.zeros(_lib.DPG_BC_STATS, dtype=np.float64)
+        da, dz = np.zeros((ix.size, 4), dtype=np.float32), np.zeros((ix.size, 4), dtype=np.float32)
+        q, qe = np.zeros(ix.size, dtype=np.float32), (np.zeros(ix.size, dtype=np.float32) if q_filter else None)
+        check(self._L.clothhip_policy_fit_dpg_bc_grad(self._h, C.byref(p), C.byref(b), _lib.i32p(ix), ix.size, _lib.fp(grad), _lib.dp(stats), _lib.fp(da),
+                                                      _lib.fp(dz), _lib.fp(q), _lib.fp(qe)))
+        return dict(stats=stats, grad=grad, da=da, dz=dz, q=q, qe=qe)
+
+    def dpg_bc_fit(self, idx_table, act_bound=1.0, q_coef=1.0, bc_coef=0.0, q_filter=True, optimizer='adam', lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8,
+                   momentum=0.0):
+        """n_steps optimizer steps of the shared policy network on q_coef (-mean Q(s, clamp(mu(s)))) + bc_coef / (4 B) sum over the rows
+        that carry an expert action (and, q_filter, where Q(s, a_E) > Q(s, mu(s))) of |mu - clamp(a_E)|^2, the critic held fixed
+        (clothhip_policy_fit_dpg_bc). Returns float64[n_steps, 6]."""
+        ix = self._fit_idx(idx_table, 2)
+        p = self._fit_params(dict(optimizer=optimizer, lr=lr, beta1=beta1, beta2=beta2, eps=eps, momentum=momentum), 1)
+        q, b = self._ddpg_params(0.0, 0.0, act_bound), bc_params(q_coef, bc_coef, q_filter)
+        self._q_params()
+        self._fit_n_params()
+        stats = np.zeros((ix.shape[0], _lib.DPG_BC_STATS), dtype=np.float64)
+        check(self._L.clothhip_policy_fit_dpg_bc(self._h, p, C.byref(q), C.byref(b), _lib.i32p(ix), ix.shape[0], ix.shape[1], _lib.dp(stats)))
+        return stats
+
+
+def bc_params(q_coef=1.0, bc_coef=0.0, q_filter=True):
+    """ClothBcParams of the two coefficients (each finite and >= 0 as a float32, not both 0) and the Q-filter."""
+    with np.errstate(over='ignore'):                      # (a double past float32's range becomes inf, refused below)
+        qc, bc = float(np.float32(q_coef)), float(np.float32(bc_coef))
+    if not (np.isfinite(qc) and np.isfinite(bc) and qc >= 0.0 and bc >= 0.0):
+        raise ValueError("q_coef and bc_coef are finite and >= 0 (got %r, %r)" % (q_coef, bc_coef))
+    if qc == 0.0 and bc == 0.0:
+        raise ValueError("q_coef and bc_coef are both 0: the step has no loss")
+    return _lib.ClothBcParams(qc, bc, _lib.BC_QFILTER if q_filter else 0, 0)
+
+
+def expert_rows(actions):
+    """float32[n, 4] as clothhip_fit_data_set_expert stores it: a row of four finite float32 values stays, a row of four NaNs becomes four
+    times the fill pattern _lib.FIT_NO_EXPERT_BITS ("no expert action"); ValueError for another shape, a row that mixes NaN and finite
+    values, or an infinity (as a float32)."""
+    a = np.asarray(actions, dtype=np.float64)
+    if a.ndim != 2 or a.shape[1] != 4:
+        raise ValueError("actions must have shape (n, 4)")
+    with np.errstate(over="ignore"):
+        a = np.ascontiguousarray(a, dtype=np.float32)
+    if np.isinf(a).any():
+        raise ValueError("an expert action is infinite (float32)")
+    nan = np.isnan(a)
+    if (nan.any(axis=1) != nan.all(axis=1)).any():
+        raise ValueError("a row mixes NaN and finite values: a row is four finite values, or four NaNs (no expert action)")
+    bits = a.view(np.uint32).copy()
+    bits[nan] = _lib.FIT_NO_EXPERT_BITS
+    return bits.view(np.float32)
+
+
+def has_expert(actions):
+    """bool[n]: which rows of an expert column float32[n, 4] carry an expert action -- component 0 not a NaN, by its bits."""
+    bits = np.ascontiguousarray(actions, dtype=np.float32).view(np.uint32).reshape(-1, 4)[:, 0]
+    return (bits & np.uint32(0x7fffffff)) <= np.uint32(0x7f800000)

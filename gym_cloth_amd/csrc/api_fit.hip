@@ -139,6 +139,9 @@ static FitLoss ppo_loss(const double *q) { FitLoss l = {}; l.kind = FitLoss::PPO
 static FitLoss ppo_sigma_loss(double lo, double hi, double ent_coef) { FitLoss l = {}; l.kind = FitLoss::PPO_SIGMA; l.stats = FIT_PPO_SIGMA_STATS; l.s = {lo, hi, ent_coef}; return l; }
 FitLoss td_loss(const float *qn, float *y_out, double gamma) { FitLoss l = {}; l.kind = FitLoss::TD; l.stats = FIT_TD_STATS; l.td = {qn, y_out, gamma}; return l; }
 FitLoss dpg_loss(const float *dA, const float *q, float bound) { FitLoss l = {}; l.kind = FitLoss::DPG; l.stats = FIT_DPG_STATS; l.dpg = {dA, q, bound}; return l; }
+FitLoss dpg_bc_loss(const float *dA, const float *q, const float *qe, float bound, float qc, float bc) {
+    FitLoss l = {}; l.kind = FitLoss::DPG_BC; l.stats = FIT_DPG_BC_STATS; l.bc = {dA, q, qe, bound, qc, bc}; return l;
+}
 
 // The launches of one network's step, each over all n_m members: forward, loss, backward. The forward of the present weights over rows
 // d_idx [n_m][B]: member j's y is then at w.act + j * p.act + p.h_off[L - 1].
@@ -167,7 +170,7 @@ int enqueue_forward(clothhip_handle *h, const MlpDesc &D, const FitPlan &p, int3
 }
 // The loss of the forward's y in w and its dZ of the last layer, into w: d_stats [n_m][loss.stats]. The surrogates: d_ratio (may be NULL)
 // [n_m][B]; PPO reads member j's constants from row j of h->fit.d_ppo_q (the caller has uploaded loss.q); PPO_SIGMA reads the handle's
-// log-sigma head where it lies, writes the head's gradient to h->fit.d_grad_ls and the head it read to d_ls (may be NULL). TD and DPG
+// log-sigma head where it lies, writes the head's gradient to h->fit.d_grad_ls and the head it read to d_ls (may be NULL). TD, DPG and DPG_BC
 // (n_m == 1): cloth_fit_ddpg.hpp's one workgroup each
 int enqueue_loss(clothhip_handle *h, const FitNet &net, const FitPlan &p, const FitLoss &loss, int32_t n_m, const int32_t *d_idx, int32_t B, double *d_stats,
                         float *d_ratio, float *d_ls, const FitWork &w) {
@@ -186,6 +189,11 @@ int enqueue_loss(clothhip_handle *h, const FitNet &net, const FitPlan &p, const 
         FitDpgArgs g = {};
         g.dA = loss.dpg.dA; g.y = y; g.q = loss.dpg.q; g.dz = dz; g.stats = d_stats; g.bound = loss.dpg.bound; g.B = B;
         hipLaunchKernelGGL(k_fit_dpg_dz, dim3(1), dim3(FIT_DDPG_THREADS), 0, h->stream, g);
+    } else if (loss.kind == FitLoss::DPG_BC) {
+        FitDpgBcArgs g = {};
+        g.dA = loss.bc.dA; g.y = y; g.q = loss.bc.q; g.qe = loss.bc.qe; g.expert = d.expert(); g.rows = d_idx; g.dz = dz; g.stats = d_stats;
+        g.bound = loss.bc.bound; g.qc = loss.bc.qc; g.bc = loss.bc.bc; g.B = B;
+        hipLaunchKernelGGL(k_fit_dpg_bc, dim3(1), dim3(FIT_DDPG_THREADS), 0, h->stream, g);
     } else if (loss.kind == FitLoss::PPO_SIGMA) {
         FitPpoSigmaArgs q = {};
         q.y = y; q.lab = d.lab(); q.old = d.old(); q.old_ls = d.old_ls(); q.wgt = d.w(); q.ls = h->pol.d_log_sigma; q.rows = d_idx;
@@ -750,6 +758,8 @@ extern "C" int clothhip_value_predict(clothhip_handle *h, const int32_t *idx, in
 
 // ---- DDPG's launches (api_fit_ddpg.hip has the entries and the order; cloth_fit_ddpg.hpp the kernels) ---------------------------------------
 static_assert(FIT_TD_STATS + FIT_DPG_STATS == CLOTHHIP_DDPG_STATS && FIT_TD_STATS == CLOTHHIP_Q_STATS && FIT_DPG_STATS == CLOTHHIP_DPG_STATS, "the statistics of the header and of the kernels");
+static_assert(FIT_DPG_BC_STATS == CLOTHHIP_DPG_BC_STATS && FIT_TD_STATS + FIT_DPG_BC_STATS == CLOTHHIP_DDPG_BC_STATS, "the statistics of the header and of the BC kernel");
+static_assert(FIT_NO_EXPERT == FIT_COL[COL_EXP].fill, "the expert column's fill as the kernels test it");
 static_assert(FIT_NEXT_TERMINAL == CLOTHHIP_FIT_NEXT_TERMINAL, "the terminal mark of the header and of the kernel");
 
 int enqueue_concat(clothhip_handle *h, bool label, const float *act, const int32_t *d_rows, int32_t B, float bound) {
@@ -757,6 +767,13 @@ int enqueue_concat(clothhip_handle *h, bool label, const float *act, const int32
     c.obs = h->dataset.obs(); c.lab = h->dataset.lab(); c.act = act; c.rows = d_rows; c.X = h->fit.d_qx; c.bound = bound; c.B = B; c.L = 3 * h->P;
     if (label) hipLaunchKernelGGL(k_fit_concat<true>, dim3((unsigned)B), dim3(FIT_DDPG_THREADS), 0, h->stream, c);
     else hipLaunchKernelGGL(k_fit_concat<false>, dim3((unsigned)B), dim3(FIT_DDPG_THREADS), 0, h->stream, c);
+    HIPCHECK(hipGetLastError());
+    return 0;
+}
+int enqueue_concat_expert(clothhip_handle *h, const int32_t *d_rows, int32_t B, float bound) {
+    FitConcatArgs c = {};
+    c.obs = h->dataset.obs(); c.lab = h->dataset.expert(); c.rows = d_rows; c.X = h->fit.d_qxe; c.bound = bound; c.B = B; c.L = 3 * h->P;
+    hipLaunchKernelGGL((k_fit_concat<true, true>), dim3((unsigned)B), dim3(FIT_DDPG_THREADS), 0, h->stream, c);
     HIPCHECK(hipGetLastError());
     return 0;
 }

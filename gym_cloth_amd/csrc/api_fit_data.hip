@@ -232,6 +232,34 @@ extern "C" int clothhip_fit_data_get(clothhip_handle *h, int64_t first, int64_t 
     return read_rows(h, first, n, {{COL_OBS, obs}, {COL_LAB, labels}}, true);
 }
 
+// ---- the expert-action column of DDPG from demonstrations (clothhip.h: DDPG FROM DEMONSTRATIONS) ---------------------------------------
+// a row is four finite values, or four NaNs: "no expert action", stored as the column's fill pattern whatever NaN was passed
+extern "C" int clothhip_fit_data_set_expert(clothhip_handle *h, int64_t first, int64_t n, const float *a) {
+    std::vector<uint32_t> bits;
+    auto check = [&] {
+        for (int64_t i = 0; i < n; i++) {
+            int nans = 0;
+            for (int k = 0; k < 4; k++) {
+                const float v = a[4 * i + k];
+                if (std::isinf(v)) return fail(CLOTHHIP_EINVAL, "a[%lld][%d] is infinite", (long long)i, k);
+                nans += std::isnan(v) ? 1 : 0;
+            }
+            if (nans != 0 && nans != 4) return fail(CLOTHHIP_EINVAL, "a[%lld] mixes NaN and finite values: a row is four finite values, or four NaNs (no expert action)", (long long)i);
+            for (int k = 0; k < 4; k++) {
+                if (nans) bits[(size_t)(4 * i + k)] = FIT_COL[COL_EXP].fill;
+                else memcpy(&bits[(size_t)(4 * i + k)], &a[4 * i + k], 4);
+            }
+        }
+        return 0;
+    };
+    // the table uploaded is `bits`, which check() fills: write_rows takes the pointer before it runs check(), so the room is made here,
+    // for a range that write_rows will accept
+    if (h && a && first >= 0 && n > 0 && first <= h->dataset.n && n <= h->dataset.n - first) { try { bits.resize((size_t)n * 4); } catch (const std::bad_alloc &) { return fail(CLOTHHIP_ENOMEM, "out of host memory (%lld rows)", (long long)n); } }
+    return write_rows(h, first, n, {{COL_EXP, a ? (const void *)bits.data() : nullptr}}, check);
+}
+
+extern "C" int clothhip_fit_data_get_expert(clothhip_handle *h, int64_t first, int64_t n, float *a) { return read_rows(h, first, n, {{COL_EXP, a}}); }
+
 // ---- rows named by where they lie on the device (cloth_fit_gather.hpp) ------------------------------------------------------------------
 // One (source, row) of a caller's table against what the handle holds now; the launch tables are valid under launch_table's rule.
 static int check_source(const clothhip_handle *h, int64_t i, int32_t src, int32_t row) {
@@ -258,7 +286,7 @@ static int check_source(const clothhip_handle *h, int64_t i, int32_t src, int32_
 // entry names a label and no weight is written (the held rows), else CLOTHHIP_FIT_LABEL_* and dst_w gets `weights` [n] (host; NULL:
 // ones). Synchronous.
 static int run_gather(clothhip_handle *h, const std::vector<int32_t> &tab, int64_t n, float *dst_obs, float *dst_lab, float *dst_w, int32_t label_src,
-                      const float *weights, bool *bad) {
+                      const float *weights, bool *bad, float *dst_exp = nullptr) {
     auto &d = h->dataset;
     if (int rc = d.d_rows.reserve((size_t)n * 16)) return rc;
     if (int rc = d.d_flag.reserve(4)) return rc;
@@ -271,8 +299,10 @@ static int run_gather(clothhip_handle *h, const std::vector<int32_t> &tab, int64
     FitGatherArgs a = {};
     a.table[FIT_SRC_SLOTS] = (const float *)h->epi.d_fobs; a.table[FIT_SRC_RESETS] = (const float *)h->epi.d_frobs; a.table[FIT_SRC_HELD] = d.d_held;
     a.rows = d.d_rows;
-    a.labels = label_src == CLOTHHIP_FIT_LABEL_EXPERT ? (const double *)h->epi.d_flab : nullptr;
-    a.records = label_src == CLOTHHIP_FIT_LABEL_ACTION ? (const unsigned char *)(const void *)h->epi.d_frec : nullptr;
+    // (ACTION_EXPERT: both tables -- the record's action is the label, the label table's row goes to dst_exp)
+    a.labels = label_src == CLOTHHIP_FIT_LABEL_EXPERT || label_src == CLOTHHIP_FIT_LABEL_ACTION_EXPERT ? (const double *)h->epi.d_flab : nullptr;
+    a.records = label_src == CLOTHHIP_FIT_LABEL_ACTION || label_src == CLOTHHIP_FIT_LABEL_ACTION_EXPERT ? (const unsigned char *)(const void *)h->epi.d_frec : nullptr;
+    a.dst_exp = dst_exp;
     a.weights = weights ? (const float *)d.d_wtab : nullptr;
     a.dst_obs = dst_obs; a.dst_lab = dst_lab; a.dst_w = dst_w; a.flag = d.d_flag; a.n = n; a.L = 3 * h->P;
     HIPCHECK(hipEventRecord(h->ev0, h->stream));
@@ -289,7 +319,7 @@ static int run_gather(clothhip_handle *h, const std::vector<int32_t> &tab, int64
 
 // The refusal of an append whose kernel raised the flag, with clothhip_fit_data_append's message: what the kernel wrote behind the rows
 // that count is read back and searched in that entry's order (observations first, then the rounded labels).
-static int bad_value(clothhip_handle *h, int64_t n) {
+static int bad_value(clothhip_handle *h, int64_t n, bool expert) {
     const size_t row = (size_t)3 * h->P;
     std::vector<float> buf;
     try { buf.resize((size_t)n * std::max<size_t>(row, 4)); } catch (const std::bad_alloc &) { return fail(CLOTHHIP_EINVAL, "an observation or a label is not a finite float"); }
@@ -297,6 +327,10 @@ static int bad_value(clothhip_handle *h, int64_t n) {
     if (int rc = check_obs_rows(buf.data(), n, h->P)) return rc;
     HIPCHECK(hipMemcpy(buf.data(), col_at(h, COL_LAB, h->dataset.n), col_bytes(h, COL_LAB, n), hipMemcpyDeviceToHost));
     if (int rc = check_label_rows(buf.data(), (size_t)n)) return rc;
+    if (expert) {
+        HIPCHECK(hipMemcpy(buf.data(), col_at(h, COL_EXP, h->dataset.n), col_bytes(h, COL_EXP, n), hipMemcpyDeviceToHost));
+        if (int rc = check_finite(buf.data(), n, 4, "expert")) return rc;
+    }
     return fail(CLOTHHIP_EINVAL, "an observation or a label is not a finite float");
 }
 
@@ -340,8 +374,9 @@ static_assert(sizeof(ClothStepRecord) == FIT_REC_BYTES && offsetof(ClothStepReco
 extern "C" int clothhip_fit_data_append_launch_ex(clothhip_handle *h, const int32_t *rows, int64_t n, int32_t label_src, const float *weights) {
     if (!h) return fail(CLOTHHIP_EINVAL, "handle is NULL");
     if (int rc = check_idle(h)) return rc;
-    if (label_src != CLOTHHIP_FIT_LABEL_EXPERT && label_src != CLOTHHIP_FIT_LABEL_ACTION && label_src != CLOTHHIP_FIT_LABEL_ZERO)
-        return fail(CLOTHHIP_EINVAL, "unknown label source %d (CLOTHHIP_FIT_LABEL_EXPERT, CLOTHHIP_FIT_LABEL_ACTION or CLOTHHIP_FIT_LABEL_ZERO)", label_src);
+    const bool both = label_src == CLOTHHIP_FIT_LABEL_ACTION_EXPERT;      // the executed action as the label AND the expert's into its column
+    if (label_src != CLOTHHIP_FIT_LABEL_EXPERT && label_src != CLOTHHIP_FIT_LABEL_ACTION && label_src != CLOTHHIP_FIT_LABEL_ZERO && !both)
+        return fail(CLOTHHIP_EINVAL, "unknown label source %d (CLOTHHIP_FIT_LABEL_EXPERT, CLOTHHIP_FIT_LABEL_ACTION, CLOTHHIP_FIT_LABEL_ZERO or CLOTHHIP_FIT_LABEL_ACTION_EXPERT)", label_src);
     const bool zero = label_src == CLOTHHIP_FIT_LABEL_ZERO;      // no label table is read: label_row is ignored (the kernel is told row 0 of no table)
     if (n < 0) return fail(CLOTHHIP_EINVAL, "n < 0");
     if (n == 0) return 0;
@@ -350,6 +385,11 @@ extern "C" int clothhip_fit_data_append_launch_ex(clothhip_handle *h, const int3
     if (d.n + n > INT32_MAX) return fail(CLOTHHIP_EINVAL, "%lld + %lld rows: a minibatch names its rows by int32", (long long)d.n, (long long)n);
     int64_t n_lab = 0;
     if (!zero) if (int rc = launch_table(h, label_src == CLOTHHIP_FIT_LABEL_ACTION ? LaunchTable::records : LaunchTable::labels, nullptr, &n_lab)) return rc;
+    if (both) {      // (both tables have T * E rows)
+        int64_t n_rec = 0;
+        if (int rc = launch_table(h, LaunchTable::records, nullptr, &n_rec)) return rc;
+        n_lab = std::min(n_lab, n_rec);
+    }
     if (int rc = check_weights(weights, n)) return rc;
     std::vector<int32_t> tab;
     try { tab.resize((size_t)n * 4); } catch (const std::bad_alloc &) { return fail(CLOTHHIP_ENOMEM, "out of host memory (%lld rows)", (long long)n); }
@@ -364,8 +404,8 @@ extern "C" int clothhip_fit_data_append_launch_ex(clothhip_handle *h, const int3
     if (int rc = default_rows(h, n)) return rc;
     // the kernel writes behind the n rows that count; they count only if every value it wrote is finite
     bool bad = false;
-    if (int rc = run_gather(h, tab, n, d.obs(), d.lab(), d.w(), label_src, weights, &bad)) return rc;
-    if (bad) return bad_value(h, n);
+    if (int rc = run_gather(h, tab, n, d.obs(), d.lab(), d.w(), label_src, weights, &bad, both ? d.expert() : nullptr)) return rc;
+    if (bad) return bad_value(h, n, both);      // (what was written lies behind the rows that count: the next append's defaults overwrite it)
     d.n += n;
     return 0;
 }

@@ -55,11 +55,11 @@ struct LaunchRecord {
 enum class LaunchTable { obs, reset_obs, labels, records };
 
 // The columns of the trainer's dataset (clothhip_handle::FitData), each a device table of 4-byte elements, float or int32: obs [3P], the
-// label [4], the loss weight, the reward, the value target, the successor row (or CLOTHHIP_FIT_NEXT_*), PPO's old mean [4] and its old log sigma [4]. A column is
+// label [4], the loss weight, the reward, the value target, the successor row (or CLOTHHIP_FIT_NEXT_*), PPO's old mean [4] and its old log sigma [4], the expert's action [4] of DDPG from demonstrations. A column is
 // described HERE and nowhere else: its width in elements per row (per_particle * P + fixed), and whether a new row gets a default -- the
 // 32-bit pattern `fill` -- or is written by every append. A new column is one enumerator plus one entry, plus whatever reads it: growth,
 // the defaults, clear and the range reader and writer of api_fit_data.hip are loops over this table and name no column.
-enum FitCol { COL_OBS, COL_LAB, COL_W, COL_REW, COL_RET, COL_NEXT, COL_OLD, COL_OLD_LS, FIT_COLS };
+enum FitCol { COL_OBS, COL_LAB, COL_W, COL_REW, COL_RET, COL_NEXT, COL_OLD, COL_OLD_LS, COL_EXP, FIT_COLS };
 struct FitColDesc {
     int per_particle, fixed;
     bool defaulted;
@@ -75,6 +75,7 @@ constexpr FitColDesc FIT_COL[] = {
     {0, 1, true, (uint32_t)CLOTHHIP_FIT_NEXT_NONE},       // COL_NEXT: no successor, a leaf
     {0, 4, true, 0},                                      // COL_OLD: zeros, and not set (FitData::h_old_set)
     {0, 4, true, 0},                                      // COL_OLD_LS: zeros, and not set (FitData::h_old_ls_set)
+    {0, 4, true, 0x7fc00000u},                            // COL_EXP: four quiet NaNs, "this row has no expert action" (a row holds four finite values or four of these)
 };
 static_assert(sizeof(FIT_COL) / sizeof(FIT_COL[0]) == FIT_COLS, "one description per column");
 
@@ -235,6 +236,7 @@ struct clothhip_handle : HostPlan {
         int32_t *next() const { return (int32_t *)col[COL_NEXT]; }
         float *old() const { return (float *)col[COL_OLD]; }
         float *old_ls() const { return (float *)col[COL_OLD_LS]; }
+        float *expert() const { return (float *)col[COL_EXP]; }
         // host mirrors [n] that grow and clear with the rows: of `next`, against which clothhip_fit_data_gae checks a range without a
         // download, and one byte per row and old column: whether its old mean / its old log sigma has been written -- against which
         // clothhip_policy_fit_ppo* (the first) and clothhip_policy_fit_ppo_sigma* (both) check a minibatch
@@ -266,11 +268,13 @@ struct clothhip_handle : HostPlan {
         struct Pass { Buffer<float> d_act, d_dz, d_part, d_grad; } own, qpass;
         // DDPG's other scratch: the critic's input rows X [B][3P + 4], dL/da [B][4], the TD targets y [B], the successor rows of a minibatch
         Buffer<float> d_qx, d_da, d_tdy;
+        Buffer<float> d_qxe;         // the BC actor's step under the Q-filter: the critic's input rows on the expert's action, X_E [B][3P + 4]
         Buffer<int32_t> d_succ;
         // what the last DDPG call left in that scratch, for clothhip_ddpg_last_tables: its B (0: nothing), whether it ran the
         // critic (the target critic's values are then there), and where in qpass.d_act the target critic's and the critic's outputs lie
         int32_t ddpg_B = 0;
         bool ddpg_critic = false;
+        bool ddpg_x_expert = false;  // the last call was a BC actor's step under the Q-filter: clothhip_ddpg_last_tables' X is d_qxe
         size_t ddpg_qn_at = 0, ddpg_q_at = 0;
         // one call's tables, sized on demand: the index table, the losses; the call's member rows and its table of per-target, per-step,
         // per-member optimizer constants

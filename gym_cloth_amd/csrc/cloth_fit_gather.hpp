@@ -34,6 +34,8 @@ struct FitGatherArgs {
     const float *weights;       // [n] the destination rows' loss weights in entry order, or NULL: 1.0f
     float *dst_obs, *dst_lab;   // destination tables [..][L], [..][4] (dst_lab may be NULL then)
     float *dst_w;               // [..] (NULL: no weight is written -- the held rows have none)
+    float *dst_exp;             // [..][4] the expert-action column, or NULL (every source but CLOTHHIP_FIT_LABEL_ACTION_EXPERT): with it `records` AND
+                                // `labels` are there, the label is the record's and this gets (float)labels[label row][0..3]
     int32_t *flag;              // raised (integer atomic OR) when a copied observation value or a rounded label is not finite, or a
                                 // named record did not run (its label is then stored as NaN, the label of a slot that did not run)
     int64_t n;
@@ -78,6 +80,11 @@ __global__ __launch_bounds__(FIT_GATHER_THREADS) void k_fit_gather(FitGatherArgs
             bad |= fit_not_finite(lv);
         }
         if (a.dst_w && tid == 4) a.dst_w[drow] = a.weights ? a.weights[r] : 1.0f;      // (another lane than the labels': no second pass)
+        if (a.dst_exp && lrow >= 0 && tid >= 8 && tid < 12) {      // (and four more lanes: the expert's action beside the executed one)
+            const float ev = (float)a.labels[(int64_t)lrow * 4 + (tid - 8)];
+            a.dst_exp[(int64_t)drow * 4 + (tid - 8)] = ev;
+            bad |= fit_not_finite(ev);
+        }
     }
     if (bad) atomicOr(a.flag, 1);
 }

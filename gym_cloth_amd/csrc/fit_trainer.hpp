@@ -52,19 +52,21 @@ struct FitWork { float *act, *dz, *part, *grad; const float *x; };
 FitWork fit_work(const clothhip_handle::Fit::Pass &t, const float *x = nullptr);
 
 // What a step minimises, with the fields that loss reads and no others. The width of the squared error comes from FitNet; both
-// surrogates and DPG are the policy's table only, TD the Q network's. A new loss is one more kind, its fields, and its case in enqueue_loss.
+// surrogates, DPG and DPG_BC are the policy's table only, TD the Q network's. A new loss is one more kind, its fields, and its case in enqueue_loss.
 struct FitLoss {
-    enum Kind { SQUARED_ERROR, PPO, PPO_SIGMA, TD, DPG } kind;
+    enum Kind { SQUARED_ERROR, PPO, PPO_SIGMA, TD, DPG, DPG_BC } kind;
     int stats;                                      // doubles per member and step in the loss table: the loss, or the loss's statistics
     union {
         const double *q;                            // PPO: host [n_m][4] {inv_s2, half_inv_s2, lo, hi}, row j member j's (check_ppo makes it)
         struct { double lo, hi, ent_coef; } s;      // PPO_SIGMA: 1 - eps, 1 + eps and the entropy coefficient; 1 / sigma^2 comes from the head
         struct { const float *qn; float *y_out; double gamma; } td;      // TD: the target critic's values [B], where y [B] goes, the discount
         struct { const float *dA, *q; float bound; } dpg;                // DPG: dL/da [B][4], the critic's output this pass [B], the action bound
+        struct { const float *dA, *q, *qe; float bound, qc, bc; } bc;    // DPG_BC: DPG's, the critic on the expert's action [B] (NULL: no Q-filter), q_coef and bc_coef
     };
 };
 FitLoss td_loss(const float *qn, float *y_out, double gamma);
 FitLoss dpg_loss(const float *dA, const float *q, float bound);
+FitLoss dpg_bc_loss(const float *dA, const float *q, const float *qe, float bound, float qc, float bc);
 
 // Where a call's results go on the host, each NULL when the caller does not want it: loss [n_steps][n_m][stats]; of a gradient call grad
 // [n_m][n_params], ratio [n_m][B] (the surrogates), grad_ls [4] (PPO_SIGMA); of a PPO_SIGMA fit ls [n_steps][4], the head before each update
@@ -79,6 +81,7 @@ int enqueue_action_grad(clothhip_handle *h, const MlpDesc &D, const FitPlan &p, 
 int enqueue_predict(clothhip_handle *h, const FitNet &net, const int32_t *members, int32_t n_m, const int32_t *idx, int64_t n, float *dst);
 // cloth_fit_ddpg.hpp's k_fit_concat and k_fit_polyak, and cloth_policy_fit.hpp's k_fit_fill_ls over n4 floats
 int enqueue_concat(clothhip_handle *h, bool label, const float *act, const int32_t *d_rows, int32_t B, float bound);
+int enqueue_concat_expert(clothhip_handle *h, const int32_t *d_rows, int32_t B, float bound);      // k_fit_concat's expert mode, into h->fit.d_qxe
 int enqueue_polyak(clothhip_handle *h, double tau);
 int enqueue_fill_ls(clothhip_handle *h, float *dst, int64_t n4);
 

@@ -476,7 +476,8 @@ def episode_links(row_env, row_slot, done, n_envs, first):
     return nxt.astype(np.int32)
 
 
-def actor_critic_collect(env, trainer, n_actions=12, policy_noise=None, slots_per_launch=12, time_budget_ms=0.0, max_launches=None):
+def actor_critic_collect(env, trainer, n_actions=12, policy_noise=None, slots_per_launch=12, time_budget_ms=0.0, max_launches=None, expert=None, beta=0.0,
+                         seed=0, expert_choices=None):
     """Collect rows for an ACTOR-CRITIC step: reward_collect's loop (labels = the action the slot executed, weight 0), which also
     writes the transitions. Per launch the rows that ran are appended where they lie; and where an env's LAST collected slot (its slot
     n_actions - 1) left its episode open, the state after that slot -- row t * E + e of that launch's observation table -- is appended
@@ -486,10 +487,23 @@ def actor_critic_collect(env, trainer, n_actions=12, policy_noise=None, slots_pe
     rew float32[n], next int32[n]: the env, per-env slot number (a leaf: n_actions), kind, reward and successor of every appended row
     in DATASET order (n = appended + open_rows), open_rows: the leaves, nonleaf int[appended]: the dataset indices of the other rows,
     episode_return float64[episodes]: the undiscounted return from the first collected slot of every episode that completed,
-    t_append / t_set_transitions: seconds in those calls. Nothing is trained here: actor_critic_fit below does."""
+    t_append / t_set_transitions: seconds in those calls. Nothing is trained here: actor_critic_fit below does.
+    expert (a name as dagger_collect takes it; None: none): the launches are ARMED as dagger_collect arms them -- the expert labels
+    every state the learner reaches and takes the action over where dagger_mixture(n_actions, E, beta, seed) says so (beta = 1: pure
+    demonstrations; expert_choices [n_actions, E] as there) -- and the rows are appended with labels="action+expert": the executed action
+    as the label, the expert's into the row's expert column (DDPG from demonstrations: ddpg_fit(bc_coef=...)). Leaves stay
+    labels="zero" and carry no expert action."""
     import time
     from ._lib import FIT_SRC_SLOTS
     first, N, E = trainer.size(), int(n_actions), env.E
+    row_labels, launch_kw, keys = "action", (lambda idx, ee: {}), ('reset_before',)
+    if expert is not None:
+        mix = dagger_mixture(N, E, beta, seed)
+        choices = None if expert_choices is None else np.asarray(expert_choices)
+        if choices is not None and choices.shape != (N, E):
+            raise ValueError("expert_choices must have shape (%d, %d)" % (N, E))
+        row_labels, keys = "action+expert", ('reset_before', 'expert_took')
+        launch_kw = lambda idx, ee: dict(expert=expert, expert_mix=mix[idx, ee], expert_choices=None if choices is None else choices[idx, ee])
     spent = {'append': 0.0}
     cols = {'env': [], 'slot': [], 'leaf': [], 'done': [], 'rew': []}
 
@@ -498,7 +512,7 @@ def actor_critic_collect(env, trainer, n_actions=12, policy_noise=None, slots_pe
         done = np.asarray(out['done'], dtype=bool)[t_, e_]
         open_ = (slot == N - 1) & ~done
         t0 = time.perf_counter()
-        trainer.append_launch(rows, labels="action", weights=np.zeros(len(rows), dtype=np.float32))
+        trainer.append_launch(rows, labels=row_labels, weights=np.zeros(len(rows), dtype=np.float32))
         if open_.any():
             leaves = np.stack([np.full(int(open_.sum()), FIT_SRC_SLOTS), rows[open_, 2], np.zeros(int(open_.sum()), dtype=np.int64)], axis=1)
             trainer.append_launch(leaves, labels="zero", weights=np.zeros(len(leaves), dtype=np.float32))
@@ -509,8 +523,7 @@ def actor_critic_collect(env, trainer, n_actions=12, policy_noise=None, slots_pe
         cols['done'] += [done, np.zeros(k, dtype=bool)]
         cols['rew'] += [np.asarray(out['rew'], dtype=np.float64)[t_, e_], np.zeros(k)]
 
-    res = _collect_loop(env, trainer, N, slots_per_launch, time_budget_ms, policy_noise, max_launches, lambda idx, ee: {}, append,
-                        ('reset_before',))
+    res = _collect_loop(env, trainer, N, slots_per_launch, time_budget_ms, policy_noise, max_launches, launch_kw, append, keys)
     cat = lambda k, dt: np.concatenate(cols[k]).astype(dt) if cols[k] else np.zeros(0, dtype=dt)
     ds_env, ds_slot, leaf, done, rew = cat('env', np.int64), cat('slot', np.int64), cat('leaf', bool), cat('done', bool), cat('rew', np.float32)
     nxt = episode_links(ds_env, ds_slot, done, E, first)
@@ -544,7 +557,31 @@ def actor_critic_fit(env, trainer, critic, col, gamma=0.99, lam=0.95, n_value_st
     return {'adv': adv, 'ret': ret, 'value_losses': vl, 'policy_losses': pl, 'rows': trainer.size()}
 
 
-def ddpg_fit(env, trainer, qcritic, col, gamma=0.99, tau=0.005, n_steps=100, batch_size=64, seed=0, act_bound=1.0):
+def demo_table(replay, labelled, n_steps, batch_size, seed, demo_fraction=None):
+    """The minibatches of ddpg_fit, int32[n_steps, batch_size] dataset rows, a pure function of its arguments: replay int[m] the rows
+    with a transition, labelled int[k] those of them that carry an expert action. demo_fraction None: replay[MLPTrainer.index_table(m,
+    n_steps, batch_size, seed)], what ddpg_fit always drew. Else the first floor(demo_fraction * batch_size) positions of every
+    minibatch are labelled[RandomState(seed + 1).randint(0, k, ...)] and the others are the corresponding positions of that table.
+    ValueError for a fraction outside [0, 1], or when there are no labelled rows."""
+    from .trainers import MLPTrainer
+    replay, labelled = np.asarray(replay).reshape(-1), np.asarray(labelled).reshape(-1)
+    table = replay.astype(np.int32)[MLPTrainer.index_table(replay.size, n_steps, batch_size, seed)]
+    if demo_fraction is None:
+        return table
+    if not 0.0 <= float(demo_fraction) <= 1.0:
+        raise ValueError("demo_fraction must lie in [0, 1] (got %r)" % (demo_fraction,))
+    if labelled.size < 1:
+        raise ValueError("demo_fraction is set and no row with a transition carries an expert action: collect with an expert first")
+    k = int(np.floor(float(demo_fraction) * int(batch_size)))
+    if k > 0:
+        pick = np.random.RandomState(int(seed) + 1).randint(0, labelled.size, size=(int(n_steps), k))
+        table = table.copy()
+        table[:, :k] = labelled.astype(np.int32)[pick]
+    return table
+
+
+def ddpg_fit(env, trainer, qcritic, col, gamma=0.99, tau=0.005, n_steps=100, batch_size=64, seed=0, act_bound=1.0, q_coef=1.0, bc_coef=0.0, q_filter=True,
+             demo_fraction=None):
     """The refit after actor_critic_collect under DDPG, on the device: n_steps steps of MLPTrainer.ddpg_step with
     `qcritic` (policies.QTrainer on `env`), each a TD step of the critic, a step of the policy up the critic's action gradient and the
     soft update of both targets. The minibatches are drawn from the non-leaf rows of the WHOLE dataset -- the replay buffer: rows of
@@ -552,8 +589,13 @@ def ddpg_fit(env, trainer, qcritic, col, gamma=0.99, tau=0.005, n_steps=100, bat
     first use of this (trainer, qcritic) pair and whenever a new network dropped one. `col` is the collection that was just added (only
     its row count is reported). Returns dict(stats float64[n_steps, 6]: the critic's loss, mean q, mean y, then the actor's loss,
     gated fraction, mean |dL/da| of every step before its update; rows int32[n_steps, B]: the minibatches; replay: the non-leaf
-    rows sampled from; synced: whether this call synced the targets)."""
+    rows sampled from; synced: whether this call synced the targets).
+    bc_coef != 0 or q_coef != 1: the actor's step is that of DDPG from demonstrations (MLPTrainer.ddpg_step) and stats
+    is float64[n_steps, 9]: behind the critic's three the actor's -mean q, gated fraction, mean |dL/da|, bc_loss, labelled share and
+    filter-pass share. demo_fraction: that share of every minibatch, rounded down, is drawn from the non-leaf rows that carry an
+    expert action (demo_table; ValueError when there are none); the dict then also has labelled: those rows."""
     from ._lib import FIT_NEXT_NONE, ClothHipError
+    from .batch_fit import has_expert
     if trainer.env is not env or qcritic.env is not env:
         raise ValueError("the trainer or the Q critic belongs to another env")
     replay = np.nonzero(env.batch.fit_get_transitions()[1] != FIT_NEXT_NONE)[0]
@@ -565,9 +607,16 @@ def ddpg_fit(env, trainer, qcritic, col, gamma=0.99, tau=0.005, n_steps=100, bat
     except ClothHipError:
         qcritic.sync_targets()
         synced = True
-    table = replay.astype(np.int32)[trainer.index_table(replay.size, n_steps, batch_size, seed)]
-    stats = env.batch.ddpg_fit(table, gamma, tau, act_bound, policy_hyper=trainer.hyper, q_hyper=qcritic.hyper)
-    return {'stats': stats, 'rows': table, 'replay': replay, 'synced': synced, 'collected': int(col['appended']) if col is not None else 0}
+    labelled = None
+    if demo_fraction is not None:
+        labelled = replay[has_expert(env.batch.fit_expert())[replay]]
+    table = demo_table(replay, labelled if labelled is not None else replay[:0], n_steps, batch_size, seed, demo_fraction)
+    stats = trainer.ddpg_step(qcritic, n_steps, batch_size, seed, gamma=gamma, tau=tau, act_bound=act_bound, q_coef=q_coef, bc_coef=bc_coef,
+                              q_filter=q_filter, table=table)
+    res = {'stats': stats, 'rows': table, 'replay': replay, 'synced': synced, 'collected': int(col['appended']) if col is not None else 0}
+    if labelled is not None:
+        res['labelled'] = labelled
+    return res
 
 
 def ppo_fit(env, trainer, critic, col, sigma=None, gamma=0.99, lam=0.95, clip=0.2, n_value_steps=100, n_epochs=10, batch_size=64, seed=0,

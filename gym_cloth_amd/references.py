@@ -180,14 +180,92 @@ def dpg_reference(policy_layers, q_layers, obs, idx, act_bound=np.inf):
     return stats, mlp_backward(Wp, hp, np.where(gated, 0.0, dA)), dA
 
 
-def concat_reference(obs, act, idx, act_bound=np.inf):
+def concat_reference(obs, act, idx, act_bound=np.inf, expert=False):
     """k_fit_concat restated, bit for bit: float32 [B, 3P + 4] = [obs[idx], min(max(act, -bound), +bound)]; act float32 [B, 4] is one
-    action per minibatch row -- the label column at idx (the critic's step), or a network's output on the minibatch."""
+    action per minibatch row -- the label column at idx (the critic's step), or a network's output on the minibatch. expert: act is
+    the EXPERT column at idx, and a row without an expert action (component 0 a NaN by its bits) gets four +0.0 by a select, whatever
+    its other components hold."""
     ix = np.asarray(idx, dtype=np.int64).reshape(-1)
     x, a = np.asarray(obs, dtype=np.float32), np.asarray(act, dtype=np.float32)
     if a.shape != (len(ix), 4):
         raise ValueError("act must hold one action per minibatch row: shape (%d, 4)" % len(ix))
-    return np.concatenate([x[ix], _clamp(a, act_bound).astype(np.float32)], axis=1)
+    with np.errstate(invalid='ignore'):
+        c = _clamp(a, act_bound).astype(np.float32)
+    if expert:
+        c = np.where(expert_mask(a)[:, None], c, np.float32(0.0)).astype(np.float32)
+    return np.concatenate([x[ix], c], axis=1)
+
+
+def expert_mask(a):
+    """bool [B]: which rows of an expert column float32 [B, 4] carry an expert action -- the device's test on the bits of component 0:
+    (bits & 0x7fffffff) > 0x7f800000 means none."""
+    bits = np.ascontiguousarray(np.asarray(a, dtype=np.float32)[:, 0]).view(np.uint32)
+    return (bits & np.uint32(0x7fffffff)) <= np.uint32(0x7f800000)
+
+
+def dpg_bc_dz_reference(dA, y, q, qe, expert, act_bound=np.inf, q_coef=1.0, bc_coef=0.0):
+    """k_fit_dpg_bc restated in numpy float32 / float64, bit for bit, reduction order included: dA float32 [B, 4], y float32 [B, 4] the
+    policy's output, q float32 [B] the critic on the policy's action, qe float32 [B] the critic on the expert's (None: no Q-filter),
+    expert float32 [B, 4] the expert column at the minibatch rows. Returns (dz float32[B, 4], stats float64[6] = -mean q, gated
+    fraction, mean |dA|, bc_loss, labelled share, filter-pass share)."""
+    g, mu = np.asarray(dA, dtype=np.float32), np.asarray(y, dtype=np.float32)
+    q32, ae = np.asarray(q, dtype=np.float32).reshape(-1), np.asarray(expert, dtype=np.float32)
+    b, qc, bc = np.float32(act_bound), np.float32(q_coef), np.float32(bc_coef)
+    B = len(g)
+    m = expert_mask(ae)
+    f = m.copy() if qe is None else (m & (np.asarray(qe, dtype=np.float32).reshape(-1) > q32))
+    gated = ((mu >= b) & (g < 0.0)) | ((mu <= -b) & (g > 0.0))
+    with np.errstate(invalid='ignore', over='ignore'):
+        a = (qc * np.where(gated, np.float32(0.0), g).astype(np.float32)).astype(np.float32)
+        e = np.where(f[:, None], np.minimum(np.maximum(ae, -b), b), np.float32(0.0)).astype(np.float32)
+        d = (mu - e).astype(np.float32)
+        bt = ((bc * d).astype(np.float32) / np.float32(2 * B)).astype(np.float32)
+        clone = f[:, None] & (bc != 0.0)
+        dz = np.where(clone, (a + bt).astype(np.float32), a).astype(np.float32)      # (elsewhere NO addition: the sign of a zero survives)
+        dd = mu.astype(np.float64) - e.astype(np.float64)
+    sq = np.where(f[:, None], dd * dd, 0.0)
+    stats = np.array([-_house_sum(q32.astype(np.float64)) / float(B), _house_sum_rows(gated.astype(np.float64)) / float(4 * B),
+                      _house_sum_rows(np.abs(g).astype(np.float64)) / float(4 * B), _house_sum_rows(sq) / float(4 * B),
+                      _house_sum(m.astype(np.float64)) / float(B), _house_sum(f.astype(np.float64)) / float(B)])
+    return dz, stats
+
+
+def dpg_bc_reference(policy_layers, q_layers, obs, expert, idx, act_bound=np.inf, q_coef=1.0, bc_coef=0.0, q_filter=True, mask=None):
+    """Pure-numpy float64 loss and gradient of the actor's step of DDPG from demonstrations (clothhip_policy_fit_dpg_bc_grad):
+        L = q_coef (-1 / B sum_r Q(s_r, clamp(mu(s_r)))) + bc_coef / (4 B) sum_{r: f_r} sum_k (mu_rk - clamp(a_E_rk))^2
+    over the policy's weights, the critic fixed; f_r = the row carries an expert action (expert [n, 4], the dataset's column) and,
+    q_filter, Q(s_r, clamp(a_E_r)) > Q(s_r, clamp(mu(s_r))), decided from the float64 values (mask [B] bool: f given, held fixed --
+    for finite differences). No gradient flows through f or the expert's action; the policy-gradient term's dz is dpg_reference's
+    gate. Returns dict(loss, stats [6] = -mean Q, gated fraction, mean |dA|, bc_loss, labelled share, filter-pass share; grads
+    [(dW, db), ...] of the policy; dA, dz [B, 4]; q, qe [B] (qe None without the filter); m, f bool [B])."""
+    ix = np.asarray(idx, dtype=np.int64).reshape(-1)
+    x = np.asarray(obs, dtype=np.float32).astype(np.float64)[ix]
+    ae32 = np.asarray(expert, dtype=np.float32)[ix]
+    B, b = len(ix), float(np.float32(act_bound))
+    qc, bc = float(np.float32(q_coef)), float(np.float32(bc_coef))
+    m = expert_mask(ae32)
+    e = np.where(m[:, None], _clamp(np.where(m[:, None], ae32, np.float32(0.0)).astype(np.float64), act_bound), 0.0)
+    Wp, bp = mlp_float64(policy_layers)
+    hp = mlp_forward(Wp, bp, x)
+    mu = hp[-1]
+    Wq, bq = mlp_float64(q_layers)
+    hq = mlp_forward(Wq, bq, np.concatenate([x, _clamp(mu, act_bound)], axis=1))
+    q = hq[-1][:, 0]
+    qe = mlp_forward(Wq, bq, np.concatenate([x, e], axis=1))[-1][:, 0] if q_filter else None
+    if mask is not None:
+        f = np.asarray(mask, dtype=bool).reshape(-1) & m
+    else:
+        f = m & (qe > q) if q_filter else m.copy()
+    g = np.full((B, 1), -1.0 / B)
+    for l in range(len(Wq) - 1, 0, -1):
+        g = (g @ Wq[l]) * (hq[l] > 0.0)
+    dA = (g @ Wq[0])[:, -4:]
+    gated = ((mu >= b) & (dA < 0.0)) | ((mu <= -b) & (dA > 0.0))
+    diff = np.where(f[:, None], mu - e, 0.0)
+    bc_loss = (diff * diff).sum() / (4.0 * B)
+    dz = qc * np.where(gated, 0.0, dA) + bc * diff / (2.0 * B)
+    stats = np.array([-q.sum() / B, gated.sum() / (4.0 * B), np.abs(dA).sum() / (4.0 * B), bc_loss, m.sum() / float(B), f.sum() / float(B)])
+    return dict(loss=qc * stats[0] + bc * bc_loss, stats=stats, grads=mlp_backward(Wp, hp, dz), dA=dA, dz=dz, q=q, qe=qe, m=m, f=f)
 
 
 def td_loss_reference(q, qn, rew, next, gamma):

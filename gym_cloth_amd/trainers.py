@@ -179,22 +179,30 @@ class MLPTrainer(_EnvDataset):
             self.last_log_sigma = np.concatenate(heads) if heads else np.zeros((0, 4), dtype=np.float32)
         return (np.concatenate(out) if out else np.zeros((0, 3 if sigma is not None else 4))), epochs
 
-    def ddpg_step(self, qcritic, n_steps, batch_size, seed, gamma=0.99, tau=0.005, act_bound=1.0, rows=None):
+    def ddpg_step(self, qcritic, n_steps, batch_size, seed, gamma=0.99, tau=0.005, act_bound=1.0, rows=None, q_coef=1.0, bc_coef=0.0, q_filter=True,
+                  table=None):
         """n_steps DDPG steps on the device in ONE call (ClothBatch.ddpg_fit): per step the TD step of `qcritic` (a
         QTrainer on the same env), this network's step up the critic's action gradient, the soft update of both targets -- under this
         trainer's optimizer for the policy and qcritic's for the critic. The minibatches are index_table(m, n_steps, batch_size, seed)
         over `rows` (int [m] dataset rows WITH a transition; None: every non-leaf row of the dataset, old collections included). The
         targets must have been synced (qcritic.sync_targets). Returns float64[n_steps, 6]: the critic's (loss, mean q, mean y), then
-        the actor's (loss = -mean q, gated fraction, mean |dL/da|), each before its update."""
+        the actor's (loss = -mean q, gated fraction, mean |dL/da|), each before its update.
+        bc_coef != 0 or q_coef != 1: the actor's step of DDPG from demonstrations (ClothBatch.dpg_bc_fit has the loss),
+        q_filter: its Q-filter; returns float64[n_steps, 9] then, the actor's six behind the critic's three. bc_coef == 0 with
+        q_coef == 1 takes the plain path, whatever q_filter says. table (int [n_steps, batch_size] dataset rows): the minibatches
+        themselves, in the place of rows and seed."""
         if qcritic.env is not self.env:
             raise ValueError("the Q critic belongs to another env")
+        bc = None if (float(bc_coef) == 0.0 and float(q_coef) == 1.0) else dict(q_coef=q_coef, bc_coef=bc_coef, q_filter=q_filter)
+        if table is not None:
+            return self.env.batch.ddpg_fit(np.asarray(table), gamma, tau, act_bound, policy_hyper=self.hyper, q_hyper=qcritic.hyper, bc=bc)
         if rows is None:
             rows = np.nonzero(self.env.batch.fit_get_transitions()[1] != _lib.FIT_NEXT_NONE)[0]
             if rows.size < 1:
                 raise ValueError("the dataset holds no row with a transition: collect first")
         rows = _check_rows(rows)
         table = rows.astype(np.int32)[self.index_table(rows.size, n_steps, batch_size, seed)]
-        return self.env.batch.ddpg_fit(table, gamma, tau, act_bound, policy_hyper=self.hyper, q_hyper=qcritic.hyper)
+        return self.env.batch.ddpg_fit(table, gamma, tau, act_bound, policy_hyper=self.hyper, q_hyper=qcritic.hyper, bc=bc)
 
     def layers(self):
         """The network as the device holds it now: [(W, b), ...] float32, by download (clothhip_get_policy_mlp)."""

@@ -517,7 +517,8 @@ int clothhip_fit_data_append_weighted(clothhip_handle *h, const float *obs_rows,
  * The refusals are those above; besides, CLOTHHIP_ESTATE for LABEL_ACTION with no launch since creation (or none whose record table
  * is still there), CLOTHHIP_EINVAL for an unknown label_src or a non-finite weight. */
 enum { CLOTHHIP_FIT_SRC_SLOTS = 0, CLOTHHIP_FIT_SRC_RESETS = 1, CLOTHHIP_FIT_SRC_HELD = 2 };
-enum { CLOTHHIP_FIT_LABEL_EXPERT = 0, CLOTHHIP_FIT_LABEL_ACTION = 1, CLOTHHIP_FIT_LABEL_ZERO = 3 /* ACTOR-CRITIC below; 2 names no source and stays refused */ };
+enum { CLOTHHIP_FIT_LABEL_EXPERT = 0, CLOTHHIP_FIT_LABEL_ACTION = 1, CLOTHHIP_FIT_LABEL_ZERO = 3 /* ACTOR-CRITIC below; 2 names no source and stays refused */,
+       CLOTHHIP_FIT_LABEL_ACTION_EXPERT = 4 /* DDPG FROM DEMONSTRATIONS below */ };
 int clothhip_fit_hold(clothhip_handle *h, const int32_t *src);
 int clothhip_fit_data_append_launch(clothhip_handle *h, const int32_t *rows, int64_t n);
 int clothhip_fit_data_append_launch_ex(clothhip_handle *h, const int32_t *rows, int64_t n, int32_t label_src, const float *weights);
@@ -920,6 +921,61 @@ int clothhip_policy_fit_dpg(clothhip_handle *h, const ClothFitParams *p, const C
 int clothhip_ddpg_polyak(clothhip_handle *h, double tau);
 int clothhip_ddpg_last_tables(clothhip_handle *h, int32_t B, float *x_out, float *qn_out, float *q_out);
 int clothhip_ddpg_fit(clothhip_handle *h, const ClothFitParams *p_policy, const ClothFitParams *p_q, const ClothDdpgParams *q, const int32_t *idx, int32_t n_steps, int32_t B, double *stats_out);
+
+/* DDPG FROM DEMONSTRATIONS (additive, ABI 7; the actor loss of Nair et al., "Overcoming Exploration in Reinforcement
+ * Learning with Demonstrations"): the deterministic policy gradient plus a behaviour-cloning term on the rows that carry an EXPERT
+ * ACTION, under the Q-FILTER only where the critic rates the expert's action above the policy's own. Any row the learner reached can
+ * carry one -- the expert armed beside the acting policy labels every state --, so these are DAgger's labels inside DDPG's loss. Every
+ * entry above keeps its kernels, its launches and its bytes.
+ * THE EXPERT COLUMN. A dataset row has one more column, float [4], whose default is four times the 32-bit pattern 0x7fc00000 (a quiet
+ * NaN): "no expert action". A row has an expert action iff component 0 is not a NaN, tested on the bits:
+ * (bits & 0x7fffffff) > 0x7f800000 means none; every writer stores four finite values or four fill patterns. Rows appended by any
+ * earlier entry or label source read back as the fill. clothhip_fit_data_set_expert(h, first, n, a[n][4]): a row of four finite values
+ * sets the expert action, a row of four NaNs (any NaNs) clears it and is stored as the fill; a row that mixes the two, or an infinity,
+ * is CLOTHHIP_EINVAL and the dataset stays what it was. clothhip_fit_data_get_expert reads the column. Both refuse what
+ * clothhip_fit_data_set_weights refuses.
+ * CLOTHHIP_FIT_LABEL_ACTION_EXPERT is a fourth label source of clothhip_fit_data_append_launch_ex: the label is
+ * (float)record.action[0..3] exactly as under LABEL_ACTION and the expert column gets (float)labels[label_row][0..3] of the last armed
+ * launch exactly as the label does under LABEL_EXPERT, in the one kernel launch. It refuses what either source refuses:
+ * CLOTHHIP_ESTATE for a launch that was not armed or no record table; CLOTHHIP_EINVAL, the dataset what it was, for a record with
+ * ran != 1 or a rounded value of either that is not finite.
+ * THE ACTOR'S STEP under ClothBcParams {q_coef, bc_coef, flags, reserved}, filter = flags & CLOTHHIP_BC_QFILTER. With the filter, first
+ * k_fit_concat's expert mode writes X_E[r] = [obs[idx[r]], min(max(a_E, -bound), bound)] -- a row without an expert action gets four
+ * 0.0f, by a select on the bit test -- and the live critic's forward over X_E gives qe[B] (computed and ignored on such a row), in the
+ * activation slot the critic's step uses for the target critic. Then the sequence of clothhip_policy_fit_dpg up to dA, and
+ * k_fit_dpg_bc in the place of the gate. Per minibatch row r: m_r = the row has an expert action; f_r = m_r and (no filter or
+ * qe_r > q_r), the comparison strict and in float32 (a tie does not pass). Per component k, every operation ONE float32 rounding:
+ *   g = the gate above (0 where held, else dA_rk);  a = fl(q_coef g)
+ *   where f_r and bc_coef != 0:  e = min(max(a_E_rk, -bound), bound);  d = fl(y_rk - e);  b = fl(fl(bc_coef d) / fl(2 B));  dz_rk = fl(a + b)
+ *   elsewhere dz_rk = a, and NO addition is made: the sign of a zero survives, and with q_coef = 1 (an exact product) dz is
+ *   clothhip_policy_fit_dpg's by bytes.
+ * No gradient flows through the filter or through e. The BC loss adds dd dd, dd = (double)y_rk - (double)e, over the rows with f_r
+ * (thread t of 256 takes rows t, t + 256, ..., k ascending, then the halving tree) and is reported over 4 B, NOT scaled by bc_coef: the
+ * normalisation of clothhip_policy_fit's loss, B and not the number of labelled rows -- the caller scales bc_coef.
+ *   stats = {-(sum q) / B, gated / (4 B), (sum |dA|) / (4 B), bc_loss, (sum m_r) / B, (sum f_r) / B}     (CLOTHHIP_DPG_BC_STATS; the first three are CLOTHHIP_DPG_STATS)
+ * With q_coef = 0, bc_coef = 1, no filter and every row labelled the gradient EQUALS clothhip_policy_fit_grad's on labels
+ * clamp(a_E) with weights 1 as numbers, not by bytes: 0 g may be -0, and x + (-0) differs from x only in the sign of a zero.
+ * clothhip_policy_fit_dpg_bc_grad: grad_out[n_params of the policy], stats_out[6], da_out[B][4], dz_out[B][4], q_out[B], qe_out[B],
+ * each may be NULL; qe_out without the filter is CLOTHHIP_EINVAL; nothing is updated. clothhip_policy_fit_dpg_bc: n_steps steps under
+ * p with the policy's optimizer state, stats_out[n_steps][6]. clothhip_ddpg_fit_bc: clothhip_ddpg_fit with this actor's step,
+ * stats_out[n_steps][9] (the critic's three, then these six); it equals, by bytes, clothhip_q_fit (1 step),
+ * clothhip_policy_fit_dpg_bc (1 step) and clothhip_ddpg_polyak one call at a time. Without the filter no extra concat or forward is
+ * launched. A minibatch with no labelled row is legal: a DPG step scaled by q_coef. None of the three changes the Q network (but
+ * clothhip_ddpg_fit_bc's critic step), the value network, the head or a dataset column.
+ * Refused before anything is touched: what the DDPG entries refuse, and CLOTHHIP_EINVAL for a coefficient that is NaN, infinite or
+ * negative, both coefficients 0, unknown flags, reserved != 0.
+ * After a call of these with the filter, clothhip_ddpg_last_tables' x_out is X_E (the expert rows have a table of their own) and its
+ * qn_out is refused as after an actor's step: that slot holds qe.
+ * OUT OF SCOPE: TD3, n-step targets, prioritised replay, BC for a population, a BC term in the critic. */
+typedef struct ClothBcParams { float q_coef, bc_coef; int32_t flags; int32_t reserved; } ClothBcParams;
+#define CLOTHHIP_BC_QFILTER 1
+#define CLOTHHIP_DPG_BC_STATS 6   /* CLOTHHIP_DPG_STATS, then bc_loss, labelled share, filter-pass share */
+#define CLOTHHIP_DDPG_BC_STATS 9  /* clothhip_ddpg_fit_bc: the critic's, then the BC actor's */
+int clothhip_fit_data_set_expert(clothhip_handle *h, int64_t first, int64_t n, const float *a);
+int clothhip_fit_data_get_expert(clothhip_handle *h, int64_t first, int64_t n, float *a);
+int clothhip_policy_fit_dpg_bc_grad(clothhip_handle *h, const ClothDdpgParams *q, const ClothBcParams *bc, const int32_t *idx, int32_t B, float *grad_out, double *stats_out, float *da_out, float *dz_out, float *q_out, float *qe_out);
+int clothhip_policy_fit_dpg_bc(clothhip_handle *h, const ClothFitParams *p, const ClothDdpgParams *q, const ClothBcParams *bc, const int32_t *idx, int32_t n_steps, int32_t B, double *stats_out);
+int clothhip_ddpg_fit_bc(clothhip_handle *h, const ClothFitParams *p_policy, const ClothFitParams *p_q, const ClothDdpgParams *q, const ClothBcParams *bc, const int32_t *idx, int32_t n_steps, int32_t B, double *stats_out);
 
 int clothhip_run_actions(clothhip_handle *h, const ClothEpisodeParams *ep, int32_t T, int32_t policy,
                          const double *actions, int32_t actions_on_device, const int32_t *policy_arg,

@@ -6,12 +6,18 @@ the policy up the critic's action gradient and the soft update of both targets, 
 dataset -- the replay buffer: no collection is thrown away. It prints, per iteration, the mean return of the episodes that completed,
 the rows in the buffer, and the first and last step's critic loss, mean Q, gated fraction and mean |dL/da|; with --out FILE it also
 appends the lines there. profiles/ddpg.txt holds a run. The tool claims nothing about learning curves: it says what came out.
+With --expert NAME the launches are armed: the expert labels every state the learner reaches and, with --beta, takes the
+action over on that share of the slots; the rows carry its action in the dataset's expert column, and --bc-coef / --q-coef /
+--no-q-filter / --demo-fraction shape the actor's loss of DDPG from demonstrations; a second line per iteration then reports the BC loss,
+the labelled share and the filter-pass share. Without these options the run is the plain one. profiles/ddpg_bc.txt holds both.
 With --bench it measures instead, on the four shapes of tools/fit_bench.py (25x25; hidden [64, 64] and [256, 256, 256]; B = 256 and
 4096): the device time of one clothhip_ddpg_fit step beside a clothhip_policy_fit step plus a clothhip_value_fit step of the same shapes
-on the same handle, alternated, and the step's launch count. With --one-shape it runs clothhip_ddpg_fit calls of that one shape
+on the same handle, alternated, and the step's launch count; and the BC actor's step (clothhip_policy_fit_dpg_bc, half of the rows
+labelled, bc_coef 1), filter on and off, beside the plain actor's step on that handle, with its launch count. With --one-shape it runs clothhip_ddpg_fit calls of that one shape
 and nothing else: under a kernel trace (rocprofv3 --kernel-trace --stats -- python3 tools/ddpg_demo.py --bench --one-shape ...) the
 per-kernel totals then are a DDPG step's, k_fit_concat's share among them (profiles/ddpg.txt).
     python3 tools/ddpg_demo.py [--envs 64] [--slots 12] [--iters 4] [--steps 100] [--batch 256] [--sigma 0.1] [--out FILE]
+    python3 tools/ddpg_demo.py --expert oracle_corner [--beta 0.5] [--bc-coef 1.0] [--q-coef 1.0] [--no-q-filter] [--demo-fraction 0.5]
     python3 tools/ddpg_demo.py --bench [--bench-steps 20] [--rounds 5] [--out FILE]
     python3 tools/ddpg_demo.py --bench --one-shape 256,256,256:4096 [--bench-steps 20] [--rounds 1]"""
 import argparse
@@ -64,16 +70,22 @@ def run(args):
         "exploration noise sigma %g made on the device; per iteration %d DDPG steps on minibatches of %d rows from the whole replay buffer, gamma %g, "
         "tau %g, act_bound %g, Adam lr %g (policy) and %g (critic)" % (E, hidden, T, args.sigma, args.steps, args.batch, args.gamma, args.tau, args.act_bound,
                                                                     args.lr, args.q_lr))
+    bc = args.expert is not None or args.bc_coef != 0.0 or args.q_coef != 1.0
+    if bc:
+        say("    from demonstrations: expert %s beside the policy, beta %g; actor loss q_coef %g (-mean Q) + bc_coef %g BC, Q-filter %s, demo_fraction %r"
+            % (args.expert, args.beta, args.q_coef, args.bc_coef, "off" if args.no_q_filter else "on", args.demo_fraction))
     for i in range(args.iters):
         env.seed([2000 + e for e in range(E)])                                # every iteration from the same start states
         env.reset()
         try:
-            col = actor_critic_collect(env, pol, n_actions=T, policy_noise=DeviceNoise(100 + i, sigma=args.sigma), slots_per_launch=T)
+            col = actor_critic_collect(env, pol, n_actions=T, policy_noise=DeviceNoise(100 + i, sigma=args.sigma), slots_per_launch=T, expert=args.expert,
+                                       beta=args.beta, seed=i)
         except ValueError as e:                                               # a network that ran away acts with values that are not finite
             say("iteration %d: the collection was refused (%s): the run ends here" % (i, e))
             break
         t0 = time.perf_counter()
-        fit = ddpg_fit(env, pol, qc, col, gamma=args.gamma, tau=args.tau, n_steps=args.steps, batch_size=args.batch, seed=i, act_bound=args.act_bound)
+        fit = ddpg_fit(env, pol, qc, col, gamma=args.gamma, tau=args.tau, n_steps=args.steps, batch_size=args.batch, seed=i, act_bound=args.act_bound,
+                       q_coef=args.q_coef, bc_coef=args.bc_coef, q_filter=not args.no_q_filter, demo_fraction=args.demo_fraction)
         dt = time.perf_counter() - t0
         st = fit["stats"]
         say("iteration %d: %4d rows + %d leaves collected (%.0f ms), %3d completed episodes, mean return %.4f; replay buffer %d rows, %d with a "
@@ -83,6 +95,9 @@ def run(args):
         say("    %d steps in %.0f ms (device %.1f ms)%s; critic loss %.5f -> %.5f, mean Q %.4f -> %.4f, mean y %.4f -> %.4f; actor -mean Q %.4f -> %.4f, "
             "gated %.3f -> %.3f, mean |dL/da| %.2e -> %.2e" % (len(st), dt * 1e3, env.batch.last_kernel_ms, ", targets synced" if fit["synced"] else "", st[0, 0], st[-1, 0],
                                                             st[0, 1], st[-1, 1], st[0, 2], st[-1, 2], st[0, 3], st[-1, 3], st[0, 4], st[-1, 4], st[0, 5], st[-1, 5]))
+        if st.shape[1] == 9:
+            say("    BC loss %.5f -> %.5f (mean over the steps %.5f), labelled share %.3f -> %.3f, filter-pass share %.3f -> %.3f (mean %.3f)"
+                % (st[0, 6], st[-1, 6], st[:, 6].mean(), st[0, 7], st[-1, 7], st[0, 8], st[-1, 8], st[:, 8].mean()))
     env.close()
 
 
@@ -94,6 +109,14 @@ def launches_per_step(pw, qw, B):
     critic = Lp + 1 + Lq + 1 + Lq + 1 + back(Lq) + 1          # target policy, concat, target Q, concat, Q, TD loss, backward, optimizer
     actor = Lp + 1 + Lq + 1 + Lq + 1 + back(Lp) + 1           # policy, concat, Q, the constant fill, the input-gradient chain, the gate, backward, optimizer
     return critic + actor + 2                                  # ... and the two soft updates
+
+
+def bc_launches_per_step(pw, qw, B, q_filter):
+    """Kernel launches of one clothhip_policy_fit_dpg_bc step: the plain actor's, k_fit_dpg_bc in the place of the gate, and under the
+    Q-filter one concat and one Q forward in front."""
+    Lp, Lq, split = len(pw) - 1, len(qw) - 1, 1 if B > 256 else 0
+    back = lambda L: L * (2 + split) + (L - 1)
+    return Lp + 1 + Lq + 1 + Lq + 1 + back(Lp) + 1 + ((1 + Lq) if q_filter else 0)
 
 
 def bench_section(args):
@@ -110,6 +133,9 @@ def bench_section(args):
     nxt[-1] = -1
     b.fit_set_transitions(r.normal(size=n).astype(np.float32), nxt)
     b.fit_set_returns(r.normal(size=n).astype(np.float32))
+    ex = r.uniform(-1, 1, size=(n, 4)).astype(np.float32)
+    ex[r.random_sample(n) < 0.5] = np.nan                                     # half of the rows carry an expert action
+    b.fit_set_expert(ex)
     say("ddpg bench: one 25x25 cloth, a dataset of %d uniform rows in episodes of 12; Adam; %d steps per call, %d calls of each kind ALTERNATED after one warm-up "
         "call each; device ms per step by HIP events around all steps of a call (median; min-max)" % (n, args.bench_steps, args.rounds))
     for hidden, B in shapes:
@@ -120,7 +146,8 @@ def bench_section(args):
         b.ddpg_sync_targets()
         table = r.randint(0, n, size=(args.bench_steps, B)).astype(np.int32)
         kinds = {"ddpg": lambda: b.ddpg_fit(table, 0.99, 0.005, 1.0), "policy": lambda: b.fit(table), "value": lambda: b.value_fit(table),
-                 "critic": lambda: b.q_fit(table, 0.99, 1.0), "actor": lambda: b.dpg_fit(table, 1.0)}
+                 "critic": lambda: b.q_fit(table, 0.99, 1.0), "actor": lambda: b.dpg_fit(table, 1.0),
+                 "bc_filter": lambda: b.dpg_bc_fit(table, 1.0, 1.0, 1.0, True), "bc_nofilter": lambda: b.dpg_bc_fit(table, 1.0, 1.0, 1.0, False)}
         if args.one_shape:                                                    # for a kernel trace: DDPG steps and nothing else
             for _ in range(args.rounds + 1):
                 kinds["ddpg"]()
@@ -140,6 +167,11 @@ def bench_section(args):
             "%.3f (%.3f-%.3f) = %.3f ms; ratio %.2f; %d launches per DDPG step" % (hidden, B, med["ddpg"], min(dev["ddpg"]), max(dev["ddpg"]), med["critic"], med["actor"],
                                                                                    med["policy"], min(dev["policy"]), max(dev["policy"]), med["value"], min(dev["value"]),
                                                                                    max(dev["value"]), base, med["ddpg"] / base, launches_per_step(pw, qw, B)))
+        say("    BC actor step, filter on %.3f ms (%.3f-%.3f), ratio to the plain actor step %.3f, %d launches; filter off %.3f ms (%.3f-%.3f), ratio %.3f, %d launches; "
+            "plain actor step %.3f ms (%.3f-%.3f), %d launches" % (med["bc_filter"], min(dev["bc_filter"]), max(dev["bc_filter"]), med["bc_filter"] / med["actor"],
+                                                                   bc_launches_per_step(pw, qw, B, True), med["bc_nofilter"], min(dev["bc_nofilter"]), max(dev["bc_nofilter"]),
+                                                                   med["bc_nofilter"] / med["actor"], bc_launches_per_step(pw, qw, B, False), med["actor"], min(dev["actor"]),
+                                                                   max(dev["actor"]), bc_launches_per_step(pw, qw, B, False)))
     b.close()
 
 
@@ -157,6 +189,12 @@ def main():
     ap.add_argument("--hidden", default="64,64")
     ap.add_argument("--lr", type=float, default=1e-4, help="the policy's Adam learning rate")
     ap.add_argument("--q-lr", type=float, default=1e-3, help="the critic's Adam learning rate")
+    ap.add_argument("--expert", default=None, help="arm this expert beside the policy (oracle_corner, highest_point): the rows carry its action")
+    ap.add_argument("--beta", type=float, default=0.0, help="with --expert: the share of the slots on which the expert takes the action over")
+    ap.add_argument("--bc-coef", type=float, default=0.0, help="the coefficient of the behaviour-cloning term of the actor's loss")
+    ap.add_argument("--q-coef", type=float, default=1.0, help="the coefficient of the policy-gradient term of the actor's loss")
+    ap.add_argument("--no-q-filter", action="store_true", help="clone on every labelled row, not only where the critic rates the expert's action higher")
+    ap.add_argument("--demo-fraction", type=float, default=None, help="that share of every minibatch is drawn from the rows with an expert action")
     ap.add_argument("--bench", action="store_true", help="time a DDPG step beside a policy_fit step plus a value_fit step")
     ap.add_argument("--bench-steps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
